@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the filter hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload door_pf|push_pf|door_ekf]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload door_pf|push_pf|door_ekf] [--full] [--dump-outputs DIR]
 
 A *step* is one filter time step over one batch: for the particle-filter workloads the
 per-trajectory encoders (CNNs, control / observation MLPs, modality weights), the fused
@@ -22,9 +22,20 @@ from one ``forward_loop`` call to the next -- so the timed steps are a filter th
 measurement heads calibrated (``calibrate_to_band``) to hold ESS/M inside SURVEY.md 8d's [0.05, 0.5]
 there (the line reports the engine's own ESS/M over the timed steps: ``ess_over_m``).
 
-``configs`` (one GPU, default on): BASELINE.json's other configurations and the blackout workloads
-(``tasks/_door.py:181-197``) as bounded legs of the same run -- each with its value,
-ms per step, its dominant kernel's roofline fraction and one parity number against the oracle.
+A plain run does only what the headline figure needs: set-up (incl. the head calibration), pre-roll, burn-in,
+W warm-up steps, the K timed steps, the outputs (``--dump-outputs``) and the line.  ``--full`` adds everything
+else the benchmark measures or checks, each still switchable off by its ``--no-*`` option: the pass opening the
+process and the pass in exact-f32 mode, the per-kernel timers and rooflines, the error study against fp64, the
+engine's ESS/M over the timed steps, the reference-sized regimes, the CPU-oracle baseline with its parity numbers,
+and ``configs`` (one GPU): BASELINE.json's other configurations and the blackout workloads (SURVEY.md 8d,
+``tasks/_door.py:181-197``) as bounded legs of the same run -- each with its value, ms per step, its dominant
+kernel's roofline fraction and one parity number against the oracle.
+
+``--dump-outputs DIR``: after the timed steps, what the timed path computed in its last step -- for a filter the
+posterior means ``forward_loop`` returned for that step (``posterior_mean.npy``, ``(N, d)``) and the per-trajectory
+squared errors of the timed steps (``per_trajectory_mse.npy``); for ``push_train`` the loss of the last optimiser
+step and the parameters it left -- as float32 / float64 ``.npy`` files, at most 64 MB in all.  Inputs, weights and
+noise are seeded: the same arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -149,6 +160,23 @@ def pmc_traffic_k4_ekf():
             if all(hits):
                 return sum(h[0]["hbm_bytes_corrected"] for h in hits), os.path.relpath(path, ROOT)
     return None, None
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """``--dump-outputs``: every array as ``path/<name>.npy`` (float64 stays float64, anything else becomes float32).  An
+    array larger than its share of the 64 MB is replaced by a fixed, seeded sample of its flattened elements (in order)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays)) - 4096  # room for the .npy headers
+    for name, a in arrays.items():
+        a = a.detach().cpu() if torch.is_tensor(a) else torch.as_tensor(a)
+        x = (a.double() if a.dtype == torch.float64 else a.float()).numpy()
+        if x.nbytes > share:
+            keep = np.random.default_rng(0).choice(x.size, share // x.itemsize, replace=False)
+            x = x.reshape(-1)[np.sort(keep)]
+        np.save(os.path.join(path, f"{name}.npy"), x)
 
 
 def build_filter(wl, device, seed=0):
@@ -537,11 +565,16 @@ def main_train(args, wl):
         distributed.all_reduce_gradients = real
         engine.set_training_backend(None)
         engine.set_image_encoder_precision(None)
-    # replicated weights must still be replicated: every rank's parameter checksum
-    chk = torch.stack([p.detach().double().sum() for p in f.parameters()]).sum().reshape(1, 1).float()
-    sums = distributed.all_gather_rows(chk)
+    # replicated weights must still be replicated: every rank's parameter checksum (--full)
+    sums = None
+    if args.full:
+        chk = torch.stack([p.detach().double().sum() for p in f.parameters()]).sum().reshape(1, 1).float()
+        sums = distributed.all_gather_rows(chk)
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": np.array([losses[-1]], dtype=np.float64),
+                                         "parameters": torch.cat([p.detach().reshape(-1) for p in f.parameters()])})
     ar_ms = [m[1].elapsed_time(m[2]) for m in marks]      # the collective alone (gloo: incl. its host round trip)
     ex_ms = [m[0].elapsed_time(m[3]) for m in marks]      # pack kernel + collective + scale kernel; no copy back
     out = {"metric": "training particle-steps/sec (batch x particles x subsequence steps, forward + backward + optimiser)",
@@ -557,7 +590,7 @@ def main_train(args, wl):
            "gradient_exchange_ms": (sum(ex_ms) / len(ex_ms)) if ex_ms else 0.0,
            "gradient_exchange": "torch.cat into one flat buffer, ONE in-place all-reduce, one scale kernel, p.grad re-pointed at views (no copy back)",
            "allreduce_elements": sum(p.numel() for p in f.parameters() if p.requires_grad),
-           "weights_identical_across_ranks": bool((sums == sums[0]).all()),
+           "weights_identical_across_ranks": None if sums is None else bool((sums == sums[0]).all()),
            "loss_first_last": [losses[0], losses[-1]],
            "peak_memory_GB": torch.cuda.max_memory_allocated() / 2 ** 30,
            "training_recursion": "fused" if engine.TRAIN_FUSED else "three-pass",
@@ -848,7 +881,15 @@ def main():
     ap.add_argument("--global-batch", type=int, default=None,
                     help="STRONG scaling: this many trajectories in total, sharded over the ranks "
                          "(BASELINE config 4: --workload door_ekf --global-batch 8192)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure (the --no-* options switch parts off); "
+                         "a plain run only sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the headline figure only
+        args.no_cpu_baseline = args.no_kernel_timers = args.no_precision_study = args.no_f32_mode = True
+        args.no_reference_sizes = args.no_configs = True
 
     # N > 1 without a launcher: become the launcher (before the HIP library or the GPU is touched)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -980,8 +1021,8 @@ def main():
     # Order of the GPU work (one GPU): the headline pass, the comparison pass in exact-f32 mode, the error study
     # against fp64, one second of idle, and the headline pass AGAIN -- each pass does its own pre-roll, burn-in and W
     # warm-up steps and times exactly K.  `value` is the LAST pass; the first is reported beside it as `pass_order`.
-    # With more than one rank the extras are skipped and the single pass is the value.
-    lean = world > 1
+    # With more than one rank, or without --full, the extras are skipped and the single pass is the value.
+    lean = world > 1 or not args.full
     first = None
     if not lean and (pf or not args.no_precision_study):
         first = timed_pass()[0]
@@ -990,6 +1031,7 @@ def main():
         engine.set_default_precision("f32")
         f32_pass = timed_pass()
         engine.set_default_precision(precision)
+        outputs_f32 = {"posterior_mean": f32_pass[3][-1].cpu(), "per_trajectory_mse": f32_pass[2].cpu()}
     # arithmetic error of each mode against fp64, at the benchmark's size (rank 0, no collective)
     study = None
     if rank == 0 and not args.no_precision_study and not lean:
@@ -1005,6 +1047,8 @@ def main():
         time.sleep(1.0)
     distributed.barrier()
     elapsed, timer, mse_all, pred_main = timed_pass()
+    # what a caller of the timed path receives for its last step (copied now: later runs of the filter reuse its memory)
+    outputs = {"posterior_mean": pred_main[-1].cpu(), "per_trajectory_mse": mse_all.cpu()}
 
     total_batch = args.global_batch if args.global_batch else B * world
     units_per_step = total_batch * M if pf else total_batch
@@ -1089,7 +1133,7 @@ def main():
     if "roofline" not in out:
         out["roofline"] = None
 
-    if pf:
+    if pf and args.full:
         # the ENGINE's own weights over the timed steps: the same run again, every step's log-likelihoods kept
         # (bit-identical: same kernels, same inputs), on the first 64 trajectories' worth of memory at a time
         nb = B if 4.0 * B * M * T_all <= 3e9 else min(B, 64)  # the whole batch where its log-likelihood record fits 3 GB
@@ -1137,6 +1181,7 @@ def main():
             out["dtype"] = "f32"
             out["roofline"] = out["f32_mode"].get("roofline")
             value = out["value"]
+            outputs = outputs_f32
         elif precision == "f16x3" and ok:
             out["dtype"] = ("f32-equivalent via f16x3: fp32 operands split into two round-to-nearest f16 halves "
                             "(x = hi + lo to 2^-22), 3 f16 MFMA products per product, f32 accumulate; error vs fp64 "
@@ -1198,6 +1243,8 @@ def main():
             if leg.get("roofline"):
                 summary[short + "_frac"] = leg["roofline"]["frac"]
     out["summary"] = {k: (float(f"{v:.6g}") if isinstance(v, float) else v) for k, v in summary.items()}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outputs)
     print(json.dumps(out), flush=True)
 
 

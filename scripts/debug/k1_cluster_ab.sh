@@ -1,5 +1,5 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
-LEAN="--no-cpu-baseline --no-precision-study --no-reference-sizes --no-configs --no-f32-mode"
+LEAN="--full --no-cpu-baseline --no-precision-study --no-reference-sizes --no-configs --no-f32-mode"
 for rep in 1 2; do
 for c in 1 0; do  # 1: cluster, 0: one workgroup per trajectory (the default)
   echo "# MMF_K1_CLUSTER=$c: bench.py --workload door_pf --batch 32 --steps 64"

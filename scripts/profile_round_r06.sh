@@ -19,7 +19,7 @@ $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fno-slp-vectorize -Wno-unused-value
 $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -o $R/scripts/ubench/mfma_shape $R/scripts/ubench/mfma_shape.hip >> $OUT/ubench_build.log 2>&1
 $HIPCC --offload-arch=gfx950 -O3 -Wno-unused-value -o $R/scripts/ubench/handoff_latency $R/scripts/ubench/handoff_latency.hip >> $OUT/ubench_build.log 2>&1
 cd /tmp && export TMPDIR=/tmp
-LEAN="--no-cpu-baseline --no-precision-study --no-reference-sizes --no-configs"
+LEAN="--full --no-cpu-baseline --no-precision-study --no-reference-sizes --no-configs"
 rocprofv3 --kernel-trace --stats --output-format csv -d $P/stats -- python3 $R/bench.py --steps 32 --warmup 4 $LEAN --no-f32-mode > $OUT/bench_under_rocprof.json 2> $P/stats.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $P/stats_f32 -- python3 $R/bench.py --steps 32 --warmup 4 $LEAN --precision f32 > $OUT/bench_under_rocprof_f32.json 2> $P/stats_f32.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $P/stats_ekf -- python3 $R/bench.py --workload door_ekf --steps 32 --warmup 4 $LEAN > $OUT/bench_under_rocprof_ekf.json 2> $P/stats_ekf.err
@@ -75,7 +75,7 @@ bash scripts/pmc_k4_r04.sh final > /dev/null 2>&1
 cp gpurun_out/pmc_k4_r04/final.json $OUT/pmc_k4_sq_counters.json
 bash scripts/debug/k4_ablate.sh > $OUT/k4_ablate_final.txt 2>&1
 ./scripts/ubench/mfma_shape > $OUT/ubench_mfma_shape.txt 2>&1
-python scripts/debug/find_copies.py --steps 20 --warmup 5 --no-cpu-baseline --no-configs --no-reference-sizes > /dev/null 2> $OUT/find_copies.txt
+python scripts/debug/find_copies.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-configs --no-reference-sizes > /dev/null 2> $OUT/find_copies.txt
 bash scripts/debug/k1_cluster_ab.sh > $OUT/k1_cluster_ab_final.txt 2>&1
 { ./scripts/ubench/k4_wg_spread 4096 2 0; ./scripts/ubench/k4_wg_spread 4096 3 0; ./scripts/ubench/k4_wg_spread 1024 2 0 b; } > $OUT/ubench_k4_wg_spread.txt 2>&1
 ./scripts/ubench/handoff_latency > $OUT/ubench_handoff_latency.txt 2>&1
@@ -83,11 +83,11 @@ bash scripts/debug/k1_cluster_ab.sh > $OUT/k1_cluster_ab_final.txt 2>&1
   echo "# MMF_K4_PRECISION=f16x3 (image-encoder training forward = the resident K4 kernel)"; MMF_K4_PRECISION=f16x3 python scripts/bench_reference_sizes.py --only train --backends hip --no-cpu 2>&1 | grep "^{";
   echo "# default again"; python scripts/bench_reference_sizes.py --only train --backends hip --no-cpu 2>&1 | grep "^{"; } > $OUT/bench_train_refsize_ab.txt
 # plain bench lines (un-profiled)
-python bench.py > $OUT/bench_door_pf_n1.json 2> $OUT/bench.err
-python bench.py --steps 20 --warmup 5 > $OUT/bench_driver_flags_door_pf.json 2>> $OUT/bench.err
+python bench.py --full > $OUT/bench_door_pf_n1.json 2> $OUT/bench.err
+python bench.py --steps 20 --warmup 5 --full > $OUT/bench_driver_flags_door_pf.json 2>> $OUT/bench.err
 python bench.py --noise philox $LEAN > $OUT/bench_door_pf_philox.json 2>> $OUT/bench.err
-python bench.py --workload push_pf --no-reference-sizes --no-configs > $OUT/bench_push_pf_n1.json 2>> $OUT/bench.err
-python bench.py --workload door_ekf --no-configs > $OUT/bench_door_ekf_n1.json 2>> $OUT/bench.err
+python bench.py --workload push_pf --full --no-reference-sizes --no-configs > $OUT/bench_push_pf_n1.json 2>> $OUT/bench.err
+python bench.py --workload door_ekf --full --no-configs > $OUT/bench_door_ekf_n1.json 2>> $OUT/bench.err
 python bench.py --workload door_ekf --steps 20 --warmup 5 $LEAN > $OUT/bench_driver_flags_door_ekf.json 2>> $OUT/bench.err
 python bench.py --workload door_pf_blackout $LEAN --no-f32-mode > $OUT/bench_door_pf_blackout.json 2>> $OUT/bench.err
 python bench.py --workload door_ekf_blackout $LEAN > $OUT/bench_door_ekf_blackout.json 2>> $OUT/bench.err
@@ -95,9 +95,9 @@ python bench.py --workload door_pf --batch 32 --steps 64 $LEAN --no-f32-mode > $
 python bench.py --workload door_pf --batch 1024 --steps 32 $LEAN --no-f32-mode > $OUT/bench_door_pf_n1024_m4096.json 2>> $OUT/bench.err
 python bench.py --workload door_ekf --global-batch 8192 --steps 32 --warmup 4 $LEAN > $OUT/bench_c4_door_ekf_n8192_one_gpu.json 2>> $OUT/bench.err
 python bench.py --workload door_pf --steps 800 $LEAN --no-f32-mode > $OUT/bench_door_pf_800_steps.json 2>> $OUT/bench.err
-MMF_DIST_BACKEND=gloo python bench.py --gpus 2 --steps 32 --warmup 8 2>> $OUT/bench.err | grep "^{" > $OUT/bench_gpus2_gloo_one_gpu.json
-python bench.py --workload push_train --steps 20 --warmup 5 2>> $OUT/bench.err | grep "^{" > $OUT/bench_push_train_n1.json
-MMF_DIST_BACKEND=gloo python bench.py --workload push_train --gpus 2 --steps 4 --warmup 1 --batch 16 2>> $OUT/bench.err | grep "^{" > $OUT/bench_push_train_gpus2_gloo_one_gpu.json
+MMF_DIST_BACKEND=gloo python bench.py --gpus 2 --steps 32 --warmup 8 --full 2>> $OUT/bench.err | grep "^{" > $OUT/bench_gpus2_gloo_one_gpu.json
+python bench.py --workload push_train --steps 20 --warmup 5 --full 2>> $OUT/bench.err | grep "^{" > $OUT/bench_push_train_n1.json
+MMF_DIST_BACKEND=gloo python bench.py --workload push_train --gpus 2 --steps 4 --warmup 1 --batch 16 --full 2>> $OUT/bench.err | grep "^{" > $OUT/bench_push_train_gpus2_gloo_one_gpu.json
 python scripts/debug/rccl_probe.py 2>&1 | grep -E "^rank|^world|Duplicate GPU" | sort -u > $OUT/bench_rccl_probe.txt
 python scripts/bench_k4.py > $OUT/bench_k4.txt 2>> $OUT/bench.err
 python scripts/bench_k1.py > $OUT/bench_k1.txt 2>> $OUT/bench.err

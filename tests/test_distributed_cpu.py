@@ -192,6 +192,24 @@ def test_bench_launcher_propagates_a_failing_rank():
     assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
 
 
+def test_bench_dump_outputs_dtypes_and_size_bound(tmp_path, monkeypatch):
+    """``bench.py --dump-outputs``: one ``.npy`` per array, float64 kept, anything else float32; an array past its share of
+    the bound becomes a seeded sample of its elements -- the same one in every run."""
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 3 * (16 << 10))  # a share of 16 KB (less the header room) per array
+    big = torch.arange(1 << 14, dtype=torch.float32)  # 64 KB
+    arrays = {"small": torch.ones(3, 2, dtype=torch.float16), "loss": np.array([0.25]), "big": big}
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays)
+    small, loss = np.load(tmp_path / "a" / "small.npy"), np.load(tmp_path / "a" / "loss.npy")
+    assert small.dtype == np.float32 and small.shape == (3, 2) and loss.dtype == np.float64 and loss[0] == 0.25
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float32 and 0 < a.nbytes <= (16 << 10) - 4096
+    assert np.array_equal(a, b) and np.all(np.diff(a) > 0) and np.all(np.isin(a, big.numpy()))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= bench.DUMP_LIMIT_BYTES
+
+
 @pytest.mark.timeout(600)
 def test_bench_eight_rank_preflight_strong_scaling_shards():
     """The command the driver will run on an 8-GPU node for BASELINE config 4, rehearsed with 8 gloo ranks and no GPU
