@@ -10,6 +10,7 @@ import torch.nn as nn
 
 from . import _abi
 from .layers import ResLinear
+from .utils import cached
 
 
 # MAC per row of each per-particle network: enc 64*(d) [+bias via the MFMA],
@@ -357,7 +358,7 @@ class PackedParticleNet:
         self._enc_in, self._enc_res = enc_in, enc_res
         self._res = list(res_blocks)
         self._head = head
-        self._blobs = {}       # precision code -> (stamp, blob)
+        self._blobs = {}       # ("fwd" | "T", precision code) -> (stamp, blob)
         self.precision = None  # None -> engine.DEFAULT_PRECISION at call time
 
     def precision_code(self) -> int:
@@ -373,12 +374,11 @@ class PackedParticleNet:
         return ts
 
     def blob(self, precision: int = None) -> torch.Tensor:
-        src = self._sources()
         prec = self.precision_code() if precision is None else precision
-        stamp = tuple((t.data_ptr(), t._version, str(t.device)) for t in src)
-        cached = self._blobs.get(prec)
-        if cached is not None and cached[0] == stamp:
-            return cached[1]
+        src = self._sources()
+        return cached(self._blobs, ("fwd", prec), src, lambda: self._pack(src, prec))
+
+    def _pack(self, src: List[torch.Tensor], prec: int) -> torch.Tensor:
         dev = src[0].device
         require_device(src[0], "PackedParticleNet")
         keep = [t.detach().to(torch.float32).contiguous() for t in src]
@@ -396,43 +396,38 @@ class PackedParticleNet:
         d.w_head, d.b_head = P(keep[-2]), P(keep[-1])
         blob = torch.empty(_abi.particle_net_floats(self.n_res), dtype=torch.float32, device=dev)
         _abi.pack_particle_net(d, blob, prec)
-        self._blobs[prec] = (stamp, blob)
         return blob
 
+    def transposed_blob(self, precision: int = _abi.PREC_F32) -> torch.Tensor:
+        """Blob of the TRANSPOSED 64x64 layers (K6 backward data path: ``dx = W^T dz`` is a forward
+        layer with ``W^T``) in the given arithmetic's fragment order; cached like the forward blobs."""
+        src = self._sources()
+        return cached(self._blobs, ("T", precision), src, lambda: self._pack_transposed(src, precision))
 
-def _transposed_blob(net: PackedParticleNet, precision: int = _abi.PREC_F32) -> torch.Tensor:
-    """Blob of the TRANSPOSED 64x64 layers (K6 backward data path: ``dx = W^T dz`` is a forward
-    layer with ``W^T``) in the given arithmetic's fragment order; cached like the forward blobs."""
-    src = net._sources()
-    stamp = tuple((t.data_ptr(), t._version, str(t.device)) for t in src)
-    key = "transposed" if precision == _abi.PREC_F32 else f"transposed_{precision}"
-    cached = net._blobs.get(key)
-    if cached is not None and cached[0] == stamp:
-        return cached[1]
-    dev = src[0].device
-    f32 = lambda t: t.detach().to(torch.float32)
-    T = lambda t: f32(t).t().contiguous()
-    zeros = torch.zeros(_abi.MMF_UNITS, dtype=torch.float32, device=dev)
-    off = net.join_state_off
-    keep = [f32(src[0]).contiguous(), f32(src[1]).contiguous(), T(src[2]), T(src[4]),
-            f32(src[6])[:, off:off + _abi.MMF_UNITS].t().contiguous()]
-    for i in range(net.n_res):
-        keep += [T(src[7 + 4 * i]), T(src[9 + 4 * i])]
-    keep += [f32(src[-2]).contiguous(), f32(src[-1]).contiguous(), zeros]
-    P = lambda t: ctypes.c_void_p(t.data_ptr())
-    d = _abi.MmfParticleNetDesc()
-    d.d_in, d.n_res, d.relu_after_join, d.n_out = net.d_in, net.n_res, int(net.relu_after_join), net.n_out
-    d.join_in, d.join_state_off = _abi.MMF_UNITS, 0
-    d.w_in, d.b_in = P(keep[0]), P(keep[1])
-    d.w_enc[0], d.b_enc[0], d.w_enc[1], d.b_enc[1] = P(keep[2]), P(zeros), P(keep[3]), P(zeros)
-    d.w_join = P(keep[4])
-    for i in range(2 * net.n_res):
-        d.w_res[i], d.b_res[i] = P(keep[5 + i]), P(zeros)
-    d.w_head, d.b_head = P(keep[-3]), P(keep[-2])
-    blob = torch.empty(_abi.particle_net_floats(net.n_res), dtype=torch.float32, device=dev)
-    _abi.pack_particle_net(d, blob, precision)
-    net._blobs[key] = (stamp, blob)
-    return blob
+    def _pack_transposed(self, src: List[torch.Tensor], precision: int) -> torch.Tensor:
+        dev = src[0].device
+        f32 = lambda t: t.detach().to(torch.float32)
+        T = lambda t: f32(t).t().contiguous()
+        zeros = torch.zeros(_abi.MMF_UNITS, dtype=torch.float32, device=dev)
+        off = self.join_state_off
+        keep = [f32(src[0]).contiguous(), f32(src[1]).contiguous(), T(src[2]), T(src[4]),
+                f32(src[6])[:, off:off + _abi.MMF_UNITS].t().contiguous()]
+        for i in range(self.n_res):
+            keep += [T(src[7 + 4 * i]), T(src[9 + 4 * i])]
+        keep += [f32(src[-2]).contiguous(), f32(src[-1]).contiguous(), zeros]
+        P = lambda t: ctypes.c_void_p(t.data_ptr())
+        d = _abi.MmfParticleNetDesc()
+        d.d_in, d.n_res, d.relu_after_join, d.n_out = self.d_in, self.n_res, int(self.relu_after_join), self.n_out
+        d.join_in, d.join_state_off = _abi.MMF_UNITS, 0
+        d.w_in, d.b_in = P(keep[0]), P(keep[1])
+        d.w_enc[0], d.b_enc[0], d.w_enc[1], d.b_enc[1] = P(keep[2]), P(zeros), P(keep[3]), P(zeros)
+        d.w_join = P(keep[4])
+        for i in range(2 * self.n_res):
+            d.w_res[i], d.b_res[i] = P(keep[5 + i]), P(zeros)
+        d.w_head, d.b_head = P(keep[-3]), P(keep[-2])
+        blob = torch.empty(_abi.particle_net_floats(self.n_res), dtype=torch.float32, device=dev)
+        _abi.pack_particle_net(d, blob, precision)
+        return blob
 
 
 class ParticleNetFunction(torch.autograd.Function):
@@ -471,7 +466,7 @@ class ParticleNetFunction(torch.autograd.Function):
         head_w = params[-2].to(torch.float32).contiguous()
         dz = torch.empty_like(stash)
         d_states = torch.empty_like(st)
-        _abi.particle_net_train_backward(_transposed_blob(net), head_w, net.n_res, kind, mask, d_out, dz,
+        _abi.particle_net_train_backward(net.transposed_blob(), head_w, net.n_res, kind, mask, d_out, dz,
                                          d_states, R, d)
         grads = [None] * len(params)
         U = _abi.MMF_UNITS
@@ -651,7 +646,7 @@ class PfTrainLoopFunction(torch.autograd.Function):
                      p_dout=E(T, N * SL, 4), p_traj=E(T, N * SL, U))
             bufs.append(b)
             head_ws.append(params[offs[i + 1] - 2].to(torch.float32).contiguous())
-            tblobs.append(None if fused else _transposed_blob(net, _abi.PREC_F32))
+            tblobs.append(None if fused else net.transposed_blob(_abi.PREC_F32))
             if fused:
                 tn.packed_dual = P(net.blob(_abi.PREC_F16X3_DUAL))
             tn.packed_f32 = P(ctx.blobs[i])
@@ -878,15 +873,15 @@ def _is_default_image_encoder(seq) -> bool:
 
 
 class PackedImageEncoder:
-    """Fragment-ordered device copy of one default ``observation_image_layers`` stack
-    (``layers.image_encoder``), rebuilt lazily when a source parameter changes."""
+    """Fragment-ordered device copies of one default ``observation_image_layers`` stack
+    (``layers.image_encoder``): the inference / training-forward blob and the convolutions' backward
+    blob, each rebuilt lazily when one of its source parameters changes."""
 
     def __init__(self, seq: nn.Sequential):
         self.variant = _image_encoder_variant(seq)
         assert self.variant is not None
         self.seq = seq
-        self._blob = None
-        self._stamp = None
+        self._blobs = {}   # "fwd" | "bwd" -> (stamp, blob)
 
     def _sources(self):
         q = self.seq
@@ -897,9 +892,9 @@ class PackedImageEncoder:
 
     def blob(self) -> torch.Tensor:
         src = self._sources()
-        stamp = tuple((t.data_ptr(), t._version, str(t.device)) for t in src)
-        if self._blob is not None and stamp == self._stamp:
-            return self._blob
+        return cached(self._blobs, "fwd", src, lambda: self._pack(src))
+
+    def _pack(self, src) -> torch.Tensor:
         require_device(src[0], "PackedImageEncoder")
         keep = [t.detach().to(torch.float32).contiguous() for t in src]
         P = lambda t: ctypes.c_void_p(t.data_ptr())
@@ -911,8 +906,33 @@ class PackedImageEncoder:
         d.variant = self.variant
         blob = torch.empty(_abi.image_encoder_floats(), dtype=torch.float32, device=src[0].device)
         _abi.pack_image_encoder(d, blob)
-        self._blob, self._stamp = blob, stamp
         return blob
+
+    def backward_blob(self) -> torch.Tensor:
+        """Transposed + flipped convolution weights of the backward data path (``mmf_pack_image_convs_backward``
+        reads ``conv_w[1..4]``; the 5x5 stem has no data gradient to form)."""
+        src = self._sources()[1:5]
+        return cached(self._blobs, "bwd", src, lambda: self._pack_backward(src))
+
+    def _pack_backward(self, src) -> torch.Tensor:
+        keep = [t.detach().to(torch.float32).contiguous() for t in src]
+        d = _abi.MmfImageEncoderDesc()
+        for i, t in enumerate(keep):
+            d.conv_w[1 + i] = ctypes.c_void_p(t.data_ptr())
+        d.variant = _abi.ENCODER_DEFAULT
+        blob = torch.empty(_abi.image_convs_backward_floats(), dtype=torch.float32, device=src[0].device)
+        _abi.pack_image_convs_backward(d, blob)
+        return blob
+
+
+def packed_image_encoder(seq: nn.Sequential) -> PackedImageEncoder:
+    """The ``PackedImageEncoder`` of ``seq``, created on first use and kept on the module (outside its
+    parameters and state dict)."""
+    packed = getattr(seq, "_mmf_packed", None)
+    if packed is None:
+        packed = PackedImageEncoder(seq)
+        object.__setattr__(seq, "_mmf_packed", packed)
+    return packed
 
 
 class ImageConvsFunction(torch.autograd.Function):
@@ -928,9 +948,7 @@ class ImageConvsFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, seq, images, *params):
         require_device(images, "ImageConvsFunction")
-        if not hasattr(seq, "_mmf_packed"):
-            object.__setattr__(seq, "_mmf_packed", PackedImageEncoder(seq))
-        blob = seq._mmf_packed.blob()
+        blob = packed_image_encoder(seq).blob()
         img = images.detach().to(torch.float32).contiguous()
         N = img.shape[0]
         mk = lambda c: torch.empty((N, c, 32, 32), dtype=torch.float32, device=img.device)
@@ -947,28 +965,16 @@ class ImageConvsFunction(torch.autograd.Function):
         seq = ctx.seq
         img, a1, h, a2, a3 = ctx.saved_tensors
         N = img.shape[0]
-        src = seq._mmf_packed._sources()
-        stamp = tuple((t.data_ptr(), t._version) for t in src[1:5])
-        cached = getattr(seq, "_mmf_packed_bwd", None)
-        if cached is None or cached[0] != stamp:
-            keep = [t.detach().to(torch.float32).contiguous() for t in src[:5]]
-            d = _abi.MmfImageEncoderDesc()
-            for i in range(5):
-                d.conv_w[i] = ctypes.c_void_p(keep[i].data_ptr())
-            d.variant = _abi.ENCODER_DEFAULT
-            blob_b = torch.empty(_abi.image_convs_backward_floats(), dtype=torch.float32, device=img.device)
-            _abi.pack_image_convs_backward(d, blob_b)
-            cached = (stamp, blob_b)
-            object.__setattr__(seq, "_mmf_packed_bwd", cached)
+        blob_b = packed_image_encoder(seq).backward_blob()
         g_a4 = g_a4.to(torch.float32).contiguous()
         g1, gh, g2 = torch.empty_like(a1), torch.empty_like(a1), torch.empty_like(a1)
         g3 = torch.empty_like(a3)
         gmax = None   # f16x3 backward: max |g3|, |g2|, |gh|, |g_a4| as device scalars (the operand splits' scales)
         if training_image_precision_code() != _abi.PREC_F32:   # round 6: the 32-output-channel layers on the f16 matrix pipe
             gmax = torch.empty(4, dtype=torch.float32, device=img.device)
-            _abi.image_convs_train_backward_h(cached[1], a1, h, a2, a3, g_a4, g1, gh, g2, g3, gmax)
+            _abi.image_convs_train_backward_h(blob_b, a1, h, a2, a3, g_a4, g1, gh, g2, g3, gmax)
         else:
-            _abi.image_convs_train_backward(cached[1], a1, h, a2, a3, g_a4, g1, gh, g2, g3)
+            _abi.image_convs_train_backward(blob_b, a1, h, a2, a3, g_a4, g1, gh, g2, g3)
         blocks = max(1, min(2 * N, 256))  # a workgroup walks half-images; one partial per workgroup
         partial = torch.empty((blocks, 9, 32, 32), dtype=torch.float32, device=img.device)
         partial_b = torch.empty((blocks, 32), dtype=torch.float32, device=img.device)
@@ -1033,7 +1039,7 @@ def image_features_autograd(seq, images: torch.Tensor, pre_activation: bool = Fa
     (``ImageConvsFunction``, ``Fc64Function``); otherwise the torch module as it stands.  ``pre_activation``: stop behind
     the linear layer (the caller's K7 program applies the ReLU and the ResLinear; default stacks on the device only)."""
     if use_hip_backward() and images.is_cuda and _image_encoder_variant(seq) == _abi.ENCODER_DEFAULT:
-        params = PackedImageEncoder(seq)._sources()[:10] if not hasattr(seq, "_mmf_packed") else seq._mmf_packed._sources()[:10]
+        params = packed_image_encoder(seq)._sources()[:10]
         a4 = ImageConvsFunction.apply(seq, images, *params)
         x = a4.flatten(1)
         if TRAIN_TRAJ_PROGRAMS and seq[7].weight.dtype == torch.float32 and seq[7].out_features == 64:
@@ -1102,12 +1108,7 @@ def encode_images(encoders, images: torch.Tensor):
         same = [i for i, vi in enumerate(variants) if vi == v]
         groups += [(v, same[lo:lo + _MAX_NETS]) for lo in range(0, len(same), _MAX_NETS)]
     for variant, grp in groups:
-        packs = []
-        for i in grp:
-            e = encoders[i]
-            if not hasattr(e, "_mmf_packed"):
-                object.__setattr__(e, "_mmf_packed", PackedImageEncoder(e))
-            packs.append(e._mmf_packed.blob())
+        packs = [packed_image_encoder(encoders[i]).blob() for i in grp]
         pieces = []  # per chunk: (nets, n, 64), written by the launch sequence itself
         # bounded workspace: at most _IMAGE_CHUNK images per launch sequence, in EQUAL chunks (round 5: 5,120 images run
         # as 2 x 2,560, not 4,096 + 1,024 -- the short chunk's persistent grids spent a third of their launch filling

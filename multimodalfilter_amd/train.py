@@ -91,8 +91,12 @@ class GraphedFilterStep:
     copies of the batch and replays it; later calls copy the batch in and replay.  Randomness: the explicit ``NoiseSource``
     generators are registered with the graph, so every replay draws fresh numbers, in the order the eager step would.  The
     checks that need a host read (range flag, "covariance not positive definite") accumulate on the device during a replay and are
-    read once after it.  Requirements: a capturable optimiser (``torch.optim.SGD``, or Adam with ``capturable=True``), no
-    host-dependent control flow in user models, batches of one shape (a new shape raises)."""
+    read once after it.  Packed weights: a replay writes the parameters without moving their ``Tensor._version``, which every
+    packed-weight cache keys on (``utils.cached``), so the step moves it itself -- before the capture (the pack kernels are
+    captured even when the blobs are fresh, or when a fused optimiser, which never moves it, ran the eager steps) and after
+    every replay (the next eager or eval forward re-packs the weights the replay wrote).  Requirements: a capturable
+    optimiser (``torch.optim.SGD``, or Adam with ``capturable=True``), no host-dependent control flow in user models,
+    batches of one shape (a new shape raises)."""
 
     def __init__(self, filter_model, optimizer: torch.optim.Optimizer, *, initial_covariance: torch.Tensor,
                  noise: Optional[NoiseSource] = None, measurement_initialize: bool = False, all_reduce: bool = False,
@@ -105,6 +109,9 @@ class GraphedFilterStep:
         self.stream = None   # eager steps and the capture share ONE side stream: autograd remembers the stream a parameter's
                              # gradient accumulator was created on, and a capture must not reach back to the default stream
 
+    def _params(self):
+        return [p for group in self.optimizer.param_groups for p in group["params"]]
+
     def _capture(self, batch):
         dev = batch["states"].device
         self.static = {k: v.detach().clone() for k, v in batch.items()}
@@ -114,6 +121,7 @@ class GraphedFilterStep:
         for src in sources.values():
             self.graph.register_generator_state(src._gen(dev))
         self.optimizer.zero_grad(set_to_none=True)
+        torch.autograd.graph.increment_version(self._params())
         engine.clear_range(dev)
         engine.CAPTURING = True
         try:
@@ -143,6 +151,7 @@ class GraphedFilterStep:
                 assert batch[k].shape == v.shape, f"GraphedFilterStep was captured for {k} of shape {tuple(v.shape)}, got {tuple(batch[k].shape)}"
                 v.copy_(batch[k])
         self.graph.replay()
+        torch.autograd.graph.increment_version(self._params())
         engine.check_range(batch["states"].device)   # the replay's deferred checks: one 4-byte read
         return float(self.loss)
 

@@ -20,6 +20,7 @@ import torch.nn as nn
 
 from . import _abi
 from .layers import ResLinear
+from .utils import cached
 
 Src = Tuple[int, int, int]  # (slot, first feature, width)
 
@@ -73,7 +74,7 @@ class TrajProgram:
         self._free = list(range(_abi.TRAJ_SLOTS))
         self._prog_dev = None
         self._blob = None
-        self._stamp = None
+        self._packed = {}          # "blob" -> (stamp of the parameters, self._blob)
         self._train = None         # reverse-mode plan (built on first use)
         self._pack = None          # (parameter addresses, device table of MmfTrajPackDesc, count)
         self._lin_info = {}        # LINEAR instruction index -> (weight, first column, source widths, bias | None)
@@ -159,9 +160,9 @@ class TrajProgram:
         """Weight blob of the current parameter values: ONE pack launch when a parameter has changed (their addresses
         do not: optimisers update in place, so the descriptor table is built once)."""
         params = [p for _, p, _, _ in self._blob_parts]
-        stamp = tuple((p.data_ptr(), p._version, str(p.device)) for p in params)
-        if self._blob is not None and stamp == self._stamp:
-            return
+        cached(self._packed, "blob", params, lambda: self._pack_blob(params, device))
+
+    def _pack_blob(self, params, device) -> torch.Tensor:
         device = torch.device(device)
         # parameters that do not live on the device as contiguous fp32 (a host-resident user model) are staged: the table
         # then follows the copies' addresses and is rebuilt with them
@@ -188,9 +189,9 @@ class TrajProgram:
             self._pack = (addr, _pack_table(descs, device), len(descs))
             self._blob = torch.empty(max(off, 4), dtype=torch.float32, device=device)
         _abi.traj_pack(self._pack[1], self._pack[2], self._blob)
-        self._stamp = stamp
         if self._prog_dev is None or self._prog_dev.device != self._blob.device:
             self._prog_dev = _to_device(self._instrs, self._blob.device)
+        return self._blob
 
     def _footprint(self):
         return _footprint_of(self._instrs)

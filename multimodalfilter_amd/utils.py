@@ -27,6 +27,25 @@ def tree_leading_shape(x: Any):
     return tuple(x.shape)
 
 
+def stamp(sources) -> tuple:
+    """What a derived copy of ``sources`` was built from: each tensor's address, version counter and device.  An
+    in-place update (an optimiser step, or ``torch.autograd.graph.increment_version`` after a graph replay wrote
+    the tensor), a replaced tensor (``load_state_dict``) or a move changes it."""
+    return tuple((t.data_ptr(), t._version, str(t.device)) for t in sources)
+
+
+def cached(cache: dict, key, sources, build: Callable):
+    """``cache[key]``'s value while ``sources`` still carry the stamp it was built from; otherwise ``build()``,
+    stored under ``key`` with the current stamp.  The one staleness rule of every packed-weight copy."""
+    s = stamp(sources)
+    hit = cache.get(key)
+    if hit is not None and hit[0] == s:
+        return hit[1]
+    value = build()
+    cache[key] = (s, value)
+    return value
+
+
 def rank_seed(base_seed: int = 0) -> int:
     """``base_seed`` offset by this process's data-parallel rank (``torch.distributed`` when
     initialised, else torchrun's ``RANK``): ranks own different trajectories and must not

@@ -1171,3 +1171,70 @@ def test_graphed_training_step_replays_the_eager_step(optim):
     assert graphed == eager
     for (n, p), q in zip(f.named_parameters(), g.parameters()):
         assert torch.equal(p.detach(), q.detach()), n
+
+
+def test_graphed_training_then_eval_sees_current_weights():
+    """Train / validate with ``train.GraphedFilterStep``: a replay writes the parameters on the device, and the packed
+    weight blobs must follow it.  Eval forwards interleaved with the training steps -- one right before the capture (fresh
+    blobs at capture time: the pack kernels must still be captured) and after replays (the blobs must be re-packed from
+    the weights the replays wrote) -- equal those of an eagerly trained twin bit for bit, and so do the losses and the
+    final weights."""
+    import copy
+
+    import multimodalfilter_amd as mmf
+    from multimodalfilter_amd import engine, synthetic, train
+
+    dev = torch.device("cuda:0")
+    N, M, L, d = 8, 30, 6, 3
+    batches = [{k: v.to(dev) for k, v in synthetic.make_trajectories(state_dim=d, T=L - 1, N=N, seed=3 + i).items()} for i in range(3)]
+    probe = {k: v.to(dev) for k, v in synthetic.make_trajectories(state_dim=d, T=L - 1, N=N, seed=40).items()}
+    cov = torch.eye(d, device=dev) * 0.1
+    torch.manual_seed(0)
+    f = mmf.door_models.DoorCrossmodalParticleFilter().to(dev).train()
+    f.num_particles = M
+    g = copy.deepcopy(f)
+    of, og = (torch.optim.Adam(m.parameters(), lr=1e-4, capturable=True) for m in (f, g))
+    f.noise, g.noise = mmf.NoiseSource(seed=5), mmf.NoiseSource(seed=5)
+    eval_noise = {id(f): mmf.NoiseSource(seed=11), id(g): mmf.NoiseSource(seed=11)}
+
+    def evaluate(m):   # the training noise stream is put back untouched
+        train_noise, m.noise = m.noise, eval_noise[id(m)]
+        m.eval()
+        try:
+            with torch.no_grad():
+                m.initialize_beliefs(mean=probe["states"][0], covariance=cov[None].expand(N, d, d))
+                return m.forward_loop(observations={k: probe[k][1:] for k in ("image", "gripper_pos", "gripper_sensors")},
+                                      controls=probe["controls"][1:])
+        finally:
+            m.train()
+            m.noise = train_noise
+
+    seen = []   # (what, eager twin's, graphed twin's) in the order they happened
+    engine.set_training_backend("hip")
+    engine.set_image_encoder_precision("f16x3")
+    try:
+        step = train.GraphedFilterStep(g, og, initial_covariance=cov, noise=g.noise, eager_steps=2)
+
+        def train_both(i):
+            seen.append((f"loss of step {i}", train.train_filter_step(f, batches[i % 3], of, initial_covariance=cov, noise=f.noise),
+                         step(batches[i % 3])))
+
+        def eval_both(when):
+            seen.append((f"eval {when}", evaluate(f), evaluate(g)))
+
+        train_both(0)
+        train_both(1)
+        eval_both("before the capture")
+        train_both(2)
+        assert step.graph is not None
+        eval_both("after the first replay")
+        train_both(3)
+        train_both(4)
+        eval_both("after three replays")
+    finally:
+        engine.set_image_encoder_precision(None)
+        engine.set_training_backend(None)
+    for what, a, b in seen:
+        assert torch.equal(a, b) if torch.is_tensor(a) else a == b, what
+    for (n, p), q in zip(f.named_parameters(), g.parameters()):
+        assert torch.equal(p.detach(), q.detach()), n

@@ -66,3 +66,37 @@ def test_training_entry_points_fail_loudly_without_backend_or_gpu():
         engine.set_training_backend(None)
     with pytest.raises(AssertionError):
         engine.set_training_backend("cpu")
+
+
+def test_packed_weight_cache_rebuilds_exactly_when_a_source_changes():
+    """``utils.cached``, the staleness rule of every packed-weight blob: the same object while nothing changed; a
+    rebuild after an in-place update, a version bump with no write (what a graph replay's writes need), a replaced
+    tensor, a move to another device, and under another key."""
+    from multimodalfilter_amd.utils import cached
+
+    builds = []
+
+    def build():
+        builds.append(1)
+        return object()
+
+    w, b = torch.zeros(4, 3), torch.zeros(4)
+    cache = {}
+    first = cached(cache, "k", [w, b], build)
+    assert cached(cache, "k", [w, b], build) is first and len(builds) == 1
+    w.add_(1.0)
+    v = cached(cache, "k", [w, b], build)
+    assert v is not first and len(builds) == 2
+    assert cached(cache, "k", [w, b], build) is v and len(builds) == 2
+    torch.autograd.graph.increment_version(b)
+    v = cached(cache, "k", [w, b], build)
+    assert len(builds) == 3 and cached(cache, "k", [w, b], build) is v
+    w2 = w.clone()
+    v = cached(cache, "k", [w2, b], build)
+    assert len(builds) == 4 and cached(cache, "k", [w2, b], build) is v
+    other = cached(cache, "other", [w2, b], build)
+    assert len(builds) == 5 and other is not v and cached(cache, "k", [w2, b], build) is v
+    if torch.cuda.is_available():
+        wd = w2.to("cuda:0")
+        cached(cache, "k", [wd, b], build)
+        assert len(builds) == 6
