@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MMF_ABI_VERSION 40
+#define MMF_ABI_VERSION 41
 
 #define MMF_EINVAL (-1)      /* bad argument (null pointer, d out of range, ...) */
 #define MMF_ETOOLARGE (-2)   /* size beyond what the kernel supports (see each call) */
@@ -871,6 +871,53 @@ int mmf_ekf_forward_loop(const MmfEkfLoopArgs* args /* host */, void* stream);
  *   or a device with too few CUs to keep every workgroup resident).  d must be 2 or 3, n_res_dyn 3. */
 int mmf_ekf_persistent_plan(int N, int K);
 size_t mmf_ekf_persistent_sync_words(int N, int K, int d);
+
+/* ---------------------------------------------------------------- LSTM baselines: the recurrence
+ * The two-layer nn.LSTM(in_dim, 512, 2) of DoorLSTMFilter / PushLSTMFilter over a whole (T, N, in_dim) sequence, the
+ * hidden state carried in and out (crossmodal/door_models/lstm.py:94, push_models/lstm.py:96: `lstm_out,
+ * self.lstm_hidden = self.lstm(fused_features, self.lstm_hidden)`).  PyTorch's gate order and formulas: gates i, f, g, o
+ * of W_ih x + b_ih + W_hh h + b_hh, sigma on i, f, o and tanh on g (both the deterministic forms of mmf_detmath.h),
+ * c' = f c + i g, h' = o tanh(c').  Exact fp32 products (v_mfma_f32_32x32x2_f32) in every MMF_PRECISION mode: a step is
+ * bound by the hand-off between workgroups, not by its ~0.2 GFLOP at N = 32.  csrc/lstm.hip.
+ *
+ *   mmf_lstm_blob_floats(in_dim): floats of the packed weights; in_dim a multiple of 8 in [8, 512], else 0.  Layout:
+ *     per layer l (K_0 = in_dim + 512, K_1 = 1024), per workgroup g < 64, 32 x K_l floats [k / 2][k & 1][row q], row
+ *     q = gate * 8 + j standing for row gate * 512 + 8 g + j of [W_ih | W_hh]; then (b_ih + b_hh) per layer as [g][q]:
+ *     2048 (K_0 + K_1 + 2) floats in all.
+ *   mmf_lstm_pack: the eight nn.LSTM tensors (weight_ih_l0 (2048, in_dim), weight_hh_l0 (2048, 512), bias_ih_l0,
+ *     bias_hh_l0 (2048), then the same of layer 1 with in_dim = 512) -> that layout, in one device pass.
+ *   mmf_lstm_persistent_plan(N, T): workgroups of the persistent form (> 0), 0 when not eligible (N > 256, a device
+ *     without room for 128 resident workgroups, or no device), MMF_EINVAL for N < 1 or T < 1.
+ *   mmf_lstm_sync_words(N): 4-byte words of MmfLstmArgs.sync_words: [abort word, padded to 16 B][64 progress words]
+ *     [2 layers][2 parities][512][N] 8-byte granules; 0 for N < 1.
+ *   mmf_lstm_forward: the whole sequence; persistent != 0 -> ONE launch (falls back to the loop of launches where the
+ *     plan is 0), otherwise T + 1 launches.  Both forms give the same bits.
+ */
+#define MMF_LSTM_HIDDEN 512
+#define MMF_LSTM_LAYERS 2
+
+typedef struct MmfLstmArgs {
+  int32_t T, N, in_dim;
+  int32_t persistent;        /* != 0: ONE persistent launch where mmf_lstm_persistent_plan(N, T) > 0                 */
+  const float* x;            /* (T, N, in_dim) layer-0 input                                                        */
+  const float* h0;           /* (2, N, 512) initial hidden state                                                    */
+  const float* c0;           /* (2, N, 512) initial cell state                                                      */
+  float* hT;                 /* (2, N, 512) out: final hidden state (not h0)                                        */
+  float* cT;                 /* (2, N, 512) out: final cell state (not c0)                                          */
+  float* h2;                 /* (T, N, 512) out: layer 1's hidden state at every step (nn.LSTM's output)           */
+  const float* packed;       /* mmf_lstm_pack                                                                       */
+  int32_t* range_flag;       /* or null; bit 2 = "a hand-off of the persistent launch timed out: discard the outputs
+                                and run the call again as launches"                                                 */
+  uint32_t* sync_words;      /* device workspace (mmf_lstm_sync_words), zeroed by the call; word 0 is the abort word */
+  size_t n_sync_words;       /* 4-byte words of sync_words                                                          */
+} MmfLstmArgs;               /* host struct holding device pointers                                                 */
+
+size_t mmf_lstm_blob_floats(int in_dim);
+int mmf_lstm_pack(const float* w_ih0, const float* w_hh0, const float* b_ih0, const float* b_hh0, const float* w_ih1,
+                  const float* w_hh1, const float* b_ih1, const float* b_hh1, float* packed, int in_dim, void* stream);
+int mmf_lstm_persistent_plan(int N, int T);
+size_t mmf_lstm_sync_words(int N);
+int mmf_lstm_forward(const MmfLstmArgs* args /* host */, void* stream);
 
 #ifdef __cplusplus
 }

@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("MMF_LIB_PATH") or os.path.join(_HERE, "libmmf_hip.so"
 MMF_UNITS = 64
 MMF_MAX_RES = 3
 MMF_MAX_STATE_DIM = 4
-ABI_VERSION = 40
+ABI_VERSION = 41
 KIND_DYNAMICS, KIND_MEASURE, KIND_JACOBIAN = 0, 1, 2  # particle-network kinds (csrc/particle_net.hip)
 PREC_F32, PREC_F16X3, PREC_BF16, PREC_F16X3_DUAL = 0, 1, 2, 3
 PRECISIONS = {"f32": PREC_F32, "f16x3": PREC_F16X3}                          # per-particle networks (K2)
@@ -128,6 +128,12 @@ class MmfEkfLoopArgs(Structure):
                 ("persistent", c_int32), ("n_sync_words", c_int32), ("sync_words", _FP)]
 
 
+class MmfLstmArgs(Structure):
+    _fields_ = [("T", c_int32), ("N", c_int32), ("in_dim", c_int32), ("persistent", c_int32),
+                ("x", _FP), ("h0", _FP), ("c0", _FP), ("hT", _FP), ("cT", _FP), ("h2", _FP), ("packed", _FP),
+                ("range_flag", _FP), ("sync_words", _FP), ("n_sync_words", c_size_t)]
+
+
 class MmfImageEncoderDesc(Structure):
     _fields_ = [("conv_w", _FP * 5), ("conv_b", _FP * 5), ("fc_w", _FP), ("fc_b", _FP),
                 ("res_w", _FP * 2), ("res_b", _FP * 2), ("variant", c_int32)]
@@ -175,6 +181,11 @@ SIGNATURES = {
     "mmf_ekf_forward_loop": (c_int, [POINTER(MmfEkfLoopArgs), c_void_p]),
     "mmf_ekf_persistent_plan": (c_int, [c_int, c_int]),
     "mmf_ekf_persistent_sync_words": (c_size_t, [c_int, c_int, c_int]),
+    "mmf_lstm_blob_floats": (c_size_t, [c_int]),
+    "mmf_lstm_pack": (c_int, [_FP] * 9 + [c_int, c_void_p]),
+    "mmf_lstm_persistent_plan": (c_int, [c_int, c_int]),
+    "mmf_lstm_sync_words": (c_size_t, [c_int]),
+    "mmf_lstm_forward": (c_int, [POINTER(MmfLstmArgs), c_void_p]),
     "mmf_dynamics_jacobian_multi": (c_int, [POINTER(c_void_p), c_int, c_int, _FP, POINTER(c_void_p), _FP, _FP, _FP,
                                             c_int, c_int, c_int, c_void_p]),
     "mmf_particle_net_train_forward": (c_int, [_FP, c_int, c_int, _FP, _FP, _FP, _FP, _FP, c_int, c_int, c_int, c_void_p]),
@@ -539,6 +550,34 @@ def ekf_forward_loop(args: MmfEkfLoopArgs, like: torch.Tensor):
     """Enqueue T fused-EKF steps (see include/mmf.h)."""
     with _on(like):
         _check(load().mmf_ekf_forward_loop(ctypes.byref(args), stream_of(like)), "mmf_ekf_forward_loop")
+
+
+LSTM_HIDDEN, LSTM_LAYERS = 512, 2
+
+
+def lstm_blob_floats(in_dim: int) -> int:
+    return int(load().mmf_lstm_blob_floats(in_dim))
+
+
+def lstm_pack(tensors, packed: torch.Tensor, in_dim: int):
+    """``tensors``: weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0, then the same of layer 1 (fp32, contiguous)."""
+    with _on(packed):
+        _check(load().mmf_lstm_pack(*[ptr(t) for t in tensors], ptr(packed), in_dim, stream_of(packed)), "mmf_lstm_pack")
+
+
+def lstm_persistent_plan(N: int, T: int) -> int:
+    """> 0: workgroups of the persistent form; 0: not eligible (or no device)."""
+    return int(load().mmf_lstm_persistent_plan(N, T))
+
+
+def lstm_sync_words(N: int) -> int:
+    return int(load().mmf_lstm_sync_words(N))
+
+
+def lstm_forward(args: MmfLstmArgs, like: torch.Tensor):
+    """The two-layer recurrence over a whole sequence (see include/mmf.h)."""
+    with _on(like):
+        _check(load().mmf_lstm_forward(ctypes.byref(args), stream_of(like)), "mmf_lstm_forward")
 
 
 def image_encoder_floats() -> int:

@@ -25,6 +25,8 @@
 // kernels combine in their epilogues), evaluated by one thread per particle before pass 1.
 #pragma once
 
+#include "mmf_granule.h"
+
 #ifndef K1_STAMP  // phase stamps of scripts/ubench/k1_phases.hip (pf_resample.hip defines it under MMF_K1_PHASE_CLOCKS)
 #define K1_STAMP(i)
 #endif
@@ -49,22 +51,6 @@ __device__ __forceinline__ float ld_coherent(const float* p) {
 __device__ __forceinline__ void st_coherent(float* p, float v) {
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-
-// ---- granules: {fp32 value, u32 tag} in one naturally aligned 8-byte word, written and read by ONE instruction
-using Granule = unsigned long long;
-__device__ __forceinline__ Granule make_granule(float v, unsigned tag) {
-  return (static_cast<Granule>(tag) << 32) | static_cast<Granule>(__float_as_uint(v));
-}
-__device__ __forceinline__ float granule_value(Granule g) { return __uint_as_float(static_cast<unsigned>(g)); }
-__device__ __forceinline__ unsigned granule_tag(Granule g) { return static_cast<unsigned>(g >> 32); }
-__device__ __forceinline__ Granule ld_granule(const Granule* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st_granule(Granule* p, float v, unsigned tag) {
-  __hip_atomic_store(p, make_granule(v, tag), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-constexpr unsigned kGranuleSpinLimit = 1u << 13;  // polls (>= ~0.5 us each: 4-8 ms) before a reader gives up and the
-                                                   // host re-runs the loop as launches (a healthy hand-off takes microseconds)
 
 // the crossmodal combine of two modalities' log-likelihoods, as the measurement kernel's epilogue evaluates it
 // (exact-fp32 mode: the shared deterministic logaddexp of include/mmf_detmath.h)

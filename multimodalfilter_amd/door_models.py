@@ -1,10 +1,11 @@
 """Door-task models (``state_dim = 3``) under the reference's class names
-(``/root/reference/crossmodal/door_models/__init__.py:5-19``; the LSTM baseline is out of
-scope)."""
+(``/root/reference/crossmodal/door_models/__init__.py:5-19``).  ``model_types`` mirrors the task's filter registry;
+the LSTM baseline (``__init__.py:16``) is exported by name and listed in ``baseline_types``."""
 from . import task_models as _tm
 
 _ns = _tm.make_task_models(_tm.DOOR)
 model_types = _ns.model_types
+baseline_types = _ns.baseline_types
 
 DoorDynamicsModel = _ns.DoorDynamicsModel
 DoorDynamicsModelBrent = _ns.DoorDynamicsModelBrent
@@ -21,3 +22,4 @@ DoorCrossmodalKalmanFilter = _ns.DoorCrossmodalKalmanFilter
 DoorUnimodalKalmanFilter = _ns.DoorUnimodalKalmanFilter
 DoorMeasurementCrossmodalKalmanFilter = _ns.DoorMeasurementCrossmodalKalmanFilter
 DoorMeasurementUnimodalKalmanFilter = _ns.DoorMeasurementUnimodalKalmanFilter
+DoorLSTMFilter = _ns.DoorLSTMFilter

@@ -152,6 +152,10 @@ PF_PERSISTENT = os.environ.get("MMF_PF_PERSISTENT", "1") not in ("", "0")
 # The EKF step loop likewise (mmf_ekf_persistent_plan > 0; csrc/ekf_persistent.inc): a wave owns 8 trajectories of one
 # sub-filter for all T steps, K > 1 sub-filters meet once per step through L2; bit-identical to the 2 T launches.
 EKF_PERSISTENT = os.environ.get("MMF_EKF_PERSISTENT", "1") not in ("", "0")
+# The recurrence of the LSTM baselines (mmf_lstm_persistent_plan > 0; csrc/lstm.hip): a workgroup owns 8 hidden units of
+# one layer for all T steps, the two layers run as a wavefront and hand their hidden states over through L2 once per
+# round; bit-identical to the T + 1 launches.  "0": A/B, off.
+LSTM_PERSISTENT = os.environ.get("MMF_LSTM_PERSISTENT", "1") not in ("", "0")
 
 
 # Training is opt-in: nothing switches paths silently, and eval() always means the forward-only HIP
@@ -202,7 +206,7 @@ def persistent_loop_gave_up(device) -> bool:
     out because a workgroup of the launch was not resident, e.g. another process shares the GPU)?  Clears the bit,
     switches the persistent form off for the rest of the process and warns once; the caller re-runs the loop as a
     loop of launches.  One 4-byte device->host read."""
-    global PF_PERSISTENT, EKF_PERSISTENT, _PERSISTENT_WARNED
+    global PF_PERSISTENT, EKF_PERSISTENT, LSTM_PERSISTENT, _PERSISTENT_WARNED
     flag = _RANGE_FLAGS.get(str(device))
     if flag is None:
         return False
@@ -210,13 +214,14 @@ def persistent_loop_gave_up(device) -> bool:
     if not bits & 4:
         return False
     flag.bitwise_and_(~4)
-    PF_PERSISTENT = EKF_PERSISTENT = False
+    PF_PERSISTENT = EKF_PERSISTENT = LSTM_PERSISTENT = False
     if not _PERSISTENT_WARNED:
         _PERSISTENT_WARNED = True
         import warnings
         warnings.warn("a persistent filter loop gave up waiting for a hand-off (a workgroup of its launch was not "
                       "resident -- is another process using this GPU?); this forward_loop is re-run as a loop of launches and the "
-                      "persistent forms are switched off for this process (MMF_PF_PERSISTENT=0 MMF_EKF_PERSISTENT=0 do so from the start)")
+                      "persistent forms are switched off for this process (MMF_PF_PERSISTENT=0 MMF_EKF_PERSISTENT=0 "
+                      "MMF_LSTM_PERSISTENT=0 do so from the start)")
     return True
 
 
@@ -242,6 +247,76 @@ def run_ekf_loop(a, mu: torch.Tensor, Sigma: torch.Tensor):
         Sigma.copy_(keep[2])
         a.persistent = 0
         _abi.ekf_forward_loop(a, mu)
+
+
+class PackedLstm:
+    """The eight tensors of a two-layer ``nn.LSTM(in_dim, 512, 2)`` packed into the recurrence kernel's layout
+    (``mmf_lstm_pack``: one device pass), rebuilt through ``utils.cached`` whenever one of them changed, moved or was
+    replaced."""
+
+    def __init__(self, lstm: nn.LSTM):
+        assert (lstm.num_layers == _abi.LSTM_LAYERS and lstm.hidden_size == _abi.LSTM_HIDDEN and lstm.bias
+                and not lstm.batch_first and not lstm.bidirectional and lstm.proj_size == 0), "unsupported nn.LSTM"
+        assert _abi.lstm_blob_floats(lstm.input_size) > 0, f"input size {lstm.input_size}: a multiple of 8 in [8, 512]"
+        self.lstm = lstm
+        self.in_dim = lstm.input_size
+        self._blobs = {}
+
+    def _sources(self) -> List[torch.Tensor]:
+        m = self.lstm
+        return [m.weight_ih_l0, m.weight_hh_l0, m.bias_ih_l0, m.bias_hh_l0,
+                m.weight_ih_l1, m.weight_hh_l1, m.bias_ih_l1, m.bias_hh_l1]
+
+    def blob(self) -> torch.Tensor:
+        src = self._sources()
+        return cached(self._blobs, "fwd", src, lambda: self._pack(src))
+
+    def _pack(self, src) -> torch.Tensor:
+        require_device(src[0], "PackedLstm")
+        keep = [t.detach().to(torch.float32).contiguous() for t in src]
+        blob = torch.empty(_abi.lstm_blob_floats(self.in_dim), dtype=torch.float32, device=src[0].device)
+        _abi.lstm_pack(keep, blob, self.in_dim)
+        return blob
+
+
+def packed_lstm(lstm: nn.LSTM) -> PackedLstm:
+    """The ``PackedLstm`` of ``lstm``, created on first use and kept on the module (outside its parameters and state dict)."""
+    packed = getattr(lstm, "_mmf_packed", None)
+    if packed is None:
+        packed = PackedLstm(lstm)
+        object.__setattr__(lstm, "_mmf_packed", packed)
+    return packed
+
+
+def run_lstm_loop(packed: PackedLstm, x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor):
+    """``mmf_lstm_forward``: ``x (T, N, in_dim)``, ``h0`` / ``c0 (2, N, 512)`` -> ``(h2 (T, N, 512), hT, cT)``, as ONE
+    persistent launch where the problem is eligible (``LSTM_PERSISTENT``, nothing being captured), with the loop of
+    launches as the fallback.  If a hand-off of the persistent launch timed out (bit 2 of the range flag) the call is run
+    again as launches: the kernel never writes its inputs, so ``h0`` / ``c0`` are still the initial state."""
+    require_device(x, "run_lstm_loop")
+    T, N, _ = x.shape
+    dev = x.device
+    H = _abi.LSTM_HIDDEN
+    x = x.to(torch.float32).contiguous()
+    h0 = h0.to(torch.float32).contiguous()
+    c0 = c0.to(torch.float32).contiguous()
+    assert h0.shape == c0.shape == (_abi.LSTM_LAYERS, N, H)
+    h2 = torch.empty((T, N, H), dtype=torch.float32, device=dev)
+    hT, cT = torch.empty_like(h0), torch.empty_like(c0)
+    n_words = _abi.lstm_sync_words(N)
+    sync = torch.empty(n_words, dtype=torch.int32, device=dev)  # abort word, progress words, granules (zeroed by the call)
+    a = _abi.MmfLstmArgs()
+    a.T, a.N, a.in_dim = T, N, packed.in_dim
+    a.persistent = int(LSTM_PERSISTENT and not CAPTURING and T > 0 and _abi.lstm_persistent_plan(N, T) > 0)
+    P = lambda t: ctypes.c_void_p(t.data_ptr())
+    a.x, a.h0, a.c0, a.hT, a.cT, a.h2, a.packed = P(x), P(h0), P(c0), P(hT), P(cT), P(h2), P(packed.blob())
+    a.range_flag = P(range_flag(dev))
+    a.sync_words, a.n_sync_words = P(sync), n_words
+    _abi.lstm_forward(a, x)
+    if a.persistent and persistent_loop_gave_up(dev):
+        a.persistent = 0
+        _abi.lstm_forward(a, x)
+    return h2, hT, cT
 
 
 # While a training step is being captured into a hipGraph (train.GraphedFilterStep) nothing may read the device: the checks

@@ -1,9 +1,11 @@
 """Push-task models (``state_dim = 2``) under the reference's class names
-(``/root/reference/crossmodal/push_models/__init__.py:5-21``; LSTM baseline out of scope)."""
+(``/root/reference/crossmodal/push_models/__init__.py:5-21``).  ``model_types`` mirrors the task's filter registry;
+the LSTM baseline (``__init__.py:18``) is exported by name and listed in ``baseline_types``."""
 from . import task_models as _tm
 
 _ns = _tm.make_task_models(_tm.PUSH)
 model_types = _ns.model_types
+baseline_types = _ns.baseline_types
 
 PushDynamicsModel = _ns.PushDynamicsModel
 PushMeasurementModel = _ns.PushMeasurementModel
@@ -19,3 +21,4 @@ PushCrossmodalKalmanFilter = _ns.PushCrossmodalKalmanFilter
 PushUnimodalKalmanFilter = _ns.PushUnimodalKalmanFilter
 PushMeasurementCrossmodalKalmanFilter = _ns.PushMeasurementCrossmodalKalmanFilter
 PushMeasurementUnimodalKalmanFilter = _ns.PushMeasurementUnimodalKalmanFilter
+PushLSTMFilter = _ns.PushLSTMFilter

@@ -792,6 +792,126 @@ def make_task_models(task: TaskSpec) -> SimpleNamespace:
                 virtual_sensor_model=base_models.UnimodalVirtualSensorModel(
                     virtual_sensor_model=_modal_sensors(), state_dim=D))
 
+    # ------------------------------------------------------------- LSTM baseline
+    class LSTMFilter(base.Filter):
+        """The baseline every filter is compared against (``door_models/lstm.py:13-100``, ``push_models/lstm.py:13-102``):
+        encoders + fusion MLP per frame, a two-layer ``nn.LSTM(units, 512)`` over the sequence, an MLP head.  Not a Bayes
+        filter: the "belief" is the LSTM's ``(h, c)``, zeroed by ``initialize_beliefs`` and carried from one
+        ``forward_loop`` to the next (``lstm.py:94``).
+
+        Eval path, in HIP: the image encoder for all ``T*N`` frames through K4, encoders + fusion as one K7 program over
+        the ``T*N`` rows, the whole recurrence as one persistent launch (``engine.run_lstm_loop``, ``csrc/lstm.hip``), the
+        head as one K7 program over ``T*N`` rows.  Training (``engine.use_autograd``): the owned torch modules, as the
+        reference trains them (``train_helpers.py:124-162``)."""
+
+        def __init__(self, units: int = 64):
+            super().__init__(state_dim=D)
+            self.lstm_hidden_dim = 512
+            self.lstm_num_layers = 2
+            self.units = units
+
+            # the reference's construction order (same seeded weights)
+            self.image_rows = 32
+            self.image_cols = 32
+            self.observation_image_layers = layers.image_encoder(units, spanning_avg_pool=task is PUSH)
+            self.observation_pos_layers = layers.vector_encoder(task.obs_pos_dim, units)
+            self.observation_sensors_layers = layers.vector_encoder(task.obs_sensors_dim, units)
+            self.control_layers = layers.vector_encoder(task.control_dim, units)
+            self.fusion_layers = nn.Sequential(nn.Linear(units * 4, units), nn.ReLU(inplace=True), layers.ResLinear(units))
+            self.lstm = nn.LSTM(units, self.lstm_hidden_dim, self.lstm_num_layers)
+            self.output_layers = nn.Sequential(nn.Linear(self.lstm_hidden_dim, units), nn.ReLU(inplace=True),
+                                               nn.Linear(units, self.state_dim))
+            self._fuse_prog = None
+            self._head_prog = None
+
+        def initialize_beliefs(self, *, mean: torch.Tensor, covariance: torch.Tensor) -> None:
+            N = len(mean)
+            device = next(self.parameters()).device
+            self.lstm_hidden = (
+                torch.zeros(self.lstm_num_layers, N, self.lstm_hidden_dim, device=device),
+                torch.zeros(self.lstm_num_layers, N, self.lstm_hidden_dim, device=device),
+            )
+
+        def forward_loop(self, *, observations, controls) -> torch.Tensor:
+            return engine.checked_loop(type(self)._forward_loop)(self, observations=observations, controls=controls)
+
+        def _forward_loop(self, *, observations, controls) -> torch.Tensor:
+            T, N = observations["image"].shape[:2]
+            assert observations["gripper_pos"].shape[:2] == (T, N)
+            assert observations["gripper_sensors"].shape[:2] == (T, N)
+            if engine.use_autograd(self):
+                return self._forward_loop_autograd(observations, controls, T, N)
+            with torch.no_grad():
+                return self._forward_loop_native(observations, controls, T, N)
+
+        def _forward_loop_autograd(self, observations, controls, T, N):
+            """The reference's formulation (``lstm.py:62-100``) on the owned torch modules; the hidden state carries the
+            graph from one call to the next, as it does there."""
+            images = observations["image"].reshape(T * N, self.image_rows, self.image_cols)
+            image_features = engine.image_features_autograd(self.observation_image_layers, images).reshape(T, N, self.units)
+            merged = torch.cat((image_features, self.observation_pos_layers(observations["gripper_pos"]),
+                                self.observation_sensors_layers(observations["gripper_sensors"]),
+                                self.control_layers(controls)), dim=-1)
+            fused = self.fusion_layers(merged)
+            lstm_out, self.lstm_hidden = self.lstm(fused, self.lstm_hidden)
+            return self.output_layers(lstm_out)
+
+        def _programs(self):
+            U = self.units
+            if self._fuse_prog is None:
+                # encoders + fusion (lstm.py:74-87): concatenation order image, pos, sensors, control
+                p = TrajProgram()
+                srcs = [(p.load("image_feat", U), 0, U)]
+                for name, seq, dim in (("gripper_pos", self.observation_pos_layers, task.obs_pos_dim),
+                                       ("gripper_sensors", self.observation_sensors_layers, task.obs_sensors_dim),
+                                       ("controls", self.control_layers, task.control_dim)):
+                    raw = p.load(name, dim)
+                    srcs.append((p.vector_encoder(seq, raw, dim), 0, U))
+                    p.free(raw)
+                x = p.linear(srcs, self.fusion_layers[0], _abi.ACT_RELU)
+                for (slot, _o, _w) in srcs:
+                    p.free(slot)
+                p.res_linear(self.fusion_layers[2], x, U)
+                p.store("fused", x, U)
+                self._fuse_prog = p
+            if self._head_prog is None:
+                # output head (lstm.py:97): Linear(512, units) + ReLU + Linear(units, d) on the LSTM's output rows, read as
+                # four 128-wide pieces of each 512-wide row
+                H, W = self.lstm_hidden_dim, 128
+                p = TrajProgram()
+                srcs = [(p.load("h2", W, stride=H, off=o), 0, W) for o in range(0, H, W)]
+                a = p.linear(srcs, self.output_layers[0], _abi.ACT_RELU)
+                for (slot, _o, _w) in srcs:
+                    p.free(slot)
+                p.store("out", p.linear([(a, 0, U)], self.output_layers[2]), self.state_dim)
+                self._head_prog = p
+            return self._fuse_prog, self._head_prog
+
+        def _forward_loop_native(self, observations, controls, T, N):
+            dev = observations["gripper_pos"].device
+            engine.require_device(observations["gripper_pos"], f"{type(self).__name__}.forward_loop")
+            R = T * N
+            fuse, head = self._programs()
+            f32 = lambda t, w: t.reshape(R, w).to(torch.float32).contiguous()
+            images = observations["image"].reshape(R, self.image_rows, self.image_cols)
+            image_feat = engine.encode_images([self.observation_image_layers], images)[0]
+            fused = torch.empty((R, self.units), dtype=torch.float32, device=dev)
+            fuse.run({"image_feat": image_feat.contiguous(), "gripper_pos": f32(observations["gripper_pos"], task.obs_pos_dim),
+                      "gripper_sensors": f32(observations["gripper_sensors"], task.obs_sensors_dim),
+                      "controls": f32(controls, task.control_dim), "fused": fused}, R)
+            h, c = self.lstm_hidden
+            h2, hT, cT = engine.run_lstm_loop(engine.packed_lstm(self.lstm), fused.view(T, N, self.units),
+                                              h.detach(), c.detach())
+            self.lstm_hidden = (hT, cT)
+            out = torch.empty((R, self.state_dim), dtype=torch.float32, device=dev)
+            head.run({"h2": h2.view(R, self.lstm_hidden_dim), "out": out}, R)
+            return out.view(T, N, self.state_dim)
+
+    LSTMFilter.__name__ = LSTMFilter.__qualname__ = f"{P}LSTMFilter"
+    setattr(ns, f"{P}LSTMFilter", LSTMFilter)
+    # not in model_types: the registry mirrors crossmodal/tasks/_task.py, whose filters every oracle test builds
+    ns.baseline_types = {f"{P}LSTMFilter": LSTMFilter}
+
     # reference class names
     renamed = {}
     for short, cls in list(ns.model_types.items()):
