@@ -36,6 +36,23 @@ extern "C" {
 #define MMF_MAX_RES 3        /* residual blocks after the join layer (LDS: 3 -> 149.5 KiB) */
 #define MMF_MAX_STATE_DIM 4
 
+/* The device status word: ONE int32 per device that the host hands to every call as `range_flag` (or null). Kernels only
+ * ever OR into it; the host reads it (one 4-byte copy) where a result is about to be used, and clears what it consumed.
+ *   MMF_FLAG_RANGE    OR-ed by an MMF_PREC_F16X3 kernel whose operand left the range in which the two-half f16
+ *                     split is exact (|x| >= 65504: the result is finite but wrong -- re-run with MMF_PREC_F32); never
+ *                     written by MMF_PREC_F32 launches.  Consumed by the host's check at the end of a forward_loop / step.
+ *   MMF_FLAG_GAVE_UP  OR-ed by a persistent launch (mmf_pf_forward_loop, mmf_ekf_forward_loop, mmf_lstm_forward with
+ *                     `persistent`) when a hand-off's bounded spin ran out because a workgroup of the launch was not
+ *                     resident: every output of that call is to be discarded.  Consumed by the host right after the call,
+ *                     which restores the call's in-place inputs and runs it again as launches.
+ *   MMF_FLAG_NOT_PD   never OR-ed by a kernel of this library: the host ORs it in while it captures a training step (no
+ *                     host read there) when initialize_beliefs met a covariance that is not positive definite; consumed
+ *                     after the replay.
+ * The value 2 is unused. */
+#define MMF_FLAG_RANGE 1
+#define MMF_FLAG_GAVE_UP 4
+#define MMF_FLAG_NOT_PD 16
+
 /* arithmetic of the 64x64 layers of the per-particle networks (K2) */
 #define MMF_PREC_F32 0    /* v_mfma_f32_32x32x2_f32: exact fp32 products                        */
 #define MMF_PREC_BF16 2   /* mmf_image_encoder only: operands rounded to ONE bf16, one v_mfma_*_bf16 per
@@ -176,7 +193,7 @@ int mmf_pack_particle_net(const MmfParticleNetDesc* desc /* host */, float* pack
  *  noise       (N*M, d) standard normal, or null (EKF predict / open-loop rollouts)
  *  scale_tril  (d, d) row-major lower-triangular, shared by all rows (ignored if noise null)
  *  states_out  (N*M, d)     may alias states_in
- *  range_flag  int32 on the device or null; MMF_PREC_F16X3 ORs 1 into it when an activation
+ *  range_flag  int32 on the device or null; MMF_PREC_F16X3 ORs MMF_FLAG_RANGE into it when an activation
  *              exceeded the f16-split range (|x| >= 65504: the result is finite but wrong --
  *              re-run with MMF_PREC_F32); never written otherwise
  */
@@ -307,7 +324,7 @@ int mmf_pack_image_encoder(const MmfImageEncoderDesc* desc /* host */, float* pa
  *  images     (N, 32, 32)        shared by every encoder
  *  feat       (n_nets, N, 64)    out
  *  workspace  >= mmf_image_encoder_workspace_bytes(N, n_nets) bytes of device memory
- *  range_flag int32 on the device or null: MMF_PREC_F16X3 ORs 1 into it when an activation
+ *  range_flag int32 on the device or null: MMF_PREC_F16X3 ORs MMF_FLAG_RANGE into it when an activation
  *             left the f16-split range (see mmf_pf_dynamics)
  *  variant    MMF_ENCODER_*: the architecture every blob of this call was packed for
  *  precision  MMF_PREC_F32: every layer on the f32 MFMA, one launch per layer.  MMF_PREC_F16X3: split-f16
@@ -371,7 +388,7 @@ int mmf_image_convs_train_backward_h(const float* packed_bwd, const float* a1, c
  * three-product f16 split of both operands (csrc/image_encoder_train_h.inc): 54 MFMAs of 32 cycles per image row instead of
  * 144 of 64.  g_absmax: DEVICE scalar, the largest |g| (the caller reduces it first: no host read) -- g is multiplied by the
  * power of two that brings it to [2^14, 2^15) and the sums are multiplied back, so gradients of any magnitude keep their
- * leading bits; db is the exact fp32 sum.  range_flag (or null): OR-ed with 1 if an activation left the f16 range. */
+ * leading bits; db is the exact fp32 sum.  range_flag (or null): OR-ed with MMF_FLAG_RANGE if an activation left the f16 range. */
 int mmf_conv_weight_grads_h(const float* g, const float* act, const float* g_absmax, float* partial, float* partial_b,
                             int32_t* range_flag, int N, int co, int ci, int n_blocks, float* dw, float* db, void* stream);
 
@@ -405,7 +422,7 @@ typedef struct MmfPfLoopArgs {
   float* logw_b;             /* (N, M) scratch                                                */
   float* loglik;             /* (N, M) scratch                                                */
   float* estimates;          /* (T, N, d) out                                                 */
-  int32_t* range_flag;       /* device int32 or null (see mmf_pf_dynamics)                    */
+  int32_t* range_flag;       /* device status word or null (MMF_FLAG_*)                       */
   int32_t* final_location;   /* HOST int32 out or null: bit 0 belief states in states_b,      */
                              /* bit 1 log-weights in logw_b                                   */
   void* const* events;       /* HOST array of hipEvent_t or null: recorded around every launch */
@@ -837,7 +854,7 @@ typedef struct MmfEkfLoopArgs {
   int32_t fusion, feedback;  /* as mmf_ekf_step                                              */
   int32_t n_res_dyn;
   int32_t precision;         /* of dyn_packed (the Jacobian launches)                          */
-  int32_t* range_flag;       /* f16x3: OR-ed with 1 when an operand leaves the f16 range, or null */
+  int32_t* range_flag;       /* device status word or null: MMF_FLAG_RANGE (f16x3), MMF_FLAG_GAVE_UP (persistent) */
   const float* dyn_packed[MMF_LOOP_MAX_MEAS];  /* blobs of the dynamics networks (mmf_pack_particle_net) */
   const float* dyn_bias[MMF_LOOP_MAX_MEAS];    /* (T*N, 64) hoisted control terms               */
   const float* q_tril;       /* (K, d, d)                                                      */
@@ -857,8 +874,8 @@ typedef struct MmfEkfLoopArgs {
                                 mu_pred and A are not touched; same bits as the loop of launches                  */
   int32_t n_sync_words;      /* 4-byte words of sync_words (>= mmf_ekf_persistent_sync_words(N, K, d))            */
   uint32_t* sync_words;      /* persistent: device workspace of the in-launch hand-offs between the K sub-filters'
-                                workgroups (tagged 8-byte granules), zeroed by the call; range_flag bit 2 = "a
-                                hand-off timed out: discard this loop and run it as launches"                     */
+                                workgroups (tagged 8-byte granules), zeroed by the call; a hand-off that times
+                                out ORs MMF_FLAG_GAVE_UP into range_flag: discard this loop, run it as launches   */
 } MmfEkfLoopArgs;            /* host struct holding device pointers                            */
 
 int mmf_ekf_forward_loop(const MmfEkfLoopArgs* args /* host */, void* stream);
@@ -906,8 +923,8 @@ typedef struct MmfLstmArgs {
   float* cT;                 /* (2, N, 512) out: final cell state (not c0)                                          */
   float* h2;                 /* (T, N, 512) out: layer 1's hidden state at every step (nn.LSTM's output)           */
   const float* packed;       /* mmf_lstm_pack                                                                       */
-  int32_t* range_flag;       /* or null; bit 2 = "a hand-off of the persistent launch timed out: discard the outputs
-                                and run the call again as launches"                                                 */
+  int32_t* range_flag;       /* or null; MMF_FLAG_GAVE_UP = "a hand-off of the persistent launch timed out: discard the
+                                outputs and run the call again as launches"                                         */
   uint32_t* sync_words;      /* device workspace (mmf_lstm_sync_words), zeroed by the call; word 0 is the abort word */
   size_t n_sync_words;       /* 4-byte words of sync_words                                                          */
 } MmfLstmArgs;               /* host struct holding device pointers                                                 */

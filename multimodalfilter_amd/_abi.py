@@ -22,6 +22,7 @@ KIND_DYNAMICS, KIND_MEASURE, KIND_JACOBIAN = 0, 1, 2  # particle-network kinds (
 PREC_F32, PREC_F16X3, PREC_BF16, PREC_F16X3_DUAL = 0, 1, 2, 3
 PRECISIONS = {"f32": PREC_F32, "f16x3": PREC_F16X3}                          # per-particle networks (K2)
 IMAGE_PRECISIONS = {"f32": PREC_F32, "f16x3": PREC_F16X3, "bf16": PREC_BF16}  # image encoder (K4)
+FLAG_RANGE, FLAG_GAVE_UP, FLAG_NOT_PD = 1, 4, 16  # the device status word (include/mmf.h: MMF_FLAG_*)
 
 _FP = c_void_p  # device pointers travel as integers
 
@@ -255,6 +256,11 @@ def ptr(t: torch.Tensor, *, dtype=torch.float32):
     if not t.is_contiguous():
         raise MmfError("tensor must be contiguous")
     return t.data_ptr()
+
+
+def vp(t: torch.Tensor, dtype=torch.float32):
+    """``ptr`` as the ``c_void_p`` a struct field takes (``None`` -> NULL)."""
+    return None if t is None else c_void_p(ptr(t, dtype=dtype))
 
 
 def _on(t: torch.Tensor):

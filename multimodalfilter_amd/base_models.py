@@ -14,7 +14,6 @@ fusion arithmetic in HIP.
 Reference quirks that change numbers are preserved and flag-gated.
 """
 import abc
-import ctypes
 from typing import List, Optional
 
 import numpy as np
@@ -355,8 +354,7 @@ class _FusedKalmanFilters(base.Filter, _EnabledModels):
         fusion, feedback, fuse_w = plan[:3]
         gate = plan[3] if len(plan) > 3 else None  # (T,) int32 device words: step t writes back only where != 0
         outs = self._loop_sensor_outputs
-        d, K = self.state_dim, len(live)
-        dev = live[0]._belief_mean.device
+        d = self.state_dim
         for f in live:
             assert f._initialized, "Kalman filter not initialized!"
         f32 = lambda x: x.to(torch.float32)
@@ -365,29 +363,12 @@ class _FusedKalmanFilters(base.Filter, _EnabledModels):
         mu = torch.stack([f._belief_mean for f in live]).contiguous()
         Sigma = torch.stack([f._belief_covariance for f in live]).contiguous()
         q = torch.stack([m.scale_tril() for m in dyns]).to(torch.float32).contiguous()
-        mu_pred, A = torch.empty_like(mu), torch.empty_like(Sigma)
-        Sigma_f = torch.empty((N, d, d), dtype=torch.float32, device=dev)
-        est = torch.empty((T, N, d), dtype=torch.float32, device=dev)
-        prec = dyns[0]._net.precision_code()
-        blobs = [m._net.blob(prec) for m in dyns]
-        biases = [ctrl_all[i]["bias"] for i in live_idx]
-        fw = None if fuse_w is None else f32(fuse_w).contiguous()
-        P = lambda t: None if t is None else ctypes.c_void_p(_abi.ptr(t))
-        a = _abi.MmfEkfLoopArgs()
-        a.T, a.N, a.d, a.K, a.fusion, a.feedback = T, N, d, K, fusion, feedback
-        a.n_res_dyn, a.precision = dyns[0]._net.n_res, prec
-        a.range_flag = (ctypes.c_void_p(_abi.ptr(engine.range_flag(dev), dtype=torch.int32))
-                        if prec != _abi.PREC_F32 else None)
-        for k in range(K):
-            a.dyn_packed[k], a.dyn_bias[k] = P(blobs[k]), P(biases[k])
-        a.q_tril, a.z, a.r_tril, a.fuse_w = P(q), P(z), P(r), P(fw)
-        a.mu, a.Sigma, a.mu_pred, a.A, a.Sigma_f, a.estimates = P(mu), P(Sigma), P(mu_pred), P(A), P(Sigma_f), P(est)
-        if gate is not None:
-            a.feedback_gate = ctypes.c_void_p(_abi.ptr(gate, dtype=torch.int32))
-        engine.run_ekf_loop(a, mu, Sigma)
+        est, Sigma_f = engine.run_ekf_loop([m._net for m in dyns], [ctrl_all[i]["bias"] for i in live_idx], q, z, r, mu, Sigma,
+                                           fusion=fusion, feedback=feedback, gate=gate,
+                                           fuse_w=None if fuse_w is None else f32(fuse_w).contiguous())
         for k, f in enumerate(live):
             f._belief_mean, f._belief_covariance = mu[k], Sigma[k]
-        return est, (Sigma_f if fusion else None)
+        return est, Sigma_f
 
     @engine.checked_loop
     def forward_loop(self, *, observations, controls):

@@ -125,7 +125,7 @@ __device__ __forceinline__ void jacobian_tile(const float* __restrict__ lds, con
     }
   }
   if constexpr (F16) {
-    if (range_flag != nullptr && (amax[0] >= kF16Saturated || amax[1] >= kF16Saturated)) atomicOr(range_flag, 1);
+    if (range_flag != nullptr && (amax[0] >= kF16Saturated || amax[1] >= kF16Saturated)) atomicOr(range_flag, MMF_FLAG_RANGE);
   }
   float mine[NOUT];
 #pragma unroll
@@ -281,10 +281,10 @@ __global__ __launch_bounds__(kEkfPersistThreads, 1) void ekf_persistent_loop_ker
 #pragma unroll
             for (int jj = 0; jj < D; ++jj) Ss[kk].a[i][jj] = v[D + i * D + jj];
         }
-        if (gave_up) {  // wave-uniform: the host discards this loop and re-runs it as launches (engine.check_range, bit 2)
+        if (gave_up) {  // wave-uniform: the host discards this loop and re-runs it as launches (engine.run_persistent, MMF_FLAG_GAVE_UP)
           if (lane == 0) {
             __hip_atomic_store(a.abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (a.range_flag != nullptr) atomicOr(a.range_flag, 4);
+            if (a.range_flag != nullptr) atomicOr(a.range_flag, MMF_FLAG_GAVE_UP);
           }
           return;
         }

@@ -484,7 +484,7 @@ __global__ __launch_bounds__(256) void fc_partial_f16x3_kernel(FcArgs a) {
     if (ks + 2 < KSTEPS) load_w(ks + 2, ks & 1);
     __builtin_amdgcn_sched_barrier(0);  // left alone the scheduler sinks every request to just before its use
   }
-  if (a.range_flag != nullptr && !(amax < 65504.0f)) atomicOr(a.range_flag, 1);
+  if (a.range_flag != nullptr && !(amax < 65504.0f)) atomicOr(a.range_flag, MMF_FLAG_RANGE);
   if (img0 + j < a.N) {
     // lane (image j, h), register r of tile t -> output 32 t + (r & 3) + 8 (r >> 2) + 4 h
     float* p = a.partial + ((static_cast<size_t>(net) * kFcSplit + split) * a.N + img0 + j) * kFeat + 4 * h;

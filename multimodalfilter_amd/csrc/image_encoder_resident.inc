@@ -493,7 +493,7 @@ __global__ __launch_bounds__(kFusedThreads) void image_encoder_resident_kernel(F
     }
   }
   K4F_WG_STAMP(0, 1);
-  if (a.range_flag != nullptr && saturated(amax)) atomicOr(a.range_flag, 1);
+  if (a.range_flag != nullptr && saturated(amax)) atomicOr(a.range_flag, MMF_FLAG_RANGE);
 }
 
 // image -> E in ONE launch (persistent 512-thread workgroups, one per CU, networks on blockIdx.y)

@@ -108,7 +108,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_h_kernel(const float* __restri
 #pragma unroll
       for (int r = 0; r < 16; ++r) p[(tap * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * 32 + i] = acc[tap][r];
   }
-  if (range_flag != nullptr && saturated(amax)) atomicOr(range_flag, 1);
+  if (range_flag != nullptr && saturated(amax)) atomicOr(range_flag, MMF_FLAG_RANGE);
 }
 
 // ---- K6, image encoder, f16x3 data gradients of the 3x3 layers with 32 output channels ------------------------------------

@@ -55,7 +55,7 @@ struct LstmKernelArgs {
   mmf::Granule* hx;       // [layer][parity][512][N] granules
   unsigned* abort_word;
   unsigned* progress;     // [64]: layer-1 workgroup g has finished its reads of step progress[g] - 1
-  int* range_flag;        // bit 2: a hand-off timed out
+  int* range_flag;        // MMF_FLAG_GAVE_UP: a hand-off timed out
 };
 
 __host__ __device__ inline int layer_k(int layer, int in_dim) { return layer ? 2 * kH : in_dim + kH; }
@@ -237,7 +237,7 @@ __global__ void __launch_bounds__(kThreads) lstm_rounds_kernel(LstmKernelArgs a)
   if (gave_up) {
     if (tid == 0) {
       __hip_atomic_store(a.abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (a.range_flag != nullptr) atomicOr(a.range_flag, 4);
+      if (a.range_flag != nullptr) atomicOr(a.range_flag, MMF_FLAG_GAVE_UP);
     }
     return;
   }

@@ -635,7 +635,7 @@ __global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(NetArgsMul
       // clamped by the next relu_sat -- either way the tile's outputs stay finite and the flag says they are
       // invalid (engine.check_range raises: per forward_loop, and per step for a bare forward())
       if (a.range_flag != nullptr && (amax[0] >= kF16Saturated || amax[1] >= kF16Saturated))
-        atomicOr(a.range_flag, 1);
+        atomicOr(a.range_flag, MMF_FLAG_RANGE);
     }
 
     // ---- head (64 -> NOUT) on the VALU: each lane holds 32 of the 64 features of its columns

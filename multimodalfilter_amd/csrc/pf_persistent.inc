@@ -28,7 +28,7 @@
 // 4.2 us per hop, 12.5 of a 46 us step at 32 x 300).  WAR hazards are excluded by the chain itself: a row is
 // rewritten only by the stage whose input depends on every reader of the old value having finished.  Every spin
 // is bounded: a reader that waits too long (or sees the abort word) sets the abort word and leaves, every other
-// wave follows at its next poll, and the host raises (engine.check_range: bit 2 of the range flag).
+// wave follows at its next poll, and the host re-runs the loop as launches (MMF_FLAG_GAVE_UP in the status word: engine.run_persistent).
 // Correctness does not depend on placement or dispatch order; progress needs all workgroups resident, which the
 // grid (<= 240 workgroups of one per CU, LDS-limited) guarantees on an otherwise idle 256-CU device.
 
@@ -172,7 +172,7 @@ __device__ __forceinline__ bool small_tile(const float* __restrict__ lds, const 
         if (__builtin_amdgcn_readfirstlane(stop)) {
           if (lane == 0) {
             __hip_atomic_store(a.abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (a.range_flag != nullptr) atomicOr(a.range_flag, 4);  // engine.check_range: "the persistent loop gave up"
+            if (a.range_flag != nullptr) atomicOr(a.range_flag, MMF_FLAG_GAVE_UP);
           }
           return false;
         }
@@ -231,7 +231,7 @@ __device__ __forceinline__ bool small_tile(const float* __restrict__ lds, const 
     for (int i = 0; i < NRES; ++i) res_block<1, false>(lds, NRES, 3 + 2 * i, H, X, lane, true);
   }
   if constexpr (F16) {
-    if (a.range_flag != nullptr && (amax[0] >= kF16Saturated || amax[1] >= kF16Saturated)) atomicOr(a.range_flag, 1);
+    if (a.range_flag != nullptr && (amax[0] >= kF16Saturated || amax[1] >= kF16Saturated)) atomicOr(a.range_flag, MMF_FLAG_RANGE);
   }
   // ---- head (64 -> NOUT) on the VALU
   float mine[NOUT];
@@ -396,7 +396,7 @@ __global__ __launch_bounds__(kPersistThreads, 2) void pf_persistent_loop_kernel(
       tr.lo = (last && a.logw_out_last) ? a.logw_out_last + static_cast<size_t>(n) * a.M : nullptr;
       tr.io = nullptr;
       if (!mmf::resample_systematic_trajectory<D, true, true, PREC == MMF_PREC_F32>(smem, tr, a.M, a.M, a.lw_uniform, log_uniform)) {
-        if (threadIdx.x == 0 && a.range_flag != nullptr) atomicOr(a.range_flag, 4);
+        if (threadIdx.x == 0 && a.range_flag != nullptr) atomicOr(a.range_flag, MMF_FLAG_GAVE_UP);
         return;
       }
       __syncthreads();  // the LDS of this trajectory is free again
@@ -591,7 +591,7 @@ int mmf_internal_pf_persistent(const MmfPfLoopArgs* a, void* stream) {
                        pa.stamp_step, names[k1r ? 5 : role], cnt, busy / cnt, mx, wait / cnt, comp / cnt, real > 0 ? busy / real * 0.1 : 0.0);
     }
   }
-  // a reader that gives up ORs bit 2 into the range flag: engine.check_range raises after the loop
+  // a reader that gives up ORs MMF_FLAG_GAVE_UP into the status word: the host re-runs the loop as launches
   if (a->final_location) *a->final_location = last_into_b ? 2 : 0;
   return 0;
 }

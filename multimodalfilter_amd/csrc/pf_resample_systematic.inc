@@ -77,7 +77,7 @@ struct K1Trajectory {  // pointers of ONE trajectory's rows
   unsigned in_tag;       // COH: the tag this step's log-likelihood / particle granules carry
   unsigned so_tag;       // COH: tag of the granules written (0: plain floats -- the loop's last step)
   unsigned* abort_word;  // COH: bounded spins
-  int* range_flag;       // COH: bit 2 = "a reader gave up" (engine.check_range), or null
+  int* range_flag;       // COH: MMF_FLAG_GAVE_UP = "a reader gave up" (engine.run_persistent), or null
   unsigned long long* stamps;  // COH diagnostic: [4] cycle stamps of thread 0, or null
   int spin_sleep;        // COH: s_sleep between polls (0: busy polling)
 };
@@ -132,9 +132,9 @@ __device__ __forceinline__ bool resample_systematic_trajectory(unsigned char* sm
       }
       if (granule_tag(g) != a.in_tag) {
         // timed out: the value read is NOT this step's row.  Report it the way the other spins do -- the abort word stops
-        // the other roles, bit 2 of the range flag makes the host discard this loop and re-run it as launches
+        // the other roles, MMF_FLAG_GAVE_UP in the status word makes the host discard this loop and re-run it as launches
         __hip_atomic_store(a.abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (a.range_flag != nullptr) atomicOr(a.range_flag, 4);
+        if (a.range_flag != nullptr) atomicOr(a.range_flag, MMF_FLAG_GAVE_UP);
       }
       return granule_value(g);
     } else {

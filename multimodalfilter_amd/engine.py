@@ -1,8 +1,12 @@
 """Bridges ``nn.Module`` parameters to the HIP kernels: fragment-ordered weight blobs for
 the per-particle networks, and the launches of K2 / K5 (``csrc/particle_net.hip``).
 """
+import contextlib
 import ctypes
+import functools
 import os
+import threading
+import warnings
 from typing import List, Sequence
 
 import torch
@@ -190,8 +194,7 @@ _RANGE_FLAGS = {}
 
 
 def range_flag(device) -> torch.Tensor:
-    """Per-device sticky int32: the f16x3 kernels OR 1 into it when an activation left the
-    range in which the two-half split is exact."""
+    """The device status word (``include/mmf.h``, ``MMF_FLAG_*``): one sticky int32 per device that kernels OR into."""
     key = str(device)
     if key not in _RANGE_FLAGS:
         _RANGE_FLAGS[key] = torch.zeros(1, dtype=torch.int32, device=device)
@@ -199,25 +202,35 @@ def range_flag(device) -> torch.Tensor:
 
 
 _PERSISTENT_WARNED = False
+_LOCAL = threading.local()  # per thread: .capturing; .depth[device] > 0 while a checked forward_loop / forward runs for that device
 
 
-def persistent_loop_gave_up(device) -> bool:
-    """After a persistent particle-filter loop: did it abort (bit 2 of the range flag: a hand-off's bounded spin ran
-    out because a workgroup of the launch was not resident, e.g. another process shares the GPU)?  Clears the bit,
-    switches the persistent form off for the rest of the process and warns once; the caller re-runs the loop as a
-    loop of launches.  One 4-byte device->host read."""
+@contextlib.contextmanager
+def persistent_forms(pf=None, ekf=None, lstm=None):
+    """Set the given persistent-form switches (``None``: as it is) and re-arm the give-up warning; on exit all three
+    switches and the warning latch are what they were, whatever gave up inside."""
     global PF_PERSISTENT, EKF_PERSISTENT, LSTM_PERSISTENT, _PERSISTENT_WARNED
-    flag = _RANGE_FLAGS.get(str(device))
-    if flag is None:
+    saved = (PF_PERSISTENT, EKF_PERSISTENT, LSTM_PERSISTENT, _PERSISTENT_WARNED)
+    PF_PERSISTENT, EKF_PERSISTENT, LSTM_PERSISTENT = (old if new is None else bool(new)
+                                                      for new, old in zip((pf, ekf, lstm), saved))
+    _PERSISTENT_WARNED = False
+    try:
+        yield
+    finally:
+        PF_PERSISTENT, EKF_PERSISTENT, LSTM_PERSISTENT, _PERSISTENT_WARNED = saved
+
+
+def _gave_up(flag: torch.Tensor) -> bool:
+    """After a persistent launch: did it abort (``FLAG_GAVE_UP``: a hand-off's bounded spin ran out because a workgroup
+    of the launch was not resident, e.g. another process shares the GPU)?  Consumes that bit and leaves the others,
+    switches the persistent forms off for the rest of the process and warns once.  One 4-byte device->host read."""
+    global PF_PERSISTENT, EKF_PERSISTENT, LSTM_PERSISTENT, _PERSISTENT_WARNED
+    if not int(flag.item()) & _abi.FLAG_GAVE_UP:
         return False
-    bits = int(flag.item())
-    if not bits & 4:
-        return False
-    flag.bitwise_and_(~4)
+    flag.bitwise_and_(~_abi.FLAG_GAVE_UP)
     PF_PERSISTENT = EKF_PERSISTENT = LSTM_PERSISTENT = False
     if not _PERSISTENT_WARNED:
         _PERSISTENT_WARNED = True
-        import warnings
         warnings.warn("a persistent filter loop gave up waiting for a hand-off (a workgroup of its launch was not "
                       "resident -- is another process using this GPU?); this forward_loop is re-run as a loop of launches and the "
                       "persistent forms are switched off for this process (MMF_PF_PERSISTENT=0 MMF_EKF_PERSISTENT=0 "
@@ -225,28 +238,53 @@ def persistent_loop_gave_up(device) -> bool:
     return True
 
 
-def run_ekf_loop(a, mu: torch.Tensor, Sigma: torch.Tensor):
-    """``mmf_ekf_forward_loop`` on filled ``MmfEkfLoopArgs`` (``mu`` / ``Sigma``: its in / out belief tensors): as ONE
-    persistent launch where the problem is eligible (``EKF_PERSISTENT``), with the loop of launches as the fallback if a
-    hand-off of that launch timed out (the belief is restored first)."""
-    import ctypes
-
-    dev = mu.device
-    keep = None
-    if (EKF_PERSISTENT and not CAPTURING and a.T > 0 and a.d in (2, 3) and a.n_res_dyn == 3
-            and _abi.ekf_persistent_plan(a.N, a.K) > 0):
-        n_words = _abi.ekf_persistent_sync_words(a.N, a.K, a.d)
-        sync = torch.empty(n_words, dtype=torch.int32, device=dev)  # tagged granules of the hand-offs (zeroed by the call)
-        keep = (sync, mu.clone(), Sigma.clone()) if a.K > 1 else (sync, None, None)  # (one sub-filter: no hand-offs, nothing can time out)
-        a.persistent, a.n_sync_words = 1, n_words
-        a.sync_words = ctypes.c_void_p(_abi.ptr(sync, dtype=torch.int32))
-        a.range_flag = ctypes.c_void_p(_abi.ptr(range_flag(dev), dtype=torch.int32))  # bit 2: "a hand-off timed out"
-    _abi.ekf_forward_loop(a, mu)
-    if a.persistent and a.K > 1 and persistent_loop_gave_up(dev):
-        mu.copy_(keep[1])
-        Sigma.copy_(keep[2])
+def run_persistent(a, call, *, n_sync_words: int, device, restore=()):
+    """The host protocol of every persistent loop.  ``call()`` runs the C entry point on the filled args struct ``a`` and
+    returns its result.  ``n_sync_words == 0``: not eligible -> one plain call.  Otherwise the hand-off words (zeroed by
+    the call) and the status word are attached, ``a.persistent`` is set and the call made; if that launch gave up
+    (``FLAG_GAVE_UP``), the ``restore`` tensors -- what the call updates in place -- get back what they held,
+    ``a.persistent`` is cleared and the call is made again as launches.  ``restore=None``: a launch without hand-offs,
+    which cannot give up -> no copies and NO host read."""
+    if not n_sync_words:
+        return call()
+    sync = torch.empty(n_sync_words, dtype=torch.int32, device=device)  # (it and the copies live until both calls are enqueued)
+    flag = range_flag(device)
+    a.persistent, a.n_sync_words = 1, n_sync_words
+    a.sync_words, a.range_flag = ctypes.c_void_p(sync.data_ptr()), ctypes.c_void_p(flag.data_ptr())
+    saved = None if restore is None else [t.clone() for t in restore]
+    out = call()
+    if saved is not None and _gave_up(flag):
+        for t, was in zip(restore, saved):
+            t.copy_(was)
         a.persistent = 0
-        _abi.ekf_forward_loop(a, mu)
+        out = call()
+    return out
+
+
+def run_ekf_loop(nets, biases, q, z, r, mu, Sigma, *, fusion=0, feedback=0, fuse_w=None, gate=None):
+    """``mmf_ekf_forward_loop`` for ``K = len(nets)`` sub-filters: ``nets`` their dynamics networks (``PackedParticleNet``),
+    ``biases`` the hoisted control terms ``(T*N, 64)``, ``q (K, d, d)``, ``z (T, K, N, d)``, ``r (T, K, N, d, d)``,
+    ``mu (K, N, d)`` / ``Sigma (K, N, d, d)`` the belief, updated in place -> ``(estimates (T, N, d), Sigma_f | None)``.
+    ONE persistent launch where the problem is eligible (``EKF_PERSISTENT``), else / after a give-up 2 T launches."""
+    T, K, N, d = z.shape
+    E = lambda *shape: torch.empty(shape, dtype=torch.float32, device=mu.device)
+    mu_pred, A, est, Sigma_f = torch.empty_like(mu), torch.empty_like(Sigma), E(T, N, d), (E(N, d, d) if fusion else None)
+    P, prec = _abi.vp, nets[0].precision_code()
+    a = _abi.MmfEkfLoopArgs()
+    a.T, a.N, a.d, a.K, a.fusion, a.feedback = T, N, d, K, fusion, feedback
+    a.n_res_dyn, a.precision = nets[0].n_res, prec
+    a.range_flag = P(range_flag(mu.device), torch.int32) if prec != _abi.PREC_F32 else None
+    for k in range(K):
+        a.dyn_packed[k], a.dyn_bias[k] = P(nets[k].blob(prec)), P(biases[k])
+    a.q_tril, a.z, a.r_tril, a.fuse_w, a.feedback_gate = P(q), P(z), P(r), P(fuse_w), P(gate, torch.int32)
+    a.mu, a.Sigma, a.mu_pred, a.A, a.Sigma_f, a.estimates = P(mu), P(Sigma), P(mu_pred), P(A), P(Sigma_f), P(est)
+    go = (EKF_PERSISTENT and not is_capturing() and T > 0 and d in (2, 3) and a.n_res_dyn == 3
+          and _abi.ekf_persistent_plan(N, K) > 0)
+    n_words = _abi.ekf_persistent_sync_words(N, K, d) if go else 0
+    # (one sub-filter: no hand-offs, nothing can time out -> nothing to copy, nothing to ask)
+    run_persistent(a, lambda: _abi.ekf_forward_loop(a, mu), n_sync_words=n_words, device=mu.device,
+                   restore=(mu, Sigma) if K > 1 else None)
+    return est, Sigma_f
 
 
 class PackedLstm:
@@ -291,8 +329,8 @@ def packed_lstm(lstm: nn.LSTM) -> PackedLstm:
 def run_lstm_loop(packed: PackedLstm, x: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor):
     """``mmf_lstm_forward``: ``x (T, N, in_dim)``, ``h0`` / ``c0 (2, N, 512)`` -> ``(h2 (T, N, 512), hT, cT)``, as ONE
     persistent launch where the problem is eligible (``LSTM_PERSISTENT``, nothing being captured), with the loop of
-    launches as the fallback.  If a hand-off of the persistent launch timed out (bit 2 of the range flag) the call is run
-    again as launches: the kernel never writes its inputs, so ``h0`` / ``c0`` are still the initial state."""
+    launches as the fallback.  If a hand-off of the persistent launch timed out the call is run again as launches with
+    nothing to restore: the kernel never writes its inputs, so ``h0`` / ``c0`` are still the initial state."""
     require_device(x, "run_lstm_loop")
     T, N, _ = x.shape
     dev = x.device
@@ -303,42 +341,51 @@ def run_lstm_loop(packed: PackedLstm, x: torch.Tensor, h0: torch.Tensor, c0: tor
     assert h0.shape == c0.shape == (_abi.LSTM_LAYERS, N, H)
     h2 = torch.empty((T, N, H), dtype=torch.float32, device=dev)
     hT, cT = torch.empty_like(h0), torch.empty_like(c0)
-    n_words = _abi.lstm_sync_words(N)
-    sync = torch.empty(n_words, dtype=torch.int32, device=dev)  # abort word, progress words, granules (zeroed by the call)
+    n_words = _abi.lstm_sync_words(N)  # abort word, progress words, granules (zeroed by the call)
+    P = _abi.vp
     a = _abi.MmfLstmArgs()
     a.T, a.N, a.in_dim = T, N, packed.in_dim
-    a.persistent = int(LSTM_PERSISTENT and not CAPTURING and T > 0 and _abi.lstm_persistent_plan(N, T) > 0)
-    P = lambda t: ctypes.c_void_p(t.data_ptr())
     a.x, a.h0, a.c0, a.hT, a.cT, a.h2, a.packed = P(x), P(h0), P(c0), P(hT), P(cT), P(h2), P(packed.blob())
-    a.range_flag = P(range_flag(dev))
-    a.sync_words, a.n_sync_words = P(sync), n_words
-    _abi.lstm_forward(a, x)
-    if a.persistent and persistent_loop_gave_up(dev):
-        a.persistent = 0
-        _abi.lstm_forward(a, x)
+    go = LSTM_PERSISTENT and not is_capturing() and T > 0 and _abi.lstm_persistent_plan(N, T) > 0
+    if not go:  # the launches hand the hidden states over through the same words (and are given the status word alike)
+        sync = torch.empty(n_words, dtype=torch.int32, device=dev)
+        a.sync_words, a.n_sync_words, a.range_flag = P(sync, torch.int32), n_words, P(range_flag(dev), torch.int32)
+    run_persistent(a, lambda: _abi.lstm_forward(a, x), n_sync_words=n_words if go else 0, device=dev)
     return h2, hT, cT
 
 
-# While a training step is being captured into a hipGraph (train.GraphedFilterStep) nothing may read the device: the checks
-# that cost a host read -- the range flag at the end of a forward_loop, "covariance not positive definite" in
-# initialize_beliefs -- only accumulate in the range flag (bits 1 / 16) and are read ONCE after every replay.
-CAPTURING = False
+@contextlib.contextmanager
+def capturing():
+    """While a training step is being captured into a hipGraph (``train.GraphedFilterStep``) nothing on the capturing thread
+    may read the device: the checks that cost a host read -- the status word at the end of a forward_loop, "covariance
+    not positive definite" in initialize_beliefs -- only accumulate in the status word (``FLAG_RANGE`` / ``FLAG_NOT_PD``)
+    and are read ONCE after every replay; no loop goes persistent."""
+    was = is_capturing()
+    _LOCAL.capturing = True
+    try:
+        yield
+    finally:
+        _LOCAL.capturing = was
+
+
+def is_capturing() -> bool:
+    return getattr(_LOCAL, "capturing", False)
 
 
 def check_range(device):
-    """Raise if any f16x3 launch since the last check saturated its operand split (one
-    4-byte device->host read; filters call it once per ``forward_loop`` / on demand)."""
+    """Raise what the status word reports since the last check (one 4-byte device->host read; filters call it once per
+    ``forward_loop`` / on demand) and clear it."""
     flag = _RANGE_FLAGS.get(str(device))
     bits = 0 if flag is None else int(flag.item())
-    if bits & 16:
+    if bits & _abi.FLAG_NOT_PD:
         flag.zero_()
         raise ValueError("initialize_beliefs: covariance is not positive definite (reported by a captured training step)")
-    if bits & 4:
+    if bits & _abi.FLAG_GAVE_UP:
         flag.zero_()
         raise _abi.MmfError(
-            "the persistent particle-filter loop gave up waiting for a hand-off (a workgroup of its launch was not "
+            "a persistent loop gave up waiting for a hand-off (a workgroup of its launch was not "
             "resident -- is another process using this GPU?): results of this forward_loop are invalid; "
-            "MMF_PF_PERSISTENT=0 selects the launch-per-step loop")
+            "MMF_PF_PERSISTENT=0 MMF_EKF_PERSISTENT=0 MMF_LSTM_PERSISTENT=0 select the loops of launches")
     if bits != 0:
         flag.zero_()
         raise _abi.MmfError(
@@ -346,14 +393,7 @@ def check_range(device):
             "filter steps are invalid; set MMF_PRECISION=f32 / engine.set_default_precision('f32')")
 
 
-import threading
-
-_CHECK = threading.local()  # .depth[device]: > 0 while a checked forward_loop / forward is running ON THIS THREAD for that device
-
-
 def _checked(fn, *, step: bool):
-    import functools
-
     @functools.wraps(fn)
     def wrapper(self, *args, **kwargs):
         dev = None
@@ -366,11 +406,11 @@ def _checked(fn, *, step: bool):
         # hands the flag to mmf_image_convs_train_forward), in which case the step is checked like any other
         if dev is None or dev.type != "cuda" or (step and use_autograd(self) and training_image_precision_code() == _abi.PREC_F32):
             return fn(self, *args, **kwargs)
-        if CAPTURING:  # a hipGraph capture: no host read; the flag accumulates and is read after the replay
+        if is_capturing():  # a hipGraph capture: no host read; the flag accumulates and is read after the replay
             return fn(self, *args, **kwargs)
-        depth = getattr(_CHECK, "depth", None)
+        depth = getattr(_LOCAL, "depth", None)
         if depth is None:
-            depth = _CHECK.depth = {}
+            depth = _LOCAL.depth = {}
         key = str(dev)
         if depth.get(key, 0) > 0:  # an enclosing checked call on this thread and device owns the check
             return fn(self, *args, **kwargs)
@@ -457,7 +497,7 @@ class PackedParticleNet:
         dev = src[0].device
         require_device(src[0], "PackedParticleNet")
         keep = [t.detach().to(torch.float32).contiguous() for t in src]
-        P = lambda t: ctypes.c_void_p(t.data_ptr())
+        P = _abi.vp
         d = _abi.MmfParticleNetDesc()
         d.d_in, d.n_res, d.relu_after_join, d.n_out = self.d_in, self.n_res, int(self.relu_after_join), self.n_out
         d.join_in, d.join_state_off = self.join.in_features, self.join_state_off
@@ -490,7 +530,7 @@ class PackedParticleNet:
         for i in range(self.n_res):
             keep += [T(src[7 + 4 * i]), T(src[9 + 4 * i])]
         keep += [f32(src[-2]).contiguous(), f32(src[-1]).contiguous(), zeros]
-        P = lambda t: ctypes.c_void_p(t.data_ptr())
+        P = _abi.vp
         d = _abi.MmfParticleNetDesc()
         d.d_in, d.n_res, d.relu_after_join, d.n_out = self.d_in, self.n_res, int(self.relu_after_join), self.n_out
         d.join_in, d.join_state_off = _abi.MMF_UNITS, 0
@@ -652,7 +692,7 @@ class PfTrainLoopFunction(torch.autograd.Function):
                     loglik=torch.empty((N, M), dtype=torch.float32, device=dev),
                     ll_steps=torch.empty((T, K, N, M), dtype=torch.float32, device=dev))
         a = _abi.MmfPfTrainArgs()
-        P = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        P = _abi.vp
         a.T, a.N, a.M, a.d, a.n_meas = T, N, M, d, K
         a.n_res_dyn, a.n_res_meas, a.logw_stride = dyn_net.n_res, meas[0][0].n_res, K_all
         # forward pass in the engine's arithmetic mode (f16x3 by default: the inference kernels); the backward
@@ -669,7 +709,7 @@ class PfTrainLoopFunction(torch.autograd.Function):
         a.dyn_bias, a.noise, a.scale_tril = P(keep["dyn_bias"]), P(keep["eps"]), P(keep["tril"])
         a.states, a.logw, a.estimates = P(states), P(logw), P(est)
         a.loglik, a.ll_steps = P(keep["loglik"]), P(keep["ll_steps"])
-        a.range_flag = ctypes.c_void_p(range_flag(dev).data_ptr())
+        a.range_flag = P(range_flag(dev), torch.int32)
         _abi.pf_train_forward(a, states)
         ctx.nets, ctx.shape, ctx.keep, ctx.blobs = nets, (T, N, M, d), keep, blobs
         ctx.fwd_blobs, ctx.fwd_precision = fwd_blobs, int(a.precision)
@@ -694,7 +734,7 @@ class PfTrainLoopFunction(torch.autograd.Function):
         nets = [dyn_net] + [m for m, _ in meas]
         NLmax = max(3 + 2 * n.n_res for n in nets)
         E = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        P = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        P = _abi.vp
         a = _abi.MmfPfTrainArgs()
         a.T, a.N, a.M, a.d, a.n_meas = T, N, M, d, K
         a.n_res_dyn, a.n_res_meas, a.logw_stride = dyn_net.n_res, meas[0][0].n_res, K_all
@@ -747,7 +787,8 @@ class PfTrainLoopFunction(torch.autograd.Function):
         a.dyn_bias, a.noise, a.scale_tril, a.g_estimates = P(keep["dyn_bias"]), P(keep["eps"]), P(keep["tril"]), P(g_est)
         a.states, a.logw, a.estimates = P(keep["states"]), P(keep["logw"]), P(keep["est"])
         a.loglik, a.ll_steps = P(keep["loglik"]), P(keep["ll_steps"])
-        a.stash, a.mask, a.dz, a.raw, a.d_raw, a.d_tmp = (P(scratch[k]) for k in ("stash", "mask", "dz", "raw", "d_raw", "d_tmp"))
+        a.stash, a.dz, a.mask = P(scratch["stash"], torch.float16), P(scratch["dz"], torch.float16), P(scratch["mask"], torch.int32)
+        a.raw, a.d_raw, a.d_tmp = (P(scratch[k]) for k in ("raw", "d_raw", "d_tmp"))
         a.dz_scale = P(scratch["dz_scale"])
         a.g_states_a, a.g_states_b, a.g_logw_a, a.g_logw_b = P(scratch["ga"]), P(scratch["gb"]), P(scratch["la"]), P(scratch["lb"])
         a.d_states0, a.d_logw0 = P(scratch["d_states0"]), P(scratch["d_logw0"])
@@ -972,7 +1013,7 @@ class PackedImageEncoder:
     def _pack(self, src) -> torch.Tensor:
         require_device(src[0], "PackedImageEncoder")
         keep = [t.detach().to(torch.float32).contiguous() for t in src]
-        P = lambda t: ctypes.c_void_p(t.data_ptr())
+        P = _abi.vp
         d = _abi.MmfImageEncoderDesc()
         for i in range(5):
             d.conv_w[i], d.conv_b[i] = P(keep[i]), P(keep[5 + i])
@@ -993,7 +1034,7 @@ class PackedImageEncoder:
         keep = [t.detach().to(torch.float32).contiguous() for t in src]
         d = _abi.MmfImageEncoderDesc()
         for i, t in enumerate(keep):
-            d.conv_w[1 + i] = ctypes.c_void_p(t.data_ptr())
+            d.conv_w[1 + i] = _abi.vp(t)
         d.variant = _abi.ENCODER_DEFAULT
         blob = torch.empty(_abi.image_convs_backward_floats(), dtype=torch.float32, device=src[0].device)
         _abi.pack_image_convs_backward(d, blob)

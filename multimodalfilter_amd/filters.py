@@ -12,7 +12,6 @@ itself running in hand-written HIP: ``mmf_pf_init_particles`` for the initial be
 (``mmf_pf_forward_loop`` / ``mmf_ekf_forward_loop``) behind ``forward_loop``.
 Step order follows upstream torchfilter.
 """
-import ctypes
 import math
 from typing import Optional
 
@@ -92,8 +91,8 @@ class ParticleFilter(base.Filter):
             _abi.pf_init_particles(mean.detach().to(torch.float32).contiguous(),
                                    covariance.detach().to(torch.float32).contiguous(),
                                    eps.to(torch.float32).contiguous(), states, logw, not_pd)
-            if engine.CAPTURING:  # no host read inside a hipGraph capture: bit 16 of the range flag, read after the replay
-                engine.range_flag(mean.device).bitwise_or_(not_pd.ne(0).to(torch.int32) * 16)
+            if engine.is_capturing():  # no host read inside a hipGraph capture: FLAG_NOT_PD in the status word, read after the replay
+                engine.range_flag(mean.device).bitwise_or_(not_pd.ne(0).to(torch.int32) * _abi.FLAG_NOT_PD)
             elif int(not_pd.item()):
                 raise ValueError("initialize_beliefs: covariance is not positive definite")
             self.particle_states, self.particle_log_weights = states, logw
@@ -309,7 +308,7 @@ class ParticleFilter(base.Filter):
         est = torch.empty((T, N, d), dtype=torch.float32, device=dev)
         tril = dyn.scale_tril().contiguous()
         keep = [nets, eps, u, tril]  # keep every operand alive until the launches are enqueued
-        P = lambda t: None if t is None else ctypes.c_void_p(_abi.ptr(t))
+        P = _abi.vp
         a = _abi.MmfPfLoopArgs()
         a.T, a.N, a.M, a.d, a.n_meas, a.resample_mode = T, N, M, d, len(nets), mode
         a.precision = dyn._net.precision_code()
@@ -331,8 +330,8 @@ class ParticleFilter(base.Filter):
             a.loglik_steps = P(self.last_log_likelihoods)
             if mode != 0:
                 self.last_resample_indices = torch.empty((T, N, M), dtype=torch.int32, device=dev)
-                a.indices_steps = ctypes.c_void_p(_abi.ptr(self.last_resample_indices, dtype=torch.int32))
-        a.range_flag = ctypes.c_void_p(engine.range_flag(dev).data_ptr())
+                a.indices_steps = P(self.last_resample_indices, torch.int32)
+        a.range_flag = P(engine.range_flag(dev), torch.int32)
         if do_resample and self.soft_resample_alpha < 1.0:
             a.soft_alpha = float(self.soft_resample_alpha)  # survivors carry importance weights (mmf_pf_reweight_resample_soft)
         if self.estimation_method == "argmax":
@@ -340,33 +339,22 @@ class ParticleFilter(base.Filter):
             keep.append(est_scratch)
             a.estimate_argmax, a.estimate_scratch = 1, P(est_scratch)
         timer = engine.kernel_timer()
-        if (engine.PF_PERSISTENT and mode == 1 and timer is None and not self.record_indices
-                and a.soft_alpha == 0.0 and not a.estimate_argmax and d in (2, 3)
-                and dyn._net.n_res == 3 and all(net.n_res == 2 for net, _b, _l in nets)
-                and _abi.pf_persistent_plan(N, M, len(nets)) > 0):
-            # small problem: ONE launch for all T steps (csrc/pf_persistent.inc); same bits as the loop of launches
-            n_words = _abi.pf_persistent_sync_words(N, M, d, len(nets))
-            sync = torch.empty(n_words, dtype=torch.int32, device=dev)  # tagged granules of the hand-offs (zeroed by the call)
-            keep.append(sync)
-            a.persistent, a.n_sync_words = 1, n_words
-            a.sync_words = ctypes.c_void_p(_abi.ptr(sync, dtype=torch.int32))
-            # the persistent launch needs ALL its workgroups resident; if it gives up (another process on this GPU),
-            # the loop is re-run from this copy of the belief as a loop of launches -- see below
-            belief_backup = (states_a.clone(), logw_a.clone())
+        # small problem: ONE launch for all T steps (csrc/pf_persistent.inc); same bits as the loop of launches
+        go = (engine.PF_PERSISTENT and mode == 1 and timer is None and not self.record_indices
+              and a.soft_alpha == 0.0 and not a.estimate_argmax and d in (2, 3)
+              and dyn._net.n_res == 3 and all(net.n_res == 2 for net, _b, _l in nets)
+              and _abi.pf_persistent_plan(N, M, len(nets)) > 0)
         events = None
         names = ["particle_net_dynamics"] + ["particle_net_measure"] * len(nets) + ["pf_reweight_resample"]
         stride = 1
         if timer is not None:
             stride = max(1, int(timer.loop_stride))
             events = timer.loop_events(2 * len(names) * len(range(stride // 2, T, stride)))  # pf_loop.hip samples t % stride == stride // 2
-        loc = _abi.pf_forward_loop(a, like, events, stride)
-        if a.persistent and engine.persistent_loop_gave_up(dev):
-            # bounded spins ran out (a workgroup of the launch was not resident): nothing of this call can be used.
-            # Restore the belief, take the launch-per-step path for this call and for the rest of the process.
-            states_a.copy_(belief_backup[0])
-            logw_a.copy_(belief_backup[1])
-            a.persistent = 0
-            loc = _abi.pf_forward_loop(a, like, events, stride)
+        # the persistent launch needs ALL its workgroups resident; if it gives up (another process on this GPU) the belief
+        # is restored and the loop re-run as launches, for this call and for the rest of the process (engine.run_persistent)
+        loc = engine.run_persistent(a, lambda: _abi.pf_forward_loop(a, like, events, stride), device=dev,
+                                    n_sync_words=_abi.pf_persistent_sync_words(N, M, d, len(nets)) if go else 0,
+                                    restore=(states_a, logw_a))
         if timer is not None:
             R = N * M
             dflops = 2.0 * R * engine.particle_net_macs(d, dyn._net.n_res, dyn._net.n_out)
@@ -596,20 +584,7 @@ class VirtualSensorExtendedKalmanFilter(base.Filter):
         mu = self._belief_mean.reshape(1, N, d).contiguous().clone()
         Sigma = self._belief_covariance.reshape(1, N, d, d).contiguous().clone()
         q = dyn.scale_tril().to(torch.float32).reshape(1, d, d).contiguous()
-        mu_pred, A = torch.empty_like(mu), torch.empty_like(Sigma)
-        est = torch.empty((T, N, d), dtype=torch.float32, device=mu.device)
-        prec = dyn._net.precision_code()
-        blob = dyn._net.blob(prec)
-        P = lambda t: ctypes.c_void_p(_abi.ptr(t))
-        a = _abi.MmfEkfLoopArgs()
-        a.T, a.N, a.d, a.K, a.fusion, a.feedback = T, N, d, 1, 0, 0
-        a.n_res_dyn, a.precision = dyn._net.n_res, prec
-        a.range_flag = (ctypes.c_void_p(_abi.ptr(engine.range_flag(mu.device), dtype=torch.int32))
-                        if prec != _abi.PREC_F32 else None)
-        a.dyn_packed[0], a.dyn_bias[0] = P(blob), P(ctrl_all["bias"])
-        a.q_tril, a.z, a.r_tril = P(q), P(z), P(r)
-        a.mu, a.Sigma, a.mu_pred, a.A, a.estimates = P(mu), P(Sigma), P(mu_pred), P(A), P(est)
-        engine.run_ekf_loop(a, mu, Sigma)
+        est, _ = engine.run_ekf_loop([dyn._net], [ctrl_all["bias"]], q, z, r, mu, Sigma)
         self._belief_mean, self._belief_covariance = mu[0], Sigma[0]
         return est
 

@@ -123,16 +123,12 @@ class GraphedFilterStep:
         self.optimizer.zero_grad(set_to_none=True)
         torch.autograd.graph.increment_version(self._params())
         engine.clear_range(dev)
-        engine.CAPTURING = True
-        try:
-            with torch.cuda.graph(self.graph, stream=self.stream):
-                loss = filter_loss(self.model, self.static, initial_covariance=self.cov, noise=self.noise,
-                                   measurement_initialize=self.measurement_initialize, initial_scale_tril=self.tril)
-                loss.backward()
-                self.optimizer.step()
-                self.loss = loss.detach()
-        finally:
-            engine.CAPTURING = False
+        with engine.capturing(), torch.cuda.graph(self.graph, stream=self.stream):
+            loss = filter_loss(self.model, self.static, initial_covariance=self.cov, noise=self.noise,
+                               measurement_initialize=self.measurement_initialize, initial_scale_tril=self.tril)
+            loss.backward()
+            self.optimizer.step()
+            self.loss = loss.detach()
 
     def __call__(self, batch: Dict[str, torch.Tensor]) -> float:
         if self.stream is None:

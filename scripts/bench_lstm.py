@@ -33,35 +33,35 @@ def leg(form: str, N: int, T: int, reps: int) -> dict:
     from multimodalfilter_amd.door_models import DoorLSTMFilter
 
     dev = torch.device("cuda:0")
-    engine.LSTM_PERSISTENT = form == "persistent"
-    torch.manual_seed(0)
-    model = DoorLSTMFilter().to(dev).eval()
-    traj = {k: v.to(dev) for k, v in synthetic.make_trajectories(state_dim=3, T=T, N=N, seed=1).items()}
-    if form == "torch":
-        def run():
-            with torch.no_grad():
-                obs = {k: traj[k][1:] for k in ("image", "gripper_pos", "gripper_sensors")}
-                hidden = (torch.zeros(2, N, 512, device=dev), torch.zeros(2, N, 512, device=dev))
-                feat = model.observation_image_layers(obs["image"].reshape(T * N, 1, 32, 32)).reshape(T, N, 64)
-                merged = torch.cat((feat, model.observation_pos_layers(obs["gripper_pos"]),
-                                    model.observation_sensors_layers(obs["gripper_sensors"]),
-                                    model.control_layers(traj["controls"][1:])), dim=-1)
-                out, _ = model.lstm(model.fusion_layers(merged), hidden)
-                return model.output_layers(out)
-    else:
-        def run():
-            return evaluation.run_filter(model, traj)
-    for _ in range(2):
-        run()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        run()
-        e.record()
+    with engine.persistent_forms(lstm=form == "persistent"):
+        torch.manual_seed(0)
+        model = DoorLSTMFilter().to(dev).eval()
+        traj = {k: v.to(dev) for k, v in synthetic.make_trajectories(state_dim=3, T=T, N=N, seed=1).items()}
+        if form == "torch":
+            def run():
+                with torch.no_grad():
+                    obs = {k: traj[k][1:] for k in ("image", "gripper_pos", "gripper_sensors")}
+                    hidden = (torch.zeros(2, N, 512, device=dev), torch.zeros(2, N, 512, device=dev))
+                    feat = model.observation_image_layers(obs["image"].reshape(T * N, 1, 32, 32)).reshape(T, N, 64)
+                    merged = torch.cat((feat, model.observation_pos_layers(obs["gripper_pos"]),
+                                        model.observation_sensors_layers(obs["gripper_sensors"]),
+                                        model.control_layers(traj["controls"][1:])), dim=-1)
+                    out, _ = model.lstm(model.fusion_layers(merged), hidden)
+                    return model.output_layers(out)
+        else:
+            def run():
+                return evaluation.run_filter(model, traj)
+        for _ in range(2):
+            run()
         torch.cuda.synchronize()
-        times.append(s.elapsed_time(e))
+        times = []
+        for _ in range(reps):
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            run()
+            e.record()
+            torch.cuda.synchronize()
+            times.append(s.elapsed_time(e))
     times.sort()
     return {"form": form, "N": N, "T": T, "ms_per_step": times[len(times) // 2] / T,
             "ms_per_step_min": times[0] / T, "reps": reps}

@@ -78,10 +78,8 @@ def eval_ekf_regime(args, dev, cls):
     obs = {k: traj[k][1:] for k in ("image", "gripper_pos", "gripper_sensors")}
     cov = (torch.eye(d, device=dev) * 0.1)[None].expand(N, d, d)
     out = {"regime": "eval_ekf", "filter": cls, "batch": N, "steps": T}
-    old = engine.EKF_PERSISTENT
-    try:
-        for persistent in (True, False):
-            engine.EKF_PERSISTENT = persistent
+    for persistent in (True, False):
+        with engine.persistent_forms(ekf=persistent):
             times = []
             for it in range(args.eval_repeats + 1):
                 f.initialize_beliefs(mean=traj["states"][0], covariance=cov)
@@ -94,8 +92,6 @@ def eval_ekf_regime(args, dev, cls):
             out[key] = {"ms_per_step": 1e3 * min(times[1:]) / T, "trajectory_steps_per_s": N * T / min(times[1:])}
             out.setdefault("estimates", est.clone())
             out["same_bits"] = bool(torch.equal(out["estimates"], est))
-    finally:
-        engine.EKF_PERSISTENT = old
     del out["estimates"]
     return out
 

@@ -25,9 +25,9 @@ for cls, tname, prec in (("DoorKalmanFilter", "door", "f16x3"), ("DoorKalmanFilt
     f = mmf.model_types(tname)[cls]().to(dev).eval()
     outs = {}
     for persistent in (False, True):
-        engine.EKF_PERSISTENT = persistent
-        f.initialize_beliefs(mean=x0, covariance=cov)
-        outs[persistent] = f.forward_loop(observations=obs, controls=ctrl)
+        with engine.persistent_forms(ekf=persistent):
+            f.initialize_beliefs(mean=x0, covariance=cov)
+            outs[persistent] = f.forward_loop(observations=obs, controls=ctrl)
         subs = list(f.filter_models) if hasattr(f, "filter_models") else [f]
         outs[(persistent, "S")] = torch.stack([m._belief_covariance for m in subs])
     a, b = outs[False], outs[True]

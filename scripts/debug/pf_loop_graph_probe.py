@@ -13,7 +13,6 @@ import multimodalfilter_amd as mmf  # noqa: E402
 from multimodalfilter_amd import _abi, engine, synthetic  # noqa: E402
 
 dev = torch.device("cuda:0")
-engine.PF_PERSISTENT = False
 for N, M, T in ((256, 4096, 64), (256, 1024, 64), (32, 4096, 64)):
     torch.manual_seed(0)
     f = mmf.door_models.DoorCrossmodalParticleFilter().to(dev).eval()
@@ -59,7 +58,8 @@ for N, M, T in ((256, 4096, 64), (256, 1024, 64), (32, 4096, 64)):
 
     _abi.pf_forward_loop = probe
     try:
-        bench.run_pf(f, traj, noise, M)
+        with engine.persistent_forms(pf=False):
+            bench.run_pf(f, traj, noise, M)
     finally:
         _abi.pf_forward_loop = real
     print(result.get("line", "no loop of >= 32 steps seen"), flush=True)

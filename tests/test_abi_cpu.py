@@ -29,6 +29,15 @@ def test_library_exports_every_declared_symbol():
     assert _abi.load().mmf_version() == _abi.ABI_VERSION
 
 
+def test_status_word_names_of_header_and_binding_agree():
+    from multimodalfilter_amd import _abi
+
+    text = open(os.path.join(ROOT, "include", "mmf.h")).read()
+    flags = {name: int(value) for name, value in re.findall(r"^#define MMF_FLAG_(\w+)\s+(\d+)\s*$", text, re.M)}
+    assert flags == {"RANGE": _abi.FLAG_RANGE, "GAVE_UP": _abi.FLAG_GAVE_UP, "NOT_PD": _abi.FLAG_NOT_PD}
+    assert sorted(flags.values()) == [1, 4, 16]  # distinct bits; 2 is unused
+
+
 def test_size_queries_need_no_gpu():
     from multimodalfilter_amd import _abi
 

@@ -111,16 +111,14 @@ def _run_forms(N, T, seed=0):
         taken.append(int(a.persistent))
         return real(a, like)
 
-    old = engine.LSTM_PERSISTENT
     _abi.lstm_forward = spy
     try:
-        engine.LSTM_PERSISTENT = True
-        pers = engine.run_lstm_loop(packed, x, h0, c0)
-        engine.LSTM_PERSISTENT = False
-        launches = engine.run_lstm_loop(packed, x, h0, c0)
+        with engine.persistent_forms(lstm=True):
+            pers = engine.run_lstm_loop(packed, x, h0, c0)
+        with engine.persistent_forms(lstm=False):
+            launches = engine.run_lstm_loop(packed, x, h0, c0)
     finally:
         _abi.lstm_forward = real
-        engine.LSTM_PERSISTENT = old
     with torch.no_grad():
         want, (hw, cw) = lstm(x, (h0, c0))
     return taken, pers, launches, (want, hw, cw)
@@ -166,45 +164,41 @@ def test_persistent_lstm_that_gives_up_is_rerun_as_a_loop_of_launches():
     inp = _inputs(T, N, 9, dev)
     d = f.state_dim
     cov = torch.eye(d, device=dev)[None].expand(N, d, d)
-    old_persist, old_warned = engine.LSTM_PERSISTENT, engine._PERSISTENT_WARNED
-    old_pf, old_ekf = engine.PF_PERSISTENT, engine.EKF_PERSISTENT
-    try:
-        def run(persistent, sabotage):
-            engine.LSTM_PERSISTENT, engine._PERSISTENT_WARNED = persistent, False
-            taken = []
-            real = _abi.lstm_forward
 
-            def spy(a, like):
-                taken.append(int(a.persistent))
-                real(a, like)
-                if sabotage and a.persistent:  # what an aborted launch leaves behind: garbage and the abort bit
-                    torch.cuda.synchronize()
-                    for name, rows in (("h2", T), ("hT", 2), ("cT", 2)):
-                        ctypes_fill(getattr(a, name), rows * N * 512)
-                    engine.range_flag(dev).bitwise_or_(4)
+    def run(sabotage):
+        taken = []
+        real = _abi.lstm_forward
 
-            _abi.lstm_forward = spy
-            try:
-                f.initialize_beliefs(mean=torch.zeros(N, d, device=dev), covariance=cov)
-                with warnings.catch_warnings(record=True) as caught:
-                    warnings.simplefilter("always")
-                    out = _call(f, inp)
-                    out2 = _call(f, inp)
-            finally:
-                _abi.lstm_forward = real
-            return taken, out, out2, [t.clone() for t in f.lstm_hidden], caught
+        def spy(a, like):
+            taken.append(int(a.persistent))
+            real(a, like)
+            if sabotage and a.persistent:  # what an aborted launch leaves behind: garbage and the abort bit
+                torch.cuda.synchronize()
+                for name, rows in (("h2", T), ("hT", 2), ("cT", 2)):
+                    ctypes_fill(getattr(a, name), rows * N * 512)
+                engine.range_flag(dev).bitwise_or_(_abi.FLAG_GAVE_UP)
 
-        taken_ref, ref, ref2, hid_ref, _ = run(False, False)
-        taken, out, out2, hid, caught = run(True, True)
+        _abi.lstm_forward = spy
+        try:
+            f.initialize_beliefs(mean=torch.zeros(N, d, device=dev), covariance=cov)
+            with warnings.catch_warnings(record=True) as caught:
+                warnings.simplefilter("always")
+                out = _call(f, inp)
+                out2 = _call(f, inp)
+        finally:
+            _abi.lstm_forward = real
+        return taken, out, out2, [t.clone() for t in f.lstm_hidden], caught
+
+    with engine.persistent_forms(lstm=False):
+        taken_ref, ref, ref2, hid_ref, _ = run(False)
+    with engine.persistent_forms(lstm=True):
+        taken, out, out2, hid, caught = run(True)
         assert taken_ref == [0, 0]
         assert taken == [1, 0, 0], taken  # aborted persistent call, its rerun, then the next call on launches
         assert torch.equal(out, ref) and torch.equal(out2, ref2)
         assert all(torch.equal(a, b) for a, b in zip(hid, hid_ref))
         assert sum("gave up" in str(w.message) for w in caught) == 1
         assert engine.LSTM_PERSISTENT is False
-    finally:
-        engine.LSTM_PERSISTENT, engine._PERSISTENT_WARNED = old_persist, old_warned
-        engine.PF_PERSISTENT, engine.EKF_PERSISTENT = old_pf, old_ekf
 
 
 def ctypes_fill(address: int, n: int):

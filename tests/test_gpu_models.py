@@ -276,7 +276,7 @@ def test_kalman_filters_track_oracle(tname, cls, okw):
     engine.to(dev).eval()
     engine.initialize_beliefs(mean=x0.to(dev), covariance=cov.to(dev))
     got = engine.forward_loop(observations={k: v.to(dev) for k, v in obs.items()}, controls=ctrl.to(dev))
-    # element-wise relative (tests/_tol.py): every mean and covariance entry against its own magnitude
+    # norm-wise relative (tests/_tol.rel_err): every mean VECTOR and every covariance MATRIX against its own Frobenius norm
     assert rel_err(got, want) < REL_TOL, rel_err(got, want)
     subs_o = list(oracle.filter_models) if hasattr(oracle, "filter_models") else [oracle]
     subs_e = list(engine.filter_models) if hasattr(engine, "filter_models") else [engine]
@@ -351,48 +351,47 @@ def test_persistent_loop_that_gives_up_is_rerun_as_a_loop_of_launches():
 
     dev = torch.device("cuda:0")
     N, M, T, d = 8, 300, 5, 3
-    old_persist, old_warned = engine.PF_PERSISTENT, engine._PERSISTENT_WARNED
-    try:
-        torch.manual_seed(3)
-        f = mmf.door_models.DoorCrossmodalParticleFilter().to(dev).eval()
-        f.num_particles = M
-        traj = {k: v.to(dev) for k, v in synthetic.make_trajectories(state_dim=d, T=T + 1, N=N, seed=23).items()}
-        obs = {k: traj[k][1:] for k in ("image", "gripper_pos", "gripper_sensors")}
-        ctrl = traj["controls"][1:]
-        cov = (torch.eye(d, device=dev) * 0.1)[None].expand(N, d, d)
-        g = torch.Generator(device=dev).manual_seed(5)
-        eps0 = torch.randn((N, M, d), generator=g, device=dev)
-        eps = torch.randn((2 * T, N, M, d), generator=g, device=dev)
-        us = torch.rand((2 * T, N), generator=g, device=dev)
+    torch.manual_seed(3)
+    f = mmf.door_models.DoorCrossmodalParticleFilter().to(dev).eval()
+    f.num_particles = M
+    traj = {k: v.to(dev) for k, v in synthetic.make_trajectories(state_dim=d, T=T + 1, N=N, seed=23).items()}
+    obs = {k: traj[k][1:] for k in ("image", "gripper_pos", "gripper_sensors")}
+    ctrl = traj["controls"][1:]
+    cov = (torch.eye(d, device=dev) * 0.1)[None].expand(N, d, d)
+    g = torch.Generator(device=dev).manual_seed(5)
+    eps0 = torch.randn((N, M, d), generator=g, device=dev)
+    eps = torch.randn((2 * T, N, M, d), generator=g, device=dev)
+    us = torch.rand((2 * T, N), generator=g, device=dev)
 
-        def run(persistent, sabotage):
-            engine.PF_PERSISTENT, engine._PERSISTENT_WARNED = persistent, False
-            taken = []
-            real = _abi.pf_forward_loop
+    def run(sabotage):
+        taken = []
+        real = _abi.pf_forward_loop
 
-            def spy(a, like, *r, **k):
-                taken.append(int(a.persistent))
-                loc = real(a, like, *r, **k)
-                if sabotage and a.persistent:  # what an aborted launch leaves behind: garbage and the abort bit
-                    f.particle_states.fill_(float("nan"))
-                    f.particle_log_weights.fill_(0.0)
-                    engine.range_flag(dev).bitwise_or_(4)
-                return loc
+        def spy(a, like, *r, **k):
+            taken.append(int(a.persistent))
+            loc = real(a, like, *r, **k)
+            if sabotage and a.persistent:  # what an aborted launch leaves behind: garbage and the abort bit
+                f.particle_states.fill_(float("nan"))
+                f.particle_log_weights.fill_(0.0)
+                engine.range_flag(dev).bitwise_or_(_abi.FLAG_GAVE_UP)
+            return loc
 
-            _abi.pf_forward_loop = spy
-            try:
-                f.noise = mmf.StackedNoise(eps0, eps, us)
-                f.initialize_beliefs(mean=traj["states"][0], covariance=cov)
-                with warnings.catch_warnings(record=True) as caught:
-                    warnings.simplefilter("always")
-                    a = f.forward_loop(observations=obs, controls=ctrl)
-                    b = f.forward_loop(observations={k: v[:2] for k, v in obs.items()}, controls=ctrl[:2])
-                return taken, [str(w.message) for w in caught], a, b, f.particle_states.clone(), f.particle_log_weights.clone()
-            finally:
-                _abi.pf_forward_loop = real
+        _abi.pf_forward_loop = spy
+        try:
+            f.noise = mmf.StackedNoise(eps0, eps, us)
+            f.initialize_beliefs(mean=traj["states"][0], covariance=cov)
+            with warnings.catch_warnings(record=True) as caught:
+                warnings.simplefilter("always")
+                a = f.forward_loop(observations=obs, controls=ctrl)
+                b = f.forward_loop(observations={k: v[:2] for k, v in obs.items()}, controls=ctrl[:2])
+            return taken, [str(w.message) for w in caught], a, b, f.particle_states.clone(), f.particle_log_weights.clone()
+        finally:
+            _abi.pf_forward_loop = real
 
-        ref = run(False, False)
-        got = run(True, True)
+    with engine.persistent_forms(pf=False):
+        ref = run(False)
+    with engine.persistent_forms(pf=True):
+        got = run(True)
         assert ref[0] == [0, 0]
         assert got[0] == [1, 0, 0], got[0]          # persistent, its re-run, and a second call that does not try again
         assert len(got[1]) == 1 and "gave up" in got[1][0]
@@ -400,8 +399,6 @@ def test_persistent_loop_that_gives_up_is_rerun_as_a_loop_of_launches():
         for x, y in zip(ref[2:], got[2:]):
             assert torch.equal(x, y)
         engine.check_range(dev)                      # the abort bit was consumed: nothing left to raise
-    finally:
-        engine.PF_PERSISTENT, engine._PERSISTENT_WARNED = old_persist, old_warned
 
 
 @pytest.mark.parametrize("cls,N,M,T,precision,noise", [
@@ -430,7 +427,7 @@ def test_persistent_step_loop_equals_loop_of_launches(cls, N, M, T, precision, n
     dev = torch.device("cuda:0")
     tname = "door" if cls.startswith("Door") else "push"
     d = om.TASKS[tname].state_dim
-    old_prec, old_persist = engine.DEFAULT_PRECISION, engine.PF_PERSISTENT
+    old_prec = engine.DEFAULT_PRECISION
     engine.set_default_precision(precision)
     try:
         torch.manual_seed(3)
@@ -446,8 +443,7 @@ def test_persistent_step_loop_equals_loop_of_launches(cls, N, M, T, precision, n
         eps = torch.randn((T + 3, N, M, d), generator=g, device=dev)   # 1 + T + 2 steps are drawn below
         us = torch.rand((T + 3, N), generator=g, device=dev)
 
-        def run(persistent):
-            engine.PF_PERSISTENT = persistent
+        def run():
             taken = []
             real = _abi.pf_forward_loop
             _abi.pf_forward_loop = lambda a, *r, **k: (taken.append(int(a.persistent)), real(a, *r, **k))[1]
@@ -465,15 +461,16 @@ def test_persistent_step_loop_equals_loop_of_launches(cls, N, M, T, precision, n
             finally:
                 _abi.pf_forward_loop = real
 
-        ref = run(False)
-        got = run(True)
+        with engine.persistent_forms(pf=False):
+            ref = run()
+        with engine.persistent_forms(pf=True):
+            got = run()
         assert ref[0] == [0, 0, 0] and got[0] == [0, 1, 1], (ref[0], got[0])  # (the no-resampling step keeps the launches)
         for x, y in zip(ref[1:], got[1:]):
             assert torch.equal(x, y)
         assert bool(torch.isfinite(got[2]).all())
     finally:
         engine.set_default_precision(old_prec)
-        engine.PF_PERSISTENT = old_persist
 
 
 @pytest.mark.parametrize("cls,kw,masked", [
@@ -562,7 +559,7 @@ def test_persistent_ekf_loop_equals_loop_of_launches(cls, kw, N, T, precision):
     dev = torch.device("cuda:0")
     tname = "door" if cls.startswith("Door") else "push"
     d = om.TASKS[tname].state_dim
-    old_prec, old_persist = engine.DEFAULT_PRECISION, engine.EKF_PERSISTENT
+    old_prec = engine.DEFAULT_PRECISION
     engine.set_default_precision(precision)
     try:
         torch.manual_seed(5)
@@ -578,8 +575,7 @@ def test_persistent_ekf_loop_equals_loop_of_launches(cls, kw, N, T, precision):
             obs["image"][3, N - 1] = 0.0
         f = mmf.model_types(tname)[cls](**kw).to(dev).eval()
 
-        def run(persistent):
-            engine.EKF_PERSISTENT = persistent
+        def run():
             taken = []
             real = _abi.ekf_forward_loop
             _abi.ekf_forward_loop = lambda a, *r, **k: (taken.append(int(a.persistent)), real(a, *r, **k))[1]
@@ -594,8 +590,10 @@ def test_persistent_ekf_loop_equals_loop_of_launches(cls, kw, N, T, precision):
             finally:
                 _abi.ekf_forward_loop = real
 
-        ref = run(False)
-        got = run(True)
+        with engine.persistent_forms(ekf=False):
+            ref = run()
+        with engine.persistent_forms(ekf=True):
+            got = run()
         assert ref[0] == [0, 0] and got[0] == [1, 1], (ref[0], got[0])
         assert torch.equal(ref[1], got[1]) and torch.equal(ref[2], got[2])
         assert bool(torch.isfinite(got[1]).all())
@@ -605,7 +603,111 @@ def test_persistent_ekf_loop_equals_loop_of_launches(cls, kw, N, T, precision):
             assert torch.equal(ref[4], got[4])
     finally:
         engine.set_default_precision(old_prec)
-        engine.EKF_PERSISTENT = old_persist
+
+
+def _ekf_loop_inputs(N, T, d, dev, seed=41):
+    g = torch.Generator().manual_seed(seed)
+    obs = {"image": (torch.randn((T, N, 32, 32), generator=g) * 0.5).clamp(-1, 1).to(dev),
+           "gripper_pos": torch.randn((T, N, 3), generator=g).to(dev),
+           "gripper_sensors": torch.randn((T, N, 7), generator=g).to(dev)}
+    ctrl = torch.randn((T, N, 7), generator=g).to(dev)
+    x0 = torch.randn((N, d), generator=g).to(dev)
+    cov = (torch.eye(d) * 0.1)[None].expand(N, d, d).to(dev)
+    return obs, ctrl, x0, cov
+
+
+def test_persistent_ekf_loop_that_gives_up_is_rerun_as_a_loop_of_launches():
+    """The particle filter's give-up test for a crossmodal (K = 2) Kalman filter: the first (persistent) C call is followed
+    by a belief of NaN and ``FLAG_GAVE_UP`` -- ``engine.run_ekf_loop`` must restore ``mu`` / ``Sigma``, re-run the call as
+    launches, warn once and not try again; estimates and both sub-filters' beliefs equal the launch path's bit for bit.
+    (The abort is simulated on the host; no kernel is made to time out.)"""
+    _need_gpu()
+    import warnings
+    import multimodalfilter_amd as mmf
+    from multimodalfilter_amd import _abi, engine
+
+    dev = torch.device("cuda:0")
+    N, T, d = 37, 6, 3
+    torch.manual_seed(5)
+    obs, ctrl, x0, cov = _ekf_loop_inputs(N, T, d, dev)
+    f = mmf.door_models.DoorCrossmodalKalmanFilter().to(dev).eval()
+    assert _abi.ekf_persistent_plan(N, 2) > 0
+
+    def run(sabotage):
+        taken = []
+        real = _abi.ekf_forward_loop
+
+        def spy(a, like):
+            taken.append(int(a.persistent))
+            real(a, like)
+            if sabotage and a.persistent:  # what an aborted launch leaves behind: garbage and the abort bit
+                torch.cuda.synchronize()
+                fill_nan(a.mu, 2 * N * d)
+                fill_nan(a.Sigma, 2 * N * d * d)
+                engine.range_flag(dev).bitwise_or_(_abi.FLAG_GAVE_UP)
+
+        _abi.ekf_forward_loop = spy
+        try:
+            f.initialize_beliefs(mean=x0, covariance=cov)
+            with warnings.catch_warnings(record=True) as caught:
+                warnings.simplefilter("always")
+                a = f.forward_loop(observations=obs, controls=ctrl)
+                b = f.forward_loop(observations={k: v[:2] for k, v in obs.items()}, controls=ctrl[:2])
+            beliefs = [(m._belief_mean.clone(), m._belief_covariance.clone()) for m in f.filter_models]
+            return taken, [str(w.message) for w in caught], a, b, beliefs
+        finally:
+            _abi.ekf_forward_loop = real
+
+    with engine.persistent_forms(ekf=False):
+        ref = run(False)
+    with engine.persistent_forms(ekf=True):
+        got = run(True)
+        assert ref[0] == [0, 0]
+        assert got[0] == [1, 0, 0], got[0]          # persistent, its re-run, and a second call that does not try again
+        assert len(got[1]) == 1 and "gave up" in got[1][0]
+        assert engine.EKF_PERSISTENT is False
+        assert torch.equal(ref[2], got[2]) and torch.equal(ref[3], got[3])
+        assert bool(torch.isfinite(got[2]).all())
+        for (m0, s0), (m1, s1) in zip(ref[4], got[4]):
+            assert torch.equal(m0, m1) and torch.equal(s0, s1)
+        engine.check_range(dev)                      # the abort bit was consumed: nothing left to raise
+
+
+def test_persistent_ekf_loop_of_one_filter_never_reads_the_status_word():
+    """K = 1: the persistent launch has no hand-offs and cannot give up, so ``engine.run_persistent`` neither copies the
+    belief nor reads the status word -- the ``checked_loop`` read at the end of ``forward_loop`` is the only host read."""
+    _need_gpu()
+    import multimodalfilter_amd as mmf
+    from multimodalfilter_amd import _abi, engine
+
+    dev = torch.device("cuda:0")
+    N, T, d = 100, 5, 3
+    torch.manual_seed(5)
+    obs, ctrl, x0, cov = _ekf_loop_inputs(N, T, d, dev)
+    f = mmf.door_models.DoorKalmanFilter().to(dev).eval()
+    taken, asked = [], []
+    real, real_check = _abi.ekf_forward_loop, engine._gave_up
+    _abi.ekf_forward_loop = lambda a, *r, **k: (taken.append(int(a.persistent)), real(a, *r, **k))[1]
+    engine._gave_up = lambda flag: (asked.append(1), real_check(flag))[1]
+    try:
+        with engine.persistent_forms(ekf=True):
+            f.initialize_beliefs(mean=x0, covariance=cov)
+            f.forward_loop(observations=obs, controls=ctrl)
+            f.forward_loop(observations={k: v[:2] for k, v in obs.items()}, controls=ctrl[:2])
+    finally:
+        _abi.ekf_forward_loop, engine._gave_up = real, real_check
+    assert taken == [1, 1], taken
+    assert asked == []
+
+
+def fill_nan(address: int, n: int):
+    """Overwrite ``n`` floats of device memory at ``address`` with NaN bytes (the HIP runtime's own memset)."""
+    import ctypes
+
+    hip = ctypes.CDLL("libamdhip64.so")
+    hip.hipMemset.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t]
+    assert hip.hipMemset(ctypes.c_void_p(address), 0xFF, 4 * n) == 0
+    torch.cuda.synchronize()
 
 
 @pytest.mark.parametrize("tname", ["door", "push"])

@@ -100,3 +100,115 @@ def test_packed_weight_cache_rebuilds_exactly_when_a_source_changes():
         wd = w2.to("cuda:0")
         cached(cache, "k", [wd, b], build)
         assert len(builds) == 6
+
+
+class _FakeLoopArgs(ctypes.Structure):
+    _fields_ = [("persistent", ctypes.c_int32), ("n_sync_words", ctypes.c_int32), ("sync_words", ctypes.c_void_p),
+                ("range_flag", ctypes.c_void_p)]
+
+
+def test_run_persistent_is_the_give_up_protocol_of_every_loop():
+    """``engine.run_persistent`` with a fake entry point on host tensors: one plain call when not eligible; one persistent
+    call when all goes well; after a give-up the in-place tensors are restored BEFORE the second call, ``FLAG_GAVE_UP`` is
+    consumed and every other bit left alone, one warning, all three switches off, and the next invocation does not try
+    again; ``restore=None`` never reads the status word.  ``persistent_forms`` puts switches and latch back."""
+    import warnings
+
+    cpu = torch.device("cpu")
+    flag = engine.range_flag(cpu)
+    flag.zero_()
+    start = (engine.PF_PERSISTENT, engine.EKF_PERSISTENT, engine.LSTM_PERSISTENT, engine._PERSISTENT_WARNED)
+    mu, Sigma = torch.arange(6.0), torch.arange(18.0)
+    mu0, Sigma0 = mu.clone(), Sigma.clone()
+    seen = []
+
+    def call(a, sabotage=False):
+        seen.append((int(a.persistent), int(a.n_sync_words), a.sync_words, a.range_flag, mu.clone(), Sigma.clone()))
+        if sabotage and a.persistent:
+            mu.fill_(float("nan"))
+            Sigma.fill_(float("nan"))
+            flag.bitwise_or_(_abi.FLAG_GAVE_UP | _abi.FLAG_RANGE)
+        return len(seen)
+
+    with engine.persistent_forms(pf=True, ekf=True, lstm=True):
+        # not eligible
+        a = _FakeLoopArgs()
+        assert engine.run_persistent(a, lambda: call(a), n_sync_words=0, device=cpu, restore=(mu, Sigma)) == 1
+        assert [s[:4] for s in seen] == [(0, 0, None, None)]
+        # eligible, and the launch ran to its end
+        del seen[:]
+        a = _FakeLoopArgs()
+        assert engine.run_persistent(a, lambda: call(a), n_sync_words=40, device=cpu, restore=(mu, Sigma)) == 1
+        assert [s[:2] for s in seen] == [(1, 40)] and seen[0][2] and seen[0][3] == flag.data_ptr()
+        assert int(flag.item()) == 0
+        # eligible, and the launch gave up
+        del seen[:]
+        a = _FakeLoopArgs()
+        with warnings.catch_warnings(record=True) as caught:
+            warnings.simplefilter("always")
+            assert engine.run_persistent(a, lambda: call(a, True), n_sync_words=40, device=cpu, restore=(mu, Sigma)) == 2  # the rerun's result
+            assert [s[0] for s in seen] == [1, 0]
+            assert torch.equal(seen[1][4], mu0) and torch.equal(seen[1][5], Sigma0)  # restored before the second call
+            assert int(flag.item()) == _abi.FLAG_RANGE
+            assert (engine.PF_PERSISTENT, engine.EKF_PERSISTENT, engine.LSTM_PERSISTENT) == (False, False, False)
+            # what a caller's eligibility expression now yields: no further attempt, and no second warning after another give-up
+            a = _FakeLoopArgs()
+            engine.run_persistent(a, lambda: call(a, True), n_sync_words=40 if engine.EKF_PERSISTENT else 0, device=cpu, restore=(mu, Sigma))
+            assert [s[0] for s in seen] == [1, 0, 0]
+            a = _FakeLoopArgs()
+            engine.run_persistent(a, lambda: call(a, True), n_sync_words=40, device=cpu, restore=(mu, Sigma))
+        assert len(caught) == 1 and "gave up" in str(caught[0].message)
+        with pytest.raises(_abi.MmfError, match="f16x3 operand range"):  # FLAG_RANGE is still there for the loop's own check
+            engine.check_range(cpu)
+        # restore=None: a launch without hand-offs -- no copies, and the status word is not read at all
+        del seen[:]
+        a = _FakeLoopArgs()
+        flag.item = lambda: pytest.fail("the status word was read")
+        try:
+            engine.run_persistent(a, lambda: call(a, True), n_sync_words=40, device=cpu, restore=None)
+        finally:
+            del flag.item
+        assert [s[0] for s in seen] == [1] and bool(torch.isnan(mu).all())
+        flag.zero_()
+    # the switches and the warned-once latch are back where they started, although a give-up cleared all three inside
+    assert (engine.PF_PERSISTENT, engine.EKF_PERSISTENT, engine.LSTM_PERSISTENT, engine._PERSISTENT_WARNED) == start
+    with engine.persistent_forms(ekf=False):
+        assert (engine.PF_PERSISTENT, engine.EKF_PERSISTENT, engine.LSTM_PERSISTENT) == (start[0], False, start[2])
+    assert (engine.PF_PERSISTENT, engine.EKF_PERSISTENT, engine.LSTM_PERSISTENT, engine._PERSISTENT_WARNED) == start
+
+
+def test_check_range_names_the_three_reports():
+    cpu = torch.device("cpu")
+    flag = engine.range_flag(cpu)
+    for bits, exc, text in ((_abi.FLAG_NOT_PD | _abi.FLAG_GAVE_UP | _abi.FLAG_RANGE, ValueError, "not positive definite"),
+                            (_abi.FLAG_GAVE_UP | _abi.FLAG_RANGE, _abi.MmfError, "MMF_EKF_PERSISTENT=0"),
+                            (_abi.FLAG_RANGE, _abi.MmfError, "f16x3 operand range")):
+        flag.fill_(bits)
+        with pytest.raises(exc, match=text):
+            engine.check_range(cpu)
+        assert int(flag.item()) == 0
+    engine.check_range(cpu)
+
+
+def test_capturing_is_seen_by_the_capturing_thread_only():
+    import threading
+
+    seen = {}
+    inside, done = threading.Event(), threading.Event()
+
+    def other():
+        inside.wait(10)
+        seen["other"] = engine.is_capturing()
+        done.set()
+
+    t = threading.Thread(target=other)
+    t.start()
+    assert not engine.is_capturing()
+    with engine.capturing():
+        with engine.capturing():  # nests
+            pass
+        seen["own"] = engine.is_capturing()
+        inside.set()
+        assert done.wait(10)
+    t.join()
+    assert seen == {"own": True, "other": False} and not engine.is_capturing()
