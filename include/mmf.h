@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MMF_ABI_VERSION 41
+#define MMF_ABI_VERSION 42
 
 #define MMF_EINVAL (-1)      /* bad argument (null pointer, d out of range, ...) */
 #define MMF_ETOOLARGE (-2)   /* size beyond what the kernel supports (see each call) */
@@ -111,6 +111,35 @@ int mmf_pf_reweight_resample_soft(const float* loglik, const float* logw_in, con
                                   const float* u, float* estimate, float* states_out,
                                   float* logw_out, int32_t* indices_out, int N, int M, int M_out,
                                   int d, int mode, float alpha, void* stream);
+
+/* ABI 42.  K1 with the BELIEF RECORD of the step: the second moment, the effective sample size and the evidence increment of
+ * the pre-resampling weighted set -- the set the weighted-mean estimate is taken from -- which upstream torchfilter leaves
+ * to the caller (particle_states / particle_log_weights after every forward; the reference's vis_pf_likelihoods.ipynb).
+ * With a_m = logw_in_m + loglik_m (logw_in null: uniform -log M), w_m = exp(a_m - logsumexp(a)), mu = sum_m w_m x_m:
+ *   cov          (N, d, d)  sum_m w_m (x_m - mu)(x_m - mu)^T: full symmetric storage (symmetric bit for bit), no Bessel
+ *                           factor -- the moment-matched Gaussian of the weighted set; about the weighted MEAN also where
+ *                           estimation_method "argmax" reports another point
+ *   ess          (N)        1 / sum_m w_m^2, in [1, M]
+ *   log_evidence (N)        logsumexp_m(a_m): the step's increment of the log marginal likelihood estimate when logw_in is
+ *                           normalised (every path of this library keeps it so)
+ * each or null; all null = mmf_pf_reweight_resample (alpha == 1) / mmf_pf_reweight_resample_soft, same kernels: the
+ * recording is a template flag of both K1 kernels, so the non-recording instantiations are the ones without it.
+ * Arithmetic (fp32, one pass next to the estimate's sums): moments about a PIVOT, the first highest-weight particle p --
+ *   e_m = exp(a_m - max), S = sum e, m1 = sum e (x - p), M2 = sum e (x - p)(x - p)^T, cov = M2 / S - (m1 / S)(m1 / S)^T,
+ *   ess = S^2 / sum e^2, log_evidence = max + log S
+ * -- chosen over a second pass about the fp32 mean because pass 1 already finds the maximum and the rows are in registers
+ * when the estimate is accumulated (no second sweep, no re-read).  Raw moments E[x x^T] - mu mu^T lose a 1e-3-wide
+ * cloud of O(1) states entirely in fp32; a fixed pivot fails once the weight sits far from it.  The sums follow the
+ * estimate's partition rule (csrc/pf_resample_systematic.inc), so every form of K1 -- launch, persistent loop -- gives the
+ * same bits.  A particle with a_m = -inf contributes exactly zero.  The opt-in cluster form does not record: a recording
+ * call takes the one-workgroup kernels.
+ * Limits: as mmf_pf_reweight_resample, less the record's reduction rows in LDS: M <= 20,200 (modes 1/2) / 40,500 (mode 0),
+ *         larger -> MMF_ETOOLARGE.  mode 0 takes alpha == 1 only. */
+int mmf_pf_reweight_resample_belief(const float* loglik, const float* logw_in, const float* states_in,
+                                    const float* u, float* estimate, float* states_out,
+                                    float* logw_out, int32_t* indices_out, int N, int M, int M_out,
+                                    int d, int mode, float alpha, float* cov, float* ess,
+                                    float* log_evidence, void* stream);
 
 /* Belief initialisation (replaces torchfilter's ParticleFilter.initialize_beliefs; call site
  * eval_helpers.py:125-131): states[n][m] = mean[n] + chol(covariance[n]) eps[n][m], logw = -log M.
@@ -448,6 +477,10 @@ typedef struct MmfPfLoopArgs {
   int32_t n_sync_words;      /* 4-byte words of sync_words (>= mmf_pf_persistent_sync_words(N, M, d, n_meas))              */
   uint32_t* sync_words;      /* persistent: device workspace of the in-launch hand-offs -- tagged 8-byte granules of the   */
                              /* particle rows and log-likelihoods --, zeroed by the call; an allocation of its own         */
+  float* cov_steps;          /* ABI 42. (T, N, d, d) or null: every step's belief record (mmf_pf_reweight_resample_belief);  */
+  float* ess_steps;          /* (T, N) or null                                                                             */
+  float* log_evidence_steps; /* (T, N) or null.  Recording does not change eligibility for the persistent form, whose K1   */
+                             /* workgroups write the records straight to these arrays; all null: the kernels without it    */
 } MmfPfLoopArgs;             /* host struct holding device pointers                           */
 
 int mmf_pf_forward_loop(const MmfPfLoopArgs* args /* host */, void* stream);
@@ -879,6 +912,15 @@ typedef struct MmfEkfLoopArgs {
 } MmfEkfLoopArgs;            /* host struct holding device pointers                            */
 
 int mmf_ekf_forward_loop(const MmfEkfLoopArgs* args /* host */, void* stream);
+
+/* ABI 42.  mmf_ekf_forward_loop that also keeps the posterior covariance as every step leaves it (upstream torchfilter's
+ * belief_covariance after each forward of crossmodal_kf.py:88-151 / unimodal_kf.py:162-250):
+ *   Sigma_steps (T, N, d, d), required: the fused Sigma_f for fusion != 0 (also where feedback is gated off), sub-filter 0's
+ *   Sigma for fusion 0 -- the matrix that goes with estimates[t].
+ * Written by whichever form runs: the persistent launch stores the matrix it holds in registers next to the estimate, the
+ * loop of launches copies it after each step.  An argument of its own and not a field: MmfEkfLoopArgs keeps its size, so a
+ * binding built against ABI 40 / 41 still describes it. */
+int mmf_ekf_forward_loop_belief(const MmfEkfLoopArgs* args /* host */, float* Sigma_steps, void* stream);
 
 /* The persistent form of the EKF step loop (MmfEkfLoopArgs.persistent; csrc/ekf_persistent.inc): a wave owns 8
  * trajectories of ONE sub-filter for all T steps -- belief in registers, the dynamics network's weights in LDS, per step

@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("MMF_LIB_PATH") or os.path.join(_HERE, "libmmf_hip.so"
 MMF_UNITS = 64
 MMF_MAX_RES = 3
 MMF_MAX_STATE_DIM = 4
-ABI_VERSION = 41
+ABI_VERSION = 42
 KIND_DYNAMICS, KIND_MEASURE, KIND_JACOBIAN = 0, 1, 2  # particle-network kinds (csrc/particle_net.hip)
 PREC_F32, PREC_F16X3, PREC_BF16, PREC_F16X3_DUAL = 0, 1, 2, 3
 PRECISIONS = {"f32": PREC_F32, "f16x3": PREC_F16X3}                          # per-particle networks (K2)
@@ -89,7 +89,8 @@ class MmfPfLoopArgs(Structure):
                 ("noise_seed", ctypes.c_uint64), ("noise_step0", ctypes.c_uint32), ("noise_traj0", ctypes.c_uint32),
                 ("noise_mode", c_int32),
                 ("soft_alpha", ctypes.c_float), ("estimate_argmax", c_int32), ("estimate_scratch", _FP),
-                ("persistent", c_int32), ("n_sync_words", c_int32), ("sync_words", _FP)]
+                ("persistent", c_int32), ("n_sync_words", c_int32), ("sync_words", _FP),
+                ("cov_steps", _FP), ("ess_steps", _FP), ("log_evidence_steps", _FP)]
 
 
 class MmfTrainNet(Structure):
@@ -146,6 +147,8 @@ SIGNATURES = {
                                          c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "mmf_pf_reweight_resample_soft": (c_int, [_FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP,
                                               c_int, c_int, c_int, c_int, c_int, ctypes.c_float, c_void_p]),
+    "mmf_pf_reweight_resample_belief": (c_int, [_FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP,
+                                                c_int, c_int, c_int, c_int, c_int, ctypes.c_float, _FP, _FP, _FP, c_void_p]),
     "mmf_pf_reweight_resample_lds_bytes": (c_size_t, [c_int, c_int]),
     "mmf_pf_set_resample_cluster": (None, [c_int]),
     "mmf_pf_get_resample_cluster": (c_int, []),
@@ -180,6 +183,7 @@ SIGNATURES = {
     "mmf_fc64_train_backward": (c_int, [_FP, _FP, _FP, _FP, _FP, _FP, c_int, c_int, c_void_p]),
     "mmf_fuse_virtual_sensors": (c_int, [_FP, _FP, _FP, _FP, _FP, c_int, c_int, c_int, c_int, c_void_p]),
     "mmf_ekf_forward_loop": (c_int, [POINTER(MmfEkfLoopArgs), c_void_p]),
+    "mmf_ekf_forward_loop_belief": (c_int, [POINTER(MmfEkfLoopArgs), _FP, c_void_p]),
     "mmf_ekf_persistent_plan": (c_int, [c_int, c_int]),
     "mmf_ekf_persistent_sync_words": (c_size_t, [c_int, c_int, c_int]),
     "mmf_lstm_blob_floats": (c_size_t, [c_int]),
@@ -292,6 +296,24 @@ def pf_reweight_resample(loglik, logw_in, states_in, u, estimate, states_out, lo
             ptr(loglik), ptr(logw_in), ptr(states_in), ptr(u), ptr(estimate), ptr(states_out),
             ptr(logw_out), ptr(indices_out, dtype=torch.int32), N, M, M_out, d, mode,
             stream_of(states_in)), "mmf_pf_reweight_resample")
+
+
+def pf_reweight_resample_belief(loglik, logw_in, states_in, u, estimate, states_out, logw_out, indices_out, mode: int,
+                                soft_alpha: float = 1.0, *, cov=None, ess=None, log_evidence=None, M_out: int = None):
+    """K1 with the step's belief record (``mmf_pf_reweight_resample_belief``): ``cov (N, d, d)``, ``ess (N)``,
+    ``log_evidence (N)`` of the pre-resampling weighted set, each or ``None``.  ``logw_in`` / ``logw_out`` may be ``None``
+    where the C entry point takes null (plain resampling: uniform weights in / out)."""
+    N, M, d = states_in.shape
+    if M_out is None:
+        M_out = M if mode == 0 else (logw_out.shape[1] if logw_out is not None else states_out.shape[1])
+    assert loglik.shape == (N, M) and estimate.shape == (N, d)
+    assert cov is None or cov.shape == (N, d, d)
+    assert (ess is None or ess.shape == (N,)) and (log_evidence is None or log_evidence.shape == (N,))
+    with _on(states_in):
+        _check(load().mmf_pf_reweight_resample_belief(
+            ptr(loglik), ptr(logw_in), ptr(states_in), ptr(u), ptr(estimate), ptr(states_out),
+            ptr(logw_out), ptr(indices_out, dtype=torch.int32), N, M, M_out, d, mode, float(soft_alpha),
+            ptr(cov), ptr(ess), ptr(log_evidence), stream_of(states_in)), "mmf_pf_reweight_resample_belief")
 
 
 def pf_set_resample_cluster(enabled: bool) -> bool:
@@ -552,10 +574,15 @@ def fuse_virtual_sensors(z, tril, w, z_out, tril_out, mode: int):
                                                stream_of(z)), "mmf_fuse_virtual_sensors")
 
 
-def ekf_forward_loop(args: MmfEkfLoopArgs, like: torch.Tensor):
-    """Enqueue T fused-EKF steps (see include/mmf.h)."""
+def ekf_forward_loop(args: MmfEkfLoopArgs, like: torch.Tensor, Sigma_steps: torch.Tensor = None):
+    """Enqueue T fused-EKF steps (see include/mmf.h); ``Sigma_steps (T, N, d, d)``: every step's posterior covariance is
+    kept there (``mmf_ekf_forward_loop_belief``)."""
     with _on(like):
-        _check(load().mmf_ekf_forward_loop(ctypes.byref(args), stream_of(like)), "mmf_ekf_forward_loop")
+        if Sigma_steps is None:
+            _check(load().mmf_ekf_forward_loop(ctypes.byref(args), stream_of(like)), "mmf_ekf_forward_loop")
+        else:
+            _check(load().mmf_ekf_forward_loop_belief(ctypes.byref(args), ptr(Sigma_steps), stream_of(like)),
+                   "mmf_ekf_forward_loop_belief")
 
 
 LSTM_HIDDEN, LSTM_LAYERS = 512, 2

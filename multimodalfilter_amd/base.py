@@ -18,12 +18,26 @@ Models that only implement ``forward`` still work: the filters fall back to call
 (on the GPU) and use the HIP kernels for the recursion itself.
 """
 import abc
+from types import SimpleNamespace
 from typing import Tuple
 
 import torch
 import torch.nn as nn
 
 from .utils import tree_index, tree_leading_shape, tree_map
+
+
+def belief_record(**fields) -> SimpleNamespace:
+    """What a filter with ``record_belief`` set leaves in ``last_belief``: ``covariance (..., N, d, d)`` for every filter;
+    ``ess`` / ``log_evidence (..., N)`` for the particle filter (``include/mmf.h``, K1, has the definitions)."""
+    return SimpleNamespace(**fields)
+
+
+def stack_belief_records(steps) -> SimpleNamespace:
+    """Per-step records -> one record with a leading ``T`` axis (the step-by-step loops; no host read)."""
+    if not steps:
+        return None
+    return SimpleNamespace(**{k: torch.stack([getattr(s, k) for s in steps]) for k in vars(steps[0])})
 
 
 class DynamicsModel(nn.Module, abc.ABC):
@@ -117,6 +131,11 @@ class Filter(nn.Module, abc.ABC):
     def _forward_loop_steps(self, *, observations, controls) -> torch.Tensor:
         T = tree_leading_shape(controls)[0]
         assert tree_leading_shape(observations)[0] == T
-        out = [self(observations=tree_index(observations, t), controls=tree_index(controls, t))
-               for t in range(T)]
+        out, beliefs = [], []
+        for t in range(T):
+            out.append(self(observations=tree_index(observations, t), controls=tree_index(controls, t)))
+            if getattr(self, "record_belief", False):
+                beliefs.append(self.last_belief)
+        if beliefs:
+            self.last_belief = stack_belief_records(beliefs)
         return torch.stack(out, dim=0)

@@ -212,6 +212,10 @@ class _FusedKalmanFilters(base.Filter, _EnabledModels):
         self.filter_models = nn.ModuleList(filter_models)
         self._enabled_models: List[bool] = [True for _ in self.filter_models]
         self.weighted_covariances = None
+        # record_belief: last_belief.covariance = the posterior covariance as every step leaves it -- the fused one, or
+        # the only enabled sub-filter's where nothing is fused: the matrix that goes with the returned mean
+        self.record_belief = False
+        self.last_belief = None
 
     def _num_models(self):
         return len(self.filter_models)
@@ -273,6 +277,7 @@ class _FusedKalmanFilters(base.Filter, _EnabledModels):
                       mu, Sigma, mu_f, Sigma_f, fusion=fusion, feedback=feedback)
         for k, f in enumerate(live):
             f._belief_mean, f._belief_covariance = mu[k], Sigma[k]
+        self.last_belief = base.belief_record(covariance=Sigma_f if fusion else Sigma[0]) if self.record_belief else None
         return mu_f, Sigma_f, mu, Sigma
 
     def _autograd_unimodal(self, observations, controls):
@@ -285,7 +290,11 @@ class _FusedKalmanFilters(base.Filter, _EnabledModels):
     def forward(self, *, observations, controls):
         N, _ = controls.shape
         if use_autograd(self):
-            return self._forward_autograd(observations, controls)
+            self._autograd_covariance = None
+            out = self._forward_autograd(observations, controls)
+            cov = self._autograd_covariance
+            self.last_belief = base.belief_record(covariance=cov.detach()) if self.record_belief and cov is not None else None
+            return out
         with torch.no_grad():
             return self._forward_encoded(observations, controls, self._encode_step(observations),
                                          self._encode_controls(controls))
@@ -363,9 +372,11 @@ class _FusedKalmanFilters(base.Filter, _EnabledModels):
         mu = torch.stack([f._belief_mean for f in live]).contiguous()
         Sigma = torch.stack([f._belief_covariance for f in live]).contiguous()
         q = torch.stack([m.scale_tril() for m in dyns]).to(torch.float32).contiguous()
+        steps = torch.empty((T, N, d, d), dtype=torch.float32, device=mu.device) if self.record_belief else None
         est, Sigma_f = engine.run_ekf_loop([m._net for m in dyns], [ctrl_all[i]["bias"] for i in live_idx], q, z, r, mu, Sigma,
-                                           fusion=fusion, feedback=feedback, gate=gate,
+                                           fusion=fusion, feedback=feedback, gate=gate, Sigma_steps=steps,
                                            fuse_w=None if fuse_w is None else f32(fuse_w).contiguous())
+        self.last_belief = base.belief_record(covariance=steps) if self.record_belief else None
         for k, f in enumerate(live):
             f._belief_mean, f._belief_covariance = mu[k], Sigma[k]
         return est, Sigma_f
@@ -384,12 +395,15 @@ class _FusedKalmanFilters(base.Filter, _EnabledModels):
             native = self._native_loop(encs, ctrl_all, T, N, observations)
             if native is not None:
                 return self._after_native_loop(*native)
-            out = []
+            out, beliefs = [], []
             for t in range(T):
                 sl = slice(t * N, (t + 1) * N)
                 ctrl = [None if c is None else {k: v[sl] for k, v in c.items()} for c in ctrl_all]
                 out.append(self._forward_encoded(tree_index(observations, t), tree_index(controls, t),
                                                  encs[t], ctrl))
+                beliefs.append(self.last_belief)
+            if self.record_belief:
+                self.last_belief = base.stack_belief_records(beliefs)
         return torch.stack(out, dim=0)
 
 
@@ -455,7 +469,7 @@ class CrossmodalKalmanFilter(_FusedKalmanFilters):
             raw = self.crossmodal_weight_model(observations=observations)
         w = self._state_weights(raw, N, means.device)
         mu, Sigma = self.calculate_weighted_states(w, means, covs)
-        self.weighted_covariances = Sigma
+        self.weighted_covariances = self._autograd_covariance = Sigma
         for f in self.filter_models:
             f.states_prev, f.states_covariance_prev = mu, Sigma
             if self.feedback == "belief":
@@ -504,9 +518,10 @@ class UnimodalKalmanFilter(_FusedKalmanFilters):
     def _forward_autograd(self, observations, controls):
         means, covs = self._autograd_unimodal(observations, controls)
         if means.shape[0] == 1:
+            self._autograd_covariance = covs[0]
             return means[0]
         prec = torch.inverse(covs + 1e-9)
-        Sigma = torch.inverse(torch.sum(prec, dim=0) + 1e-9)
+        Sigma = self._autograd_covariance = torch.inverse(torch.sum(prec, dim=0) + 1e-9)
         return (Sigma @ torch.sum(prec @ means[..., None], dim=0)).squeeze(-1)
 
     def _native_plan(self, encs, T, N, observations=None):

@@ -7,7 +7,8 @@
 // recursion was bound by ~20 launches and tensor shuffles of interpreter work per step.
 #include "mmf_common.h"
 
-extern "C" int mmf_ekf_forward_loop(const MmfEkfLoopArgs* a, void* stream) {
+// Sigma_steps: (T, N, d, d) or null -- every step's posterior covariance (mmf_ekf_forward_loop_belief)
+static int ekf_forward_loop(const MmfEkfLoopArgs* a, float* Sigma_steps, void* stream) {
   if (!a) return MMF_EINVAL;
   if (a->T < 0 || a->N < 1 || a->K < 1 || a->K > MMF_LOOP_MAX_MEAS || a->d < 1) return MMF_EINVAL;
   if (a->fusion < 0 || a->fusion > 2) return MMF_EINVAL;
@@ -18,7 +19,7 @@ extern "C" int mmf_ekf_forward_loop(const MmfEkfLoopArgs* a, void* stream) {
   for (int k = 0; k < a->K; ++k)
     if (!a->dyn_packed[k] || !a->dyn_bias[k]) return MMF_EINVAL;
   if (a->persistent && a->T > 0) {  // ONE launch for all T steps (ekf_persistent.inc); same bits
-    const int rc = mmf_internal_ekf_persistent(a, stream);
+    const int rc = mmf_internal_ekf_persistent(a, Sigma_steps, stream);
     if (rc != MMF_INTERNAL_NOT_RESIDENT) return rc;
     // this device cannot hold the persistent grid, or the problem is not eligible: the loop of launches
   }
@@ -42,6 +43,18 @@ extern "C" int mmf_ekf_forward_loop(const MmfEkfLoopArgs* a, void* stream) {
       const hipError_t e = hipMemcpyAsync(est, a->mu, N * d * sizeof(float), hipMemcpyDeviceToDevice, hs);
       if (e != hipSuccess) return static_cast<int>(e);
     }
+    if (Sigma_steps) {  // the step's posterior covariance: the fused one, or sub-filter 0's (the first block of Sigma)
+      const hipError_t e = hipMemcpyAsync(Sigma_steps + t * N * d * d, a->fusion ? a->Sigma_f : a->Sigma,
+                                          N * d * d * sizeof(float), hipMemcpyDeviceToDevice, hs);
+      if (e != hipSuccess) return static_cast<int>(e);
+    }
   }
   return 0;
+}
+
+extern "C" int mmf_ekf_forward_loop(const MmfEkfLoopArgs* a, void* stream) { return ekf_forward_loop(a, nullptr, stream); }
+
+extern "C" int mmf_ekf_forward_loop_belief(const MmfEkfLoopArgs* a, float* Sigma_steps, void* stream) {
+  if (!Sigma_steps) return MMF_EINVAL;
+  return ekf_forward_loop(a, Sigma_steps, stream);
 }

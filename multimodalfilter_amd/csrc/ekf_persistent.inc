@@ -41,6 +41,7 @@ struct EkfPersistArgs {
   float* Sigma;                          // (K, N, d, d) in / out
   float* Sigma_f;                        // (N, d, d) out (fusion != 0)
   float* estimates;                      // (T, N, d)
+  float* Sigma_steps;                    // (T, N, d, d) or null: every step's posterior covariance (fused, or sub-filter 0's)
   const int32_t* feedback_gate;          // (T) or null
   mmf::Granule* xg;                      // [2 slots][K][N][d + d*d] corrected beliefs on their way to the other roles
   unsigned* abort_word;
@@ -312,6 +313,8 @@ __global__ __launch_bounds__(kEkfPersistThreads, 1) void ekf_persistent_loop_ker
       if (writer && k == 0) {  // the fused mean, or (no fusion) sub-filter 0's corrected mean
 #pragma unroll
         for (int i = 0; i < D; ++i) a.estimates[(static_cast<size_t>(t) * N + n) * D + i] = a.fusion != 0 ? mf[i] : mine_mu[i];
+        // ... and the matrix that goes with it (gated-off feedback: still the fused posterior, as the estimate is)
+        if (a.Sigma_steps != nullptr) store_mat<D>(a.Sigma_steps + (static_cast<size_t>(t) * N + n) * D * D, a.fusion != 0 ? Sf : mine_S);
       }
     }
     if (writer) {
@@ -372,7 +375,7 @@ extern "C" size_t mmf_ekf_persistent_sync_words(int N, int K, int d) {
   return 4 + 2 * (2 * static_cast<size_t>(K) * N * (d + d * d));
 }
 
-int mmf_internal_ekf_persistent(const MmfEkfLoopArgs* a, void* stream) {
+int mmf_internal_ekf_persistent(const MmfEkfLoopArgs* a, float* Sigma_steps, void* stream) {
   if (!a || !a->sync_words) return MMF_EINVAL;
   if ((a->d != 2 && a->d != 3) || a->n_res_dyn != 3 || a->T < 1) return MMF_EINVAL;
   if (a->precision != MMF_PREC_F32 && a->precision != MMF_PREC_F16X3) return MMF_EINVAL;
@@ -384,7 +387,7 @@ int mmf_internal_ekf_persistent(const MmfEkfLoopArgs* a, void* stream) {
   pa.T = a->T; pa.N = a->N; pa.K = a->K; pa.fusion = a->fusion; pa.feedback = a->feedback;
   for (int k = 0; k < a->K; ++k) { pa.dyn_packed[k] = a->dyn_packed[k]; pa.dyn_bias[k] = a->dyn_bias[k]; }
   pa.q_tril = a->q_tril; pa.z = a->z; pa.r_tril = a->r_tril; pa.fuse_w = a->fuse_w;
-  pa.mu = a->mu; pa.Sigma = a->Sigma; pa.Sigma_f = a->Sigma_f; pa.estimates = a->estimates;
+  pa.mu = a->mu; pa.Sigma = a->Sigma; pa.Sigma_f = a->Sigma_f; pa.estimates = a->estimates; pa.Sigma_steps = Sigma_steps;
   pa.feedback_gate = a->feedback_gate;
   unsigned* w = reinterpret_cast<unsigned*>(a->sync_words);
   pa.abort_word = w;

@@ -64,6 +64,10 @@ static int pf_enqueue_steps(const MmfPfLoopArgs* a, void* stream, bool with_even
       }
     }
     float* est = a->estimates + t * row * a->d;
+    // this step's slices of the belief record (null: the non-recording kernels)
+    float* cov = a->cov_steps ? a->cov_steps + t * row * a->d * a->d : nullptr;
+    float* ess = a->ess_steps ? a->ess_steps + t * row : nullptr;
+    float* lev = a->log_evidence_steps ? a->log_evidence_steps + t * row : nullptr;
     if (a->estimate_argmax) {
       // the particle with the largest pre-resampling weight; K1's weighted mean goes to the scratch.  In the plain
       // resampling loop the incoming weights are uniform from the second step on (see below)
@@ -76,12 +80,12 @@ static int pf_enqueue_steps(const MmfPfLoopArgs* a, void* stream, bool with_even
     if (soft) {
       // torchfilter's soft resampling: survivors carry importance weights, so the log-weights travel every step
       const float* u = a->uniforms + t * (a->resample_mode == 1 ? row : nm);
-      rc = mmf_pf_reweight_resample_soft(ll, lw_cur, other, u, est, cur, lw_other, anc, a->N, a->M, a->M, a->d,
-                                         a->resample_mode, a->soft_alpha, stream);
+      rc = mmf_pf_reweight_resample_belief(ll, lw_cur, other, u, est, cur, lw_other, anc, a->N, a->M, a->M, a->d,
+                                           a->resample_mode, a->soft_alpha, cov, ess, lev, stream);
       if (rc) return rc;
     } else if (a->resample_mode == 0) {
-      rc = mmf_pf_reweight_resample(ll, lw_cur, other, nullptr, est, nullptr, lw_other, nullptr, a->N,
-                                    a->M, a->M, a->d, 0, stream);
+      rc = mmf_pf_reweight_resample_belief(ll, lw_cur, other, nullptr, est, nullptr, lw_other, nullptr, a->N,
+                                           a->M, a->M, a->d, 0, 1.0f, cov, ess, lev, stream);
       if (rc) return rc;
       float* s = cur; cur = other; other = s;  // propagated particles are the new belief
     } else {
@@ -89,9 +93,9 @@ static int pf_enqueue_steps(const MmfPfLoopArgs* a, void* stream, bool with_even
       // every step of this loop resamples, so from the second step on the incoming weights are the
       // uniform -log M the previous step would have written, and only the last step's are ever read
       // again: 8 of the 40 B per particle-step stay out of HBM
-      rc = mmf_pf_reweight_resample(ll, t == 0 ? lw_cur : nullptr, other, u, est, cur,
-                                    t == a->T - 1 ? lw_other : nullptr, anc, a->N, a->M, a->M, a->d,
-                                    a->resample_mode, stream);
+      rc = mmf_pf_reweight_resample_belief(ll, t == 0 ? lw_cur : nullptr, other, u, est, cur,
+                                           t == a->T - 1 ? lw_other : nullptr, anc, a->N, a->M, a->M, a->d,
+                                           a->resample_mode, 1.0f, cov, ess, lev, stream);
       if (rc) return rc;  // resampled particles land back in `cur`
     }
     if ((rc = mark())) return rc;

@@ -61,6 +61,9 @@ struct PersistArgs {
   const float* logw_in0;               // (N, M) log-weights on entry (read by step 0 only)
   float* logw_out_last;                // (N, M) written by the last step only
   float* estimates;                    // (T, N, D)
+  float* cov_steps;                    // REC: (T, N, D, D) / (T, N) / (T, N) belief records, each or null: written by the K1
+  float* ess_steps;                    // role straight to global memory -- nobody in the launch reads them back
+  float* log_evidence_steps;
   int* range_flag;
   unsigned* abort_word;
   unsigned long long noise_seed;
@@ -291,7 +294,8 @@ __device__ __forceinline__ bool small_tile(const float* __restrict__ lds, const 
   return true;
 }
 
-template <int D, int PREC>
+// REC: the K1 role also writes every step's belief record (mmf::K1Belief); the other roles are the same code
+template <int D, int PREC, bool REC = false>
 __global__ __launch_bounds__(kPersistThreads, 2) void pf_persistent_loop_kernel(PersistArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int kNresDyn = 3, kNresMeas = 2;
@@ -395,7 +399,13 @@ __global__ __launch_bounds__(kPersistThreads, 2) void pf_persistent_loop_kernel(
       tr.stamps = my_stamps;
       tr.lo = (last && a.logw_out_last) ? a.logw_out_last + static_cast<size_t>(n) * a.M : nullptr;
       tr.io = nullptr;
-      if (!mmf::resample_systematic_trajectory<D, true, true, PREC == MMF_PREC_F32>(smem, tr, a.M, a.M, a.lw_uniform, log_uniform)) {
+      if constexpr (REC) {
+        const size_t tn = static_cast<size_t>(t) * a.N + n;
+        tr.cov = a.cov_steps ? a.cov_steps + tn * D * D : nullptr;
+        tr.ess = a.ess_steps ? a.ess_steps + tn : nullptr;
+        tr.log_evidence = a.log_evidence_steps ? a.log_evidence_steps + tn : nullptr;
+      }
+      if (!mmf::resample_systematic_trajectory<D, true, true, PREC == MMF_PREC_F32, REC>(smem, tr, a.M, a.M, a.lw_uniform, log_uniform)) {
         if (threadIdx.x == 0 && a.range_flag != nullptr) atomicOr(a.range_flag, MMF_FLAG_GAVE_UP);
         return;
       }
@@ -405,21 +415,40 @@ __global__ __launch_bounds__(kPersistThreads, 2) void pf_persistent_loop_kernel(
   }
 }
 
-size_t persist_k1_lds_bytes(int M, int d) {
+size_t persist_k1_lds_bytes(int M, int d, bool rec) {
   const size_t slots = (static_cast<size_t>(M) * 8 + 15) & ~static_cast<size_t>(15);
   const size_t sc = (sizeof(mmf::K1Scratch) + 15) & ~static_cast<size_t>(15);
   const size_t marks = ((static_cast<size_t>(M) + 4) * 4 + 15) & ~static_cast<size_t>(15);
-  return slots + sc + marks + static_cast<size_t>(M) * d * sizeof(float) + 32;
+  return slots + sc + marks + static_cast<size_t>(M) * d * sizeof(float) + 32 + (rec ? mmf::k1_belief_lds_bytes() : 0);
 }
 
-template <int D, int PREC>
+template <int D, int PREC, bool REC>
 int launch_persistent(const PersistArgs& pa, size_t lds, int blocks, hipStream_t s) {
-  auto k = pf_persistent_loop_kernel<D, PREC>;
+  auto k = pf_persistent_loop_kernel<D, PREC, REC>;
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
   if (e != hipSuccess) return static_cast<int>(e);
   k<<<blocks, kPersistThreads, lds, s>>>(pa);
   MMF_CHECK_LAUNCH();
   return 0;
+}
+
+// residency check and launch of the instantiation for (precision, d)
+template <bool REC>
+int persistent_dispatch(int precision, int d, const PersistArgs& pa, size_t lds, int blocks, hipStream_t hs) {
+  if (precision != MMF_PREC_F32 && precision != MMF_PREC_F16X3) return MMF_EINVAL;
+  {  // the plan assumed one resident workgroup per CU: hold the launch to what the runtime says about THIS kernel
+    int per_cu = 0, dev = 0, cus = 0;
+    const void* fn = precision == MMF_PREC_F32
+                         ? (d == 3 ? reinterpret_cast<const void*>(pf_persistent_loop_kernel<3, MMF_PREC_F32, REC>) : reinterpret_cast<const void*>(pf_persistent_loop_kernel<2, MMF_PREC_F32, REC>))
+                         : (d == 3 ? reinterpret_cast<const void*>(pf_persistent_loop_kernel<3, MMF_PREC_F16X3, REC>) : reinterpret_cast<const void*>(pf_persistent_loop_kernel<2, MMF_PREC_F16X3, REC>));
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kPersistWaves * MMF_WAVE, lds) != hipSuccess ||
+        hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+      return MMF_EINVAL;
+    if (per_cu < 1 || blocks > per_cu * cus) return MMF_INTERNAL_NOT_RESIDENT;  // mmf_pf_forward_loop takes the launch path
+  }
+  if (precision == MMF_PREC_F32) return d == 3 ? launch_persistent<3, MMF_PREC_F32, REC>(pa, lds, blocks, hs) : launch_persistent<2, MMF_PREC_F32, REC>(pa, lds, blocks, hs);
+  return d == 3 ? launch_persistent<3, MMF_PREC_F16X3, REC>(pa, lds, blocks, hs) : launch_persistent<2, MMF_PREC_F16X3, REC>(pa, lds, blocks, hs);
 }
 
 }  // namespace
@@ -524,6 +553,8 @@ int mmf_internal_pf_persistent(const MmfPfLoopArgs* a, void* stream) {
   const bool last_into_b = ((a->T - 1) & 1) == 0;
   pa.logw_out_last = last_into_b ? a->logw_b : a->logw_a;
   pa.estimates = a->estimates; pa.range_flag = a->range_flag;
+  pa.cov_steps = a->cov_steps; pa.ess_steps = a->ess_steps; pa.log_evidence_steps = a->log_evidence_steps;
+  const bool rec = a->cov_steps || a->ess_steps || a->log_evidence_steps;  // the recording instantiation of the kernel
   const size_t NM = static_cast<size_t>(a->N) * a->M;
   unsigned* w = reinterpret_cast<unsigned*>(a->sync_words);
   pa.abort_word = w;
@@ -545,24 +576,11 @@ int mmf_internal_pf_persistent(const MmfPfLoopArgs* a, void* stream) {
     pa.stamp_step = atoi(stamp_env);
   }
   size_t lds = static_cast<size_t>(blob_floats(3)) * sizeof(float);
-  const size_t k1 = persist_k1_lds_bytes(a->M, a->d);
+  const size_t k1 = persist_k1_lds_bytes(a->M, a->d, rec);
   if (k1 > lds) lds = k1;
   if (lds > 160 * 1024) return MMF_ETOOLARGE;
-  {  // the plan assumed one resident workgroup per CU: hold the launch to what the runtime says about THIS kernel
-    int per_cu = 0, dev = 0, cus = 0;
-    const void* fn = a->precision == MMF_PREC_F32
-                         ? (a->d == 3 ? reinterpret_cast<const void*>(pf_persistent_loop_kernel<3, MMF_PREC_F32>) : reinterpret_cast<const void*>(pf_persistent_loop_kernel<2, MMF_PREC_F32>))
-                         : (a->d == 3 ? reinterpret_cast<const void*>(pf_persistent_loop_kernel<3, MMF_PREC_F16X3>) : reinterpret_cast<const void*>(pf_persistent_loop_kernel<2, MMF_PREC_F16X3>));
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kPersistWaves * MMF_WAVE, lds) != hipSuccess ||
-        hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return MMF_EINVAL;
-    if (per_cu < 1 || blocks > per_cu * cus) return MMF_INTERNAL_NOT_RESIDENT;  // mmf_pf_forward_loop takes the launch path
-  }
-  int rc;
-  if (a->precision == MMF_PREC_F32) rc = a->d == 3 ? launch_persistent<3, MMF_PREC_F32>(pa, lds, blocks, hs) : launch_persistent<2, MMF_PREC_F32>(pa, lds, blocks, hs);
-  else if (a->precision == MMF_PREC_F16X3) rc = a->d == 3 ? launch_persistent<3, MMF_PREC_F16X3>(pa, lds, blocks, hs) : launch_persistent<2, MMF_PREC_F16X3>(pa, lds, blocks, hs);
-  else return MMF_EINVAL;
+  const int rc = rec ? persistent_dispatch<true>(a->precision, a->d, pa, lds, blocks, hs)
+                     : persistent_dispatch<false>(a->precision, a->d, pa, lds, blocks, hs);
   if (rc) return rc;
   if (pa.stamps) {
     std::vector<unsigned long long> h(n_stamps);

@@ -50,13 +50,18 @@ using Scratch = mmf::K1Scratch;  // lives behind the slots in dynamic LDS
 // alpha * w_i + (1 - alpha) / M, in fixed point q'_i = ((A q_i << 8) + (2^24 - A) floor((Q << 8) / M)) >> 32
 // with A = floor(alpha 2^24) (so q'_i <= 2^24 and every bound of the integer scheme still holds), and the
 // survivors carry the importance weights w / mixture, normalised (oracle/resample.py).
-template <int D, bool STAGE, bool SOFT = false>
+// REC: the belief record (covariance, ESS, log-evidence of the weighted set; mmf::K1Belief in pf_resample_systematic.inc),
+// its sums in this kernel's own partition -- per thread over all its chunks, a butterfly per wave, the waves in order.
+// The non-recording instantiation is the kernel as it was.
+struct BeliefOut { float* cov; float* ess; float* log_evidence; };  // (N, d, d), (N), (N); each or null
+
+template <int D, bool STAGE, bool SOFT = false, bool REC = false>
 __global__ __launch_bounds__(kBlock) void pf_reweight_resample_kernel(
     const float* __restrict__ loglik, const float* __restrict__ logw_in,
     const float* __restrict__ states_in, const float* __restrict__ u,
     float* __restrict__ estimate, float* states_out, float* logw_out,
     int32_t* __restrict__ indices_out, int M, int M_out, int mode, float alpha, float lw_uniform,
-    float log_uniform) {
+    float log_uniform, BeliefOut rec) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const bool need_cdf = mode != 0;
   const int slot_bytes = need_cdf ? 8 : 4;
@@ -65,6 +70,9 @@ __global__ __launch_bounds__(kBlock) void pf_reweight_resample_kernel(
   unsigned long long* cdf = reinterpret_cast<unsigned long long*>(smem);  // modes 1/2
   Scratch& sc = *reinterpret_cast<Scratch*>(smem + slots_sz);
   float* xs_lds = reinterpret_cast<float*>(smem + slots_sz + ((sizeof(Scratch) + 15) & ~static_cast<size_t>(15)));  // STAGE
+  mmf::K1BeliefScratch& bsc = *reinterpret_cast<mmf::K1BeliefScratch*>(  // REC: behind the staged states
+      smem + slots_sz + ((sizeof(Scratch) + 15) & ~static_cast<size_t>(15)) +
+      (STAGE ? (static_cast<size_t>(M) * D * sizeof(float) + 15) & ~static_cast<size_t>(15) : 0));
 
   const int n = blockIdx.x;
   const int tid = threadIdx.x;
@@ -110,6 +118,7 @@ __global__ __launch_bounds__(kBlock) void pf_reweight_resample_kernel(
 
   // ---- pass 1: x_i = logw_i + loglik_i -> LDS, row max
   float mx = -INFINITY;
+  int mi = 0x7fffffff;  // REC: the first of this thread's particles that holds its maximum
   for (int base = 0; base < M; base += chunk) {
     const int i0 = base + tid * 4;
     float v[4];
@@ -123,14 +132,33 @@ __global__ __launch_bounds__(kBlock) void pf_reweight_resample_kernel(
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-      if (i0 + j < M) { x_store(i0 + j, v[j]); mx = fmaxf(mx, v[j]); }
+      if (i0 + j < M) {
+        x_store(i0 + j, v[j]);
+        if constexpr (REC) { if (v[j] > mx || mi == 0x7fffffff) mi = i0 + j; }
+        mx = fmaxf(mx, v[j]);
+      }
   }
+  const float mx_thread = mx;
   mx = mmf::wave_max(mx);
   if (lane == 0) sc.red[wave][0] = mx;
   __syncthreads();
   mx = sc.red[0][0];
   for (int w = 1; w < nwaves; ++w) mx = fmaxf(mx, sc.red[w][0]);
+  if constexpr (REC) {  // the pivot: the smallest index holding the row maximum (indices < 2^24 are exact floats)
+    const float cand = mmf::wave_max((mi != 0x7fffffff && mx_thread == mx) ? -static_cast<float>(mi) : -INFINITY);
+    if (lane == 0) bsc.piv_wave[wave] = cand;
+  }
   __syncthreads();
+  float piv[D];
+  mmf::K1Belief<D> bel;
+  if constexpr (REC) {
+    float best = bsc.piv_wave[0];
+    for (int w = 1; w < nwaves; ++w) best = fmaxf(best, bsc.piv_wave[w]);
+    const int p = best > -INFINITY ? static_cast<int>(-best) : 0;
+#pragma unroll
+    for (int c = 0; c < D; ++c) piv[c] = xs[static_cast<size_t>(p) * D + c];
+    bel.reset();
+  }
   K1_STAMP(1);
 
   // ---- pass 2: e_i = detexp(x_i - max); float sums for the estimate; integer CDF
@@ -172,6 +200,10 @@ __global__ __launch_bounds__(kBlock) void pf_reweight_resample_kernel(
       S += e[j];
 #pragma unroll
       for (int c = 0; c < D; ++c) acc[c] = __builtin_fmaf(e[j], st[j * D + c], acc[c]);  // explicit: oracle/strict restates this chain
+      if constexpr (REC) {
+        const float xv = ok ? x_load(i0 + j) : -INFINITY;
+        bel.add(xv == -INFINITY ? 0.f : e[j], st + j * D, piv);
+      }
     }
     qsum += tsum;
     if (need_cdf && !SOFT) {
@@ -274,6 +306,22 @@ __global__ __launch_bounds__(kBlock) void pf_reweight_resample_kernel(
   K1_STAMP(2);
   S = sc.bcast[0];
   if (tid < D) estimate[static_cast<size_t>(n) * D + tid] = sc.bcast[1 + tid] / S;
+  if constexpr (REC) {  // a round of its own: this kernel is not the one on the small problems' critical path
+#pragma unroll
+    for (int k = 0; k < mmf::K1Belief<D>::kSums; ++k) {
+      const float bw = mmf::wave_sum(bel.s[k]);
+      if (lane == 0) bsc.red[wave][k] = bw;
+    }
+    __syncthreads();
+    if (tid < mmf::K1Belief<D>::kSums) {
+      float t = 0.f;
+      for (int w = 0; w < nwaves; ++w) t += bsc.red[w][tid];
+      bsc.tot[tid] = t;
+    }
+    __syncthreads();
+    mmf::k1_belief_store<D>(bsc.tot, S, mx, rec.cov ? rec.cov + static_cast<size_t>(n) * D * D : nullptr,
+                            rec.ess ? rec.ess + n : nullptr, rec.log_evidence ? rec.log_evidence + n : nullptr, tid);
+  }
 
   // ---- mode 0: normalised log-weights out, particles stay
   if (!need_cdf) {
@@ -392,11 +440,11 @@ __global__ __launch_bounds__(kBlock) void pf_reweight_resample_kernel(
 
 // ---- plain systematic resampling WITHOUT a search (the bench's and the reference's evaluation mode): the body is
 // mmf::resample_systematic_trajectory (pf_resample_systematic.inc, shared with the persistent small-problem loop)
-template <int D, bool STAGE>
+template <int D, bool STAGE, bool REC = false>
 __global__ __launch_bounds__(kBlock) void pf_resample_systematic_kernel(
     const float* __restrict__ loglik, const float* __restrict__ logw_in, const float* __restrict__ states_in,
     const float* __restrict__ u, float* __restrict__ estimate, float* states_out, float* logw_out,
-    int32_t* __restrict__ indices_out, int M, int M_out, float lw_uniform, float log_uniform) {
+    int32_t* __restrict__ indices_out, int M, int M_out, float lw_uniform, float log_uniform, BeliefOut rec) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int n = blockIdx.x;
   mmf::K1Trajectory a{};
@@ -409,7 +457,12 @@ __global__ __launch_bounds__(kBlock) void pf_resample_systematic_kernel(
   a.so = states_out + static_cast<size_t>(n) * M_out * D;
   a.lo = logw_out ? logw_out + static_cast<size_t>(n) * M_out : nullptr;
   a.io = indices_out ? indices_out + static_cast<size_t>(n) * M_out : nullptr;
-  mmf::resample_systematic_trajectory<D, STAGE, false, false>(smem, a, M, M_out, lw_uniform, log_uniform);
+  if constexpr (REC) {
+    a.cov = rec.cov ? rec.cov + static_cast<size_t>(n) * D * D : nullptr;
+    a.ess = rec.ess ? rec.ess + n : nullptr;
+    a.log_evidence = rec.log_evidence ? rec.log_evidence + n : nullptr;
+  }
+  mmf::resample_systematic_trajectory<D, STAGE, false, false, REC>(smem, a, M, M_out, lw_uniform, log_uniform);
 }
 
 }  // namespace
@@ -430,7 +483,7 @@ size_t staged_lds_bytes(int M, int d, int mode) {
 namespace {
 int launch_reweight_resample(const float* loglik, const float* logw_in, const float* states_in, const float* u,
                              float* estimate, float* states_out, float* logw_out, int32_t* indices_out, int N,
-                             int M, int M_out, int d, int mode, float alpha, void* stream) {
+                             int M, int M_out, int d, int mode, float alpha, BeliefOut rec, void* stream) {
   if (!loglik || !states_in || !estimate) return MMF_EINVAL;
   if (N < 0 || M < 1 || M_out < 1 || d < 1 || d > MMF_MAX_STATE_DIM || mode < 0 || mode > 2) return MMF_EINVAL;
   // the uniform-weight shortcuts (null logw_in / logw_out) belong to plain resampling
@@ -441,13 +494,20 @@ int launch_reweight_resample(const float* loglik, const float* logw_in, const fl
   if (M > 65536 || M_out > 65536) return MMF_ETOOLARGE;
   size_t lds = mmf_pf_reweight_resample_lds_bytes(M, mode);
   if (lds > 160 * 1024) return MMF_ETOOLARGE;
+  // a recording call keeps its sums' reduction rows behind everything else in LDS (the non-recording layout and
+  // limits are untouched): M <= 20,200 in modes 1/2, 40,500 in mode 0
+  const bool recording = rec.cov || rec.ess || rec.log_evidence;
+  const size_t rec_sz = recording ? mmf::k1_belief_lds_bytes() : 0;
+  if (((lds + 15) & ~static_cast<size_t>(15)) + rec_sz > 160 * 1024) return MMF_ETOOLARGE;
   if (N == 0) return 0;
   const bool soft = mode != 0 && alpha < 1.f;
   // stage the states in LDS when occupancy does not pay for it: always if every trajectory gets
   // a CU of its own (N <= 256), otherwise only while two workgroups still fit a CU (<= 80 KB each)
-  const size_t staged = staged_lds_bytes(M, d, mode);
+  const size_t staged = recording ? ((staged_lds_bytes(M, d, mode) + 15) & ~static_cast<size_t>(15)) + rec_sz
+                                  : staged_lds_bytes(M, d, mode);
   const bool stage = mode != 0 && (N <= 256 ? staged <= 160 * 1024 : staged <= 80 * 1024);
   if (stage) lds = staged;
+  else if (recording) lds = ((lds + 15) & ~static_cast<size_t>(15)) + rec_sz;
   // enough threads to give each one a float4 of work, at least one wave
   int block = ((M + 3) / 4 + MMF_WAVE - 1) / MMF_WAVE * MMF_WAVE;
   if (block > kBlock) block = kBlock;
@@ -457,7 +517,7 @@ int launch_reweight_resample(const float* loglik, const float* logw_in, const fl
   if (mode == 1 && !soft && (d == 2 || d == 3)) {
     // few trajectories (round 6): a cluster of workgroups per trajectory, two meetings through L2, the same bits
     int dev = 0, cus = 0;
-    if (g_cluster_enabled && hipGetDevice(&dev) == hipSuccess &&
+    if (g_cluster_enabled && !recording && hipGetDevice(&dev) == hipSuccess &&
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) {
       const int C = cluster::plan(N, M, M_out, cus);
       if (C > 0) {
@@ -496,23 +556,27 @@ int launch_reweight_resample(const float* loglik, const float* logw_in, const fl
     const size_t slots = (static_cast<size_t>(M) * 8 + 15) & ~static_cast<size_t>(15);
     const size_t sc_sz = (sizeof(Scratch) + 15) & ~static_cast<size_t>(15);
     const size_t marks_sz = ((static_cast<size_t>(M_out) + 4) * 4 + 15) & ~static_cast<size_t>(15);
-    const size_t base_sz = slots + sc_sz + marks_sz;
-    const size_t with_states = base_sz + static_cast<size_t>(M) * d * sizeof(float);
+    const size_t base_sz = slots + sc_sz + marks_sz + rec_sz;
+    const size_t xs_sz = static_cast<size_t>(M) * d * sizeof(float);
+    const size_t with_states = base_sz + (recording ? (xs_sz + 15) & ~static_cast<size_t>(15) : xs_sz);
     if (base_sz <= 160 * 1024) {
       const bool st = N <= 256 ? with_states <= 160 * 1024 : with_states <= 80 * 1024;
       const size_t bytes = st ? with_states : base_sz;
-#define MMF_K1S_LAUNCH(D, ST)                                                                        \
+#define MMF_K1S_LAUNCH(D, ST, RC)                                                                    \
   {                                                                                                  \
     if (bytes > 64 * 1024) {                                                                         \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pf_resample_systematic_kernel<D, ST>), \
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pf_resample_systematic_kernel<D, ST, RC>), \
                                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes)); \
       if (e != hipSuccess) return static_cast<int>(e);                                               \
     }                                                                                                \
-    pf_resample_systematic_kernel<D, ST><<<N, block, bytes, s>>>(loglik, logw_in, states_in, u, estimate, states_out, \
-                                                                 logw_out, indices_out, M, M_out, lw_uniform, log_uniform); \
+    pf_resample_systematic_kernel<D, ST, RC><<<N, block, bytes, s>>>(loglik, logw_in, states_in, u, estimate, states_out, \
+                                                                 logw_out, indices_out, M, M_out, lw_uniform, log_uniform, rec); \
   }
-#define MMF_K1S(D) \
-  case D: { if (st) MMF_K1S_LAUNCH(D, true) else MMF_K1S_LAUNCH(D, false) } break;
+#define MMF_K1S(D)                                                                                   \
+  case D: {                                                                                          \
+    if (recording) { if (st) MMF_K1S_LAUNCH(D, true, true) else MMF_K1S_LAUNCH(D, false, true) }     \
+    else if (st) MMF_K1S_LAUNCH(D, true, false) else MMF_K1S_LAUNCH(D, false, false)                 \
+  } break;
       switch (d) { MMF_K1S(1) MMF_K1S(2) MMF_K1S(3) MMF_K1S(4) }
 #undef MMF_K1S
 #undef MMF_K1S_LAUNCH
@@ -520,26 +584,29 @@ int launch_reweight_resample(const float* loglik, const float* logw_in, const fl
       return 0;
     }
   }
-#define MMF_K1_LAUNCH(D, ST, SO)                                                               \
+#define MMF_K1_LAUNCH(D, ST, SO, RC)                                                           \
   {                                                                                            \
     if (lds > 64 * 1024) {                                                                     \
       hipError_t e = hipFuncSetAttribute(                                                      \
-          reinterpret_cast<const void*>(&pf_reweight_resample_kernel<D, ST, SO>),              \
+          reinterpret_cast<const void*>(&pf_reweight_resample_kernel<D, ST, SO, RC>),          \
           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));                  \
       if (e != hipSuccess) return static_cast<int>(e);                                         \
     }                                                                                          \
-    pf_reweight_resample_kernel<D, ST, SO><<<N, block, lds, s>>>(loglik, logw_in, states_in, u, \
-        estimate, states_out, logw_out, indices_out, M, M_out, mode, alpha, lw_uniform, log_uniform); \
+    pf_reweight_resample_kernel<D, ST, SO, RC><<<N, block, lds, s>>>(loglik, logw_in, states_in, u, \
+        estimate, states_out, logw_out, indices_out, M, M_out, mode, alpha, lw_uniform, log_uniform, rec); \
+  }
+#define MMF_K1_SS(D, RC)                                                                       \
+  {                                                                                            \
+    if (soft) { if (stage) MMF_K1_LAUNCH(D, true, true, RC) else MMF_K1_LAUNCH(D, false, true, RC) } \
+    else if (stage) MMF_K1_LAUNCH(D, true, false, RC) else MMF_K1_LAUNCH(D, false, false, RC)  \
   }
 #define MMF_K1(D)                                                                              \
-  case D: {                                                                                    \
-    if (soft) { if (stage) MMF_K1_LAUNCH(D, true, true) else MMF_K1_LAUNCH(D, false, true) }   \
-    else if (stage) MMF_K1_LAUNCH(D, true, false) else MMF_K1_LAUNCH(D, false, false)          \
-  } break;
+  case D: { if (recording) MMF_K1_SS(D, true) else MMF_K1_SS(D, false) } break;
   switch (d) {
     MMF_K1(1) MMF_K1(2) MMF_K1(3) MMF_K1(4)
   }
 #undef MMF_K1
+#undef MMF_K1_SS
 #undef MMF_K1_LAUNCH
   MMF_CHECK_LAUNCH();
   return 0;
@@ -608,8 +675,8 @@ extern "C" int mmf_pf_reweight_resample(const float* loglik, const float* logw_i
                                         const float* states_in, const float* u, float* estimate,
                                         float* states_out, float* logw_out, int32_t* indices_out,
                                         int N, int M, int M_out, int d, int mode, void* stream) {
-  return launch_reweight_resample(loglik, logw_in, states_in, u, estimate, states_out, logw_out, indices_out, N, M,
-                                  M_out, d, mode, 1.0f, stream);
+  return mmf_pf_reweight_resample_belief(loglik, logw_in, states_in, u, estimate, states_out, logw_out, indices_out, N, M,
+                                         M_out, d, mode, 1.0f, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int mmf_pf_reweight_resample_soft(const float* loglik, const float* logw_in,
@@ -618,6 +685,15 @@ extern "C" int mmf_pf_reweight_resample_soft(const float* loglik, const float* l
                                              int N, int M, int M_out, int d, int mode, float alpha,
                                              void* stream) {
   if (mode == 0) return MMF_EINVAL;
+  return mmf_pf_reweight_resample_belief(loglik, logw_in, states_in, u, estimate, states_out, logw_out, indices_out, N, M,
+                                         M_out, d, mode, alpha, nullptr, nullptr, nullptr, stream);
+}
+
+extern "C" int mmf_pf_reweight_resample_belief(const float* loglik, const float* logw_in, const float* states_in,
+                                               const float* u, float* estimate, float* states_out, float* logw_out,
+                                               int32_t* indices_out, int N, int M, int M_out, int d, int mode,
+                                               float alpha, float* cov, float* ess, float* log_evidence, void* stream) {
+  if (mode == 0 && alpha != 1.f) return MMF_EINVAL;  // soft resampling needs a resampling mode
   return launch_reweight_resample(loglik, logw_in, states_in, u, estimate, states_out, logw_out, indices_out, N, M,
-                                  M_out, d, mode, alpha, stream);
+                                  M_out, d, mode, alpha, BeliefOut{cov, ess, log_evidence}, stream);
 }

@@ -45,6 +45,67 @@ struct K1Scratch {  // lives behind the slots in dynamic LDS
   unsigned gave_up;  // COH: a reader timed out (zero on entry: the persistent loop's K1 workgroups clear it once)
 };
 
+// The belief record of a step (include/mmf.h, K1: covariance / ESS / log-evidence of the pre-resampling weighted set), compiled
+// in by the REC flag of the kernels below.  One pass, next to the estimate's sums and in the same partition (so every form
+// of K1 produces the same bits): with e_m = exp(a_m - max) and the FIRST highest-weight particle p as pivot,
+//   W2 = sum e^2,  m1_i = sum e (x_i - p_i),  M2_ij = sum e (x_i - p_i)(x_j - p_j)   (i >= j)
+//   covariance = M2 / S - (m1 / S)(m1 / S)^T,  ess = S^2 / W2,  log_evidence = max + log S.
+// Deviations from a particle inside the cloud keep fp32 meaningful where raw moments of O(1) states lose a 1e-3-wide
+// cloud entirely; the highest-weight particle is never far from the mass (a fixed particle is, once the weight collapses).
+// A particle of weight exp(-inf) contributes exactly nothing (detexp clamps it to 2^-126 for the resampler's CDF).
+template <int D>
+struct K1Belief {
+  static constexpr int kM2 = D * (D + 1) / 2;
+  static constexpr int kSums = 1 + D + kM2;
+  float s[kSums];  // [W2, m1[D], M2 (lower triangle, row by row)]
+  __device__ __forceinline__ void reset() {
+#pragma unroll
+    for (int k = 0; k < kSums; ++k) s[k] = 0.f;
+  }
+  __device__ __forceinline__ void add(float e, const float* x, const float* piv) {
+    s[0] = __builtin_fmaf(e, e, s[0]);
+    float dx[D];
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+      dx[i] = x[i] - piv[i];
+      s[1 + i] = __builtin_fmaf(e, dx[i], s[1 + i]);
+    }
+    int k = 1 + D;
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+      const float t = e * dx[i];
+#pragma unroll
+      for (int j = 0; j <= i; ++j, ++k) s[k] = __builtin_fmaf(t, dx[j], s[k]);
+    }
+  }
+};
+constexpr int kK1BeliefMaxSums = 1 + MMF_MAX_STATE_DIM + MMF_MAX_STATE_DIM * (MMF_MAX_STATE_DIM + 1) / 2;
+
+struct K1BeliefScratch {  // REC only: behind everything else in dynamic LDS (mmf::k1_belief_lds_bytes)
+  float red[kK1MaxWaves][kK1BeliefMaxSums];
+  float tot[kK1BeliefMaxSums];
+  float piv_wave[kK1MaxWaves];  // per wave: -(smallest index holding the row maximum), -inf: none
+};
+constexpr size_t k1_belief_lds_bytes() { return (sizeof(K1BeliefScratch) + 15) & ~static_cast<size_t>(15); }
+
+// the outputs of one trajectory, from the reduced sums (threads 0 .. D*D - 1 write; symmetric bit for bit: entry (i, j) and
+// (j, i) evaluate the same expression on the same operands)
+template <int D>
+__device__ __forceinline__ void k1_belief_store(const float* tot, float S, float mx, float* cov, float* ess, float* log_evidence, int tid) {
+#pragma clang fp contract(off)
+  if (cov != nullptr && tid < D * D) {
+    const int i = tid / D, j = tid % D;
+    const int hi = i > j ? i : j, lo = i > j ? j : i;
+    const float m2 = tot[1 + D + hi * (hi + 1) / 2 + lo];
+    const float bi = tot[1 + hi] / S, bj = tot[1 + lo] / S;
+    cov[tid] = m2 / S - bi * bj;
+  }
+  if (tid == 0) {
+    if (ess != nullptr) *ess = (S * S) / tot[0];
+    if (log_evidence != nullptr) *log_evidence = mx + logf(S);
+  }
+}
+
 __device__ __forceinline__ float ld_coherent(const float* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -71,6 +132,9 @@ struct K1Trajectory {  // pointers of ONE trajectory's rows
   const float* xs;       // (M, D) propagated particles; COH: granules (M, D)
   float u;               // this trajectory's uniform
   float* estimate;       // (D)
+  float* cov;            // REC: (D, D) covariance of the weighted set, or null
+  float* ess;            // REC: effective sample size, or null
+  float* log_evidence;   // REC: logsumexp of the unnormalised log-weights, or null
   float* so;             // (M_out, D) resampled particles; COH with so_tag != 0: granules (M_out, D) tagged so_tag
   float* lo;             // (M_out) or null (uniform by definition)
   int32_t* io;           // (M_out) ancestors or null
@@ -83,7 +147,7 @@ struct K1Trajectory {  // pointers of ONE trajectory's rows
 };
 
 // returns false (workgroup-uniform) when a COH reader gave up waiting for its granules
-template <int D, bool STAGE, bool COH, bool DET>
+template <int D, bool STAGE, bool COH, bool DET, bool REC = false>
 __device__ __forceinline__ bool resample_systematic_trajectory(unsigned char* smem, const K1Trajectory& a, int M, int M_out,
                                                                float lw_uniform, float log_uniform) {
   const size_t slots_sz = (static_cast<size_t>(M) * 8 + 15) & ~static_cast<size_t>(15);
@@ -93,6 +157,8 @@ __device__ __forceinline__ bool resample_systematic_trajectory(unsigned char* sm
   unsigned* marks = reinterpret_cast<unsigned*>(smem + slots_sz + sc_sz);                       // [M_out + 4]
   const size_t marks_sz = ((static_cast<size_t>(M_out) + 4) * 4 + 15) & ~static_cast<size_t>(15);
   float* xs_lds = reinterpret_cast<float*>(smem + slots_sz + sc_sz + marks_sz);                 // STAGE: [M][D]
+  const size_t xs_sz = STAGE ? (static_cast<size_t>(M) * D * sizeof(float) + 15) & ~static_cast<size_t>(15) : 0;
+  K1BeliefScratch& bsc = *reinterpret_cast<K1BeliefScratch*>(smem + slots_sz + sc_sz + marks_sz + xs_sz);  // REC
 
   const int tid = threadIdx.x;
   const int lane = tid & (MMF_WAVE - 1), wave = tid >> 6;
@@ -223,6 +289,7 @@ __device__ __forceinline__ bool resample_systematic_trajectory(unsigned char* sm
 
   // ---- pass 1: x_i = logw_i + loglik_i -> LDS, row max
   float mx = -INFINITY;
+  int mi = 0x7fffffff;  // REC: the first of this thread's particles that holds its maximum
   for (int base = 0; base < M; base += chunk) {
     const int i0 = base + tid * 4;
     float v[4];
@@ -239,20 +306,39 @@ __device__ __forceinline__ bool resample_systematic_trajectory(unsigned char* sm
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-      if (i0 + j < M) { reinterpret_cast<float*>(cdf + i0 + j)[0] = v[j]; mx = fmaxf(mx, v[j]); }
+      if (i0 + j < M) {
+        reinterpret_cast<float*>(cdf + i0 + j)[0] = v[j];
+        if constexpr (REC) { if (v[j] > mx || mi == 0x7fffffff) mi = i0 + j; }
+        mx = fmaxf(mx, v[j]);
+      }
   }
+  const float mx_thread = mx;
   mx = wave_max(mx);
   if (lane == 0) sc.red[wave][0] = mx;
   __syncthreads();
   mx = sc.red[0][0];
   for (int w = 1; w < nwaves; ++w) mx = fmaxf(mx, sc.red[w][0]);
+  if constexpr (REC) {  // the pivot: the smallest index holding the row maximum (indices < 2^24 are exact floats)
+    const float cand = wave_max((mi != 0x7fffffff && mx_thread == mx) ? -static_cast<float>(mi) : -INFINITY);
+    if (lane == 0) bsc.piv_wave[wave] = cand;
+  }
   __syncthreads();
+  float piv[D];
+  if constexpr (REC) {
+    float best = bsc.piv_wave[0];
+    for (int w = 1; w < nwaves; ++w) best = fmaxf(best, bsc.piv_wave[w]);
+    const int p = best > -INFINITY ? static_cast<int>(-best) : 0;  // (every value NaN: the filter is lost either way)
+#pragma unroll
+    for (int c = 0; c < D; ++c) piv[c] = state_at(static_cast<size_t>(p) * D + c);
+  }
   K1_STAMP(1);
 
   // ---- pass 2: e_i, fixed-point q_i, float sums of the estimate, integer CDF (kept in LDS for multi-chunk rows)
   float S = 0.f, acc[D];
 #pragma unroll
   for (int c = 0; c < D; ++c) acc[c] = 0.f;
+  K1Belief<D> bel;  // REC
+  if constexpr (REC) bel.reset();
   unsigned long long carry = 0;
   unsigned long long own[4] = {0, 0, 0, 0};  // CDF of this thread's particles in the LAST chunk
   unsigned long long own_prev = 0;           // ... and of the particle just before them
@@ -265,6 +351,7 @@ __device__ __forceinline__ bool resample_systematic_trajectory(unsigned char* sm
       S = 0.f;
 #pragma unroll
       for (int c = 0; c < D; ++c) acc[c] = 0.f;
+      if constexpr (REC) bel.reset();
     }
     if (base == 0) {
 #pragma unroll
@@ -294,6 +381,10 @@ __device__ __forceinline__ bool resample_systematic_trajectory(unsigned char* sm
       S += e[j];
 #pragma unroll
       for (int c = 0; c < D; ++c) acc[c] = __builtin_fmaf(e[j], st[j * D + c], acc[c]);  // explicit: oracle/strict restates this chain
+      if constexpr (REC) {
+        const float xv = ok ? reinterpret_cast<const float*>(cdf + i0 + j)[0] : -INFINITY;
+        bel.add(xv == -INFINITY ? 0.f : e[j], st + j * D, piv);
+      }
     }
     const unsigned long long incl = wave_inclusive_scan(tsum, lane);
     if (lane == MMF_WAVE - 1) sc.wave_tot[wave] = incl;
@@ -309,12 +400,26 @@ __device__ __forceinline__ bool resample_systematic_trajectory(unsigned char* sm
 #pragma unroll
         for (int c = 0; c < D; ++c) sc.red[row][1 + c] = aw[c];
       }
+      if constexpr (REC) {  // the record's sums: same partition, same order of the waves
+#pragma unroll
+        for (int k = 0; k < K1Belief<D>::kSums; ++k) {
+          const float bw = wave_sum(bel.s[k]);
+          if (lane == 0 && row < kK1MaxWaves) bsc.red[row][k] = bw;
+        }
+      }
     }
     __syncthreads();
     if (last_chunk && tid <= D) {
       float t = 0.f;
       for (int w = 0; w < nwaves_red; ++w) t += sc.red[w][tid];
       sc.bcast[tid] = t;
+    }
+    if constexpr (REC) {
+      if (last_chunk && tid < K1Belief<D>::kSums) {
+        float t = 0.f;
+        for (int w = 0; w < nwaves_red; ++w) t += bsc.red[w][tid];
+        bsc.tot[tid] = t;
+      }
     }
     unsigned long long before = carry, total = 0;
     for (int w = 0; w < nwaves; ++w) {
@@ -340,6 +445,7 @@ __device__ __forceinline__ bool resample_systematic_trajectory(unsigned char* sm
     const float est = sc.bcast[1 + tid] / S;
     a.estimate[tid] = est;
   }
+  if constexpr (REC) k1_belief_store<D>(bsc.tot, S, mx, a.cov, a.ess, a.log_evidence, tid);
 
   // ---- offspring boundaries: the first particle of every run of equal k_end announces itself,
   // marks[k_end(i - 1)] = i  when  k_end(i - 1) < k_end(i)  -- one writer per entry, plain LDS stores

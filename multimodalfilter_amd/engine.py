@@ -261,10 +261,12 @@ def run_persistent(a, call, *, n_sync_words: int, device, restore=()):
     return out
 
 
-def run_ekf_loop(nets, biases, q, z, r, mu, Sigma, *, fusion=0, feedback=0, fuse_w=None, gate=None):
+def run_ekf_loop(nets, biases, q, z, r, mu, Sigma, *, fusion=0, feedback=0, fuse_w=None, gate=None, Sigma_steps=None):
     """``mmf_ekf_forward_loop`` for ``K = len(nets)`` sub-filters: ``nets`` their dynamics networks (``PackedParticleNet``),
     ``biases`` the hoisted control terms ``(T*N, 64)``, ``q (K, d, d)``, ``z (T, K, N, d)``, ``r (T, K, N, d, d)``,
     ``mu (K, N, d)`` / ``Sigma (K, N, d, d)`` the belief, updated in place -> ``(estimates (T, N, d), Sigma_f | None)``.
+    ``Sigma_steps (T, N, d, d)`` or ``None``: every step's posterior covariance (fused, or sub-filter 0's for fusion 0),
+    written by whichever form runs.
     ONE persistent launch where the problem is eligible (``EKF_PERSISTENT``), else / after a give-up 2 T launches."""
     T, K, N, d = z.shape
     E = lambda *shape: torch.empty(shape, dtype=torch.float32, device=mu.device)
@@ -278,11 +280,13 @@ def run_ekf_loop(nets, biases, q, z, r, mu, Sigma, *, fusion=0, feedback=0, fuse
         a.dyn_packed[k], a.dyn_bias[k] = P(nets[k].blob(prec)), P(biases[k])
     a.q_tril, a.z, a.r_tril, a.fuse_w, a.feedback_gate = P(q), P(z), P(r), P(fuse_w), P(gate, torch.int32)
     a.mu, a.Sigma, a.mu_pred, a.A, a.Sigma_f, a.estimates = P(mu), P(Sigma), P(mu_pred), P(A), P(Sigma_f), P(est)
+    assert Sigma_steps is None or Sigma_steps.shape == (T, N, d, d)
     go = (EKF_PERSISTENT and not is_capturing() and T > 0 and d in (2, 3) and a.n_res_dyn == 3
           and _abi.ekf_persistent_plan(N, K) > 0)
     n_words = _abi.ekf_persistent_sync_words(N, K, d) if go else 0
     # (one sub-filter: no hand-offs, nothing can time out -> nothing to copy, nothing to ask)
-    run_persistent(a, lambda: _abi.ekf_forward_loop(a, mu), n_sync_words=n_words, device=mu.device,
+    call = (lambda: _abi.ekf_forward_loop(a, mu)) if Sigma_steps is None else (lambda: _abi.ekf_forward_loop(a, mu, Sigma_steps))
+    run_persistent(a, call, n_sync_words=n_words, device=mu.device,
                    restore=(mu, Sigma) if K > 1 else None)
     return est, Sigma_f
 

@@ -1,6 +1,7 @@
 """Evaluation harness: the role of ``/root/reference/crossmodal/eval_helpers.py:70-217`` on
 device-resident ``(T, N, ...)`` batches, plus the multi-GPU reduction of its error statistic.
 """
+import math
 from typing import Dict
 
 import numpy as np
@@ -12,20 +13,72 @@ START_TRUNCATION = 30
 
 
 def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale: float = 0.1,
-               measurement_initialize: bool = False) -> torch.Tensor:
+               measurement_initialize: bool = False, return_belief: bool = False):
     """Initialise the belief at ``states[0]`` with covariance ``0.1 I`` (or from the first
-    observation, ``eval_helpers.py:116-131``) and filter ``[1:]`` (``:139-142``)."""
+    observation, ``eval_helpers.py:116-131``) and filter ``[1:]`` (``:139-142``).
+    ``return_belief``: run with ``record_belief`` set and return ``(estimates, filter_model.last_belief)`` -- the per-step
+    posterior covariances (and the particle filter's ESS / log-evidence) for the calibration metrics below."""
     states = traj["states"]
     T1, N, d = states.shape
     obs = {k: traj[k] for k in ("image", "gripper_pos", "gripper_sensors")}
-    with torch.no_grad():
-        if measurement_initialize and hasattr(filter_model, "measurement_initialize_beliefs"):
-            filter_model.measurement_initialize_beliefs({k: v[0] for k, v in obs.items()})
-        else:
-            cov = (torch.eye(d, device=states.device) * initial_cov_scale)[None].expand(N, d, d)
-            filter_model.initialize_beliefs(mean=states[0], covariance=cov)
-        return filter_model.forward_loop(observations={k: v[1:] for k, v in obs.items()},
-                                         controls=traj["controls"][1:])
+    was = getattr(filter_model, "record_belief", None)
+    if return_belief:
+        assert was is not None, f"{type(filter_model).__name__} keeps no belief to record"
+        filter_model.record_belief = True
+    try:
+        with torch.no_grad():
+            if measurement_initialize and hasattr(filter_model, "measurement_initialize_beliefs"):
+                filter_model.measurement_initialize_beliefs({k: v[0] for k, v in obs.items()})
+            else:
+                cov = (torch.eye(d, device=states.device) * initial_cov_scale)[None].expand(N, d, d)
+                filter_model.initialize_beliefs(mean=states[0], covariance=cov)
+            est = filter_model.forward_loop(observations={k: v[1:] for k, v in obs.items()},
+                                            controls=traj["controls"][1:])
+    finally:
+        if return_belief:
+            filter_model.record_belief = was
+    return (est, filter_model.last_belief) if return_belief else est
+
+
+def _whitened_error(predicted: torch.Tensor, covariance: torch.Tensor, true: torch.Tensor):
+    """``(L^-1 e, L)`` with ``C = L L^T`` (Cholesky) and ``e = predicted - true``, batched over ``(T, N)``."""
+    L = torch.linalg.cholesky(covariance)
+    e = (predicted - true).to(covariance.dtype)
+    return torch.linalg.solve_triangular(L, e[..., None], upper=False)[..., 0], L
+
+
+def nees(predicted: torch.Tensor, covariance: torch.Tensor, true: torch.Tensor,
+         start: int = START_TRUNCATION) -> torch.Tensor:
+    """Normalised estimation error squared ``e^T C^-1 e`` of every step after the burn-in: ``(T, N, d)``, ``(T, N, d, d)``,
+    ``(T, N, d)`` -> ``(T - start, N)``.  Its mean is ``d`` for a calibrated filter (chi-square with ``d`` degrees)."""
+    y, _ = _whitened_error(predicted[start:], covariance[start:], true[start:])
+    return torch.sum(y * y, dim=-1)
+
+
+def gaussian_nll(predicted: torch.Tensor, covariance: torch.Tensor, true: torch.Tensor,
+                 start: int = START_TRUNCATION) -> torch.Tensor:
+    """Negative log-likelihood of the true state under ``N(predicted, covariance)``, mean over time after the burn-in:
+    ``0.5 (e^T C^-1 e + log det C + d log 2 pi)`` -> ``(N,)``, one number per trajectory."""
+    y, L = _whitened_error(predicted[start:], covariance[start:], true[start:])
+    logdet = 2.0 * torch.sum(torch.log(torch.diagonal(L, dim1=-2, dim2=-1)), dim=-1)
+    d = predicted.shape[-1]
+    return torch.mean(0.5 * (torch.sum(y * y, dim=-1) + logdet + d * math.log(2.0 * math.pi)), dim=0)
+
+
+def coverage(predicted: torch.Tensor, covariance: torch.Tensor, true: torch.Tensor, level: float = 0.95,
+             start: int = START_TRUNCATION) -> torch.Tensor:
+    """Share of the steps after the burn-in whose true state lies inside the ``level`` ellipsoid of the belief, i.e. whose
+    NEES is at most the ``level`` quantile of the chi-square distribution with ``d`` degrees -> ``(N,)``; ``level`` for a
+    calibrated filter.  The test is made on the CDF side, ``F_d(nees) <= level``: ``F_2(x) = 1 - exp(-x / 2)`` in closed
+    form, otherwise the regularised lower incomplete gamma ``P(d / 2, x / 2)`` (``torch.special.gammainc``)."""
+    assert 0.0 < level < 1.0
+    x = nees(predicted, covariance, true, start)
+    d = predicted.shape[-1]
+    if d == 2:
+        cdf = 1.0 - torch.exp(-0.5 * x)
+    else:
+        cdf = torch.special.gammainc(torch.full_like(x, 0.5 * d), 0.5 * x)
+    return torch.mean((cdf <= level).to(x.dtype), dim=0)
 
 
 def per_trajectory_mse(predicted: torch.Tensor, true: torch.Tensor,

@@ -36,6 +36,11 @@ class ParticleFilter(base.Filter):
     particle).  Both use the fixed-point CDF of ``csrc/pf_resample.hip``.
 
     Belief: ``particle_states (N, M, d)``, ``particle_log_weights (N, M)``.
+    ``record_belief = True``: every step also leaves the second moment of the belief it took its estimate from -- the
+    pre-resampling weighted set -- in ``last_belief``: ``covariance (N, d, d)`` about the weighted mean, ``ess (N)``,
+    ``log_evidence (N)`` (``include/mmf.h``, K1); after ``forward_loop`` with a leading ``T`` axis, written by the native
+    loops themselves (the persistent launch included).  Training (autograd) paths compute it with detached torch ops
+    from the particle tensors, step by step: correct, not fast.
     Randomness comes from ``self.noise`` (``utils.NoiseSource``), never from global RNG state.
     """
 
@@ -65,6 +70,8 @@ class ParticleFilter(base.Filter):
         self.last_resample_indices = None
         self.last_log_likelihoods = None
         self.last_log_weights_in = None
+        self.record_belief = False    # per-step covariance / ESS / log-evidence -> last_belief
+        self.last_belief = None
         self.use_native_loop = True   # False: forward_loop keeps the step-by-step Python loop
         self.particle_states: torch.Tensor = None
         self.particle_log_weights: torch.Tensor = None
@@ -182,6 +189,7 @@ class ParticleFilter(base.Filter):
                 self.last_log_likelihoods, self.last_log_weights_in = loglik, self.particle_log_weights
 
             estimate = torch.empty((N, d), dtype=torch.float32, device=states.device)
+            rec = self._new_belief_record((N,), d, states.device) if self.record_belief else None
             if do_resample:
                 Mo = self.num_particles
                 mode = _MODES[self.resample_mode]
@@ -194,17 +202,27 @@ class ParticleFilter(base.Filter):
                 idx = (torch.empty((N, Mo), dtype=torch.int32, device=states.device)
                        if self.record_indices else None)
                 lw_in = self.particle_log_weights
-                _timed("pf_reweight_resample", 0.0, N * M * 4.0 * (2 + d) + N * Mo * 4.0 * d,
-                       lambda: _abi.pf_reweight_resample(loglik, lw_in, states, u, estimate,
-                                                         out, logw_out, idx, mode, self.soft_resample_alpha))
+                if rec is None:
+                    k1 = lambda: _abi.pf_reweight_resample(loglik, lw_in, states, u, estimate,
+                                                           out, logw_out, idx, mode, self.soft_resample_alpha)
+                else:
+                    k1 = lambda: _abi.pf_reweight_resample_belief(loglik, lw_in, states, u, estimate, out, logw_out, idx, mode,
+                                                                  self.soft_resample_alpha, cov=rec.covariance, ess=rec.ess,
+                                                                  log_evidence=rec.log_evidence)
+                _timed("pf_reweight_resample", 0.0, N * M * 4.0 * (2 + d) + N * Mo * 4.0 * d, k1)
                 self._spare_states = states
                 self.last_resample_indices = idx
             else:
                 out, logw_out = states, torch.empty_like(loglik)
                 if states.data_ptr() != self.particle_states.data_ptr():
                     self._spare_states = self.particle_states  # the old belief is the next scratch
-                _abi.pf_reweight_resample(loglik, self.particle_log_weights, states, None, estimate,
-                                          None, logw_out, None, 0)
+                if rec is None:
+                    _abi.pf_reweight_resample(loglik, self.particle_log_weights, states, None, estimate,
+                                              None, logw_out, None, 0)
+                else:
+                    _abi.pf_reweight_resample_belief(loglik, self.particle_log_weights, states, None, estimate, None, logw_out,
+                                                     None, 0, cov=rec.covariance, ess=rec.ess, log_evidence=rec.log_evidence)
+            self.last_belief = rec
             if self.estimation_method == "argmax":
                 # arg-max of the *pre-resampling* normalised weights
                 tot = self.particle_log_weights + loglik
@@ -213,6 +231,24 @@ class ParticleFilter(base.Filter):
             self.particle_states = out
             self.particle_log_weights = logw_out
         return estimate
+
+    @staticmethod
+    def _new_belief_record(lead, d, device):
+        E = lambda *shape: torch.empty(tuple(lead) + shape, dtype=torch.float32, device=device)
+        return base.belief_record(covariance=E(d, d), ess=E(), log_evidence=E())
+
+    @staticmethod
+    def _belief_record_torch(states, logw_in, loglik):
+        """The belief record from the particle tensors with detached torch ops in fp64 (the training paths)."""
+        with torch.no_grad():
+            a = (logw_in + loglik).detach().double()
+            lev = torch.logsumexp(a, dim=1)
+            w = torch.exp(a - lev[:, None])
+            x = states.detach().double()
+            dx = x - torch.sum(w[:, :, None] * x, dim=1, keepdim=True)
+            cov = torch.einsum("nm,nmi,nmj->nij", w, dx, dx)
+            return base.belief_record(covariance=cov.float(), ess=(1.0 / torch.sum(w * w, dim=1)).float(),
+                                      log_evidence=lev.float())
 
     def _step_autograd(self, observations, controls, dyn_bias=None, meas_ctx=None) -> torch.Tensor:
         """Differentiable torch formulation of the step (training backend "autograd"): gradients
@@ -240,6 +276,8 @@ class ParticleFilter(base.Filter):
             loglik = self.measurement_model.forward_encoded_autograd(states, meas_ctx)
         else:
             loglik = self.measurement_model(states=states, observations=observations)
+        self.last_belief = (self._belief_record_torch(states, self.particle_log_weights, loglik)
+                            if self.record_belief else None)
         if engine.use_hip_backward() and self.estimation_method == "weighted_average":
             # K6: reweight + normalise + estimate forward (K1 mode 0) and backward in HIP
             estimate, logw = engine.ReweightEstimateFunction.apply(loglik, self.particle_log_weights, states)
@@ -331,6 +369,10 @@ class ParticleFilter(base.Filter):
             if mode != 0:
                 self.last_resample_indices = torch.empty((T, N, M), dtype=torch.int32, device=dev)
                 a.indices_steps = P(self.last_resample_indices, torch.int32)
+        self.last_belief = None
+        if self.record_belief:  # written by K1 in every form of the loop; does not change which form runs
+            self.last_belief = rec = self._new_belief_record((T, N), d, dev)
+            a.cov_steps, a.ess_steps, a.log_evidence_steps = P(rec.covariance), P(rec.ess), P(rec.log_evidence)
         a.range_flag = P(engine.range_flag(dev), torch.int32)
         if do_resample and self.soft_resample_alpha < 1.0:
             a.soft_alpha = float(self.soft_resample_alpha)  # survivors carry importance weights (mmf_pf_reweight_resample_soft)
@@ -377,7 +419,8 @@ class ParticleFilter(base.Filter):
         dyn, meas = self.dynamics_model, self.measurement_model
         do_resample = (not self.training) if self.resample is None else bool(self.resample)
         if (dyn_all is None or meas_all is None or not hasattr(dyn, "_net") or not hasattr(meas, "train_plan")
-                or do_resample or self.estimation_method != "weighted_average" or T == 0 or not self.use_native_loop):
+                or do_resample or self.estimation_method != "weighted_average" or T == 0 or not self.use_native_loop
+                or self.record_belief):  # (the training recursion keeps no per-step record: the step loop computes it)
             return None
         assert self._initialized, "Particle filter not initialized!"
         Nb, M, d = self.particle_states.shape
@@ -439,13 +482,16 @@ class ParticleFilter(base.Filter):
             native = self._native_train_loop(dyn_all, meas_all, T, N)
             if native is not None:
                 return native
-            out = []
+            out, beliefs = [], []
             for t in range(T):
                 sl = slice(t * N, (t + 1) * N)
                 out.append(self._step_autograd(
                     tree_index(observations, t), tree_index(controls, t),
                     None if dyn_all is None else dyn_all[sl],
                     None if meas_all is None else {k: v[sl] for k, v in meas_all.items()}))
+                beliefs.append(self.last_belief)
+            if self.record_belief:
+                self.last_belief = base.stack_belief_records(beliefs)
             return torch.stack(out, dim=0)
         obs_all = ctrl_all = None
         with torch.no_grad():
@@ -456,20 +502,25 @@ class ParticleFilter(base.Filter):
             native = self._native_loop(obs_all, ctrl_all, T, N)
         if native is not None:
             return native
-        out = []
+        out, beliefs = [], []
         for t in range(T):
             sl = slice(t * N, (t + 1) * N)
             out.append(self._step(
                 tree_index(observations, t), tree_index(controls, t),
                 None if obs_all is None else {k: v[sl] for k, v in obs_all.items()},
                 None if ctrl_all is None else {k: v[sl] for k, v in ctrl_all.items()}))
+            beliefs.append(self.last_belief)
+        if self.record_belief:
+            self.last_belief = base.stack_belief_records(beliefs)
         return torch.stack(out, dim=0)
 
 
 class VirtualSensorExtendedKalmanFilter(base.Filter):
     """EKF whose measurement is a learned virtual sensor ``(z, R^1/2)`` observed through
     ``C = I`` (T2).  predict: ``S- = A S A^T + L L^T`` with ``A`` the dynamics Jacobian;
-    correct: ``K = S-(S- + R)^-1``, ``mu = mu- + K(z - mu-)``, ``S = (I - K) S-``."""
+    correct: ``K = S-(S- + R)^-1``, ``mu = mu- + K(z - mu-)``, ``S = (I - K) S-``.
+    ``record_belief = True``: ``last_belief.covariance`` is the posterior covariance as every step leaves it --
+    ``(N, d, d)`` after ``forward``, ``(T, N, d, d)`` after ``forward_loop`` (written by the native loop itself)."""
 
     def __init__(self, *, dynamics_model: base.DynamicsModel,
                  virtual_sensor_model: base.VirtualSensorModel):
@@ -481,6 +532,11 @@ class VirtualSensorExtendedKalmanFilter(base.Filter):
         self._belief_mean = None
         self._belief_covariance = None
         self._initialized = False
+        self.record_belief = False
+        self.last_belief = None
+
+    def _record_step_belief(self):
+        self.last_belief = base.belief_record(covariance=self._belief_covariance.detach()) if self.record_belief else None
 
     @property
     def belief_mean(self):
@@ -533,6 +589,7 @@ class VirtualSensorExtendedKalmanFilter(base.Filter):
                           r_tril.to(torch.float32).reshape(1, N, d, d).contiguous(), None,
                           mu, Sigma, None, None, fusion=0, feedback=0)
             self._belief_mean, self._belief_covariance = mu[0], Sigma[0]
+        self._record_step_belief()
         return self._belief_mean
 
     def _step_autograd(self, observations, controls):
@@ -556,11 +613,13 @@ class VirtualSensorExtendedKalmanFilter(base.Filter):
             # K6: the Kalman algebra forward (K3) and backward (closed-form adjoints) in HIP; the
             # networks around it (sensor, dynamics, Jacobian) keep their autograd form
             self._belief_mean, self._belief_covariance = engine.EkfStepFunction.apply(A, mu_pred, L[0], z, r_tril, Sigma)
+            self._record_step_belief()
             return self._belief_mean
         Sp = A @ Sigma @ A.transpose(-1, -2) + L @ L.transpose(-1, -2)
         K = Sp @ torch.inverse(Sp + r_tril @ r_tril.transpose(-1, -2))
         self._belief_mean = mu_pred + (K @ (z - mu_pred)[:, :, None]).squeeze(-1)
         self._belief_covariance = (torch.eye(K.shape[-1], device=K.device) - K) @ Sp
+        self._record_step_belief()
         return self._belief_mean
 
     @engine.checked_step
@@ -584,8 +643,10 @@ class VirtualSensorExtendedKalmanFilter(base.Filter):
         mu = self._belief_mean.reshape(1, N, d).contiguous().clone()
         Sigma = self._belief_covariance.reshape(1, N, d, d).contiguous().clone()
         q = dyn.scale_tril().to(torch.float32).reshape(1, d, d).contiguous()
-        est, _ = engine.run_ekf_loop([dyn._net], [ctrl_all["bias"]], q, z, r, mu, Sigma)
+        steps = torch.empty((T, N, d, d), dtype=torch.float32, device=mu.device) if self.record_belief else None
+        est, _ = engine.run_ekf_loop([dyn._net], [ctrl_all["bias"]], q, z, r, mu, Sigma, Sigma_steps=steps)
         self._belief_mean, self._belief_covariance = mu[0], Sigma[0]
+        self.last_belief = base.belief_record(covariance=steps) if self.record_belief else None
         return est
 
     @engine.checked_loop
@@ -602,11 +663,14 @@ class VirtualSensorExtendedKalmanFilter(base.Filter):
             if native is not None:
                 return native
             sensors = [self.virtual_sensor_model(observations=tree_index(observations, t)) for t in range(T)]
-        out = []
+        out, beliefs = [], []
         for t in range(T):
             sl = slice(t * N, (t + 1) * N)
             out.append(self._step(tree_index(observations, t), tree_index(controls, t), sensors[t],
                                   None if ctrl_all is None else {k: v[sl] for k, v in ctrl_all.items()}))
+            beliefs.append(self.last_belief)
+        if self.record_belief:
+            self.last_belief = base.stack_belief_records(beliefs)
         return torch.stack(out, dim=0)
 
 
@@ -710,6 +774,7 @@ class VirtualSensorUnscentedKalmanFilter(VirtualSensorExtendedKalmanFilter):
                           r_tril.to(torch.float32).reshape(1, N, d, d).contiguous(), None,
                           mu, Sigma, None, None, fusion=0, feedback=0)
             self._belief_mean, self._belief_covariance = mu[0], Sigma[0]
+        self._record_step_belief()
         return self._belief_mean
 
     def _step_autograd(self, observations, controls):
@@ -731,12 +796,15 @@ class VirtualSensorUnscentedKalmanFilter(VirtualSensorExtendedKalmanFilter):
                 sensors = [(z[t * N:(t + 1) * N], r[t * N:(t + 1) * N]) for t in range(T)]
             else:
                 sensors = [self.virtual_sensor_model(observations=tree_index(observations, t)) for t in range(T)]
-        out = []
+        out, beliefs = [], []
         not_pd = torch.zeros(1, dtype=torch.int32, device=self._belief_mean.device)  # one flag, one read per loop
         for t in range(T):
             sl = slice(t * N, (t + 1) * N)
             out.append(self._step(tree_index(observations, t), tree_index(controls, t), sensors[t],
                                   None if ctrl_all is None else {k: v[sl] for k, v in ctrl_all.items()}, not_pd))
+            beliefs.append(self.last_belief)
+        if self.record_belief:  # the per-step posterior covariances, stacked on the device
+            self.last_belief = base.stack_belief_records(beliefs)
         if T > 0 and int(not_pd.item()):
             raise ValueError("unscented predict: belief covariance is not positive definite")
         return torch.stack(out, dim=0)
