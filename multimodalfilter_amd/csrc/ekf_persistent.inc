@@ -16,9 +16,9 @@
 // of the K roles meet once per step and trajectory through 8-byte {value, tag} granules in L2 (pf_persistent.inc's
 // hand-off: the data is the flag), two slots by step parity: a role can be at most one step ahead of a role it waits for.
 //
-// Same bits as the loop of launches: the tile is particle_net_kernel<D, 3, kJacobian, 1, PREC, 2>'s statements (a
-// column does not depend on what else sits in its tile), the algebra is ekf_algebra.h's functions, which ekf_step_kernel
-// calls too (tests/test_gpu_models.py::test_persistent_ekf_loop_equals_loop_of_launches).
+// Same bits as the loop of launches: jacobian_tile and particle_net_kernel<D, 3, kJacobian, 1, PREC, 2> call the same
+// network pieces of particle_net_tiles.h (a column does not depend on what else sits in its tile), the algebra is
+// ekf_algebra.h's functions, which ekf_step_kernel calls too (tests/test_gpu_models.py::test_persistent_ekf_loop_equals_loop_of_launches).
 
 #include "ekf_algebra.h"
 
@@ -55,6 +55,9 @@ __device__ __forceinline__ float quad_lane(float x) {  // lane (l & ~3) + Q of e
 
 // One Jacobian tile: 32 columns = 8 trajectories x {primal, e_1 .. e_3}; x: the trajectory's mean, the same in every lane of
 // its quad and in both lane halves.  Out, in every lane of the quad: x' = f(x) and A = d x' / d x.
+// Built from particle_net_tiles.h's pieces, as particle_net_kernel<D, 3, kJacobian, 1, PREC, 2> is: first_layer,
+// seed_nonfinite, net_unpipelined (join_init from this step's row), report_range, head, jacobian_outputs.  Its own: the
+// first-layer operands come from the register mean, the outputs are broadcast across the quad into Mat<D>.
 template <int D, int PREC>
 __device__ __forceinline__ void jacobian_tile(const float* __restrict__ lds, const float* __restrict__ traj_bias_row,
                                               const float (&x)[D], int lane, float neg_one, int* range_flag,
@@ -65,7 +68,7 @@ __device__ __forceinline__ void jacobian_tile(const float* __restrict__ lds, con
   const int j = lane & 31, h = lane >> 5;
   const int role = j & 3;
   const bool primal = role == 0;
-  float b0[KS0];
+  float b0[KS0][1];
 #pragma unroll
   for (int s = 0; s < KS0; ++s) {
     const int comp = 2 * s + h;
@@ -73,90 +76,22 @@ __device__ __forceinline__ void jacobian_tile(const float* __restrict__ lds, con
 #pragma unroll
     for (int i = 0; i < D; ++i) v = comp == i ? x[i] : v;
     const float prim = comp < D ? v : (comp == D ? 1.f : 0.f);
-    b0[s] = primal ? prim : ((comp == role - 1) ? 1.f : 0.f);
+    b0[s][0] = primal ? prim : ((comp == role - 1) ? 1.f : 0.f);
   }
   Act<1> X, H;
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) X.v[t][0][r] = 0.f;
-#pragma unroll
-  for (int s = 0; s < KS0; ++s) {
-    const int comp = 2 * s + h;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const float w = lds[off_w0() + (32 * t + j) * kW0Cols + comp];
-      X.v[t][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(w, b0[s], X.v[t][0], 0, 0, 0);
-    }
-  }
-  relu<1, true>(X, primal);
-  SplitAct<F16 ? 1 : 0> SP;
+  first_layer<1>(lds, b0, X, lane);
   short2v amax = {0, 0};
-  if constexpr (F16) {
-    bool bad = false;
+  if constexpr (F16) seed_nonfinite<1>(b0, amax);
+  net_unpipelined<1, NRES, kJacobian, PREC>(lds, X, H, [&](Act<1>& acc) {
+    join_init<1>(acc, 0, load_join_row(traj_bias_row, lane), primal);
+  }, lane, neg_one, amax, primal);
+  if constexpr (F16) report_range(range_flag, amax);
+  float out[NOUT][1], mine[NOUT], own[D];
+  head<NRES>(lds, H, lane, out);
 #pragma unroll
-    for (int s = 0; s < KS0; ++s) bad |= !(fabsf(b0[s]) <= 3.0e38f);
-    if (bad) amax = short2v{0x7fff, 0x7fff};
-  }
-  if constexpr (F16) res_block_f16<1, false, true>(lds, NRES, 0, X, H, SP, lane, neg_one, amax, primal);
-  else res_block<1, true>(lds, NRES, 0, X, H, lane, primal);
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    const float* tb = traj_bias_row + 32 * t + 4 * h;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const f32x4 b = *reinterpret_cast<const f32x4*>(tb + 8 * g);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) H.v[t][0][4 * g + e] = !primal ? 0.f : b[e];
-    }
-  }
-  if constexpr (F16) {
-    split_act<1, true>(X, SP, neg_one, amax);
-    mfma_layer_f16<1>(lds + off_layers() + 2 * kLayerFloats, SP, H, lane);
-  } else {
-    mfma_layer<1>(lds + off_layers() + 2 * kLayerFloats, X, H, lane);
-  }
-#pragma unroll
-  for (int i = 0; i < NRES; ++i) {
-    if constexpr (F16) {
-      if (i == 0) res_block_f16<1, true, true>(lds, NRES, 3, H, X, SP, lane, neg_one, amax, primal);
-      else res_block_f16<1, false, true>(lds, NRES, 3 + 2 * i, H, X, SP, lane, neg_one, amax, primal);
-    } else {
-      res_block<1, true>(lds, NRES, 3 + 2 * i, H, X, lane, primal);
-    }
-  }
-  if constexpr (F16) {
-    if (range_flag != nullptr && (amax[0] >= kF16Saturated || amax[1] >= kF16Saturated)) atomicOr(range_flag, MMF_FLAG_RANGE);
-  }
-  float mine[NOUT];
-#pragma unroll
-  for (int o = 0; o < NOUT; ++o) {
-    float part = 0.f;
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const f32x4 w = *reinterpret_cast<const f32x4*>(lds + off_whead(NRES) + o * kUnits + 32 * t + 8 * g + 4 * h);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) part = __builtin_fmaf(w[e], H.v[t][0][4 * g + e], part);
-      }
-    mine[o] = part + __shfl_xor(part, 32);
-  }
-  const float* bh = lds + off_bhead(NRES);
-  float dirp[D], gatep;
-#pragma unroll
-  for (int i = 0; i < D; ++i) dirp[i] = quad_first(mine[i] + bh[i]);
-  gatep = quad_first(mine[D] + bh[D]);
-  const float sg = 1.0f / (1.0f + expf(-gatep));
+  for (int o = 0; o < NOUT; ++o) mine[o] = out[o][0];
   // this lane's own output: role 0 -> x'_i, role c + 1 -> column c of the Jacobian
-  float own[D];
-  const float dgate = mine[D];  // tangent columns carry no bias
-#pragma unroll
-  for (int i = 0; i < D; ++i) {
-    const float prim = jac_primal(x[i], dirp[i], sg);
-    const float dv = jac_tangent(mine[i], sg, dirp[i], dgate, (i == role - 1) ? 1.f : 0.f);
-    own[i] = primal ? prim : dv;
-  }
+  jacobian_outputs<D>(mine, lds + off_bhead(NRES), x, role, own);
 #pragma unroll
   for (int i = 0; i < D; ++i) {
     xp[i] = quad_lane<0>(own[i]);
@@ -268,7 +203,7 @@ __global__ __launch_bounds__(kEkfPersistThreads, 1) void ekf_persistent_loop_ker
             }
             if (__all(ok)) break;
             __builtin_amdgcn_s_sleep(1);
-            if ((++spins & 63u) == 0) {  // wave-uniform
+            if ((++spins & 63u) == 0) {  // wave-uniform; mirrors mmf::spin_stop (calling it here costs two more spilled SGPRs)
               int stop = 0;
               if (lane == 0) stop = (spins > mmf::kGranuleSpinLimit || __hip_atomic_load(a.abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) ? 1 : 0;
               if (__builtin_amdgcn_readfirstlane(stop)) { gave_up = true; break; }
@@ -283,10 +218,7 @@ __global__ __launch_bounds__(kEkfPersistThreads, 1) void ekf_persistent_loop_ker
             for (int jj = 0; jj < D; ++jj) Ss[kk].a[i][jj] = v[D + i * D + jj];
         }
         if (gave_up) {  // wave-uniform: the host discards this loop and re-runs it as launches (engine.run_persistent, MMF_FLAG_GAVE_UP)
-          if (lane == 0) {
-            __hip_atomic_store(a.abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (a.range_flag != nullptr) atomicOr(a.range_flag, MMF_FLAG_GAVE_UP);
-          }
+          if (lane == 0) mmf::give_up(a.abort_word, a.range_flag);
           return;
         }
       } else {

@@ -101,14 +101,10 @@ __device__ __forceinline__ Operand load_operand(const LstmKernelArgs& a, int lay
   return o;
 }
 
-// polls of a wave: true when it must give up (spin budget spent, or another workgroup gave up)
+// one failed poll of a wave: true when it must give up (spin budget spent, or another workgroup gave up)
 __device__ __forceinline__ bool spin_stop(const LstmKernelArgs& a, unsigned& spins, int lane) {
   __builtin_amdgcn_s_sleep(1);
-  if ((++spins & 63u) != 0) return false;
-  int stop = 0;
-  if (lane == 0)
-    stop = (spins > mmf::kGranuleSpinLimit || __hip_atomic_load(a.abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) ? 1 : 0;
-  return __builtin_amdgcn_readfirstlane(stop) != 0;
+  return mmf::spin_stop(a.abort_word, spins, lane);
 }
 
 // one wave's partial of a 32 x 32 gate tile: the k pairs [kp0, kp1) of the LDS weight slice against the operand columns
@@ -235,10 +231,7 @@ __global__ void __launch_bounds__(kThreads) lstm_rounds_kernel(LstmKernelArgs a)
       __hip_atomic_store(a.progress + g, static_cast<unsigned>(s + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   if (gave_up) {
-    if (tid == 0) {
-      __hip_atomic_store(a.abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (a.range_flag != nullptr) atomicOr(a.range_flag, MMF_FLAG_GAVE_UP);
-    }
+    if (tid == 0) mmf::give_up(a.abort_word, a.range_flag);
     return;
   }
 #pragma unroll

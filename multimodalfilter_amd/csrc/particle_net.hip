@@ -468,14 +468,8 @@ __global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(NetArgsMul
     }
     const bool primal = col_primal[0];  // same for every c: 32 is a multiple of 4
 
-    // ---- encoder layer 0: relu(W0 [x; 1]) as (kW0Cols / 2) k-steps
+    // ---- encoder layer 0: W0 [x; 1] (its ReLU opens the trunk)
     Act<CT> X, H;
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int c = 0; c < CT; ++c)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) X.v[t][c][r] = 0.f;
     float bcur[KS0][CT];
 #pragma unroll
     for (int s = 0; s < KS0; ++s)
@@ -483,34 +477,14 @@ __global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(NetArgsMul
       for (int c = 0; c < CT; ++c) bcur[s][c] = bnext[s][c];
     if (tile_next < ntiles) first_layer_inputs(tile_next, bnext);
     i_next = claim(i_next);
-#pragma unroll
-    for (int s = 0; s < KS0; ++s) {
-      const int comp = 2 * s + h;
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const float w = lds[off_w0() + (32 * t + j) * kW0Cols + comp];
-#pragma unroll
-        for (int c = 0; c < CT; ++c)
-          X.v[t][c] = __builtin_amdgcn_mfma_f32_32x32x2f32(w, bcur[s][c], X.v[t][c], 0, 0, 0);
-      }
-    }
-    relu<CT, JAC>(X, primal);
-
-    SplitAct<F16 ? CT : 0> SP;
+    first_layer<CT>(lds, bcur, X, lane);
     short2v amax = {0, 0};  // f16x3: largest hi halves handed to the MFMAs in this tile
-    if constexpr (F16) {
-      // a NaN / inf particle state: the first layer's exact-f32 MFMAs turn it into NaNs of either sign, and a
-      // negative NaN would pass the ReLU as 0 -- report the input itself (a handful of compares per tile)
-      bool bad = false;
-#pragma unroll
-      for (int s = 0; s < KS0; ++s)
-#pragma unroll
-        for (int c = 0; c < CT; ++c) bad |= !(fabsf(bcur[s][c]) <= 3.0e38f);
-      if (bad) amax = short2v{0x7fff, 0x7fff};
-    }
+    if constexpr (F16) seed_nonfinite<CT>(bcur, amax);
     if constexpr (PIPE) {
       constexpr int NL = 3 + 2 * NRES;  // 64x64 layers: encoder block, join, NRES trunk blocks
       FragPair frag;                    // weight fragments of the next MFMA group, in flight
+      SplitAct<CT> SP;
+      relu<CT, false>(X, true);
       // V(C, l): everything half C needs before layer l's MFMAs -- the ReLU that ends layer
       // l - 1, the operand split of layer l's input, the initial value of its accumulator.
       // Layers 0, 2, 3, 5, .. read X-or-H alternately: even position in a block reads the block
@@ -529,15 +503,7 @@ __global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(NetArgsMul
         } else if constexpr (l == 2) {     // join: H = traj_bias + W relu(X)
           relu_half<C>(X);
           split_half<C, false>(X, SP, neg_one, amax);
-          const float* tb = a.traj_bias + static_cast<size_t>(col_traj[C]) * kUnits + 4 * h;
-#pragma unroll
-          for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-              const f32x4 b = *reinterpret_cast<const f32x4*>(tb + 32 * t + 8 * g);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) H.v[t][C][4 * g + e] = b[e];
-            }
+          join_init<CT>(H, C, load_join_row(a.traj_bias + static_cast<size_t>(col_traj[C]) * kUnits, lane));
         } else if constexpr ((l - 3) % 2 == 0) {  // trunk block, first layer: X = b + W H
           constexpr bool kSigned = (l == 3 && KIND != kMeasure);  // no ReLU after the join (dynamics)
           // l == 3 consumes the per-trajectory term: its ReLU keeps a NaN / inf for the split to report (relu_sat)
@@ -581,84 +547,17 @@ __global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(NetArgsMul
       });
       relu_half<1>(H);
     } else {
-    // ---- encoder residual block (layers 0, 1)
-    if constexpr (F16) res_block_f16<CT, false, JAC>(lds, NRES, 0, X, H, SP, lane, neg_one, amax, primal);
-    else res_block<CT, JAC>(lds, NRES, 0, X, H, lane, primal);
+      // the per-trajectory hoisted half of the join layer arrives as its accumulator's initial value
+      net_unpipelined<CT, NRES, KIND, PREC>(lds, X, H, [&](Act<CT>& acc) {
+#pragma unroll
+        for (int c = 0; c < CT; ++c)
+          join_init<CT>(acc, c, load_join_row(a.traj_bias + static_cast<size_t>(col_traj[c]) * kUnits, lane), !JAC || primal);
+      }, lane, neg_one, amax, primal);
+    }
+    if constexpr (F16) report_range(a.range_flag, amax);  // engine.check_range raises: per forward_loop, and per step for a bare forward()
 
-    // ---- join layer (2): per-trajectory hoisted half arrives as the accumulator init
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int c = 0; c < CT; ++c) {
-        const float* tb = a.traj_bias + static_cast<size_t>(col_traj[c]) * kUnits + 32 * t + 4 * h;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const f32x4 b = *reinterpret_cast<const f32x4*>(tb + 8 * g);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) H.v[t][c][4 * g + e] = (JAC && !primal) ? 0.f : b[e];
-        }
-      }
-    if constexpr (F16) {
-      split_act<CT, JAC>(X, SP, neg_one, amax);
-      mfma_layer_f16<CT>(lds + off_layers() + 2 * kLayerFloats, SP, H, lane);
-    } else {
-      mfma_layer<CT>(lds + off_layers() + 2 * kLayerFloats, X, H, lane);
-    }
-    if (KIND == kMeasure) {
-      if constexpr (F16) {  // consumes the per-trajectory term: keep a NaN of either sign for the next split to report
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-          for (int c = 0; c < CT; ++c)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) H.v[t][c][r] = relu_keepnan(H.v[t][c][r]);
-      } else {
-        relu<CT, JAC>(H, primal);
-      }
-    }
-
-    // ---- residual trunk: activations now live in H, X is scratch
-#pragma unroll
-    for (int i = 0; i < NRES; ++i) {
-      // without a ReLU after the join layer (dynamics) the trunk's first split sees signed values
-      if constexpr (F16) {
-        if (i == 0 && KIND != kMeasure) res_block_f16<CT, true, JAC>(lds, NRES, 3, H, X, SP, lane, neg_one, amax, primal);
-        else res_block_f16<CT, false, JAC>(lds, NRES, 3 + 2 * i, H, X, SP, lane, neg_one, amax, primal);
-      }
-      else res_block<CT, JAC>(lds, NRES, 3 + 2 * i, H, X, lane, primal);
-    }
-
-    }
-    if constexpr (F16) {
-      // an operand beyond the f16 range cannot be split exactly: inner activations saturate at 65504 (relu_sat,
-      // hi = 0x7BFF), a non-finite state or per-trajectory term arrives as hi = inf / NaN (>= 0x7C00) and is
-      // clamped by the next relu_sat -- either way the tile's outputs stay finite and the flag says they are
-      // invalid (engine.check_range raises: per forward_loop, and per step for a bare forward())
-      if (a.range_flag != nullptr && (amax[0] >= kF16Saturated || amax[1] >= kF16Saturated))
-        atomicOr(a.range_flag, MMF_FLAG_RANGE);
-    }
-
-    // ---- head (64 -> NOUT) on the VALU: each lane holds 32 of the 64 features of its columns
     float out[NOUT][CT];
-#pragma unroll
-    for (int o = 0; o < NOUT; ++o) {
-      float part[CT];
-#pragma unroll
-      for (int c = 0; c < CT; ++c) part[c] = 0.f;
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const f32x4 w = *reinterpret_cast<const f32x4*>(
-              lds + off_whead(NRES) + o * kUnits + 32 * t + 8 * g + 4 * h);
-#pragma unroll
-          for (int c = 0; c < CT; ++c)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) part[c] = __builtin_fmaf(w[e], H.v[t][c][4 * g + e], part[c]);  // explicit: the strict mode's chain
-        }
-#pragma unroll
-      for (int c = 0; c < CT; ++c) out[o][c] = part[c] + __shfl_xor(part[c], 32);
-    }
+    head<NRES>(lds, H, lane, out);
 
     // ---- epilogue: lane l finalises column l of the tile (CT == 2) or column j (CT == 1, h == 0)
     float mine[NOUT];
@@ -678,7 +577,7 @@ __global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(NetArgsMul
     const bool active = my_row < a.R && (CT == 2 || h == 0);
     const float* bh = lds + off_bhead(NRES);
 
-    if (KIND == kMeasure) {
+    if constexpr (KIND == kMeasure) {
       if (active) {
         const int traj = my_row / a.M;
         float ll = mine[0] + bh[0];
@@ -695,57 +594,60 @@ __global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(NetArgsMul
         }
         a.loglik[my_row] = ll;
       }
-    } else if (KIND == kDynamics) {
+    } else if constexpr (KIND == kDynamics) {
       if (active) {
-        const float gate = mine[D] + bh[D];
-        float sg;
-        if constexpr (PREC == MMF_PREC_F32) sg = mmf_det_sigmoid(gate);
-        else sg = 1.0f / (1.0f + expf(-gate));
-        float xo[D], eps[D];
-        const bool noisy = a.noise != nullptr || a.noise_mode == 2;
-        if (a.noise_mode == 2) {
-          // counter-based noise: a pure function of (seed, step, trajectory, particle) -- nothing is read
-          float z[4];
-          const unsigned traj = static_cast<unsigned>(my_row / a.M);
-          mmf_philox_normal4(a.noise_seed, a.noise_step, a.noise_traj0 + traj, static_cast<unsigned>(my_row) - traj * a.M, z);
-#pragma unroll
-          for (int i = 0; i < D; ++i) eps[i] = z[i];
-        }
+        float xo[D], eps[D], xn[D];
 #pragma unroll
         for (int i = 0; i < D; ++i) {
           xo[i] = a.states_in[static_cast<size_t>(my_row) * D + i];
-          if (a.noise_mode != 2) eps[i] = a.noise ? a.noise[static_cast<size_t>(my_row) * D + i] : 0.f;
+          eps[i] = (a.noise_mode != 2 && a.noise) ? a.noise[static_cast<size_t>(my_row) * D + i] : 0.f;
         }
+        const unsigned traj = static_cast<unsigned>(my_row / a.M);
+        dynamics_update<D, PREC>(mine, bh, xo, eps, a.scale_tril, a.noise != nullptr || a.noise_mode == 2, a.noise_mode == 2,
+                                 a.noise_seed, a.noise_step, a.noise_traj0 + traj, static_cast<unsigned>(my_row) - traj * a.M, xn);
 #pragma unroll
-        for (int i = 0; i < D; ++i) {
-          float v = __builtin_fmaf(mine[i] + bh[i], sg, xo[i]);
-          if (noisy) {
-#pragma unroll
-            for (int k = 0; k < D; ++k) v = __builtin_fmaf(a.scale_tril[i * D + k], eps[k], v);
-          }
-          a.states_out[static_cast<size_t>(my_row) * D + i] = v;
-        }
+        for (int i = 0; i < D; ++i) a.states_out[static_cast<size_t>(my_row) * D + i] = xn[i];
       }
     } else {  // jacobian: primal column -> x', tangent column c -> d x' / d x_c
-      const int role = my_row & 3;
-      const int traj = my_row >> 2;
-      float dirp[D], gatep;
+      if constexpr (CT == 1 || F16) {
+        // mirrors jacobian_outputs: through the shared function the 32-column kernel took 16.2 us against 14.5 (32 trajectories)
+        // and the 64-column f16x3 d = 2 kernel spilled two more SGPRs; the 64-column f32 kernels spill less with it
+        // (profiles/net_tile/README.md)
+        const int role = my_row & 3;
+        const int traj = my_row >> 2;
+        float dirp[D], gatep;
 #pragma unroll
-      for (int i = 0; i < D; ++i) dirp[i] = quad_first(mine[i] + bh[i]);
-      gatep = quad_first(mine[D] + bh[D]);
-      const float sg = 1.0f / (1.0f + expf(-gatep));
-      if (active) {
-        if (role == 0) {
+        for (int i = 0; i < D; ++i) dirp[i] = quad_first(mine[i] + bh[i]);
+        gatep = quad_first(mine[D] + bh[D]);
+        const float sg = 1.0f / (1.0f + expf(-gatep));
+        if (active) {
+          if (role == 0) {
 #pragma unroll
-          for (int i = 0; i < D; ++i)
-            a.states_out[traj * D + i] = jac_primal(a.states_in[traj * D + i], dirp[i], sg);
-        } else if (role <= D) {
-          const float dgate = mine[D];  // tangent columns carry no bias
+            for (int i = 0; i < D; ++i)
+              a.states_out[traj * D + i] = jac_primal(a.states_in[traj * D + i], dirp[i], sg);
+          } else if (role <= D) {
+            const float dgate = mine[D];  // tangent columns carry no bias
 #pragma unroll
-          for (int i = 0; i < D; ++i) {
-            const float dv = jac_tangent(mine[i], sg, dirp[i], dgate, (i == role - 1) ? 1.f : 0.f);
-            a.jac[(static_cast<size_t>(traj) * D + i) * D + (role - 1)] = dv;
+            for (int i = 0; i < D; ++i) {
+              const float dv = jac_tangent(mine[i], sg, dirp[i], dgate, (i == role - 1) ? 1.f : 0.f);
+              a.jac[(static_cast<size_t>(traj) * D + i) * D + (role - 1)] = dv;
+            }
           }
+        }
+      } else {
+        const int my_col = my_row < a.R ? my_row : a.R - 1;  // (an inactive lane repeats the last column, as the tile does)
+        const int role = my_col & 3;
+        const int traj = my_col >> 2;
+        float x[D], own[D];
+#pragma unroll
+        for (int i = 0; i < D; ++i) x[i] = role == 0 ? a.states_in[traj * D + i] : 0.f;  // (only the primal column reads it)
+        jacobian_outputs<D>(mine, bh, x, role, own);
+        // role 0: row `traj` of states_out; role c + 1: column c of the trajectory's D x D block
+        float* dst = role == 0 ? a.states_out + traj * D : a.jac + static_cast<size_t>(traj) * D * D + (role - 1);
+        const int stride = role == 0 ? 1 : D;
+        if (active && role <= D) {
+#pragma unroll
+          for (int i = 0; i < D; ++i) dst[i * stride] = own[i];
         }
       }
     }
@@ -806,11 +708,11 @@ int launch_multi(const NetArgsMulti& m, int count, int d, int n_res, int precisi
     if (precision == MMF_PREC_F16X3) return launch_ct<D, NR, KIND, MMF_PREC_F16X3>(m, count, s); \
     return MMF_EINVAL;                                                               \
   }
-  if (KIND == kJacobian || KIND == kDynamics) {
+  if constexpr (KIND == kJacobian || KIND == kDynamics) {  // (constexpr: no kernel is instantiated for a depth its kind never has)
     MMF_CASE(2, 3) MMF_CASE(3, 3)
-    return MMF_EINVAL;
+  } else {
+    MMF_CASE(2, 2) MMF_CASE(3, 2)
   }
-  MMF_CASE(2, 2) MMF_CASE(3, 2)
 #undef MMF_CASE
   return MMF_EINVAL;
 }

@@ -8,8 +8,12 @@
 #include <utility>
 
 #include "mmf_common.h"
+#include "../../include/mmf_detmath.h"
+#include "../../include/mmf_philox.h"
 
 namespace {
+
+enum Kind { kDynamics = 0, kMeasure = 1, kJacobian = 2 };
 
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
@@ -68,8 +72,8 @@ __device__ __forceinline__ float quad_first(float x) {
   return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), 0x00, 0xf, 0xf, true));
 }
 
-// The epilogue of a Jacobian column group, spelled out (explicit fused multiply-adds, no implicit contraction): the launch
-// kernel and the persistent EKF loop (ekf_persistent.inc) must produce the same bits whatever surrounds these statements.
+// The arithmetic of a Jacobian column group's epilogue (jacobian_outputs), spelled out (explicit fused multiply-adds, no
+// implicit contraction): the launch kernel and the persistent EKF loop must produce the same bits whatever surrounds it.
 // x' = x + dir sigmoid(gate);  d x'_i / d x_c = d dir_i s + dir_i s (1 - s) d gate + [i == c]
 __device__ __forceinline__ float jac_primal(float x, float dir, float sg) {
 #pragma clang fp contract(off)
@@ -442,6 +446,194 @@ __device__ __forceinline__ void pin_mfma_valu_interleave() {
   }
 }
 
-enum Kind { kDynamics = 0, kMeasure = 1, kJacobian = 2 };
+// ------------------------------------------------------------------------------ the network, piece by piece
+// One body for the three forms that must agree bit for bit: particle_net_kernel (particle_net.hip: K2 dynamics, K2
+// measurement, K5 Jacobian), small_tile (pf_persistent.inc) and jacobian_tile (ekf_persistent.inc).  A caller keeps
+// what is its own -- where the first-layer inputs come from, when the per-trajectory row is requested, where the
+// outputs go -- and the PIPE / row-pipelined schedules keep their own trunks; everything else is here, once.
+
+// encoder layer 0, pre-activation: W0 [x; 1] as KS0 = (D + 2) / 2 k-steps; lane (j, h) feeds component 2s + h in b[s]
+template <int CT, int KS0>
+__device__ __forceinline__ void first_layer(const float* __restrict__ lds, const float (&b)[KS0][CT], Act<CT>& X, int lane) {
+  const int j = lane & 31, h = lane >> 5;
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int c = 0; c < CT; ++c)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) X.v[t][c][r] = 0.f;
+#pragma unroll
+  for (int s = 0; s < KS0; ++s) {
+    const int comp = 2 * s + h;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const float w = lds[off_w0() + (32 * t + j) * kW0Cols + comp];
+#pragma unroll
+      for (int c = 0; c < CT; ++c) X.v[t][c] = __builtin_amdgcn_mfma_f32_32x32x2f32(w, b[s][c], X.v[t][c], 0, 0, 0);
+    }
+  }
+}
+
+// f16x3: a NaN / inf particle state.  The first layer's exact-f32 MFMAs turn it into NaNs of either sign, and a
+// negative NaN would pass the ReLU as 0 -- report the input itself (a handful of compares per tile).
+template <int CT, int KS0>
+__device__ __forceinline__ void seed_nonfinite(const float (&b)[KS0][CT], short2v& amax) {
+  bool bad = false;
+#pragma unroll
+  for (int s = 0; s < KS0; ++s)
+#pragma unroll
+    for (int c = 0; c < CT; ++c) bad |= !(fabsf(b[s][c]) <= 3.0e38f);
+  if (bad) amax = short2v{0x7fff, 0x7fff};
+}
+
+// The join layer's accumulator starts from the hoisted per-trajectory term: the lane's 32 features of one (N, 64) row.
+// Request and use are separate so that a caller can ask for the row where the latency hides best.
+struct JoinRow {
+  f32x4 v[2][4];
+};
+__device__ __forceinline__ JoinRow load_join_row(const float* __restrict__ row, int lane) {
+  JoinRow r;
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) r.v[t][g] = *reinterpret_cast<const f32x4*>(row + 32 * t + 8 * g + 4 * (lane >> 5));
+  return r;
+}
+// column tile c of acc = the row; `keep` = false zeroes it (the tangent columns of a Jacobian group take no bias)
+template <int CT>
+__device__ __forceinline__ void join_init(Act<CT>& acc, int c, const JoinRow& r, bool keep = true) {
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc.v[t][c][4 * g + e] = keep ? r.v[t][g][e] : 0.f;
+}
+
+// The 64 x 64 layers, unpipelined.  On entry X holds the first layer's pre-activation; on exit H holds the trunk's
+// output, activated (what the head reads).  `join(acc)` writes the per-trajectory term of the join layer (join_init).
+// Same contract as rowpipe_net_f16 (particle_net.hip), which computes the same bits on another schedule.
+template <int CT, int NRES, int KIND, int PREC, class Join>
+__device__ __forceinline__ void net_unpipelined(const float* __restrict__ lds, Act<CT>& X, Act<CT>& H, Join&& join, int lane,
+                                                float neg_one, short2v& amax, bool primal) {
+  constexpr bool JAC = KIND == kJacobian, F16 = PREC == MMF_PREC_F16X3;
+  SplitAct<F16 ? CT : 0> SP;
+  relu<CT, JAC>(X, primal);
+  // ---- encoder residual block (layers 0, 1)
+  if constexpr (F16) res_block_f16<CT, false, JAC>(lds, NRES, 0, X, H, SP, lane, neg_one, amax, primal);
+  else res_block<CT, JAC>(lds, NRES, 0, X, H, lane, primal);
+  // ---- join layer (2)
+  join(H);
+  if constexpr (F16) {
+    split_act<CT, JAC>(X, SP, neg_one, amax);
+    mfma_layer_f16<CT>(lds + off_layers() + 2 * kLayerFloats, SP, H, lane);
+  } else {
+    mfma_layer<CT>(lds + off_layers() + 2 * kLayerFloats, X, H, lane);
+  }
+  if constexpr (KIND == kMeasure) {
+    if constexpr (F16) {  // consumes the per-trajectory term: keep a NaN of either sign for the next split to report
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int c = 0; c < CT; ++c)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) H.v[t][c][r] = relu_keepnan(H.v[t][c][r]);
+    } else {
+      relu<CT, JAC>(H, primal);
+    }
+  }
+  // ---- residual trunk: activations now live in H, X is scratch
+#pragma unroll
+  for (int i = 0; i < NRES; ++i) {
+    if constexpr (F16) {
+      // without a ReLU after the join layer (dynamics) the trunk's first split sees signed values
+      if (i == 0 && KIND != kMeasure) res_block_f16<CT, true, JAC>(lds, NRES, 3, H, X, SP, lane, neg_one, amax, primal);
+      else res_block_f16<CT, false, JAC>(lds, NRES, 3 + 2 * i, H, X, SP, lane, neg_one, amax, primal);
+    } else {
+      res_block<CT, JAC>(lds, NRES, 3 + 2 * i, H, X, lane, primal);
+    }
+  }
+}
+
+// f16x3: an operand beyond the f16 range cannot be split exactly.  Inner activations saturate at 65504 (relu_sat,
+// hi = 0x7BFF), a non-finite state or per-trajectory term arrives as hi = inf / NaN (>= 0x7C00) and is clamped by the
+// next relu_sat -- either way the tile's outputs stay finite and the flag says they are invalid (engine.check_range).
+__device__ __forceinline__ void report_range(int* range_flag, short2v amax) {
+  if (range_flag != nullptr && (amax[0] >= kF16Saturated || amax[1] >= kF16Saturated)) atomicOr(range_flag, MMF_FLAG_RANGE);
+}
+
+// head (64 -> NOUT) on the VALU, bias not included: each lane holds 32 of the 64 features of its columns, the two lane
+// halves meet in one shuffle.  Explicit fused multiply-adds in this order: oracle/strict restates the chain.
+template <int NRES, int NOUT, int CT>
+__device__ __forceinline__ void head(const float* __restrict__ lds, const Act<CT>& H, int lane, float (&out)[NOUT][CT]) {
+#pragma unroll
+  for (int o = 0; o < NOUT; ++o) {
+    float part[CT];
+#pragma unroll
+    for (int c = 0; c < CT; ++c) part[c] = 0.f;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const f32x4 w = *reinterpret_cast<const f32x4*>(lds + off_whead(NRES) + o * kUnits + 32 * t + 8 * g + 4 * (lane >> 5));
+#pragma unroll
+        for (int c = 0; c < CT; ++c)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) part[c] = __builtin_fmaf(w[e], H.v[t][c][4 * g + e], part[c]);
+      }
+#pragma unroll
+    for (int c = 0; c < CT; ++c) out[o][c] = part[c] + __shfl_xor(part[c], 32);
+  }
+}
+
+// Dynamics epilogue of one particle: x' = x + (dir + b) sigmoid(gate + b) + scale_tril eps.  mine: the head's D
+// directions and gate, bh: the head's bias, eps: the caller's noise row, replaced by the counter-based draw for
+// (seed, step, traj, particle) when `philox`; tril: D x D, row-major (a pointer or a register array).
+template <int D, int PREC, class Tril>
+__device__ __forceinline__ void dynamics_update(const float (&mine)[D + 1], const float* __restrict__ bh, const float (&x)[D],
+                                                float (&eps)[D], const Tril& tril, bool noisy, bool philox,
+                                                unsigned long long seed, unsigned step, unsigned traj, unsigned particle,
+                                                float (&xn)[D]) {
+  const float gate = mine[D] + bh[D];
+  float sg;
+  // exact-fp32 mode = the bit-reproducible mode: shared deterministic sigmoid (mmf_detmath.h)
+  if constexpr (PREC == MMF_PREC_F32) sg = mmf_det_sigmoid(gate);
+  else sg = 1.0f / (1.0f + expf(-gate));
+  if (philox) {
+    // counter-based noise: a pure function of (seed, step, trajectory, particle) -- nothing is read
+    float z[4];
+    mmf_philox_normal4(seed, step, traj, particle, z);
+#pragma unroll
+    for (int i = 0; i < D; ++i) eps[i] = z[i];
+  }
+#pragma unroll
+  for (int i = 0; i < D; ++i) {
+    float v = __builtin_fmaf(mine[i] + bh[i], sg, x[i]);
+    if (noisy) {
+#pragma unroll
+      for (int k = 0; k < D; ++k) v = __builtin_fmaf(tril[i * D + k], eps[k], v);
+    }
+    xn[i] = v;
+  }
+}
+
+// Jacobian epilogue of one column of a group {primal, e_1 .. e_3} (role = column & 3): the lane's own D values --
+// role 0: x'_i (x: the trajectory's state, read by role 0 only), role c + 1: d x'_i / d x_c.  Every lane of a quad calls it.
+template <int D>
+__device__ __forceinline__ void jacobian_outputs(const float (&mine)[D + 1], const float* __restrict__ bh, const float (&x)[D],
+                                                 int role, float (&own)[D]) {
+  float dirp[D];
+#pragma unroll
+  for (int i = 0; i < D; ++i) dirp[i] = quad_first(mine[i] + bh[i]);
+  const float gatep = quad_first(mine[D] + bh[D]);
+  const float sg = 1.0f / (1.0f + expf(-gatep));
+  const float dgate = mine[D];  // tangent columns carry no bias
+#pragma unroll
+  for (int i = 0; i < D; ++i) {
+    const float prim = jac_primal(x[i], dirp[i], sg);
+    const float dv = jac_tangent(mine[i], sg, dirp[i], dgate, (i == role - 1) ? 1.f : 0.f);
+    own[i] = role == 0 ? prim : dv;
+  }
+}
 
 }  // namespace

@@ -11,9 +11,9 @@
 // nothing else before K1, and K1 only a trajectory), so trajectories drift apart freely and no grid-wide barrier
 // exists.
 //
-// Same arithmetic as the launch path, bit for bit: a tile is 32 particles of one trajectory through the very
-// functions particle_net_kernel<D, NRES, KIND, 1, PREC, 2, false> (the small-problem variant of the launch path)
-// calls -- a particle's column does not depend on what else sits in its tile --, each measurement network writes
+// Same arithmetic as the launch path, bit for bit: a tile is 32 particles of one trajectory through the network pieces
+// of particle_net_tiles.h that particle_net_kernel<D, NRES, KIND, 1, PREC, 2, false> (the small-problem variant of the
+// launch path) is built from -- a particle's column does not depend on what else sits in its tile --, each measurement network writes
 // its own log-likelihood and K1 folds them with the epilogue's own logaddexp (combine_loglik), and K1 is
 // mmf::resample_systematic_trajectory, whose result does not depend on the workgroup size
 // (tests/test_gpu_models.py::test_persistent_step_loop_equals_loop_of_launches).
@@ -100,9 +100,14 @@ struct SmallTile {
   int spin_sleep;
 };
 
-// 32 particles (rows row0 .. row0 + nvalid - 1 of trajectory `traj`, particle indices m0 ..) through one network:
-// particle_net_kernel's CT = 1, unpipelined path, function for function.  Returns false when the wave gave up
-// waiting for its input granules.
+// 32 particles (rows row0 .. row0 + nvalid - 1 of trajectory `traj`, particle indices m0 ..) through one network.
+// Built from particle_net_tiles.h's pieces, as particle_net_kernel's CT = 1 variant is: first_layer, seed_nonfinite,
+// report_range, head, dynamics_update; the 64 x 64 layers are net_unpipelined (f32) or, for f16x3, rowpipe_net_f16<1>
+// -- another schedule of the same per-accumulator MFMA chains, hence the same bits.  Its own: the inputs arrive as
+// granules behind a bounded spin (mmf::spin_stop / give_up), the per-trajectory row, the noise and scale_tril are
+// requested at the top of the tile, the step's start state is taken from the first layer's operands, the outputs leave
+// as granules.
+// Returns false when the wave gave up waiting for its input granules.
 template <int D, int NRES, int KIND, int PREC>
 __device__ __forceinline__ bool small_tile(const float* __restrict__ lds, const SmallTile& a, int traj, int row0, int m0,
                                            int nvalid, int lane, float neg_one) {
@@ -117,7 +122,7 @@ __device__ __forceinline__ bool small_tile(const float* __restrict__ lds, const 
   // ---- everything that does not depend on another workgroup is requested first: the per-trajectory term of the
   // join layer (32 floats per lane) and the process noise would otherwise be dependent loads in the middle / at the
   // end of the chain (~1-2 k cycles each at this occupancy)
-  f32x4 tbv[2][4];
+  f32x4 tbv[2][4];  // mirrors load_join_row / join_init (through JoinRow the REC f16x3 d = 2 kernel spills two more VGPRs)
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
     const float* tb = a.traj_bias + static_cast<size_t>(traj) * kUnits + 32 * t + 4 * h;
@@ -145,12 +150,12 @@ __device__ __forceinline__ bool small_tile(const float* __restrict__ lds, const 
   }
 
   // ---- first-layer inputs: lane (j, h) feeds components 2s + h of its column's state
-  float b0[KS0];
+  float b0[KS0][1];
   if (a.in_plain != nullptr) {
 #pragma unroll
     for (int s = 0; s < KS0; ++s) {
       const int comp = 2 * s + h;
-      b0[s] = comp < D ? a.in_plain[row * D + comp] : (comp == D ? 1.f : 0.f);
+      b0[s][0] = comp < D ? a.in_plain[row * D + comp] : (comp == D ? 1.f : 0.f);
     }
   } else {
     unsigned spins = 0;
@@ -162,133 +167,66 @@ __device__ __forceinline__ bool small_tile(const float* __restrict__ lds, const 
         if (comp < D) {
           const Granule g = mmf::ld_granule(a.in_g + row * D + comp);
           ok &= mmf::granule_tag(g) == a.in_tag;
-          b0[s] = mmf::granule_value(g);
+          b0[s][0] = mmf::granule_value(g);
         } else {
-          b0[s] = comp == D ? 1.f : 0.f;
+          b0[s][0] = comp == D ? 1.f : 0.f;
         }
       }
       if (__all(ok)) break;
       if (a.spin_sleep) __builtin_amdgcn_s_sleep(1);
-      if ((++spins & 63u) == 0) {  // wave-uniform
-        int stop = 0;
-        if (lane == 0) stop = (spins > mmf::kGranuleSpinLimit || __hip_atomic_load(a.abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) ? 1 : 0;
-        if (__builtin_amdgcn_readfirstlane(stop)) {
-          if (lane == 0) {
-            __hip_atomic_store(a.abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (a.range_flag != nullptr) atomicOr(a.range_flag, MMF_FLAG_GAVE_UP);
-          }
-          return false;
-        }
+      if (mmf::spin_stop(a.abort_word, spins, lane)) {  // wave-uniform
+        if (lane == 0) mmf::give_up(a.abort_word, a.range_flag);
+        return false;
       }
     }
   }
   if (a.stamps && lane == 0) a.stamps[1] = persist_clock();
   Act<1> X, H;
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) X.v[t][0][r] = 0.f;
-#pragma unroll
-  for (int s = 0; s < KS0; ++s) {
-    const int comp = 2 * s + h;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const float w = lds[off_w0() + (32 * t + j) * kW0Cols + comp];
-      X.v[t][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(w, b0[s], X.v[t][0], 0, 0, 0);
-    }
-  }
-  if constexpr (!F16) relu<1, false>(X, true);
-
-  SplitAct<F16 ? 1 : 0> SP;
+  first_layer<1>(lds, b0, X, lane);
   short2v amax = {0, 0};
-  if constexpr (F16) {
-    bool bad = false;
-#pragma unroll
-    for (int s = 0; s < KS0; ++s) bad |= !(fabsf(b0[s]) <= 3.0e38f);
-    if (bad) amax = short2v{0x7fff, 0x7fff};
-  }
-  if constexpr (F16) {
-    // (the first layer's ReLU is rowpipe_net_f16's prologue: X holds the pre-activation here)
-    rowpipe_net_f16<1, NRES, KIND>(lds, X, H, SP, [&](Act<1>& acc) {
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) acc.v[t][0][4 * g + e] = tbv[t][g][e];
-    }, lane, neg_one, amax);
-  } else {
-    // ---- encoder residual block (layers 0, 1)
-    res_block<1, false>(lds, NRES, 0, X, H, lane, true);
-    // ---- join layer (2): the per-trajectory hoisted half arrives as the accumulator init
+  if constexpr (F16) seed_nonfinite<1>(b0, amax);
+  auto join = [&](Act<1>& acc) {
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int g = 0; g < 4; ++g)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) H.v[t][0][4 * g + e] = tbv[t][g][e];
-    mfma_layer<1>(lds + off_layers() + 2 * kLayerFloats, X, H, lane);
-    if (KIND == kMeasure) relu<1, false>(H, true);
-    // ---- residual trunk: activations live in H, X is scratch
-#pragma unroll
-    for (int i = 0; i < NRES; ++i) res_block<1, false>(lds, NRES, 3 + 2 * i, H, X, lane, true);
-  }
+        for (int e = 0; e < 4; ++e) acc.v[t][0][4 * g + e] = tbv[t][g][e];
+  };
   if constexpr (F16) {
-    if (a.range_flag != nullptr && (amax[0] >= kF16Saturated || amax[1] >= kF16Saturated)) atomicOr(a.range_flag, MMF_FLAG_RANGE);
+    SplitAct<1> SP;
+    rowpipe_net_f16<1, NRES, KIND>(lds, X, H, SP, join, lane, neg_one, amax);
+    report_range(a.range_flag, amax);
+  } else {
+    net_unpipelined<1, NRES, KIND, PREC>(lds, X, H, join, lane, neg_one, amax, true);
   }
-  // ---- head (64 -> NOUT) on the VALU
-  float mine[NOUT];
-#pragma unroll
-  for (int o = 0; o < NOUT; ++o) {
-    float part = 0.f;
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const f32x4 w = *reinterpret_cast<const f32x4*>(lds + off_whead(NRES) + o * kUnits + 32 * t + 8 * g + 4 * h);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) part = __builtin_fmaf(w[e], H.v[t][0][4 * g + e], part);
-      }
-    mine[o] = part + __shfl_xor(part, 32);
-  }
+  float out[NOUT][1];
+  head<NRES>(lds, H, lane, out);
   const float* bh = lds + off_bhead(NRES);
   if (a.stamps && lane == 0) a.stamps[2] = persist_clock();
-  if (KIND == kMeasure) {
+  if constexpr (KIND == kMeasure) {
     if (active) {
-      float ll = mine[0] + bh[0];
+      float ll = out[0][0] + bh[0];
       if (a.mod_logw) ll += logw_mod;
       mmf::st_granule(a.out_g + row, ll, a.out_tag);  // this modality's OWN log-likelihood: K1 folds the modalities
     }
   } else {
     // the state the step started from: components 2s of this column sit in this lane's b0, components 2s + 1 in the
     // partner lane's (lane ^ 32) -- no second load
-    float xo[D];
+    float xo[D], mine[NOUT];
 #pragma unroll
     for (int i = 0; i < D; ++i) {
-      const float other_half = __shfl_xor(b0[i / 2], 32);
-      xo[i] = (i & 1) ? other_half : b0[i / 2];
+      const float other_half = __shfl_xor(b0[i / 2][0], 32);
+      xo[i] = (i & 1) ? other_half : b0[i / 2][0];
     }
+#pragma unroll
+    for (int o = 0; o < NOUT; ++o) mine[o] = out[o][0];
     if (active) {
-      const float gate = mine[D] + bh[D];
-      float sg;
-      if constexpr (PREC == MMF_PREC_F32) sg = mmf_det_sigmoid(gate);
-      else sg = 1.0f / (1.0f + expf(-gate));
-      const bool noisy = a.noise != nullptr || a.noise_mode == 2;
-      if (a.noise_mode == 2) {
-        float z[4];
-        mmf_philox_normal4(a.noise_seed, a.noise_step, a.noise_traj0 + static_cast<unsigned>(traj), static_cast<unsigned>(m0 + j), z);
+      float xn[D];
+      dynamics_update<D, PREC>(mine, bh, xo, eps, tril, a.noise != nullptr || a.noise_mode == 2, a.noise_mode == 2, a.noise_seed,
+                               a.noise_step, a.noise_traj0 + static_cast<unsigned>(traj), static_cast<unsigned>(m0 + j), xn);
 #pragma unroll
-        for (int i = 0; i < D; ++i) eps[i] = z[i];
-      }
-#pragma unroll
-      for (int i = 0; i < D; ++i) {
-        float v = __builtin_fmaf(mine[i] + bh[i], sg, xo[i]);
-        if (noisy) {
-#pragma unroll
-          for (int k = 0; k < D; ++k) v = __builtin_fmaf(tril[i * D + k], eps[k], v);
-        }
-        mmf::st_granule(a.out_g + row * D + i, v, a.out_tag);
-      }
+      for (int i = 0; i < D; ++i) mmf::st_granule(a.out_g + row * D + i, xn[i], a.out_tag);
     }
   }
   return true;

@@ -700,6 +700,74 @@ def test_persistent_ekf_loop_of_one_filter_never_reads_the_status_word():
     assert asked == []
 
 
+@pytest.mark.parametrize("kind", ["pf", "ekf"])
+def test_persistent_loops_report_a_saturated_operand_split(kind):
+    """The f16x3 range report is one device function (csrc/particle_net_tiles.h, ``report_range``) shared by the launch
+    kernels and the tiles of the two persistent loops: with the dynamics network's first layer scaled by 1e5 (first-layer
+    outputs ~1e5 > 65504, as in ``test_k2_f16x3_range_flag_reports_saturated_split``) ``forward_loop`` must raise in the
+    persistent form (ONE launch: asserted) exactly as it does as a loop of launches, and leave the status word clear.
+    Saturated activations stay finite (relu_sat / clamp_sat), so nothing here is a fault: only the flag is raised."""
+    _need_gpu()
+    import multimodalfilter_amd as mmf
+    from multimodalfilter_amd import _abi, engine, synthetic
+
+    dev = torch.device("cuda:0")
+    d, T = 3, 2
+    old_prec = engine.DEFAULT_PRECISION
+    engine.set_default_precision("f16x3")
+    try:
+        torch.manual_seed(3)
+        if kind == "pf":  # the ragged-tile shape of test_persistent_step_loop_equals_loop_of_launches
+            N, M = 5, 77
+            f = mmf.door_models.DoorParticleFilter()
+            dynamics = [f.dynamics_model]
+        else:             # the smallest K = 2 shape of test_persistent_ekf_loop_equals_loop_of_launches
+            N = 37
+            f = mmf.door_models.DoorCrossmodalKalmanFilter()
+            dynamics = [m.dynamics_model for m in f.filter_models]
+        with torch.no_grad():
+            for dyn in dynamics:
+                dyn.state_layers[0].weight.mul_(1e5)
+        f = f.to(dev).eval()
+        cov = (torch.eye(d, device=dev) * 0.1)[None].expand(N, d, d)
+        if kind == "pf":
+            f.num_particles = M
+            traj = {k: v.to(dev) for k, v in synthetic.make_trajectories(state_dim=d, T=T, N=N, seed=17).items()}
+            obs = {k: traj[k][1:] for k in ("image", "gripper_pos", "gripper_sensors")}
+            ctrl, x0 = traj["controls"][1:], traj["states"][0]
+            g = torch.Generator(device=dev).manual_seed(5)
+            eps0 = torch.randn((N, M, d), generator=g, device=dev)
+            eps = torch.randn((T, N, M, d), generator=g, device=dev)
+            us = torch.rand((T, N), generator=g, device=dev)
+        else:
+            obs, ctrl, x0, cov = _ekf_loop_inputs(N, T, d, dev)
+        name = "pf_forward_loop" if kind == "pf" else "ekf_forward_loop"
+
+        def run():
+            taken = []
+            real = getattr(_abi, name)
+            setattr(_abi, name, lambda a, *r, **k: (taken.append(int(a.persistent)), real(a, *r, **k))[1])
+            try:
+                if kind == "pf":
+                    f.noise = mmf.StackedNoise(eps0, eps, us)
+                f.initialize_beliefs(mean=x0, covariance=cov)
+                engine.check_range(dev)  # clear
+                with pytest.raises(_abi.MmfError, match="f16x3 operand range"):
+                    f.forward_loop(observations=obs, controls=ctrl)
+                assert int(engine.range_flag(dev).item()) == 0  # the report was consumed: nothing left to raise
+                engine.check_range(dev)
+                return taken
+            finally:
+                setattr(_abi, name, real)
+
+        with engine.persistent_forms(**{kind: True}):
+            assert run() == [1]
+        with engine.persistent_forms(**{kind: False}):
+            assert run() == [0]
+    finally:
+        engine.set_default_precision(old_prec)
+
+
 def fill_nan(address: int, n: int):
     """Overwrite ``n`` floats of device memory at ``address`` with NaN bytes (the HIP runtime's own memset)."""
     import ctypes
