@@ -141,6 +141,37 @@ int mmf_pf_reweight_resample_belief(const float* loglik, const float* logw_in, c
                                     int d, int mode, float alpha, float* cov, float* ess,
                                     float* log_evidence, void* stream);
 
+/* K1 with ESS-TRIGGERED (adaptive) resampling: a trajectory resamples only when its effective sample size has dropped below
+ * a fraction of M, and otherwise carries its weights forward (the estimator between upstream's resample-always and
+ * resample-never).  Purely additive to ABI 42: two new symbols (this one and mmf_pf_forward_loop_adaptive), no struct layout
+ * changes, so MMF_ABI_VERSION stays 42.  The one definition every form of K1 follows:
+ *   - mode 1 or 2, M_out == M, optional soft alpha, ess_threshold in (0, 1]
+ *   - ess_n is the fp32 value the belief record reports (mmf_pf_reweight_resample_belief: S^2 / sum e^2 -- the same sums,
+ *     the same partition rule, the same bits)
+ *   - trajectory n RESAMPLES iff !(ess_n >= ess_threshold * (float)M), the product rounded once in fp32: a NaN ESS resamples
+ *     (what a degenerate row does today), a tie keeps (uniform weights with ess_threshold == 1 keep)
+ *   - a resampling trajectory produces bit for bit what mmf_pf_reweight_resample_belief produces with that mode / alpha:
+ *     states_out, logw_out (-log M, or the soft importance weights), indices_out
+ *   - a KEPT trajectory: states_out is a bit copy of states_in, logw_out is bit for bit what mode 0 writes for the same
+ *     inputs, indices_out is 0 .. M-1
+ *   - estimate and the record (cov, ess, log_evidence) are those of the pre-resampling set on both branches, unchanged
+ *   - the uniforms `u` of a step are consumed whether or not a trajectory uses them ((N) / (N, M) as the mode says), so the
+ *     noise stream of a run does not depend on its decisions and results stay shard-invariant
+ *  logw_in     null = uniform (plain resampling only, as above)
+ *  logw_out    required (a kept trajectory's weights are not uniform), must not alias logw_in
+ *  resampled   (N) int32 1 / 0, or null
+ * The decision is workgroup-uniform -- taken from the broadcast totals of S and sum e^2 after pass 2's reductions -- and a kept
+ * trajectory leaves before the announcements / search and the gather.  A template flag of both K1 kernels, as the record is:
+ * the instantiations without it are the ones that existed before.  Sum e^2 is reduced through the record's rows in LDS whether
+ * or not a record is requested, so the size limits are those of a recording call.  The cluster form does not do adaptive.
+ * MMF_EINVAL: mode 0, null logw_out / states_out / u, in-place gather, ess_threshold <= 0, > 1 or NaN, alpha outside (0, 1];
+ * N == 0 is a successful no-op. */
+int mmf_pf_reweight_resample_adaptive(const float* loglik, const float* logw_in, const float* states_in,
+                                      const float* u, float* estimate, float* states_out,
+                                      float* logw_out, int32_t* indices_out, int N, int M, int d, int mode,
+                                      float alpha, float ess_threshold, int32_t* resampled, float* cov,
+                                      float* ess, float* log_evidence, void* stream);
+
 /* Belief initialisation (replaces torchfilter's ParticleFilter.initialize_beliefs; call site
  * eval_helpers.py:125-131): states[n][m] = mean[n] + chol(covariance[n]) eps[n][m], logw = -log M.
  *  mean (N, d), covariance (N, d, d), eps (N, M, d) standard normal -> states (N, M, d), logw (N, M)
@@ -484,6 +515,19 @@ typedef struct MmfPfLoopArgs {
 } MmfPfLoopArgs;             /* host struct holding device pointers                           */
 
 int mmf_pf_forward_loop(const MmfPfLoopArgs* args /* host */, void* stream);
+
+/* The step loop with ESS-triggered resampling (mmf_pf_reweight_resample_adaptive's definition, per trajectory and step).  The
+ * threshold and the per-step decisions are arguments of this entry point so that MmfPfLoopArgs keeps its layout (ABI 42);
+ * everything else is read from the unchanged struct: resample_mode (1 or 2; 0 -> MMF_EINVAL), soft_alpha, estimate_argmax,
+ * loglik_steps / indices_steps, the belief records, persistent.  Every step reads and writes the log-weights (as soft
+ * resampling makes the loop do), and final_location reports where they ended up.  The persistent form (same eligibility:
+ * plain systematic resampling, weighted-average estimates, mmf_pf_persistent_plan > 0) takes the adaptive branch in its K1
+ * role; a kept trajectory publishes its rows to the dynamics role as an identity gather and carries its log-weights to its
+ * own next step through logw_a / logw_b (the same workgroup, in program order).  Same bits as the loop of launches.
+ *   ess_threshold    in (0, 1]; otherwise MMF_EINVAL
+ *   resampled_steps  (T, N) int32 1 / 0, or null */
+int mmf_pf_forward_loop_adaptive(const MmfPfLoopArgs* args /* host */, float ess_threshold,
+                                 int32_t* resampled_steps, void* stream);
 
 /* The persistent form of the step loop (MmfPfLoopArgs.persistent): at the sizes the reference itself runs (32
  * trajectories x 300 particles: door_models/pf.py:24-27, eval_helpers.py:125-142) a step is bound by the fixed cost

@@ -149,6 +149,8 @@ SIGNATURES = {
                                               c_int, c_int, c_int, c_int, c_int, ctypes.c_float, c_void_p]),
     "mmf_pf_reweight_resample_belief": (c_int, [_FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP,
                                                 c_int, c_int, c_int, c_int, c_int, ctypes.c_float, _FP, _FP, _FP, c_void_p]),
+    "mmf_pf_reweight_resample_adaptive": (c_int, [_FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, c_int, c_int, c_int, c_int,
+                                                  ctypes.c_float, ctypes.c_float, _FP, _FP, _FP, _FP, c_void_p]),
     "mmf_pf_reweight_resample_lds_bytes": (c_size_t, [c_int, c_int]),
     "mmf_pf_set_resample_cluster": (None, [c_int]),
     "mmf_pf_get_resample_cluster": (c_int, []),
@@ -167,6 +169,7 @@ SIGNATURES = {
     "mmf_pf_reweight_backward": (c_int, [_FP, _FP, _FP, _FP, _FP, _FP, c_int, c_int, c_int, c_void_p]),
     "mmf_pf_init_particles": (c_int, [_FP, _FP, _FP, _FP, _FP, _FP, c_int, c_int, c_int, c_void_p]),
     "mmf_pf_forward_loop": (c_int, [POINTER(MmfPfLoopArgs), c_void_p]),
+    "mmf_pf_forward_loop_adaptive": (c_int, [POINTER(MmfPfLoopArgs), ctypes.c_float, _FP, c_void_p]),
     "mmf_pf_argmax_estimate": (c_int, [_FP, _FP, _FP, _FP, c_int, c_int, c_int, c_void_p]),
     "mmf_pf_persistent_plan": (c_int, [c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     "mmf_pf_persistent_sync_words": (c_size_t, [c_int, c_int, c_int, c_int]),
@@ -314,6 +317,25 @@ def pf_reweight_resample_belief(loglik, logw_in, states_in, u, estimate, states_
             ptr(loglik), ptr(logw_in), ptr(states_in), ptr(u), ptr(estimate), ptr(states_out),
             ptr(logw_out), ptr(indices_out, dtype=torch.int32), N, M, M_out, d, mode, float(soft_alpha),
             ptr(cov), ptr(ess), ptr(log_evidence), stream_of(states_in)), "mmf_pf_reweight_resample_belief")
+
+
+def pf_reweight_resample_adaptive(loglik, logw_in, states_in, u, estimate, states_out, logw_out, indices_out, mode: int,
+                                  soft_alpha: float = 1.0, *, ess_threshold: float, resampled=None, cov=None, ess=None,
+                                  log_evidence=None):
+    """K1 with ESS-triggered resampling (``mmf_pf_reweight_resample_adaptive``): trajectory ``n`` resamples iff
+    ``not (ess[n] >= float32(ess_threshold * M))`` and otherwise keeps its particles and carries its normalised weights.
+    ``resampled``: ``(N,)`` int32 1 / 0 or ``None``; the record as ``pf_reweight_resample_belief``."""
+    N, M, d = states_in.shape
+    assert loglik.shape == (N, M) and estimate.shape == (N, d) and logw_out.shape == (N, M) and states_out.shape == (N, M, d)
+    assert resampled is None or resampled.shape == (N,)
+    assert cov is None or cov.shape == (N, d, d)
+    assert (ess is None or ess.shape == (N,)) and (log_evidence is None or log_evidence.shape == (N,))
+    with _on(states_in):
+        _check(load().mmf_pf_reweight_resample_adaptive(
+            ptr(loglik), ptr(logw_in), ptr(states_in), ptr(u), ptr(estimate), ptr(states_out), ptr(logw_out),
+            ptr(indices_out, dtype=torch.int32), N, M, d, mode, float(soft_alpha), float(ess_threshold),
+            ptr(resampled, dtype=torch.int32), ptr(cov), ptr(ess), ptr(log_evidence), stream_of(states_in)),
+            "mmf_pf_reweight_resample_adaptive")
 
 
 def pf_set_resample_cluster(enabled: bool) -> bool:
@@ -704,10 +726,13 @@ def pf_init_particles(mean, covariance, eps, states, logw, not_pd):
                "mmf_pf_init_particles")
 
 
-def pf_forward_loop(args: MmfPfLoopArgs, like: torch.Tensor, events=None, event_stride: int = 1) -> int:
+def pf_forward_loop(args: MmfPfLoopArgs, like: torch.Tensor, events=None, event_stride: int = 1, *,
+                    ess_threshold: float = None, resampled_steps=None) -> int:
     """Enqueue T filter steps; returns the final-location bits (see include/mmf.h).
     ``events``: optional flat list of created ``torch.cuda.Event`` (timing) recorded in C
-    around the launches of every ``event_stride``-th step."""
+    around the launches of every ``event_stride``-th step.
+    ``ess_threshold``: ESS-triggered resampling (``mmf_pf_forward_loop_adaptive``), ``resampled_steps`` its ``(T, N)`` int32
+    decisions or ``None``."""
     loc = c_int32(0)
     args.final_location = ctypes.pointer(loc)
     if events is not None:
@@ -715,5 +740,10 @@ def pf_forward_loop(args: MmfPfLoopArgs, like: torch.Tensor, events=None, event_
         args.events = arr
         args.event_stride = event_stride
     with _on(like):
-        _check(load().mmf_pf_forward_loop(ctypes.byref(args), stream_of(like)), "mmf_pf_forward_loop")
+        if ess_threshold is not None:
+            _check(load().mmf_pf_forward_loop_adaptive(ctypes.byref(args), float(ess_threshold),
+                                                       ptr(resampled_steps, dtype=torch.int32), stream_of(like)),
+                   "mmf_pf_forward_loop_adaptive")
+        else:
+            _check(load().mmf_pf_forward_loop(ctypes.byref(args), stream_of(like)), "mmf_pf_forward_loop")
     return int(loc.value)

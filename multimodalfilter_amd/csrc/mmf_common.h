@@ -15,7 +15,9 @@
 
 // the persistent small-problem step loop (pf_persistent.inc, compiled with particle_net.hip); reached through
 // mmf_pf_forward_loop when MmfPfLoopArgs.persistent is set
-int mmf_internal_pf_persistent(const MmfPfLoopArgs* args, void* stream);
+// ess_threshold > 0: ESS-triggered resampling (mmf_pf_forward_loop_adaptive), resampled_steps (T, N) or null
+int mmf_internal_pf_persistent(const MmfPfLoopArgs* args, void* stream, float ess_threshold = 0.f,
+                               int32_t* resampled_steps = nullptr);
 int mmf_internal_ekf_persistent(const MmfEkfLoopArgs* args, float* Sigma_steps /* or null */, void* stream);  /* ekf_persistent.inc */
 #define MMF_INTERNAL_NOT_RESIDENT (-1000)  /* its grid would not be co-resident on this device: take the launch path */
 

@@ -8,8 +8,11 @@
 
 #include "mmf_common.h"
 
-static int pf_enqueue_steps(const MmfPfLoopArgs* a, void* stream, bool with_events) {
+// ess_threshold > 0: ESS-triggered resampling (mmf_pf_forward_loop_adaptive), resampled_steps (T, N) or null
+static int pf_enqueue_steps(const MmfPfLoopArgs* a, void* stream, bool with_events, float ess_threshold = 0.f,
+                            int32_t* resampled_steps = nullptr) {
   if (!a) return MMF_EINVAL;
+  const bool adaptive = ess_threshold > 0.f;
   if (a->T < 0 || a->N < 1 || a->M < 1 || a->n_meas < 1 || a->n_meas > MMF_LOOP_MAX_MEAS) return MMF_EINVAL;
   if (a->resample_mode < 0 || a->resample_mode > 2) return MMF_EINVAL;
   if (!a->dyn_packed || !a->dyn_bias || (!a->noise && a->noise_mode != 2) || !a->scale_tril || !a->states_a || !a->states_b ||
@@ -71,13 +74,20 @@ static int pf_enqueue_steps(const MmfPfLoopArgs* a, void* stream, bool with_even
     if (a->estimate_argmax) {
       // the particle with the largest pre-resampling weight; K1's weighted mean goes to the scratch.  In the plain
       // resampling loop the incoming weights are uniform from the second step on (see below)
-      const bool uniform_in = a->resample_mode != 0 && !soft && t > 0;
+      const bool uniform_in = a->resample_mode != 0 && !soft && !adaptive && t > 0;
       rc = mmf_pf_argmax_estimate(ll, uniform_in ? nullptr : lw_cur, other, est, a->N, a->M, a->d, stream);
       if (rc) return rc;
       est = a->estimate_scratch;
     }
     if ((rc = mark())) return rc;
-    if (soft) {
+    if (adaptive) {
+      // a kept trajectory carries its weights forward, so the log-weights travel every step (as with soft resampling)
+      const float* u = a->uniforms + t * (a->resample_mode == 1 ? row : nm);
+      rc = mmf_pf_reweight_resample_adaptive(ll, lw_cur, other, u, est, cur, lw_other, anc, a->N, a->M, a->d, a->resample_mode,
+                                             soft ? a->soft_alpha : 1.0f, ess_threshold,
+                                             resampled_steps ? resampled_steps + t * row : nullptr, cov, ess, lev, stream);
+      if (rc) return rc;
+    } else if (soft) {
       // torchfilter's soft resampling: survivors carry importance weights, so the log-weights travel every step
       const float* u = a->uniforms + t * (a->resample_mode == 1 ? row : nm);
       rc = mmf_pf_reweight_resample_belief(ll, lw_cur, other, u, est, cur, lw_other, anc, a->N, a->M, a->M, a->d,
@@ -120,6 +130,20 @@ extern "C" int mmf_pf_forward_loop(const MmfPfLoopArgs* a, void* stream) {
     a = &launches;
   }
   return pf_enqueue_steps(a, stream, true);
+}
+
+extern "C" int mmf_pf_forward_loop_adaptive(const MmfPfLoopArgs* a, float ess_threshold, int32_t* resampled_steps, void* stream) {
+  if (!a || a->resample_mode == 0) return MMF_EINVAL;  // a threshold needs a resampling mode
+  if (!(ess_threshold > 0.f && ess_threshold <= 1.f)) return MMF_EINVAL;
+  MmfPfLoopArgs launches;
+  if (a->persistent) {  // eligibility as mmf_pf_forward_loop's: plain systematic resampling, weighted-average estimates
+    const int rc = mmf_internal_pf_persistent(a, stream, ess_threshold, resampled_steps);
+    if (rc != MMF_INTERNAL_NOT_RESIDENT) return rc;
+    launches = *a;
+    launches.persistent = 0;
+    a = &launches;
+  }
+  return pf_enqueue_steps(a, stream, true, ess_threshold, resampled_steps);
 }
 
 // Open-loop rollout x_t = f(x_{t-1}, u_t): replaces torchfilter's DynamicsModel.forward_loop (call

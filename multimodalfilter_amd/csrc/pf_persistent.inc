@@ -73,6 +73,11 @@ struct PersistArgs {
   unsigned long long* stamps;          // MMF_PERSIST_STAMPS=<step> (diagnostic): [block][wave][4] cycle stamps of one step
   int stamp_step;
   int spin_sleep;                      // s_sleep between polls
+  // ADAPT (ESS-triggered resampling): every step reads and writes the log-weights, ping-ponging as the loop of launches does
+  // -- step t reads logw[t & 1] and writes the other; a trajectory's rows are written and read back by ITS K1 workgroup only
+  float* logw[2];                      // {logw_a, logw_b}, (N, M) each
+  float ess_floor;                     // fl32(ess_threshold * M)
+  int32_t* resampled_steps;            // (T, N) 1 / 0, or null
 };
 
 __device__ __forceinline__ unsigned long long persist_clock() {
@@ -233,7 +238,10 @@ __device__ __forceinline__ bool small_tile(const float* __restrict__ lds, const 
 }
 
 // REC: the K1 role also writes every step's belief record (mmf::K1Belief); the other roles are the same code
-template <int D, int PREC, bool REC = false>
+// ADAPT: the K1 role resamples a trajectory only where its ESS fell below the floor; a kept trajectory publishes its rows to
+// the dynamics role through the same tagged granules (an identity gather) and carries its normalised log-weights to its own
+// next step -- the same workgroup in program order (n = b - n_net_blocks + k GK), so no hand-off is added
+template <int D, int PREC, bool REC = false, bool ADAPT = false>
 __global__ __launch_bounds__(kPersistThreads, 2) void pf_persistent_loop_kernel(PersistArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int kNresDyn = 3, kNresMeas = 2;
@@ -337,13 +345,19 @@ __global__ __launch_bounds__(kPersistThreads, 2) void pf_persistent_loop_kernel(
       tr.stamps = my_stamps;
       tr.lo = (last && a.logw_out_last) ? a.logw_out_last + static_cast<size_t>(n) * a.M : nullptr;
       tr.io = nullptr;
+      if constexpr (ADAPT) {
+        tr.lw = ((t & 1) ? a.logw[1] : a.logw[0]) + static_cast<size_t>(n) * a.M;
+        tr.lo = ((t & 1) ? a.logw[0] : a.logw[1]) + static_cast<size_t>(n) * a.M;
+        tr.ess_floor = a.ess_floor;
+        tr.resampled = a.resampled_steps ? a.resampled_steps + static_cast<size_t>(t) * a.N + n : nullptr;
+      }
       if constexpr (REC) {
         const size_t tn = static_cast<size_t>(t) * a.N + n;
         tr.cov = a.cov_steps ? a.cov_steps + tn * D * D : nullptr;
         tr.ess = a.ess_steps ? a.ess_steps + tn : nullptr;
         tr.log_evidence = a.log_evidence_steps ? a.log_evidence_steps + tn : nullptr;
       }
-      if (!mmf::resample_systematic_trajectory<D, true, true, PREC == MMF_PREC_F32, REC>(smem, tr, a.M, a.M, a.lw_uniform, log_uniform)) {
+      if (!mmf::resample_systematic_trajectory<D, true, true, PREC == MMF_PREC_F32, REC, ADAPT>(smem, tr, a.M, a.M, a.lw_uniform, log_uniform)) {
         if (threadIdx.x == 0 && a.range_flag != nullptr) atomicOr(a.range_flag, MMF_FLAG_GAVE_UP);
         return;
       }
@@ -353,16 +367,16 @@ __global__ __launch_bounds__(kPersistThreads, 2) void pf_persistent_loop_kernel(
   }
 }
 
-size_t persist_k1_lds_bytes(int M, int d, bool rec) {
+size_t persist_k1_lds_bytes(int M, int d, bool rec) {  // rec: the record's reduction rows (a recording or an adaptive loop)
   const size_t slots = (static_cast<size_t>(M) * 8 + 15) & ~static_cast<size_t>(15);
   const size_t sc = (sizeof(mmf::K1Scratch) + 15) & ~static_cast<size_t>(15);
   const size_t marks = ((static_cast<size_t>(M) + 4) * 4 + 15) & ~static_cast<size_t>(15);
   return slots + sc + marks + static_cast<size_t>(M) * d * sizeof(float) + 32 + (rec ? mmf::k1_belief_lds_bytes() : 0);
 }
 
-template <int D, int PREC, bool REC>
+template <int D, int PREC, bool REC, bool ADAPT>
 int launch_persistent(const PersistArgs& pa, size_t lds, int blocks, hipStream_t s) {
-  auto k = pf_persistent_loop_kernel<D, PREC, REC>;
+  auto k = pf_persistent_loop_kernel<D, PREC, REC, ADAPT>;
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
   if (e != hipSuccess) return static_cast<int>(e);
   k<<<blocks, kPersistThreads, lds, s>>>(pa);
@@ -371,22 +385,22 @@ int launch_persistent(const PersistArgs& pa, size_t lds, int blocks, hipStream_t
 }
 
 // residency check and launch of the instantiation for (precision, d)
-template <bool REC>
+template <bool REC, bool ADAPT>
 int persistent_dispatch(int precision, int d, const PersistArgs& pa, size_t lds, int blocks, hipStream_t hs) {
   if (precision != MMF_PREC_F32 && precision != MMF_PREC_F16X3) return MMF_EINVAL;
   {  // the plan assumed one resident workgroup per CU: hold the launch to what the runtime says about THIS kernel
     int per_cu = 0, dev = 0, cus = 0;
     const void* fn = precision == MMF_PREC_F32
-                         ? (d == 3 ? reinterpret_cast<const void*>(pf_persistent_loop_kernel<3, MMF_PREC_F32, REC>) : reinterpret_cast<const void*>(pf_persistent_loop_kernel<2, MMF_PREC_F32, REC>))
-                         : (d == 3 ? reinterpret_cast<const void*>(pf_persistent_loop_kernel<3, MMF_PREC_F16X3, REC>) : reinterpret_cast<const void*>(pf_persistent_loop_kernel<2, MMF_PREC_F16X3, REC>));
+                         ? (d == 3 ? reinterpret_cast<const void*>(pf_persistent_loop_kernel<3, MMF_PREC_F32, REC, ADAPT>) : reinterpret_cast<const void*>(pf_persistent_loop_kernel<2, MMF_PREC_F32, REC, ADAPT>))
+                         : (d == 3 ? reinterpret_cast<const void*>(pf_persistent_loop_kernel<3, MMF_PREC_F16X3, REC, ADAPT>) : reinterpret_cast<const void*>(pf_persistent_loop_kernel<2, MMF_PREC_F16X3, REC, ADAPT>));
     if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess ||
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kPersistWaves * MMF_WAVE, lds) != hipSuccess ||
         hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
       return MMF_EINVAL;
     if (per_cu < 1 || blocks > per_cu * cus) return MMF_INTERNAL_NOT_RESIDENT;  // mmf_pf_forward_loop takes the launch path
   }
-  if (precision == MMF_PREC_F32) return d == 3 ? launch_persistent<3, MMF_PREC_F32, REC>(pa, lds, blocks, hs) : launch_persistent<2, MMF_PREC_F32, REC>(pa, lds, blocks, hs);
-  return d == 3 ? launch_persistent<3, MMF_PREC_F16X3, REC>(pa, lds, blocks, hs) : launch_persistent<2, MMF_PREC_F16X3, REC>(pa, lds, blocks, hs);
+  if (precision == MMF_PREC_F32) return d == 3 ? launch_persistent<3, MMF_PREC_F32, REC, ADAPT>(pa, lds, blocks, hs) : launch_persistent<2, MMF_PREC_F32, REC, ADAPT>(pa, lds, blocks, hs);
+  return d == 3 ? launch_persistent<3, MMF_PREC_F16X3, REC, ADAPT>(pa, lds, blocks, hs) : launch_persistent<2, MMF_PREC_F16X3, REC, ADAPT>(pa, lds, blocks, hs);
 }
 
 }  // namespace
@@ -465,8 +479,10 @@ extern "C" size_t mmf_pf_persistent_sync_words(int N, int M, int d, int n_meas) 
   return 4 + 2 * (2 * NM * d + static_cast<size_t>(n_meas) * NM);
 }
 
-int mmf_internal_pf_persistent(const MmfPfLoopArgs* a, void* stream) {
+int mmf_internal_pf_persistent(const MmfPfLoopArgs* a, void* stream, float ess_threshold, int32_t* resampled_steps) {
   if (!a || !a->sync_words) return MMF_EINVAL;
+  const bool adaptive = ess_threshold > 0.f;
+  if (adaptive && (!a->logw_a || !a->logw_b)) return MMF_EINVAL;
   if (a->resample_mode != 1 || (a->soft_alpha > 0.f && a->soft_alpha < 1.f) || a->estimate_argmax || a->events ||
       a->loglik_steps || a->indices_steps || a->n_res_dyn != 3 || a->n_res_meas != 2 || a->T < 1)
     return MMF_EINVAL;
@@ -492,6 +508,9 @@ int mmf_internal_pf_persistent(const MmfPfLoopArgs* a, void* stream) {
   pa.logw_out_last = last_into_b ? a->logw_b : a->logw_a;
   pa.estimates = a->estimates; pa.range_flag = a->range_flag;
   pa.cov_steps = a->cov_steps; pa.ess_steps = a->ess_steps; pa.log_evidence_steps = a->log_evidence_steps;
+  pa.logw[0] = a->logw_a; pa.logw[1] = a->logw_b;  // ADAPT: step t writes logw[(t + 1) & 1], so the last step's land where last_into_b says
+  pa.ess_floor = ess_threshold * static_cast<float>(a->M);  // the product rounded once, in fp32
+  pa.resampled_steps = resampled_steps;
   const bool rec = a->cov_steps || a->ess_steps || a->log_evidence_steps;  // the recording instantiation of the kernel
   const size_t NM = static_cast<size_t>(a->N) * a->M;
   unsigned* w = reinterpret_cast<unsigned*>(a->sync_words);
@@ -514,11 +533,13 @@ int mmf_internal_pf_persistent(const MmfPfLoopArgs* a, void* stream) {
     pa.stamp_step = atoi(stamp_env);
   }
   size_t lds = static_cast<size_t>(blob_floats(3)) * sizeof(float);
-  const size_t k1 = persist_k1_lds_bytes(a->M, a->d, rec);
+  const size_t k1 = persist_k1_lds_bytes(a->M, a->d, rec || adaptive);
   if (k1 > lds) lds = k1;
   if (lds > 160 * 1024) return MMF_ETOOLARGE;
-  const int rc = rec ? persistent_dispatch<true>(a->precision, a->d, pa, lds, blocks, hs)
-                     : persistent_dispatch<false>(a->precision, a->d, pa, lds, blocks, hs);
+  const int rc = adaptive ? (rec ? persistent_dispatch<true, true>(a->precision, a->d, pa, lds, blocks, hs)
+                                 : persistent_dispatch<false, true>(a->precision, a->d, pa, lds, blocks, hs))
+                          : (rec ? persistent_dispatch<true, false>(a->precision, a->d, pa, lds, blocks, hs)
+                                 : persistent_dispatch<false, false>(a->precision, a->d, pa, lds, blocks, hs));
   if (rc) return rc;
   if (pa.stamps) {
     std::vector<unsigned long long> h(n_stamps);

@@ -53,15 +53,18 @@ using Scratch = mmf::K1Scratch;  // lives behind the slots in dynamic LDS
 // REC: the belief record (covariance, ESS, log-evidence of the weighted set; mmf::K1Belief in pf_resample_systematic.inc),
 // its sums in this kernel's own partition -- per thread over all its chunks, a butterfly per wave, the waves in order.
 // The non-recording instantiation is the kernel as it was.
+// ADAPT: ESS-triggered resampling (include/mmf.h, K1): the decision follows the sums' reductions; a kept trajectory writes
+// mode 0's outputs and leaves before the search and the gather.  Without REC only sum e^2 of the record is accumulated.
 struct BeliefOut { float* cov; float* ess; float* log_evidence; };  // (N, d, d), (N), (N); each or null
+struct AdaptIn { float ess_floor; int32_t* resampled; };            // fl32(threshold * M); (N) 1 / 0 or null
 
-template <int D, bool STAGE, bool SOFT = false, bool REC = false>
+template <int D, bool STAGE, bool SOFT = false, bool REC = false, bool ADAPT = false>
 __global__ __launch_bounds__(kBlock) void pf_reweight_resample_kernel(
     const float* __restrict__ loglik, const float* __restrict__ logw_in,
     const float* __restrict__ states_in, const float* __restrict__ u,
     float* __restrict__ estimate, float* states_out, float* logw_out,
     int32_t* __restrict__ indices_out, int M, int M_out, int mode, float alpha, float lw_uniform,
-    float log_uniform, BeliefOut rec) {
+    float log_uniform, BeliefOut rec, AdaptIn ad) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const bool need_cdf = mode != 0;
   const int slot_bytes = need_cdf ? 8 : 4;
@@ -165,6 +168,7 @@ __global__ __launch_bounds__(kBlock) void pf_reweight_resample_kernel(
   float S = 0.f, acc[D];
 #pragma unroll
   for (int c = 0; c < D; ++c) acc[c] = 0.f;
+  float w2 = 0.f;  // ADAPT without REC: bel.s[0] alone
   unsigned long long carry = 0, qsum = 0;
   for (int base = 0; base < M; base += chunk) {
     const int i0 = base + tid * 4;
@@ -203,6 +207,10 @@ __global__ __launch_bounds__(kBlock) void pf_reweight_resample_kernel(
       if constexpr (REC) {
         const float xv = ok ? x_load(i0 + j) : -INFINITY;
         bel.add(xv == -INFINITY ? 0.f : e[j], st + j * D, piv);
+      } else if constexpr (ADAPT) {
+        const float xv = ok ? x_load(i0 + j) : -INFINITY;
+        const float ev = xv == -INFINITY ? 0.f : e[j];
+        w2 = __builtin_fmaf(ev, ev, w2);
       }
     }
     qsum += tsum;
@@ -321,6 +329,36 @@ __global__ __launch_bounds__(kBlock) void pf_reweight_resample_kernel(
     __syncthreads();
     mmf::k1_belief_store<D>(bsc.tot, S, mx, rec.cov ? rec.cov + static_cast<size_t>(n) * D * D : nullptr,
                             rec.ess ? rec.ess + n : nullptr, rec.log_evidence ? rec.log_evidence + n : nullptr, tid);
+  } else if constexpr (ADAPT) {  // sum e^2 in the record's partition: per thread, a butterfly per wave, the waves in order
+    const float bw = mmf::wave_sum(w2);
+    if (lane == 0) bsc.red[wave][0] = bw;
+    __syncthreads();
+    if (tid == 0) {
+      float t = 0.f;
+      for (int w = 0; w < nwaves; ++w) t += bsc.red[w][0];
+      bsc.tot[0] = t;
+    }
+    __syncthreads();
+  }
+  if constexpr (ADAPT) {
+    // S and sum e^2 are the broadcast totals (LDS), so every lane of every wave takes the same side
+    const bool keep = mmf::k1_ess(S, bsc.tot[0]) >= ad.ess_floor;  // a NaN resamples, a tie keeps
+    if (tid == 0 && ad.resampled != nullptr) ad.resampled[n] = keep ? 0 : 1;
+    if (keep) {
+      // mode 0's outputs (M_out == M).  The slots hold the CDF by now: x_i is formed again from the inputs (the same addition)
+      const float logS = logf(S);
+      float* lo = logw_out + static_cast<size_t>(n) * M;
+      float* so = states_out + static_cast<size_t>(n) * M * D;
+      int32_t* io = indices_out ? indices_out + static_cast<size_t>(n) * M : nullptr;
+      for (int i = tid; i < M; i += blockDim.x) {
+        const float x = (lw ? lw[i] : lw_uniform) + ll[i];
+        lo[i] = (x - mx) - logS;
+#pragma unroll
+        for (int c = 0; c < D; ++c) so[static_cast<size_t>(i) * D + c] = STAGE ? xs_lds[i * D + c] : xs[static_cast<size_t>(i) * D + c];
+        if (io) io[i] = i;
+      }
+      return;
+    }
   }
 
   // ---- mode 0: normalised log-weights out, particles stay
@@ -440,11 +478,11 @@ __global__ __launch_bounds__(kBlock) void pf_reweight_resample_kernel(
 
 // ---- plain systematic resampling WITHOUT a search (the bench's and the reference's evaluation mode): the body is
 // mmf::resample_systematic_trajectory (pf_resample_systematic.inc, shared with the persistent small-problem loop)
-template <int D, bool STAGE, bool REC = false>
+template <int D, bool STAGE, bool REC = false, bool ADAPT = false>
 __global__ __launch_bounds__(kBlock) void pf_resample_systematic_kernel(
     const float* __restrict__ loglik, const float* __restrict__ logw_in, const float* __restrict__ states_in,
     const float* __restrict__ u, float* __restrict__ estimate, float* states_out, float* logw_out,
-    int32_t* __restrict__ indices_out, int M, int M_out, float lw_uniform, float log_uniform, BeliefOut rec) {
+    int32_t* __restrict__ indices_out, int M, int M_out, float lw_uniform, float log_uniform, BeliefOut rec, AdaptIn ad) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int n = blockIdx.x;
   mmf::K1Trajectory a{};
@@ -462,7 +500,11 @@ __global__ __launch_bounds__(kBlock) void pf_resample_systematic_kernel(
     a.ess = rec.ess ? rec.ess + n : nullptr;
     a.log_evidence = rec.log_evidence ? rec.log_evidence + n : nullptr;
   }
-  mmf::resample_systematic_trajectory<D, STAGE, false, false, REC>(smem, a, M, M_out, lw_uniform, log_uniform);
+  if constexpr (ADAPT) {
+    a.ess_floor = ad.ess_floor;
+    a.resampled = ad.resampled ? ad.resampled + n : nullptr;
+  }
+  mmf::resample_systematic_trajectory<D, STAGE, false, false, REC, ADAPT>(smem, a, M, M_out, lw_uniform, log_uniform);
 }
 
 }  // namespace
@@ -483,7 +525,8 @@ size_t staged_lds_bytes(int M, int d, int mode) {
 namespace {
 int launch_reweight_resample(const float* loglik, const float* logw_in, const float* states_in, const float* u,
                              float* estimate, float* states_out, float* logw_out, int32_t* indices_out, int N,
-                             int M, int M_out, int d, int mode, float alpha, BeliefOut rec, void* stream) {
+                             int M, int M_out, int d, int mode, float alpha, BeliefOut rec, void* stream,
+                             float ess_threshold = 0.f, int32_t* resampled = nullptr) {  // > 0: the adaptive call
   if (!loglik || !states_in || !estimate) return MMF_EINVAL;
   if (N < 0 || M < 1 || M_out < 1 || d < 1 || d > MMF_MAX_STATE_DIM || mode < 0 || mode > 2) return MMF_EINVAL;
   // the uniform-weight shortcuts (null logw_in / logw_out) belong to plain resampling
@@ -497,17 +540,19 @@ int launch_reweight_resample(const float* loglik, const float* logw_in, const fl
   // a recording call keeps its sums' reduction rows behind everything else in LDS (the non-recording layout and
   // limits are untouched): M <= 20,200 in modes 1/2, 40,500 in mode 0
   const bool recording = rec.cov || rec.ess || rec.log_evidence;
-  const size_t rec_sz = recording ? mmf::k1_belief_lds_bytes() : 0;
+  const bool adaptive = ess_threshold > 0.f;  // reduces sum e^2 through the record's rows: the recording call's layout and limits
+  const AdaptIn ad{ess_threshold * static_cast<float>(M), resampled};  // the product rounded once, in fp32
+  const size_t rec_sz = (recording || adaptive) ? mmf::k1_belief_lds_bytes() : 0;
   if (((lds + 15) & ~static_cast<size_t>(15)) + rec_sz > 160 * 1024) return MMF_ETOOLARGE;
   if (N == 0) return 0;
   const bool soft = mode != 0 && alpha < 1.f;
   // stage the states in LDS when occupancy does not pay for it: always if every trajectory gets
   // a CU of its own (N <= 256), otherwise only while two workgroups still fit a CU (<= 80 KB each)
-  const size_t staged = recording ? ((staged_lds_bytes(M, d, mode) + 15) & ~static_cast<size_t>(15)) + rec_sz
+  const size_t staged = (recording || adaptive) ? ((staged_lds_bytes(M, d, mode) + 15) & ~static_cast<size_t>(15)) + rec_sz
                                   : staged_lds_bytes(M, d, mode);
   const bool stage = mode != 0 && (N <= 256 ? staged <= 160 * 1024 : staged <= 80 * 1024);
   if (stage) lds = staged;
-  else if (recording) lds = ((lds + 15) & ~static_cast<size_t>(15)) + rec_sz;
+  else if (recording || adaptive) lds = ((lds + 15) & ~static_cast<size_t>(15)) + rec_sz;
   // enough threads to give each one a float4 of work, at least one wave
   int block = ((M + 3) / 4 + MMF_WAVE - 1) / MMF_WAVE * MMF_WAVE;
   if (block > kBlock) block = kBlock;
@@ -517,7 +562,7 @@ int launch_reweight_resample(const float* loglik, const float* logw_in, const fl
   if (mode == 1 && !soft && (d == 2 || d == 3)) {
     // few trajectories (round 6): a cluster of workgroups per trajectory, two meetings through L2, the same bits
     int dev = 0, cus = 0;
-    if (g_cluster_enabled && !recording && hipGetDevice(&dev) == hipSuccess &&
+    if (g_cluster_enabled && !recording && !adaptive && hipGetDevice(&dev) == hipSuccess &&
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) {
       const int C = cluster::plan(N, M, M_out, cus);
       if (C > 0) {
@@ -558,50 +603,55 @@ int launch_reweight_resample(const float* loglik, const float* logw_in, const fl
     const size_t marks_sz = ((static_cast<size_t>(M_out) + 4) * 4 + 15) & ~static_cast<size_t>(15);
     const size_t base_sz = slots + sc_sz + marks_sz + rec_sz;
     const size_t xs_sz = static_cast<size_t>(M) * d * sizeof(float);
-    const size_t with_states = base_sz + (recording ? (xs_sz + 15) & ~static_cast<size_t>(15) : xs_sz);
+    const size_t with_states = base_sz + ((recording || adaptive) ? (xs_sz + 15) & ~static_cast<size_t>(15) : xs_sz);
     if (base_sz <= 160 * 1024) {
       const bool st = N <= 256 ? with_states <= 160 * 1024 : with_states <= 80 * 1024;
       const size_t bytes = st ? with_states : base_sz;
-#define MMF_K1S_LAUNCH(D, ST, RC)                                                                    \
+#define MMF_K1S_LAUNCH(D, ST, RC, AD)                                                                \
   {                                                                                                  \
     if (bytes > 64 * 1024) {                                                                         \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pf_resample_systematic_kernel<D, ST, RC>), \
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pf_resample_systematic_kernel<D, ST, RC, AD>), \
                                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes)); \
       if (e != hipSuccess) return static_cast<int>(e);                                               \
     }                                                                                                \
-    pf_resample_systematic_kernel<D, ST, RC><<<N, block, bytes, s>>>(loglik, logw_in, states_in, u, estimate, states_out, \
-                                                                 logw_out, indices_out, M, M_out, lw_uniform, log_uniform, rec); \
+    pf_resample_systematic_kernel<D, ST, RC, AD><<<N, block, bytes, s>>>(loglik, logw_in, states_in, u, estimate, states_out, \
+                                                                 logw_out, indices_out, M, M_out, lw_uniform, log_uniform, rec, ad); \
   }
+#define MMF_K1S_ST(D, RC, AD) { if (st) MMF_K1S_LAUNCH(D, true, RC, AD) else MMF_K1S_LAUNCH(D, false, RC, AD) }
 #define MMF_K1S(D)                                                                                   \
   case D: {                                                                                          \
-    if (recording) { if (st) MMF_K1S_LAUNCH(D, true, true) else MMF_K1S_LAUNCH(D, false, true) }     \
-    else if (st) MMF_K1S_LAUNCH(D, true, false) else MMF_K1S_LAUNCH(D, false, false)                 \
+    if (adaptive) { if (recording) MMF_K1S_ST(D, true, true) else MMF_K1S_ST(D, false, true) }       \
+    else if (recording) MMF_K1S_ST(D, true, false) else MMF_K1S_ST(D, false, false)                  \
   } break;
       switch (d) { MMF_K1S(1) MMF_K1S(2) MMF_K1S(3) MMF_K1S(4) }
 #undef MMF_K1S
+#undef MMF_K1S_ST
 #undef MMF_K1S_LAUNCH
       MMF_CHECK_LAUNCH();
       return 0;
     }
   }
-#define MMF_K1_LAUNCH(D, ST, SO, RC)                                                           \
+#define MMF_K1_LAUNCH(D, ST, SO, RC, AD)                                                       \
   {                                                                                            \
     if (lds > 64 * 1024) {                                                                     \
       hipError_t e = hipFuncSetAttribute(                                                      \
-          reinterpret_cast<const void*>(&pf_reweight_resample_kernel<D, ST, SO, RC>),          \
+          reinterpret_cast<const void*>(&pf_reweight_resample_kernel<D, ST, SO, RC, AD>),      \
           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));                  \
       if (e != hipSuccess) return static_cast<int>(e);                                         \
     }                                                                                          \
-    pf_reweight_resample_kernel<D, ST, SO, RC><<<N, block, lds, s>>>(loglik, logw_in, states_in, u, \
-        estimate, states_out, logw_out, indices_out, M, M_out, mode, alpha, lw_uniform, log_uniform, rec); \
+    pf_reweight_resample_kernel<D, ST, SO, RC, AD><<<N, block, lds, s>>>(loglik, logw_in, states_in, u, \
+        estimate, states_out, logw_out, indices_out, M, M_out, mode, alpha, lw_uniform, log_uniform, rec, ad); \
   }
-#define MMF_K1_SS(D, RC)                                                                       \
+#define MMF_K1_SS(D, RC, AD)                                                                   \
   {                                                                                            \
-    if (soft) { if (stage) MMF_K1_LAUNCH(D, true, true, RC) else MMF_K1_LAUNCH(D, false, true, RC) } \
-    else if (stage) MMF_K1_LAUNCH(D, true, false, RC) else MMF_K1_LAUNCH(D, false, false, RC)  \
+    if (soft) { if (stage) MMF_K1_LAUNCH(D, true, true, RC, AD) else MMF_K1_LAUNCH(D, false, true, RC, AD) } \
+    else if (stage) MMF_K1_LAUNCH(D, true, false, RC, AD) else MMF_K1_LAUNCH(D, false, false, RC, AD)  \
   }
 #define MMF_K1(D)                                                                              \
-  case D: { if (recording) MMF_K1_SS(D, true) else MMF_K1_SS(D, false) } break;
+  case D: {                                                                                    \
+    if (adaptive) { if (recording) MMF_K1_SS(D, true, true) else MMF_K1_SS(D, false, true) }   \
+    else if (recording) MMF_K1_SS(D, true, false) else MMF_K1_SS(D, false, false)              \
+  } break;
   switch (d) {
     MMF_K1(1) MMF_K1(2) MMF_K1(3) MMF_K1(4)
   }
@@ -696,4 +746,18 @@ extern "C" int mmf_pf_reweight_resample_belief(const float* loglik, const float*
   if (mode == 0 && alpha != 1.f) return MMF_EINVAL;  // soft resampling needs a resampling mode
   return launch_reweight_resample(loglik, logw_in, states_in, u, estimate, states_out, logw_out, indices_out, N, M,
                                   M_out, d, mode, alpha, BeliefOut{cov, ess, log_evidence}, stream);
+}
+
+extern "C" int mmf_pf_reweight_resample_adaptive(const float* loglik, const float* logw_in, const float* states_in,
+                                                 const float* u, float* estimate, float* states_out, float* logw_out,
+                                                 int32_t* indices_out, int N, int M, int d, int mode, float alpha,
+                                                 float ess_threshold, int32_t* resampled, float* cov, float* ess,
+                                                 float* log_evidence, void* stream) {
+  if (mode != 1 && mode != 2) return MMF_EINVAL;                            // a threshold needs a resampling mode
+  if (!(ess_threshold > 0.f && ess_threshold <= 1.f)) return MMF_EINVAL;    // (a NaN fails both comparisons)
+  if (!logw_out || logw_out == logw_in) return MMF_EINVAL;                  // a kept trajectory's weights go somewhere else
+  if (!(alpha > 0.f && alpha <= 1.f)) return MMF_EINVAL;
+  // everything else -- null pointers, the in-place gather, d, the size limits (those of a recording call) -- is the launcher's
+  return launch_reweight_resample(loglik, logw_in, states_in, u, estimate, states_out, logw_out, indices_out, N, M, M, d,
+                                  mode, alpha, BeliefOut{cov, ess, log_evidence}, stream, ess_threshold, resampled);
 }

@@ -81,7 +81,7 @@ struct K1Belief {
 };
 constexpr int kK1BeliefMaxSums = 1 + MMF_MAX_STATE_DIM + MMF_MAX_STATE_DIM * (MMF_MAX_STATE_DIM + 1) / 2;
 
-struct K1BeliefScratch {  // REC only: behind everything else in dynamic LDS (mmf::k1_belief_lds_bytes)
+struct K1BeliefScratch {  // REC / ADAPT only: behind everything else in dynamic LDS (mmf::k1_belief_lds_bytes)
   float red[kK1MaxWaves][kK1BeliefMaxSums];
   float tot[kK1BeliefMaxSums];
   float piv_wave[kK1MaxWaves];  // per wave: -(smallest index holding the row maximum), -inf: none
@@ -104,6 +104,13 @@ __device__ __forceinline__ void k1_belief_store(const float* tot, float S, float
     if (ess != nullptr) *ess = (S * S) / tot[0];
     if (log_evidence != nullptr) *log_evidence = mx + logf(S);
   }
+}
+
+// ADAPT (ESS-triggered resampling, include/mmf.h): the effective sample size from the reduced sums, the expression -- and so the
+// bits -- k1_belief_store writes as the record's `ess`; a trajectory is KEPT iff k1_ess(...) >= fl32(threshold * M)
+__device__ __forceinline__ float k1_ess(float S, float W2) {
+#pragma clang fp contract(off)
+  return (S * S) / W2;
 }
 
 __device__ __forceinline__ float ld_coherent(const float* p) {
@@ -144,10 +151,15 @@ struct K1Trajectory {  // pointers of ONE trajectory's rows
   int* range_flag;       // COH: MMF_FLAG_GAVE_UP = "a reader gave up" (engine.run_persistent), or null
   unsigned long long* stamps;  // COH diagnostic: [4] cycle stamps of thread 0, or null
   int spin_sleep;        // COH: s_sleep between polls (0: busy polling)
+  float ess_floor;       // ADAPT: fl32(ess_threshold * M); the trajectory resamples iff !(ess >= ess_floor)
+  int32_t* resampled;    // ADAPT: 1 (resampled) / 0 (kept) of this trajectory, or null
 };
 
 // returns false (workgroup-uniform) when a COH reader gave up waiting for its granules
-template <int D, bool STAGE, bool COH, bool DET, bool REC = false>
+// ADAPT: ESS-triggered resampling (include/mmf.h, K1; M_out == M): the decision follows pass 2's reductions, and a KEPT
+// trajectory leaves before the announcements, the prefix maximum and the gather -- it writes mode 0's log-weights, its rows
+// as they came and the identity ancestors.  Sum e^2 is the record's own (REC) or, without a record, the same chain alone.
+template <int D, bool STAGE, bool COH, bool DET, bool REC = false, bool ADAPT = false>
 __device__ __forceinline__ bool resample_systematic_trajectory(unsigned char* smem, const K1Trajectory& a, int M, int M_out,
                                                                float lw_uniform, float log_uniform) {
   const size_t slots_sz = (static_cast<size_t>(M) * 8 + 15) & ~static_cast<size_t>(15);
@@ -182,6 +194,12 @@ __device__ __forceinline__ bool resample_systematic_trajectory(unsigned char* sm
   const float* lw = a.lw;
   const float* xs = a.xs;
   const bool vec = !COH && (M & 3) == 0;
+  // ADAPT, COH: the log-weights travel from step to step through global memory, written and read back by THIS workgroup
+  // only -- agent-scope relaxed atomics (through L2, as every other re-read of the launch), ordered by the barriers between
+  auto lw_at = [&](int i) -> float {
+    if constexpr (COH && ADAPT) return ld_coherent(lw + i);
+    else return lw[i];
+  };
   auto state_at = [&](size_t e) -> float {
     if constexpr (COH) {
       // every granule carries its own tag, and the gather CHECKS it: that the row belongs to this step follows from
@@ -274,7 +292,7 @@ __device__ __forceinline__ bool resample_systematic_trajectory(unsigned char* sm
 #pragma unroll
       for (int k = 1; k < MMF_LOOP_MAX_MEAS; ++k)
         if (k < a.n_ll) v = combine_loglik<DET>(v, granule_value(gk[k]));
-      reinterpret_cast<float*>(cdf + i)[0] = (lw ? lw[i] : lw_uniform) + v;
+      reinterpret_cast<float*>(cdf + i)[0] = (lw ? lw_at(i) : lw_uniform) + v;
     }
     if (gave_up) sc.gave_up = 1u;
     __syncthreads();
@@ -339,6 +357,7 @@ __device__ __forceinline__ bool resample_systematic_trajectory(unsigned char* sm
   for (int c = 0; c < D; ++c) acc[c] = 0.f;
   K1Belief<D> bel;  // REC
   if constexpr (REC) bel.reset();
+  float w2 = 0.f;   // ADAPT without REC: bel.s[0] alone
   unsigned long long carry = 0;
   unsigned long long own[4] = {0, 0, 0, 0};  // CDF of this thread's particles in the LAST chunk
   unsigned long long own_prev = 0;           // ... and of the particle just before them
@@ -352,6 +371,7 @@ __device__ __forceinline__ bool resample_systematic_trajectory(unsigned char* sm
 #pragma unroll
       for (int c = 0; c < D; ++c) acc[c] = 0.f;
       if constexpr (REC) bel.reset();
+      if constexpr (ADAPT && !REC) w2 = 0.f;
     }
     if (base == 0) {
 #pragma unroll
@@ -384,6 +404,10 @@ __device__ __forceinline__ bool resample_systematic_trajectory(unsigned char* sm
       if constexpr (REC) {
         const float xv = ok ? reinterpret_cast<const float*>(cdf + i0 + j)[0] : -INFINITY;
         bel.add(xv == -INFINITY ? 0.f : e[j], st + j * D, piv);
+      } else if constexpr (ADAPT) {
+        const float xv = ok ? reinterpret_cast<const float*>(cdf + i0 + j)[0] : -INFINITY;
+        const float ev = xv == -INFINITY ? 0.f : e[j];
+        w2 = __builtin_fmaf(ev, ev, w2);
       }
     }
     const unsigned long long incl = wave_inclusive_scan(tsum, lane);
@@ -406,6 +430,9 @@ __device__ __forceinline__ bool resample_systematic_trajectory(unsigned char* sm
           const float bw = wave_sum(bel.s[k]);
           if (lane == 0 && row < kK1MaxWaves) bsc.red[row][k] = bw;
         }
+      } else if constexpr (ADAPT) {
+        const float bw = wave_sum(w2);
+        if (lane == 0 && row < kK1MaxWaves) bsc.red[row][0] = bw;
       }
     }
     __syncthreads();
@@ -419,6 +446,12 @@ __device__ __forceinline__ bool resample_systematic_trajectory(unsigned char* sm
         float t = 0.f;
         for (int w = 0; w < nwaves_red; ++w) t += bsc.red[w][tid];
         bsc.tot[tid] = t;
+      }
+    } else if constexpr (ADAPT) {
+      if (last_chunk && tid == 0) {
+        float t = 0.f;
+        for (int w = 0; w < nwaves_red; ++w) t += bsc.red[w][0];
+        bsc.tot[0] = t;
       }
     }
     unsigned long long before = carry, total = 0;
@@ -446,6 +479,47 @@ __device__ __forceinline__ bool resample_systematic_trajectory(unsigned char* sm
     a.estimate[tid] = est;
   }
   if constexpr (REC) k1_belief_store<D>(bsc.tot, S, mx, a.cov, a.ess, a.log_evidence, tid);
+
+  float* so = a.so;
+  float* lo = a.lo;
+  int32_t* io = a.io;
+  if constexpr (ADAPT) {
+    // S and sum e^2 are the broadcast totals (LDS), so every lane of every wave takes the same side
+    const bool keep = k1_ess(S, bsc.tot[0]) >= a.ess_floor;  // a NaN resamples, a tie keeps
+    if (tid == 0 && a.resampled != nullptr) *a.resampled = keep ? 0 : 1;
+    if (keep) {
+      // mode 0's outputs: logw = (x - max) - log S, the rows as they came, ancestors 0 .. M - 1.  The slots of every chunk
+      // but the last hold the CDF by now: their x_i are formed again from the inputs (the same single addition)
+      const float logS = logf(S);
+      const int last_base = ((M - 1) / chunk) * chunk;
+      for (int i = tid; i < M; i += blockDim.x) {
+        float x;
+        if (i >= last_base) {
+          x = reinterpret_cast<const float*>(cdf + i)[0];
+        } else if constexpr (COH) {
+          float v = granule_value(ld_granule(reinterpret_cast<const Granule*>(a.ll[0]) + i));  // (tags checked before pass 1)
+#pragma unroll
+          for (int k = 1; k < MMF_LOOP_MAX_MEAS; ++k)
+            if (k < a.n_ll) v = combine_loglik<DET>(v, granule_value(ld_granule(reinterpret_cast<const Granule*>(a.ll[k]) + i)));
+          x = (lw ? lw_at(i) : lw_uniform) + v;
+        } else {
+          x = (lw ? lw[i] : lw_uniform) + ll[i];
+        }
+        const float w = (x - mx) - logS;
+        if constexpr (COH) st_coherent(lo + i, w);
+        else lo[i] = w;
+#pragma unroll
+        for (int c = 0; c < D; ++c) {
+          const float v = STAGE ? xs_lds[i * D + c] : state_at(static_cast<size_t>(i) * D + c);
+          if (COH && a.so_tag != 0) st_granule(reinterpret_cast<Granule*>(so) + static_cast<size_t>(i) * D + c, v, a.so_tag);
+          else so[static_cast<size_t>(i) * D + c] = v;
+        }
+        if (io) io[i] = i;
+      }
+      K1_STAMP(3);
+      return true;
+    }
+  }
 
   // ---- offspring boundaries: the first particle of every run of equal k_end announces itself,
   // marks[k_end(i - 1)] = i  when  k_end(i - 1) < k_end(i)  -- one writer per entry, plain LDS stores
@@ -491,9 +565,6 @@ __device__ __forceinline__ bool resample_systematic_trajectory(unsigned char* sm
     if (a.stamps && tid == 0) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory"); a.stamps[2] = t_; }
   }
   // ---- ancestor(k) = the latest announcement at or before k = inclusive prefix MAX of marks; gather; store
-  float* so = a.so;
-  float* lo = a.lo;
-  int32_t* io = a.io;
   const bool vec_out = !COH && (M_out & 3) == 0;
   unsigned carry2 = 0;
   for (int base = 0; base < M_out; base += chunk) {
@@ -541,7 +612,10 @@ __device__ __forceinline__ bool resample_systematic_trajectory(unsigned char* sm
             if (COH && a.so_tag != 0) st_granule(reinterpret_cast<Granule*>(so) + static_cast<size_t>(k) * D + c, g[j * D + c], a.so_tag);
             else so[static_cast<size_t>(k) * D + c] = g[j * D + c];
           }
-          if (lo) lo[k] = log_uniform;
+          if (lo) {
+            if constexpr (COH && ADAPT) st_coherent(lo + k, log_uniform);
+            else lo[k] = log_uniform;
+          }
           if (io) io[k] = idx[j];
         }
       }

@@ -35,6 +35,14 @@ class ParticleFilter(base.Filter):
     ``north_star`` asks for) or ``"multinomial"`` (upstream's distribution, one uniform per
     particle).  Both use the fixed-point CDF of ``csrc/pf_resample.hip``.
 
+    ``resample_ess_threshold`` in ``(0, 1]`` (``None``: off): ESS-triggered resampling -- on a step that resamples, a
+    trajectory resamples only if its effective sample size is below ``threshold * M`` (``not (ess >= float32(threshold *
+    M))``: a tie keeps) and otherwise keeps its particles and carries its normalised weights forward
+    (``mmf_pf_reweight_resample_adaptive`` / ``mmf_pf_forward_loop_adaptive``, the persistent launch included).  The
+    step's uniforms are drawn either way, so the noise stream does not depend on the decisions.  ``last_resampled``: the
+    decisions, ``bool (N,)`` after ``forward`` and ``(T, N)`` after ``forward_loop`` (``None`` while the threshold is unset).
+    A step that changes the particle count resamples every trajectory.
+
     Belief: ``particle_states (N, M, d)``, ``particle_log_weights (N, M)``.
     ``record_belief = True``: every step also leaves the second moment of the belief it took its estimate from -- the
     pre-resampling weighted set -- in ``last_belief``: ``covariance (N, d, d)`` about the weighted mean, ``ess (N)``,
@@ -48,10 +56,13 @@ class ParticleFilter(base.Filter):
                  measurement_model: base.ParticleFilterMeasurementModel,
                  num_particles: int = 100, resample: Optional[bool] = None,
                  resample_mode: str = "systematic",
-                 estimation_method: str = "weighted_average", soft_resample_alpha: float = 1.0):
+                 estimation_method: str = "weighted_average", soft_resample_alpha: float = 1.0,
+                 resample_ess_threshold: Optional[float] = None):
         super().__init__(state_dim=dynamics_model.state_dim)
         assert 0.0 < soft_resample_alpha <= 1.0
         self.soft_resample_alpha = soft_resample_alpha
+        self.resample_ess_threshold = resample_ess_threshold
+        self.last_resampled = None
         assert isinstance(dynamics_model, base.DynamicsModel)
         assert isinstance(measurement_model, base.ParticleFilterMeasurementModel)
         assert measurement_model.state_dim == self.state_dim
@@ -77,6 +88,15 @@ class ParticleFilter(base.Filter):
         self.particle_log_weights: torch.Tensor = None
         self._spare_states = None
         self._initialized = False
+
+    @property
+    def resample_ess_threshold(self) -> Optional[float]:
+        return self._resample_ess_threshold
+
+    @resample_ess_threshold.setter
+    def resample_ess_threshold(self, value: Optional[float]) -> None:
+        assert value is None or 0.0 < float(value) <= 1.0, "resample_ess_threshold must lie in (0, 1]"  # (a NaN fails too)
+        self._resample_ess_threshold = None if value is None else float(value)
 
     # ------------------------------------------------------------------ belief
     def initialize_beliefs(self, *, mean: torch.Tensor, covariance: torch.Tensor) -> None:
@@ -190,6 +210,10 @@ class ParticleFilter(base.Filter):
 
             estimate = torch.empty((N, d), dtype=torch.float32, device=states.device)
             rec = self._new_belief_record((N,), d, states.device) if self.record_belief else None
+            thr = self.resample_ess_threshold
+            # the decisions of this step: nobody on a step that does not resample, everybody where the particle count changes
+            self.last_resampled = None if thr is None else torch.full(
+                (N,), bool(do_resample), dtype=torch.bool, device=states.device)
             if do_resample:
                 Mo = self.num_particles
                 mode = _MODES[self.resample_mode]
@@ -202,7 +226,13 @@ class ParticleFilter(base.Filter):
                 idx = (torch.empty((N, Mo), dtype=torch.int32, device=states.device)
                        if self.record_indices else None)
                 lw_in = self.particle_log_weights
-                if rec is None:
+                if thr is not None and Mo == M:
+                    took = torch.empty((N,), dtype=torch.int32, device=states.device)
+                    rk = {} if rec is None else dict(cov=rec.covariance, ess=rec.ess, log_evidence=rec.log_evidence)
+                    k1 = lambda: _abi.pf_reweight_resample_adaptive(loglik, lw_in, states, u, estimate, out, logw_out, idx, mode,
+                                                                    self.soft_resample_alpha, ess_threshold=thr,
+                                                                    resampled=took, **rk)
+                elif rec is None:
                     k1 = lambda: _abi.pf_reweight_resample(loglik, lw_in, states, u, estimate,
                                                            out, logw_out, idx, mode, self.soft_resample_alpha)
                 else:
@@ -210,6 +240,8 @@ class ParticleFilter(base.Filter):
                                                                   self.soft_resample_alpha, cov=rec.covariance, ess=rec.ess,
                                                                   log_evidence=rec.log_evidence)
                 _timed("pf_reweight_resample", 0.0, N * M * 4.0 * (2 + d) + N * Mo * 4.0 * d, k1)
+                if thr is not None and Mo == M:
+                    self.last_resampled = took.ne(0)
                 self._spare_states = states
                 self.last_resample_indices = idx
             else:
@@ -289,6 +321,8 @@ class ParticleFilter(base.Filter):
             else:
                 estimate = states[torch.arange(N, device=states.device), torch.argmax(logw, dim=1)]
         self.particle_states, self.particle_log_weights = states, logw
+        thr = self.resample_ess_threshold
+        self.last_resampled = None if thr is None else torch.full((N,), bool(do_resample), dtype=torch.bool, device=states.device)
         if do_resample:
             Mo = self.num_particles
             mode = _MODES[self.resample_mode]
@@ -298,10 +332,18 @@ class ParticleFilter(base.Filter):
             scratch = torch.empty((N, d), dtype=torch.float32, device=states.device)
             soft = self.soft_resample_alpha < 1.0
             idx = torch.empty((N, Mo), dtype=torch.int32, device=states.device) if soft else None
+            adaptive = thr is not None and Mo == M
             with torch.no_grad():
-                _abi.pf_reweight_resample(torch.zeros_like(logw), logw.detach().contiguous(),
-                                          states.detach().contiguous(), u, scratch, out, logw_out, idx, mode,
-                                          self.soft_resample_alpha)
+                if adaptive:  # K1 supplies the ancestors and the decisions (the ESS of the normalised weights)
+                    took = torch.empty((N,), dtype=torch.int32, device=states.device)
+                    _abi.pf_reweight_resample_adaptive(torch.zeros_like(logw), logw.detach().contiguous(),
+                                                       states.detach().contiguous(), u, scratch, out, logw_out, idx, mode,
+                                                       self.soft_resample_alpha, ess_threshold=thr, resampled=took)
+                    self.last_resampled = took.ne(0)
+                else:
+                    _abi.pf_reweight_resample(torch.zeros_like(logw), logw.detach().contiguous(),
+                                              states.detach().contiguous(), u, scratch, out, logw_out, idx, mode,
+                                              self.soft_resample_alpha)
             if soft:
                 # upstream's soft resampling is differentiable: the ancestors come from K1, the
                 # survivors' states and importance weights are re-derived with torch ops so that
@@ -312,6 +354,12 @@ class ParticleFilter(base.Filter):
                 new = torch.gather(logw - mix, 1, gi)
                 out = torch.gather(states, 1, gi[:, :, None].expand(N, Mo, d))
                 logw_out = new - torch.logsumexp(new, dim=1, keepdim=True)
+            if adaptive:
+                # per trajectory: a kept one is the no-resample step's belief, gradients through its weights included
+                # (soft: its identity ancestors make `out` the same rows already; the weights are the ones to select)
+                took = self.last_resampled
+                out = torch.where(took[:, None, None], out, states)
+                logw_out = torch.where(took[:, None], logw_out, logw)
             self.particle_states, self.particle_log_weights = out, logw_out
         return estimate
 
@@ -373,6 +421,8 @@ class ParticleFilter(base.Filter):
         if self.record_belief:  # written by K1 in every form of the loop; does not change which form runs
             self.last_belief = rec = self._new_belief_record((T, N), d, dev)
             a.cov_steps, a.ess_steps, a.log_evidence_steps = P(rec.covariance), P(rec.ess), P(rec.log_evidence)
+        thr = self.resample_ess_threshold if mode != 0 else None  # (only steps that resample have a decision to take)
+        took = torch.empty((T, N), dtype=torch.int32, device=dev) if thr is not None else None
         a.range_flag = P(engine.range_flag(dev), torch.int32)
         if do_resample and self.soft_resample_alpha < 1.0:
             a.soft_alpha = float(self.soft_resample_alpha)  # survivors carry importance weights (mmf_pf_reweight_resample_soft)
@@ -382,6 +432,7 @@ class ParticleFilter(base.Filter):
             a.estimate_argmax, a.estimate_scratch = 1, P(est_scratch)
         timer = engine.kernel_timer()
         # small problem: ONE launch for all T steps (csrc/pf_persistent.inc); same bits as the loop of launches
+        # (ESS-triggered resampling does not change eligibility: the K1 role takes the adaptive branch)
         go = (engine.PF_PERSISTENT and mode == 1 and timer is None and not self.record_indices
               and a.soft_alpha == 0.0 and not a.estimate_argmax and d in (2, 3)
               and dyn._net.n_res == 3 and all(net.n_res == 2 for net, _b, _l in nets)
@@ -394,7 +445,8 @@ class ParticleFilter(base.Filter):
             events = timer.loop_events(2 * len(names) * len(range(stride // 2, T, stride)))  # pf_loop.hip samples t % stride == stride // 2
         # the persistent launch needs ALL its workgroups resident; if it gives up (another process on this GPU) the belief
         # is restored and the loop re-run as launches, for this call and for the rest of the process (engine.run_persistent)
-        loc = engine.run_persistent(a, lambda: _abi.pf_forward_loop(a, like, events, stride), device=dev,
+        loc = engine.run_persistent(a, lambda: _abi.pf_forward_loop(a, like, events, stride, ess_threshold=thr,
+                                                                    resampled_steps=took), device=dev,
                                     n_sync_words=_abi.pf_persistent_sync_words(N, M, d, len(nets)) if go else 0,
                                     restore=(states_a, logw_a))
         if timer is not None:
@@ -409,6 +461,10 @@ class ParticleFilter(base.Filter):
         self.particle_states = states_b if loc & 1 else states_a
         self._spare_states = states_a if loc & 1 else states_b
         self.particle_log_weights = logw_b if loc & 2 else logw_a
+        if self.resample_ess_threshold is None:
+            self.last_resampled = None
+        else:
+            self.last_resampled = took.ne(0) if took is not None else torch.zeros((T, N), dtype=torch.bool, device=dev)
         del keep
         return est
 
@@ -454,6 +510,20 @@ class ParticleFilter(base.Filter):
         self._spare_states = None
         return est
 
+    def _loop_of_steps(self, T, step, N):
+        """``forward_loop`` step by step: ``step(t, rows of step t in the T*N flattened arrays)``; the per-step records
+        (``last_belief``, ``last_resampled``) are stacked along a leading ``T`` axis."""
+        out, beliefs, took = [], [], []
+        for t in range(T):
+            out.append(step(t, slice(t * N, (t + 1) * N)))
+            beliefs.append(self.last_belief)
+            took.append(self.last_resampled)
+        if self.record_belief:
+            self.last_belief = base.stack_belief_records(beliefs)
+        if took and took[0] is not None:
+            self.last_resampled = torch.stack(took, dim=0)
+        return torch.stack(out, dim=0)
+
     @engine.checked_step
     def forward(self, *, observations, controls) -> torch.Tensor:
         if use_autograd(self):
@@ -471,7 +541,8 @@ class ParticleFilter(base.Filter):
         flat = lambda x: x.reshape((T * N,) + tuple(x.shape[2:]))
         if use_autograd(self):
             if not engine.use_hip_backward():
-                return base.Filter.forward_loop(self, observations=observations, controls=controls)
+                return self._loop_of_steps(T, lambda t, sl: self(
+                    observations=tree_index(observations, t), controls=tree_index(controls, t)), N)
             # training, K6 backend: the per-trajectory networks (image CNNs, encoders, weight
             # model) are differentiable torch ops evaluated ONCE on the T*N flattened rows
             dyn_all = meas_all = None
@@ -480,19 +551,14 @@ class ParticleFilter(base.Filter):
             if hasattr(self.measurement_model, "encode_observations_autograd"):
                 meas_all = self.measurement_model.encode_observations_autograd(tree_map(observations, flat))
             native = self._native_train_loop(dyn_all, meas_all, T, N)
-            if native is not None:
+            if native is not None:  # (it only runs without resampling: nobody resampled)
+                self.last_resampled = (None if self.resample_ess_threshold is None else
+                                       torch.zeros((T, N), dtype=torch.bool, device=native.device))
                 return native
-            out, beliefs = [], []
-            for t in range(T):
-                sl = slice(t * N, (t + 1) * N)
-                out.append(self._step_autograd(
-                    tree_index(observations, t), tree_index(controls, t),
-                    None if dyn_all is None else dyn_all[sl],
-                    None if meas_all is None else {k: v[sl] for k, v in meas_all.items()}))
-                beliefs.append(self.last_belief)
-            if self.record_belief:
-                self.last_belief = base.stack_belief_records(beliefs)
-            return torch.stack(out, dim=0)
+            return self._loop_of_steps(T, lambda t, sl: self._step_autograd(
+                tree_index(observations, t), tree_index(controls, t),
+                None if dyn_all is None else dyn_all[sl],
+                None if meas_all is None else {k: v[sl] for k, v in meas_all.items()}), N)
         obs_all = ctrl_all = None
         with torch.no_grad():
             if hasattr(self.measurement_model, "forward_encoded"):
@@ -502,17 +568,10 @@ class ParticleFilter(base.Filter):
             native = self._native_loop(obs_all, ctrl_all, T, N)
         if native is not None:
             return native
-        out, beliefs = [], []
-        for t in range(T):
-            sl = slice(t * N, (t + 1) * N)
-            out.append(self._step(
-                tree_index(observations, t), tree_index(controls, t),
-                None if obs_all is None else {k: v[sl] for k, v in obs_all.items()},
-                None if ctrl_all is None else {k: v[sl] for k, v in ctrl_all.items()}))
-            beliefs.append(self.last_belief)
-        if self.record_belief:
-            self.last_belief = base.stack_belief_records(beliefs)
-        return torch.stack(out, dim=0)
+        return self._loop_of_steps(T, lambda t, sl: self._step(
+            tree_index(observations, t), tree_index(controls, t),
+            None if obs_all is None else {k: v[sl] for k, v in obs_all.items()},
+            None if ctrl_all is None else {k: v[sl] for k, v in ctrl_all.items()}), N)
 
 
 class VirtualSensorExtendedKalmanFilter(base.Filter):
