@@ -910,6 +910,10 @@ int mmf_ukf_sigma_points(const float* mu, const float* Sigma, float scale, float
 /*  points (N, 2d+1, d) propagated sigma points; wm0 / wc0: mean / covariance weight of point 0,
  *  wi: weight of every other point; q_tril (d, d): dynamics noise (Q = L L^T)
  *  -> mu_pred (N, d), Sigma_pred (N, d, d) = sum_i wc_i (X_i - mu)(X_i - mu)^T + Q
+ *  The mean weights must be NORMALISED, wm0 + 2 d wi = 1 (Julier's and Merwe's are; so is any set that reproduces a
+ *  constant): the sums are taken about point 0, mu = X_0 + wi sum_i (X_i - X_0), which keeps fp32 accurate where
+ *  wm0 ~ -1e4 (Merwe's default alpha = 1e-2) would cancel.  A wm0 off by more than a few float32 ulps of the largest
+ *  of wm0, 2 d wi (both arrive rounded to float32) is refused with MMF_EINVAL.
  */
 int mmf_ukf_moments(const float* points, float wm0, float wc0, float wi, const float* q_tril,
                     float* mu_pred, float* Sigma_pred, int N, int d, void* stream);

@@ -13,10 +13,15 @@
 
 namespace mmf_ekf {
 
-template <int D>
+template <int D, typename F = float>
 struct Mat {
-  float a[D][D];
+  F a[D][D];
 };
+
+__device__ __forceinline__ float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ double fma_(double a, double b, double c) { return __builtin_fma(a, b, c); }
+__device__ __forceinline__ float abs_(float a) { return __builtin_fabsf(a); }
+__device__ __forceinline__ double abs_(double a) { return __builtin_fabs(a); }
 
 template <int D>
 __device__ __forceinline__ Mat<D> load_mat(const float* p) {
@@ -70,31 +75,31 @@ __device__ __forceinline__ Mat<D> matmul_nt(const Mat<D>& x, const Mat<D>& y) { 
 
 // Gauss-Jordan with partial pivoting (the pivot order LU-based torch.inverse uses); row
 // swaps are branch-free selects so every index stays compile-time and the matrix stays in
-// registers.
-template <int D>
-__device__ __forceinline__ Mat<D> inverse(Mat<D> m) {
+// registers.  F = float everywhere but in the information-form fusion (see fuse).
+template <int D, typename F>
+__device__ __forceinline__ Mat<D, F> inverse(Mat<D, F> m) {
 #pragma clang fp contract(off)
-  Mat<D> inv;
+  Mat<D, F> inv;
 #pragma unroll
   for (int i = 0; i < D; ++i)
 #pragma unroll
-    for (int j = 0; j < D; ++j) inv.a[i][j] = (i == j) ? 1.f : 0.f;
+    for (int j = 0; j < D; ++j) inv.a[i][j] = (i == j) ? F(1) : F(0);
 #pragma unroll
   for (int c = 0; c < D; ++c) {
 #pragma unroll
     for (int r = c + 1; r < D; ++r) {
-      const bool sw = fabsf(m.a[r][c]) > fabsf(m.a[c][c]);
+      const bool sw = abs_(m.a[r][c]) > abs_(m.a[c][c]);
 #pragma unroll
       for (int j = 0; j < D; ++j) {
-        const float t0 = m.a[c][j], t1 = m.a[r][j];
+        const F t0 = m.a[c][j], t1 = m.a[r][j];
         m.a[c][j] = sw ? t1 : t0;
         m.a[r][j] = sw ? t0 : t1;
-        const float u0 = inv.a[c][j], u1 = inv.a[r][j];
+        const F u0 = inv.a[c][j], u1 = inv.a[r][j];
         inv.a[c][j] = sw ? u1 : u0;
         inv.a[r][j] = sw ? u0 : u1;
       }
     }
-    const float piv = 1.0f / m.a[c][c];
+    const F piv = F(1) / m.a[c][c];
 #pragma unroll
     for (int j = 0; j < D; ++j) {
       m.a[c][j] *= piv;
@@ -103,11 +108,11 @@ __device__ __forceinline__ Mat<D> inverse(Mat<D> m) {
 #pragma unroll
     for (int r = 0; r < D; ++r) {
       if (r == c) continue;
-      const float f = m.a[r][c];
+      const F f = m.a[r][c];
 #pragma unroll
       for (int j = 0; j < D; ++j) {
-        m.a[r][j] = __builtin_fmaf(-f, m.a[c][j], m.a[r][j]);
-        inv.a[r][j] = __builtin_fmaf(-f, inv.a[c][j], inv.a[r][j]);
+        m.a[r][j] = fma_(-f, m.a[c][j], m.a[r][j]);
+        inv.a[r][j] = fma_(-f, inv.a[c][j], inv.a[r][j]);
       }
     }
   }
@@ -117,7 +122,7 @@ __device__ __forceinline__ Mat<D> inverse(Mat<D> m) {
 constexpr int kMaxK = 4;
 
 // predict + correct of one sub-filter (C = I):  S- = A S A^T + L L^T;  K = S- (S- + T T^T)^-1;
-// mu = mu- + K (z - mu-);  S = (I - K) S-
+// mu = mu- + K (z - mu-);  S = (I - K) S-  with  I - K = T T^T (S- + T T^T)^-1
 template <int D>
 __device__ __forceinline__ void predict_correct(const Mat<D>& Ak, const Mat<D>& S0, const Mat<D>& L, const Mat<D>& T,
                                                 const float (&mp)[D], const float (&z)[D], float (&mu_out)[D], Mat<D>& S_out) {
@@ -134,19 +139,20 @@ __device__ __forceinline__ void predict_correct(const Mat<D>& Ak, const Mat<D>& 
       Sp.a[i][j] += Q.a[i][j];
       Sinn.a[i][j] = Sp.a[i][j] + Rm.a[i][j];
     }
-  const Mat<D> G = matmul<D>(Sp, inverse<D>(Sinn));
+  const Mat<D> Si = inverse<D>(Sinn);
+  const Mat<D> G = matmul<D>(Sp, Si);
+  // I - G = (Sinn - S-) Sinn^-1 = T T^T Sinn^-1, formed as that product: where the sensor is sharp next to the prediction
+  // G is close to I and "I - G" keeps only the rounding of G -- 7e-5 of S on its small directions, which the information
+  // form (fuse, fusion 2) inverts: mu_f went 2e-4 .. 6e-4 off from that alone.  As a product, S is good to 1e-5.
+  const Mat<D> ImG = matmul<D>(Rm, Si);
   float innov[D];
 #pragma unroll
   for (int i = 0; i < D; ++i) innov[i] = z[i] - mp[i];
-  Mat<D> ImG;
 #pragma unroll
   for (int i = 0; i < D; ++i) {
     float s = 0.f;
 #pragma unroll
-    for (int j = 0; j < D; ++j) {
-      s = __builtin_fmaf(G.a[i][j], innov[j], s);
-      ImG.a[i][j] = ((i == j) ? 1.f : 0.f) - G.a[i][j];
-    }
+    for (int j = 0; j < D; ++j) s = __builtin_fmaf(G.a[i][j], innov[j], s);
     mu_out[i] = mp[i] + s;
   }
   S_out = matmul<D>(ImG, Sp);
@@ -187,29 +193,34 @@ __device__ __forceinline__ void fuse(int K, int fusion, const float (&w)[kMaxK][
     }
   } else if (fusion == 2) {
     // P_k = (Sigma_k + 1e-9)^-1 ; Sigma_f = (sum_k P_k + 1e-9)^-1 ; mu_f = Sigma_f sum_k P_k mu_k
-    Mat<D> Psum;
-    float info[D];
+    // In DOUBLE: the posteriors of a well-observed state are ill-conditioned (condition 1e2 .. 1e3 is common), their
+    // precisions are summed and inverted again, and mu_f is a product of nearly cancelling factors.  In float32 the K + 1
+    // inversions alone put mu_f up to 4e-3 off (four times what torch's fp32 LU form loses on the same rows).  What is left
+    // in double is the rounding of the float32 posteriors themselves, amplified by their condition: under 4e-5 with
+    // predict_correct's product form of I - G.  5 d x d inversions per trajectory: no time next to the launch.
+    Mat<D, double> Psum;
+    double info[D];
 #pragma unroll
     for (int i = 0; i < D; ++i) {
-      info[i] = 0.f;
+      info[i] = 0.0;
 #pragma unroll
-      for (int j = 0; j < D; ++j) Psum.a[i][j] = 0.f;
+      for (int j = 0; j < D; ++j) Psum.a[i][j] = 0.0;
     }
 #pragma unroll
     for (int k = 0; k < kMaxK; ++k) {
       if (k >= K) break;
-      Mat<D> t = Ss[k];
+      Mat<D, double> t;
 #pragma unroll
       for (int i = 0; i < D; ++i)
 #pragma unroll
-        for (int j = 0; j < D; ++j) t.a[i][j] += 1e-9f;
-      const Mat<D> P = inverse<D>(t);
+        for (int j = 0; j < D; ++j) t.a[i][j] = static_cast<double>(Ss[k].a[i][j]) + 1e-9;
+      const Mat<D, double> P = inverse<D>(t);
 #pragma unroll
       for (int i = 0; i < D; ++i) {
-        float s = 0.f;
+        double s = 0.0;
 #pragma unroll
         for (int j = 0; j < D; ++j) {
-          s = __builtin_fmaf(P.a[i][j], mus[k][j], s);
+          s = fma_(P.a[i][j], static_cast<double>(mus[k][j]), s);
           Psum.a[i][j] += P.a[i][j];
         }
         info[i] += s;
@@ -218,14 +229,17 @@ __device__ __forceinline__ void fuse(int K, int fusion, const float (&w)[kMaxK][
 #pragma unroll
     for (int i = 0; i < D; ++i)
 #pragma unroll
-      for (int j = 0; j < D; ++j) Psum.a[i][j] += 1e-9f;
-    Sf = inverse<D>(Psum);
+      for (int j = 0; j < D; ++j) Psum.a[i][j] += 1e-9;
+    const Mat<D, double> Sfd = inverse<D>(Psum);
 #pragma unroll
     for (int i = 0; i < D; ++i) {
-      float s = 0.f;
+      double s = 0.0;
 #pragma unroll
-      for (int j = 0; j < D; ++j) s = __builtin_fmaf(Sf.a[i][j], info[j], s);
-      mf[i] = s;
+      for (int j = 0; j < D; ++j) {
+        s = fma_(Sfd.a[i][j], info[j], s);
+        Sf.a[i][j] = static_cast<float>(Sfd.a[i][j]);
+      }
+      mf[i] = static_cast<float>(s);
     }
   }
 }

@@ -753,7 +753,13 @@ class JulierSigmaPointStrategy:
 
 class MerweSigmaPointStrategy:
     """Van der Merwe's scaled points: ``lambda = alpha^2 (d + kappa) - d``, ``kappa = 3 - d`` unless
-    given; ``wc0 = wm0 + 1 - alpha^2 + beta`` (upstream ``torchfilter.utils.MerweSigmaPointStrategy``)."""
+    given; ``wc0 = wm0 + 1 - alpha^2 + beta`` (upstream ``torchfilter.utils.MerweSigmaPointStrategy``).
+
+    Small ``alpha`` means large weights of opposite sign: the default ``alpha = 1e-2`` has ``wm0 ~ -1e4`` and ``wi ~
+    1.7e3``.  ``mmf_ukf_moments`` takes its sums about point 0 (``wm0 + 2 d wi = 1``), which keeps the default within the
+    fp32 bar (``tests/test_gpu_kalman_kernels.py``, group F: 1e-4 on the mean, three times the fp32 yardstick's ~1e-4 on the
+    covariance).  ``alpha = 1e-3`` (``wi ~ 1.7e5``) is beyond float32 in any summation order -- the covariance is off by
+    ~1e-2 -- and is neither tested nor supported at that accuracy; use ``alpha >= 1e-2``."""
 
     def __init__(self, alpha: float = 1e-2, beta: float = 2.0, kappa: Optional[float] = None):
         self.alpha, self.beta, self.kappa = alpha, beta, kappa
