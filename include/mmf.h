@@ -529,6 +529,55 @@ int mmf_pf_forward_loop(const MmfPfLoopArgs* args /* host */, void* stream);
 int mmf_pf_forward_loop_adaptive(const MmfPfLoopArgs* args /* host */, float ess_threshold,
                                  int32_t* resampled_steps, void* stream);
 
+/* The step loop that runs the dynamics network ONCE PER DISTINCT RESAMPLED ANCESTOR.  Systematic resampling copies a
+ * surviving particle into CONSECUTIVE output slots (the ancestor sequence is non-decreasing): a run.  The dynamics network's
+ * output is a pure function of the particle's state and its trajectory's control -- a particle is a column of the MFMA tiles
+ * and columns do not mix -- so every copy of an ancestor gets the same head outputs bit for bit; only the noise added in the
+ * epilogue differs, and that chain is separable (x' = [x + (dir + b) sigmoid(gate + b)] + scale_tril eps).  With a workspace:
+ *   - K1 of steps 0 .. T-2 is mmf_pf_resample_runs: the RUN TABLE instead of the gather (no state row is read for the
+ *     gather or stored: 4 B per slot + 8 B per run instead of 8 d B per particle);
+ *   - the dynamics launch of steps 1 .. T-1 is mmf_pf_dynamics_runs: a tile is 64 (small problems: 32) runs of one trajectory,
+ *     its columns read the ancestors' rows from the buffer the previous step PROPAGATED, and the epilogue expands every run
+ *     into its output slots, each with its own noise (tensor row or counter-based draw of the SLOT);
+ *   - step 0's dynamics and step T-1's K1 are the kernels of mmf_pf_forward_loop (the belief on entry and on return is a
+ *     full particle set); states_a / states_b ping-pong as propagated buffers, final_location as ever.
+ * Purely additive to ABI 42, as the adaptive loop was: new symbols and a struct of their own, MmfPfLoopArgs keeps its layout.
+ * Every output of the loop -- estimates, records, indices_steps, loglik_steps, the belief on return -- has the bits
+ * mmf_pf_forward_loop produces (tests/test_gpu_dedup_dynamics.py).  The path is taken when mmf_pf_dedup_plan() == 1 -- plain
+ * systematic resampling (resample_mode 1, soft_alpha 0 or 1), M a multiple of 64, d = 2 or 3, the run variant of K1 fits LDS --
+ * and every workspace pointer is set; otherwise (and with ws == null) the call IS mmf_pf_forward_loop.  The persistent form
+ * (args->persistent) is unchanged; only its fallback to launches takes the workspace. */
+typedef struct MmfPfDedupWorkspace {
+  int32_t* rank;       /* (N, M)      index of the run every output slot belongs to                  */
+  int32_t* run_anc;    /* (N, M + 1)  ancestor particle of every run                                 */
+  int32_t* run_start;  /* (N, M + 1)  first output slot of every run; run_start[n][n_runs[n]] = M    */
+  int32_t* n_runs;     /* (N)         number of runs = distinct ancestors                            */
+} MmfPfDedupWorkspace;   /* host struct holding device pointers; mmf_pf_dedup_workspace_words(N, M) int32 in all */
+int mmf_pf_forward_loop_dedup(const MmfPfLoopArgs* args /* host */, const MmfPfDedupWorkspace* ws /* host or null */,
+                              void* stream);
+/* 1: the sizes / modes take the run path, 0: they do not, MMF_EINVAL: M < 1 or d < 1.  `recording`: a belief record is kept. */
+int mmf_pf_dedup_plan(int M, int d, int resample_mode, float soft_alpha, int recording);
+size_t mmf_pf_dedup_workspace_words(int N, int M);
+/* K1, plain systematic resampling (mode 1, M_out == M), writing the run table instead of the gathered particles.  estimate,
+ * cov / ess / log_evidence (each or null), indices_out (or null) and logw_out (or null: uniform by definition) are bit for
+ * bit what mmf_pf_reweight_resample_belief writes on the same inputs; rank / run_anc / run_start / n_runs as in
+ * MmfPfDedupWorkspace.  Limits: the search-free K1's (12 B of LDS per particle: M <= 13,000), larger -> MMF_ETOOLARGE. */
+int mmf_pf_resample_runs(const float* loglik, const float* logw_in, const float* states_in, const float* u,
+                         float* estimate, float* logw_out, int32_t* indices_out, int32_t* rank, int32_t* run_anc,
+                         int32_t* run_start, int32_t* n_runs, int N, int M, int d, float* cov, float* ess,
+                         float* log_evidence, void* stream);
+/* mmf_pf_dynamics over a run table: states_out[n][k] = drift(states_prev[n][run_anc[n][rank[n][k]]]) + scale_tril eps[n][k],
+ * the network evaluated once per run.  M a multiple of 64, n_res = 3, d = 2 or 3, states_out != states_prev. */
+int mmf_pf_dynamics_runs(const float* packed, int n_res, int precision, const float* states_prev,
+                         const float* traj_bias, const float* noise, const float* scale_tril, const int32_t* rank,
+                         const int32_t* run_anc, const int32_t* run_start, const int32_t* n_runs, float* states_out,
+                         int* range_flag, int N, int M, int d, void* stream);
+int mmf_pf_dynamics_runs_philox(const float* packed, int n_res, int precision, const float* states_prev,
+                                const float* traj_bias, unsigned long long seed, unsigned step, unsigned traj0,
+                                const float* scale_tril, const int32_t* rank, const int32_t* run_anc,
+                                const int32_t* run_start, const int32_t* n_runs, float* states_out, int* range_flag,
+                                int N, int M, int d, void* stream);
+
 /* The persistent form of the step loop (MmfPfLoopArgs.persistent): at the sizes the reference itself runs (32
  * trajectories x 300 particles: door_models/pf.py:24-27, eval_helpers.py:125-142) a step is bound by the fixed cost
  * of its four launches; one launch whose workgroups keep ONE network's weights in LDS for all T steps and hand

@@ -93,6 +93,11 @@ class MmfPfLoopArgs(Structure):
                 ("cov_steps", _FP), ("ess_steps", _FP), ("log_evidence_steps", _FP)]
 
 
+class MmfPfDedupWorkspace(Structure):
+    """Run table of ``mmf_pf_forward_loop_dedup`` (include/mmf.h): int32 device arrays."""
+    _fields_ = [("rank", _FP), ("run_anc", _FP), ("run_start", _FP), ("n_runs", _FP)]
+
+
 class MmfTrainNet(Structure):
     _fields_ = [("packed", _FP), ("packed_f32", _FP), ("packed_t", _FP), ("head_w", _FP), ("pw", _FP), ("pb", _FP),
                 ("p_first", _FP), ("p_head", _FP), ("p_dout", _FP), ("p_traj", _FP), ("packed_dual", _FP)]
@@ -170,6 +175,14 @@ SIGNATURES = {
     "mmf_pf_init_particles": (c_int, [_FP, _FP, _FP, _FP, _FP, _FP, c_int, c_int, c_int, c_void_p]),
     "mmf_pf_forward_loop": (c_int, [POINTER(MmfPfLoopArgs), c_void_p]),
     "mmf_pf_forward_loop_adaptive": (c_int, [POINTER(MmfPfLoopArgs), ctypes.c_float, _FP, c_void_p]),
+    "mmf_pf_forward_loop_dedup": (c_int, [POINTER(MmfPfLoopArgs), POINTER(MmfPfDedupWorkspace), c_void_p]),
+    "mmf_pf_dedup_plan": (c_int, [c_int, c_int, c_int, ctypes.c_float, c_int]),
+    "mmf_pf_dedup_workspace_words": (c_size_t, [c_int, c_int]),
+    "mmf_pf_resample_runs": (c_int, [_FP] * 11 + [c_int, c_int, c_int, _FP, _FP, _FP, c_void_p]),
+    "mmf_pf_dynamics_runs": (c_int, [_FP, c_int, c_int, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP,
+                                     c_int, c_int, c_int, c_void_p]),
+    "mmf_pf_dynamics_runs_philox": (c_int, [_FP, c_int, c_int, _FP, _FP, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                            _FP, _FP, _FP, _FP, _FP, _FP, _FP, c_int, c_int, c_int, c_void_p]),
     "mmf_pf_argmax_estimate": (c_int, [_FP, _FP, _FP, _FP, c_int, c_int, c_int, c_void_p]),
     "mmf_pf_persistent_plan": (c_int, [c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     "mmf_pf_persistent_sync_words": (c_size_t, [c_int, c_int, c_int, c_int]),
@@ -726,13 +739,45 @@ def pf_init_particles(mean, covariance, eps, states, logw, not_pd):
                "mmf_pf_init_particles")
 
 
+def pf_dedup_plan(M: int, d: int, resample_mode: int, soft_alpha: float = 0.0, recording: bool = False) -> bool:
+    """Whether ``mmf_pf_forward_loop_dedup`` takes the run path at these sizes / modes (include/mmf.h)."""
+    return load().mmf_pf_dedup_plan(int(M), int(d), int(resample_mode), float(soft_alpha), int(bool(recording))) == 1
+
+
+def pf_dedup_workspace_words(N: int, M: int) -> int:
+    return int(load().mmf_pf_dedup_workspace_words(int(N), int(M)))
+
+
+def pf_dedup_workspace(words: torch.Tensor, N: int, M: int):
+    """Carve ``MmfPfDedupWorkspace`` out of one int32 tensor of ``pf_dedup_workspace_words(N, M)`` elements:
+    ``rank (N, M) | run_anc (N, M + 1) | run_start (N, M + 1) | n_runs (N)``."""
+    assert words.dtype == torch.int32 and words.is_contiguous() and words.numel() >= N * M + 2 * N * (M + 1) + N
+    ws = MmfPfDedupWorkspace()
+    base, o1, o2, o3 = words.data_ptr(), N * M, N * M + N * (M + 1), N * M + 2 * N * (M + 1)
+    ws.rank, ws.run_anc, ws.run_start, ws.n_runs = base, base + 4 * o1, base + 4 * o2, base + 4 * o3
+    return ws
+
+
+def pf_resample_runs(loglik, logw_in, states, u, estimate, indices_out, rank, run_anc, run_start, n_runs, *,
+                     logw_out=None, cov=None, ess=None, log_evidence=None):
+    """K1's run variant alone (``mmf_pf_resample_runs``): the run table of plain systematic resampling."""
+    N, M, d = states.shape
+    i32 = torch.int32
+    with _on(states):
+        _check(load().mmf_pf_resample_runs(ptr(loglik), ptr(logw_in), ptr(states), ptr(u), ptr(estimate), ptr(logw_out),
+                                           ptr(indices_out, dtype=i32), ptr(rank, dtype=i32), ptr(run_anc, dtype=i32),
+                                           ptr(run_start, dtype=i32), ptr(n_runs, dtype=i32), N, M, d, ptr(cov), ptr(ess),
+                                           ptr(log_evidence), stream_of(states)), "mmf_pf_resample_runs")
+
+
 def pf_forward_loop(args: MmfPfLoopArgs, like: torch.Tensor, events=None, event_stride: int = 1, *,
-                    ess_threshold: float = None, resampled_steps=None) -> int:
+                    ess_threshold: float = None, resampled_steps=None, dedup: MmfPfDedupWorkspace = None) -> int:
     """Enqueue T filter steps; returns the final-location bits (see include/mmf.h).
     ``events``: optional flat list of created ``torch.cuda.Event`` (timing) recorded in C
     around the launches of every ``event_stride``-th step.
     ``ess_threshold``: ESS-triggered resampling (``mmf_pf_forward_loop_adaptive``), ``resampled_steps`` its ``(T, N)`` int32
-    decisions or ``None``."""
+    decisions or ``None``.  ``dedup``: the run-table workspace (``mmf_pf_forward_loop_dedup``: the dynamics network once per
+    distinct resampled ancestor; plain resampling only) or ``None``."""
     loc = c_int32(0)
     args.final_location = ctypes.pointer(loc)
     if events is not None:
@@ -744,6 +789,9 @@ def pf_forward_loop(args: MmfPfLoopArgs, like: torch.Tensor, events=None, event_
             _check(load().mmf_pf_forward_loop_adaptive(ctypes.byref(args), float(ess_threshold),
                                                        ptr(resampled_steps, dtype=torch.int32), stream_of(like)),
                    "mmf_pf_forward_loop_adaptive")
+        elif dedup is not None:
+            _check(load().mmf_pf_forward_loop_dedup(ctypes.byref(args), ctypes.byref(dedup), stream_of(like)),
+                   "mmf_pf_forward_loop_dedup")
         else:
             _check(load().mmf_pf_forward_loop(ctypes.byref(args), stream_of(like)), "mmf_pf_forward_loop")
     return int(loc.value)

@@ -314,9 +314,32 @@ struct NetArgsMulti {
   NetArgs a[MMF_LOOP_MAX_MEAS];
 };
 
-template <int D, int NRES, int KIND, int CT, int PREC, int WPS, bool PIPE = false>
-__global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(NetArgsMulti multi) {
+// RUNS (dynamics only): the launch that follows a run-table K1 (pf_resample_systematic.inc).  Systematic resampling leaves
+// every surviving particle as a RUN of consecutive output slots; the network's output is a pure function of the particle's
+// state and its trajectory's control, and a particle is a column that mixes with no other, so all copies of an ancestor
+// would produce the same head outputs bit for bit.  The network therefore runs ONCE per run: a tile is 32 CT runs of one
+// trajectory, column c reads the row of run_anc[traj][32 CT q + c] in the buffer the previous step propagated, and the
+// epilogue expands -- each lane holds the noise-free half of its run's update (dynamics_drift), the wave walks the tile's
+// contiguous output slots run_start[first run] .. run_start[last run + 1] 64 at a time, fetches the slot's run's values
+// from the owning lane (ds_bpermute) and adds the slot's OWN noise (dynamics_diffuse: the same chain as everywhere).
+// The tile index space stays N x M / (32 CT), ordered q-major (tile = q' N + traj, q = (q' + traj) mod M / (32 CT): the
+// per-workgroup index lists of tile_of() are strided by a multiple of M / (32 CT), a trajectory-major order would leave whole
+// workgroups with empty tiles only); a tile with 32 CT q >= n_runs[traj] is skipped right after its claim, before any load of its inputs.
+struct RunTable {
+  const int32_t* rank;       // (N, M) run index of every output slot
+  const int32_t* run_anc;    // (N, M + 1) ancestor (row of states_in inside the trajectory) of every run
+  const int32_t* run_start;  // (N, M + 1) first slot of every run, run_start[n_runs] = M
+  const int32_t* n_runs;     // (N)
+};
+struct NetArgsRuns {
+  NetArgs a[1];
+  RunTable rt;
+};
+
+template <int D, int NRES, int KIND, int CT, int PREC, int WPS, bool PIPE = false, bool RUNS = false>
+__global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(std::conditional_t<RUNS, NetArgsRuns, NetArgsMulti> multi) {
   const NetArgs a = multi.a[blockIdx.y];
+  static_assert(!RUNS || KIND == kDynamics, "only the dynamics launch consumes a run table");
   K2_WG_STAMP(0);
   static_assert(!PIPE || (CT == 2 && PREC == MMF_PREC_F16X3 && KIND != kJacobian), "pipelined halves: f16x3, 64-particle tiles");
   constexpr int kThreads = WPS * 256;           // WPS waves per SIMD, one workgroup per CU (LDS)
@@ -366,8 +389,25 @@ __global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(NetArgsMul
   // column) are requested one tile ahead: a tile opens with a dependent HBM access otherwise
   // (~1-2 k cycles with nothing else to issue), 8 times per wave at the headline size.
   constexpr int KS0 = (D + 2) / 2;
+  // RUNS: tile = q N + traj; its columns are runs TILE q .. TILE q + TILE - 1 of the trajectory (wave-uniform bookkeeping)
+  const int n_traj = RUNS ? a.R / a.M : 1;
+  auto runs_of = [&](int tile, int& q, int& traj) {  // -> n_runs of the tile's trajectory, clamped to what a table can hold
+    q = tile / n_traj;
+    traj = tile - q * n_traj;
+    // ... rotated by the trajectory: a workgroup's index list visits a handful of consecutive trajectories at q's that are
+    // a fixed stride apart, so without the rotation its share of non-empty tiles depends on where that stride falls
+    // (5 of 8 rounds against 4 of 8 at 256 x 4096 with 35 real tiles per trajectory); with it the trajectories of a
+    // workgroup cover every residue.  A bijection per trajectory: every (traj, q) is still visited exactly once.
+    q = (q + traj) % (a.M / TILE);
+    int nr = 0;
+    if constexpr (RUNS) nr = multi.rt.n_runs[traj];
+    nr = nr < 1 ? 1 : (nr > a.M ? a.M : nr);
+    return nr;
+  };
   auto first_layer_inputs = [&](int tile, float (&b)[KS0][CT]) {
     const int base = tile * TILE;
+    int run_q = 0, run_traj = 0, run_n = 0;
+    if constexpr (RUNS) run_n = runs_of(tile, run_q, run_traj);
 #pragma unroll
     for (int s = 0; s < KS0; ++s) {
       const int comp = 2 * s + h;
@@ -375,6 +415,13 @@ __global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(NetArgsMul
       for (int c = 0; c < CT; ++c) {
         int row = base + 32 * c + j;
         row = row < a.R ? row : a.R - 1;
+        if constexpr (RUNS) {  // columns past the trajectory's last run repeat it (and are not expanded)
+          int run = run_q * TILE + 32 * c + j;
+          run = run < run_n ? run : run_n - 1;
+          int anc = multi.rt.run_anc[static_cast<size_t>(run_traj) * (a.M + 1) + run];
+          anc = anc < 0 ? 0 : (anc < a.M ? anc : a.M - 1);
+          row = run_traj * a.M + anc;
+        }
         float v;
         if (JAC) {
           const int role = row & 3;
@@ -388,7 +435,22 @@ __global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(NetArgsMul
     }
   };
   float bnext[KS0][CT];
-  if (wave_global < ntiles) first_layer_inputs(wave_global, bnext);
+  // RUNS: is there anything in this tile?  (one scalar load)
+  auto tile_real = [&](int tile) {
+    int q, traj;
+    const int nr = runs_of(tile, q, traj);
+    return q * TILE < nr;
+  };
+  bool first_pending = false;  // RUNS, wave-uniform: the wave's first tile is empty -- it looks for a real one once claims work
+  if constexpr (RUNS) {
+    const int t0 = __builtin_amdgcn_readfirstlane(wave_global);  // (the wave id is uniform, but not provably so)
+    if (t0 < ntiles) {
+      if (tile_real(t0)) first_layer_inputs(t0, bnext);
+      else first_pending = true;
+    }
+  } else {
+    if (wave_global < ntiles) first_layer_inputs(wave_global, bnext);
+  }
   bool layers_pending = false;  // wave-uniform: layers 2 .. of the weights are still on their way
   __shared__ int s_next_index;  // the tile claims' counter (below)
   if constexpr (ASYNC_STAGE) {
@@ -451,10 +513,30 @@ __global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(NetArgsMul
     return __builtin_amdgcn_readfirstlane(v);
   };
   int i_next = (threadIdx.x >> 6) + kWavesPerBlock;  // the second round is still dealt: its inputs are requested below
+  // RUNS: claim until a tile that holds runs turns up, and request ITS inputs (the claim-one-ahead prefetch, for real tiles
+  // only: an empty tile costs its claim and one scalar load).  Returns >= ntiles when the workgroup's list is exhausted.
+  auto advance = [&]() {
+    for (;;) {
+      const int t = __builtin_amdgcn_readfirstlane(tile_of(i_next));
+      i_next = claim(i_next);
+      if (t >= ntiles) return t;
+      if (tile_real(t)) {
+        first_layer_inputs(t, bnext);
+        return t;
+      }
+    }
+  };
+  int tile_first = wave_global;
+  if constexpr (RUNS) {
+    tile_first = __builtin_amdgcn_readfirstlane(tile_first);
+    if (first_pending) tile_first = advance();
+  }
 
-  for (int tile = wave_global; tile < ntiles;) {
-    const int tile_next = tile_of(i_next);
+  for (int tile = tile_first; tile < ntiles;) {
+    int tile_next = RUNS ? 0 : tile_of(i_next);
     const int base = tile * TILE;
+    int run_q = 0, run_traj = 0, run_n = 0;  // RUNS
+    if constexpr (RUNS) run_n = runs_of(tile, run_q, run_traj);
     // column -> row / trajectory bookkeeping for the CT columns this lane feeds
     int col_row[CT], col_traj[CT];
     bool col_primal[CT];
@@ -463,7 +545,7 @@ __global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(NetArgsMul
       int row = base + 32 * c + j;
       row = row < a.R ? row : a.R - 1;
       col_row[c] = row;
-      col_traj[c] = JAC ? (row >> 2) : (row / a.M);
+      col_traj[c] = RUNS ? run_traj : JAC ? (row >> 2) : (row / a.M);
       col_primal[c] = JAC ? ((row & 3) == 0) : true;
     }
     const bool primal = col_primal[0];  // same for every c: 32 is a multiple of 4
@@ -475,8 +557,12 @@ __global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(NetArgsMul
     for (int s = 0; s < KS0; ++s)
 #pragma unroll
       for (int c = 0; c < CT; ++c) bcur[s][c] = bnext[s][c];
-    if (tile_next < ntiles) first_layer_inputs(tile_next, bnext);
-    i_next = claim(i_next);
+    if constexpr (RUNS) {
+      tile_next = advance();
+    } else {
+      if (tile_next < ntiles) first_layer_inputs(tile_next, bnext);
+      i_next = claim(i_next);
+    }
     first_layer<CT>(lds, bcur, X, lane);
     short2v amax = {0, 0};  // f16x3: largest hi halves handed to the MFMAs in this tile
     if constexpr (F16) seed_nonfinite<CT>(bcur, amax);
@@ -594,6 +680,43 @@ __global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(NetArgsMul
         }
         a.loglik[my_row] = ll;
       }
+    } else if constexpr (KIND == kDynamics && RUNS) {
+      // the lane's run: its ancestor's row, the noise-free half of the update; lanes past the last run repeat it
+      const size_t tab = static_cast<size_t>(run_traj) * (a.M + 1);
+      const int r0 = run_q * TILE;
+      const int r1 = r0 + TILE < run_n ? r0 + TILE : run_n;
+      int my_run = r0 + (CT == 2 ? lane : j);
+      my_run = my_run < run_n ? my_run : run_n - 1;
+      int anc = multi.rt.run_anc[tab + my_run];
+      anc = anc < 0 ? 0 : (anc < a.M ? anc : a.M - 1);
+      float xo[D], v0[D];
+#pragma unroll
+      for (int i = 0; i < D; ++i) xo[i] = a.states_in[(static_cast<size_t>(run_traj) * a.M + anc) * D + i];
+      dynamics_drift<D, PREC>(mine, bh, xo, v0);
+      // the tile's output slots are contiguous: 64 per pass, every lane takes part in the exchange
+      int s0 = multi.rt.run_start[tab + r0], s1 = multi.rt.run_start[tab + r1];
+      s0 = s0 < 0 ? 0 : s0;
+      s1 = s1 > a.M ? a.M : s1;
+      const bool noisy = a.noise != nullptr || a.noise_mode == 2;
+      for (int kb = s0; kb < s1; kb += MMF_WAVE) {
+        const int k = kb + lane;
+        const bool live = k < s1;
+        const int kk = live ? k : s1 - 1;
+        const size_t slot = static_cast<size_t>(run_traj) * a.M + kk;
+        const int src = multi.rt.rank[slot] - r0;  // the lane that owns the slot's run
+        float v[D], eps[D], xn[D];
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+          v[i] = __shfl(v0[i], src);
+          eps[i] = (a.noise_mode != 2 && a.noise) ? a.noise[slot * D + i] : 0.f;
+        }
+        dynamics_diffuse<D>(v, eps, a.scale_tril, noisy, a.noise_mode == 2, a.noise_seed, a.noise_step,
+                            a.noise_traj0 + static_cast<unsigned>(run_traj), static_cast<unsigned>(kk), xn);
+        if (live) {
+#pragma unroll
+          for (int i = 0; i < D; ++i) a.states_out[slot * D + i] = xn[i];
+        }
+      }
     } else if constexpr (KIND == kDynamics) {
       if (active) {
         float xo[D], eps[D], xn[D];
@@ -690,6 +813,60 @@ int launch_ct(const NetArgsMulti& m, int count, hipStream_t s) {
   return launch_variant<D, NRES, KIND, PREC, 1, 2>(m, count, s);
 }
 
+// the run-consuming dynamics launch: the tile organisation launch_ct picks for the same N x M (so the columns go through the
+// same code as in the launch it replaces), one problem per launch
+template <int D, int PREC, int CT, bool PIPE>
+int launch_runs_variant(const NetArgsRuns& m, hipStream_t s) {
+  constexpr int NRES = 3, WPS = 2;
+  const size_t lds = static_cast<size_t>(blob_floats(NRES)) * sizeof(float);
+  constexpr int waves = WPS * 4, tile = 32 * CT;
+  const int ntiles = m.a[0].R / tile;  // M is a multiple of 64
+  int grid = (ntiles + waves - 1) / waves;
+  if (grid > 256) grid = 256;
+  if (grid < 1) grid = 1;
+  auto k = particle_net_kernel<D, NRES, kDynamics, CT, PREC, WPS, PIPE, true>;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+  if (e != hipSuccess) return static_cast<int>(e);
+  k<<<dim3(grid, 1), WPS * 256, lds, s>>>(m);
+  MMF_CHECK_LAUNCH();
+  return 0;
+}
+
+template <int D>
+int launch_runs(const NetArgsRuns& m, int precision, hipStream_t s) {
+  const bool big = m.a[0].R >= 256 * 8 * 64;  // as launch_ct
+  if (precision == MMF_PREC_F16X3) {
+    if (big) return launch_runs_variant<D, MMF_PREC_F16X3, 2, true>(m, s);
+    return launch_runs_variant<D, MMF_PREC_F16X3, 1, false>(m, s);
+  }
+  if (precision == MMF_PREC_F32) {
+    if (big) return launch_runs_variant<D, MMF_PREC_F32, 2, false>(m, s);
+    return launch_runs_variant<D, MMF_PREC_F32, 1, false>(m, s);
+  }
+  return MMF_EINVAL;
+}
+
+int dynamics_runs(const float* packed, int n_res, int precision, const float* states_prev, const float* traj_bias,
+                  const float* noise, const float* scale_tril, const int32_t* rank, const int32_t* run_anc,
+                  const int32_t* run_start, const int32_t* n_runs, float* states_out, int* range_flag, int N, int M, int d,
+                  unsigned long long seed, unsigned step, unsigned traj0, int noise_mode, void* stream) {
+  if (!packed || !states_prev || !traj_bias || !states_out || !rank || !run_anc || !run_start || !n_runs) return MMF_EINVAL;
+  if (states_out == states_prev || ((noise || noise_mode == 2) && !scale_tril)) return MMF_EINVAL;
+  if (N < 0 || M < 1 || M % 64 != 0 || n_res != 3) return MMF_EINVAL;
+  if (static_cast<long long>(N) * M > 0x7fffffffLL / 8) return MMF_ETOOLARGE;
+  if (N == 0) return 0;
+  NetArgsRuns m{};
+  NetArgs& a = m.a[0];
+  a.packed = packed; a.states_in = states_prev; a.traj_bias = traj_bias; a.noise = noise;
+  a.scale_tril = scale_tril; a.states_out = states_out; a.R = N * M; a.M = M;
+  a.range_flag = range_flag;
+  a.noise_seed = seed; a.noise_step = step; a.noise_traj0 = traj0; a.noise_mode = noise_mode;
+  m.rt = RunTable{rank, run_anc, run_start, n_runs};
+  if (d == 2) return launch_runs<2>(m, precision, static_cast<hipStream_t>(stream));
+  if (d == 3) return launch_runs<3>(m, precision, static_cast<hipStream_t>(stream));
+  return MMF_EINVAL;
+}
+
 template <int KIND>
 int launch_multi(const NetArgsMulti& m, int count, int d, int n_res, int precision, hipStream_t s);
 
@@ -778,6 +955,24 @@ extern "C" int mmf_pf_dynamics_philox(const float* packed, int n_res, int precis
   a.range_flag = range_flag;
   a.noise_seed = seed; a.noise_step = step; a.noise_traj0 = traj0; a.noise_mode = 2;
   return launch<kDynamics>(a, d, n_res, precision, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int mmf_pf_dynamics_runs(const float* packed, int n_res, int precision, const float* states_prev,
+                                    const float* traj_bias, const float* noise, const float* scale_tril, const int32_t* rank,
+                                    const int32_t* run_anc, const int32_t* run_start, const int32_t* n_runs,
+                                    float* states_out, int* range_flag, int N, int M, int d, void* stream) {
+  return dynamics_runs(packed, n_res, precision, states_prev, traj_bias, noise, scale_tril, rank, run_anc, run_start, n_runs,
+                       states_out, range_flag, N, M, d, 0ull, 0u, 0u, 0, stream);
+}
+
+extern "C" int mmf_pf_dynamics_runs_philox(const float* packed, int n_res, int precision, const float* states_prev,
+                                           const float* traj_bias, unsigned long long seed, unsigned step, unsigned traj0,
+                                           const float* scale_tril, const int32_t* rank, const int32_t* run_anc,
+                                           const int32_t* run_start, const int32_t* n_runs, float* states_out,
+                                           int* range_flag, int N, int M, int d, void* stream) {
+  if (!scale_tril) return MMF_EINVAL;
+  return dynamics_runs(packed, n_res, precision, states_prev, traj_bias, nullptr, scale_tril, rank, run_anc, run_start, n_runs,
+                       states_out, range_flag, N, M, d, seed, step, traj0, 2, stream);
 }
 
 namespace {

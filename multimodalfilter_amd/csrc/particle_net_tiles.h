@@ -586,19 +586,27 @@ __device__ __forceinline__ void head(const float* __restrict__ lds, const Act<CT
   }
 }
 
-// Dynamics epilogue of one particle: x' = x + (dir + b) sigmoid(gate + b) + scale_tril eps.  mine: the head's D
-// directions and gate, bh: the head's bias, eps: the caller's noise row, replaced by the counter-based draw for
-// (seed, step, traj, particle) when `philox`; tril: D x D, row-major (a pointer or a register array).
-template <int D, int PREC, class Tril>
-__device__ __forceinline__ void dynamics_update(const float (&mine)[D + 1], const float* __restrict__ bh, const float (&x)[D],
-                                                float (&eps)[D], const Tril& tril, bool noisy, bool philox,
-                                                unsigned long long seed, unsigned step, unsigned traj, unsigned particle,
-                                                float (&xn)[D]) {
+// Dynamics epilogue of one particle: x' = x + (dir + b) sigmoid(gate + b) + scale_tril eps, in two halves.
+// dynamics_drift: the noise-free part v0 = x + (dir + b) sigmoid(gate + b) -- a pure function of the particle's state and its
+// trajectory's control, so every copy of a resampled ancestor shares it (the run-consuming kernel evaluates it once per run).
+// mine: the head's D directions and gate, bh: the head's bias.
+template <int D, int PREC>
+__device__ __forceinline__ void dynamics_drift(const float (&mine)[D + 1], const float* __restrict__ bh, const float (&x)[D],
+                                               float (&v0)[D]) {
   const float gate = mine[D] + bh[D];
   float sg;
   // exact-fp32 mode = the bit-reproducible mode: shared deterministic sigmoid (mmf_detmath.h)
   if constexpr (PREC == MMF_PREC_F32) sg = mmf_det_sigmoid(gate);
   else sg = 1.0f / (1.0f + expf(-gate));
+#pragma unroll
+  for (int i = 0; i < D; ++i) v0[i] = __builtin_fmaf(mine[i] + bh[i], sg, x[i]);
+}
+// dynamics_diffuse: the noise chain on top of it, xn = v0 + scale_tril eps.  eps: the caller's noise row, replaced by the
+// counter-based draw for (seed, step, traj, particle) when `philox`; tril: D x D, row-major (a pointer or a register array).
+template <int D, class Tril>
+__device__ __forceinline__ void dynamics_diffuse(const float (&v0)[D], float (&eps)[D], const Tril& tril, bool noisy, bool philox,
+                                                 unsigned long long seed, unsigned step, unsigned traj, unsigned particle,
+                                                 float (&xn)[D]) {
   if (philox) {
     // counter-based noise: a pure function of (seed, step, trajectory, particle) -- nothing is read
     float z[4];
@@ -608,13 +616,23 @@ __device__ __forceinline__ void dynamics_update(const float (&mine)[D + 1], cons
   }
 #pragma unroll
   for (int i = 0; i < D; ++i) {
-    float v = __builtin_fmaf(mine[i] + bh[i], sg, x[i]);
+    float v = v0[i];
     if (noisy) {
 #pragma unroll
       for (int k = 0; k < D; ++k) v = __builtin_fmaf(tril[i * D + k], eps[k], v);
     }
     xn[i] = v;
   }
+}
+// both halves: what every kernel that propagates one particle per column calls
+template <int D, int PREC, class Tril>
+__device__ __forceinline__ void dynamics_update(const float (&mine)[D + 1], const float* __restrict__ bh, const float (&x)[D],
+                                                float (&eps)[D], const Tril& tril, bool noisy, bool philox,
+                                                unsigned long long seed, unsigned step, unsigned traj, unsigned particle,
+                                                float (&xn)[D]) {
+  float v0[D];
+  dynamics_drift<D, PREC>(mine, bh, x, v0);
+  dynamics_diffuse<D>(v0, eps, tril, noisy, philox, seed, step, traj, particle, xn);
 }
 
 // Jacobian epilogue of one column of a group {primal, e_1 .. e_3} (role = column & 3): the lane's own D values --

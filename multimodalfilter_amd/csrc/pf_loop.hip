@@ -9,8 +9,13 @@
 #include "mmf_common.h"
 
 // ess_threshold > 0: ESS-triggered resampling (mmf_pf_forward_loop_adaptive), resampled_steps (T, N) or null
+// ws (mmf_pf_forward_loop_dedup): the run-table workspace, or null.  With it, plain systematic resampling (mmf_pf_dedup_plan)
+// runs the dynamics network once per DISTINCT resampled ancestor: K1 of steps 0 .. T-2 writes the run table instead of
+// gathering (mmf_pf_resample_runs), the dynamics launch of steps 1 .. T-1 consumes it (mmf_pf_dynamics_runs) reading the
+// ancestors' rows from the buffer the previous step propagated; step 0's dynamics (the incoming belief is a full particle
+// set) and step T-1's K1 (the belief the caller sees is complete) are the kernels of every other loop.  Same bits.
 static int pf_enqueue_steps(const MmfPfLoopArgs* a, void* stream, bool with_events, float ess_threshold = 0.f,
-                            int32_t* resampled_steps = nullptr) {
+                            int32_t* resampled_steps = nullptr, const MmfPfDedupWorkspace* ws = nullptr) {
   if (!a) return MMF_EINVAL;
   const bool adaptive = ess_threshold > 0.f;
   if (a->T < 0 || a->N < 1 || a->M < 1 || a->n_meas < 1 || a->n_meas > MMF_LOOP_MAX_MEAS) return MMF_EINVAL;
@@ -21,6 +26,9 @@ static int pf_enqueue_steps(const MmfPfLoopArgs* a, void* stream, bool with_even
   if (a->resample_mode != 0 && !a->uniforms) return MMF_EINVAL;
   const bool soft = a->resample_mode != 0 && a->soft_alpha > 0.f && a->soft_alpha < 1.f;
   if (a->estimate_argmax && !a->estimate_scratch) return MMF_EINVAL;
+  const bool runs = ws && ws->rank && ws->run_anc && ws->run_start && ws->n_runs && !adaptive &&
+                    mmf_pf_dedup_plan(a->M, a->d, a->resample_mode, a->soft_alpha,
+                                      a->cov_steps || a->ess_steps || a->log_evidence_steps) == 1;
   const size_t row = static_cast<size_t>(a->N);
   const size_t nm = row * a->M;
   float* cur = a->states_a;   // belief on entry
@@ -42,7 +50,18 @@ static int pf_enqueue_steps(const MmfPfLoopArgs* a, void* stream, bool with_even
     int rc;
     sampled = a->events && t % stride == stride / 2;  // the middle step of every stride-long window
     if ((rc = mark())) return rc;
-    if (a->noise_mode == 2)
+    const bool runs_in = runs && t > 0;            // the previous step left a run table and its propagated rows in `cur`
+    const bool runs_out = runs && t + 1 < a->T;    // this step leaves them for the next
+    if (runs_in && a->noise_mode == 2)
+      rc = mmf_pf_dynamics_runs_philox(a->dyn_packed, a->n_res_dyn, a->precision, cur, a->dyn_bias + t * row * MMF_UNITS,
+                                       a->noise_seed, a->noise_step0 + static_cast<unsigned>(t), a->noise_traj0, a->scale_tril,
+                                       ws->rank, ws->run_anc, ws->run_start, ws->n_runs, other, a->range_flag, a->N, a->M,
+                                       a->d, stream);
+    else if (runs_in)
+      rc = mmf_pf_dynamics_runs(a->dyn_packed, a->n_res_dyn, a->precision, cur, a->dyn_bias + t * row * MMF_UNITS,
+                                a->noise + t * nm * a->d, a->scale_tril, ws->rank, ws->run_anc, ws->run_start, ws->n_runs,
+                                other, a->range_flag, a->N, a->M, a->d, stream);
+    else if (a->noise_mode == 2)
       rc = mmf_pf_dynamics_philox(a->dyn_packed, a->n_res_dyn, a->precision, cur, a->dyn_bias + t * row * MMF_UNITS,
                                   a->noise_seed, a->noise_step0 + static_cast<unsigned>(t), a->noise_traj0, a->scale_tril,
                                   other, a->range_flag, a->N, a->M, a->d, stream);
@@ -98,6 +117,13 @@ static int pf_enqueue_steps(const MmfPfLoopArgs* a, void* stream, bool with_even
                                            a->M, a->M, a->d, 0, 1.0f, cov, ess, lev, stream);
       if (rc) return rc;
       float* s = cur; cur = other; other = s;  // propagated particles are the new belief
+    } else if (runs_out) {
+      // the run table instead of the gathered particles: the propagated rows stay where they are and become `cur`
+      // (the incoming weights are uniform from the second step on and no step but the last writes them: see below)
+      rc = mmf_pf_resample_runs(ll, t == 0 ? lw_cur : nullptr, other, a->uniforms + t * row, est, nullptr, anc, ws->rank,
+                                ws->run_anc, ws->run_start, ws->n_runs, a->N, a->M, a->d, cov, ess, lev, stream);
+      if (rc) return rc;
+      float* s = cur; cur = other; other = s;
     } else {
       const float* u = a->uniforms + t * (a->resample_mode == 1 ? row : nm);
       // every step of this loop resamples, so from the second step on the incoming weights are the
@@ -130,6 +156,18 @@ extern "C" int mmf_pf_forward_loop(const MmfPfLoopArgs* a, void* stream) {
     a = &launches;
   }
   return pf_enqueue_steps(a, stream, true);
+}
+
+extern "C" int mmf_pf_forward_loop_dedup(const MmfPfLoopArgs* a, const MmfPfDedupWorkspace* ws, void* stream) {
+  MmfPfLoopArgs launches;
+  if (a && a->persistent) {  // the persistent launch is what it was; only its fallback to launches takes the workspace
+    const int rc = mmf_internal_pf_persistent(a, stream);
+    if (rc != MMF_INTERNAL_NOT_RESIDENT) return rc;
+    launches = *a;
+    launches.persistent = 0;
+    a = &launches;
+  }
+  return pf_enqueue_steps(a, stream, true, 0.f, nullptr, ws);
 }
 
 extern "C" int mmf_pf_forward_loop_adaptive(const MmfPfLoopArgs* a, float ess_threshold, int32_t* resampled_steps, void* stream) {

@@ -507,7 +507,94 @@ __global__ __launch_bounds__(kBlock) void pf_resample_systematic_kernel(
   mmf::resample_systematic_trajectory<D, STAGE, false, false, REC, ADAPT>(smem, a, M, M_out, lw_uniform, log_uniform);
 }
 
+// K1 of a step whose successor is the run-consuming dynamics kernel (pf_loop.hip): the same body with RUNS -- the run table
+// instead of the gathered particles; no staging (nothing is gathered)
+struct RunTableOut { int32_t* rank; int32_t* run_anc; int32_t* run_start; int32_t* n_runs; };  // (N, M), (N, M + 1) x 2, (N)
+
+template <int D, bool REC>
+__global__ __launch_bounds__(kBlock) void pf_resample_runs_kernel(
+    const float* __restrict__ loglik, const float* __restrict__ logw_in, const float* __restrict__ states_in,
+    const float* __restrict__ u, float* __restrict__ estimate, float* logw_out, int32_t* __restrict__ indices_out,
+    RunTableOut rt, int M, float lw_uniform, BeliefOut rec) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int n = blockIdx.x;
+  mmf::K1Trajectory a{};
+  a.ll[0] = loglik + static_cast<size_t>(n) * M;
+  a.n_ll = 1;
+  a.lw = logw_in ? logw_in + static_cast<size_t>(n) * M : nullptr;
+  a.xs = states_in + static_cast<size_t>(n) * M * D;
+  a.u = u[n];
+  a.estimate = estimate + static_cast<size_t>(n) * D;
+  a.lo = logw_out ? logw_out + static_cast<size_t>(n) * M : nullptr;
+  a.io = indices_out ? indices_out + static_cast<size_t>(n) * M : nullptr;
+  a.rank = rt.rank + static_cast<size_t>(n) * M;
+  a.run_anc = rt.run_anc + static_cast<size_t>(n) * (M + 1);
+  a.run_start = rt.run_start + static_cast<size_t>(n) * (M + 1);
+  a.n_runs = rt.n_runs + n;
+  if constexpr (REC) {
+    a.cov = rec.cov ? rec.cov + static_cast<size_t>(n) * D * D : nullptr;
+    a.ess = rec.ess ? rec.ess + n : nullptr;
+    a.log_evidence = rec.log_evidence ? rec.log_evidence + n : nullptr;
+  }
+  mmf::resample_systematic_trajectory<D, false, false, false, REC, false, true>(smem, a, M, M, lw_uniform, lw_uniform);
+}
+
+// dynamic LDS of the run variant: CDF slots, scratch, marks (+ the record's rows)
+size_t runs_lds_bytes(int M, bool recording) {
+  const size_t slots = (static_cast<size_t>(M) * 8 + 15) & ~static_cast<size_t>(15);
+  const size_t sc_sz = (sizeof(Scratch) + 15) & ~static_cast<size_t>(15);
+  const size_t marks_sz = ((static_cast<size_t>(M) + 4) * 4 + 15) & ~static_cast<size_t>(15);
+  return slots + sc_sz + marks_sz + (recording ? mmf::k1_belief_lds_bytes() : 0);
+}
+
 }  // namespace
+
+extern "C" int mmf_pf_dedup_plan(int M, int d, int resample_mode, float soft_alpha, int recording) {
+  if (M < 1 || d < 1) return MMF_EINVAL;
+  const bool soft = resample_mode != 0 && soft_alpha > 0.f && soft_alpha < 1.f;
+  if (resample_mode != 1 || soft) return 0;
+  if (M % 64 != 0 || (d != 2 && d != 3)) return 0;
+  return runs_lds_bytes(M, recording != 0) <= 160 * 1024 ? 1 : 0;
+}
+
+extern "C" size_t mmf_pf_dedup_workspace_words(int N, int M) {
+  if (N < 0 || M < 1) return 0;
+  return static_cast<size_t>(N) * M + 2 * static_cast<size_t>(N) * (static_cast<size_t>(M) + 1) + static_cast<size_t>(N);
+}
+
+extern "C" int mmf_pf_resample_runs(const float* loglik, const float* logw_in, const float* states_in, const float* u,
+                                    float* estimate, float* logw_out, int32_t* indices_out, int32_t* rank, int32_t* run_anc,
+                                    int32_t* run_start, int32_t* n_runs, int N, int M, int d, float* cov, float* ess,
+                                    float* log_evidence, void* stream) {
+  if (!loglik || !states_in || !u || !estimate || !rank || !run_anc || !run_start || !n_runs) return MMF_EINVAL;
+  if (N < 0 || M < 1 || d < 1 || d > MMF_MAX_STATE_DIM) return MMF_EINVAL;
+  const bool recording = cov || ess || log_evidence;
+  const size_t bytes = runs_lds_bytes(M, recording);
+  if (M > 65536 || bytes > 160 * 1024) return MMF_ETOOLARGE;
+  if (N == 0) return 0;
+  int block = ((M + 3) / 4 + MMF_WAVE - 1) / MMF_WAVE * MMF_WAVE;
+  if (block > kBlock) block = kBlock;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const float lw_uniform = static_cast<float>(-std::log(static_cast<double>(M)));
+  const RunTableOut rt{rank, run_anc, run_start, n_runs};
+  const BeliefOut rec{cov, ess, log_evidence};
+#define MMF_K1R_LAUNCH(D, RC)                                                                                         \
+  {                                                                                                                   \
+    if (bytes > 64 * 1024) {                                                                                          \
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pf_resample_runs_kernel<D, RC>),              \
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));        \
+      if (e != hipSuccess) return static_cast<int>(e);                                                                \
+    }                                                                                                                 \
+    pf_resample_runs_kernel<D, RC><<<N, block, bytes, s>>>(loglik, logw_in, states_in, u, estimate, logw_out, indices_out, rt, \
+                                                            M, lw_uniform, rec);                                      \
+  }
+#define MMF_K1R(D) case D: { if (recording) MMF_K1R_LAUNCH(D, true) else MMF_K1R_LAUNCH(D, false) } break;
+  switch (d) { MMF_K1R(1) MMF_K1R(2) MMF_K1R(3) MMF_K1R(4) }
+#undef MMF_K1R
+#undef MMF_K1R_LAUNCH
+  MMF_CHECK_LAUNCH();
+  return 0;
+}
 
 extern "C" size_t mmf_pf_reweight_resample_lds_bytes(int M, int mode) {
   const size_t slots = (static_cast<size_t>(M) * (mode ? 8 : 4) + 15) & ~static_cast<size_t>(15);

@@ -153,13 +153,24 @@ struct K1Trajectory {  // pointers of ONE trajectory's rows
   int spin_sleep;        // COH: s_sleep between polls (0: busy polling)
   float ess_floor;       // ADAPT: fl32(ess_threshold * M); the trajectory resamples iff !(ess >= ess_floor)
   int32_t* resampled;    // ADAPT: 1 (resampled) / 0 (kept) of this trajectory, or null
+  int32_t* rank;         // RUNS: (M_out) index of the run every output slot belongs to
+  int32_t* run_anc;      // RUNS: (M_out + 1) ancestor of every run
+  int32_t* run_start;    // RUNS: (M_out + 1) first output slot of every run; run_start[n_runs] = M_out
+  int32_t* n_runs;       // RUNS: number of runs = distinct ancestors of this trajectory
 };
 
 // returns false (workgroup-uniform) when a COH reader gave up waiting for its granules
 // ADAPT: ESS-triggered resampling (include/mmf.h, K1; M_out == M): the decision follows pass 2's reductions, and a KEPT
 // trajectory leaves before the announcements, the prefix maximum and the gather -- it writes mode 0's log-weights, its rows
 // as they came and the identity ancestors.  Sum e^2 is the record's own (REC) or, without a record, the same chain alone.
-template <int D, bool STAGE, bool COH, bool DET, bool REC = false, bool ADAPT = false>
+// RUNS (launch path, plain resampling; not COH, not ADAPT, not STAGE): the RUN TABLE instead of the gathered particles.
+// The ancestor sequence is non-decreasing, so the copies of an ancestor fill consecutive output slots -- a run; slot 0
+// starts one, slot k > 0 does iff marks[k] != 0 (only particle 0 announces the value 0, and only at slot 0).  One more
+// integer block scan (an inclusive count of the run starts, the prefix maximum's wave scan + carry structure) numbers the
+// runs; per slot its run's index, per run its ancestor and first slot, per trajectory the number of runs.  No state row
+// is gathered or stored (`so` is not touched): the next dynamics launch reads the ancestors' rows from `xs` itself
+// (particle_net.hip, RUNS).  Estimates, the belief record, `io`, `lo` and every float reduction are untouched.
+template <int D, bool STAGE, bool COH, bool DET, bool REC = false, bool ADAPT = false, bool RUNS = false>
 __device__ __forceinline__ bool resample_systematic_trajectory(unsigned char* smem, const K1Trajectory& a, int M, int M_out,
                                                                float lw_uniform, float log_uniform) {
   const size_t slots_sz = (static_cast<size_t>(M) * 8 + 15) & ~static_cast<size_t>(15);
@@ -565,14 +576,23 @@ __device__ __forceinline__ bool resample_systematic_trajectory(unsigned char* sm
     if (a.stamps && tid == 0) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory"); a.stamps[2] = t_; }
   }
   // ---- ancestor(k) = the latest announcement at or before k = inclusive prefix MAX of marks; gather; store
+  static_assert(!RUNS || (!COH && !ADAPT && !STAGE), "the run table belongs to the launch path's plain resampling");
   const bool vec_out = !COH && (M_out & 3) == 0;
   unsigned carry2 = 0;
+  unsigned runs_before = 0;  // RUNS: run starts in the chunks before this one
   for (int base = 0; base < M_out; base += chunk) {
     const int k0 = base + tid * 4;
     unsigned m[4] = {0u, 0u, 0u, 0u};
     if (k0 < M_out) {
       const uint4 t = *reinterpret_cast<const uint4*>(marks + k0);  // marks is padded by 4 zero entries
       m[0] = t.x; m[1] = t.y; m[2] = t.z; m[3] = t.w;
+    }
+    unsigned starts[4] = {0u, 0u, 0u, 0u}, starts_incl = 0;  // RUNS
+    if constexpr (RUNS) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) starts[j] = (k0 + j < M_out && (k0 + j == 0 || m[j] != 0u)) ? 1u : 0u;
+      starts_incl = wave_inclusive_scan_u32(starts[0] + starts[1] + starts[2] + starts[3]);
+      if (lane == MMF_WAVE - 1) sc.wave_tot[wave] = starts_incl;  // (pass 2 is done with these rows)
     }
     m[1] = max(m[1], m[0]); m[2] = max(m[2], m[1]); m[3] = max(m[3], m[2]);
     const unsigned incl = wave_inclusive_scan_max_u32(m[3]);
@@ -588,6 +608,45 @@ __device__ __forceinline__ bool resample_systematic_trajectory(unsigned char* sm
     // everything announced before this thread's first output: previous waves / chunks and the lanes below
     const unsigned below = max(before, dpp_u32<kDppWaveShr1>(0u, incl));
     int idx[4];
+    if constexpr (RUNS) {
+      unsigned rb = runs_before, rt = 0;
+      for (int w = 0; w < nwaves; ++w) {
+        const unsigned t = static_cast<unsigned>(sc.wave_tot[w]);
+        if (w < wave) rb += t;
+        rt += t;
+      }
+      runs_before += rt;
+      // run starts at or before slot k0 + j, minus one: the run's index
+      int rk[4];
+      unsigned cnt = rb + starts_incl - (starts[0] + starts[1] + starts[2] + starts[3]);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        idx[j] = static_cast<int>(max(below, m[j]));
+        cnt += starts[j];
+        rk[j] = static_cast<int>(cnt) - 1;
+        if (starts[j]) {  // this thread owns the run's first slot
+          a.run_anc[rk[j]] = idx[j];
+          a.run_start[rk[j]] = k0 + j;
+        }
+      }
+      if (vec_out && k0 + 3 < M_out) {
+        *reinterpret_cast<int4*>(a.rank + k0) = make_int4(rk[0], rk[1], rk[2], rk[3]);
+        if (lo) *reinterpret_cast<float4*>(lo + k0) = make_float4(log_uniform, log_uniform, log_uniform, log_uniform);
+        if (io) *reinterpret_cast<int4*>(io + k0) = make_int4(idx[0], idx[1], idx[2], idx[3]);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int k = k0 + j;
+          if (k < M_out) {
+            a.rank[k] = rk[j];
+            if (lo) lo[k] = log_uniform;
+            if (io) io[k] = idx[j];
+          }
+        }
+      }
+      if (base + chunk < M_out) __syncthreads();  // wave_cnt / wave_tot are reused by the next chunk
+      continue;
+    }
     float g[4 * D];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -621,6 +680,12 @@ __device__ __forceinline__ bool resample_systematic_trajectory(unsigned char* sm
       }
     }
     if (base + chunk < M_out) __syncthreads();  // wave_cnt is reused by the next chunk
+  }
+  if constexpr (RUNS) {
+    if (tid == 0) {  // every thread has added every chunk's count
+      *a.n_runs = static_cast<int>(runs_before);
+      a.run_start[runs_before] = M_out;
+    }
   }
   K1_STAMP(3);
   return true;

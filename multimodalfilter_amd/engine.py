@@ -25,7 +25,10 @@ def particle_net_macs(d_in: int, n_res: int, n_out: int) -> int:
 
 class KernelTimer:
     """HIP-event timing of individual kernel launches on the launching stream (used by
-    ``bench.py`` for the roofline figure; off by default, no cost when off)."""
+    ``bench.py`` for the roofline figure; off by default, no cost when off).
+    The particle filter's dynamics launch is always recorded with its ALGORITHMIC work, 2 R MAC FLOPs for R = N M particles:
+    with ``PF_DEDUP`` the network runs on the distinct resampled ancestors only, so that record's FLOP/s is a rate of
+    particles served, not of the matrix pipe (only the measurement kernel's roofline is reported)."""
 
     def __init__(self, prealloc: int = 512, loop_stride: int = 1):
         self.records = {}
@@ -153,6 +156,10 @@ def training_image_precision_code() -> int:
 # launch per forward_loop: role-specialised workgroups keep one network's weights in LDS for all T steps and hand the
 # particles over through L2 (csrc/pf_persistent.inc); bit-identical to the launch-per-step loop.  "0": A/B, off.
 PF_PERSISTENT = os.environ.get("MMF_PF_PERSISTENT", "1") not in ("", "0")
+# The launch-per-step particle-filter loop with plain systematic resampling runs the dynamics network once per DISTINCT
+# resampled ancestor (mmf_pf_forward_loop_dedup, include/mmf.h: K1 writes a run table instead of gathering, the next dynamics
+# launch expands every run into its slots with the slots' own noise); bit-identical to mmf_pf_forward_loop.  "0": A/B, off.
+PF_DEDUP = os.environ.get("MMF_PF_DEDUP", "1") not in ("", "0")
 # The EKF step loop likewise (mmf_ekf_persistent_plan > 0; csrc/ekf_persistent.inc): a wave owns 8 trajectories of one
 # sub-filter for all T steps, K > 1 sub-filters meet once per step through L2; bit-identical to the 2 T launches.
 EKF_PERSISTENT = os.environ.get("MMF_EKF_PERSISTENT", "1") not in ("", "0")

@@ -24,6 +24,20 @@ from .utils import CounterBlock, NoiseSource, tree_index, tree_leading_shape, tr
 _MODES = {"none": 0, "systematic": 1, "multinomial": 2}
 
 
+def dedup_workspace_words(N: int, M: int) -> int:
+    """int32 elements of the run-table workspace (``include/mmf.h``: ``mmf_pf_dedup_workspace_words``)."""
+    return N * M + 2 * N * (M + 1) + N
+
+
+def dedup_eligible(*, T: int, M: int, d: int, mode: int, soft_alpha: float, adaptive: bool, recording: bool = False) -> bool:
+    """Whether ``forward_loop`` hands the native loop a run-table workspace: the switch, a loop long enough to have a
+    step that consumes a table (``T >= 2``), no ESS-triggered resampling, and the library's own rule
+    (``mmf_pf_dedup_plan``: plain systematic resampling, ``M % 64 == 0``, ``d`` 2 or 3, K1's run variant fits LDS)."""
+    if not engine.PF_DEDUP or adaptive or T < 2:
+        return False
+    return _abi.pf_dedup_plan(M, d, mode, soft_alpha, recording)
+
+
 class ParticleFilter(base.Filter):
     """Bootstrap particle filter (T1).
 
@@ -87,6 +101,7 @@ class ParticleFilter(base.Filter):
         self.particle_states: torch.Tensor = None
         self.particle_log_weights: torch.Tensor = None
         self._spare_states = None
+        self._dedup_words = None      # int32 run-table workspace of the native loop (engine.PF_DEDUP)
         self._initialized = False
 
     @property
@@ -140,6 +155,8 @@ class ParticleFilter(base.Filter):
         # 8 steps' worth of particle buffers: initialize_beliefs() builds the new belief while the
         # previous run's belief and scratch are still alive (measured: 4x left the first loop at
         # a new length one 12 MB segment short = one stream-draining hipMalloc)
+        # the run table of the native loop (engine.PF_DEDUP): rank (N, M), run_anc / run_start (N, M + 1), n_runs (N), int32
+        per_step += 4 * dedup_workspace_words(batch, M)
         nbytes = steps * batch * per_row + 8 * per_step + (64 << 20)
         reserve_memory(dev, nbytes)
         return nbytes
@@ -430,6 +447,15 @@ class ParticleFilter(base.Filter):
             est_scratch = torch.empty((N, d), dtype=torch.float32, device=dev)
             keep.append(est_scratch)
             a.estimate_argmax, a.estimate_scratch = 1, P(est_scratch)
+        # plain systematic resampling: the dynamics network once per distinct resampled ancestor (mmf_pf_forward_loop_dedup);
+        # the C side takes the same decision from the same arguments and otherwise IS mmf_pf_forward_loop
+        dedup = None
+        if dedup_eligible(T=T, M=M, d=d, mode=mode, soft_alpha=float(a.soft_alpha), adaptive=thr is not None,
+                          recording=self.record_belief):
+            words = dedup_workspace_words(N, M)
+            if self._dedup_words is None or self._dedup_words.numel() != words or self._dedup_words.device != dev:
+                self._dedup_words = torch.empty(words, dtype=torch.int32, device=dev)
+            dedup = _abi.pf_dedup_workspace(self._dedup_words, N, M)
         timer = engine.kernel_timer()
         # small problem: ONE launch for all T steps (csrc/pf_persistent.inc); same bits as the loop of launches
         # (ESS-triggered resampling does not change eligibility: the K1 role takes the adaptive branch)
@@ -446,7 +472,7 @@ class ParticleFilter(base.Filter):
         # the persistent launch needs ALL its workgroups resident; if it gives up (another process on this GPU) the belief
         # is restored and the loop re-run as launches, for this call and for the rest of the process (engine.run_persistent)
         loc = engine.run_persistent(a, lambda: _abi.pf_forward_loop(a, like, events, stride, ess_threshold=thr,
-                                                                    resampled_steps=took), device=dev,
+                                                                    resampled_steps=took, dedup=dedup), device=dev,
                                     n_sync_words=_abi.pf_persistent_sync_words(N, M, d, len(nets)) if go else 0,
                                     restore=(states_a, logw_a))
         if timer is not None:
