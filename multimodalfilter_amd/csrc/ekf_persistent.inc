@@ -282,15 +282,8 @@ template <int D, int PREC>
 int launch_ekf_persistent(const EkfPersistArgs& pa, int blocks, hipStream_t s) {
   auto kfn = ekf_persistent_loop_kernel<D, PREC>;
   const size_t lds = static_cast<size_t>(blob_floats(3)) * sizeof(float);
-  int per_cu = 0, dev = 0, cus = 0;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kfn), kEkfPersistThreads, lds) != hipSuccess ||
-      hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    return MMF_EINVAL;
-  if (per_cu < 1 || blocks > per_cu * cus) return MMF_INTERNAL_NOT_RESIDENT;
-  kfn<<<dim3(pa.G, pa.K), kEkfPersistThreads, lds, s>>>(pa);
-  MMF_CHECK_LAUNCH();
-  return 0;
+  if (const int rc = mmf::resident(kfn, blocks, kEkfPersistThreads, lds)) return rc;
+  return mmf::launch(kfn, dim3(pa.G, pa.K), kEkfPersistThreads, lds, s, pa);
 }
 
 }  // namespace

@@ -22,6 +22,7 @@
 #include <hip/hip_fp16.h>
 
 #include "mmf_common.h"
+#include "mmf_launch.h"
 
 namespace {
 
@@ -555,16 +556,8 @@ template <int CIN, int COUT, int KS, bool RELU, bool SKIP, bool MASK = false>
 int launch_conv(const ConvArgs& a, int nets, hipStream_t s) {
   constexpr int RB = kBand + 2 * (KS / 2);
   constexpr size_t lds = (static_cast<size_t>(CIN) * RB * kWP + mtiles(COUT) * ksteps(CIN, KS) * 64) * sizeof(float);
-  static_assert(lds <= 160 * 1024, "conv tile + weights must fit LDS");
-  auto k = conv_kernel<CIN, COUT, KS, RELU, SKIP, MASK>;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-    if (e != hipSuccess) return static_cast<int>(e);
-  }
-  k<<<dim3(2 * a.N, nets), kConvThreads, lds, s>>>(a);
-  MMF_CHECK_LAUNCH();
-  return 0;
+  static_assert(lds <= mmf::kLdsPerCu, "conv tile + weights must fit LDS");
+  return mmf::launch(conv_kernel<CIN, COUT, KS, RELU, SKIP, MASK>, dim3(2 * a.N, nets), kConvThreads, lds, s, a);
 }
 
 
@@ -647,7 +640,7 @@ __global__ void pack_convs_backward_kernel(MmfImageEncoderDesc d, float* __restr
 // caller.  db[co] = sum of g comes from the same A registers (`partial_b`).
 constexpr int kWgradTile = 9 * 32 * 32;
 constexpr size_t kLdsWgrad = 4 * kWgradTile * sizeof(float);
-static_assert(kLdsWgrad <= 160 * 1024, "weight-gradient reduction must fit LDS");
+static_assert(kLdsWgrad <= mmf::kLdsPerCu, "weight-gradient reduction must fit LDS");
 
 __device__ __forceinline__ void wgrad_load16(const float* __restrict__ p, bool ok, float* v) {
 #pragma unroll
@@ -1008,12 +1001,7 @@ using WgradKernel = void (*)(const float*, const float*, float*, float*, int);
 
 static int launch_wgrad(WgradKernel k, const float* g, const float* act, float* partial, float* partial_b, int N,
                         int n_blocks, hipStream_t s) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     static_cast<int>(kLdsWgrad));
-  if (e != hipSuccess) return static_cast<int>(e);
-  k<<<n_blocks, 512, kLdsWgrad, s>>>(g, act, partial, partial_b, N);
-  MMF_CHECK_LAUNCH();
-  return 0;
+  return mmf::launch(k, n_blocks, 512, kLdsWgrad, s, g, act, partial, partial_b, N);
 }
 
 // partial slots -> the layer's gradients in nn.Conv2d layout, slots in ascending order.  One thread per value of a slot,
@@ -1056,12 +1044,8 @@ extern "C" int mmf_conv_weight_grads_h(const float* g, const float* act, const f
   else if (co == 16 && ci == 32) k = conv_wgrad_h_kernel<16, 32>;
   else if (co == 8 && ci == 16) k = conv_wgrad_h_kernel<8, 16>;
   else return MMF_EINVAL;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     static_cast<int>(kLdsWgrad));
-  if (e != hipSuccess) return static_cast<int>(e);
-  k<<<n_blocks, 512, kLdsWgrad, s>>>(g, act, partial, partial_b, N, g_absmax, range_flag);
-  MMF_CHECK_LAUNCH();
-  if (!dw) return 0;
+  const int rc = mmf::launch(k, n_blocks, 512, kLdsWgrad, s, g, act, partial, partial_b, N, g_absmax, range_flag);
+  if (rc || !dw) return rc;
   conv_wgrad_finalize_kernel<<<(9216 + co + 255) / 256, 256, 0, s>>>(partial, partial_b, n_blocks, co, ci, dw, db);
   MMF_CHECK_LAUNCH();
   return 0;

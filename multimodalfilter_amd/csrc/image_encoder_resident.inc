@@ -52,7 +52,7 @@ constexpr int kResRP = 2 * kRow32;           // a ring row: hi plane row, then l
 constexpr int kResDRow16 = kWPh * 16;        // D: bytes per (plane, 8-channel chunk, row)
 constexpr int kResDSlot = 4 * kResDRow16;    // D ring slot: [hi|lo][chunk 2][34 cols][8 halves]
 constexpr size_t kLdsResident = 4 * kImgPlane + 128 + (kResA + 2 * kResR) * kResRP + kResR * kResDSlot + kResRP + 256;
-static_assert(kLdsResident <= 160 * 1024, "the resident K4 kernel must fit LDS");
+static_assert(kLdsResident <= mmf::kLdsPerCu, "the resident K4 kernel must fit LDS");
 static_assert(kResDSlot <= kResRP, "the shared zero row pair must cover a D slot");
 
 // hi / lo halves of a pair of values as they are KEPT for the skip connection: f16x3 mode = the operand split itself;
@@ -504,13 +504,8 @@ inline int launch_resident(const FusedArgs& a_in, int nets, bool bf16, hipStream
   a.ablate = getenv("MMF_K4_ABLATE") ? atoi(getenv("MMF_K4_ABLATE")) : 0;
 #endif
   auto k = bf16 ? image_encoder_resident_kernel<true> : image_encoder_resident_kernel<false>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     static_cast<int>(kLdsResident));
-  if (e != hipSuccess) return static_cast<int>(e);
   int gx = device_cus() / nets;  // persistent workgroups per network
   if (gx > a.N) gx = a.N;
   if (gx < 1) gx = 1;
-  k<<<dim3(gx, nets), kFusedThreads, kLdsResident, s>>>(a);
-  MMF_CHECK_LAUNCH();
-  return 0;
+  return mmf::launch(k, dim3(gx, nets), kFusedThreads, kLdsResident, s, a);
 }

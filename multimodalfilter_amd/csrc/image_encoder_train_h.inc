@@ -280,15 +280,10 @@ template <int CIN, bool SKIP>
 int launch_dgrad_h(const DgradHArgs& a, hipStream_t s) {
   constexpr int BAND = 8;
   constexpr size_t lds = 2 * (BAND + 2) * kWPh * CIN * 2 + 9 * (CIN / 16) * 2 * 64 * 16;
-  static_assert(2 * lds <= 160 * 1024, "two workgroups per CU");
-  auto k = conv_dgrad_h_kernel<CIN, SKIP>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-  if (e != hipSuccess) return static_cast<int>(e);
+  static_assert(lds <= mmf::kLdsHalfCu, "two workgroups per CU");
   int gx = (kImg / BAND) * a.N;
   if (gx > 2 * device_cus()) gx = 2 * device_cus();  // persistent workgroups, two per CU
-  k<<<gx, BAND * 32, lds, s>>>(a);
-  MMF_CHECK_LAUNCH();
-  return 0;
+  return mmf::launch(conv_dgrad_h_kernel<CIN, SKIP>, gx, BAND * 32, lds, s, a);
 }
 
 // largest magnitude of a tensor into a device word (zeroed by the caller): non-negative floats order like their bit patterns;

@@ -20,6 +20,7 @@
 //    launch; the granules of the previous round are there when the launch starts, so no spin waits.
 // Both run the same device function on the same operands in the same order: the same bits.
 #include "mmf_common.h"
+#include "mmf_launch.h"
 #include "mmf_granule.h"
 #include "../../include/mmf_detmath.h"
 
@@ -340,28 +341,21 @@ extern "C" int mmf_lstm_forward(const MmfLstmArgs* a, void* stream) {
   k.progress = words + 4;
   k.hx = reinterpret_cast<mmf::Granule*>(words + kSyncHeader);
   k.range_flag = a->range_flag;
-  auto kfn = lstm_rounds_kernel;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLdsBytes)) != hipSuccess)
-    return MMF_EINVAL;
   if (a->persistent) {
     const int blocks = lstm_persistent_plan(a->N);
-    int per_cu = 0, dev = 0, cus = 0;
-    if (blocks > 0 && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kfn), kThreads, kLdsBytes) == hipSuccess &&
-        hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-        per_cu >= 1 && blocks <= per_cu * cus) {
+    const int rc = blocks > 0 ? mmf::resident(lstm_rounds_kernel, blocks, kThreads, kLdsBytes) : MMF_INTERNAL_NOT_RESIDENT;
+    if (rc == 0) {
       k.round_begin = 0; k.round_end = a->T + 1; k.persistent = 1;
-      kfn<<<dim3(blocks, 1), kThreads, kLdsBytes, hs>>>(k);
-      MMF_CHECK_LAUNCH();
-      return 0;
+      return mmf::launch(lstm_rounds_kernel, dim3(blocks, 1), kThreads, kLdsBytes, hs, k);
     }
+    if (rc != MMF_INTERNAL_NOT_RESIDENT) return rc;  // a query failed
     // not eligible here: the loop of launches
   }
   const unsigned groups = static_cast<unsigned>((a->N + kCols - 1) / kCols);
   k.persistent = 0;
   for (int r = 0; r <= a->T; ++r) {
     k.round_begin = r; k.round_end = r + 1;
-    kfn<<<dim3(2 * kWgPerLayer, groups), kThreads, kLdsBytes, hs>>>(k);
-    MMF_CHECK_LAUNCH();
+    if (const int rc = mmf::launch(lstm_rounds_kernel, dim3(2 * kWgPerLayer, groups), kThreads, kLdsBytes, hs, k)) return rc;
   }
   return 0;
 }

@@ -30,6 +30,7 @@
 #include <utility>
 
 #include "mmf_common.h"
+#include "mmf_launch.h"
 #include "../../include/mmf_detmath.h"
 #include "../../include/mmf_philox.h"
 
@@ -790,12 +791,7 @@ int launch_variant(const NetArgsMulti& m, int count, hipStream_t s) {
   if (grid > 256) grid = 256;
   if (grid < 1) grid = 1;
   auto k = particle_net_kernel<D, NRES, KIND, CT, PREC, WPS, PIPE>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-  if (e != hipSuccess) return static_cast<int>(e);
-  k<<<dim3(grid, count), WPS * 256, lds, s>>>(m);
-  MMF_CHECK_LAUNCH();
-  return 0;
+  return mmf::launch(k, dim3(grid, count), WPS * 256, lds, s, m);
 }
 
 template <int D, int NRES, int KIND, int PREC>
@@ -825,11 +821,7 @@ int launch_runs_variant(const NetArgsRuns& m, hipStream_t s) {
   if (grid > 256) grid = 256;
   if (grid < 1) grid = 1;
   auto k = particle_net_kernel<D, NRES, kDynamics, CT, PREC, WPS, PIPE, true>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-  if (e != hipSuccess) return static_cast<int>(e);
-  k<<<dim3(grid, 1), WPS * 256, lds, s>>>(m);
-  MMF_CHECK_LAUNCH();
-  return 0;
+  return mmf::launch(k, dim3(grid, 1), WPS * 256, lds, s, m);
 }
 
 template <int D>

@@ -45,6 +45,7 @@
 // What still travels through HBM in the round-4 compact format: dz of the first layer and of the join layer and the
 // head's input (3 x 128 B per particle), for the narrow reductions of small_grads_h_kernel.
 
+#include "mmf_launch.h"
 #include "particle_net_train_common.h"
 
 // Phase clocks for scripts/ubench/fused_phases.hip (compiled out of the library): wave 0 of workgroup 0 accumulates
@@ -808,13 +809,9 @@ int launch_fused(const FusedArgs* nets, int n, hipStream_t s) {
   const int cap = PART == kEncFwd ? 256 : (a.slots < 256 ? a.slots : 256);
   grid = grid > cap ? cap : (grid < 1 ? 1 : grid);
   auto k = particle_net_train_fused_kernel<D, NRES, KIND, PART>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, LY::kBytes);
-  if (e != hipSuccess) return static_cast<int>(e);
   FusedArgsMulti m{};
   for (int i = 0; i < n; ++i) m.net[i] = nets[i];
-  k<<<dim3(grid, n), 256, LY::kBytes, s>>>(m);
-  MMF_CHECK_LAUNCH();
-  return 0;
+  return mmf::launch(k, dim3(grid, n), 256, LY::kBytes, s, m);
 }
 
 template <int D, int NRES, int KIND, int PART>

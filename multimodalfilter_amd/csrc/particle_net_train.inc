@@ -621,12 +621,7 @@ int launch_train_fwd(const TrainArgs& a, hipStream_t s) {
   int grid = (ntiles + wpb - 1) / wpb;
   grid = grid > 256 ? 256 : (grid < 1 ? 1 : grid);
   auto k = particle_net_train_fwd_kernel<D, NRES, KIND, QUAD, COMPACT>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     static_cast<int>(lds));
-  if (e != hipSuccess) return static_cast<int>(e);
-  k<<<grid, wpb * 64, lds, s>>>(a);
-  MMF_CHECK_LAUNCH();
-  return 0;
+  return mmf::launch(k, grid, wpb * 64, lds, s, a);
 }
 
 template <int NRES, int KIND, int NOUT, bool QUAD = false, bool COMPACT = false>
@@ -637,12 +632,7 @@ int launch_train_bwd(const TrainArgs& a, hipStream_t s) {
   int grid = (ntiles + wpb - 1) / wpb;
   grid = grid > 256 ? 256 : (grid < 1 ? 1 : grid);
   auto k = particle_net_train_bwd_kernel<NRES, KIND, NOUT, QUAD, COMPACT>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     static_cast<int>(lds));
-  if (e != hipSuccess) return static_cast<int>(e);
-  k<<<grid, wpb * 64, lds, s>>>(a);
-  MMF_CHECK_LAUNCH();
-  return 0;
+  return mmf::launch(k, grid, wpb * 64, lds, s, a);
 }
 
 }  // namespace

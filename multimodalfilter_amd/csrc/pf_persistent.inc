@@ -368,39 +368,24 @@ __global__ __launch_bounds__(kPersistThreads, 2) void pf_persistent_loop_kernel(
 }
 
 size_t persist_k1_lds_bytes(int M, int d, bool rec) {  // rec: the record's reduction rows (a recording or an adaptive loop)
-  const size_t slots = (static_cast<size_t>(M) * 8 + 15) & ~static_cast<size_t>(15);
-  const size_t sc = (sizeof(mmf::K1Scratch) + 15) & ~static_cast<size_t>(15);
-  const size_t marks = ((static_cast<size_t>(M) + 4) * 4 + 15) & ~static_cast<size_t>(15);
-  return slots + sc + marks + static_cast<size_t>(M) * d * sizeof(float) + 32 + (rec ? mmf::k1_belief_lds_bytes() : 0);
-}
-
-template <int D, int PREC, bool REC, bool ADAPT>
-int launch_persistent(const PersistArgs& pa, size_t lds, int blocks, hipStream_t s) {
-  auto k = pf_persistent_loop_kernel<D, PREC, REC, ADAPT>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-  if (e != hipSuccess) return static_cast<int>(e);
-  k<<<blocks, kPersistThreads, lds, s>>>(pa);
-  MMF_CHECK_LAUNCH();
-  return 0;
+  // + 32: this sum has always put the record's rows straight behind the UNROUNDED staged states plus 32 spare bytes, which
+  // covers the rounding to 16 the device applies in front of them.  Kept as it is: the loop's LDS request, and with it what
+  // the residency test sees, does not change.
+  return mmf::k1_systematic_lds(M, M, d, true, false).end + 32 + (rec ? mmf::k1_belief_lds_bytes() : 0);
 }
 
 // residency check and launch of the instantiation for (precision, d)
 template <bool REC, bool ADAPT>
 int persistent_dispatch(int precision, int d, const PersistArgs& pa, size_t lds, int blocks, hipStream_t hs) {
   if (precision != MMF_PREC_F32 && precision != MMF_PREC_F16X3) return MMF_EINVAL;
-  {  // the plan assumed one resident workgroup per CU: hold the launch to what the runtime says about THIS kernel
-    int per_cu = 0, dev = 0, cus = 0;
-    const void* fn = precision == MMF_PREC_F32
-                         ? (d == 3 ? reinterpret_cast<const void*>(pf_persistent_loop_kernel<3, MMF_PREC_F32, REC, ADAPT>) : reinterpret_cast<const void*>(pf_persistent_loop_kernel<2, MMF_PREC_F32, REC, ADAPT>))
-                         : (d == 3 ? reinterpret_cast<const void*>(pf_persistent_loop_kernel<3, MMF_PREC_F16X3, REC, ADAPT>) : reinterpret_cast<const void*>(pf_persistent_loop_kernel<2, MMF_PREC_F16X3, REC, ADAPT>));
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kPersistWaves * MMF_WAVE, lds) != hipSuccess ||
-        hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return MMF_EINVAL;
-    if (per_cu < 1 || blocks > per_cu * cus) return MMF_INTERNAL_NOT_RESIDENT;  // mmf_pf_forward_loop takes the launch path
-  }
-  if (precision == MMF_PREC_F32) return d == 3 ? launch_persistent<3, MMF_PREC_F32, REC, ADAPT>(pa, lds, blocks, hs) : launch_persistent<2, MMF_PREC_F32, REC, ADAPT>(pa, lds, blocks, hs);
-  return d == 3 ? launch_persistent<3, MMF_PREC_F16X3, REC, ADAPT>(pa, lds, blocks, hs) : launch_persistent<2, MMF_PREC_F16X3, REC, ADAPT>(pa, lds, blocks, hs);
+  auto run = [&](auto k) {
+    // the plan assumed one resident workgroup per CU: hold the launch to what the runtime says about THIS kernel
+    // (MMF_INTERNAL_NOT_RESIDENT: mmf_pf_forward_loop takes the launch path)
+    if (const int rc = mmf::resident(k, blocks, kPersistThreads, lds)) return rc;
+    return mmf::launch(k, blocks, kPersistThreads, lds, hs, pa);
+  };
+  if (precision == MMF_PREC_F32) return d == 3 ? run(pf_persistent_loop_kernel<3, MMF_PREC_F32, REC, ADAPT>) : run(pf_persistent_loop_kernel<2, MMF_PREC_F32, REC, ADAPT>);
+  return d == 3 ? run(pf_persistent_loop_kernel<3, MMF_PREC_F16X3, REC, ADAPT>) : run(pf_persistent_loop_kernel<2, MMF_PREC_F16X3, REC, ADAPT>);
 }
 
 }  // namespace
@@ -535,7 +520,7 @@ int mmf_internal_pf_persistent(const MmfPfLoopArgs* a, void* stream, float ess_t
   size_t lds = static_cast<size_t>(blob_floats(3)) * sizeof(float);
   const size_t k1 = persist_k1_lds_bytes(a->M, a->d, rec || adaptive);
   if (k1 > lds) lds = k1;
-  if (lds > 160 * 1024) return MMF_ETOOLARGE;
+  if (lds > mmf::kLdsPerCu) return MMF_ETOOLARGE;
   const int rc = adaptive ? (rec ? persistent_dispatch<true, true>(a->precision, a->d, pa, lds, blocks, hs)
                                  : persistent_dispatch<false, true>(a->precision, a->d, pa, lds, blocks, hs))
                           : (rec ? persistent_dispatch<true, false>(a->precision, a->d, pa, lds, blocks, hs)

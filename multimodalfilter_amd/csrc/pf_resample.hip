@@ -14,6 +14,7 @@
 #include <cmath>
 
 #include "mmf_common.h"
+#include "mmf_launch.h"
 #include "../../include/mmf_detmath.h"
 
 // Phase stamps for scripts/ubench/k1_phases.hip (compiled out of the library): thread 0 of every
@@ -66,6 +67,7 @@ __global__ __launch_bounds__(kBlock) void pf_reweight_resample_kernel(
     int32_t* __restrict__ indices_out, int M, int M_out, int mode, float alpha, float lw_uniform,
     float log_uniform, BeliefOut rec, AdaptIn ad) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  // (the host's byte count of these sections is mmf::k1_search_lds, pf_resample_systematic.inc: the two must agree)
   const bool need_cdf = mode != 0;
   const int slot_bytes = need_cdf ? 8 : 4;
   const size_t slots_sz = (static_cast<size_t>(M) * slot_bytes + 15) & ~static_cast<size_t>(15);
@@ -539,13 +541,8 @@ __global__ __launch_bounds__(kBlock) void pf_resample_runs_kernel(
   mmf::resample_systematic_trajectory<D, false, false, false, REC, false, true>(smem, a, M, M, lw_uniform, lw_uniform);
 }
 
-// dynamic LDS of the run variant: CDF slots, scratch, marks (+ the record's rows)
-size_t runs_lds_bytes(int M, bool recording) {
-  const size_t slots = (static_cast<size_t>(M) * 8 + 15) & ~static_cast<size_t>(15);
-  const size_t sc_sz = (sizeof(Scratch) + 15) & ~static_cast<size_t>(15);
-  const size_t marks_sz = ((static_cast<size_t>(M) + 4) * 4 + 15) & ~static_cast<size_t>(15);
-  return slots + sc_sz + marks_sz + (recording ? mmf::k1_belief_lds_bytes() : 0);
-}
+// dynamic LDS of the run variant: CDF slots, scratch, marks (+ the record's rows); no state is staged, so d does not enter
+size_t runs_lds_bytes(int M, bool recording) { return mmf::k1_systematic_lds(M, M, 0, false, recording).end; }
 
 }  // namespace
 
@@ -554,7 +551,7 @@ extern "C" int mmf_pf_dedup_plan(int M, int d, int resample_mode, float soft_alp
   const bool soft = resample_mode != 0 && soft_alpha > 0.f && soft_alpha < 1.f;
   if (resample_mode != 1 || soft) return 0;
   if (M % 64 != 0 || (d != 2 && d != 3)) return 0;
-  return runs_lds_bytes(M, recording != 0) <= 160 * 1024 ? 1 : 0;
+  return runs_lds_bytes(M, recording != 0) <= mmf::kLdsPerCu ? 1 : 0;
 }
 
 extern "C" size_t mmf_pf_dedup_workspace_words(int N, int M) {
@@ -570,7 +567,7 @@ extern "C" int mmf_pf_resample_runs(const float* loglik, const float* logw_in, c
   if (N < 0 || M < 1 || d < 1 || d > MMF_MAX_STATE_DIM) return MMF_EINVAL;
   const bool recording = cov || ess || log_evidence;
   const size_t bytes = runs_lds_bytes(M, recording);
-  if (M > 65536 || bytes > 160 * 1024) return MMF_ETOOLARGE;
+  if (M > 65536 || bytes > mmf::kLdsPerCu) return MMF_ETOOLARGE;
   if (N == 0) return 0;
   int block = ((M + 3) / 4 + MMF_WAVE - 1) / MMF_WAVE * MMF_WAVE;
   if (block > kBlock) block = kBlock;
@@ -578,36 +575,17 @@ extern "C" int mmf_pf_resample_runs(const float* loglik, const float* logw_in, c
   const float lw_uniform = static_cast<float>(-std::log(static_cast<double>(M)));
   const RunTableOut rt{rank, run_anc, run_start, n_runs};
   const BeliefOut rec{cov, ess, log_evidence};
-#define MMF_K1R_LAUNCH(D, RC)                                                                                         \
-  {                                                                                                                   \
-    if (bytes > 64 * 1024) {                                                                                          \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pf_resample_runs_kernel<D, RC>),              \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));        \
-      if (e != hipSuccess) return static_cast<int>(e);                                                                \
-    }                                                                                                                 \
-    pf_resample_runs_kernel<D, RC><<<N, block, bytes, s>>>(loglik, logw_in, states_in, u, estimate, logw_out, indices_out, rt, \
-                                                            M, lw_uniform, rec);                                      \
-  }
-#define MMF_K1R(D) case D: { if (recording) MMF_K1R_LAUNCH(D, true) else MMF_K1R_LAUNCH(D, false) } break;
-  switch (d) { MMF_K1R(1) MMF_K1R(2) MMF_K1R(3) MMF_K1R(4) }
-#undef MMF_K1R
-#undef MMF_K1R_LAUNCH
-  MMF_CHECK_LAUNCH();
-  return 0;
+  return mmf::with_state_dim(d, [&](auto D) {
+    return mmf::with_bool(recording, [&](auto RC) {
+      return mmf::launch(pf_resample_runs_kernel<decltype(D)::value, decltype(RC)::value>, N, block, bytes, s, loglik, logw_in,
+                         states_in, u, estimate, logw_out, indices_out, rt, M, lw_uniform, rec);
+    });
+  });
 }
 
 extern "C" size_t mmf_pf_reweight_resample_lds_bytes(int M, int mode) {
-  const size_t slots = (static_cast<size_t>(M) * (mode ? 8 : 4) + 15) & ~static_cast<size_t>(15);
-  return slots + sizeof(Scratch);
+  return mmf::k1_search_lds(M, mode, 0, false, false).end;
 }
-
-namespace {
-// LDS with the particle states staged behind the CDF; used when one workgroup per CU still fits
-size_t staged_lds_bytes(int M, int d, int mode) {
-  const size_t slots = (static_cast<size_t>(M) * (mode ? 8 : 4) + 15) & ~static_cast<size_t>(15);
-  return slots + ((sizeof(Scratch) + 15) & ~static_cast<size_t>(15)) + static_cast<size_t>(M) * d * sizeof(float);
-}
-}  // namespace
 
 namespace {
 int launch_reweight_resample(const float* loglik, const float* logw_in, const float* states_in, const float* u,
@@ -622,24 +600,19 @@ int launch_reweight_resample(const float* loglik, const float* logw_in, const fl
   if (mode == 0 && M_out != M) return MMF_EINVAL;
   if (!(alpha > 0.f && alpha <= 1.f)) return MMF_EINVAL;
   if (M > 65536 || M_out > 65536) return MMF_ETOOLARGE;
-  size_t lds = mmf_pf_reweight_resample_lds_bytes(M, mode);
-  if (lds > 160 * 1024) return MMF_ETOOLARGE;
   // a recording call keeps its sums' reduction rows behind everything else in LDS (the non-recording layout and
   // limits are untouched): M <= 20,200 in modes 1/2, 40,500 in mode 0
   const bool recording = rec.cov || rec.ess || rec.log_evidence;
   const bool adaptive = ess_threshold > 0.f;  // reduces sum e^2 through the record's rows: the recording call's layout and limits
   const AdaptIn ad{ess_threshold * static_cast<float>(M), resampled};  // the product rounded once, in fp32
-  const size_t rec_sz = (recording || adaptive) ? mmf::k1_belief_lds_bytes() : 0;
-  if (((lds + 15) & ~static_cast<size_t>(15)) + rec_sz > 160 * 1024) return MMF_ETOOLARGE;
+  const bool rows = recording || adaptive;
+  const size_t unstaged = mmf::k1_search_lds(M, mode, d, false, rows).end;
+  if (unstaged > mmf::kLdsPerCu) return MMF_ETOOLARGE;
   if (N == 0) return 0;
   const bool soft = mode != 0 && alpha < 1.f;
-  // stage the states in LDS when occupancy does not pay for it: always if every trajectory gets
-  // a CU of its own (N <= 256), otherwise only while two workgroups still fit a CU (<= 80 KB each)
-  const size_t staged = (recording || adaptive) ? ((staged_lds_bytes(M, d, mode) + 15) & ~static_cast<size_t>(15)) + rec_sz
-                                  : staged_lds_bytes(M, d, mode);
-  const bool stage = mode != 0 && (N <= 256 ? staged <= 160 * 1024 : staged <= 80 * 1024);
-  if (stage) lds = staged;
-  else if (recording || adaptive) lds = ((lds + 15) & ~static_cast<size_t>(15)) + rec_sz;
+  const size_t staged = mmf::k1_search_lds(M, mode, d, true, rows).end;
+  const bool stage = mode != 0 && mmf::k1_stage_fits(N, staged);
+  const size_t lds = stage ? staged : unstaged;
   // enough threads to give each one a float4 of work, at least one wave
   int block = ((M + 3) / 4 + MMF_WAVE - 1) / MMF_WAVE * MMF_WAVE;
   if (block > kBlock) block = kBlock;
@@ -685,68 +658,36 @@ int launch_reweight_resample(const float* loglik, const float* logw_in, const fl
   }
   if (mode == 1 && !soft && M <= 20000 && M_out <= 20000) {
     // plain systematic resampling: the search-free kernel (offspring boundaries + prefix sum of marks)
-    const size_t slots = (static_cast<size_t>(M) * 8 + 15) & ~static_cast<size_t>(15);
-    const size_t sc_sz = (sizeof(Scratch) + 15) & ~static_cast<size_t>(15);
-    const size_t marks_sz = ((static_cast<size_t>(M_out) + 4) * 4 + 15) & ~static_cast<size_t>(15);
-    const size_t base_sz = slots + sc_sz + marks_sz + rec_sz;
-    const size_t xs_sz = static_cast<size_t>(M) * d * sizeof(float);
-    const size_t with_states = base_sz + ((recording || adaptive) ? (xs_sz + 15) & ~static_cast<size_t>(15) : xs_sz);
-    if (base_sz <= 160 * 1024) {
-      const bool st = N <= 256 ? with_states <= 160 * 1024 : with_states <= 80 * 1024;
-      const size_t bytes = st ? with_states : base_sz;
-#define MMF_K1S_LAUNCH(D, ST, RC, AD)                                                                \
-  {                                                                                                  \
-    if (bytes > 64 * 1024) {                                                                         \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pf_resample_systematic_kernel<D, ST, RC, AD>), \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes)); \
-      if (e != hipSuccess) return static_cast<int>(e);                                               \
-    }                                                                                                \
-    pf_resample_systematic_kernel<D, ST, RC, AD><<<N, block, bytes, s>>>(loglik, logw_in, states_in, u, estimate, states_out, \
-                                                                 logw_out, indices_out, M, M_out, lw_uniform, log_uniform, rec, ad); \
-  }
-#define MMF_K1S_ST(D, RC, AD) { if (st) MMF_K1S_LAUNCH(D, true, RC, AD) else MMF_K1S_LAUNCH(D, false, RC, AD) }
-#define MMF_K1S(D)                                                                                   \
-  case D: {                                                                                          \
-    if (adaptive) { if (recording) MMF_K1S_ST(D, true, true) else MMF_K1S_ST(D, false, true) }       \
-    else if (recording) MMF_K1S_ST(D, true, false) else MMF_K1S_ST(D, false, false)                  \
-  } break;
-      switch (d) { MMF_K1S(1) MMF_K1S(2) MMF_K1S(3) MMF_K1S(4) }
-#undef MMF_K1S
-#undef MMF_K1S_ST
-#undef MMF_K1S_LAUNCH
-      MMF_CHECK_LAUNCH();
-      return 0;
+    const size_t base_sz = mmf::k1_systematic_lds(M, M_out, d, false, rows).end;
+    if (base_sz <= mmf::kLdsPerCu) {
+      const size_t with_states = mmf::k1_systematic_lds(M, M_out, d, true, rows).end;
+      const bool st = mmf::k1_stage_fits(N, with_states);
+      return mmf::with_state_dim(d, [&](auto D) {
+        return mmf::with_bool(st, [&](auto ST) {
+          return mmf::with_bool(recording, [&](auto RC) {
+            return mmf::with_bool(adaptive, [&](auto AD) {
+              return mmf::launch(pf_resample_systematic_kernel<decltype(D)::value, decltype(ST)::value, decltype(RC)::value, decltype(AD)::value>,
+                                 N, block, st ? with_states : base_sz, s, loglik, logw_in, states_in, u, estimate, states_out,
+                                 logw_out, indices_out, M, M_out, lw_uniform, log_uniform, rec, ad);
+            });
+          });
+        });
+      });
     }
   }
-#define MMF_K1_LAUNCH(D, ST, SO, RC, AD)                                                       \
-  {                                                                                            \
-    if (lds > 64 * 1024) {                                                                     \
-      hipError_t e = hipFuncSetAttribute(                                                      \
-          reinterpret_cast<const void*>(&pf_reweight_resample_kernel<D, ST, SO, RC, AD>),      \
-          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));                  \
-      if (e != hipSuccess) return static_cast<int>(e);                                         \
-    }                                                                                          \
-    pf_reweight_resample_kernel<D, ST, SO, RC, AD><<<N, block, lds, s>>>(loglik, logw_in, states_in, u, \
-        estimate, states_out, logw_out, indices_out, M, M_out, mode, alpha, lw_uniform, log_uniform, rec, ad); \
-  }
-#define MMF_K1_SS(D, RC, AD)                                                                   \
-  {                                                                                            \
-    if (soft) { if (stage) MMF_K1_LAUNCH(D, true, true, RC, AD) else MMF_K1_LAUNCH(D, false, true, RC, AD) } \
-    else if (stage) MMF_K1_LAUNCH(D, true, false, RC, AD) else MMF_K1_LAUNCH(D, false, false, RC, AD)  \
-  }
-#define MMF_K1(D)                                                                              \
-  case D: {                                                                                    \
-    if (adaptive) { if (recording) MMF_K1_SS(D, true, true) else MMF_K1_SS(D, false, true) }   \
-    else if (recording) MMF_K1_SS(D, true, false) else MMF_K1_SS(D, false, false)              \
-  } break;
-  switch (d) {
-    MMF_K1(1) MMF_K1(2) MMF_K1(3) MMF_K1(4)
-  }
-#undef MMF_K1
-#undef MMF_K1_SS
-#undef MMF_K1_LAUNCH
-  MMF_CHECK_LAUNCH();
-  return 0;
+  return mmf::with_state_dim(d, [&](auto D) {
+    return mmf::with_bool(stage, [&](auto ST) {
+      return mmf::with_bool(soft, [&](auto SO) {
+        return mmf::with_bool(recording, [&](auto RC) {
+          return mmf::with_bool(adaptive, [&](auto AD) {
+            return mmf::launch(pf_reweight_resample_kernel<decltype(D)::value, decltype(ST)::value, decltype(SO)::value, decltype(RC)::value, decltype(AD)::value>,
+                               N, block, lds, s, loglik, logw_in, states_in, u, estimate, states_out, logw_out, indices_out, M,
+                               M_out, mode, alpha, lw_uniform, log_uniform, rec, ad);
+          });
+        });
+      });
+    });
+  });
 }
 }  // namespace
 

@@ -26,6 +26,7 @@
 #pragma once
 
 #include "mmf_granule.h"
+#include "mmf_launch.h"
 
 #ifndef K1_STAMP  // phase stamps of scripts/ubench/k1_phases.hip (pf_resample.hip defines it under MMF_K1_PHASE_CLOCKS)
 #define K1_STAMP(i)
@@ -87,6 +88,41 @@ struct K1BeliefScratch {  // REC / ADAPT only: behind everything else in dynamic
   float piv_wave[kK1MaxWaves];  // per wave: -(smallest index holding the row maximum), -inf: none
 };
 constexpr size_t k1_belief_lds_bytes() { return (sizeof(K1BeliefScratch) + 15) & ~static_cast<size_t>(15); }
+
+// ---- The dynamic LDS of every form of K1, host side: the ONE place a launcher's byte count and stage decision come from.
+// Behind the slots (offset 0) lie, each at the next multiple of 16 bytes: K1Scratch, the marks (search-free kernel only), the
+// staged states (STAGE), the belief rows (REC / ADAPT).  `end` is the end of the last section in use -- the launch's dynamic LDS;
+// nothing is rounded behind it.  The device prologues (resample_systematic_trajectory below, pf_reweight_resample_kernel in
+// pf_resample.hip) keep their own offset arithmetic and must agree: a host sum below theirs is an out-of-bounds LDS write.
+constexpr size_t k1_align16(size_t bytes) { return (bytes + 15) & ~static_cast<size_t>(15); }
+
+struct K1Lds { size_t scratch, marks, states, belief, end; };
+
+constexpr K1Lds k1_lds_sections(size_t slots_bytes, size_t marks_bytes, size_t states_bytes, bool with_belief_rows) {
+  K1Lds p{};
+  p.scratch = k1_align16(slots_bytes);
+  p.end = p.scratch + sizeof(K1Scratch);
+  p.marks = k1_align16(p.end);
+  if (marks_bytes != 0) p.end = p.marks + marks_bytes;
+  p.states = k1_align16(p.end);
+  if (states_bytes != 0) p.end = p.states + states_bytes;
+  p.belief = k1_align16(p.end);
+  if (with_belief_rows) p.end = p.belief + k1_belief_lds_bytes();
+  return p;
+}
+// the search-free kernels (resample_systematic_trajectory): u64 CDF slots; M_out + 4 marks, read as uint4 -- whole 16 bytes
+constexpr K1Lds k1_systematic_lds(int M, int M_out, int d, bool staged, bool with_belief_rows) {
+  return k1_lds_sections(static_cast<size_t>(M) * 8, k1_align16((static_cast<size_t>(M_out) + 4) * 4),
+                         staged ? static_cast<size_t>(M) * d * sizeof(float) : 0, with_belief_rows);
+}
+// the search kernel (pf_reweight_resample_kernel): fp32 slots in mode 0, the u64 CDF in modes 1 / 2; no marks
+constexpr K1Lds k1_search_lds(int M, int mode, int d, bool staged, bool with_belief_rows) {
+  return k1_lds_sections(static_cast<size_t>(M) * (mode ? 8 : 4), 0, staged ? static_cast<size_t>(M) * d * sizeof(float) : 0,
+                         with_belief_rows);
+}
+// The staging rule: the states go to LDS when occupancy does not pay for it -- always if every trajectory gets a CU of its own
+// (N <= 256), otherwise only while two workgroups still fit a CU
+constexpr bool k1_stage_fits(int N, size_t staged_bytes) { return staged_bytes <= (N <= 256 ? kLdsPerCu : kLdsHalfCu); }
 
 // the outputs of one trajectory, from the reduced sums (threads 0 .. D*D - 1 write; symmetric bit for bit: entry (i, j) and
 // (j, i) evaluate the same expression on the same operands)
@@ -173,6 +209,7 @@ struct K1Trajectory {  // pointers of ONE trajectory's rows
 template <int D, bool STAGE, bool COH, bool DET, bool REC = false, bool ADAPT = false, bool RUNS = false>
 __device__ __forceinline__ bool resample_systematic_trajectory(unsigned char* smem, const K1Trajectory& a, int M, int M_out,
                                                                float lw_uniform, float log_uniform) {
+  // (the host's byte count of these sections is mmf::k1_systematic_lds above: the two must agree)
   const size_t slots_sz = (static_cast<size_t>(M) * 8 + 15) & ~static_cast<size_t>(15);
   unsigned long long* cdf = reinterpret_cast<unsigned long long*>(smem);  // first the fp32 x_i, then the u64 CDF
   K1Scratch& sc = *reinterpret_cast<K1Scratch*>(smem + slots_sz);

@@ -14,6 +14,7 @@
 // Rows are few (N or T*N) and the work is ~50 kMAC per row: the point is to keep library
 // heuristics and ~50 launches per step off the hot path, and the step's latency short.
 #include "mmf_common.h"
+#include "mmf_launch.h"
 
 namespace {
 
@@ -291,17 +292,11 @@ extern "C" int mmf_traj_program(const MmfTrajInstr* prog, int n_instr, const flo
   IoPtrs p{};
   for (int i = 0; i < MMF_TRAJ_MAX_IO; ++i) p.p[i] = io[i];
   const size_t lds = static_cast<size_t>(n_slots) * kRows * (vec_width + kPad) * sizeof(float);  // one task's slot file
-  if (lds > 160 * 1024) return MMF_ETOOLARGE;
-  auto k = traj_program_kernel;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-  if (e != hipSuccess) return static_cast<int>(e);
+  if (lds > mmf::kLdsPerCu) return MMF_ETOOLARGE;
   const int tasks = (R + kRows - 1) / kRows;
   // a 5-slot, 64-wide program takes 21 KB per task: seven workgroups (28 waves) share a CU
-  const int per_cu = static_cast<int>((160 * 1024) / lds) < 8 ? static_cast<int>((160 * 1024) / lds) : 8;
+  const int per_cu = static_cast<int>(mmf::kLdsPerCu / lds) < 8 ? static_cast<int>(mmf::kLdsPerCu / lds) : 8;
   int grid = tasks < 256 * per_cu ? tasks : 256 * per_cu;
-  const int waves = kWaves;
-  k<<<grid, waves * MMF_WAVE, lds, static_cast<hipStream_t>(stream)>>>(prog, n_instr, weights, p, R, n_slots, vec_width);
-  MMF_CHECK_LAUNCH();
-  return 0;
+  return mmf::launch(traj_program_kernel, grid, kWaves * MMF_WAVE, lds, static_cast<hipStream_t>(stream), prog, n_instr, weights, p,
+                     R, n_slots, vec_width);
 }

@@ -3,6 +3,7 @@ K1 (reweight + resample) bit-exact on indices against ``oracle/resample.py``; K3
 algebra + fusion) and K2/K5 (per-particle networks, Jacobian) within 1e-4 relative of the
 oracle's fp32 torch restatement (the tolerance ``north_star`` states).
 """
+import functools
 import math
 import os
 
@@ -67,6 +68,107 @@ def test_k1_indices_bit_exact(N, M, d, mode):
     np.testing.assert_array_equal(xo, w_x)               # gathered particles are copies
     np.testing.assert_allclose(lwo, w_lw, rtol=1e-6, atol=1e-6)
     np.testing.assert_allclose(est, w_est, rtol=1e-4, atol=1e-5)
+
+
+_K1_LAUNCH_FAMILIES = {"systematic": (1, 1.0), "multinomial": (2, 1.0), "soft": (1, 0.5)}
+_K1_LAUNCH_THR = 0.5
+
+
+@functools.lru_cache(maxsize=None)
+def _k1_launch_case(M, d, family):
+    """Inputs of the largest batch of this (M, d, family) -- a smaller batch is its first trajectories --, the fp64 ESS / M of
+    every trajectory and the oracle's outputs; computed once and shared by the cases.  The log-likelihoods of the even
+    trajectories are nearly flat (x 0.05: the trajectory is kept at a threshold of 0.5), those of the odd ones spread (x 3:
+    it resamples)."""
+    mode, alpha = _K1_LAUNCH_FAMILIES[family]
+    N = 257 if M < 8192 else 2
+    rng = np.random.RandomState(7 * M + d)
+    scale = np.where(np.arange(N) % 2 == 0, 0.05, 3.0)
+    ll = (rng.standard_normal((N, M)) * scale[:, None]).astype(np.float32)
+    lw = np.log(rng.dirichlet(np.ones(M) * 8.0, N)).astype(np.float32)
+    x = rng.standard_normal((N, M, d)).astype(np.float32)
+    u = np.minimum(rng.uniform(0, 1, (N,) if mode == 1 else (N, M)).astype(np.float32),  # (a million draws: one rounds to 1.0)
+                   np.float32(1.0) - np.float32(2.0 ** -24))
+    a = ll.astype(np.float64) + lw.astype(np.float64)
+    w = np.exp(a - a.max(axis=1, keepdims=True))
+    ess_frac = w.sum(axis=1) ** 2 / (w * w).sum(axis=1) / M
+    want = rs.reweight_resample(ll, lw, x, u, "systematic" if mode == 1 else "multinomial", M, soft_alpha=alpha)
+    for arr in (ll, lw, x, u, ess_frac) + tuple(want):
+        arr.setflags(write=False)
+    return (ll, lw, x, u), ess_frac, want
+
+
+@pytest.mark.parametrize("family", list(_K1_LAUNCH_FAMILIES))
+@pytest.mark.parametrize("d", [2, 3])
+@pytest.mark.parametrize("N,M", [(2, 3072), (257, 3072), (2, 4096), (257, 4096), (2, 8192)])
+def test_k1_every_launch_choice_gives_the_oracles_bits(N, M, d, family):
+    """The launcher's choices, each against the oracle: states staged in LDS or gathered from global memory, on either side of
+    both staging limits (a whole CU while N <= 256, half a CU beyond), for the search-free and the search kernel, with and
+    without the record and the ESS-triggered decision, and dynamic LDS below and above the 64 KiB a launch gets without asking.
+    At d = 3: M = 3072 is staged for any N (the search kernel's 61,984 B need no opt-in), M = 4096 (98,864 B search-free,
+    82,464 B search) only for N <= 256, M = 8192 for no N.  The first two trajectories of an N = 257 batch are the N = 2
+    inputs, so their records must carry the same bits staged and unstaged."""
+    abi = _abi()
+    dev = _cuda()
+    mode, alpha = _K1_LAUNCH_FAMILIES[family]
+    inputs, ess_frac, want = _k1_launch_case(M, d, family)
+    ll_h, lw_h, x_h, u_h = (a[:N] for a in inputs)
+    w_est, w_x, w_lw, w_idx = (a[:N] for a in want)
+    ess_frac = ess_frac[:N]
+    # the adaptive calls decide far from the threshold, and both ways
+    assert np.abs(ess_frac - _K1_LAUNCH_THR).min() > 0.02, ess_frac
+    want_keep = ess_frac > _K1_LAUNCH_THR
+    assert want_keep.any() and not want_keep.all()
+    ll, lw, x, u = (torch.from_numpy(np.array(a)).to(dev) for a in (ll_h, lw_h, x_h, u_h))  # (copies: the shared arrays are read-only)
+
+    def call(n, rec, adaptive, mode=mode, alpha=alpha):
+        o = dict(est=torch.full((n, d), math.nan, device=dev), so=torch.full((n, M, d), math.nan, device=dev),
+                 lw=torch.full((n, M), math.nan, device=dev), idx=torch.full((n, M), -1, dtype=torch.int32, device=dev))
+        kw = {}
+        if rec:
+            o.update(cov=torch.full((n, d, d), math.nan, device=dev), ess=torch.full((n,), math.nan, device=dev),
+                     lev=torch.full((n,), math.nan, device=dev))
+            kw = dict(cov=o["cov"], ess=o["ess"], log_evidence=o["lev"])
+        args = (ll[:n], lw[:n], x[:n], u[:n] if mode else None, o["est"], o["so"], o["lw"], o["idx"] if mode else None, mode, alpha)
+        if adaptive:
+            o["took"] = torch.full((n,), -1, dtype=torch.int32, device=dev)
+            abi.pf_reweight_resample_adaptive(*args, ess_threshold=_K1_LAUNCH_THR, resampled=o["took"], **kw)
+        else:
+            abi.pf_reweight_resample_belief(*args, **kw)
+        return o
+
+    plain = call(N, False, False)
+    np.testing.assert_array_equal(plain["idx"].cpu().numpy(), w_idx)            # bit-exact ancestors
+    np.testing.assert_array_equal(plain["so"].cpu().numpy(), w_x)               # gathered particles are copies
+    np.testing.assert_allclose(plain["lw"].cpu().numpy(), w_lw, rtol=1e-6, atol=1e-6)
+    np.testing.assert_allclose(plain["est"].cpu().numpy(), w_est, rtol=1e-4, atol=1e-5)
+
+    recd = call(N, True, False)
+    for k in ("est", "so", "lw", "idx"):
+        assert torch.equal(recd[k], plain[k]), k
+
+    ada, ada_rec = call(N, False, True), call(N, True, True)
+    for k in ("cov", "ess", "lev"):  # one record, whichever kernel writes it
+        assert torch.equal(ada_rec[k], recd[k]), k
+    if N > 2:  # ... and however many trajectories share the launch: staged (N = 2) against unstaged
+        for rec2 in (call(2, True, False), call(2, True, True)):
+            for k in ("cov", "ess", "lev"):
+                assert torch.equal(rec2[k], recd[k][:2]), k
+
+    floor = np.float32(_K1_LAUNCH_THR) * np.float32(M)  # the product rounded once in fp32
+    keeps = ada_rec["ess"] >= float(floor)
+    print(f"{family} N={N} M={M} d={d}: kept {int(keeps.sum())} of {N}; fp64 ess / M in "
+          f"[{ess_frac[want_keep].min():.3f}, {ess_frac[want_keep].max():.3f}] and [{ess_frac[~want_keep].min():.2e}, {ess_frac[~want_keep].max():.2e}]")
+    assert np.array_equal(keeps.cpu().numpy(), want_keep)
+    mode0 = call(N, False, False, mode=0, alpha=1.0)
+    ident = torch.arange(M, dtype=torch.int32, device=dev)[None].expand(N, M)
+    for got in (ada, ada_rec):
+        assert torch.equal(got["took"], (~keeps).to(torch.int32))
+        for k in ("so", "lw", "idx"):
+            assert torch.equal(got[k][~keeps], plain[k][~keeps]), (k, "resampled")
+        assert torch.equal(got["lw"][keeps], mode0["lw"][keeps])
+        assert torch.equal(got["so"][keeps], x[keeps]) and torch.equal(got["idx"][keeps], ident[keeps])
+        assert torch.equal(got["est"], plain["est"])
 
 
 @pytest.mark.parametrize("N,M,d", [(8, 1024, 3), (32, 4096, 3), (5, 2048, 2), (3, 4096, 2), (100, 512, 3), (16, 3072, 3)])
