@@ -1217,6 +1217,20 @@ def image_encoder_flops(n_images: int) -> float:
     return 2.0 * 26_124_288 * n_images  # MAC per image of the default stack
 
 
+def _image_chunks(N: int) -> "list[int]":
+    """Sizes of the launch sequences ``encode_images`` splits ``N`` images into.  Bounded workspace: at most
+    ``_IMAGE_CHUNK`` images per launch sequence, in EQUAL chunks (5,120 images run as 2 x 2,560, not 4,096 + 1,024: a
+    short chunk's persistent grids spend a third of their launch filling and draining), each a multiple of 256 so every
+    workgroup of the persistent grids gets the same number of images.  ``N <= 256`` is one chunk, ``N == 0`` none."""
+    if N <= 0:
+        return []
+    if N <= 256:
+        return [N]
+    n_chunks = -(-N // _IMAGE_CHUNK)
+    per = max(1, min(_IMAGE_CHUNK, -(-(-(-N // n_chunks)) // 256) * 256))
+    return [min(per, N - c0) for c0 in range(0, N, per)]
+
+
 def encode_images(encoders, images: torch.Tensor):
     """Run several image encoders on the same ``(N, 32, 32)`` batch: default stacks go
     (``door_models/layers.py:43-63``) and the push virtual sensor's spanning-pool stacks
@@ -1237,15 +1251,10 @@ def encode_images(encoders, images: torch.Tensor):
     for variant, grp in groups:
         packs = [packed_image_encoder(encoders[i]).blob() for i in grp]
         pieces = []  # per chunk: (nets, n, 64), written by the launch sequence itself
-        # bounded workspace: at most _IMAGE_CHUNK images per launch sequence, in EQUAL chunks (round 5: 5,120 images run
-        # as 2 x 2,560, not 4,096 + 1,024 -- the short chunk's persistent grids spent a third of their launch filling
-        # and draining, profiles/r04: 0.265 PF against 0.31), a multiple of 256 so every workgroup of the persistent
-        # grids gets the same number of images
-        n_chunks = -(-N // _IMAGE_CHUNK)
-        per = max(1, min(_IMAGE_CHUNK, -(-(-(-N // n_chunks)) // 256) * 256) if N > 256 else N)  # N == 0: an empty loop
-        for c0 in range(0, N, per):
-            n = min(per, N - c0)
+        c0 = 0
+        for n in _image_chunks(N):
             chunk = images[c0:c0 + n]
+            c0 += n
             feat = torch.empty((len(grp), n, 64), dtype=torch.float32, device=images.device)
             ws = _image_workspace(images.device, n, len(grp))
             prec = image_encoder_precision_code()

@@ -9,6 +9,7 @@ pytestmark = pytest.mark.gpu
 from oracle import models as om
 from oracle.tf.base import ReplayNoise
 
+from _conv_cases import image_convs_against_fp64 as _image_convs_against_fp64
 from _tol import rel_err, scalar_rel
 
 
@@ -687,46 +688,6 @@ def test_k6_image_convs_function_matches_fp64_autograd(N, precision):
             _image_convs_against_fp64(N, 1e-7)
     finally:
         engine.set_image_encoder_precision(None)
-
-
-def _image_convs_against_fp64(N, gscale):
-    import torch.nn.functional as F
-
-    from multimodalfilter_amd import engine, layers
-
-    dev = torch.device("cuda:0")
-    torch.manual_seed(70 + N)
-    seq = layers.image_encoder(64).to(dev)
-    g = torch.Generator().manual_seed(N)
-    img = (torch.randn((N, 32, 32), generator=g) * 0.5).clamp(-1, 1)
-    img[N // 2] = 0.0
-    gout = torch.randn((N, 8, 32, 32), generator=g) * gscale
-    params = engine.PackedImageEncoder(seq)._sources()[:10]
-    a4 = engine.ImageConvsFunction.apply(seq, img.to(dev), *params)
-    got = torch.autograd.grad(a4, params, gout.to(dev))
-
-    # Among ~1e6 pre-activations a few sit within fp32 rounding of zero, where an fp32 forward and an
-    # fp64 one take different ReLU branches (one such pixel moves a weight gradient by 1e-3): the
-    # reference applies the masks of the kernel's own forward, so that only arithmetic is compared
-    from multimodalfilter_amd import _abi
-    mk = lambda c: torch.empty((N, c, 32, 32), dtype=torch.float32, device=dev)
-    k1, kh, k2, k3, k4 = mk(32), mk(32), mk(32), mk(16), mk(8)
-    _abi.image_convs_train_forward(seq._mmf_packed.blob(), img.to(dev).contiguous(), k1, kh, k2, k3, k4, engine.range_flag(dev),
-                                   engine.training_image_precision_code())   # the arithmetic ImageConvsFunction ran in
-    m1, mh, m2, m3 = [(t > 0).double().cpu() for t in (k1, kh, k2, k3)]
-    p64 = [p.detach().double().cpu().requires_grad_(True) for p in params]
-    w1, w2a, w2b, w3, w4, b1, b2a, b2b, b3, b4 = p64
-    x = img.double()[:, None]
-    a1 = F.conv2d(x, w1, b1, padding=2) * m1
-    h = F.conv2d(a1, w2a, b2a, padding=1) * mh
-    a2 = (a1 + F.conv2d(h, w2b, b2b, padding=1)) * m2
-    a3 = F.conv2d(a2, w3, b3, padding=1) * m3
-    ref = F.conv2d(a3, w4, b4, padding=1)
-    want = torch.autograd.grad(ref, p64, gout.double())
-    assert rel_err(a4.detach(), ref.detach(), dims=3) < 1e-4   # every image's (8, 32, 32) feature map
-    for name, a, b in zip("w1 w2a w2b w3 w4 b1 b2a b2b b3 b4".split(), got, want):
-        scale = max(1e-30, float(b.abs().max()))
-        assert float((a.cpu().double() - b).abs().max()) / scale < 1e-4, (name, gscale)
 
 
 @pytest.mark.parametrize("tname", ["door", "push"])
