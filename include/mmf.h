@@ -578,6 +578,36 @@ int mmf_pf_dynamics_runs_philox(const float* packed, int n_res, int precision, c
                                 const int32_t* run_start, const int32_t* n_runs, float* states_out, int* range_flag,
                                 int N, int M, int d, void* stream);
 
+/* The step loop that KEEPS ITS HISTORY for particle smoothing (mmf_pf_smooth): the set every step propagated, the log-weights
+ * every step's K1 started from, and -- through args->loglik_steps / args->indices_steps -- the log-likelihoods and the
+ * ancestors.  Upstream torchfilter overwrites particle_states / particle_log_weights at every step and leaves keeping them
+ * to the caller.  Purely additive to ABI 42: a new symbol and a struct of its own, MmfPfLoopArgs keeps its layout.  The
+ * forward side needs no kernel change, only pointers: the dynamics launch of step t writes slice t of states_steps, the
+ * measurement launches and K1 read it there, and K1 gathers into the scratch buffers states_a / states_b (never into a
+ * history slice: the run-table path's last K1 included).  Without resampling the next dynamics launch reads slice t
+ * directly and ONE device-to-device copy after the last step puts the belief where final_location says; the run-table path
+ * reads the ancestors' rows from slice t - 1.  Where logw_in_steps is given, K1's logw_out of step t is slice t + 1 (the
+ * last step's goes to logw_a / logw_b as ever); a kept trajectory of the adaptive loop already writes identity ancestors and
+ * carried weights.  Every output the loop had before -- estimates, records, indices_steps, loglik_steps, the belief on return,
+ * resampled_steps, final_location -- has the same bits with the history attached.
+ * The call takes the loop of launches: the persistent form keeps no history (as it keeps no indices_steps) and
+ * args->persistent is ignored.
+ *   ess_threshold    0: off (mmf_pf_forward_loop / _dedup); otherwise as mmf_pf_forward_loop_adaptive
+ *   resampled_steps  (T, N) int32 or null (adaptive only)
+ *   ws               the run-table workspace of mmf_pf_forward_loop_dedup, or null
+ * MMF_EINVAL: null args / history / states_steps / logw_in0, null args->loglik_steps, null args->indices_steps with
+ * resample_mode != 0, null logw_in_steps where weights travel, and whatever the loop it stands for refuses. */
+typedef struct MmfPfHistory {
+  float*   states_steps;   /* (T, N, M, d)  the set step t PROPAGATED (what K1 of step t read)              */
+  float*   logw_in_steps;  /* (T, N, M) or null: the log-weights K1 of step t started from.  Required where */
+                           /* weights travel (resample_mode 0, soft alpha, ESS threshold); null allowed for  */
+                           /* plain resampling, where they are uniform for t > 0 and step 0's are the belief's */
+  float*   logw_in0;       /* (N, M): copy of the belief's log-weights on entry (written by the call)        */
+} MmfPfHistory;
+int mmf_pf_forward_loop_history(const MmfPfLoopArgs* args /* host */, const MmfPfHistory* history /* host */,
+                                float ess_threshold, int32_t* resampled_steps,
+                                const MmfPfDedupWorkspace* ws /* host or null */, void* stream);
+
 /* The persistent form of the step loop (MmfPfLoopArgs.persistent): at the sizes the reference itself runs (32
  * trajectories x 300 particles: door_models/pf.py:24-27, eval_helpers.py:125-142) a step is bound by the fixed cost
  * of its four launches; one launch whose workgroups keep ONE network's weights in LDS for all T steps and hand
@@ -624,6 +654,41 @@ int mmf_philox_uniforms(unsigned long long seed, unsigned step0, unsigned traj0,
 int mmf_dynamics_forward_loop(const float* packed, int n_res, int precision, const float* x0,
                               const float* traj_bias, float* out, int32_t* range_flag, int T, int N, int d,
                               void* stream);
+
+/* ---------------------------------------------------------------- particle smoothing: ancestry trace + moments
+ * The estimate E[x_t | y_1..s] for an endpoint s >= t from a filter run's history (mmf_pf_forward_loop_history, or the same
+ * arrays stacked step by step).  Upstream torchfilter's ParticleFilter reports the filtered estimate only and leaves
+ * particle_states / particle_log_weights to the caller after each step; this is what a caller would build on them.
+ * Ancestry (genealogy) smoothing with a fixed-lag option: for particle m of the endpoint the path index is b_s[m] = m,
+ * b_t[m] = A_t[b_{t+1}[m]] (A_t: the ancestors step t drew, identity where nothing was resampled), and the smoothed moments
+ * of step t are those of {X_t[b_t[m]]} under the endpoint's normalised weights w_s = softmax_m(loglik_s + logw_in_s).
+ * With lag L the endpoint of step t is s(t) = min(t + L, T - 1); L >= T - 1 is the full smoother, L = 0 the filter's own
+ * weighted set.  One workgroup per (trajectory, endpoint): endpoint s < T - 1 walks back L steps and writes step s - L,
+ * endpoint T - 1 writes every step it passes (itself included); endpoints with s - L < 0 are not launched.  b lives in
+ * registers (several particles per thread beyond 1024), the weights in LDS.
+ * Arithmetic: K1's pivot form (mmf_pf_reweight_resample_belief) -- pivot p = the row of the first highest-weight path,
+ * e_m = exp(a_m - max), S = sum e, m1 = sum e (x - p), M2 = sum e (x - p)(x - p)^T, mean = p + m1 / S,
+ * cov = M2 / S - (m1 / S)(m1 / S)^T, stored symmetric bit for bit; a path with a_m = -inf contributes exactly zero.
+ * Reductions in a fixed order (DPP wave sums, then the waves' partials in LDS in wave order; no float atomics): two runs
+ * give the same bits.  unique: a bitmap of M bits in LDS (integer atomics) and a popcount, over the paths with a_m > -inf.
+ * Ancestors are clamped to [0, M): a corrupted index gives a wrong number, never a fault.
+ * Limits: 1 <= d <= 4; M <= 65536 and mmf_pf_smooth_lds_bytes(M) <= 160 KiB (4 B per particle + the bitmap: M <= 39,400),
+ * larger -> MMF_ETOOLARGE.  lag < 0, T < 0, N < 0, M < 1 or a null args / states_steps / loglik_steps / mean -> MMF_EINVAL.
+ * N == 0 or T == 0 is a successful no-op. */
+typedef struct MmfPfSmoothArgs {
+  int32_t T, N, M, d, lag;          /* lag >= 0; lag >= T-1: full smoother */
+  const float* states_steps;        /* (T, N, M, d) */
+  const float* loglik_steps;        /* (T, N, M)    */
+  const float* logw_in_steps;       /* (T, N, M) or null = uniform for t > 0 */
+  const float* logw_in0;            /* (N, M) or null = uniform; read for step 0 when logw_in_steps is null */
+  const int32_t* indices_steps;     /* (T, N, M) or null = identity */
+  float* mean;                      /* (T, N, d)    */
+  float* cov;                       /* (T, N, d, d) or null */
+  int32_t* unique;                  /* (T, N) or null: distinct particles of step t on the endpoint's paths */
+} MmfPfSmoothArgs;                  /* host struct holding device pointers */
+int mmf_pf_smooth(const MmfPfSmoothArgs* args /* host */, void* stream);
+/* Dynamic LDS bytes mmf_pf_smooth requests for M particles (monotone in M). */
+size_t mmf_pf_smooth_lds_bytes(int M);
 
 /* ---------------------------------------------------------------- K6, fused: one network call of the training backward
  * Recompute (the forward pass's f16x3 arithmetic), backward data path and weight / bias gradients of ONE per-particle

@@ -98,6 +98,17 @@ class MmfPfDedupWorkspace(Structure):
     _fields_ = [("rank", _FP), ("run_anc", _FP), ("run_start", _FP), ("n_runs", _FP)]
 
 
+class MmfPfHistory(Structure):
+    """History arrays of ``mmf_pf_forward_loop_history`` (include/mmf.h): float32 device arrays."""
+    _fields_ = [("states_steps", _FP), ("logw_in_steps", _FP), ("logw_in0", _FP)]
+
+
+class MmfPfSmoothArgs(Structure):
+    _fields_ = [("T", c_int32), ("N", c_int32), ("M", c_int32), ("d", c_int32), ("lag", c_int32),
+                ("states_steps", _FP), ("loglik_steps", _FP), ("logw_in_steps", _FP), ("logw_in0", _FP),
+                ("indices_steps", _FP), ("mean", _FP), ("cov", _FP), ("unique", _FP)]
+
+
 class MmfTrainNet(Structure):
     _fields_ = [("packed", _FP), ("packed_f32", _FP), ("packed_t", _FP), ("head_w", _FP), ("pw", _FP), ("pb", _FP),
                 ("p_first", _FP), ("p_head", _FP), ("p_dout", _FP), ("p_traj", _FP), ("packed_dual", _FP)]
@@ -176,6 +187,10 @@ SIGNATURES = {
     "mmf_pf_forward_loop": (c_int, [POINTER(MmfPfLoopArgs), c_void_p]),
     "mmf_pf_forward_loop_adaptive": (c_int, [POINTER(MmfPfLoopArgs), ctypes.c_float, _FP, c_void_p]),
     "mmf_pf_forward_loop_dedup": (c_int, [POINTER(MmfPfLoopArgs), POINTER(MmfPfDedupWorkspace), c_void_p]),
+    "mmf_pf_forward_loop_history": (c_int, [POINTER(MmfPfLoopArgs), POINTER(MmfPfHistory), ctypes.c_float, _FP,
+                                            POINTER(MmfPfDedupWorkspace), c_void_p]),
+    "mmf_pf_smooth": (c_int, [POINTER(MmfPfSmoothArgs), c_void_p]),
+    "mmf_pf_smooth_lds_bytes": (c_size_t, [c_int]),
     "mmf_pf_dedup_plan": (c_int, [c_int, c_int, c_int, ctypes.c_float, c_int]),
     "mmf_pf_dedup_workspace_words": (c_size_t, [c_int, c_int]),
     "mmf_pf_resample_runs": (c_int, [_FP] * 11 + [c_int, c_int, c_int, _FP, _FP, _FP, c_void_p]),
@@ -771,13 +786,15 @@ def pf_resample_runs(loglik, logw_in, states, u, estimate, indices_out, rank, ru
 
 
 def pf_forward_loop(args: MmfPfLoopArgs, like: torch.Tensor, events=None, event_stride: int = 1, *,
-                    ess_threshold: float = None, resampled_steps=None, dedup: MmfPfDedupWorkspace = None) -> int:
+                    ess_threshold: float = None, resampled_steps=None, dedup: MmfPfDedupWorkspace = None,
+                    history: MmfPfHistory = None) -> int:
     """Enqueue T filter steps; returns the final-location bits (see include/mmf.h).
     ``events``: optional flat list of created ``torch.cuda.Event`` (timing) recorded in C
     around the launches of every ``event_stride``-th step.
     ``ess_threshold``: ESS-triggered resampling (``mmf_pf_forward_loop_adaptive``), ``resampled_steps`` its ``(T, N)`` int32
     decisions or ``None``.  ``dedup``: the run-table workspace (``mmf_pf_forward_loop_dedup``: the dynamics network once per
-    distinct resampled ancestor; plain resampling only) or ``None``."""
+    distinct resampled ancestor; plain resampling only) or ``None``.  ``history``: the arrays a smoother needs
+    (``mmf_pf_forward_loop_history``: the loop of launches with the same threshold / workspace) or ``None``."""
     loc = c_int32(0)
     args.final_location = ctypes.pointer(loc)
     if events is not None:
@@ -785,7 +802,12 @@ def pf_forward_loop(args: MmfPfLoopArgs, like: torch.Tensor, events=None, event_
         args.events = arr
         args.event_stride = event_stride
     with _on(like):
-        if ess_threshold is not None:
+        if history is not None:
+            _check(load().mmf_pf_forward_loop_history(
+                ctypes.byref(args), ctypes.byref(history), 0.0 if ess_threshold is None else float(ess_threshold),
+                ptr(resampled_steps, dtype=torch.int32), None if dedup is None else ctypes.byref(dedup), stream_of(like)),
+                "mmf_pf_forward_loop_history")
+        elif ess_threshold is not None:
             _check(load().mmf_pf_forward_loop_adaptive(ctypes.byref(args), float(ess_threshold),
                                                        ptr(resampled_steps, dtype=torch.int32), stream_of(like)),
                    "mmf_pf_forward_loop_adaptive")
@@ -795,3 +817,26 @@ def pf_forward_loop(args: MmfPfLoopArgs, like: torch.Tensor, events=None, event_
         else:
             _check(load().mmf_pf_forward_loop(ctypes.byref(args), stream_of(like)), "mmf_pf_forward_loop")
     return int(loc.value)
+
+
+def pf_smooth_lds_bytes(M: int) -> int:
+    return int(load().mmf_pf_smooth_lds_bytes(int(M)))
+
+
+def pf_smooth(states_steps, loglik_steps, logw_in_steps, logw_in0, indices_steps, lag: int, mean, cov=None, unique=None):
+    """Ancestry smoothing of a filter run's history (``mmf_pf_smooth``, include/mmf.h): ``states_steps (T, N, M, d)``,
+    ``loglik_steps (T, N, M)``, ``logw_in_steps (T, N, M)`` / ``logw_in0 (N, M)`` / ``indices_steps (T, N, M)`` int32 each or
+    ``None`` -> ``mean (T, N, d)``, ``cov (T, N, d, d)`` and ``unique (T, N)`` int32, each of the last two or ``None``."""
+    T, N, M, d = states_steps.shape
+    assert loglik_steps.shape == (T, N, M) and mean.shape == (T, N, d)
+    assert logw_in_steps is None or logw_in_steps.shape == (T, N, M)
+    assert logw_in0 is None or logw_in0.shape == (N, M)
+    assert indices_steps is None or indices_steps.shape == (T, N, M)
+    assert cov is None or cov.shape == (T, N, d, d)
+    assert unique is None or unique.shape == (T, N)
+    a = MmfPfSmoothArgs()
+    a.T, a.N, a.M, a.d, a.lag = T, N, M, d, int(lag)
+    a.states_steps, a.loglik_steps, a.logw_in_steps, a.logw_in0 = vp(states_steps), vp(loglik_steps), vp(logw_in_steps), vp(logw_in0)
+    a.indices_steps, a.mean, a.cov, a.unique = vp(indices_steps, torch.int32), vp(mean), vp(cov), vp(unique, torch.int32)
+    with _on(states_steps):
+        _check(load().mmf_pf_smooth(ctypes.byref(a), stream_of(states_steps)), "mmf_pf_smooth")

@@ -14,8 +14,13 @@
 // gathering (mmf_pf_resample_runs), the dynamics launch of steps 1 .. T-1 consumes it (mmf_pf_dynamics_runs) reading the
 // ancestors' rows from the buffer the previous step propagated; step 0's dynamics (the incoming belief is a full particle
 // set) and step T-1's K1 (the belief the caller sees is complete) are the kernels of every other loop.  Same bits.
+// h (mmf_pf_forward_loop_history): the same launches with other pointers.  Step t propagates into slice t of
+// h->states_steps (`prop`) instead of `other`, K1 still gathers into `cur` -- a scratch buffer, never a history slice --, and
+// where a step reads what the previous one PROPAGATED (no resampling, the run table) it reads slice t - 1 (`rd`).  `cur` /
+// `other` / `lw_cur` / `lw_other` keep swapping as names, so final_location is what it is without a history.  Same bits.
 static int pf_enqueue_steps(const MmfPfLoopArgs* a, void* stream, bool with_events, float ess_threshold = 0.f,
-                            int32_t* resampled_steps = nullptr, const MmfPfDedupWorkspace* ws = nullptr) {
+                            int32_t* resampled_steps = nullptr, const MmfPfDedupWorkspace* ws = nullptr,
+                            const MmfPfHistory* h = nullptr) {
   if (!a) return MMF_EINVAL;
   const bool adaptive = ess_threshold > 0.f;
   if (a->T < 0 || a->N < 1 || a->M < 1 || a->n_meas < 1 || a->n_meas > MMF_LOOP_MAX_MEAS) return MMF_EINVAL;
@@ -36,6 +41,13 @@ static int pf_enqueue_steps(const MmfPfLoopArgs* a, void* stream, bool with_even
   float* lw_cur = a->logw_a;
   float* lw_other = a->logw_b;
   hipStream_t hs = static_cast<hipStream_t>(stream);
+  if (h) {  // the belief's log-weights on entry: step 0's slice and the copy of its own
+    const size_t bytes = nm * sizeof(float);
+    hipError_t e = hipMemcpyAsync(h->logw_in0, lw_cur, bytes, hipMemcpyDeviceToDevice, hs);
+    if (e == hipSuccess && h->logw_in_steps && a->T > 0)
+      e = hipMemcpyAsync(h->logw_in_steps, lw_cur, bytes, hipMemcpyDeviceToDevice, hs);
+    if (e != hipSuccess) return static_cast<int>(e);
+  }
   int ev = 0;  // optional timing events: [sample][dynamics, measure x n_meas, resample][start, end]
   const int stride = a->event_stride > 1 ? a->event_stride : 1;
   bool sampled = false;  // an event record costs a barrier packet: long loops sample every stride-th step
@@ -52,22 +64,29 @@ static int pf_enqueue_steps(const MmfPfLoopArgs* a, void* stream, bool with_even
     if ((rc = mark())) return rc;
     const bool runs_in = runs && t > 0;            // the previous step left a run table and its propagated rows in `cur`
     const bool runs_out = runs && t + 1 < a->T;    // this step leaves them for the next
+    const size_t slice = static_cast<size_t>(t) * nm * a->d;
+    float* prop = h ? h->states_steps + slice : other;  // where this step's propagated set lives
+    // what the dynamics launch reads: a gathered set in `cur`, or -- with a history -- the slice the previous step propagated
+    const float* rd = h && t > 0 && (a->resample_mode == 0 || runs_in) ? h->states_steps + (slice - nm * a->d) : cur;
+    // the log-weights K1 starts from and leaves: with a history, slices t and t + 1 (the last step's go where they always went)
+    const float* lw_in = h && h->logw_in_steps && t > 0 ? h->logw_in_steps + t * nm : lw_cur;
+    float* lw_out = h && h->logw_in_steps && t + 1 < a->T ? h->logw_in_steps + (t + 1) * nm : lw_other;
     if (runs_in && a->noise_mode == 2)
-      rc = mmf_pf_dynamics_runs_philox(a->dyn_packed, a->n_res_dyn, a->precision, cur, a->dyn_bias + t * row * MMF_UNITS,
+      rc = mmf_pf_dynamics_runs_philox(a->dyn_packed, a->n_res_dyn, a->precision, rd, a->dyn_bias + t * row * MMF_UNITS,
                                        a->noise_seed, a->noise_step0 + static_cast<unsigned>(t), a->noise_traj0, a->scale_tril,
-                                       ws->rank, ws->run_anc, ws->run_start, ws->n_runs, other, a->range_flag, a->N, a->M,
+                                       ws->rank, ws->run_anc, ws->run_start, ws->n_runs, prop, a->range_flag, a->N, a->M,
                                        a->d, stream);
     else if (runs_in)
-      rc = mmf_pf_dynamics_runs(a->dyn_packed, a->n_res_dyn, a->precision, cur, a->dyn_bias + t * row * MMF_UNITS,
+      rc = mmf_pf_dynamics_runs(a->dyn_packed, a->n_res_dyn, a->precision, rd, a->dyn_bias + t * row * MMF_UNITS,
                                 a->noise + t * nm * a->d, a->scale_tril, ws->rank, ws->run_anc, ws->run_start, ws->n_runs,
-                                other, a->range_flag, a->N, a->M, a->d, stream);
+                                prop, a->range_flag, a->N, a->M, a->d, stream);
     else if (a->noise_mode == 2)
-      rc = mmf_pf_dynamics_philox(a->dyn_packed, a->n_res_dyn, a->precision, cur, a->dyn_bias + t * row * MMF_UNITS,
+      rc = mmf_pf_dynamics_philox(a->dyn_packed, a->n_res_dyn, a->precision, rd, a->dyn_bias + t * row * MMF_UNITS,
                                   a->noise_seed, a->noise_step0 + static_cast<unsigned>(t), a->noise_traj0, a->scale_tril,
-                                  other, a->range_flag, a->N, a->M, a->d, stream);
+                                  prop, a->range_flag, a->N, a->M, a->d, stream);
     else
-      rc = mmf_pf_dynamics(a->dyn_packed, a->n_res_dyn, a->precision, cur, a->dyn_bias + t * row * MMF_UNITS,
-                           a->noise + t * nm * a->d, a->scale_tril, other, a->range_flag, a->N, a->M, a->d,
+      rc = mmf_pf_dynamics(a->dyn_packed, a->n_res_dyn, a->precision, rd, a->dyn_bias + t * row * MMF_UNITS,
+                           a->noise + t * nm * a->d, a->scale_tril, prop, a->range_flag, a->N, a->M, a->d,
                            stream);
     if (rc) return rc;
     if ((rc = mark())) return rc;
@@ -78,7 +97,7 @@ static int pf_enqueue_steps(const MmfPfLoopArgs* a, void* stream, bool with_even
       for (int k = 0; k < a->n_meas; ++k) {
         const float* lw = a->meas_logw[k] ? a->meas_logw[k] + t * row * a->logw_stride : nullptr;
         if ((rc = mark())) return rc;
-        rc = mmf_pf_measure(a->meas_packed[k], a->n_res_meas, a->precision, other,
+        rc = mmf_pf_measure(a->meas_packed[k], a->n_res_meas, a->precision, prop,
                             a->meas_bias[k] + t * row * MMF_UNITS, lw, a->logw_stride, ll, k > 0,
                             a->range_flag, a->N, a->M, a->d, stream);
         if (rc) return rc;
@@ -94,7 +113,7 @@ static int pf_enqueue_steps(const MmfPfLoopArgs* a, void* stream, bool with_even
       // the particle with the largest pre-resampling weight; K1's weighted mean goes to the scratch.  In the plain
       // resampling loop the incoming weights are uniform from the second step on (see below)
       const bool uniform_in = a->resample_mode != 0 && !soft && !adaptive && t > 0;
-      rc = mmf_pf_argmax_estimate(ll, uniform_in ? nullptr : lw_cur, other, est, a->N, a->M, a->d, stream);
+      rc = mmf_pf_argmax_estimate(ll, uniform_in ? nullptr : lw_in, prop, est, a->N, a->M, a->d, stream);
       if (rc) return rc;
       est = a->estimate_scratch;
     }
@@ -102,25 +121,27 @@ static int pf_enqueue_steps(const MmfPfLoopArgs* a, void* stream, bool with_even
     if (adaptive) {
       // a kept trajectory carries its weights forward, so the log-weights travel every step (as with soft resampling)
       const float* u = a->uniforms + t * (a->resample_mode == 1 ? row : nm);
-      rc = mmf_pf_reweight_resample_adaptive(ll, lw_cur, other, u, est, cur, lw_other, anc, a->N, a->M, a->d, a->resample_mode,
+      rc = mmf_pf_reweight_resample_adaptive(ll, lw_in, prop, u, est, cur, lw_out, anc, a->N, a->M, a->d, a->resample_mode,
                                              soft ? a->soft_alpha : 1.0f, ess_threshold,
                                              resampled_steps ? resampled_steps + t * row : nullptr, cov, ess, lev, stream);
       if (rc) return rc;
     } else if (soft) {
       // torchfilter's soft resampling: survivors carry importance weights, so the log-weights travel every step
       const float* u = a->uniforms + t * (a->resample_mode == 1 ? row : nm);
-      rc = mmf_pf_reweight_resample_belief(ll, lw_cur, other, u, est, cur, lw_other, anc, a->N, a->M, a->M, a->d,
+      rc = mmf_pf_reweight_resample_belief(ll, lw_in, prop, u, est, cur, lw_out, anc, a->N, a->M, a->M, a->d,
                                            a->resample_mode, a->soft_alpha, cov, ess, lev, stream);
       if (rc) return rc;
     } else if (a->resample_mode == 0) {
-      rc = mmf_pf_reweight_resample_belief(ll, lw_cur, other, nullptr, est, nullptr, lw_other, nullptr, a->N,
+      rc = mmf_pf_reweight_resample_belief(ll, lw_in, prop, nullptr, est, nullptr, lw_out, nullptr, a->N,
                                            a->M, a->M, a->d, 0, 1.0f, cov, ess, lev, stream);
       if (rc) return rc;
       float* s = cur; cur = other; other = s;  // propagated particles are the new belief
     } else if (runs_out) {
       // the run table instead of the gathered particles: the propagated rows stay where they are and become `cur`
       // (the incoming weights are uniform from the second step on and no step but the last writes them: see below)
-      rc = mmf_pf_resample_runs(ll, t == 0 ? lw_cur : nullptr, other, a->uniforms + t * row, est, nullptr, anc, ws->rank,
+      // (a history that keeps the log-weights has the uniform -log M written into its next slice)
+      rc = mmf_pf_resample_runs(ll, t == 0 ? lw_cur : nullptr, prop, a->uniforms + t * row, est,
+                                h && h->logw_in_steps ? lw_out : nullptr, anc, ws->rank,
                                 ws->run_anc, ws->run_start, ws->n_runs, a->N, a->M, a->d, cov, ess, lev, stream);
       if (rc) return rc;
       float* s = cur; cur = other; other = s;
@@ -129,13 +150,19 @@ static int pf_enqueue_steps(const MmfPfLoopArgs* a, void* stream, bool with_even
       // every step of this loop resamples, so from the second step on the incoming weights are the
       // uniform -log M the previous step would have written, and only the last step's are ever read
       // again: 8 of the 40 B per particle-step stay out of HBM
-      rc = mmf_pf_reweight_resample_belief(ll, t == 0 ? lw_cur : nullptr, other, u, est, cur,
-                                           t == a->T - 1 ? lw_other : nullptr, anc, a->N, a->M, a->M, a->d,
+      rc = mmf_pf_reweight_resample_belief(ll, t == 0 ? lw_cur : nullptr, prop, u, est, cur,
+                                           t == a->T - 1 || (h && h->logw_in_steps) ? lw_out : nullptr, anc, a->N, a->M, a->M, a->d,
                                            a->resample_mode, 1.0f, cov, ess, lev, stream);
       if (rc) return rc;  // resampled particles land back in `cur`
     }
     if ((rc = mark())) return rc;
     float* l = lw_cur; lw_cur = lw_other; lw_other = l;
+  }
+  if (h && a->resample_mode == 0 && a->T > 0) {
+    // no step gathered: the belief is the last slice of the history; one copy puts it where final_location says
+    const hipError_t e = hipMemcpyAsync(cur, h->states_steps + static_cast<size_t>(a->T - 1) * nm * a->d,
+                                        nm * a->d * sizeof(float), hipMemcpyDeviceToDevice, hs);
+    if (e != hipSuccess) return static_cast<int>(e);
   }
   // tell the caller where the belief ended up: bit 0 = states in states_b, bit 1 = log-weights in logw_b
   if (a->final_location)
@@ -182,6 +209,21 @@ extern "C" int mmf_pf_forward_loop_adaptive(const MmfPfLoopArgs* a, float ess_th
     a = &launches;
   }
   return pf_enqueue_steps(a, stream, true, ess_threshold, resampled_steps);
+}
+
+// The loop that keeps its history for mmf_pf_smooth (include/mmf.h): always the loop of launches -- the persistent form
+// keeps no per-step arrays, as with indices_steps -- whichever of the three loops above the other arguments select.
+extern "C" int mmf_pf_forward_loop_history(const MmfPfLoopArgs* a, const MmfPfHistory* h, float ess_threshold,
+                                           int32_t* resampled_steps, const MmfPfDedupWorkspace* ws, void* stream) {
+  if (!a || !h || !h->states_steps || !h->logw_in0 || !a->loglik_steps) return MMF_EINVAL;
+  if (a->resample_mode != 0 && !a->indices_steps) return MMF_EINVAL;
+  const bool adaptive = ess_threshold != 0.f;
+  if (adaptive && (a->resample_mode == 0 || !(ess_threshold > 0.f && ess_threshold <= 1.f))) return MMF_EINVAL;
+  const bool soft = a->resample_mode != 0 && a->soft_alpha > 0.f && a->soft_alpha < 1.f;
+  if ((a->resample_mode == 0 || soft || adaptive) && !h->logw_in_steps) return MMF_EINVAL;  // the weights travel
+  MmfPfLoopArgs launches = *a;
+  launches.persistent = 0;
+  return pf_enqueue_steps(&launches, stream, true, adaptive ? ess_threshold : 0.f, adaptive ? resampled_steps : nullptr, ws, h);
 }
 
 // Open-loop rollout x_t = f(x_{t-1}, u_t): replaces torchfilter's DynamicsModel.forward_loop (call

@@ -13,11 +13,15 @@ START_TRUNCATION = 30
 
 
 def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale: float = 0.1,
-               measurement_initialize: bool = False, return_belief: bool = False):
+               measurement_initialize: bool = False, return_belief: bool = False, smooth_lag=False):
     """Initialise the belief at ``states[0]`` with covariance ``0.1 I`` (or from the first
     observation, ``eval_helpers.py:116-131``) and filter ``[1:]`` (``:139-142``).
     ``return_belief``: run with ``record_belief`` set and return ``(estimates, filter_model.last_belief)`` -- the per-step
-    posterior covariances (and the particle filter's ESS / log-evidence) for the calibration metrics below."""
+    posterior covariances (and the particle filter's ESS / log-evidence) for the calibration metrics below.
+    ``smooth_lag``: ``False`` (the default) leaves all of this as it is; an integer or ``None`` (the full smoother) runs a
+    particle filter with ``record_history`` set and returns ``filter_model.smooth(smooth_lag)`` -- the whole recorded
+    trajectory is at hand, so ``E[x_t | y_1..t+lag]`` is the better estimate -- and, with ``return_belief``, the smoothed
+    record ``filter_model.last_smoothed`` (``covariance``, ``unique``, ``lag``) in place of the filter's."""
     states = traj["states"]
     T1, N, d = states.shape
     obs = {k: traj[k] for k in ("image", "gripper_pos", "gripper_sensors")}
@@ -25,6 +29,11 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
     if return_belief:
         assert was is not None, f"{type(filter_model).__name__} keeps no belief to record"
         filter_model.record_belief = True
+    smoothing = smooth_lag is not False  # (0 is a lag)
+    if smoothing:
+        assert hasattr(filter_model, "record_history"), f"{type(filter_model).__name__} keeps no history to smooth"
+        was_history = filter_model.record_history
+        filter_model.record_history = True
     try:
         with torch.no_grad():
             if measurement_initialize and hasattr(filter_model, "measurement_initialize_beliefs"):
@@ -37,6 +46,11 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
     finally:
         if return_belief:
             filter_model.record_belief = was
+        if smoothing:
+            filter_model.record_history = was_history
+    if smoothing:
+        est = filter_model.smooth(smooth_lag)
+        return (est, filter_model.last_smoothed) if return_belief else est
     return (est, filter_model.last_belief) if return_belief else est
 
 

@@ -63,6 +63,12 @@ class ParticleFilter(base.Filter):
     ``log_evidence (N)`` (``include/mmf.h``, K1); after ``forward_loop`` with a leading ``T`` axis, written by the native
     loops themselves (the persistent launch included).  Training (autograd) paths compute it with detached torch ops
     from the particle tensors, step by step: correct, not fast.
+    ``record_history = True`` (evaluation only; setting it on a training-mode filter raises): ``forward_loop`` keeps what a
+    smoother needs in ``last_history`` (``base.history_record``: the propagated sets, log-likelihoods, incoming log-weights
+    and ancestors of every step, ``4 (d + 3)`` bytes per particle-step) -- the native loop writes it in place
+    (``mmf_pf_forward_loop_history``: the loop of launches; the persistent launch is skipped, as with ``record_indices``),
+    the step-by-step loop stacks the same tensors.  ``smooth(lag)`` then returns the ancestry-smoothed means
+    ``E[x_t | y_1..min(t + lag, T)]`` (``mmf_pf_smooth``).  Every other output of the loop has the same bits either way.
     Randomness comes from ``self.noise`` (``utils.NoiseSource``), never from global RNG state.
     """
 
@@ -97,6 +103,10 @@ class ParticleFilter(base.Filter):
         self.last_log_weights_in = None
         self.record_belief = False    # per-step covariance / ESS / log-evidence -> last_belief
         self.last_belief = None
+        self.record_history = False   # forward_loop keeps the per-step sets / weights / ancestors -> last_history, smooth()
+        self.last_history = None
+        self.last_smoothed = None
+        self._step_history = None
         self.use_native_loop = True   # False: forward_loop keeps the step-by-step Python loop
         self.particle_states: torch.Tensor = None
         self.particle_log_weights: torch.Tensor = None
@@ -112,6 +122,16 @@ class ParticleFilter(base.Filter):
     def resample_ess_threshold(self, value: Optional[float]) -> None:
         assert value is None or 0.0 < float(value) <= 1.0, "resample_ess_threshold must lie in (0, 1]"  # (a NaN fails too)
         self._resample_ess_threshold = None if value is None else float(value)
+
+    @property
+    def record_history(self) -> bool:
+        return self._record_history
+
+    @record_history.setter
+    def record_history(self, value: bool) -> None:
+        if value and self.training:
+            raise RuntimeError("record_history: the training (autograd) paths keep no history; call .eval() first")
+        self._record_history = bool(value)
 
     # ------------------------------------------------------------------ belief
     def initialize_beliefs(self, *, mean: torch.Tensor, covariance: torch.Tensor) -> None:
@@ -158,6 +178,8 @@ class ParticleFilter(base.Filter):
         # the run table of the native loop (engine.PF_DEDUP): rank (N, M), run_anc / run_start (N, M + 1), n_runs (N), int32
         per_step += 4 * dedup_workspace_words(batch, M)
         nbytes = steps * batch * per_row + 8 * per_step + (64 << 20)
+        if self.record_history:  # states, log-likelihoods, incoming log-weights, ancestors of every step
+            nbytes += steps * batch * M * 4 * (d + 3)
         reserve_memory(dev, nbytes)
         return nbytes
 
@@ -215,6 +237,8 @@ class ParticleFilter(base.Filter):
         N, M, d = self.particle_states.shape
         do_resample = (not self.training) if self.resample is None else bool(self.resample)
         if not do_resample and self.num_particles != M:
+            if self.record_history:  # (the adapted set is a re-indexing of the belief that no ancestor array records)
+                raise RuntimeError("record_history: a step that adapts the particle count without resampling keeps no ancestry")
             self._adapt_particle_count()
             N, M, d = self.particle_states.shape
 
@@ -224,6 +248,8 @@ class ParticleFilter(base.Filter):
             assert loglik.shape == (N, M)
             if self.record_indices:
                 self.last_log_likelihoods, self.last_log_weights_in = loglik, self.particle_log_weights
+            keep_history = self.record_history
+            lw_before = self.particle_log_weights
 
             estimate = torch.empty((N, d), dtype=torch.float32, device=states.device)
             rec = self._new_belief_record((N,), d, states.device) if self.record_belief else None
@@ -241,7 +267,7 @@ class ParticleFilter(base.Filter):
                     out = torch.empty((N, Mo, d), dtype=torch.float32, device=states.device)
                 logw_out = torch.empty((N, Mo), dtype=torch.float32, device=states.device)
                 idx = (torch.empty((N, Mo), dtype=torch.int32, device=states.device)
-                       if self.record_indices else None)
+                       if self.record_indices or keep_history else None)
                 lw_in = self.particle_log_weights
                 if thr is not None and Mo == M:
                     took = torch.empty((N,), dtype=torch.int32, device=states.device)
@@ -259,11 +285,16 @@ class ParticleFilter(base.Filter):
                 _timed("pf_reweight_resample", 0.0, N * M * 4.0 * (2 + d) + N * Mo * 4.0 * d, k1)
                 if thr is not None and Mo == M:
                     self.last_resampled = took.ne(0)
-                self._spare_states = states
-                self.last_resample_indices = idx
+                # (the history keeps `states`: it must not come back as the next step's output buffer)
+                self._spare_states = None if keep_history else states
+                self.last_resample_indices = idx if self.record_indices else None
+                self._step_history = (states, loglik, lw_before, idx) if keep_history else None
             else:
+                self._step_history = (states, loglik, lw_before, None) if keep_history else None
                 out, logw_out = states, torch.empty_like(loglik)
-                if states.data_ptr() != self.particle_states.data_ptr():
+                if keep_history:
+                    self._spare_states = None  # the old belief is a slice of the history: the next step gets a new buffer
+                elif states.data_ptr() != self.particle_states.data_ptr():
                     self._spare_states = self.particle_states  # the old belief is the next scratch
                 if rec is None:
                     _abi.pf_reweight_resample(loglik, self.particle_log_weights, states, None, estimate,
@@ -427,13 +458,25 @@ class ParticleFilter(base.Filter):
         a.scale_tril, a.uniforms = P(tril), P(u)
         a.states_a, a.states_b, a.logw_a, a.logw_b = P(states_a), P(states_b), P(logw_a), P(logw_b)
         a.loglik, a.estimates = P(loglik), P(est)
-        if self.record_indices:
-            self.last_log_weights_in = logw_a.clone()
-            self.last_log_likelihoods = torch.empty((T, N, M), dtype=torch.float32, device=dev)
-            a.loglik_steps = P(self.last_log_likelihoods)
-            if mode != 0:
-                self.last_resample_indices = torch.empty((T, N, M), dtype=torch.int32, device=dev)
-                a.indices_steps = P(self.last_resample_indices, torch.int32)
+        history = hist = None
+        if self.record_indices or self.record_history:
+            ll_steps = torch.empty((T, N, M), dtype=torch.float32, device=dev)
+            idx_steps = torch.empty((T, N, M), dtype=torch.int32, device=dev) if mode != 0 else None
+            a.loglik_steps, a.indices_steps = P(ll_steps), P(idx_steps, torch.int32)
+            if self.record_indices:
+                self.last_log_weights_in = logw_a.clone()
+                self.last_log_likelihoods = ll_steps
+                if mode != 0:
+                    self.last_resample_indices = idx_steps
+            if self.record_history:  # the loop writes the propagated sets and the incoming log-weights in place
+                hist = base.history_record(states=torch.empty((T, N, M, d), dtype=torch.float32, device=dev),
+                                           log_likelihoods=ll_steps,
+                                           log_weights_in=torch.empty((T, N, M), dtype=torch.float32, device=dev),
+                                           ancestors=idx_steps, resampled=None)
+                logw_in0 = torch.empty_like(logw_a)
+                keep.append(logw_in0)
+                history = _abi.MmfPfHistory()
+                history.states_steps, history.logw_in_steps, history.logw_in0 = P(hist.states), P(hist.log_weights_in), P(logw_in0)
         self.last_belief = None
         if self.record_belief:  # written by K1 in every form of the loop; does not change which form runs
             self.last_belief = rec = self._new_belief_record((T, N), d, dev)
@@ -459,7 +502,7 @@ class ParticleFilter(base.Filter):
         timer = engine.kernel_timer()
         # small problem: ONE launch for all T steps (csrc/pf_persistent.inc); same bits as the loop of launches
         # (ESS-triggered resampling does not change eligibility: the K1 role takes the adaptive branch)
-        go = (engine.PF_PERSISTENT and mode == 1 and timer is None and not self.record_indices
+        go = (engine.PF_PERSISTENT and mode == 1 and timer is None and not self.record_indices and history is None
               and a.soft_alpha == 0.0 and not a.estimate_argmax and d in (2, 3)
               and dyn._net.n_res == 3 and all(net.n_res == 2 for net, _b, _l in nets)
               and _abi.pf_persistent_plan(N, M, len(nets)) > 0)
@@ -472,7 +515,8 @@ class ParticleFilter(base.Filter):
         # the persistent launch needs ALL its workgroups resident; if it gives up (another process on this GPU) the belief
         # is restored and the loop re-run as launches, for this call and for the rest of the process (engine.run_persistent)
         loc = engine.run_persistent(a, lambda: _abi.pf_forward_loop(a, like, events, stride, ess_threshold=thr,
-                                                                    resampled_steps=took, dedup=dedup), device=dev,
+                                                                    resampled_steps=took, dedup=dedup, history=history),
+                                    device=dev,
                                     n_sync_words=_abi.pf_persistent_sync_words(N, M, d, len(nets)) if go else 0,
                                     restore=(states_a, logw_a))
         if timer is not None:
@@ -491,6 +535,9 @@ class ParticleFilter(base.Filter):
             self.last_resampled = None
         else:
             self.last_resampled = took.ne(0) if took is not None else torch.zeros((T, N), dtype=torch.bool, device=dev)
+        if hist is not None:
+            hist.resampled = self.last_resampled
+        self.last_history = hist
         del keep
         return est
 
@@ -539,16 +586,53 @@ class ParticleFilter(base.Filter):
     def _loop_of_steps(self, T, step, N):
         """``forward_loop`` step by step: ``step(t, rows of step t in the T*N flattened arrays)``; the per-step records
         (``last_belief``, ``last_resampled``) are stacked along a leading ``T`` axis."""
-        out, beliefs, took = [], [], []
+        out, beliefs, took, hist = [], [], [], []
         for t in range(T):
             out.append(step(t, slice(t * N, (t + 1) * N)))
             beliefs.append(self.last_belief)
             took.append(self.last_resampled)
+            hist.append(self._step_history)
         if self.record_belief:
             self.last_belief = base.stack_belief_records(beliefs)
         if took and took[0] is not None:
             self.last_resampled = torch.stack(took, dim=0)
+        self.last_history = None
+        if self.record_history and T > 0:
+            st, ll, lw, anc = zip(*hist)
+            # a resampling step that changes the particle count (num_particles differs from the belief's): every array is
+            # padded to the largest count with particles of log-likelihood -inf -- dead paths, which carry no weight and
+            # are not counted -- whose ancestor is particle 0
+            Mh = max(x.shape[1] for x in st)
+            pad = lambda x, fill: x if x.shape[1] == Mh else torch.cat(
+                [x, x.new_full((x.shape[0], Mh - x.shape[1]) + tuple(x.shape[2:]), fill)], dim=1)
+            self.last_history = base.history_record(
+                states=torch.stack([pad(x, 0.0) for x in st]), log_likelihoods=torch.stack([pad(x, -math.inf) for x in ll]),
+                log_weights_in=torch.stack([pad(x, -math.inf) for x in lw]),
+                ancestors=None if anc[0] is None else torch.stack([pad(x, 0) for x in anc]), resampled=self.last_resampled)
+        self._step_history = None
         return torch.stack(out, dim=0)
+
+    def smooth(self, lag: Optional[int] = None) -> torch.Tensor:
+        """Ancestry (genealogy) smoothing of the last ``forward_loop`` run with ``record_history`` set: ``(T, N, d)`` means
+        of ``E[x_t | y_1..s(t)]``, ``s(t) = min(t + lag, T - 1)`` -- every particle of the endpoint ``s`` is traced back
+        through the ancestors to the particle of step ``t`` it descends from, and the moments of those are taken under the
+        endpoint's weights (``mmf_pf_smooth``, ``include/mmf.h``).  ``lag = None`` (or ``>= T - 1``): the full smoother;
+        ``lag = 0``: the filter's own weighted set.  Leaves ``last_smoothed``: ``covariance (T, N, d, d)``, ``unique (T, N)``
+        int32 -- the distinct particles of step ``t`` still alive on the endpoint's paths; where it drops to a handful the
+        genealogy has collapsed and a shorter lag trades bias for variance -- and ``lag``.  The smoothed estimate is the
+        weighted MEAN also where ``estimation_method == "argmax"`` makes the filter report another point."""
+        h = self.last_history
+        assert h is not None, "smooth() needs a history: set record_history and run forward_loop (evaluation mode) first"
+        assert lag is None or int(lag) >= 0, "lag must be >= 0 (None: the full smoother)"
+        T, N, M, d = h.states.shape
+        dev = h.states.device
+        mean = torch.empty((T, N, d), dtype=torch.float32, device=dev)
+        cov = torch.empty((T, N, d, d), dtype=torch.float32, device=dev)
+        unique = torch.empty((T, N), dtype=torch.int32, device=dev)
+        _abi.pf_smooth(h.states, h.log_likelihoods, h.log_weights_in, None, h.ancestors,
+                       max(T - 1, 0) if lag is None else min(int(lag), max(T - 1, 0)), mean, cov, unique)
+        self.last_smoothed = base.belief_record(covariance=cov, unique=unique, lag=lag)
+        return mean
 
     @engine.checked_step
     def forward(self, *, observations, controls) -> torch.Tensor:
@@ -566,6 +650,8 @@ class ParticleFilter(base.Filter):
         assert tree_leading_shape(observations)[:2] == (T, N)
         flat = lambda x: x.reshape((T * N,) + tuple(x.shape[2:]))
         if use_autograd(self):
+            if self.record_history:
+                raise RuntimeError("record_history: the training (autograd) paths keep no history; call .eval() first")
             if not engine.use_hip_backward():
                 return self._loop_of_steps(T, lambda t, sl: self(
                     observations=tree_index(observations, t), controls=tree_index(controls, t)), N)
