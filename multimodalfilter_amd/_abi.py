@@ -785,6 +785,29 @@ def pf_resample_runs(loglik, logw_in, states, u, estimate, indices_out, rank, ru
                                            ptr(log_evidence), stream_of(states)), "mmf_pf_resample_runs")
 
 
+def pf_dynamics_runs(packed, n_res, precision, states_prev, traj_bias, noise, scale_tril, rank, run_anc, run_start, n_runs,
+                     states_out, range_flag, N, M, d):
+    """The run-consuming dynamics launch alone (``mmf_pf_dynamics_runs``): the network once per run of the table."""
+    i32 = torch.int32
+    with _on(states_prev):
+        _check(load().mmf_pf_dynamics_runs(ptr(packed), n_res, precision, ptr(states_prev), ptr(traj_bias), ptr(noise),
+                                           ptr(scale_tril), ptr(rank, dtype=i32), ptr(run_anc, dtype=i32),
+                                           ptr(run_start, dtype=i32), ptr(n_runs, dtype=i32), ptr(states_out),
+                                           ptr(range_flag, dtype=i32), N, M, d, stream_of(states_prev)),
+               "mmf_pf_dynamics_runs")
+
+
+def pf_dynamics_runs_philox(packed, n_res, precision, states_prev, traj_bias, seed, step, traj0, scale_tril, rank, run_anc,
+                            run_start, n_runs, states_out, range_flag, N, M, d):
+    i32 = torch.int32
+    with _on(states_prev):
+        _check(load().mmf_pf_dynamics_runs_philox(ptr(packed), n_res, precision, ptr(states_prev), ptr(traj_bias), seed, step,
+                                                  traj0, ptr(scale_tril), ptr(rank, dtype=i32), ptr(run_anc, dtype=i32),
+                                                  ptr(run_start, dtype=i32), ptr(n_runs, dtype=i32), ptr(states_out),
+                                                  ptr(range_flag, dtype=i32), N, M, d, stream_of(states_prev)),
+               "mmf_pf_dynamics_runs_philox")
+
+
 def pf_forward_loop(args: MmfPfLoopArgs, like: torch.Tensor, events=None, event_stride: int = 1, *,
                     ess_threshold: float = None, resampled_steps=None, dedup: MmfPfDedupWorkspace = None,
                     history: MmfPfHistory = None) -> int:

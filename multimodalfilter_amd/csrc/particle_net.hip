@@ -369,10 +369,50 @@ __global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(std::condi
   const int wave_global = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
   const int waves_total = gridDim.x * kWavesPerBlock;
   const int ntiles = (a.R + TILE - 1) / TILE;
+  // index i of a workgroup's tile list -> tile (the claims below)
+  auto tile_of = [&](int i) { return (i / kWavesPerBlock) * waves_total + blockIdx.x * kWavesPerBlock + i % kWavesPerBlock; };
+  // RUNS: whether a tile holds runs is asked of n_runs[its trajectory] for every index of the workgroup's list, about half of
+  // them empty tiles whose answer is all the wave wants before it claims again.  The list's n_runs are fetched once, by the
+  // whole workgroup, ahead of the weight copy (their latency sits under it), and published in the LDS the blob leaves free
+  // with the barrier that publishes the weights; a list longer than kProbeCap keeps the scalar load per index.
+  constexpr int kProbeRegs = 4;                      // entries fetched per thread
+  constexpr int kProbeCap = kProbeRegs * kThreads;   // 2048: 8 KB of the 10.7 KB beside the blob (256 entries at 1024 x 4096, 64 at the headline)
+  static_assert(!RUNS || (blob_floats(NRES) + kProbeCap + 4) * sizeof(float) <= mmf::kLdsPerCu, "the probe list shares a CU's LDS with the blob");
+  const int n_traj = RUNS ? a.R / a.M : 1;
+  auto clamp_runs = [&](int nr) { return nr < 1 ? 1 : (nr > a.M ? a.M : nr); };  // what a table can hold
+  const int probe_len = RUNS ? (ntiles + waves_total - 1) / waves_total * kWavesPerBlock : 0;
+  const bool probe_lds = RUNS && probe_len <= kProbeCap;  // wave-uniform
+  int* probe = nullptr;
+  int probe_val[kProbeRegs];
+  if constexpr (RUNS) {
+    __shared__ int s_probe[kProbeCap];
+    probe = s_probe;
+    if (probe_lds) {
+#pragma unroll
+      for (int r = 0; r < kProbeRegs; ++r) {
+        probe_val[r] = 0;
+        if (r * kThreads < probe_len) {
+          const int i = r * kThreads + static_cast<int>(threadIdx.x);
+          const int t = tile_of(i);
+          if (i < probe_len && t < ntiles) probe_val[r] = multi.rt.n_runs[t % n_traj];
+        }
+      }
+    }
+  }
+  auto publish_probe = [&]() {  // ahead of the barrier that ends the weight copy
+    if (probe_lds) {
+#pragma unroll
+      for (int r = 0; r < kProbeRegs; ++r) {
+        const int i = r * kThreads + static_cast<int>(threadIdx.x);
+        if (i < probe_len) probe[i] = clamp_runs(probe_val[r]);
+      }
+    }
+  };
   if constexpr (!ASYNC_STAGE) {
     const float4* src = reinterpret_cast<const float4*>(a.packed);
     float4* dst = reinterpret_cast<float4*>(lds);
     mmf::stage_to_lds<blob_floats(NRES) / 4, kThreads>(src, dst, threadIdx.x);
+    if constexpr (RUNS) publish_probe();
     __syncthreads();
   } else {
     const float4* src = reinterpret_cast<const float4*>(a.packed);
@@ -380,6 +420,7 @@ __global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(std::condi
     static_assert(off_layers() % 256 == 0 && off_bias(NRES) % 4 == 0 && blob_floats(NRES) % 4 == 0, "16-byte sections, 1 KB pieces");
     for (int i = threadIdx.x; i < off_layers() / 4; i += kThreads) dst[i] = src[i];
     for (int i = off_bias(NRES) / 4 + threadIdx.x; i < blob_floats(NRES) / 4; i += kThreads) dst[i] = src[i];
+    if constexpr (RUNS) publish_probe();  // (published by the barrier that follows the DMAs' issue)
   }
 
   // -1.0f in an SGPR, opaque to the optimiser (see split_pair); the asm emits no instruction
@@ -391,8 +432,7 @@ __global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(std::condi
   // (~1-2 k cycles with nothing else to issue), 8 times per wave at the headline size.
   constexpr int KS0 = (D + 2) / 2;
   // RUNS: tile = q N + traj; its columns are runs TILE q .. TILE q + TILE - 1 of the trajectory (wave-uniform bookkeeping)
-  const int n_traj = RUNS ? a.R / a.M : 1;
-  auto runs_of = [&](int tile, int& q, int& traj) {  // -> n_runs of the tile's trajectory, clamped to what a table can hold
+  auto run_tile = [&](int tile, int& q, int& traj) {
     q = tile / n_traj;
     traj = tile - q * n_traj;
     // ... rotated by the trajectory: a workgroup's index list visits a handful of consecutive trajectories at q's that are
@@ -400,15 +440,42 @@ __global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(std::condi
     // (5 of 8 rounds against 4 of 8 at 256 x 4096 with 35 real tiles per trajectory); with it the trajectories of a
     // workgroup cover every residue.  A bijection per trajectory: every (traj, q) is still visited exactly once.
     q = (q + traj) % (a.M / TILE);
+  };
+  auto runs_of = [&](int tile, int& q, int& traj) {  // -> n_runs of the tile's trajectory (one scalar load), clamped
+    run_tile(tile, q, traj);
     int nr = 0;
     if constexpr (RUNS) nr = multi.rt.n_runs[traj];
-    nr = nr < 1 ? 1 : (nr > a.M ? a.M : nr);
-    return nr;
+    return clamp_runs(nr);
   };
-  auto first_layer_inputs = [&](int tile, float (&b)[KS0][CT]) {
+  // RUNS: with a tile's first-layer inputs come the two things its epilogue would otherwise fetch in a dependent chain of
+  // its own after the last layer -- the ancestor of the lane's OWN run (column h of the lane's two: run 32 h + j = lane) and
+  // the tile's first / one-past-last output slot (run_start[r0] in the even lanes, run_start[r1] in the odd ones: a vector
+  // load, so that no LDS wait of the layers has to wait for a scalar one)
+  int anc_next = 0, slots_next = 0;
+  auto first_layer_inputs = [&](int tile, float (&b)[KS0][CT], int run_n = 0) {  // run_n: the clamped n_runs of the tile's trajectory
     const int base = tile * TILE;
-    int run_q = 0, run_traj = 0, run_n = 0;
-    if constexpr (RUNS) run_n = runs_of(tile, run_q, run_traj);
+    int run_q = 0, run_traj = 0;
+    int run_row[CT];
+    if constexpr (RUNS) {
+      run_tile(tile, run_q, run_traj);
+      const size_t tab = static_cast<size_t>(run_traj) * (a.M + 1);
+#pragma unroll
+      for (int c = 0; c < CT; ++c) {  // columns past the trajectory's last run repeat it (and are not expanded)
+        int run = run_q * TILE + 32 * c + j;
+        run = run < run_n ? run : run_n - 1;
+        int anc = multi.rt.run_anc[tab + run];
+        anc = anc < 0 ? 0 : (anc < a.M ? anc : a.M - 1);
+        run_row[c] = anc;
+      }
+      int lo_col = run_row[0], hi_col = run_row[CT - 1];  // (pinned: see the epilogue's `mine`)
+      asm volatile("" : "+v"(lo_col), "+v"(hi_col));
+      anc_next = h ? hi_col : lo_col;
+      const int r0 = run_q * TILE;
+      const int r1 = r0 + TILE < run_n ? r0 + TILE : run_n;
+      slots_next = multi.rt.run_start[tab + ((lane & 1) ? r1 : r0)];
+#pragma unroll
+      for (int c = 0; c < CT; ++c) run_row[c] += run_traj * a.M;
+    }
 #pragma unroll
     for (int s = 0; s < KS0; ++s) {
       const int comp = 2 * s + h;
@@ -416,13 +483,7 @@ __global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(std::condi
       for (int c = 0; c < CT; ++c) {
         int row = base + 32 * c + j;
         row = row < a.R ? row : a.R - 1;
-        if constexpr (RUNS) {  // columns past the trajectory's last run repeat it (and are not expanded)
-          int run = run_q * TILE + 32 * c + j;
-          run = run < run_n ? run : run_n - 1;
-          int anc = multi.rt.run_anc[static_cast<size_t>(run_traj) * (a.M + 1) + run];
-          anc = anc < 0 ? 0 : (anc < a.M ? anc : a.M - 1);
-          row = run_traj * a.M + anc;
-        }
+        if constexpr (RUNS) row = run_row[c];
         float v;
         if (JAC) {
           const int role = row & 3;
@@ -436,17 +497,15 @@ __global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(std::condi
     }
   };
   float bnext[KS0][CT];
-  // RUNS: is there anything in this tile?  (one scalar load)
-  auto tile_real = [&](int tile) {
-    int q, traj;
-    const int nr = runs_of(tile, q, traj);
-    return q * TILE < nr;
-  };
+  // RUNS: is there anything in tile q of a trajectory with nr runs?
+  auto tile_real = [&](int q, int nr) { return q * TILE < nr; };
   bool first_pending = false;  // RUNS, wave-uniform: the wave's first tile is empty -- it looks for a real one once claims work
   if constexpr (RUNS) {
     const int t0 = __builtin_amdgcn_readfirstlane(wave_global);  // (the wave id is uniform, but not provably so)
     if (t0 < ntiles) {
-      if (tile_real(t0)) first_layer_inputs(t0, bnext);
+      int q, traj;
+      const int nr = runs_of(t0, q, traj);  // (the list in LDS is not published yet)
+      if (tile_real(q, nr)) first_layer_inputs(t0, bnext, nr);
       else first_pending = true;
     }
   } else {
@@ -462,6 +521,7 @@ __global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(std::condi
     for (int s = 0; s < KS0; ++s)
 #pragma unroll
       for (int c = 0; c < CT; ++c) asm volatile("" : "+v"(bnext[s][c]));
+    if constexpr (RUNS) asm volatile("" : "+v"(anc_next), "+v"(slots_next));
     const unsigned lds_base = static_cast<unsigned>(reinterpret_cast<uintptr_t>(lds)) + off_layers() * 4;
     const unsigned char* gsrc = reinterpret_cast<const unsigned char*>(a.packed + off_layers()) + lane * 16;
     const int wv = threadIdx.x >> 6;
@@ -506,7 +566,6 @@ __global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(std::condi
       __syncthreads();
     }
   }
-  auto tile_of = [&](int i) { return (i / kWavesPerBlock) * waves_total + blockIdx.x * kWavesPerBlock + i % kWavesPerBlock; };
   auto claim = [&](int after) {
     if (!claims) return after + kWavesPerBlock;  // the fixed stride
     int v = 0;
@@ -515,14 +574,19 @@ __global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(std::condi
   };
   int i_next = (threadIdx.x >> 6) + kWavesPerBlock;  // the second round is still dealt: its inputs are requested below
   // RUNS: claim until a tile that holds runs turns up, and request ITS inputs (the claim-one-ahead prefetch, for real tiles
-  // only: an empty tile costs its claim and one scalar load).  Returns >= ntiles when the workgroup's list is exhausted.
+  // only: an empty tile costs its claim and one LDS read).  Returns >= ntiles when the workgroup's list is exhausted.
   auto advance = [&]() {
     for (;;) {
-      const int t = __builtin_amdgcn_readfirstlane(tile_of(i_next));
+      const int i = i_next;
+      const int t = __builtin_amdgcn_readfirstlane(tile_of(i));
       i_next = claim(i_next);
-      if (t >= ntiles) return t;
-      if (tile_real(t)) {
-        first_layer_inputs(t, bnext);
+      if (t >= ntiles) return t;  // (an index past the list lands here: i >= probe_len -> t >= ntiles)
+      int q, traj;
+      run_tile(t, q, traj);
+      int nr = 0;
+      if constexpr (RUNS) nr = probe_lds ? __builtin_amdgcn_readfirstlane(probe[i]) : clamp_runs(multi.rt.n_runs[traj]);
+      if (tile_real(q, nr)) {
+        first_layer_inputs(t, bnext, nr);
         return t;
       }
     }
@@ -536,8 +600,8 @@ __global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(std::condi
   for (int tile = tile_first; tile < ntiles;) {
     int tile_next = RUNS ? 0 : tile_of(i_next);
     const int base = tile * TILE;
-    int run_q = 0, run_traj = 0, run_n = 0;  // RUNS
-    if constexpr (RUNS) run_n = runs_of(tile, run_q, run_traj);
+    int run_q = 0, run_traj = 0;  // RUNS
+    if constexpr (RUNS) run_tile(tile, run_q, run_traj);
     // column -> row / trajectory bookkeeping for the CT columns this lane feeds
     int col_row[CT], col_traj[CT];
     bool col_primal[CT];
@@ -558,8 +622,30 @@ __global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(std::condi
     for (int s = 0; s < KS0; ++s)
 #pragma unroll
       for (int c = 0; c < CT; ++c) bcur[s][c] = bnext[s][c];
+    // RUNS: what the epilogue reads that does not depend on the network -- the ancestor row of the lane's run and the first
+    // pass's rank / noise row -- requested here, behind the next tile's inputs: by the first wait of a layer (the join row, at
+    // layer 2) they are long back, so the in-order counter makes no layer wait for them; further passes load as they go
+    int slot_lo = 0, slot_hi = 0, rank_first = 0;
+    float xo_mine[D], eps_first[D];
     if constexpr (RUNS) {
+      const int anc_mine = anc_next, slots = slots_next;
       tile_next = advance();
+      slot_lo = __builtin_amdgcn_readlane(slots, 0);
+      slot_hi = __builtin_amdgcn_readlane(slots, 1);
+      slot_lo = slot_lo < 0 ? 0 : slot_lo;
+      slot_hi = slot_hi > a.M ? a.M : slot_hi;
+#pragma unroll
+      for (int i = 0; i < D; ++i) {
+        xo_mine[i] = a.states_in[(static_cast<size_t>(run_traj) * a.M + anc_mine) * D + i];
+        eps_first[i] = 0.f;
+      }
+      if (slot_lo < slot_hi) {
+        const int k = slot_lo + lane;
+        const size_t slot = static_cast<size_t>(run_traj) * a.M + (k < slot_hi ? k : slot_hi - 1);
+        rank_first = multi.rt.rank[slot];
+#pragma unroll
+        for (int i = 0; i < D; ++i) eps_first[i] = (a.noise_mode != 2 && a.noise) ? a.noise[slot * D + i] : 0.f;
+      }
     } else {
       if (tile_next < ntiles) first_layer_inputs(tile_next, bnext);
       i_next = claim(i_next);
@@ -682,35 +768,32 @@ __global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(std::condi
         a.loglik[my_row] = ll;
       }
     } else if constexpr (KIND == kDynamics && RUNS) {
-      // the lane's run: its ancestor's row, the noise-free half of the update; lanes past the last run repeat it
-      const size_t tab = static_cast<size_t>(run_traj) * (a.M + 1);
+      // the lane's run (run_q TILE + lane; lanes past the last run repeat it): its ancestor's row, requested at the tile's
+      // start, and the noise-free half of the update
       const int r0 = run_q * TILE;
-      const int r1 = r0 + TILE < run_n ? r0 + TILE : run_n;
-      int my_run = r0 + (CT == 2 ? lane : j);
-      my_run = my_run < run_n ? my_run : run_n - 1;
-      int anc = multi.rt.run_anc[tab + my_run];
-      anc = anc < 0 ? 0 : (anc < a.M ? anc : a.M - 1);
-      float xo[D], v0[D];
-#pragma unroll
-      for (int i = 0; i < D; ++i) xo[i] = a.states_in[(static_cast<size_t>(run_traj) * a.M + anc) * D + i];
-      dynamics_drift<D, PREC>(mine, bh, xo, v0);
+      float v0[D];
+      dynamics_drift<D, PREC>(mine, bh, xo_mine, v0);
       // the tile's output slots are contiguous: 64 per pass, every lane takes part in the exchange
-      int s0 = multi.rt.run_start[tab + r0], s1 = multi.rt.run_start[tab + r1];
-      s0 = s0 < 0 ? 0 : s0;
-      s1 = s1 > a.M ? a.M : s1;
+      const int s0 = slot_lo, s1 = slot_hi;
       const bool noisy = a.noise != nullptr || a.noise_mode == 2;
+      int slot_rank = rank_first;
+      float eps[D];
+#pragma unroll
+      for (int i = 0; i < D; ++i) eps[i] = eps_first[i];
       for (int kb = s0; kb < s1; kb += MMF_WAVE) {
         const int k = kb + lane;
         const bool live = k < s1;
         const int kk = live ? k : s1 - 1;
         const size_t slot = static_cast<size_t>(run_traj) * a.M + kk;
-        const int src = multi.rt.rank[slot] - r0;  // the lane that owns the slot's run
-        float v[D], eps[D], xn[D];
+        if (kb != s0) {  // (the first pass's were requested at the tile's start)
+          slot_rank = multi.rt.rank[slot];
 #pragma unroll
-        for (int i = 0; i < D; ++i) {
-          v[i] = __shfl(v0[i], src);
-          eps[i] = (a.noise_mode != 2 && a.noise) ? a.noise[slot * D + i] : 0.f;
+          for (int i = 0; i < D; ++i) eps[i] = (a.noise_mode != 2 && a.noise) ? a.noise[slot * D + i] : 0.f;
         }
+        const int src = slot_rank - r0;  // the lane that owns the slot's run
+        float v[D], xn[D];
+#pragma unroll
+        for (int i = 0; i < D; ++i) v[i] = __shfl(v0[i], src);
         dynamics_diffuse<D>(v, eps, a.scale_tril, noisy, a.noise_mode == 2, a.noise_seed, a.noise_step,
                             a.noise_traj0 + static_cast<unsigned>(run_traj), static_cast<unsigned>(kk), xn);
         if (live) {
