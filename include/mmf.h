@@ -577,6 +577,13 @@ int mmf_pf_dynamics_runs_philox(const float* packed, int n_res, int precision, c
                                 const float* scale_tril, const int32_t* rank, const int32_t* run_anc,
                                 const int32_t* run_start, const int32_t* n_runs, float* states_out, int* range_flag,
                                 int N, int M, int d, void* stream);
+/* How mmf_pf_dynamics_runs deals its real tiles where a workgroup builds a dense list of them (tiles are claimed, N <= 2048,
+ * at most 2048 entries per workgroup): a trajectory holds ceil(clamp(n_runs, 1, M) / tile) real tiles, the real tiles of
+ * the launch are numbered trajectory-major, and number k belongs to workgroup k mod grid.  Writes the first `cap` entries of
+ * workgroup b's list to `out` as tile numbers q' N + traj (tile q = (q' + traj) mod (M / tile) of trajectory traj) and
+ * returns the list's length.  HOST pointers; the kernel calls the same functions (csrc/particle_net_deal.h).  MMF_EINVAL:
+ * a null pointer, M % tile != 0, b outside [0, grid), N / M / tile / grid < 1.  Additive to ABI 42. */
+int mmf_pf_dedup_deal(const int32_t* n_runs, int N, int M, int tile, int grid, int b, int32_t* out, int cap);
 
 /* The step loop that KEEPS ITS HISTORY for particle smoothing (mmf_pf_smooth): the set every step propagated, the log-weights
  * every step's K1 started from, and -- through args->loglik_steps / args->indices_steps -- the log-likelihoods and the

@@ -198,6 +198,7 @@ SIGNATURES = {
                                      c_int, c_int, c_int, c_void_p]),
     "mmf_pf_dynamics_runs_philox": (c_int, [_FP, c_int, c_int, _FP, _FP, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
                                             _FP, _FP, _FP, _FP, _FP, _FP, _FP, c_int, c_int, c_int, c_void_p]),
+    "mmf_pf_dedup_deal": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int]),
     "mmf_pf_argmax_estimate": (c_int, [_FP, _FP, _FP, _FP, c_int, c_int, c_int, c_void_p]),
     "mmf_pf_persistent_plan": (c_int, [c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     "mmf_pf_persistent_sync_words": (c_size_t, [c_int, c_int, c_int, c_int]),
@@ -761,6 +762,14 @@ def pf_dedup_plan(M: int, d: int, resample_mode: int, soft_alpha: float = 0.0, r
 
 def pf_dedup_workspace_words(N: int, M: int) -> int:
     return int(load().mmf_pf_dedup_workspace_words(int(N), int(M)))
+
+
+def pf_dedup_deal(n_runs, N: int, M: int, tile: int, grid: int, b: int, out, cap: int) -> int:
+    """``mmf_pf_dedup_deal`` (include/mmf.h): workgroup ``b``'s list of real tiles of the run-consuming dynamics launch.
+    ``n_runs`` / ``out``: contiguous int32 numpy arrays on the HOST (or ``None``: the call refuses it).  Returns the list's
+    length, negative for a refused argument."""
+    p = lambda x: None if x is None else x.ctypes.data
+    return int(load().mmf_pf_dedup_deal(p(n_runs), int(N), int(M), int(tile), int(grid), int(b), p(out), int(cap)))
 
 
 def pf_dedup_workspace(words: torch.Tensor, N: int, M: int):

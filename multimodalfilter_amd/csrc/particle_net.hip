@@ -35,6 +35,7 @@
 #include "../../include/mmf_philox.h"
 
 #include "particle_net_tiles.h"
+#include "particle_net_deal.h"
 
 namespace {
 
@@ -336,6 +337,8 @@ struct NetArgsRuns {
   NetArgs a[1];
   RunTable rt;
 };
+// RUNS: places in the ring of expansion passes (the epilogue): the one being written and those requested ahead of it
+constexpr int kExpandAhead = 8;
 
 template <int D, int NRES, int KIND, int CT, int PREC, int WPS, bool PIPE = false, bool RUNS = false>
 __global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(std::conditional_t<RUNS, NetArgsRuns, NetArgsMulti> multi) {
@@ -377,16 +380,41 @@ __global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(std::condi
   // with the barrier that publishes the weights; a list longer than kProbeCap keeps the scalar load per index.
   constexpr int kProbeRegs = 4;                      // entries fetched per thread
   constexpr int kProbeCap = kProbeRegs * kThreads;   // 2048: 8 KB of the 10.7 KB beside the blob (256 entries at 1024 x 4096, 64 at the headline)
-  static_assert(!RUNS || (blob_floats(NRES) + kProbeCap + 4) * sizeof(float) <= mmf::kLdsPerCu, "the probe list shares a CU's LDS with the blob");
+  // DENSE mode (RUNS, where tiles are claimed): the workgroup does not walk tile_of()'s list, half of it empty tiles, but
+  // builds the list of its REAL tiles (particle_net_deal.h): every thread fetches kProbeRegs consecutive n_runs in place of
+  // the probe loads, a block-wide scan of the tiles per trajectory gives P[0 .. N) in the probe array, thread i finds entry
+  // i (dense index b + i G) by a search over P, and after a barrier the list is written over P.  No workgroup talks to
+  // another one; whatever the table holds, every thread passes the same four barriers.  The caps: P needs one word per
+  // trajectory and the list one per entry, both in the probe array -- N <= kDenseTrajCap and, for the longest list any
+  // table can give a workgroup, ceil(ntiles / G) <= kDenseListCap (256 x 4096: 64 entries, 1024 x 4096: 256); beyond
+  // either, and wherever tiles are dealt by the fixed stride, the probe path above runs as it did.
+  constexpr int kDenseTrajCap = kProbeCap;   // 2048 trajectories
+  constexpr int kDenseListCap = kProbeCap;   // 2048 entries per workgroup
+  static_assert(!RUNS || (blob_floats(NRES) + kProbeCap + kWavesPerBlock + 8) * sizeof(float) <= mmf::kLdsPerCu,
+                "the probe list / dense list shares a CU's LDS with the blob");
   const int n_traj = RUNS ? a.R / a.M : 1;
-  auto clamp_runs = [&](int nr) { return nr < 1 ? 1 : (nr > a.M ? a.M : nr); };  // what a table can hold
+  auto clamp_runs = [&](int nr) { return mmf_deal::clamp_runs(nr, a.M); };  // what a table can hold
+  const int tiles_per_traj = RUNS ? a.M / TILE : 1;
+  const int dense_bound = RUNS ? (ntiles + static_cast<int>(gridDim.x) - 1) / static_cast<int>(gridDim.x) : 0;
+  const bool dense = RUNS && ntiles > 2 * waves_total && n_traj <= kDenseTrajCap && dense_bound <= kDenseListCap;  // wave-uniform
+  int dense_len = 0;  // entries of this workgroup's list
   const int probe_len = RUNS ? (ntiles + waves_total - 1) / waves_total * kWavesPerBlock : 0;
-  const bool probe_lds = RUNS && probe_len <= kProbeCap;  // wave-uniform
+  const bool probe_lds = RUNS && !dense && probe_len <= kProbeCap;  // wave-uniform
   int* probe = nullptr;
+  int* wave_sum = nullptr;
   int probe_val[kProbeRegs];
   if constexpr (RUNS) {
     __shared__ int s_probe[kProbeCap];
+    __shared__ int s_wave_sum[kWavesPerBlock];
     probe = s_probe;
+    wave_sum = s_wave_sum;
+    if (dense) {  // tiles of trajectories kProbeRegs tid .. + kProbeRegs - 1
+#pragma unroll
+      for (int r = 0; r < kProbeRegs; ++r) {
+        const int n = kProbeRegs * static_cast<int>(threadIdx.x) + r;
+        probe_val[r] = n < n_traj ? mmf_deal::tiles_of_runs(multi.rt.n_runs[n], a.M, TILE) : 0;
+      }
+    }
     if (probe_lds) {
 #pragma unroll
       for (int r = 0; r < kProbeRegs; ++r) {
@@ -421,6 +449,57 @@ __global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(std::condi
     for (int i = threadIdx.x; i < off_layers() / 4; i += kThreads) dst[i] = src[i];
     for (int i = off_bias(NRES) / 4 + threadIdx.x; i < blob_floats(NRES) / 4; i += kThreads) dst[i] = src[i];
     if constexpr (RUNS) publish_probe();  // (published by the barrier that follows the DMAs' issue)
+  }
+
+  if constexpr (RUNS) {
+    if (dense) {  // (block-uniform: all kThreads threads pass the four barriers)
+      const int wv = threadIdx.x >> 6;
+      int own = 0;
+#pragma unroll
+      for (int r = 0; r < kProbeRegs; ++r) own += probe_val[r];
+      int incl = own;
+#pragma unroll
+      for (int dlt = 1; dlt < MMF_WAVE; dlt <<= 1) {
+        const int up = __shfl_up(incl, dlt);
+        if (lane >= dlt) incl += up;
+      }
+      if (lane == MMF_WAVE - 1) wave_sum[wv] = incl;
+      __syncthreads();
+      int before = 0, total = 0;
+#pragma unroll
+      for (int w = 0; w < kWavesPerBlock; ++w) {
+        const int ws = wave_sum[w];
+        before += w < wv ? ws : 0;
+        total += ws;
+      }
+      int excl = before + incl - own;
+#pragma unroll
+      for (int r = 0; r < kProbeRegs; ++r) {
+        const int n = kProbeRegs * static_cast<int>(threadIdx.x) + r;
+        if (n < n_traj) probe[n] = excl;
+        excl += probe_val[r];
+      }
+      __syncthreads();
+      total = __builtin_amdgcn_readfirstlane(total);
+      const int G = static_cast<int>(gridDim.x), b = static_cast<int>(blockIdx.x);
+      dense_len = mmf_deal::list_length(total, G, b);
+      dense_len = dense_len < dense_bound ? dense_len : dense_bound;  // (a consistent table never exceeds it)
+      const int top = mmf_deal::search_top(n_traj);
+      int entry[kProbeRegs];
+#pragma unroll
+      for (int r = 0; r < kProbeRegs; ++r) {
+        const int i = r * kThreads + static_cast<int>(threadIdx.x);
+        entry[r] = ntiles;  // past the end
+        if (r * kThreads < dense_bound && i < dense_len) entry[r] = mmf_deal::list_entry(probe, n_traj, tiles_per_traj, G, b, i, top);
+      }
+      __syncthreads();  // every search has read P: the list goes over it
+#pragma unroll
+      for (int r = 0; r < kProbeRegs; ++r) {
+        const int i = r * kThreads + static_cast<int>(threadIdx.x);
+        if (i < dense_bound) probe[i] = entry[r];
+      }
+      __syncthreads();
+    }
   }
 
   // -1.0f in an SGPR, opaque to the optimiser (see split_pair); the asm emits no instruction
@@ -500,12 +579,18 @@ __global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(std::condi
   // RUNS: is there anything in tile q of a trajectory with nr runs?
   auto tile_real = [&](int q, int nr) { return q * TILE < nr; };
   bool first_pending = false;  // RUNS, wave-uniform: the wave's first tile is empty -- it looks for a real one once claims work
+  int tile_first = wave_global;
   if constexpr (RUNS) {
-    const int t0 = __builtin_amdgcn_readfirstlane(wave_global);  // (the wave id is uniform, but not provably so)
+    int t0 = __builtin_amdgcn_readfirstlane(wave_global);  // (the wave id is uniform, but not provably so)
+    if (dense) {  // entry `wave` of the dense list, if the list is that long
+      const int wv = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+      t0 = wv < dense_len ? __builtin_amdgcn_readfirstlane(probe[wv]) : ntiles;
+    }
+    tile_first = t0;
     if (t0 < ntiles) {
       int q, traj;
       const int nr = runs_of(t0, q, traj);  // (the list in LDS is not published yet)
-      if (tile_real(q, nr)) first_layer_inputs(t0, bnext, nr);
+      if (dense || tile_real(q, nr)) first_layer_inputs(t0, bnext, nr);
       else first_pending = true;
     }
   } else {
@@ -576,6 +661,19 @@ __global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(std::condi
   // RUNS: claim until a tile that holds runs turns up, and request ITS inputs (the claim-one-ahead prefetch, for real tiles
   // only: an empty tile costs its claim and one LDS read).  Returns >= ntiles when the workgroup's list is exhausted.
   auto advance = [&]() {
+    if constexpr (RUNS) {
+      if (dense) {  // the next entry of the dense list: a real tile, or the list's end
+        const int i = i_next;
+        i_next = claim(i_next);
+        const int t = i < dense_len ? __builtin_amdgcn_readfirstlane(probe[i]) : ntiles;
+        if (t < ntiles) {
+          int q, traj;
+          const int nr = runs_of(t, q, traj);
+          first_layer_inputs(t, bnext, nr);
+        }
+        return t;
+      }
+    }
     for (;;) {
       const int i = i_next;
       const int t = __builtin_amdgcn_readfirstlane(tile_of(i));
@@ -591,9 +689,7 @@ __global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(std::condi
       }
     }
   };
-  int tile_first = wave_global;
   if constexpr (RUNS) {
-    tile_first = __builtin_amdgcn_readfirstlane(tile_first);
     if (first_pending) tile_first = advance();
   }
 
@@ -776,30 +872,60 @@ __global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(std::condi
       // the tile's output slots are contiguous: 64 per pass, every lane takes part in the exchange
       const int s0 = slot_lo, s1 = slot_hi;
       const bool noisy = a.noise != nullptr || a.noise_mode == 2;
-      int slot_rank = rank_first;
-      float eps[D];
+      // The first pass's rank / noise row were requested at the tile's start; the passes after it are requested
+      // kExpandAhead - 1 passes ahead of their use (the layers' registers are dead here), so that a tile of p passes waits
+      // for about p / (kExpandAhead - 1) memory round trips instead of p - 1 (a degenerate trajectory's tile has up to
+      // M / 64 passes, all on one wave).  The queue is a ring of kExpandAhead places with STATIC indices -- the loop is
+      // unrolled by the ring's length -- and free of branches but its exits: a value moved from place to place, or a load
+      // under a branch, makes the wait in front of a pass a wait for every load in flight.  A request past the tile's end
+      // repeats its last slot (in range, unused).  The two noise sources are two copies of the loop for the same reason.
+      // scale_tril in registers, once per tile: read through the pointer inside the loop it is reloaded after every
+      // pass's stores (they might alias it), and the wait for that load is a wait for the whole ring
+      float tril[D * D];
 #pragma unroll
-      for (int i = 0; i < D; ++i) eps[i] = eps_first[i];
-      for (int kb = s0; kb < s1; kb += MMF_WAVE) {
-        const int k = kb + lane;
-        const bool live = k < s1;
-        const int kk = live ? k : s1 - 1;
-        const size_t slot = static_cast<size_t>(run_traj) * a.M + kk;
-        if (kb != s0) {  // (the first pass's were requested at the tile's start)
-          slot_rank = multi.rt.rank[slot];
+      for (int i = 0; i < D * D; ++i) tril[i] = noisy ? a.scale_tril[i] : 0.f;
+      auto expand = [&](auto tensor_noise) {
+        constexpr bool TN = decltype(tensor_noise)::value;
+        int ring_rank[kExpandAhead];
+        float ring_eps[kExpandAhead][D];
+        auto request_pass = [&](int kb, int& rk, float (&e)[D]) {
+          const int k = kb + lane;
+          const size_t slot = static_cast<size_t>(run_traj) * a.M + (k < s1 ? k : s1 - 1);
+          rk = multi.rt.rank[slot];
 #pragma unroll
-          for (int i = 0; i < D; ++i) eps[i] = (a.noise_mode != 2 && a.noise) ? a.noise[slot * D + i] : 0.f;
+          for (int i = 0; i < D; ++i) e[i] = TN ? a.noise[slot * D + i] : 0.f;
+        };
+        ring_rank[0] = rank_first;
+#pragma unroll
+        for (int i = 0; i < D; ++i) ring_eps[0][i] = eps_first[i];
+#pragma unroll
+        for (int p = 1; p < kExpandAhead; ++p) request_pass(s0 + p * MMF_WAVE, ring_rank[p], ring_eps[p]);
+        for (int kb = s0; kb < s1;) {
+#pragma unroll
+          for (int u = 0; u < kExpandAhead; ++u) {
+            if (kb >= s1) break;
+            const int k = kb + lane;
+            const bool live = k < s1;
+            const int kk = live ? k : s1 - 1;
+            const size_t slot = static_cast<size_t>(run_traj) * a.M + kk;
+            const int src = ring_rank[u] - r0;  // the lane that owns the slot's run
+            float v[D], xn[D];
+#pragma unroll
+            for (int i = 0; i < D; ++i) v[i] = __shfl(v0[i], src);
+            dynamics_diffuse<D>(v, ring_eps[u], tril, noisy, a.noise_mode == 2, a.noise_seed, a.noise_step,
+                                a.noise_traj0 + static_cast<unsigned>(run_traj), static_cast<unsigned>(kk), xn);
+            if (live) {
+#pragma unroll
+              for (int i = 0; i < D; ++i) a.states_out[slot * D + i] = xn[i];
+            }
+            request_pass(kb + kExpandAhead * MMF_WAVE, ring_rank[u], ring_eps[u]);  // the place is free: its next pass
+            kb += MMF_WAVE;
+          }
         }
-        const int src = slot_rank - r0;  // the lane that owns the slot's run
-        float v[D], xn[D];
-#pragma unroll
-        for (int i = 0; i < D; ++i) v[i] = __shfl(v0[i], src);
-        dynamics_diffuse<D>(v, eps, a.scale_tril, noisy, a.noise_mode == 2, a.noise_seed, a.noise_step,
-                            a.noise_traj0 + static_cast<unsigned>(run_traj), static_cast<unsigned>(kk), xn);
-        if (live) {
-#pragma unroll
-          for (int i = 0; i < D; ++i) a.states_out[slot * D + i] = xn[i];
-        }
+      };
+      if (s0 < s1) {  // (s1 - 1 >= s0 >= 0: every slot above is one of the trajectory's)
+        if (a.noise_mode != 2 && a.noise) expand(std::true_type{});
+        else expand(std::false_type{});
       }
     } else if constexpr (KIND == kDynamics) {
       if (active) {
@@ -1048,6 +1174,20 @@ extern "C" int mmf_pf_dynamics_runs_philox(const float* packed, int n_res, int p
   if (!scale_tril) return MMF_EINVAL;
   return dynamics_runs(packed, n_res, precision, states_prev, traj_bias, nullptr, scale_tril, rank, run_anc, run_start, n_runs,
                        states_out, range_flag, N, M, d, seed, step, traj0, 2, stream);
+}
+
+// The dealing of the dense mode of the run kernel, on the host (particle_net_deal.h: the functions the kernel calls).
+extern "C" int mmf_pf_dedup_deal(const int32_t* n_runs, int N, int M, int tile, int grid, int b, int32_t* out, int cap) {
+  if (!n_runs || !out) return MMF_EINVAL;
+  if (N < 1 || M < 1 || tile < 1 || M % tile != 0 || grid < 1 || b < 0 || b >= grid || cap < 0) return MMF_EINVAL;
+  if (static_cast<long long>(N) * (M / tile) > 0x7fffffffLL / 2) return MMF_ETOOLARGE;
+  std::vector<int> P(static_cast<size_t>(N) + 1);
+  P[0] = 0;
+  for (int n = 0; n < N; ++n) P[n + 1] = P[n] + mmf_deal::tiles_of_runs(n_runs[n], M, tile);
+  const int len = mmf_deal::list_length(P[N], grid, b);
+  const int top = mmf_deal::search_top(N);
+  for (int i = 0; i < len && i < cap; ++i) out[i] = mmf_deal::list_entry(P.data(), N, M / tile, grid, b, i, top);
+  return len;
 }
 
 namespace {
