@@ -697,6 +697,54 @@ int mmf_pf_smooth(const MmfPfSmoothArgs* args /* host */, void* stream);
 /* Dynamic LDS bytes mmf_pf_smooth requests for M particles (monotone in M). */
 size_t mmf_pf_smooth_lds_bytes(int M);
 
+/* ---------------------------------------------------------------- marginal particle smoothing (forward filter, backward smoother)
+ * The ancestry smoother above re-weights the particles of step t by how many of the endpoint's paths still pass through
+ * them; far from the endpoint that is a handful (unique[t]).  The forward-filter backward-smoothing recursion (FFBSm;
+ * Doucet, Godsill & Andrieu 2000) keeps EVERY particle of step t and re-weights it through the transition density, so it
+ * reads no ancestors and holds for every resampling mode (plain, multinomial, soft, ESS-triggered, none).  Upstream
+ * torchfilter's ParticleFilter has no smoother; a caller writing this one in torch ops on the kept sets materialises an
+ * (M, M, d) tensor per trajectory and step.  Purely additive to ABI 42: a struct and a symbol of its own.
+ * From a history of T steps: X_t (N, M, d) the set step t propagated, W_t = softmax_m(loglik_t + logw_in_t) the filter's
+ * weights on it (a particle with -inf has weight exactly 0, and whatever its rows hold never reaches a result),
+ * F_t[i] = f(X_t[i], u_{t+1}), t = 0 .. T - 2, the dynamics mean of particle i under the control step t + 1 was propagated
+ * with (pred_steps: the caller evaluates it, e.g. with one mmf_pf_dynamics call without noise over all (T - 1) N
+ * trajectories), L the lower-triangular scale_tril (d, d) of the process noise, one for all particles and steps.
+ *   lp_t[i, j]   = -1/2 || L^-1 (X_{t+1}[j] - F_t[i]) ||^2        (the Gaussian constant cancels)
+ *   logD_t[j]    = logsumexp_i( log W_t[i] + lp_t[i, j] )
+ *   W_{T-1|T}    = W_{T-1}
+ *   W_{t|T}[i]   = sum_j W_{t+1|T}[j] exp( log W_t[i] + lp_t[i, j] - logD_t[j] ),   renormalised to sum 1
+ * The difference X - F is formed first, in fp32, and then whitened with L^-1 (computed in the kernels by forward
+ * substitution from the device copy of L: no host round trip): with states O(1) and noise 0.005 .. 0.05 wide the whitened
+ * coordinates are 20 .. 200, and differencing THEM -- or expanding the square -- would cost 1e-4 .. 1e-2 absolute in the
+ * exponent.  Every term of the second sum is at most W_{t+1|T}[j]: it needs no maximum and cannot overflow.  A column j
+ * with W_{t+1|T}[j] = 0 is skipped (its logD may be -inf).
+ * Four kinds of launch behind the one call: the weights (a_t - max a_t per step and trajectory); logD for all steps at once
+ * (a thread owns a column j, the rows i stream through LDS in chunks of fixed size, log-sum-exp with a running maximum
+ * rescaled once per group of rows); the backward sweep, T - 1 launches (a thread owns a row i, the columns stream through
+ * LDS; every workgroup sums the unnormalised W_{t+1|T} of its trajectory itself, in one fixed order); the moments.  LDS use
+ * does not depend on M.  exp / log are the hardware's base-2 forms: this smoother has no strict bit-exact twin.
+ * Moments in the pivot form of mmf_pf_smooth (pivot = the row of the first largest smoothed weight), cov symmetric bit for
+ * bit; ess = 1 / sum W_{t|T}^2, the diagnostic in the place of unique.  All reductions in a fixed order, no float atomics:
+ * two runs give the same bits, and trajectory n's results do not depend on N.
+ * Limits: 1 <= d <= 4, 1 <= M <= 65536, N <= 65535, beyond -> MMF_ETOOLARGE (d outside 1 .. 4 included).  A null args /
+ * states_steps / loglik_steps / scale_tril / weights / mean, a null pred_steps / logd with T >= 2, T < 0, N < 0, M < 1 or
+ * d < 1 -> MMF_EINVAL.  N == 0 or T == 0 is a successful no-op; T == 1 runs the weights and the moments only.  All decided
+ * on the host before any HIP call.  A non-positive or non-finite diagonal of L makes every result NaN; it never faults. */
+typedef struct MmfPfSmoothMarginalArgs {
+  int32_t T, N, M, d;
+  const float* states_steps;        /* (T, N, M, d)     X_t                                                  */
+  const float* pred_steps;          /* (T - 1, N, M, d) F_t; unread (may be null) for T < 2                  */
+  const float* loglik_steps;        /* (T, N, M)                                                             */
+  const float* logw_in_steps;       /* (T, N, M) or null = uniform                                           */
+  const float* scale_tril;          /* (d, d) DEVICE, row-major; the upper triangle is not read              */
+  float* logd;                      /* workspace (T - 1, N, M): logD_t; unread (may be null) for T < 2       */
+  float* weights;                   /* (T, N, M)    W_{t|T}                                                  */
+  float* mean;                      /* (T, N, d)                                                             */
+  float* cov;                       /* (T, N, d, d) or null                                                  */
+  float* ess;                       /* (T, N) or null                                                        */
+} MmfPfSmoothMarginalArgs;          /* host struct holding device pointers */
+int mmf_pf_smooth_marginal(const MmfPfSmoothMarginalArgs* args /* host */, void* stream);
+
 /* ---------------------------------------------------------------- K6, fused: one network call of the training backward
  * Recompute (the forward pass's f16x3 arithmetic), backward data path and weight / bias gradients of ONE per-particle
  * network over N * M rows in one kernel (the dynamics network: three launches -- encoder forward, trunk, encoder

@@ -37,8 +37,9 @@ def history_record(**fields) -> SimpleNamespace:
     """What a particle filter with ``record_history`` set leaves in ``last_history`` after ``forward_loop`` -- everything a
     smoother needs, each with a leading ``T`` axis: ``states (T, N, M, d)`` the set every step propagated (before
     resampling), ``log_likelihoods (T, N, M)``, ``log_weights_in (T, N, M)`` the log-weights every step started from,
-    ``ancestors (T, N, M)`` int32 (``None``: no step resampled -- the identity), and ``resampled`` (the filter's
-    ``last_resampled``).  Where a step changed the particle count, ``M`` is the largest count and the shorter steps are
+    ``ancestors (T, N, M)`` int32 (``None``: no step resampled -- the identity), ``resampled`` (the filter's
+    ``last_resampled``) and ``controls``, a reference to (not a copy of) the controls the loop was given, which
+    ``smooth(method="marginal")`` evaluates the dynamics means with.  Where a step changed the particle count, ``M`` is the largest count and the shorter steps are
     padded with dead particles (log-likelihood ``-inf``).  ``include/mmf.h`` ("particle smoothing") has the definitions."""
     return SimpleNamespace(**fields)
 

@@ -1,0 +1,362 @@
+// Marginal particle smoothing: the forward-filter backward-smoothing recursion over a filter run's history (include/mmf.h,
+// "marginal particle smoothing").  Where the ancestry smoother of pf_smooth.hip follows the resampling lottery backwards,
+// this one re-weights every particle of step t through the transition density N(X_{t+1}[j]; F_t[i], L L^T): O(M^2) pairs per
+// trajectory and step, VALU work (the difference X - F is formed before it is whitened, so there is no K = d product an MFMA
+// could take).  Four kernels behind one C call:
+//   weights  one workgroup per (step, trajectory): a - max a into `weights` (the last step: exp of it)
+//   logd     one launch over (column tile, trajectory, step): a thread owns a column j, the rows i stream through LDS
+//   sweep    T - 1 launches over (row tile, trajectory), t = T - 2 .. 0: a thread owns a row i, the columns j stream through
+//            LDS; W_{t|T}[i] replaces a_t[i] - max in `weights` (only the thread that owns row i touches it in that launch)
+//   moments  one workgroup per (step, trajectory): normalises `weights` in place; mean, covariance, ESS
+// Between the kernels `weights` holds UNNORMALISED values; every reader divides by the sum it takes itself, in one fixed order.
+// The exponent lives in base 2: L^-1 is scaled by sqrt(log2(e) / 2), so that v_exp_f32 takes la2 - |z|^2 as it stands.
+
+#include <cmath>
+
+#include "mmf_launch.h"
+
+namespace {
+
+constexpr int kPairThreads = 64;    // threads of a pair-kernel workgroup: one column (logd) or row (sweep) each
+constexpr int kPairChunk = 256;     // rows / columns staged in LDS at a time, whatever M is
+constexpr int kPairGroup = 8;       // pairs evaluated between two rescalings of the running maximum
+constexpr int kMomentThreads = 256;
+constexpr int kMomentWaves = kMomentThreads / MMF_WAVE;
+constexpr int kMomentSums = MMF_MAX_STATE_DIM + MMF_MAX_STATE_DIM * (MMF_MAX_STATE_DIM + 1) / 2;
+constexpr float kLog2e = 1.4426950408889634f, kLn2 = 0.6931471805599453f;
+static_assert(kPairChunk % kPairThreads == 0 && kPairChunk % kPairGroup == 0, "a chunk is staged and consumed whole");
+static_assert(kPairThreads == MMF_WAVE, "the sweep sums its trajectory's weights with one wave sum");
+
+struct MarginalArgs {
+  const float* states;   // (T, N, M, D)
+  const float* pred;     // (T - 1, N, M, D)
+  const float* loglik;   // (T, N, M)
+  const float* logw;     // (T, N, M) or null
+  const float* tril;     // (D, D)
+  float* logd;           // (T - 1, N, M), natural logarithm
+  float* weights;        // (T, N, M)
+  float* mean;           // (T, N, D)
+  float* cov;            // (T, N, D, D) or null
+  float* ess;            // (T, N) or null
+  int T, N, M;
+  int t0;                // logd: the step of blockIdx.z == 0; sweep: the step
+};
+
+// one staged row or column: D coordinates and the log2-weight that goes with them, in 4 (D < 4) or 8 floats
+template <int D>
+struct Staged {
+  static constexpr int kFloat4s = D < 4 ? 1 : 2;
+  float x[D];
+  float w;
+  __device__ __forceinline__ void store(float4* lds, int i) const {
+    float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < D; ++c) v[c] = x[c];
+    v[D] = w;
+    lds[i * kFloat4s] = make_float4(v[0], v[1], v[2], v[3]);
+    if (D == 4) lds[i * kFloat4s + 1] = make_float4(v[4], v[5], v[6], v[7]);
+  }
+  // every lane reads the same address: a broadcast, no bank conflict
+  __device__ __forceinline__ void load(const float4* lds, int i) {
+    const float4 a = lds[i * kFloat4s];
+    const float v[5] = {a.x, a.y, a.z, a.w, D < 4 ? 0.f : reinterpret_cast<const float*>(lds)[i * 4 * kFloat4s + 4]};
+#pragma unroll
+    for (int c = 0; c < D; ++c) x[c] = v[c];
+    w = v[D];
+  }
+};
+
+// sqrt(log2(e) / 2) L^-1 by forward substitution, column by column (uniform over the workgroup).  A diagonal entry that is
+// not a positive finite number makes every entry NaN, and with them every result.
+template <int D>
+__device__ __forceinline__ void whitener(const float* __restrict__ tril, float (&W)[D][D]) {
+  const float s = sqrtf(0.5f * kLog2e);
+  bool bad = false;
+#pragma unroll
+  for (int r = 0; r < D; ++r) {
+    const float g = tril[r * D + r];
+    bad = bad || !(g > 0.f) || !(g < INFINITY);
+  }
+#pragma unroll
+  for (int c = 0; c < D; ++c)
+#pragma unroll
+    for (int r = 0; r < D; ++r) {
+      float acc = r == c ? s : 0.f;
+      if (r < c) { W[r][c] = 0.f; continue; }
+#pragma unroll
+      for (int k = c; k < r; ++k) acc = acc - tril[r * D + k] * W[k][c];
+      W[r][c] = bad ? NAN : acc / tril[r * D + r];
+    }
+}
+
+// |sqrt(log2(e) / 2) L^-1 (x - f)|^2 subtracted from `from`: the difference first, then the whitening
+template <int D>
+__device__ __forceinline__ float minus_sq_dist(float from, const float (&x)[D], const float (&f)[D], const float (&W)[D][D]) {
+  float dx[D];
+#pragma unroll
+  for (int c = 0; c < D; ++c) dx[c] = x[c] - f[c];
+#pragma unroll
+  for (int r = 0; r < D; ++r) {
+    float z = W[r][0] * dx[0];
+#pragma unroll
+    for (int c = 1; c <= r; ++c) z = fmaf(W[r][c], dx[c], z);
+    from = fmaf(-z, z, from);
+  }
+  return from;
+}
+
+__device__ __forceinline__ float exp2_hw(float x) { return __builtin_amdgcn_exp2f(x); }
+__device__ __forceinline__ float log2_hw(float x) { return __builtin_amdgcn_logf(x); }
+
+// ---- weights: la = (loglik + logw_in) - max per (step, trajectory); -inf stays -inf.  The last step gets exp(la): the
+// filter's own weights, unnormalised, which is what the sweep starts from.
+__global__ __launch_bounds__(kMomentThreads) void pf_marginal_weights_kernel(MarginalArgs a) {
+  __shared__ float wmax[kMomentWaves];
+  const int tid = threadIdx.x, t = blockIdx.x, n = blockIdx.y, M = a.M;
+  const size_t row0 = (static_cast<size_t>(t) * a.N + n) * M;
+  const float* ll = a.loglik + row0;
+  const float* lw = a.logw ? a.logw + row0 : nullptr;
+  float* out = a.weights + row0;
+  float mx = -INFINITY;
+  for (int m = tid; m < M; m += kMomentThreads) mx = fmaxf(mx, lw ? ll[m] + lw[m] : ll[m]);
+  mx = mmf::wave_max(mx);
+  if ((tid & (MMF_WAVE - 1)) == 0) wmax[tid >> 6] = mx;
+  __syncthreads();
+  mx = wmax[0];
+  for (int w = 1; w < kMomentWaves; ++w) mx = fmaxf(mx, wmax[w]);
+  const bool last = t == a.T - 1;
+  for (int m = tid; m < M; m += kMomentThreads) {
+    const float av = lw ? ll[m] + lw[m] : ll[m];
+    const float la = av == -INFINITY ? -INFINITY : av - mx;  // (every value -inf: stays -inf, the step's results are NaN)
+    out[m] = last ? exp2_hw(la * kLog2e) : la;
+  }
+}
+
+// ---- logd: logD_t[j] = logsumexp_i(la_t[i] + lp_t[i, j]) for the columns of one tile
+template <int D>
+__global__ __launch_bounds__(kPairThreads) void pf_marginal_logd_kernel(MarginalArgs a) {
+  __shared__ float4 lds[kPairChunk * Staged<D>::kFloat4s];
+  const int tid = threadIdx.x, n = blockIdx.y, t = a.t0 + static_cast<int>(blockIdx.z), M = a.M;
+  const size_t nm = static_cast<size_t>(a.N) * M;
+  const size_t rows_t = static_cast<size_t>(t) * nm + static_cast<size_t>(n) * M;        // step t: the rows i
+  const size_t cols_t = static_cast<size_t>(t + 1) * nm + static_cast<size_t>(n) * M;    // step t + 1: the columns j
+  const int j = blockIdx.x * kPairThreads + tid;
+  float W[D][D];
+  whitener<D>(a.tril, W);
+  float x[D];
+  {
+    const float* X = a.states + (cols_t + min(j, M - 1)) * D;
+#pragma unroll
+    for (int c = 0; c < D; ++c) x[c] = X[c];
+  }
+  float mx = -INFINITY, sum = 0.f;
+  for (int c0 = 0; c0 < M; c0 += kPairChunk) {
+    __syncthreads();  // the previous chunk has been consumed
+#pragma unroll
+    for (int k = 0; k < kPairChunk / kPairThreads; ++k) {
+      const int s = k * kPairThreads + tid, i = c0 + s;
+      Staged<D> row;
+      row.w = i < M ? a.weights[rows_t + i] * kLog2e : -INFINITY;
+      const bool dead = row.w == -INFINITY;  // its row may hold anything: it is not read
+#pragma unroll
+      for (int c = 0; c < D; ++c) row.x[c] = dead ? 0.f : a.pred[(rows_t + i) * D + c];
+      row.store(lds, s);
+    }
+    __syncthreads();
+    const int rows = min(kPairChunk, (M - c0 + kPairGroup - 1) / kPairGroup * kPairGroup);  // the padding rows are dead
+    for (int i0 = 0; i0 < rows; i0 += kPairGroup) {
+      float v[kPairGroup];
+      float top = mx;
+#pragma unroll
+      for (int u = 0; u < kPairGroup; ++u) {
+        Staged<D> row;
+        row.load(lds, i0 + u);
+        v[u] = minus_sq_dist<D>(row.w, x, row.x, W);
+        top = fmaxf(top, v[u]);
+      }
+      const float ref = top == -INFINITY ? 0.f : top;  // nothing alive so far: exp2(-inf - 0) = 0, not exp2(nan)
+      sum = sum * exp2_hw(mx - ref);
+#pragma unroll
+      for (int u = 0; u < kPairGroup; ++u) sum = sum + exp2_hw(v[u] - ref);
+      mx = top;
+    }
+  }
+  if (j < M) a.logd[rows_t + j] = (mx + log2_hw(sum)) * kLn2;
+}
+
+// ---- sweep, step t: W_{t|T}[i] = sum_j W_{t+1|T}[j] exp(la_t[i] + lp_t[i, j] - logD_t[j]) for the rows of one tile
+template <int D>
+__global__ __launch_bounds__(kPairThreads) void pf_marginal_sweep_kernel(MarginalArgs a) {
+  __shared__ float4 lds[kPairChunk * Staged<D>::kFloat4s];
+  const int tid = threadIdx.x, n = blockIdx.y, t = a.t0, M = a.M;
+  const size_t nm = static_cast<size_t>(a.N) * M;
+  const size_t rows_t = static_cast<size_t>(t) * nm + static_cast<size_t>(n) * M;
+  const size_t cols_t = static_cast<size_t>(t + 1) * nm + static_cast<size_t>(n) * M;
+  const int i = blockIdx.x * kPairThreads + tid;
+  float W[D][D];
+  whitener<D>(a.tril, W);
+  float f[D];
+  const float la = i < M ? a.weights[rows_t + i] * kLog2e : -INFINITY;
+  {
+    const bool dead = la == -INFINITY;
+    const float* F = a.pred + (rows_t + min(i, M - 1)) * D;
+#pragma unroll
+    for (int c = 0; c < D; ++c) f[c] = dead ? 0.f : F[c];
+  }
+  float acc = 0.f, total = 0.f;
+  for (int c0 = 0; c0 < M; c0 += kPairChunk) {
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kPairChunk / kPairThreads; ++k) {
+      const int s = k * kPairThreads + tid, j = c0 + s;
+      Staged<D> col;
+      const float w = j < M ? a.weights[cols_t + j] : 0.f;
+      const bool skip = w == 0.f;  // no weight: the column is skipped, its logD may be -inf and its row anything
+      col.w = skip ? -INFINITY : log2_hw(w) - a.logd[rows_t + j] * kLog2e;
+#pragma unroll
+      for (int c = 0; c < D; ++c) col.x[c] = skip ? 0.f : a.states[(cols_t + j) * D + c];
+      col.store(lds, s);
+      total = total + w;  // the same columns in the same order in every workgroup of the trajectory
+    }
+    __syncthreads();
+    const int cols = min(kPairChunk, (M - c0 + kPairGroup - 1) / kPairGroup * kPairGroup);
+    for (int j0 = 0; j0 < cols; j0 += kPairGroup) {
+#pragma unroll
+      for (int u = 0; u < kPairGroup; ++u) {
+        Staged<D> col;
+        col.load(lds, j0 + u);
+        acc = acc + exp2_hw(minus_sq_dist<D>(la + col.w, col.x, f, W));
+      }
+    }
+  }
+  total = mmf::wave_sum(total);
+  if (i < M) a.weights[rows_t + i] = la == -INFINITY ? 0.f : acc / total;
+}
+
+// ---- moments: `weights` normalised in place; mean, covariance and ESS in the pivot form of pf_smooth.hip
+template <int D>
+__global__ __launch_bounds__(kMomentThreads) void pf_marginal_moments_kernel(MarginalArgs a) {
+#pragma clang fp contract(off)
+  constexpr int NS = D + D * (D + 1) / 2;
+  __shared__ float partial[(kMomentSums + 2) * kMomentWaves];
+  __shared__ float total[kMomentSums + 2];
+  __shared__ float wtop[kMomentWaves];
+  __shared__ int witop[kMomentWaves];
+  const int tid = threadIdx.x, lane = tid & (MMF_WAVE - 1), wave = tid >> 6;
+  const int t = blockIdx.x, n = blockIdx.y, M = a.M;
+  const size_t row0 = (static_cast<size_t>(t) * a.N + n) * M;
+  float* w = a.weights + row0;
+  const float* X = a.states + row0 * D;
+  bool bad = false;
+#pragma unroll
+  for (int r = 0; r < D; ++r) {
+    const float g = a.tril[r * D + r];
+    bad = bad || !(g > 0.f) || !(g < INFINITY);
+  }
+  // the pivot: the first largest weight (ascending m per thread, ties to the lower index)
+  float bv = -INFINITY, s1 = 0.f, s2 = 0.f;
+  int bi = 0x7fffffff;
+  for (int m = tid; m < M; m += kMomentThreads) {
+    const float e = w[m];
+    if (e > bv) { bv = e; bi = m; }
+    s1 = s1 + e;
+    s2 = s2 + e * e;
+  }
+  auto better = [](float v, int i, float u, int j) { return v > u || (v == u && i < j); };
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const float ov = __shfl_xor(bv, off);
+    const int oi = __shfl_xor(bi, off);
+    if (better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+  }
+  s1 = mmf::wave_sum(s1);
+  s2 = mmf::wave_sum(s2);
+  if (lane == 0) {
+    wtop[wave] = bv; witop[wave] = bi;
+    partial[NS * kMomentWaves + wave] = s1;
+    partial[(NS + 1) * kMomentWaves + wave] = s2;
+  }
+  __syncthreads();
+  bv = wtop[0];
+  bi = witop[0];  // every thread combines the waves' candidates in the same order: one pivot for the workgroup
+  for (int k = 1; k < kMomentWaves; ++k)
+    if (better(wtop[k], witop[k], bv, bi)) { bv = wtop[k]; bi = witop[k]; }
+  if (bi < 0 || bi >= M) bi = 0;  // every weight NaN: the result is NaN either way, the reads stay in range
+  float S = 0.f, S2 = 0.f;
+  for (int k = 0; k < kMomentWaves; ++k) { S = S + partial[NS * kMomentWaves + k]; S2 = S2 + partial[(NS + 1) * kMomentWaves + k]; }
+  if (bad) S = NAN;
+  float p[D], acc[NS];
+#pragma unroll
+  for (int c = 0; c < D; ++c) p[c] = X[static_cast<size_t>(bi) * D + c];
+#pragma unroll
+  for (int v = 0; v < NS; ++v) acc[v] = 0.f;
+  for (int m = tid; m < M; m += kMomentThreads) {
+    const float e = w[m];
+    if (e != 0.f) {  // a particle of zero weight contributes exactly zero, whatever its row holds
+      float dx[D];
+#pragma unroll
+      for (int c = 0; c < D; ++c) dx[c] = X[static_cast<size_t>(m) * D + c] - p[c];
+      int v = D;
+#pragma unroll
+      for (int i = 0; i < D; ++i) {
+        acc[i] = acc[i] + e * dx[i];
+#pragma unroll
+        for (int j = i; j < D; ++j, ++v) acc[v] = acc[v] + (e * dx[i]) * dx[j];
+      }
+    }
+    w[m] = e / S;
+  }
+#pragma unroll
+  for (int v = 0; v < NS; ++v) {
+    const float r = mmf::wave_sum(acc[v]);
+    if (lane == 0) partial[v * kMomentWaves + wave] = r;
+  }
+  __syncthreads();
+  if (tid < NS) {
+    float r = 0.f;
+    for (int k = 0; k < kMomentWaves; ++k) r = r + partial[tid * kMomentWaves + k];
+    total[tid] = r;
+  }
+  __syncthreads();
+  const size_t out = static_cast<size_t>(t) * a.N + n;
+  if (tid < D) a.mean[out * D + tid] = p[tid] + total[tid] / S;
+  if (a.cov && tid < D * D) {
+    const int r = tid / D, c = tid % D, i = min(r, c), j = max(r, c);
+    const int v = D + i * D - i * (i - 1) / 2 + (j - i);  // (i, j) of the upper triangle, row-major
+    a.cov[out * D * D + tid] = total[v] / S - (total[i] / S) * (total[j] / S);
+  }
+  if (a.ess && tid == 0) a.ess[out] = (S * S) / S2;
+}
+
+constexpr int kMaxGridZ = 65535;
+
+}  // namespace
+
+extern "C" int mmf_pf_smooth_marginal(const MmfPfSmoothMarginalArgs* a, void* stream) {
+  if (!a || !a->states_steps || !a->loglik_steps || !a->scale_tril || !a->weights || !a->mean) return MMF_EINVAL;
+  if (a->T < 0 || a->N < 0 || a->M < 1 || a->d < 1) return MMF_EINVAL;
+  if (a->T >= 2 && (!a->pred_steps || !a->logd)) return MMF_EINVAL;
+  if (a->d > MMF_MAX_STATE_DIM || a->M > 65536 || a->N > 65535) return MMF_ETOOLARGE;
+  if (a->N == 0 || a->T == 0) return 0;
+  MarginalArgs k{};
+  k.states = a->states_steps; k.pred = a->pred_steps; k.loglik = a->loglik_steps; k.logw = a->logw_in_steps;
+  k.tril = a->scale_tril; k.logd = a->logd; k.weights = a->weights; k.mean = a->mean; k.cov = a->cov; k.ess = a->ess;
+  k.T = a->T; k.N = a->N; k.M = a->M;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int T = a->T, N = a->N;
+  const int tiles = (a->M + kPairThreads - 1) / kPairThreads;
+  return mmf::with_state_dim(a->d, [&](auto D) -> int {
+    constexpr int d = decltype(D)::value;
+    if (const int rc = mmf::launch(pf_marginal_weights_kernel, dim3(T, N), kMomentThreads, 0, s, k)) return rc;
+    for (int t0 = 0; t0 < T - 1; t0 += kMaxGridZ) {  // all steps are independent: one launch (the grid's z holds 65535 of them)
+      k.t0 = t0;
+      const int steps = T - 1 - t0 < kMaxGridZ ? T - 1 - t0 : kMaxGridZ;
+      if (const int rc = mmf::launch(pf_marginal_logd_kernel<d>, dim3(tiles, N, steps), kPairThreads, 0, s, k)) return rc;
+    }
+    for (int t = T - 2; t >= 0; --t) {
+      k.t0 = t;
+      if (const int rc = mmf::launch(pf_marginal_sweep_kernel<d>, dim3(tiles, N), kPairThreads, 0, s, k)) return rc;
+    }
+    return mmf::launch(pf_marginal_moments_kernel<d>, dim3(T, N), kMomentThreads, 0, s, k);
+  });
+}

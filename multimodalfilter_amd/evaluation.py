@@ -13,7 +13,8 @@ START_TRUNCATION = 30
 
 
 def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale: float = 0.1,
-               measurement_initialize: bool = False, return_belief: bool = False, smooth_lag=False):
+               measurement_initialize: bool = False, return_belief: bool = False, smooth_lag=False,
+               smooth_method: str = "ancestry"):
     """Initialise the belief at ``states[0]`` with covariance ``0.1 I`` (or from the first
     observation, ``eval_helpers.py:116-131``) and filter ``[1:]`` (``:139-142``).
     ``return_belief``: run with ``record_belief`` set and return ``(estimates, filter_model.last_belief)`` -- the per-step
@@ -21,7 +22,9 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
     ``smooth_lag``: ``False`` (the default) leaves all of this as it is; an integer or ``None`` (the full smoother) runs a
     particle filter with ``record_history`` set and returns ``filter_model.smooth(smooth_lag)`` -- the whole recorded
     trajectory is at hand, so ``E[x_t | y_1..t+lag]`` is the better estimate -- and, with ``return_belief``, the smoothed
-    record ``filter_model.last_smoothed`` (``covariance``, ``unique``, ``lag``) in place of the filter's."""
+    record ``filter_model.last_smoothed`` (``covariance``, ``unique``, ``lag``) in place of the filter's.
+    ``smooth_method``: passed to ``smooth(method=)``; ``"marginal"`` smooths also where ``smooth_lag`` is left at ``False``
+    (it is the full smoother: ``smooth_lag`` must be ``False`` or ``None``) and leaves ``covariance``, ``ess``, ``weights``."""
     states = traj["states"]
     T1, N, d = states.shape
     obs = {k: traj[k] for k in ("image", "gripper_pos", "gripper_sensors")}
@@ -29,6 +32,8 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
     if return_belief:
         assert was is not None, f"{type(filter_model).__name__} keeps no belief to record"
         filter_model.record_belief = True
+    if smooth_method != "ancestry" and smooth_lag is False:
+        smooth_lag = None
     smoothing = smooth_lag is not False  # (0 is a lag)
     if smoothing:
         assert hasattr(filter_model, "record_history"), f"{type(filter_model).__name__} keeps no history to smooth"
@@ -49,7 +54,7 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
         if smoothing:
             filter_model.record_history = was_history
     if smoothing:
-        est = filter_model.smooth(smooth_lag)
+        est = filter_model.smooth(smooth_lag, method=smooth_method)
         return (est, filter_model.last_smoothed) if return_belief else est
     return (est, filter_model.last_belief) if return_belief else est
 

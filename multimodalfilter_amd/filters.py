@@ -612,7 +612,7 @@ class ParticleFilter(base.Filter):
         self._step_history = None
         return torch.stack(out, dim=0)
 
-    def smooth(self, lag: Optional[int] = None) -> torch.Tensor:
+    def smooth(self, lag: Optional[int] = None, *, method: str = "ancestry") -> torch.Tensor:
         """Ancestry (genealogy) smoothing of the last ``forward_loop`` run with ``record_history`` set: ``(T, N, d)`` means
         of ``E[x_t | y_1..s(t)]``, ``s(t) = min(t + lag, T - 1)`` -- every particle of the endpoint ``s`` is traced back
         through the ancestors to the particle of step ``t`` it descends from, and the moments of those are taken under the
@@ -620,9 +620,17 @@ class ParticleFilter(base.Filter):
         ``lag = 0``: the filter's own weighted set.  Leaves ``last_smoothed``: ``covariance (T, N, d, d)``, ``unique (T, N)``
         int32 -- the distinct particles of step ``t`` still alive on the endpoint's paths; where it drops to a handful the
         genealogy has collapsed and a shorter lag trades bias for variance -- and ``lag``.  The smoothed estimate is the
-        weighted MEAN also where ``estimation_method == "argmax"`` makes the filter report another point."""
+        weighted MEAN also where ``estimation_method == "argmax"`` makes the filter report another point.
+        ``method = "marginal"``: the forward-filter backward-smoothing recursion instead (``_smooth_marginal``); ``lag`` must
+        be ``None`` there."""
+        if method not in ("ancestry", "marginal"):
+            raise ValueError(f"smooth: method must be 'ancestry' or 'marginal', got {method!r}")
+        if method == "marginal" and lag is not None:
+            raise ValueError("smooth(method='marginal') is the full smoother: a fixed-lag marginal smoother is not implemented")
         h = self.last_history
         assert h is not None, "smooth() needs a history: set record_history and run forward_loop (evaluation mode) first"
+        if method == "marginal":
+            return self._smooth_marginal(h)
         assert lag is None or int(lag) >= 0, "lag must be >= 0 (None: the full smoother)"
         T, N, M, d = h.states.shape
         dev = h.states.device
@@ -632,6 +640,48 @@ class ParticleFilter(base.Filter):
         _abi.pf_smooth(h.states, h.log_likelihoods, h.log_weights_in, None, h.ancestors,
                        max(T - 1, 0) if lag is None else min(int(lag), max(T - 1, 0)), mean, cov, unique)
         self.last_smoothed = base.belief_record(covariance=cov, unique=unique, lag=lag)
+        return mean
+
+    def _smooth_marginal(self, h) -> torch.Tensor:
+        """Marginal smoothing (forward filter, backward smoother; ``mmf_pf_smooth_marginal``, ``include/mmf.h``): every
+        particle of step ``t`` is kept and re-weighted through the transition density ``N(X_{t+1}[j]; f(X_t[i], u_{t+1}),
+        L L^T)``, so no ancestors are read and every resampling mode is covered; ``O(M^2)`` pairs per trajectory and step.
+        The dynamics means of all ``(T - 1) N`` trajectories are evaluated in one go with the controls the history kept.
+        Leaves ``last_smoothed``: ``covariance (T, N, d, d)``, ``ess (T, N)`` = ``1 / sum W^2`` of the smoothed weights,
+        ``weights (T, N, M)``, ``lag = None``, ``method = "marginal"``."""
+        T, N, M, d = h.states.shape
+        dev = h.states.device
+        dyn = self.dynamics_model
+        pred = None
+        with torch.no_grad():
+            if T > 1:
+                past = h.states[:-1]
+                ctrl = tree_map(h.controls, lambda c: c[1:])
+                if hasattr(dyn, "propagate_encoded"):
+                    ctx = dyn.encode_controls(tree_map(ctrl, lambda c: c.reshape(((T - 1) * N,) + tuple(c.shape[2:]))))
+                    pred = dyn.propagate_encoded(past.reshape((T - 1) * N, M, d), ctx, None).reshape(T - 1, N, M, d)
+                    tril = dyn.scale_tril()
+                else:
+                    R = (T - 1) * N * M
+                    rows = tree_map(ctrl, lambda c: c[:, :, None].expand((T - 1, N, M) + tuple(c.shape[2:])).reshape(
+                        (R,) + tuple(c.shape[2:])))
+                    pred, trils = dyn(initial_states=past.reshape(R, d), controls=rows)
+                    if not bool((trils == trils[:1]).all()):
+                        raise ValueError("smooth(method='marginal') needs one process-noise scale_tril for all particles and "
+                                         "steps; this dynamics model returns state-dependent noise")
+                    pred, tril = pred.reshape(T - 1, N, M, d), trils[0]
+            elif hasattr(dyn, "scale_tril"):
+                tril = dyn.scale_tril()
+            else:  # (one step: the transition density is never evaluated)
+                tril = torch.eye(d, dtype=torch.float32, device=dev)
+            tril = tril.detach().to(device=dev, dtype=torch.float32).contiguous()
+            weights = torch.empty((T, N, M), dtype=torch.float32, device=dev)
+            mean = torch.empty((T, N, d), dtype=torch.float32, device=dev)
+            cov = torch.empty((T, N, d, d), dtype=torch.float32, device=dev)
+            ess = torch.empty((T, N), dtype=torch.float32, device=dev)
+            _abi.pf_smooth_marginal(h.states, None if pred is None else pred.to(torch.float32).contiguous(), h.log_likelihoods,
+                                    h.log_weights_in, tril, weights, mean, cov, ess)
+        self.last_smoothed = base.belief_record(covariance=cov, ess=ess, weights=weights, lag=None, method="marginal")
         return mean
 
     @engine.checked_step
@@ -678,12 +728,13 @@ class ParticleFilter(base.Filter):
             if hasattr(self.dynamics_model, "propagate_encoded"):
                 ctrl_all = self.dynamics_model.encode_controls(tree_map(controls, flat))
             native = self._native_loop(obs_all, ctrl_all, T, N)
-        if native is not None:
-            return native
-        return self._loop_of_steps(T, lambda t, sl: self._step(
+        est = native if native is not None else self._loop_of_steps(T, lambda t, sl: self._step(
             tree_index(observations, t), tree_index(controls, t),
             None if obs_all is None else {k: v[sl] for k, v in obs_all.items()},
             None if ctrl_all is None else {k: v[sl] for k, v in ctrl_all.items()}), N)
+        if self.last_history is not None:
+            self.last_history.controls = controls  # (a reference, not a copy) what smooth(method="marginal") predicts with
+        return est
 
 
 class VirtualSensorExtendedKalmanFilter(base.Filter):
