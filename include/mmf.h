@@ -745,6 +745,55 @@ typedef struct MmfPfSmoothMarginalArgs {
 } MmfPfSmoothMarginalArgs;          /* host struct holding device pointers */
 int mmf_pf_smooth_marginal(const MmfPfSmoothMarginalArgs* args /* host */, void* stream);
 
+/* ---------------------------------------------------------------- backward-simulation particle smoothing (forward filter, backward simulation)
+ * The two smoothers above return marginals: moments, and per-step weights W_{t|T}.  Forward filtering, backward simulation
+ * (FFBSi; Godsill, Doucet & West 2004) draws WHOLE trajectories from the joint smoothing distribution
+ * p(x_{0:T-1} | y_{0:T-1}), which is what any function of the path needs (was the door ever open, path length, pairwise
+ * moments for an EM refit of the noise).  Upstream torchfilter's ParticleFilter has no smoother and no path sampler; a caller
+ * writing this one in torch ops on the kept sets runs T dependent steps of an (N, S, M, d) broadcast, a cumsum and a
+ * search each.  Purely additive to ABI 42: a struct and a symbol of its own.
+ * From a history of T steps, as for the marginal smoother: X_t (N, M, d), W_t = softmax_m(loglik_t + logw_in_t),
+ * F_t[i] = f(X_t[i], u_{t+1}) (pred_steps), L the one process-noise scale_tril (d, d); and uniforms u (T, N, S) in [0, 1).
+ * For trajectory n and draw s:
+ *   v_{T-1}[i] = log W_{T-1}[i]
+ *   v_t[i]     = log W_t[i] - 1/2 || L^-1 (X_{t+1}[j_{t+1}] - F_t[i]) ||^2        t = T-2 .. 0
+ *   p_t[i]     = exp(v_t[i] - max_i v_t),   c_t[i] = sum_{k <= i} p_t[k]          (ascending i)
+ *   j_t        = the smallest i with c_t[i] > u[t, n, s] * c_t[M-1]
+ * The inequality is strict: a particle of weight zero (loglik = -inf included) is never chosen, and whatever its rows hold
+ * never reaches a result.  Where rounding leaves no such i, j_t is the last i with p_t[i] > 0.  The difference X - F is
+ * formed before it is whitened (the marginal smoother's rule, for its reason); log W_t is taken relative to the step's
+ * largest log-weight, and the softmax's normaliser cancels in the draw.  exp is the hardware's base-2 form.
+ * A draw is dead where every v_t[i] is -inf, a v is NaN, or the diagonal of L is not positive and finite: it gets index -1
+ * and NaN states at that step and at every earlier one; it never faults.  mean and cov of a step with a dead draw are NaN.
+ * Outputs: indices (T, N, S) int32; trajectories (T, N, S, d) = X_t[n, j_t] copied bit for bit; mean (T, N, d) the plain
+ * average over the S draws; cov (T, N, d, d) or null: 1/S, about the mean, in the pivot form of the other smoothers (the
+ * pivot is draw 0), symmetric bit for bit.
+ * Two launches behind the one call.  The sampler is ONE launch for all steps over (draw blocks, N): a workgroup owns
+ * trajectory n and a block of B draws and walks t = T-1 .. 0 itself; no workgroup talks to another.  Per step a thread owns
+ * a contiguous segment of rows, which stream through LDS in chunks of fixed size (LDS use does not depend on M); per draw it
+ * keeps an online (max, sum) over its segment; the workgroup combines the pairs in thread order, scans them, and the
+ * segment that holds u * total is walked once more for j_t.  The moments: one workgroup per (t, n).
+ * All reductions in a fixed order, no float atomics: two calls give the same bits, and the result for (n, s) depends only
+ * on trajectory n's history and u[:, n, s] -- not on N, on S or on which workgroup took the draw.
+ * Limits: 1 <= d <= 4, 1 <= M <= 65536, N <= 65535, 1 <= S <= 65535, beyond -> MMF_ETOOLARGE.  A null args / states_steps /
+ * loglik_steps / scale_tril / uniforms / indices / trajectories / mean, a null pred_steps with T >= 2, T < 0, N < 0, or
+ * M, S or d below 1 -> MMF_EINVAL (an invalid call is invalid whatever its size).  N == 0 or T == 0 is a successful no-op.
+ * All decided on the host before any HIP call. */
+typedef struct MmfPfSmoothSimulateArgs {
+  int32_t T, N, M, d, S;
+  const float* states_steps;        /* (T, N, M, d)     X_t                                                  */
+  const float* pred_steps;          /* (T - 1, N, M, d) F_t; unread (may be null) for T < 2                  */
+  const float* loglik_steps;        /* (T, N, M)                                                             */
+  const float* logw_in_steps;       /* (T, N, M) or null = uniform                                           */
+  const float* scale_tril;          /* (d, d) DEVICE, row-major; the upper triangle is not read              */
+  const float* uniforms;            /* (T, N, S) in [0, 1)                                                   */
+  int32_t* indices;                 /* (T, N, S)    j_t, -1 where the draw is dead                           */
+  float* trajectories;              /* (T, N, S, d) X_t[n, j_t]                                              */
+  float* mean;                      /* (T, N, d)                                                             */
+  float* cov;                       /* (T, N, d, d) or null                                                  */
+} MmfPfSmoothSimulateArgs;          /* host struct holding device pointers */
+int mmf_pf_smooth_simulate(const MmfPfSmoothSimulateArgs* args /* host */, void* stream);
+
 /* ---------------------------------------------------------------- K6, fused: one network call of the training backward
  * Recompute (the forward pass's f16x3 arithmetic), backward data path and weight / bias gradients of ONE per-particle
  * network over N * M rows in one kernel (the dynamics network: three launches -- encoder forward, trunk, encoder

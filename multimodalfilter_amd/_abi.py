@@ -115,6 +115,12 @@ class MmfPfSmoothMarginalArgs(Structure):
                 ("scale_tril", _FP), ("logd", _FP), ("weights", _FP), ("mean", _FP), ("cov", _FP), ("ess", _FP)]
 
 
+class MmfPfSmoothSimulateArgs(Structure):
+    _fields_ = [("T", c_int32), ("N", c_int32), ("M", c_int32), ("d", c_int32), ("S", c_int32),
+                ("states_steps", _FP), ("pred_steps", _FP), ("loglik_steps", _FP), ("logw_in_steps", _FP),
+                ("scale_tril", _FP), ("uniforms", _FP), ("indices", _FP), ("trajectories", _FP), ("mean", _FP), ("cov", _FP)]
+
+
 class MmfTrainNet(Structure):
     _fields_ = [("packed", _FP), ("packed_f32", _FP), ("packed_t", _FP), ("head_w", _FP), ("pw", _FP), ("pb", _FP),
                 ("p_first", _FP), ("p_head", _FP), ("p_dout", _FP), ("p_traj", _FP), ("packed_dual", _FP)]
@@ -198,6 +204,7 @@ SIGNATURES = {
     "mmf_pf_smooth": (c_int, [POINTER(MmfPfSmoothArgs), c_void_p]),
     "mmf_pf_smooth_lds_bytes": (c_size_t, [c_int]),
     "mmf_pf_smooth_marginal": (c_int, [POINTER(MmfPfSmoothMarginalArgs), c_void_p]),
+    "mmf_pf_smooth_simulate": (c_int, [POINTER(MmfPfSmoothSimulateArgs), c_void_p]),
     "mmf_pf_dedup_plan": (c_int, [c_int, c_int, c_int, ctypes.c_float, c_int]),
     "mmf_pf_dedup_workspace_words": (c_size_t, [c_int, c_int]),
     "mmf_pf_resample_runs": (c_int, [_FP] * 11 + [c_int, c_int, c_int, _FP, _FP, _FP, c_void_p]),
@@ -907,3 +914,31 @@ def pf_smooth_marginal(states_steps, pred_steps, loglik_steps, logw_in_steps, sc
     a.scale_tril, a.logd, a.weights, a.mean, a.cov, a.ess = vp(scale_tril), vp(logd), vp(weights), vp(mean), vp(cov), vp(ess)
     with _on(states_steps):
         _check(load().mmf_pf_smooth_marginal(ctypes.byref(a), stream_of(states_steps)), "mmf_pf_smooth_marginal")
+
+
+def pf_smooth_simulate(states_steps, pred_steps, loglik_steps, logw_in_steps, scale_tril, uniforms, indices, trajectories, mean,
+                       cov=None):
+    """Backward-simulation particle smoothing of a filter run's history (``mmf_pf_smooth_simulate``, include/mmf.h):
+    ``states_steps (T, N, M, d)``, ``pred_steps (T - 1, N, M, d)`` the dynamics means ``f(X_t, u_{t+1})`` (``None`` allowed for
+    ``T < 2``), ``loglik_steps (T, N, M)``, ``logw_in_steps (T, N, M)`` or ``None`` (uniform), ``scale_tril (d, d)`` on the
+    device, ``uniforms (T, N, S)`` in ``[0, 1)`` -> ``indices (T, N, S)`` int32, ``trajectories (T, N, S, d)``,
+    ``mean (T, N, d)`` and ``cov (T, N, d, d)`` or ``None``."""
+    T, N, M, d = states_steps.shape
+    assert uniforms.dim() == 3 and uniforms.shape[:2] == (T, N)
+    S = uniforms.shape[2]
+    assert loglik_steps.shape == (T, N, M) and mean.shape == (T, N, d)
+    assert indices.shape == (T, N, S) and trajectories.shape == (T, N, S, d)
+    assert logw_in_steps is None or logw_in_steps.shape == (T, N, M)
+    assert scale_tril.shape == (d, d)
+    assert cov is None or cov.shape == (T, N, d, d)
+    if T >= 2:
+        assert pred_steps is not None and pred_steps.shape == (T - 1, N, M, d)
+    else:
+        pred_steps = None
+    a = MmfPfSmoothSimulateArgs()
+    a.T, a.N, a.M, a.d, a.S = T, N, M, d, S
+    a.states_steps, a.pred_steps, a.loglik_steps, a.logw_in_steps = vp(states_steps), vp(pred_steps), vp(loglik_steps), vp(logw_in_steps)
+    a.scale_tril, a.uniforms, a.indices, a.trajectories = vp(scale_tril), vp(uniforms), vp(indices, torch.int32), vp(trajectories)
+    a.mean, a.cov = vp(mean), vp(cov)
+    with _on(states_steps):
+        _check(load().mmf_pf_smooth_simulate(ctypes.byref(a), stream_of(states_steps)), "mmf_pf_smooth_simulate")

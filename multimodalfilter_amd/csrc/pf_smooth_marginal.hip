@@ -14,8 +14,11 @@
 #include <cmath>
 
 #include "mmf_launch.h"
+#include "pf_smooth_math.h"
 
 namespace {
+
+using namespace mmf::smooth_math;  // the whitener, minus_sq_dist, exp2_hw / log2_hw, kLog2e / kLn2
 
 constexpr int kPairThreads = 64;    // threads of a pair-kernel workgroup: one column (logd) or row (sweep) each
 constexpr int kPairChunk = 256;     // rows / columns staged in LDS at a time, whatever M is
@@ -23,7 +26,6 @@ constexpr int kPairGroup = 8;       // pairs evaluated between two rescalings of
 constexpr int kMomentThreads = 256;
 constexpr int kMomentWaves = kMomentThreads / MMF_WAVE;
 constexpr int kMomentSums = MMF_MAX_STATE_DIM + MMF_MAX_STATE_DIM * (MMF_MAX_STATE_DIM + 1) / 2;
-constexpr float kLog2e = 1.4426950408889634f, kLn2 = 0.6931471805599453f;
 static_assert(kPairChunk % kPairThreads == 0 && kPairChunk % kPairGroup == 0, "a chunk is staged and consumed whole");
 static_assert(kPairThreads == MMF_WAVE, "the sweep sums its trajectory's weights with one wave sum");
 
@@ -65,48 +67,6 @@ struct Staged {
     w = v[D];
   }
 };
-
-// sqrt(log2(e) / 2) L^-1 by forward substitution, column by column (uniform over the workgroup).  A diagonal entry that is
-// not a positive finite number makes every entry NaN, and with them every result.
-template <int D>
-__device__ __forceinline__ void whitener(const float* __restrict__ tril, float (&W)[D][D]) {
-  const float s = sqrtf(0.5f * kLog2e);
-  bool bad = false;
-#pragma unroll
-  for (int r = 0; r < D; ++r) {
-    const float g = tril[r * D + r];
-    bad = bad || !(g > 0.f) || !(g < INFINITY);
-  }
-#pragma unroll
-  for (int c = 0; c < D; ++c)
-#pragma unroll
-    for (int r = 0; r < D; ++r) {
-      float acc = r == c ? s : 0.f;
-      if (r < c) { W[r][c] = 0.f; continue; }
-#pragma unroll
-      for (int k = c; k < r; ++k) acc = acc - tril[r * D + k] * W[k][c];
-      W[r][c] = bad ? NAN : acc / tril[r * D + r];
-    }
-}
-
-// |sqrt(log2(e) / 2) L^-1 (x - f)|^2 subtracted from `from`: the difference first, then the whitening
-template <int D>
-__device__ __forceinline__ float minus_sq_dist(float from, const float (&x)[D], const float (&f)[D], const float (&W)[D][D]) {
-  float dx[D];
-#pragma unroll
-  for (int c = 0; c < D; ++c) dx[c] = x[c] - f[c];
-#pragma unroll
-  for (int r = 0; r < D; ++r) {
-    float z = W[r][0] * dx[0];
-#pragma unroll
-    for (int c = 1; c <= r; ++c) z = fmaf(W[r][c], dx[c], z);
-    from = fmaf(-z, z, from);
-  }
-  return from;
-}
-
-__device__ __forceinline__ float exp2_hw(float x) { return __builtin_amdgcn_exp2f(x); }
-__device__ __forceinline__ float log2_hw(float x) { return __builtin_amdgcn_logf(x); }
 
 // ---- weights: la = (loglik + logw_in) - max per (step, trajectory); -inf stays -inf.  The last step gets exp(la): the
 // filter's own weights, unnormalised, which is what the sweep starts from.

@@ -7,6 +7,7 @@ from typing import Dict
 import numpy as np
 import torch
 
+from .filters import _DEFAULT_DRAWS
 from .task_models import DOOR, PUSH
 
 START_TRUNCATION = 30
@@ -14,7 +15,7 @@ START_TRUNCATION = 30
 
 def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale: float = 0.1,
                measurement_initialize: bool = False, return_belief: bool = False, smooth_lag=False,
-               smooth_method: str = "ancestry"):
+               smooth_method: str = "ancestry", smooth_draws: int = _DEFAULT_DRAWS):
     """Initialise the belief at ``states[0]`` with covariance ``0.1 I`` (or from the first
     observation, ``eval_helpers.py:116-131``) and filter ``[1:]`` (``:139-142``).
     ``return_belief``: run with ``record_belief`` set and return ``(estimates, filter_model.last_belief)`` -- the per-step
@@ -24,7 +25,12 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
     trajectory is at hand, so ``E[x_t | y_1..t+lag]`` is the better estimate -- and, with ``return_belief``, the smoothed
     record ``filter_model.last_smoothed`` (``covariance``, ``unique``, ``lag``) in place of the filter's.
     ``smooth_method``: passed to ``smooth(method=)``; ``"marginal"`` smooths also where ``smooth_lag`` is left at ``False``
-    (it is the full smoother: ``smooth_lag`` must be ``False`` or ``None``) and leaves ``covariance``, ``ess``, ``weights``."""
+    (it is the full smoother: ``smooth_lag`` must be ``False`` or ``None``) and leaves ``covariance``, ``ess``, ``weights``;
+    ``"simulation"`` likewise, with ``smooth_draws`` joint paths per trajectory (``smooth(num_draws=)``, default 64; passing it with
+    another method is the ``ValueError`` it is there), and leaves ``covariance``, ``trajectories``, ``indices``, ``num_draws``."""
+    if smooth_draws is not _DEFAULT_DRAWS and smooth_method != "simulation":  # (before the run, not after it)
+        raise ValueError(f"run_filter: smooth_draws is the number of paths smooth_method='simulation' draws; "
+                         f"smooth_method={smooth_method!r} takes none")
     states = traj["states"]
     T1, N, d = states.shape
     obs = {k: traj[k] for k in ("image", "gripper_pos", "gripper_sensors")}
@@ -54,7 +60,8 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
         if smoothing:
             filter_model.record_history = was_history
     if smoothing:
-        est = filter_model.smooth(smooth_lag, method=smooth_method)
+        draws = {} if smooth_draws is _DEFAULT_DRAWS else {"num_draws": smooth_draws}  # (another method refuses it, as smooth() does)
+        est = filter_model.smooth(smooth_lag, method=smooth_method, **draws)
         return (est, filter_model.last_smoothed) if return_belief else est
     return (est, filter_model.last_belief) if return_belief else est
 

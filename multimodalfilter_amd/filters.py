@@ -19,7 +19,7 @@ import torch
 
 from . import _abi, base, engine
 from .engine import _timed, check_range, require_device, reserve_memory, use_autograd
-from .utils import CounterBlock, NoiseSource, tree_index, tree_leading_shape, tree_map
+from .utils import CounterBlock, CounterNoise, NoiseSource, tree_index, tree_leading_shape, tree_map
 
 _MODES = {"none": 0, "systematic": 1, "multinomial": 2}
 
@@ -36,6 +36,14 @@ def dedup_eligible(*, T: int, M: int, d: int, mode: int, soft_alpha: float, adap
     if not engine.PF_DEDUP or adaptive or T < 2:
         return False
     return _abi.pf_dedup_plan(M, d, mode, soft_alpha, recording)
+
+
+class _DefaultDraws(int):
+    """The default of ``ParticleFilter.smooth(num_draws=)``: 64, told apart by identity from a 64 the caller passed, since
+    ``num_draws`` with a method that draws no paths is an error."""
+
+
+_DEFAULT_DRAWS = _DefaultDraws(64)
 
 
 class ParticleFilter(base.Filter):
@@ -612,7 +620,7 @@ class ParticleFilter(base.Filter):
         self._step_history = None
         return torch.stack(out, dim=0)
 
-    def smooth(self, lag: Optional[int] = None, *, method: str = "ancestry") -> torch.Tensor:
+    def smooth(self, lag: Optional[int] = None, *, method: str = "ancestry", num_draws: int = _DEFAULT_DRAWS) -> torch.Tensor:
         """Ancestry (genealogy) smoothing of the last ``forward_loop`` run with ``record_history`` set: ``(T, N, d)`` means
         of ``E[x_t | y_1..s(t)]``, ``s(t) = min(t + lag, T - 1)`` -- every particle of the endpoint ``s`` is traced back
         through the ancestors to the particle of step ``t`` it descends from, and the moments of those are taken under the
@@ -622,15 +630,25 @@ class ParticleFilter(base.Filter):
         genealogy has collapsed and a shorter lag trades bias for variance -- and ``lag``.  The smoothed estimate is the
         weighted MEAN also where ``estimation_method == "argmax"`` makes the filter report another point.
         ``method = "marginal"``: the forward-filter backward-smoothing recursion instead (``_smooth_marginal``); ``lag`` must
-        be ``None`` there."""
-        if method not in ("ancestry", "marginal"):
-            raise ValueError(f"smooth: method must be 'ancestry' or 'marginal', got {method!r}")
-        if method == "marginal" and lag is not None:
-            raise ValueError("smooth(method='marginal') is the full smoother: a fixed-lag marginal smoother is not implemented")
+        be ``None`` there.
+        ``method = "simulation"``: ``num_draws`` (default 64) whole trajectories drawn from the joint smoothing distribution
+        by backward simulation (``_smooth_simulation``); returns their mean, ``lag`` must be ``None``.  It draws
+        ``(T, N, num_draws)`` uniforms from ``self.noise`` and so ADVANCES the filter's noise stream.  ``num_draws`` belongs
+        to this method alone."""
+        if method not in ("ancestry", "marginal", "simulation"):
+            raise ValueError(f"smooth: method must be 'ancestry', 'marginal' or 'simulation', got {method!r}")
+        if method != "ancestry" and lag is not None:
+            raise ValueError(f"smooth(method={method!r}) is the full smoother: a fixed-lag {method} smoother is not implemented")
+        if method != "simulation" and num_draws is not _DEFAULT_DRAWS:
+            raise ValueError(f"smooth: num_draws is the number of paths method='simulation' draws; method={method!r} takes none")
+        if isinstance(num_draws, bool) or not isinstance(num_draws, int) or num_draws < 1:
+            raise ValueError(f"smooth(method='simulation'): num_draws must be an int >= 1, got {num_draws!r}")
         h = self.last_history
         assert h is not None, "smooth() needs a history: set record_history and run forward_loop (evaluation mode) first"
         if method == "marginal":
             return self._smooth_marginal(h)
+        if method == "simulation":
+            return self._smooth_simulation(h, num_draws)
         assert lag is None or int(lag) >= 0, "lag must be >= 0 (None: the full smoother)"
         T, N, M, d = h.states.shape
         dev = h.states.device
@@ -651,37 +669,74 @@ class ParticleFilter(base.Filter):
         ``weights (T, N, M)``, ``lag = None``, ``method = "marginal"``."""
         T, N, M, d = h.states.shape
         dev = h.states.device
-        dyn = self.dynamics_model
-        pred = None
         with torch.no_grad():
-            if T > 1:
-                past = h.states[:-1]
-                ctrl = tree_map(h.controls, lambda c: c[1:])
-                if hasattr(dyn, "propagate_encoded"):
-                    ctx = dyn.encode_controls(tree_map(ctrl, lambda c: c.reshape(((T - 1) * N,) + tuple(c.shape[2:]))))
-                    pred = dyn.propagate_encoded(past.reshape((T - 1) * N, M, d), ctx, None).reshape(T - 1, N, M, d)
-                    tril = dyn.scale_tril()
-                else:
-                    R = (T - 1) * N * M
-                    rows = tree_map(ctrl, lambda c: c[:, :, None].expand((T - 1, N, M) + tuple(c.shape[2:])).reshape(
-                        (R,) + tuple(c.shape[2:])))
-                    pred, trils = dyn(initial_states=past.reshape(R, d), controls=rows)
-                    if not bool((trils == trils[:1]).all()):
-                        raise ValueError("smooth(method='marginal') needs one process-noise scale_tril for all particles and "
-                                         "steps; this dynamics model returns state-dependent noise")
-                    pred, tril = pred.reshape(T - 1, N, M, d), trils[0]
-            elif hasattr(dyn, "scale_tril"):
-                tril = dyn.scale_tril()
-            else:  # (one step: the transition density is never evaluated)
-                tril = torch.eye(d, dtype=torch.float32, device=dev)
-            tril = tril.detach().to(device=dev, dtype=torch.float32).contiguous()
+            pred, tril = self._smoothing_transition(h, "marginal")
             weights = torch.empty((T, N, M), dtype=torch.float32, device=dev)
             mean = torch.empty((T, N, d), dtype=torch.float32, device=dev)
             cov = torch.empty((T, N, d, d), dtype=torch.float32, device=dev)
             ess = torch.empty((T, N), dtype=torch.float32, device=dev)
-            _abi.pf_smooth_marginal(h.states, None if pred is None else pred.to(torch.float32).contiguous(), h.log_likelihoods,
-                                    h.log_weights_in, tril, weights, mean, cov, ess)
+            _abi.pf_smooth_marginal(h.states, pred, h.log_likelihoods, h.log_weights_in, tril, weights, mean, cov, ess)
         self.last_smoothed = base.belief_record(covariance=cov, ess=ess, weights=weights, lag=None, method="marginal")
+        return mean
+
+    def _smoothing_transition(self, h, method: str):
+        """What the smoothers that evaluate the transition density read beside the history: the dynamics means
+        ``F_t = f(X_t, u_{t+1})`` of all ``(T - 1) N`` trajectories, evaluated in one go with the controls the history kept
+        (``(T - 1, N, M, d)`` float32, ``None`` for ``T < 2``), and the one process-noise ``scale_tril (d, d)`` on the
+        history's device.  State-dependent noise is refused."""
+        T, N, M, d = h.states.shape
+        dev = h.states.device
+        dyn = self.dynamics_model
+        pred = None
+        if T > 1:
+            past = h.states[:-1]
+            ctrl = tree_map(h.controls, lambda c: c[1:])
+            if hasattr(dyn, "propagate_encoded"):
+                ctx = dyn.encode_controls(tree_map(ctrl, lambda c: c.reshape(((T - 1) * N,) + tuple(c.shape[2:]))))
+                pred = dyn.propagate_encoded(past.reshape((T - 1) * N, M, d), ctx, None).reshape(T - 1, N, M, d)
+                tril = dyn.scale_tril()
+            else:
+                R = (T - 1) * N * M
+                rows = tree_map(ctrl, lambda c: c[:, :, None].expand((T - 1, N, M) + tuple(c.shape[2:])).reshape(
+                    (R,) + tuple(c.shape[2:])))
+                pred, trils = dyn(initial_states=past.reshape(R, d), controls=rows)
+                if not bool((trils == trils[:1]).all()):
+                    raise ValueError(f"smooth(method={method!r}) needs one process-noise scale_tril for all particles and "
+                                     "steps; this dynamics model returns state-dependent noise")
+                pred, tril = pred.reshape(T - 1, N, M, d), trils[0]
+            pred = pred.to(torch.float32).contiguous()
+        elif hasattr(dyn, "scale_tril"):
+            tril = dyn.scale_tril()
+        else:  # (one step: the transition density is never evaluated)
+            tril = torch.eye(d, dtype=torch.float32, device=dev)
+        return pred, tril.detach().to(device=dev, dtype=torch.float32).contiguous()
+
+    def _smooth_simulation(self, h, num_draws: int) -> torch.Tensor:
+        """Backward-simulation smoothing (forward filtering, backward simulation; ``mmf_pf_smooth_simulate``,
+        ``include/mmf.h``): ``num_draws`` whole trajectories per filter trajectory from the joint smoothing distribution --
+        the last particle from the filter's weights, then backwards every particle of step ``t`` re-weighted by the
+        transition density into the particle the path chose at ``t + 1``.  ``(T - 1) N S M`` densities.  The ``(T, N, S)``
+        uniforms are ONE ``self.noise.uniform`` draw (a ``ReplayNoise`` can supply them); the filter's noise stream advances.
+        Returns the ``(T, N, d)`` mean of the draws and leaves ``last_smoothed``: ``covariance (T, N, d, d)`` of the draws,
+        ``trajectories (T, N, S, d)``, ``indices (T, N, S)`` int32 (``-1`` / NaN where a draw is dead), ``num_draws``,
+        ``lag = None``, ``method = "simulation"``."""
+        T, N, M, d = h.states.shape
+        dev = h.states.device
+        S = int(num_draws)
+        if isinstance(self.noise, CounterNoise):
+            raise ValueError("smooth(method='simulation') draws (T, N, num_draws) uniforms from the filter's noise source; "
+                             "CounterNoise draws one uniform per trajectory only: set filter.noise to a NoiseSource (or a "
+                             "ReplayNoise holding the uniforms) before smoothing")
+        with torch.no_grad():
+            pred, tril = self._smoothing_transition(h, "simulation")
+            u = self.noise.uniform((T, N, S), like=h.states)
+            indices = torch.empty((T, N, S), dtype=torch.int32, device=dev)
+            trajectories = torch.empty((T, N, S, d), dtype=torch.float32, device=dev)
+            mean = torch.empty((T, N, d), dtype=torch.float32, device=dev)
+            cov = torch.empty((T, N, d, d), dtype=torch.float32, device=dev)
+            _abi.pf_smooth_simulate(h.states, pred, h.log_likelihoods, h.log_weights_in, tril, u, indices, trajectories, mean, cov)
+        self.last_smoothed = base.belief_record(covariance=cov, trajectories=trajectories, indices=indices, num_draws=S,
+                                                lag=None, method="simulation")
         return mean
 
     @engine.checked_step
