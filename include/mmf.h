@@ -794,6 +794,61 @@ typedef struct MmfPfSmoothSimulateArgs {
 } MmfPfSmoothSimulateArgs;          /* host struct holding device pointers */
 int mmf_pf_smooth_simulate(const MmfPfSmoothSimulateArgs* args /* host */, void* stream);
 
+/* ---------------------------------------------------------------- two-slice smoothing moments (the E-step of an EM refit of the process noise)
+ * The smoothers above return per-step marginals or sampled paths.  Refitting the process noise Q = L L^T by EM needs the
+ * expected transition residual and its second moment under the TWO-SLICE smoothing distribution p(x_t, x_{t+1} | y_{1:T})
+ * over particle pairs; the M-step is then a mean and a Cholesky factor.  Upstream torchfilter's ParticleFilter has no
+ * smoother and nothing that estimates Q; a caller can approximate the moments from mmf_pf_smooth_simulate's paths with
+ * 1 / sqrt(S) Monte-Carlo noise on top, or sum all M^2 pairs in torch ops over an (M, M, d) tensor per trajectory and step.
+ * Purely additive to ABI 42: a struct and two symbols of its own.
+ * From a history of T steps, as for mmf_pf_smooth_marginal (X_t, F_t = pred_steps, W_t = softmax_m(loglik_t + logw_in_t),
+ * lp_t[i, j] and logD_t[j] exactly as that section defines them, L the device scale_tril), and from two results of a
+ * preceding mmf_pf_smooth_marginal call on the SAME history and L: its normalised weights W_{t|T} (T, N, M) and its logd
+ * workspace (T - 1, N, M).  For t = 0 .. T - 2 and trajectory n:
+ *   xi_t[i, j]  ~ W_t[i] exp( lp_t[i, j] - logD_t[j] ) W_{t+1|T}[j]          normalised to sum 1 over (i, j)
+ *   e_t[i, j]   = X_{t+1}[j] - F_t[i]                                        formed in fp32, before anything else
+ *   residual_mean[t, n]          = sum_ij xi e                               (T - 1, N, d)
+ *   residual_second_moment[t, n] = sum_ij xi e e^T                           (T - 1, N, d, d), RAW (not centred)
+ * The rules of the marginal smoother carry over.  A row i with W_t[i] = 0 (loglik + logw_in = -inf) is skipped and so is
+ * a column j with W_{t+1|T}[j] = 0: whatever their rows of X / F hold, inf included, never reaches a result.  The kernel
+ * divides by the total of xi that it sums itself, so any per-(t, n) constant in log W_t cancels; log W_t is taken relative
+ * to the step's largest log-weight -- the basis logD was computed in, so every term is at most W_{t+1|T}[j] and nothing
+ * overflows.  That maximum is taken by EACH WORKGROUP ITSELF from the step's M log-weights (M reads beside its 64 M pairs):
+ * no launch of its own and no (T - 1, N, M) array for it.  exp / log are the hardware's base-2 forms with L^-1 scaled by
+ * sqrt(log2(e) / 2) (pf_smooth_math.h): no strict bit-exact twin.  The difference e is formed first and whitened after,
+ * for the marginal smoother's reason; the same e enters the sums, so nothing is expanded into x x^T - x f^T - ...: with
+ * states O(1) and noise 0.005 .. 0.05 wide that cancellation would cost the second moment three to five digits.
+ * Two launches behind the one call.  Pairs: ONE launch over (row tile of 64, trajectory, step) -- all T - 1 steps are
+ * independent (the grid's z holds 65535 of them per launch) -- a thread owns row i with F_t[i] and log2 W_t[i] in registers,
+ * the columns stream through LDS in chunks of fixed size (LDS use does not depend on M) with log2 W_{t+1|T}[j] -
+ * logD_t[j] log2(e) beside them; per pair one whitened distance, one exp2, and 1 + d + d (d + 1) / 2 sums (the total, p e,
+ * the upper triangle of p e e^T).  Each sum is wave-summed and lane 0 writes the tile's partials to
+ * workspace (T - 1, N, tiles, 1 + d + d (d + 1) / 2), tiles = ceil(M / 64).  Reduce: one workgroup per (t, n) adds the
+ * tiles' partials in tile order, divides by the total, and writes both outputs; the second moment's lower triangle is a
+ * copy of the upper: symmetric bit for bit.  All reductions in a fixed order, no float atomics: two calls give the same
+ * bits, and trajectory n's results do not depend on N.
+ * Limits: 1 <= d <= 4, 1 <= M <= 65536, N <= 65535, beyond -> MMF_ETOOLARGE.  A null args / states_steps / loglik_steps /
+ * scale_tril / weights, with T >= 2 a null pred_steps / logd / workspace / residual_mean / residual_second_moment, T < 0,
+ * N < 0, M < 1 or d < 1 -> MMF_EINVAL (an invalid call is invalid whatever its size).  N == 0 or T < 2 (no transition)
+ * writes nothing and returns 0.  All decided on the host before any HIP call.  A non-positive or non-finite diagonal of L
+ * makes every output NaN; it never faults. */
+typedef struct MmfPfSmoothPairArgs {
+  int32_t T, N, M, d;
+  const float* states_steps;        /* (T, N, M, d)     X_t                                                  */
+  const float* pred_steps;          /* (T - 1, N, M, d) F_t; unread (may be null) for T < 2                  */
+  const float* loglik_steps;        /* (T, N, M)                                                             */
+  const float* logw_in_steps;       /* (T, N, M) or null = uniform                                           */
+  const float* scale_tril;          /* (d, d) DEVICE, row-major; the upper triangle is not read              */
+  const float* weights;             /* (T, N, M)     W_{t|T} as mmf_pf_smooth_marginal left them             */
+  const float* logd;                /* (T - 1, N, M) logD_t as mmf_pf_smooth_marginal left it                */
+  float* workspace;                 /* mmf_pf_smooth_pair_workspace_floats(T, N, M, d) floats                */
+  float* residual_mean;             /* (T - 1, N, d)                                                         */
+  float* residual_second_moment;    /* (T - 1, N, d, d)                                                      */
+} MmfPfSmoothPairArgs;              /* host struct holding device pointers */
+int mmf_pf_smooth_pair_moments(const MmfPfSmoothPairArgs* args /* host */, void* stream);
+/* Floats of the workspace above: (T - 1) N ceil(M / 64) (1 + d + d (d + 1) / 2); 0 for T < 2, N < 1 or sizes outside the limits. */
+size_t mmf_pf_smooth_pair_workspace_floats(int T, int N, int M, int d);
+
 /* ---------------------------------------------------------------- K6, fused: one network call of the training backward
  * Recompute (the forward pass's f16x3 arithmetic), backward data path and weight / bias gradients of ONE per-particle
  * network over N * M rows in one kernel (the dynamics network: three launches -- encoder forward, trunk, encoder

@@ -121,6 +121,13 @@ class MmfPfSmoothSimulateArgs(Structure):
                 ("scale_tril", _FP), ("uniforms", _FP), ("indices", _FP), ("trajectories", _FP), ("mean", _FP), ("cov", _FP)]
 
 
+class MmfPfSmoothPairArgs(Structure):
+    _fields_ = [("T", c_int32), ("N", c_int32), ("M", c_int32), ("d", c_int32),
+                ("states_steps", _FP), ("pred_steps", _FP), ("loglik_steps", _FP), ("logw_in_steps", _FP),
+                ("scale_tril", _FP), ("weights", _FP), ("logd", _FP), ("workspace", _FP),
+                ("residual_mean", _FP), ("residual_second_moment", _FP)]
+
+
 class MmfTrainNet(Structure):
     _fields_ = [("packed", _FP), ("packed_f32", _FP), ("packed_t", _FP), ("head_w", _FP), ("pw", _FP), ("pb", _FP),
                 ("p_first", _FP), ("p_head", _FP), ("p_dout", _FP), ("p_traj", _FP), ("packed_dual", _FP)]
@@ -205,6 +212,8 @@ SIGNATURES = {
     "mmf_pf_smooth_lds_bytes": (c_size_t, [c_int]),
     "mmf_pf_smooth_marginal": (c_int, [POINTER(MmfPfSmoothMarginalArgs), c_void_p]),
     "mmf_pf_smooth_simulate": (c_int, [POINTER(MmfPfSmoothSimulateArgs), c_void_p]),
+    "mmf_pf_smooth_pair_moments": (c_int, [POINTER(MmfPfSmoothPairArgs), c_void_p]),
+    "mmf_pf_smooth_pair_workspace_floats": (c_size_t, [c_int, c_int, c_int, c_int]),
     "mmf_pf_dedup_plan": (c_int, [c_int, c_int, c_int, ctypes.c_float, c_int]),
     "mmf_pf_dedup_workspace_words": (c_size_t, [c_int, c_int]),
     "mmf_pf_resample_runs": (c_int, [_FP] * 11 + [c_int, c_int, c_int, _FP, _FP, _FP, c_void_p]),
@@ -914,6 +923,41 @@ def pf_smooth_marginal(states_steps, pred_steps, loglik_steps, logw_in_steps, sc
     a.scale_tril, a.logd, a.weights, a.mean, a.cov, a.ess = vp(scale_tril), vp(logd), vp(weights), vp(mean), vp(cov), vp(ess)
     with _on(states_steps):
         _check(load().mmf_pf_smooth_marginal(ctypes.byref(a), stream_of(states_steps)), "mmf_pf_smooth_marginal")
+
+
+def pf_smooth_pair_workspace_floats(T: int, N: int, M: int, d: int) -> int:
+    return int(load().mmf_pf_smooth_pair_workspace_floats(int(T), int(N), int(M), int(d)))
+
+
+def pf_smooth_pair_moments(states_steps, pred_steps, loglik_steps, logw_in_steps, scale_tril, weights, logd, residual_mean,
+                           residual_second_moment, workspace=None):
+    """Two-slice smoothing moments of a filter run's history (``mmf_pf_smooth_pair_moments``, include/mmf.h) after a
+    ``pf_smooth_marginal`` call on the same history and ``scale_tril``: the inputs of that call, its ``weights (T, N, M)`` and
+    its ``logd (T - 1, N, M)`` -> ``residual_mean (T - 1, N, d)`` and ``residual_second_moment (T - 1, N, d, d)`` (raw) of
+    ``X_{t+1}[j] - F_t[i]`` over the particle pairs.  ``workspace``: ``pf_smooth_pair_workspace_floats(T, N, M, d)`` floats,
+    allocated when ``None``.  ``T < 2``: there is no transition, nothing is written."""
+    T, N, M, d = states_steps.shape
+    Tm = max(T - 1, 0)
+    assert loglik_steps.shape == (T, N, M) and weights.shape == (T, N, M)
+    assert logw_in_steps is None or logw_in_steps.shape == (T, N, M)
+    assert scale_tril.shape == (d, d)
+    assert residual_mean.shape == (Tm, N, d) and residual_second_moment.shape == (Tm, N, d, d)
+    if T >= 2:
+        assert pred_steps is not None and pred_steps.shape == (T - 1, N, M, d)
+        assert logd is not None and logd.shape == (T - 1, N, M)
+        need = pf_smooth_pair_workspace_floats(T, N, M, d)
+        if workspace is None:
+            workspace = torch.empty((max(need, 1),), dtype=torch.float32, device=states_steps.device)
+        assert workspace.numel() >= need
+    else:
+        pred_steps = logd = workspace = None
+    a = MmfPfSmoothPairArgs()
+    a.T, a.N, a.M, a.d = T, N, M, d
+    a.states_steps, a.pred_steps, a.loglik_steps, a.logw_in_steps = vp(states_steps), vp(pred_steps), vp(loglik_steps), vp(logw_in_steps)
+    a.scale_tril, a.weights, a.logd, a.workspace = vp(scale_tril), vp(weights), vp(logd), vp(workspace)
+    a.residual_mean, a.residual_second_moment = vp(residual_mean), vp(residual_second_moment)
+    with _on(states_steps):
+        _check(load().mmf_pf_smooth_pair_moments(ctypes.byref(a), stream_of(states_steps)), "mmf_pf_smooth_pair_moments")
 
 
 def pf_smooth_simulate(states_steps, pred_steps, loglik_steps, logw_in_steps, scale_tril, uniforms, indices, trajectories, mean,

@@ -52,6 +52,10 @@ def stack_belief_records(steps) -> SimpleNamespace:
 
 
 class DynamicsModel(nn.Module, abc.ABC):
+    """Optional, beside the encoded protocol above: a model with ONE process-noise factor may offer ``scale_tril() -> (d, d)``
+    and ``set_scale_tril(L)``, which replaces it in place (and ``diagonal_noise``, true where it holds a diagonal only);
+    ``evaluation.fit_process_noise`` refits the noise through them and refuses a model without."""
+
     def __init__(self, *, state_dim: int):
         super().__init__()
         self.state_dim = state_dim

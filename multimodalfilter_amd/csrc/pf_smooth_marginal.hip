@@ -18,11 +18,8 @@
 
 namespace {
 
-using namespace mmf::smooth_math;  // the whitener, minus_sq_dist, exp2_hw / log2_hw, kLog2e / kLn2
+using namespace mmf::smooth_math;  // the whitener, minus_sq_dist, Staged and the kPair* sizes, exp2_hw / log2_hw, kLog2e / kLn2
 
-constexpr int kPairThreads = 64;    // threads of a pair-kernel workgroup: one column (logd) or row (sweep) each
-constexpr int kPairChunk = 256;     // rows / columns staged in LDS at a time, whatever M is
-constexpr int kPairGroup = 8;       // pairs evaluated between two rescalings of the running maximum
 constexpr int kMomentThreads = 256;
 constexpr int kMomentWaves = kMomentThreads / MMF_WAVE;
 constexpr int kMomentSums = MMF_MAX_STATE_DIM + MMF_MAX_STATE_DIM * (MMF_MAX_STATE_DIM + 1) / 2;
@@ -42,30 +39,6 @@ struct MarginalArgs {
   float* ess;            // (T, N) or null
   int T, N, M;
   int t0;                // logd: the step of blockIdx.z == 0; sweep: the step
-};
-
-// one staged row or column: D coordinates and the log2-weight that goes with them, in 4 (D < 4) or 8 floats
-template <int D>
-struct Staged {
-  static constexpr int kFloat4s = D < 4 ? 1 : 2;
-  float x[D];
-  float w;
-  __device__ __forceinline__ void store(float4* lds, int i) const {
-    float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int c = 0; c < D; ++c) v[c] = x[c];
-    v[D] = w;
-    lds[i * kFloat4s] = make_float4(v[0], v[1], v[2], v[3]);
-    if (D == 4) lds[i * kFloat4s + 1] = make_float4(v[4], v[5], v[6], v[7]);
-  }
-  // every lane reads the same address: a broadcast, no bank conflict
-  __device__ __forceinline__ void load(const float4* lds, int i) {
-    const float4 a = lds[i * kFloat4s];
-    const float v[5] = {a.x, a.y, a.z, a.w, D < 4 ? 0.f : reinterpret_cast<const float*>(lds)[i * 4 * kFloat4s + 4]};
-#pragma unroll
-    for (int c = 0; c < D; ++c) x[c] = v[c];
-    w = v[D];
-  }
 };
 
 // ---- weights: la = (loglik + logw_in) - max per (step, trajectory); -inf stays -inf.  The last step gets exp(la): the

@@ -50,8 +50,53 @@ __device__ __forceinline__ float minus_sq_dist(float from, const float (&x)[D], 
   return from;
 }
 
+// the same, and the difference dx = x - f handed back (pf_smooth_pairs.hip: the residual whose moments it takes)
+template <int D>
+__device__ __forceinline__ float minus_sq_dist_dx(float from, const float (&x)[D], const float (&f)[D], const float (&W)[D][D],
+                                                  float (&dx)[D]) {
+#pragma unroll
+  for (int c = 0; c < D; ++c) dx[c] = x[c] - f[c];
+#pragma unroll
+  for (int r = 0; r < D; ++r) {
+    float z = W[r][0] * dx[0];
+#pragma unroll
+    for (int c = 1; c <= r; ++c) z = fmaf(W[r][c], dx[c], z);
+    from = fmaf(-z, z, from);
+  }
+  return from;
+}
+
 __device__ __forceinline__ float exp2_hw(float x) { return __builtin_amdgcn_exp2f(x); }
 __device__ __forceinline__ float log2_hw(float x) { return __builtin_amdgcn_logf(x); }
+
+constexpr int kPairThreads = 64;    // threads of a pair-kernel workgroup: one column (logd) or row (sweep, pairs) each
+constexpr int kPairChunk = 256;     // rows / columns staged in LDS at a time, whatever M is
+constexpr int kPairGroup = 8;       // pairs evaluated in one unrolled group (logd: between two rescalings of the running maximum)
+
+// one staged row or column of the pair kernels (pf_smooth_marginal.hip, pf_smooth_pairs.hip): D coordinates and the
+// log2-weight that goes with them, in 4 (D < 4) or 8 floats
+template <int D>
+struct Staged {
+  static constexpr int kFloat4s = D < 4 ? 1 : 2;
+  float x[D];
+  float w;
+  __device__ __forceinline__ void store(float4* lds, int i) const {
+    float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < D; ++c) v[c] = x[c];
+    v[D] = w;
+    lds[i * kFloat4s] = make_float4(v[0], v[1], v[2], v[3]);
+    if (D == 4) lds[i * kFloat4s + 1] = make_float4(v[4], v[5], v[6], v[7]);
+  }
+  // every lane reads the same address: a broadcast, no bank conflict
+  __device__ __forceinline__ void load(const float4* lds, int i) {
+    const float4 a = lds[i * kFloat4s];
+    const float v[5] = {a.x, a.y, a.z, a.w, D < 4 ? 0.f : reinterpret_cast<const float*>(lds)[i * 4 * kFloat4s + 4]};
+#pragma unroll
+    for (int c = 0; c < D; ++c) x[c] = v[c];
+    w = v[D];
+  }
+};
 
 }  // namespace smooth_math
 }  // namespace mmf

@@ -15,7 +15,7 @@ START_TRUNCATION = 30
 
 def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale: float = 0.1,
                measurement_initialize: bool = False, return_belief: bool = False, smooth_lag=False,
-               smooth_method: str = "ancestry", smooth_draws: int = _DEFAULT_DRAWS):
+               smooth_method: str = "ancestry", smooth_draws: int = _DEFAULT_DRAWS, smooth_transition_moments: bool = False):
     """Initialise the belief at ``states[0]`` with covariance ``0.1 I`` (or from the first
     observation, ``eval_helpers.py:116-131``) and filter ``[1:]`` (``:139-142``).
     ``return_belief``: run with ``record_belief`` set and return ``(estimates, filter_model.last_belief)`` -- the per-step
@@ -27,7 +27,12 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
     ``smooth_method``: passed to ``smooth(method=)``; ``"marginal"`` smooths also where ``smooth_lag`` is left at ``False``
     (it is the full smoother: ``smooth_lag`` must be ``False`` or ``None``) and leaves ``covariance``, ``ess``, ``weights``;
     ``"simulation"`` likewise, with ``smooth_draws`` joint paths per trajectory (``smooth(num_draws=)``, default 64; passing it with
-    another method is the ``ValueError`` it is there), and leaves ``covariance``, ``trajectories``, ``indices``, ``num_draws``."""
+    another method is the ``ValueError`` it is there), and leaves ``covariance``, ``trajectories``, ``indices``, ``num_draws``.
+    ``smooth_transition_moments``: smooths with the filter's ``record_transition_moments`` set (and puts the switch back) -- with ``smooth_method="marginal"`` alone, refused
+    before the run otherwise; the record gains ``residual_mean`` and ``residual_second_moment`` (``process_noise_m_step``)."""
+    if smooth_transition_moments and smooth_method != "marginal":  # (before the run, not after it)
+        raise ValueError(f"run_filter: smooth_transition_moments are the two-slice moments smooth_method='marginal' computes; "
+                         f"smooth_method={smooth_method!r} has none")
     if smooth_draws is not _DEFAULT_DRAWS and smooth_method != "simulation":  # (before the run, not after it)
         raise ValueError(f"run_filter: smooth_draws is the number of paths smooth_method='simulation' draws; "
                          f"smooth_method={smooth_method!r} takes none")
@@ -61,9 +66,91 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
             filter_model.record_history = was_history
     if smoothing:
         draws = {} if smooth_draws is _DEFAULT_DRAWS else {"num_draws": smooth_draws}  # (another method refuses it, as smooth() does)
-        est = filter_model.smooth(smooth_lag, method=smooth_method, **draws)
+        was_moments = getattr(filter_model, "record_transition_moments", False)
+        if smooth_transition_moments:
+            assert hasattr(filter_model, "record_transition_moments"), f"{type(filter_model).__name__} computes no transition moments"
+            filter_model.record_transition_moments = True
+        try:
+            est = filter_model.smooth(smooth_lag, method=smooth_method, **draws)
+        finally:
+            if smooth_transition_moments:
+                filter_model.record_transition_moments = was_moments
         return (est, filter_model.last_smoothed) if return_belief else est
     return (est, filter_model.last_belief) if return_belief else est
+
+
+def process_noise_m_step(record, *, diagonal: bool = False, start: int = 0) -> torch.Tensor:
+    """The M-step of EM for the process noise from a smoothed record with transition moments
+    (``smooth(method="marginal")`` with ``record_transition_moments`` set): ``Q = mean over steps >= start and all trajectories of
+    residual_second_moment`` -- the raw second moment, since the model's noise has mean zero -- and the ``(d, d)``
+    ``scale_tril = cholesky(Q)``; ``diagonal``: ``diag(sqrt(diag Q))``, for a model that holds a diagonal only.  Plain torch,
+    on the record's device (CPU tensors included).  A non-finite entry, or a ``Q`` that is not positive definite, is a
+    ``ValueError`` naming the first offending ``(t, n)``."""
+    m2 = getattr(record, "residual_second_moment", None)
+    if m2 is None:
+        raise ValueError("process_noise_m_step: the record has no residual_second_moment; smooth with "
+                         "method='marginal' and the filter's record_transition_moments set")
+    if m2.dim() != 4 or m2.shape[-1] != m2.shape[-2]:
+        raise ValueError(f"process_noise_m_step: residual_second_moment must be (T - 1, N, d, d), got {tuple(m2.shape)}")
+    start = int(start)
+    if start < 0 or start >= m2.shape[0] or m2.shape[1] == 0:
+        raise ValueError(f"process_noise_m_step: no transitions at steps >= {start} ({m2.shape[0]} steps, {m2.shape[1]} trajectories)")
+    m2 = m2[start:].detach()
+
+    def first(bad):  # the first (t, n) in row-major order, t counted from the record's step 0
+        k = int(torch.nonzero(bad.reshape(-1))[0])
+        return start + k // bad.shape[1], k % bad.shape[1]
+
+    bad = ~torch.isfinite(m2).all(-1).all(-1)
+    if bool(bad.any()):
+        raise ValueError("process_noise_m_step: non-finite residual_second_moment at (t, n) = (%d, %d)" % first(bad))
+    Q = m2.to(torch.float64).mean(dim=(0, 1))
+    Q = 0.5 * (Q + Q.t())
+    if diagonal:
+        var = torch.diagonal(Q)
+        if not bool((var > 0).all()):
+            zero = ~(torch.diagonal(m2, dim1=-2, dim2=-1) > 0).all(-1)
+            where = first(zero) if bool(zero.any()) else (start, 0)
+            raise ValueError("process_noise_m_step: the refitted noise is not positive definite; first degenerate "
+                             "residual_second_moment at (t, n) = (%d, %d)" % where)
+        return torch.diag(torch.sqrt(var)).to(m2.dtype)
+    L, info = torch.linalg.cholesky_ex(Q)
+    if int(info) != 0:
+        each = torch.linalg.cholesky_ex(m2.to(torch.float64))[1] != 0
+        where = first(each) if bool(each.any()) else (start, 0)
+        raise ValueError("process_noise_m_step: the refitted noise is not positive definite; first degenerate "
+                         "residual_second_moment at (t, n) = (%d, %d)" % where)
+    return L.to(m2.dtype)
+
+
+def fit_process_noise(filter_model, traj: Dict[str, torch.Tensor], *, iterations: int = 5, start: int = 0, **run_filter_kwargs):
+    """EM for the process noise of ``filter_model.dynamics_model`` on the trajectories ``traj``: every iteration runs
+    ``run_filter(smooth_method="marginal", smooth_transition_moments=True, return_belief=True)`` (the E-step: the two-slice
+    moments under the current noise), takes ``process_noise_m_step`` over the steps ``>= start`` and hands the factor to
+    ``dynamics_model.set_scale_tril`` -- the diagonal form where the model's ``diagonal_noise`` is true.  Returns the list
+    of ``(d, d)`` factors, the initial one first: ``iterations + 1`` entries.  ``run_filter_kwargs`` go to ``run_filter``
+    (``initial_cov_scale``, ``measurement_initialize``); the smoothing switches are this function's own.  The filter's
+    ``record_*`` switches are restored on every path; a model without ``set_scale_tril`` is a ``TypeError`` before any
+    run.  The moments are those of THIS process's trajectories: summing them across ranks is out of scope."""
+    dyn = getattr(filter_model, "dynamics_model", None)
+    if dyn is None or not callable(getattr(dyn, "set_scale_tril", None)) or not callable(getattr(dyn, "scale_tril", None)):
+        raise TypeError(f"fit_process_noise: {type(dyn).__name__} has no set_scale_tril(L) / scale_tril(): the process noise "
+                        "of this dynamics model cannot be refitted (base.DynamicsModel documents the optional method)")
+    for k in ("smooth_method", "smooth_transition_moments", "return_belief", "smooth_lag", "smooth_draws"):
+        if k in run_filter_kwargs:
+            raise TypeError(f"fit_process_noise: {k} is set by fit_process_noise itself")
+    iterations = int(iterations)
+    if iterations < 0:
+        raise ValueError(f"fit_process_noise: iterations must be >= 0, got {iterations}")
+    diagonal = bool(getattr(dyn, "diagonal_noise", False))
+    out = [dyn.scale_tril().detach().clone()]
+    for _ in range(iterations):
+        _est, record = run_filter(filter_model, traj, smooth_method="marginal", smooth_transition_moments=True,
+                                  return_belief=True, **run_filter_kwargs)
+        L = process_noise_m_step(record, diagonal=diagonal, start=start)
+        dyn.set_scale_tril(L)
+        out.append(dyn.scale_tril().detach().clone())
+    return out
 
 
 def _whitened_error(predicted: torch.Tensor, covariance: torch.Tensor, true: torch.Tensor):

@@ -77,6 +77,10 @@ class ParticleFilter(base.Filter):
     (``mmf_pf_forward_loop_history``: the loop of launches; the persistent launch is skipped, as with ``record_indices``),
     the step-by-step loop stacks the same tensors.  ``smooth(lag)`` then returns the ancestry-smoothed means
     ``E[x_t | y_1..min(t + lag, T)]`` (``mmf_pf_smooth``).  Every other output of the loop has the same bits either way.
+    ``record_transition_moments = True``: ``smooth(method="marginal")`` also leaves the two-slice moments of the transition
+    residual in ``last_smoothed`` (``residual_mean``, ``residual_second_moment``; ``mmf_pf_smooth_pair_moments``), what
+    ``evaluation.process_noise_m_step`` refits the process noise from.  A switch like the other ``record_*`` ones and not
+    an argument of ``smooth``, whose parameter list stays ``(lag, *, method, num_draws)``; another method with it set raises.
     Randomness comes from ``self.noise`` (``utils.NoiseSource``), never from global RNG state.
     """
 
@@ -114,6 +118,7 @@ class ParticleFilter(base.Filter):
         self.record_history = False   # forward_loop keeps the per-step sets / weights / ancestors -> last_history, smooth()
         self.last_history = None
         self.last_smoothed = None
+        self.record_transition_moments = False  # smooth(method="marginal") adds the two-slice residual moments to last_smoothed
         self._step_history = None
         self.use_native_loop = True   # False: forward_loop keeps the step-by-step Python loop
         self.particle_states: torch.Tensor = None
@@ -634,7 +639,11 @@ class ParticleFilter(base.Filter):
         ``method = "simulation"``: ``num_draws`` (default 64) whole trajectories drawn from the joint smoothing distribution
         by backward simulation (``_smooth_simulation``); returns their mean, ``lag`` must be ``None``.  It draws
         ``(T, N, num_draws)`` uniforms from ``self.noise`` and so ADVANCES the filter's noise stream.  ``num_draws`` belongs
-        to this method alone."""
+        to this method alone.
+        With ``self.record_transition_moments`` set (``method = "marginal"`` alone; any other method is a ``ValueError``):
+        also the two-slice moments of the transition residual ``X_{t+1} - f(X_t, u_{t+1})`` -- ``last_smoothed`` gains
+        ``residual_mean (T - 1, N, d)`` and ``residual_second_moment (T - 1, N, d, d)``, what
+        ``evaluation.process_noise_m_step`` refits the process noise from."""
         if method not in ("ancestry", "marginal", "simulation"):
             raise ValueError(f"smooth: method must be 'ancestry', 'marginal' or 'simulation', got {method!r}")
         if method != "ancestry" and lag is not None:
@@ -643,10 +652,14 @@ class ParticleFilter(base.Filter):
             raise ValueError(f"smooth: num_draws is the number of paths method='simulation' draws; method={method!r} takes none")
         if isinstance(num_draws, bool) or not isinstance(num_draws, int) or num_draws < 1:
             raise ValueError(f"smooth(method='simulation'): num_draws must be an int >= 1, got {num_draws!r}")
+        transition_moments = bool(getattr(self, "record_transition_moments", False))
+        if transition_moments and method != "marginal":
+            raise ValueError(f"smooth: record_transition_moments is set, and the two-slice moments are method='marginal''s; "
+                             f"method={method!r} has none (unset the switch, or smooth with method='marginal')")
         h = self.last_history
         assert h is not None, "smooth() needs a history: set record_history and run forward_loop (evaluation mode) first"
         if method == "marginal":
-            return self._smooth_marginal(h)
+            return self._smooth_marginal(h, transition_moments)
         if method == "simulation":
             return self._smooth_simulation(h, num_draws)
         assert lag is None or int(lag) >= 0, "lag must be >= 0 (None: the full smoother)"
@@ -660,23 +673,34 @@ class ParticleFilter(base.Filter):
         self.last_smoothed = base.belief_record(covariance=cov, unique=unique, lag=lag)
         return mean
 
-    def _smooth_marginal(self, h) -> torch.Tensor:
+    def _smooth_marginal(self, h, transition_moments: bool = False) -> torch.Tensor:
         """Marginal smoothing (forward filter, backward smoother; ``mmf_pf_smooth_marginal``, ``include/mmf.h``): every
         particle of step ``t`` is kept and re-weighted through the transition density ``N(X_{t+1}[j]; f(X_t[i], u_{t+1}),
         L L^T)``, so no ancestors are read and every resampling mode is covered; ``O(M^2)`` pairs per trajectory and step.
         The dynamics means of all ``(T - 1) N`` trajectories are evaluated in one go with the controls the history kept.
         Leaves ``last_smoothed``: ``covariance (T, N, d, d)``, ``ess (T, N)`` = ``1 / sum W^2`` of the smoothed weights,
-        ``weights (T, N, M)``, ``lag = None``, ``method = "marginal"``."""
+        ``weights (T, N, M)``, ``lag = None``, ``method = "marginal"``.
+        ``transition_moments``: the same predictions, noise factor and ``logD`` go on to ``mmf_pf_smooth_pair_moments`` -- one
+        more pass over the pairs, all steps in one launch -- and the record gains ``residual_mean (T - 1, N, d)`` and
+        ``residual_second_moment (T - 1, N, d, d)``: mean and RAW second moment of ``X_{t+1}[j] - F_t[i]`` under the
+        two-slice smoothing distribution over the particle pairs ``(i, j)`` (leading size 0 for ``T == 1``)."""
         T, N, M, d = h.states.shape
         dev = h.states.device
+        extra = {}
         with torch.no_grad():
             pred, tril = self._smoothing_transition(h, "marginal")
             weights = torch.empty((T, N, M), dtype=torch.float32, device=dev)
             mean = torch.empty((T, N, d), dtype=torch.float32, device=dev)
             cov = torch.empty((T, N, d, d), dtype=torch.float32, device=dev)
             ess = torch.empty((T, N), dtype=torch.float32, device=dev)
-            _abi.pf_smooth_marginal(h.states, pred, h.log_likelihoods, h.log_weights_in, tril, weights, mean, cov, ess)
-        self.last_smoothed = base.belief_record(covariance=cov, ess=ess, weights=weights, lag=None, method="marginal")
+            logd = torch.empty((T - 1, N, M), dtype=torch.float32, device=dev) if transition_moments and T > 1 else None
+            _abi.pf_smooth_marginal(h.states, pred, h.log_likelihoods, h.log_weights_in, tril, weights, mean, cov, ess, logd)
+            if transition_moments:
+                extra["residual_mean"] = torch.empty((max(T - 1, 0), N, d), dtype=torch.float32, device=dev)
+                extra["residual_second_moment"] = torch.empty((max(T - 1, 0), N, d, d), dtype=torch.float32, device=dev)
+                _abi.pf_smooth_pair_moments(h.states, pred, h.log_likelihoods, h.log_weights_in, tril, weights, logd,
+                                            extra["residual_mean"], extra["residual_second_moment"])
+        self.last_smoothed = base.belief_record(covariance=cov, ess=ess, weights=weights, lag=None, method="marginal", **extra)
         return mean
 
     def _smoothing_transition(self, h, method: str):

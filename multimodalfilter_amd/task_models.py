@@ -185,6 +185,30 @@ def make_task_models(task: TaskSpec) -> SimpleNamespace:
                 return torch.diag(self.Q_scale_tril_diag)
             return self.Q_scale_tril
 
+        @property
+        def diagonal_noise(self) -> bool:
+            """Whether the model holds a diagonal process-noise factor only (``set_scale_tril`` refuses anything else)."""
+            return self._brent
+
+        def set_scale_tril(self, L) -> None:
+            """Replace the process-noise factor by ``L (d, d)``, lower-triangular with a positive diagonal (e.g. from
+            ``evaluation.process_noise_m_step``).  Copied in place, under ``no_grad``, into the parameter the model was
+            built with: every loop that holds its pointer sees the new values."""
+            store = self.Q_scale_tril_diag if self._brent else self.Q_scale_tril
+            L = torch.as_tensor(L).detach().to(device=store.device, dtype=store.dtype)
+            if L.shape != (D, D):
+                raise ValueError(f"set_scale_tril: expected a ({D}, {D}) factor, got {tuple(L.shape)}")
+            diag = torch.diagonal(L)
+            if not bool(torch.isfinite(L).all()) or not bool((diag > 0).all()):
+                raise ValueError("set_scale_tril: the factor must be finite with a positive diagonal")
+            if bool((torch.triu(L, 1) != 0).any()):
+                raise ValueError("set_scale_tril: the factor must be lower-triangular")
+            if self._brent and bool((L != torch.diag(diag)).any()):
+                raise ValueError(f"set_scale_tril: {type(self).__name__} holds a diagonal process noise only "
+                                 "(diagonal_noise is True); the factor has off-diagonal mass")
+            with torch.no_grad():
+                store.copy_(diag if self._brent else L)
+
         # encoded protocol (see base.py)
         def encode_controls(self, controls):
             """Control encoder + the hoisted control half of ``shared_layers[0]``: one K7 launch."""

@@ -1,0 +1,423 @@
+"""Two-slice smoothing moments on the GPU (``include/mmf.h``: ``mmf_pf_smooth_pair_moments``;
+``ParticleFilter.smooth(method="marginal")`` with the filter's ``record_transition_moments`` set) and the EM refit of the
+process noise built on them (``evaluation.process_noise_m_step`` / ``fit_process_noise``).
+
+The kernels are held to the fp64 definition (``_pair_cases.reference``) at the project's bar (``_tol.REL_TOL`` through
+``rel_err``, per trajectory so that a narrow cloud is measured against its own scale).  The smoothed weights and ``logD``
+the kernel reads come from the GPU marginal call on the same inputs, as they do in use."""
+import functools
+import math
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from oracle import models as om
+
+import _pair_cases as pc
+from _tol import REL_TOL, rel_err
+
+CHUNK = 256  # columns the pair kernels stage at a time (csrc/pf_smooth_math.h: kPairChunk)
+_WIDTHS = (1e-3, 1e-2, 0.3)
+
+
+def _dev():
+    if not torch.cuda.is_available():
+        pytest.fail("GPU tests need a real MI355X")
+    return torch.device("cuda:0")
+
+
+def _G(x):
+    return None if x is None else torch.as_tensor(np.ascontiguousarray(x), dtype=torch.float32).to(_dev())
+
+
+def _marginal(X, F, ll, lw, L):
+    """The GPU marginal call: ``dict`` of the device inputs and its ``weights``, ``logd``, ``mean``."""
+    from multimodalfilter_amd import _abi
+
+    dev = _dev()
+    T, N, M, d = X.shape
+    g = dict(X=_G(X), F=_G(F) if T > 1 else None, ll=_G(ll), lw=_G(lw), L=_G(L))
+    g["weights"] = torch.full((T, N, M), math.nan, device=dev)
+    g["mean"] = torch.full((T, N, d), math.nan, device=dev)
+    g["logd"] = torch.full((T - 1, N, M), math.nan, device=dev) if T > 1 else None
+    _abi.pf_smooth_marginal(g["X"], g["F"], g["ll"], g["lw"], g["L"], g["weights"], g["mean"], None, None, g["logd"])
+    return g
+
+
+def _pairs(g, L=None, workspace=None):
+    """``mmf_pf_smooth_pair_moments`` on what ``_marginal`` left (``L``: another noise factor than the marginal call's)."""
+    from multimodalfilter_amd import _abi
+
+    dev = _dev()
+    T, N, M, d = g["X"].shape
+    mean = torch.full((max(T - 1, 0), N, d), math.nan, device=dev)
+    second = torch.full((max(T - 1, 0), N, d, d), math.nan, device=dev)
+    _abi.pf_smooth_pair_moments(g["X"], g["F"], g["ll"], g["lw"], g["L"] if L is None else _G(L), g["weights"], g["logd"],
+                                mean, second, workspace)
+    torch.cuda.synchronize()
+    return mean, second
+
+
+def _run(X, F, ll, lw, L):
+    return _pairs(_marginal(X, F, ll, lw, L))
+
+
+def _check(got, want, what):
+    """Both outputs within the bar per trajectory; the second moment symmetric bit for bit and PSD to ``-1e-4 x trace``.
+    Prints the figures before asserting."""
+    mean, second = got
+    wmean, wsecond = want["residual_mean"], want["residual_second_moment"]
+    N = wmean.shape[1]
+    e_mean = max(rel_err(mean[:, n], wmean[:, n], dims=1) for n in range(N))
+    e_second = max(rel_err(second[:, n], wsecond[:, n], dims=2) for n in range(N))
+    print(f"{what}: residual mean {e_mean:.2e} second moment {e_second:.2e}")
+    assert bool(torch.isfinite(mean).all()) and bool(torch.isfinite(second).all()), what
+    assert e_mean <= REL_TOL, (what, e_mean)
+    assert e_second <= REL_TOL, (what, e_second)
+    assert torch.equal(second, second.transpose(-1, -2)), what
+    c = second.double().cpu()
+    floor = -1e-4 * torch.diagonal(c, dim1=-2, dim2=-1).sum(-1)
+    assert bool((torch.linalg.eigvalsh(c).min(-1).values >= floor - 1e-30).all()), what
+
+
+# ------------------------------------------------------------------------------------------ 1. kernels against fp64
+@pytest.mark.parametrize("ll_scale", [0.5, 50.0])
+@pytest.mark.parametrize("d", [2, 3, 4])
+@pytest.mark.parametrize("M", [1, 37, 300, 2 * CHUNK + 88])
+def test_pair_kernels_match_fp64(M, d, ll_scale):
+    """Three trajectories of widths 1e-3 / 1e-2 / 0.3 per call, T = 5; the process noise once diagonal and once a full lower
+    triangle.  M = 300 spans five row tiles, one whole chunk of columns and a part of one; M = 600 two chunks and a part; at
+    scale 50 a particle or two hold the filter's weight at every step, scale 0.5 keeps hundreds alive."""
+    T, N = 5, 3
+    for full in (False, True):
+        L = pc.tril(d, full)
+        X, F, ll, lw = pc.make_case(T, N, M, d, _WIDTHS, ll_scale, L, seed=1000 * M + 10 * d + int(ll_scale) + full)
+        _check(_run(X, F, ll, lw, L), pc.reference(X, F, ll, lw, L), f"M={M} d={d} scale={ll_scale} full={full}")
+
+
+# ------------------------------------------------------------------------------------------ 2. edges
+@pytest.mark.parametrize("d", [2, 4])
+def test_a_single_particle_gives_its_own_residual(d):
+    """M = 1: the one pair's weight p cancels, ``mean = (p e) / p`` and ``second = ((p e_r) e_c) / p`` with ``e`` the fp32
+    difference -- two roundings on the mean (<= 2 x 2^-24 relative, held to 2^-23) and three on the second moment
+    (<= 3 x 2^-24 of the exact product of the fp32 ``e``, held to 2^-22): the last bit of fp32 products."""
+    L = pc.tril(d, True)
+    X, F, ll, lw = pc.make_case(5, 2, 1, d, _WIDTHS, 0.5, L, seed=2)
+    mean, second = _run(X, F, ll, lw, L)
+    e = (X[1:, :, 0] - F[:, :, 0]).astype(np.float64)  # the fp32 difference
+    assert e.dtype == np.float64 and (X[1:, :, 0] - F[:, :, 0]).dtype == np.float32
+    outer = e[..., :, None] * e[..., None, :]
+    dm = np.abs(mean.double().cpu().numpy() - e)
+    ds = np.abs(second.double().cpu().numpy() - outer)
+    print(f"M=1 d={d}: mean off by {float((dm / np.abs(e)).max()):.2e}, second moment by {float((ds / np.abs(outer)).max()):.2e} (relative)")
+    assert (dm <= 2.0 ** -23 * np.abs(e)).all()
+    assert (ds <= 2.0 ** -22 * np.abs(outer)).all()
+    assert torch.equal(second, second.transpose(-1, -2))
+
+
+def test_dead_particles_and_a_single_heavy_particle():
+    """-inf log-likelihoods on half a row at every step, ``inf`` in the dead rows of ``X`` and ``F``: a finite result equal to
+    the reference over the rest.  One particle with all the weight at the last step: the last transition's moments are
+    those of the pairs into that particle alone."""
+    T, N, M, d = 5, 3, 300, 3
+    L = pc.tril(d, True)
+    X, F, ll, lw = pc.make_case(T, N, M, d, _WIDTHS, 0.5, L, seed=11)
+    ll[:, 1, ::2] = -np.inf
+    X[:, 1, ::2] = np.inf
+    F[:, 1, ::2] = np.inf
+    _check(_run(X, F, ll, lw, L), pc.reference(X, F, ll, lw, L), "half dead")
+    X, F, ll, lw = pc.make_case(T, N, M, d, _WIDTHS, 0.5, L, seed=12)
+    ll[-1, :, 17] = 60.0  # the others keep exp(-60) ~ 1e-26 of it
+    got = _run(X, F, ll, lw, L)
+    _check(got, pc.reference(X, F, ll, lw, L), "one heavy particle")
+    # by the definition, with one column: xi[i] is proportional to W_{T-2}[i] N(X_{T-1}[17]; F_{T-2}[i], L L^T)
+    e = (X[-1, :, 17][:, None, :] - F[-1]).astype(np.float64)
+    z = e @ np.linalg.inv(L.astype(np.float64)).T
+    xi = pc.softmax_rows(ll[-2].astype(np.float64) + lw[-2] - 0.5 * (z * z).sum(-1))
+    assert rel_err(got[0][-1], np.einsum("ni,nic->nc", xi, e), dims=1) <= REL_TOL
+    assert rel_err(got[1][-1], np.einsum("ni,nic,nik->nck", xi, e, e), dims=2) <= REL_TOL
+
+
+@pytest.mark.parametrize("M", [300, 2 * CHUNK + 88])
+def test_two_calls_split_batches_and_a_supplied_workspace_give_the_same_bits(M):
+    """Fixed-order reductions: two calls on the same inputs return the same bits; the call on N = 3 trajectories returns
+    what three calls on one trajectory each do; a caller's workspace (larger than needed, full of NaN) changes nothing;
+    null incoming log-weights are uniform ones."""
+    from multimodalfilter_amd import _abi
+
+    L = pc.tril(3, True)
+    X, F, ll, lw = pc.make_case(5, 3, M, 3, _WIDTHS, 0.5, L, seed=3 + M)
+    g = _marginal(X, F, ll, lw, L)
+    a, b = _pairs(g), _pairs(g)
+    for x, y in zip(a, b):
+        assert torch.equal(x, y)
+    for n in range(3):
+        one = _run(X[:, n:n + 1], F[:, n:n + 1], ll[:, n:n + 1], lw[:, n:n + 1], L)
+        for x, y in zip(a, one):
+            assert torch.equal(x[:, n:n + 1], y), n
+    need = _abi.pf_smooth_pair_workspace_floats(5, 3, M, 3)
+    assert need == 4 * 3 * ((M + 63) // 64) * 10
+    ws = torch.full((need + 1000,), math.nan, device=_dev())
+    c = _pairs(g, workspace=ws)
+    for x, y in zip(a, c):
+        assert torch.equal(x, y)
+    assert bool(torch.isfinite(ws[:need]).all()) and bool(torch.isnan(ws[need:]).all())  # all of it written, nothing beyond
+    uniform = _run(X, F, ll, None, L)
+    zeros = _run(X, F, ll, np.zeros_like(lw), L)
+    for x, y in zip(uniform, zeros):
+        assert torch.equal(x, y)
+
+
+def test_a_bad_noise_factor_gives_nan_and_no_fault():
+    """A zero, negative or non-finite diagonal entry of ``L`` -- handed to this call alone after a good marginal call, or to
+    both: every output is NaN.  ``T = 1``: nothing to write, and the call succeeds."""
+    L = pc.tril(3, True)
+    X, F, ll, lw = pc.make_case(3, 2, 70, 3, _WIDTHS, 0.5, L, seed=21)
+    good = _marginal(X, F, ll, lw, L)
+    for bad in (0.0, -0.02, math.inf, math.nan):
+        Lb = L.copy()
+        Lb[1, 1] = bad
+        for got in (_pairs(good, L=Lb), _run(X, F, ll, lw, Lb)):
+            for x in got:
+                assert bool(torch.isnan(x).all()), bad
+    mean, second = _run(X[:1], F[:0], ll[:1], lw[:1], L)
+    assert mean.shape == (0, 2, 3) and second.shape == (0, 2, 3, 3)
+
+
+# ------------------------------------------------------------------------------------------ 3. a known limit
+def test_a_flat_transition_factorises():
+    """``L = 1e3 I``: every transition density is the same to 1e-6, so ``xi = W_t[i] W_{t+1|T}[j]`` and the residual mean is
+    ``mean_{t+1|T} - sum_i W_t[i] F_t[i]`` -- the marginal call's own smoothed means against the filter's weights."""
+    T, N, M, d = 5, 3, 300, 3
+    X, F, ll, lw = pc.make_case(T, N, M, d, _WIDTHS, 0.5, pc.tril(d, True), seed=31)
+    g = _marginal(X, F, ll, lw, (1e3 * np.eye(d)).astype(np.float32))
+    mean, second = _pairs(g)
+    W = pc.softmax_rows(ll.astype(np.float64) + lw)
+    want = g["mean"].double().cpu().numpy()[1:] - np.einsum("tnm,tnmc->tnc", W[:-1], F.astype(np.float64))
+    e_mean = max(rel_err(mean[:, n], want[:, n], dims=1) for n in range(N))
+    sharp = _run(X, F, ll, lw, pc.tril(d, True))
+    moved = max(rel_err(sharp[0][:, n], want[:, n], dims=1) for n in range(N))
+    print(f"flat transition: residual mean against the factorised form {e_mean:.2e}; the sharp transition's differs by {moved:.2e}")
+    assert e_mean <= REL_TOL
+    assert moved > 10 * REL_TOL  # (the comparison above is not vacuous)
+    assert torch.equal(second, second.transpose(-1, -2))
+
+
+# ------------------------------------------------------------------------------------------ 4. whole filters
+_CONFIGS = {"plain": {}, "ess": {"resample_ess_threshold": 0.5}}
+
+
+def _filter(cls, N, M, T, dev):
+    import multimodalfilter_amd as mmf
+    from multimodalfilter_amd import synthetic
+
+    tname = "door" if cls.startswith("Door") else "push"
+    d = om.TASKS[tname].state_dim
+    torch.manual_seed(3)
+    f = mmf.model_types(tname)[cls]().to(dev).eval()
+    f.num_particles = M
+    traj = {k: v.to(dev) for k, v in synthetic.make_trajectories(state_dim=d, T=T, N=N, seed=17).items()}
+    obs = {k: traj[k][1:] for k in ("image", "gripper_pos", "gripper_sensors")}
+    cal = traj["states"][0][:, None, :] + 0.3 * torch.randn((N, 256, d), device=dev)
+    synthetic.calibrate_measurement_heads(f, {k: v[0] for k, v in obs.items()}, cal, target_std=1.2)
+    cov = (torch.eye(d, device=dev) * 0.1)[None].expand(N, d, d)
+    return f, d, traj, obs, traj["controls"][1:], cov
+
+
+_FILTER_CASES = [(cls, c, M) for cls in ("DoorParticleFilter", "PushParticleFilter") for c in _CONFIGS for M in (64, 300)]
+
+
+@pytest.mark.parametrize("cls,config,M", _FILTER_CASES)
+def test_filter_transition_moments_match_the_reference_and_the_marginal_record_is_unchanged(cls, config, M):
+    """``smooth(method="marginal")`` with ``record_transition_moments`` set, on a filter's own history, equals the fp64 reference on that
+    history (with the predictions ``F_t`` the test obtains itself); means, covariance, ESS and weights have the bits of the
+    call without the flag, whose record has the fields it had; the flagged record has exactly two more."""
+    import multimodalfilter_amd as mmf
+
+    dev = _dev()
+    N, T = 4, 6
+    f, d, traj, obs, ctrl, cov = _filter(cls, N, M, T, dev)
+    for k, v in _CONFIGS[config].items():
+        setattr(f, k, v)
+    f.record_history = True
+    f.noise = mmf.CounterNoise(99)
+    f.initialize_beliefs(mean=traj["states"][0], covariance=cov)
+    f.forward_loop(observations=obs, controls=ctrl)
+    h = f.last_history
+    plain_mean = f.smooth(method="marginal")
+    plain = f.last_smoothed
+    old = {"covariance", "ess", "weights", "lag", "method"}
+    assert set(vars(plain)) == old
+    f.record_transition_moments = True
+    mean = f.smooth(method="marginal")
+    rec = f.last_smoothed
+    with pytest.raises(ValueError, match="record_transition_moments"):
+        f.smooth()  # the switch belongs to the marginal method
+    f.record_transition_moments = False
+    assert set(vars(rec)) == old | {"residual_mean", "residual_second_moment"}
+    assert rec.method == "marginal" and rec.lag is None
+    assert torch.equal(mean, plain_mean)
+    for k in ("covariance", "ess", "weights"):
+        assert torch.equal(getattr(rec, k), getattr(plain, k)), k
+    assert rec.residual_mean.shape == (T - 1, N, d) and rec.residual_second_moment.shape == (T - 1, N, d, d)
+    dyn = f.dynamics_model
+    with torch.no_grad():
+        ctx = dyn.encode_controls(h.controls[1:].reshape((T - 1) * N, -1))
+        F = dyn.propagate_encoded(h.states[:-1].reshape((T - 1) * N, M, d), ctx, None).reshape(T - 1, N, M, d)
+    C = lambda x: x.detach().cpu().numpy()
+    want = pc.reference(C(h.states), C(F), C(h.log_likelihoods), C(h.log_weights_in), C(dyn.scale_tril()))
+    _check((rec.residual_mean, rec.residual_second_moment), want, f"{cls} {config} M={M}")
+    f.smooth()  # the ancestry path's record is what it was
+    assert set(vars(f.last_smoothed)) == {"covariance", "unique", "lag"}
+
+
+def test_a_single_step_history_has_empty_moments():
+    import multimodalfilter_amd as mmf
+
+    dev = _dev()
+    N, M, T = 2, 64, 1
+    f, d, traj, obs, ctrl, cov = _filter("DoorParticleFilter", N, M, T, dev)
+    f.record_history = True
+    f.noise = mmf.CounterNoise(5)
+    f.initialize_beliefs(mean=traj["states"][0], covariance=cov)
+    f.forward_loop(observations=obs, controls=ctrl)
+    f.record_transition_moments = True
+    mean = f.smooth(method="marginal")
+    rec = f.last_smoothed
+    assert mean.shape == (1, N, d) and bool(torch.isfinite(mean).all())
+    assert rec.residual_mean.shape == (0, N, d) and rec.residual_second_moment.shape == (0, N, d, d)
+
+
+# ------------------------------------------------------------------------------------------ 5. the EM refit
+def _linear_gaussian_filter(d, q0, r, M, dev):
+    """The linear-Gaussian user models of ``test_gpu_marginal_smoothing.py`` (a random walk, ``z = x + r eps`` read from the
+    ``gripper_pos`` entry ``run_filter`` passes on), the dynamics with a ``set_scale_tril`` added."""
+    import multimodalfilter_amd as mmf
+    from multimodalfilter_amd import base
+
+    class RandomWalk(base.DynamicsModel):
+        def __init__(self):
+            super().__init__(state_dim=d)
+            self.L = (q0 * torch.eye(d)).to(dev)
+
+        def scale_tril(self):
+            return self.L
+
+        def set_scale_tril(self, L):
+            with torch.no_grad():
+                self.L.copy_(L.to(self.L))
+
+        def forward(self, *, initial_states, controls):
+            return initial_states, self.L[None].expand(initial_states.shape[0], d, d)
+
+    class GaussianLik(base.ParticleFilterMeasurementModel):
+        def __init__(self):
+            super().__init__(state_dim=d)
+
+        def forward(self, *, states, observations):
+            e = observations["gripper_pos"][:, None, :] - states
+            return -0.5 * (e * e).sum(-1) / (r * r)
+
+    f = mmf.filters.ParticleFilter(dynamics_model=RandomWalk(), measurement_model=GaussianLik(), num_particles=M)
+    f.eval()
+    return f
+
+
+@functools.lru_cache(maxsize=None)
+def _linear_gaussian_data():
+    from multimodalfilter_amd import synthetic
+
+    d, N, T, r = 3, 8, 40, 0.3
+    truth = synthetic.make_trajectories(state_dim=d, T=T, N=N, seed=23)["states"]  # x' = x + 0.05 eps, (T + 1, N, d)
+    z = truth.clone()
+    z[1:] = truth[1:] + r * torch.randn((T, N, d), generator=torch.Generator().manual_seed(29))
+    return d, N, T, r, truth, z
+
+
+def _traj(truth, z, dev):
+    T1, N, _ = truth.shape
+    zeros = lambda *s: torch.zeros((T1, N) + s, device=dev)
+    return {"states": truth.to(dev), "controls": zeros(7), "image": zeros(1), "gripper_pos": z.to(dev), "gripper_sensors": zeros(1)}
+
+
+def test_fit_process_noise_follows_the_exact_em_steps():
+    """The random-walk states of ``synthetic.make_trajectories`` (``q = 0.05``) observed through ``z = x + 0.3 eps``:
+    d = 3, N = 8, M = 512, T = 40.  From ``q0 = 0.15`` the first M-step's ``sqrt(mean diag Q)`` is within 3 % of the exact
+    Kalman / RTS EM step computed here in fp64 (six times the 0.5 % of the fp64 study on the CPU: the GPU run draws other
+    noise); three iterations decrease monotonically; from ``q0 = 0.02`` the first step increases.  Every returned factor
+    is lower-triangular with a positive diagonal, and the filter's switches are as they were."""
+    import multimodalfilter_amd as mmf
+    from multimodalfilter_amd import evaluation
+
+    dev = _dev()
+    d, N, T, r, truth, z = _linear_gaussian_data()
+    M = 512
+    traj = _traj(truth, z, dev)
+    size = lambda L: float(torch.sqrt(torch.diagonal(L.double() @ L.double().t()).mean()))
+    f = _linear_gaussian_filter(d, 0.15, r, M, dev)
+    f.noise = mmf.NoiseSource(31)
+    assert f.record_history is False and f.record_belief is False and f.record_transition_moments is False
+    factors = evaluation.fit_process_noise(f, traj, iterations=3)
+    assert f.record_history is False and f.record_belief is False and f.record_transition_moments is False
+    assert len(factors) == 4 and torch.equal(factors[0].cpu(), 0.15 * torch.eye(d))
+    assert torch.equal(f.dynamics_model.scale_tril(), factors[-1])
+    q = [size(L) for L in factors]
+    exact = pc.rts_em_step(z[1:].double().numpy(), truth[0].double().numpy(), 0.1, 0.15, r)
+    print(f"EM from 0.15: {q[1]:.5f} {q[2]:.5f} {q[3]:.5f}; exact first step {exact:.5f}, ratio - 1 = {q[1] / exact - 1.0:+.2e}")
+    for L in factors:
+        assert L.shape == (d, d) and bool(torch.isfinite(L).all())
+        assert torch.equal(L, torch.tril(L)) and bool((torch.diagonal(L) > 0).all())
+    assert abs(q[1] / exact - 1.0) <= 0.03
+    assert q[0] > q[1] > q[2] > q[3] > 0.05
+    f = _linear_gaussian_filter(d, 0.02, r, M, dev)
+    f.noise = mmf.NoiseSource(31)
+    up = evaluation.fit_process_noise(f, traj, iterations=1)
+    print(f"EM from 0.02: {size(up[1]):.5f}")
+    assert size(up[1]) > size(up[0])
+    assert torch.equal(up[1], torch.tril(up[1])) and bool((torch.diagonal(up[1]) > 0).all())
+
+
+def test_fit_process_noise_restores_the_switches_when_a_run_fails():
+    import multimodalfilter_amd as mmf
+    from multimodalfilter_amd import evaluation
+
+    dev = _dev()
+    d, N, T, r, truth, z = _linear_gaussian_data()
+    f = _linear_gaussian_filter(d, 0.15, r, 64, dev)
+    f.noise = mmf.NoiseSource(31)
+    traj = _traj(truth[:4], z[:4], dev)
+    del traj["controls"]
+    with pytest.raises(KeyError):
+        evaluation.fit_process_noise(f, traj, iterations=1)
+    assert f.record_history is False and f.record_belief is False and f.record_transition_moments is False
+    assert torch.equal(f.dynamics_model.scale_tril().cpu(), 0.15 * torch.eye(d))  # nothing was refitted
+
+
+@pytest.mark.parametrize("cls", ["DoorParticleFilter", "PushParticleFilter"])
+def test_fit_process_noise_on_the_task_models(cls):
+    """``fit_process_noise`` on a task filter (N = 4, M = 300, T = 8, two iterations): finite factors, diagonal where the
+    model's ``diagonal_noise`` says so (the door filter's dynamics) and a full lower triangle otherwise; the model's
+    ``scale_tril()`` afterwards is the last one returned."""
+    import multimodalfilter_amd as mmf
+    from multimodalfilter_amd import evaluation
+
+    dev = _dev()
+    N, M, T = 4, 300, 8
+    f, d, traj, obs, ctrl, cov = _filter(cls, N, M, T, dev)
+    f.noise = mmf.CounterNoise(7)
+    dyn = f.dynamics_model
+    assert dyn.diagonal_noise is (cls == "DoorParticleFilter")
+    first = dyn.scale_tril().clone()
+    factors = evaluation.fit_process_noise(f, traj, iterations=2)
+    assert len(factors) == 3 and torch.equal(factors[0], first)
+    for L in factors:
+        assert L.shape == (d, d) and L.device == first.device and bool(torch.isfinite(L).all())
+        assert torch.equal(L, torch.tril(L)) and bool((torch.diagonal(L) > 0).all())
+        if dyn.diagonal_noise:
+            assert torch.equal(L, torch.diag(torch.diagonal(L)))
+    assert not torch.equal(factors[1], factors[0]) and not torch.equal(factors[2], factors[1])
+    assert torch.equal(dyn.scale_tril(), factors[-1])
+    assert f.record_history is False and f.record_belief is False and f.record_transition_moments is False
