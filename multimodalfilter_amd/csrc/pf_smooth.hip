@@ -7,17 +7,19 @@
 
 #include <cmath>
 
-#include "mmf_launch.h"
+#include "pf_smooth_math.h"
 
 namespace {
 
+using namespace mmf::smooth_math;  // log_weight, first_max, the pivot-form moment pieces
+
 constexpr int kSmoothThreads = 1024;            // most threads of a workgroup: 16 waves
 constexpr int kSmoothWaves = kSmoothThreads / MMF_WAVE;
-constexpr int kSmoothSums = MMF_MAX_STATE_DIM + MMF_MAX_STATE_DIM * (MMF_MAX_STATE_DIM + 1) / 2;  // m1 and the upper triangle of M2
+constexpr int kSmoothSums = moment_sums(MMF_MAX_STATE_DIM);
 constexpr int kSmoothMaxPer = 40;               // particles per thread at the largest M the LDS plan takes
 
 // dynamic LDS, in 4-byte words: weights (M) | bitmap (ceil(M / 32)) | partial sums (kSmoothSums x waves) | totals
-// (kSmoothSums + 2, padded to 16) | pivot row (4) | wave maxima (waves) | their indices (waves) | pivot path, count (4)
+// (kSmoothSums + 2, padded to 16) | pivot row (4) | wave maxima (waves) | their indices (waves) | 4 words: [1] the count of distinct particles, [0] unused
 struct SmoothLds {
   size_t weights, bitmap, partial, total, pivot, wmax, widx, misc, end;
 };
@@ -63,9 +65,9 @@ __global__ __launch_bounds__(kSmoothThreads) void pf_smooth_kernel(SmoothArgs a)
   float* const pivot = smem + a.o_pivot;
   float* const wmax = smem + a.o_wmax;
   int* const widx = reinterpret_cast<int*>(smem + a.o_widx);
-  int* const misc = reinterpret_cast<int*>(smem + a.o_misc);  // [0] pivot path, [1] count of distinct particles
+  int* const misc = reinterpret_cast<int*>(smem + a.o_misc);  // [1] count of distinct particles
 
-  constexpr int NS = D + D * (D + 1) / 2;
+  constexpr int NS = moment_sums(D);
   const int tid = threadIdx.x, threads = blockDim.x, lane = tid & (MMF_WAVE - 1), wave = tid >> 6, waves = threads >> 6;
   const int n = blockIdx.y, M = a.M;
   const int s = a.lag + static_cast<int>(blockIdx.x);  // the endpoint: lag .. T - 1
@@ -77,41 +79,23 @@ __global__ __launch_bounds__(kSmoothThreads) void pf_smooth_kernel(SmoothArgs a)
   // ---- the endpoint's weights: a = loglik + logw_in, first maximum, e = exp(a - max)
   const float* ll = a.loglik + s * nm + row0;
   const float* lw = a.logw ? a.logw + s * nm + row0 : (s == 0 && a.logw0 ? a.logw0 + row0 : nullptr);
-  float bv = -INFINITY;
-  int bi = 0x7fffffff;
+  float mx = -INFINITY;
+  int pm = 0x7fffffff;  // the pivot path: the first highest-weight one
 #pragma unroll
   for (int k = 0; k < PER; ++k) {
     const int m = k * threads + tid;
     if (m < M) {
-      const float av = lw ? ll[m] + lw[m] : ll[m];
-      if (av > bv) { bv = av; bi = m; }  // ascending m per thread: the first of equal values stays
+      const float av = log_weight(ll, lw, m);
+      if (av > mx) { mx = av; pm = m; }
     }
   }
-  auto better = [](float v, int i, float w, int j) { return v > w || (v == w && i < j); };
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const float ov = __shfl_xor(bv, off);
-    const int oi = __shfl_xor(bi, off);
-    if (better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-  }
-  if (lane == 0) { wmax[wave] = bv; widx[wave] = bi; }
-  __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < waves; ++w)
-      if (better(wmax[w], widx[w], bv, bi)) { bv = wmax[w]; bi = widx[w]; }
-    if (bi < 0 || bi >= M) bi = 0;  // every value -inf or NaN: the result is NaN either way, the gathers stay in range
-    wmax[0] = bv;
-    misc[0] = bi;
-  }
-  __syncthreads();
-  const float mx = wmax[0];
-  const int pm = misc[0];
+  first_max(mx, pm, wmax, widx, tid, waves, M);
   float ssum = 0.f;
 #pragma unroll
   for (int k = 0; k < PER; ++k) {
     const int m = k * threads + tid;
     if (m < M) {
-      const float av = lw ? ll[m] + lw[m] : ll[m];  // read again (L2) instead of kept: PER registers fewer
+      const float av = log_weight(ll, lw, m);  // read again (L2) instead of kept: PER registers fewer
       const bool dead = av == -INFINITY;
       const float e = dead ? 0.f : expf(av - mx);
       w_lds[m] = dead ? kDeadPath : e;
@@ -156,45 +140,19 @@ __global__ __launch_bounds__(kSmoothThreads) void pf_smooth_kernel(SmoothArgs a)
         if (m < M) {
           const float e = w_lds[m];
           if (e >= 0.f) atomicOr(&bitmap[b[k] >> 5], 1u << (b[k] & 31));
-          if (e > 0.f) {  // a path of zero weight contributes exactly zero, whatever its row holds
-            float dx[D];
-#pragma unroll
-            for (int c = 0; c < D; ++c) dx[c] = X[static_cast<size_t>(b[k]) * D + c] - p[c];
-            int v = D;
-#pragma unroll
-            for (int i = 0; i < D; ++i) {
-              acc[i] = acc[i] + e * dx[i];
-#pragma unroll
-              for (int j = i; j < D; ++j, ++v) acc[v] = acc[v] + (e * dx[i]) * dx[j];
-            }
-          }
+          // a path of zero weight contributes exactly zero, whatever its row holds
+          if (e > 0.f) pivot_accumulate<D>(acc, e, X + static_cast<size_t>(b[k]) * D, p);
         }
       }
-#pragma unroll
-      for (int v = 0; v < NS; ++v) {
-        const float r = mmf::wave_sum(acc[v]);
-        if (lane == 0) partial[v * kSmoothWaves + wave] = r;
-      }
-      __syncthreads();
-      if (tid < NS) {
-        float r = 0.f;
-        for (int w = 0; w < waves; ++w) r = r + partial[tid * kSmoothWaves + w];
-        total[tid] = r;
-      }
+      block_sums(acc, partial, total, kSmoothWaves, waves, tid);
       if (a.unique) {
         int c = 0;
         for (int i = tid; i < (M + 31) / 32; i += threads) c += __popc(bitmap[i]);
         if (c) atomicAdd(&misc[1], c);
       }
       __syncthreads();
-      const float S = total[NS];
       const size_t out = static_cast<size_t>(t) * a.N + n;
-      if (tid < D) a.mean[out * D + tid] = p[tid] + total[tid] / S;
-      if (a.cov && tid < D * D) {
-        const int r = tid / D, c = tid % D, i = min(r, c), j = max(r, c);
-        const int v = D + i * D - i * (i - 1) / 2 + (j - i);  // (i, j) of the upper triangle, row-major
-        a.cov[out * D * D + tid] = total[v] / S - (total[i] / S) * (total[j] / S);
-      }
+      write_moments<D>(a.mean, a.cov, out, tid, p, total, total[NS]);
       if (a.unique && tid == 0) a.unique[out] = misc[1];
       __syncthreads();  // the next written step reuses pivot, bitmap, partial and total
     }

@@ -13,18 +13,11 @@
 
 #include <cmath>
 
-#include "mmf_launch.h"
 #include "pf_smooth_math.h"
 
 namespace {
 
-using namespace mmf::smooth_math;  // the whitener, minus_sq_dist, Staged and the kPair* sizes, exp2_hw / log2_hw, kLog2e / kLn2
-
-constexpr int kMomentThreads = 256;
-constexpr int kMomentWaves = kMomentThreads / MMF_WAVE;
-constexpr int kMomentSums = MMF_MAX_STATE_DIM + MMF_MAX_STATE_DIM * (MMF_MAX_STATE_DIM + 1) / 2;
-static_assert(kPairChunk % kPairThreads == 0 && kPairChunk % kPairGroup == 0, "a chunk is staged and consumed whole");
-static_assert(kPairThreads == MMF_WAVE, "the sweep sums its trajectory's weights with one wave sum");
+using namespace mmf::smooth_math;  // the log-weights, the transition density, the staged chunks, the pivot-form moments
 
 struct MarginalArgs {
   const float* states;   // (T, N, M, D)
@@ -51,7 +44,7 @@ __global__ __launch_bounds__(kMomentThreads) void pf_marginal_weights_kernel(Mar
   const float* lw = a.logw ? a.logw + row0 : nullptr;
   float* out = a.weights + row0;
   float mx = -INFINITY;
-  for (int m = tid; m < M; m += kMomentThreads) mx = fmaxf(mx, lw ? ll[m] + lw[m] : ll[m]);
+  for (int m = tid; m < M; m += kMomentThreads) mx = fmaxf(mx, log_weight(ll, lw, m));
   mx = mmf::wave_max(mx);
   if ((tid & (MMF_WAVE - 1)) == 0) wmax[tid >> 6] = mx;
   __syncthreads();
@@ -59,7 +52,7 @@ __global__ __launch_bounds__(kMomentThreads) void pf_marginal_weights_kernel(Mar
   for (int w = 1; w < kMomentWaves; ++w) mx = fmaxf(mx, wmax[w]);
   const bool last = t == a.T - 1;
   for (int m = tid; m < M; m += kMomentThreads) {
-    const float av = lw ? ll[m] + lw[m] : ll[m];
+    const float av = log_weight(ll, lw, m);
     const float la = av == -INFINITY ? -INFINITY : av - mx;  // (every value -inf: stays -inf, the step's results are NaN)
     out[m] = last ? exp2_hw(la * kLog2e) : la;
   }
@@ -96,7 +89,7 @@ __global__ __launch_bounds__(kPairThreads) void pf_marginal_logd_kernel(Marginal
       row.store(lds, s);
     }
     __syncthreads();
-    const int rows = min(kPairChunk, (M - c0 + kPairGroup - 1) / kPairGroup * kPairGroup);  // the padding rows are dead
+    const int rows = padded_chunk(M, c0);
     for (int i0 = 0; i0 < rows; i0 += kPairGroup) {
       float v[kPairGroup];
       float top = mx;
@@ -107,7 +100,7 @@ __global__ __launch_bounds__(kPairThreads) void pf_marginal_logd_kernel(Marginal
         v[u] = minus_sq_dist<D>(row.w, x, row.x, W);
         top = fmaxf(top, v[u]);
       }
-      const float ref = top == -INFINITY ? 0.f : top;  // nothing alive so far: exp2(-inf - 0) = 0, not exp2(nan)
+      const float ref = rescale_ref(top);
       sum = sum * exp2_hw(mx - ref);
 #pragma unroll
       for (int u = 0; u < kPairGroup; ++u) sum = sum + exp2_hw(v[u] - ref);
@@ -152,7 +145,7 @@ __global__ __launch_bounds__(kPairThreads) void pf_marginal_sweep_kernel(Margina
       total = total + w;  // the same columns in the same order in every workgroup of the trajectory
     }
     __syncthreads();
-    const int cols = min(kPairChunk, (M - c0 + kPairGroup - 1) / kPairGroup * kPairGroup);
+    const int cols = padded_chunk(M, c0);
     for (int j0 = 0; j0 < cols; j0 += kPairGroup) {
 #pragma unroll
       for (int u = 0; u < kPairGroup; ++u) {
@@ -170,7 +163,7 @@ __global__ __launch_bounds__(kPairThreads) void pf_marginal_sweep_kernel(Margina
 template <int D>
 __global__ __launch_bounds__(kMomentThreads) void pf_marginal_moments_kernel(MarginalArgs a) {
 #pragma clang fp contract(off)
-  constexpr int NS = D + D * (D + 1) / 2;
+  constexpr int NS = moment_sums(D);
   __shared__ float partial[(kMomentSums + 2) * kMomentWaves];
   __shared__ float total[kMomentSums + 2];
   __shared__ float wtop[kMomentWaves];
@@ -186,7 +179,7 @@ __global__ __launch_bounds__(kMomentThreads) void pf_marginal_moments_kernel(Mar
     const float g = a.tril[r * D + r];
     bad = bad || !(g > 0.f) || !(g < INFINITY);
   }
-  // the pivot: the first largest weight (ascending m per thread, ties to the lower index)
+  // the pivot: the first largest weight
   float bv = -INFINITY, s1 = 0.f, s2 = 0.f;
   int bi = 0x7fffffff;
   for (int m = tid; m < M; m += kMomentThreads) {
@@ -195,26 +188,13 @@ __global__ __launch_bounds__(kMomentThreads) void pf_marginal_moments_kernel(Mar
     s1 = s1 + e;
     s2 = s2 + e * e;
   }
-  auto better = [](float v, int i, float u, int j) { return v > u || (v == u && i < j); };
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const float ov = __shfl_xor(bv, off);
-    const int oi = __shfl_xor(bi, off);
-    if (better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-  }
   s1 = mmf::wave_sum(s1);
   s2 = mmf::wave_sum(s2);
   if (lane == 0) {
-    wtop[wave] = bv; witop[wave] = bi;
     partial[NS * kMomentWaves + wave] = s1;
     partial[(NS + 1) * kMomentWaves + wave] = s2;
   }
-  __syncthreads();
-  bv = wtop[0];
-  bi = witop[0];  // every thread combines the waves' candidates in the same order: one pivot for the workgroup
-  for (int k = 1; k < kMomentWaves; ++k)
-    if (better(wtop[k], witop[k], bv, bi)) { bv = wtop[k]; bi = witop[k]; }
-  if (bi < 0 || bi >= M) bi = 0;  // every weight NaN: the result is NaN either way, the reads stay in range
+  first_max(bv, bi, wtop, witop, tid, kMomentWaves, M);  // (its barrier orders the partials too)
   float S = 0.f, S2 = 0.f;
   for (int k = 0; k < kMomentWaves; ++k) { S = S + partial[NS * kMomentWaves + k]; S2 = S2 + partial[(NS + 1) * kMomentWaves + k]; }
   if (bad) S = NAN;
@@ -225,43 +205,16 @@ __global__ __launch_bounds__(kMomentThreads) void pf_marginal_moments_kernel(Mar
   for (int v = 0; v < NS; ++v) acc[v] = 0.f;
   for (int m = tid; m < M; m += kMomentThreads) {
     const float e = w[m];
-    if (e != 0.f) {  // a particle of zero weight contributes exactly zero, whatever its row holds
-      float dx[D];
-#pragma unroll
-      for (int c = 0; c < D; ++c) dx[c] = X[static_cast<size_t>(m) * D + c] - p[c];
-      int v = D;
-#pragma unroll
-      for (int i = 0; i < D; ++i) {
-        acc[i] = acc[i] + e * dx[i];
-#pragma unroll
-        for (int j = i; j < D; ++j, ++v) acc[v] = acc[v] + (e * dx[i]) * dx[j];
-      }
-    }
+    // a particle of zero weight contributes exactly zero, whatever its row holds
+    if (e != 0.f) pivot_accumulate<D>(acc, e, X + static_cast<size_t>(m) * D, p);
     w[m] = e / S;
   }
-#pragma unroll
-  for (int v = 0; v < NS; ++v) {
-    const float r = mmf::wave_sum(acc[v]);
-    if (lane == 0) partial[v * kMomentWaves + wave] = r;
-  }
-  __syncthreads();
-  if (tid < NS) {
-    float r = 0.f;
-    for (int k = 0; k < kMomentWaves; ++k) r = r + partial[tid * kMomentWaves + k];
-    total[tid] = r;
-  }
+  block_sums(acc, partial, total, kMomentWaves, kMomentWaves, tid);
   __syncthreads();
   const size_t out = static_cast<size_t>(t) * a.N + n;
-  if (tid < D) a.mean[out * D + tid] = p[tid] + total[tid] / S;
-  if (a.cov && tid < D * D) {
-    const int r = tid / D, c = tid % D, i = min(r, c), j = max(r, c);
-    const int v = D + i * D - i * (i - 1) / 2 + (j - i);  // (i, j) of the upper triangle, row-major
-    a.cov[out * D * D + tid] = total[v] / S - (total[i] / S) * (total[j] / S);
-  }
+  write_moments<D>(a.mean, a.cov, out, tid, p, total, S);
   if (a.ess && tid == 0) a.ess[out] = (S * S) / S2;
 }
-
-constexpr int kMaxGridZ = 65535;
 
 }  // namespace
 
@@ -269,7 +222,7 @@ extern "C" int mmf_pf_smooth_marginal(const MmfPfSmoothMarginalArgs* a, void* st
   if (!a || !a->states_steps || !a->loglik_steps || !a->scale_tril || !a->weights || !a->mean) return MMF_EINVAL;
   if (a->T < 0 || a->N < 0 || a->M < 1 || a->d < 1) return MMF_EINVAL;
   if (a->T >= 2 && (!a->pred_steps || !a->logd)) return MMF_EINVAL;
-  if (a->d > MMF_MAX_STATE_DIM || a->M > 65536 || a->N > 65535) return MMF_ETOOLARGE;
+  if (!sizes_in_range(a->M, a->N, a->d)) return MMF_ETOOLARGE;
   if (a->N == 0 || a->T == 0) return 0;
   MarginalArgs k{};
   k.states = a->states_steps; k.pred = a->pred_steps; k.loglik = a->loglik_steps; k.logw = a->logw_in_steps;
@@ -281,11 +234,7 @@ extern "C" int mmf_pf_smooth_marginal(const MmfPfSmoothMarginalArgs* a, void* st
   return mmf::with_state_dim(a->d, [&](auto D) -> int {
     constexpr int d = decltype(D)::value;
     if (const int rc = mmf::launch(pf_marginal_weights_kernel, dim3(T, N), kMomentThreads, 0, s, k)) return rc;
-    for (int t0 = 0; t0 < T - 1; t0 += kMaxGridZ) {  // all steps are independent: one launch (the grid's z holds 65535 of them)
-      k.t0 = t0;
-      const int steps = T - 1 - t0 < kMaxGridZ ? T - 1 - t0 : kMaxGridZ;
-      if (const int rc = mmf::launch(pf_marginal_logd_kernel<d>, dim3(tiles, N, steps), kPairThreads, 0, s, k)) return rc;
-    }
+    if (const int rc = launch_steps(pf_marginal_logd_kernel<d>, tiles, N, T - 1, s, k)) return rc;
     for (int t = T - 2; t >= 0; --t) {
       k.t0 = t;
       if (const int rc = mmf::launch(pf_marginal_sweep_kernel<d>, dim3(tiles, N), kPairThreads, 0, s, k)) return rc;

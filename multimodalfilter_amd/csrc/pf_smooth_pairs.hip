@@ -13,17 +13,13 @@
 
 #include <cmath>
 
-#include "mmf_launch.h"
 #include "pf_smooth_math.h"
 
 namespace {
 
-using namespace mmf::smooth_math;  // the whitener, minus_sq_dist_dx, Staged and the kPair* sizes, exp2_hw / log2_hw, kLog2e
+using namespace mmf::smooth_math;  // the log-weights, the transition density, the staged chunks, moment_sums / tri_index
 
-static_assert(kPairThreads == MMF_WAVE, "a pairs workgroup is one wave: its sums are wave sums");
-static_assert(kPairChunk % kPairThreads == 0 && kPairChunk % kPairGroup == 0, "a chunk is staged and consumed whole");
-
-constexpr int sums_of(int d) { return 1 + d + d * (d + 1) / 2; }  // the total, p e, the upper triangle of p e e^T
+constexpr int sums_of(int d) { return 1 + moment_sums(d); }  // the total, p e, the upper triangle of p e e^T
 
 struct PairArgs {
   const float* states;   // (T, N, M, D)
@@ -56,13 +52,9 @@ __global__ __launch_bounds__(kPairThreads) void pf_pair_sums_kernel(PairArgs a) 
   const float* ll = a.loglik + rows_t;
   const float* lw = a.logw ? a.logw + rows_t : nullptr;
   float mx = -INFINITY;
-  for (int m = tid; m < M; m += kPairThreads) mx = fmaxf(mx, lw ? ll[m] + lw[m] : ll[m]);
+  for (int m = tid; m < M; m += kPairThreads) mx = fmaxf(mx, log_weight(ll, lw, m));
   mx = mmf::wave_max(mx);
-  float la = -INFINITY;
-  if (i < M) {
-    const float av = lw ? ll[i] + lw[i] : ll[i];
-    la = av == -INFINITY ? -INFINITY : (av - mx) * kLog2e;
-  }
+  const float la = i < M ? log2_weight(log_weight(ll, lw, i), mx) : -INFINITY;
   float f[D];
   {
     const bool dead = la == -INFINITY;  // no weight: the row is skipped, its prediction may hold anything
@@ -87,7 +79,7 @@ __global__ __launch_bounds__(kPairThreads) void pf_pair_sums_kernel(PairArgs a) 
       col.store(lds, s);
     }
     __syncthreads();
-    const int cols = min(kPairChunk, (M - c0 + kPairGroup - 1) / kPairGroup * kPairGroup);  // the padding columns are skipped ones
+    const int cols = padded_chunk(M, c0);
     for (int j0 = 0; j0 < cols; j0 += kPairGroup) {
 #pragma unroll
       for (int u = 0; u < kPairGroup; ++u) {
@@ -134,14 +126,9 @@ __global__ __launch_bounds__(kPairThreads) void pf_pair_reduce_kernel(PairArgs a
   if (tid < D) a.mean[out * D + tid] = total[1 + tid] / S;
   if (tid < D * D) {
     const int r = tid / D, c = tid % D, i = min(r, c), j = max(r, c);
-    const int v = 1 + D + i * D - i * (i - 1) / 2 + (j - i);  // (i, j) of the upper triangle, row-major
-    a.second[out * D * D + tid] = total[v] / S;
+    a.second[out * D * D + tid] = total[1 + tri_index<D>(i, j)] / S;
   }
 }
-
-constexpr int kMaxGridZ = 65535;
-
-bool sizes_in_range(int M, int N, int d) { return d <= MMF_MAX_STATE_DIM && M <= 65536 && N <= 65535; }
 
 }  // namespace
 
@@ -167,11 +154,7 @@ extern "C" int mmf_pf_smooth_pair_moments(const MmfPfSmoothPairArgs* a, void* st
   const int T = a->T, N = a->N, tiles = k.tiles;
   return mmf::with_state_dim(a->d, [&](auto D) -> int {
     constexpr int d = decltype(D)::value;
-    for (int t0 = 0; t0 < T - 1; t0 += kMaxGridZ) {  // all steps are independent: one launch (the grid's z holds 65535 of them)
-      k.t0 = t0;
-      const int steps = T - 1 - t0 < kMaxGridZ ? T - 1 - t0 : kMaxGridZ;
-      if (const int rc = mmf::launch(pf_pair_sums_kernel<d>, dim3(tiles, N, steps), kPairThreads, 0, s, k)) return rc;
-    }
+    if (const int rc = launch_steps(pf_pair_sums_kernel<d>, tiles, N, T - 1, s, k)) return rc;
     return mmf::launch(pf_pair_reduce_kernel<d>, dim3(T - 1, N), kPairThreads, 0, s, k);
   });
 }

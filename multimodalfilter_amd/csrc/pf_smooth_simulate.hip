@@ -14,7 +14,6 @@
 #include <climits>
 #include <cmath>
 
-#include "mmf_launch.h"
 #include "pf_smooth_math.h"
 
 namespace {
@@ -28,9 +27,6 @@ constexpr int kSimWaves = kSimThreads / MMF_WAVE;
 #endif
 constexpr int kSimDraws = MMF_SIM_DRAWS;  // B: draws of a workgroup, the tuning constant (DESIGN.md has the values measured)
 constexpr int kSimRows = 4;    // rows of a thread's segment staged per chunk, at most: a chunk is kSimThreads * kSimRows rows, whatever M is
-constexpr int kMomentThreads = 256;
-constexpr int kMomentWaves = kMomentThreads / MMF_WAVE;
-constexpr int kMomentSums = MMF_MAX_STATE_DIM + MMF_MAX_STATE_DIM * (MMF_MAX_STATE_DIM + 1) / 2;
 static_assert(kSimDraws <= MMF_WAVE && kSimDraws <= kSimThreads, "one thread per draw sets a step up");
 
 struct SimulateArgs {
@@ -63,9 +59,6 @@ __device__ __forceinline__ float lane_value(float v, int lane) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
 }
 
-// log2 of the unnormalised weight of a particle, relative to the step's largest: -inf stays -inf (every value -inf included)
-__device__ __forceinline__ float log2_weight(float a, float amax) { return a == -INFINITY ? -INFINITY : (a - amax) * kLog2e; }
-
 // ---- simulate: kSimDraws joint draws of trajectory blockIdx.y, all steps
 // ROWS: the rows of a segment staged per chunk, 1, 2 or kSimRows: min(kSimRows, the segment rounded up to a power of two)
 template <int D, int ROWS>
@@ -97,7 +90,7 @@ __global__ __launch_bounds__(kSimThreads) void pf_simulate_kernel(SimulateArgs a
     const float* F = t < T - 1 ? a.pred + row0 * D : nullptr;
     // the step's largest log-weight
     float amax = -INFINITY;
-    for (int i = tid; i < M; i += kSimThreads) amax = fmaxf(amax, lw ? ll[i] + lw[i] : ll[i]);
+    for (int i = tid; i < M; i += kSimThreads) amax = fmaxf(amax, log_weight(ll, lw, i));
     amax = mmf::wave_max(amax);
     if (lane == 0) amax_w[wave] = amax;
     if (tid < B) {
@@ -122,7 +115,7 @@ __global__ __launch_bounds__(kSimThreads) void pf_simulate_kernel(SimulateArgs a
         const int i = owner * seg + k0 + r;
         float v[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
         float w = -INFINITY;
-        if (k0 + r < seg && i < M) w = log2_weight(lw ? ll[i] + lw[i] : ll[i], amax);
+        if (k0 + r < seg && i < M) w = log2_weight(log_weight(ll, lw, i), amax);
         if (F && w != -INFINITY) {  // a dead row may hold anything: it is not read
 #pragma unroll
           for (int c = 0; c < D; ++c) v[c] = F[static_cast<size_t>(i) * D + c];
@@ -154,7 +147,7 @@ __global__ __launch_bounds__(kSimThreads) void pf_simulate_kernel(SimulateArgs a
           v[r] = minus_sq_dist<D>(w[r], x, f[r], W);
           hi = fmaxf(hi, v[r]);  // (a NaN is not a maximum; it reaches the sum through its own exp2)
         }
-        const float ref = hi == -INFINITY ? 0.f : hi;  // nothing alive so far: exp2(-inf - 0) = 0, not exp2(nan)
+        const float ref = rescale_ref(hi);
         float acc = sum[b] * exp2_hw(top[b] - ref);
 #pragma unroll
         for (int r = 0; r < ROWS; ++r) acc = acc + exp2_hw(v[r] - ref);
@@ -233,7 +226,7 @@ __global__ __launch_bounds__(kSimThreads) void pf_simulate_kernel(SimulateArgs a
           float f[D], w = -INFINITY;
 #pragma unroll
           for (int c = 0; c < D; ++c) f[c] = 0.f;
-          if (q0 + lane < seg && i < M) w = log2_weight(lw ? ll[i] + lw[i] : ll[i], amax);
+          if (q0 + lane < seg && i < M) w = log2_weight(log_weight(ll, lw, i), amax);
           if (F && w != -INFINITY) {
 #pragma unroll
             for (int c = 0; c < D; ++c) f[c] = F[static_cast<size_t>(i) * D + c];
@@ -274,11 +267,10 @@ __global__ __launch_bounds__(kSimThreads) void pf_simulate_kernel(SimulateArgs a
 template <int D>
 __global__ __launch_bounds__(kMomentThreads) void pf_simulate_moments_kernel(SimulateArgs a) {
 #pragma clang fp contract(off)
-  constexpr int NS = D + D * (D + 1) / 2;
+  constexpr int NS = moment_sums(D);
   __shared__ float partial[kMomentSums * kMomentWaves];
   __shared__ float total[kMomentSums];
-  const int tid = threadIdx.x, lane = tid & (MMF_WAVE - 1), wave = tid >> 6;
-  const int t = blockIdx.x, n = blockIdx.y, S = a.S;
+  const int tid = threadIdx.x, t = blockIdx.x, n = blockIdx.y, S = a.S;
   const size_t out = static_cast<size_t>(t) * a.N + n;
   const float* X = a.traj + out * S * D;
   float p[D], acc[NS];
@@ -286,37 +278,11 @@ __global__ __launch_bounds__(kMomentThreads) void pf_simulate_moments_kernel(Sim
   for (int c = 0; c < D; ++c) p[c] = X[c];
 #pragma unroll
   for (int v = 0; v < NS; ++v) acc[v] = 0.f;
-  for (int s = tid; s < S; s += kMomentThreads) {
-    float dx[D];
-#pragma unroll
-    for (int c = 0; c < D; ++c) dx[c] = X[static_cast<size_t>(s) * D + c] - p[c];  // a dead draw: NaN, and so is the step
-    int v = D;
-#pragma unroll
-    for (int i = 0; i < D; ++i) {
-      acc[i] = acc[i] + dx[i];
-#pragma unroll
-      for (int j = i; j < D; ++j, ++v) acc[v] = acc[v] + dx[i] * dx[j];
-    }
-  }
-#pragma unroll
-  for (int v = 0; v < NS; ++v) {
-    const float r = mmf::wave_sum(acc[v]);
-    if (lane == 0) partial[v * kMomentWaves + wave] = r;
-  }
+  // every draw weighs one (the multiplication by it is exact); a dead draw: NaN, and so is the step
+  for (int s = tid; s < S; s += kMomentThreads) pivot_accumulate<D>(acc, 1.f, X + static_cast<size_t>(s) * D, p);
+  block_sums(acc, partial, total, kMomentWaves, kMomentWaves, tid);
   __syncthreads();
-  if (tid < NS) {
-    float r = 0.f;
-    for (int k = 0; k < kMomentWaves; ++k) r = r + partial[tid * kMomentWaves + k];
-    total[tid] = r;
-  }
-  __syncthreads();
-  const float count = static_cast<float>(S);
-  if (tid < D) a.mean[out * D + tid] = p[tid] + total[tid] / count;
-  if (a.cov && tid < D * D) {
-    const int r = tid / D, c = tid % D, i = min(r, c), j = max(r, c);
-    const int v = D + i * D - i * (i - 1) / 2 + (j - i);  // (i, j) of the upper triangle, row-major
-    a.cov[out * D * D + tid] = total[v] / count - (total[i] / count) * (total[j] / count);
-  }
+  write_moments<D>(a.mean, a.cov, out, tid, p, total, static_cast<float>(S));
 }
 
 }  // namespace
@@ -326,7 +292,7 @@ extern "C" int mmf_pf_smooth_simulate(const MmfPfSmoothSimulateArgs* a, void* st
     return MMF_EINVAL;
   if (a->T < 0 || a->N < 0 || a->M < 1 || a->d < 1 || a->S < 1) return MMF_EINVAL;
   if (a->T >= 2 && !a->pred_steps) return MMF_EINVAL;
-  if (a->d > MMF_MAX_STATE_DIM || a->M > 65536 || a->N > 65535 || a->S > 65535) return MMF_ETOOLARGE;
+  if (!sizes_in_range(a->M, a->N, a->d) || a->S > 65535) return MMF_ETOOLARGE;
   if (a->N == 0 || a->T == 0) return 0;
   SimulateArgs k{};
   k.states = a->states_steps; k.pred = a->pred_steps; k.loglik = a->loglik_steps; k.logw = a->logw_in_steps;

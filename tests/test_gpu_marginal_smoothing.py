@@ -17,7 +17,7 @@ from oracle import models as om
 
 from _tol import REL_TOL, rel_err
 
-CHUNK = 256  # rows / columns the pair kernels stage at a time (csrc/pf_smooth_marginal.hip: kPairChunk)
+CHUNK = 256  # rows / columns the pair kernels stage at a time (csrc/pf_smooth_math.h: kPairChunk)
 
 
 def _dev():
@@ -145,7 +145,7 @@ _WIDTHS = (1e-3, 1e-2, 0.3)
 
 
 @pytest.mark.parametrize("ll_scale", [0.5, 50.0])
-@pytest.mark.parametrize("d", [2, 3, 4])
+@pytest.mark.parametrize("d", [1, 2, 3, 4])
 @pytest.mark.parametrize("M", [1, 37, 300, 2 * CHUNK + 88])
 def test_marginal_kernels_match_fp64(M, d, ll_scale):
     """Three trajectories of widths 1e-3 / 1e-2 / 0.3 per call, T = 5; the process noise once diagonal and once a full lower

@@ -85,7 +85,7 @@ def _check(got, want, what):
 
 # ------------------------------------------------------------------------------------------ 1. kernels against fp64
 @pytest.mark.parametrize("ll_scale", [0.5, 50.0])
-@pytest.mark.parametrize("d", [2, 3, 4])
+@pytest.mark.parametrize("d", [1, 2, 3, 4])
 @pytest.mark.parametrize("M", [1, 37, 300, 2 * CHUNK + 88])
 def test_pair_kernels_match_fp64(M, d, ll_scale):
     """Three trajectories of widths 1e-3 / 1e-2 / 0.3 per call, T = 5; the process noise once diagonal and once a full lower

@@ -197,6 +197,7 @@ _CASES = [
     (257, 3, 6, 70, 1, True, True, 0.3),
     (512, 2, 6, 70, 1, True, True, 0.3),
     (513, 2, 6, 70, 1, True, True, 0.3),
+    (1100, 1, 6, 70, 3, True, False, 0.05),
 ]
 _IDS = ["M{}-d{}-T{}-S{}-N{}-{}-{}-x{}".format(M, d, T, S, N, "lw" if lw else "nolw", "full" if full else "diag", k)
         for M, d, T, S, N, lw, full, k in _CASES]

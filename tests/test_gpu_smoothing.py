@@ -117,7 +117,7 @@ _WIDTHS = (1e-3, 1e-2, 0.3)
 
 
 @pytest.mark.parametrize("ll_scale", [0.5, 5.0, 50.0])
-@pytest.mark.parametrize("d", [2, 3, 4])
+@pytest.mark.parametrize("d", [1, 2, 3, 4])
 @pytest.mark.parametrize("M", [1, 37, 300, 1100])
 def test_smooth_kernel_matches_fp64(M, d, ll_scale):
     """The issue's grid: three trajectories of widths 1e-3 / 1e-2 / 0.3 per call, T = 9, lags 0 / 2 / 12 (full), the
