@@ -897,6 +897,18 @@ def pf_smooth(states_steps, loglik_steps, logw_in_steps, logw_in0, indices_steps
         _check(load().mmf_pf_smooth(ctypes.byref(a), stream_of(states_steps)), "mmf_pf_smooth")
 
 
+def _smooth_history(a, states_steps, pred_steps, loglik_steps, logw_in_steps, scale_tril):
+    """The history the marginal, pair-moment and simulation smoothers share, checked and put into their struct ``a``: the
+    sizes and the five inputs; ``pred_steps`` is required from ``T = 2`` on and passed as null below (no transition)."""
+    T, N, M, d = states_steps.shape
+    assert loglik_steps.shape == (T, N, M) and scale_tril.shape == (d, d)
+    assert logw_in_steps is None or logw_in_steps.shape == (T, N, M)
+    assert T < 2 or (pred_steps is not None and pred_steps.shape == (T - 1, N, M, d))
+    a.T, a.N, a.M, a.d = T, N, M, d
+    a.states_steps, a.pred_steps = vp(states_steps), vp(pred_steps if T >= 2 else None)
+    a.loglik_steps, a.logw_in_steps, a.scale_tril = vp(loglik_steps), vp(logw_in_steps), vp(scale_tril)
+
+
 def pf_smooth_marginal(states_steps, pred_steps, loglik_steps, logw_in_steps, scale_tril, weights, mean, cov=None, ess=None,
                        logd=None):
     """Marginal (forward-filter backward-smoothing) particle smoothing of a filter run's history
@@ -905,22 +917,18 @@ def pf_smooth_marginal(states_steps, pred_steps, loglik_steps, logw_in_steps, sc
     ``None`` (uniform), ``scale_tril (d, d)`` on the device -> ``weights (T, N, M)``, ``mean (T, N, d)``, ``cov (T, N, d, d)``
     and ``ess (T, N)``, each of the last two or ``None``.  ``logd``: the ``(T - 1, N, M)`` workspace, allocated when ``None``."""
     T, N, M, d = states_steps.shape
-    assert loglik_steps.shape == (T, N, M) and weights.shape == (T, N, M) and mean.shape == (T, N, d)
-    assert logw_in_steps is None or logw_in_steps.shape == (T, N, M)
-    assert scale_tril.shape == (d, d)
+    assert weights.shape == (T, N, M) and mean.shape == (T, N, d)
     assert cov is None or cov.shape == (T, N, d, d)
     assert ess is None or ess.shape == (T, N)
     if T >= 2:
-        assert pred_steps is not None and pred_steps.shape == (T - 1, N, M, d)
         if logd is None:
             logd = torch.empty((T - 1, N, M), dtype=torch.float32, device=states_steps.device)
         assert logd.shape == (T - 1, N, M)
     else:
-        pred_steps = logd = None
+        logd = None
     a = MmfPfSmoothMarginalArgs()
-    a.T, a.N, a.M, a.d = T, N, M, d
-    a.states_steps, a.pred_steps, a.loglik_steps, a.logw_in_steps = vp(states_steps), vp(pred_steps), vp(loglik_steps), vp(logw_in_steps)
-    a.scale_tril, a.logd, a.weights, a.mean, a.cov, a.ess = vp(scale_tril), vp(logd), vp(weights), vp(mean), vp(cov), vp(ess)
+    _smooth_history(a, states_steps, pred_steps, loglik_steps, logw_in_steps, scale_tril)
+    a.logd, a.weights, a.mean, a.cov, a.ess = vp(logd), vp(weights), vp(mean), vp(cov), vp(ess)
     with _on(states_steps):
         _check(load().mmf_pf_smooth_marginal(ctypes.byref(a), stream_of(states_steps)), "mmf_pf_smooth_marginal")
 
@@ -938,23 +946,19 @@ def pf_smooth_pair_moments(states_steps, pred_steps, loglik_steps, logw_in_steps
     allocated when ``None``.  ``T < 2``: there is no transition, nothing is written."""
     T, N, M, d = states_steps.shape
     Tm = max(T - 1, 0)
-    assert loglik_steps.shape == (T, N, M) and weights.shape == (T, N, M)
-    assert logw_in_steps is None or logw_in_steps.shape == (T, N, M)
-    assert scale_tril.shape == (d, d)
+    assert weights.shape == (T, N, M)
     assert residual_mean.shape == (Tm, N, d) and residual_second_moment.shape == (Tm, N, d, d)
     if T >= 2:
-        assert pred_steps is not None and pred_steps.shape == (T - 1, N, M, d)
         assert logd is not None and logd.shape == (T - 1, N, M)
         need = pf_smooth_pair_workspace_floats(T, N, M, d)
         if workspace is None:
             workspace = torch.empty((max(need, 1),), dtype=torch.float32, device=states_steps.device)
         assert workspace.numel() >= need
     else:
-        pred_steps = logd = workspace = None
+        logd = workspace = None
     a = MmfPfSmoothPairArgs()
-    a.T, a.N, a.M, a.d = T, N, M, d
-    a.states_steps, a.pred_steps, a.loglik_steps, a.logw_in_steps = vp(states_steps), vp(pred_steps), vp(loglik_steps), vp(logw_in_steps)
-    a.scale_tril, a.weights, a.logd, a.workspace = vp(scale_tril), vp(weights), vp(logd), vp(workspace)
+    _smooth_history(a, states_steps, pred_steps, loglik_steps, logw_in_steps, scale_tril)
+    a.weights, a.logd, a.workspace = vp(weights), vp(logd), vp(workspace)
     a.residual_mean, a.residual_second_moment = vp(residual_mean), vp(residual_second_moment)
     with _on(states_steps):
         _check(load().mmf_pf_smooth_pair_moments(ctypes.byref(a), stream_of(states_steps)), "mmf_pf_smooth_pair_moments")
@@ -970,19 +974,12 @@ def pf_smooth_simulate(states_steps, pred_steps, loglik_steps, logw_in_steps, sc
     T, N, M, d = states_steps.shape
     assert uniforms.dim() == 3 and uniforms.shape[:2] == (T, N)
     S = uniforms.shape[2]
-    assert loglik_steps.shape == (T, N, M) and mean.shape == (T, N, d)
+    assert mean.shape == (T, N, d)
     assert indices.shape == (T, N, S) and trajectories.shape == (T, N, S, d)
-    assert logw_in_steps is None or logw_in_steps.shape == (T, N, M)
-    assert scale_tril.shape == (d, d)
     assert cov is None or cov.shape == (T, N, d, d)
-    if T >= 2:
-        assert pred_steps is not None and pred_steps.shape == (T - 1, N, M, d)
-    else:
-        pred_steps = None
     a = MmfPfSmoothSimulateArgs()
-    a.T, a.N, a.M, a.d, a.S = T, N, M, d, S
-    a.states_steps, a.pred_steps, a.loglik_steps, a.logw_in_steps = vp(states_steps), vp(pred_steps), vp(loglik_steps), vp(logw_in_steps)
-    a.scale_tril, a.uniforms, a.indices, a.trajectories = vp(scale_tril), vp(uniforms), vp(indices, torch.int32), vp(trajectories)
-    a.mean, a.cov = vp(mean), vp(cov)
+    _smooth_history(a, states_steps, pred_steps, loglik_steps, logw_in_steps, scale_tril)
+    a.S, a.uniforms, a.indices = S, vp(uniforms), vp(indices, torch.int32)
+    a.trajectories, a.mean, a.cov = vp(trajectories), vp(mean), vp(cov)
     with _on(states_steps):
         _check(load().mmf_pf_smooth_simulate(ctypes.byref(a), stream_of(states_steps)), "mmf_pf_smooth_simulate")

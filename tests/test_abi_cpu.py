@@ -26,7 +26,7 @@ def test_library_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in include/mmf.h but not exported"
     assert set(declared) == set(_abi.SIGNATURES), "ctypes binding and header disagree"
-    assert _abi.load().mmf_version() == _abi.ABI_VERSION
+    assert _abi.load().mmf_version() == _abi.ABI_VERSION == 42  # (the literal: a bump of the ABI number is made here on purpose)
 
 
 def test_status_word_names_of_header_and_binding_agree():
@@ -189,20 +189,25 @@ def test_size_limits_and_empty_batches_at_the_boundary():
 
 
 def test_every_host_struct_of_the_binding_matches_the_header_field_by_field(tmp_path):
-    """The ctypes structures of ``_abi.py`` against ``include/mmf.h`` as a C compiler lays it out: a small C program
-    (gcc, the header compiled as plain C) prints ``sizeof`` and the ``offsetof`` of every field, which must equal
-    ctypes' -- a field added to one side only, or in another order, fails here instead of corrupting a launch."""
+    """The ctypes structures of ``_abi.py`` against ``include/mmf.h`` as a C compiler lays it out -- every
+    ``ctypes.Structure`` the binding defines and every ``} MmfXxx;`` typedef of the header, which must be the same names: a
+    small C program (gcc, the header compiled as plain C) prints ``sizeof`` and the ``offsetof`` of every field, which must
+    equal ctypes' -- a field added to one side only, or in another order, fails here instead of corrupting a launch."""
     import shutil
     import subprocess
 
     from multimodalfilter_amd import _abi
 
+    text = open(os.path.join(ROOT, "include", "mmf.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    declared = set(re.findall(r"^\}\s*(Mmf\w+)\s*;", text, re.M))
+    bound = {name for name, cls in vars(_abi).items()
+             if isinstance(cls, type) and issubclass(cls, ctypes.Structure) and cls.__module__ == _abi.__name__}
+    assert declared == bound, ("only in include/mmf.h", sorted(declared - bound), "only in _abi.py", sorted(bound - declared))
     gcc = shutil.which("gcc")
     if gcc is None:
-        import pytest
         pytest.skip("no gcc")
-    structs = ["MmfParticleNetDesc", "MmfImageEncoderDesc", "MmfPfLoopArgs", "MmfTrainNet", "MmfPfTrainArgs", "MmfTrajInstr",
-               "MmfEkfLoopArgs"]
+    structs = sorted(bound)
     lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{os.path.join(ROOT, "include", "mmf.h")}"', "int main(void) {"]
     for name in structs:
         cls = getattr(_abi, name)

@@ -1,9 +1,10 @@
 """Marginal (forward-filter backward-smoothing) particle smoothing on the GPU (``include/mmf.h``: ``mmf_pf_smooth_marginal``;
 ``ParticleFilter.smooth(method="marginal")`` / ``evaluation.run_filter(smooth_method=)``).
 
-The kernels are held to an fp64 restatement of the definition (``_reference`` below) at the project's bar (``_tol.REL_TOL``
-through ``rel_err``, per trajectory so that a narrow cloud is measured against its own scale); the weights to the bar against
-the norm of their row, the ESS to 1e-4 relative.  The forward side is held to the loop it stands for, bit for bit."""
+The kernels are held to an fp64 restatement of the definition (``_smooth_cases.reference`` with the difference ``X - F`` in
+fp64: ``_reference64`` below) at the project's bar (``_tol.REL_TOL`` through ``rel_err``, per trajectory so that a narrow cloud
+is measured against its own scale); the weights to the bar against the norm of their row, the ESS to 1e-4 relative.  The
+forward side is held to the loop it stands for, bit for bit."""
 import functools
 import math
 
@@ -13,114 +14,27 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from oracle import models as om
-
+import _smooth_cases as sc
 from _tol import REL_TOL, rel_err
 
 CHUNK = 256  # rows / columns the pair kernels stage at a time (csrc/pf_smooth_math.h: kPairChunk)
 
 
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a real MI355X")
-    return torch.device("cuda:0")
-
-
-# ------------------------------------------------------------------------------------------ the fp64 reference
-def _softmax_rows(a):
-    """``softmax`` over the last axis in fp64; ``-inf`` gives exactly 0."""
-    a = np.asarray(a, dtype=np.float64)
-    e = np.exp(a - a.max(-1, keepdims=True))
-    return e / e.sum(-1, keepdims=True)
-
-
-def _moments(X, W):
-    """Mean, covariance and ``1 / sum W^2`` of ``X (..., M, d)`` under ``W (..., M)`` in fp64; rows of zero weight are not read."""
-    X = np.where((W > 0)[..., None], np.asarray(X, dtype=np.float64), 0.0)
-    mean = np.einsum("...m,...md->...d", W, X)
-    dx = np.where((W > 0)[..., None], X - mean[..., None, :], 0.0)
-    return mean, np.einsum("...m,...mi,...mj->...ij", W, dx, dx), 1.0 / (W * W).sum(-1)
-
-
-def _reference(X, F, ll, lw, L):
-    """Definition of ``mmf_pf_smooth_marginal`` in fp64 numpy: ``X (T, N, M, d)``, ``F (T - 1, N, M, d)``, ``ll (T, N, M)``,
-    ``lw (T, N, M)`` or None, ``L (d, d)`` -> weights, mean, cov, ess.  Particles of zero weight are left out of every sum."""
-    T, N, M, d = X.shape
-    a = ll.astype(np.float64) + (0.0 if lw is None else lw.astype(np.float64))
-    W = _softmax_rows(a)
-    Linv = np.linalg.inv(np.tril(np.asarray(L, dtype=np.float64)))
-    S = np.zeros((T, N, M))
-    S[T - 1] = W[T - 1]
-    for n in range(N):
-        for t in range(T - 2, -1, -1):
-            rows, cols = np.flatnonzero(W[t, n] > 0), np.flatnonzero(S[t + 1, n] > 0)
-            diff = X[t + 1, n][cols].astype(np.float64)[None, :, :] - F[t, n][rows].astype(np.float64)[:, None, :]
-            z = diff @ Linv.T
-            term = np.log(W[t, n][rows])[:, None] - 0.5 * (z * z).sum(-1)
-            top = term.max(0)
-            logD = top + np.log(np.exp(term - top).sum(0))
-            w = (S[t + 1, n][cols][None, :] * np.exp(term - logD[None, :])).sum(1)
-            S[t, n][rows] = w / w.sum()
-    return (S,) + _moments(X, S)
-
-
-def _systematic(w, u):
-    """Ancestors of systematic resampling (numpy, fp64): positions ``(u + k) / M`` in the CDF of ``w``."""
-    M = len(w)
-    cdf = np.cumsum(w / w.sum())
-    cdf[-1] = 1.0
-    return np.minimum(np.searchsorted(cdf, (u + np.arange(M)) / M, side="right"), M - 1)
-
-
-def _tril(d, full, scale=0.02, seed=5):
-    """The process noise of the kernel cases: 0.01 .. 0.04 wide, diagonal or a full lower triangle."""
-    L = np.diag(scale * np.array([1.0, 0.5, 2.0, 1.5])[:d])
-    if full:
-        L = L + np.tril(0.4 * scale * np.random.default_rng(seed).normal(size=(d, d)), -1)
-    return L.astype(np.float32)
-
-
-def _make_case(T, N, M, d, widths, ll_scale, L, seed):
-    """A run a filter could have left: step 0 is a cloud of the trajectory's width around an O(1) centre; every later set is
-    drawn around the predictions ``F_t = X_t + drift_t`` of ancestors resampled systematically from the step's own weights
-    (so the transition densities are not all negligible), with noise ``L``."""
-    rng = np.random.default_rng(seed)
-    widths = np.resize(np.asarray(widths, dtype=np.float64), N)
-    X = np.zeros((T, N, M, d), dtype=np.float32)
-    F = np.zeros((max(T - 1, 0), N, M, d), dtype=np.float32)
-    ll = (ll_scale * rng.normal(size=(T, N, M))).astype(np.float32)
-    lw = 0.3 * rng.normal(size=(T, N, M))
-    lw = (lw - np.log(np.exp(lw).sum(-1, keepdims=True))).astype(np.float32)
-    X[0] = rng.normal(size=(N, 1, d)) + widths[:, None, None] * rng.normal(size=(N, M, d))
-    for t in range(T - 1):
-        F[t] = X[t] + 0.05 * rng.normal(size=(N, 1, d))
-        for n in range(N):
-            a = ll[t, n].astype(np.float64) + lw[t, n]
-            A = _systematic(np.exp(a - a.max()), rng.uniform())
-            X[t + 1, n] = F[t, n][A] + rng.normal(size=(M, d)) @ L.astype(np.float64).T
-    return X, F, ll, lw
+def _reference64(X, F, ll, lw, L):
+    """The shared definition with the difference ``X_{t+1}[j] - F_t[i]`` formed in fp64, as these kernels are held to it."""
+    return sc.reference(X.astype(np.float64), F.astype(np.float64), ll, lw, L)
 
 
 def _run(X, F, ll, lw, L, want_cov=True, want_ess=True):
-    from multimodalfilter_amd import _abi
-
-    dev = _dev()
-    T, N, M, d = X.shape
-    G = lambda x: None if x is None else torch.as_tensor(np.ascontiguousarray(x), dtype=torch.float32).to(dev)
-    weights = torch.full((T, N, M), math.nan, device=dev)
-    mean = torch.full((T, N, d), math.nan, device=dev)
-    cov = torch.full((T, N, d, d), math.nan, device=dev) if want_cov else None
-    ess = torch.full((T, N), math.nan, device=dev) if want_ess else None
-    _abi.pf_smooth_marginal(G(X), G(F) if T > 1 else None, G(ll), G(lw), G(L), weights, mean, cov, ess)
-    torch.cuda.synchronize()
-    return weights, mean, cov, ess
+    g = sc.gpu_marginal(X, F, ll, lw, L, want_cov=want_cov, want_ess=want_ess, want_logd=False)
+    return g["weights"], g["mean"], g["cov"], g["ess"]
 
 
 def _check(got, want, what):
     """Weights within the bar of their row's norm, means and covariances within the bar per trajectory, ESS to 1e-4 relative,
     ``cov`` symmetric bit for bit and PSD to ``-1e-4 x trace``.  Prints the figures before asserting."""
     weights, mean, cov, ess = got
-    wweights, wmean, wcov, wess = want
+    wweights, wmean, wcov, wess = want["weights"], want["mean"], want["cov"], want["ess"]
     N = wmean.shape[1]
     e_w = max(rel_err(weights[:, n], wweights[:, n], dims=1) for n in range(N))
     e_mean = max(rel_err(mean[:, n], wmean[:, n], dims=1) for n in range(N))
@@ -134,10 +48,7 @@ def _check(got, want, what):
     assert e_cov <= REL_TOL, (what, e_cov)
     assert e_ess <= 1e-4, (what, e_ess)
     assert float((weights.double().sum(-1) - 1.0).abs().max()) <= 1e-5, what
-    assert torch.equal(cov, cov.transpose(-1, -2)), what
-    c = cov.double().cpu()
-    floor = -1e-4 * torch.diagonal(c, dim1=-2, dim2=-1).sum(-1)
-    assert bool((torch.linalg.eigvalsh(c).min(-1).values >= floor - 1e-30).all()), what
+    sc.assert_symmetric_psd(cov, what)
 
 
 # ------------------------------------------------------------------------------------------ 1. kernels against fp64
@@ -153,22 +64,22 @@ def test_marginal_kernels_match_fp64(M, d, ll_scale):
     the filter's weight at every step, scale 0.5 keeps hundreds alive."""
     T, N = 5, 3
     for full in (False, True):
-        L = _tril(d, full)
-        X, F, ll, lw = _make_case(T, N, M, d, _WIDTHS, ll_scale, L, seed=1000 * M + 10 * d + int(ll_scale) + full)
-        _check(_run(X, F, ll, lw, L), _reference(X, F, ll, lw, L), f"M={M} d={d} scale={ll_scale} full={full}")
+        L = sc.tril(d, full)
+        X, F, ll, lw = sc.make_case(T, N, M, d, _WIDTHS, ll_scale, L, seed=1000 * M + 10 * d + int(ll_scale) + full)
+        _check(_run(X, F, ll, lw, L), _reference64(X, F, ll, lw, L), f"M={M} d={d} scale={ll_scale} full={full}")
 
 
 # ------------------------------------------------------------------------------------------ 2. edges
 def test_single_step_and_single_particle():
-    L = _tril(3, True)
-    X, F, ll, lw = _make_case(1, 3, 300, 3, _WIDTHS, 0.5, L, seed=1)
+    L = sc.tril(3, True)
+    X, F, ll, lw = sc.make_case(1, 3, 300, 3, _WIDTHS, 0.5, L, seed=1)
     got = _run(X, F, ll, lw, L)
-    _check(got, _reference(X, F, ll, lw, L), "T=1")
-    assert rel_err(got[0][0], _softmax_rows(ll[0].astype(np.float64) + lw[0]), dims=1) <= REL_TOL  # the filter's weights
-    L = _tril(2, False)
-    X, F, ll, lw = _make_case(5, 2, 1, 2, _WIDTHS, 0.5, L, seed=2)
+    _check(got, _reference64(X, F, ll, lw, L), "T=1")
+    assert rel_err(got[0][0], sc.softmax_rows(ll[0].astype(np.float64) + lw[0]), dims=1) <= REL_TOL  # the filter's weights
+    L = sc.tril(2, False)
+    X, F, ll, lw = sc.make_case(5, 2, 1, 2, _WIDTHS, 0.5, L, seed=2)
     got = _run(X, F, ll, lw, L)
-    _check(got, _reference(X, F, ll, lw, L), "M=1")
+    _check(got, _reference64(X, F, ll, lw, L), "M=1")
     assert torch.equal(got[1].cpu(), torch.from_numpy(X[:, :, 0]))  # the one particle is the mean
     assert float(got[2].abs().max()) == 0.0 and bool((got[0] == 1).all()) and bool((got[3] == 1).all())
 
@@ -178,23 +89,23 @@ def test_dead_particles_and_a_single_heavy_particle():
     the reference over the rest, zero weight on the dead.  One particle with all the weight at the last step: step T - 2 is
     re-weighted by the transition into that particle alone."""
     T, N, M, d = 5, 3, 300, 3
-    L = _tril(d, True)
-    X, F, ll, lw = _make_case(T, N, M, d, _WIDTHS, 0.5, L, seed=11)
+    L = sc.tril(d, True)
+    X, F, ll, lw = sc.make_case(T, N, M, d, _WIDTHS, 0.5, L, seed=11)
     ll[:, 1, ::2] = -np.inf
     X[:, 1, ::2] = np.inf
     F[:, 1, ::2] = np.inf
     got = _run(X, F, ll, lw, L)
-    _check(got, _reference(X, F, ll, lw, L), "half dead")
+    _check(got, _reference64(X, F, ll, lw, L), "half dead")
     assert float(got[0][:, 1, ::2].abs().max()) == 0.0 and bool((got[0][:, 1, 1::2] > 0).any())
-    X, F, ll, lw = _make_case(T, N, M, d, _WIDTHS, 0.5, L, seed=12)
+    X, F, ll, lw = sc.make_case(T, N, M, d, _WIDTHS, 0.5, L, seed=12)
     ll[-1, :, 17] = 60.0  # the others keep exp(-60) ~ 1e-26 of it
     got = _run(X, F, ll, lw, L)
-    want = _reference(X, F, ll, lw, L)
+    want = _reference64(X, F, ll, lw, L)
     _check(got, want, "one heavy particle")
-    assert float(got[0][-1, :, 17].min()) >= 1.0 - 1e-6 and float(want[3][-1].max()) <= 1.0 + 1e-9
+    assert float(got[0][-1, :, 17].min()) >= 1.0 - 1e-6 and float(want["ess"][-1].max()) <= 1.0 + 1e-9
     # by the definition, with one column: W_{T-2|T}[i] is proportional to W_{T-2}[i] N(X_{T-1}[17]; F_{T-2}[i], L L^T)
     z = (X[-1, :, 17].astype(np.float64)[:, None, :] - F[-1].astype(np.float64)) @ np.linalg.inv(L.astype(np.float64)).T
-    direct = _softmax_rows(ll[-2].astype(np.float64) + lw[-2] - 0.5 * (z * z).sum(-1))
+    direct = sc.softmax_rows(ll[-2].astype(np.float64) + lw[-2] - 0.5 * (z * z).sum(-1))
     assert rel_err(got[0][-2], direct, dims=1) <= REL_TOL
 
 
@@ -202,8 +113,8 @@ def test_dead_particles_and_a_single_heavy_particle():
 def test_two_calls_and_split_batches_give_the_same_bits(M):
     """Fixed-order reductions: two calls on the same inputs return the same bits, and the call on N = 3 trajectories returns
     what three calls on one trajectory each do.  Outputs that are not asked for change nothing."""
-    L = _tril(3, True)
-    X, F, ll, lw = _make_case(5, 3, M, 3, _WIDTHS, 0.5, L, seed=3 + M)
+    L = sc.tril(3, True)
+    X, F, ll, lw = sc.make_case(5, 3, M, 3, _WIDTHS, 0.5, L, seed=3 + M)
     a, b = _run(X, F, ll, lw, L), _run(X, F, ll, lw, L)
     for x, y in zip(a, b):
         assert torch.equal(x, y)
@@ -221,8 +132,8 @@ def test_two_calls_and_split_batches_give_the_same_bits(M):
 
 def test_a_bad_noise_factor_gives_nan_and_no_fault():
     """A zero, negative or non-finite diagonal entry of ``L``: every result is NaN (T = 1, where ``L`` is not used, included)."""
-    L = _tril(3, True)
-    X, F, ll, lw = _make_case(3, 2, 70, 3, _WIDTHS, 0.5, L, seed=21)
+    L = sc.tril(3, True)
+    X, F, ll, lw = sc.make_case(3, 2, 70, 3, _WIDTHS, 0.5, L, seed=21)
     for T in (3, 1):
         for bad in (0.0, -0.02, math.inf, math.nan):
             Lb = L.copy()
@@ -238,18 +149,18 @@ def test_a_flat_transition_gives_the_filter_and_the_last_step_is_the_filters():
     (``mmf_pf_smooth`` at lag 0 on the same history).  Any ``L``: the last step's weights are the softmax of the last step."""
     from multimodalfilter_amd import _abi
 
-    dev = _dev()
+    dev = sc.dev()
     T, N, M, d = 5, 3, 300, 3
-    L = _tril(d, True)
-    X, F, ll, lw = _make_case(T, N, M, d, _WIDTHS, 0.5, L, seed=31)
-    G = lambda x: torch.as_tensor(x, dtype=torch.float32).contiguous().to(dev)
+    L = sc.tril(d, True)
+    X, F, ll, lw = sc.make_case(T, N, M, d, _WIDTHS, 0.5, L, seed=31)
+    G = sc.to_device
     fmean, fcov = torch.empty((T, N, d), device=dev), torch.empty((T, N, d, d), device=dev)
     _abi.pf_smooth(G(X), G(ll), G(lw), None, None, 0, fmean, fcov, None)
     flat = _run(X, F, ll, lw, (1e3 * np.eye(d)).astype(np.float32))
     sharp = _run(X, F, ll, lw, L)
     e_mean = max(rel_err(flat[1][:, n], fmean[:, n], dims=1) for n in range(N))
     e_cov = max(rel_err(flat[2][:, n], fcov[:, n], dims=2) for n in range(N))
-    last = _softmax_rows(ll[-1].astype(np.float64) + lw[-1])
+    last = sc.softmax_rows(ll[-1].astype(np.float64) + lw[-1])
     e_last = max(rel_err(flat[0][-1], last, dims=1), rel_err(sharp[0][-1], last, dims=1))
     moved = rel_err(sharp[1][0], fmean[0], dims=1)
     print(f"flat transition against the filter: mean {e_mean:.2e} cov {e_cov:.2e}; last step's weights {e_last:.2e}; "
@@ -262,32 +173,15 @@ def test_a_flat_transition_gives_the_filter_and_the_last_step_is_the_filters():
 _CONFIGS = {"plain": {}, "soft": {"soft_resample_alpha": 0.5}, "ess": {"resample_ess_threshold": 0.5}, "noresample": {"resample": False}}
 
 
-def _filter(cls, N, M, T, dev):
-    import multimodalfilter_amd as mmf
-    from multimodalfilter_amd import synthetic
-
-    tname = "door" if cls.startswith("Door") else "push"
-    d = om.TASKS[tname].state_dim
-    torch.manual_seed(3)
-    f = mmf.model_types(tname)[cls]().to(dev).eval()
-    f.num_particles = M
-    traj = {k: v.to(dev) for k, v in synthetic.make_trajectories(state_dim=d, T=T, N=N, seed=17).items()}
-    obs = {k: traj[k][1:] for k in ("image", "gripper_pos", "gripper_sensors")}
-    cal = traj["states"][0][:, None, :] + 0.3 * torch.randn((N, 256, d), device=dev)
-    synthetic.calibrate_measurement_heads(f, {k: v[0] for k, v in obs.items()}, cal, target_std=1.2)
-    cov = (torch.eye(d, device=dev) * 0.1)[None].expand(N, d, d)
-    return f, d, traj, obs, traj["controls"][1:], cov
-
-
 @functools.lru_cache(maxsize=None)
 def _filter_runs(cls, config, M):
     """One filter, three runs on the same randomness: with ``record_indices`` (what the loop did before this history field
     existed), with ``record_history`` through the native loop and with ``record_history`` step by step."""
     import multimodalfilter_amd as mmf
 
-    dev = _dev()
+    dev = sc.dev()
     N, T = 4, 6
-    f, d, traj, obs, ctrl, cov = _filter(cls, N, M, T, dev)
+    f, d, traj, obs, ctrl, cov = sc.small_filter(cls, N, M, T, dev)
     for k, v in _CONFIGS[config].items():
         setattr(f, k, v)
 
@@ -335,7 +229,7 @@ def test_filter_marginal_smoothing_matches_the_reference_and_the_loop_is_unchang
         ctx = dyn.encode_controls(h.controls[1:].reshape((T - 1) * N, -1))
         F = dyn.propagate_encoded(h.states[:-1].reshape((T - 1) * N, M, d), ctx, None).reshape(T - 1, N, M, d)
     C = lambda x: x.detach().cpu().numpy()
-    want = _reference(C(h.states), C(F), C(h.log_likelihoods), C(h.log_weights_in), C(dyn.scale_tril()))
+    want = _reference64(C(h.states), C(F), C(h.log_likelihoods), C(h.log_weights_in), C(dyn.scale_tril()))
     f.last_history = h
     mean = f.smooth(method="marginal")
     rec = f.last_smoothed
@@ -352,9 +246,9 @@ def test_run_filter_returns_the_marginal_record():
     import multimodalfilter_amd as mmf
     from multimodalfilter_amd import evaluation
 
-    dev = _dev()
+    dev = sc.dev()
     N, M, T = 4, 300, 8
-    f, d, traj, obs, ctrl, cov = _filter("DoorParticleFilter", N, M, T, dev)
+    f, d, traj, obs, ctrl, cov = sc.small_filter("DoorParticleFilter", N, M, T, dev)
     f.noise = mmf.CounterNoise(7)
     est, rec = evaluation.run_filter(f, traj, smooth_method="marginal", return_belief=True)
     assert f.record_history is False and f.record_belief is False  # switched back
@@ -375,48 +269,6 @@ def test_run_filter_returns_the_marginal_record():
 
 
 # ------------------------------------------------------------------------------------------ 5. linear-Gaussian known answer
-def _rts(z, m0, p0, q, r):
-    """Exact Kalman filter and Rauch-Tung-Striebel smoother of ``x' = x + q eps``, ``z = x + r eps`` in fp64: every state
-    dimension is a scalar problem with the same variances.  ``z (T, ...)``, prior ``N(m0, p0)`` before the first step."""
-    T = z.shape[0]
-    mf, pf, mp, pp = np.zeros_like(z), np.zeros(T), np.zeros_like(z), np.zeros(T)
-    m, p = m0, p0
-    for t in range(T):
-        mp[t], pp[t] = m, p + q * q
-        k = pp[t] / (pp[t] + r * r)
-        m, p = mp[t] + k * (z[t] - mp[t]), (1.0 - k) * pp[t]
-        mf[t], pf[t] = m, p
-    ms = mf.copy()
-    for t in range(T - 2, -1, -1):
-        ms[t] = mf[t] + pf[t] / pp[t + 1] * (ms[t + 1] - mp[t + 1])
-    return ms
-
-
-def _linear_gaussian_models(d, q, r, dev, state_dependent=False):
-    from multimodalfilter_amd import base
-
-    class RandomWalk(base.DynamicsModel):
-        def __init__(self):
-            super().__init__(state_dim=d)
-            self.L = (q * torch.eye(d)).to(dev)
-
-        def forward(self, *, initial_states, controls):
-            L = self.L[None].expand(initial_states.shape[0], d, d)
-            if state_dependent:
-                L = L * (1.0 + initial_states[:, :1, None].abs())
-            return initial_states, L
-
-    class GaussianLik(base.ParticleFilterMeasurementModel):
-        def __init__(self):
-            super().__init__(state_dim=d)
-
-        def forward(self, *, states, observations):
-            e = observations["z"][:, None, :] - states
-            return -0.5 * (e * e).sum(-1) / (r * r)
-
-    return RandomWalk(), GaussianLik()
-
-
 def test_marginal_is_no_worse_than_ancestry_against_the_exact_smoother():
     """The random-walk states of ``synthetic.make_trajectories`` (x' = x + 0.05 eps) observed through ``z = x + 0.3 eps``,
     filtered with the model that generated them (user models: the step-by-step history and the generic prediction path):
@@ -425,12 +277,12 @@ def test_marginal_is_no_worse_than_ancestry_against_the_exact_smoother():
     import multimodalfilter_amd as mmf
     from multimodalfilter_amd import synthetic
 
-    dev = _dev()
+    dev = sc.dev()
     d, N, M, T = 3, 8, 512, 40
     q, r = 0.05, 0.3
     truth = synthetic.make_trajectories(state_dim=d, T=T, N=N, seed=23)["states"]
     z = truth[1:] + r * torch.randn((T, N, d), generator=torch.Generator().manual_seed(29))
-    dyn, meas = _linear_gaussian_models(d, q, r, dev)
+    dyn, meas = sc.linear_gaussian_models(d, q, r, dev)
     f = mmf.filters.ParticleFilter(dynamics_model=dyn, measurement_model=meas, num_particles=M)
     f.eval()
     f.record_history = True
@@ -442,7 +294,7 @@ def test_marginal_is_no_worse_than_ancestry_against_the_exact_smoother():
     unique = f.last_smoothed.unique.float()
     marginal = f.smooth(method="marginal")
     rec = f.last_smoothed
-    exact = torch.from_numpy(_rts(z.double().numpy(), truth[0].double().numpy(), 0.1, q, r))
+    exact = torch.from_numpy(sc.rts(z.double().numpy(), truth[0].double().numpy(), 0.1, q, r))
     rmse = lambda x: float((x.double().cpu()[:T - 9] - exact[:T - 9]).pow(2).sum(-1).mean().sqrt())
     print(f"RMSE to the exact smoother over steps 0 .. T-10: marginal {rmse(marginal):.5f}, ancestry {rmse(ancestry):.5f}, "
           f"filter {rmse(est):.5f}; mean ess[0] {float(rec.ess[0].mean()):.1f}, mean unique[0] {float(unique[0].mean()):.1f}")
@@ -453,9 +305,9 @@ def test_marginal_is_no_worse_than_ancestry_against_the_exact_smoother():
 def test_state_dependent_noise_is_refused():
     import multimodalfilter_amd as mmf
 
-    dev = _dev()
+    dev = sc.dev()
     d, N, M, T = 2, 2, 64, 3
-    dyn, meas = _linear_gaussian_models(d, 0.05, 0.3, dev, state_dependent=True)
+    dyn, meas = sc.linear_gaussian_models(d, 0.05, 0.3, dev, state_dependent=True)
     f = mmf.filters.ParticleFilter(dynamics_model=dyn, measurement_model=meas, num_particles=M)
     f.eval()
     f.record_history = True

@@ -2,7 +2,7 @@
 ``ParticleFilter.smooth(method="marginal")`` with the filter's ``record_transition_moments`` set) and the EM refit of the
 process noise built on them (``evaluation.process_noise_m_step`` / ``fit_process_noise``).
 
-The kernels are held to the fp64 definition (``_pair_cases.reference``) at the project's bar (``_tol.REL_TOL`` through
+The kernels are held to the fp64 definition (``_smooth_cases.reference``) at the project's bar (``_tol.REL_TOL`` through
 ``rel_err``, per trajectory so that a narrow cloud is measured against its own scale).  The smoothed weights and ``logD``
 the kernel reads come from the GPU marginal call on the same inputs, as they do in use."""
 import functools
@@ -14,48 +14,27 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from oracle import models as om
-
-import _pair_cases as pc
+import _smooth_cases as sc
 from _tol import REL_TOL, rel_err
 
 CHUNK = 256  # columns the pair kernels stage at a time (csrc/pf_smooth_math.h: kPairChunk)
 _WIDTHS = (1e-3, 1e-2, 0.3)
 
 
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a real MI355X")
-    return torch.device("cuda:0")
-
-
-def _G(x):
-    return None if x is None else torch.as_tensor(np.ascontiguousarray(x), dtype=torch.float32).to(_dev())
-
-
 def _marginal(X, F, ll, lw, L):
     """The GPU marginal call: ``dict`` of the device inputs and its ``weights``, ``logd``, ``mean``."""
-    from multimodalfilter_amd import _abi
-
-    dev = _dev()
-    T, N, M, d = X.shape
-    g = dict(X=_G(X), F=_G(F) if T > 1 else None, ll=_G(ll), lw=_G(lw), L=_G(L))
-    g["weights"] = torch.full((T, N, M), math.nan, device=dev)
-    g["mean"] = torch.full((T, N, d), math.nan, device=dev)
-    g["logd"] = torch.full((T - 1, N, M), math.nan, device=dev) if T > 1 else None
-    _abi.pf_smooth_marginal(g["X"], g["F"], g["ll"], g["lw"], g["L"], g["weights"], g["mean"], None, None, g["logd"])
-    return g
+    return sc.gpu_marginal(X, F, ll, lw, L, want_cov=False, want_ess=False, want_logd=True)
 
 
 def _pairs(g, L=None, workspace=None):
     """``mmf_pf_smooth_pair_moments`` on what ``_marginal`` left (``L``: another noise factor than the marginal call's)."""
     from multimodalfilter_amd import _abi
 
-    dev = _dev()
+    dev = sc.dev()
     T, N, M, d = g["X"].shape
     mean = torch.full((max(T - 1, 0), N, d), math.nan, device=dev)
     second = torch.full((max(T - 1, 0), N, d, d), math.nan, device=dev)
-    _abi.pf_smooth_pair_moments(g["X"], g["F"], g["ll"], g["lw"], g["L"] if L is None else _G(L), g["weights"], g["logd"],
+    _abi.pf_smooth_pair_moments(g["X"], g["F"], g["ll"], g["lw"], g["L"] if L is None else sc.to_device(L), g["weights"], g["logd"],
                                 mean, second, workspace)
     torch.cuda.synchronize()
     return mean, second
@@ -77,10 +56,7 @@ def _check(got, want, what):
     assert bool(torch.isfinite(mean).all()) and bool(torch.isfinite(second).all()), what
     assert e_mean <= REL_TOL, (what, e_mean)
     assert e_second <= REL_TOL, (what, e_second)
-    assert torch.equal(second, second.transpose(-1, -2)), what
-    c = second.double().cpu()
-    floor = -1e-4 * torch.diagonal(c, dim1=-2, dim2=-1).sum(-1)
-    assert bool((torch.linalg.eigvalsh(c).min(-1).values >= floor - 1e-30).all()), what
+    sc.assert_symmetric_psd(second, what)
 
 
 # ------------------------------------------------------------------------------------------ 1. kernels against fp64
@@ -93,9 +69,9 @@ def test_pair_kernels_match_fp64(M, d, ll_scale):
     scale 50 a particle or two hold the filter's weight at every step, scale 0.5 keeps hundreds alive."""
     T, N = 5, 3
     for full in (False, True):
-        L = pc.tril(d, full)
-        X, F, ll, lw = pc.make_case(T, N, M, d, _WIDTHS, ll_scale, L, seed=1000 * M + 10 * d + int(ll_scale) + full)
-        _check(_run(X, F, ll, lw, L), pc.reference(X, F, ll, lw, L), f"M={M} d={d} scale={ll_scale} full={full}")
+        L = sc.tril(d, full)
+        X, F, ll, lw = sc.make_case(T, N, M, d, _WIDTHS, ll_scale, L, seed=1000 * M + 10 * d + int(ll_scale) + full)
+        _check(_run(X, F, ll, lw, L), sc.reference(X, F, ll, lw, L), f"M={M} d={d} scale={ll_scale} full={full}")
 
 
 # ------------------------------------------------------------------------------------------ 2. edges
@@ -104,8 +80,8 @@ def test_a_single_particle_gives_its_own_residual(d):
     """M = 1: the one pair's weight p cancels, ``mean = (p e) / p`` and ``second = ((p e_r) e_c) / p`` with ``e`` the fp32
     difference -- two roundings on the mean (<= 2 x 2^-24 relative, held to 2^-23) and three on the second moment
     (<= 3 x 2^-24 of the exact product of the fp32 ``e``, held to 2^-22): the last bit of fp32 products."""
-    L = pc.tril(d, True)
-    X, F, ll, lw = pc.make_case(5, 2, 1, d, _WIDTHS, 0.5, L, seed=2)
+    L = sc.tril(d, True)
+    X, F, ll, lw = sc.make_case(5, 2, 1, d, _WIDTHS, 0.5, L, seed=2)
     mean, second = _run(X, F, ll, lw, L)
     e = (X[1:, :, 0] - F[:, :, 0]).astype(np.float64)  # the fp32 difference
     assert e.dtype == np.float64 and (X[1:, :, 0] - F[:, :, 0]).dtype == np.float32
@@ -123,20 +99,20 @@ def test_dead_particles_and_a_single_heavy_particle():
     the reference over the rest.  One particle with all the weight at the last step: the last transition's moments are
     those of the pairs into that particle alone."""
     T, N, M, d = 5, 3, 300, 3
-    L = pc.tril(d, True)
-    X, F, ll, lw = pc.make_case(T, N, M, d, _WIDTHS, 0.5, L, seed=11)
+    L = sc.tril(d, True)
+    X, F, ll, lw = sc.make_case(T, N, M, d, _WIDTHS, 0.5, L, seed=11)
     ll[:, 1, ::2] = -np.inf
     X[:, 1, ::2] = np.inf
     F[:, 1, ::2] = np.inf
-    _check(_run(X, F, ll, lw, L), pc.reference(X, F, ll, lw, L), "half dead")
-    X, F, ll, lw = pc.make_case(T, N, M, d, _WIDTHS, 0.5, L, seed=12)
+    _check(_run(X, F, ll, lw, L), sc.reference(X, F, ll, lw, L), "half dead")
+    X, F, ll, lw = sc.make_case(T, N, M, d, _WIDTHS, 0.5, L, seed=12)
     ll[-1, :, 17] = 60.0  # the others keep exp(-60) ~ 1e-26 of it
     got = _run(X, F, ll, lw, L)
-    _check(got, pc.reference(X, F, ll, lw, L), "one heavy particle")
+    _check(got, sc.reference(X, F, ll, lw, L), "one heavy particle")
     # by the definition, with one column: xi[i] is proportional to W_{T-2}[i] N(X_{T-1}[17]; F_{T-2}[i], L L^T)
     e = (X[-1, :, 17][:, None, :] - F[-1]).astype(np.float64)
     z = e @ np.linalg.inv(L.astype(np.float64)).T
-    xi = pc.softmax_rows(ll[-2].astype(np.float64) + lw[-2] - 0.5 * (z * z).sum(-1))
+    xi = sc.softmax_rows(ll[-2].astype(np.float64) + lw[-2] - 0.5 * (z * z).sum(-1))
     assert rel_err(got[0][-1], np.einsum("ni,nic->nc", xi, e), dims=1) <= REL_TOL
     assert rel_err(got[1][-1], np.einsum("ni,nic,nik->nck", xi, e, e), dims=2) <= REL_TOL
 
@@ -148,8 +124,8 @@ def test_two_calls_split_batches_and_a_supplied_workspace_give_the_same_bits(M):
     null incoming log-weights are uniform ones."""
     from multimodalfilter_amd import _abi
 
-    L = pc.tril(3, True)
-    X, F, ll, lw = pc.make_case(5, 3, M, 3, _WIDTHS, 0.5, L, seed=3 + M)
+    L = sc.tril(3, True)
+    X, F, ll, lw = sc.make_case(5, 3, M, 3, _WIDTHS, 0.5, L, seed=3 + M)
     g = _marginal(X, F, ll, lw, L)
     a, b = _pairs(g), _pairs(g)
     for x, y in zip(a, b):
@@ -160,7 +136,7 @@ def test_two_calls_split_batches_and_a_supplied_workspace_give_the_same_bits(M):
             assert torch.equal(x[:, n:n + 1], y), n
     need = _abi.pf_smooth_pair_workspace_floats(5, 3, M, 3)
     assert need == 4 * 3 * ((M + 63) // 64) * 10
-    ws = torch.full((need + 1000,), math.nan, device=_dev())
+    ws = torch.full((need + 1000,), math.nan, device=sc.dev())
     c = _pairs(g, workspace=ws)
     for x, y in zip(a, c):
         assert torch.equal(x, y)
@@ -174,8 +150,8 @@ def test_two_calls_split_batches_and_a_supplied_workspace_give_the_same_bits(M):
 def test_a_bad_noise_factor_gives_nan_and_no_fault():
     """A zero, negative or non-finite diagonal entry of ``L`` -- handed to this call alone after a good marginal call, or to
     both: every output is NaN.  ``T = 1``: nothing to write, and the call succeeds."""
-    L = pc.tril(3, True)
-    X, F, ll, lw = pc.make_case(3, 2, 70, 3, _WIDTHS, 0.5, L, seed=21)
+    L = sc.tril(3, True)
+    X, F, ll, lw = sc.make_case(3, 2, 70, 3, _WIDTHS, 0.5, L, seed=21)
     good = _marginal(X, F, ll, lw, L)
     for bad in (0.0, -0.02, math.inf, math.nan):
         Lb = L.copy()
@@ -192,13 +168,13 @@ def test_a_flat_transition_factorises():
     """``L = 1e3 I``: every transition density is the same to 1e-6, so ``xi = W_t[i] W_{t+1|T}[j]`` and the residual mean is
     ``mean_{t+1|T} - sum_i W_t[i] F_t[i]`` -- the marginal call's own smoothed means against the filter's weights."""
     T, N, M, d = 5, 3, 300, 3
-    X, F, ll, lw = pc.make_case(T, N, M, d, _WIDTHS, 0.5, pc.tril(d, True), seed=31)
+    X, F, ll, lw = sc.make_case(T, N, M, d, _WIDTHS, 0.5, sc.tril(d, True), seed=31)
     g = _marginal(X, F, ll, lw, (1e3 * np.eye(d)).astype(np.float32))
     mean, second = _pairs(g)
-    W = pc.softmax_rows(ll.astype(np.float64) + lw)
+    W = sc.softmax_rows(ll.astype(np.float64) + lw)
     want = g["mean"].double().cpu().numpy()[1:] - np.einsum("tnm,tnmc->tnc", W[:-1], F.astype(np.float64))
     e_mean = max(rel_err(mean[:, n], want[:, n], dims=1) for n in range(N))
-    sharp = _run(X, F, ll, lw, pc.tril(d, True))
+    sharp = _run(X, F, ll, lw, sc.tril(d, True))
     moved = max(rel_err(sharp[0][:, n], want[:, n], dims=1) for n in range(N))
     print(f"flat transition: residual mean against the factorised form {e_mean:.2e}; the sharp transition's differs by {moved:.2e}")
     assert e_mean <= REL_TOL
@@ -208,23 +184,6 @@ def test_a_flat_transition_factorises():
 
 # ------------------------------------------------------------------------------------------ 4. whole filters
 _CONFIGS = {"plain": {}, "ess": {"resample_ess_threshold": 0.5}}
-
-
-def _filter(cls, N, M, T, dev):
-    import multimodalfilter_amd as mmf
-    from multimodalfilter_amd import synthetic
-
-    tname = "door" if cls.startswith("Door") else "push"
-    d = om.TASKS[tname].state_dim
-    torch.manual_seed(3)
-    f = mmf.model_types(tname)[cls]().to(dev).eval()
-    f.num_particles = M
-    traj = {k: v.to(dev) for k, v in synthetic.make_trajectories(state_dim=d, T=T, N=N, seed=17).items()}
-    obs = {k: traj[k][1:] for k in ("image", "gripper_pos", "gripper_sensors")}
-    cal = traj["states"][0][:, None, :] + 0.3 * torch.randn((N, 256, d), device=dev)
-    synthetic.calibrate_measurement_heads(f, {k: v[0] for k, v in obs.items()}, cal, target_std=1.2)
-    cov = (torch.eye(d, device=dev) * 0.1)[None].expand(N, d, d)
-    return f, d, traj, obs, traj["controls"][1:], cov
 
 
 _FILTER_CASES = [(cls, c, M) for cls in ("DoorParticleFilter", "PushParticleFilter") for c in _CONFIGS for M in (64, 300)]
@@ -237,9 +196,9 @@ def test_filter_transition_moments_match_the_reference_and_the_marginal_record_i
     call without the flag, whose record has the fields it had; the flagged record has exactly two more."""
     import multimodalfilter_amd as mmf
 
-    dev = _dev()
+    dev = sc.dev()
     N, T = 4, 6
-    f, d, traj, obs, ctrl, cov = _filter(cls, N, M, T, dev)
+    f, d, traj, obs, ctrl, cov = sc.small_filter(cls, N, M, T, dev)
     for k, v in _CONFIGS[config].items():
         setattr(f, k, v)
     f.record_history = True
@@ -268,7 +227,7 @@ def test_filter_transition_moments_match_the_reference_and_the_marginal_record_i
         ctx = dyn.encode_controls(h.controls[1:].reshape((T - 1) * N, -1))
         F = dyn.propagate_encoded(h.states[:-1].reshape((T - 1) * N, M, d), ctx, None).reshape(T - 1, N, M, d)
     C = lambda x: x.detach().cpu().numpy()
-    want = pc.reference(C(h.states), C(F), C(h.log_likelihoods), C(h.log_weights_in), C(dyn.scale_tril()))
+    want = sc.reference(C(h.states), C(F), C(h.log_likelihoods), C(h.log_weights_in), C(dyn.scale_tril()))
     _check((rec.residual_mean, rec.residual_second_moment), want, f"{cls} {config} M={M}")
     f.smooth()  # the ancestry path's record is what it was
     assert set(vars(f.last_smoothed)) == {"covariance", "unique", "lag"}
@@ -277,9 +236,9 @@ def test_filter_transition_moments_match_the_reference_and_the_marginal_record_i
 def test_a_single_step_history_has_empty_moments():
     import multimodalfilter_amd as mmf
 
-    dev = _dev()
+    dev = sc.dev()
     N, M, T = 2, 64, 1
-    f, d, traj, obs, ctrl, cov = _filter("DoorParticleFilter", N, M, T, dev)
+    f, d, traj, obs, ctrl, cov = sc.small_filter("DoorParticleFilter", N, M, T, dev)
     f.record_history = True
     f.noise = mmf.CounterNoise(5)
     f.initialize_beliefs(mean=traj["states"][0], covariance=cov)
@@ -293,7 +252,7 @@ def test_a_single_step_history_has_empty_moments():
 
 # ------------------------------------------------------------------------------------------ 5. the EM refit
 def _linear_gaussian_filter(d, q0, r, M, dev):
-    """The linear-Gaussian user models of ``test_gpu_marginal_smoothing.py`` (a random walk, ``z = x + r eps`` read from the
+    """The linear-Gaussian user models of ``_smooth_cases.linear_gaussian_models`` (a random walk, ``z = x + r eps`` read from the
     ``gripper_pos`` entry ``run_filter`` passes on), the dynamics with a ``set_scale_tril`` added."""
     import multimodalfilter_amd as mmf
     from multimodalfilter_amd import base
@@ -352,7 +311,7 @@ def test_fit_process_noise_follows_the_exact_em_steps():
     import multimodalfilter_amd as mmf
     from multimodalfilter_amd import evaluation
 
-    dev = _dev()
+    dev = sc.dev()
     d, N, T, r, truth, z = _linear_gaussian_data()
     M = 512
     traj = _traj(truth, z, dev)
@@ -365,7 +324,7 @@ def test_fit_process_noise_follows_the_exact_em_steps():
     assert len(factors) == 4 and torch.equal(factors[0].cpu(), 0.15 * torch.eye(d))
     assert torch.equal(f.dynamics_model.scale_tril(), factors[-1])
     q = [size(L) for L in factors]
-    exact = pc.rts_em_step(z[1:].double().numpy(), truth[0].double().numpy(), 0.1, 0.15, r)
+    exact = sc.rts_em_step(z[1:].double().numpy(), truth[0].double().numpy(), 0.1, 0.15, r)
     print(f"EM from 0.15: {q[1]:.5f} {q[2]:.5f} {q[3]:.5f}; exact first step {exact:.5f}, ratio - 1 = {q[1] / exact - 1.0:+.2e}")
     for L in factors:
         assert L.shape == (d, d) and bool(torch.isfinite(L).all())
@@ -384,7 +343,7 @@ def test_fit_process_noise_restores_the_switches_when_a_run_fails():
     import multimodalfilter_amd as mmf
     from multimodalfilter_amd import evaluation
 
-    dev = _dev()
+    dev = sc.dev()
     d, N, T, r, truth, z = _linear_gaussian_data()
     f = _linear_gaussian_filter(d, 0.15, r, 64, dev)
     f.noise = mmf.NoiseSource(31)
@@ -404,9 +363,9 @@ def test_fit_process_noise_on_the_task_models(cls):
     import multimodalfilter_amd as mmf
     from multimodalfilter_amd import evaluation
 
-    dev = _dev()
+    dev = sc.dev()
     N, M, T = 4, 300, 8
-    f, d, traj, obs, ctrl, cov = _filter(cls, N, M, T, dev)
+    f, d, traj, obs, ctrl, cov = sc.small_filter(cls, N, M, T, dev)
     f.noise = mmf.CounterNoise(7)
     dyn = f.dynamics_model
     assert dyn.diagonal_noise is (cls == "DoorParticleFilter")

@@ -15,20 +15,13 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from oracle import models as om
-
+import _smooth_cases as sc
 from _tol import REL_TOL, rel_err
 
 B = 2            # draws of a workgroup (csrc/pf_smooth_simulate.hip: kSimDraws)
 THREADS = 256    # threads of a workgroup (kSimThreads): a thread owns ceil(M / THREADS) rows, staged 1, 2 or 4 at a time
 CDF_TOL = 2 * REL_TOL
 MIN_PROB, MIN_SHARE = 2e-3, 0.8  # the share of drawn particles whose fp64 probability makes a misplaced index visible
-
-
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a real MI355X")
-    return torch.device("cuda:0")
 
 
 # ------------------------------------------------------------------------------------------ the fp64 restatement
@@ -90,52 +83,21 @@ def _simulate64(X, F, ll, lw, L, u):
     return idx
 
 
-def _systematic(w, u):
-    """Ancestors of systematic resampling (numpy, fp64): positions ``(u + k) / M`` in the CDF of ``w``."""
-    M = len(w)
-    cdf = np.cumsum(w / w.sum())
-    cdf[-1] = 1.0
-    return np.minimum(np.searchsorted(cdf, (u + np.arange(M)) / M, side="right"), M - 1)
-
-
-def _tril(d, full, factor=0.3, seed=5):
-    """The process noise of the kernel cases: ``factor`` times ``L0``, which is 0.01 .. 0.04 wide, diagonal or a full lower
-    triangle."""
-    L = np.diag(0.02 * np.array([1.0, 0.5, 2.0, 1.5])[:d])
-    if full:
-        L = L + np.tril(0.4 * 0.02 * np.random.default_rng(seed).normal(size=(d, d)), -1)
-    return (factor * L).astype(np.float32)
+def _tril(d, full, factor=0.3):
+    """The process noise of the kernel cases: ``factor`` times the factor of the marginal smoother's cases."""
+    return sc.tril(d, full, factor=factor)
 
 
 _WIDTHS = (1e-2, 0.1, 0.3)
 
 
 def _make_case(T, N, M, d, L, seed, S, use_lw=True, ll_scale=0.5, dead=True):
-    """A run a filter could have left (the construction of ``test_gpu_marginal_smoothing.py``): step 0 is a cloud of the
-    trajectory's width around an O(1) centre; every later set is drawn around the predictions ``F_t = X_t + drift_t`` of
-    ancestors resampled systematically from the step's own weights, with noise ``L``.  ``dead``: every 7th particle (from
-    particle 3) has log-likelihood ``-inf`` and NaN rows in ``X`` and ``F``.  Uniforms ``(T, N, S)`` float32 in [0, 1)."""
+    """A run a filter could have left (``_smooth_cases.make_case``; ``dead``: every 7th particle, from particle 3, has
+    log-likelihood ``-inf`` and NaN rows in ``X`` and ``F``), and after it, from the same generator, the uniforms
+    ``(T, N, S)`` float32 in [0, 1)."""
     rng = np.random.default_rng(seed)
-    widths = np.resize(np.asarray(_WIDTHS, dtype=np.float64), N)
-    X = np.zeros((T, N, M, d), dtype=np.float32)
-    F = np.zeros((max(T - 1, 0), N, M, d), dtype=np.float32)
-    ll = (ll_scale * rng.normal(size=(T, N, M))).astype(np.float32)
-    lw = 0.3 * rng.normal(size=(T, N, M))
-    lw = (lw - np.log(np.exp(lw).sum(-1, keepdims=True))).astype(np.float32)
-    if dead:
-        ll[:, :, 3::7] = -np.inf
-    X[0] = rng.normal(size=(N, 1, d)) + widths[:, None, None] * rng.normal(size=(N, M, d))
-    for t in range(T - 1):
-        F[t] = X[t] + 0.05 * rng.normal(size=(N, 1, d))
-        for n in range(N):
-            a = ll[t, n].astype(np.float64) + (lw[t, n] if use_lw else 0.0)
-            A = _systematic(np.exp(a - a.max()), rng.uniform())
-            X[t + 1, n] = F[t, n][A] + rng.normal(size=(M, d)) @ L.astype(np.float64).T
-    if dead:
-        X[:, :, 3::7] = np.nan
-        F[:, :, 3::7] = np.nan
-    u = rng.random(size=(T, N, S), dtype=np.float32)
-    return X, F, ll, (lw if use_lw else None), u
+    X, F, ll, lw = sc.make_case(T, N, M, d, _WIDTHS, ll_scale, L, rng, use_lw=use_lw, dead=dead)
+    return X, F, ll, lw, rng.random(size=(T, N, S), dtype=np.float32)
 
 
 def _run(X, F, ll, lw, L, u, want_cov=True):
@@ -143,10 +105,10 @@ def _run(X, F, ll, lw, L, u, want_cov=True):
     values a forgotten write would leave visible)."""
     from multimodalfilter_amd import _abi
 
-    dev = _dev()
+    dev = sc.dev()
     T, N, M, d = X.shape
     S = u.shape[2]
-    G = lambda x: None if x is None else torch.as_tensor(np.ascontiguousarray(x), dtype=torch.float32).to(dev)
+    G = sc.to_device
     idx = torch.full((T, N, S), -7, dtype=torch.int32, device=dev)
     traj = torch.full((T, N, S, d), 12345.0, device=dev)
     mean = torch.full((T, N, d), 12345.0, device=dev)
@@ -418,10 +380,10 @@ def test_the_draws_follow_the_smoothing_distribution(M, d, T, N, S):
     failure points at the kernel.  ``cov`` is the sample covariance of ``trajectories``."""
     from multimodalfilter_amd import _abi
 
-    dev = _dev()
+    dev = sc.dev()
     L = _tril(d, True)
     X, F, ll, lw, u = _make_case(T, N, M, d, L, seed=600 + M, S=S, dead=False)
-    G = lambda x: torch.as_tensor(np.ascontiguousarray(x), dtype=torch.float32).to(dev)
+    G = sc.to_device
     mw, mmean, mcov = torch.empty((T, N, M), device=dev), torch.empty((T, N, d), device=dev), torch.empty((T, N, d, d), device=dev)
     _abi.pf_smooth_marginal(G(X), G(F), G(ll), G(lw), G(L), mw, mmean, mcov, None)
     mmean = mmean.double().cpu()
@@ -450,22 +412,6 @@ def test_the_draws_follow_the_smoothing_distribution(M, d, T, N, S):
 _CONFIGS = {"plain": {}, "ess": {"resample_ess_threshold": 0.5}}
 
 
-def _filter(cls, N, M, T, dev):
-    import multimodalfilter_amd as mmf
-    from multimodalfilter_amd import synthetic
-
-    d = om.TASKS["door"].state_dim
-    torch.manual_seed(3)
-    f = mmf.model_types("door")[cls]().to(dev).eval()
-    f.num_particles = M
-    traj = {k: v.to(dev) for k, v in synthetic.make_trajectories(state_dim=d, T=T, N=N, seed=17).items()}
-    obs = {k: traj[k][1:] for k in ("image", "gripper_pos", "gripper_sensors")}
-    cal = traj["states"][0][:, None, :] + 0.3 * torch.randn((N, 256, d), device=dev)
-    synthetic.calibrate_measurement_heads(f, {k: v[0] for k, v in obs.items()}, cal, target_std=1.2)
-    cov = (torch.eye(d, device=dev) * 0.1)[None].expand(N, d, d)
-    return f, d, traj, obs, traj["controls"][1:], cov
-
-
 @pytest.mark.parametrize("config", list(_CONFIGS))
 @pytest.mark.parametrize("cls", ["DoorParticleFilter", "DoorCrossmodalParticleFilter"])
 def test_filter_simulation_smoothing(cls, config):
@@ -475,9 +421,9 @@ def test_filter_simulation_smoothing(cls, config):
     the paths; the other two methods leave the records they left before."""
     import multimodalfilter_amd as mmf
 
-    dev = _dev()
+    dev = sc.dev()
     N, M, T, S = 4, 300, 8, 16
-    f, d, traj, obs, ctrl, cov = _filter(cls, N, M, T, dev)
+    f, d, traj, obs, ctrl, cov = sc.small_filter(cls, N, M, T, dev)
     for k, v in _CONFIGS[config].items():
         setattr(f, k, v)
 
@@ -536,9 +482,9 @@ def test_run_filter_returns_the_simulation_record():
     import multimodalfilter_amd as mmf
     from multimodalfilter_amd import evaluation
 
-    dev = _dev()
+    dev = sc.dev()
     N, M, T, S = 4, 300, 8, 16
-    f, d, traj, obs, ctrl, cov = _filter("DoorParticleFilter", N, M, T, dev)
+    f, d, traj, obs, ctrl, cov = sc.small_filter("DoorParticleFilter", N, M, T, dev)
     f.noise = mmf.NoiseSource(7)
     est, rec = evaluation.run_filter(f, traj, smooth_method="simulation", smooth_draws=S, return_belief=True)
     assert f.record_history is False and f.record_belief is False  # switched back
@@ -567,48 +513,6 @@ def test_run_filter_returns_the_simulation_record():
 
 
 # ------------------------------------------------------------------------------------------ linear-Gaussian known answer
-def _rts(z, m0, p0, q, r):
-    """Exact Kalman filter and Rauch-Tung-Striebel smoother of ``x' = x + q eps``, ``z = x + r eps`` in fp64: every state
-    dimension is a scalar problem with the same variances.  ``z (T, ...)``, prior ``N(m0, p0)`` before the first step."""
-    T = z.shape[0]
-    mf, pf, mp, pp = np.zeros_like(z), np.zeros(T), np.zeros_like(z), np.zeros(T)
-    m, p = m0, p0
-    for t in range(T):
-        mp[t], pp[t] = m, p + q * q
-        k = pp[t] / (pp[t] + r * r)
-        m, p = mp[t] + k * (z[t] - mp[t]), (1.0 - k) * pp[t]
-        mf[t], pf[t] = m, p
-    ms = mf.copy()
-    for t in range(T - 2, -1, -1):
-        ms[t] = mf[t] + pf[t] / pp[t + 1] * (ms[t + 1] - mp[t + 1])
-    return ms
-
-
-def _linear_gaussian_models(d, q, r, dev, state_dependent=False):
-    from multimodalfilter_amd import base
-
-    class RandomWalk(base.DynamicsModel):
-        def __init__(self):
-            super().__init__(state_dim=d)
-            self.L = (q * torch.eye(d)).to(dev)
-
-        def forward(self, *, initial_states, controls):
-            L = self.L[None].expand(initial_states.shape[0], d, d)
-            if state_dependent:
-                L = L * (1.0 + initial_states[:, :1, None].abs())
-            return initial_states, L
-
-    class GaussianLik(base.ParticleFilterMeasurementModel):
-        def __init__(self):
-            super().__init__(state_dim=d)
-
-        def forward(self, *, states, observations):
-            e = observations["z"][:, None, :] - states
-            return -0.5 * (e * e).sum(-1) / (r * r)
-
-    return RandomWalk(), GaussianLik()
-
-
 def test_simulation_is_no_worse_than_ancestry_against_the_exact_smoother():
     """The random-walk states of ``synthetic.make_trajectories`` (x' = x + 0.05 eps) observed through ``z = x + 0.3 eps``,
     filtered with the model that generated them (user models: the step-by-step history and the generic prediction path):
@@ -618,12 +522,12 @@ def test_simulation_is_no_worse_than_ancestry_against_the_exact_smoother():
     import multimodalfilter_amd as mmf
     from multimodalfilter_amd import synthetic
 
-    dev = _dev()
+    dev = sc.dev()
     d, N, M, T, S = 3, 8, 512, 40, 256
     q, r = 0.05, 0.3
     truth = synthetic.make_trajectories(state_dim=d, T=T, N=N, seed=23)["states"]
     z = truth[1:] + r * torch.randn((T, N, d), generator=torch.Generator().manual_seed(29))
-    dyn, meas = _linear_gaussian_models(d, q, r, dev)
+    dyn, meas = sc.linear_gaussian_models(d, q, r, dev)
     f = mmf.filters.ParticleFilter(dynamics_model=dyn, measurement_model=meas, num_particles=M)
     f.eval()
     f.record_history = True
@@ -640,7 +544,7 @@ def test_simulation_is_no_worse_than_ancestry_against_the_exact_smoother():
     L = C(q * torch.eye(d))
     idx64 = torch.from_numpy(_simulate64(C(h.states), C(h.states[:-1]), C(h.log_likelihoods), C(h.log_weights_in), L, C(u)))
     sim64 = _gather(h.states.cpu(), idx64).double().mean(2)
-    exact = torch.from_numpy(_rts(z.double().numpy(), truth[0].double().numpy(), 0.1, q, r))
+    exact = torch.from_numpy(sc.rts(z.double().numpy(), truth[0].double().numpy(), 0.1, q, r))
     rmse = lambda x: float((x.double().cpu()[:T - 9] - exact[:T - 9]).pow(2).sum(-1).mean().sqrt())
     print(f"RMSE to the exact smoother over steps 0 .. T-10: simulation {rmse(simulation):.5f} (fp64 restatement "
           f"{rmse(sim64):.5f}), ancestry {rmse(ancestry):.5f}, filter {rmse(est):.5f}")
@@ -652,9 +556,9 @@ def test_simulation_is_no_worse_than_ancestry_against_the_exact_smoother():
 def test_state_dependent_noise_is_refused():
     import multimodalfilter_amd as mmf
 
-    dev = _dev()
+    dev = sc.dev()
     d, N, M, T = 2, 2, 64, 3
-    dyn, meas = _linear_gaussian_models(d, 0.05, 0.3, dev, state_dependent=True)
+    dyn, meas = sc.linear_gaussian_models(d, 0.05, 0.3, dev, state_dependent=True)
     f = mmf.filters.ParticleFilter(dynamics_model=dyn, measurement_model=meas, num_particles=M)
     f.eval()
     f.record_history = True

@@ -1,9 +1,9 @@
 """Particle smoothing on the GPU (``include/mmf.h``: ``mmf_pf_smooth``, ``mmf_pf_forward_loop_history``;
 ``ParticleFilter.record_history`` / ``smooth`` / ``evaluation.run_filter(smooth_lag=)``).
 
-The kernel is held to an fp64 restatement of the definition (``_reference`` below: ancestry trace + weighted moments) at
-the project's bar (``_tol.REL_TOL`` through ``rel_err``, per trajectory so that a narrow cloud is measured against its own
-scale); ``unique`` exactly.  The forward side is held to the loop it stands for, bit for bit."""
+The kernel is held to an fp64 restatement of the definition (``_smooth_cases.ancestry_reference``: ancestry trace + weighted
+moments) at the project's bar (``_tol.REL_TOL`` through ``rel_err``, per trajectory so that a narrow cloud is measured against
+its own scale); ``unique`` exactly.  The forward side is held to the loop it stands for, bit for bit."""
 import functools
 import math
 
@@ -13,81 +13,19 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from oracle import models as om
-
+import _smooth_cases as sc
 from _tol import REL_TOL, rel_err
-
-
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a real MI355X")
-    return torch.device("cuda:0")
-
-
-# ------------------------------------------------------------------------------------------ the fp64 reference
-def _reference(X, ll, lw, lw0, A, lag):
-    """Definition of ``mmf_pf_smooth`` in fp64 numpy: ``X (T, N, M, d)``, ``ll (T, N, M)``, ``lw (T, N, M)`` or None,
-    ``lw0 (N, M)`` or None, ``A (T, N, M)`` or None (identity) -> mean, cov, unique."""
-    T, N, M, d = X.shape
-    L = min(int(lag), max(T - 1, 0))
-    mean, cov, uniq = np.zeros((T, N, d)), np.zeros((T, N, d, d)), np.zeros((T, N), dtype=np.int64)
-    for n in range(N):
-        for t in range(T):
-            s = min(t + L, T - 1)
-            a = ll[s, n].astype(np.float64)
-            if lw is not None:
-                a = a + lw[s, n]
-            elif s == 0 and lw0 is not None:
-                a = a + lw0[n]
-            b = np.arange(M)
-            for r in range(s, t, -1):  # from step r to r - 1
-                if A is not None:
-                    b = A[r - 1, n][b]
-            w = np.exp(a - a.max())
-            w = w / w.sum()
-            alive = a > -np.inf
-            x = X[t, n].astype(np.float64)[b[alive]]
-            mu = w[alive] @ x
-            dx = x - mu
-            mean[t, n], cov[t, n], uniq[t, n] = mu, (w[alive][:, None] * dx).T @ dx, len(np.unique(b[alive]))
-    return mean, cov, uniq
-
-
-def _systematic(w, u):
-    """Ancestors of systematic resampling (numpy, fp64): positions ``(u + k) / M`` in the CDF of ``w``."""
-    M = len(w)
-    cdf = np.cumsum(w / w.sum())
-    cdf[-1] = 1.0
-    return np.minimum(np.searchsorted(cdf, (u + np.arange(M)) / M, side="right"), M - 1).astype(np.int32)
-
-
-def _make_case(T, N, M, d, widths, ll_scale, seed, same_ancestor=None):
-    """Clouds of the given widths around an O(1) mean that drifts with the step; ancestors from systematic resampling of
-    the step's own weights (so that high-likelihood particles have many descendants)."""
-    rng = np.random.default_rng(seed)
-    widths = np.resize(np.asarray(widths, dtype=np.float64), N)
-    centre = rng.normal(size=(1, N, 1, d)) + 0.1 * rng.normal(size=(T, N, 1, d)).cumsum(0)
-    X = (centre + widths[None, :, None, None] * rng.normal(size=(T, N, M, d))).astype(np.float32)
-    ll = (ll_scale * rng.normal(size=(T, N, M))).astype(np.float32)
-    lw = 0.3 * rng.normal(size=(T, N, M))
-    lw = (lw - np.log(np.exp(lw).sum(-1, keepdims=True))).astype(np.float32)
-    A = np.zeros((T, N, M), dtype=np.int32)
-    for t in range(T):
-        for n in range(N):
-            a = ll[t, n].astype(np.float64) + lw[t, n]
-            A[t, n] = _systematic(np.exp(a - a.max()), rng.uniform()) if same_ancestor is None else same_ancestor
-    return X, ll, lw, A
 
 
 def _run(X, ll, lw, lw0, A, lag, want_cov=True, want_unique=True):
     from multimodalfilter_amd import _abi
 
-    dev = _dev()
+    dev = sc.dev()
     T, N, M, d = X.shape
-    G = lambda x, dt=torch.float32: None if x is None else torch.as_tensor(x, dtype=dt).contiguous().to(dev)
     mean = torch.full((T, N, d), math.nan, device=dev)
     cov = torch.full((T, N, d, d), math.nan, device=dev) if want_cov else None
     uniq = torch.full((T, N), -1, dtype=torch.int32, device=dev) if want_unique else None
+    G = sc.to_device
     _abi.pf_smooth(G(X), G(ll), G(lw), G(lw0), G(A, torch.int32), lag, mean, cov, uniq)
     torch.cuda.synchronize()
     return mean, cov, uniq
@@ -106,10 +44,7 @@ def _check(got, want, what):
     assert e_mean <= REL_TOL, (what, e_mean)
     assert e_cov <= REL_TOL, (what, e_cov)
     assert np.array_equal(uniq.cpu().numpy().astype(np.int64), wuniq), what
-    assert torch.equal(cov, cov.transpose(-1, -2)), what
-    c = cov.double().cpu()
-    floor = -1e-4 * torch.diagonal(c, dim1=-2, dim2=-1).sum(-1)
-    assert bool((torch.linalg.eigvalsh(c).min(-1).values >= floor - 1e-30).all()), what
+    sc.assert_symmetric_psd(cov, what)
 
 
 # ------------------------------------------------------------------------------------------ 1. kernel against fp64
@@ -124,23 +59,23 @@ def test_smooth_kernel_matches_fp64(M, d, ll_scale):
     incoming log-weights and the ancestors each null and given.  At scale 50 the genealogy collapses to one path after a
     step; scale 0.5 keeps dozens of paths alive."""
     T, N = 9, 3
-    X, ll, lw, A = _make_case(T, N, M, d, _WIDTHS, ll_scale, seed=1000 * M + 10 * d + int(ll_scale))
+    X, ll, lw, A = sc.make_ancestry_case(T, N, M, d, _WIDTHS, ll_scale, seed=1000 * M + 10 * d + int(ll_scale))
     for lag in (0, 2, 12):
         for use_lw in (False, True):
             for use_A in (False, True):
                 lw_, lw0_, A_ = (lw if use_lw else None), (None if use_lw else lw[0]), (A if use_A else None)
                 got = _run(X, ll, lw_, lw0_, A_, lag)
-                _check(got, _reference(X, ll, lw_, lw0_, A_, lag), f"M={M} d={d} scale={ll_scale} lag={lag} lw={use_lw} A={use_A}")
+                _check(got, sc.ancestry_reference(X, ll, lw_, lw0_, A_, lag), f"M={M} d={d} scale={ll_scale} lag={lag} lw={use_lw} A={use_A}")
 
 
 # ------------------------------------------------------------------------------------------ 2. edges
 def test_single_step_and_single_particle():
-    X, ll, lw, A = _make_case(1, 3, 300, 3, _WIDTHS, 0.5, seed=1)
+    X, ll, lw, A = sc.make_ancestry_case(1, 3, 300, 3, _WIDTHS, 0.5, seed=1)
     for lag in (0, 5):
-        _check(_run(X, ll, lw, None, A, lag), _reference(X, ll, lw, None, A, lag), f"T=1 lag={lag}")
-    X, ll, lw, A = _make_case(5, 2, 1, 2, _WIDTHS, 0.5, seed=2)
+        _check(_run(X, ll, lw, None, A, lag), sc.ancestry_reference(X, ll, lw, None, A, lag), f"T=1 lag={lag}")
+    X, ll, lw, A = sc.make_ancestry_case(5, 2, 1, 2, _WIDTHS, 0.5, seed=2)
     got = _run(X, ll, lw, None, A, 2)
-    _check(got, _reference(X, ll, lw, None, A, 2), "M=1")
+    _check(got, sc.ancestry_reference(X, ll, lw, None, A, 2), "M=1")
     assert torch.equal(got[0].cpu(), torch.from_numpy(X[:, :, 0]))  # the one particle is the mean
     assert float(got[1].abs().max()) == 0.0 and bool((got[2] == 1).all())
 
@@ -150,11 +85,11 @@ def test_lags_and_the_full_smoother(M):
     """Lags 0, T - 1 and T + 3: the last two are the same launch and give identical bits; two calls on the same inputs
     return the same bits (fixed-order reductions).  M = 1100 / 4096: a thread owns several particles."""
     T = 6
-    X, ll, lw, A = _make_case(T, 3, M, 3, _WIDTHS, 0.5, seed=3 + M)
+    X, ll, lw, A = sc.make_ancestry_case(T, 3, M, 3, _WIDTHS, 0.5, seed=3 + M)
     outs = {}
     for lag in (0, T - 1, T + 3):
         outs[lag] = _run(X, ll, lw, None, A, lag)
-        _check(outs[lag], _reference(X, ll, lw, None, A, lag), f"M={M} lag={lag}")
+        _check(outs[lag], sc.ancestry_reference(X, ll, lw, None, A, lag), f"M={M} lag={lag}")
         again = _run(X, ll, lw, None, A, lag)
         for x, y in zip(outs[lag], again):
             assert torch.equal(x, y), (M, lag)
@@ -168,21 +103,21 @@ def test_lags_and_the_full_smoother(M):
 @pytest.mark.parametrize("M,d", [(5000, 3), (17000, 2)])
 def test_many_particles_per_thread(M, d):
     """The two largest per-thread particle counts of the dispatcher (16 and 40 per thread)."""
-    X, ll, lw, A = _make_case(3, 2, M, d, (1e-2, 0.3), 0.5, seed=M)
-    _check(_run(X, ll, None, lw[0], A, 3), _reference(X, ll, None, lw[0], A, 3), f"M={M}")
+    X, ll, lw, A = sc.make_ancestry_case(3, 2, M, d, (1e-2, 0.3), 0.5, seed=M)
+    _check(_run(X, ll, None, lw[0], A, 3), sc.ancestry_reference(X, ll, None, lw[0], A, 3), f"M={M}")
 
 
 def test_one_common_ancestor_and_identity_ancestors():
     T, N, M, d = 5, 3, 300, 3
-    X, ll, lw, A = _make_case(T, N, M, d, _WIDTHS, 0.5, seed=7, same_ancestor=123)
+    X, ll, lw, A = sc.make_ancestry_case(T, N, M, d, _WIDTHS, 0.5, seed=7, same_ancestor=123)
     got = _run(X, ll, lw, None, A, T)
-    _check(got, _reference(X, ll, lw, None, A, T), "one ancestor")
+    _check(got, sc.ancestry_reference(X, ll, lw, None, A, T), "one ancestor")
     assert bool((got[2][:-1] == 1).all()) and bool((got[2][-1] == M).all())
     assert float(got[1][:-1].abs().max()) == 0.0  # one particle: no spread at all
     assert torch.equal(got[0][:-1].cpu(), torch.from_numpy(X[:-1, :, 123]))
     ident = np.broadcast_to(np.arange(M, dtype=np.int32), (T, N, M)).copy()
     a, b = _run(X, ll, lw, None, ident, T), _run(X, ll, lw, None, None, T)
-    _check(a, _reference(X, ll, lw, None, None, T), "identity ancestors")
+    _check(a, sc.ancestry_reference(X, ll, lw, None, None, T), "identity ancestors")
     for x, y in zip(a, b):
         assert torch.equal(x, y)  # null IS the identity
     assert bool((a[2] == M).all())
@@ -192,21 +127,21 @@ def test_dead_paths_and_a_single_heavy_particle():
     """-inf log-likelihoods on half a row: a finite result equal to the reference over the rest (whatever the dead rows
     hold: they are filled with inf), counted out of ``unique``.  One particle with all the weight: its path alone."""
     T, N, M, d = 5, 3, 300, 3
-    X, ll, lw, A = _make_case(T, N, M, d, _WIDTHS, 0.5, seed=11)
+    X, ll, lw, A = sc.make_ancestry_case(T, N, M, d, _WIDTHS, 0.5, seed=11)
     ll[:, 1, ::2] = -np.inf
     X[-1, 1, ::2] = np.inf  # only a path of zero weight ever reads these rows at the endpoint
     for t in range(T):      # ancestors drawn from the weights never point at a dead particle
         a = ll[t, 1].astype(np.float64) + lw[t, 1]
-        A[t, 1] = _systematic(np.exp(a - a.max()), 0.37)
+        A[t, 1] = sc.systematic(np.exp(a - a.max()), 0.37)
     for lag in (0, 2, T):
         got = _run(X, ll, lw, None, A, lag)
-        want = _reference(X, ll, lw, None, A, lag)
+        want = sc.ancestry_reference(X, ll, lw, None, A, lag)
         _check(got, want, f"half dead lag={lag}")
         assert int(got[2][-1, 1]) == M // 2
-    X, ll, lw, A = _make_case(T, N, M, d, _WIDTHS, 0.5, seed=12)
+    X, ll, lw, A = sc.make_ancestry_case(T, N, M, d, _WIDTHS, 0.5, seed=12)
     ll[-1, :, 17] = 60.0  # the others keep exp(-60) ~ 1e-26 of it: far below an fp32 ulp of the mean, not yet zero
     got = _run(X, ll, lw, None, A, T)
-    _check(got, _reference(X, ll, lw, None, A, T), "one heavy particle")
+    _check(got, sc.ancestry_reference(X, ll, lw, None, A, T), "one heavy particle")
     b = np.full(N, 17)
     for t in range(T - 1, -1, -1):
         assert rel_err(got[0][t], torch.from_numpy(X[t, np.arange(N), b]), dims=1) <= 1e-6, t  # its path alone
@@ -217,15 +152,15 @@ def test_dead_paths_and_a_single_heavy_particle():
 def test_out_of_range_ancestors_are_clamped():
     """Indices just outside ``[0, M)`` behave as the nearest valid one: a wrong number at worst, never a stray read."""
     T, N, M, d = 4, 2, 300, 3
-    X, ll, lw, A = _make_case(T, N, M, d, (1e-2, 0.3), 0.5, seed=13)
+    X, ll, lw, A = sc.make_ancestry_case(T, N, M, d, (1e-2, 0.3), 0.5, seed=13)
     bad = A.copy()
     bad[:, :, 5], bad[:, :, 6], bad[:, :, 7] = -1, M, M + 7
     got = _run(X, ll, lw, None, bad, T)
-    _check(got, _reference(X, ll, lw, None, np.clip(bad, 0, M - 1), T), "clamped")
+    _check(got, sc.ancestry_reference(X, ll, lw, None, np.clip(bad, 0, M - 1), T), "clamped")
 
 
 def test_optional_outputs_may_be_null():
-    X, ll, lw, A = _make_case(4, 2, 300, 3, (1e-2, 0.3), 0.5, seed=14)
+    X, ll, lw, A = sc.make_ancestry_case(4, 2, 300, 3, (1e-2, 0.3), 0.5, seed=14)
     full = _run(X, ll, lw, None, A, 2)
     only_mean = _run(X, ll, lw, None, A, 2, want_cov=False, want_unique=False)
     assert torch.equal(full[0], only_mean[0])
@@ -236,23 +171,6 @@ _CONFIGS = {"plain": {}, "multinomial": {"resample_mode": "multinomial"}, "soft"
             "ess": {"resample_ess_threshold": 0.5}, "noresample": {"resample": False}}
 
 
-def _filter(cls, N, M, T, dev):
-    import multimodalfilter_amd as mmf
-    from multimodalfilter_amd import synthetic
-
-    tname = "door" if cls.startswith("Door") else "push"
-    d = om.TASKS[tname].state_dim
-    torch.manual_seed(3)
-    f = mmf.model_types(tname)[cls]().to(dev).eval()
-    f.num_particles = M
-    traj = {k: v.to(dev) for k, v in synthetic.make_trajectories(state_dim=d, T=T, N=N, seed=17).items()}
-    obs = {k: traj[k][1:] for k in ("image", "gripper_pos", "gripper_sensors")}
-    cal = traj["states"][0][:, None, :] + 0.3 * torch.randn((N, 256, d), device=dev)
-    synthetic.calibrate_measurement_heads(f, {k: v[0] for k, v in obs.items()}, cal, target_std=1.2)
-    cov = (torch.eye(d, device=dev) * 0.1)[None].expand(N, d, d)
-    return f, d, traj, obs, traj["controls"][1:], cov
-
-
 @functools.lru_cache(maxsize=None)
 def _runs(config, M, noise):
     """One filter, four runs on the same randomness: plain, with ``record_indices``, with ``record_history`` through the
@@ -260,9 +178,9 @@ def _runs(config, M, noise):
     import multimodalfilter_amd as mmf
     from multimodalfilter_amd import _abi
 
-    dev = _dev()
+    dev = sc.dev()
     N, T = 4, 6
-    f, d, traj, obs, ctrl, cov = _filter("DoorParticleFilter" if noise == "tensor" else "PushParticleFilter", N, M, T, dev)
+    f, d, traj, obs, ctrl, cov = sc.small_filter("DoorParticleFilter" if noise == "tensor" else "PushParticleFilter", N, M, T, dev)
     for k, v in _CONFIGS[config].items():
         setattr(f, k, v)
     mode = f.resample_mode
@@ -357,12 +275,6 @@ def test_lag_zero_is_the_filter_and_unique_shrinks_backwards(config, M):
         assert (uniq[0] < M).all()  # resampling has merged paths
 
 
-def _reference_of_history(h, lag):
-    T = h.states.shape[0]
-    N = lambda x: None if x is None else x.cpu().numpy()
-    return _reference(N(h.states), N(h.log_likelihoods), N(h.log_weights_in), None, N(h.ancestors), T if lag is None else lag)
-
-
 @pytest.mark.parametrize("config,M,noise", [("plain", 300, "tensor"), ("plain", 64, "philox"), ("ess", 300, "tensor"),
                                             ("noresample", 64, "tensor")])
 def test_filter_smooth_matches_the_reference_on_its_history(config, M, noise):
@@ -373,7 +285,7 @@ def test_filter_smooth_matches_the_reference_on_its_history(config, M, noise):
         mean = f.smooth(lag)
         rec = f.last_smoothed
         assert rec.lag == lag and rec.unique.dtype == torch.int32
-        _check((mean, rec.covariance, rec.unique), _reference_of_history(f.last_history, lag), f"{config} M={M} {noise} lag={lag}")
+        _check((mean, rec.covariance, rec.unique), sc.ancestry_reference_of_history(f.last_history, lag), f"{config} M={M} {noise} lag={lag}")
 
 
 def test_run_filter_returns_the_smoothed_record():
@@ -382,9 +294,9 @@ def test_run_filter_returns_the_smoothed_record():
     import multimodalfilter_amd as mmf
     from multimodalfilter_amd import evaluation
 
-    dev = _dev()
+    dev = sc.dev()
     N, M, T = 4, 300, 8
-    f, d, traj, obs, ctrl, cov = _filter("DoorParticleFilter", N, M, T, dev)
+    f, d, traj, obs, ctrl, cov = sc.small_filter("DoorParticleFilter", N, M, T, dev)
     f.noise = mmf.CounterNoise(7)
     plain = evaluation.run_filter(f, traj)
     assert f.last_history is None and f.record_history is False
@@ -392,7 +304,7 @@ def test_run_filter_returns_the_smoothed_record():
     est, rec = evaluation.run_filter(f, traj, smooth_lag=None, return_belief=True)
     assert f.record_history is False and f.record_belief is False  # switched back
     assert est.shape == (T, N, d) and rec.covariance.shape == (T, N, d, d) and rec.unique.shape == (T, N) and rec.lag is None
-    _check((est, rec.covariance, rec.unique), _reference_of_history(f.last_history, None), "run_filter full smoother")
+    _check((est, rec.covariance, rec.unique), sc.ancestry_reference_of_history(f.last_history, None), "run_filter full smoother")
     assert torch.equal(est[-1], f.smooth(0)[-1])  # the last step has nothing to look ahead to
     assert rel_err(est[-1], plain[-1], dims=1) <= REL_TOL
     f.noise = mmf.CounterNoise(7)
@@ -412,7 +324,7 @@ def test_history_of_a_belief_with_another_particle_count():
     history pads step 0 with dead particles (log-likelihood -inf), and ``smooth`` equals the reference on it."""
     r = _runs("plain", 300, "tensor")
     f = r["filter"]
-    dev = _dev()
+    dev = sc.dev()
     import multimodalfilter_amd as mmf
     from multimodalfilter_amd import synthetic
 
@@ -434,7 +346,7 @@ def test_history_of_a_belief_with_another_particle_count():
     assert bool(torch.isfinite(h.log_likelihoods[1:]).all()) and int(h.ancestors[0].max()) < M0
     for lag in (0, None):
         mean = f.smooth(lag)
-        _check((mean, f.last_smoothed.covariance, f.last_smoothed.unique), _reference_of_history(h, lag), f"100 -> 300 lag={lag}")
+        _check((mean, f.last_smoothed.covariance, f.last_smoothed.unique), sc.ancestry_reference_of_history(h, lag), f"100 -> 300 lag={lag}")
     assert rel_err(f.smooth(0), est, dims=1) <= REL_TOL
     assert int(f.smooth(0).shape[0]) == T and bool((f.last_smoothed.unique[0] <= M0).all())
 
@@ -446,7 +358,7 @@ def test_full_smoother_is_no_worse_than_the_filter_on_a_linear_gaussian_trajecto
     import multimodalfilter_amd as mmf
     from multimodalfilter_amd import base, synthetic
 
-    dev = _dev()
+    dev = sc.dev()
     d, N, M, T = 3, 8, 512, 40
     q, r = 0.05, 0.3
     truth = synthetic.make_trajectories(state_dim=d, T=T, N=N, seed=23)["states"]
@@ -476,7 +388,7 @@ def test_full_smoother_is_no_worse_than_the_filter_on_a_linear_gaussian_trajecto
     est = f.forward_loop(observations={"z": z.to(dev)}, controls=torch.zeros((T, N, 7), device=dev))
     assert f.last_history.states.shape == (T, N, M, d) and f.last_history.ancestors.shape == (T, N, M)
     smoothed = f.smooth()
-    _check((smoothed, f.last_smoothed.covariance, f.last_smoothed.unique), _reference_of_history(f.last_history, None), "linear-Gaussian")
+    _check((smoothed, f.last_smoothed.covariance, f.last_smoothed.unique), sc.ancestry_reference_of_history(f.last_history, None), "linear-Gaussian")
     rmse = lambda x: float((x.cpu()[:T - 9] - truth[1:][:T - 9]).pow(2).sum(-1).mean().sqrt())
     print(f"RMSE over steps 0 .. T-10: filter {rmse(est):.5f}, full smoother {rmse(smoothed):.5f}; "
           f"unique at step 0 / T-10 / T-1: {f.last_smoothed.unique[[0, T - 10, T - 1]].float().mean(-1).tolist()}")

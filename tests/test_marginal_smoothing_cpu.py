@@ -1,80 +1,31 @@
 """CPU-side checks of marginal particle smoothing's boundary (``include/mmf.h``: ``MmfPfSmoothMarginalArgs`` /
-``mmf_pf_smooth_marginal``): header, binding and exports agree on the struct; the entry point refuses bad arguments on the
-host, before any HIP call; the Python switches refuse what they cannot do and keep what they did before."""
+``mmf_pf_smooth_marginal``): the entry point refuses bad arguments on the host, before any HIP call; the Python switches
+refuse what they cannot do and keep what they did before.  (The struct's layout: ``test_abi_cpu.py``, for every struct of the
+binding.)"""
 import ctypes
 import inspect
-import os
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import _smooth_cases as sc
+
 EINVAL, ETOOLARGE = -1, -2
-
-
-def _lib():
-    from multimodalfilter_amd import _abi, build
-
-    build.build()
-    return _abi.load()
-
-
-def test_marginal_struct_matches_the_header_field_by_field(tmp_path):
-    """``offsetof`` / ``sizeof`` as gcc lays ``include/mmf.h`` out against ctypes' (the technique of
-    ``test_smoothing_cpu.py``); the library exports the symbol the binding declares and is still ABI 42."""
-    from multimodalfilter_amd import _abi
-
-    lib = _lib()
-    assert "mmf_pf_smooth_marginal" in _abi.SIGNATURES and hasattr(lib, "mmf_pf_smooth_marginal")
-    assert lib.mmf_version() == 42 == _abi.ABI_VERSION  # purely additive
-    gcc = shutil.which("gcc")
-    if gcc is None:
-        pytest.skip("no gcc")
-    name, cls = "MmfPfSmoothMarginalArgs", _abi.MmfPfSmoothMarginalArgs
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{os.path.join(ROOT, "include", "mmf.h")}"', "int main(void) {",
-             f'  printf("size %zu\\n", sizeof({name}));']
-    for field, _t in cls._fields_:
-        lines.append(f'  printf("{field} %zu\\n", offsetof({name}, {field}));')
-    lines += ["  return 0;", "}"]
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    out = subprocess.run([gcc, "-std=c99", "-o", str(exe), str(src)], capture_output=True, text=True)
-    assert out.returncode == 0, out.stderr[-2000:]
-    got = dict((k, int(v)) for k, v in (line.split() for line in
-                                        subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines()))
-    assert got["size"] == ctypes.sizeof(cls), (got["size"], ctypes.sizeof(cls))
-    for field, _t in cls._fields_:
-        assert got[field] == getattr(cls, field).offset, field
-    last, last_t = cls._fields_[-1]
-    assert getattr(cls, last).offset + ctypes.sizeof(last_t) + 8 > ctypes.sizeof(cls)  # no hidden C field at the end
-
 
 _POINTERS = ("states_steps", "pred_steps", "loglik_steps", "logw_in_steps", "scale_tril", "logd", "weights", "mean", "cov", "ess")
 
 
-def _args(keep, **over):
+def _args(**over):
     from multimodalfilter_amd import _abi
 
-    bufs = [(ctypes.c_float * 16)() for _ in _POINTERS]
-    keep.append(bufs)
-    a = _abi.MmfPfSmoothMarginalArgs()
-    a.T, a.N, a.M, a.d = 4, 2, 64, 3
-    for name, b in zip(_POINTERS, bufs):
-        setattr(a, name, ctypes.cast(b, ctypes.c_void_p))
-    for k, v in over.items():
-        setattr(a, k, v)
-    return a
+    return sc.host_args(_abi.MmfPfSmoothMarginalArgs, _POINTERS, **{**dict(T=4, N=2, M=64, d=3), **over})
 
 
 def test_marginal_refuses_bad_arguments_on_the_host():
     """Nulls and negative sizes -> ``MMF_EINVAL``; ``d``, ``M`` or ``N`` beyond the limits -> ``MMF_ETOOLARGE``; no
     trajectories or no steps -> a successful no-op.  All decided before any HIP call: the pointers are host memory and never
     dereferenced, and the stream is null."""
-    lib = _lib()
-    keep = []
-    call = lambda **over: lib.mmf_pf_smooth_marginal(ctypes.byref(_args(keep, **over)), None)
+    lib = sc.lib()
+    call = lambda **over: lib.mmf_pf_smooth_marginal(ctypes.byref(_args(**over)), None)
     assert lib.mmf_pf_smooth_marginal(None, None) == EINVAL
     for field in ("states_steps", "loglik_steps", "scale_tril", "weights", "mean", "pred_steps", "logd"):
         assert call(**{field: None}) == EINVAL, field

@@ -1,89 +1,36 @@
 """CPU-side checks of the two-slice smoothing moments (``include/mmf.h``: ``MmfPfSmoothPairArgs`` /
-``mmf_pf_smooth_pair_moments``) and of the EM refit built on them: header, binding and exports agree on the struct; the
-entry point refuses bad arguments on the host, before any HIP call; the Python switches refuse what they cannot do; the
-M-step's known answers; the fp64 reference of the GPU tests is tied to the marginal smoother's and to the exact
-linear-Gaussian EM step."""
+``mmf_pf_smooth_pair_moments``) and of the EM refit built on them: the entry point refuses bad arguments on the host,
+before any HIP call; the Python switches refuse what they cannot do; the M-step's known answers; the fp64 reference of the
+GPU tests (``_smooth_cases.reference``) is held to its own identities, with the difference ``X - F`` in either precision,
+and to the exact linear-Gaussian EM step.  (The struct's layout: ``test_abi_cpu.py``, for every struct of the binding.)"""
 import ctypes
 import inspect
-import os
-import shutil
-import subprocess
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
-import _pair_cases as pc
+import _smooth_cases as sc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL, ETOOLARGE = -1, -2
-
-
-def _lib():
-    from multimodalfilter_amd import _abi, build
-
-    build.build()
-    return _abi.load()
-
-
-def test_pair_struct_matches_the_header_field_by_field(tmp_path):
-    """``offsetof`` / ``sizeof`` as gcc lays ``include/mmf.h`` out against ctypes' (the technique of
-    ``test_marginal_smoothing_cpu.py``); the library exports the symbols the binding declares and is still ABI 42."""
-    from multimodalfilter_amd import _abi
-
-    lib = _lib()
-    for sym in ("mmf_pf_smooth_pair_moments", "mmf_pf_smooth_pair_workspace_floats"):
-        assert sym in _abi.SIGNATURES and hasattr(lib, sym), sym
-    assert lib.mmf_version() == 42 == _abi.ABI_VERSION  # purely additive
-    gcc = shutil.which("gcc")
-    if gcc is None:
-        pytest.skip("no gcc")
-    name, cls = "MmfPfSmoothPairArgs", _abi.MmfPfSmoothPairArgs
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{os.path.join(ROOT, "include", "mmf.h")}"', "int main(void) {",
-             f'  printf("size %zu\\n", sizeof({name}));']
-    for field, _t in cls._fields_:
-        lines.append(f'  printf("{field} %zu\\n", offsetof({name}, {field}));')
-    lines += ["  return 0;", "}"]
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    out = subprocess.run([gcc, "-std=c99", "-o", str(exe), str(src)], capture_output=True, text=True)
-    assert out.returncode == 0, out.stderr[-2000:]
-    got = dict((k, int(v)) for k, v in (line.split() for line in
-                                        subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines()))
-    assert got["size"] == ctypes.sizeof(cls), (got["size"], ctypes.sizeof(cls))
-    for field, _t in cls._fields_:
-        assert got[field] == getattr(cls, field).offset, field
-    last, last_t = cls._fields_[-1]
-    assert getattr(cls, last).offset + ctypes.sizeof(last_t) + 8 > ctypes.sizeof(cls)  # no hidden C field at the end
-
 
 _POINTERS = ("states_steps", "pred_steps", "loglik_steps", "logw_in_steps", "scale_tril", "weights", "logd", "workspace",
              "residual_mean", "residual_second_moment")
 
 
-def _args(keep, **over):
+def _args(**over):
     from multimodalfilter_amd import _abi
 
-    bufs = [(ctypes.c_float * 16)() for _ in _POINTERS]
-    keep.append(bufs)
-    a = _abi.MmfPfSmoothPairArgs()
-    a.T, a.N, a.M, a.d = 4, 2, 64, 3
-    for name, b in zip(_POINTERS, bufs):
-        setattr(a, name, ctypes.cast(b, ctypes.c_void_p))
-    for k, v in over.items():
-        setattr(a, k, v)
-    return a
+    return sc.host_args(_abi.MmfPfSmoothPairArgs, _POINTERS, **{**dict(T=4, N=2, M=64, d=3), **over})
 
 
 def test_pair_moments_refuse_bad_arguments_on_the_host():
     """Nulls and negative sizes -> ``MMF_EINVAL``; ``d``, ``M`` or ``N`` beyond the limits -> ``MMF_ETOOLARGE``; no
     trajectories or no transition (``T < 2``) -> a successful no-op.  All decided before any HIP call: the pointers are host
     memory and never dereferenced, and the stream is null."""
-    lib = _lib()
-    keep = []
-    call = lambda **over: lib.mmf_pf_smooth_pair_moments(ctypes.byref(_args(keep, **over)), None)
+    lib = sc.lib()
+    call = lambda **over: lib.mmf_pf_smooth_pair_moments(ctypes.byref(_args(**over)), None)
     assert lib.mmf_pf_smooth_pair_moments(None, None) == EINVAL
     for field in ("states_steps", "loglik_steps", "scale_tril", "weights", "pred_steps", "logd", "workspace", "residual_mean",
                   "residual_second_moment"):
@@ -102,7 +49,7 @@ def test_pair_moments_refuse_bad_arguments_on_the_host():
 
 
 def test_workspace_size_is_the_documented_one():
-    lib = _lib()
+    lib = sc.lib()
     size = lib.mmf_pf_smooth_pair_workspace_floats
     for T, N, M, d in [(5, 3, 300, 3), (2, 1, 1, 1), (40, 8, 512, 4), (5, 3, 64, 2), (5, 3, 65, 2)]:
         assert size(T, N, M, d) == (T - 1) * N * ((M + 63) // 64) * (1 + d + d * (d + 1) // 2), (T, N, M, d)
@@ -227,43 +174,22 @@ def test_model_noise_setters_and_fit_refusal():
         evaluation.fit_process_noise(push, None, smooth_method="ancestry")
 
 
-def _marginal_reference(X, F, ll, lw, L):
-    """The marginal smoother's definition as ``test_gpu_marginal_smoothing.py`` states it (the difference in fp64)."""
-    T, N, M, d = X.shape
-    W = pc.softmax_rows(ll.astype(np.float64) + (0.0 if lw is None else lw.astype(np.float64)))
-    Linv = np.linalg.inv(np.tril(np.asarray(L, dtype=np.float64)))
-    S = np.zeros((T, N, M))
-    S[T - 1] = W[T - 1]
-    for n in range(N):
-        for t in range(T - 2, -1, -1):
-            rows, cols = np.flatnonzero(W[t, n] > 0), np.flatnonzero(S[t + 1, n] > 0)
-            diff = X[t + 1, n][cols].astype(np.float64)[None, :, :] - F[t, n][rows].astype(np.float64)[:, None, :]
-            z = diff @ Linv.T
-            term = np.log(W[t, n][rows])[:, None] - 0.5 * (z * z).sum(-1)
-            top = term.max(0)
-            logD = top + np.log(np.exp(term - top).sum(0))
-            w = (S[t + 1, n][cols][None, :] * np.exp(term - logD[None, :])).sum(1)
-            S[t, n][rows] = w / w.sum()
-    return S
-
-
 @pytest.mark.parametrize("M,d,full,ll_scale", [(37, 2, False, 0.5), (150, 3, True, 0.5), (150, 4, True, 50.0)])
 def test_reference_row_marginal_is_the_marginal_smoothers_weight(M, d, full, ll_scale):
     """``sum_j xi[i, j] = W_{t|T}[i]`` and ``sum_ij xi = 1`` to 1e-12 inside the two-slice reference; its ``W_{t|T}`` are those
-    of the marginal smoother's own reference up to the fp32 rounding of the difference ``X - F`` (the one thing the two
-    restatements do differently), and, with dead particles, zero where theirs are."""
-    L = pc.tril(d, full)
-    X, F, ll, lw = pc.make_case(5, 3, M, d, (1e-3, 1e-2, 0.3), ll_scale, L, seed=7 + M + d)
+    of the same reference with the difference ``X - F`` formed in fp64 (what the marginal smoother's kernels are held to) up
+    to the fp32 rounding of that difference, and, with dead particles, zero where theirs are."""
+    L = sc.tril(d, full)
+    X, F, ll, lw = sc.make_case(5, 3, M, d, (1e-3, 1e-2, 0.3), ll_scale, L, seed=7 + M + d)
     ll[:, 1, ::3] = -np.inf
     X[:, 1, ::3] = np.inf
     F[:, 1, ::3] = np.inf
-    ref = pc.reference(X, F, ll, lw, L)
+    ref = sc.reference(X, F, ll, lw, L)
     assert np.abs(ref["total"] - 1.0).max() <= 1e-12
     assert np.abs(ref["row_marginal"] - ref["weights"][:-1]).max() <= 1e-12
     assert np.abs(ref["weights"].sum(-1) - 1.0).max() <= 1e-12
     assert np.isfinite(ref["residual_mean"]).all() and np.isfinite(ref["residual_second_moment"]).all()
-    Xd, Fd = X.astype(np.float64), F.astype(np.float64)
-    S = _marginal_reference(Xd, Fd, ll, lw, L)
+    S = sc.reference(X.astype(np.float64), F.astype(np.float64), ll, lw, L)["weights"]  # (as the marginal GPU test calls it)
     assert (S[:, 1, ::3] == 0).all() and (ref["weights"][:, 1, ::3] == 0).all()
     # the fp32 difference is off by <= 2^-24 |x| ~ 1e-7, i.e. <= 1e-5 whitened at noise 0.01, against distances of a few
     assert np.abs(ref["weights"] - S).max() <= 1e-3 * S.max()
@@ -290,10 +216,10 @@ def test_one_em_step_matches_the_exact_linear_gaussian_step(q0):
         x = x + c.q_true * rng.normal(size=(c.N, c.d))
         truth[t] = x
     z = truth + c.r * rng.normal(size=truth.shape)
-    X, F, ll = pc.bootstrap_filter_history(z, m0, c.p0, q0, c.r, c.M, seed=202)
-    ref = pc.reference(X, F, ll, None, q0 * np.eye(c.d))
+    X, F, ll = sc.bootstrap_filter_history(z, m0, c.p0, q0, c.r, c.M, seed=202)
+    ref = sc.reference(X, F, ll, None, q0 * np.eye(c.d))
     q_pf = float(np.sqrt(np.mean(np.diagonal(ref["residual_second_moment"], axis1=-2, axis2=-1))))
-    q_exact = pc.rts_em_step(z, m0, c.p0, q0, c.r)
+    q_exact = sc.rts_em_step(z, m0, c.p0, q0, c.r)
     print(f"q0 {q0}: particle EM step {q_pf:.5f}, exact RTS EM step {q_exact:.5f}, ratio - 1 = {q_pf / q_exact - 1.0:+.2e}")
     assert abs(q_pf / q_exact - 1.0) <= 0.02
     assert (q_pf < q0) if q0 > c.q_true else (q_pf > q0)

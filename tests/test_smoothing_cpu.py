@@ -1,84 +1,28 @@
 """CPU-side checks of particle smoothing's boundary (``include/mmf.h``: ``MmfPfHistory`` / ``mmf_pf_forward_loop_history``,
-``MmfPfSmoothArgs`` / ``mmf_pf_smooth``): header, binding and exports agree on the two structs; the entry points refuse
-bad arguments on the host, before any HIP call; the Python switches refuse what they cannot do."""
+``MmfPfSmoothArgs`` / ``mmf_pf_smooth``): the entry points refuse bad arguments on the host, before any HIP call; the
+Python switches refuse what they cannot do.  (The structs' layout: ``test_abi_cpu.py``, for every struct of the binding.)"""
 import ctypes
-import os
-import shutil
-import subprocess
 
 import pytest
-import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import _smooth_cases as sc
+
 EINVAL, ETOOLARGE = -1, -2
 
-
-def _lib():
-    from multimodalfilter_amd import _abi, build
-
-    build.build()
-    return _abi.load()
+_POINTERS = ("states_steps", "loglik_steps", "logw_in_steps", "logw_in0", "indices_steps", "mean", "cov", "unique")
 
 
-def test_history_and_smooth_structs_match_the_header_field_by_field(tmp_path):
-    """``offsetof`` / ``sizeof`` as gcc lays ``include/mmf.h`` out against ctypes' (the technique of ``test_abi_cpu.py``),
-    and the library exports the three new symbols the binding declares."""
+def _smooth_args(**over):
     from multimodalfilter_amd import _abi
 
-    lib = _lib()
-    for name in ("mmf_pf_forward_loop_history", "mmf_pf_smooth", "mmf_pf_smooth_lds_bytes"):
-        assert name in _abi.SIGNATURES and hasattr(lib, name), name
-    assert lib.mmf_version() == 42  # purely additive
-    gcc = shutil.which("gcc")
-    if gcc is None:
-        pytest.skip("no gcc")
-    structs = ["MmfPfHistory", "MmfPfSmoothArgs"]
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{os.path.join(ROOT, "include", "mmf.h")}"', "int main(void) {"]
-    for name in structs:
-        cls = getattr(_abi, name)
-        lines.append(f'  printf("{name} size %zu\\n", sizeof({name}));')
-        for field, _t in cls._fields_:
-            lines.append(f'  printf("{name} {field} %zu\\n", offsetof({name}, {field}));')
-    lines += ["  return 0;", "}"]
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    out = subprocess.run([gcc, "-std=c99", "-o", str(exe), str(src)], capture_output=True, text=True)
-    assert out.returncode == 0, out.stderr[-2000:]
-    got = {}
-    for line in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines():
-        name, field, value = line.split()
-        got[(name, field)] = int(value)
-    for name in structs:
-        cls = getattr(_abi, name)
-        assert got[(name, "size")] == ctypes.sizeof(cls), (name, got[(name, "size")], ctypes.sizeof(cls))
-        for field, _t in cls._fields_:
-            assert got[(name, field)] == getattr(cls, field).offset, (name, field)
-        last, last_t = cls._fields_[-1]
-        assert getattr(cls, last).offset + ctypes.sizeof(last_t) + 8 > ctypes.sizeof(cls), name  # no hidden C field at the end
-
-
-def _smooth_args(keep, **over):
-    from multimodalfilter_amd import _abi
-
-    bufs = [(ctypes.c_float * 16)() for _ in range(8)]
-    keep.append(bufs)
-    P = [ctypes.cast(b, ctypes.c_void_p) for b in bufs]
-    a = _abi.MmfPfSmoothArgs()
-    a.T, a.N, a.M, a.d, a.lag = 4, 2, 64, 3, 1
-    a.states_steps, a.loglik_steps, a.logw_in_steps, a.logw_in0 = P[0], P[1], P[2], P[3]
-    a.indices_steps, a.mean, a.cov, a.unique = P[4], P[5], P[6], P[7]
-    for k, v in over.items():
-        setattr(a, k, v)
-    return a
+    return sc.host_args(_abi.MmfPfSmoothArgs, _POINTERS, **{**dict(T=4, N=2, M=64, d=3, lag=1), **over})
 
 
 def test_smooth_refuses_bad_arguments_on_the_host():
     """Nulls, a negative lag, d = 5 -> ``MMF_EINVAL``; an ``M`` beyond the LDS plan -> ``MMF_ETOOLARGE``; no trajectories or
     no steps -> a successful no-op.  All decided before any HIP call: the pointers are host memory, never dereferenced."""
-    lib = _lib()
-    keep = []
-    call = lambda **over: lib.mmf_pf_smooth(ctypes.byref(_smooth_args(keep, **over)), None)
+    lib = sc.lib()
+    call = lambda **over: lib.mmf_pf_smooth(ctypes.byref(_smooth_args(**over)), None)
     assert lib.mmf_pf_smooth(None, None) == EINVAL
     for field in ("states_steps", "loglik_steps", "mean"):
         assert call(**{field: None}) == EINVAL, field
@@ -93,7 +37,7 @@ def test_smooth_refuses_bad_arguments_on_the_host():
 
 
 def test_smooth_lds_bytes_is_monotone_and_covers_what_it_holds():
-    lib = _lib()
+    lib = sc.lib()
     sizes = [lib.mmf_pf_smooth_lds_bytes(M) for M in (1, 2, 37, 64, 300, 1024, 1100, 4096, 20000, 39000, 40000, 65536)]
     assert all(a <= b for a, b in zip(sizes, sizes[1:])), sizes
     assert sizes[0] < sizes[-1]
@@ -107,7 +51,7 @@ def test_history_loop_refuses_null_arguments_on_the_host():
     (``loglik_steps``; ``indices_steps`` with a resampling mode; ``logw_in_steps`` where weights travel)."""
     from multimodalfilter_amd import _abi
 
-    lib = _lib()
+    lib = sc.lib()
     bufs = [(ctypes.c_float * 16)() for _ in range(4)]
     P = [ctypes.cast(b, ctypes.c_void_p) for b in bufs]
     a, h = _abi.MmfPfLoopArgs(), _abi.MmfPfHistory()
