@@ -1252,6 +1252,49 @@ int mmf_ekf_forward_loop_belief(const MmfEkfLoopArgs* args /* host */, float* Si
 int mmf_ekf_persistent_plan(int N, int K);
 size_t mmf_ekf_persistent_sync_words(int N, int K, int d);
 
+/* ---------------------------------------------------------------- RTS smoothing of an extended Kalman filter's recorded run
+ * E[x_t | y_1..T] of a Gaussian belief by the Rauch-Tung-Striebel backward sweep.  Upstream torchfilter's
+ * ExtendedKalmanFilter (the recursion behind every Kalman filter of the reference; external dependency) keeps
+ * no history and has no smoother, and the evaluation that this project restates (crossmodal/eval_helpers.py:139-142 runs
+ * forward_loop over a recorded trajectory, :148-160 scores its estimates) reports the FILTERED means although all T
+ * observations are at hand.  Purely additive to ABI 42: a struct and a symbol of its own.
+ * Steps t = 0 .. T - 1 are the steps of mmf_ekf_forward_loop; (m_t, S_t) the filtered belief step t left; L the constant
+ * process-noise factor; A_t, x^_{t+1} the dynamics Jacobian and prediction at (m_t, u_{t+1}).  For t < T - 1:
+ *   P-_{t+1} = A_t S_t A_t^T + L L^T          G_t = S_t A_t^T (P-_{t+1})^-1
+ *   m^s_t = m_t + G_t (m^s_{t+1} - x^_{t+1})  P^s_t = S_t + G_t (P^s_{t+1} - P-_{t+1}) G_t^T
+ * from (m^s_{T-1}, P^s_{T-1}) = (m_{T-1}, S_{T-1}).  lag >= 0: E[x_t | y_1..min(t + lag, T - 1)] -- the same step from the
+ * FILTERED belief of step e = min(t + lag, T - 1), for s = e - 1 .. t; lag = 0 returns (mu, Sigma) bit for bit, any
+ * lag >= T - 1 the full sweep's bits (both sweeps run one device function).  lag < 0: the full sweep.
+ * Two-slice moments (full sweep only) of the linearised residual r_t = x_{t+1} - x^_{t+1} - A_t (x_t - m_t), with
+ * C_t = G_t P^s_{t+1}:
+ *   resid_mean[t] = e_t = m^s_{t+1} - x^_{t+1} - A_t (m^s_t - m_t)
+ *   resid_m2[t]   = P^s_{t+1} - A_t C_t - (A_t C_t)^T + A_t P^s_t A_t^T + e_t e_t^T          RAW (not centred)
+ * -- the quantities mmf_pf_smooth_pair_moments leaves for a particle filter, under the same names.
+ * Three kernels (csrc/ekf_smooth.hip): gains (one thread per transition: P-, G, the inversion), then the full sweep (one
+ * lane per trajectory, T - 1 dependent steps) or the fixed-lag sweep (one thread per (t, n), at most lag steps).  fp32,
+ * every product-sum an explicit fma in a fixed order: two calls give the same bits and trajectory n's results do not
+ * depend on N.  T == 1 copies (mu, Sigma) to the outputs.
+ * Limits: 1 <= d <= 4, otherwise MMF_EINVAL; T N <= 2^31 - 257, beyond -> MMF_ETOOLARGE.  A null args / mu / Sigma /
+ * q_tril / mu_s / Sigma_s, with T >= 2 a null A / mu_pred / gain / Sigma_pred, T < 0, N < 0, one of resid_mean / resid_m2
+ * without the other, either of them with lag >= 0, or an output whose bytes overlap an input's or another output's
+ * -> MMF_EINVAL.  T == 0 or N == 0 is a successful no-op.  All decided on the host before any HIP call. */
+typedef struct MmfEkfSmoothArgs {
+  int32_t T, N, d;
+  int32_t lag;               /* < 0: the full smoother                                          */
+  const float* mu;           /* (T, N, d)         filtered means                                */
+  const float* Sigma;        /* (T, N, d, d)      filtered covariances                          */
+  const float* A;            /* (T - 1, N, d, d)  Jacobians at (m_t, u_{t+1})                   */
+  const float* mu_pred;      /* (T - 1, N, d)     predictions f(m_t, u_{t+1})                   */
+  const float* q_tril;       /* (d, d) DEVICE, row-major                                        */
+  float* mu_s;               /* (T, N, d)         out: smoothed means                           */
+  float* Sigma_s;            /* (T, N, d, d)      out: smoothed covariances                     */
+  float* gain;               /* (T - 1, N, d, d)  out: G_t (written by the gains kernel, read by the sweeps) */
+  float* Sigma_pred;         /* (T - 1, N, d, d)  workspace: P-_{t+1}                           */
+  float* resid_mean;         /* (T - 1, N, d)     or null: not computed                         */
+  float* resid_m2;           /* (T - 1, N, d, d)  or null: not computed                         */
+} MmfEkfSmoothArgs;          /* host struct holding device pointers                             */
+int mmf_ekf_smooth(const MmfEkfSmoothArgs* args /* host */, void* stream);
+
 /* ---------------------------------------------------------------- LSTM baselines: the recurrence
  * The two-layer nn.LSTM(in_dim, 512, 2) of DoorLSTMFilter / PushLSTMFilter over a whole (T, N, in_dim) sequence, the
  * hidden state carried in and out (crossmodal/door_models/lstm.py:94, push_models/lstm.py:96: `lstm_out,

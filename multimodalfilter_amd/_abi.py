@@ -165,6 +165,13 @@ class MmfEkfLoopArgs(Structure):
                 ("persistent", c_int32), ("n_sync_words", c_int32), ("sync_words", _FP)]
 
 
+class MmfEkfSmoothArgs(Structure):
+    _fields_ = [("T", c_int32), ("N", c_int32), ("d", c_int32), ("lag", c_int32),
+                ("mu", _FP), ("Sigma", _FP), ("A", _FP), ("mu_pred", _FP), ("q_tril", _FP),
+                ("mu_s", _FP), ("Sigma_s", _FP), ("gain", _FP), ("Sigma_pred", _FP),
+                ("resid_mean", _FP), ("resid_m2", _FP)]
+
+
 class MmfLstmArgs(Structure):
     _fields_ = [("T", c_int32), ("N", c_int32), ("in_dim", c_int32), ("persistent", c_int32),
                 ("x", _FP), ("h0", _FP), ("c0", _FP), ("hT", _FP), ("cT", _FP), ("h2", _FP), ("packed", _FP),
@@ -239,6 +246,7 @@ SIGNATURES = {
     "mmf_fuse_virtual_sensors": (c_int, [_FP, _FP, _FP, _FP, _FP, c_int, c_int, c_int, c_int, c_void_p]),
     "mmf_ekf_forward_loop": (c_int, [POINTER(MmfEkfLoopArgs), c_void_p]),
     "mmf_ekf_forward_loop_belief": (c_int, [POINTER(MmfEkfLoopArgs), _FP, c_void_p]),
+    "mmf_ekf_smooth": (c_int, [POINTER(MmfEkfSmoothArgs), c_void_p]),
     "mmf_ekf_persistent_plan": (c_int, [c_int, c_int]),
     "mmf_ekf_persistent_sync_words": (c_size_t, [c_int, c_int, c_int]),
     "mmf_lstm_blob_floats": (c_size_t, [c_int]),
@@ -660,6 +668,34 @@ def ekf_forward_loop(args: MmfEkfLoopArgs, like: torch.Tensor, Sigma_steps: torc
 
 
 LSTM_HIDDEN, LSTM_LAYERS = 512, 2
+
+
+def ekf_smooth(mu, Sigma, A, mu_pred, q_tril, lag, mu_s, Sigma_s, gain, Sigma_pred=None, resid_mean=None, resid_m2=None):
+    """RTS smoothing of a recorded EKF run (``mmf_ekf_smooth``, include/mmf.h): filtered ``mu (T, N, d)`` / ``Sigma (T, N, d,
+    d)``, the transitions' Jacobians ``A (T - 1, N, d, d)`` and predictions ``mu_pred (T - 1, N, d)``, ``q_tril (d, d)`` on the
+    device, ``lag`` (``None``: the full smoother) -> ``mu_s``, ``Sigma_s``, ``gain (T - 1, N, d, d)`` and, both or neither and
+    with ``lag = None`` only, ``resid_mean (T - 1, N, d)`` / ``resid_m2 (T - 1, N, d, d)``.  ``Sigma_pred``: the
+    ``(T - 1, N, d, d)`` workspace, allocated when ``None``.  ``T == 0`` or ``N == 0``: nothing to do, no call."""
+    T, N, d = mu.shape
+    Tm = max(T - 1, 0)
+    assert Sigma.shape == (T, N, d, d) and q_tril.shape == (d, d)
+    assert mu_s.shape == (T, N, d) and Sigma_s.shape == (T, N, d, d) and gain.shape == (Tm, N, d, d)
+    assert A.shape == (Tm, N, d, d) and mu_pred.shape == (Tm, N, d)
+    assert resid_mean is None or resid_mean.shape == (Tm, N, d)
+    assert resid_m2 is None or resid_m2.shape == (Tm, N, d, d)
+    if T == 0 or N == 0:
+        return
+    if Sigma_pred is None:
+        Sigma_pred = torch.empty((Tm, N, d, d), dtype=torch.float32, device=mu.device)
+    assert Sigma_pred.shape == (Tm, N, d, d)
+    some = lambda t: vp(t) if T >= 2 else None  # (an empty tensor has no address to speak of)
+    a = MmfEkfSmoothArgs()
+    a.T, a.N, a.d, a.lag = T, N, d, -1 if lag is None else min(int(lag), 0x7fffffff)
+    a.mu, a.Sigma, a.A, a.mu_pred, a.q_tril = vp(mu), vp(Sigma), some(A), some(mu_pred), vp(q_tril)
+    a.mu_s, a.Sigma_s, a.gain, a.Sigma_pred = vp(mu_s), vp(Sigma_s), some(gain), some(Sigma_pred)
+    a.resid_mean, a.resid_m2 = (None if resid_mean is None else some(resid_mean)), (None if resid_m2 is None else some(resid_m2))
+    with _on(mu):
+        _check(load().mmf_ekf_smooth(ctypes.byref(a), stream_of(mu)), "mmf_ekf_smooth")
 
 
 def lstm_blob_floats(in_dim: int) -> int:

@@ -962,6 +962,11 @@ def run_measure(net: PackedParticleNet, states: torch.Tensor, traj_bias: torch.T
     return loglik
 
 
+# rows of one mmf_dynamics_jacobian call, the check of csrc/particle_net.hip (one more is MMF_ETOOLARGE:
+# tests/test_rts_cases_cpu.py holds the two together); callers chunk
+JACOBIAN_MAX_ROWS = 0x7FFFFFFF // 32
+
+
 def run_jacobian(net: PackedParticleNet, states: torch.Tensor, traj_bias: torch.Tensor):
     """``(N, d)`` -> ``(x' (N, d), J (N, d, d))`` by forward-mode tangents (K5)."""
     require_device(states, "run_jacobian")

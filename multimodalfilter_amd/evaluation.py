@@ -13,9 +13,17 @@ from .task_models import DOOR, PUSH
 START_TRUNCATION = 30
 
 
+class _DefaultMethod(str):
+    """The default of ``run_filter(smooth_method=)``: ``"ancestry"``, told apart by identity from an ``"ancestry"`` the
+    caller passed, since a filter may name another default (``default_smooth_method``)."""
+
+
+_DEFAULT_METHOD = _DefaultMethod("ancestry")
+
+
 def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale: float = 0.1,
                measurement_initialize: bool = False, return_belief: bool = False, smooth_lag=False,
-               smooth_method: str = "ancestry", smooth_draws: int = _DEFAULT_DRAWS, smooth_transition_moments: bool = False):
+               smooth_method: str = _DEFAULT_METHOD, smooth_draws: int = _DEFAULT_DRAWS, smooth_transition_moments: bool = False):
     """Initialise the belief at ``states[0]`` with covariance ``0.1 I`` (or from the first
     observation, ``eval_helpers.py:116-131``) and filter ``[1:]`` (``:139-142``).
     ``return_belief``: run with ``record_belief`` set and return ``(estimates, filter_model.last_belief)`` -- the per-step
@@ -24,14 +32,20 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
     particle filter with ``record_history`` set and returns ``filter_model.smooth(smooth_lag)`` -- the whole recorded
     trajectory is at hand, so ``E[x_t | y_1..t+lag]`` is the better estimate -- and, with ``return_belief``, the smoothed
     record ``filter_model.last_smoothed`` (``covariance``, ``unique``, ``lag``) in place of the filter's.
-    ``smooth_method``: passed to ``smooth(method=)``; ``"marginal"`` smooths also where ``smooth_lag`` is left at ``False``
+    ``smooth_method``: passed to ``smooth(method=)``; left at its default it is the filter's ``default_smooth_method`` --
+    ``"rts"`` for the extended Kalman filters (``VirtualSensorExtendedKalmanFilter.smooth``: ``covariance``, ``gain``,
+    ``lag``), ``"ancestry"`` for every filter that names none, the particle filter included; ``"marginal"`` smooths also where ``smooth_lag`` is left at ``False``
     (it is the full smoother: ``smooth_lag`` must be ``False`` or ``None``) and leaves ``covariance``, ``ess``, ``weights``;
     ``"simulation"`` likewise, with ``smooth_draws`` joint paths per trajectory (``smooth(num_draws=)``, default 64; passing it with
     another method is the ``ValueError`` it is there), and leaves ``covariance``, ``trajectories``, ``indices``, ``num_draws``.
-    ``smooth_transition_moments``: smooths with the filter's ``record_transition_moments`` set (and puts the switch back) -- with ``smooth_method="marginal"`` alone, refused
+    ``smooth_transition_moments``: smooths with the filter's ``record_transition_moments`` set (and puts the switch back) -- with ``smooth_method="marginal"`` or ``"rts"`` alone, refused
     before the run otherwise; the record gains ``residual_mean`` and ``residual_second_moment`` (``process_noise_m_step``)."""
-    if smooth_transition_moments and smooth_method != "marginal":  # (before the run, not after it)
-        raise ValueError(f"run_filter: smooth_transition_moments are the two-slice moments smooth_method='marginal' computes; "
+    named = smooth_method is not _DEFAULT_METHOD
+    if not named:
+        smooth_method = getattr(filter_model, "default_smooth_method", "ancestry")
+    if smooth_transition_moments and smooth_method not in ("marginal", "rts"):  # (before the run, not after it)
+        raise ValueError(f"run_filter: smooth_transition_moments are the two-slice moments that smooth_method='marginal' (particle "
+                         f"filters) and 'rts' (extended Kalman filters) compute; "
                          f"smooth_method={smooth_method!r} has none")
     if smooth_draws is not _DEFAULT_DRAWS and smooth_method != "simulation":  # (before the run, not after it)
         raise ValueError(f"run_filter: smooth_draws is the number of paths smooth_method='simulation' draws; "
@@ -43,7 +57,7 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
     if return_belief:
         assert was is not None, f"{type(filter_model).__name__} keeps no belief to record"
         filter_model.record_belief = True
-    if smooth_method != "ancestry" and smooth_lag is False:
+    if named and smooth_method != "ancestry" and smooth_lag is False:
         smooth_lag = None
     smoothing = smooth_lag is not False  # (0 is a lag)
     if smoothing:
@@ -81,7 +95,8 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
 
 def process_noise_m_step(record, *, diagonal: bool = False, start: int = 0) -> torch.Tensor:
     """The M-step of EM for the process noise from a smoothed record with transition moments
-    (``smooth(method="marginal")`` with ``record_transition_moments`` set): ``Q = mean over steps >= start and all trajectories of
+    (``smooth(method="marginal")`` of a particle filter or ``smooth()`` of an extended Kalman filter, ``method="rts"``, with
+    ``record_transition_moments`` set): ``Q = mean over steps >= start and all trajectories of
     residual_second_moment`` -- the raw second moment, since the model's noise has mean zero -- and the ``(d, d)``
     ``scale_tril = cholesky(Q)``; ``diagonal``: ``diag(sqrt(diag Q))``, for a model that holds a diagonal only.  Plain torch,
     on the record's device (CPU tensors included).  A non-finite entry, or a ``Q`` that is not positive definite, is a
@@ -89,7 +104,8 @@ def process_noise_m_step(record, *, diagonal: bool = False, start: int = 0) -> t
     m2 = getattr(record, "residual_second_moment", None)
     if m2 is None:
         raise ValueError("process_noise_m_step: the record has no residual_second_moment; smooth with "
-                         "method='marginal' and the filter's record_transition_moments set")
+                         "the filter's record_transition_moments set (method='marginal' for a particle filter, the full "
+                         "'rts' smoother for an extended Kalman filter)")
     if m2.dim() != 4 or m2.shape[-1] != m2.shape[-2]:
         raise ValueError(f"process_noise_m_step: residual_second_moment must be (T - 1, N, d, d), got {tuple(m2.shape)}")
     start = int(start)
@@ -123,10 +139,16 @@ def process_noise_m_step(record, *, diagonal: bool = False, start: int = 0) -> t
     return L.to(m2.dtype)
 
 
+def _moments_method(filter_model) -> str:
+    """The smoothing method whose record carries the two-slice transition moments: the Kalman smoother for a filter whose
+    default it is, the particle filter's marginal smoother otherwise."""
+    return "rts" if getattr(filter_model, "default_smooth_method", None) == "rts" else "marginal"
+
+
 def fit_process_noise(filter_model, traj: Dict[str, torch.Tensor], *, iterations: int = 5, start: int = 0, **run_filter_kwargs):
     """EM for the process noise of ``filter_model.dynamics_model`` on the trajectories ``traj``: every iteration runs
     ``run_filter(smooth_method="marginal", smooth_transition_moments=True, return_belief=True)`` (the E-step: the two-slice
-    moments under the current noise), takes ``process_noise_m_step`` over the steps ``>= start`` and hands the factor to
+    moments under the current noise; ``smooth_method="rts"`` for an extended Kalman filter), takes ``process_noise_m_step`` over the steps ``>= start`` and hands the factor to
     ``dynamics_model.set_scale_tril`` -- the diagonal form where the model's ``diagonal_noise`` is true.  Returns the list
     of ``(d, d)`` factors, the initial one first: ``iterations + 1`` entries.  ``run_filter_kwargs`` go to ``run_filter``
     (``initial_cov_scale``, ``measurement_initialize``); the smoothing switches are this function's own.  The filter's
@@ -145,7 +167,7 @@ def fit_process_noise(filter_model, traj: Dict[str, torch.Tensor], *, iterations
     diagonal = bool(getattr(dyn, "diagonal_noise", False))
     out = [dyn.scale_tril().detach().clone()]
     for _ in range(iterations):
-        _est, record = run_filter(filter_model, traj, smooth_method="marginal", smooth_transition_moments=True,
+        _est, record = run_filter(filter_model, traj, smooth_method=_moments_method(filter_model), smooth_transition_moments=True,
                                   return_belief=True, **run_filter_kwargs)
         L = process_noise_m_step(record, diagonal=diagonal, start=start)
         dyn.set_scale_tril(L)

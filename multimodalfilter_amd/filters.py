@@ -821,7 +821,12 @@ class VirtualSensorExtendedKalmanFilter(base.Filter):
     ``C = I`` (T2).  predict: ``S- = A S A^T + L L^T`` with ``A`` the dynamics Jacobian;
     correct: ``K = S-(S- + R)^-1``, ``mu = mu- + K(z - mu-)``, ``S = (I - K) S-``.
     ``record_belief = True``: ``last_belief.covariance`` is the posterior covariance as every step leaves it --
-    ``(N, d, d)`` after ``forward``, ``(T, N, d, d)`` after ``forward_loop`` (written by the native loop itself)."""
+    ``(N, d, d)`` after ``forward``, ``(T, N, d, d)`` after ``forward_loop`` (written by the native loop itself).
+    ``record_history = True`` (evaluation mode): ``forward_loop`` leaves ``last_history`` -- ``means (T, N, d)``,
+    ``covariances (T, N, d, d)`` and ``controls``, a reference to the controls it was given -- which ``smooth()`` turns into
+    the Rauch-Tung-Striebel smoothed belief; no other output of the loop changes by a bit."""
+
+    default_smooth_method = "rts"  # what evaluation.run_filter smooths this filter with when no method is named
 
     def __init__(self, *, dynamics_model: base.DynamicsModel,
                  virtual_sensor_model: base.VirtualSensorModel):
@@ -835,6 +840,10 @@ class VirtualSensorExtendedKalmanFilter(base.Filter):
         self._initialized = False
         self.record_belief = False
         self.last_belief = None
+        self.record_history = False             # forward_loop keeps the filtered beliefs -> last_history
+        self.record_transition_moments = False  # smooth() also leaves the two-slice residual moments
+        self.last_history = None
+        self.last_smoothed = None
 
     def _record_step_belief(self):
         self.last_belief = base.belief_record(covariance=self._belief_covariance.detach()) if self.record_belief else None
@@ -944,15 +953,21 @@ class VirtualSensorExtendedKalmanFilter(base.Filter):
         mu = self._belief_mean.reshape(1, N, d).contiguous().clone()
         Sigma = self._belief_covariance.reshape(1, N, d, d).contiguous().clone()
         q = dyn.scale_tril().to(torch.float32).reshape(1, d, d).contiguous()
-        steps = torch.empty((T, N, d, d), dtype=torch.float32, device=mu.device) if self.record_belief else None
+        keep = self.record_belief or self.record_history  # (the same Sigma_steps path for either)
+        steps = torch.empty((T, N, d, d), dtype=torch.float32, device=mu.device) if keep else None
         est, _ = engine.run_ekf_loop([dyn._net], [ctrl_all["bias"]], q, z, r, mu, Sigma, Sigma_steps=steps)
         self._belief_mean, self._belief_covariance = mu[0], Sigma[0]
         self.last_belief = base.belief_record(covariance=steps) if self.record_belief else None
+        if self.record_history:
+            self.last_history = base.history_record(means=est, covariances=steps)
         return est
 
     @engine.checked_loop
     def forward_loop(self, *, observations, controls):
+        self.last_history = None
         if use_autograd(self):
+            if self.record_history:
+                raise RuntimeError("record_history: the training (autograd) paths keep no history; call .eval() first")
             return base.Filter.forward_loop(self, observations=observations, controls=controls)
         T, N = tree_leading_shape(controls)[:2]
         flat = lambda t: t.reshape((T * N,) + tuple(t.shape[2:]))
@@ -962,17 +977,97 @@ class VirtualSensorExtendedKalmanFilter(base.Filter):
                 ctrl_all = self.dynamics_model.encode_controls(tree_map(controls, flat))
             native = self._native_loop(observations, ctrl_all, T, N, flat)
             if native is not None:
+                if self.last_history is not None:
+                    self.last_history.controls = controls  # (a reference, not a copy) what smooth() predicts with
                 return native
             sensors = [self.virtual_sensor_model(observations=tree_index(observations, t)) for t in range(T)]
-        out, beliefs = [], []
+        out, beliefs, covs = [], [], []
         for t in range(T):
             sl = slice(t * N, (t + 1) * N)
             out.append(self._step(tree_index(observations, t), tree_index(controls, t), sensors[t],
                                   None if ctrl_all is None else {k: v[sl] for k, v in ctrl_all.items()}))
             beliefs.append(self.last_belief)
+            covs.append(self._belief_covariance)
         if self.record_belief:
             self.last_belief = base.stack_belief_records(beliefs)
-        return torch.stack(out, dim=0)
+        est = torch.stack(out, dim=0)
+        if self.record_history and T > 0:
+            self.last_history = base.history_record(means=est, covariances=torch.stack(covs, dim=0), controls=controls)
+        return est
+
+    def smooth(self, lag: Optional[int] = None, *, method: str = "rts") -> torch.Tensor:
+        """Rauch-Tung-Striebel smoothing of the last ``forward_loop`` run with ``record_history`` set
+        (``mmf_ekf_smooth``, ``include/mmf.h``): ``(T, N, d)`` means of ``E[x_t | y_1..s(t)]``, ``s(t) = min(t + lag, T - 1)``
+        -- the meaning of ``ParticleFilter.smooth(lag)``.  ``lag = None``: the full smoother; ``lag = 0``: the filter's own
+        belief.  The forward recursion is not touched: the Jacobians ``A_t`` and predictions ``f(m_t, u_{t+1})`` of the
+        ``T - 1`` transitions are evaluated again here, in one batched call over the ``(T - 1) N`` recorded means (means
+        ``[0 : T - 1]`` with controls ``[1 : T]``).  Leaves ``last_smoothed``: ``covariance (T, N, d, d)``, ``gain
+        (T - 1, N, d, d)``, ``lag``, ``method = "rts"`` and, with ``self.record_transition_moments`` set (``lag = None``
+        only), ``residual_mean (T - 1, N, d)`` / ``residual_second_moment (T - 1, N, d, d)``: mean and RAW second moment of
+        the linearised transition residual under the two-slice smoothing distribution, what
+        ``evaluation.process_noise_m_step`` refits the process noise from.  The process noise must be one ``scale_tril``
+        for the whole batch."""
+        if method != "rts":
+            raise ValueError(f"smooth: the Kalman filters have one smoother, method='rts'; got {method!r} "
+                             "('ancestry', 'marginal' and 'simulation' are the particle filter's)")
+        if lag is not None and (isinstance(lag, bool) or not isinstance(lag, int) or lag < 0):
+            raise ValueError(f"smooth: lag must be an int >= 0 (None: the full smoother), got {lag!r}")
+        moments = bool(self.record_transition_moments)
+        if moments and lag is not None:
+            raise ValueError("smooth: record_transition_moments is set, and the two-slice moments are the full smoother's; "
+                             f"lag={lag!r} has none (unset the switch, or smooth with lag=None)")
+        h = self.last_history
+        if h is None:
+            raise ValueError("smooth() needs a history: set record_history and run forward_loop (evaluation mode) first")
+        T, N, d = h.means.shape
+        dev = h.means.device
+        E = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        with torch.no_grad():
+            mu_pred, A, tril = self._smoothing_transition(h)
+            mean, cov, gain = E(T, N, d), E(T, N, d, d), E(max(T - 1, 0), N, d, d)
+            extra = {}
+            if moments:
+                extra["residual_mean"], extra["residual_second_moment"] = E(max(T - 1, 0), N, d), E(max(T - 1, 0), N, d, d)
+            _abi.ekf_smooth(h.means.to(torch.float32).contiguous(), h.covariances.to(torch.float32).contiguous(), A, mu_pred,
+                            tril, lag, mean, cov, gain, None, extra.get("residual_mean"), extra.get("residual_second_moment"))
+        self.last_smoothed = base.belief_record(covariance=cov, gain=gain, lag=lag, method="rts", **extra)
+        return mean
+
+    def _smoothing_transition(self, h):
+        """``(x^ (T - 1, N, d), A (T - 1, N, d, d), L (d, d))`` of the ``T - 1`` recorded transitions, float32 on the
+        history's device: the dynamics prediction and Jacobian at ``(means[t], controls[t + 1])`` in one batched call over
+        the ``(T - 1) N`` rows (chunks of ``engine.JACOBIAN_MAX_ROWS`` where the Jacobian entry limits its rows) -- K5
+        (``predict_with_jacobian``) for the built-in models, ``dyn(...)`` and ``dyn.jacobian(...)`` for a user model.
+        A process noise that differs over the batch is refused."""
+        T, N, d = h.means.shape
+        dev = h.means.device
+        dyn = self.dynamics_model
+        R = max(T - 1, 0) * N
+        if R == 0:  # (no transition: the noise is never read)
+            tril = dyn.scale_tril() if hasattr(dyn, "scale_tril") else torch.eye(d)
+            return (torch.empty((max(T - 1, 0), N, d), dtype=torch.float32, device=dev),
+                    torch.empty((max(T - 1, 0), N, d, d), dtype=torch.float32, device=dev),
+                    tril.detach().to(device=dev, dtype=torch.float32).contiguous())
+        past = h.means[:T - 1].reshape(R, d).to(torch.float32).contiguous()
+        rows = tree_map(h.controls, lambda c: c[1:T].reshape((R,) + tuple(c.shape[2:])))
+        preds, jacs, tril = [], [], None
+        for r0 in range(0, R, engine.JACOBIAN_MAX_ROWS):
+            sl = slice(r0, min(r0 + engine.JACOBIAN_MAX_ROWS, R))
+            ctrl = tree_map(rows, lambda c: c[sl])
+            if hasattr(dyn, "predict_with_jacobian"):
+                x, J, tril = dyn.predict_with_jacobian(past[sl], dyn.encode_controls(ctrl))
+            else:
+                x, trils = dyn(initial_states=past[sl], controls=ctrl)
+                J = dyn.jacobian(initial_states=past[sl], controls=ctrl)
+                if (tril is not None and not bool((trils == tril).all())) or not bool((trils == trils[:1]).all()):
+                    raise ValueError("smooth(method='rts') needs one process-noise scale_tril for all trajectories and steps; "
+                                     "this dynamics model returns noise that differs over the batch")
+                tril = trils[0]
+            preds.append(x.detach())
+            jacs.append(J.detach())
+        x, J = (preds[0], jacs[0]) if len(preds) == 1 else (torch.cat(preds), torch.cat(jacs))
+        return (x.to(torch.float32).reshape(T - 1, N, d).contiguous(), J.to(torch.float32).reshape(T - 1, N, d, d).contiguous(),
+                tril.detach().to(device=dev, dtype=torch.float32).contiguous())
 
 
 # ------------------------------------------------------------------------------ unscented filter
@@ -1031,6 +1126,22 @@ class VirtualSensorUnscentedKalmanFilter(VirtualSensorExtendedKalmanFilter):
     def __init__(self, *, dynamics_model, virtual_sensor_model, sigma_point_strategy=None):
         super().__init__(dynamics_model=dynamics_model, virtual_sensor_model=virtual_sensor_model)
         self.sigma_point_strategy = sigma_point_strategy if sigma_point_strategy is not None else JulierSigmaPointStrategy()
+
+    _NO_SMOOTHER = ("VirtualSensorUnscentedKalmanFilter has no smoother: the RTS sweep of an unscented filter needs the "
+                    "cross-covariance of the sigma points before and after the dynamics, which its forward pass does not "
+                    "keep (the extended filter's smoother linearises through the Jacobian instead)")
+
+    @property
+    def record_history(self) -> bool:
+        return False
+
+    @record_history.setter
+    def record_history(self, value: bool) -> None:
+        if value:
+            raise NotImplementedError(self._NO_SMOOTHER)
+
+    def smooth(self, lag: Optional[int] = None, *, method: str = "rts") -> torch.Tensor:
+        raise NotImplementedError(self._NO_SMOOTHER)
 
     def _unscented_predict(self, controls, ctrl_ctx=None, not_pd=None):
         """``not_pd``: a loop-wide device flag (checked by the caller after the loop) -- ``None`` checks
