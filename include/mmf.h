@@ -1252,6 +1252,43 @@ int mmf_ekf_forward_loop_belief(const MmfEkfLoopArgs* args /* host */, float* Si
 int mmf_ekf_persistent_plan(int N, int K);
 size_t mmf_ekf_persistent_sync_words(int N, int K, int d);
 
+/* ---------------------------------------------------------------- innovation statistics and NIS gating of the Kalman step
+ * Replaces the update of upstream torchfilter's ExtendedKalmanFilter (_update_step; the recursion behind every Kalman filter
+ * of the reference, external dependency), which forms the innovation and its covariance, uses them for the
+ * gain and discards them: neither it nor the filters built on it (crossmodal_kf.py:88-151, unimodal_kf.py:162-250) can report
+ * a likelihood, a consistency statistic, or refuse an outlying measurement.  Purely additive to ABI 42: two symbols and a
+ * struct of their own; MmfEkfLoopArgs keeps its size.
+ * Per sub-filter k and trajectory n of one step (observation matrix = I), with S- = A Sigma A^T + L L^T and R = T T^T:
+ *   nu = z - mu-          S = S- + R          nis = nu^T S^-1 nu          loglik = -1/2 (nis + log det S + d log 2 pi)
+ *   accepted = nis_gate < 0 (no gating)  or  nis <= nis_gate;  a NaN nis is rejected.
+ * An accepted measurement leaves the bits of mmf_ekf_step_gated; a rejected one leaves mu = mu-, Sigma = S-, the values the
+ * step formed on the way, bit for bit.  Fusion and write-back then run unchanged on what every sub-filter holds: a rejected
+ * sub-filter enters the fusion with its predicted belief.  nis and loglik are written for rejected measurements too.
+ * nis is an fma chain over S^-1 nu with the inverse the gain uses; log det S comes from a Cholesky factorisation of S in
+ * registers with the deterministic log of mmf_detmath.h (an S that is not positive definite -> loglik NaN).
+ *   nis, loglik (K, N) float, accepted (K, N) int32 (1 / 0): any of them may be null.
+ * mmf_ekf_step_innov: the other operands as mmf_ekf_step_gated's (feedback_gate may be null), and its argument checks;
+ *   also MMF_EINVAL: d outside 1..4, K outside 1..4, a NaN nis_gate, an output (mu, Sigma, mu_f, Sigma_f, nis, loglik,
+ *   accepted) whose bytes overlap an input's or another output's.  N == 0 is a successful no-op.  All decided on the host
+ *   before any HIP call.
+ * mmf_ekf_forward_loop_innov: mmf_ekf_forward_loop[_belief] with that step, as the LOOP OF LAUNCHES: args->persistent is
+ *   ignored -- the persistent launch (csrc/ekf_persistent.inc) keeps no innovation and is not taken, as the particle filter's
+ *   is not taken for a recorded history.  innov is required, Sigma_steps (T, N, d, d) may be null.  Argument checks as
+ *   mmf_ekf_forward_loop's, d in 1..4, and no record on top of an operand of the loop; T == 0 or N == 0 is a successful no-op. */
+int mmf_ekf_step_innov(const float* A, const float* mu_pred, const float* q_tril, const float* z,
+                       const float* r_tril, const float* fuse_w, float* mu, float* Sigma,
+                       float* mu_f, float* Sigma_f, int N, int d, int K, int fusion, int feedback,
+                       const int32_t* feedback_gate, float nis_gate, float* nis, float* loglik, int32_t* accepted,
+                       void* stream);
+typedef struct MmfEkfInnovArgs {
+  float nis_gate;            /* < 0: no gating                                                  */
+  float* nis_steps;          /* (T, K, N) or null                                               */
+  float* loglik_steps;       /* (T, K, N) or null                                               */
+  int32_t* accepted_steps;   /* (T, K, N) or null                                               */
+} MmfEkfInnovArgs;           /* host struct holding device pointers                             */
+int mmf_ekf_forward_loop_innov(const MmfEkfLoopArgs* args /* host */, const MmfEkfInnovArgs* innov /* host */,
+                               float* Sigma_steps /* or null */, void* stream);
+
 /* ---------------------------------------------------------------- RTS smoothing of an extended Kalman filter's recorded run
  * E[x_t | y_1..T] of a Gaussian belief by the Rauch-Tung-Striebel backward sweep.  Upstream torchfilter's
  * ExtendedKalmanFilter (the recursion behind every Kalman filter of the reference; external dependency) keeps

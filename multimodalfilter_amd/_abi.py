@@ -165,6 +165,12 @@ class MmfEkfLoopArgs(Structure):
                 ("persistent", c_int32), ("n_sync_words", c_int32), ("sync_words", _FP)]
 
 
+class MmfEkfInnovArgs(Structure):
+    """The innovation record of ``mmf_ekf_forward_loop_innov`` (include/mmf.h): the NIS gate (< 0: none) and three
+    ``(T, K, N)`` device arrays, any of them null."""
+    _fields_ = [("nis_gate", c_float), ("nis_steps", _FP), ("loglik_steps", _FP), ("accepted_steps", _FP)]
+
+
 class MmfEkfSmoothArgs(Structure):
     _fields_ = [("T", c_int32), ("N", c_int32), ("d", c_int32), ("lag", c_int32),
                 ("mu", _FP), ("Sigma", _FP), ("A", _FP), ("mu_pred", _FP), ("q_tril", _FP),
@@ -205,6 +211,7 @@ SIGNATURES = {
     "mmf_dynamics_jacobian": (c_int, [_FP, c_int, c_int, _FP, _FP, _FP, _FP, _FP, c_int, c_int, c_void_p]),
     "mmf_ekf_step": (c_int, [_FP] * 10 + [c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "mmf_ekf_step_gated": (c_int, [_FP] * 10 + [c_int, c_int, c_int, c_int, c_int, _FP, c_void_p]),
+    "mmf_ekf_step_innov": (c_int, [_FP] * 10 + [c_int, c_int, c_int, c_int, c_int, _FP, c_float, _FP, _FP, _FP, c_void_p]),
     "mmf_ekf_step_backward": (c_int, [_FP] * 13 + [c_int, c_int, c_int, c_void_p]),
     "mmf_ukf_sigma_points": (c_int, [_FP, _FP, ctypes.c_float, _FP, _FP, c_int, c_int, c_void_p]),
     "mmf_ukf_moments": (c_int, [_FP, ctypes.c_float, ctypes.c_float, ctypes.c_float, _FP, _FP, _FP, c_int, c_int, c_void_p]),
@@ -246,6 +253,7 @@ SIGNATURES = {
     "mmf_fuse_virtual_sensors": (c_int, [_FP, _FP, _FP, _FP, _FP, c_int, c_int, c_int, c_int, c_void_p]),
     "mmf_ekf_forward_loop": (c_int, [POINTER(MmfEkfLoopArgs), c_void_p]),
     "mmf_ekf_forward_loop_belief": (c_int, [POINTER(MmfEkfLoopArgs), _FP, c_void_p]),
+    "mmf_ekf_forward_loop_innov": (c_int, [POINTER(MmfEkfLoopArgs), POINTER(MmfEkfInnovArgs), _FP, c_void_p]),
     "mmf_ekf_smooth": (c_int, [POINTER(MmfEkfSmoothArgs), c_void_p]),
     "mmf_ekf_persistent_plan": (c_int, [c_int, c_int]),
     "mmf_ekf_persistent_sync_words": (c_size_t, [c_int, c_int, c_int]),
@@ -510,6 +518,22 @@ def ekf_step(A, mu_pred, q_tril, z, r_tril, fuse_w, mu, Sigma, mu_f, Sigma_f, fu
                                    N, d, K, fusion, feedback, stream_of(mu_pred)), "mmf_ekf_step")
 
 
+def ekf_step_innov(A, mu_pred, q_tril, z, r_tril, fuse_w, mu, Sigma, mu_f, Sigma_f, fusion: int, feedback: int,
+                   feedback_gate=None, *, nis_gate=None, nis=None, loglik=None, accepted=None):
+    """``ekf_step`` that also leaves the innovation statistics and applies the NIS gate (``mmf_ekf_step_innov``,
+    include/mmf.h): ``nis_gate`` a threshold > 0 or ``None`` (no gating); ``nis`` / ``loglik`` float32 and ``accepted`` int32,
+    each ``(K, N)`` or ``None``."""
+    K, N, d = mu_pred.shape
+    for t in (nis, loglik, accepted):
+        assert t is None or t.shape == (K, N)
+    with _on(mu_pred):
+        _check(load().mmf_ekf_step_innov(ptr(A), ptr(mu_pred), ptr(q_tril), ptr(z), ptr(r_tril), ptr(fuse_w), ptr(mu),
+                                         ptr(Sigma), ptr(mu_f), ptr(Sigma_f), N, d, K, fusion, feedback,
+                                         ptr(feedback_gate, dtype=torch.int32), -1.0 if nis_gate is None else float(nis_gate),
+                                         ptr(nis), ptr(loglik), ptr(accepted, dtype=torch.int32), stream_of(mu_pred)),
+               "mmf_ekf_step_innov")
+
+
 def image_convs_train_forward(packed, images, a1, h, a2, a3, a4, range_flag=None, precision: int = PREC_F32):
     with _on(images):
         _check(load().mmf_image_convs_train_forward(ptr(packed), ptr(images), ptr(a1), ptr(h), ptr(a2), ptr(a3), ptr(a4),
@@ -656,11 +680,15 @@ def fuse_virtual_sensors(z, tril, w, z_out, tril_out, mode: int):
                                                stream_of(z)), "mmf_fuse_virtual_sensors")
 
 
-def ekf_forward_loop(args: MmfEkfLoopArgs, like: torch.Tensor, Sigma_steps: torch.Tensor = None):
+def ekf_forward_loop(args: MmfEkfLoopArgs, like: torch.Tensor, Sigma_steps: torch.Tensor = None, innov: MmfEkfInnovArgs = None):
     """Enqueue T fused-EKF steps (see include/mmf.h); ``Sigma_steps (T, N, d, d)``: every step's posterior covariance is
-    kept there (``mmf_ekf_forward_loop_belief``)."""
+    kept there (``mmf_ekf_forward_loop_belief``); ``innov``: the loop of launches with the innovation step, which fills that
+    record (``mmf_ekf_forward_loop_innov``; ``Sigma_steps`` may go with it)."""
     with _on(like):
-        if Sigma_steps is None:
+        if innov is not None:
+            _check(load().mmf_ekf_forward_loop_innov(ctypes.byref(args), ctypes.byref(innov), ptr(Sigma_steps), stream_of(like)),
+                   "mmf_ekf_forward_loop_innov")
+        elif Sigma_steps is None:
             _check(load().mmf_ekf_forward_loop(ctypes.byref(args), stream_of(like)), "mmf_ekf_forward_loop")
         else:
             _check(load().mmf_ekf_forward_loop_belief(ctypes.byref(args), ptr(Sigma_steps), stream_of(like)),

@@ -203,8 +203,12 @@ class CrossmodalKalmanFilterWeightModel(nn.Module, abc.ABC):
         ...
 
 
-class _FusedKalmanFilters(base.Filter, _EnabledModels):
-    """Shared machinery: K virtual-sensor EKFs stepped and fused by one K3 launch."""
+class _FusedKalmanFilters(base.Filter, _EnabledModels, filters.InnovationSwitches):
+    """Shared machinery: K virtual-sensor EKFs stepped and fused by one K3 launch.
+    ``record_innovations`` / ``innovation_gate`` (evaluation mode): ``filters.InnovationSwitches`` -- ``last_innovations``
+    with ``nis``, ``log_likelihood`` and ``accepted`` per ENABLED sub-filter, ``(K, N)`` after ``forward`` and ``(T, K, N)``
+    after ``forward_loop``.  The one gate applies to every sub-filter; a rejected sub-filter enters the fusion with its
+    predicted belief.  The sub-filters' own switches are not read."""
 
     def __init__(self, *, filter_models: List[filters.VirtualSensorExtendedKalmanFilter],
                  state_dim: int):
@@ -216,6 +220,7 @@ class _FusedKalmanFilters(base.Filter, _EnabledModels):
         # the only enabled sub-filter's where nothing is fused: the matrix that goes with the returned mean
         self.record_belief = False
         self.last_belief = None
+        self._init_innovation_switches()
 
     def _num_models(self):
         return len(self.filter_models)
@@ -270,11 +275,19 @@ class _FusedKalmanFilters(base.Filter, _EnabledModels):
         if fusion:
             mu_f = torch.empty((N, d), dtype=torch.float32, device=dev)
             Sigma_f = torch.empty((N, d, d), dtype=torch.float32, device=dev)
-        _abi.ekf_step(torch.stack(A).contiguous(), torch.stack(mu_pred).contiguous(),
-                      torch.stack(L).contiguous(), torch.stack(z).contiguous(),
-                      torch.stack(r).contiguous(),
-                      None if fuse_w is None else fuse_w.to(torch.float32).contiguous(),
-                      mu, Sigma, mu_f, Sigma_f, fusion=fusion, feedback=feedback)
+        operands = (torch.stack(A).contiguous(), torch.stack(mu_pred).contiguous(),
+                    torch.stack(L).contiguous(), torch.stack(z).contiguous(),
+                    torch.stack(r).contiguous(),
+                    None if fuse_w is None else fuse_w.to(torch.float32).contiguous(),
+                    mu, Sigma, mu_f, Sigma_f)
+        if self._innovations_on():
+            buf = self._innovation_buffers((K, N), dev)
+            _abi.ekf_step_innov(*operands, fusion=fusion, feedback=feedback, nis_gate=self._innovation_gate,
+                                nis=buf[0], loglik=buf[1], accepted=buf[2])
+            self.last_innovations = self._innovation_record(buf, fused=True)
+        else:
+            self.last_innovations = None
+            _abi.ekf_step(*operands, fusion=fusion, feedback=feedback)
         for k, f in enumerate(live):
             f._belief_mean, f._belief_covariance = mu[k], Sigma[k]
         self.last_belief = base.belief_record(covariance=Sigma_f if fusion else Sigma[0]) if self.record_belief else None
@@ -290,6 +303,7 @@ class _FusedKalmanFilters(base.Filter, _EnabledModels):
     def forward(self, *, observations, controls):
         N, _ = controls.shape
         if use_autograd(self):
+            self._refuse_innovations_in_training()
             self._autograd_covariance = None
             out = self._forward_autograd(observations, controls)
             cov = self._autograd_covariance
@@ -373,9 +387,12 @@ class _FusedKalmanFilters(base.Filter, _EnabledModels):
         Sigma = torch.stack([f._belief_covariance for f in live]).contiguous()
         q = torch.stack([m.scale_tril() for m in dyns]).to(torch.float32).contiguous()
         steps = torch.empty((T, N, d, d), dtype=torch.float32, device=mu.device) if self.record_belief else None
+        buf = self._innovation_buffers((T, len(live), N), mu.device) if self._innovations_on() else None
         est, Sigma_f = engine.run_ekf_loop([m._net for m in dyns], [ctrl_all[i]["bias"] for i in live_idx], q, z, r, mu, Sigma,
                                            fusion=fusion, feedback=feedback, gate=gate, Sigma_steps=steps,
-                                           fuse_w=None if fuse_w is None else f32(fuse_w).contiguous())
+                                           fuse_w=None if fuse_w is None else f32(fuse_w).contiguous(),
+                                           innovations=buf, nis_gate=self._innovation_gate)
+        self.last_innovations = None if buf is None else self._innovation_record(buf, fused=True)
         self.last_belief = base.belief_record(covariance=steps) if self.record_belief else None
         for k, f in enumerate(live):
             f._belief_mean, f._belief_covariance = mu[k], Sigma[k]
@@ -386,7 +403,9 @@ class _FusedKalmanFilters(base.Filter, _EnabledModels):
         """Sensors, fusion weights and control encoders do not depend on the belief: they are
         evaluated ahead of the recursion for all ``T*N`` rows at once."""
         T, N = tree_leading_shape(controls)[:2]
+        self.last_innovations = None
         if use_autograd(self):
+            self._refuse_innovations_in_training()
             return base.Filter.forward_loop(self, observations=observations, controls=controls)
         with torch.no_grad():
             encs = self._encode_loop(observations, T, N)
@@ -395,15 +414,18 @@ class _FusedKalmanFilters(base.Filter, _EnabledModels):
             native = self._native_loop(encs, ctrl_all, T, N, observations)
             if native is not None:
                 return self._after_native_loop(*native)
-            out, beliefs = [], []
+            out, beliefs, innovations = [], [], []
             for t in range(T):
                 sl = slice(t * N, (t + 1) * N)
                 ctrl = [None if c is None else {k: v[sl] for k, v in c.items()} for c in ctrl_all]
                 out.append(self._forward_encoded(tree_index(observations, t), tree_index(controls, t),
                                                  encs[t], ctrl))
                 beliefs.append(self.last_belief)
+                innovations.append(self.last_innovations)
             if self.record_belief:
                 self.last_belief = base.stack_belief_records(beliefs)
+            if self._innovations_on():
+                self.last_innovations = self._stack_innovation_records(innovations)
         return torch.stack(out, dim=0)
 
 

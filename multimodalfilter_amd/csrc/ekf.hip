@@ -6,6 +6,8 @@
 //   /root/reference/crossmodal/base_models/crossmodal_kf.py:153-167  (crossmodal fusion)
 //   /root/reference/crossmodal/base_models/utility.py:4-11           (weighted_average)
 //   /root/reference/crossmodal/base_models/unimodal_kf.py:204-242    (information-form fusion)
+// The innovation form of the step (mmf_ekf_step_innov: NIS, log-likelihood and the NIS gate per sub-filter and trajectory;
+// include/mmf.h, "innovation statistics") is the same kernel with INNOV = true: 12 B more per sub-filter-trajectory-step.
 // HBM bytes per trajectory-step (K=2, d=3): 2*(A 36 + mu- 12 + z 12 + T 36 + w 12 + Sigma 36 r/w 72
 // + mu 12) + fused 48 = 432 B for ~1.5 kFLOP: launch-latency-bound in isolation.
 #include "ekf_algebra.h"
@@ -15,12 +17,24 @@ namespace {
 using namespace mmf_ekf;
 
 
-template <int D>
+// What the INNOV form of the step adds (mmf_ekf_step_innov): the NIS gate and the three (K, N) outputs, any of them null.
+struct InnovOut {
+  float gate;  // < 0: no gating
+  float* nis;
+  float* loglik;
+  int32_t* accepted;
+};
+
+// INNOV = false: the step as it always was (InnovOut is not read).  INNOV = true: the same device functions, the by-products
+// of predict_correct_parts kept for the innovation statistics, and a measurement whose NIS exceeds the gate rejected --
+// that sub-filter keeps (mu-, S-), the values predict_correct_parts formed, and enters the fusion with them.
+template <int D, bool INNOV>
 __global__ __launch_bounds__(256) void ekf_step_kernel(
     const float* __restrict__ A, const float* __restrict__ mu_pred, const float* __restrict__ q_tril,
     const float* __restrict__ z, const float* __restrict__ r_tril, const float* __restrict__ fuse_w,
     float* __restrict__ mu, float* __restrict__ Sigma, float* __restrict__ mu_f,
-    float* __restrict__ Sigma_f, int N, int K, int fusion, int feedback, const int32_t* __restrict__ feedback_gate) {
+    float* __restrict__ Sigma_f, int N, int K, int fusion, int feedback, const int32_t* __restrict__ feedback_gate,
+    InnovOut io) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
   // a batch-global, data-dependent branch of the reference (door_models/crossmodal_kf.py:59-62: ANY blacked-out
@@ -43,7 +57,23 @@ __global__ __launch_bounds__(256) void ekf_step_kernel(
       mp[i] = mu_pred[row * D + i];
       zk[i] = z[row * D + i];
     }
-    predict_correct<D>(Ak, S0, L, T, mp, zk, mus[k], Ss[k]);
+    if constexpr (INNOV) {
+      Mat<D> Sp, Sinn, Si;
+      float innov[D], nis, logdet;
+      predict_correct_parts<D>(Ak, S0, L, T, mp, zk, mus[k], Ss[k], Sp, Sinn, Si, innov);
+      innovation_stats<D>(Sinn, Si, innov, nis, logdet);
+      const bool ok = io.gate < 0.f || nis <= io.gate;  // (a NaN NIS is rejected)
+      if (!ok) {
+#pragma unroll
+        for (int i = 0; i < D; ++i) mus[k][i] = mp[i];
+        Ss[k] = Sp;
+      }
+      if (io.nis != nullptr) io.nis[row] = nis;
+      if (io.loglik != nullptr) io.loglik[row] = loglik_of(nis, logdet, D);
+      if (io.accepted != nullptr) io.accepted[row] = ok ? 1 : 0;
+    } else {
+      predict_correct<D>(Ak, S0, L, T, mp, zk, mus[k], Ss[k]);
+    }
     if (fusion == 1) {
 #pragma unroll
       for (int i = 0; i < D; ++i) w[k][i] = fuse_w[row * D + i];
@@ -301,21 +331,29 @@ extern "C" int mmf_ekf_step(const float* A, const float* mu_pred, const float* q
                             nullptr, stream);
 }
 
-extern "C" int mmf_ekf_step_gated(const float* A, const float* mu_pred, const float* q_tril,
-                                  const float* z, const float* r_tril, const float* fuse_w, float* mu,
-                                  float* Sigma, float* mu_f, float* Sigma_f, int N, int d, int K,
-                                  int fusion, int feedback, const int32_t* feedback_gate, void* stream) {
+namespace {
+
+// The argument checks of the K3 step, all on the host before any HIP call; 1: nothing to do (N == 0).
+int ekf_step_check(const float* A, const float* mu_pred, const float* q_tril, const float* z, const float* r_tril,
+                   const float* fuse_w, float* mu, float* Sigma, float* mu_f, float* Sigma_f, int N, int d, int K,
+                   int fusion) {
   if (!A || !mu_pred || !q_tril || !z || !r_tril || !mu || !Sigma) return MMF_EINVAL;
   if (N < 0 || d < 1 || d > MMF_MAX_STATE_DIM || K < 1 || K > kMaxK) return MMF_EINVAL;
   if (fusion < 0 || fusion > 2 || (fusion == 1 && !fuse_w)) return MMF_EINVAL;
   if (fusion != 0 && (!mu_f || !Sigma_f)) return MMF_EINVAL;
-  if (N == 0) return 0;
+  return N == 0 ? 1 : 0;
+}
+
+template <bool INNOV>
+int ekf_step_launch(const float* A, const float* mu_pred, const float* q_tril, const float* z, const float* r_tril,
+                    const float* fuse_w, float* mu, float* Sigma, float* mu_f, float* Sigma_f, int N, int d, int K,
+                    int fusion, int feedback, const int32_t* feedback_gate, const InnovOut& io, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int block = 256, grid = (N + block - 1) / block;
-#define MMF_K3(D)                                                                               \
-  case D:                                                                                       \
-    ekf_step_kernel<D><<<grid, block, 0, s>>>(A, mu_pred, q_tril, z, r_tril, fuse_w, mu, Sigma,  \
-                                              mu_f, Sigma_f, N, K, fusion, feedback, feedback_gate); \
+#define MMF_K3(D)                                                                                              \
+  case D:                                                                                                      \
+    ekf_step_kernel<D, INNOV><<<grid, block, 0, s>>>(A, mu_pred, q_tril, z, r_tril, fuse_w, mu, Sigma, mu_f,    \
+                                                     Sigma_f, N, K, fusion, feedback, feedback_gate, io);      \
     break;
   switch (d) {
     MMF_K3(1) MMF_K3(2) MMF_K3(3) MMF_K3(4)
@@ -323,6 +361,44 @@ extern "C" int mmf_ekf_step_gated(const float* A, const float* mu_pred, const fl
 #undef MMF_K3
   MMF_CHECK_LAUNCH();
   return 0;
+}
+
+}  // namespace
+
+extern "C" int mmf_ekf_step_gated(const float* A, const float* mu_pred, const float* q_tril,
+                                  const float* z, const float* r_tril, const float* fuse_w, float* mu,
+                                  float* Sigma, float* mu_f, float* Sigma_f, int N, int d, int K,
+                                  int fusion, int feedback, const int32_t* feedback_gate, void* stream) {
+  const int rc = ekf_step_check(A, mu_pred, q_tril, z, r_tril, fuse_w, mu, Sigma, mu_f, Sigma_f, N, d, K, fusion);
+  if (rc != 0) return rc < 0 ? rc : 0;
+  return ekf_step_launch<false>(A, mu_pred, q_tril, z, r_tril, fuse_w, mu, Sigma, mu_f, Sigma_f, N, d, K, fusion, feedback,
+                                feedback_gate, InnovOut{-1.f, nullptr, nullptr, nullptr}, stream);
+}
+
+extern "C" int mmf_ekf_step_innov(const float* A, const float* mu_pred, const float* q_tril, const float* z,
+                                  const float* r_tril, const float* fuse_w, float* mu, float* Sigma, float* mu_f,
+                                  float* Sigma_f, int N, int d, int K, int fusion, int feedback,
+                                  const int32_t* feedback_gate, float nis_gate, float* nis, float* loglik,
+                                  int32_t* accepted, void* stream) {
+  const int rc = ekf_step_check(A, mu_pred, q_tril, z, r_tril, fuse_w, mu, Sigma, mu_f, Sigma_f, N, d, K, fusion);
+  if (rc < 0) return rc;
+  if (nis_gate != nis_gate) return MMF_EINVAL;  // a NaN threshold decides nothing
+  {  // no output on top of an input or of another output (Sigma, in/out, stands among the outputs)
+    const size_t kn = static_cast<size_t>(K) * N, v = sizeof(float) * d, m = v * d;
+    const void* ins[] = {A, mu_pred, q_tril, z, r_tril, fuse_w, feedback_gate};
+    const size_t in_bytes[] = {kn * m, kn * v, K * m, kn * v, kn * m, fusion == 1 ? kn * v : 0, N > 0 ? sizeof(int32_t) : 0};
+    const void* outs[] = {mu, Sigma, fusion ? mu_f : nullptr, fusion ? Sigma_f : nullptr, nis, loglik, accepted};
+    const size_t out_bytes[] = {kn * v, kn * m, N * v, N * m, kn * sizeof(float), kn * sizeof(float), kn * sizeof(int32_t)};
+    for (int o = 0; o < 7; ++o) {
+      for (int i = 0; i < 7; ++i)
+        if (mmf_bytes_overlap(outs[o], out_bytes[o], ins[i], in_bytes[i])) return MMF_EINVAL;
+      for (int p = 0; p < o; ++p)
+        if (mmf_bytes_overlap(outs[o], out_bytes[o], outs[p], out_bytes[p])) return MMF_EINVAL;
+    }
+  }
+  if (rc == 1) return 0;
+  return ekf_step_launch<true>(A, mu_pred, q_tril, z, r_tril, fuse_w, mu, Sigma, mu_f, Sigma_f, N, d, K, fusion, feedback,
+                               feedback_gate, InnovOut{nis_gate, nis, loglik, accepted}, stream);
 }
 
 extern "C" int mmf_ekf_step_backward(const float* A, const float* mu_pred, const float* q_tril, const float* z,

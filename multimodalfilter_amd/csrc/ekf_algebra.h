@@ -10,6 +10,7 @@
 //   /root/reference/crossmodal/base_models/unimodal_kf.py:204-242    (information-form fusion)
 #pragma once
 #include "mmf_common.h"
+#include "../../include/mmf_detmath.h"
 
 namespace mmf_ekf {
 
@@ -123,15 +124,18 @@ constexpr int kMaxK = 4;
 
 // predict + correct of one sub-filter (C = I):  S- = A S A^T + L L^T;  K = S- (S- + T T^T)^-1;
 // mu = mu- + K (z - mu-);  S = (I - K) S-  with  I - K = T T^T (S- + T T^T)^-1
+// The by-products a caller may keep: Sp = S- (the predicted covariance), Sinn = S- + T T^T (the innovation covariance),
+// Si = Sinn^-1 and innov = z - mu-.  predict_correct below drops them; the statements that form mu_out / S_out are these, in
+// this order, for either caller.
 template <int D>
-__device__ __forceinline__ void predict_correct(const Mat<D>& Ak, const Mat<D>& S0, const Mat<D>& L, const Mat<D>& T,
-                                                const float (&mp)[D], const float (&z)[D], float (&mu_out)[D], Mat<D>& S_out) {
+__device__ __forceinline__ void predict_correct_parts(const Mat<D>& Ak, const Mat<D>& S0, const Mat<D>& L, const Mat<D>& T,
+                                                      const float (&mp)[D], const float (&z)[D], float (&mu_out)[D],
+                                                      Mat<D>& S_out, Mat<D>& Sp, Mat<D>& Sinn, Mat<D>& Si, float (&innov)[D]) {
 #pragma clang fp contract(off)
   const Mat<D> AS = matmul<D>(Ak, S0);
-  Mat<D> Sp = matmul_nt<D>(AS, Ak);
+  Sp = matmul_nt<D>(AS, Ak);
   const Mat<D> Q = matmul_nt<D>(L, L);
   const Mat<D> Rm = matmul_nt<D>(T, T);
-  Mat<D> Sinn;
 #pragma unroll
   for (int i = 0; i < D; ++i)
 #pragma unroll
@@ -139,13 +143,12 @@ __device__ __forceinline__ void predict_correct(const Mat<D>& Ak, const Mat<D>& 
       Sp.a[i][j] += Q.a[i][j];
       Sinn.a[i][j] = Sp.a[i][j] + Rm.a[i][j];
     }
-  const Mat<D> Si = inverse<D>(Sinn);
+  Si = inverse<D>(Sinn);
   const Mat<D> G = matmul<D>(Sp, Si);
   // I - G = (Sinn - S-) Sinn^-1 = T T^T Sinn^-1, formed as that product: where the sensor is sharp next to the prediction
   // G is close to I and "I - G" keeps only the rounding of G -- 7e-5 of S on its small directions, which the information
   // form (fuse, fusion 2) inverts: mu_f went 2e-4 .. 6e-4 off from that alone.  As a product, S is good to 1e-5.
   const Mat<D> ImG = matmul<D>(Rm, Si);
-  float innov[D];
 #pragma unroll
   for (int i = 0; i < D; ++i) innov[i] = z[i] - mp[i];
 #pragma unroll
@@ -156,6 +159,61 @@ __device__ __forceinline__ void predict_correct(const Mat<D>& Ak, const Mat<D>& 
     mu_out[i] = mp[i] + s;
   }
   S_out = matmul<D>(ImG, Sp);
+}
+
+template <int D>
+__device__ __forceinline__ void predict_correct(const Mat<D>& Ak, const Mat<D>& S0, const Mat<D>& L, const Mat<D>& T,
+                                                const float (&mp)[D], const float (&z)[D], float (&mu_out)[D], Mat<D>& S_out) {
+  Mat<D> Sp, Sinn, Si;
+  float innov[D];
+  predict_correct_parts<D>(Ak, S0, L, T, mp, z, mu_out, S_out, Sp, Sinn, Si, innov);
+}
+
+// What the innovation says about the model (include/mmf.h, "innovation statistics"):  nis = innov^T Sinn^-1 innov as an
+// explicit fma chain over Si innov, and log det Sinn from the Cholesky factorisation of Sinn in registers -- the sum of the
+// logs of the squared pivots, with the deterministic log of mmf_detmath.h.  A pivot that is not positive (Sinn not positive
+// definite, or not finite) makes log det NaN; the NIS is whatever the inverse gave.
+template <int D>
+__device__ __forceinline__ void innovation_stats(const Mat<D>& Sinn, const Mat<D>& Si, const float (&innov)[D], float& nis,
+                                                 float& logdet) {
+#pragma clang fp contract(off)
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < D; ++i) {
+    float y = 0.f;
+#pragma unroll
+    for (int j = 0; j < D; ++j) y = __builtin_fmaf(Si.a[i][j], innov[j], y);
+    q = __builtin_fmaf(innov[i], y, q);
+  }
+  nis = q;
+  Mat<D> C;  // lower triangle: Sinn = C C^T
+  float ld = 0.f;
+  bool pd = true;
+#pragma unroll
+  for (int j = 0; j < D; ++j) {
+    float s = Sinn.a[j][j];
+#pragma unroll
+    for (int k = 0; k < j; ++k) s = __builtin_fmaf(-C.a[j][k], C.a[j][k], s);
+    pd = pd && s >= 1.17549435e-38f && s <= 3.40282347e+38f;  // mmf_det_log's domain: normal, finite (false for NaN too)
+    ld += mmf_det_log(pd ? s : 1.f);
+    const float dj = __builtin_sqrtf(s);
+    C.a[j][j] = dj;
+#pragma unroll
+    for (int i = j + 1; i < D; ++i) {
+      float t = Sinn.a[i][j];
+#pragma unroll
+      for (int k = 0; k < j; ++k) t = __builtin_fmaf(-C.a[i][k], C.a[j][k], t);
+      C.a[i][j] = t / dj;
+    }
+  }
+  logdet = pd ? ld : __builtin_nanf("");
+}
+
+// log N(innov; 0, Sinn) = -1/2 (nis + log det Sinn + d log 2 pi)
+__device__ __forceinline__ float loglik_of(float nis, float logdet, int d) {
+#pragma clang fp contract(off)
+  const float c = static_cast<float>(d) * 1.8378770664093453f;
+  return -0.5f * ((nis + logdet) + c);
 }
 
 // fusion of K corrected sub-filters: 1 = crossmodal weighted average (w: (K, D) weights of this trajectory),

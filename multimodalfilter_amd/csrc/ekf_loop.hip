@@ -8,9 +8,12 @@
 #include "mmf_common.h"
 
 // Sigma_steps: (T, N, d, d) or null -- every step's posterior covariance (mmf_ekf_forward_loop_belief)
-static int ekf_forward_loop(const MmfEkfLoopArgs* a, float* Sigma_steps, void* stream) {
+// innov: null, or the innovation record of mmf_ekf_forward_loop_innov -- K3 is then the step of mmf_ekf_step_innov and the
+// loop is the loop of launches, whatever a->persistent says
+static int ekf_forward_loop(const MmfEkfLoopArgs* a, float* Sigma_steps, const MmfEkfInnovArgs* innov, void* stream) {
   if (!a) return MMF_EINVAL;
-  if (a->T < 0 || a->N < 1 || a->K < 1 || a->K > MMF_LOOP_MAX_MEAS || a->d < 1) return MMF_EINVAL;
+  if (a->T < 0 || a->N < (innov ? 0 : 1) || a->K < 1 || a->K > MMF_LOOP_MAX_MEAS || a->d < 1) return MMF_EINVAL;
+  if (innov && a->d > MMF_MAX_STATE_DIM) return MMF_EINVAL;
   if (a->fusion < 0 || a->fusion > 2) return MMF_EINVAL;
   if (!a->q_tril || !a->z || !a->r_tril || !a->mu || !a->Sigma || !a->mu_pred || !a->A || !a->estimates)
     return MMF_EINVAL;
@@ -18,7 +21,28 @@ static int ekf_forward_loop(const MmfEkfLoopArgs* a, float* Sigma_steps, void* s
   if (a->fusion != 0 && (!a->Sigma_f)) return MMF_EINVAL;
   for (int k = 0; k < a->K; ++k)
     if (!a->dyn_packed[k] || !a->dyn_bias[k]) return MMF_EINVAL;
-  if (a->persistent && a->T > 0) {  // ONE launch for all T steps (ekf_persistent.inc); same bits
+  if (innov) {
+    if (innov->nis_gate != innov->nis_gate) return MMF_EINVAL;
+    const size_t rows = static_cast<size_t>(a->T) * a->K * a->N, kn = static_cast<size_t>(a->K) * a->N;
+    const size_t tn = static_cast<size_t>(a->T) * a->N, v = sizeof(float) * a->d, m = v * a->d;
+    const void* ins[] = {a->q_tril, a->z, a->r_tril, a->fuse_w, a->feedback_gate};
+    const size_t in_bytes[] = {a->K * m, rows * v, rows * m, a->fusion == 1 ? rows * v : 0, a->T * sizeof(int32_t)};
+    const void* state[] = {a->mu, a->Sigma, a->mu_pred, a->A, a->fusion ? a->Sigma_f : nullptr, a->estimates, Sigma_steps};
+    const size_t state_bytes[] = {kn * v, kn * m, kn * v, kn * m, a->N * m, tn * v, tn * m};
+    const void* outs[] = {innov->nis_steps, innov->loglik_steps, innov->accepted_steps};
+    for (int o = 0; o < 3; ++o) {  // no record on top of an input, of the loop's state and outputs, or of another record
+      const size_t nb = rows * sizeof(float);
+      auto hits = [&](const void* q, size_t nq) { return mmf_bytes_overlap(outs[o], nb, q, nq); };
+      for (int i = 0; i < 5; ++i)
+        if (hits(ins[i], in_bytes[i])) return MMF_EINVAL;
+      for (int i = 0; i < 7; ++i)
+        if (hits(state[i], state_bytes[i])) return MMF_EINVAL;
+      for (int q = 0; q < o; ++q)
+        if (hits(outs[q], nb)) return MMF_EINVAL;
+    }
+    if (a->T == 0 || a->N == 0) return 0;
+  }
+  if (!innov && a->persistent && a->T > 0) {  // ONE launch for all T steps (ekf_persistent.inc); same bits
     const int rc = mmf_internal_ekf_persistent(a, Sigma_steps, stream);
     if (rc != MMF_INTERNAL_NOT_RESIDENT) return rc;
     // this device cannot hold the persistent grid, or the problem is not eligible: the loop of launches
@@ -34,10 +58,18 @@ static int ekf_forward_loop(const MmfEkfLoopArgs* a, float* Sigma_steps, void* s
       if (rc) return rc;
     }
     float* est = a->estimates + t * N * d;
-    const int rc = mmf_ekf_step_gated(a->A, a->mu_pred, a->q_tril, a->z + t * K * N * d, a->r_tril + t * K * N * d * d,
-                                      a->fuse_w ? a->fuse_w + t * K * N * d : nullptr, a->mu, a->Sigma,
-                                      a->fusion ? est : nullptr, a->fusion ? a->Sigma_f : nullptr, a->N, a->d,
-                                      a->K, a->fusion, a->feedback, a->feedback_gate ? a->feedback_gate + t : nullptr, stream);
+    const float* fuse_w = a->fuse_w ? a->fuse_w + t * K * N * d : nullptr;
+    const int32_t* gate = a->feedback_gate ? a->feedback_gate + t : nullptr;
+    const int rc =
+        innov ? mmf_ekf_step_innov(a->A, a->mu_pred, a->q_tril, a->z + t * K * N * d, a->r_tril + t * K * N * d * d, fuse_w,
+                                   a->mu, a->Sigma, a->fusion ? est : nullptr, a->fusion ? a->Sigma_f : nullptr, a->N, a->d,
+                                   a->K, a->fusion, a->feedback, gate, innov->nis_gate,
+                                   innov->nis_steps ? innov->nis_steps + t * K * N : nullptr,
+                                   innov->loglik_steps ? innov->loglik_steps + t * K * N : nullptr,
+                                   innov->accepted_steps ? innov->accepted_steps + t * K * N : nullptr, stream)
+              : mmf_ekf_step_gated(a->A, a->mu_pred, a->q_tril, a->z + t * K * N * d, a->r_tril + t * K * N * d * d, fuse_w,
+                                   a->mu, a->Sigma, a->fusion ? est : nullptr, a->fusion ? a->Sigma_f : nullptr, a->N, a->d,
+                                   a->K, a->fusion, a->feedback, gate, stream);
     if (rc) return rc;
     if (a->fusion == 0) {  // a single (enabled) sub-filter: its corrected mean is the estimate
       const hipError_t e = hipMemcpyAsync(est, a->mu, N * d * sizeof(float), hipMemcpyDeviceToDevice, hs);
@@ -52,9 +84,17 @@ static int ekf_forward_loop(const MmfEkfLoopArgs* a, float* Sigma_steps, void* s
   return 0;
 }
 
-extern "C" int mmf_ekf_forward_loop(const MmfEkfLoopArgs* a, void* stream) { return ekf_forward_loop(a, nullptr, stream); }
+extern "C" int mmf_ekf_forward_loop(const MmfEkfLoopArgs* a, void* stream) {
+  return ekf_forward_loop(a, nullptr, nullptr, stream);
+}
 
 extern "C" int mmf_ekf_forward_loop_belief(const MmfEkfLoopArgs* a, float* Sigma_steps, void* stream) {
   if (!Sigma_steps) return MMF_EINVAL;
-  return ekf_forward_loop(a, Sigma_steps, stream);
+  return ekf_forward_loop(a, Sigma_steps, nullptr, stream);
+}
+
+extern "C" int mmf_ekf_forward_loop_innov(const MmfEkfLoopArgs* a, const MmfEkfInnovArgs* innov, float* Sigma_steps,
+                                          void* stream) {
+  if (!innov) return MMF_EINVAL;
+  return ekf_forward_loop(a, Sigma_steps, innov, stream);
 }

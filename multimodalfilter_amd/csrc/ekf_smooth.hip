@@ -195,12 +195,6 @@ __global__ __launch_bounds__(256) void ekf_smooth_lag_kernel(SmoothArgs a) {
   store_mat<D>(a.Sigma_s + row * D * D, Ps);
 }
 
-bool overlap(const void* p, size_t np, const void* q, size_t nq) {  // byte ranges; an empty range overlaps nothing
-  if (!p || !q || np == 0 || nq == 0) return false;
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-  return a < b + nq && b < a + np;
-}
-
 template <int D>
 int launch(const SmoothArgs& a, hipStream_t s) {
   const size_t transitions = static_cast<size_t>(a.T - 1) * a.N, rows = static_cast<size_t>(a.T) * a.N;
@@ -239,9 +233,9 @@ extern "C" int mmf_ekf_smooth(const MmfEkfSmoothArgs* args, void* stream) {
   const size_t out_bytes[] = {rows * v, rows * m, trans * m, trans * m, trans * v, trans * m};
   for (int o = 0; o < 6; ++o) {
     for (int i = 0; i < 5; ++i)
-      if (overlap(outs[o], out_bytes[o], ins[i], in_bytes[i])) return MMF_EINVAL;
+      if (mmf_bytes_overlap(outs[o], out_bytes[o], ins[i], in_bytes[i])) return MMF_EINVAL;
     for (int p = 0; p < o; ++p)
-      if (overlap(outs[o], out_bytes[o], outs[p], out_bytes[p])) return MMF_EINVAL;
+      if (mmf_bytes_overlap(outs[o], out_bytes[o], outs[p], out_bytes[p])) return MMF_EINVAL;
   }
   if (T == 0 || N == 0) return 0;
   SmoothArgs a;

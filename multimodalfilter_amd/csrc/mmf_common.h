@@ -13,6 +13,13 @@
     if (_e != hipSuccess) return static_cast<int>(_e); \
   } while (0)
 
+// Host-side argument check: do the byte ranges [p, p + np) and [q, q + nq) overlap?  An empty or null range overlaps nothing.
+inline bool mmf_bytes_overlap(const void* p, size_t np, const void* q, size_t nq) {
+  if (!p || !q || np == 0 || nq == 0) return false;
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+  return a < b + nq && b < a + np;
+}
+
 // the persistent small-problem step loop (pf_persistent.inc, compiled with particle_net.hip); reached through
 // mmf_pf_forward_loop when MmfPfLoopArgs.persistent is set
 // ess_threshold > 0: ESS-triggered resampling (mmf_pf_forward_loop_adaptive), resampled_steps (T, N) or null

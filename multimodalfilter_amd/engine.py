@@ -268,12 +268,16 @@ def run_persistent(a, call, *, n_sync_words: int, device, restore=()):
     return out
 
 
-def run_ekf_loop(nets, biases, q, z, r, mu, Sigma, *, fusion=0, feedback=0, fuse_w=None, gate=None, Sigma_steps=None):
+def run_ekf_loop(nets, biases, q, z, r, mu, Sigma, *, fusion=0, feedback=0, fuse_w=None, gate=None, Sigma_steps=None,
+                 innovations=None, nis_gate=None):
     """``mmf_ekf_forward_loop`` for ``K = len(nets)`` sub-filters: ``nets`` their dynamics networks (``PackedParticleNet``),
     ``biases`` the hoisted control terms ``(T*N, 64)``, ``q (K, d, d)``, ``z (T, K, N, d)``, ``r (T, K, N, d, d)``,
     ``mu (K, N, d)`` / ``Sigma (K, N, d, d)`` the belief, updated in place -> ``(estimates (T, N, d), Sigma_f | None)``.
     ``Sigma_steps (T, N, d, d)`` or ``None``: every step's posterior covariance (fused, or sub-filter 0's for fusion 0),
     written by whichever form runs.
+    ``innovations``: ``None`` (today's path), or the record ``(nis, log_likelihood, accepted)`` to fill -- float32, float32
+    and int32 ``(T, K, N)`` tensors -- with ``nis_gate`` the NIS threshold (``None``: no gating): K3 is then the step of
+    ``mmf_ekf_step_innov`` and the loop is the loop of launches (``mmf_ekf_forward_loop_innov``).
     ONE persistent launch where the problem is eligible (``EKF_PERSISTENT``), else / after a give-up 2 T launches."""
     T, K, N, d = z.shape
     E = lambda *shape: torch.empty(shape, dtype=torch.float32, device=mu.device)
@@ -288,6 +292,15 @@ def run_ekf_loop(nets, biases, q, z, r, mu, Sigma, *, fusion=0, feedback=0, fuse
     a.q_tril, a.z, a.r_tril, a.fuse_w, a.feedback_gate = P(q), P(z), P(r), P(fuse_w), P(gate, torch.int32)
     a.mu, a.Sigma, a.mu_pred, a.A, a.Sigma_f, a.estimates = P(mu), P(Sigma), P(mu_pred), P(A), P(Sigma_f), P(est)
     assert Sigma_steps is None or Sigma_steps.shape == (T, N, d, d)
+    if innovations is not None:  # the persistent launch keeps no innovation: the loop of launches, nothing to give up
+        nis, loglik, accepted = innovations
+        assert all(t.shape == (T, K, N) for t in innovations)
+        i = _abi.MmfEkfInnovArgs()
+        i.nis_gate = -1.0 if nis_gate is None else float(nis_gate)
+        i.nis_steps, i.loglik_steps, i.accepted_steps = P(nis), P(loglik), P(accepted, torch.int32)
+        _abi.ekf_forward_loop(a, mu, Sigma_steps, innov=i)
+        return est, Sigma_f
+    assert nis_gate is None, "run_ekf_loop: a NIS gate needs the innovation record (accepted is what the caller needs)"
     go = (EKF_PERSISTENT and not is_capturing() and T > 0 and d in (2, 3) and a.n_res_dyn == 3
           and _abi.ekf_persistent_plan(N, K) > 0)
     n_words = _abi.ekf_persistent_sync_words(N, K, d) if go else 0

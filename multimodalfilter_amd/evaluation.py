@@ -23,7 +23,8 @@ _DEFAULT_METHOD = _DefaultMethod("ancestry")
 
 def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale: float = 0.1,
                measurement_initialize: bool = False, return_belief: bool = False, smooth_lag=False,
-               smooth_method: str = _DEFAULT_METHOD, smooth_draws: int = _DEFAULT_DRAWS, smooth_transition_moments: bool = False):
+               smooth_method: str = _DEFAULT_METHOD, smooth_draws: int = _DEFAULT_DRAWS, smooth_transition_moments: bool = False,
+               return_innovations: bool = False):
     """Initialise the belief at ``states[0]`` with covariance ``0.1 I`` (or from the first
     observation, ``eval_helpers.py:116-131``) and filter ``[1:]`` (``:139-142``).
     ``return_belief``: run with ``record_belief`` set and return ``(estimates, filter_model.last_belief)`` -- the per-step
@@ -39,7 +40,14 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
     ``"simulation"`` likewise, with ``smooth_draws`` joint paths per trajectory (``smooth(num_draws=)``, default 64; passing it with
     another method is the ``ValueError`` it is there), and leaves ``covariance``, ``trajectories``, ``indices``, ``num_draws``.
     ``smooth_transition_moments``: smooths with the filter's ``record_transition_moments`` set (and puts the switch back) -- with ``smooth_method="marginal"`` or ``"rts"`` alone, refused
-    before the run otherwise; the record gains ``residual_mean`` and ``residual_second_moment`` (``process_noise_m_step``)."""
+    before the run otherwise; the record gains ``residual_mean`` and ``residual_second_moment`` (``process_noise_m_step``).
+    ``return_innovations``: runs a Kalman filter with ``record_innovations`` set (and puts the switch back) and appends
+    ``filter_model.last_innovations`` -- ``nis``, ``log_likelihood``, ``accepted`` per step (``innovation_summary``) -- to what
+    is returned: ``(estimates, innovations)`` or ``(estimates, record, innovations)``.  A filter without the switch (the
+    particle filters, the LSTM baselines) is refused before the run."""
+    if return_innovations and not hasattr(filter_model, "record_innovations"):  # (before the run, not after it)
+        raise ValueError(f"run_filter: return_innovations needs a Kalman filter; {type(filter_model).__name__} has no "
+                         "record_innovations (a particle filter reports log_evidence through return_belief)")
     named = smooth_method is not _DEFAULT_METHOD
     if not named:
         smooth_method = getattr(filter_model, "default_smooth_method", "ancestry")
@@ -64,6 +72,10 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
         assert hasattr(filter_model, "record_history"), f"{type(filter_model).__name__} keeps no history to smooth"
         was_history = filter_model.record_history
         filter_model.record_history = True
+    if return_innovations:
+        was_innovations = filter_model.record_innovations
+        filter_model.record_innovations = True
+    innovations = None
     try:
         with torch.no_grad():
             if measurement_initialize and hasattr(filter_model, "measurement_initialize_beliefs"):
@@ -73,7 +85,11 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
                 filter_model.initialize_beliefs(mean=states[0], covariance=cov)
             est = filter_model.forward_loop(observations={k: v[1:] for k, v in obs.items()},
                                             controls=traj["controls"][1:])
+        if return_innovations:
+            innovations = filter_model.last_innovations
     finally:
+        if return_innovations:
+            filter_model.record_innovations = was_innovations
         if return_belief:
             filter_model.record_belief = was
         if smoothing:
@@ -89,8 +105,40 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
         finally:
             if smooth_transition_moments:
                 filter_model.record_transition_moments = was_moments
-        return (est, filter_model.last_smoothed) if return_belief else est
-    return (est, filter_model.last_belief) if return_belief else est
+        out = (est, filter_model.last_smoothed) if return_belief else est
+    else:
+        out = (est, filter_model.last_belief) if return_belief else est
+    if return_innovations:
+        return (out if isinstance(out, tuple) else (out,)) + (innovations,)
+    return out
+
+
+def innovation_summary(record, dim: int) -> Dict[str, torch.Tensor]:
+    """What a Kalman filter's innovation record (``last_innovations``; ``run_filter(return_innovations=True)``) says about
+    the model, without ground truth.  ``dim``: the state dimension ``d``.  Under a consistent filter the NIS is chi-squared
+    with ``d`` degrees of freedom, so ``mean_nis`` should be close to ``d``.
+    ``mean_nis``: the mean NIS over ALL measurements, rejected ones included; ``accepted_fraction``; ``log_likelihood``: the
+    sum of the per-step log-likelihoods over the ACCEPTED measurements (``log p(y_{1:T})`` of the model where nothing was
+    rejected).  One 0-d tensor each for a single filter, ``(K,)`` -- one entry per sub-filter -- for a fused record;
+    ``nis_over_dim = mean_nis / dim``, close to 1 for a consistent filter.  Plain torch on the record's device."""
+    dim = int(dim)
+    if dim < 1:
+        raise ValueError(f"innovation_summary: dim must be the state dimension (>= 1), got {dim}")
+    for k in ("nis", "log_likelihood", "accepted"):
+        if getattr(record, k, None) is None:
+            raise ValueError(f"innovation_summary: the record has no {k}; run the filter with record_innovations set")
+    nis, ll, acc = record.nis.to(torch.float64), record.log_likelihood.to(torch.float64), record.accepted.to(torch.bool)
+    if getattr(record, "sub_filters", None) is not None:  # (..., K, N) -> (K, everything else)
+        nis, ll, acc = (t.movedim(-2, 0).reshape(t.shape[-2], -1) for t in (nis, ll, acc))
+        axis = 1
+    else:
+        nis, ll, acc = (t.reshape(-1) for t in (nis, ll, acc))
+        axis = 0
+    if nis.shape[axis] == 0:
+        raise ValueError("innovation_summary: the record holds no measurement")
+    mean_nis = nis.mean(dim=axis)
+    return {"mean_nis": mean_nis, "nis_over_dim": mean_nis / dim, "accepted_fraction": acc.to(torch.float64).mean(dim=axis),
+            "log_likelihood": torch.where(acc, ll, torch.zeros_like(ll)).sum(dim=axis)}
 
 
 def process_noise_m_step(record, *, diagonal: bool = False, start: int = 0) -> torch.Tensor:
@@ -145,7 +193,8 @@ def _moments_method(filter_model) -> str:
     return "rts" if getattr(filter_model, "default_smooth_method", None) == "rts" else "marginal"
 
 
-def fit_process_noise(filter_model, traj: Dict[str, torch.Tensor], *, iterations: int = 5, start: int = 0, **run_filter_kwargs):
+def fit_process_noise(filter_model, traj: Dict[str, torch.Tensor], *, iterations: int = 5, start: int = 0,
+                      return_log_likelihood: bool = False, **run_filter_kwargs):
     """EM for the process noise of ``filter_model.dynamics_model`` on the trajectories ``traj``: every iteration runs
     ``run_filter(smooth_method="marginal", smooth_transition_moments=True, return_belief=True)`` (the E-step: the two-slice
     moments under the current noise; ``smooth_method="rts"`` for an extended Kalman filter), takes ``process_noise_m_step`` over the steps ``>= start`` and hands the factor to
@@ -153,25 +202,39 @@ def fit_process_noise(filter_model, traj: Dict[str, torch.Tensor], *, iterations
     of ``(d, d)`` factors, the initial one first: ``iterations + 1`` entries.  ``run_filter_kwargs`` go to ``run_filter``
     (``initial_cov_scale``, ``measurement_initialize``); the smoothing switches are this function's own.  The filter's
     ``record_*`` switches are restored on every path; a model without ``set_scale_tril`` is a ``TypeError`` before any
-    run.  The moments are those of THIS process's trajectories: summing them across ranks is out of scope."""
+    run.  The moments are those of THIS process's trajectories: summing them across ranks is out of scope.
+    ``return_log_likelihood`` (Kalman filters): also returns, as a second list of ``iterations + 1`` floats, the total
+    log-likelihood ``sum_t,n log p(y_t | y_1..t-1)`` of the filter under each factor of the first list (``innovation_summary``
+    of the E-step's own run; one more filter run for the last factor) -- what EM must not decrease, up to the linearisation.
+    A filter without ``record_innovations`` is refused before any run."""
     dyn = getattr(filter_model, "dynamics_model", None)
     if dyn is None or not callable(getattr(dyn, "set_scale_tril", None)) or not callable(getattr(dyn, "scale_tril", None)):
         raise TypeError(f"fit_process_noise: {type(dyn).__name__} has no set_scale_tril(L) / scale_tril(): the process noise "
                         "of this dynamics model cannot be refitted (base.DynamicsModel documents the optional method)")
-    for k in ("smooth_method", "smooth_transition_moments", "return_belief", "smooth_lag", "smooth_draws"):
+    if return_log_likelihood and not hasattr(filter_model, "record_innovations"):
+        raise ValueError(f"fit_process_noise: return_log_likelihood needs a Kalman filter; {type(filter_model).__name__} has no "
+                         "record_innovations")
+    for k in ("smooth_method", "smooth_transition_moments", "return_belief", "smooth_lag", "smooth_draws", "return_innovations"):
         if k in run_filter_kwargs:
             raise TypeError(f"fit_process_noise: {k} is set by fit_process_noise itself")
     iterations = int(iterations)
     if iterations < 0:
         raise ValueError(f"fit_process_noise: iterations must be >= 0, got {iterations}")
     diagonal = bool(getattr(dyn, "diagonal_noise", False))
-    out = [dyn.scale_tril().detach().clone()]
+    out, logliks = [dyn.scale_tril().detach().clone()], []
+    total = lambda innovations: float(innovation_summary(innovations, traj["states"].shape[-1])["log_likelihood"].sum())
     for _ in range(iterations):
-        _est, record = run_filter(filter_model, traj, smooth_method=_moments_method(filter_model), smooth_transition_moments=True,
-                                  return_belief=True, **run_filter_kwargs)
+        got = run_filter(filter_model, traj, smooth_method=_moments_method(filter_model), smooth_transition_moments=True,
+                         return_belief=True, return_innovations=return_log_likelihood, **run_filter_kwargs)
+        record = got[1]
+        if return_log_likelihood:
+            logliks.append(total(got[2]))
         L = process_noise_m_step(record, diagonal=diagonal, start=start)
         dyn.set_scale_tril(L)
         out.append(dyn.scale_tril().detach().clone())
+    if return_log_likelihood:  # (the last factor has had no E-step)
+        logliks.append(total(run_filter(filter_model, traj, return_innovations=True, **run_filter_kwargs)[1]))
+        return out, logliks
     return out
 
 

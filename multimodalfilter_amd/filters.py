@@ -816,7 +816,73 @@ class ParticleFilter(base.Filter):
         return est
 
 
-class VirtualSensorExtendedKalmanFilter(base.Filter):
+class InnovationSwitches:
+    """The two innovation switches of every Kalman filter (evaluation mode only, both off by default; with both off every
+    launch and every bit is as without them).  Per step ``t``, sub-filter ``k`` and trajectory ``n`` (``include/mmf.h``,
+    "innovation statistics"): ``nu = z - mu-``, ``S = Sigma- + R``, ``nis = nu^T S^-1 nu`` (chi-squared with ``d`` degrees of
+    freedom under a consistent filter), ``log_likelihood = -1/2 (nis + log det S + d log 2 pi)``.
+
+    ``record_innovations = True``: ``forward`` / ``forward_loop`` leave ``last_innovations``, a ``base.belief_record`` of
+    ``nis``, ``log_likelihood`` (float32) and ``accepted`` (bool) -- ``(N,)`` for a single filter and ``(K, N)`` for a fused
+    one (``K`` enabled sub-filters, ``sub_filters = K`` in the record; ``None`` for a single filter), with a leading ``T``
+    after ``forward_loop``.
+    ``innovation_gate``: ``None`` or a float > 0, the NIS threshold (the caller picks the chi-squared quantile): a
+    measurement with ``nis > gate`` (or a NaN ``nis``) is rejected and that (sub-)filter keeps its predicted belief
+    ``(mu-, Sigma-)``; fusion and feedback then run on whatever every sub-filter holds.  With the gate alone
+    ``last_innovations`` is still left: ``accepted`` is what the caller needs.  A fused filter applies its one gate to
+    every sub-filter and ignores the sub-filters' own switches (evaluation mode).
+    The native loop then runs as a loop of launches: the persistent launch keeps no innovation and is not taken."""
+
+    def _init_innovation_switches(self):
+        self.record_innovations = False
+        self._innovation_gate = None
+        self.last_innovations = None
+
+    @property
+    def innovation_gate(self) -> Optional[float]:
+        return self._innovation_gate
+
+    @innovation_gate.setter
+    def innovation_gate(self, value) -> None:
+        if value is not None:
+            ok = isinstance(value, (int, float)) and not isinstance(value, bool) and math.isfinite(value) and value > 0
+            if not ok:
+                raise ValueError(f"innovation_gate must be None or a finite float > 0 (the NIS threshold), got {value!r}")
+            value = float(value)
+        self._innovation_gate = value
+
+    def _innovations_on(self) -> bool:
+        return bool(self.record_innovations) or self._innovation_gate is not None
+
+    def _refuse_innovations_in_training(self):
+        if self.record_innovations:
+            raise RuntimeError("record_innovations: the training (autograd) paths record no innovations; call .eval() first")
+        if self._innovation_gate is not None:
+            raise RuntimeError("innovation_gate: the training (autograd) paths gate no measurement; call .eval() first")
+
+    @staticmethod
+    def _innovation_buffers(lead, device):
+        """``(nis, log_likelihood, accepted)`` to hand to the step / loop entry: float32, float32, int32 of shape ``lead``."""
+        return (torch.empty(lead, dtype=torch.float32, device=device), torch.empty(lead, dtype=torch.float32, device=device),
+                torch.empty(lead, dtype=torch.int32, device=device))
+
+    @staticmethod
+    def _innovation_record(buffers, fused: bool):
+        """The filled buffers ``(..., K, N)`` as the record: a single filter's drop the ``K = 1`` axis."""
+        nis, ll, acc = buffers
+        if not fused:
+            nis, ll, acc = (t.squeeze(-2) for t in (nis, ll, acc))
+        return base.belief_record(nis=nis, log_likelihood=ll, accepted=acc != 0, sub_filters=nis.shape[-2] if fused else None)
+
+    @staticmethod
+    def _stack_innovation_records(steps):
+        if not steps:
+            return None
+        return base.belief_record(sub_filters=steps[0].sub_filters,
+                                  **{k: torch.stack([getattr(s, k) for s in steps]) for k in ("nis", "log_likelihood", "accepted")})
+
+
+class VirtualSensorExtendedKalmanFilter(base.Filter, InnovationSwitches):
     """EKF whose measurement is a learned virtual sensor ``(z, R^1/2)`` observed through
     ``C = I`` (T2).  predict: ``S- = A S A^T + L L^T`` with ``A`` the dynamics Jacobian;
     correct: ``K = S-(S- + R)^-1``, ``mu = mu- + K(z - mu-)``, ``S = (I - K) S-``.
@@ -824,7 +890,9 @@ class VirtualSensorExtendedKalmanFilter(base.Filter):
     ``(N, d, d)`` after ``forward``, ``(T, N, d, d)`` after ``forward_loop`` (written by the native loop itself).
     ``record_history = True`` (evaluation mode): ``forward_loop`` leaves ``last_history`` -- ``means (T, N, d)``,
     ``covariances (T, N, d, d)`` and ``controls``, a reference to the controls it was given -- which ``smooth()`` turns into
-    the Rauch-Tung-Striebel smoothed belief; no other output of the loop changes by a bit."""
+    the Rauch-Tung-Striebel smoothed belief; no other output of the loop changes by a bit.
+    ``record_innovations`` / ``innovation_gate`` (evaluation mode): ``InnovationSwitches`` -- ``last_innovations`` with
+    ``nis``, ``log_likelihood`` and ``accepted``, ``(N,)`` after ``forward`` and ``(T, N)`` after ``forward_loop``."""
 
     default_smooth_method = "rts"  # what evaluation.run_filter smooths this filter with when no method is named
 
@@ -844,6 +912,7 @@ class VirtualSensorExtendedKalmanFilter(base.Filter):
         self.record_transition_moments = False  # smooth() also leaves the two-slice residual moments
         self.last_history = None
         self.last_smoothed = None
+        self._init_innovation_switches()
 
     def _record_step_belief(self):
         self.last_belief = base.belief_record(covariance=self._belief_covariance.detach()) if self.record_belief else None
@@ -894,13 +963,24 @@ class VirtualSensorExtendedKalmanFilter(base.Filter):
             N, d = mu_pred.shape
             mu = torch.empty((1, N, d), dtype=torch.float32, device=mu_pred.device)
             Sigma = self._belief_covariance.reshape(1, N, d, d).clone()
-            _abi.ekf_step(A.reshape(1, N, d, d), mu_pred.reshape(1, N, d), L.reshape(1, d, d).contiguous(),
-                          z.to(torch.float32).reshape(1, N, d).contiguous(),
-                          r_tril.to(torch.float32).reshape(1, N, d, d).contiguous(), None,
-                          mu, Sigma, None, None, fusion=0, feedback=0)
+            self._k3(A.reshape(1, N, d, d), mu_pred.reshape(1, N, d), L.reshape(1, d, d).contiguous(),
+                     z.to(torch.float32).reshape(1, N, d).contiguous(),
+                     r_tril.to(torch.float32).reshape(1, N, d, d).contiguous(), mu, Sigma)
             self._belief_mean, self._belief_covariance = mu[0], Sigma[0]
         self._record_step_belief()
         return self._belief_mean
+
+    def _k3(self, A, mu_pred, L, z, r_tril, mu, Sigma):
+        """K3 for this filter alone (K = 1, no fusion): ``mmf_ekf_step``, or with an innovation switch set
+        ``mmf_ekf_step_innov``, which also leaves ``last_innovations`` ``(N,)``."""
+        if not self._innovations_on():
+            self.last_innovations = None
+            _abi.ekf_step(A, mu_pred, L, z, r_tril, None, mu, Sigma, None, None, fusion=0, feedback=0)
+            return
+        buf = self._innovation_buffers(tuple(mu_pred.shape[:2]), mu_pred.device)
+        _abi.ekf_step_innov(A, mu_pred, L, z, r_tril, None, mu, Sigma, None, None, fusion=0, feedback=0,
+                            nis_gate=self._innovation_gate, nis=buf[0], loglik=buf[1], accepted=buf[2])
+        self.last_innovations = self._innovation_record(buf, fused=False)
 
     def _step_autograd(self, observations, controls):
         """Differentiable torch formulation (training backend "autograd")."""
@@ -935,6 +1015,7 @@ class VirtualSensorExtendedKalmanFilter(base.Filter):
     @engine.checked_step
     def forward(self, *, observations, controls):
         if use_autograd(self):
+            self._refuse_innovations_in_training()
             return self._step_autograd(observations, controls)
         return self._step(observations, controls)
 
@@ -955,7 +1036,10 @@ class VirtualSensorExtendedKalmanFilter(base.Filter):
         q = dyn.scale_tril().to(torch.float32).reshape(1, d, d).contiguous()
         keep = self.record_belief or self.record_history  # (the same Sigma_steps path for either)
         steps = torch.empty((T, N, d, d), dtype=torch.float32, device=mu.device) if keep else None
-        est, _ = engine.run_ekf_loop([dyn._net], [ctrl_all["bias"]], q, z, r, mu, Sigma, Sigma_steps=steps)
+        buf = self._innovation_buffers((T, 1, N), mu.device) if self._innovations_on() else None
+        est, _ = engine.run_ekf_loop([dyn._net], [ctrl_all["bias"]], q, z, r, mu, Sigma, Sigma_steps=steps,
+                                     innovations=buf, nis_gate=self._innovation_gate)
+        self.last_innovations = None if buf is None else self._innovation_record(buf, fused=False)
         self._belief_mean, self._belief_covariance = mu[0], Sigma[0]
         self.last_belief = base.belief_record(covariance=steps) if self.record_belief else None
         if self.record_history:
@@ -965,9 +1049,11 @@ class VirtualSensorExtendedKalmanFilter(base.Filter):
     @engine.checked_loop
     def forward_loop(self, *, observations, controls):
         self.last_history = None
+        self.last_innovations = None
         if use_autograd(self):
             if self.record_history:
                 raise RuntimeError("record_history: the training (autograd) paths keep no history; call .eval() first")
+            self._refuse_innovations_in_training()
             return base.Filter.forward_loop(self, observations=observations, controls=controls)
         T, N = tree_leading_shape(controls)[:2]
         flat = lambda t: t.reshape((T * N,) + tuple(t.shape[2:]))
@@ -981,15 +1067,18 @@ class VirtualSensorExtendedKalmanFilter(base.Filter):
                     self.last_history.controls = controls  # (a reference, not a copy) what smooth() predicts with
                 return native
             sensors = [self.virtual_sensor_model(observations=tree_index(observations, t)) for t in range(T)]
-        out, beliefs, covs = [], [], []
+        out, beliefs, covs, innovations = [], [], [], []
         for t in range(T):
             sl = slice(t * N, (t + 1) * N)
             out.append(self._step(tree_index(observations, t), tree_index(controls, t), sensors[t],
                                   None if ctrl_all is None else {k: v[sl] for k, v in ctrl_all.items()}))
             beliefs.append(self.last_belief)
             covs.append(self._belief_covariance)
+            innovations.append(self.last_innovations)
         if self.record_belief:
             self.last_belief = base.stack_belief_records(beliefs)
+        if self._innovations_on():
+            self.last_innovations = self._stack_innovation_records(innovations)
         est = torch.stack(out, dim=0)
         if self.record_history and T > 0:
             self.last_history = base.history_record(means=est, covariances=torch.stack(covs, dim=0), controls=controls)
@@ -1186,11 +1275,10 @@ class VirtualSensorUnscentedKalmanFilter(VirtualSensorExtendedKalmanFilter):
             eye = torch.eye(d, dtype=torch.float32, device=mu_pred.device)[None].expand(N, d, d).contiguous()
             mu = torch.empty((1, N, d), dtype=torch.float32, device=mu_pred.device)
             Sigma = Sigma_pred.reshape(1, N, d, d)
-            _abi.ekf_step(eye.reshape(1, N, d, d), mu_pred.reshape(1, N, d),
-                          torch.zeros((1, d, d), dtype=torch.float32, device=mu_pred.device),
-                          z.to(torch.float32).reshape(1, N, d).contiguous(),
-                          r_tril.to(torch.float32).reshape(1, N, d, d).contiguous(), None,
-                          mu, Sigma, None, None, fusion=0, feedback=0)
+            self._k3(eye.reshape(1, N, d, d), mu_pred.reshape(1, N, d),
+                     torch.zeros((1, d, d), dtype=torch.float32, device=mu_pred.device),
+                     z.to(torch.float32).reshape(1, N, d).contiguous(),
+                     r_tril.to(torch.float32).reshape(1, N, d, d).contiguous(), mu, Sigma)
             self._belief_mean, self._belief_covariance = mu[0], Sigma[0]
         self._record_step_belief()
         return self._belief_mean
@@ -1203,6 +1291,8 @@ class VirtualSensorUnscentedKalmanFilter(VirtualSensorExtendedKalmanFilter):
 
     @engine.checked_loop
     def forward_loop(self, *, observations, controls):
+        if use_autograd(self):
+            self._refuse_innovations_in_training()
         T, N = tree_leading_shape(controls)[:2]
         flat = lambda t: t.reshape((T * N,) + tuple(t.shape[2:]))
         with torch.no_grad():
@@ -1214,15 +1304,19 @@ class VirtualSensorUnscentedKalmanFilter(VirtualSensorExtendedKalmanFilter):
                 sensors = [(z[t * N:(t + 1) * N], r[t * N:(t + 1) * N]) for t in range(T)]
             else:
                 sensors = [self.virtual_sensor_model(observations=tree_index(observations, t)) for t in range(T)]
-        out, beliefs = [], []
+        out, beliefs, innovations = [], [], []
         not_pd = torch.zeros(1, dtype=torch.int32, device=self._belief_mean.device)  # one flag, one read per loop
+        self.last_innovations = None
         for t in range(T):
             sl = slice(t * N, (t + 1) * N)
             out.append(self._step(tree_index(observations, t), tree_index(controls, t), sensors[t],
                                   None if ctrl_all is None else {k: v[sl] for k, v in ctrl_all.items()}, not_pd))
             beliefs.append(self.last_belief)
+            innovations.append(self.last_innovations)
         if self.record_belief:  # the per-step posterior covariances, stacked on the device
             self.last_belief = base.stack_belief_records(beliefs)
+        if self._innovations_on():
+            self.last_innovations = self._stack_innovation_records(innovations)
         if T > 0 and int(not_pd.item()):
             raise ValueError("unscented predict: belief covariance is not positive definite")
         return torch.stack(out, dim=0)
