@@ -849,6 +849,66 @@ int mmf_pf_smooth_pair_moments(const MmfPfSmoothPairArgs* args /* host */, void*
 /* Floats of the workspace above: (T - 1) N ceil(M / 64) (1 + d + d (d + 1) / 2); 0 for T < 2, N < 1 or sizes outside the limits. */
 size_t mmf_pf_smooth_pair_workspace_floats(int T, int N, int M, int d);
 
+/* ---------------------------------------------------------------- MAP path smoothing (Viterbi over the particle history)
+ * The smoothers above return moments or random draws.  None returns the single most probable state SEQUENCE, which is the
+ * estimate to report where the posterior is multimodal (is the door open or closed?): the smoothed mean lies between the
+ * modes, in a state the system was never in, and a backward-simulation draw is a legitimate path but a random one.  This is
+ * the MAP sequence estimate over the particle grid of Godsill, Doucet & West (2001): a max-plus (Viterbi) recursion over the
+ * same M^2 particle pairs per trajectory and step that the marginal smoother walks.  Upstream torchfilter's ParticleFilter
+ * has no smoother; in torch ops the recursion materialises an (M, M, d) tensor per trajectory and step.  Purely additive to
+ * ABI 42: a struct and a symbol of its own.
+ * From a history of T steps, as for mmf_pf_smooth_marginal: X_t (N, M, d), F_t[i] = f(X_t[i], u_{t+1}), t = 0 .. T - 2
+ * (pred_steps), loglik_t, L the one lower-triangular scale_tril; and logw_in_0, of step 0 ONLY: the particles' own incoming
+ * log-weights stand in for log p(x_0) (null: 0; after initialize_beliefs they are uniform, a flat prior over the step-0 set).
+ * The incoming weights of later steps are the filter's importance weights and enter no density.  Natural logarithms, with
+ * c = sum_k log L_kk + (d / 2) log 2 pi:
+ *   lp_t[i, j]  = -1/2 || L^-1 (X_{t+1}[j] - F_t[i]) ||^2        (the difference first, then whitened: the marginal smoother's rule)
+ *   v_0[j]      = loglik_0[j] + logw_in_0[j]
+ *   top_t       = max_j v_t[j]                                    (exact: a maximum has no rounding)
+ *   v_t[j]      = loglik_t[j] + max_i( (v_{t-1}[i] - top_{t-1}) + lp_{t-1}[i, j] )        t >= 1
+ *   psi_t[j]    = the FIRST i attaining that maximum (ties to the lower index);  psi_0 = -1
+ *   i_{T-1}     = first argmax_j v_{T-1}[j];   i_t = psi_{t+1}[i_{t+1}]
+ *   path[t]     = X_t[i_t]
+ *   log_posterior = sum_t top_t - (T - 1) c   =   v_0[i_0] + sum_{t >= 1} ( loglik_t[i_t] + lp_{t-1}[i_{t-1}, i_t] - c )
+ * The rescaling by top_{t-1} is part of the definition: without it v grows to 1e5 .. 1e6 over a run (whitened distances are
+ * 20 .. 200) and fp32 no longer resolves the decisions.
+ * A particle with loglik = -inf (dead, or the padding of a step with fewer particles) has v = -inf, psi = -1 and is never
+ * chosen; whatever its rows of X / F hold is not read.  A column none of whose candidates is above -inf is dead likewise.  A
+ * trajectory with a step where every particle is dead gets indices = -1, a NaN path and log_posterior = -inf; the reads stay
+ * in range and nothing faults, and the other trajectories of the call are unaffected.  A non-positive or non-finite diagonal
+ * of L makes every floating output NaN and every index -1.
+ * Launches behind the one call: step 0 element-wise; the forward pass, T - 1 launches over (column tile of 64, trajectory),
+ * t = 1 .. T - 1, on the plan of the marginal smoother's logD kernel (a wave per workgroup, a thread owns a column j of step t,
+ * the rows i of step t - 1 -- F_{t-1}[i] and v_{t-1}[i] - top_{t-1} -- stream through LDS in chunks of fixed size and are
+ * consumed in groups of 8: the group's maximum first, the index resolved only where the group improves the running maximum,
+ * strictly, so that the first index wins across groups, chunks and tiles); every workgroup takes top_{t-1} of its trajectory
+ * itself (M reads) and the first one stores it into step_max; the backtrack, one wave per trajectory: the first maximum of
+ * v_{T-1}, one lane walks psi backwards, writes indices and path and sums top_t in ascending t.  LDS use does not depend on
+ * M.  The recursion has no exp and no log; inside the forward kernel the values live in base 2 (the shared whitener's
+ * scaling), every output is in natural logarithms.  No float atomics, no contraction left to the compiler outside the shared
+ * whitener: two calls give the same bits, and trajectory n's outputs do not depend on N.
+ * v, step_max and backpointers are outputs as defined above, not scratch.
+ * Limits: 1 <= d <= 4, 1 <= M <= 65536, N <= 65535, beyond -> MMF_ETOOLARGE.  A null args / states_steps / loglik_steps /
+ * scale_tril / v / step_max / backpointers / indices / path / log_posterior, a null pred_steps with T >= 2, T < 0, N < 0,
+ * M < 1 or d < 1 -> MMF_EINVAL (an invalid call is invalid whatever its size); an output that overlaps an input or another
+ * output -> MMF_EINVAL.  N == 0 or T == 0 is a successful no-op; T == 1 runs step 0 and the backtrack only.  All decided on
+ * the host before any HIP call. */
+typedef struct MmfPfSmoothMapArgs {
+  int32_t T, N, M, d;
+  const float* states_steps;        /* (T, N, M, d)     X_t                                                  */
+  const float* pred_steps;          /* (T - 1, N, M, d) F_t; unread (may be null) for T < 2                  */
+  const float* loglik_steps;        /* (T, N, M)                                                             */
+  const float* logw_in_steps;       /* (T, N, M) or null = 0; only step 0 is read                            */
+  const float* scale_tril;          /* (d, d) DEVICE, row-major; the upper triangle is not read              */
+  float* v;                         /* (T, N, M)    v_t                                                      */
+  float* step_max;                  /* (T, N)       top_t                                                    */
+  int32_t* backpointers;            /* (T, N, M)    psi_t                                                    */
+  int32_t* indices;                 /* (T, N)       i_t, -1 where the trajectory is dead                     */
+  float* path;                      /* (T, N, d)    X_t[n, i_t]                                              */
+  float* log_posterior;             /* (N)                                                                   */
+} MmfPfSmoothMapArgs;               /* host struct holding device pointers */
+int mmf_pf_smooth_map(const MmfPfSmoothMapArgs* args /* host */, void* stream);
+
 /* ---------------------------------------------------------------- K6, fused: one network call of the training backward
  * Recompute (the forward pass's f16x3 arithmetic), backward data path and weight / bias gradients of ONE per-particle
  * network over N * M rows in one kernel (the dynamics network: three launches -- encoder forward, trunk, encoder

@@ -128,6 +128,13 @@ class MmfPfSmoothPairArgs(Structure):
                 ("residual_mean", _FP), ("residual_second_moment", _FP)]
 
 
+class MmfPfSmoothMapArgs(Structure):
+    _fields_ = [("T", c_int32), ("N", c_int32), ("M", c_int32), ("d", c_int32),
+                ("states_steps", _FP), ("pred_steps", _FP), ("loglik_steps", _FP), ("logw_in_steps", _FP),
+                ("scale_tril", _FP), ("v", _FP), ("step_max", _FP), ("backpointers", _FP), ("indices", _FP),
+                ("path", _FP), ("log_posterior", _FP)]
+
+
 class MmfTrainNet(Structure):
     _fields_ = [("packed", _FP), ("packed_f32", _FP), ("packed_t", _FP), ("head_w", _FP), ("pw", _FP), ("pb", _FP),
                 ("p_first", _FP), ("p_head", _FP), ("p_dout", _FP), ("p_traj", _FP), ("packed_dual", _FP)]
@@ -228,6 +235,7 @@ SIGNATURES = {
     "mmf_pf_smooth_simulate": (c_int, [POINTER(MmfPfSmoothSimulateArgs), c_void_p]),
     "mmf_pf_smooth_pair_moments": (c_int, [POINTER(MmfPfSmoothPairArgs), c_void_p]),
     "mmf_pf_smooth_pair_workspace_floats": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "mmf_pf_smooth_map": (c_int, [POINTER(MmfPfSmoothMapArgs), c_void_p]),
     "mmf_pf_dedup_plan": (c_int, [c_int, c_int, c_int, ctypes.c_float, c_int]),
     "mmf_pf_dedup_workspace_words": (c_size_t, [c_int, c_int]),
     "mmf_pf_resample_runs": (c_int, [_FP] * 11 + [c_int, c_int, c_int, _FP, _FP, _FP, c_void_p]),
@@ -1047,3 +1055,29 @@ def pf_smooth_simulate(states_steps, pred_steps, loglik_steps, logw_in_steps, sc
     a.trajectories, a.mean, a.cov = vp(trajectories), vp(mean), vp(cov)
     with _on(states_steps):
         _check(load().mmf_pf_smooth_simulate(ctypes.byref(a), stream_of(states_steps)), "mmf_pf_smooth_simulate")
+
+
+def pf_smooth_map(states_steps, pred_steps, loglik_steps, logw_in_steps, scale_tril, indices, path, log_posterior, v=None,
+                  step_max=None, backpointers=None):
+    """MAP path smoothing of a filter run's history (``mmf_pf_smooth_map``, include/mmf.h): ``states_steps (T, N, M, d)``,
+    ``pred_steps (T - 1, N, M, d)`` the dynamics means ``f(X_t, u_{t+1})`` (``None`` allowed for ``T < 2``),
+    ``loglik_steps (T, N, M)``, ``logw_in_steps (T, N, M)`` or ``None`` (step 0 alone is read: the prior over the step-0 set),
+    ``scale_tril (d, d)`` on the device -> ``indices (T, N)`` int32, ``path (T, N, d)``, ``log_posterior (N)``.  ``v (T, N, M)``,
+    ``step_max (T, N)`` and ``backpointers (T, N, M)`` int32 -- the recursion's values, their per-step maxima and its
+    decisions -- are allocated when ``None``."""
+    T, N, M, d = states_steps.shape
+    dev = states_steps.device
+    assert indices.shape == (T, N) and path.shape == (T, N, d) and log_posterior.shape == (N,)
+    if v is None:
+        v = torch.empty((T, N, M), dtype=torch.float32, device=dev)
+    if step_max is None:
+        step_max = torch.empty((T, N), dtype=torch.float32, device=dev)
+    if backpointers is None:
+        backpointers = torch.empty((T, N, M), dtype=torch.int32, device=dev)
+    assert v.shape == (T, N, M) and step_max.shape == (T, N) and backpointers.shape == (T, N, M)
+    a = MmfPfSmoothMapArgs()
+    _smooth_history(a, states_steps, pred_steps, loglik_steps, logw_in_steps, scale_tril)
+    a.v, a.step_max, a.backpointers = vp(v), vp(step_max), vp(backpointers, torch.int32)
+    a.indices, a.path, a.log_posterior = vp(indices, torch.int32), vp(path), vp(log_posterior)
+    with _on(states_steps):
+        _check(load().mmf_pf_smooth_map(ctypes.byref(a), stream_of(states_steps)), "mmf_pf_smooth_map")

@@ -38,7 +38,9 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
     ``lag``), ``"ancestry"`` for every filter that names none, the particle filter included; ``"marginal"`` smooths also where ``smooth_lag`` is left at ``False``
     (it is the full smoother: ``smooth_lag`` must be ``False`` or ``None``) and leaves ``covariance``, ``ess``, ``weights``;
     ``"simulation"`` likewise, with ``smooth_draws`` joint paths per trajectory (``smooth(num_draws=)``, default 64; passing it with
-    another method is the ``ValueError`` it is there), and leaves ``covariance``, ``trajectories``, ``indices``, ``num_draws``.
+    another method is the ``ValueError`` it is there), and leaves ``covariance``, ``trajectories``, ``indices``, ``num_draws``;
+    ``"map"`` likewise returns the most probable particle PATH ``(T, N, d)`` and leaves ``indices``, ``log_posterior`` and no
+    ``covariance`` (a path is not a distribution: ``gaussian_nll`` / ``nees`` / ``coverage`` do not apply).
     ``smooth_transition_moments``: smooths with the filter's ``record_transition_moments`` set (and puts the switch back) -- with ``smooth_method="marginal"`` or ``"rts"`` alone, refused
     before the run otherwise; the record gains ``residual_mean`` and ``residual_second_moment`` (``process_noise_m_step``).
     ``return_innovations``: runs a Kalman filter with ``record_innovations`` set (and puts the switch back) and appends
@@ -111,6 +113,47 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
     if return_innovations:
         return (out if isinstance(out, tuple) else (out,)) + (innovations,)
     return out
+
+
+def path_log_density(filter_model, indices) -> torch.Tensor:
+    """The joint log-density of index paths through ``filter_model.last_history`` -- ``log_posterior`` of
+    ``smooth(method="map")`` by its definition (``include/mmf.h``, "MAP path smoothing"): for ``indices (T, N)`` or
+    ``(T, N, S)`` integers ``i_t`` into the particles of step ``t``,
+    ``v_0[i_0] + sum_{t >= 1} (loglik_t[i_t] - 1/2 |L^-1 (X_t[i_t] - F_{t-1}[i_{t-1}])|^2 - c)`` with
+    ``v_0 = loglik_0 + logw_in_0`` and ``c = sum_k log L_kk + (d / 2) log 2 pi`` -> ``(N,)`` or ``(N, S)`` float64.  Float64
+    torch ops on the chosen pairs only, ``O(T N S d^2)`` beside one evaluation of the dynamics means: no ``M^2``.  A path
+    with a ``-1`` anywhere (a dead draw of ``method="simulation"``, a dead trajectory of ``method="map"``) gets ``-inf``.
+    It compares the MAP path with the paths ``smooth(method="simulation")`` drew (``last_smoothed.indices``) and with the
+    filter's ancestral lines."""
+    h = getattr(filter_model, "last_history", None)
+    if h is None or getattr(h, "states", None) is None:
+        raise ValueError("path_log_density needs a particle history: set record_history and run forward_loop first")
+    idx = torch.as_tensor(indices)
+    if idx.dtype in (torch.bool,) or idx.is_floating_point() or idx.is_complex():
+        raise ValueError(f"path_log_density: indices must be integers, got {idx.dtype}")
+    T, N, M, d = h.states.shape
+    if idx.dim() not in (2, 3) or tuple(idx.shape[:2]) != (T, N):
+        raise ValueError(f"path_log_density: indices must be (T, N) or (T, N, S) = ({T}, {N}[, S]), got {tuple(idx.shape)}")
+    single = idx.dim() == 2
+    idx = (idx[..., None] if single else idx).to(device=h.states.device, dtype=torch.int64)
+    if bool(((idx < -1) | (idx >= M)).any()):
+        raise ValueError(f"path_log_density: indices must lie in -1 .. {M - 1}")
+    dead = (idx < 0).any(dim=0)
+    g = idx.clamp_min(0)
+    take = lambda rows, k: torch.gather(rows.to(torch.float64), 2, k[..., None].expand(k.shape + (d,)))
+    with torch.no_grad():
+        pred, tril = filter_model._smoothing_transition(h, "map")
+        total = torch.gather(h.log_likelihoods.to(torch.float64), 2, g).sum(dim=0)
+        if h.log_weights_in is not None:
+            total = total + torch.gather(h.log_weights_in[0].to(torch.float64), 1, g[0])
+        if T > 1:
+            L = torch.tril(tril.to(torch.float64))
+            e = take(h.states[1:], g[1:]) - take(pred, g[:-1])
+            z = torch.linalg.solve_triangular(L, e[..., None], upper=False)[..., 0]
+            c = torch.log(torch.diagonal(L)).sum() + 0.5 * d * math.log(2.0 * math.pi)
+            total = total + (-0.5 * (z * z).sum(-1) - c).sum(dim=0)
+        total = torch.where(dead, torch.full_like(total, -math.inf), total)
+    return total[:, 0] if single else total
 
 
 def innovation_summary(record, dim: int) -> Dict[str, torch.Tensor]:

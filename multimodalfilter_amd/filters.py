@@ -640,12 +640,15 @@ class ParticleFilter(base.Filter):
         by backward simulation (``_smooth_simulation``); returns their mean, ``lag`` must be ``None``.  It draws
         ``(T, N, num_draws)`` uniforms from ``self.noise`` and so ADVANCES the filter's noise stream.  ``num_draws`` belongs
         to this method alone.
+        ``method = "map"``: the single most probable index path through the particle history instead (``_smooth_map``): a
+        ``(T, N, d)`` PATH of particles, not a mean; ``lag`` must be ``None``.  Its record has no ``covariance`` -- a path is
+        not a distribution, so ``evaluation.gaussian_nll`` / ``nees`` / ``coverage`` do not apply to it.
         With ``self.record_transition_moments`` set (``method = "marginal"`` alone; any other method is a ``ValueError``):
         also the two-slice moments of the transition residual ``X_{t+1} - f(X_t, u_{t+1})`` -- ``last_smoothed`` gains
         ``residual_mean (T - 1, N, d)`` and ``residual_second_moment (T - 1, N, d, d)``, what
         ``evaluation.process_noise_m_step`` refits the process noise from."""
-        if method not in ("ancestry", "marginal", "simulation"):
-            raise ValueError(f"smooth: method must be 'ancestry', 'marginal' or 'simulation', got {method!r}")
+        if method not in ("ancestry", "marginal", "simulation", "map"):
+            raise ValueError(f"smooth: method must be 'ancestry', 'marginal', 'simulation' or 'map', got {method!r}")
         if method != "ancestry" and lag is not None:
             raise ValueError(f"smooth(method={method!r}) is the full smoother: a fixed-lag {method} smoother is not implemented")
         if method != "simulation" and num_draws is not _DEFAULT_DRAWS:
@@ -662,6 +665,8 @@ class ParticleFilter(base.Filter):
             return self._smooth_marginal(h, transition_moments)
         if method == "simulation":
             return self._smooth_simulation(h, num_draws)
+        if method == "map":
+            return self._smooth_map(h)
         assert lag is None or int(lag) >= 0, "lag must be >= 0 (None: the full smoother)"
         T, N, M, d = h.states.shape
         dev = h.states.device
@@ -762,6 +767,28 @@ class ParticleFilter(base.Filter):
         self.last_smoothed = base.belief_record(covariance=cov, trajectories=trajectories, indices=indices, num_draws=S,
                                                 lag=None, method="simulation")
         return mean
+
+    def _smooth_map(self, h) -> torch.Tensor:
+        """MAP path smoothing (``mmf_pf_smooth_map``, ``include/mmf.h``; Godsill, Doucet & West 2001): the most probable
+        sequence of particles ``X_0[i_0], .., X_{T-1}[i_{T-1}]`` under ``p(x_0) prod_t p(y_t | x_t) N(x_t; f(x_{t-1}, u_t),
+        L L^T)`` restricted to the particle grid, by a max-plus (Viterbi) recursion over the ``(T - 1) N M^2`` particle pairs;
+        the incoming log-weights of step 0 stand in for ``log p(x_0)``.  No ancestors are read, so every resampling mode is
+        covered, and no noise is drawn: the filter's noise stream does not move.  Returns the ``(T, N, d)`` path -- a state
+        the filter did hold at every step, where a smoothed mean may lie between two modes -- and leaves ``last_smoothed``:
+        ``indices (T, N)`` int32 (``-1``, with a NaN path, where a step left no particle alive), ``log_posterior (N,)`` the
+        joint log-density of the path (``evaluation.path_log_density`` of ``indices``), ``lag = None``, ``method = "map"``.
+        There is NO ``covariance``: a path is not a distribution, and ``evaluation.gaussian_nll`` / ``nees`` / ``coverage``
+        do not apply."""
+        T, N, M, d = h.states.shape
+        dev = h.states.device
+        with torch.no_grad():
+            pred, tril = self._smoothing_transition(h, "map")
+            indices = torch.empty((T, N), dtype=torch.int32, device=dev)
+            path = torch.empty((T, N, d), dtype=torch.float32, device=dev)
+            log_posterior = torch.empty((N,), dtype=torch.float32, device=dev)
+            _abi.pf_smooth_map(h.states, pred, h.log_likelihoods, h.log_weights_in, tril, indices, path, log_posterior)
+        self.last_smoothed = base.belief_record(indices=indices, log_posterior=log_posterior, lag=None, method="map")
+        return path
 
     @engine.checked_step
     def forward(self, *, observations, controls) -> torch.Tensor:
