@@ -909,6 +909,56 @@ typedef struct MmfPfSmoothMapArgs {
 } MmfPfSmoothMapArgs;               /* host struct holding device pointers */
 int mmf_pf_smooth_map(const MmfPfSmoothMapArgs* args /* host */, void* stream);
 
+/* ---------------------------------------------------------------- Particle-posterior quantiles, credible intervals and PIT
+ * Upstream torchfilter's ParticleFilter leaves particle_states / particle_log_weights to the caller, and the evaluation of
+ * crossmodal/eval_helpers.py:148-160 judges the posterior mean alone.  Everything above that judges the belief is Gaussian
+ * (a covariance, NEES, the moment-matched ellipsoid); for a bimodal set the ellipsoid covers the empty ground between the
+ * modes.  This is the non-parametric counterpart: per-dimension weighted quantiles of a particle set (median, credible
+ * intervals) and the weighted CDF at a query point (the probability integral transform of the true state), on K1's integer
+ * fixed-point weights.  In torch ops it is sort + cumsum + searchsorted + gather over (R, M, d), with an fp32 cumulative sum
+ * whose crossings depend on the summation order.  Purely additive to ABI 42: a struct and two symbols of their own.
+ * Per row r (R rows, e.g. T * N, of M particles) and state dimension k, with x_m = states[r, m, k]:
+ *   a_m   = log_a[r, m] + log_b[r, m]      one fp32 add; a null addend is 0, both null: uniform weights
+ *   t_m   = a_m - max_m a_m                one fp32 subtract (the maximum skips NaN);  e_m = expf(t_m)
+ *   q_m   = (uint32) floor(e_m * 2^24)     in [0, 2^24]: K1's fixed point.  a_m = -inf or NaN gives q_m = 0 exactly: such a
+ *                                          particle is never returned, whatever its state row holds (the histories carry NaN
+ *                                          rows for dead particles).  Particles below 2^-24 of the row's heaviest count as
+ *                                          weightless, as in K1.
+ *   Qtot  = sum_m q_m                      64-bit integers.  A row without a live particle (max a is -inf, NaN or +inf, i.e.
+ *                                          Qtot = 0) gives NaN quantiles and a NaN cdf.
+ *   quantile p:  the particles ascending by x_m, c_j the inclusive integer sums of q in that order,
+ *                thr = max(1, ceil((double) p * (double) Qtot));  the result is the x of the first j with c_j >= thr -- the
+ *                inverted weighted CDF, always a particle's own value, bit for bit.  p = 0: the smallest particle with q > 0;
+ *                p = 1: the largest.  (Equal x may sort in any order: the integer CDF at the end of a tie group is the same.)
+ *   cdf[r, k]  = (float) ((double) sum_{m : x_m <= query[r, k]} q_m / (double) Qtot);  a NaN query gives NaN.
+ * Every sum is an integer sum, so the result does not depend on thread count, scan order or R:
+ *   - two calls give the same bits;
+ *   - a row computed alone (R = 1) has the bits it has in a batch;
+ *   - with equal weights the quantile is sort(x)[max(1, ceil(p M)) - 1] exactly and the cdf is count / M rounded once.
+ * One launch: a workgroup per (row, dimension) packs (order-preserving uint32 key of x) << 32 | q into one uint64 per
+ * particle in LDS, padded to the next power of two P >= max(M, 64) with all-ones keys of weight 0, sorts them (bitonic; a
+ * thread owns P / threads consecutive slots and runs the short strides in registers), scans q in integers and searches once
+ * per p.  The cdf sum is a reduction before the sort: Q == 0 with a query does not sort.  One wave for P <= 512, 256 threads
+ * beyond.  mmf_pf_quantiles_lds_bytes(M): the dynamic LDS of that workgroup, 8 B per padded slot and one spare slot per thread
+ * -- monotone in M, at most 160 KiB at the limit M = 16384 (for M beyond it: the value at the limit; 0 for M < 1).
+ * Limits, all decided on the host before any HIP call: null args / states, d outside 1 .. 4, M < 1, R < 0, Q outside
+ * 0 .. MMF_QUANTILES_MAX, a p outside [0, 1] or NaN, nothing requested (Q == 0 and no query), quantiles null with Q > 0 (with
+ * Q == 0 it is not written), exactly one of query / cdf null, an output overlapping an input or the other output -> MMF_EINVAL;
+ * M > 16384 or R * d beyond a 32-bit grid -> MMF_ETOOLARGE; R == 0 is a successful no-op. */
+#define MMF_QUANTILES_MAX 16
+typedef struct MmfPfQuantilesArgs {
+  int32_t R, M, d, Q;             /* R rows (e.g. T*N) of M particles; Q in 0 .. MMF_QUANTILES_MAX */
+  float probs[MMF_QUANTILES_MAX]; /* host values, each in [0, 1] */
+  const float* states;            /* (R, M, d) */
+  const float* log_a;             /* (R, M) or null = 0 */
+  const float* log_b;             /* (R, M) or null = 0 (history: log_weights_in + log_likelihoods) */
+  const float* query;             /* (R, d) or null */
+  float* quantiles;               /* (R, Q, d); null iff Q == 0 */
+  float* cdf;                     /* (R, d); null iff query is null */
+} MmfPfQuantilesArgs;             /* host struct holding device pointers */
+int mmf_pf_quantiles(const MmfPfQuantilesArgs* args /* host */, void* stream);
+size_t mmf_pf_quantiles_lds_bytes(int M);
+
 /* ---------------------------------------------------------------- K6, fused: one network call of the training backward
  * Recompute (the forward pass's f16x3 arithmetic), backward data path and weight / bias gradients of ONE per-particle
  * network over N * M rows in one kernel (the dynamics network: three launches -- encoder forward, trunk, encoder

@@ -135,6 +135,15 @@ class MmfPfSmoothMapArgs(Structure):
                 ("path", _FP), ("log_posterior", _FP)]
 
 
+QUANTILES_MAX = 16    # MMF_QUANTILES_MAX
+QUANTILES_MAX_M = 16384  # particles per row that mmf_pf_quantiles sorts in LDS
+
+
+class MmfPfQuantilesArgs(Structure):
+    _fields_ = [("R", c_int32), ("M", c_int32), ("d", c_int32), ("Q", c_int32), ("probs", ctypes.c_float * QUANTILES_MAX),
+                ("states", _FP), ("log_a", _FP), ("log_b", _FP), ("query", _FP), ("quantiles", _FP), ("cdf", _FP)]
+
+
 class MmfTrainNet(Structure):
     _fields_ = [("packed", _FP), ("packed_f32", _FP), ("packed_t", _FP), ("head_w", _FP), ("pw", _FP), ("pb", _FP),
                 ("p_first", _FP), ("p_head", _FP), ("p_dout", _FP), ("p_traj", _FP), ("packed_dual", _FP)]
@@ -236,6 +245,8 @@ SIGNATURES = {
     "mmf_pf_smooth_pair_moments": (c_int, [POINTER(MmfPfSmoothPairArgs), c_void_p]),
     "mmf_pf_smooth_pair_workspace_floats": (c_size_t, [c_int, c_int, c_int, c_int]),
     "mmf_pf_smooth_map": (c_int, [POINTER(MmfPfSmoothMapArgs), c_void_p]),
+    "mmf_pf_quantiles": (c_int, [POINTER(MmfPfQuantilesArgs), c_void_p]),
+    "mmf_pf_quantiles_lds_bytes": (c_size_t, [c_int]),
     "mmf_pf_dedup_plan": (c_int, [c_int, c_int, c_int, ctypes.c_float, c_int]),
     "mmf_pf_dedup_workspace_words": (c_size_t, [c_int, c_int]),
     "mmf_pf_resample_runs": (c_int, [_FP] * 11 + [c_int, c_int, c_int, _FP, _FP, _FP, c_void_p]),
@@ -1081,3 +1092,37 @@ def pf_smooth_map(states_steps, pred_steps, loglik_steps, logw_in_steps, scale_t
     a.indices, a.path, a.log_posterior = vp(indices, torch.int32), vp(path), vp(log_posterior)
     with _on(states_steps):
         _check(load().mmf_pf_smooth_map(ctypes.byref(a), stream_of(states_steps)), "mmf_pf_smooth_map")
+
+
+def pf_quantiles_lds_bytes(M: int) -> int:
+    return int(load().mmf_pf_quantiles_lds_bytes(int(M)))
+
+
+def pf_quantiles(states, log_a, log_b, probs, quantiles, query=None, cdf=None):
+    """Weighted quantiles and the weighted CDF of particle sets on the integer fixed-point weights of K1
+    (``mmf_pf_quantiles``, include/mmf.h): ``states (..., M, d)`` -- ``R`` rows, the product of the leading sizes -- with
+    log-weights ``log_a + log_b``, each ``(..., M)`` or ``None`` (0; both ``None``: uniform), and ``probs``, up to 16 host
+    floats in ``[0, 1]`` -> ``quantiles (..., Q, d)`` (``None`` allowed for an empty ``probs``; not written then).  ``query
+    (..., d)`` with ``cdf (..., d)``, both or neither: the weighted share of the particles at or below the query, per
+    dimension."""
+    lead, (M, d) = tuple(states.shape[:-2]), states.shape[-2:]
+    R = 1
+    for n in lead:
+        R *= int(n)
+    probs = [float(p) for p in probs]
+    Q = len(probs)
+    if Q > QUANTILES_MAX:
+        raise MmfError(f"mmf_pf_quantiles takes at most {QUANTILES_MAX} probabilities, got {Q}")
+    assert log_a is None or tuple(log_a.shape) == lead + (M,)
+    assert log_b is None or tuple(log_b.shape) == lead + (M,)
+    assert quantiles is None or tuple(quantiles.shape) == lead + (Q, d)
+    assert (query is None) == (cdf is None)
+    assert query is None or (tuple(query.shape) == lead + (d,) and tuple(cdf.shape) == lead + (d,))
+    a = MmfPfQuantilesArgs()
+    a.R, a.M, a.d, a.Q = R, M, d, Q
+    for i, p in enumerate(probs):
+        a.probs[i] = p
+    a.states, a.log_a, a.log_b, a.query = vp(states), vp(log_a), vp(log_b), vp(query)
+    a.quantiles, a.cdf = vp(quantiles), vp(cdf)
+    with _on(states):
+        _check(load().mmf_pf_quantiles(ctypes.byref(a), stream_of(states)), "mmf_pf_quantiles")

@@ -1,0 +1,311 @@
+// Weighted quantiles and the weighted CDF of a particle set, per row and state dimension (include/mmf.h, "Particle-posterior
+// quantiles"): K1's integer fixed-point weights q_m = floor(exp(a_m - max a) 2^24), so that every sum is an integer sum and the
+// selection does not depend on the thread count, the scan order or the number of rows.  One kernel, one workgroup per
+// (row, dimension):
+//   weights    a = log_a + log_b held in registers, the row maximum (exact in any order), q_m
+//   cdf        the integer sum of q_m over x_m <= query, reduced before the sort; Q == 0 ends here
+//   keys       (order-preserving uint32 of x_m) << 32 | q_m, one uint64 per particle in LDS, padded to P = 2^k >= M with
+//              all-ones keys of weight 0
+//   sort       bitonic over the P uint64s: a thread owns E = P / THREADS consecutive slots; the stages whose stride is below E
+//              run in its registers, the others through LDS.  Slot i lives at i + i / E: the E-slot runs of neighbouring lanes
+//              start 8 (E + 1) bytes apart, an odd number of 8-byte bank pairs, so the run loads and stores are conflict-free
+//   scan       thread sums, the wave scan of K1 (mmf::wave_inclusive_scan), wave totals through LDS
+//   search     per p: thr = max(1, ceil(p Qtot)) in double; the one thread whose run crosses thr walks it and stores the value
+// The weights are recomputed by each of the d workgroups of a row (M reads, M exp beside a sort of P log^2 P compare-exchanges).
+
+#include <cmath>
+
+#include "mmf_launch.h"
+
+namespace {
+
+using u64 = unsigned long long;
+
+constexpr int kMaxM = 16384;
+constexpr int kMaxWaves = 4;
+constexpr u64 kPadKey = 0xFFFFFFFF00000000ull;
+
+struct QArgs {
+  const float* states;  // (R, M, d)
+  const float* log_a;   // (R, M) or null
+  const float* log_b;   // (R, M) or null
+  const float* query;   // (R, d) or null
+  float* quantiles;     // (R, Q, d) or null
+  float* cdf;           // (R, d) or null
+  int M, d, Q;
+  float probs[MMF_QUANTILES_MAX];
+};
+
+// threads and slots per thread of the workgroup that sorts M particles: one wave up to P = 512 (8 slots per lane), 256 threads
+// beyond.  Measured at P = 512 on the 32 x 300 x 100 history: 256 threads x 2 slots 0.083 ms, 128 x 4 0.076 ms, 64 x 8 0.067 ms;
+// at P = 4096: 256 x 16 0.162 ms, 128 x 32 0.214 ms, 64 x 64 0.314 ms (profiles/quantiles/README.md)
+struct Plan {
+  int threads, E;
+};
+inline Plan plan_of(int M) {
+  int P = MMF_WAVE;
+  while (P < M) P <<= 1;
+  const int threads = P <= 8 * MMF_WAVE ? MMF_WAVE : 256;
+  return {threads, P / threads};
+}
+inline size_t slots_of(const Plan& p) {
+  return static_cast<size_t>(p.threads) * p.E + (p.E > 1 ? p.threads : 0);  // the padding slot after every run of E
+}
+
+// a total order on the bit patterns that agrees with < on the numbers: negatives inverted, the others with the sign bit set
+__device__ __forceinline__ unsigned key_of(float x) {
+  const unsigned b = __float_as_uint(x);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float value_of(unsigned k) {
+  return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
+}
+
+template <int E>
+__device__ __forceinline__ int slot(int i) {
+  return E > 1 ? i + i / E : i;
+}
+
+template <int THREADS>
+__device__ __forceinline__ float block_max(float v, float* scratch, int tid) {
+  v = mmf::wave_max(v);
+  if constexpr (THREADS > MMF_WAVE) {
+    if ((tid & (MMF_WAVE - 1)) == 0) scratch[tid / MMF_WAVE] = v;
+    __syncthreads();
+    v = scratch[0];
+#pragma unroll
+    for (int w = 1; w < THREADS / MMF_WAVE; ++w) v = fmaxf(v, scratch[w]);
+    __syncthreads();
+  }
+  return v;
+}
+
+// inclusive scan of per-thread values below 2^40 over the workgroup, and its total
+template <int THREADS>
+__device__ __forceinline__ u64 block_scan(u64 v, u64* scratch, int tid, u64& total) {
+  const int lane = tid & (MMF_WAVE - 1), wave = tid / MMF_WAVE;
+  u64 incl = mmf::wave_inclusive_scan(v, lane);
+  if (lane == MMF_WAVE - 1) scratch[wave] = incl;
+  __syncthreads();
+  total = 0;
+#pragma unroll
+  for (int w = 0; w < THREADS / MMF_WAVE; ++w) {
+    const u64 t = scratch[w];
+    if (w < wave) incl += t;
+    total += t;
+  }
+  __syncthreads();
+  return incl;
+}
+
+// the stages of phase k whose stride is jmax, jmax / 2, .. 1, all below E: inside the E consecutive slots from `base`
+template <int E>
+__device__ __forceinline__ void local_stages(u64 (&v)[E], int base, int k, int jmax) {
+#pragma unroll
+  for (int j = E / 2; j >= 1; j >>= 1) {
+    if (j > jmax) continue;
+#pragma unroll
+    for (int l = 0; l < E; ++l) {
+      if (l & j) continue;
+      const bool up = ((base + l) & k) == 0;
+      const u64 lo = v[l], hi = v[l + j];
+      const bool swap = (lo > hi) == up;
+      v[l] = swap ? hi : lo;
+      v[l + j] = swap ? lo : hi;
+    }
+  }
+}
+
+template <int THREADS, int E>
+__global__ __launch_bounds__(THREADS) void pf_quantiles_kernel(QArgs a) {
+  extern __shared__ u64 lds[];
+  __shared__ u64 wave_tot[kMaxWaves];
+  __shared__ float wave_top[kMaxWaves];
+  constexpr int P = THREADS * E;
+  const int tid = threadIdx.x, M = a.M, d = a.d;
+  const int r = blockIdx.x / d, k = blockIdx.x - r * d;
+  const size_t row = static_cast<size_t>(r) * M;
+  const float* x = a.states + row * d + k;
+
+  // a_m = log_a[m] + log_b[m]; particle m = tid + u THREADS
+  float av[E];
+  float top = -INFINITY;
+#pragma unroll
+  for (int u = 0; u < E; ++u) {
+    const int m = tid + u * THREADS;
+    float s = -INFINITY;
+    if (m < M) {
+      const float la = a.log_a ? a.log_a[row + m] : 0.f, lb = a.log_b ? a.log_b[row + m] : 0.f;
+      s = la + lb;
+    }
+    av[u] = s;
+    top = fmaxf(top, s);  // (a NaN is skipped)
+  }
+  top = block_max<THREADS>(top, wave_top, tid);
+
+  const bool want_cdf = a.query != nullptr;
+  const float query = want_cdf ? a.query[static_cast<size_t>(r) * d + k] : 0.f;
+  u64 qsum = 0, below = 0;
+#pragma unroll
+  for (int u = 0; u < E; ++u) {
+    const int m = tid + u * THREADS;
+    u64 packed = kPadKey;
+    if (m < M) {
+      const float t = av[u] - top;
+      const float e = expf(t);
+      const unsigned q = t <= 0.f ? static_cast<unsigned>(floorf(e * 16777216.0f)) : 0u;  // (a NaN t: 0)
+      const float xv = x[static_cast<size_t>(m) * d];
+      qsum += q;
+      if (xv <= query) below += q;
+      packed = (static_cast<u64>(key_of(xv)) << 32) | q;
+    }
+    if (a.Q > 0) lds[slot<E>(m)] = packed;
+  }
+  u64 Qtot, below_tot = 0;
+  block_scan<THREADS>(qsum, wave_tot, tid, Qtot);
+  if (want_cdf) block_scan<THREADS>(below, wave_tot, tid, below_tot);
+  const bool dead = !(top > -INFINITY) || !(top < INFINITY) || Qtot == 0;  // no live particle in the row
+  if (want_cdf && tid == 0) {
+    const float c = static_cast<float>(static_cast<double>(below_tot) / static_cast<double>(Qtot));
+    a.cdf[static_cast<size_t>(r) * d + k] = dead || query != query ? NAN : c;
+  }
+  if (a.Q == 0) return;
+  if (dead) {
+    for (int i = tid; i < a.Q; i += THREADS) a.quantiles[(static_cast<size_t>(r) * a.Q + i) * d + k] = NAN;
+    return;
+  }
+
+  // ---- bitonic sort, ascending
+  const int base = tid * E;
+  u64 v[E];
+  __syncthreads();
+  if constexpr (E > 1) {
+#pragma unroll
+    for (int l = 0; l < E; ++l) v[l] = lds[slot<E>(base) + l];
+#pragma unroll
+    for (int kk = 2; kk <= E; kk <<= 1) local_stages<E>(v, base, kk, kk / 2);
+    for (int kk = 2 * E; kk <= P; kk <<= 1) {
+#pragma unroll
+      for (int l = 0; l < E; ++l) lds[slot<E>(base) + l] = v[l];
+      __syncthreads();
+      for (int j = kk / 2; j >= E; j >>= 1) {
+#pragma unroll
+        for (int u = 0; u < E / 2; ++u) {
+          const int p = tid + u * THREADS;
+          const int i = 2 * p - (p & (j - 1));  // pair p of stride j: 2 j (p / j) + p % j
+          const bool up = (i & kk) == 0;
+          const u64 lo = lds[slot<E>(i)], hi = lds[slot<E>(i + j)];
+          if ((lo > hi) == up) {
+            lds[slot<E>(i)] = hi;
+            lds[slot<E>(i + j)] = lo;
+          }
+        }
+        __syncthreads();
+      }
+#pragma unroll
+      for (int l = 0; l < E; ++l) v[l] = lds[slot<E>(base) + l];
+      local_stages<E>(v, base, kk, E / 2);
+    }
+  } else {
+    for (int kk = 2; kk <= P; kk <<= 1)
+      for (int j = kk / 2; j >= 1; j >>= 1) {
+        if (tid < P / 2) {
+          const int i = 2 * tid - (tid & (j - 1));  // pair tid of stride j: 2 j (tid / j) + tid % j
+          const bool up = (i & kk) == 0;
+          const u64 lo = lds[i], hi = lds[i + j];
+          if ((lo > hi) == up) {
+            lds[i] = hi;
+            lds[i + j] = lo;
+          }
+        }
+        __syncthreads();
+      }
+    v[0] = lds[tid];
+  }
+
+  // ---- the integer CDF in sorted order: this thread's run covers (excl, excl + mine]
+  u64 mine = 0;
+#pragma unroll
+  for (int l = 0; l < E; ++l) mine += v[l] & 0xFFFFFFFFull;
+  u64 total;
+  const u64 excl = block_scan<THREADS>(mine, wave_tot, tid, total) - mine;
+#pragma unroll 1
+  for (int i = 0; i < a.Q; ++i) {
+    const double want = ceil(static_cast<double>(a.probs[i]) * static_cast<double>(total));
+    const u64 thr = want < 1.0 ? 1ull : static_cast<u64>(want);
+    if (excl < thr && thr <= excl + mine) {
+      u64 c = excl;
+      unsigned key = 0;
+      bool found = false;
+#pragma unroll
+      for (int l = 0; l < E; ++l) {
+        c += v[l] & 0xFFFFFFFFull;
+        const bool hit = !found && c >= thr;
+        key = hit ? static_cast<unsigned>(v[l] >> 32) : key;
+        found = found || hit;
+      }
+      a.quantiles[(static_cast<size_t>(r) * a.Q + i) * d + k] = value_of(key);
+    }
+  }
+}
+
+template <int THREADS, int E>
+int run(const QArgs& k, unsigned grid, size_t lds_bytes, hipStream_t s) {
+  return mmf::launch(pf_quantiles_kernel<THREADS, E>, grid, THREADS, lds_bytes, s, k);
+}
+
+}  // namespace
+
+extern "C" size_t mmf_pf_quantiles_lds_bytes(int M) {
+  if (M < 1) return 0;
+  if (M > kMaxM) M = kMaxM;
+  return slots_of(plan_of(M)) * sizeof(u64);
+}
+
+extern "C" int mmf_pf_quantiles(const MmfPfQuantilesArgs* a, void* stream) {
+  if (!a || !a->states) return MMF_EINVAL;
+  if (a->R < 0 || a->M < 1 || a->d < 1 || a->d > MMF_MAX_STATE_DIM || a->Q < 0 || a->Q > MMF_QUANTILES_MAX) return MMF_EINVAL;
+  for (int i = 0; i < a->Q; ++i)
+    if (!(a->probs[i] >= 0.f && a->probs[i] <= 1.f)) return MMF_EINVAL;
+  if (a->Q == 0 && !a->query) return MMF_EINVAL;
+  if (a->Q > 0 && !a->quantiles) return MMF_EINVAL;
+  if ((a->query != nullptr) != (a->cdf != nullptr)) return MMF_EINVAL;
+  if (a->M > kMaxM) return MMF_ETOOLARGE;
+  if (static_cast<long long>(a->R) * a->d > 0x7fffffffll) return MMF_ETOOLARGE;
+  {
+    const size_t R = a->R, M = a->M, d = a->d, Q = a->Q, f = sizeof(float);
+    const void* ins[4] = {a->states, a->log_a, a->log_b, a->query};
+    const size_t in_bytes[4] = {R * M * d * f, R * M * f, R * M * f, R * d * f};
+    const void* outs[2] = {a->quantiles, a->cdf};
+    const size_t out_bytes[2] = {R * Q * d * f, R * d * f};
+    for (int o = 0; o < 2; ++o)
+      for (int i = 0; i < 4; ++i)
+        if (mmf_bytes_overlap(outs[o], out_bytes[o], ins[i], in_bytes[i])) return MMF_EINVAL;
+    if (mmf_bytes_overlap(outs[0], out_bytes[0], outs[1], out_bytes[1])) return MMF_EINVAL;
+  }
+  if (a->R == 0) return 0;
+  QArgs k{};
+  k.states = a->states; k.log_a = a->log_a; k.log_b = a->log_b; k.query = a->query;
+  k.quantiles = a->quantiles; k.cdf = a->cdf;
+  k.M = a->M; k.d = a->d; k.Q = a->Q;
+  for (int i = 0; i < a->Q; ++i) k.probs[i] = a->probs[i];
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const unsigned grid = static_cast<unsigned>(a->R) * static_cast<unsigned>(a->d);
+  const Plan p = plan_of(a->M);
+  const size_t lds_bytes = slots_of(p) * sizeof(u64);
+  if (p.threads == MMF_WAVE) {
+    switch (p.E) {
+      case 1: return run<MMF_WAVE, 1>(k, grid, lds_bytes, s);
+      case 2: return run<MMF_WAVE, 2>(k, grid, lds_bytes, s);
+      case 4: return run<MMF_WAVE, 4>(k, grid, lds_bytes, s);
+      default: return run<MMF_WAVE, 8>(k, grid, lds_bytes, s);
+    }
+  }
+  switch (p.E) {
+    case 4: return run<256, 4>(k, grid, lds_bytes, s);
+    case 8: return run<256, 8>(k, grid, lds_bytes, s);
+    case 16: return run<256, 16>(k, grid, lds_bytes, s);
+    case 32: return run<256, 32>(k, grid, lds_bytes, s);
+    default: return run<256, 64>(k, grid, lds_bytes, s);
+  }
+}

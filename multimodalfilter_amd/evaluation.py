@@ -24,7 +24,7 @@ _DEFAULT_METHOD = _DefaultMethod("ancestry")
 def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale: float = 0.1,
                measurement_initialize: bool = False, return_belief: bool = False, smooth_lag=False,
                smooth_method: str = _DEFAULT_METHOD, smooth_draws: int = _DEFAULT_DRAWS, smooth_transition_moments: bool = False,
-               return_innovations: bool = False):
+               return_innovations: bool = False, return_quantiles=None):
     """Initialise the belief at ``states[0]`` with covariance ``0.1 I`` (or from the first
     observation, ``eval_helpers.py:116-131``) and filter ``[1:]`` (``:139-142``).
     ``return_belief``: run with ``record_belief`` set and return ``(estimates, filter_model.last_belief)`` -- the per-step
@@ -46,7 +46,15 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
     ``return_innovations``: runs a Kalman filter with ``record_innovations`` set (and puts the switch back) and appends
     ``filter_model.last_innovations`` -- ``nis``, ``log_likelihood``, ``accepted`` per step (``innovation_summary``) -- to what
     is returned: ``(estimates, innovations)`` or ``(estimates, record, innovations)``.  A filter without the switch (the
-    particle filters, the LSTM baselines) is refused before the run."""
+    particle filters, the LSTM baselines) is refused before the run.
+    ``return_quantiles``: a sequence of probabilities runs a particle filter with ``record_history`` set (and puts the switch
+    back), calls ``filter_model.belief_quantiles(probs, of=..., truth=traj["states"][1:])`` -- ``of="smoothed"`` exactly when
+    the call smooths with ``"marginal"`` or ``"simulation"``, the filter's own weighted sets otherwise -- and appends
+    ``filter_model.last_quantiles`` (``probs``, ``quantiles (T, N, Q, d)``, ``of``, ``pit (T, N, d)``; ``interval_coverage``,
+    ``pit_histogram``) as the LAST element of what is returned.  A filter without ``belief_quantiles`` (the Kalman filters,
+    whose quantiles are closed form, and the LSTM baselines) and a smoothing method without a weighted set (``"ancestry"``
+    with a lag, ``"map"``, ``"rts"``) are refused before the run.  Left at ``None``, every return value and every bit is as
+    without it."""
     if return_innovations and not hasattr(filter_model, "record_innovations"):  # (before the run, not after it)
         raise ValueError(f"run_filter: return_innovations needs a Kalman filter; {type(filter_model).__name__} has no "
                          "record_innovations (a particle filter reports log_evidence through return_belief)")
@@ -60,6 +68,17 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
     if smooth_draws is not _DEFAULT_DRAWS and smooth_method != "simulation":  # (before the run, not after it)
         raise ValueError(f"run_filter: smooth_draws is the number of paths smooth_method='simulation' draws; "
                          f"smooth_method={smooth_method!r} takes none")
+    want_quantiles = return_quantiles is not None
+    if want_quantiles:  # (before the run, not after it)
+        if not hasattr(filter_model, "belief_quantiles"):
+            raise ValueError(f"run_filter: return_quantiles needs a particle filter; {type(filter_model).__name__} has no "
+                             "belief_quantiles (a Gaussian belief's quantiles are closed form: mean and covariance)")
+        will_smooth = smooth_lag is not False or (named and smooth_method != "ancestry")
+        if will_smooth and smooth_method not in ("marginal", "simulation"):
+            raise ValueError(f"run_filter: return_quantiles reads a weighted particle set per step; smooth_method={smooth_method!r} "
+                             "leaves none (ancestry keeps no per-step weights, a MAP path is not a distribution): smooth with "
+                             "'marginal' or 'simulation', or do not smooth")
+        quantiles_of = "smoothed" if will_smooth else "filtered"
     states = traj["states"]
     T1, N, d = states.shape
     obs = {k: traj[k] for k in ("image", "gripper_pos", "gripper_sensors")}
@@ -70,7 +89,7 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
     if named and smooth_method != "ancestry" and smooth_lag is False:
         smooth_lag = None
     smoothing = smooth_lag is not False  # (0 is a lag)
-    if smoothing:
+    if smoothing or want_quantiles:
         assert hasattr(filter_model, "record_history"), f"{type(filter_model).__name__} keeps no history to smooth"
         was_history = filter_model.record_history
         filter_model.record_history = True
@@ -94,7 +113,7 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
             filter_model.record_innovations = was_innovations
         if return_belief:
             filter_model.record_belief = was
-        if smoothing:
+        if smoothing or want_quantiles:
             filter_model.record_history = was_history
     if smoothing:
         draws = {} if smooth_draws is _DEFAULT_DRAWS else {"num_draws": smooth_draws}  # (another method refuses it, as smooth() does)
@@ -111,7 +130,10 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
     else:
         out = (est, filter_model.last_belief) if return_belief else est
     if return_innovations:
-        return (out if isinstance(out, tuple) else (out,)) + (innovations,)
+        out = (out if isinstance(out, tuple) else (out,)) + (innovations,)
+    if want_quantiles:
+        filter_model.belief_quantiles(return_quantiles, of=quantiles_of, truth=states[1:])
+        out = (out if isinstance(out, tuple) else (out,)) + (filter_model.last_quantiles,)
     return out
 
 
@@ -320,6 +342,33 @@ def coverage(predicted: torch.Tensor, covariance: torch.Tensor, true: torch.Tens
     else:
         cdf = torch.special.gammainc(torch.full_like(x, 0.5 * d), 0.5 * x)
     return torch.mean((cdf <= level).to(x.dtype), dim=0)
+
+
+def interval_coverage(lower: torch.Tensor, upper: torch.Tensor, true: torch.Tensor, start: int = START_TRUNCATION) -> torch.Tensor:
+    """Share of the steps after the burn-in whose true state lies inside the credible interval, per trajectory and state
+    dimension: ``(T, N, d)`` x3 -> ``(N, d)``, the mean over time of ``lower <= true <= upper``; the interval's level for a
+    calibrated filter -- e.g. 0.95 for the ``0.025`` and ``0.975`` quantiles of ``ParticleFilter.belief_quantiles``.  The
+    non-parametric counterpart of ``coverage``, which tests against the moment-matched ellipsoid.  A NaN bound (a step without
+    a live particle) does not cover."""
+    assert lower.shape == upper.shape == true.shape, (tuple(lower.shape), tuple(upper.shape), tuple(true.shape))
+    inside = (lower[start:] <= true[start:]) & (true[start:] <= upper[start:])
+    return torch.mean(inside.to(torch.float32), dim=0)
+
+
+def pit_histogram(pit: torch.Tensor, bins: int = 10, start: int = START_TRUNCATION) -> torch.Tensor:
+    """Histogram of the probability integral transform (``belief_quantiles(truth=)``'s ``pit (T, N, d)``) after the burn-in,
+    over all steps and trajectories: ``(d, bins)`` shares of equal-width bins of ``[0, 1]`` that sum to 1 per dimension, with
+    ``pit == 1`` in the last bin.  Flat (``1 / bins`` each) for a calibrated filter; a U shape says the belief is too narrow,
+    a hump too wide, a slope biased.  NaN entries (steps without a live particle) are left out."""
+    assert isinstance(bins, int) and bins >= 1
+    p = pit[start:]
+    d = p.shape[-1]
+    p = p.reshape(-1, d)
+    ok = ~torch.isnan(p)
+    idx = torch.clamp(torch.floor(torch.nan_to_num(p, nan=0.0).to(torch.float64) * bins).to(torch.int64), 0, bins - 1)
+    counts = torch.zeros((d, bins), dtype=torch.float64, device=p.device)
+    counts.scatter_add_(1, idx.t().contiguous(), ok.t().to(torch.float64).contiguous())
+    return (counts / counts.sum(dim=1, keepdim=True)).to(torch.float32)
 
 
 def per_trajectory_mse(predicted: torch.Tensor, true: torch.Tensor,

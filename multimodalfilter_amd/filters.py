@@ -13,6 +13,7 @@ itself running in hand-written HIP: ``mmf_pf_init_particles`` for the initial be
 Step order follows upstream torchfilter.
 """
 import math
+import numbers
 from typing import Optional
 
 import torch
@@ -81,6 +82,8 @@ class ParticleFilter(base.Filter):
     residual in ``last_smoothed`` (``residual_mean``, ``residual_second_moment``; ``mmf_pf_smooth_pair_moments``), what
     ``evaluation.process_noise_m_step`` refits the process noise from.  A switch like the other ``record_*`` ones and not
     an argument of ``smooth``, whose parameter list stays ``(lag, *, method, num_draws)``; another method with it set raises.
+    ``belief_quantiles(probs, of=, truth=)``: per-dimension weighted quantiles of the recorded sets (and the PIT of a true
+    state) -> ``last_quantiles``; the non-parametric counterpart of the covariance (``mmf_pf_quantiles``).
     Randomness comes from ``self.noise`` (``utils.NoiseSource``), never from global RNG state.
     """
 
@@ -118,6 +121,7 @@ class ParticleFilter(base.Filter):
         self.record_history = False   # forward_loop keeps the per-step sets / weights / ancestors -> last_history, smooth()
         self.last_history = None
         self.last_smoothed = None
+        self.last_quantiles = None    # belief_quantiles(): per-dimension weighted quantiles (and the PIT) of the recorded sets
         self.record_transition_moments = False  # smooth(method="marginal") adds the two-slice residual moments to last_smoothed
         self._step_history = None
         self.use_native_loop = True   # False: forward_loop keeps the step-by-step Python loop
@@ -789,6 +793,76 @@ class ParticleFilter(base.Filter):
             _abi.pf_smooth_map(h.states, pred, h.log_likelihoods, h.log_weights_in, tril, indices, path, log_posterior)
         self.last_smoothed = base.belief_record(indices=indices, log_posterior=log_posterior, lag=None, method="map")
         return path
+
+    def belief_quantiles(self, probs, *, of: str = "filtered", truth: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Per-dimension weighted quantiles of the recorded particle sets (``mmf_pf_quantiles``, ``include/mmf.h``): the
+        non-parametric counterpart of ``record_belief``'s covariance -- median, credible intervals -- for a belief that need
+        not be Gaussian.  ``probs``: 1 .. 16 floats in ``[0, 1]``.  Returns ``(T, N, Q, d)``; every value is a particle's own
+        coordinate (the inverted weighted CDF on K1's integer fixed-point weights: the same bits whatever the batch).
+        ``of = "filtered"``: the pre-resampling weighted set of every step of ``last_history`` (``record_history`` and
+        ``forward_loop`` first) -- ``states`` under ``log_weights_in + log_likelihoods``, the set the estimate is taken from.
+        ``of = "smoothed"``: the sets of ``last_smoothed`` -- after ``smooth(method="marginal")`` the history's states under
+        the smoothed ``weights``; after ``smooth(method="simulation")`` the ``num_draws`` drawn ``trajectories``, equally
+        weighted.  ``"ancestry"`` keeps no per-step weights and ``"map"`` is a path, not a distribution: both are refused.
+        ``truth (T, N, d)``: also the probability integral transform of the true state, ``pit (T, N, d)`` -- the weighted share
+        of the particles at or below it, per dimension; under a calibrated filter it is uniform on ``[0, 1]``
+        (``evaluation.pit_histogram``).  Leaves ``last_quantiles``: ``probs`` (a tuple), ``quantiles``, ``of`` and, with a
+        truth, ``pit``.  Draws no noise and leaves ``last_history`` / ``last_smoothed`` as they are.  A step without a live
+        particle gives NaN."""
+        if of not in ("filtered", "smoothed"):
+            raise ValueError(f"belief_quantiles: of must be 'filtered' or 'smoothed', got {of!r}")
+        try:
+            ps = [p for p in probs]
+        except TypeError:
+            raise ValueError(f"belief_quantiles: probs must be a sequence of floats in [0, 1], got {probs!r}") from None
+        if not 1 <= len(ps) <= _abi.QUANTILES_MAX:
+            raise ValueError(f"belief_quantiles: probs must hold 1 .. {_abi.QUANTILES_MAX} probabilities, got {len(ps)}")
+        for p in ps:
+            if isinstance(p, bool) or not isinstance(p, numbers.Real) or not 0.0 <= float(p) <= 1.0:  # (a NaN fails the range)
+                raise ValueError(f"belief_quantiles: probs must be floats in [0, 1], got {p!r}")
+        ps = tuple(float(p) for p in ps)
+        h = self.last_history
+        log_a = log_b = None
+        if of == "filtered":
+            if h is None or getattr(h, "states", None) is None:
+                raise ValueError("belief_quantiles needs a history: set record_history and run forward_loop (evaluation mode) first")
+            states, log_a, log_b = h.states, h.log_weights_in, h.log_likelihoods
+        else:
+            s = self.last_smoothed
+            if s is None:
+                raise ValueError("belief_quantiles(of='smoothed') needs a smoothed record: call smooth(method='marginal') or "
+                                 "smooth(method='simulation') first")
+            method = getattr(s, "method", "ancestry")
+            if method == "marginal":
+                if h is None or getattr(h, "states", None) is None or tuple(h.states.shape[:3]) != tuple(s.weights.shape):
+                    raise ValueError("belief_quantiles(of='smoothed'): the marginal smoother's weights belong to a history that "
+                                     "is no longer there: run forward_loop with record_history and smooth again")
+                states = h.states
+            elif method == "simulation":
+                states = s.trajectories
+            elif method == "map":
+                raise ValueError("belief_quantiles(of='smoothed'): smooth(method='map') leaves one path, and a path is not a "
+                                 "distribution: smooth with method='marginal' or 'simulation'")
+            else:
+                raise ValueError(f"belief_quantiles(of='smoothed'): smooth(method={method!r}) keeps no per-step weights over the "
+                                 "recorded sets: smooth with method='marginal' or 'simulation'")
+        T, N, M, d = states.shape
+        if M > _abi.QUANTILES_MAX_M:
+            raise ValueError(f"belief_quantiles: {M} particles per set; mmf_pf_quantiles sorts at most {_abi.QUANTILES_MAX_M} in LDS")
+        if truth is not None and (not isinstance(truth, torch.Tensor) or tuple(truth.shape) != (T, N, d)):
+            raise ValueError(f"belief_quantiles: truth must be a (T, N, d) = ({T}, {N}, {d}) tensor, got "
+                             f"{tuple(truth.shape) if isinstance(truth, torch.Tensor) else type(truth).__name__}")
+        dev = states.device
+        with torch.no_grad():
+            if of == "smoothed" and method == "marginal":
+                log_a = torch.log(self.last_smoothed.weights)
+            query = None if truth is None else truth.detach().to(device=dev, dtype=torch.float32).contiguous()
+            quantiles = torch.empty((T, N, len(ps), d), dtype=torch.float32, device=dev)
+            pit = None if query is None else torch.empty((T, N, d), dtype=torch.float32, device=dev)
+            _abi.pf_quantiles(states, log_a, log_b, ps, quantiles, query, pit)
+        extra = {} if pit is None else {"pit": pit}
+        self.last_quantiles = base.belief_record(probs=ps, quantiles=quantiles, of=of, **extra)
+        return quantiles
 
     @engine.checked_step
     def forward(self, *, observations, controls) -> torch.Tensor:
