@@ -959,6 +959,62 @@ typedef struct MmfPfQuantilesArgs {
 int mmf_pf_quantiles(const MmfPfQuantilesArgs* args /* host */, void* stream);
 size_t mmf_pf_quantiles_lds_bytes(int M);
 
+/* ---------------------------------------------------------------- Particle-posterior scores: CRPS and the energy score
+ * The evaluation of crossmodal/eval_helpers.py:148-160 scores point estimates only (the squared error of the posterior
+ * mean); the quantiles above judge calibration only, and a filter that always answers "somewhere in the room" has a uniform
+ * PIT.  These are the two standard strictly proper scoring rules taken on the weighted particle set itself (Gneiting &
+ * Raftery 2007): they reward calibration and sharpness together, are in the state's own units, reduce to the absolute /
+ * Euclidean error for a point mass and have a closed form for a Gaussian.  Both are E|X - y| - 1/2 E|X - X'|; the second
+ * expectation runs over all M^2 pairs of a set, which in torch ops is an (M, M, d) tensor or a chunked loop over one.
+ * Purely additive to ABI 42: a struct and two symbols of their own.
+ * Per row r (R rows, e.g. T * N, of M particles x_m = states[r, m, :]) with a truth y = truth[r, :]:
+ *   a_m      = log_a[r, m] + log_b[r, m]     one fp32 add; a null addend is 0, both null: uniform weights
+ *   w_m      = expf(a_m - max_m a_m)         one fp32 subtract (the maximum skips NaN); 0 where a_m is -inf or NaN
+ *   W_m      = w_m / sum w                   in double, once, at the end
+ *   crps[k]  = sum_m W_m |x_mk - y_k| - 1/2 spread[k]                             k < d
+ *   spread[k]= sum_m sum_l W_m W_l |x_mk - x_lk|                                  Gini's mean difference of dimension k
+ *   energy   = sum_m W_m |(x_m - y) / s|_2 - 1/2 spread[d]
+ *   spread[d]= sum_m sum_l W_m W_l |(x_m - x_l) / s|_2
+ * s = scale[0 .. d): a per-dimension scale that makes the Euclidean norm meaningful across units; it enters energy and
+ * spread[d] only, crps stays in each dimension's own units (the kernel multiplies by the fp32 reciprocal 1 / s_k).
+ * The weights are plain floats, NOT K1's 2^24 fixed point: nothing is selected here, so there is nothing for integer sums
+ * to protect, and an fp64 evaluation of these lines differs from the kernel by the ulps of expf and of the fp32 pair terms.
+ *   - a particle with w_m = 0 contributes nothing, whatever its state row holds (the histories carry NaN rows for dead
+ *     particles): the zero weight selects the term away, it does not multiply it;
+ *   - a row without a live particle (sum w = 0: max a is -inf, NaN or +inf) gives NaN everywhere;
+ *   - a NaN y_k gives NaN in crps[k] and in energy; the other dimensions and spread stay finite;
+ *   - spread needs no truth; crps or energy without one is refused.
+ * Determinism: every sum is taken in a fixed order and there are no floating-point atomics -- two calls give the same bits,
+ * and a row's result depends on neither R nor the other rows (the plan is a function of M alone).
+ * Kernel plan: no (M, M) array in memory.  A row is dealt to nb = ceil(M / 512) workgroups in equal i-chunks; a thread holds
+ * one i-particle (M <= 512, up to 512 threads) or two (beyond, up to 256 threads) in registers and walks j-tiles of 1024
+ * particles staged through LDS as structure-of-arrays (d coordinate planes and w), four j per broadcast 16-byte read; the d
+ * differences of a pair feed the d absolute-value accumulators and the one norm.  fp32 accumulators over runs of 64 pairs,
+ * flushed to double; 2 d + 3 double sums per workgroup (the pair sums, the truth sums, sum w), reduced in a fixed order.  With
+ * nb == 1 the workgroup writes the row; otherwise it writes its sums to the workspace and a finishing kernel adds a row's nb
+ * partial sums in order.  mmf_pf_scores_workspace_bytes(R, M, d): 88 R nb bytes for M > 512, 0 up to 512 (and for R, M or
+ * d below 1).
+ * Limits, all decided on the host before any HIP call: null args / states, d outside 1 .. 4, M < 1, R < 0, a scale[k < d]
+ * that is not positive and finite, all three outputs null, crps or energy without truth, a workspace that is needed and null,
+ * smaller than the query's answer or not 8-byte aligned, an output (or the workspace) overlapping an input or another
+ * output -> MMF_EINVAL; M > 16384 or R * nb beyond a 32-bit grid -> MMF_ETOOLARGE; R == 0 is a successful no-op.
+ * Coordinates whose squared difference overflows fp32 (beyond 1e19) are outside what the energy score serves. */
+typedef struct MmfPfScoresArgs {
+  int32_t R, M, d;                  /* R rows (e.g. T*N) of M particles */
+  float scale[MMF_MAX_STATE_DIM];   /* host values, scale[k < d] > 0 and finite; 1 for plain Euclidean distance */
+  const float* states;              /* (R, M, d) */
+  const float* log_a;               /* (R, M) or null = 0 */
+  const float* log_b;               /* (R, M) or null = 0 (history: log_weights_in + log_likelihoods) */
+  const float* truth;               /* (R, d); null allowed with spread alone */
+  float* crps;                      /* (R, d) or null */
+  float* energy;                    /* (R) or null */
+  float* spread;                    /* (R, d + 1) or null */
+  void* workspace;                  /* device, 8-byte aligned, mmf_pf_scores_workspace_bytes(R, M, d) bytes; unused when that is 0 */
+  size_t workspace_bytes;
+} MmfPfScoresArgs;                  /* host struct holding device pointers */
+int mmf_pf_scores(const MmfPfScoresArgs* args /* host */, void* stream);
+size_t mmf_pf_scores_workspace_bytes(int R, int M, int d);
+
 /* ---------------------------------------------------------------- K6, fused: one network call of the training backward
  * Recompute (the forward pass's f16x3 arithmetic), backward data path and weight / bias gradients of ONE per-particle
  * network over N * M rows in one kernel (the dynamics network: three launches -- encoder forward, trunk, encoder

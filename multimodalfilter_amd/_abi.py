@@ -144,6 +144,15 @@ class MmfPfQuantilesArgs(Structure):
                 ("states", _FP), ("log_a", _FP), ("log_b", _FP), ("query", _FP), ("quantiles", _FP), ("cdf", _FP)]
 
 
+SCORES_MAX_M = 16384  # particles per row that mmf_pf_scores serves
+
+
+class MmfPfScoresArgs(Structure):
+    _fields_ = [("R", c_int32), ("M", c_int32), ("d", c_int32), ("scale", ctypes.c_float * MMF_MAX_STATE_DIM),
+                ("states", _FP), ("log_a", _FP), ("log_b", _FP), ("truth", _FP), ("crps", _FP), ("energy", _FP), ("spread", _FP),
+                ("workspace", _FP), ("workspace_bytes", c_size_t)]
+
+
 class MmfTrainNet(Structure):
     _fields_ = [("packed", _FP), ("packed_f32", _FP), ("packed_t", _FP), ("head_w", _FP), ("pw", _FP), ("pb", _FP),
                 ("p_first", _FP), ("p_head", _FP), ("p_dout", _FP), ("p_traj", _FP), ("packed_dual", _FP)]
@@ -247,6 +256,8 @@ SIGNATURES = {
     "mmf_pf_smooth_map": (c_int, [POINTER(MmfPfSmoothMapArgs), c_void_p]),
     "mmf_pf_quantiles": (c_int, [POINTER(MmfPfQuantilesArgs), c_void_p]),
     "mmf_pf_quantiles_lds_bytes": (c_size_t, [c_int]),
+    "mmf_pf_scores": (c_int, [POINTER(MmfPfScoresArgs), c_void_p]),
+    "mmf_pf_scores_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "mmf_pf_dedup_plan": (c_int, [c_int, c_int, c_int, ctypes.c_float, c_int]),
     "mmf_pf_dedup_workspace_words": (c_size_t, [c_int, c_int]),
     "mmf_pf_resample_runs": (c_int, [_FP] * 11 + [c_int, c_int, c_int, _FP, _FP, _FP, c_void_p]),
@@ -1126,3 +1137,41 @@ def pf_quantiles(states, log_a, log_b, probs, quantiles, query=None, cdf=None):
     a.quantiles, a.cdf = vp(quantiles), vp(cdf)
     with _on(states):
         _check(load().mmf_pf_quantiles(ctypes.byref(a), stream_of(states)), "mmf_pf_quantiles")
+
+
+def pf_scores_workspace_bytes(R: int, M: int, d: int) -> int:
+    return int(load().mmf_pf_scores_workspace_bytes(int(R), int(M), int(d)))
+
+
+def pf_scores(states, log_a, log_b, truth, crps, energy, spread, scale=None):
+    """CRPS per state dimension and the energy score of weighted particle sets against a true state, with their sharpness
+    terms (``mmf_pf_scores``, include/mmf.h): ``states (..., M, d)`` -- ``R`` rows, the product of the leading sizes -- with
+    log-weights ``log_a + log_b``, each ``(..., M)`` or ``None`` (0; both ``None``: uniform), and ``truth (..., d)`` ->
+    ``crps (..., d)``, ``energy (...)``, ``spread (..., d + 1)``, each of which may be ``None`` (not all three); ``truth`` may
+    be ``None`` with ``spread`` alone.  ``scale``: ``None`` (ones) or ``d`` positive finite host floats dividing the
+    coordinates inside the Euclidean norm of ``energy`` and ``spread[..., d]``.  The workspace of the partial sums is allocated
+    here, on the tensors' device."""
+    lead, (M, d) = tuple(states.shape[:-2]), states.shape[-2:]
+    R = 1
+    for n in lead:
+        R *= int(n)
+    scale = [1.0] * d if scale is None else [float(s) for s in scale]
+    if len(scale) != d or d > MMF_MAX_STATE_DIM:
+        raise MmfError(f"mmf_pf_scores takes one scale per state dimension (d = {d} <= {MMF_MAX_STATE_DIM}), got {len(scale)}")
+    assert log_a is None or tuple(log_a.shape) == lead + (M,)
+    assert log_b is None or tuple(log_b.shape) == lead + (M,)
+    assert truth is None or tuple(truth.shape) == lead + (d,)
+    assert crps is None or tuple(crps.shape) == lead + (d,)
+    assert energy is None or tuple(energy.shape) == lead
+    assert spread is None or tuple(spread.shape) == lead + (d + 1,)
+    a = MmfPfScoresArgs()
+    a.R, a.M, a.d = R, M, d
+    for i, s in enumerate(scale):
+        a.scale[i] = s
+    a.states, a.log_a, a.log_b, a.truth = vp(states), vp(log_a), vp(log_b), vp(truth)
+    a.crps, a.energy, a.spread = vp(crps), vp(energy), vp(spread)
+    with _on(states):
+        need = pf_scores_workspace_bytes(R, M, d)
+        work = torch.empty((need // 8,), dtype=torch.float64, device=states.device) if need else None
+        a.workspace, a.workspace_bytes = vp(work, torch.float64), need
+        _check(load().mmf_pf_scores(ctypes.byref(a), stream_of(states)), "mmf_pf_scores")

@@ -7,6 +7,7 @@ from typing import Dict
 import numpy as np
 import torch
 
+from . import base
 from .filters import _DEFAULT_DRAWS
 from .task_models import DOOR, PUSH
 
@@ -24,7 +25,7 @@ _DEFAULT_METHOD = _DefaultMethod("ancestry")
 def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale: float = 0.1,
                measurement_initialize: bool = False, return_belief: bool = False, smooth_lag=False,
                smooth_method: str = _DEFAULT_METHOD, smooth_draws: int = _DEFAULT_DRAWS, smooth_transition_moments: bool = False,
-               return_innovations: bool = False, return_quantiles=None):
+               return_innovations: bool = False, return_quantiles=None, return_scores: bool = False, score_scale=None):
     """Initialise the belief at ``states[0]`` with covariance ``0.1 I`` (or from the first
     observation, ``eval_helpers.py:116-131``) and filter ``[1:]`` (``:139-142``).
     ``return_belief``: run with ``record_belief`` set and return ``(estimates, filter_model.last_belief)`` -- the per-step
@@ -54,7 +55,18 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
     ``pit_histogram``) as the LAST element of what is returned.  A filter without ``belief_quantiles`` (the Kalman filters,
     whose quantiles are closed form, and the LSTM baselines) and a smoothing method without a weighted set (``"ancestry"``
     with a lag, ``"map"``, ``"rts"``) are refused before the run.  Left at ``None``, every return value and every bit is as
-    without it."""
+    without it.
+    ``return_scores``: appends a score record -- strictly proper scores of the belief against ``traj["states"][1:]``, the one
+    scale on which the three kinds of filter can be ranked as distributions (``score_summary``) -- after the innovations and
+    before the quantiles record, which stays last.  A particle filter runs with ``record_history`` set (and puts the switch
+    back) and calls ``belief_scores(traj["states"][1:], of=..., scale=score_scale)``: ``crps (T, N, d)``, ``energy (T, N)``,
+    ``spread (T, N, d + 1)`` of its weighted sets, ``of`` chosen and the smoothing methods refused as for
+    ``return_quantiles``.  A filter with a belief covariance (the Kalman filters) runs with ``record_belief`` set (and puts
+    the switch back); the record holds ``crps = gaussian_crps(...)`` of the returned means and the covariance that goes with
+    them -- the smoothed one when the call smooths -- and no ``energy``, which has no closed form.  A filter with neither (the
+    LSTM baselines) gets the scores of a point mass: ``crps = |estimate - true|``, ``energy = |(estimate - true) / s|``.
+    ``score_scale``: ``None`` or ``d`` positive finite floats ``s`` for the Euclidean norm of ``energy``; without
+    ``return_scores`` it is refused.  Left at ``False``, every return value and every bit is as without it."""
     if return_innovations and not hasattr(filter_model, "record_innovations"):  # (before the run, not after it)
         raise ValueError(f"run_filter: return_innovations needs a Kalman filter; {type(filter_model).__name__} has no "
                          "record_innovations (a particle filter reports log_evidence through return_belief)")
@@ -68,6 +80,26 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
     if smooth_draws is not _DEFAULT_DRAWS and smooth_method != "simulation":  # (before the run, not after it)
         raise ValueError(f"run_filter: smooth_draws is the number of paths smooth_method='simulation' draws; "
                          f"smooth_method={smooth_method!r} takes none")
+    want_scores = bool(return_scores)
+    if score_scale is not None:  # (before the run, not after it)
+        if not want_scores:
+            raise ValueError("run_filter: score_scale is the scale of return_scores' energy score; without return_scores it has no use")
+        try:
+            score_scale = tuple(float(v) for v in score_scale)
+        except (TypeError, ValueError):
+            raise ValueError(f"run_filter: score_scale must be None or d positive finite floats, got {score_scale!r}") from None
+        if not score_scale or not all(0.0 < v < math.inf for v in score_scale):
+            raise ValueError(f"run_filter: score_scale must be None or d positive finite floats, got {score_scale!r}")
+    scores_kind = None
+    if want_scores:  # (before the run, not after it)
+        scores_kind = ("particles" if hasattr(filter_model, "belief_scores") else
+                       "gaussian" if hasattr(filter_model, "record_belief") else "point")
+        will_smooth = smooth_lag is not False or (named and smooth_method != "ancestry")
+        if scores_kind == "particles" and will_smooth and smooth_method not in ("marginal", "simulation"):
+            raise ValueError(f"run_filter: return_scores reads a weighted particle set per step; smooth_method={smooth_method!r} "
+                             "leaves none (ancestry keeps no per-step weights, a MAP path is not a distribution): smooth with "
+                             "'marginal' or 'simulation', or do not smooth")
+        scores_of = "smoothed" if will_smooth else "filtered"
     want_quantiles = return_quantiles is not None
     if want_quantiles:  # (before the run, not after it)
         if not hasattr(filter_model, "belief_quantiles"):
@@ -81,15 +113,19 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
         quantiles_of = "smoothed" if will_smooth else "filtered"
     states = traj["states"]
     T1, N, d = states.shape
+    if score_scale is not None and len(score_scale) != d:
+        raise ValueError(f"run_filter: score_scale must be None or d = {d} positive finite floats, got {score_scale!r}")
     obs = {k: traj[k] for k in ("image", "gripper_pos", "gripper_sensors")}
     was = getattr(filter_model, "record_belief", None)
-    if return_belief:
+    need_belief = return_belief or scores_kind == "gaussian"
+    if need_belief:
         assert was is not None, f"{type(filter_model).__name__} keeps no belief to record"
         filter_model.record_belief = True
     if named and smooth_method != "ancestry" and smooth_lag is False:
         smooth_lag = None
     smoothing = smooth_lag is not False  # (0 is a lag)
-    if smoothing or want_quantiles:
+    need_history = smoothing or want_quantiles or scores_kind == "particles"
+    if need_history:
         assert hasattr(filter_model, "record_history"), f"{type(filter_model).__name__} keeps no history to smooth"
         was_history = filter_model.record_history
         filter_model.record_history = True
@@ -111,9 +147,9 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
     finally:
         if return_innovations:
             filter_model.record_innovations = was_innovations
-        if return_belief:
+        if need_belief:
             filter_model.record_belief = was
-        if smoothing or want_quantiles:
+        if need_history:
             filter_model.record_history = was_history
     if smoothing:
         draws = {} if smooth_draws is _DEFAULT_DRAWS else {"num_draws": smooth_draws}  # (another method refuses it, as smooth() does)
@@ -131,6 +167,22 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
         out = (est, filter_model.last_belief) if return_belief else est
     if return_innovations:
         out = (out if isinstance(out, tuple) else (out,)) + (innovations,)
+    if want_scores:
+        truth = states[1:]
+        if scores_kind == "particles":
+            filter_model.belief_scores(truth, of=scores_of, scale=score_scale)
+            scores = filter_model.last_scores
+        else:
+            s = (1.0,) * d if score_scale is None else score_scale
+            with torch.no_grad():
+                if scores_kind == "gaussian":
+                    cov = (filter_model.last_smoothed if smoothing else filter_model.last_belief).covariance
+                    scores = base.belief_record(crps=gaussian_crps(est, cov, truth), of=scores_of, scale=s)
+                else:
+                    e = est - truth
+                    energy = torch.linalg.vector_norm(e / torch.tensor(s, dtype=e.dtype, device=e.device), dim=-1)
+                    scores = base.belief_record(crps=e.abs(), energy=energy, of=scores_of, scale=s)
+        out = (out if isinstance(out, tuple) else (out,)) + (scores,)
     if want_quantiles:
         filter_model.belief_quantiles(return_quantiles, of=quantiles_of, truth=states[1:])
         out = (out if isinstance(out, tuple) else (out,)) + (filter_model.last_quantiles,)
@@ -342,6 +394,44 @@ def coverage(predicted: torch.Tensor, covariance: torch.Tensor, true: torch.Tens
     else:
         cdf = torch.special.gammainc(torch.full_like(x, 0.5 * d), 0.5 * x)
     return torch.mean((cdf <= level).to(x.dtype), dim=0)
+
+
+def gaussian_crps(predicted: torch.Tensor, covariance: torch.Tensor, true: torch.Tensor) -> torch.Tensor:
+    """The continuous ranked probability score of the Gaussian belief ``N(predicted, covariance)`` at the true state, per
+    state dimension, in closed form on the covariance's diagonal: ``(T, N, d)``, ``(T, N, d, d)``, ``(T, N, d)`` -> ``(T, N,
+    d)``, ``sigma [z (2 Phi(z) - 1) + 2 phi(z) - 1 / sqrt(pi)]`` with ``z = (y - mu) / sigma`` (Gneiting & Raftery 2007), and
+    ``|y - mu|`` where ``sigma = 0``: a point mass.  The same number ``ParticleFilter.belief_scores`` takes on a weighted
+    particle set, so the two kinds of belief are ranked on one scale.  In the dtype of ``covariance``."""
+    var = torch.diagonal(covariance, dim1=-2, dim2=-1)
+    sigma = torch.sqrt(var.clamp_min(0.0))
+    e = (true - predicted).to(sigma.dtype)
+    point = sigma == 0
+    z = e / torch.where(point, torch.ones_like(sigma), sigma)
+    phi = torch.exp(-0.5 * z * z) / math.sqrt(2.0 * math.pi)
+    closed = sigma * (z * torch.erf(z / math.sqrt(2.0)) + 2.0 * phi - 1.0 / math.sqrt(math.pi))
+    return torch.where(point, e.abs(), closed)
+
+
+def score_summary(record, start: int = START_TRUNCATION) -> Dict[str, object]:
+    """Means of a score record (``ParticleFilter.last_scores``; ``run_filter(return_scores=True)``) over the finite entries
+    of the steps after the burn-in, over time and trajectories: ``crps (d,)``, and, where the record holds them, ``energy``
+    (a float) and ``spread (d + 1,)``.  Lower is better; ``crps`` is in each state dimension's own units.  Steps without a
+    live particle (NaN) are left out, like the other metrics leave them."""
+    if getattr(record, "crps", None) is None:
+        raise ValueError("score_summary: the record has no crps; take it from belief_scores or run_filter(return_scores=True)")
+
+    def mean(x):  # over every axis but the last
+        x = x[start:].to(torch.float64)
+        x = x.reshape(-1, x.shape[-1])
+        ok = torch.isfinite(x)
+        return (torch.where(ok, x, torch.zeros_like(x)).sum(dim=0) / ok.sum(dim=0)).to(torch.float32)
+
+    out = {"crps": mean(record.crps)}
+    if getattr(record, "energy", None) is not None:
+        out["energy"] = float(mean(record.energy[..., None])[0])
+    if getattr(record, "spread", None) is not None:
+        out["spread"] = mean(record.spread)
+    return out
 
 
 def interval_coverage(lower: torch.Tensor, upper: torch.Tensor, true: torch.Tensor, start: int = START_TRUNCATION) -> torch.Tensor:

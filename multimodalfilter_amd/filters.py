@@ -84,6 +84,8 @@ class ParticleFilter(base.Filter):
     an argument of ``smooth``, whose parameter list stays ``(lag, *, method, num_draws)``; another method with it set raises.
     ``belief_quantiles(probs, of=, truth=)``: per-dimension weighted quantiles of the recorded sets (and the PIT of a true
     state) -> ``last_quantiles``; the non-parametric counterpart of the covariance (``mmf_pf_quantiles``).
+    ``belief_scores(truth, of=, scale=)``: CRPS per dimension and the energy score of the recorded sets against the true
+    states -> ``last_scores``; strictly proper, so calibration and sharpness in one number (``mmf_pf_scores``).
     Randomness comes from ``self.noise`` (``utils.NoiseSource``), never from global RNG state.
     """
 
@@ -122,6 +124,7 @@ class ParticleFilter(base.Filter):
         self.last_history = None
         self.last_smoothed = None
         self.last_quantiles = None    # belief_quantiles(): per-dimension weighted quantiles (and the PIT) of the recorded sets
+        self.last_scores = None       # belief_scores(): CRPS, energy score and sharpness of the recorded sets against the truth
         self.record_transition_moments = False  # smooth(method="marginal") adds the two-slice residual moments to last_smoothed
         self._step_history = None
         self.use_native_loop = True   # False: forward_loop keeps the step-by-step Python loop
@@ -794,6 +797,79 @@ class ParticleFilter(base.Filter):
         self.last_smoothed = base.belief_record(indices=indices, log_posterior=log_posterior, lag=None, method="map")
         return path
 
+    def _recorded_sets(self, of: str, who: str):
+        """``(states (T, N, M, d), log_a, log_b)`` of the weighted particle sets that ``who`` (``belief_quantiles``,
+        ``belief_scores``) reads: ``of="filtered"`` the history's ``states`` under ``log_weights_in + log_likelihoods``;
+        ``of="smoothed"`` the history's states under ``log(weights)`` after the marginal smoother, the drawn ``trajectories``
+        with no weights after backward simulation.  Everything else is the ``ValueError`` of ``who``."""
+        h = self.last_history
+        if of == "filtered":
+            if h is None or getattr(h, "states", None) is None:
+                raise ValueError(f"{who} needs a history: set record_history and run forward_loop (evaluation mode) first")
+            return h.states, h.log_weights_in, h.log_likelihoods
+        s = self.last_smoothed
+        if s is None:
+            raise ValueError(f"{who}(of='smoothed') needs a smoothed record: call smooth(method='marginal') or "
+                             "smooth(method='simulation') first")
+        method = getattr(s, "method", "ancestry")
+        if method == "marginal":
+            if h is None or getattr(h, "states", None) is None or tuple(h.states.shape[:3]) != tuple(s.weights.shape):
+                raise ValueError(f"{who}(of='smoothed'): the marginal smoother's weights belong to a history that "
+                                 "is no longer there: run forward_loop with record_history and smooth again")
+            with torch.no_grad():
+                return h.states, torch.log(s.weights), None
+        if method == "simulation":
+            return s.trajectories, None, None
+        if method == "map":
+            raise ValueError(f"{who}(of='smoothed'): smooth(method='map') leaves one path, and a path is not a "
+                             "distribution: smooth with method='marginal' or 'simulation'")
+        raise ValueError(f"{who}(of='smoothed'): smooth(method={method!r}) keeps no per-step weights over the "
+                         "recorded sets: smooth with method='marginal' or 'simulation'")
+
+    def belief_scores(self, truth: torch.Tensor, *, of: str = "filtered", scale=None) -> torch.Tensor:
+        """Strictly proper scores of the recorded particle sets against the true states (``mmf_pf_scores``,
+        ``include/mmf.h``): the continuous ranked probability score per state dimension, ``crps (T, N, d)`` -- returned --
+        and its multivariate form, the energy score ``energy (T, N)``, both ``E|X - y| - 1/2 E|X - X'|`` over the weighted
+        set, the second expectation over all ``M^2`` pairs of a set in HIP.  They reward calibration and sharpness
+        together, are in the state's own units and reduce to the absolute / Euclidean error for a point mass
+        (``evaluation.gaussian_crps`` is the closed form of a Gaussian belief).  ``spread (T, N, d + 1)`` is the sharpness
+        term ``E|X - X'|`` alone, per dimension and, last, in the Euclidean norm.
+        ``truth (T, N, d)`` is required.  ``of`` means what it means for ``belief_quantiles``: ``"filtered"`` reads
+        ``last_history``, ``"smoothed"`` reads ``last_smoothed`` after ``smooth(method="marginal")`` or ``"simulation"``;
+        ``"ancestry"`` and ``"map"`` records are refused.  ``scale``: ``None`` or ``d`` positive finite floats dividing the
+        coordinates inside the Euclidean norm (``energy`` and ``spread[..., d]`` only), for states whose dimensions have
+        different units.  Leaves ``last_scores``: ``crps``, ``energy``, ``spread``, ``of``, ``scale`` (a tuple).  Draws no
+        noise and leaves ``last_history`` / ``last_smoothed`` / ``last_quantiles`` as they are.  A step without a live
+        particle gives NaN; a NaN component of the truth gives NaN in its ``crps`` and in ``energy``."""
+        if of not in ("filtered", "smoothed"):
+            raise ValueError(f"belief_scores: of must be 'filtered' or 'smoothed', got {of!r}")
+        states, log_a, log_b = self._recorded_sets(of, "belief_scores")
+        T, N, M, d = states.shape
+        if M > _abi.SCORES_MAX_M:
+            raise ValueError(f"belief_scores: {M} particles per set; mmf_pf_scores serves at most {_abi.SCORES_MAX_M}")
+        if not isinstance(truth, torch.Tensor) or tuple(truth.shape) != (T, N, d):
+            raise ValueError(f"belief_scores: truth must be a (T, N, d) = ({T}, {N}, {d}) tensor, got "
+                             f"{tuple(truth.shape) if isinstance(truth, torch.Tensor) else type(truth).__name__}")
+        if scale is None:
+            sc = (1.0,) * d
+        else:
+            try:
+                sc = [s for s in scale]
+            except TypeError:
+                raise ValueError(f"belief_scores: scale must be None or {d} positive finite floats, got {scale!r}") from None
+            if len(sc) != d or any(isinstance(s, bool) or not isinstance(s, numbers.Real) or not 0.0 < float(s) < math.inf for s in sc):
+                raise ValueError(f"belief_scores: scale must be None or {d} positive finite floats, got {scale!r}")
+            sc = tuple(float(s) for s in sc)
+        dev = states.device
+        with torch.no_grad():
+            y = truth.detach().to(device=dev, dtype=torch.float32).contiguous()
+            crps = torch.empty((T, N, d), dtype=torch.float32, device=dev)
+            energy = torch.empty((T, N), dtype=torch.float32, device=dev)
+            spread = torch.empty((T, N, d + 1), dtype=torch.float32, device=dev)
+            _abi.pf_scores(states, log_a, log_b, y, crps, energy, spread, sc)
+        self.last_scores = base.belief_record(crps=crps, energy=energy, spread=spread, of=of, scale=sc)
+        return crps
+
     def belief_quantiles(self, probs, *, of: str = "filtered", truth: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Per-dimension weighted quantiles of the recorded particle sets (``mmf_pf_quantiles``, ``include/mmf.h``): the
         non-parametric counterpart of ``record_belief``'s covariance -- median, credible intervals -- for a belief that need
@@ -821,31 +897,7 @@ class ParticleFilter(base.Filter):
             if isinstance(p, bool) or not isinstance(p, numbers.Real) or not 0.0 <= float(p) <= 1.0:  # (a NaN fails the range)
                 raise ValueError(f"belief_quantiles: probs must be floats in [0, 1], got {p!r}")
         ps = tuple(float(p) for p in ps)
-        h = self.last_history
-        log_a = log_b = None
-        if of == "filtered":
-            if h is None or getattr(h, "states", None) is None:
-                raise ValueError("belief_quantiles needs a history: set record_history and run forward_loop (evaluation mode) first")
-            states, log_a, log_b = h.states, h.log_weights_in, h.log_likelihoods
-        else:
-            s = self.last_smoothed
-            if s is None:
-                raise ValueError("belief_quantiles(of='smoothed') needs a smoothed record: call smooth(method='marginal') or "
-                                 "smooth(method='simulation') first")
-            method = getattr(s, "method", "ancestry")
-            if method == "marginal":
-                if h is None or getattr(h, "states", None) is None or tuple(h.states.shape[:3]) != tuple(s.weights.shape):
-                    raise ValueError("belief_quantiles(of='smoothed'): the marginal smoother's weights belong to a history that "
-                                     "is no longer there: run forward_loop with record_history and smooth again")
-                states = h.states
-            elif method == "simulation":
-                states = s.trajectories
-            elif method == "map":
-                raise ValueError("belief_quantiles(of='smoothed'): smooth(method='map') leaves one path, and a path is not a "
-                                 "distribution: smooth with method='marginal' or 'simulation'")
-            else:
-                raise ValueError(f"belief_quantiles(of='smoothed'): smooth(method={method!r}) keeps no per-step weights over the "
-                                 "recorded sets: smooth with method='marginal' or 'simulation'")
+        states, log_a, log_b = self._recorded_sets(of, "belief_quantiles")
         T, N, M, d = states.shape
         if M > _abi.QUANTILES_MAX_M:
             raise ValueError(f"belief_quantiles: {M} particles per set; mmf_pf_quantiles sorts at most {_abi.QUANTILES_MAX_M} in LDS")
@@ -854,8 +906,6 @@ class ParticleFilter(base.Filter):
                              f"{tuple(truth.shape) if isinstance(truth, torch.Tensor) else type(truth).__name__}")
         dev = states.device
         with torch.no_grad():
-            if of == "smoothed" and method == "marginal":
-                log_a = torch.log(self.last_smoothed.weights)
             query = None if truth is None else truth.detach().to(device=dev, dtype=torch.float32).contiguous()
             quantiles = torch.empty((T, N, len(ps), d), dtype=torch.float32, device=dev)
             pit = None if query is None else torch.empty((T, N, d), dtype=torch.float32, device=dev)

@@ -1,0 +1,349 @@
+"""Particle-posterior scores on the GPU: ``mmf_pf_scores`` (``csrc/pf_scores.hip``) against the fp64 definition of
+``tests/_score_cases.py`` on its whole family, its bit-for-bit identities (two calls, a row alone, a point mass), the scale
+of the energy score, the particle limit, and ``ParticleFilter.belief_scores`` / ``evaluation.run_filter(return_scores=)`` end
+to end on small real filters.
+
+The bar: ``rel_err_elementwise(got, fp64, floor=1e-3) < REL_TOL`` for ``crps``, ``energy`` and ``spread``, with NaN exactly
+where the definition puts it.  Every figure is printed before it is asserted."""
+import functools
+import itertools
+
+import numpy as np
+import pytest
+import torch
+
+import _quantile_cases as qc
+import _score_cases as sk
+import _smooth_cases as sc
+from _tol import REL_TOL
+
+pytestmark = pytest.mark.gpu
+
+OUTPUTS = ("crps", "energy", "spread")
+
+
+class _Guarded:
+    """A float32 device array of ``rows`` leading slices between ``GUARD_ROWS`` guard slices holding the sentinel."""
+
+    def __init__(self, rows, tail, dev):
+        self.full = torch.full((rows + 2 * sk.GUARD_ROWS,) + tuple(tail), sk.SENTINEL, dtype=torch.float32, device=dev)
+        self.view = self.full[sk.GUARD_ROWS:sk.GUARD_ROWS + rows]
+
+    def guards_intact(self):
+        g = sk.GUARD_ROWS
+        return bool((self.full[:g] == sk.SENTINEL).all()) and bool((self.full[self.full.shape[0] - g:] == sk.SENTINEL).all())
+
+    def untouched(self):
+        return bool((self.full == sk.SENTINEL).all())
+
+
+def _run(case, want=OUTPUTS, rows=None, states=None):
+    """``_abi.pf_scores`` on a case (or on ``rows`` of it) with every output between guard rows; the outputs not in ``want``
+    are handed over as null and their buffers must come back untouched -> ``dict`` of device tensors (``None`` for those)."""
+    from multimodalfilter_amd import _abi
+
+    dev = sc.dev()
+    pick = (lambda x: x) if rows is None else (lambda x: None if x is None else x[rows])
+    X, la, lb, y = (sc.to_device(pick(case[k])) for k in ("states", "log_a", "log_b", "truth"))
+    if states is not None:
+        X = states
+    R, M, d = X.shape
+    bufs = {"crps": _Guarded(R, (d,), dev), "energy": _Guarded(R, (), dev), "spread": _Guarded(R, (d + 1,), dev)}
+    _abi.pf_scores(X, la, lb, y, *(bufs[k].view if k in want else None for k in OUTPUTS), scale=case["scale"])
+    torch.cuda.synchronize()
+    for k, b in bufs.items():
+        assert b.guards_intact(), f"a guard row of {k} was written (M={M} d={d} R={R})"
+        if k not in want:
+            assert b.untouched(), f"{k} was not asked for and was written (M={M} d={d} R={R})"
+    return {k: (bufs[k].view.clone() if k in want else None) for k in OUTPUTS}
+
+
+N = lambda t: None if t is None else t.cpu().numpy()
+
+
+def _same_bits(a, b):
+    return torch.equal(a.view(torch.int32), b.view(torch.int32))
+
+
+def _hold(case, ref, got, what):
+    """The three outputs against the reference (those the case has); returns the errors."""
+    errs = {}
+    for k, want in zip(OUTPUTS, ref):
+        if want is None:
+            continue
+        errs[k] = sk.compare(N(got[k]), want, f"{what} {k}")
+    print(f"{what}: " + ", ".join(f"{k} {e:.3e}" for k, e in errs.items()) + f" (bar {REL_TOL:.0e})")
+    for k, e in errs.items():
+        assert e < REL_TOL, (what, k, e)
+    return errs
+
+
+# ------------------------------------------------------------------------------------------ 1. the kernel against the definition
+@pytest.mark.parametrize("M", sk.ALL_MS)
+def test_kernel_holds_the_definition_on_the_family(M):
+    for M_, d, R, variant in sk.family():
+        if M_ != M:
+            continue
+        case, ref = sk.family_case(M, d, R, variant)
+        want = OUTPUTS if case["truth"] is not None else ("spread",)
+        got = _run(case, want)
+        _hold(case, ref, got, f"M={M} d={d} R={R} {variant}")
+
+
+@pytest.mark.parametrize("M", [65, sk.I_BLOCK, sk.I_BLOCK + 1, 1000])
+def test_every_allowed_combination_of_null_outputs_writes_only_what_was_asked_for(M):
+    """With a truth every non-empty subset of the three outputs, without one the spread alone; what is written has the
+    bits of the full call (the untouched buffers are checked inside ``_run``)."""
+    case, _ = sk.family_case(M, 3, 3, "plain") if M <= sk.SMALL else (sk.make_case(M, 3, 3, "plain"), None)
+    full = _run(case)
+    for n in (1, 2):
+        for want in itertools.combinations(OUTPUTS, n):
+            got = _run(case, want)
+            for k in want:
+                assert _same_bits(got[k], full[k]), (M, want, k)
+    alone = _run(dict(case, truth=None), ("spread",))
+    assert _same_bits(alone["spread"], full["spread"])
+
+
+def test_kernel_at_the_particle_limit():
+    """32 workgroups per row, 16 j-tiles each."""
+    case = sk.make_case(sk.MAX_M, 1, 1, "plain")
+    _hold(case, sk.reference(case), _run(case), f"M={sk.MAX_M} d=1")
+
+
+# ------------------------------------------------------------------------------------------ 2. bit-for-bit identities
+@pytest.mark.parametrize("M", [1, 65, 257, sk.I_BLOCK, sk.I_BLOCK + 1, sk.J_TILE + 1, 4096])
+def test_two_calls_and_a_row_alone_give_the_same_bits(M):
+    for d, variant in ((1, "plain"), (3, "dead_row"), (4, "scaled")):
+        case = sk.make_case(M, d, 3, variant)
+        got = _run(case)
+        again = _run(case)
+        for k in OUTPUTS:
+            assert _same_bits(got[k], again[k]), (M, d, variant, k)
+        for r in range(3):
+            one = _run(case, rows=slice(r, r + 1))
+            for k in OUTPUTS:
+                assert _same_bits(one[k], got[k][r:r + 1]), (M, d, variant, r, k)
+
+
+def test_a_point_mass_has_no_spread_exactly():
+    for d in sk.DIMS:
+        for variant in ("plain", "uniform", "scaled"):
+            case = sk.make_case(1, d, 3, variant)
+            got = _run(case)
+            assert bool((got["spread"] == 0).all()), (d, variant)
+            e = case["states"][:, 0, :].astype(np.float64) - case["truth"]
+            assert np.allclose(N(got["crps"]), np.abs(e), rtol=1e-6, atol=0)
+            assert np.allclose(N(got["energy"]), np.sqrt(((e / sk._scale64(case)) ** 2).sum(-1)), rtol=1e-6, atol=0)
+
+
+def test_one_dimension_with_unit_scale_has_energy_equal_to_crps():
+    for M in (2, 65, 1000):
+        case = sk.make_case(M, 1, 3, "plain")
+        got = _run(case)
+        assert _same_bits(got["energy"], got["crps"][:, 0]) and _same_bits(got["spread"][:, 1], got["spread"][:, 0])
+
+
+# ------------------------------------------------------------------------------------------ 3. the scale
+@pytest.mark.parametrize("M", [65, 1000])
+def test_scale_divides_the_coordinates_of_the_norm_only(M):
+    """``energy`` / ``spread[d]`` under a scale equal those of pre-divided states under none, to ``REL_TOL``; ``crps`` and the
+    per-dimension ``spread`` do not see the scale at all."""
+    for d in (2, 3, 4):
+        case = sk.make_case(M, d, 3, "scaled")
+        s = np.asarray(case["scale"], np.float32)
+        got = _run(case)
+        unscaled = _run(dict(case, scale=None))
+        assert _same_bits(got["crps"], unscaled["crps"]) and _same_bits(got["spread"][:, :d], unscaled["spread"][:, :d])
+        assert not _same_bits(got["energy"], unscaled["energy"])
+        divided = dict(case, states=case["states"] / s, truth=case["truth"] / s, scale=None)
+        pre = _run(divided)
+        e_energy = sk.compare(N(got["energy"]), N(pre["energy"]).astype(np.float64), "energy")
+        e_spread = sk.compare(N(got["spread"][:, d]), N(pre["spread"][:, d]).astype(np.float64), "spread[d]")
+        print(f"M={M} d={d}: scaled against pre-divided energy {e_energy:.3e}, spread[d] {e_spread:.3e}")
+        assert e_energy < REL_TOL and e_spread < REL_TOL
+
+
+# ------------------------------------------------------------------------------------------ 4. through the filter
+@functools.lru_cache(maxsize=None)
+def _filter_run(M, N_=3, T=6):
+    import multimodalfilter_amd as mmf
+
+    dev = sc.dev()
+    f, d, traj, obs, ctrl, cov = sc.small_filter("DoorCrossmodalParticleFilter", N_, M, T, dev)
+
+    def forward():
+        f.record_history = True
+        f.noise = mmf.NoiseSource(31)
+        f.initialize_beliefs(mean=traj["states"][0], covariance=cov)
+        est = f.forward_loop(observations=obs, controls=ctrl)
+        torch.cuda.synchronize()
+        return est
+
+    return f, forward, traj, (T, N_, M, d)
+
+
+def _case_of(states, log_a, log_b, truth, scale=None):
+    T, N_, M, d = states.shape
+    flat = lambda x, tail: None if x is None else x.detach().cpu().numpy().reshape((T * N_,) + tail)
+    return dict(states=flat(states, (M, d)), log_a=flat(log_a, (M,)), log_b=flat(log_b, (M,)), truth=flat(truth, (d,)), scale=scale)
+
+
+def _hold_record(rec, case, shape, what):
+    T, N_, M, d = shape
+    got = {"crps": rec.crps.reshape(T * N_, d), "energy": rec.energy.reshape(T * N_), "spread": rec.spread.reshape(T * N_, d + 1)}
+    _hold(case, sk.reference(case), got, what)
+
+
+@pytest.mark.parametrize("M", [64, 300])
+def test_belief_scores_on_a_real_filter(M):
+    """``of="filtered"``, ``of="smoothed"`` after the marginal smoother and after backward simulation equal the fp64
+    definition evaluated on the records' own arrays.  Nothing else moves: the estimates, the history, the smoothed record,
+    the quantile record and the noise stream are what they are without the calls."""
+    from multimodalfilter_amd.utils import ReplayNoise
+
+    f, forward, traj, shape = _filter_run(M)
+    T, N_, _, d = shape
+    est = forward().clone()
+    h = f.last_history
+    truth = traj["states"][1:]
+    before = {k: getattr(h, k).clone() for k in ("states", "log_likelihoods", "log_weights_in", "ancestors") if getattr(h, k) is not None}
+    f.belief_quantiles((0.5,), truth=truth)
+    quantiles = f.last_quantiles
+    kept_q = quantiles.quantiles.clone()
+    f.last_scores = None
+    crps = f.belief_scores(truth)
+    rec = f.last_scores
+    assert set(vars(rec)) == {"crps", "energy", "spread", "of", "scale"} and rec.of == "filtered" and rec.scale == (1.0,) * d
+    assert rec.crps is crps and crps.shape == (T, N_, d) and rec.energy.shape == (T, N_) and rec.spread.shape == (T, N_, d + 1)
+    _hold_record(rec, _case_of(h.states, h.log_weights_in, h.log_likelihoods, truth), shape, f"M={M} filtered")
+    assert bool((crps >= 0).all()) and bool((rec.energy >= 0).all()) and bool((rec.spread >= 0).all())
+    scale = (0.5, 2.0, 4.0)
+    scaled = f.belief_scores(truth, scale=scale)
+    assert f.last_scores.scale == scale and torch.equal(scaled, crps) and not torch.equal(f.last_scores.energy, rec.energy)
+    _hold_record(f.last_scores, _case_of(h.states, h.log_weights_in, h.log_likelihoods, truth, scale), shape, f"M={M} filtered, scaled")
+    assert f.last_quantiles is quantiles and torch.equal(quantiles.quantiles, kept_q)
+    after = f.noise.uniform((4, 5), like=h.states).clone()  # where the noise stream stands after the calls ...
+    assert torch.equal(forward(), est)
+    assert torch.equal(f.noise.uniform((4, 5), like=h.states), after)  # ... is where it stands without them
+    f.last_history = h
+    for k, x in before.items():
+        assert torch.equal(getattr(h, k), x), k
+
+    # the marginal smoother's weights over the history's states
+    mean = f.smooth(method="marginal").clone()
+    s = f.last_smoothed
+    weights = s.weights.clone()
+    f.belief_scores(truth, of="smoothed")
+    assert f.last_smoothed is s and torch.equal(s.weights, weights) and f.last_scores.of == "smoothed"
+    _hold_record(f.last_scores, _case_of(h.states, torch.log(weights), None, truth), shape, f"M={M} marginal")
+    assert torch.equal(f.smooth(method="marginal"), mean)
+
+    # backward simulation: 16 equally weighted draws per step
+    S = 16
+    f.noise = ReplayNoise(uniforms=[torch.rand((T, N_, S), generator=torch.Generator().manual_seed(5))])
+    f.smooth(method="simulation", num_draws=S)
+    s = f.last_smoothed
+    assert bool(torch.isfinite(s.trajectories).all())
+    f.belief_scores(truth, of="smoothed")
+    _hold_record(f.last_scores, _case_of(s.trajectories, None, None, truth), (T, N_, S, d), f"M={M} simulation")
+    assert f.last_smoothed is s and f.last_history is h and f.last_quantiles is quantiles
+    for k, x in before.items():
+        assert torch.equal(getattr(h, k), x), k
+    for method in ("ancestry", "map"):
+        f.smooth(method=method)
+        kept = f.last_scores
+        with pytest.raises(ValueError, match="of='smoothed'"):
+            f.belief_scores(truth, of="smoothed")
+        assert f.last_scores is kept
+
+
+# ------------------------------------------------------------------------------------------ 5. run_filter(return_scores=)
+def test_run_filter_places_the_score_record_before_the_quantiles():
+    import multimodalfilter_amd as mmf
+    from multimodalfilter_amd import evaluation
+
+    dev = sc.dev()
+    N_, M, T = 3, 64, 6
+    f, d, traj, obs, ctrl, cov = sc.small_filter("DoorCrossmodalParticleFilter", N_, M, T, dev)
+    f.noise = mmf.CounterNoise(7)
+    plain = evaluation.run_filter(f, traj)
+    f.noise = mmf.CounterNoise(7)
+    off = evaluation.run_filter(f, traj, return_scores=False)
+    assert isinstance(off, torch.Tensor) and torch.equal(off, plain)
+    f.noise = mmf.CounterNoise(7)
+    est, rec = evaluation.run_filter(f, traj, return_scores=True)
+    assert f.record_history is False and f.record_belief is False  # put back
+    assert torch.equal(est, plain)
+    assert rec is f.last_scores and rec.of == "filtered" and rec.crps.shape == (T, N_, d) and rec.energy.shape == (T, N_)
+    h = f.last_history
+    _hold_record(rec, _case_of(h.states, h.log_weights_in, h.log_likelihoods, traj["states"][1:]), (T, N_, M, d), "run_filter")
+    summary = evaluation.score_summary(rec, start=0)
+    assert set(summary) == {"crps", "energy", "spread"} and summary["crps"].shape == (d,) and summary["spread"].shape == (d + 1,)
+    assert torch.allclose(summary["crps"], rec.crps.double().mean((0, 1)).float(), rtol=1e-6) and summary["energy"] > 0
+    f.noise = mmf.CounterNoise(7)
+    out = evaluation.run_filter(f, traj, return_belief=True, return_scores=True, score_scale=(0.5, 2.0, 4.0),
+                                return_quantiles=(0.5,))
+    assert len(out) == 4 and out[1] is f.last_belief and out[2] is f.last_scores and out[3] is f.last_quantiles
+    assert out[2].scale == (0.5, 2.0, 4.0) and torch.equal(out[2].crps, rec.crps) and torch.equal(out[0], plain)
+    f.noise = mmf.CounterNoise(7)
+    out = evaluation.run_filter(f, traj, smooth_method="marginal", return_scores=True, return_quantiles=(0.5,))
+    assert len(out) == 3 and out[1] is f.last_scores and out[1].of == "smoothed" and out[2] is f.last_quantiles
+    assert out[2].of == "smoothed" and f.record_history is False and f.record_belief is False
+    f.noise = mmf.NoiseSource(7)  # (backward simulation draws (T, N, S) uniforms, which a CounterNoise does not)
+    out = evaluation.run_filter(f, traj, smooth_method="simulation", smooth_draws=8, return_belief=True, return_scores=True)
+    assert len(out) == 3 and out[1] is f.last_smoothed and out[2].of == "smoothed" and out[2].spread.shape == (T, N_, d + 1)
+
+
+def test_run_filter_scores_a_kalman_filter_in_closed_form():
+    import multimodalfilter_amd as mmf
+    from multimodalfilter_amd import evaluation
+
+    dev = sc.dev()
+    N_, T = 3, 6
+    f, d, traj = _task_filter(mmf.door_models.DoorKalmanFilter, N_, T, dev)
+    plain = evaluation.run_filter(f, traj)
+    est, belief = evaluation.run_filter(f, traj, return_belief=True)
+    assert torch.equal(est, plain)
+    est2, rec = evaluation.run_filter(f, traj, return_scores=True)
+    assert f.record_belief is False and torch.equal(est2, plain)
+    assert set(vars(rec)) == {"crps", "of", "scale"} and rec.of == "filtered" and rec.crps.shape == (T, N_, d)
+    assert torch.equal(rec.crps, evaluation.gaussian_crps(est, belief.covariance, traj["states"][1:]))
+    assert bool((rec.crps > 0).all()) and set(evaluation.score_summary(rec, start=0)) == {"crps"}
+    out = evaluation.run_filter(f, traj, return_belief=True, return_innovations=True, return_scores=True)
+    assert len(out) == 4 and out[2] is f.last_innovations and torch.equal(out[3].crps, rec.crps)
+    # smoothed: the smoothed means under the smoothed covariance
+    sm, srec = evaluation.run_filter(f, traj, smooth_lag=None, return_belief=True)
+    sm2, rec2 = evaluation.run_filter(f, traj, smooth_lag=None, return_scores=True)
+    assert torch.equal(sm, sm2) and rec2.of == "smoothed"
+    assert torch.equal(rec2.crps, evaluation.gaussian_crps(sm, srec.covariance, traj["states"][1:]))
+
+
+def test_run_filter_scores_an_lstm_baseline_as_a_point_mass():
+    import multimodalfilter_amd as mmf
+    from multimodalfilter_amd import evaluation
+
+    dev = sc.dev()
+    N_, T = 3, 6
+    f, d, traj = _task_filter(mmf.door_models.DoorLSTMFilter, N_, T, dev)
+    plain = evaluation.run_filter(f, traj)
+    est, rec = evaluation.run_filter(f, traj, return_scores=True, score_scale=(0.5, 2.0, 4.0))
+    assert torch.equal(est, plain) and set(vars(rec)) == {"crps", "energy", "of", "scale"}
+    e = est - traj["states"][1:]
+    assert torch.equal(rec.crps, e.abs())
+    want = torch.sqrt(((e / torch.tensor((0.5, 2.0, 4.0), device=dev)) ** 2).sum(-1))
+    assert torch.allclose(rec.energy, want, rtol=1e-6, atol=0)
+    assert set(evaluation.score_summary(rec, start=0)) == {"crps", "energy"}
+
+
+def _task_filter(ctor, N_, T, dev):
+    """A door filter with its initial weights and ``N_`` synthetic trajectories of ``T`` steps (no calibration: these
+    filters have no measurement heads to calibrate)."""
+    from multimodalfilter_amd import synthetic
+    from oracle import models as om
+
+    d = om.TASKS["door"].state_dim
+    torch.manual_seed(3)
+    f = ctor().to(dev).eval()
+    traj = {k: v.to(dev) for k, v in synthetic.make_trajectories(state_dim=d, T=T, N=N_, seed=17).items()}
+    return f, d, traj
