@@ -1015,6 +1015,73 @@ typedef struct MmfPfScoresArgs {
 int mmf_pf_scores(const MmfPfScoresArgs* args /* host */, void* stream);
 size_t mmf_pf_scores_workspace_bytes(int R, int M, int d);
 
+/* ---------------------------------------------------------------- Particle-posterior density: log score, mode, entropy
+ * The evaluation of crossmodal/eval_helpers.py:148-160 scores point estimates only; the scores above rank a belief as a
+ * distribution but not by the logarithmic score, the "NLL" the filtering literature reports, and the only per-step point
+ * estimate of a multimodal belief is its mean, which lies between the modes.  All three missing figures -- the log score of
+ * the truth, the mode (the particle where the density is highest) and the entropy -- are functions of a kernel density
+ * estimate of the weighted set evaluated at M + 1 points: M^2 pairs per set with an exp each, in torch ops an (M, M, d)
+ * tensor or a chunked logsumexp loop over one.  Purely additive to ABI 42: a struct and two symbols of their own.
+ * Per row r (R rows, e.g. T * N, of M particles x_m = states[r, m, :]) with an optional truth y = truth[r, :]:
+ *   a_m, w_m = expf(a_m - max a), W_m = w_m / sum w      exactly as in "Particle-posterior scores"
+ *   n_eff    = 1 / sum W_m^2
+ *   mu_k     = sum W_m x_mk      sigma_k^2 = sum W_m (x_mk - mu_k)^2     two passes, in double, live particles only, no
+ *                                                                       Bessel term
+ *   c        = rule 1 (Silverman): (4 / ((d + 2) n_eff))^(1/(d+4))      rule 2 (Scott): n_eff^(-1/(d+4))
+ *   h_k      = max(sigma_k c, min_bandwidth[k])       rules 1, 2;   rule 0: h_k = bandwidth[k] as given
+ *   log p(q) = log sum_m W_m exp(-1/2 sum_k ((q_k - x_mk) / h_k)^2) - sum_k log h_k - (d/2) log 2 pi
+ *   log_density[m] = log p(x_m) where w_m > 0, -inf where w_m = 0
+ *   log_score      = log p(y)
+ *   entropy        = - sum_{m live} W_m log p(x_m)     the resubstitution estimate; the zero weight selects a dead term away
+ *   mode_index     = the lowest live m whose log_density[m] (the float that is written) is the row maximum
+ *   mode           = a bit copy of states[r, mode_index, :]
+ *   bandwidth_out[k] = h_k
+ * A Gaussian product kernel, one bandwidth per dimension: the form that stays meaningful when the dimensions have different
+ * units.  No full-covariance bandwidth and no leave-one-out.
+ *   - a row without a live particle gives NaN in every float output and mode_index = -1;
+ *   - a NaN y_k gives NaN in log_score only;
+ *   - a dead particle's NaN row never reaches a sum.
+ * log p is a true log-sum-exp: the running maximum is taken over the exponents log w_m - 1/2 z themselves, so it is finite
+ * wherever the fp64 definition is finite and 1/2 sum ((q - x) / h)^2 is representable in fp32 -- a truth 5 sigma off a
+ * collapsed set is the normal case of a log score.  The kernel takes the coordinates relative to float(mu_k) before it
+ * multiplies them by the fp32 reciprocal 1 / h_k (h_k rounded to float), and works in base 2: e = log2 w_m - z (1/2 log2 e).
+ * Determinism: every sum is taken in a fixed order and there are no floating-point atomics -- two calls give the same bits,
+ * a row's result depends on neither R nor the other rows (the plan is a function of M alone), the particle outputs are the
+ * same bits with and without a truth, and whichever outputs are null, the others are the bits of the full call.
+ * Kernel plan: no (M, M) array in memory.  A row is dealt to nb = ceil(M / 512) workgroups in equal i-chunks; every workgroup
+ * forms the row's max a, sum w, sum w^2, mu, sigma^2 and h itself, in one fixed order.  A thread holds one query particle
+ * (M <= 512) or two in registers and walks j-tiles of 1024 particles staged through LDS as structure-of-arrays (d planes of
+ * (x - mu) / h, one of log2 w), four j per broadcast 16-byte read; per query a running maximum and an fp32 sum rescaled once
+ * per four j.  The truth is one more query per row, its j dealt over the threads of the row's first workgroup.  Entropy terms
+ * in double and the (value, index) of the mode are reduced in a fixed order; with nb == 1 the workgroup writes the row,
+ * otherwise it leaves a partial in the workspace and a finishing kernel takes a row's nb partials in block order.
+ * mmf_pf_density_workspace_bytes(R, M, d): 16 R nb bytes for M > 512, 0 up to 512 (and for R, M or d below 1).
+ * Limits, all decided on the host before any HIP call: null args / states, d outside 1 .. 4, M < 1, R < 0, rule outside
+ * 0 .. 2, a bandwidth[k < d] (rule 0) or min_bandwidth[k < d] (rules 1, 2) that is not positive and finite, all six outputs
+ * null, log_score without truth, a workspace that is needed and null, smaller than the query's answer or not 8-byte aligned,
+ * an output (or the workspace) overlapping an input or another output -> MMF_EINVAL; M > 16384 or R * nb beyond a 32-bit
+ * grid -> MMF_ETOOLARGE; R == 0 is a successful no-op. */
+typedef struct MmfPfDensityArgs {
+  int32_t R, M, d;                          /* R rows (e.g. T*N) of M particles */
+  int32_t rule;                             /* 0: bandwidth[] as given; 1: Silverman; 2: Scott */
+  float bandwidth[MMF_MAX_STATE_DIM];       /* host values, read with rule 0: bandwidth[k < d] > 0 and finite */
+  float min_bandwidth[MMF_MAX_STATE_DIM];   /* host values, read with rules 1, 2: the floor of h_k, > 0 and finite */
+  const float* states;                      /* (R, M, d) */
+  const float* log_a;                       /* (R, M) or null = 0 */
+  const float* log_b;                       /* (R, M) or null = 0 (history: log_weights_in + log_likelihoods) */
+  const float* truth;                       /* (R, d); null allowed without log_score */
+  float* log_density;                       /* (R, M) or null */
+  float* log_score;                         /* (R) or null */
+  float* entropy;                           /* (R) or null */
+  float* mode;                              /* (R, d) or null */
+  int32_t* mode_index;                      /* (R) or null */
+  float* bandwidth_out;                     /* (R, d) or null */
+  void* workspace;                          /* device, 8-byte aligned, mmf_pf_density_workspace_bytes(R, M, d) bytes; unused when that is 0 */
+  size_t workspace_bytes;
+} MmfPfDensityArgs;                         /* host struct holding device pointers */
+int mmf_pf_density(const MmfPfDensityArgs* args /* host */, void* stream);
+size_t mmf_pf_density_workspace_bytes(int R, int M, int d);
+
 /* ---------------------------------------------------------------- K6, fused: one network call of the training backward
  * Recompute (the forward pass's f16x3 arithmetic), backward data path and weight / bias gradients of ONE per-particle
  * network over N * M rows in one kernel (the dynamics network: three launches -- encoder forward, trunk, encoder

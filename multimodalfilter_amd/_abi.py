@@ -153,6 +153,18 @@ class MmfPfScoresArgs(Structure):
                 ("workspace", _FP), ("workspace_bytes", c_size_t)]
 
 
+DENSITY_MAX_M = 16384  # particles per row that mmf_pf_density serves
+DENSITY_RULES = {"fixed": 0, "silverman": 1, "scott": 2}  # MmfPfDensityArgs.rule
+
+
+class MmfPfDensityArgs(Structure):
+    _fields_ = [("R", c_int32), ("M", c_int32), ("d", c_int32), ("rule", c_int32),
+                ("bandwidth", ctypes.c_float * MMF_MAX_STATE_DIM), ("min_bandwidth", ctypes.c_float * MMF_MAX_STATE_DIM),
+                ("states", _FP), ("log_a", _FP), ("log_b", _FP), ("truth", _FP), ("log_density", _FP), ("log_score", _FP),
+                ("entropy", _FP), ("mode", _FP), ("mode_index", _FP), ("bandwidth_out", _FP),
+                ("workspace", _FP), ("workspace_bytes", c_size_t)]
+
+
 class MmfTrainNet(Structure):
     _fields_ = [("packed", _FP), ("packed_f32", _FP), ("packed_t", _FP), ("head_w", _FP), ("pw", _FP), ("pb", _FP),
                 ("p_first", _FP), ("p_head", _FP), ("p_dout", _FP), ("p_traj", _FP), ("packed_dual", _FP)]
@@ -258,6 +270,8 @@ SIGNATURES = {
     "mmf_pf_quantiles_lds_bytes": (c_size_t, [c_int]),
     "mmf_pf_scores": (c_int, [POINTER(MmfPfScoresArgs), c_void_p]),
     "mmf_pf_scores_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "mmf_pf_density": (c_int, [POINTER(MmfPfDensityArgs), c_void_p]),
+    "mmf_pf_density_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "mmf_pf_dedup_plan": (c_int, [c_int, c_int, c_int, ctypes.c_float, c_int]),
     "mmf_pf_dedup_workspace_words": (c_size_t, [c_int, c_int]),
     "mmf_pf_resample_runs": (c_int, [_FP] * 11 + [c_int, c_int, c_int, _FP, _FP, _FP, c_void_p]),
@@ -1175,3 +1189,50 @@ def pf_scores(states, log_a, log_b, truth, crps, energy, spread, scale=None):
         work = torch.empty((need // 8,), dtype=torch.float64, device=states.device) if need else None
         a.workspace, a.workspace_bytes = vp(work, torch.float64), need
         _check(load().mmf_pf_scores(ctypes.byref(a), stream_of(states)), "mmf_pf_scores")
+
+
+def pf_density_workspace_bytes(R: int, M: int, d: int) -> int:
+    return int(load().mmf_pf_density_workspace_bytes(int(R), int(M), int(d)))
+
+
+def pf_density(states, log_a, log_b, truth, *, rule="silverman", bandwidth=None, min_bandwidth=None, log_density=None,
+               log_score=None, entropy=None, mode=None, mode_index=None, bandwidth_out=None):
+    """Gaussian product-kernel density of weighted particle sets (``mmf_pf_density``, include/mmf.h): ``states (..., M, d)``
+    -- ``R`` rows, the product of the leading sizes -- with log-weights ``log_a + log_b``, each ``(..., M)`` or ``None`` (0;
+    both ``None``: uniform), and ``truth (..., d)`` or ``None`` -> ``log_density (..., M)``, ``log_score (...)`` (needs the
+    truth), ``entropy (...)``, ``mode (..., d)``, ``mode_index (...)`` int32, ``bandwidth_out (..., d)``, each of which may be
+    ``None`` (not all six).  ``rule``: ``"silverman"`` or ``"scott"`` with ``min_bandwidth``, ``d`` positive finite host
+    floats, the floor of the bandwidths; ``"fixed"`` with ``bandwidth``, ``d`` positive finite host floats.  The workspace of
+    the partial results is allocated here, on the tensors' device."""
+    lead, (M, d) = tuple(states.shape[:-2]), states.shape[-2:]
+    R = 1
+    for n in lead:
+        R *= int(n)
+    if rule not in DENSITY_RULES:
+        raise MmfError(f"mmf_pf_density: rule must be one of {sorted(DENSITY_RULES)}, got {rule!r}")
+    given = bandwidth if rule == "fixed" else min_bandwidth
+    given = [] if given is None else [float(h) for h in given]
+    if len(given) != d or d > MMF_MAX_STATE_DIM:
+        raise MmfError(f"mmf_pf_density takes one {'bandwidth' if rule == 'fixed' else 'min_bandwidth'} per state dimension "
+                       f"(d = {d} <= {MMF_MAX_STATE_DIM}), got {len(given)}")
+    assert log_a is None or tuple(log_a.shape) == lead + (M,)
+    assert log_b is None or tuple(log_b.shape) == lead + (M,)
+    assert truth is None or tuple(truth.shape) == lead + (d,)
+    assert log_density is None or tuple(log_density.shape) == lead + (M,)
+    assert log_score is None or tuple(log_score.shape) == lead
+    assert entropy is None or tuple(entropy.shape) == lead
+    assert mode is None or tuple(mode.shape) == lead + (d,)
+    assert mode_index is None or tuple(mode_index.shape) == lead
+    assert bandwidth_out is None or tuple(bandwidth_out.shape) == lead + (d,)
+    a = MmfPfDensityArgs()
+    a.R, a.M, a.d, a.rule = R, M, d, DENSITY_RULES[rule]
+    for i, h in enumerate(given):
+        (a.bandwidth if rule == "fixed" else a.min_bandwidth)[i] = h
+    a.states, a.log_a, a.log_b, a.truth = vp(states), vp(log_a), vp(log_b), vp(truth)
+    a.log_density, a.log_score, a.entropy = vp(log_density), vp(log_score), vp(entropy)
+    a.mode, a.mode_index, a.bandwidth_out = vp(mode), vp(mode_index, torch.int32), vp(bandwidth_out)
+    with _on(states):
+        need = pf_density_workspace_bytes(R, M, d)
+        work = torch.empty((need // 8,), dtype=torch.float64, device=states.device) if need else None
+        a.workspace, a.workspace_bytes = vp(work, torch.float64), need
+        _check(load().mmf_pf_density(ctypes.byref(a), stream_of(states)), "mmf_pf_density")

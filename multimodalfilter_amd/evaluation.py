@@ -20,12 +20,14 @@ class _DefaultMethod(str):
 
 
 _DEFAULT_METHOD = _DefaultMethod("ancestry")
+_DEFAULT_BANDWIDTH = _DefaultMethod("silverman")  # likewise the default of ``run_filter(density_bandwidth=)``
 
 
 def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale: float = 0.1,
                measurement_initialize: bool = False, return_belief: bool = False, smooth_lag=False,
                smooth_method: str = _DEFAULT_METHOD, smooth_draws: int = _DEFAULT_DRAWS, smooth_transition_moments: bool = False,
-               return_innovations: bool = False, return_quantiles=None, return_scores: bool = False, score_scale=None):
+               return_innovations: bool = False, return_density: bool = False, density_bandwidth=_DEFAULT_BANDWIDTH,
+               return_quantiles=None, return_scores: bool = False, score_scale=None):
     """Initialise the belief at ``states[0]`` with covariance ``0.1 I`` (or from the first
     observation, ``eval_helpers.py:116-131``) and filter ``[1:]`` (``:139-142``).
     ``return_belief``: run with ``record_belief`` set and return ``(estimates, filter_model.last_belief)`` -- the per-step
@@ -66,7 +68,18 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
     them -- the smoothed one when the call smooths -- and no ``energy``, which has no closed form.  A filter with neither (the
     LSTM baselines) gets the scores of a point mass: ``crps = |estimate - true|``, ``energy = |(estimate - true) / s|``.
     ``score_scale``: ``None`` or ``d`` positive finite floats ``s`` for the Euclidean norm of ``energy``; without
-    ``return_scores`` it is refused.  Left at ``False``, every return value and every bit is as without it."""
+    ``return_scores`` it is refused.  Left at ``False``, every return value and every bit is as without it.
+    ``return_density``: appends a density record -- the logarithmic score of the belief at ``traj["states"][1:]``, its
+    entropy and its mode (``density_summary``) -- after the score record and before the quantiles record, which stays last.
+    A particle filter runs with ``record_history`` set (and puts the switch back) and calls ``belief_density(traj["states"][1:],
+    of=..., bandwidth=density_bandwidth)``: ``last_density``, ``of`` chosen and the smoothing methods refused as for
+    ``return_scores``.  A filter with a belief covariance (the Kalman filters) runs with ``record_belief`` set (and puts the
+    switch back); the record holds the closed forms of its Gaussian belief -- ``log_score = gaussian_log_density(...)``,
+    ``entropy = gaussian_entropy(...)`` and ``mode``, the returned means -- under the covariance that goes with them.  A
+    filter with neither (the LSTM baselines) is refused before the run: a point estimate has no density.
+    ``density_bandwidth``: ``"silverman"`` (the default), ``"scott"`` or ``d`` positive finite floats, the
+    ``bandwidth`` of ``belief_density``; without ``return_density`` it is refused.  Left at ``False``, every return value and
+    every bit is as without it."""
     if return_innovations and not hasattr(filter_model, "record_innovations"):  # (before the run, not after it)
         raise ValueError(f"run_filter: return_innovations needs a Kalman filter; {type(filter_model).__name__} has no "
                          "record_innovations (a particle filter reports log_evidence through return_belief)")
@@ -100,6 +113,30 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
                              "leaves none (ancestry keeps no per-step weights, a MAP path is not a distribution): smooth with "
                              "'marginal' or 'simulation', or do not smooth")
         scores_of = "smoothed" if will_smooth else "filtered"
+    want_density = bool(return_density)
+    if density_bandwidth is not _DEFAULT_BANDWIDTH and not want_density:  # (before the run, not after it)
+        raise ValueError("run_filter: density_bandwidth is the bandwidth of return_density's kernel density; without "
+                         "return_density it has no use")
+    density_kind = None
+    if want_density:  # (before the run, not after it)
+        density_kind = ("particles" if hasattr(filter_model, "belief_density") else
+                        "gaussian" if hasattr(filter_model, "record_belief") else None)
+        if density_kind is None:
+            raise ValueError(f"run_filter: return_density needs a belief; {type(filter_model).__name__} returns a point "
+                             "estimate, which has no density (no belief_density, no record_belief)")
+        if not (isinstance(density_bandwidth, str) and density_bandwidth in ("silverman", "scott")):
+            try:
+                density_bandwidth = tuple(float(v) for v in ("" if isinstance(density_bandwidth, str) else density_bandwidth))
+            except (TypeError, ValueError):
+                density_bandwidth = ()
+            if not density_bandwidth or not all(0.0 < v < math.inf for v in density_bandwidth):
+                raise ValueError("run_filter: density_bandwidth must be 'silverman', 'scott' or d positive finite floats")
+        will_smooth = smooth_lag is not False or (named and smooth_method != "ancestry")
+        if density_kind == "particles" and will_smooth and smooth_method not in ("marginal", "simulation"):
+            raise ValueError(f"run_filter: return_density reads a weighted particle set per step; smooth_method={smooth_method!r} "
+                             "leaves none (ancestry keeps no per-step weights, a MAP path is not a distribution): smooth with "
+                             "'marginal' or 'simulation', or do not smooth")
+        density_of = "smoothed" if will_smooth else "filtered"
     want_quantiles = return_quantiles is not None
     if want_quantiles:  # (before the run, not after it)
         if not hasattr(filter_model, "belief_quantiles"):
@@ -117,14 +154,17 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
         raise ValueError(f"run_filter: score_scale must be None or d = {d} positive finite floats, got {score_scale!r}")
     obs = {k: traj[k] for k in ("image", "gripper_pos", "gripper_sensors")}
     was = getattr(filter_model, "record_belief", None)
-    need_belief = return_belief or scores_kind == "gaussian"
+    if isinstance(density_bandwidth, tuple) and len(density_bandwidth) != d:
+        raise ValueError(f"run_filter: density_bandwidth must be 'silverman', 'scott' or d = {d} positive finite floats, got "
+                         f"{density_bandwidth!r}")
+    need_belief = return_belief or scores_kind == "gaussian" or density_kind == "gaussian"
     if need_belief:
         assert was is not None, f"{type(filter_model).__name__} keeps no belief to record"
         filter_model.record_belief = True
     if named and smooth_method != "ancestry" and smooth_lag is False:
         smooth_lag = None
     smoothing = smooth_lag is not False  # (0 is a lag)
-    need_history = smoothing or want_quantiles or scores_kind == "particles"
+    need_history = smoothing or want_quantiles or scores_kind == "particles" or density_kind == "particles"
     if need_history:
         assert hasattr(filter_model, "record_history"), f"{type(filter_model).__name__} keeps no history to smooth"
         was_history = filter_model.record_history
@@ -183,6 +223,17 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
                     energy = torch.linalg.vector_norm(e / torch.tensor(s, dtype=e.dtype, device=e.device), dim=-1)
                     scores = base.belief_record(crps=e.abs(), energy=energy, of=scores_of, scale=s)
         out = (out if isinstance(out, tuple) else (out,)) + (scores,)
+    if want_density:
+        truth = states[1:]
+        if density_kind == "particles":
+            filter_model.belief_density(truth, of=density_of, bandwidth=density_bandwidth)
+            density = filter_model.last_density
+        else:
+            with torch.no_grad():
+                cov = (filter_model.last_smoothed if smoothing else filter_model.last_belief).covariance
+                density = base.belief_record(log_score=gaussian_log_density(est, cov, truth), entropy=gaussian_entropy(cov),
+                                             mode=est, of=density_of)
+        out = (out if isinstance(out, tuple) else (out,)) + (density,)
     if want_quantiles:
         filter_model.belief_quantiles(return_quantiles, of=quantiles_of, truth=states[1:])
         out = (out if isinstance(out, tuple) else (out,)) + (filter_model.last_quantiles,)
@@ -378,6 +429,45 @@ def gaussian_nll(predicted: torch.Tensor, covariance: torch.Tensor, true: torch.
     logdet = 2.0 * torch.sum(torch.log(torch.diagonal(L, dim1=-2, dim2=-1)), dim=-1)
     d = predicted.shape[-1]
     return torch.mean(0.5 * (torch.sum(y * y, dim=-1) + logdet + d * math.log(2.0 * math.pi)), dim=0)
+
+
+def gaussian_log_density(predicted: torch.Tensor, covariance: torch.Tensor, true: torch.Tensor) -> torch.Tensor:
+    """The log density of the true state under ``N(predicted, covariance)``, per step: ``(T, N, d)``, ``(T, N, d, d)``,
+    ``(T, N, d)`` -> ``(T, N)``, ``-0.5 (e^T C^-1 e + log det C + d log 2 pi)``: the logarithmic score of a Gaussian belief,
+    the number ``ParticleFilter.belief_density`` leaves as ``log_score`` for a particle set.  ``gaussian_nll`` is its negated
+    mean over the steps after the burn-in.  In the dtype of ``covariance``."""
+    y, L = _whitened_error(predicted, covariance, true)
+    logdet = 2.0 * torch.sum(torch.log(torch.diagonal(L, dim1=-2, dim2=-1)), dim=-1)
+    d = predicted.shape[-1]
+    return -0.5 * (torch.sum(y * y, dim=-1) + logdet + d * math.log(2.0 * math.pi))
+
+
+def gaussian_entropy(covariance: torch.Tensor) -> torch.Tensor:
+    """The differential entropy of ``N(., covariance)``: ``(T, N, d, d)`` -> ``(T, N)``, ``0.5 log det(2 pi e C)``; what
+    ``ParticleFilter.belief_density`` estimates as ``entropy`` for a particle set."""
+    L = torch.linalg.cholesky(covariance)
+    logdet = 2.0 * torch.sum(torch.log(torch.diagonal(L, dim1=-2, dim2=-1)), dim=-1)
+    d = covariance.shape[-1]
+    return 0.5 * (logdet + d * (1.0 + math.log(2.0 * math.pi)))
+
+
+def density_summary(record, start: int = START_TRUNCATION) -> Dict[str, float]:
+    """Means of a density record (``ParticleFilter.last_density``; ``run_filter(return_density=True)``) over the finite
+    entries of the steps after the burn-in, over time and trajectories: ``log_score`` (where the record holds one; higher is
+    better, its negation is the NLL) and ``entropy``, two floats.  Steps without a live particle (NaN) and log scores of
+    ``-inf`` are left out, like ``score_summary`` leaves them."""
+    if getattr(record, "entropy", None) is None:
+        raise ValueError("density_summary: the record has no entropy; take it from belief_density or run_filter(return_density=True)")
+
+    def mean(x):
+        x = x[start:].to(torch.float64).reshape(-1)
+        ok = torch.isfinite(x)
+        return float(torch.where(ok, x, torch.zeros_like(x)).sum() / ok.sum())
+
+    out = {"entropy": mean(record.entropy)}
+    if getattr(record, "log_score", None) is not None:
+        out["log_score"] = mean(record.log_score)
+    return out
 
 
 def coverage(predicted: torch.Tensor, covariance: torch.Tensor, true: torch.Tensor, level: float = 0.95,

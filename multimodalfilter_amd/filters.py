@@ -86,6 +86,9 @@ class ParticleFilter(base.Filter):
     state) -> ``last_quantiles``; the non-parametric counterpart of the covariance (``mmf_pf_quantiles``).
     ``belief_scores(truth, of=, scale=)``: CRPS per dimension and the energy score of the recorded sets against the true
     states -> ``last_scores``; strictly proper, so calibration and sharpness in one number (``mmf_pf_scores``).
+    ``belief_density(truth=, of=, bandwidth=, min_bandwidth=)``: the kernel density of the recorded sets -- the mode per step
+    (returned), the log density at every particle, the entropy and, with a truth, the logarithmic score -> ``last_density``
+    (``mmf_pf_density``).
     Randomness comes from ``self.noise`` (``utils.NoiseSource``), never from global RNG state.
     """
 
@@ -125,6 +128,7 @@ class ParticleFilter(base.Filter):
         self.last_smoothed = None
         self.last_quantiles = None    # belief_quantiles(): per-dimension weighted quantiles (and the PIT) of the recorded sets
         self.last_scores = None       # belief_scores(): CRPS, energy score and sharpness of the recorded sets against the truth
+        self.last_density = None      # belief_density(): mode, log density, entropy and log score of the recorded sets
         self.record_transition_moments = False  # smooth(method="marginal") adds the two-slice residual moments to last_smoothed
         self._step_history = None
         self.use_native_loop = True   # False: forward_loop keeps the step-by-step Python loop
@@ -799,7 +803,7 @@ class ParticleFilter(base.Filter):
 
     def _recorded_sets(self, of: str, who: str):
         """``(states (T, N, M, d), log_a, log_b)`` of the weighted particle sets that ``who`` (``belief_quantiles``,
-        ``belief_scores``) reads: ``of="filtered"`` the history's ``states`` under ``log_weights_in + log_likelihoods``;
+        ``belief_scores``, ``belief_density``) reads: ``of="filtered"`` the history's ``states`` under ``log_weights_in + log_likelihoods``;
         ``of="smoothed"`` the history's states under ``log(weights)`` after the marginal smoother, the drawn ``trajectories``
         with no weights after backward simulation.  Everything else is the ``ValueError`` of ``who``."""
         h = self.last_history
@@ -869,6 +873,65 @@ class ParticleFilter(base.Filter):
             _abi.pf_scores(states, log_a, log_b, y, crps, energy, spread, sc)
         self.last_scores = base.belief_record(crps=crps, energy=energy, spread=spread, of=of, scale=sc)
         return crps
+
+    def belief_density(self, truth: Optional[torch.Tensor] = None, *, of: str = "filtered", bandwidth="silverman",
+                       min_bandwidth=1e-6) -> torch.Tensor:
+        """The kernel density estimate of the recorded particle sets (``mmf_pf_density``, ``include/mmf.h``): a Gaussian
+        product kernel on the weighted set, one bandwidth per state dimension, all ``M^2`` pairs of a set in HIP.  Returns
+        ``mode (T, N, d)``: per step the particle where the density is highest -- the point estimate of a multimodal belief,
+        a state the filter holds, where the mean lies between the modes.  Leaves ``last_density``: ``mode``, ``mode_index
+        (T, N)`` int32, ``log_density (T, N, M)`` (``-inf`` at a dead particle), ``entropy (T, N)`` -- the resubstitution
+        estimate ``-sum W log p(x)``, a sharpness figure that assumes no Gaussian --, ``bandwidth (T, N, d)``, ``of``,
+        ``rule`` and, with ``truth (T, N, d)``, ``log_score (T, N)``: the log density at the true state, the logarithmic
+        score (its negated mean is the NLL that ``evaluation.gaussian_nll`` is for a Gaussian belief).
+        ``bandwidth``: ``"silverman"`` or ``"scott"`` -- the rule of thumb per step on the weighted standard deviation of
+        each dimension and the effective sample size, not below ``min_bandwidth`` (a float or ``d`` floats) -- or ``d``
+        positive finite floats used as they are (``rule == "fixed"``).  ``of`` means what it means for ``belief_scores``.
+        Draws no noise and leaves ``last_history`` / ``last_smoothed`` / ``last_quantiles`` / ``last_scores`` as they are.  A
+        step without a live particle gives NaN and ``mode_index = -1``; a NaN component of the truth gives NaN in its
+        ``log_score`` only."""
+        if of not in ("filtered", "smoothed"):
+            raise ValueError(f"belief_density: of must be 'filtered' or 'smoothed', got {of!r}")
+        states, log_a, log_b = self._recorded_sets(of, "belief_density")
+        T, N, M, d = states.shape
+        if M > _abi.DENSITY_MAX_M:
+            raise ValueError(f"belief_density: {M} particles per set; mmf_pf_density serves at most {_abi.DENSITY_MAX_M}")
+        if truth is not None and (not isinstance(truth, torch.Tensor) or tuple(truth.shape) != (T, N, d)):
+            raise ValueError(f"belief_density: truth must be None or a (T, N, d) = ({T}, {N}, {d}) tensor, got "
+                             f"{tuple(truth.shape) if isinstance(truth, torch.Tensor) else type(truth).__name__}")
+
+        def floats(value, name, or_what):
+            real = lambda v: not isinstance(v, bool) and isinstance(v, numbers.Real) and 0.0 < float(v) < math.inf
+            try:
+                vs = [] if isinstance(value, (str, bytes)) else [v for v in value]
+            except TypeError:
+                vs = []
+            if len(vs) != d or not all(real(v) for v in vs):
+                raise ValueError(f"belief_density: {name} must be {or_what} or {d} positive finite floats, got {value!r}")
+            return tuple(float(v) for v in vs)
+
+        if isinstance(bandwidth, str) and bandwidth in ("silverman", "scott"):
+            rule, fixed = str(bandwidth), None
+        else:
+            rule, fixed = "fixed", floats(bandwidth, "bandwidth", "'silverman', 'scott'")
+        if not isinstance(min_bandwidth, bool) and isinstance(min_bandwidth, numbers.Real):
+            min_bandwidth = (min_bandwidth,) * d
+        floor = floats(min_bandwidth, "min_bandwidth", "a positive finite float")
+        dev = states.device
+        with torch.no_grad():
+            y = None if truth is None else truth.detach().to(device=dev, dtype=torch.float32).contiguous()
+            log_density = torch.empty((T, N, M), dtype=torch.float32, device=dev)
+            log_score = None if y is None else torch.empty((T, N), dtype=torch.float32, device=dev)
+            entropy = torch.empty((T, N), dtype=torch.float32, device=dev)
+            mode = torch.empty((T, N, d), dtype=torch.float32, device=dev)
+            mode_index = torch.empty((T, N), dtype=torch.int32, device=dev)
+            h = torch.empty((T, N, d), dtype=torch.float32, device=dev)
+            _abi.pf_density(states, log_a, log_b, y, rule=rule, bandwidth=fixed, min_bandwidth=floor, log_density=log_density,
+                            log_score=log_score, entropy=entropy, mode=mode, mode_index=mode_index, bandwidth_out=h)
+        extra = {} if log_score is None else {"log_score": log_score}
+        self.last_density = base.belief_record(mode=mode, mode_index=mode_index, log_density=log_density, entropy=entropy,
+                                               bandwidth=h, of=of, rule=rule, **extra)
+        return mode
 
     def belief_quantiles(self, probs, *, of: str = "filtered", truth: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Per-dimension weighted quantiles of the recorded particle sets (``mmf_pf_quantiles``, ``include/mmf.h``): the
