@@ -1569,9 +1569,11 @@ int mmf_ekf_smooth(const MmfEkfSmoothArgs* args /* host */, void* stream);
  * The two-layer nn.LSTM(in_dim, 512, 2) of DoorLSTMFilter / PushLSTMFilter over a whole (T, N, in_dim) sequence, the
  * hidden state carried in and out (crossmodal/door_models/lstm.py:94, push_models/lstm.py:96: `lstm_out,
  * self.lstm_hidden = self.lstm(fused_features, self.lstm_hidden)`).  PyTorch's gate order and formulas: gates i, f, g, o
- * of W_ih x + b_ih + W_hh h + b_hh, sigma on i, f, o and tanh on g (both the deterministic forms of mmf_detmath.h),
- * c' = f c + i g, h' = o tanh(c').  Exact fp32 products (v_mfma_f32_32x32x2_f32) in every MMF_PRECISION mode: a step is
- * bound by the hand-off between workgroups, not by its ~0.2 GFLOP at N = 32.  csrc/lstm.hip.
+ * of W_ih x + b_ih + W_hh h + b_hh, sigma on i, f, o and tanh on g (both the deterministic forms of mmf_detmath.h:
+ * mmf_det_sigmoid, absolute error <= 3e-7, and mmf_det_tanh, RELATIVE error <= 3.3e-7 measured and held to 7e-7 -- small
+ * pre-activations and cell states keep their digits), c' = f c + i g, h' = o tanh(c').  Exact fp32 products
+ * (v_mfma_f32_32x32x2_f32) in every MMF_PRECISION mode: a step is bound by the hand-off between workgroups, not by its
+ * ~0.2 GFLOP at N = 32.  csrc/lstm.hip.
  *
  *   mmf_lstm_blob_floats(in_dim): floats of the packed weights; in_dim a multiple of 8 in [8, 512], else 0.  Layout:
  *     per layer l (K_0 = in_dim + 512, K_1 = 1024), per workgroup g < 64, 32 x K_l floats [k / 2][k & 1][row q], row
@@ -1584,7 +1586,9 @@ int mmf_ekf_smooth(const MmfEkfSmoothArgs* args /* host */, void* stream);
  *   mmf_lstm_sync_words(N): 4-byte words of MmfLstmArgs.sync_words: [abort word, padded to 16 B][64 progress words]
  *     [2 layers][2 parities][512][N] 8-byte granules; 0 for N < 1.
  *   mmf_lstm_forward: the whole sequence; persistent != 0 -> ONE launch (falls back to the loop of launches where the
- *     plan is 0), otherwise T + 1 launches.  Both forms give the same bits.
+ *     plan is 0), otherwise T + 1 launches.  Both forms give the same bits.  T = 0: no launch, hT / cT are copies of
+ *     h0 / c0, and x and h2 (both empty) may be null.  Refused with MMF_EINVAL, nothing written: in_dim not a multiple
+ *     of 8 in [8, 512], N < 1, T < 0, hT == h0 or cT == c0, n_sync_words < mmf_lstm_sync_words(N), a null pointer.
  */
 #define MMF_LSTM_HIDDEN 512
 #define MMF_LSTM_LAYERS 2
@@ -1592,12 +1596,13 @@ int mmf_ekf_smooth(const MmfEkfSmoothArgs* args /* host */, void* stream);
 typedef struct MmfLstmArgs {
   int32_t T, N, in_dim;
   int32_t persistent;        /* != 0: ONE persistent launch where mmf_lstm_persistent_plan(N, T) > 0                 */
-  const float* x;            /* (T, N, in_dim) layer-0 input                                                        */
+  const float* x;            /* (T, N, in_dim) layer-0 input (T = 0: may be null)                                   */
   const float* h0;           /* (2, N, 512) initial hidden state                                                    */
   const float* c0;           /* (2, N, 512) initial cell state                                                      */
   float* hT;                 /* (2, N, 512) out: final hidden state (not h0)                                        */
   float* cT;                 /* (2, N, 512) out: final cell state (not c0)                                          */
-  float* h2;                 /* (T, N, 512) out: layer 1's hidden state at every step (nn.LSTM's output)           */
+  float* h2;                 /* (T, N, 512) out: layer 1's hidden state at every step (nn.LSTM's output; T = 0: may
+                                be null)                                                                            */
   const float* packed;       /* mmf_lstm_pack                                                                       */
   int32_t* range_flag;       /* or null; MMF_FLAG_GAVE_UP = "a hand-off of the persistent launch timed out: discard the
                                 outputs and run the call again as launches"                                         */

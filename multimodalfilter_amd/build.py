@@ -27,7 +27,8 @@ OBJ = os.path.join(CSRC, "_obj")
 
 def _headers():
     files = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))]
-    files.append(os.path.join(os.path.dirname(HERE), "include", "mmf.h"))
+    include = os.path.join(os.path.dirname(HERE), "include")  # mmf.h, and mmf_detmath.h / mmf_philox.h that the kernels share with oracle/strict
+    files += [os.path.join(include, f) for f in sorted(os.listdir(include)) if f.endswith(".h")]
     files.append(os.path.abspath(__file__))
     return files
 

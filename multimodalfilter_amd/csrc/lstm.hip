@@ -1,6 +1,8 @@
 // The recurrence of the LSTM baselines (crossmodal/door_models/lstm.py:13-100, push_models/lstm.py:13-102): the
 // two-layer nn.LSTM(in_dim, 512, 2) of DoorLSTMFilter / PushLSTMFilter over (T, N, in_dim), PyTorch's gate order and
-// formulas -- gates i, f, g, o of W_ih x + b_ih + W_hh h + b_hh; c' = f c + i g, h' = o tanh(c').
+// formulas -- gates i, f, g, o of W_ih x + b_ih + W_hh h + b_hh; c' = f c + i g, h' = o tanh(c').  sigma and tanh are
+// mmf_det_sigmoid (absolute error <= 3e-7) and mmf_det_tanh (RELATIVE error <= 3.3e-7, so that cell states of 1e-4 keep
+// their digits) of mmf_detmath.h.
 //
 // Work split.  A workgroup owns 8 hidden units of ONE layer, i.e. the 32 gate rows {i, f, g, o} x 8 of those units, and
 // keeps that slice of [W_ih | W_hh] in LDS: 64 workgroups per layer, 128 in all.  Per step it forms the 32 x N gate
@@ -66,10 +68,6 @@ __host__ __device__ inline size_t layer_weight_offset(int layer, int in_dim) {
 __host__ __device__ inline size_t bias_offset(int in_dim) {
   return static_cast<size_t>(kRows) * kWgPerLayer * (layer_k(0, in_dim) + layer_k(1, in_dim));
 }
-
-// tanh(x) = 2 sigmoid(2x) - 1 on the deterministic sigmoid (absolute error <= 7e-7: twice the sigmoid's 3e-7, plus the
-// rounding of the final fma); saturates to -1 / +1 exactly as the sigmoid does to 0 / 1
-__device__ __forceinline__ float det_tanh(float x) { return __builtin_fmaf(2.0f, mmf_det_sigmoid(2.0f * x), -1.0f); }
 
 // B operand (k, column) of layer `layer` at step s: [x_s ; h_{s-1}], granules checked against their tag
 struct Operand {
@@ -216,9 +214,9 @@ __global__ void __launch_bounds__(kThreads) lstm_rounds_kernel(LstmKernelArgs a)
         return __fadd_rn(__fadd_rn(__fadd_rn(p0, p1), __fadd_rn(p2, p3)), b);
       };
       const float ig = mmf_det_sigmoid(pre(0, b_i)), fg = mmf_det_sigmoid(pre(1, b_f));
-      const float gg = det_tanh(pre(2, b_g)), og = mmf_det_sigmoid(pre(3, b_o));
+      const float gg = mmf_det_tanh(pre(2, b_g)), og = mmf_det_sigmoid(pre(3, b_o));
       const float cn = __builtin_fmaf(fg, c[ct], __fmul_rn(ig, gg));
-      const float hn = __fmul_rn(og, det_tanh(cn));
+      const float hn = __fmul_rn(og, mmf_det_tanh(cn));
       c[ct] = cn;
       if (n < a.N) {
         mmf::st_granule(a.hx + ((layer * 2 + (s & 1)) * static_cast<size_t>(kH) + u) * N + n, hn, static_cast<unsigned>(s + 1));
@@ -320,7 +318,8 @@ extern "C" size_t mmf_lstm_sync_words(int N) {
 extern "C" int mmf_lstm_forward(const MmfLstmArgs* a, void* stream) {
   if (!a) return MMF_EINVAL;
   if (a->T < 0 || a->N < 1 || !valid_in_dim(a->in_dim)) return MMF_EINVAL;
-  if (!a->x || !a->h0 || !a->c0 || !a->hT || !a->cT || !a->h2 || !a->packed || !a->sync_words) return MMF_EINVAL;
+  if (!a->h0 || !a->c0 || !a->hT || !a->cT || !a->packed || !a->sync_words) return MMF_EINVAL;
+  if (a->T > 0 && (!a->x || !a->h2)) return MMF_EINVAL;  // T = 0: both are empty, and an empty tensor has no address
   if (a->hT == a->h0 || a->cT == a->c0) return MMF_EINVAL;
   if (a->n_sync_words < mmf_lstm_sync_words(a->N)) return MMF_EINVAL;
   if (static_cast<size_t>(a->T) * a->N * kH >= (static_cast<size_t>(1) << 40)) return MMF_ETOOLARGE;

@@ -87,8 +87,9 @@ def lib():
     if _lib is None:
         L = ctypes.CDLL(build())
         P = c_void_p
-        for name in ("strict_det_exp_nonpos", "strict_det_log", "strict_det_sigmoid"):
+        for name in ("strict_det_exp_nonpos", "strict_det_log", "strict_det_sigmoid", "strict_det_tanh"):
             getattr(L, name).argtypes = [P, P, c_long]
+            getattr(L, name).restype = None
         L.strict_det_logaddexp.argtypes = [P, P, P, c_long]
         L.strict_linear.argtypes = [P, c_long, c_int, P, c_int, c_int, P, P, c_int, c_int, c_float, P]
         L.strict_conv.argtypes = [P, P, P, P, c_long, c_int, c_int, c_int, c_int, P]
@@ -138,6 +139,11 @@ def det_log(x):
 
 def det_sigmoid(x):
     return _unary("strict_det_sigmoid", x)
+
+
+def det_tanh(x):
+    """``mmf_det_tanh``: the tanh of the LSTM recurrence (``csrc/lstm.hip``), accurate RELATIVELY down to the denormals."""
+    return _unary("strict_det_tanh", x)
 
 
 def det_logaddexp(a, b):

@@ -54,6 +54,9 @@ void strict_det_log(const float* x, float* y, long n) {
 void strict_det_sigmoid(const float* x, float* y, long n) {
   for (long i = 0; i < n; ++i) y[i] = mmf_det_sigmoid(x[i]);
 }
+void strict_det_tanh(const float* x, float* y, long n) {
+  for (long i = 0; i < n; ++i) y[i] = mmf_det_tanh(x[i]);
+}
 void strict_det_logaddexp(const float* a, const float* b, float* y, long n) {
   for (long i = 0; i < n; ++i) y[i] = mmf_det_logaddexp(a[i], b[i]);
 }

@@ -41,6 +41,67 @@ def test_deterministic_transcendentals_against_fp64():
     assert np.max(np.abs(lae[fin] - want[fin])) < 1.5e-6
 
 
+TANH_SEAM = np.float32(0.625)      # mmf_det_tanh: the polynomial below, 2 sigmoid(2|x|) - 1 from it on
+
+
+def _old_tanh(x):
+    """``fmaf(2, mmf_det_sigmoid(2x), -1)``, what the LSTM evaluated before ``mmf_det_tanh`` (2 s is exact: one rounding)."""
+    s = strict.det_sigmoid((np.float32(2.0) * x).astype(np.float32))
+    return (2.0 * s.astype(np.float64) - 1.0).astype(np.float32)
+
+
+def test_det_tanh_relative_error_against_fp64():
+    """<= 7e-7 RELATIVE (the absolute 7e-7 the LSTM's tanh used to be documented with, turned relative; |tanh| <= 1, so it
+    implies the absolute bound): 1e-30 <= |x| <= 20 log-spaced, a dense linear sweep of one octave either side of the seam,
+    and every float of the 4096 next to the seam, both signs.  Prints the worst (include/mmf_detmath.h quotes it)."""
+    mag = np.concatenate([np.logspace(-30, np.log10(20.0), 400001), np.linspace(0.5 * TANH_SEAM, 2.0 * TANH_SEAM, 400001),
+                          TANH_SEAM * (1.0 + np.arange(-2048, 2048) * 2.0 ** -24)]).astype(np.float32)
+    x = np.concatenate([mag, -mag])
+    want = np.tanh(x.astype(np.float64))
+    rel = np.abs(strict.det_tanh(x) - want) / np.abs(want)
+    worst = int(np.argmax(rel))
+    print(f"mmf_det_tanh: worst relative error {rel[worst]:.3e} at x = {x[worst]!r}; "
+          f"below the seam {rel[np.abs(x) < TANH_SEAM].max():.3e}; old form at |x| = 1e-4: "
+          f"{abs(float(_old_tanh(np.float32([1e-4]))[0]) - np.tanh(1e-4)) / np.tanh(1e-4):.3e}")
+    assert rel.max() <= 7e-7, (rel[worst], x[worst])
+    assert np.max(np.abs(strict.det_tanh(x) - want)) <= 7e-7
+    # the form it replaces keeps its ABSOLUTE bound and misses the relative one by three orders at 1e-4
+    small = np.float32([1e-4, -1e-4, 3e-5])
+    assert np.all(np.abs(_old_tanh(small) - np.tanh(small.astype(np.float64))) / np.abs(np.tanh(small.astype(np.float64))) > 1e-4)
+
+
+def test_det_tanh_zeros_symmetry_saturation_and_seam():
+    t = strict.det_tanh
+    z = t(np.float32([0.0, -0.0]))
+    assert np.array_equal(z, [0.0, 0.0]) and np.array_equal(np.signbit(z), [False, True])
+    # denormals and the smallest normals come back as they are (tanh x = x to fp32 there), infinities saturate, NaN stays
+    tiny = np.float32([1e-45, 1e-40, 1.1754944e-38, 1e-30, -1e-40])
+    assert np.array_equal(t(tiny), tiny)
+    assert np.array_equal(t(np.float32([np.inf, -np.inf, 100.0, -100.0])), [1.0, -1.0, 1.0, -1.0]) and np.isnan(t(np.float32([np.nan]))[0])
+    # odd, bit for bit
+    g = np.random.default_rng(2)
+    x = np.concatenate([np.logspace(-38, 1.5, 200001), g.standard_normal(100000) * 3.0, np.linspace(0.3, 1.3, 200001)]).astype(np.float32)
+    assert np.array_equal(t(-x).view(np.int32), (-t(x)).view(np.int32))
+    # exactly +-1 wherever 2 sigmoid(2x) - 1 was, and exactly 1 from 8.32 on (exp(-2x) <= 2^-24)
+    big = np.concatenate([np.linspace(5.0, 30.0, 250001), np.logspace(1, 38, 1000)]).astype(np.float32)
+    for s in (np.float32(1.0), np.float32(-1.0)):
+        old, new = _old_tanh(s * big), t(s * big)
+        assert np.all(new[old == s] == s) and np.any(old == s)
+        assert np.all(new[big >= 8.32] == s) and np.all(np.abs(new[big <= 8.3]) < 1.0)
+    # for x >= the seam the value IS the old form's (x > 0: the same operations)
+    assert np.array_equal(t(big), _old_tanh(big))
+    pos = x[x >= TANH_SEAM]
+    assert np.array_equal(t(pos), _old_tanh(pos))
+    # non-decreasing across the seam: the 64 floats below it against the 64 from it on, and along the whole window
+    ulp = np.float32(2.0 ** -24)                                # spacing of floats in [0.5, 1)
+    window = (TANH_SEAM + np.arange(-64, 64).astype(np.float32) * ulp).astype(np.float32)
+    assert window[64] == TANH_SEAM and np.all(np.diff(window) == ulp)
+    y = t(window)
+    assert y[63] <= y[64] and y[:64].max() <= y[64:].min()
+    assert np.all(np.diff(y) >= 0)
+    assert np.all(np.diff(t(-window)) <= 0)
+
+
 def test_strict_layers_match_the_torch_oracle():
     torch.manual_seed(0)
     task = om.TASKS["door"]
