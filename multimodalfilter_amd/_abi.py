@@ -136,15 +136,13 @@ class MmfPfSmoothMapArgs(Structure):
 
 
 QUANTILES_MAX = 16    # MMF_QUANTILES_MAX
-QUANTILES_MAX_M = 16384  # particles per row that mmf_pf_quantiles sorts in LDS
+SUMMARY_MAX_M = 16384  # particles per row that mmf_pf_quantiles sorts in LDS and mmf_pf_scores and mmf_pf_density serve
+QUANTILES_MAX_M = SCORES_MAX_M = DENSITY_MAX_M = SUMMARY_MAX_M
 
 
 class MmfPfQuantilesArgs(Structure):
     _fields_ = [("R", c_int32), ("M", c_int32), ("d", c_int32), ("Q", c_int32), ("probs", ctypes.c_float * QUANTILES_MAX),
                 ("states", _FP), ("log_a", _FP), ("log_b", _FP), ("query", _FP), ("quantiles", _FP), ("cdf", _FP)]
-
-
-SCORES_MAX_M = 16384  # particles per row that mmf_pf_scores serves
 
 
 class MmfPfScoresArgs(Structure):
@@ -153,7 +151,6 @@ class MmfPfScoresArgs(Structure):
                 ("workspace", _FP), ("workspace_bytes", c_size_t)]
 
 
-DENSITY_MAX_M = 16384  # particles per row that mmf_pf_density serves
 DENSITY_RULES = {"fixed": 0, "silverman": 1, "scott": 2}  # MmfPfDensityArgs.rule
 
 
@@ -1119,6 +1116,24 @@ def pf_smooth_map(states_steps, pred_steps, loglik_steps, logw_in_steps, scale_t
         _check(load().mmf_pf_smooth_map(ctypes.byref(a), stream_of(states_steps)), "mmf_pf_smooth_map")
 
 
+def _summary_rows(states, log_a, log_b):
+    """``lead, R, M, d`` of ``states (lead..., M, d)``, ``R`` the product of ``lead``; ``log_a``, ``log_b``: ``(lead..., M)`` or ``None``."""
+    lead, (M, d) = tuple(states.shape[:-2]), states.shape[-2:]
+    R = 1
+    for n in lead:
+        R *= int(n)
+    assert log_a is None or tuple(log_a.shape) == lead + (M,)
+    assert log_b is None or tuple(log_b.shape) == lead + (M,)
+    return lead, R, M, d
+
+
+def _summary_workspace(a, need: int, like):
+    """``need`` bytes of float64 workspace on ``like``'s device into ``a``; the caller keeps the tensor until the launch is made."""
+    work = torch.empty((need // 8,), dtype=torch.float64, device=like.device) if need else None
+    a.workspace, a.workspace_bytes = vp(work, torch.float64), need
+    return work
+
+
 def pf_quantiles_lds_bytes(M: int) -> int:
     return int(load().mmf_pf_quantiles_lds_bytes(int(M)))
 
@@ -1130,16 +1145,11 @@ def pf_quantiles(states, log_a, log_b, probs, quantiles, query=None, cdf=None):
     floats in ``[0, 1]`` -> ``quantiles (..., Q, d)`` (``None`` allowed for an empty ``probs``; not written then).  ``query
     (..., d)`` with ``cdf (..., d)``, both or neither: the weighted share of the particles at or below the query, per
     dimension."""
-    lead, (M, d) = tuple(states.shape[:-2]), states.shape[-2:]
-    R = 1
-    for n in lead:
-        R *= int(n)
     probs = [float(p) for p in probs]
     Q = len(probs)
     if Q > QUANTILES_MAX:
         raise MmfError(f"mmf_pf_quantiles takes at most {QUANTILES_MAX} probabilities, got {Q}")
-    assert log_a is None or tuple(log_a.shape) == lead + (M,)
-    assert log_b is None or tuple(log_b.shape) == lead + (M,)
+    lead, R, M, d = _summary_rows(states, log_a, log_b)
     assert quantiles is None or tuple(quantiles.shape) == lead + (Q, d)
     assert (query is None) == (cdf is None)
     assert query is None or (tuple(query.shape) == lead + (d,) and tuple(cdf.shape) == lead + (d,))
@@ -1165,15 +1175,10 @@ def pf_scores(states, log_a, log_b, truth, crps, energy, spread, scale=None):
     be ``None`` with ``spread`` alone.  ``scale``: ``None`` (ones) or ``d`` positive finite host floats dividing the
     coordinates inside the Euclidean norm of ``energy`` and ``spread[..., d]``.  The workspace of the partial sums is allocated
     here, on the tensors' device."""
-    lead, (M, d) = tuple(states.shape[:-2]), states.shape[-2:]
-    R = 1
-    for n in lead:
-        R *= int(n)
+    lead, R, M, d = _summary_rows(states, log_a, log_b)
     scale = [1.0] * d if scale is None else [float(s) for s in scale]
     if len(scale) != d or d > MMF_MAX_STATE_DIM:
         raise MmfError(f"mmf_pf_scores takes one scale per state dimension (d = {d} <= {MMF_MAX_STATE_DIM}), got {len(scale)}")
-    assert log_a is None or tuple(log_a.shape) == lead + (M,)
-    assert log_b is None or tuple(log_b.shape) == lead + (M,)
     assert truth is None or tuple(truth.shape) == lead + (d,)
     assert crps is None or tuple(crps.shape) == lead + (d,)
     assert energy is None or tuple(energy.shape) == lead
@@ -1185,9 +1190,7 @@ def pf_scores(states, log_a, log_b, truth, crps, energy, spread, scale=None):
     a.states, a.log_a, a.log_b, a.truth = vp(states), vp(log_a), vp(log_b), vp(truth)
     a.crps, a.energy, a.spread = vp(crps), vp(energy), vp(spread)
     with _on(states):
-        need = pf_scores_workspace_bytes(R, M, d)
-        work = torch.empty((need // 8,), dtype=torch.float64, device=states.device) if need else None
-        a.workspace, a.workspace_bytes = vp(work, torch.float64), need
+        work = _summary_workspace(a, pf_scores_workspace_bytes(R, M, d), states)
         _check(load().mmf_pf_scores(ctypes.byref(a), stream_of(states)), "mmf_pf_scores")
 
 
@@ -1204,10 +1207,7 @@ def pf_density(states, log_a, log_b, truth, *, rule="silverman", bandwidth=None,
     ``None`` (not all six).  ``rule``: ``"silverman"`` or ``"scott"`` with ``min_bandwidth``, ``d`` positive finite host
     floats, the floor of the bandwidths; ``"fixed"`` with ``bandwidth``, ``d`` positive finite host floats.  The workspace of
     the partial results is allocated here, on the tensors' device."""
-    lead, (M, d) = tuple(states.shape[:-2]), states.shape[-2:]
-    R = 1
-    for n in lead:
-        R *= int(n)
+    lead, R, M, d = _summary_rows(states, log_a, log_b)
     if rule not in DENSITY_RULES:
         raise MmfError(f"mmf_pf_density: rule must be one of {sorted(DENSITY_RULES)}, got {rule!r}")
     given = bandwidth if rule == "fixed" else min_bandwidth
@@ -1215,8 +1215,6 @@ def pf_density(states, log_a, log_b, truth, *, rule="silverman", bandwidth=None,
     if len(given) != d or d > MMF_MAX_STATE_DIM:
         raise MmfError(f"mmf_pf_density takes one {'bandwidth' if rule == 'fixed' else 'min_bandwidth'} per state dimension "
                        f"(d = {d} <= {MMF_MAX_STATE_DIM}), got {len(given)}")
-    assert log_a is None or tuple(log_a.shape) == lead + (M,)
-    assert log_b is None or tuple(log_b.shape) == lead + (M,)
     assert truth is None or tuple(truth.shape) == lead + (d,)
     assert log_density is None or tuple(log_density.shape) == lead + (M,)
     assert log_score is None or tuple(log_score.shape) == lead
@@ -1232,7 +1230,5 @@ def pf_density(states, log_a, log_b, truth, *, rule="silverman", bandwidth=None,
     a.log_density, a.log_score, a.entropy = vp(log_density), vp(log_score), vp(entropy)
     a.mode, a.mode_index, a.bandwidth_out = vp(mode), vp(mode_index, torch.int32), vp(bandwidth_out)
     with _on(states):
-        need = pf_density_workspace_bytes(R, M, d)
-        work = torch.empty((need // 8,), dtype=torch.float64, device=states.device) if need else None
-        a.workspace, a.workspace_bytes = vp(work, torch.float64), need
+        work = _summary_workspace(a, pf_density_workspace_bytes(R, M, d), states)
         _check(load().mmf_pf_density(ctypes.byref(a), stream_of(states)), "mmf_pf_density")

@@ -19,6 +19,17 @@ inline bool mmf_bytes_overlap(const void* p, size_t np, const void* q, size_t nq
   const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
   return a < b + nq && b < a + np;
 }
+// does one of the n_out output ranges overlap an input range or another output range?
+inline bool mmf_outputs_overlap(const void* const* outs, const size_t* out_bytes, int n_out, const void* const* ins,
+                                const size_t* in_bytes, int n_in) {
+  for (int o = 0; o < n_out; ++o) {
+    for (int i = 0; i < n_in; ++i)
+      if (mmf_bytes_overlap(outs[o], out_bytes[o], ins[i], in_bytes[i])) return true;
+    for (int p = o + 1; p < n_out; ++p)
+      if (mmf_bytes_overlap(outs[o], out_bytes[o], outs[p], out_bytes[p])) return true;
+  }
+  return false;
+}
 
 // the persistent small-problem step loop (pf_persistent.inc, compiled with particle_net.hip); reached through
 // mmf_pf_forward_loop when MmfPfLoopArgs.persistent is set

@@ -1,8 +1,7 @@
 // Gaussian product-kernel density of a weighted particle set (include/mmf.h, "Particle-posterior density"): the log density at
 // every particle of the set and at a true state, the resubstitution entropy and the mode, over all M^2 pairs of a row.
-// Weights as in pf_scores.hip: plain floats w_m = exp(a_m - max a); every sum in a fixed order, no atomics.
-//   plan      a row's particles are dealt to nb = ceil(M / 512) workgroups in equal i-chunks (pf_scores.hip's dealing); a thread
-//             holds IPT query particles in registers: one, in up to 512 threads, while the row is one workgroup, two beyond
+// The plain float live weights of pf_summary.h; every sum in a fixed order, no atomics.
+//   plan      the dealing of pf_summary.h: nb workgroups to a row, IPT query particles of a thread in registers
 //   moments   every workgroup of a row forms max a, sum w, sum w^2, mu and sigma^2 over the WHOLE row itself, two passes in
 //             double in one fixed order: M loads beside M^2 / nb pairs, no workgroup waits on another, all hold the same bits
 //   pairs     j-tiles of 1024 particles through LDS as structure-of-arrays: d planes of (x - mu) / h and one of log2 w (-inf
@@ -12,22 +11,20 @@
 //             double, kept relative to the maximum at the flush, every 64 j: the rounding of the sum does not grow with M
 //   truth     one more query per row: workgroup 0 splits the row's j over its threads, each with its own running (max, sum),
 //             combined by a butterfly over the wave and the waves in order.  The particle outputs do not see it
-//   reduce    entropy terms in double and (value, index) of the mode: butterfly over the wave, the waves in order through LDS
+//   reduce    entropy terms in double and (value, index) of the mode: butterfly over the wave, the waves in order through LDS;
+//             the moments through summary::block_sum
 //   finish    nb == 1: the workgroup writes the row.  nb > 1: partials to the workspace and pf_density_finish_kernel, a
 //             thread per row, takes them in block order
 
 #include <climits>
 #include <cmath>
 
-#include "mmf_launch.h"
+#include "pf_summary.h"
 
 namespace {
 
-constexpr int kMaxM = 16384;
-constexpr int kIBlock = 512;   // i-particles of a workgroup at most
-constexpr int kJTile = 1024;   // j-particles of an LDS tile
-constexpr int kRun = 64;       // pairs an fp32 sum takes before it is flushed to double
-constexpr int kMaxWaves = kIBlock / MMF_WAVE;
+using namespace mmf::summary;  // the dealing, the weights, block_max, block_sum, pick and the host's checks
+
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kHalfLog2e = 0.7213475204444817f;
 constexpr double kLn2 = 0.6931471805599453;
@@ -56,49 +53,22 @@ struct DArgs {
   float bandwidth[MMF_MAX_STATE_DIM], min_bandwidth[MMF_MAX_STATE_DIM];
 };
 
-// pf_scores.hip's dealing: a function of M alone, so a row has the same bits whatever the batch
-struct Plan {
-  int nb, chunk, ipt, threads;
-};
-inline Plan plan_of(int M) {
-  Plan p;
-  p.nb = (M + kIBlock - 1) / kIBlock;
-  p.chunk = (M + p.nb - 1) / p.nb;
-  p.ipt = p.nb == 1 ? 1 : 2;
-  const int lanes = (p.chunk + p.ipt - 1) / p.ipt;
-  p.threads = (lanes + MMF_WAVE - 1) / MMF_WAVE * MMF_WAVE;
-  return p;
-}
-
 // w_m and log2 w_m (-inf where w_m = 0) of the particle at `at`
 __device__ __forceinline__ float weight_of(const DArgs& a, size_t at, float top, float* l2w) {
-  const float la = a.log_a ? a.log_a[at] : 0.f, lb = a.log_b ? a.log_b[at] : 0.f;
-  const float t = (la + lb) - top;
-  const float w = t <= 0.f ? expf(t) : 0.f;  // (a NaN t: 0)
+  const float t = log_weight(a.log_a, a.log_b, at) - top;
+  const float w = live_weight(t);
   *l2w = w > 0.f ? t * kLog2e : -INFINITY;
   return w;
 }
 
 __device__ __forceinline__ bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
 
-// sums of K doubles over the workgroup: a butterfly in each wave, then the waves in order; every thread gets the same bits
-template <int K>
-__device__ __forceinline__ void block_sum(double* v, double (*scratch)[MMF_MAX_STATE_DIM + 2], int lane, int wave, int waves) {
-  __syncthreads();  // the scratch's last readers are done
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    double s = v[k];
-#pragma unroll
-    for (int off = 1; off < MMF_WAVE; off <<= 1) s += __shfl_xor(s, off, MMF_WAVE);
-    if (lane == 0) scratch[wave][k] = s;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    double s = scratch[0][k];
-    for (int w = 1; w < waves; ++w) s += scratch[w][k];
-    v[k] = s;
-  }
+// an online (max, sum of 2^(e - max)) takes another one in: both sums rescaled to the larger maximum
+__device__ __forceinline__ void merge(float& m, float& s, float om, float os) {
+  const float mn = fmaxf(m, om);
+  const float mine = s * __builtin_amdgcn_exp2f(m - mn), theirs = os * __builtin_amdgcn_exp2f(om - mn);
+  s = mine + theirs;
+  m = mn;
 }
 
 // log p at a query from its running maximum and sum: cst = -log S - sum log h - d/2 log 2 pi
@@ -130,15 +100,8 @@ __global__ __launch_bounds__(kIBlock / IPT) void pf_density_kernel(DArgs a) {
 
   // ---- the row maximum of a_m = log_a[m] + log_b[m]
   float top = -INFINITY;
-  for (int m = tid; m < M; m += threads) {
-    const float la = a.log_a ? a.log_a[row + m] : 0.f, lb = a.log_b ? a.log_b[row + m] : 0.f;
-    top = fmaxf(top, la + lb);  // (a NaN is skipped)
-  }
-  top = mmf::wave_max(top);
-  if (lane == 0) wave_f[0][wave] = top;
-  __syncthreads();
-  top = wave_f[0][0];
-  for (int w = 1; w < waves; ++w) top = fmaxf(top, wave_f[0][w]);
+  for (int m = tid; m < M; m += threads) top = fmaxf(top, log_weight(a.log_a, a.log_b, row + m));  // (a NaN is skipped)
+  top = block_max(top, wave_f[0], tid, waves);
 
   // ---- the row's moments, live particles only, two passes in double: sum w, sum w^2, sum w x; then sum w (x - mu)^2
   double v[D + 2];
@@ -154,7 +117,7 @@ __global__ __launch_bounds__(kIBlock / IPT) void pf_density_kernel(DArgs a) {
 #pragma unroll
     for (int k = 0; k < D; ++k) v[2 + k] += dw * static_cast<double>(a.states[(row + m) * D + k]);
   }
-  block_sum<D + 2>(v, wave_sum, lane, wave, waves);
+  block_sum<D + 2>(v, wave_sum, tid, waves);
   const double S = v[0];
   if (!(S > 0.0)) {  // no live particle in the row: NaN everywhere, mode_index -1
     for (int i = b * a.chunk + tid; i < min(M, (b + 1) * a.chunk); i += threads)
@@ -191,7 +154,7 @@ __global__ __launch_bounds__(kIBlock / IPT) void pf_density_kernel(DArgs a) {
         m2[k] += dw * e * e;
       }
     }
-    block_sum<D>(m2, wave_sum, lane, wave, waves);
+    block_sum<D>(m2, wave_sum, tid, waves);
   }
   // ---- the bandwidths; the coordinates are taken relative to mu before they are divided by h
   const double c = a.rule == 0 ? 1.0 : a.rule == 1 ? pow(4.0 / ((D + 2) * n_eff), 1.0 / (D + 4)) : pow(n_eff, -1.0 / (D + 4));
@@ -231,19 +194,10 @@ __global__ __launch_bounds__(kIBlock / IPT) void pf_density_kernel(DArgs a) {
         const float e = yq[k] - (a.states[(row + m) * D + k] - muf[k]) * ih[k];
         z = fmaf(e, e, z);
       }
-      const float e = fmaf(z, -kHalfLog2e, l2w);
-      const float mn = fmaxf(tm, e);
-      ts = ts * __builtin_amdgcn_exp2f(tm - mn) + __builtin_amdgcn_exp2f(e - mn);
-      tm = mn;
+      merge(tm, ts, fmaf(z, -kHalfLog2e, l2w), 1.f);
     }
 #pragma unroll
-    for (int off = 1; off < MMF_WAVE; off <<= 1) {
-      const float om = __shfl_xor(tm, off, MMF_WAVE), os = __shfl_xor(ts, off, MMF_WAVE);
-      const float mn = fmaxf(tm, om);
-      const float mine = ts * __builtin_amdgcn_exp2f(tm - mn), theirs = os * __builtin_amdgcn_exp2f(om - mn);
-      ts = mine + theirs;
-      tm = mn;
-    }
+    for (int off = 1; off < MMF_WAVE; off <<= 1) merge(tm, ts, __shfl_xor(tm, off, MMF_WAVE), __shfl_xor(ts, off, MMF_WAVE));
     __syncthreads();  // wave_f's last readers are done
     if (lane == 0) {
       wave_f[0][wave] = tm;
@@ -251,13 +205,7 @@ __global__ __launch_bounds__(kIBlock / IPT) void pf_density_kernel(DArgs a) {
     }
     __syncthreads();
     if (tid == 0) {
-      for (int w = 1; w < waves; ++w) {
-        const float om = wave_f[0][w], os = wave_f[1][w];
-        const float mn = fmaxf(tm, om);
-        const float mine = ts * __builtin_amdgcn_exp2f(tm - mn), theirs = os * __builtin_amdgcn_exp2f(om - mn);
-        ts = mine + theirs;
-        tm = mn;
-      }
+      for (int w = 1; w < waves; ++w) merge(tm, ts, wave_f[0][w], wave_f[1][w]);
       a.log_score[r] = nan_y ? NAN : static_cast<float>(log_p(tm, static_cast<double>(ts), cst));
     }
   }
@@ -307,12 +255,10 @@ __global__ __launch_bounds__(kIBlock / IPT) void pf_density_kernel(DArgs a) {
             float z = 0.f;
 #pragma unroll
             for (int k = 0; k < D; ++k) {
-              const float x = c == 0 ? xj[k].x : c == 1 ? xj[k].y : c == 2 ? xj[k].z : xj[k].w;
-              const float t = qi[u][k] - x;
+              const float t = qi[u][k] - pick(xj[k], c);
               z = fmaf(t, t, z);
             }
-            const float l = c == 0 ? lj.x : c == 1 ? lj.y : c == 2 ? lj.z : lj.w;
-            e[c] = fmaf(z, -kHalfLog2e, l);
+            e[c] = fmaf(z, -kHalfLog2e, pick(lj, c));
           }
           const float mn = fmaxf(fmaxf(mx[u], fmaxf(e[0], e[1])), fmaxf(e[2], e[3]));
           float s = sum[u] * __builtin_amdgcn_exp2f(mx[u] - mn);
@@ -417,8 +363,7 @@ extern "C" size_t mmf_pf_density_workspace_bytes(int R, int M, int d) {
 }
 
 extern "C" int mmf_pf_density(const MmfPfDensityArgs* a, void* stream) {
-  if (!a || !a->states) return MMF_EINVAL;
-  if (a->R < 0 || a->M < 1 || a->d < 1 || a->d > MMF_MAX_STATE_DIM) return MMF_EINVAL;
+  if (!a || check_rows(a->states, a->R, a->M, a->d)) return MMF_EINVAL;
   if (a->rule < 0 || a->rule > 2) return MMF_EINVAL;
   const float* read = a->rule == 0 ? a->bandwidth : a->min_bandwidth;
   for (int k = 0; k < a->d; ++k)
@@ -426,24 +371,15 @@ extern "C" int mmf_pf_density(const MmfPfDensityArgs* a, void* stream) {
   const bool pairs = a->log_density || a->entropy || a->mode || a->mode_index;
   if (!pairs && !a->log_score && !a->bandwidth_out) return MMF_EINVAL;
   if (a->log_score && !a->truth) return MMF_EINVAL;
-  if (a->M > kMaxM) return MMF_ETOOLARGE;
-  const Plan p = plan_of(a->M);
-  if (static_cast<long long>(a->R) * p.nb > 0x7fffffffll) return MMF_ETOOLARGE;
+  const Plan p = plan_of(a->M <= kMaxM ? a->M : kMaxM);  // (a larger M: check_size refuses it)
+  if (const int rc = check_size(a->R, a->M, p.nb)) return rc;
   const size_t ws_bytes = mmf_pf_density_workspace_bytes(a->R, a->M, a->d);
-  if (ws_bytes > 0 && (!a->workspace || a->workspace_bytes < ws_bytes)) return MMF_EINVAL;
-  if (ws_bytes > 0 && reinterpret_cast<uintptr_t>(a->workspace) % alignof(Partial) != 0) return MMF_EINVAL;
+  if (!workspace_ok(a->workspace, a->workspace_bytes, ws_bytes, alignof(Partial))) return MMF_EINVAL;
   {
     const size_t R = a->R, M = a->M, d = a->d, f = sizeof(float);
-    const void* ins[4] = {a->states, a->log_a, a->log_b, a->truth};
-    const size_t in_bytes[4] = {R * M * d * f, R * M * f, R * M * f, R * d * f};
     const void* outs[7] = {a->log_density, a->log_score, a->entropy, a->mode, a->mode_index, a->bandwidth_out, a->workspace};
     const size_t out_bytes[7] = {R * M * f, R * f, R * f, R * d * f, R * sizeof(int32_t), R * d * f, ws_bytes};
-    for (int o = 0; o < 7; ++o) {
-      for (int i = 0; i < 4; ++i)
-        if (mmf_bytes_overlap(outs[o], out_bytes[o], ins[i], in_bytes[i])) return MMF_EINVAL;
-      for (int o2 = o + 1; o2 < 7; ++o2)
-        if (mmf_bytes_overlap(outs[o], out_bytes[o], outs[o2], out_bytes[o2])) return MMF_EINVAL;
-    }
+    if (outputs_alias(a->states, a->log_a, a->log_b, a->truth, R, M, d, outs, out_bytes)) return MMF_EINVAL;
   }
   if (a->R == 0) return 0;
   DArgs k{};

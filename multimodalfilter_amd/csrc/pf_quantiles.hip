@@ -2,7 +2,7 @@
 // quantiles"): K1's integer fixed-point weights q_m = floor(exp(a_m - max a) 2^24), so that every sum is an integer sum and the
 // selection does not depend on the thread count, the scan order or the number of rows.  One kernel, one workgroup per
 // (row, dimension):
-//   weights    a = log_a + log_b held in registers, the row maximum (exact in any order), q_m
+//   weights    a = log_a + log_b held in registers, the row maximum, q_m under the live-weight rule (pf_summary.h)
 //   cdf        the integer sum of q_m over x_m <= query, reduced before the sort; Q == 0 ends here
 //   keys       (order-preserving uint32 of x_m) << 32 | q_m, one uint64 per particle in LDS, padded to P = 2^k >= M with
 //              all-ones keys of weight 0
@@ -15,13 +15,13 @@
 
 #include <cmath>
 
-#include "mmf_launch.h"
+#include "pf_summary.h"
 
 namespace {
 
+namespace summary = mmf::summary;
 using u64 = unsigned long long;
 
-constexpr int kMaxM = 16384;
 constexpr int kMaxWaves = 4;
 constexpr u64 kPadKey = 0xFFFFFFFF00000000ull;
 
@@ -64,20 +64,6 @@ __device__ __forceinline__ float value_of(unsigned k) {
 template <int E>
 __device__ __forceinline__ int slot(int i) {
   return E > 1 ? i + i / E : i;
-}
-
-template <int THREADS>
-__device__ __forceinline__ float block_max(float v, float* scratch, int tid) {
-  v = mmf::wave_max(v);
-  if constexpr (THREADS > MMF_WAVE) {
-    if ((tid & (MMF_WAVE - 1)) == 0) scratch[tid / MMF_WAVE] = v;
-    __syncthreads();
-    v = scratch[0];
-#pragma unroll
-    for (int w = 1; w < THREADS / MMF_WAVE; ++w) v = fmaxf(v, scratch[w]);
-    __syncthreads();
-  }
-  return v;
 }
 
 // inclusive scan of per-thread values below 2^40 over the workgroup, and its total
@@ -127,21 +113,18 @@ __global__ __launch_bounds__(THREADS) void pf_quantiles_kernel(QArgs a) {
   const size_t row = static_cast<size_t>(r) * M;
   const float* x = a.states + row * d + k;
 
-  // a_m = log_a[m] + log_b[m]; particle m = tid + u THREADS
+  // a_m = log_a[m] + log_b[m]; particle m = tid + u THREADS.  The row's own pointers: the row offset stays in scalar registers
+  const float *la = a.log_a ? a.log_a + row : nullptr, *lb = a.log_b ? a.log_b + row : nullptr;
   float av[E];
   float top = -INFINITY;
 #pragma unroll
   for (int u = 0; u < E; ++u) {
     const int m = tid + u * THREADS;
-    float s = -INFINITY;
-    if (m < M) {
-      const float la = a.log_a ? a.log_a[row + m] : 0.f, lb = a.log_b ? a.log_b[row + m] : 0.f;
-      s = la + lb;
-    }
-    av[u] = s;
-    top = fmaxf(top, s);  // (a NaN is skipped)
+    av[u] = m < M ? summary::log_weight(la, lb, m) : -INFINITY;
+    top = fmaxf(top, av[u]);  // (a NaN is skipped)
   }
-  top = block_max<THREADS>(top, wave_top, tid);
+  top = summary::block_max(top, wave_top, tid, THREADS / MMF_WAVE);
+  if constexpr (THREADS > MMF_WAVE) __syncthreads();  // (not needed; without it the sort of 4096 particles measured 1.7 % slower)
 
   const bool want_cdf = a.query != nullptr;
   const float query = want_cdf ? a.query[static_cast<size_t>(r) * d + k] : 0.f;
@@ -153,7 +136,7 @@ __global__ __launch_bounds__(THREADS) void pf_quantiles_kernel(QArgs a) {
     if (m < M) {
       const float t = av[u] - top;
       const float e = expf(t);
-      const unsigned q = t <= 0.f ? static_cast<unsigned>(floorf(e * 16777216.0f)) : 0u;  // (a NaN t: 0)
+      const unsigned q = t <= 0.f ? static_cast<unsigned>(floorf(e * 16777216.0f)) : 0u;  // (the live-weight rule: a NaN t: 0)
       const float xv = x[static_cast<size_t>(m) * d];
       qsum += q;
       if (xv <= query) below += q;
@@ -258,30 +241,23 @@ int run(const QArgs& k, unsigned grid, size_t lds_bytes, hipStream_t s) {
 
 extern "C" size_t mmf_pf_quantiles_lds_bytes(int M) {
   if (M < 1) return 0;
-  if (M > kMaxM) M = kMaxM;
+  if (M > summary::kMaxM) M = summary::kMaxM;
   return slots_of(plan_of(M)) * sizeof(u64);
 }
 
 extern "C" int mmf_pf_quantiles(const MmfPfQuantilesArgs* a, void* stream) {
-  if (!a || !a->states) return MMF_EINVAL;
-  if (a->R < 0 || a->M < 1 || a->d < 1 || a->d > MMF_MAX_STATE_DIM || a->Q < 0 || a->Q > MMF_QUANTILES_MAX) return MMF_EINVAL;
+  if (!a || summary::check_rows(a->states, a->R, a->M, a->d) || a->Q < 0 || a->Q > MMF_QUANTILES_MAX) return MMF_EINVAL;
   for (int i = 0; i < a->Q; ++i)
     if (!(a->probs[i] >= 0.f && a->probs[i] <= 1.f)) return MMF_EINVAL;
   if (a->Q == 0 && !a->query) return MMF_EINVAL;
   if (a->Q > 0 && !a->quantiles) return MMF_EINVAL;
   if ((a->query != nullptr) != (a->cdf != nullptr)) return MMF_EINVAL;
-  if (a->M > kMaxM) return MMF_ETOOLARGE;
-  if (static_cast<long long>(a->R) * a->d > 0x7fffffffll) return MMF_ETOOLARGE;
+  if (const int rc = summary::check_size(a->R, a->M, a->d)) return rc;
   {
     const size_t R = a->R, M = a->M, d = a->d, Q = a->Q, f = sizeof(float);
-    const void* ins[4] = {a->states, a->log_a, a->log_b, a->query};
-    const size_t in_bytes[4] = {R * M * d * f, R * M * f, R * M * f, R * d * f};
     const void* outs[2] = {a->quantiles, a->cdf};
     const size_t out_bytes[2] = {R * Q * d * f, R * d * f};
-    for (int o = 0; o < 2; ++o)
-      for (int i = 0; i < 4; ++i)
-        if (mmf_bytes_overlap(outs[o], out_bytes[o], ins[i], in_bytes[i])) return MMF_EINVAL;
-    if (mmf_bytes_overlap(outs[0], out_bytes[0], outs[1], out_bytes[1])) return MMF_EINVAL;
+    if (summary::outputs_alias(a->states, a->log_a, a->log_b, a->query, R, M, d, outs, out_bytes)) return MMF_EINVAL;
   }
   if (a->R == 0) return 0;
   QArgs k{};

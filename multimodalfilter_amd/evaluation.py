@@ -93,6 +93,17 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
     if smooth_draws is not _DEFAULT_DRAWS and smooth_method != "simulation":  # (before the run, not after it)
         raise ValueError(f"run_filter: smooth_draws is the number of paths smooth_method='simulation' draws; "
                          f"smooth_method={smooth_method!r} takes none")
+    # what reads a weighted particle set per step (return_scores, return_density, return_quantiles) reads the smoothed sets
+    # when the call smooths, and then only the smoothers that leave such sets will do
+    will_smooth = smooth_lag is not False or (named and smooth_method != "ancestry")
+    summary_of = "smoothed" if will_smooth else "filtered"
+
+    def needs_weighted_sets(argument):
+        if will_smooth and smooth_method not in ("marginal", "simulation"):
+            raise ValueError(f"run_filter: {argument} reads a weighted particle set per step; smooth_method={smooth_method!r} "
+                             "leaves none (ancestry keeps no per-step weights, a MAP path is not a distribution): smooth with "
+                             "'marginal' or 'simulation', or do not smooth")
+
     want_scores = bool(return_scores)
     if score_scale is not None:  # (before the run, not after it)
         if not want_scores:
@@ -107,12 +118,8 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
     if want_scores:  # (before the run, not after it)
         scores_kind = ("particles" if hasattr(filter_model, "belief_scores") else
                        "gaussian" if hasattr(filter_model, "record_belief") else "point")
-        will_smooth = smooth_lag is not False or (named and smooth_method != "ancestry")
-        if scores_kind == "particles" and will_smooth and smooth_method not in ("marginal", "simulation"):
-            raise ValueError(f"run_filter: return_scores reads a weighted particle set per step; smooth_method={smooth_method!r} "
-                             "leaves none (ancestry keeps no per-step weights, a MAP path is not a distribution): smooth with "
-                             "'marginal' or 'simulation', or do not smooth")
-        scores_of = "smoothed" if will_smooth else "filtered"
+        if scores_kind == "particles":
+            needs_weighted_sets("return_scores")
     want_density = bool(return_density)
     if density_bandwidth is not _DEFAULT_BANDWIDTH and not want_density:  # (before the run, not after it)
         raise ValueError("run_filter: density_bandwidth is the bandwidth of return_density's kernel density; without "
@@ -131,23 +138,14 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
                 density_bandwidth = ()
             if not density_bandwidth or not all(0.0 < v < math.inf for v in density_bandwidth):
                 raise ValueError("run_filter: density_bandwidth must be 'silverman', 'scott' or d positive finite floats")
-        will_smooth = smooth_lag is not False or (named and smooth_method != "ancestry")
-        if density_kind == "particles" and will_smooth and smooth_method not in ("marginal", "simulation"):
-            raise ValueError(f"run_filter: return_density reads a weighted particle set per step; smooth_method={smooth_method!r} "
-                             "leaves none (ancestry keeps no per-step weights, a MAP path is not a distribution): smooth with "
-                             "'marginal' or 'simulation', or do not smooth")
-        density_of = "smoothed" if will_smooth else "filtered"
+        if density_kind == "particles":
+            needs_weighted_sets("return_density")
     want_quantiles = return_quantiles is not None
     if want_quantiles:  # (before the run, not after it)
         if not hasattr(filter_model, "belief_quantiles"):
             raise ValueError(f"run_filter: return_quantiles needs a particle filter; {type(filter_model).__name__} has no "
                              "belief_quantiles (a Gaussian belief's quantiles are closed form: mean and covariance)")
-        will_smooth = smooth_lag is not False or (named and smooth_method != "ancestry")
-        if will_smooth and smooth_method not in ("marginal", "simulation"):
-            raise ValueError(f"run_filter: return_quantiles reads a weighted particle set per step; smooth_method={smooth_method!r} "
-                             "leaves none (ancestry keeps no per-step weights, a MAP path is not a distribution): smooth with "
-                             "'marginal' or 'simulation', or do not smooth")
-        quantiles_of = "smoothed" if will_smooth else "filtered"
+        needs_weighted_sets("return_quantiles")
     states = traj["states"]
     T1, N, d = states.shape
     if score_scale is not None and len(score_scale) != d:
@@ -210,32 +208,32 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
     if want_scores:
         truth = states[1:]
         if scores_kind == "particles":
-            filter_model.belief_scores(truth, of=scores_of, scale=score_scale)
+            filter_model.belief_scores(truth, of=summary_of, scale=score_scale)
             scores = filter_model.last_scores
         else:
             s = (1.0,) * d if score_scale is None else score_scale
             with torch.no_grad():
                 if scores_kind == "gaussian":
                     cov = (filter_model.last_smoothed if smoothing else filter_model.last_belief).covariance
-                    scores = base.belief_record(crps=gaussian_crps(est, cov, truth), of=scores_of, scale=s)
+                    scores = base.belief_record(crps=gaussian_crps(est, cov, truth), of=summary_of, scale=s)
                 else:
                     e = est - truth
                     energy = torch.linalg.vector_norm(e / torch.tensor(s, dtype=e.dtype, device=e.device), dim=-1)
-                    scores = base.belief_record(crps=e.abs(), energy=energy, of=scores_of, scale=s)
+                    scores = base.belief_record(crps=e.abs(), energy=energy, of=summary_of, scale=s)
         out = (out if isinstance(out, tuple) else (out,)) + (scores,)
     if want_density:
         truth = states[1:]
         if density_kind == "particles":
-            filter_model.belief_density(truth, of=density_of, bandwidth=density_bandwidth)
+            filter_model.belief_density(truth, of=summary_of, bandwidth=density_bandwidth)
             density = filter_model.last_density
         else:
             with torch.no_grad():
                 cov = (filter_model.last_smoothed if smoothing else filter_model.last_belief).covariance
                 density = base.belief_record(log_score=gaussian_log_density(est, cov, truth), entropy=gaussian_entropy(cov),
-                                             mode=est, of=density_of)
+                                             mode=est, of=summary_of)
         out = (out if isinstance(out, tuple) else (out,)) + (density,)
     if want_quantiles:
-        filter_model.belief_quantiles(return_quantiles, of=quantiles_of, truth=states[1:])
+        filter_model.belief_quantiles(return_quantiles, of=summary_of, truth=states[1:])
         out = (out if isinstance(out, tuple) else (out,)) + (filter_model.last_quantiles,)
     return out
 

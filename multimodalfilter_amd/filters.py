@@ -830,6 +830,37 @@ class ParticleFilter(base.Filter):
         raise ValueError(f"{who}(of='smoothed'): smooth(method={method!r}) keeps no per-step weights over the "
                          "recorded sets: smooth with method='marginal' or 'simulation'")
 
+    def _summary_inputs(self, who: str, of: str, truth, serves: str, truth_is: str = "a", required: bool = False):
+        """What ``who`` (``belief_quantiles``, ``belief_scores``, ``belief_density``) opens with, in this order: the ``of``
+        check, the recorded sets, the particle cap (``serves``: how the error words it) and the shape of ``truth (T, N, d)``,
+        which may be ``None`` unless ``required``.  Returns ``(states, log_a, log_b, y)``, ``y`` the truth as a contiguous
+        float32 tensor on the sets' device, or ``None``."""
+        if of not in ("filtered", "smoothed"):
+            raise ValueError(f"{who}: of must be 'filtered' or 'smoothed', got {of!r}")
+        states, log_a, log_b = self._recorded_sets(of, who)
+        T, N, M, d = states.shape
+        if M > _abi.SUMMARY_MAX_M:
+            raise ValueError(f"{who}: {M} particles per set; {serves.format(_abi.SUMMARY_MAX_M)}")
+        if (required or truth is not None) and (not isinstance(truth, torch.Tensor) or tuple(truth.shape) != (T, N, d)):
+            raise ValueError(f"{who}: truth must be {truth_is} (T, N, d) = ({T}, {N}, {d}) tensor, got "
+                             f"{tuple(truth.shape) if isinstance(truth, torch.Tensor) else type(truth).__name__}")
+        with torch.no_grad():
+            y = None if truth is None else truth.detach().to(device=states.device, dtype=torch.float32).contiguous()
+        return states, log_a, log_b, y
+
+    @staticmethod
+    def _positive_floats(who: str, value, name: str, or_what: str, d: int):
+        """``value`` as a tuple of ``d`` positive finite floats, or the ``ValueError`` of ``who``: ``name`` must be
+        ``or_what`` or ``d`` positive finite floats."""
+        real = lambda v: not isinstance(v, bool) and isinstance(v, numbers.Real) and 0.0 < float(v) < math.inf
+        try:
+            vs = [] if isinstance(value, (str, bytes)) else [v for v in value]
+        except TypeError:
+            vs = []
+        if len(vs) != d or not all(real(v) for v in vs):
+            raise ValueError(f"{who}: {name} must be {or_what} or {d} positive finite floats, got {value!r}")
+        return tuple(float(v) for v in vs)
+
     def belief_scores(self, truth: torch.Tensor, *, of: str = "filtered", scale=None) -> torch.Tensor:
         """Strictly proper scores of the recorded particle sets against the true states (``mmf_pf_scores``,
         ``include/mmf.h``): the continuous ranked probability score per state dimension, ``crps (T, N, d)`` -- returned --
@@ -845,28 +876,11 @@ class ParticleFilter(base.Filter):
         different units.  Leaves ``last_scores``: ``crps``, ``energy``, ``spread``, ``of``, ``scale`` (a tuple).  Draws no
         noise and leaves ``last_history`` / ``last_smoothed`` / ``last_quantiles`` as they are.  A step without a live
         particle gives NaN; a NaN component of the truth gives NaN in its ``crps`` and in ``energy``."""
-        if of not in ("filtered", "smoothed"):
-            raise ValueError(f"belief_scores: of must be 'filtered' or 'smoothed', got {of!r}")
-        states, log_a, log_b = self._recorded_sets(of, "belief_scores")
+        states, log_a, log_b, y = self._summary_inputs("belief_scores", of, truth, "mmf_pf_scores serves at most {}", required=True)
         T, N, M, d = states.shape
-        if M > _abi.SCORES_MAX_M:
-            raise ValueError(f"belief_scores: {M} particles per set; mmf_pf_scores serves at most {_abi.SCORES_MAX_M}")
-        if not isinstance(truth, torch.Tensor) or tuple(truth.shape) != (T, N, d):
-            raise ValueError(f"belief_scores: truth must be a (T, N, d) = ({T}, {N}, {d}) tensor, got "
-                             f"{tuple(truth.shape) if isinstance(truth, torch.Tensor) else type(truth).__name__}")
-        if scale is None:
-            sc = (1.0,) * d
-        else:
-            try:
-                sc = [s for s in scale]
-            except TypeError:
-                raise ValueError(f"belief_scores: scale must be None or {d} positive finite floats, got {scale!r}") from None
-            if len(sc) != d or any(isinstance(s, bool) or not isinstance(s, numbers.Real) or not 0.0 < float(s) < math.inf for s in sc):
-                raise ValueError(f"belief_scores: scale must be None or {d} positive finite floats, got {scale!r}")
-            sc = tuple(float(s) for s in sc)
+        sc = (1.0,) * d if scale is None else self._positive_floats("belief_scores", scale, "scale", "None", d)
         dev = states.device
         with torch.no_grad():
-            y = truth.detach().to(device=dev, dtype=torch.float32).contiguous()
             crps = torch.empty((T, N, d), dtype=torch.float32, device=dev)
             energy = torch.empty((T, N), dtype=torch.float32, device=dev)
             spread = torch.empty((T, N, d + 1), dtype=torch.float32, device=dev)
@@ -890,26 +904,9 @@ class ParticleFilter(base.Filter):
         Draws no noise and leaves ``last_history`` / ``last_smoothed`` / ``last_quantiles`` / ``last_scores`` as they are.  A
         step without a live particle gives NaN and ``mode_index = -1``; a NaN component of the truth gives NaN in its
         ``log_score`` only."""
-        if of not in ("filtered", "smoothed"):
-            raise ValueError(f"belief_density: of must be 'filtered' or 'smoothed', got {of!r}")
-        states, log_a, log_b = self._recorded_sets(of, "belief_density")
+        states, log_a, log_b, y = self._summary_inputs("belief_density", of, truth, "mmf_pf_density serves at most {}", "None or a")
         T, N, M, d = states.shape
-        if M > _abi.DENSITY_MAX_M:
-            raise ValueError(f"belief_density: {M} particles per set; mmf_pf_density serves at most {_abi.DENSITY_MAX_M}")
-        if truth is not None and (not isinstance(truth, torch.Tensor) or tuple(truth.shape) != (T, N, d)):
-            raise ValueError(f"belief_density: truth must be None or a (T, N, d) = ({T}, {N}, {d}) tensor, got "
-                             f"{tuple(truth.shape) if isinstance(truth, torch.Tensor) else type(truth).__name__}")
-
-        def floats(value, name, or_what):
-            real = lambda v: not isinstance(v, bool) and isinstance(v, numbers.Real) and 0.0 < float(v) < math.inf
-            try:
-                vs = [] if isinstance(value, (str, bytes)) else [v for v in value]
-            except TypeError:
-                vs = []
-            if len(vs) != d or not all(real(v) for v in vs):
-                raise ValueError(f"belief_density: {name} must be {or_what} or {d} positive finite floats, got {value!r}")
-            return tuple(float(v) for v in vs)
-
+        floats = lambda value, name, or_what: self._positive_floats("belief_density", value, name, or_what, d)
         if isinstance(bandwidth, str) and bandwidth in ("silverman", "scott"):
             rule, fixed = str(bandwidth), None
         else:
@@ -919,7 +916,6 @@ class ParticleFilter(base.Filter):
         floor = floats(min_bandwidth, "min_bandwidth", "a positive finite float")
         dev = states.device
         with torch.no_grad():
-            y = None if truth is None else truth.detach().to(device=dev, dtype=torch.float32).contiguous()
             log_density = torch.empty((T, N, M), dtype=torch.float32, device=dev)
             log_score = None if y is None else torch.empty((T, N), dtype=torch.float32, device=dev)
             entropy = torch.empty((T, N), dtype=torch.float32, device=dev)
@@ -948,7 +944,7 @@ class ParticleFilter(base.Filter):
         (``evaluation.pit_histogram``).  Leaves ``last_quantiles``: ``probs`` (a tuple), ``quantiles``, ``of`` and, with a
         truth, ``pit``.  Draws no noise and leaves ``last_history`` / ``last_smoothed`` as they are.  A step without a live
         particle gives NaN."""
-        if of not in ("filtered", "smoothed"):
+        if of not in ("filtered", "smoothed"):  # (here as well as in _summary_inputs: it goes before the probs)
             raise ValueError(f"belief_quantiles: of must be 'filtered' or 'smoothed', got {of!r}")
         try:
             ps = [p for p in probs]
@@ -960,16 +956,10 @@ class ParticleFilter(base.Filter):
             if isinstance(p, bool) or not isinstance(p, numbers.Real) or not 0.0 <= float(p) <= 1.0:  # (a NaN fails the range)
                 raise ValueError(f"belief_quantiles: probs must be floats in [0, 1], got {p!r}")
         ps = tuple(float(p) for p in ps)
-        states, log_a, log_b = self._recorded_sets(of, "belief_quantiles")
+        states, log_a, log_b, query = self._summary_inputs("belief_quantiles", of, truth, "mmf_pf_quantiles sorts at most {} in LDS")
         T, N, M, d = states.shape
-        if M > _abi.QUANTILES_MAX_M:
-            raise ValueError(f"belief_quantiles: {M} particles per set; mmf_pf_quantiles sorts at most {_abi.QUANTILES_MAX_M} in LDS")
-        if truth is not None and (not isinstance(truth, torch.Tensor) or tuple(truth.shape) != (T, N, d)):
-            raise ValueError(f"belief_quantiles: truth must be a (T, N, d) = ({T}, {N}, {d}) tensor, got "
-                             f"{tuple(truth.shape) if isinstance(truth, torch.Tensor) else type(truth).__name__}")
         dev = states.device
         with torch.no_grad():
-            query = None if truth is None else truth.detach().to(device=dev, dtype=torch.float32).contiguous()
             quantiles = torch.empty((T, N, len(ps), d), dtype=torch.float32, device=dev)
             pit = None if query is None else torch.empty((T, N, d), dtype=torch.float32, device=dev)
             _abi.pf_quantiles(states, log_a, log_b, ps, quantiles, query, pit)

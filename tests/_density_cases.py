@@ -6,7 +6,7 @@ The cases are those of ``_score_cases.make_case`` (its ``family()`` without ``"s
 so the bandwidth rules would otherwise only be exercised there -- and three bandwidth variants: Silverman, Scott and the
 fixed bandwidths ``FIXED[:d]``.
 
-The reference is the header's definition in fp64, weights as in ``_score_cases`` (``_quantile_cases.weights64``: the kernel's
+The reference is the header's definition in fp64, weights as in ``_score_cases`` (``_summary_cases.weights64``: the kernel's
 own two fp32 operations on the log-weights, then fp64), the ``M + 1`` log-sum-exps in chunks of ``CHUNK`` queries so that no
 ``(M, M, d)`` array is formed.
 
@@ -19,18 +19,15 @@ import math
 
 import numpy as np
 
-import _quantile_cases as qc
 import _score_cases as sk
+import _summary_cases as sm
+from _summary_cases import CHUNK, GUARD_ROWS, MAX_M, SENTINEL  # noqa: F401 (read as dc.* by the tests)
 
 RULES = ("silverman", "scott", "fixed")
 FIXED = (0.3, 0.5, 1.0, 2.0)
 MIN_BANDWIDTH = 1e-6
 VARIANTS = tuple(v for v in sk.VARIANTS if v != "scaled") + ("moderate",)
 CAP = sk.CAP                      # REL_TOL / 3
-SENTINEL = sk.SENTINEL
-GUARD_ROWS = sk.GUARD_ROWS
-MAX_M = 16384
-CHUNK = 256
 FLOAT_OUTPUTS = ("log_density", "log_score", "entropy", "mode", "bandwidth")
 OUTPUTS = FLOAT_OUTPUTS + ("mode_index",)
 
@@ -131,7 +128,7 @@ def reference_rows(X, W, truth, rule, bandwidth=None, min_bandwidth=None):
 
 def reference(case):
     """The outputs of a case by the fp64 definition; NaN and ``-inf`` where the definition puts them."""
-    return reference_rows(case["states"], qc.weights64(case), case["truth"], case["rule"], case["bandwidth"], case["min_bandwidth"])
+    return reference_rows(case["states"], sm.weights64(case), case["truth"], case["rule"], case["bandwidth"], case["min_bandwidth"])
 
 
 @functools.lru_cache(maxsize=None)
@@ -150,7 +147,7 @@ def torch_formulation(case, dtype=None, chunk=CHUNK, device=None):
     dtype = dtype or torch.float32
     X = torch.from_numpy(np.ascontiguousarray(case["states"])).to(device=device, dtype=dtype)
     with np.errstate(invalid="ignore"):
-        t = torch.from_numpy(qc.log_weight32(case)).to(device=device, dtype=dtype)
+        t = torch.from_numpy(sm.log_weight32(case)).to(device=device, dtype=dtype)
     y = None if case["truth"] is None else torch.from_numpy(case["truth"]).to(device=device, dtype=dtype)
     return torch_rows(X, t, y, case["rule"], case["bandwidth"], case["min_bandwidth"], chunk)
 

@@ -18,6 +18,9 @@ import math
 
 import numpy as np
 
+import _summary_cases as sm
+from _summary_cases import GUARD_ROWS, MAX_M, SENTINEL, log_weight32, weights64  # noqa: F401 (read as qc.* by the tests)
+
 MS = (1, 2, 63, 64, 65, 255, 256, 257, 1000, 4096)  # around a wave, a 256-block, a non-power-of-two, the workload's own size
 DIMS = (1, 2, 3, 4)
 RS = (1, 5)
@@ -25,9 +28,6 @@ PROBS = (0.0, 0.025, 0.05, 0.25, 0.5, 0.75, 0.95, 0.975, 1.0)
 VARIANTS = ("plain", "dead_row", "uniform", "only_a", "only_b", "cdf_only", "query_particle", "query_below", "query_above")
 EXACT = tuple((M, dead) for M in (1, 2, 63, 64, 65, 257, 1000) for dead in (False, True) if M > 8 or not dead)  # (M, an eighth dead)
 REF_EPS = 1e-12
-SENTINEL = -77.25
-GUARD_ROWS = 2
-MAX_M = 16384
 
 
 def eps(M):
@@ -40,33 +40,12 @@ def probs32(probs=PROBS):
 
 
 def make_case(M, d, R, variant="plain", seed=0):
-    """``dict(states (R, M, d), log_a, log_b (R, M) or None, query (R, d), probs)`` of the family: N(0, 1) states, half of
-    them copies of others (resampled sets are full of duplicates), ``log_a = -log M + 0.3 N(0, 1)``, ``log_b = -40 + 6 N(0,
-    1)``; for ``M > 8`` an eighth of ``log_b`` is ``-inf`` with NaN state rows there.  The queries cycle through a particle's own
-    value, below all, above all, N(0, 1) and NaN unless the variant fixes the kind."""
+    """``dict(states (R, M, d), log_a, log_b (R, M) or None, query (R, d), probs)`` of the family: the weighted set of
+    ``_summary_cases.weighted_set`` with queries that cycle through a particle's own value, below all, above all, N(0, 1) and
+    NaN unless the variant fixes the kind."""
     assert variant in VARIANTS
     rng = np.random.default_rng(1000003 * M + 1009 * d + 101 * R + 7 * VARIANTS.index(variant) + seed)
-    X = rng.standard_normal((R, M, d)).astype(np.float32)
-    for r in range(R):
-        dst = rng.choice(M, M // 2, replace=False)
-        X[r, dst] = X[r, rng.integers(0, M, M // 2)]
-    la = (-math.log(M) + 0.3 * rng.standard_normal((R, M))).astype(np.float32)
-    lb = (-40.0 + 6.0 * rng.standard_normal((R, M))).astype(np.float32)
-    if M > 8:
-        for r in range(R):
-            dead = rng.choice(M, M // 8, replace=False)
-            lb[r, dead] = -np.inf
-            X[r, dead] = np.nan
-    if variant == "dead_row":
-        lb[R // 2] = -np.inf
-    if variant == "uniform":
-        la, lb = None, None
-        X = np.where(np.isnan(X), np.float32(0.5), X)  # (every particle carries weight: no NaN among them)
-    elif variant == "only_a":
-        la, lb = lb, None
-    elif variant == "only_b":
-        la = None
-    live = np.ones((R, M), bool) if lb is None and la is None else np.isfinite((lb if lb is not None else la))
+    X, la, lb, live = sm.weighted_set(rng, M, d, R, variant)
     query = np.empty((R, d), np.float32)
     kinds = {"query_particle": 0, "query_below": 1, "query_above": 2}
     for r in range(R):
@@ -81,18 +60,12 @@ def make_case(M, d, R, variant="plain", seed=0):
 def exact_case(M, d, R, dead, seed=0):
     """Equal weights (``log_a`` one constant, ``log_b`` 0 or ``-inf``): the result is a rank of the live particles."""
     rng = np.random.default_rng(77 * M + 5 * d + R + 1000 * int(dead) + seed)
-    X = rng.standard_normal((R, M, d)).astype(np.float32)
-    for r in range(R):
-        dst = rng.choice(M, M // 2, replace=False)
-        X[r, dst] = X[r, rng.integers(0, M, M // 2)]
+    X = sm.duplicated_states(rng, M, d, R)
     la = np.full((R, M), -math.log(M), np.float32)
     lb = None
     if dead:
         lb = np.zeros((R, M), np.float32)
-        for r in range(R):
-            gone = rng.choice(M, M // 8, replace=False)
-            lb[r, gone] = -np.inf
-            X[r, gone] = np.nan
+        sm.kill_an_eighth(rng, X, lb)
     query = np.empty((R, d), np.float32)
     for r in range(R):
         for k in range(d):
@@ -117,24 +90,6 @@ def exact_expected(case):
                 quant[r, i, k] = xs[max(1, math.ceil(p * n)) - 1]
             cdf[r, k] = np.float32(np.count_nonzero(xs <= query[r, k]) / n)
     return quant, cdf
-
-
-def log_weight32(case):
-    """``t = (log_a + log_b) - max`` with the kernel's fp32 operations: ``(R, M)`` float32; a row without a live particle is NaN."""
-    R, M, _ = case["states"].shape
-    zero = np.zeros((R, M), np.float32)
-    la = zero if case["log_a"] is None else case["log_a"]
-    lb = zero if case["log_b"] is None else case["log_b"]
-    with np.errstate(invalid="ignore"):
-        a = (la + lb).astype(np.float32)
-        top = np.fmax.reduce(a, axis=1, initial=-np.inf).astype(np.float32)  # (fmax skips NaN)
-        return (a - top[:, None]).astype(np.float32)
-
-
-def weights64(case):
-    t = log_weight32(case)
-    with np.errstate(invalid="ignore"):
-        return np.where(t <= 0, np.exp(t.astype(np.float64)), 0.0)  # (NaN: no weight)
 
 
 def _sorted_cdf(x, w):

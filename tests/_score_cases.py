@@ -2,7 +2,7 @@
 numpy / torch on the CPU; shared by ``test_score_cases_cpu.py`` and ``test_gpu_scores.py``.
 
 The reference is the header's definition in fp64: ``a = log_a + log_b`` and ``t = a - max a`` with the kernel's own two fp32
-operations (``_quantile_cases.log_weight32``), then ``w = exp(float64(t))``, ``W = w / sum w`` and
+operations (``_summary_cases.log_weight32``), then ``w = exp(float64(t))``, ``W = w / sum w`` and
 
     crps[k]   = sum_m W_m |x_mk - y_k| - 1/2 spread[k]          spread[k] = sum_m sum_l W_m W_l |x_mk - x_lk|
     energy    = sum_m W_m |(x_m - y) / s| - 1/2 spread[d]       spread[d] = sum_m sum_l W_m W_l |(x_m - x_l) / s|
@@ -16,7 +16,8 @@ import math
 
 import numpy as np
 
-import _quantile_cases as qc
+import _summary_cases as sm
+from _summary_cases import CHUNK, GUARD_ROWS, MAX_M, SENTINEL  # noqa: F401 (read as sk.* by the tests)
 
 # the kernel's own sizes (csrc/pf_scores.hip): a row is one workgroup with one i-particle per thread up to I_BLOCK particles and
 # ceil(M / I_BLOCK) workgroups with two beyond; j-tiles of J_TILE particles; fp32 runs of RUN pairs
@@ -30,40 +31,15 @@ RS = (1, 3)
 VARIANTS = ("plain", "uniform", "only_a", "only_b", "dead_row", "nan_truth", "no_truth", "scaled")
 SCALE = (0.5, 2.0, 1.0, 4.0)
 CAP = 3e-5                       # REL_TOL / 3, the margin CAP_RTS uses
-SENTINEL = -77.25
-GUARD_ROWS = 2
-MAX_M = 16384
-CHUNK = 256
 
 
 def make_case(M, d, R, variant="plain", seed=0):
-    """``dict(states (R, M, d), log_a, log_b (R, M) or None, truth (R, d) or None, scale (d floats) or None)``: the family of
-    ``_quantile_cases.make_case`` -- N(0, 1) states, half of them copies of others, ``log_a = -log M + 0.3 N(0, 1)``, ``log_b
-    = -40 + 6 N(0, 1)``, for ``M > 8`` an eighth of the particles dead (``-inf``, NaN state rows) -- with truths that cycle
-    per row through a live particle's own value, the live mean + 5 and N(0, 1)."""
+    """``dict(states (R, M, d), log_a, log_b (R, M) or None, truth (R, d) or None, scale (d floats) or None)``: the weighted
+    set of ``_summary_cases.weighted_set`` with truths that cycle per row through a live particle's own value, the live mean
+    + 5 and N(0, 1)."""
     assert variant in VARIANTS
     rng = np.random.default_rng(2000003 * M + 1013 * d + 103 * R + 11 * VARIANTS.index(variant) + seed)
-    X = rng.standard_normal((R, M, d)).astype(np.float32)
-    for r in range(R):
-        dst = rng.choice(M, M // 2, replace=False)
-        X[r, dst] = X[r, rng.integers(0, M, M // 2)]
-    la = (-math.log(M) + 0.3 * rng.standard_normal((R, M))).astype(np.float32)
-    lb = (-40.0 + 6.0 * rng.standard_normal((R, M))).astype(np.float32)
-    if M > 8:
-        for r in range(R):
-            dead = rng.choice(M, M // 8, replace=False)
-            lb[r, dead] = -np.inf
-            X[r, dead] = np.nan
-    if variant == "dead_row":
-        lb[R // 2] = -np.inf
-    if variant == "uniform":
-        la, lb = None, None
-        X = np.where(np.isnan(X), np.float32(0.5), X)  # (every particle carries weight: no NaN among them)
-    elif variant == "only_a":
-        la, lb = lb, None
-    elif variant == "only_b":
-        la = None
-    live = np.ones((R, M), bool) if lb is None and la is None else np.isfinite((lb if lb is not None else la))
+    X, la, lb, live = sm.weighted_set(rng, M, d, R, variant)
     truth = np.empty((R, d), np.float32)
     for r in range(R):
         xs = X[r][live[r]] if live[r].any() else np.zeros((1, d), np.float32)
@@ -133,7 +109,7 @@ def reference_rows(X, W, truth, scale):
 
 def reference(case):
     """``(crps, energy, spread)`` of a case by the fp64 definition; NaN where the definition puts it."""
-    return reference_rows(case["states"], qc.weights64(case), case["truth"], _scale64(case))
+    return reference_rows(case["states"], sm.weights64(case), case["truth"], _scale64(case))
 
 
 @functools.lru_cache(maxsize=None)
@@ -152,7 +128,7 @@ def torch_formulation(case, dtype=None, chunk=CHUNK):
     X = torch.from_numpy(np.ascontiguousarray(case["states"])).to(dtype)
     R, M, d = X.shape
     with np.errstate(invalid="ignore"):
-        t = torch.from_numpy(qc.log_weight32(case)).to(dtype)
+        t = torch.from_numpy(sm.log_weight32(case)).to(dtype)
     w = torch.where(t <= 0, torch.exp(t), torch.zeros_like(t))
     S = w.sum(-1, keepdim=True)
     W = w / S

@@ -335,3 +335,11 @@ def host_args(struct_cls, pointer_fields, **over):
     for k, v in over.items():
         setattr(a, k, v)
     return a
+
+
+def alias_host_args(a, pointer_fields, alias):
+    """Points fields of a ``host_args`` struct into the buffers of other fields: ``alias`` maps a field to ``(the field whose
+    buffer it is pointed at, byte offset)``, or is ``None``.  Returns ``a``."""
+    for field, (target, offset) in (alias or {}).items():
+        setattr(a, field, ctypes.c_void_p(ctypes.addressof(a._buffers[pointer_fields.index(target)]) + offset))
+    return a

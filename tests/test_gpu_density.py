@@ -7,7 +7,6 @@ The bar of ``log_density``, ``log_score`` and ``entropy``: ``|got - fp64| <= REL
 with ``-inf`` and NaN exactly where the definition puts them; ``bandwidth``: ``rel_err_elementwise < REL_TOL``; the mode is the
 first maximum of the kernel's own ``log_density``, a bit copy of that particle, and within the bar of the reference's maximum
 (``_density_cases.check_mode``).  Every figure is printed before it is asserted."""
-import functools
 import itertools
 
 import numpy as np
@@ -18,28 +17,13 @@ import _density_cases as dc
 import _quantile_cases as qc
 import _score_cases as sk
 import _smooth_cases as sc
+import _summary_gpu as sg
+from _summary_gpu import N, _filter_run, _Guarded, _same_bits
 from _tol import REL_TOL
 
 pytestmark = pytest.mark.gpu
 
 OUTPUTS = dc.OUTPUTS
-INT_SENTINEL = -77
-
-
-class _Guarded:
-    """A device array of ``rows`` leading slices between ``GUARD_ROWS`` guard slices holding the sentinel."""
-
-    def __init__(self, rows, tail, dev, dtype=torch.float32):
-        self.sentinel = dc.SENTINEL if dtype == torch.float32 else INT_SENTINEL
-        self.full = torch.full((rows + 2 * dc.GUARD_ROWS,) + tuple(tail), self.sentinel, dtype=dtype, device=dev)
-        self.view = self.full[dc.GUARD_ROWS:dc.GUARD_ROWS + rows]
-
-    def guards_intact(self):
-        g = dc.GUARD_ROWS
-        return bool((self.full[:g] == self.sentinel).all()) and bool((self.full[self.full.shape[0] - g:] == self.sentinel).all())
-
-    def untouched(self):
-        return bool((self.full == self.sentinel).all())
 
 
 def _run(case, want=OUTPUTS, rows=None):
@@ -66,13 +50,6 @@ def _run(case, want=OUTPUTS, rows=None):
         if k not in want:
             assert b.untouched(), f"{k} was not asked for and was written (M={M} d={d} R={R})"
     return {k: (bufs[k].view.clone() if k in want else None) for k in OUTPUTS}
-
-
-N = lambda t: None if t is None else t.cpu().numpy()
-
-
-def _same_bits(a, b):
-    return torch.equal(a.view(torch.int32), b.view(torch.int32))
 
 
 def _hold(case, ref, got, what):
@@ -205,29 +182,9 @@ def test_the_log_score_at_a_particle_is_that_particles_log_density(M):
 
 
 # ------------------------------------------------------------------------------------------ 5. through the filter
-@functools.lru_cache(maxsize=None)
-def _filter_run(M, N_=3, T=6):
-    import multimodalfilter_amd as mmf
-
-    dev = sc.dev()
-    f, d, traj, obs, ctrl, cov = sc.small_filter("DoorCrossmodalParticleFilter", N_, M, T, dev)
-
-    def forward():
-        f.record_history = True
-        f.noise = mmf.NoiseSource(31)
-        f.initialize_beliefs(mean=traj["states"][0], covariance=cov)
-        est = f.forward_loop(observations=obs, controls=ctrl)
-        torch.cuda.synchronize()
-        return est
-
-    return f, forward, traj, (T, N_, M, d)
-
-
 def _case_of(states, log_a, log_b, truth, rule="silverman", bandwidth=None, min_bandwidth=dc.MIN_BANDWIDTH):
-    T, N_, M, d = states.shape
-    flat = lambda x, tail: None if x is None else x.detach().cpu().numpy().reshape((T * N_,) + tail)
-    return dict(states=flat(states, (M, d)), log_a=flat(log_a, (M,)), log_b=flat(log_b, (M,)), truth=flat(truth, (d,)), rule=rule,
-                bandwidth=bandwidth, min_bandwidth=(min_bandwidth,) * d)
+    d = states.shape[-1]
+    return sg._case_of(states, log_a, log_b, truth, rule=rule, bandwidth=bandwidth, min_bandwidth=(min_bandwidth,) * d)
 
 
 def _hold_record(rec, case, shape, what):
@@ -246,7 +203,7 @@ def test_belief_density_on_a_real_filter(M):
     the quantile and score records and the noise stream are what they are without the calls."""
     from multimodalfilter_amd.utils import ReplayNoise
 
-    f, forward, traj, shape = _filter_run(M)
+    f, forward, traj, shape = _filter_run("DoorCrossmodalParticleFilter", M, owner="density")
     T, N_, _, d = shape
     est = forward().clone()
     h = f.last_history

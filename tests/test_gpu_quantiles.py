@@ -6,7 +6,6 @@
 The rule: a quantile is a live particle's own value ``v`` with ``F(v) >= p - eps`` and ``F-(v) < p + eps``; a cdf is within
 ``eps`` of ``F(query)``; ``eps = (M + 16) 2^-24`` (derived in ``_quantile_cases``).  Every worst distance is printed before the
 next case is asserted."""
-import functools
 
 import numpy as np
 import pytest
@@ -14,23 +13,9 @@ import torch
 
 import _quantile_cases as qc
 import _smooth_cases as sc
+from _summary_gpu import N, _case_of, _filter_run, _Guarded, _same_bits
 
 pytestmark = pytest.mark.gpu
-
-
-class _Guarded:
-    """A float32 device array of ``rows`` leading slices between ``GUARD_ROWS`` guard slices holding the sentinel."""
-
-    def __init__(self, rows, tail, dev):
-        self.full = torch.full((rows + 2 * qc.GUARD_ROWS,) + tuple(tail), qc.SENTINEL, dtype=torch.float32, device=dev)
-        self.view = self.full[qc.GUARD_ROWS:qc.GUARD_ROWS + rows]
-
-    def guards_intact(self):
-        g = qc.GUARD_ROWS
-        return bool((self.full[:g] == qc.SENTINEL).all()) and bool((self.full[self.full.shape[0] - g:] == qc.SENTINEL).all())
-
-    def untouched(self):
-        return bool((self.full == qc.SENTINEL).all())
 
 
 def _run(case, with_query=True, rows=None):
@@ -54,9 +39,6 @@ def _run(case, with_query=True, rows=None):
     if not with_query:
         assert cdf.untouched()
     return (quant.view.clone() if Q else None), (cdf.view.clone() if with_query else None)
-
-
-N = lambda t: None if t is None else t.cpu().numpy()
 
 
 # ------------------------------------------------------------------------------------------ 1. the kernel against the rule
@@ -96,10 +78,6 @@ def test_kernel_at_the_particle_limit():
 
 
 # ------------------------------------------------------------------------------------------ 2. bit-for-bit identities
-def _same_bits(a, b):
-    return torch.equal(a.view(torch.int32), b.view(torch.int32))
-
-
 @pytest.mark.parametrize("M", [1, 65, 257, 512, 513, 1000, 4096])  # (512 | 513: one wave | 256 threads)
 def test_two_calls_and_a_row_alone_give_the_same_bits(M):
     for d, variant in ((1, "plain"), (3, "dead_row"), (4, "plain")):
@@ -149,37 +127,13 @@ def test_properties_that_need_no_reference(M):
 
 
 # ------------------------------------------------------------------------------------------ 4. through the filter
-@functools.lru_cache(maxsize=None)
-def _filter_run(N=3, M=64, T=6):
-    import multimodalfilter_amd as mmf
-
-    dev = sc.dev()
-    f, d, traj, obs, ctrl, cov = sc.small_filter("DoorParticleFilter", N, M, T, dev)
-
-    def forward():
-        f.record_history = True
-        f.noise = mmf.NoiseSource(31)
-        f.initialize_beliefs(mean=traj["states"][0], covariance=cov)
-        est = f.forward_loop(observations=obs, controls=ctrl)
-        torch.cuda.synchronize()
-        return est
-
-    return f, forward, traj, (T, N, M, d)
-
-
-def _case_of(states, log_a, log_b, truth, probs):
-    T, N_, M, d = states.shape
-    flat = lambda x, tail: None if x is None else x.detach().cpu().numpy().reshape((T * N_,) + tail)
-    return dict(states=flat(states, (M, d)), log_a=flat(log_a, (M,)), log_b=flat(log_b, (M,)), query=flat(truth, (d,)), probs=probs)
-
-
 def test_belief_quantiles_on_a_real_filter():
     """``of="filtered"`` and, after the marginal smoother, ``of="smoothed"`` are held to the rule on the CPU from the records'
     own tensors; after backward simulation the draws' quantiles are a rank of ``torch.sort``.  Nothing else moves: the
     estimates, the history, the smoothed record and the noise stream are what they are without the calls."""
     from multimodalfilter_amd.utils import ReplayNoise
 
-    f, forward, traj, (T, N_, M, d) = _filter_run()
+    f, forward, traj, (T, N_, M, d) = _filter_run("DoorParticleFilter", 64)
     est = forward().clone()
     h = f.last_history
     truth = traj["states"][1:]
@@ -190,7 +144,7 @@ def test_belief_quantiles_on_a_real_filter():
     rec = f.last_quantiles
     assert set(vars(rec)) == {"probs", "quantiles", "of", "pit"} and rec.of == "filtered" and rec.probs == probs
     assert rec.quantiles is quant and quant.shape == (T, N_, 3, d) and rec.pit.shape == (T, N_, d)
-    case = _case_of(h.states, h.log_weights_in, h.log_likelihoods, truth, probs)
+    case = _case_of(h.states, h.log_weights_in, h.log_likelihoods, truth, point="query", probs=probs)
     wq, wc = qc.check(case, N(quant).reshape(T * N_, 3, d), N(rec.pit).reshape(T * N_, d))
     print(f"filtered: worst F-distance {wq:.3e}, worst pit error {wc:.3e} (eps {qc.eps(M):.3e})")
     assert bool(((rec.pit >= 0) & (rec.pit <= 1)).all())
@@ -209,7 +163,7 @@ def test_belief_quantiles_on_a_real_filter():
     weights = s.weights.clone()
     quant = f.belief_quantiles(probs, of="smoothed", truth=truth)
     assert f.last_smoothed is s and torch.equal(s.weights, weights) and f.last_quantiles.of == "smoothed"
-    case = _case_of(h.states, torch.log(weights), None, truth, probs)
+    case = _case_of(h.states, torch.log(weights), None, truth, point="query", probs=probs)
     wq, wc = qc.check(case, N(quant).reshape(T * N_, 3, d), N(f.last_quantiles.pit).reshape(T * N_, d))
     print(f"marginal: worst F-distance {wq:.3e}, worst pit error {wc:.3e} (eps {qc.eps(M):.3e})")
     assert torch.equal(f.smooth(method="marginal"), mean)

@@ -5,36 +5,21 @@ to end on small real filters.
 
 The bar: ``rel_err_elementwise(got, fp64, floor=1e-3) < REL_TOL`` for ``crps``, ``energy`` and ``spread``, with NaN exactly
 where the definition puts it.  Every figure is printed before it is asserted."""
-import functools
 import itertools
 
 import numpy as np
 import pytest
 import torch
 
-import _quantile_cases as qc
 import _score_cases as sk
 import _smooth_cases as sc
+import _summary_gpu as sg
+from _summary_gpu import N, _filter_run, _Guarded, _same_bits
 from _tol import REL_TOL
 
 pytestmark = pytest.mark.gpu
 
 OUTPUTS = ("crps", "energy", "spread")
-
-
-class _Guarded:
-    """A float32 device array of ``rows`` leading slices between ``GUARD_ROWS`` guard slices holding the sentinel."""
-
-    def __init__(self, rows, tail, dev):
-        self.full = torch.full((rows + 2 * sk.GUARD_ROWS,) + tuple(tail), sk.SENTINEL, dtype=torch.float32, device=dev)
-        self.view = self.full[sk.GUARD_ROWS:sk.GUARD_ROWS + rows]
-
-    def guards_intact(self):
-        g = sk.GUARD_ROWS
-        return bool((self.full[:g] == sk.SENTINEL).all()) and bool((self.full[self.full.shape[0] - g:] == sk.SENTINEL).all())
-
-    def untouched(self):
-        return bool((self.full == sk.SENTINEL).all())
 
 
 def _run(case, want=OUTPUTS, rows=None, states=None):
@@ -56,13 +41,6 @@ def _run(case, want=OUTPUTS, rows=None, states=None):
         if k not in want:
             assert b.untouched(), f"{k} was not asked for and was written (M={M} d={d} R={R})"
     return {k: (bufs[k].view.clone() if k in want else None) for k in OUTPUTS}
-
-
-N = lambda t: None if t is None else t.cpu().numpy()
-
-
-def _same_bits(a, b):
-    return torch.equal(a.view(torch.int32), b.view(torch.int32))
 
 
 def _hold(case, ref, got, what):
@@ -165,28 +143,8 @@ def test_scale_divides_the_coordinates_of_the_norm_only(M):
 
 
 # ------------------------------------------------------------------------------------------ 4. through the filter
-@functools.lru_cache(maxsize=None)
-def _filter_run(M, N_=3, T=6):
-    import multimodalfilter_amd as mmf
-
-    dev = sc.dev()
-    f, d, traj, obs, ctrl, cov = sc.small_filter("DoorCrossmodalParticleFilter", N_, M, T, dev)
-
-    def forward():
-        f.record_history = True
-        f.noise = mmf.NoiseSource(31)
-        f.initialize_beliefs(mean=traj["states"][0], covariance=cov)
-        est = f.forward_loop(observations=obs, controls=ctrl)
-        torch.cuda.synchronize()
-        return est
-
-    return f, forward, traj, (T, N_, M, d)
-
-
 def _case_of(states, log_a, log_b, truth, scale=None):
-    T, N_, M, d = states.shape
-    flat = lambda x, tail: None if x is None else x.detach().cpu().numpy().reshape((T * N_,) + tail)
-    return dict(states=flat(states, (M, d)), log_a=flat(log_a, (M,)), log_b=flat(log_b, (M,)), truth=flat(truth, (d,)), scale=scale)
+    return sg._case_of(states, log_a, log_b, truth, scale=scale)
 
 
 def _hold_record(rec, case, shape, what):
@@ -202,7 +160,7 @@ def test_belief_scores_on_a_real_filter(M):
     the quantile record and the noise stream are what they are without the calls."""
     from multimodalfilter_amd.utils import ReplayNoise
 
-    f, forward, traj, shape = _filter_run(M)
+    f, forward, traj, shape = _filter_run("DoorCrossmodalParticleFilter", M, owner="scores")
     T, N_, _, d = shape
     est = forward().clone()
     h = f.last_history

@@ -69,16 +69,14 @@ def test_float32_probabilities_set_the_rank():
 
 # ------------------------------------------------------------------------------------------ 2. the entry point's host checks
 def _args(alias=None, probs=(0.25, 0.75), **over):
-    """Sizes at which every array fits the 16-float buffer ``host_args`` gives it; ``alias``: output field -> (field whose
-    buffer it is pointed at, byte offset)."""
+    """Sizes at which every array fits the 16-float buffer ``host_args`` gives it; ``alias``: as for
+    ``_smooth_cases.alias_host_args``."""
     from multimodalfilter_amd import _abi
 
     a = sc.host_args(_abi.MmfPfQuantilesArgs, _POINTERS, **{**dict(R=2, M=2, d=2, Q=len(probs)), **over})
     for i, p in enumerate(probs):
         a.probs[i] = p
-    for field, (target, offset) in (alias or {}).items():
-        setattr(a, field, ctypes.c_void_p(ctypes.addressof(a._buffers[_POINTERS.index(target)]) + offset))
-    return a
+    return sc.alias_host_args(a, _POINTERS, alias)
 
 
 def test_quantiles_refuses_bad_arguments_on_the_host():

@@ -174,16 +174,14 @@ def test_score_summary_against_hand_computed_values():
 
 # ------------------------------------------------------------------------------------------ 4. the entry point's host checks
 def _args(alias=None, scale=(1.0, 1.0), **over):
-    """Sizes at which every array fits the 16-float buffer ``host_args`` gives it; ``alias``: output field -> (field whose
-    buffer it is pointed at, byte offset)."""
+    """Sizes at which every array fits the 16-float buffer ``host_args`` gives it; ``alias``: as for
+    ``_smooth_cases.alias_host_args``."""
     from multimodalfilter_amd import _abi
 
     a = sc.host_args(_abi.MmfPfScoresArgs, _POINTERS, **{**dict(R=2, M=2, d=2, workspace_bytes=64), **over})
     for i, s in enumerate(scale):
         a.scale[i] = s
-    for field, (target, offset) in (alias or {}).items():
-        setattr(a, field, ctypes.c_void_p(ctypes.addressof(a._buffers[_POINTERS.index(target)]) + offset))
-    return a
+    return sc.alias_host_args(a, _POINTERS, alias)
 
 
 def test_scores_refuses_bad_arguments_on_the_host():
