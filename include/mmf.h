@@ -1082,6 +1082,77 @@ typedef struct MmfPfDensityArgs {
 int mmf_pf_density(const MmfPfDensityArgs* args /* host */, void* stream);
 size_t mmf_pf_density_workspace_bytes(int R, int M, int d);
 
+/* ---------------------------------------------------------------- Particle-posterior modes: quick-shift partition and masses
+ * The evaluation of crossmodal/eval_helpers.py:148-160 scores one point estimate per step, and every summary above describes
+ * the particle set as a whole: the density's `mode` is one particle and knows no second one.  The question a multimodal
+ * belief raises first -- how many hypotheses does it hold, where is each, how much probability does each carry -- is answered
+ * by quick shift (Vedaldi & Soatto, ECCV 2008) on the kernel density above: every particle points to its nearest neighbour
+ * of higher density within a radius, the roots of that forest are the modes and a tree's weight is the mode's mass.  It is
+ * deterministic, iterates nothing and has one parameter in bandwidth units; in torch ops it is an (M, M, d) broadcast and a
+ * Python loop over clusters.  Purely additive to ABI 42: a struct and two symbols of their own.
+ * Per row r (R rows, e.g. T * N, of M particles x_m = states[r, m, :]) with l_m = log_density[r, m] and h_k = bandwidth[r, k]
+ * -- the arrays mmf_pf_density writes, but inputs here, whoever wrote them -- and the host scalars tau = link_radius (finite,
+ * > 0, in bandwidth units) and K = max_modes (1 .. 8):
+ *   a_m, t_m = a_m - max a, w_m = live_weight(t_m)     exactly as in "Particle-posterior scores"
+ *   takes part     w_m > 0 and l_m is not NaN; every other particle is dead: parent = labels = -1, and its state row (NaN by
+ *                  convention) is never read into anything
+ *   j > i          l_j > l_i, or l_j == l_i and j < i: the fp32 values as given, compared as floats -- a strict total
+ *                  order, so the links form no cycle, duplicated particles included
+ *   D2(i, j)       = sum_k ((x_ik - x_jk) / h_k)^2; the kernel: the fp32 difference, times the fp32 reciprocal 1 / h_k, squared
+ *                  and summed over k in order -- a set far from the origin partitions exactly as the same set at the origin
+ *   parent[i]      among the j that take part with j > i and D2(i, j) <= tau^2 (fp32 tau * tau): the one of least D2, the
+ *                  lowest j among equals; -1 (a root) if there is none
+ *   labels[i]      the root of i's tree, a particle index; labels[root] == root
+ *   count          the number of roots; 0 in a row where no particle takes part
+ *   q_m            = (uint64) floor(w_m 2^40): exact for any float w_m <= 1, a row's sum stays below 2^54
+ *   Q_root         = sum of q_m over labels[m] == root;   mass = Q_root / sum_m q_m, formed in double, written as float:
+ *                  every sum is an integer, so its order cannot matter
+ *   reported       the min(count, K) roots of greatest Q_root, the lower root first among equals, in that order; for rank c
+ *                  index[r, c] the root, modes[r, c, :] a bit copy of its state, mass[r, c] its mass,
+ *                  mean[r, c, :] = sum over its members of q_m x_m / Q_root in double, in one fixed order;
+ *                  ranks beyond count hold -1 / NaN / 0 / NaN; a reported mode with Q_root = 0 has mass 0 and mean NaN
+ * Determinism: two calls give the same bits, a row's result depends on neither R nor the other rows, and whichever outputs
+ * are null, the others are the bits of the full call.  No floating-point atomics; the q_m are added into their roots with
+ * 64-bit integer atomics, whose result does not depend on their order.
+ * Kernel plan: no (M, M) array in memory.  The link pass is dealt like the scores and the density: nb = ceil(M / 512)
+ * workgroups to a row, one i-particle of a thread in registers (M <= 512) or two, j-tiles of 1024 particles through LDS as
+ * structure-of-arrays (d coordinate planes and one of l, NaN for a particle that does not take part), four j per broadcast
+ * 16-byte read; per pair d subtract / multiply / accumulate steps, the order test, the radius test and a strict < against
+ * the running best with j ascending, which is the lowest-j rule.  Every i writes its own parent: no partials, no finishing
+ * launch of this pass.  The finish is one workgroup per row: parent into LDS, ceil(log2 M) double-buffered rounds of pointer
+ * jumping leave labels; the q_m are added into their roots in LDS up to M = 8192 (MMF_PF_MODES_LDS_MASS_M: labels and masses
+ * together fit the 160 KiB) and in the workspace beyond; K arg-max reductions on (Q_root, -root), each below the one before,
+ * and the K d means in the fixed order of the other summaries' sums.
+ * mmf_pf_modes_workspace_bytes(R, M, d): 8 R M bytes for M > 8192 (the masses) and 4 R M for the links, rounded up to 8
+ * (read when parent is null, asked for always); 0 for R, M or d below 1.
+ * Limits, all decided on the host before any HIP call: null args / states / log_density / bandwidth, d outside 1 .. 4, M < 1,
+ * R < 0, max_modes outside 1 .. 8, a link_radius that is not finite and positive, all seven outputs null, a workspace that is
+ * null, smaller than the query's answer or not 8-byte aligned, an output (or the workspace) overlapping an input or another
+ * output -> MMF_EINVAL; M > 16384 or R * nb beyond a 32-bit grid -> MMF_ETOOLARGE; R == 0 is a successful no-op. */
+#define MMF_PF_MODES_MAX 8
+#define MMF_PF_MODES_LDS_MASS_M 8192
+typedef struct MmfPfModesArgs {
+  int32_t R, M, d;                  /* R rows (e.g. T*N) of M particles */
+  int32_t max_modes;                /* K, 1 .. MMF_PF_MODES_MAX */
+  float link_radius;                /* tau > 0 and finite, in bandwidth units */
+  const float* states;              /* (R, M, d) */
+  const float* log_a;               /* (R, M) or null = 0 */
+  const float* log_b;               /* (R, M) or null = 0 (history: log_weights_in + log_likelihoods) */
+  const float* log_density;         /* (R, M): mmf_pf_density's log_density, or any other ordering of the particles */
+  const float* bandwidth;           /* (R, d): mmf_pf_density's bandwidth_out */
+  int32_t* parent;                  /* (R, M) or null */
+  int32_t* labels;                  /* (R, M) or null */
+  int32_t* count;                   /* (R) or null */
+  int32_t* index;                   /* (R, K) or null */
+  float* modes;                     /* (R, K, d) or null */
+  float* mass;                      /* (R, K) or null */
+  float* mean;                      /* (R, K, d) or null */
+  void* workspace;                  /* device, 8-byte aligned, mmf_pf_modes_workspace_bytes(R, M, d) bytes */
+  size_t workspace_bytes;
+} MmfPfModesArgs;                   /* host struct holding device pointers */
+int mmf_pf_modes(const MmfPfModesArgs* args /* host */, void* stream);
+size_t mmf_pf_modes_workspace_bytes(int R, int M, int d);
+
 /* ---------------------------------------------------------------- K6, fused: one network call of the training backward
  * Recompute (the forward pass's f16x3 arithmetic), backward data path and weight / bias gradients of ONE per-particle
  * network over N * M rows in one kernel (the dynamics network: three launches -- encoder forward, trunk, encoder

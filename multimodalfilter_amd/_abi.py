@@ -137,7 +137,7 @@ class MmfPfSmoothMapArgs(Structure):
 
 QUANTILES_MAX = 16    # MMF_QUANTILES_MAX
 SUMMARY_MAX_M = 16384  # particles per row that mmf_pf_quantiles sorts in LDS and mmf_pf_scores and mmf_pf_density serve
-QUANTILES_MAX_M = SCORES_MAX_M = DENSITY_MAX_M = SUMMARY_MAX_M
+QUANTILES_MAX_M = SCORES_MAX_M = DENSITY_MAX_M = MODES_MAX_M = SUMMARY_MAX_M
 
 
 class MmfPfQuantilesArgs(Structure):
@@ -159,6 +159,17 @@ class MmfPfDensityArgs(Structure):
                 ("bandwidth", ctypes.c_float * MMF_MAX_STATE_DIM), ("min_bandwidth", ctypes.c_float * MMF_MAX_STATE_DIM),
                 ("states", _FP), ("log_a", _FP), ("log_b", _FP), ("truth", _FP), ("log_density", _FP), ("log_score", _FP),
                 ("entropy", _FP), ("mode", _FP), ("mode_index", _FP), ("bandwidth_out", _FP),
+                ("workspace", _FP), ("workspace_bytes", c_size_t)]
+
+
+MODES_MAX = 8               # MMF_PF_MODES_MAX
+MODES_LDS_MASS_M = 8192     # MMF_PF_MODES_LDS_MASS_M: beyond it the finish of mmf_pf_modes keeps the masses in the workspace
+
+
+class MmfPfModesArgs(Structure):
+    _fields_ = [("R", c_int32), ("M", c_int32), ("d", c_int32), ("max_modes", c_int32), ("link_radius", c_float),
+                ("states", _FP), ("log_a", _FP), ("log_b", _FP), ("log_density", _FP), ("bandwidth", _FP),
+                ("parent", _FP), ("labels", _FP), ("count", _FP), ("index", _FP), ("modes", _FP), ("mass", _FP), ("mean", _FP),
                 ("workspace", _FP), ("workspace_bytes", c_size_t)]
 
 
@@ -269,6 +280,8 @@ SIGNATURES = {
     "mmf_pf_scores_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "mmf_pf_density": (c_int, [POINTER(MmfPfDensityArgs), c_void_p]),
     "mmf_pf_density_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "mmf_pf_modes": (c_int, [POINTER(MmfPfModesArgs), c_void_p]),
+    "mmf_pf_modes_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "mmf_pf_dedup_plan": (c_int, [c_int, c_int, c_int, ctypes.c_float, c_int]),
     "mmf_pf_dedup_workspace_words": (c_size_t, [c_int, c_int]),
     "mmf_pf_resample_runs": (c_int, [_FP] * 11 + [c_int, c_int, c_int, _FP, _FP, _FP, c_void_p]),
@@ -1232,3 +1245,38 @@ def pf_density(states, log_a, log_b, truth, *, rule="silverman", bandwidth=None,
     with _on(states):
         work = _summary_workspace(a, pf_density_workspace_bytes(R, M, d), states)
         _check(load().mmf_pf_density(ctypes.byref(a), stream_of(states)), "mmf_pf_density")
+
+
+def pf_modes_workspace_bytes(R: int, M: int, d: int) -> int:
+    return int(load().mmf_pf_modes_workspace_bytes(int(R), int(M), int(d)))
+
+
+def pf_modes(states, log_a, log_b, log_density, bandwidth, *, link_radius=3.0, max_modes=4, parent=None, labels=None, count=None,
+             index=None, modes=None, mass=None, mean=None):
+    """Quick-shift modes of weighted particle sets (``mmf_pf_modes``, include/mmf.h): ``states (..., M, d)`` -- ``R`` rows, the
+    product of the leading sizes -- with log-weights ``log_a + log_b``, each ``(..., M)`` or ``None`` (0; both ``None``:
+    uniform), ``log_density (..., M)`` and ``bandwidth (..., d)`` as ``mmf_pf_density`` writes them, ``link_radius`` (finite,
+    positive, in bandwidths) and ``max_modes = K`` (1 .. 8) -> ``parent``, ``labels (..., M)`` int32, ``count (...)`` int32,
+    ``index (..., K)`` int32, ``modes (..., K, d)``, ``mass (..., K)``, ``mean (..., K, d)``, each of which may be ``None`` (not
+    all seven).  The workspace is allocated here, on the tensors' device."""
+    lead, R, M, d = _summary_rows(states, log_a, log_b)
+    K = int(max_modes)
+    if not 1 <= K <= MODES_MAX:
+        raise MmfError(f"mmf_pf_modes reports 1 .. {MODES_MAX} modes, got max_modes = {max_modes!r}")
+    assert tuple(log_density.shape) == lead + (M,) and tuple(bandwidth.shape) == lead + (d,)
+    assert parent is None or tuple(parent.shape) == lead + (M,)
+    assert labels is None or tuple(labels.shape) == lead + (M,)
+    assert count is None or tuple(count.shape) == lead
+    assert index is None or tuple(index.shape) == lead + (K,)
+    assert modes is None or tuple(modes.shape) == lead + (K, d)
+    assert mass is None or tuple(mass.shape) == lead + (K,)
+    assert mean is None or tuple(mean.shape) == lead + (K, d)
+    a = MmfPfModesArgs()
+    a.R, a.M, a.d, a.max_modes, a.link_radius = R, M, d, K, float(link_radius)
+    a.states, a.log_a, a.log_b = vp(states), vp(log_a), vp(log_b)
+    a.log_density, a.bandwidth = vp(log_density), vp(bandwidth)
+    a.parent, a.labels, a.count = vp(parent, torch.int32), vp(labels, torch.int32), vp(count, torch.int32)
+    a.index, a.modes, a.mass, a.mean = vp(index, torch.int32), vp(modes), vp(mass), vp(mean)
+    with _on(states):
+        work = _summary_workspace(a, pf_modes_workspace_bytes(R, M, d), states)
+        _check(load().mmf_pf_modes(ctypes.byref(a), stream_of(states)), "mmf_pf_modes")

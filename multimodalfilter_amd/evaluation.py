@@ -2,6 +2,7 @@
 device-resident ``(T, N, ...)`` batches, plus the multi-GPU reduction of its error statistic.
 """
 import math
+import numbers
 from typing import Dict
 
 import numpy as np
@@ -23,10 +24,18 @@ _DEFAULT_METHOD = _DefaultMethod("ancestry")
 _DEFAULT_BANDWIDTH = _DefaultMethod("silverman")  # likewise the default of ``run_filter(density_bandwidth=)``
 
 
+class _DefaultRadius(float):
+    """The default of ``run_filter(modes_link_radius=)``, told apart by identity from a ``3.0`` the caller passed."""
+
+
+_DEFAULT_RADIUS = _DefaultRadius(3.0)
+
+
 def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale: float = 0.1,
                measurement_initialize: bool = False, return_belief: bool = False, smooth_lag=False,
                smooth_method: str = _DEFAULT_METHOD, smooth_draws: int = _DEFAULT_DRAWS, smooth_transition_moments: bool = False,
                return_innovations: bool = False, return_density: bool = False, density_bandwidth=_DEFAULT_BANDWIDTH,
+               return_modes=None, modes_link_radius: float = _DEFAULT_RADIUS,
                return_quantiles=None, return_scores: bool = False, score_scale=None):
     """Initialise the belief at ``states[0]`` with covariance ``0.1 I`` (or from the first
     observation, ``eval_helpers.py:116-131``) and filter ``[1:]`` (``:139-142``).
@@ -79,7 +88,16 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
     filter with neither (the LSTM baselines) is refused before the run: a point estimate has no density.
     ``density_bandwidth``: ``"silverman"`` (the default), ``"scott"`` or ``d`` positive finite floats, the
     ``bandwidth`` of ``belief_density``; without ``return_density`` it is refused.  Left at ``False``, every return value and
-    every bit is as without it."""
+    every bit is as without it.
+    ``return_modes``: an integer ``K`` (1 .. 8) appends a modes record -- how many hypotheses the belief holds per step, where
+    they are and what each weighs (``mode_errors``, ``mode_summary``) -- after the density record and before the quantiles
+    record, which stays last.  A particle filter runs with ``record_history`` set (and puts the switch back) and calls
+    ``belief_modes(of=..., max_modes=K, link_radius=modes_link_radius)``: ``last_modes``, ``of`` chosen and the smoothing
+    methods refused as for ``return_density``.  A filter with a belief covariance (the Kalman filters) gets the one mode a
+    Gaussian has: ``modes (T, N, K, d)`` and ``mean`` with the returned means at rank 0 and NaN beyond, ``mass`` 1 and 0,
+    ``count`` 1.  A filter with neither (the LSTM baselines) is refused before the run.  ``modes_link_radius``: the
+    ``link_radius`` of ``belief_modes`` (default 3.0 bandwidths); without ``return_modes`` it is refused.  Left at ``None``,
+    every return value and every bit is as without it."""
     if return_innovations and not hasattr(filter_model, "record_innovations"):  # (before the run, not after it)
         raise ValueError(f"run_filter: return_innovations needs a Kalman filter; {type(filter_model).__name__} has no "
                          "record_innovations (a particle filter reports log_evidence through return_belief)")
@@ -140,6 +158,24 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
                 raise ValueError("run_filter: density_bandwidth must be 'silverman', 'scott' or d positive finite floats")
         if density_kind == "particles":
             needs_weighted_sets("return_density")
+    want_modes = return_modes is not None
+    if modes_link_radius is not _DEFAULT_RADIUS and not want_modes:  # (before the run, not after it)
+        raise ValueError("run_filter: modes_link_radius is the link radius of return_modes' quick shift; without return_modes "
+                         "it has no use")
+    modes_kind = None
+    if want_modes:  # (before the run, not after it)
+        modes_kind = ("particles" if hasattr(filter_model, "belief_modes") else
+                      "gaussian" if hasattr(filter_model, "record_belief") else None)
+        if modes_kind is None:
+            raise ValueError(f"run_filter: return_modes needs a belief; {type(filter_model).__name__} returns a point "
+                             "estimate, which has no modes (no belief_modes, no record_belief)")
+        if isinstance(return_modes, bool) or not isinstance(return_modes, numbers.Integral) or not 1 <= return_modes <= 8:
+            raise ValueError(f"run_filter: return_modes must be None or the number of modes to report, 1 .. 8, got {return_modes!r}")
+        if (isinstance(modes_link_radius, bool) or not isinstance(modes_link_radius, numbers.Real)
+                or not 0.0 < float(modes_link_radius) < math.inf):
+            raise ValueError(f"run_filter: modes_link_radius must be a positive finite float, got {modes_link_radius!r}")
+        if modes_kind == "particles":
+            needs_weighted_sets("return_modes")
     want_quantiles = return_quantiles is not None
     if want_quantiles:  # (before the run, not after it)
         if not hasattr(filter_model, "belief_quantiles"):
@@ -162,7 +198,7 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
     if named and smooth_method != "ancestry" and smooth_lag is False:
         smooth_lag = None
     smoothing = smooth_lag is not False  # (0 is a lag)
-    need_history = smoothing or want_quantiles or scores_kind == "particles" or density_kind == "particles"
+    need_history = smoothing or want_quantiles or "particles" in (scores_kind, density_kind, modes_kind)
     if need_history:
         assert hasattr(filter_model, "record_history"), f"{type(filter_model).__name__} keeps no history to smooth"
         was_history = filter_model.record_history
@@ -232,6 +268,20 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
                 density = base.belief_record(log_score=gaussian_log_density(est, cov, truth), entropy=gaussian_entropy(cov),
                                              mode=est, of=summary_of)
         out = (out if isinstance(out, tuple) else (out,)) + (density,)
+    if want_modes:
+        K = int(return_modes)
+        if modes_kind == "particles":
+            filter_model.belief_modes(summary_of, max_modes=K, link_radius=float(modes_link_radius))
+            modes = filter_model.last_modes
+        else:
+            with torch.no_grad():
+                at = torch.full(est.shape[:2] + (K, d), math.nan, dtype=est.dtype, device=est.device)
+                at[:, :, 0] = est
+                mass = torch.zeros(est.shape[:2] + (K,), dtype=est.dtype, device=est.device)
+                mass[:, :, 0] = 1.0
+                count = torch.ones(est.shape[:2], dtype=torch.int32, device=est.device)
+                modes = base.belief_record(modes=at, mean=at.clone(), mass=mass, count=count, of=summary_of, max_modes=K)
+        out = (out if isinstance(out, tuple) else (out,)) + (modes,)
     if want_quantiles:
         filter_model.belief_quantiles(return_quantiles, of=summary_of, truth=states[1:])
         out = (out if isinstance(out, tuple) else (out,)) + (filter_model.last_quantiles,)
@@ -465,6 +515,57 @@ def density_summary(record, start: int = START_TRUNCATION) -> Dict[str, float]:
     out = {"entropy": mean(record.entropy)}
     if getattr(record, "log_score", None) is not None:
         out["log_score"] = mean(record.log_score)
+    return out
+
+
+def mode_errors(record, true: torch.Tensor, scale=None) -> Dict[str, torch.Tensor]:
+    """Errors of a modes record (``ParticleFilter.last_modes``; ``run_filter(return_modes=K)``) against the true states
+    ``(T, N, d)``: ``top (T, N)``, the Euclidean error of the heaviest mode; ``best (T, N)``, the least error over the
+    reported modes -- the oracle error of the multi-hypothesis tracking literature: was the truth among the hypotheses? --
+    and ``best_rank (T, N)`` int64, which mode that was.  ``scale``: ``None`` or ``d`` positive finite floats dividing the
+    coordinates inside the norm.  A step that reports no mode gives NaN, NaN and ``-1``."""
+    modes = getattr(record, "modes", None)
+    if modes is None or modes.dim() != 4:
+        raise ValueError("mode_errors: the record has no modes (T, N, K, d); take it from belief_modes or run_filter(return_modes=K)")
+    T, N, K, d = modes.shape
+    if not isinstance(true, torch.Tensor) or tuple(true.shape) != (T, N, d):
+        raise ValueError(f"mode_errors: true must be a (T, N, d) = ({T}, {N}, {d}) tensor, got "
+                         f"{tuple(true.shape) if isinstance(true, torch.Tensor) else type(true).__name__}")
+    if scale is not None:
+        try:
+            scale = tuple(float(v) for v in scale)
+        except (TypeError, ValueError):
+            scale = ()
+        if len(scale) != d or not all(0.0 < v < math.inf for v in scale):
+            raise ValueError(f"mode_errors: scale must be None or d = {d} positive finite floats")
+    with torch.no_grad():
+        e = modes - true.to(device=modes.device, dtype=modes.dtype)[:, :, None, :]
+        if scale is not None:
+            e = e / torch.tensor(scale, dtype=e.dtype, device=e.device)
+        err = torch.linalg.vector_norm(e, dim=-1)                       # (T, N, K); NaN at a rank beyond the count
+        there = ~torch.isnan(err)
+        best, rank = torch.where(there, err, torch.full_like(err, math.inf)).min(dim=-1)
+        none = ~there.any(dim=-1)
+        nan = torch.full_like(best, math.nan)
+        return {"top": err[..., 0], "best": torch.where(none, nan, best), "best_rank": torch.where(none, torch.full_like(rank, -1), rank)}
+
+
+def mode_summary(record, true=None, start: int = START_TRUNCATION) -> Dict[str, float]:
+    """Means of a modes record over the steps after the burn-in, over time and trajectories: ``count``, the number of modes;
+    ``top_mass``, the mass of the heaviest; ``multimodal``, the share of steps with more than one mode.  With ``true (T, N,
+    d)`` also ``top_rmse`` and ``best_rmse``, the root mean squares of ``mode_errors``' ``top`` and ``best`` over the steps that
+    report a mode."""
+    if getattr(record, "count", None) is None or getattr(record, "mass", None) is None:
+        raise ValueError("mode_summary: the record has no count and mass; take it from belief_modes or run_filter(return_modes=K)")
+    count = record.count[start:].to(torch.float64).reshape(-1)
+    out = {"count": float(count.mean()), "top_mass": float(record.mass[start:, :, 0].to(torch.float64).mean()),
+           "multimodal": float((count > 1).to(torch.float64).mean())}
+    if true is not None:
+        errors = mode_errors(record, true)
+        for k in ("top", "best"):
+            x = errors[k][start:].to(torch.float64).reshape(-1)
+            ok = torch.isfinite(x)
+            out[k + "_rmse"] = float(torch.sqrt(torch.where(ok, x * x, torch.zeros_like(x)).sum() / ok.sum()))
     return out
 
 

@@ -89,6 +89,9 @@ class ParticleFilter(base.Filter):
     ``belief_density(truth=, of=, bandwidth=, min_bandwidth=)``: the kernel density of the recorded sets -- the mode per step
     (returned), the log density at every particle, the entropy and, with a truth, the logarithmic score -> ``last_density``
     (``mmf_pf_density``).
+    ``belief_modes(of=, max_modes=, link_radius=, bandwidth=, min_bandwidth=)``: the modes of the recorded sets by quick shift
+    on that density -- how many, where, and the mass of each (returned: ``modes (T, N, K, d)``) -> ``last_modes``
+    (``mmf_pf_modes``).
     Randomness comes from ``self.noise`` (``utils.NoiseSource``), never from global RNG state.
     """
 
@@ -129,6 +132,7 @@ class ParticleFilter(base.Filter):
         self.last_quantiles = None    # belief_quantiles(): per-dimension weighted quantiles (and the PIT) of the recorded sets
         self.last_scores = None       # belief_scores(): CRPS, energy score and sharpness of the recorded sets against the truth
         self.last_density = None      # belief_density(): mode, log density, entropy and log score of the recorded sets
+        self.last_modes = None        # belief_modes(): the modes of the recorded sets, their masses, means and members
         self.record_transition_moments = False  # smooth(method="marginal") adds the two-slice residual moments to last_smoothed
         self._step_history = None
         self.use_native_loop = True   # False: forward_loop keeps the step-by-step Python loop
@@ -861,6 +865,20 @@ class ParticleFilter(base.Filter):
             raise ValueError(f"{who}: {name} must be {or_what} or {d} positive finite floats, got {value!r}")
         return tuple(float(v) for v in vs)
 
+    @classmethod
+    def _density_bandwidths(cls, who: str, bandwidth, min_bandwidth, d: int):
+        """``(rule, fixed, floor)`` of the ``bandwidth`` / ``min_bandwidth`` arguments of ``who`` (``belief_density``,
+        ``belief_modes``): ``"silverman"`` or ``"scott"`` with the floor (a float or ``d`` floats), or ``d`` positive finite
+        floats used as they are (``rule == "fixed"``); everything else is the ``ValueError`` of ``who``."""
+        floats = lambda value, name, or_what: cls._positive_floats(who, value, name, or_what, d)
+        if isinstance(bandwidth, str) and bandwidth in ("silverman", "scott"):
+            rule, fixed = str(bandwidth), None
+        else:
+            rule, fixed = "fixed", floats(bandwidth, "bandwidth", "'silverman', 'scott'")
+        if not isinstance(min_bandwidth, bool) and isinstance(min_bandwidth, numbers.Real):
+            min_bandwidth = (min_bandwidth,) * d
+        return rule, fixed, floats(min_bandwidth, "min_bandwidth", "a positive finite float")
+
     def belief_scores(self, truth: torch.Tensor, *, of: str = "filtered", scale=None) -> torch.Tensor:
         """Strictly proper scores of the recorded particle sets against the true states (``mmf_pf_scores``,
         ``include/mmf.h``): the continuous ranked probability score per state dimension, ``crps (T, N, d)`` -- returned --
@@ -906,14 +924,7 @@ class ParticleFilter(base.Filter):
         ``log_score`` only."""
         states, log_a, log_b, y = self._summary_inputs("belief_density", of, truth, "mmf_pf_density serves at most {}", "None or a")
         T, N, M, d = states.shape
-        floats = lambda value, name, or_what: self._positive_floats("belief_density", value, name, or_what, d)
-        if isinstance(bandwidth, str) and bandwidth in ("silverman", "scott"):
-            rule, fixed = str(bandwidth), None
-        else:
-            rule, fixed = "fixed", floats(bandwidth, "bandwidth", "'silverman', 'scott'")
-        if not isinstance(min_bandwidth, bool) and isinstance(min_bandwidth, numbers.Real):
-            min_bandwidth = (min_bandwidth,) * d
-        floor = floats(min_bandwidth, "min_bandwidth", "a positive finite float")
+        rule, fixed, floor = self._density_bandwidths("belief_density", bandwidth, min_bandwidth, d)
         dev = states.device
         with torch.no_grad():
             log_density = torch.empty((T, N, M), dtype=torch.float32, device=dev)
@@ -928,6 +939,46 @@ class ParticleFilter(base.Filter):
         self.last_density = base.belief_record(mode=mode, mode_index=mode_index, log_density=log_density, entropy=entropy,
                                                bandwidth=h, of=of, rule=rule, **extra)
         return mode
+
+    def belief_modes(self, of: str = "filtered", *, max_modes: int = 4, link_radius: float = 3.0, bandwidth="silverman",
+                     min_bandwidth=1e-6) -> torch.Tensor:
+        """The modes of the recorded particle sets (``mmf_pf_modes``, ``include/mmf.h``): how many hypotheses the belief
+        holds per step, where each one is and how much probability it carries -- "the door is open with probability 0.7".
+        Quick shift on the kernel density of ``belief_density``: every particle links to its nearest neighbour of higher
+        density within ``link_radius`` bandwidths, the roots of that forest are the modes and a tree's weight is the mode's
+        mass; all ``M^2`` pairs of a set in HIP, deterministic, nothing iterated.  Returns ``modes (T, N, K, d)``, ``K =
+        max_modes`` (1 .. 8): per step the ``min(count, K)`` heaviest modes, heaviest first, each a particle of the set; ranks
+        beyond ``count`` are NaN.  Leaves ``last_modes``: ``modes``, ``index (T, N, K)`` int32 (``-1`` beyond ``count``),
+        ``mass (T, N, K)`` (0 beyond), ``mean (T, N, K, d)`` -- the weighted mean of each mode's members --, ``count (T, N)``
+        int32, ``labels`` and ``parent (T, N, M)`` int32 (every particle's mode and link, ``-1`` at a dead particle),
+        ``bandwidth (T, N, d)``, ``of``, ``rule``, ``link_radius``, ``max_modes``.
+        ``of``, ``bandwidth`` and ``min_bandwidth`` mean what they mean for ``belief_density``, whose log density and
+        bandwidths are computed here (``mmf_pf_density``) without touching ``last_density``.  Draws no noise and leaves every
+        other ``last_*`` record as it is.  A step without a live particle has ``count = 0``."""
+        states, log_a, log_b, _ = self._summary_inputs("belief_modes", of, None, "mmf_pf_modes serves at most {}")
+        T, N, M, d = states.shape
+        if isinstance(max_modes, bool) or not isinstance(max_modes, numbers.Integral) or not 1 <= max_modes <= _abi.MODES_MAX:
+            raise ValueError(f"belief_modes: max_modes must be an integer in 1 .. {_abi.MODES_MAX}, got {max_modes!r}")
+        if isinstance(link_radius, bool) or not isinstance(link_radius, numbers.Real) or not 0.0 < float(link_radius) < math.inf:
+            raise ValueError(f"belief_modes: link_radius must be a positive finite float (in bandwidths), got {link_radius!r}")
+        rule, fixed, floor = self._density_bandwidths("belief_modes", bandwidth, min_bandwidth, d)
+        K, tau = int(max_modes), float(link_radius)
+        dev = states.device
+        with torch.no_grad():
+            log_density = torch.empty((T, N, M), dtype=torch.float32, device=dev)
+            h = torch.empty((T, N, d), dtype=torch.float32, device=dev)
+            _abi.pf_density(states, log_a, log_b, None, rule=rule, bandwidth=fixed, min_bandwidth=floor, log_density=log_density,
+                            bandwidth_out=h)
+            ints = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+            parent, labels, count, index = ints(T, N, M), ints(T, N, M), ints(T, N), ints(T, N, K)
+            modes = torch.empty((T, N, K, d), dtype=torch.float32, device=dev)
+            mass = torch.empty((T, N, K), dtype=torch.float32, device=dev)
+            mean = torch.empty((T, N, K, d), dtype=torch.float32, device=dev)
+            _abi.pf_modes(states, log_a, log_b, log_density, h, link_radius=tau, max_modes=K, parent=parent, labels=labels,
+                          count=count, index=index, modes=modes, mass=mass, mean=mean)
+        self.last_modes = base.belief_record(modes=modes, index=index, mass=mass, mean=mean, count=count, labels=labels,
+                                             parent=parent, bandwidth=h, of=of, rule=rule, link_radius=tau, max_modes=K)
+        return modes
 
     def belief_quantiles(self, probs, *, of: str = "filtered", truth: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Per-dimension weighted quantiles of the recorded particle sets (``mmf_pf_quantiles``, ``include/mmf.h``): the

@@ -1,0 +1,344 @@
+"""Particle-posterior modes on the GPU: ``mmf_pf_modes`` (``csrc/pf_modes.hip``) on the three case families of
+``tests/_mode_cases.py`` under its comparison rules -- the links certified against the fp64 definition, the forest outputs
+against the definition evaluated on the kernel's own links --, its guard rows and bit-for-bit identities (two calls, a row
+alone, every single output), dead rows and NaN levels, and ``ParticleFilter.belief_modes`` /
+``evaluation.run_filter(return_modes=)`` end to end on small real filters.  Every figure is printed before it is asserted."""
+import numpy as np
+import pytest
+import torch
+
+import _mode_cases as mc
+import _score_cases as sk
+import _smooth_cases as sc
+import _summary_gpu as sg
+from _summary_gpu import N, _filter_run, _Guarded, _same_bits
+from _tol import REL_TOL
+
+pytestmark = pytest.mark.gpu
+
+OUTPUTS = mc.OUTPUTS
+
+
+def _run(case, want=OUTPUTS, rows=None):
+    """``_abi.pf_modes`` on a case (or on ``rows`` of it) with every output between guard rows; the outputs not in ``want`` are
+    handed over as null and their buffers must come back untouched -> ``dict`` of device tensors (``None`` for those)."""
+    from multimodalfilter_amd import _abi
+
+    dev = sc.dev()
+    pick = (lambda x: x) if rows is None else (lambda x: None if x is None else x[rows])
+    X, la, lb, ld, h = (sc.to_device(pick(case[k])) for k in ("states", "log_a", "log_b", "log_density", "bandwidth"))
+    R, M, d = X.shape
+    K = case["max_modes"]
+    i32 = torch.int32
+    bufs = {"parent": _Guarded(R, (M,), dev, i32), "labels": _Guarded(R, (M,), dev, i32), "count": _Guarded(R, (), dev, i32),
+            "index": _Guarded(R, (K,), dev, i32), "modes": _Guarded(R, (K, d), dev), "mass": _Guarded(R, (K,), dev),
+            "mean": _Guarded(R, (K, d), dev)}
+    _abi.pf_modes(X, la, lb, ld, h, link_radius=case["link_radius"], max_modes=K,
+                  **{k: (bufs[k].view if k in want else None) for k in OUTPUTS})
+    torch.cuda.synchronize()
+    for k, b in bufs.items():
+        assert b.guards_intact(), f"a guard row of {k} was written (M={M} d={d} R={R})"
+        if k not in want:
+            assert b.untouched(), f"{k} was not asked for and was written (M={M} d={d} R={R})"
+    return {k: (bufs[k].view.clone() if k in want else None) for k in OUTPUTS}
+
+
+def _hold(case, ref_parent, got, what, exact_index=False):
+    """The comparison rules of the case module on the outputs of one call; returns ``(certified links, forest error)``."""
+    host = {k: N(v) for k, v in got.items()}
+    certified, n = mc.check_parents(case, ref_parent, host["parent"], what)
+    worst = mc.check_forest(case, host, what, exact_index=exact_index)
+    print(f"{what}: {certified} certified links among {n} particles, mass and mean {worst:.3e} (bar {REL_TOL:.0e})")
+    assert worst <= REL_TOL, (what, worst)
+    return certified, worst
+
+
+def _same(a, b, what):
+    for k in OUTPUTS:
+        if a[k] is not None and b[k] is not None:
+            assert _same_bits(a[k], b[k]), (what, k)
+
+
+# ------------------------------------------------------------------------------------------ 1. the three families
+@pytest.mark.parametrize("M", sk.ALL_MS)
+def test_kernel_holds_the_definition_on_the_random_family(M):
+    cases = certified = 0
+    for case_id in mc.random_family():
+        if case_id[0] != M:
+            continue
+        case = mc.random_case(*case_id)
+        c, _ = _hold(case, mc.random_reference(*case_id)["parent"], _run(case), "M=%d d=%d R=%d %s %s" % case_id)
+        cases, certified = cases + 1, certified + c
+    print(f"M={M}: {certified} certified links over {cases} cases")
+    assert cases >= 6
+
+
+@pytest.mark.parametrize("M", mc.LATTICE_MS)
+def test_lattice_cases_are_reproduced_exactly_and_do_not_move_with_the_shift(M):
+    for case_id in mc.lattice_family():
+        if case_id[0] != M:
+            continue
+        case, ref = mc.lattice_case(*case_id), mc.lattice_reference(*case_id)
+        got = _run(case)
+        for k in mc.INT_OUTPUTS:
+            assert np.array_equal(N(got[k]), ref[k]), (case_id, k)
+        _hold(case, ref["parent"], got, "lattice M=%d d=%d R=%d" % case_id, exact_index=True)
+        moved = _run(mc.lattice_case(*case_id, shift=mc.LATTICE_SHIFT), want=("parent", "labels", "count", "index"))
+        for k in mc.INT_OUTPUTS:
+            assert torch.equal(moved[k], got[k]), (case_id, k, "moved with the shift")
+
+
+@pytest.mark.parametrize("M", mc.BY_MS)
+def test_cases_with_an_answer_known_by_construction(M):
+    """Chains of depth ``M - 1`` (every round of the pointer jumping), every particle a root, one duplicated point, three
+    separated clusters: at the sizes of the plan, around the finish's LDS / workspace threshold and at the particle limit."""
+    for kind in mc.CONSTRUCTIONS:
+        case, exp = mc.constructed_case(kind, M)
+        got = {k: N(v) for k, v in _run(case).items()}
+        what = f"{kind} M={M}"
+        if "parent" in exp:
+            assert np.array_equal(got["parent"][0], exp["parent"]), what
+        assert np.array_equal(got["labels"][0], exp["labels"]) and int(got["count"][0]) == exp["count"], what
+        n = len(exp["index"])
+        assert np.array_equal(got["index"][0, :n], exp["index"]) and (got["index"][0, n:] == -1).all(), (what, got["index"])
+        errs = sk.compare(got["mass"][0, :n], exp["mass"], what), sk.compare(got["mean"][0, :n], exp["mean"], what)
+        worst = mc.check_forest(case, got, what)
+        print(f"{what}: mass {errs[0]:.3e}, mean {errs[1]:.3e}, against the definition on its own links {worst:.3e}")
+        assert max(errs) <= REL_TOL and worst <= REL_TOL, (what, errs, worst)
+
+
+# ------------------------------------------------------------------------------------------ 2. bit-for-bit identities
+def _first(M, variant):
+    """The first three-row case of the random family with ``M`` particles and this variant."""
+    return mc.random_case(*[c for c in mc.random_family() if c[0] == M and c[2] == 3 and c[3] == variant][0])
+
+
+def _bit_cases(M):
+    if M <= 1025:
+        yield _first(M, "plain"), "plain"
+        yield _first(M, "dead_row"), "dead_row"
+    yield mc.lattice_case(M, 2, 3, max_modes=8), "lattice"
+
+
+BIT_MS = [1, 65, 257, 512, 513, 1025, mc.LDS_MASS_M + 1]
+
+
+@pytest.mark.parametrize("M", BIT_MS)
+def test_two_calls_and_a_row_alone_give_the_same_bits(M):
+    for case, name in _bit_cases(M):
+        got = _run(case)
+        _same(got, _run(case), (M, name, "again"))
+        R = len(case["states"])
+        for r in range(R):
+            one = _run(case, rows=slice(r, r + 1))
+            _same(one, {k: v[r:r + 1] for k, v in got.items()}, (M, name, r))
+
+
+@pytest.mark.parametrize("M", BIT_MS)
+def test_every_output_alone_writes_the_bits_of_the_full_call_and_nothing_else(M):
+    """(The untouched buffers are checked inside ``_run``.)"""
+    for case, name in _bit_cases(M):
+        full = _run(case)
+        for k in OUTPUTS:
+            _same(_run(case, (k,)), full, (M, name, k))
+        _same(_run(case, ("index", "mass", "mean")), full, (M, name, "the reported modes"))
+
+
+# ------------------------------------------------------------------------------------------ 3. dead rows and NaN levels
+@pytest.mark.parametrize("M", [2, 65, 513, 1025])
+def test_a_dead_row_and_a_nan_level_on_a_live_particle(M):
+    case = dict(_first(M, "dead_row"))
+    R, _, d = case["states"].shape
+    dead = R // 2
+    got = {k: N(v) for k, v in _run(case).items()}
+    assert got["count"][dead] == 0 and (got["parent"][dead] == -1).all() and (got["labels"][dead] == -1).all()
+    assert (got["index"][dead] == -1).all() and (got["mass"][dead] == 0).all()
+    assert np.isnan(got["modes"][dead]).all() and np.isnan(got["mean"][dead]).all()
+    # a NaN level takes a live particle out: the row is what it is with that particle dead
+    part = mc.takes_part(case)
+    r = 0 if dead != 0 else 1
+    ref = mc.reference(case)
+    victim = int(ref["index"][r, 0])                      # the heaviest mode's root, a live particle
+    ld = case["log_density"].copy()
+    ld[r, victim] = np.nan
+    holed = dict(case, log_density=ld)
+    got = _run(holed)
+    host = {k: N(v) for k, v in got.items()}
+    assert part[r, victim] and host["parent"][r, victim] == -1 and host["labels"][r, victim] == -1
+    assert not (host["parent"][r] == victim).any() and not (host["index"][r] == victim).any()
+    _hold(holed, mc.parents(holed), got, f"M={M} NaN level")
+    killed = dict(case, log_density=ld, log_b=case["log_b"].copy(), states=case["states"].copy())
+    killed["log_b"][r, victim] = -np.inf
+    killed["states"][r, victim] = np.nan
+    _same(_run(killed, ("parent", "labels", "count")), got, (M, "the particle dead instead"))  # (the masses move with max a)
+
+
+# ------------------------------------------------------------------------------------------ 4. through the filter
+def _abi_call(states, log_a, log_b, rec):
+    """The ABI call on a record's own tensors: ``dict`` of fresh outputs."""
+    from multimodalfilter_amd import _abi
+
+    T, N_, M, d = states.shape
+    K, dev = rec.max_modes, states.device
+    dens = torch.empty((T, N_, M), dtype=torch.float32, device=dev)
+    h = torch.empty((T, N_, d), dtype=torch.float32, device=dev)
+    _abi.pf_density(states, log_a, log_b, None, rule=rec.rule, min_bandwidth=(1e-6,) * d, log_density=dens, bandwidth_out=h)
+    i32 = lambda *s: torch.full(s, -5, dtype=torch.int32, device=dev)
+    f32 = lambda *s: torch.full(s, -5.0, dtype=torch.float32, device=dev)
+    out = dict(parent=i32(T, N_, M), labels=i32(T, N_, M), count=i32(T, N_), index=i32(T, N_, K), modes=f32(T, N_, K, d),
+               mass=f32(T, N_, K), mean=f32(T, N_, K, d))
+    _abi.pf_modes(states, log_a, log_b, dens, h, link_radius=rec.link_radius, max_modes=K, **out)
+    torch.cuda.synchronize()
+    return dict(out, bandwidth=h), dens
+
+
+def _hold_record(rec, states, log_a, log_b, of, what):
+    T, N_, M, d = states.shape
+    assert set(vars(rec)) == {"modes", "index", "mass", "mean", "count", "labels", "parent", "bandwidth", "of", "rule",
+                              "link_radius", "max_modes"}
+    assert rec.of == of and type(rec.rule) is str and type(rec.link_radius) is float and type(rec.max_modes) is int
+    K = rec.max_modes
+    assert rec.modes.shape == (T, N_, K, d) and rec.mean.shape == (T, N_, K, d) and rec.mass.shape == (T, N_, K)
+    assert rec.index.shape == (T, N_, K) and rec.count.shape == (T, N_) and rec.labels.shape == rec.parent.shape == (T, N_, M)
+    assert all(getattr(rec, k).dtype == torch.int32 for k in mc.INT_OUTPUTS) and rec.bandwidth.shape == (T, N_, d)
+    want, dens = _abi_call(states, log_a, log_b, rec)
+    for k, v in want.items():
+        assert _same_bits(getattr(rec, k), v), (what, k)
+    # and the record is right: the comparison rules on the record's own arrays
+    case = sg._case_of(states, log_a, log_b, None, log_density=N(dens).reshape(T * N_, M), bandwidth=N(rec.bandwidth).reshape(T * N_, d),
+                       link_radius=rec.link_radius, max_modes=K)
+    del case["truth"]
+    flat = {k: getattr(rec, k).reshape((T * N_,) + tuple(getattr(rec, k).shape[2:])) for k in OUTPUTS}
+    _hold(case, mc.parents(case), flat, what)
+    assert bool((rec.count >= 1).all()) and bool((rec.mass[..., 0] > 0).all())
+
+
+@pytest.mark.parametrize("M", [64, 300])
+def test_belief_modes_on_a_real_filter(M):
+    """``of="filtered"``, ``of="smoothed"`` after the marginal smoother and after backward simulation equal the ABI call on the
+    records' own tensors bit for bit and hold the definition.  Nothing else moves: the estimates, the history, the density,
+    score and quantile records and the noise stream are what they are without the calls."""
+    from multimodalfilter_amd.utils import ReplayNoise
+
+    f, forward, traj, shape = _filter_run("DoorCrossmodalParticleFilter", M, owner="modes")
+    T, N_, _, d = shape
+    est = forward().clone()
+    h = f.last_history
+    truth = traj["states"][1:]
+    before = {k: getattr(h, k).clone() for k in ("states", "log_likelihoods", "log_weights_in", "ancestors") if getattr(h, k) is not None}
+    f.belief_quantiles((0.5,), truth=truth)
+    f.belief_scores(truth)
+    f.belief_density(truth)
+    quantiles, scores, density = f.last_quantiles, f.last_scores, f.last_density
+    kept = quantiles.quantiles.clone(), scores.crps.clone(), density.log_density.clone()
+    f.last_modes = None
+    modes = f.belief_modes()
+    rec = f.last_modes
+    assert rec.modes is modes and rec.max_modes == 4 and rec.link_radius == 3.0 and rec.rule == "silverman"
+    _hold_record(rec, h.states, h.log_weights_in, h.log_likelihoods, "filtered", f"M={M} filtered")
+    assert _same_bits(rec.bandwidth, density.bandwidth)
+    picked = torch.gather(h.states, 2, rec.index.clamp_min(0).long()[..., None].expand(T, N_, 4, d))
+    assert torch.equal(torch.where(rec.index[..., None] >= 0, picked, torch.zeros_like(picked)), torch.nan_to_num(modes, nan=0.0))
+    f.belief_modes("filtered", max_modes=8, link_radius=1.0, bandwidth="scott")
+    assert f.last_modes.rule == "scott" and f.last_modes.max_modes == 8 and f.last_modes.link_radius == 1.0
+    _hold_record(f.last_modes, h.states, h.log_weights_in, h.log_likelihoods, "filtered", f"M={M} filtered, scott, radius 1")
+    assert f.last_quantiles is quantiles and torch.equal(quantiles.quantiles, kept[0])
+    assert f.last_scores is scores and torch.equal(scores.crps, kept[1])
+    assert f.last_density is density and _same_bits(density.log_density, kept[2])
+    after = f.noise.uniform((4, 5), like=h.states).clone()  # where the noise stream stands after the calls ...
+    assert torch.equal(forward(), est)
+    assert torch.equal(f.noise.uniform((4, 5), like=h.states), after)  # ... is where it stands without them
+    f.last_history = h
+    for k, x in before.items():
+        assert torch.equal(getattr(h, k), x), k
+
+    f.smooth(method="marginal")
+    s = f.last_smoothed
+    weights = s.weights.clone()
+    f.belief_modes("smoothed")
+    assert f.last_smoothed is s and torch.equal(s.weights, weights)
+    _hold_record(f.last_modes, h.states, torch.log(weights), None, "smoothed", f"M={M} marginal")
+
+    S = 16
+    f.noise = ReplayNoise(uniforms=[torch.rand((T, N_, S), generator=torch.Generator().manual_seed(5))])
+    f.smooth(method="simulation", num_draws=S)
+    s = f.last_smoothed
+    f.belief_modes("smoothed", max_modes=2)
+    _hold_record(f.last_modes, s.trajectories, None, None, "smoothed", f"M={M} simulation")
+    assert f.last_smoothed is s and f.last_history is h and f.last_quantiles is quantiles and f.last_scores is scores
+    assert f.last_density is density
+    for k, x in before.items():
+        assert torch.equal(getattr(h, k), x), k
+    for method in ("ancestry", "map"):
+        f.smooth(method=method)
+        kept_modes = f.last_modes
+        with pytest.raises(ValueError, match="of='smoothed'"):
+            f.belief_modes("smoothed")
+        assert f.last_modes is kept_modes
+
+
+# ------------------------------------------------------------------------------------------ 5. run_filter(return_modes=)
+def test_run_filter_places_the_modes_record_between_the_density_and_the_quantiles():
+    import multimodalfilter_amd as mmf
+    from multimodalfilter_amd import evaluation
+
+    dev = sc.dev()
+    N_, M, T = 3, 64, 6
+    f, d, traj, obs, ctrl, cov = sc.small_filter("DoorCrossmodalParticleFilter", N_, M, T, dev)
+    f.noise = mmf.CounterNoise(7)
+    plain = evaluation.run_filter(f, traj)
+    f.noise = mmf.CounterNoise(7)
+    off = evaluation.run_filter(f, traj, return_modes=None)
+    assert isinstance(off, torch.Tensor) and torch.equal(off, plain)
+    f.noise = mmf.CounterNoise(7)
+    others = evaluation.run_filter(f, traj, return_belief=True, return_scores=True, return_density=True, return_quantiles=(0.5,))
+    f.noise = mmf.CounterNoise(7)
+    est, rec = evaluation.run_filter(f, traj, return_modes=4)
+    assert f.record_history is False and f.record_belief is False  # put back
+    assert torch.equal(est, plain) and rec is f.last_modes and rec.of == "filtered" and rec.max_modes == 4 and rec.link_radius == 3.0
+    h = f.last_history
+    _hold_record(rec, h.states, h.log_weights_in, h.log_likelihoods, "filtered", "run_filter")
+    errors = evaluation.mode_errors(rec, traj["states"][1:])
+    assert errors["top"].shape == (T, N_) and bool((errors["best"] <= errors["top"]).all()) and bool((errors["best_rank"] >= 0).all())
+    summary = evaluation.mode_summary(rec, traj["states"][1:], start=0)
+    assert summary["count"] >= 1.0 and 0.0 < summary["top_mass"] <= 1.0 and summary["best_rmse"] <= summary["top_rmse"]
+    f.noise = mmf.CounterNoise(7)
+    out = evaluation.run_filter(f, traj, return_belief=True, return_scores=True, return_density=True, return_modes=2,
+                                modes_link_radius=2.0, return_quantiles=(0.5,))
+    assert len(out) == 6 and out[1] is f.last_belief and out[2] is f.last_scores and out[3] is f.last_density
+    assert out[4] is f.last_modes and out[4].max_modes == 2 and out[4].link_radius == 2.0 and out[5] is f.last_quantiles
+    assert torch.equal(out[0], others[0]) and torch.equal(out[1].covariance, others[1].covariance)
+    assert _same_bits(out[2].crps, others[2].crps) and _same_bits(out[3].log_density, others[3].log_density)
+    assert _same_bits(out[5].quantiles, others[4].quantiles)
+    f.noise = mmf.CounterNoise(7)
+    out = evaluation.run_filter(f, traj, smooth_method="marginal", return_modes=3, return_quantiles=(0.5,))
+    assert len(out) == 3 and out[1] is f.last_modes and out[1].of == "smoothed" and out[2].of == "smoothed"
+    f.noise = mmf.NoiseSource(7)  # (backward simulation draws (T, N, S) uniforms, which a CounterNoise does not)
+    out = evaluation.run_filter(f, traj, smooth_method="simulation", smooth_draws=8, return_belief=True, return_modes=3)
+    assert len(out) == 3 and out[1] is f.last_smoothed and out[2].of == "smoothed" and out[2].labels.shape == (T, N_, 8)
+
+
+def test_run_filter_gives_a_kalman_filter_its_one_mode():
+    import multimodalfilter_amd as mmf
+    from multimodalfilter_amd import evaluation, synthetic
+    from oracle import models as om
+
+    dev = sc.dev()
+    N_, T = 3, 6
+    d = om.TASKS["door"].state_dim
+    torch.manual_seed(3)
+    f = mmf.door_models.DoorKalmanFilter().to(dev).eval()
+    traj = {k: v.to(dev) for k, v in synthetic.make_trajectories(state_dim=d, T=T, N=N_, seed=17).items()}
+    plain = evaluation.run_filter(f, traj)
+    est, rec = evaluation.run_filter(f, traj, return_modes=4)
+    assert f.record_belief is False and torch.equal(est, plain)
+    assert set(vars(rec)) == {"modes", "mean", "mass", "count", "of", "max_modes"} and rec.of == "filtered"
+    assert torch.equal(rec.modes[:, :, 0], plain) and bool(torch.isnan(rec.modes[:, :, 1:]).all()) and rec.modes.shape == (T, N_, 4, d)
+    assert bool((rec.count == 1).all()) and bool((rec.mass[:, :, 0] == 1).all()) and bool((rec.mass[:, :, 1:] == 0).all())
+    errors = evaluation.mode_errors(rec, traj["states"][1:])
+    assert torch.equal(errors["top"], torch.linalg.vector_norm(plain - traj["states"][1:], dim=-1))
+    out = evaluation.run_filter(f, traj, return_belief=True, return_innovations=True, return_density=True, return_modes=1)
+    assert len(out) == 5 and torch.equal(out[0], plain) and out[2] is f.last_innovations and out[4].modes.shape == (T, N_, 1, d)
+    lstm = mmf.door_models.DoorLSTMFilter().to(dev).eval()
+    with pytest.raises(ValueError, match="return_modes"):
+        evaluation.run_filter(lstm, traj, return_modes=4)
