@@ -1153,6 +1153,72 @@ typedef struct MmfPfModesArgs {
 int mmf_pf_modes(const MmfPfModesArgs* args /* host */, void* stream);
 size_t mmf_pf_modes_workspace_bytes(int R, int M, int d);
 
+/* ---------------------------------------------------------------- Per-modality attribution of the crossmodal fusion
+ * The crossmodal particle filter fuses its modalities as logsumexp_k(beta_k + l_k) (crossmodal/base_models/crossmodal_pf.py:106-139),
+ * here in the epilogue of mmf_pf_measure, so the unimodal log-likelihoods never leave the chip; every summary above describes
+ * the fused belief and none says which sensor it came from.  The reference looks at that by hand (likelihood maps with and
+ * without the image, scripts/door_task/vis_pf_likelihoods.ipynb), and crossmodal_pf.py:123-129 computes per-modality normalised
+ * likelihoods it never uses -- a modality whose likelihoods are larger in scale wins whatever beta says, so beta alone is not
+ * the answer; the evidence-weighted share is.  Purely additive to ABI 42: a struct and a symbol of their own.
+ * Per row r (R rows, e.g. T * N, of M particles x_m = states[r, m, :]) with the incoming log-weights a_m = log_w[r, m] (null:
+ * 0, uniform), the K log-likelihood columns l_km = loglik[k][r, m] of the enabled modalities (mmf_pf_measure_multi evaluates
+ * them on the same particles in one launch) and the modality log-weights beta_k = modality_logw[r * logw_stride + k] (null: 0,
+ * as without a weight model):
+ *   s_km = beta_k + l_km        L_m = logsumexp_k s_km           A = logsumexp_m a_m
+ *   u_km = a_m + l_km           v_m = a_m + L_m
+ *   W^k_m = exp(u_km - logsumexp_m u_k)      modality k's own posterior on the shared particles
+ *   W_m   = exp(v_m  - logsumexp_m v)        the fused posterior: the filter's pre-resampling weights
+ *   log_evidence[k]   = logsumexp_m u_km - A, k < K;   log_evidence[K] = logsumexp_m v_m - A (fused)
+ *   responsibility[k] = rho_k = exp(beta_k + log_evidence[k] - log_evidence[K]) = sum_m W_m exp(s_km - L_m); they sum to 1
+ *   ess[k]            = 1 / sum_m (W^k_m)^2;   ess[K] of W
+ *   mean[k, :]        = sum_m W^k_m x_m;       mean[K, :] of W
+ *   divergence[k]     = KL(W^k || W) = sum_{m: W^k_m > 0} W^k_m (log W^k_m - log W_m)
+ *   overlap[j, k]     = sum_m sqrt(W^j_m W^k_m), the Bhattacharyya coefficient; stored symmetric bit for bit, 1 on the diagonal
+ * Hence W = sum_k rho_k W^k and mean[K] = sum_k rho_k mean[k]; 0 <= divergence[k] <= -log rho_k; K = 1 gives rho = 1 and
+ * divergence 0; identical columns give rho = softmax(beta), divergence 0 and overlap 1; modalities with disjoint support
+ * give overlap 0 exactly and divergence[k] = -log rho_k.
+ * Weights are those of "Particle-posterior scores", one pair of fp32 operations per log-weight: u = a + l, t = u - max_m u
+ * (the maximum skips NaN), w = expf(t) where t <= 0, else 0 -- a NaN or -inf carries no weight; likewise inside L_m, formed in
+ * fp32 as max_k s + logf(sum_k w(s_k - max_k s)): a NaN l_km counts as -inf.  A particle with a_m = -inf or NaN is dead under
+ * every distribution and its state row (NaN by convention) is never read into a sum.  Normalised in double, once, at the end.
+ *   - a modality with no weight on any live particle: log_evidence = -inf, responsibility = 0, and NaN in its ess, mean,
+ *     divergence and its row and column of overlap;
+ *   - a modality with beta_k = -inf (a weight model that knows of a blackout): responsibility = 0; its evidence, ess, mean
+ *     and overlaps are those of its own posterior, and its divergence is +inf where it alone weighs a particle;
+ *   - no modality with weight under a finite beta_k: the fused log_evidence = -inf, its ess and mean and every divergence NaN;
+ *   - a row without a live particle (A is -inf or NaN): NaN everywhere.
+ * Determinism: every sum is taken in a fixed order and there are no floating-point atomics -- two calls give the same bits,
+ * a row's result depends on neither R nor the other rows (the plan is a function of M alone), and whichever outputs are
+ * null, the others are the bits of the full call; an output that is null is not touched.
+ * Kernel plan: a reduction.  One workgroup per row, a thread to every four particles, rounded up to a wave of 64, 512 threads
+ * at most.  Pass 1 takes the K + 2 row maxima (of u_k, v and a) from the log columns; pass 2 reads the log columns again
+ * (from L2: the same workgroup has just read them, at most 320 KiB) and the state rows, and keeps (K + 1)(2 + d) + K +
+ * K (K - 1) / 2 + 1 sums per thread -- sum w, sum w^2, sum w x per distribution; sum w^k (t^k - t) per modality; sum
+ * sqrtf(w^j w^k) per pair; sum exp(a - max a).  A thread loads four of its particles before it uses one; its sums are fp32
+ * over those four, flushed to double; the 64 lanes of a wave are added as one more fp32 run (DPP, a fixed tree), the waves
+ * ascending in double.  The finish is spread over 3 K + 1 threads; its logarithms of the totals are fp32 (an absolute 1e-7 in
+ * numbers written as floats), its quotients double.  4 (1 + K + d) bytes per particle from memory, once; no workspace and no
+ * finishing launch.
+ * Limits, all decided on the host before any HIP call: null args / states / loglik[k < K], K outside 1 .. MMF_LOOP_MAX_MEAS,
+ * d outside 1 .. 4, M < 1, R < 0, a modality_logw with logw_stride < K, all six outputs null, an output overlapping an input
+ * or another output -> MMF_EINVAL; M > 16384 or R beyond a 32-bit grid -> MMF_ETOOLARGE; R == 0 is a successful no-op. */
+typedef struct MmfPfModalitiesArgs {
+  int32_t R, M, d;                  /* R rows (e.g. T*N) of M particles */
+  int32_t K;                        /* enabled modalities, 1 .. MMF_LOOP_MAX_MEAS */
+  int32_t logw_stride;              /* floats from one row of modality_logw to the next, >= K; not read when that is null */
+  const float* states;              /* (R, M, d) */
+  const float* log_w;               /* (R, M) or null = uniform (history: log_weights_in) */
+  const float* loglik[MMF_LOOP_MAX_MEAS];  /* (R, M) each, the first K: the unimodal log-likelihoods, no beta added */
+  const float* modality_logw;       /* (R, logw_stride), the first K of a row; or null = 0 */
+  float* log_evidence;              /* (R, K + 1) or null */
+  float* responsibility;            /* (R, K) or null */
+  float* ess;                       /* (R, K + 1) or null */
+  float* mean;                      /* (R, K + 1, d) or null */
+  float* divergence;                /* (R, K) or null */
+  float* overlap;                   /* (R, K, K) or null */
+} MmfPfModalitiesArgs;              /* host struct holding device pointers */
+int mmf_pf_modalities(const MmfPfModalitiesArgs* args /* host */, void* stream);
+
 /* ---------------------------------------------------------------- K6, fused: one network call of the training backward
  * Recompute (the forward pass's f16x3 arithmetic), backward data path and weight / bias gradients of ONE per-particle
  * network over N * M rows in one kernel (the dynamics network: three launches -- encoder forward, trunk, encoder

@@ -173,6 +173,12 @@ class MmfPfModesArgs(Structure):
                 ("workspace", _FP), ("workspace_bytes", c_size_t)]
 
 
+class MmfPfModalitiesArgs(Structure):
+    _fields_ = [("R", c_int32), ("M", c_int32), ("d", c_int32), ("K", c_int32), ("logw_stride", c_int32),
+                ("states", _FP), ("log_w", _FP), ("loglik", _FP * LOOP_MAX_MEAS), ("modality_logw", _FP),
+                ("log_evidence", _FP), ("responsibility", _FP), ("ess", _FP), ("mean", _FP), ("divergence", _FP), ("overlap", _FP)]
+
+
 class MmfTrainNet(Structure):
     _fields_ = [("packed", _FP), ("packed_f32", _FP), ("packed_t", _FP), ("head_w", _FP), ("pw", _FP), ("pb", _FP),
                 ("p_first", _FP), ("p_head", _FP), ("p_dout", _FP), ("p_traj", _FP), ("packed_dual", _FP)]
@@ -282,6 +288,7 @@ SIGNATURES = {
     "mmf_pf_density_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "mmf_pf_modes": (c_int, [POINTER(MmfPfModesArgs), c_void_p]),
     "mmf_pf_modes_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "mmf_pf_modalities": (c_int, [POINTER(MmfPfModalitiesArgs), c_void_p]),
     "mmf_pf_dedup_plan": (c_int, [c_int, c_int, c_int, ctypes.c_float, c_int]),
     "mmf_pf_dedup_workspace_words": (c_size_t, [c_int, c_int]),
     "mmf_pf_resample_runs": (c_int, [_FP] * 11 + [c_int, c_int, c_int, _FP, _FP, _FP, c_void_p]),
@@ -1280,3 +1287,36 @@ def pf_modes(states, log_a, log_b, log_density, bandwidth, *, link_radius=3.0, m
     with _on(states):
         work = _summary_workspace(a, pf_modes_workspace_bytes(R, M, d), states)
         _check(load().mmf_pf_modes(ctypes.byref(a), stream_of(states)), "mmf_pf_modes")
+
+
+def pf_modalities(states, log_w, logliks, modality_logw, *, log_evidence=None, responsibility=None, ess=None, mean=None,
+                  divergence=None, overlap=None):
+    """Per-modality attribution of the crossmodal fusion (``mmf_pf_modalities``, include/mmf.h): ``states (..., M, d)`` -- ``R``
+    rows, the product of the leading sizes -- with the incoming log-weights ``log_w (..., M)`` or ``None`` (uniform), ``logliks``,
+    the ``K`` (1 .. 4) unimodal log-likelihoods ``(..., M)`` of the enabled modalities, and ``modality_logw (..., K)`` or
+    ``None`` (0) -> ``log_evidence (..., K + 1)``, ``responsibility (..., K)``, ``ess (..., K + 1)``, ``mean (..., K + 1, d)``,
+    ``divergence (..., K)``, ``overlap (..., K, K)``, each of which may be ``None`` (not all six); the entries ``K`` are the
+    fused posterior's."""
+    lead, R, M, d = _summary_rows(states, log_w, None)
+    logliks = list(logliks)
+    K = len(logliks)
+    if not 1 <= K <= LOOP_MAX_MEAS:
+        raise MmfError(f"mmf_pf_modalities takes 1 .. {LOOP_MAX_MEAS} modalities, got {K}")
+    for l in logliks:
+        assert tuple(l.shape) == lead + (M,)
+    assert modality_logw is None or tuple(modality_logw.shape) == lead + (K,)
+    assert log_evidence is None or tuple(log_evidence.shape) == lead + (K + 1,)
+    assert responsibility is None or tuple(responsibility.shape) == lead + (K,)
+    assert ess is None or tuple(ess.shape) == lead + (K + 1,)
+    assert mean is None or tuple(mean.shape) == lead + (K + 1, d)
+    assert divergence is None or tuple(divergence.shape) == lead + (K,)
+    assert overlap is None or tuple(overlap.shape) == lead + (K, K)
+    a = MmfPfModalitiesArgs()
+    a.R, a.M, a.d, a.K, a.logw_stride = R, M, d, K, K
+    a.states, a.log_w, a.modality_logw = vp(states), vp(log_w), vp(modality_logw)
+    for k, l in enumerate(logliks):
+        a.loglik[k] = ptr(l)
+    a.log_evidence, a.responsibility, a.ess = vp(log_evidence), vp(responsibility), vp(ess)
+    a.mean, a.divergence, a.overlap = vp(mean), vp(divergence), vp(overlap)
+    with _on(states):
+        _check(load().mmf_pf_modalities(ctypes.byref(a), stream_of(states)), "mmf_pf_modalities")

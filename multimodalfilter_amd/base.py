@@ -39,7 +39,9 @@ def history_record(**fields) -> SimpleNamespace:
     resampling), ``log_likelihoods (T, N, M)``, ``log_weights_in (T, N, M)`` the log-weights every step started from,
     ``ancestors (T, N, M)`` int32 (``None``: no step resampled -- the identity), ``resampled`` (the filter's
     ``last_resampled``) and ``controls``, a reference to (not a copy of) the controls the loop was given, which
-    ``smooth(method="marginal")`` evaluates the dynamics means with.  Where a step changed the particle count, ``M`` is the largest count and the shorter steps are
+    ``smooth(method="marginal")`` evaluates the dynamics means with; under a crossmodal measurement model also ``observations``,
+    a reference to the observations the loop was given, and ``enabled_models``, a tuple: what ``belief_modalities()`` evaluates
+    the unimodal log-likelihoods again with.  Where a step changed the particle count, ``M`` is the largest count and the shorter steps are
     padded with dead particles (log-likelihood ``-inf``).  ``include/mmf.h`` ("particle smoothing") has the definitions.
     An extended Kalman filter with ``record_history`` set leaves another record under the same name: ``means (T, N, d)`` and
     ``covariances (T, N, d, d)``, the filtered belief as every step left it, and ``controls`` as above -- what its RTS

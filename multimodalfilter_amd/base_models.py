@@ -144,6 +144,37 @@ class CrossmodalParticleFilterMeasurementModel(base.ParticleFilterMeasurementMod
         assert not first, "no measurement model enabled"
         return loglik
 
+    @engine.checked_loop
+    def modality_log_likelihoods(self, states: torch.Tensor, ctx):
+        """The unimodal log-likelihoods that ``forward_encoded`` fuses on the chip, kept apart: ``states (R, M, d)`` and the
+        ``ctx`` of ``encode_observations`` over the same ``R`` rows -> ``(logliks, beta, enabled)``: a list of ``(R, M)``
+        tensors ``l_k``, one per enabled model and with no modality log-weight added, the enabled columns of the weight model's
+        ``beta`` as a contiguous ``(R, K_enabled)`` tensor (``None`` without a weight model) and the enabled models' indices.
+        Every network on the same particles in one launch (``mmf_pf_measure_multi``); the range flag of that launch is
+        checked on the way out, as the loops check theirs.  What ``ParticleFilter.belief_modalities`` attributes the fusion
+        with; a model whose unimodal models are not fused networks is refused."""
+        plan = self.fused_measurements(ctx)
+        if plan is None:
+            raise ValueError("modality_log_likelihoods: the unimodal measurement models are not fused networks (no "
+                             "fused_measurements): their log-likelihoods are evaluated by mmf_pf_measure_multi or not at all")
+        nets, _ = plan
+        enabled = tuple(i for i, on in enumerate(self._enabled_models) if on)
+        if not nets:
+            raise ValueError("modality_log_likelihoods: no measurement model enabled")
+        engine.require_device(states, "modality_log_likelihoods")
+        R, M, d = states.shape
+        with torch.no_grad():
+            states = states.contiguous()
+            net0 = nets[0][0]
+            assert all(n.n_res == net0.n_res and n.precision_code() == net0.precision_code() for n, _, _ in nets)
+            logliks = [torch.empty((R, M), dtype=torch.float32, device=states.device) for _ in nets]
+            _abi.pf_measure_multi([n.blob() for n, _, _ in nets], net0.n_res, net0.precision_code(), states,
+                                  [bias for _, bias, _ in nets], [None] * len(nets), 0, logliks, engine.range_flag(states.device))
+            beta = ctx.get("modality_log_weights")
+            if beta is not None:
+                beta = beta[:, list(enabled)].contiguous()
+        return logliks, beta, enabled
+
     def encode_observations_autograd(self, observations):
         """Training counterpart of ``encode_observations`` (differentiable torch ops on ``R`` rows):
         each enabled unimodal model's hoisted bias and the modality log-weights; ``None`` when a

@@ -35,7 +35,7 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
                measurement_initialize: bool = False, return_belief: bool = False, smooth_lag=False,
                smooth_method: str = _DEFAULT_METHOD, smooth_draws: int = _DEFAULT_DRAWS, smooth_transition_moments: bool = False,
                return_innovations: bool = False, return_density: bool = False, density_bandwidth=_DEFAULT_BANDWIDTH,
-               return_modes=None, modes_link_radius: float = _DEFAULT_RADIUS,
+               return_modes=None, modes_link_radius: float = _DEFAULT_RADIUS, return_modalities: bool = False,
                return_quantiles=None, return_scores: bool = False, score_scale=None):
     """Initialise the belief at ``states[0]`` with covariance ``0.1 I`` (or from the first
     observation, ``eval_helpers.py:116-131``) and filter ``[1:]`` (``:139-142``).
@@ -97,7 +97,15 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
     Gaussian has: ``modes (T, N, K, d)`` and ``mean`` with the returned means at rank 0 and NaN beyond, ``mass`` 1 and 0,
     ``count`` 1.  A filter with neither (the LSTM baselines) is refused before the run.  ``modes_link_radius``: the
     ``link_radius`` of ``belief_modes`` (default 3.0 bandwidths); without ``return_modes`` it is refused.  Left at ``None``,
-    every return value and every bit is as without it."""
+    every return value and every bit is as without it.
+    ``return_modalities``: appends a modalities record -- which sensor decided each step: every modality's share of the fused
+    posterior, its own evidence, mean, divergence and overlap (``modality_summary``, ``modality_errors``) -- after the modes
+    record and before the quantiles record, which stays last.  A crossmodal particle filter runs with ``record_history`` set
+    (and puts the switch back) and calls ``belief_modalities()``: ``last_modalities``, always of the filtered sets, whatever
+    the call smooths with -- a smoothed weight is not a prior times a likelihood.  Every other filter is refused before the
+    run: a particle filter with one measurement model fuses nothing, an LSTM baseline has no belief, and the Kalman filters
+    fuse their sub-filters per state dimension, whose attribution is a separate change.  Left at ``False``, every return
+    value and every bit is as without it."""
     if return_innovations and not hasattr(filter_model, "record_innovations"):  # (before the run, not after it)
         raise ValueError(f"run_filter: return_innovations needs a Kalman filter; {type(filter_model).__name__} has no "
                          "record_innovations (a particle filter reports log_evidence through return_belief)")
@@ -176,6 +184,19 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
             raise ValueError(f"run_filter: modes_link_radius must be a positive finite float, got {modes_link_radius!r}")
         if modes_kind == "particles":
             needs_weighted_sets("return_modes")
+    want_modalities = bool(return_modalities)
+    if want_modalities:  # (before the run, not after it)
+        from . import base_models, filters
+        from .base_models import CrossmodalParticleFilterMeasurementModel
+
+        if not (hasattr(filter_model, "belief_modalities")
+                and isinstance(getattr(filter_model, "measurement_model", None), CrossmodalParticleFilterMeasurementModel)):
+            what = ("the Kalman filters fuse their sub-filters per state dimension, and the attribution of that fusion is a "
+                    "separate change"
+                    if isinstance(filter_model, (base_models._FusedKalmanFilters, filters.VirtualSensorExtendedKalmanFilter))
+                    else "it fuses no modalities")
+            raise ValueError(f"run_filter: return_modalities needs a crossmodal particle filter (belief_modalities over a "
+                             f"CrossmodalParticleFilterMeasurementModel); {type(filter_model).__name__} is none: {what}")
     want_quantiles = return_quantiles is not None
     if want_quantiles:  # (before the run, not after it)
         if not hasattr(filter_model, "belief_quantiles"):
@@ -198,7 +219,7 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
     if named and smooth_method != "ancestry" and smooth_lag is False:
         smooth_lag = None
     smoothing = smooth_lag is not False  # (0 is a lag)
-    need_history = smoothing or want_quantiles or "particles" in (scores_kind, density_kind, modes_kind)
+    need_history = smoothing or want_quantiles or want_modalities or "particles" in (scores_kind, density_kind, modes_kind)
     if need_history:
         assert hasattr(filter_model, "record_history"), f"{type(filter_model).__name__} keeps no history to smooth"
         was_history = filter_model.record_history
@@ -282,6 +303,9 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
                 count = torch.ones(est.shape[:2], dtype=torch.int32, device=est.device)
                 modes = base.belief_record(modes=at, mean=at.clone(), mass=mass, count=count, of=summary_of, max_modes=K)
         out = (out if isinstance(out, tuple) else (out,)) + (modes,)
+    if want_modalities:
+        filter_model.belief_modalities()
+        out = (out if isinstance(out, tuple) else (out,)) + (filter_model.last_modalities,)
     if want_quantiles:
         filter_model.belief_quantiles(return_quantiles, of=summary_of, truth=states[1:])
         out = (out if isinstance(out, tuple) else (out,)) + (filter_model.last_quantiles,)
@@ -567,6 +591,54 @@ def mode_summary(record, true=None, start: int = START_TRUNCATION) -> Dict[str, 
             ok = torch.isfinite(x)
             out[k + "_rmse"] = float(torch.sqrt(torch.where(ok, x * x, torch.zeros_like(x)).sum() / ok.sum()))
     return out
+
+
+def modality_summary(record, start: int = START_TRUNCATION) -> Dict[str, torch.Tensor]:
+    """Means of a modalities record (``ParticleFilter.last_modalities``; ``run_filter(return_modalities=True)``) over the
+    steps after the burn-in, over time and trajectories, each over its finite entries: ``responsibility (K,)``, every
+    modality's share of the fused posterior; ``dominant (K,)``, the share of steps where modality ``k`` has the largest
+    responsibility (the lowest index among equals; steps without a live particle are left out); ``log_evidence (K + 1,)``,
+    the fused one last; ``divergence (K,)``; ``overlap (K, K)``; and ``prior (K,)``, the mean of ``softmax_k beta`` -- what the
+    weight model asked for, uniform without one -- to read ``responsibility`` against."""
+    rho = getattr(record, "responsibility", None)
+    if rho is None or getattr(record, "log_evidence", None) is None:
+        raise ValueError("modality_summary: the record has no responsibility and log_evidence; take it from belief_modalities "
+                         "or run_filter(return_modalities=True)")
+
+    def mean(x, tail=1):  # over the leading axes, of the finite entries
+        x = x[start:].to(torch.float64)
+        shape = tuple(x.shape[x.dim() - tail:])
+        x = x.reshape((-1,) + shape)
+        ok = torch.isfinite(x)
+        return (torch.where(ok, x, torch.zeros_like(x)).sum(dim=0) / ok.sum(dim=0)).to(torch.float32)
+
+    K = rho.shape[-1]
+    r = rho[start:].reshape(-1, K)
+    ok = torch.isfinite(r).all(dim=-1)
+    first = torch.argmax(torch.where(ok[:, None], r, torch.zeros_like(r)), dim=-1)  # (the first maximum: the lowest index)
+    wins = torch.nn.functional.one_hot(first, K).to(torch.float64) * ok[:, None]
+    beta = getattr(record, "log_weights", None)
+    prior = (torch.full((K,), 1.0 / K, dtype=torch.float32, device=rho.device) if beta is None else
+             mean(torch.softmax(beta.to(torch.float64), dim=-1)))
+    return {"responsibility": mean(rho), "dominant": (wins.sum(dim=0) / ok.sum()).to(torch.float32),
+            "log_evidence": mean(record.log_evidence), "divergence": mean(record.divergence),
+            "overlap": mean(record.overlap, tail=2), "prior": prior}
+
+
+def modality_errors(record, true: torch.Tensor) -> torch.Tensor:
+    """Euclidean errors ``(T, N, K + 1)`` of a modalities record's ``mean (T, N, K + 1, d)`` against the true states
+    ``(T, N, d)``: what each sensor alone would have estimated on the filter's particles, and, last, the fused estimate.  NaN
+    where a modality carried no weight."""
+    mean = getattr(record, "mean", None)
+    if mean is None or mean.dim() != 4:
+        raise ValueError("modality_errors: the record has no mean (T, N, K + 1, d); take it from belief_modalities or "
+                         "run_filter(return_modalities=True)")
+    T, N, _, d = mean.shape
+    if not isinstance(true, torch.Tensor) or tuple(true.shape) != (T, N, d):
+        raise ValueError(f"modality_errors: true must be a (T, N, d) = ({T}, {N}, {d}) tensor, got "
+                         f"{tuple(true.shape) if isinstance(true, torch.Tensor) else type(true).__name__}")
+    with torch.no_grad():
+        return torch.linalg.vector_norm(mean - true.to(device=mean.device, dtype=mean.dtype)[:, :, None, :], dim=-1)
 
 
 def coverage(predicted: torch.Tensor, covariance: torch.Tensor, true: torch.Tensor, level: float = 0.95,

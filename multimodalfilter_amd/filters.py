@@ -92,6 +92,11 @@ class ParticleFilter(base.Filter):
     ``belief_modes(of=, max_modes=, link_radius=, bandwidth=, min_bandwidth=)``: the modes of the recorded sets by quick shift
     on that density -- how many, where, and the mass of each (returned: ``modes (T, N, K, d)``) -> ``last_modes``
     (``mmf_pf_modes``).
+    ``belief_modalities()``: with a crossmodal measurement model, which sensor decided each step -- every enabled modality's
+    evidence-weighted share of the fused posterior (returned: ``responsibility (T, N, K)``), its own evidence, effective
+    sample size, mean, divergence from the fused posterior and overlap with the others -> ``last_modalities``
+    (``mmf_pf_modalities``); ``forward_loop`` keeps a reference to the observations and the ``enabled_models`` of the run
+    in the history for it.
     Randomness comes from ``self.noise`` (``utils.NoiseSource``), never from global RNG state.
     """
 
@@ -133,6 +138,7 @@ class ParticleFilter(base.Filter):
         self.last_scores = None       # belief_scores(): CRPS, energy score and sharpness of the recorded sets against the truth
         self.last_density = None      # belief_density(): mode, log density, entropy and log score of the recorded sets
         self.last_modes = None        # belief_modes(): the modes of the recorded sets, their masses, means and members
+        self.last_modalities = None   # belief_modalities(): each modality's share, evidence and own posterior on the recorded sets
         self.record_transition_moments = False  # smooth(method="marginal") adds the two-slice residual moments to last_smoothed
         self._step_history = None
         self.use_native_loop = True   # False: forward_loop keeps the step-by-step Python loop
@@ -980,6 +986,63 @@ class ParticleFilter(base.Filter):
                                              parent=parent, bandwidth=h, of=of, rule=rule, link_radius=tau, max_modes=K)
         return modes
 
+    @engine.checked_loop
+    def belief_modalities(self) -> torch.Tensor:
+        """Which sensor decided each step of the recorded run (``mmf_pf_modalities``, ``include/mmf.h``): the crossmodal
+        fusion ``logsumexp_k(beta_k + l_k)`` taken apart again.  Returns ``responsibility (T, N, K)``, ``K`` the enabled
+        modalities: the evidence-weighted share ``rho_k`` of modality ``k`` in the fused posterior, ``W = sum_k rho_k W^k``
+        with ``W^k`` the posterior that modality alone would have left on the same particles -- not ``beta``, which a
+        modality with likelihoods of larger scale overrules.  Leaves ``last_modalities``: ``responsibility``,
+        ``log_evidence (T, N, K + 1)`` -- how well each sensor alone explained the observation, the fused figure last --,
+        ``ess (T, N, K + 1)``, ``mean (T, N, K + 1, d)`` -- what each sensor alone would have estimated --, ``divergence
+        (T, N, K)``, ``KL(W^k || W)``, ``overlap (T, N, K, K)``, the Bhattacharyya coefficient between two sensors'
+        posteriors (do they agree?), ``log_likelihoods (K, T, N, M)``, the unimodal ``l_k`` themselves (likelihood maps),
+        ``log_weights (T, N, K)``, ``beta`` as the weight model gave it (``None`` without one), and ``modalities``, the
+        enabled models' indices.
+        Reads the filtered sets of ``last_history`` (``states`` under ``log_weights_in``; ``record_history`` and
+        ``forward_loop`` first) and the observations and ``enabled_models`` that run left there: the observations are encoded
+        again over the ``T N`` rows and every unimodal network is evaluated on the recorded particles in one launch
+        (``CrossmodalParticleFilterMeasurementModel.modality_log_likelihoods``).  There is no ``of=``: a smoothed weight is
+        not a prior times a likelihood.  Needs a crossmodal measurement model with the ``enabled_models`` of the run.  The
+        status word is cleared on entry and checked on the way out, as ``forward_loop`` does it, so an activation of the
+        encoders or of the networks that left the f16x3 range raises here (the weights may have changed since the run).  Draws no
+        noise and leaves every other ``last_*`` record as it is.  A modality without weight on any live particle has
+        responsibility 0 and NaN figures; a step without a live particle gives NaN."""
+        from .base_models import CrossmodalParticleFilterMeasurementModel  # (base_models imports this module)
+
+        who = "belief_modalities"
+        h = self.last_history
+        if h is None or getattr(h, "states", None) is None:
+            raise ValueError(f"{who} needs a history: set record_history and run forward_loop (evaluation mode) first")
+        meas = self.measurement_model
+        if not isinstance(meas, CrossmodalParticleFilterMeasurementModel):
+            raise ValueError(f"{who} attributes the fusion of a CrossmodalParticleFilterMeasurementModel; "
+                             f"{type(meas).__name__} fuses nothing")
+        recorded = getattr(h, "enabled_models", None)
+        if getattr(h, "observations", None) is None or recorded is None:
+            raise ValueError(f"{who}: the history holds no observations: it was not left by this filter's forward_loop")
+        if tuple(meas.enabled_models) != tuple(recorded):
+            raise ValueError(f"{who}: enabled_models = {list(meas.enabled_models)} now, {list(recorded)} when the history was "
+                             "recorded: the recorded log-likelihoods are another fusion's; run forward_loop again")
+        T, N, M, d = h.states.shape
+        if M > _abi.SUMMARY_MAX_M:
+            raise ValueError(f"{who}: {M} particles per set; mmf_pf_modalities serves at most {_abi.SUMMARY_MAX_M}")
+        R = T * N
+        dev = h.states.device
+        with torch.no_grad():
+            ctx = meas.encode_observations(tree_map(h.observations, lambda x: x.reshape((R,) + tuple(x.shape[2:]))))
+            logliks, beta, enabled = meas.modality_log_likelihoods(h.states.view(R, M, d), ctx)
+            K = len(logliks)
+            new = lambda *tail: torch.empty((T, N) + tail, dtype=torch.float32, device=dev)
+            out = dict(responsibility=new(K), log_evidence=new(K + 1), ess=new(K + 1), mean=new(K + 1, d), divergence=new(K),
+                       overlap=new(K, K))
+            _abi.pf_modalities(h.states, h.log_weights_in, [l.view(T, N, M) for l in logliks],
+                               None if beta is None else beta.view(T, N, K), **out)
+            log_likelihoods = torch.stack(logliks).view(K, T, N, M)
+        self.last_modalities = base.belief_record(log_likelihoods=log_likelihoods, log_weights=None if beta is None else beta.view(T, N, K),
+                                                  modalities=enabled, **out)
+        return out["responsibility"]
+
     def belief_quantiles(self, probs, *, of: str = "filtered", truth: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Per-dimension weighted quantiles of the recorded particle sets (``mmf_pf_quantiles``, ``include/mmf.h``): the
         non-parametric counterpart of ``record_belief``'s covariance -- median, credible intervals -- for a belief that need
@@ -1068,6 +1131,11 @@ class ParticleFilter(base.Filter):
             None if ctrl_all is None else {k: v[sl] for k, v in ctrl_all.items()}), N)
         if self.last_history is not None:
             self.last_history.controls = controls  # (a reference, not a copy) what smooth(method="marginal") predicts with
+            from .base_models import CrossmodalParticleFilterMeasurementModel  # (base_models imports this module)
+
+            if isinstance(self.measurement_model, CrossmodalParticleFilterMeasurementModel):  # what belief_modalities()
+                self.last_history.observations = observations  # encodes again (a reference, not a copy), and the fusion it
+                self.last_history.enabled_models = tuple(self.measurement_model.enabled_models)  # belongs to
         return est
 
 
