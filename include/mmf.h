@@ -1219,6 +1219,76 @@ typedef struct MmfPfModalitiesArgs {
 } MmfPfModalitiesArgs;              /* host struct holding device pointers */
 int mmf_pf_modalities(const MmfPfModalitiesArgs* args /* host */, void* stream);
 
+/* ---------------------------------------------------------------- Particle-posterior distances: two sets against each other
+ * The evaluation of crossmodal/eval_helpers.py:148-160 compares a filter with the truth only, through the posterior mean;
+ * every summary above judges ONE weighted particle set.  Nothing compares two posteriors: the filtered set of a step against
+ * its smoothed set, 300 particles against 4096, one arithmetic mode, resampling scheme or modality mask against another.
+ * These are the standard two-sample distances, per state dimension on the two weighted empirical CDFs and multivariate as the
+ * energy distance (Szekely & Rizzo).  In torch ops the first is a cat + sort + two cumsums per dimension whose fp32 crossings
+ * depend on the summation order, the second three cdists with an (Ma, Mb) array each.  Purely additive to ABI 42: a struct
+ * and three symbols of their own.
+ * There are R row pairs; row r of set A has Ma particles x_m = states_a[r, m, :], row r of set B has Mb particles
+ * y_l = states_b[r, l, :], both of dimension d.  Ma != Mb is the normal case.  Each set has its own log-weights
+ * a = log_a + log_b (one fp32 add; a null addend is 0, both null: uniform weights) and its own maximum.
+ * Per dimension k, on K1's fixed-point weights (as "Particle-posterior quantiles"):
+ *   q            = (uint32) floor(expf(a - max a) * 2^24), 0 for a = -inf or NaN, per set
+ *   F_a, F_b     the two weighted empirical CDFs: 64-bit integer prefix sums of q, divided once, in double, by the set's total
+ *   z_0 <= z_1 <= ..   the coordinates k of the particles with q > 0 of BOTH sets, ascending;  D_j = F_a(z_j) - F_b(z_j)
+ *   wasserstein[r, k] = sum_j (z_{j+1} - z_j) |D_j|     the 1-Wasserstein (earth mover's) distance, in the state's own units
+ *   cramer[r, k]      = sum_j (z_{j+1} - z_j) D_j^2     the Cramer distance, the integral of (F_a - F_b)^2: half the
+ *                                                        one-dimensional energy distance, and without its cancellation
+ *   ks[r, k]          = max_j |D_j| over the j that end a tie group (z_{j+1} > z_j)   Kolmogorov-Smirnov, in [0, 1]
+ *   - the gaps are taken in double (exact for fp32 operands), the sums in double in one fixed order;
+ *   - a particle with q = 0 is not in the union, whatever its state row holds (the histories carry NaN rows for dead
+ *     particles); a tie may sort in any order: inside a tie group the gap is 0 and ks looks at group ends only;
+ *   - every CDF value is an integer sum: two calls give the same bits, a row pair computed alone has the bits it has in a
+ *     batch, and two identical sets give exactly 0 in all three.
+ * Multivariate, on plain float weights (as "Particle-posterior scores": w = expf(a - max a), normalised once in double), with
+ * s = scale[0 .. d) dividing the coordinates inside the norm (the kernel multiplies by the fp32 reciprocal):
+ *   terms[r, :] = (E|(X - Y) / s|_2, E|(X - X') / s|_2, E|(Y - Y') / s|_2)     over all Ma Mb, Ma^2 and Mb^2 pairs
+ *   energy[r]   = sqrt(max(2 terms[0] - terms[1] - terms[2], 0))               combined in double from the three double sums
+ *   - all three expectations go through one device function with one dealing, a function of Ma and Mb alone: the same arrays
+ *     passed as A and as B give energy == 0 exactly, two calls give the same bits, a row pair does not depend on R;
+ *   - a zero weight selects its term away and never multiplies it.
+ * Resolution of energy: it is the root of a difference of three sums of like size, so its floor is set by the fp32 pair
+ * terms and the expf of the weights RELATIVE TO terms -- each of the three is good to a few 1e-7 of itself, energy^2
+ * therefore to that share of 2 terms[0] + terms[1] + terms[2] -- not to energy: two posteriors closer than about 1e-3 of
+ * their own spread are below it.  For near-identical posteriors read cramer and wasserstein, which have no cancellation.
+ * A row pair in which either set has no live particle gives NaN in every output; everything else is finite.
+ * Kernel plan: (1) a workgroup per (row pair, dimension) packs (order-preserving uint32 key of the coordinate) << 32 |
+ * set bit | q into one uint64 per live particle of both sets in LDS -- q = 0 and the padding take the all-ones key --, padded
+ * to the next power of two P >= max(Ma + Mb, 64), sorts them as mmf_pf_quantiles does, scans q in integers once per set and
+ * makes one pass over the gaps between live neighbours; one wave for P <= 512, 256 threads beyond.  (2) the pair plan of
+ * mmf_pf_scores on a cross product: one device function cross(I-set, J-set), i-particles in registers, the J-set in tiles of
+ * 1024 through LDS, fp32 runs of 64 pairs flushed to double, dealt by the plan of the I-set (ceil(M / 512) workgroups);
+ * (A, A) and (A, B) share one load of the A particles, (B, B) follows.  With Ma and Mb both <= 512 one workgroup takes the
+ * row pair and writes it; otherwise every workgroup writes its sums to the workspace and a finishing kernel adds a row
+ * pair's partial sums in order.  No floating-point atomics.
+ * mmf_pf_distance_workspace_bytes(R, Ma, Mb, d): 24 R (nb_a + nb_b) bytes when Ma or Mb exceeds 512, else 0 (and 0 for an
+ * argument below 1).  mmf_pf_distance_lds_bytes(Ma, Mb): the dynamic LDS of the sorting workgroup, 8 B per padded slot and one
+ * spare slot per thread -- monotone in Ma + Mb, at most 160 KiB at the limit (beyond it: the value at the limit; 0 for an
+ * argument below 1).
+ * Limits, all decided on the host before any HIP call: null args / states_a / states_b, d outside 1 .. 4, Ma < 1, Mb < 1,
+ * R < 0, a scale[k < d] that is not positive and finite, all five outputs null, a workspace that is needed (energy or terms
+ * asked for, and the query's answer is not 0) and null, smaller than the query's answer or not 8-byte aligned, an output (or
+ * the workspace) overlapping an input of either set or another output -> MMF_EINVAL; Ma + Mb > 16384 -- the union sort's
+ * limit, and the one limit of the whole entry -- or a grid beyond 32 bits -> MMF_ETOOLARGE; R == 0 is a successful no-op.
+ * wasserstein, cramer and ks all null skips the first kernel; energy and terms both null skips the second. */
+typedef struct MmfPfDistanceArgs {
+  int32_t R, Ma, Mb, d;                        /* R row pairs (e.g. T*N) of Ma against Mb particles */
+  float scale[MMF_MAX_STATE_DIM];              /* host values, scale[k < d] > 0 and finite; 1 for plain Euclidean distance */
+  const float *states_a, *log_a_a, *log_b_a;   /* (R, Ma, d), (R, Ma) or null = 0 */
+  const float *states_b, *log_a_b, *log_b_b;   /* (R, Mb, d), (R, Mb) or null = 0 */
+  float *wasserstein, *cramer, *ks;            /* (R, d) each, or null */
+  float* energy;                               /* (R) or null */
+  float* terms;                                /* (R, 3) or null */
+  void* workspace;                             /* device, 8-byte aligned, mmf_pf_distance_workspace_bytes(R, Ma, Mb, d) bytes */
+  size_t workspace_bytes;
+} MmfPfDistanceArgs;                           /* host struct holding device pointers */
+int mmf_pf_distance(const MmfPfDistanceArgs* args /* host */, void* stream);
+size_t mmf_pf_distance_workspace_bytes(int R, int Ma, int Mb, int d);
+size_t mmf_pf_distance_lds_bytes(int Ma, int Mb);
+
 /* ---------------------------------------------------------------- K6, fused: one network call of the training backward
  * Recompute (the forward pass's f16x3 arithmetic), backward data path and weight / bias gradients of ONE per-particle
  * network over N * M rows in one kernel (the dynamics network: three launches -- encoder forward, trunk, encoder

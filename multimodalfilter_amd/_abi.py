@@ -138,6 +138,7 @@ class MmfPfSmoothMapArgs(Structure):
 QUANTILES_MAX = 16    # MMF_QUANTILES_MAX
 SUMMARY_MAX_M = 16384  # particles per row that mmf_pf_quantiles sorts in LDS and mmf_pf_scores and mmf_pf_density serve
 QUANTILES_MAX_M = SCORES_MAX_M = DENSITY_MAX_M = MODES_MAX_M = SUMMARY_MAX_M
+DISTANCE_MAX_M = SUMMARY_MAX_M  # particles of BOTH sets of a row pair together: mmf_pf_distance sorts their union in LDS
 
 
 class MmfPfQuantilesArgs(Structure):
@@ -177,6 +178,13 @@ class MmfPfModalitiesArgs(Structure):
     _fields_ = [("R", c_int32), ("M", c_int32), ("d", c_int32), ("K", c_int32), ("logw_stride", c_int32),
                 ("states", _FP), ("log_w", _FP), ("loglik", _FP * LOOP_MAX_MEAS), ("modality_logw", _FP),
                 ("log_evidence", _FP), ("responsibility", _FP), ("ess", _FP), ("mean", _FP), ("divergence", _FP), ("overlap", _FP)]
+
+
+class MmfPfDistanceArgs(Structure):
+    _fields_ = [("R", c_int32), ("Ma", c_int32), ("Mb", c_int32), ("d", c_int32), ("scale", ctypes.c_float * MMF_MAX_STATE_DIM),
+                ("states_a", _FP), ("log_a_a", _FP), ("log_b_a", _FP), ("states_b", _FP), ("log_a_b", _FP), ("log_b_b", _FP),
+                ("wasserstein", _FP), ("cramer", _FP), ("ks", _FP), ("energy", _FP), ("terms", _FP),
+                ("workspace", _FP), ("workspace_bytes", c_size_t)]
 
 
 class MmfTrainNet(Structure):
@@ -284,6 +292,9 @@ SIGNATURES = {
     "mmf_pf_quantiles_lds_bytes": (c_size_t, [c_int]),
     "mmf_pf_scores": (c_int, [POINTER(MmfPfScoresArgs), c_void_p]),
     "mmf_pf_scores_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "mmf_pf_distance": (c_int, [POINTER(MmfPfDistanceArgs), c_void_p]),
+    "mmf_pf_distance_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "mmf_pf_distance_lds_bytes": (c_size_t, [c_int, c_int]),
     "mmf_pf_density": (c_int, [POINTER(MmfPfDensityArgs), c_void_p]),
     "mmf_pf_density_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "mmf_pf_modes": (c_int, [POINTER(MmfPfModesArgs), c_void_p]),
@@ -1320,3 +1331,43 @@ def pf_modalities(states, log_w, logliks, modality_logw, *, log_evidence=None, r
     a.mean, a.divergence, a.overlap = vp(mean), vp(divergence), vp(overlap)
     with _on(states):
         _check(load().mmf_pf_modalities(ctypes.byref(a), stream_of(states)), "mmf_pf_modalities")
+
+
+def pf_distance_workspace_bytes(R: int, Ma: int, Mb: int, d: int) -> int:
+    return int(load().mmf_pf_distance_workspace_bytes(int(R), int(Ma), int(Mb), int(d)))
+
+
+def pf_distance_lds_bytes(Ma: int, Mb: int) -> int:
+    return int(load().mmf_pf_distance_lds_bytes(int(Ma), int(Mb)))
+
+
+def pf_distance(states_a, log_a_a, log_b_a, states_b, log_a_b, log_b_b, *, wasserstein=None, cramer=None, ks=None, energy=None,
+                terms=None, scale=None):
+    """Two-sample distances between weighted particle sets (``mmf_pf_distance``, include/mmf.h): ``states_a (..., Ma, d)``
+    against ``states_b (..., Mb, d)`` with the same leading sizes -- ``R`` row pairs, their product -- each under its own
+    log-weights ``log_a + log_b``, ``(..., M)`` or ``None`` (0; both ``None``: uniform) -> per dimension ``wasserstein``,
+    ``cramer``, ``ks (..., d)`` on K1's integer fixed-point weights, and in the Euclidean norm under ``scale`` ``energy (...)``
+    and ``terms (..., 3)``, ``E|X - Y|, E|X - X'|, E|Y - Y'|``; each of the five may be ``None`` (not all).  ``scale``:
+    ``None`` (ones) or ``d`` positive finite host floats.  The workspace of the partial sums is allocated here, on the
+    tensors' device."""
+    lead, R, Ma, d = _summary_rows(states_a, log_a_a, log_b_a)
+    lead_b, _, Mb, d_b = _summary_rows(states_b, log_a_b, log_b_b)
+    assert lead_b == lead and d_b == d and states_b.device == states_a.device
+    scale = [1.0] * d if scale is None else [float(s) for s in scale]
+    if len(scale) != d or d > MMF_MAX_STATE_DIM:
+        raise MmfError(f"mmf_pf_distance takes one scale per state dimension (d = {d} <= {MMF_MAX_STATE_DIM}), got {len(scale)}")
+    for out in (wasserstein, cramer, ks):
+        assert out is None or tuple(out.shape) == lead + (d,)
+    assert energy is None or tuple(energy.shape) == lead
+    assert terms is None or tuple(terms.shape) == lead + (3,)
+    a = MmfPfDistanceArgs()
+    a.R, a.Ma, a.Mb, a.d = R, Ma, Mb, d
+    for i, s in enumerate(scale):
+        a.scale[i] = s
+    a.states_a, a.log_a_a, a.log_b_a = vp(states_a), vp(log_a_a), vp(log_b_a)
+    a.states_b, a.log_a_b, a.log_b_b = vp(states_b), vp(log_a_b), vp(log_b_b)
+    a.wasserstein, a.cramer, a.ks, a.energy, a.terms = vp(wasserstein), vp(cramer), vp(ks), vp(energy), vp(terms)
+    with _on(states_a):
+        need = pf_distance_workspace_bytes(R, Ma, Mb, d) if energy is not None or terms is not None else 0
+        work = _summary_workspace(a, need, states_a)
+        _check(load().mmf_pf_distance(ctypes.byref(a), stream_of(states_a)), "mmf_pf_distance")

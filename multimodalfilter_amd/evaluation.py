@@ -312,6 +312,68 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
     return out
 
 
+def compare_filters(filter_a, filter_b, traj: Dict[str, torch.Tensor], *, smooth_method=None, smooth_draws: int = _DEFAULT_DRAWS,
+                    scale=None, **run_filter_kwargs):
+    """Two particle filters on the same trajectories, and how far their posteriors are apart step by step: 300 particles
+    against 4096, one arithmetic mode, resampling scheme or modality mask against another.  Both run through
+    ``run_filter``'s initialisation (``run_filter_kwargs``: ``initial_cov_scale``, ``measurement_initialize``) with
+    ``record_history`` set, and the switches are put back.  ``smooth_method=None`` compares the filtered sets;
+    ``"marginal"`` or ``"simulation"`` (with ``smooth_draws`` paths) smooths both and compares the smoothed sets.  Returns
+    ``(estimates_a, estimates_b, record)``: what ``run_filter`` returns for each -- the smoothed estimates when the call
+    smooths -- and ``filter_a.last_distance`` as ``filter_a.belief_distance(filter_b, scale=scale)`` leaves it
+    (``distance_summary``).  Each filter draws from its own ``noise``.  Anything that is not a particle filter is refused
+    before either runs: a Gaussian belief or a point estimate has no particle set, and the closed forms are a separate
+    change."""
+    for name, f in (("filter_a", filter_a), ("filter_b", filter_b)):
+        if not (hasattr(f, "belief_distance") and hasattr(f, "record_history")):
+            raise ValueError(f"compare_filters: {name} must be a particle filter; {type(f).__name__} has no belief_distance (a "
+                             "Gaussian belief or a point estimate has no particle set to compare)")
+    if filter_a is filter_b:
+        raise ValueError("compare_filters: filter_a and filter_b are one object, whose second run would replace the first's "
+                         "history; compare one filter's own sets with belief_distance(of=, other_of=)")
+    if smooth_method not in (None, "marginal", "simulation"):
+        raise ValueError(f"compare_filters: smooth_method must be None, 'marginal' or 'simulation' (the smoothers that leave a "
+                         f"weighted set per step), got {smooth_method!r}")
+    if smooth_draws is not _DEFAULT_DRAWS and smooth_method != "simulation":
+        raise ValueError(f"compare_filters: smooth_draws is the number of paths smooth_method='simulation' draws; "
+                         f"smooth_method={smooth_method!r} takes none")
+    extra = sorted(set(run_filter_kwargs) - {"initial_cov_scale", "measurement_initialize"})
+    if extra:
+        raise ValueError(f"compare_filters: run_filter_kwargs may name initial_cov_scale and measurement_initialize, got {extra}")
+    smooth = {} if smooth_method is None else {"smooth_method": smooth_method}
+    if smooth_draws is not _DEFAULT_DRAWS:
+        smooth["smooth_draws"] = smooth_draws
+    estimates = []
+    for f in (filter_a, filter_b):
+        was = f.record_history
+        f.record_history = True
+        try:
+            estimates.append(run_filter(f, traj, **smooth, **run_filter_kwargs))
+        finally:
+            f.record_history = was
+    of = "filtered" if smooth_method is None else "smoothed"
+    filter_a.belief_distance(filter_b, of=of, other_of=of, scale=scale)
+    return estimates[0], estimates[1], filter_a.last_distance
+
+
+def distance_summary(record, start: int = START_TRUNCATION) -> Dict[str, object]:
+    """Means of a distance record (``ParticleFilter.last_distance``; ``compare_filters``) over the finite entries of the steps
+    after the burn-in, over time and trajectories: ``wasserstein``, ``cramer``, ``ks`` ``(d,)`` and ``energy`` (a float).
+    Steps at which a side had no live particle (NaN) are left out, like ``score_summary`` leaves them."""
+    if getattr(record, "wasserstein", None) is None:
+        raise ValueError("distance_summary: the record has no wasserstein; take it from belief_distance or compare_filters")
+
+    def mean(x):  # over every axis but the last
+        x = x[start:].to(torch.float64)
+        x = x.reshape(-1, x.shape[-1])
+        ok = torch.isfinite(x)
+        return (torch.where(ok, x, torch.zeros_like(x)).sum(dim=0) / ok.sum(dim=0)).to(torch.float32)
+
+    out = {k: mean(getattr(record, k)) for k in ("wasserstein", "cramer", "ks")}
+    out["energy"] = float(mean(record.energy[..., None])[0])
+    return out
+
+
 def path_log_density(filter_model, indices) -> torch.Tensor:
     """The joint log-density of index paths through ``filter_model.last_history`` -- ``log_posterior`` of
     ``smooth(method="map")`` by its definition (``include/mmf.h``, "MAP path smoothing"): for ``indices (T, N)`` or

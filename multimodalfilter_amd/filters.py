@@ -97,6 +97,9 @@ class ParticleFilter(base.Filter):
     sample size, mean, divergence from the fused posterior and overlap with the others -> ``last_modalities``
     (``mmf_pf_modalities``); ``forward_loop`` keeps a reference to the observations and the ``enabled_models`` of the run
     in the history for it.
+    ``belief_distance(other=, of=, other_of=, scale=)``: two-sample distances between the recorded sets of two filters, or of
+    one filter's filtered and smoothed sets -- 1-Wasserstein per dimension (returned), Cramer, Kolmogorov-Smirnov and the
+    energy distance -> ``last_distance`` (``mmf_pf_distance``).
     Randomness comes from ``self.noise`` (``utils.NoiseSource``), never from global RNG state.
     """
 
@@ -139,6 +142,7 @@ class ParticleFilter(base.Filter):
         self.last_density = None      # belief_density(): mode, log density, entropy and log score of the recorded sets
         self.last_modes = None        # belief_modes(): the modes of the recorded sets, their masses, means and members
         self.last_modalities = None   # belief_modalities(): each modality's share, evidence and own posterior on the recorded sets
+        self.last_distance = None     # belief_distance(): two-sample distances between the recorded sets of two posteriors
         self.record_transition_moments = False  # smooth(method="marginal") adds the two-slice residual moments to last_smoothed
         self._step_history = None
         self.use_native_loop = True   # False: forward_loop keeps the step-by-step Python loop
@@ -1042,6 +1046,55 @@ class ParticleFilter(base.Filter):
         self.last_modalities = base.belief_record(log_likelihoods=log_likelihoods, log_weights=None if beta is None else beta.view(T, N, K),
                                                   modalities=enabled, **out)
         return out["responsibility"]
+
+    def belief_distance(self, other: Optional["ParticleFilter"] = None, *, of: str = "filtered", other_of: str = "filtered",
+                        scale=None) -> torch.Tensor:
+        """Two-sample distances between the recorded particle sets of this filter (set A, read with ``of``) and of ``other``
+        (set B, read with ``other_of``; ``None``: this filter), step by step (``mmf_pf_distance``, ``include/mmf.h``): how far
+        two posteriors are apart as distributions, where the means can only be subtracted.  ``f.belief_distance(of="filtered",
+        other_of="smoothed")`` after ``smooth(method="marginal")`` is how far the future moved the belief; two filters run on
+        the same data with 300 and 4096 particles, two arithmetic modes or two modality masks are compared the same way.
+        Returns ``wasserstein (T, N, d)``, the 1-Wasserstein (earth mover's) distance per state dimension in the state's own
+        units.  Leaves ``last_distance``: ``wasserstein``, ``cramer (T, N, d)`` -- the integral of the squared CDF difference,
+        which has no cancellation and resolves two posteriors that are almost the same --, ``ks (T, N, d)`` -- the
+        Kolmogorov-Smirnov statistic in [0, 1] --, all three on K1's integer fixed-point weights (identical sets give exactly
+        0, a step's bits do not depend on the batch); ``energy (T, N)``, the multivariate energy distance, and ``terms
+        (T, N, 3)``, ``E|X - Y|, E|X - X'|, E|Y - Y'|`` in the Euclidean norm, ``energy = sqrt(max(2 terms[0] - terms[1] -
+        terms[2], 0))`` -- a cancelling difference: below about 1e-3 of the sets' own spread read ``cramer``; ``of``,
+        ``other_of``, ``scale`` (a tuple) and ``particles = (M_a, M_b)``.
+        ``of`` and ``other_of`` mean what ``of`` means for ``belief_quantiles``.  The two sides must agree in ``(T, N, d)``;
+        their particle counts need not, and together may not exceed 16384.  ``scale``: as in ``belief_scores``, for the
+        norm of ``energy`` and ``terms`` only.  Draws no noise and leaves every other record of both filters as it is.  A
+        step at which either side has no live particle gives NaN."""
+        who = "belief_distance"
+        if other is None:
+            other = self
+        if not isinstance(other, ParticleFilter):
+            raise ValueError(f"{who}: other must be a ParticleFilter or None, got {type(other).__name__} (a Gaussian or a "
+                             "point estimate has no particle set)")
+        for name, value in (("of", of), ("other_of", other_of)):
+            if value not in ("filtered", "smoothed"):
+                raise ValueError(f"{who}: {name} must be 'filtered' or 'smoothed', got {value!r}")
+        xa, la_a, lb_a = self._recorded_sets(of, who)
+        xb, la_b, lb_b = other._recorded_sets(other_of, who)
+        T, N, Ma, d = xa.shape
+        Mb = xb.shape[2]
+        if (xb.shape[0], xb.shape[1], xb.shape[3]) != (T, N, d):
+            raise ValueError(f"{who}: the two sides must agree in (T, N, d): this filter's {of} sets have (T, N, d) = "
+                             f"({T}, {N}, {d}), the other's {other_of} sets ({xb.shape[0]}, {xb.shape[1]}, {xb.shape[3]})")
+        if xb.device != xa.device:
+            raise ValueError(f"{who}: the two sides are on different devices ({xa.device}, {xb.device})")
+        if Ma + Mb > _abi.DISTANCE_MAX_M:
+            raise ValueError(f"{who}: {Ma} + {Mb} particles per pair of sets; mmf_pf_distance sorts at most "
+                             f"{_abi.DISTANCE_MAX_M} of both sets together in LDS")
+        sc = (1.0,) * d if scale is None else self._positive_floats(who, scale, "scale", "None", d)
+        dev = xa.device
+        with torch.no_grad():
+            new = lambda *tail: torch.empty((T, N) + tail, dtype=torch.float32, device=dev)
+            out = dict(wasserstein=new(d), cramer=new(d), ks=new(d), energy=new(), terms=new(3))
+            _abi.pf_distance(xa, la_a, lb_a, xb, la_b, lb_b, scale=sc, **out)
+        self.last_distance = base.belief_record(of=of, other_of=other_of, scale=sc, particles=(Ma, Mb), **out)
+        return out["wasserstein"]
 
     def belief_quantiles(self, probs, *, of: str = "filtered", truth: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Per-dimension weighted quantiles of the recorded particle sets (``mmf_pf_quantiles``, ``include/mmf.h``): the
