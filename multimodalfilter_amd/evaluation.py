@@ -1,14 +1,17 @@
 """Evaluation harness: the role of ``/root/reference/crossmodal/eval_helpers.py:70-217`` on
 device-resident ``(T, N, ...)`` batches, plus the multi-GPU reduction of its error statistic.
 """
+import contextlib
 import math
 import numbers
+from collections import namedtuple
 from typing import Dict
 
 import numpy as np
 import torch
 
-from . import base
+from . import base, base_models, filters
+from .base_models import CrossmodalParticleFilterMeasurementModel
 from .filters import _DEFAULT_DRAWS
 from .task_models import DOOR, PUSH
 
@@ -30,6 +33,221 @@ class _DefaultRadius(float):
 
 _DEFAULT_RADIUS = _DefaultRadius(3.0)
 
+# what a filter without the switch is told (an AssertionError: the caller asked the wrong kind of filter)
+_WITHOUT_SWITCH = {"record_belief": "keeps no belief to record", "record_history": "keeps no history to smooth",
+                   "record_transition_moments": "computes no transition moments"}
+
+
+@contextlib.contextmanager
+def _switched(filter_model, name):
+    """Runs its body with the filter's ``record_*`` switch ``name`` set and puts back what it held, on every path."""
+    assert hasattr(filter_model, name), f"{type(filter_model).__name__} {_WITHOUT_SWITCH.get(name, 'has no ' + name)}"
+    was = getattr(filter_model, name)
+    setattr(filter_model, name, True)
+    try:
+        yield
+    finally:
+        setattr(filter_model, name, was)
+
+
+def _floats(values):
+    """``values`` as a tuple of floats, or ``None`` where it is no sequence of what ``float()`` takes.  That is more than
+    ``ParticleFilter._positive_floats`` takes -- a ``bool``, a numeric string -- and every caller keeps its own message."""
+    try:
+        return tuple(float(v) for v in values)
+    except (TypeError, ValueError):
+        return None
+
+
+def _positive(values) -> bool:
+    return bool(values) and all(0.0 < v < math.inf for v in values)
+
+
+# ---- the records run_filter appends: one description each (_Record), in the order in which they are checked and returned
+_Record = namedtuple("_Record", "argument asked kind weighted switch make option default unused check sized",
+                     defaults=(None,) * 5)
+_Record.__doc__ = """``argument``: the ``return_*`` argument that asks for the record, and ``asked(value)``: whether it does.
+``option``: its companion argument, ``default`` that argument's default, compared by identity, and ``unused``: what a caller
+who passes the option without the argument is told (``None``: no option).  ``kind(filter_model)``: ``"particles"``,
+``"gaussian"`` or ``"point"``, or the ``ValueError`` of a filter that cannot give the record.  ``check(value, option)``: the
+value checks that need no trajectory; returns the option as the record is made with.  ``sized``: the message of an option
+that is a tuple of another length than the state dimension (``None``: no such option).  ``weighted``: the particle kind reads
+a weighted set per step -- the smoothed sets when the call smooths, which only ``"marginal"`` and ``"simulation"`` leave.
+``switch``: per kind, the ``record_*`` switch the run needs.  ``make(kind, run, value, option)``: the record, after the run."""
+_Run = namedtuple("_Run", "filter est truth of smoothed")  # what make() reads: est and of are the smoother's where smoothed
+
+
+def _belief_of(run):
+    """The belief record that goes with the returned means: the smoothed one when the call smooths."""
+    return run.filter.last_smoothed if run.smoothed else run.filter.last_belief
+
+
+def _is_given(value) -> bool:
+    return value is not None
+
+
+def _belief_kind(what, point=None):
+    """A particle filter has ``belief_<what>``, a Kalman filter ``record_belief``; a filter with neither (an LSTM baseline) is
+    the kind ``point``, or refused."""
+    def kind(filter_model):
+        if hasattr(filter_model, "belief_" + what):
+            return "particles"
+        if hasattr(filter_model, "record_belief"):
+            return "gaussian"
+        if point is None:
+            raise ValueError(f"run_filter: return_{what} needs a belief; {type(filter_model).__name__} returns a point "
+                             f"estimate, which has no {what} (no belief_{what}, no record_belief)")
+        return point
+    return kind
+
+
+def _innovations_kind(filter_model):
+    if not hasattr(filter_model, "record_innovations"):
+        raise ValueError(f"run_filter: return_innovations needs a Kalman filter; {type(filter_model).__name__} has no "
+                         "record_innovations (a particle filter reports log_evidence through return_belief)")
+    return "gaussian"
+
+
+def _modalities_kind(filter_model):
+    if not (hasattr(filter_model, "belief_modalities")
+            and isinstance(getattr(filter_model, "measurement_model", None), CrossmodalParticleFilterMeasurementModel)):
+        what = ("the Kalman filters fuse their sub-filters per state dimension, and the attribution of that fusion is a "
+                "separate change"
+                if isinstance(filter_model, (base_models._FusedKalmanFilters, filters.VirtualSensorExtendedKalmanFilter))
+                else "it fuses no modalities")
+        raise ValueError(f"run_filter: return_modalities needs a crossmodal particle filter (belief_modalities over a "
+                         f"CrossmodalParticleFilterMeasurementModel); {type(filter_model).__name__} is none: {what}")
+    return "particles"
+
+
+def _quantiles_kind(filter_model):
+    if not hasattr(filter_model, "belief_quantiles"):
+        raise ValueError(f"run_filter: return_quantiles needs a particle filter; {type(filter_model).__name__} has no "
+                         "belief_quantiles (a Gaussian belief's quantiles are closed form: mean and covariance)")
+    return "particles"
+
+
+def _check_score_scale(value, scale):
+    if scale is None:
+        return None
+    floats = _floats(scale)
+    if not _positive(floats):
+        raise ValueError(f"run_filter: score_scale must be None or d positive finite floats, got {scale if floats is None else floats!r}")
+    return floats
+
+
+def _check_density_bandwidth(value, bandwidth):
+    if isinstance(bandwidth, str) and bandwidth in ("silverman", "scott"):
+        return bandwidth
+    floats = _floats("" if isinstance(bandwidth, str) else bandwidth)
+    if not _positive(floats):
+        raise ValueError("run_filter: density_bandwidth must be 'silverman', 'scott' or d positive finite floats")
+    return floats
+
+
+def _check_modes(count, radius):
+    if isinstance(count, bool) or not isinstance(count, numbers.Integral) or not 1 <= count <= 8:
+        raise ValueError(f"run_filter: return_modes must be None or the number of modes to report, 1 .. 8, got {count!r}")
+    if isinstance(radius, bool) or not isinstance(radius, numbers.Real) or not 0.0 < float(radius) < math.inf:
+        raise ValueError(f"run_filter: modes_link_radius must be a positive finite float, got {radius!r}")
+    return float(radius)
+
+
+def _make_innovations(kind, run, value, option):
+    return run.filter.last_innovations
+
+
+def _make_scores(kind, run, value, scale):
+    if kind == "particles":
+        run.filter.belief_scores(run.truth, of=run.of, scale=scale)
+        return run.filter.last_scores
+    s = (1.0,) * run.truth.shape[-1] if scale is None else scale
+    with torch.no_grad():
+        if kind == "gaussian":
+            return base.belief_record(crps=gaussian_crps(run.est, _belief_of(run).covariance, run.truth), of=run.of, scale=s)
+        e = run.est - run.truth  # a point mass
+        energy = torch.linalg.vector_norm(e / torch.tensor(s, dtype=e.dtype, device=e.device), dim=-1)
+        return base.belief_record(crps=e.abs(), energy=energy, of=run.of, scale=s)
+
+
+def _make_density(kind, run, value, bandwidth):
+    if kind == "particles":
+        run.filter.belief_density(run.truth, of=run.of, bandwidth=bandwidth)
+        return run.filter.last_density
+    with torch.no_grad():
+        cov = _belief_of(run).covariance
+        return base.belief_record(log_score=gaussian_log_density(run.est, cov, run.truth), entropy=gaussian_entropy(cov),
+                                  mode=run.est, of=run.of)
+
+
+def _make_modes(kind, run, count, radius):
+    K = int(count)
+    if kind == "particles":
+        run.filter.belief_modes(run.of, max_modes=K, link_radius=radius)
+        return run.filter.last_modes
+    est = run.est
+    with torch.no_grad():  # the one mode a Gaussian has
+        at = torch.full(est.shape[:2] + (K, est.shape[-1]), math.nan, dtype=est.dtype, device=est.device)
+        at[:, :, 0] = est
+        mass = torch.zeros(est.shape[:2] + (K,), dtype=est.dtype, device=est.device)
+        mass[:, :, 0] = 1.0
+        count = torch.ones(est.shape[:2], dtype=torch.int32, device=est.device)
+        return base.belief_record(modes=at, mean=at.clone(), mass=mass, count=count, of=run.of, max_modes=K)
+
+
+def _make_modalities(kind, run, value, option):
+    run.filter.belief_modalities()  # always of the filtered sets: a smoothed weight is not a prior times a likelihood
+    return run.filter.last_modalities
+
+
+def _make_quantiles(kind, run, probs, option):
+    run.filter.belief_quantiles(probs, of=run.of, truth=run.truth)
+    return run.filter.last_quantiles
+
+
+_HISTORY = {"particles": "record_history"}
+_RECORDS = (
+    _Record(argument="return_innovations", asked=bool, kind=_innovations_kind, weighted=False,
+            switch={"gaussian": "record_innovations"}, make=_make_innovations),
+    _Record(argument="return_scores", asked=bool, option="score_scale", default=None,
+            unused="run_filter: score_scale is the scale of return_scores' energy score; without return_scores it has no use",
+            kind=_belief_kind("scores", point="point"), check=_check_score_scale,
+            sized="run_filter: score_scale must be None or d = {d} positive finite floats, got {got!r}",
+            weighted=True, switch={**_HISTORY, "gaussian": "record_belief", "point": None}, make=_make_scores),
+    _Record(argument="return_density", asked=bool, option="density_bandwidth", default=_DEFAULT_BANDWIDTH,
+            unused="run_filter: density_bandwidth is the bandwidth of return_density's kernel density; without "
+                   "return_density it has no use",
+            kind=_belief_kind("density"), check=_check_density_bandwidth,
+            sized="run_filter: density_bandwidth must be 'silverman', 'scott' or d = {d} positive finite floats, got {got!r}",
+            weighted=True, switch={**_HISTORY, "gaussian": "record_belief"}, make=_make_density),
+    _Record(argument="return_modes", asked=_is_given, option="modes_link_radius", default=_DEFAULT_RADIUS,
+            unused="run_filter: modes_link_radius is the link radius of return_modes' quick shift; without return_modes "
+                   "it has no use",
+            kind=_belief_kind("modes"), check=_check_modes, weighted=True, switch={**_HISTORY, "gaussian": None}, make=_make_modes),
+    _Record(argument="return_modalities", asked=bool, kind=_modalities_kind, weighted=False, switch=_HISTORY, make=_make_modalities),
+    _Record(argument="return_quantiles", asked=_is_given, kind=_quantiles_kind, weighted=True, switch=_HISTORY, make=_make_quantiles),
+)
+
+
+def _plan(record, filter_model, arguments, unweighted=None):
+    """The checks of one record that need no trajectory, in their order -> ``(record, kind, value, option)``, or ``None``
+    where the record is not asked for.  ``unweighted``: the smoothing method where the call smooths with one that leaves no
+    weighted set per step."""
+    value, option = arguments[record.argument], arguments.get(record.option, record.default)
+    asked = record.asked(value)
+    if option is not record.default and not asked:
+        raise ValueError(record.unused)
+    if not asked:
+        return None
+    kind = record.kind(filter_model)
+    if record.check is not None:
+        option = record.check(value, option)
+    if record.weighted and kind == "particles" and unweighted is not None:
+        raise ValueError(f"run_filter: {record.argument} reads a weighted particle set per step; smooth_method={unweighted!r} "
+                         "leaves none (ancestry keeps no per-step weights, a MAP path is not a distribution): smooth with "
+                         "'marginal' or 'simulation', or do not smooth")
+    return record, kind, value, option
+
 
 def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale: float = 0.1,
                measurement_initialize: bool = False, return_belief: bool = False, smooth_lag=False,
@@ -38,9 +256,13 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
                return_modes=None, modes_link_radius: float = _DEFAULT_RADIUS, return_modalities: bool = False,
                return_quantiles=None, return_scores: bool = False, score_scale=None):
     """Initialise the belief at ``states[0]`` with covariance ``0.1 I`` (or from the first
-    observation, ``eval_helpers.py:116-131``) and filter ``[1:]`` (``:139-142``).
-    ``return_belief``: run with ``record_belief`` set and return ``(estimates, filter_model.last_belief)`` -- the per-step
-    posterior covariances (and the particle filter's ESS / log-evidence) for the calibration metrics below.
+    observation, ``eval_helpers.py:116-131``) and filter ``[1:]`` (``:139-142``).  Returns the estimates ``(T, N, d)`` alone,
+    or one tuple: the estimates, then whatever of belief, innovations, scores, density, modes, modalities and quantiles was
+    asked for, in this order.
+
+    The run and the smoother.
+    ``return_belief``: run with ``record_belief`` set and return ``filter_model.last_belief`` -- the per-step posterior
+    covariances (and the particle filter's ESS / log-evidence) for the calibration metrics below.
     ``smooth_lag``: ``False`` (the default) leaves all of this as it is; an integer or ``None`` (the full smoother) runs a
     particle filter with ``record_history`` set and returns ``filter_model.smooth(smooth_lag)`` -- the whole recorded
     trajectory is at hand, so ``E[x_t | y_1..t+lag]`` is the better estimate -- and, with ``return_belief``, the smoothed
@@ -53,182 +275,81 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
     another method is the ``ValueError`` it is there), and leaves ``covariance``, ``trajectories``, ``indices``, ``num_draws``;
     ``"map"`` likewise returns the most probable particle PATH ``(T, N, d)`` and leaves ``indices``, ``log_posterior`` and no
     ``covariance`` (a path is not a distribution: ``gaussian_nll`` / ``nees`` / ``coverage`` do not apply).
-    ``smooth_transition_moments``: smooths with the filter's ``record_transition_moments`` set (and puts the switch back) -- with ``smooth_method="marginal"`` or ``"rts"`` alone, refused
-    before the run otherwise; the record gains ``residual_mean`` and ``residual_second_moment`` (``process_noise_m_step``).
-    ``return_innovations``: runs a Kalman filter with ``record_innovations`` set (and puts the switch back) and appends
-    ``filter_model.last_innovations`` -- ``nis``, ``log_likelihood``, ``accepted`` per step (``innovation_summary``) -- to what
-    is returned: ``(estimates, innovations)`` or ``(estimates, record, innovations)``.  A filter without the switch (the
-    particle filters, the LSTM baselines) is refused before the run.
-    ``return_quantiles``: a sequence of probabilities runs a particle filter with ``record_history`` set (and puts the switch
-    back), calls ``filter_model.belief_quantiles(probs, of=..., truth=traj["states"][1:])`` -- ``of="smoothed"`` exactly when
-    the call smooths with ``"marginal"`` or ``"simulation"``, the filter's own weighted sets otherwise -- and appends
-    ``filter_model.last_quantiles`` (``probs``, ``quantiles (T, N, Q, d)``, ``of``, ``pit (T, N, d)``; ``interval_coverage``,
-    ``pit_histogram``) as the LAST element of what is returned.  A filter without ``belief_quantiles`` (the Kalman filters,
-    whose quantiles are closed form, and the LSTM baselines) and a smoothing method without a weighted set (``"ancestry"``
-    with a lag, ``"map"``, ``"rts"``) are refused before the run.  Left at ``None``, every return value and every bit is as
-    without it.
-    ``return_scores``: appends a score record -- strictly proper scores of the belief against ``traj["states"][1:]``, the one
-    scale on which the three kinds of filter can be ranked as distributions (``score_summary``) -- after the innovations and
-    before the quantiles record, which stays last.  A particle filter runs with ``record_history`` set (and puts the switch
-    back) and calls ``belief_scores(traj["states"][1:], of=..., scale=score_scale)``: ``crps (T, N, d)``, ``energy (T, N)``,
-    ``spread (T, N, d + 1)`` of its weighted sets, ``of`` chosen and the smoothing methods refused as for
-    ``return_quantiles``.  A filter with a belief covariance (the Kalman filters) runs with ``record_belief`` set (and puts
-    the switch back); the record holds ``crps = gaussian_crps(...)`` of the returned means and the covariance that goes with
-    them -- the smoothed one when the call smooths -- and no ``energy``, which has no closed form.  A filter with neither (the
-    LSTM baselines) gets the scores of a point mass: ``crps = |estimate - true|``, ``energy = |(estimate - true) / s|``.
-    ``score_scale``: ``None`` or ``d`` positive finite floats ``s`` for the Euclidean norm of ``energy``; without
-    ``return_scores`` it is refused.  Left at ``False``, every return value and every bit is as without it.
-    ``return_density``: appends a density record -- the logarithmic score of the belief at ``traj["states"][1:]``, its
-    entropy and its mode (``density_summary``) -- after the score record and before the quantiles record, which stays last.
-    A particle filter runs with ``record_history`` set (and puts the switch back) and calls ``belief_density(traj["states"][1:],
-    of=..., bandwidth=density_bandwidth)``: ``last_density``, ``of`` chosen and the smoothing methods refused as for
-    ``return_scores``.  A filter with a belief covariance (the Kalman filters) runs with ``record_belief`` set (and puts the
-    switch back); the record holds the closed forms of its Gaussian belief -- ``log_score = gaussian_log_density(...)``,
-    ``entropy = gaussian_entropy(...)`` and ``mode``, the returned means -- under the covariance that goes with them.  A
-    filter with neither (the LSTM baselines) is refused before the run: a point estimate has no density.
-    ``density_bandwidth``: ``"silverman"`` (the default), ``"scott"`` or ``d`` positive finite floats, the
-    ``bandwidth`` of ``belief_density``; without ``return_density`` it is refused.  Left at ``False``, every return value and
-    every bit is as without it.
-    ``return_modes``: an integer ``K`` (1 .. 8) appends a modes record -- how many hypotheses the belief holds per step, where
-    they are and what each weighs (``mode_errors``, ``mode_summary``) -- after the density record and before the quantiles
-    record, which stays last.  A particle filter runs with ``record_history`` set (and puts the switch back) and calls
-    ``belief_modes(of=..., max_modes=K, link_radius=modes_link_radius)``: ``last_modes``, ``of`` chosen and the smoothing
-    methods refused as for ``return_density``.  A filter with a belief covariance (the Kalman filters) gets the one mode a
-    Gaussian has: ``modes (T, N, K, d)`` and ``mean`` with the returned means at rank 0 and NaN beyond, ``mass`` 1 and 0,
-    ``count`` 1.  A filter with neither (the LSTM baselines) is refused before the run.  ``modes_link_radius``: the
-    ``link_radius`` of ``belief_modes`` (default 3.0 bandwidths); without ``return_modes`` it is refused.  Left at ``None``,
-    every return value and every bit is as without it.
-    ``return_modalities``: appends a modalities record -- which sensor decided each step: every modality's share of the fused
-    posterior, its own evidence, mean, divergence and overlap (``modality_summary``, ``modality_errors``) -- after the modes
-    record and before the quantiles record, which stays last.  A crossmodal particle filter runs with ``record_history`` set
-    (and puts the switch back) and calls ``belief_modalities()``: ``last_modalities``, always of the filtered sets, whatever
-    the call smooths with -- a smoothed weight is not a prior times a likelihood.  Every other filter is refused before the
-    run: a particle filter with one measurement model fuses nothing, an LSTM baseline has no belief, and the Kalman filters
-    fuse their sub-filters per state dimension, whose attribution is a separate change.  Left at ``False``, every return
-    value and every bit is as without it."""
-    if return_innovations and not hasattr(filter_model, "record_innovations"):  # (before the run, not after it)
-        raise ValueError(f"run_filter: return_innovations needs a Kalman filter; {type(filter_model).__name__} has no "
-                         "record_innovations (a particle filter reports log_evidence through return_belief)")
+    ``smooth_transition_moments``: smooths with the filter's ``record_transition_moments`` set -- with
+    ``smooth_method="marginal"`` or ``"rts"`` alone; the record gains ``residual_mean`` and ``residual_second_moment``
+    (``process_noise_m_step``).
+
+    The appended records (``_RECORDS`` describes each once).  For all of them: the truth is ``traj["states"][1:]``.  A filter
+    that cannot give the record, an option without its ``return_*`` argument, a bad option and a smoothing method that does
+    not fit are refused before the run, in the order of the records; the trajectories are not read before that.  Every
+    ``record_*`` switch the run needs is put back on every path, before the record is made.  A particle filter runs with
+    ``record_history`` set and its ``belief_*`` method is called with ``of="smoothed"`` exactly when the call smooths, which
+    then must be with ``"marginal"`` or ``"simulation"``: ``"ancestry"`` with a lag, ``"map"`` and ``"rts"`` leave no weighted
+    set per step.  A filter with a belief covariance (the Kalman filters) gets the closed forms of its Gaussian belief, of the
+    returned means and the covariance that goes with them -- the smoothed one when the call smooths.  With the argument left
+    at its default every return value and every bit is as without it.
+    ``return_innovations``: runs a Kalman filter with ``record_innovations`` set and appends ``filter_model.last_innovations``
+    -- ``nis``, ``log_likelihood``, ``accepted`` per step (``innovation_summary``).  A filter without the switch (the particle
+    filters, the LSTM baselines) is refused.
+    ``return_scores``: strictly proper scores of the belief, the one scale on which the three kinds of filter can be ranked as
+    distributions (``score_summary``).  Particles: ``belief_scores(truth, of=, scale=score_scale)`` -- ``crps (T, N, d)``,
+    ``energy (T, N)``, ``spread (T, N, d + 1)``.  Gaussian, with ``record_belief`` set: ``crps = gaussian_crps(...)`` and no
+    ``energy``, which has no closed form.  A filter with neither (the LSTM baselines) gets the scores of a point mass: ``crps =
+    |estimate - true|``, ``energy = |(estimate - true) / s|``.  ``score_scale``: ``None`` or ``d`` positive finite floats ``s``
+    for the Euclidean norm of ``energy``.
+    ``return_density``: the logarithmic score of the belief at the truth, its entropy and its mode (``density_summary``).
+    Particles: ``belief_density(truth, of=, bandwidth=density_bandwidth)``.  Gaussian, with ``record_belief`` set: ``log_score =
+    gaussian_log_density(...)``, ``entropy = gaussian_entropy(...)`` and ``mode``, the returned means.  A point estimate has no
+    density: refused.  ``density_bandwidth``: ``"silverman"`` (the default), ``"scott"`` or ``d`` positive finite floats.
+    ``return_modes``: an integer ``K`` (1 .. 8): how many hypotheses the belief holds per step, where they are and what each
+    weighs (``mode_errors``, ``mode_summary``).  Particles: ``belief_modes(of, max_modes=K, link_radius=modes_link_radius)``
+    (default 3.0 bandwidths).  Gaussian: the one mode a Gaussian has -- ``modes (T, N, K, d)`` and ``mean`` with the returned
+    means at rank 0 and NaN beyond, ``mass`` 1 and 0, ``count`` 1.  A point estimate is refused.
+    ``return_modalities``: which sensor decided each step: every modality's share of the fused posterior, its own evidence,
+    mean, divergence and overlap (``modality_summary``, ``modality_errors``).  A crossmodal particle filter calls
+    ``belief_modalities()``, always of the filtered sets, whatever the call smooths with -- a smoothed weight is not a prior
+    times a likelihood.  Every other filter is refused: a particle filter with one measurement model fuses nothing, an LSTM
+    baseline has no belief, and the Kalman filters fuse their sub-filters per state dimension, whose attribution is a separate
+    change.
+    ``return_quantiles``: a sequence of probabilities; a particle filter calls ``belief_quantiles(probs, of=, truth=)``:
+    ``probs``, ``quantiles (T, N, Q, d)``, ``of``, ``pit (T, N, d)`` (``interval_coverage``, ``pit_histogram``).  A filter
+    without ``belief_quantiles`` (the Kalman filters, whose quantiles are closed form, and the LSTM baselines) is refused."""
+    # 1. check everything, in order, before the run
+    arguments = dict(return_innovations=return_innovations, return_scores=return_scores, score_scale=score_scale,
+                     return_density=return_density, density_bandwidth=density_bandwidth, return_modes=return_modes,
+                     modes_link_radius=modes_link_radius, return_modalities=return_modalities, return_quantiles=return_quantiles)
+    plans = [_plan(_RECORDS[0], filter_model, arguments)]  # (the innovations, which no smoother bears on, come first)
     named = smooth_method is not _DEFAULT_METHOD
     if not named:
         smooth_method = getattr(filter_model, "default_smooth_method", "ancestry")
-    if smooth_transition_moments and smooth_method not in ("marginal", "rts"):  # (before the run, not after it)
+    if smooth_transition_moments and smooth_method not in ("marginal", "rts"):
         raise ValueError(f"run_filter: smooth_transition_moments are the two-slice moments that smooth_method='marginal' (particle "
                          f"filters) and 'rts' (extended Kalman filters) compute; "
                          f"smooth_method={smooth_method!r} has none")
-    if smooth_draws is not _DEFAULT_DRAWS and smooth_method != "simulation":  # (before the run, not after it)
+    if smooth_draws is not _DEFAULT_DRAWS and smooth_method != "simulation":
         raise ValueError(f"run_filter: smooth_draws is the number of paths smooth_method='simulation' draws; "
                          f"smooth_method={smooth_method!r} takes none")
-    # what reads a weighted particle set per step (return_scores, return_density, return_quantiles) reads the smoothed sets
-    # when the call smooths, and then only the smoothers that leave such sets will do
-    will_smooth = smooth_lag is not False or (named and smooth_method != "ancestry")
-    summary_of = "smoothed" if will_smooth else "filtered"
-
-    def needs_weighted_sets(argument):
-        if will_smooth and smooth_method not in ("marginal", "simulation"):
-            raise ValueError(f"run_filter: {argument} reads a weighted particle set per step; smooth_method={smooth_method!r} "
-                             "leaves none (ancestry keeps no per-step weights, a MAP path is not a distribution): smooth with "
-                             "'marginal' or 'simulation', or do not smooth")
-
-    want_scores = bool(return_scores)
-    if score_scale is not None:  # (before the run, not after it)
-        if not want_scores:
-            raise ValueError("run_filter: score_scale is the scale of return_scores' energy score; without return_scores it has no use")
-        try:
-            score_scale = tuple(float(v) for v in score_scale)
-        except (TypeError, ValueError):
-            raise ValueError(f"run_filter: score_scale must be None or d positive finite floats, got {score_scale!r}") from None
-        if not score_scale or not all(0.0 < v < math.inf for v in score_scale):
-            raise ValueError(f"run_filter: score_scale must be None or d positive finite floats, got {score_scale!r}")
-    scores_kind = None
-    if want_scores:  # (before the run, not after it)
-        scores_kind = ("particles" if hasattr(filter_model, "belief_scores") else
-                       "gaussian" if hasattr(filter_model, "record_belief") else "point")
-        if scores_kind == "particles":
-            needs_weighted_sets("return_scores")
-    want_density = bool(return_density)
-    if density_bandwidth is not _DEFAULT_BANDWIDTH and not want_density:  # (before the run, not after it)
-        raise ValueError("run_filter: density_bandwidth is the bandwidth of return_density's kernel density; without "
-                         "return_density it has no use")
-    density_kind = None
-    if want_density:  # (before the run, not after it)
-        density_kind = ("particles" if hasattr(filter_model, "belief_density") else
-                        "gaussian" if hasattr(filter_model, "record_belief") else None)
-        if density_kind is None:
-            raise ValueError(f"run_filter: return_density needs a belief; {type(filter_model).__name__} returns a point "
-                             "estimate, which has no density (no belief_density, no record_belief)")
-        if not (isinstance(density_bandwidth, str) and density_bandwidth in ("silverman", "scott")):
-            try:
-                density_bandwidth = tuple(float(v) for v in ("" if isinstance(density_bandwidth, str) else density_bandwidth))
-            except (TypeError, ValueError):
-                density_bandwidth = ()
-            if not density_bandwidth or not all(0.0 < v < math.inf for v in density_bandwidth):
-                raise ValueError("run_filter: density_bandwidth must be 'silverman', 'scott' or d positive finite floats")
-        if density_kind == "particles":
-            needs_weighted_sets("return_density")
-    want_modes = return_modes is not None
-    if modes_link_radius is not _DEFAULT_RADIUS and not want_modes:  # (before the run, not after it)
-        raise ValueError("run_filter: modes_link_radius is the link radius of return_modes' quick shift; without return_modes "
-                         "it has no use")
-    modes_kind = None
-    if want_modes:  # (before the run, not after it)
-        modes_kind = ("particles" if hasattr(filter_model, "belief_modes") else
-                      "gaussian" if hasattr(filter_model, "record_belief") else None)
-        if modes_kind is None:
-            raise ValueError(f"run_filter: return_modes needs a belief; {type(filter_model).__name__} returns a point "
-                             "estimate, which has no modes (no belief_modes, no record_belief)")
-        if isinstance(return_modes, bool) or not isinstance(return_modes, numbers.Integral) or not 1 <= return_modes <= 8:
-            raise ValueError(f"run_filter: return_modes must be None or the number of modes to report, 1 .. 8, got {return_modes!r}")
-        if (isinstance(modes_link_radius, bool) or not isinstance(modes_link_radius, numbers.Real)
-                or not 0.0 < float(modes_link_radius) < math.inf):
-            raise ValueError(f"run_filter: modes_link_radius must be a positive finite float, got {modes_link_radius!r}")
-        if modes_kind == "particles":
-            needs_weighted_sets("return_modes")
-    want_modalities = bool(return_modalities)
-    if want_modalities:  # (before the run, not after it)
-        from . import base_models, filters
-        from .base_models import CrossmodalParticleFilterMeasurementModel
-
-        if not (hasattr(filter_model, "belief_modalities")
-                and isinstance(getattr(filter_model, "measurement_model", None), CrossmodalParticleFilterMeasurementModel)):
-            what = ("the Kalman filters fuse their sub-filters per state dimension, and the attribution of that fusion is a "
-                    "separate change"
-                    if isinstance(filter_model, (base_models._FusedKalmanFilters, filters.VirtualSensorExtendedKalmanFilter))
-                    else "it fuses no modalities")
-            raise ValueError(f"run_filter: return_modalities needs a crossmodal particle filter (belief_modalities over a "
-                             f"CrossmodalParticleFilterMeasurementModel); {type(filter_model).__name__} is none: {what}")
-    want_quantiles = return_quantiles is not None
-    if want_quantiles:  # (before the run, not after it)
-        if not hasattr(filter_model, "belief_quantiles"):
-            raise ValueError(f"run_filter: return_quantiles needs a particle filter; {type(filter_model).__name__} has no "
-                             "belief_quantiles (a Gaussian belief's quantiles are closed form: mean and covariance)")
-        needs_weighted_sets("return_quantiles")
+    if named and smooth_method != "ancestry" and smooth_lag is False:
+        smooth_lag = None  # a named smoother is the full one
+    smoothing = smooth_lag is not False  # (0 is a lag)
+    of = "smoothed" if smoothing else "filtered"
+    unweighted = smooth_method if smoothing and smooth_method not in ("marginal", "simulation") else None
+    plans += [_plan(record, filter_model, arguments, unweighted) for record in _RECORDS[1:]]
+    plans = [plan for plan in plans if plan is not None]
     states = traj["states"]
     T1, N, d = states.shape
-    if score_scale is not None and len(score_scale) != d:
-        raise ValueError(f"run_filter: score_scale must be None or d = {d} positive finite floats, got {score_scale!r}")
+    for record, _, _, option in plans:
+        if isinstance(option, tuple) and len(option) != d:
+            raise ValueError(record.sized.format(d=d, got=option))
     obs = {k: traj[k] for k in ("image", "gripper_pos", "gripper_sensors")}
-    was = getattr(filter_model, "record_belief", None)
-    if isinstance(density_bandwidth, tuple) and len(density_bandwidth) != d:
-        raise ValueError(f"run_filter: density_bandwidth must be 'silverman', 'scott' or d = {d} positive finite floats, got "
-                         f"{density_bandwidth!r}")
-    need_belief = return_belief or scores_kind == "gaussian" or density_kind == "gaussian"
-    if need_belief:
-        assert was is not None, f"{type(filter_model).__name__} keeps no belief to record"
-        filter_model.record_belief = True
-    if named and smooth_method != "ancestry" and smooth_lag is False:
-        smooth_lag = None
-    smoothing = smooth_lag is not False  # (0 is a lag)
-    need_history = smoothing or want_quantiles or want_modalities or "particles" in (scores_kind, density_kind, modes_kind)
-    if need_history:
-        assert hasattr(filter_model, "record_history"), f"{type(filter_model).__name__} keeps no history to smooth"
-        was_history = filter_model.record_history
-        filter_model.record_history = True
-    if return_innovations:
-        was_innovations = filter_model.record_innovations
-        filter_model.record_innovations = True
-    innovations = None
-    try:
+    # 2. set the switches (belief, history, innovations: the order in which a filter without one is told so)
+    needed = {record.switch[kind] for record, kind, _, _ in plans}
+    needed.update(["record_belief"] * bool(return_belief) + ["record_history"] * smoothing)
+    with contextlib.ExitStack() as switches:
+        for name in ("record_belief", "record_history", "record_innovations"):
+            if name in needed:
+                switches.enter_context(_switched(filter_model, name))
+        # 3. initialise, run, and smooth
         with torch.no_grad():
             if measurement_initialize and hasattr(filter_model, "measurement_initialize_beliefs"):
                 filter_model.measurement_initialize_beliefs({k: v[0] for k, v in obs.items()})
@@ -237,79 +358,15 @@ def run_filter(filter_model, traj: Dict[str, torch.Tensor], *, initial_cov_scale
                 filter_model.initialize_beliefs(mean=states[0], covariance=cov)
             est = filter_model.forward_loop(observations={k: v[1:] for k, v in obs.items()},
                                             controls=traj["controls"][1:])
-        if return_innovations:
-            innovations = filter_model.last_innovations
-    finally:
-        if return_innovations:
-            filter_model.record_innovations = was_innovations
-        if need_belief:
-            filter_model.record_belief = was
-        if need_history:
-            filter_model.record_history = was_history
     if smoothing:
         draws = {} if smooth_draws is _DEFAULT_DRAWS else {"num_draws": smooth_draws}  # (another method refuses it, as smooth() does)
-        was_moments = getattr(filter_model, "record_transition_moments", False)
-        if smooth_transition_moments:
-            assert hasattr(filter_model, "record_transition_moments"), f"{type(filter_model).__name__} computes no transition moments"
-            filter_model.record_transition_moments = True
-        try:
+        with _switched(filter_model, "record_transition_moments") if smooth_transition_moments else contextlib.nullcontext():
             est = filter_model.smooth(smooth_lag, method=smooth_method, **draws)
-        finally:
-            if smooth_transition_moments:
-                filter_model.record_transition_moments = was_moments
-        out = (est, filter_model.last_smoothed) if return_belief else est
-    else:
-        out = (est, filter_model.last_belief) if return_belief else est
-    if return_innovations:
-        out = (out if isinstance(out, tuple) else (out,)) + (innovations,)
-    if want_scores:
-        truth = states[1:]
-        if scores_kind == "particles":
-            filter_model.belief_scores(truth, of=summary_of, scale=score_scale)
-            scores = filter_model.last_scores
-        else:
-            s = (1.0,) * d if score_scale is None else score_scale
-            with torch.no_grad():
-                if scores_kind == "gaussian":
-                    cov = (filter_model.last_smoothed if smoothing else filter_model.last_belief).covariance
-                    scores = base.belief_record(crps=gaussian_crps(est, cov, truth), of=summary_of, scale=s)
-                else:
-                    e = est - truth
-                    energy = torch.linalg.vector_norm(e / torch.tensor(s, dtype=e.dtype, device=e.device), dim=-1)
-                    scores = base.belief_record(crps=e.abs(), energy=energy, of=summary_of, scale=s)
-        out = (out if isinstance(out, tuple) else (out,)) + (scores,)
-    if want_density:
-        truth = states[1:]
-        if density_kind == "particles":
-            filter_model.belief_density(truth, of=summary_of, bandwidth=density_bandwidth)
-            density = filter_model.last_density
-        else:
-            with torch.no_grad():
-                cov = (filter_model.last_smoothed if smoothing else filter_model.last_belief).covariance
-                density = base.belief_record(log_score=gaussian_log_density(est, cov, truth), entropy=gaussian_entropy(cov),
-                                             mode=est, of=summary_of)
-        out = (out if isinstance(out, tuple) else (out,)) + (density,)
-    if want_modes:
-        K = int(return_modes)
-        if modes_kind == "particles":
-            filter_model.belief_modes(summary_of, max_modes=K, link_radius=float(modes_link_radius))
-            modes = filter_model.last_modes
-        else:
-            with torch.no_grad():
-                at = torch.full(est.shape[:2] + (K, d), math.nan, dtype=est.dtype, device=est.device)
-                at[:, :, 0] = est
-                mass = torch.zeros(est.shape[:2] + (K,), dtype=est.dtype, device=est.device)
-                mass[:, :, 0] = 1.0
-                count = torch.ones(est.shape[:2], dtype=torch.int32, device=est.device)
-                modes = base.belief_record(modes=at, mean=at.clone(), mass=mass, count=count, of=summary_of, max_modes=K)
-        out = (out if isinstance(out, tuple) else (out,)) + (modes,)
-    if want_modalities:
-        filter_model.belief_modalities()
-        out = (out if isinstance(out, tuple) else (out,)) + (filter_model.last_modalities,)
-    if want_quantiles:
-        filter_model.belief_quantiles(return_quantiles, of=summary_of, truth=states[1:])
-        out = (out if isinstance(out, tuple) else (out,)) + (filter_model.last_quantiles,)
-    return out
+    # 4. make the records in order
+    run = _Run(filter_model, est, states[1:], of, smoothing)
+    out = [est, _belief_of(run)] if return_belief else [est]
+    out += [record.make(kind, run, value, option) for record, kind, value, option in plans]
+    return est if len(out) == 1 else tuple(out)
 
 
 def compare_filters(filter_a, filter_b, traj: Dict[str, torch.Tensor], *, smooth_method=None, smooth_draws: int = _DEFAULT_DRAWS,
@@ -345,15 +402,26 @@ def compare_filters(filter_a, filter_b, traj: Dict[str, torch.Tensor], *, smooth
         smooth["smooth_draws"] = smooth_draws
     estimates = []
     for f in (filter_a, filter_b):
-        was = f.record_history
-        f.record_history = True
-        try:
+        with _switched(f, "record_history"):
             estimates.append(run_filter(f, traj, **smooth, **run_filter_kwargs))
-        finally:
-            f.record_history = was
     of = "filtered" if smooth_method is None else "smoothed"
     filter_a.belief_distance(filter_b, of=of, other_of=of, scale=scale)
     return estimates[0], estimates[1], filter_a.last_distance
+
+
+def _finite_mean(x: torch.Tensor, start: int, tail: int = 0) -> torch.Tensor:
+    """The mean of the finite entries of ``x[start:]`` over its leading axes, accumulated in float64; the ``tail`` trailing
+    axes are kept -> float64.  What every record summary below means by a mean after the burn-in."""
+    x = x[start:].to(torch.float64)
+    x = x.reshape((-1,) + tuple(x.shape[x.dim() - tail:]))
+    ok = torch.isfinite(x)
+    return torch.where(ok, x, torch.zeros_like(x)).sum(dim=0) / ok.sum(dim=0)
+
+
+def _check_truth(who: str, true, T: int, N: int, d: int) -> None:
+    if not isinstance(true, torch.Tensor) or tuple(true.shape) != (T, N, d):
+        raise ValueError(f"{who}: true must be a (T, N, d) = ({T}, {N}, {d}) tensor, got "
+                         f"{tuple(true.shape) if isinstance(true, torch.Tensor) else type(true).__name__}")
 
 
 def distance_summary(record, start: int = START_TRUNCATION) -> Dict[str, object]:
@@ -362,15 +430,8 @@ def distance_summary(record, start: int = START_TRUNCATION) -> Dict[str, object]
     Steps at which a side had no live particle (NaN) are left out, like ``score_summary`` leaves them."""
     if getattr(record, "wasserstein", None) is None:
         raise ValueError("distance_summary: the record has no wasserstein; take it from belief_distance or compare_filters")
-
-    def mean(x):  # over every axis but the last
-        x = x[start:].to(torch.float64)
-        x = x.reshape(-1, x.shape[-1])
-        ok = torch.isfinite(x)
-        return (torch.where(ok, x, torch.zeros_like(x)).sum(dim=0) / ok.sum(dim=0)).to(torch.float32)
-
-    out = {k: mean(getattr(record, k)) for k in ("wasserstein", "cramer", "ks")}
-    out["energy"] = float(mean(record.energy[..., None])[0])
+    out = {k: _finite_mean(getattr(record, k), start, tail=1).to(torch.float32) for k in ("wasserstein", "cramer", "ks")}
+    out["energy"] = float(_finite_mean(record.energy[..., None], start, tail=1).to(torch.float32)[0])
     return out
 
 
@@ -592,15 +653,9 @@ def density_summary(record, start: int = START_TRUNCATION) -> Dict[str, float]:
     ``-inf`` are left out, like ``score_summary`` leaves them."""
     if getattr(record, "entropy", None) is None:
         raise ValueError("density_summary: the record has no entropy; take it from belief_density or run_filter(return_density=True)")
-
-    def mean(x):
-        x = x[start:].to(torch.float64).reshape(-1)
-        ok = torch.isfinite(x)
-        return float(torch.where(ok, x, torch.zeros_like(x)).sum() / ok.sum())
-
-    out = {"entropy": mean(record.entropy)}
+    out = {"entropy": float(_finite_mean(record.entropy, start))}
     if getattr(record, "log_score", None) is not None:
-        out["log_score"] = mean(record.log_score)
+        out["log_score"] = float(_finite_mean(record.log_score, start))
     return out
 
 
@@ -614,15 +669,10 @@ def mode_errors(record, true: torch.Tensor, scale=None) -> Dict[str, torch.Tenso
     if modes is None or modes.dim() != 4:
         raise ValueError("mode_errors: the record has no modes (T, N, K, d); take it from belief_modes or run_filter(return_modes=K)")
     T, N, K, d = modes.shape
-    if not isinstance(true, torch.Tensor) or tuple(true.shape) != (T, N, d):
-        raise ValueError(f"mode_errors: true must be a (T, N, d) = ({T}, {N}, {d}) tensor, got "
-                         f"{tuple(true.shape) if isinstance(true, torch.Tensor) else type(true).__name__}")
+    _check_truth("mode_errors", true, T, N, d)
     if scale is not None:
-        try:
-            scale = tuple(float(v) for v in scale)
-        except (TypeError, ValueError):
-            scale = ()
-        if len(scale) != d or not all(0.0 < v < math.inf for v in scale):
+        scale = _floats(scale)
+        if scale is None or len(scale) != d or not _positive(scale):
             raise ValueError(f"mode_errors: scale must be None or d = {d} positive finite floats")
     with torch.no_grad():
         e = modes - true.to(device=modes.device, dtype=modes.dtype)[:, :, None, :]
@@ -649,9 +699,8 @@ def mode_summary(record, true=None, start: int = START_TRUNCATION) -> Dict[str, 
     if true is not None:
         errors = mode_errors(record, true)
         for k in ("top", "best"):
-            x = errors[k][start:].to(torch.float64).reshape(-1)
-            ok = torch.isfinite(x)
-            out[k + "_rmse"] = float(torch.sqrt(torch.where(ok, x * x, torch.zeros_like(x)).sum() / ok.sum()))
+            x = errors[k].to(torch.float64)
+            out[k + "_rmse"] = float(torch.sqrt(_finite_mean(x * x, start)))
     return out
 
 
@@ -667,13 +716,7 @@ def modality_summary(record, start: int = START_TRUNCATION) -> Dict[str, torch.T
         raise ValueError("modality_summary: the record has no responsibility and log_evidence; take it from belief_modalities "
                          "or run_filter(return_modalities=True)")
 
-    def mean(x, tail=1):  # over the leading axes, of the finite entries
-        x = x[start:].to(torch.float64)
-        shape = tuple(x.shape[x.dim() - tail:])
-        x = x.reshape((-1,) + shape)
-        ok = torch.isfinite(x)
-        return (torch.where(ok, x, torch.zeros_like(x)).sum(dim=0) / ok.sum(dim=0)).to(torch.float32)
-
+    mean = lambda x, tail=1: _finite_mean(x, start, tail).to(torch.float32)
     K = rho.shape[-1]
     r = rho[start:].reshape(-1, K)
     ok = torch.isfinite(r).all(dim=-1)
@@ -696,9 +739,7 @@ def modality_errors(record, true: torch.Tensor) -> torch.Tensor:
         raise ValueError("modality_errors: the record has no mean (T, N, K + 1, d); take it from belief_modalities or "
                          "run_filter(return_modalities=True)")
     T, N, _, d = mean.shape
-    if not isinstance(true, torch.Tensor) or tuple(true.shape) != (T, N, d):
-        raise ValueError(f"modality_errors: true must be a (T, N, d) = ({T}, {N}, {d}) tensor, got "
-                         f"{tuple(true.shape) if isinstance(true, torch.Tensor) else type(true).__name__}")
+    _check_truth("modality_errors", true, T, N, d)
     with torch.no_grad():
         return torch.linalg.vector_norm(mean - true.to(device=mean.device, dtype=mean.dtype)[:, :, None, :], dim=-1)
 
@@ -742,13 +783,7 @@ def score_summary(record, start: int = START_TRUNCATION) -> Dict[str, object]:
     live particle (NaN) are left out, like the other metrics leave them."""
     if getattr(record, "crps", None) is None:
         raise ValueError("score_summary: the record has no crps; take it from belief_scores or run_filter(return_scores=True)")
-
-    def mean(x):  # over every axis but the last
-        x = x[start:].to(torch.float64)
-        x = x.reshape(-1, x.shape[-1])
-        ok = torch.isfinite(x)
-        return (torch.where(ok, x, torch.zeros_like(x)).sum(dim=0) / ok.sum(dim=0)).to(torch.float32)
-
+    mean = lambda x: _finite_mean(x, start, tail=1).to(torch.float32)  # over every axis but the last
     out = {"crps": mean(record.crps)}
     if getattr(record, "energy", None) is not None:
         out["energy"] = float(mean(record.energy[..., None])[0])

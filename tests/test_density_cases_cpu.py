@@ -15,6 +15,7 @@ import _density_cases as dc
 import _quantile_cases as qc
 import _score_cases as sk
 import _smooth_cases as sc
+from _filter_stubs import _Recorded
 from _tol import REL_TOL
 
 EINVAL, ETOOLARGE = -1, -2
@@ -368,26 +369,6 @@ def test_belief_density_refusals_come_before_any_device_work():
         with pytest.raises(_abi.MmfError):
             f.belief_density(**kw)
     assert f.last_density is None
-
-
-class _Recorded:
-    """A stand-in filter on the CPU: ``forward_loop`` returns fixed estimates (``run_filter`` is duck-typed); with a
-    covariance it keeps a belief record like a Kalman filter, without one it is a point estimator like the LSTM baselines."""
-
-    def __init__(self, est, cov=None):
-        self._est, self._cov = est, cov
-        if cov is not None:
-            self.record_belief, self.last_belief = False, None
-
-    def initialize_beliefs(self, *, mean, covariance):
-        pass
-
-    def forward_loop(self, *, observations, controls):
-        if self._cov is not None:
-            from multimodalfilter_amd import base
-
-            self.last_belief = base.belief_record(covariance=self._cov) if self.record_belief else None
-        return self._est
 
 
 def test_run_filter_density_of_a_gaussian_belief_and_refusal_of_a_point_estimate():

@@ -332,3 +332,52 @@ def test_run_filter_places_the_modalities_record_between_the_modes_and_the_quant
         g = ctor().to(dev).eval()
         with pytest.raises(ValueError, match="return_modalities needs a crossmodal particle filter"):
             evaluation.run_filter(g, traj, return_modalities=True)
+
+
+def _same_record(a, b, what):
+    """Two records field by field: tensors ``torch.equal`` on their bytes (a NaN beyond the count of modes is equal to
+    itself), everything else ``==``."""
+    assert set(vars(a)) == set(vars(b)), what
+    for k, x in vars(a).items():
+        y = getattr(b, k)
+        if isinstance(x, torch.Tensor):
+            assert x.dtype == y.dtype and x.shape == y.shape, (what, k)
+            assert torch.equal(x.contiguous().view(torch.uint8), y.contiguous().view(torch.uint8)), (what, k)
+        else:
+            assert x == y, (what, k)
+
+
+@pytest.mark.parametrize("smooth_method", [None, "marginal"])
+def test_run_filter_hands_every_summary_the_arguments_of_the_direct_call(smooth_method):
+    """All the records at once, in order, and each what the direct ``belief_*`` call leaves on the same filter afterwards."""
+    import multimodalfilter_amd as mmf
+    from multimodalfilter_amd import evaluation
+
+    dev = sc.dev()
+    N_, M, T = 3, 64, 6
+    f, d, traj, obs, ctrl, cov = sc.small_filter("DoorCrossmodalParticleFilter", N_, M, T, dev)
+    f.noise = mmf.CounterNoise(7)
+    probs = (0.1, 0.5, 0.9)
+    smooth = {} if smooth_method is None else {"smooth_method": smooth_method}
+    out = evaluation.run_filter(f, traj, return_belief=True, return_scores=True, return_density=True, return_modes=2,
+                                return_modalities=True, return_quantiles=probs, **smooth)
+    torch.cuda.synchronize()
+    assert type(out) is tuple and len(out) == 7                     # (the estimates and the six records a particle filter has)
+    est, belief, scores, density, modes, modalities, quantiles = out
+    assert f.record_history is False and f.record_belief is False
+    assert est.shape == (T, N_, d) and belief is (f.last_belief if smooth_method is None else f.last_smoothed)
+    assert scores is f.last_scores and density is f.last_density and modes is f.last_modes
+    assert modalities is f.last_modalities and quantiles is f.last_quantiles
+    of = "filtered" if smooth_method is None else "smoothed"
+    truth = traj["states"][1:]
+    f.belief_scores(truth, of=of)
+    _same_record(scores, f.last_scores, "scores")
+    f.belief_density(truth, of=of)
+    _same_record(density, f.last_density, "density")
+    f.belief_modes(of, max_modes=2)
+    _same_record(modes, f.last_modes, "modes")
+    f.belief_modalities()
+    _same_record(modalities, f.last_modalities, "modalities")
+    f.belief_quantiles(probs, of=of, truth=truth)
+    _same_record(quantiles, f.last_quantiles, "quantiles")
+    assert scores is not f.last_scores and quantiles is not f.last_quantiles and scores.of == density.of == modes.of == quantiles.of == of

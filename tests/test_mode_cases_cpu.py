@@ -407,7 +407,7 @@ def test_run_filter_gives_a_gaussian_belief_its_one_mode():
     import torch
 
     from multimodalfilter_amd import evaluation
-    from test_density_cases_cpu import _Recorded
+    from _filter_stubs import _Recorded
 
     g = torch.Generator().manual_seed(3)
     T, N, d = 5, 2, 3
