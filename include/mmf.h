@@ -1289,6 +1289,65 @@ int mmf_pf_distance(const MmfPfDistanceArgs* args /* host */, void* stream);
 size_t mmf_pf_distance_workspace_bytes(int R, int Ma, int Mb, int d);
 size_t mmf_pf_distance_lds_bytes(int Ma, int Mb);
 
+/* ---------------------------------------------------------------- Predictive mixtures: k-step-ahead forecasts, scored exactly
+ * Everything above judges the present or the past of a run.  The predict step of torchfilter's particle filter (un-vendored:
+ * SURVEY appendix A.2) -- x' = f(x, u) + L eps -- is what a forecast iterates, and after the LAST propagation of a roll-out the
+ * noise need not be drawn: the predictive distribution is the Gaussian mixture with one shared covariance
+ *   p(x) = sum_i W_i N(x; F_i, Q),   Q = L L^T,   sigma_k = sqrt(Q_kk)
+ * whose mean, covariance, logarithmic score, PIT and CRPS are closed forms: strictly proper scores without a bandwidth, where
+ * "Particle-posterior density" needs a kernel density estimate.  Purely additive to ABI 42: a struct and two symbols of their own.
+ * Per row r (R rows, e.g. (T - h) * N, of M centres F_i = centres[r, i, :]) with an optional truth y = truth[r, :]:
+ *   a_i, w_i = expf(a_i - max a), W_i = w_i / sum w      exactly as in "Particle-posterior scores"
+ *   mean[k]          = sum_i W_i F_ik
+ *   covariance[k, l] = sum_i W_i (F_ik - mean_k)(F_il - mean_l) + Q_kl          the difference before the product
+ *   log_score        = logsumexp_i(log W_i - 1/2 |L^-1 (y - F_i)|^2) - sum_k log L_kk - d/2 log 2 pi
+ *   pit[k]           = sum_i W_i Phi((y_k - F_ik) / sigma_k)
+ *   spread[k]        = sum_i sum_j W_i W_j A(F_ik - F_jk; sqrt(2) sigma_k)      all M^2 pairs of a row
+ *   crps[k]          = sum_i W_i A(y_k - F_ik; sigma_k) - 1/2 spread[k]
+ *   A(m; s)          = m erf(m / (s sqrt 2)) + s sqrt(2 / pi) exp(-m^2 / (2 s^2))   E|Z| for Z ~ N(m, s^2)
+ * One component gives the Gaussian closed forms.  mean, covariance, log_score and pit are taken in double throughout, the
+ * log-sum-exp about the largest exponent, so a truth 50 sigma away has a finite log score.  The pair terms are fp32:
+ * A(m; s) = s sqrt(2) g(m / (s sqrt 2)) with g(t) = t erf(t) + exp(-t^2) / sqrt(pi) evaluated as |t| + exp(-t^2) p(1 / (1 + |t| / 2)),
+ * p a fitted polynomial of degree 9: within 7e-7 of g, relative, everywhere, and every term of the sums is positive.
+ *   - scale_tril is read as a lower triangle with a positive diagonal; it is device memory and not checked;
+ *   - a particle with w_i = 0 contributes nothing, whatever its row of centres holds (NaN, by convention): the zero weight
+ *     selects the term away, it does not multiply it;
+ *   - a row without a live particle gives NaN everywhere;
+ *   - a NaN y_k gives NaN in log_score and in crps[k] and pit[k]; everything else stays finite;
+ *   - mean, covariance and spread need no truth; log_score, pit or crps without one is refused.
+ * Determinism: every sum is taken in a fixed order and there are no floating-point atomics -- two calls give the same bits, a
+ * row's result depends on neither R nor the other rows, and the bits of an output do not depend on which others are asked for.
+ * Kernel plan: (1) mean, covariance, log_score and pit: one workgroup of 256 threads per row, two passes over the row, sums
+ * in double in the order of pf_summary.h; skipped when none of the four is asked for.  (2) spread and crps: the pair plan of
+ * mmf_pf_scores with g in place of |.| -- nb = ceil(M / 512) workgroups to a row, one or two i-particles of a thread in
+ * registers, j-tiles of 1024 through LDS as structure-of-arrays read as broadcasts, dead particles staged as zeros with zero
+ * weight, fp32 runs of 64 pairs flushed to double, 2 d + 1 double sums per workgroup; with nb == 1 the workgroup writes the
+ * row, otherwise a finishing kernel adds a row's nb partial sums in order.  Skipped when neither is asked for.
+ * mmf_pf_predictive_workspace_bytes(R, M, d): 72 R nb bytes for M > 512, 0 up to 512 (and for R, M or d below 1); read only
+ * when spread or crps is asked for.
+ * Limits, all decided on the host before any HIP call: null args / centres / scale_tril, d outside 1 .. 4, M < 1, R < 0, all
+ * six outputs null, log_score, pit or crps without truth, a workspace that is needed and null, smaller than the query's answer
+ * or not 8-byte aligned, an output (or the workspace) overlapping an input or another output -> MMF_EINVAL; M > 16384 or
+ * R * nb beyond a 32-bit grid -> MMF_ETOOLARGE; R == 0 is a successful no-op. */
+typedef struct MmfPfPredictiveArgs {
+  int32_t R, M, d;                  /* R rows (e.g. (T-h)*N) of M mixture components */
+  const float* centres;             /* (R, M, d) */
+  const float* log_a;               /* (R, M) or null = 0 */
+  const float* log_b;               /* (R, M) or null = 0 (history: log_weights_in + log_likelihoods) */
+  const float* scale_tril;          /* (d, d), the process noise's L */
+  const float* truth;               /* (R, d); null allowed with mean, covariance and spread */
+  float* mean;                      /* (R, d) or null */
+  float* covariance;                /* (R, d, d) or null */
+  float* log_score;                 /* (R) or null */
+  float* pit;                       /* (R, d) or null */
+  float* spread;                    /* (R, d) or null */
+  float* crps;                      /* (R, d) or null */
+  void* workspace;                  /* device, 8-byte aligned, mmf_pf_predictive_workspace_bytes(R, M, d) bytes; unused when that is 0 */
+  size_t workspace_bytes;
+} MmfPfPredictiveArgs;              /* host struct holding device pointers */
+int mmf_pf_predictive(const MmfPfPredictiveArgs* args /* host */, void* stream);
+size_t mmf_pf_predictive_workspace_bytes(int R, int M, int d);
+
 /* ---------------------------------------------------------------- K6, fused: one network call of the training backward
  * Recompute (the forward pass's f16x3 arithmetic), backward data path and weight / bias gradients of ONE per-particle
  * network over N * M rows in one kernel (the dynamics network: three launches -- encoder forward, trunk, encoder

@@ -138,6 +138,7 @@ class MmfPfSmoothMapArgs(Structure):
 QUANTILES_MAX = 16    # MMF_QUANTILES_MAX
 SUMMARY_MAX_M = 16384  # particles per row that mmf_pf_quantiles sorts in LDS and mmf_pf_scores and mmf_pf_density serve
 QUANTILES_MAX_M = SCORES_MAX_M = DENSITY_MAX_M = MODES_MAX_M = SUMMARY_MAX_M
+PREDICTIVE_MAX_M = SUMMARY_MAX_M  # mixture components per row that mmf_pf_predictive serves
 DISTANCE_MAX_M = SUMMARY_MAX_M  # particles of BOTH sets of a row pair together: mmf_pf_distance sorts their union in LDS
 
 
@@ -184,6 +185,13 @@ class MmfPfDistanceArgs(Structure):
     _fields_ = [("R", c_int32), ("Ma", c_int32), ("Mb", c_int32), ("d", c_int32), ("scale", ctypes.c_float * MMF_MAX_STATE_DIM),
                 ("states_a", _FP), ("log_a_a", _FP), ("log_b_a", _FP), ("states_b", _FP), ("log_a_b", _FP), ("log_b_b", _FP),
                 ("wasserstein", _FP), ("cramer", _FP), ("ks", _FP), ("energy", _FP), ("terms", _FP),
+                ("workspace", _FP), ("workspace_bytes", c_size_t)]
+
+
+class MmfPfPredictiveArgs(Structure):
+    _fields_ = [("R", c_int32), ("M", c_int32), ("d", c_int32),
+                ("centres", _FP), ("log_a", _FP), ("log_b", _FP), ("scale_tril", _FP), ("truth", _FP),
+                ("mean", _FP), ("covariance", _FP), ("log_score", _FP), ("pit", _FP), ("spread", _FP), ("crps", _FP),
                 ("workspace", _FP), ("workspace_bytes", c_size_t)]
 
 
@@ -295,6 +303,8 @@ SIGNATURES = {
     "mmf_pf_distance": (c_int, [POINTER(MmfPfDistanceArgs), c_void_p]),
     "mmf_pf_distance_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "mmf_pf_distance_lds_bytes": (c_size_t, [c_int, c_int]),
+    "mmf_pf_predictive": (c_int, [POINTER(MmfPfPredictiveArgs), c_void_p]),
+    "mmf_pf_predictive_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "mmf_pf_density": (c_int, [POINTER(MmfPfDensityArgs), c_void_p]),
     "mmf_pf_density_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "mmf_pf_modes": (c_int, [POINTER(MmfPfModesArgs), c_void_p]),
@@ -1223,6 +1233,35 @@ def pf_scores(states, log_a, log_b, truth, crps, energy, spread, scale=None):
     with _on(states):
         work = _summary_workspace(a, pf_scores_workspace_bytes(R, M, d), states)
         _check(load().mmf_pf_scores(ctypes.byref(a), stream_of(states)), "mmf_pf_scores")
+
+
+def pf_predictive_workspace_bytes(R: int, M: int, d: int) -> int:
+    return int(load().mmf_pf_predictive_workspace_bytes(int(R), int(M), int(d)))
+
+
+def pf_predictive(centres, log_a, log_b, scale_tril, truth=None, *, mean=None, covariance=None, log_score=None, pit=None,
+                  spread=None, crps=None):
+    """Closed-form scores of predictive Gaussian mixtures with one shared covariance (``mmf_pf_predictive``, include/mmf.h):
+    ``centres (..., M, d)`` -- ``R`` rows, the product of the leading sizes -- with log-weights ``log_a + log_b``, each
+    ``(..., M)`` or ``None`` (0; both ``None``: uniform), the process noise's ``scale_tril (d, d)`` and ``truth (..., d)`` or
+    ``None`` -> ``mean (..., d)``, ``covariance (..., d, d)``, ``log_score (...)``, ``pit (..., d)``, ``spread (..., d)``,
+    ``crps (..., d)``, each of which may be ``None`` (not all six); ``log_score``, ``pit`` and ``crps`` need the truth.  The
+    outputs are written in place, so a contiguous slice of a larger tensor serves.  The workspace of the partial sums is
+    allocated here, on the tensors' device, when ``spread`` or ``crps`` is asked for."""
+    lead, R, M, d = _summary_rows(centres, log_a, log_b)
+    assert tuple(scale_tril.shape) == (d, d)
+    assert truth is None or tuple(truth.shape) == lead + (d,)
+    for out, tail in ((mean, (d,)), (covariance, (d, d)), (log_score, ()), (pit, (d,)), (spread, (d,)), (crps, (d,))):
+        assert out is None or tuple(out.shape) == lead + tail
+    a = MmfPfPredictiveArgs()
+    a.R, a.M, a.d = R, M, d
+    a.centres, a.log_a, a.log_b, a.scale_tril, a.truth = vp(centres), vp(log_a), vp(log_b), vp(scale_tril), vp(truth)
+    a.mean, a.covariance, a.log_score, a.pit = vp(mean), vp(covariance), vp(log_score), vp(pit)
+    a.spread, a.crps = vp(spread), vp(crps)
+    with _on(centres):
+        pairs = spread is not None or crps is not None
+        work = _summary_workspace(a, pf_predictive_workspace_bytes(R, M, d) if pairs else 0, centres)
+        _check(load().mmf_pf_predictive(ctypes.byref(a), stream_of(centres)), "mmf_pf_predictive")
 
 
 def pf_density_workspace_bytes(R: int, M: int, d: int) -> int:

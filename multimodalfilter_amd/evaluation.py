@@ -409,6 +409,78 @@ def compare_filters(filter_a, filter_b, traj: Dict[str, torch.Tensor], *, smooth
     return estimates[0], estimates[1], filter_a.last_distance
 
 
+def forecast_filter(filter_model, traj: Dict[str, torch.Tensor], horizon: int, *, crps: bool = True,
+                    initial_cov_scale: float = 0.1, measurement_initialize: bool = False):
+    """Runs a filter over the trajectories and forecasts every step ``1 .. horizon`` steps ahead: how good is the learned
+    dynamics model on its own, ``h`` steps out, under the belief the filter really held?  The run goes through
+    ``run_filter``'s initialisation with ``record_history`` set, and the switch is put back on every path; the truth is
+    ``traj["states"][1:]``.  Returns ``(estimates, record)``: the filter's estimates ``(T, N, d)`` as ``run_filter`` returns
+    them and ``filter_model.last_forecast`` (``forecast_summary``), every array with the forecast of step ``t + h`` made at
+    ``t`` at ``[h - 1, t]`` and NaN where ``t + h > T - 1``.
+    A particle filter calls ``belief_forecast(horizon, truth, crps=crps)``: ``mean``, ``covariance``, ``error``, ``log_score``,
+    ``pit``, ``horizon`` and, with ``crps``, ``spread`` and ``crps`` of the predictive mixtures (``mmf_pf_predictive``).  An
+    extended Kalman filter calls its ``belief_forecast(horizon, truth)`` and the record is completed with the closed forms of
+    its Gaussian forecasts: ``log_score = gaussian_log_density(...)``, ``pit = Phi((y - mean) / sigma)`` and, with ``crps``,
+    ``crps = gaussian_crps(...)``; there is no ``spread``.  Every other filter is refused before the run, the trajectories
+    unread: the unscented and the fused Kalman filters keep no history to forecast from, and the LSTM baselines have no
+    belief to roll out."""
+    if isinstance(filter_model, filters.VirtualSensorUnscentedKalmanFilter):
+        raise ValueError("forecast_filter: VirtualSensorUnscentedKalmanFilter keeps no history to forecast from (its "
+                         "record_history cannot be set); forecast with the extended Kalman filter or a particle filter")
+    if not (hasattr(filter_model, "belief_forecast") and hasattr(filter_model, "record_history")):
+        why = ("keeps no history to forecast from" if hasattr(filter_model, "record_belief") else
+               "has no belief to roll out through a dynamics model")
+        raise ValueError(f"forecast_filter: {type(filter_model).__name__} {why}; forecast with a particle filter or "
+                         "VirtualSensorExtendedKalmanFilter")
+    if isinstance(horizon, bool) or not isinstance(horizon, numbers.Integral) or horizon < 1:
+        raise ValueError(f"forecast_filter: horizon must be an int >= 1, got {horizon!r}")
+    with _switched(filter_model, "record_history"):
+        est = run_filter(filter_model, traj, initial_cov_scale=initial_cov_scale, measurement_initialize=measurement_initialize)
+    truth = traj["states"][1:]
+    if hasattr(filter_model, "belief_scores"):  # (a particle filter: what _belief_kind tells the kinds apart by)
+        filter_model.belief_forecast(horizon, truth, crps=crps)
+        return est, filter_model.last_forecast
+    filter_model.belief_forecast(horizon, truth)
+    rec = filter_model.last_forecast
+    T = truth.shape[0]
+    with torch.no_grad():
+        y = truth.to(device=rec.mean.device, dtype=torch.float32)
+        rec.log_score = torch.full_like(rec.mean[..., 0], math.nan)
+        rec.pit = torch.full_like(rec.mean, math.nan)
+        if crps:
+            rec.crps = torch.full_like(rec.mean, math.nan)
+        for h in range(1, min(int(horizon), T - 1) + 1):  # (the leads beyond the data hold NaN covariances: not factorised)
+            mean, cov, true = rec.mean[h - 1, :T - h], rec.covariance[h - 1, :T - h], y[h:]
+            rec.log_score[h - 1, :T - h] = gaussian_log_density(mean, cov, true)
+            sigma = torch.sqrt(torch.diagonal(cov, dim1=-2, dim2=-1))
+            rec.pit[h - 1, :T - h] = 0.5 * torch.erfc((mean - true) / (sigma * math.sqrt(2.0)))
+            if crps:
+                rec.crps[h - 1, :T - h] = gaussian_crps(mean, cov, true)
+    return est, rec
+
+
+def forecast_summary(record, start: int = START_TRUNCATION) -> Dict[str, torch.Tensor]:
+    """Means of a forecast record (``last_forecast`` after ``belief_forecast`` with a truth; ``forecast_filter``) per lead,
+    over the finite entries of the origins ``t >= start`` and the trajectories: ``rmse (H, d)`` of ``error``, ``count (H,)``
+    the number of targets with a finite error behind each lead's figures and, where the record holds them, ``crps (H, d)``,
+    ``log_score (H,)`` and ``pit_mean (H, d)`` (0.5 for a calibrated forecast).  The targets beyond the data and the steps
+    without a live particle (NaN) are left out, like ``score_summary`` leaves them; a lead without any is NaN with count 0."""
+    if getattr(record, "horizon", None) is None or getattr(record, "error", None) is None:
+        raise ValueError("forecast_summary: the record is no forecast record with a truth (no horizon or no error); take it "
+                         "from belief_forecast(horizon, truth) or forecast_filter")
+    H = int(record.horizon)
+    per_lead = lambda x, tail: torch.stack([_finite_mean(x[h], start, tail=tail) for h in range(H)]).to(torch.float32)
+    out = {"rmse": torch.sqrt(per_lead(record.error.to(torch.float64) ** 2, 1)),
+           "count": torch.isfinite(record.error[:, start:]).all(dim=-1).sum(dim=(1, 2))}
+    if getattr(record, "crps", None) is not None:
+        out["crps"] = per_lead(record.crps, 1)
+    if getattr(record, "log_score", None) is not None:
+        out["log_score"] = per_lead(record.log_score, 0)
+    if getattr(record, "pit", None) is not None:
+        out["pit_mean"] = per_lead(record.pit, 1)
+    return out
+
+
 def _finite_mean(x: torch.Tensor, start: int, tail: int = 0) -> torch.Tensor:
     """The mean of the finite entries of ``x[start:]`` over its leading axes, accumulated in float64; the ``tail`` trailing
     axes are kept -> float64.  What every record summary below means by a mean after the burn-in."""

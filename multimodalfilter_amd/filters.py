@@ -100,6 +100,9 @@ class ParticleFilter(base.Filter):
     ``belief_distance(other=, of=, other_of=, scale=)``: two-sample distances between the recorded sets of two filters, or of
     one filter's filtered and smoothed sets -- 1-Wasserstein per dimension (returned), Cramer, Kolmogorov-Smirnov and the
     energy distance -> ``last_distance`` (``mmf_pf_distance``).
+    ``belief_forecast(horizon, truth=, crps=)``: k-step-ahead forecasts from every recorded step -- the sets rolled out through
+    the dynamics, the predictive Gaussian mixture of each lead with its mean (returned), covariance, log score, PIT and CRPS in
+    closed form -> ``last_forecast`` (``mmf_pf_predictive``).
     Randomness comes from ``self.noise`` (``utils.NoiseSource``), never from global RNG state.
     """
 
@@ -143,6 +146,7 @@ class ParticleFilter(base.Filter):
         self.last_modes = None        # belief_modes(): the modes of the recorded sets, their masses, means and members
         self.last_modalities = None   # belief_modalities(): each modality's share, evidence and own posterior on the recorded sets
         self.last_distance = None     # belief_distance(): two-sample distances between the recorded sets of two posteriors
+        self.last_forecast = None     # belief_forecast(): the k-step-ahead predictive mixtures of the recorded sets, scored
         self.record_transition_moments = False  # smooth(method="marginal") adds the two-slice residual moments to last_smoothed
         self._step_history = None
         self.use_native_loop = True   # False: forward_loop keeps the step-by-step Python loop
@@ -743,27 +747,35 @@ class ParticleFilter(base.Filter):
         dyn = self.dynamics_model
         pred = None
         if T > 1:
-            past = h.states[:-1]
             ctrl = tree_map(h.controls, lambda c: c[1:])
-            if hasattr(dyn, "propagate_encoded"):
-                ctx = dyn.encode_controls(tree_map(ctrl, lambda c: c.reshape(((T - 1) * N,) + tuple(c.shape[2:]))))
-                pred = dyn.propagate_encoded(past.reshape((T - 1) * N, M, d), ctx, None).reshape(T - 1, N, M, d)
-                tril = dyn.scale_tril()
-            else:
-                R = (T - 1) * N * M
-                rows = tree_map(ctrl, lambda c: c[:, :, None].expand((T - 1, N, M) + tuple(c.shape[2:])).reshape(
-                    (R,) + tuple(c.shape[2:])))
-                pred, trils = dyn(initial_states=past.reshape(R, d), controls=rows)
-                if not bool((trils == trils[:1]).all()):
-                    raise ValueError(f"smooth(method={method!r}) needs one process-noise scale_tril for all particles and "
-                                     "steps; this dynamics model returns state-dependent noise")
-                pred, tril = pred.reshape(T - 1, N, M, d), trils[0]
-            pred = pred.to(torch.float32).contiguous()
+            pred, tril = self._transition_means(h.states[:-1], ctrl, f"smooth(method={method!r})")
         elif hasattr(dyn, "scale_tril"):
             tril = dyn.scale_tril()
         else:  # (one step: the transition density is never evaluated)
             tril = torch.eye(d, dtype=torch.float32, device=dev)
         return pred, tril.detach().to(device=dev, dtype=torch.float32).contiguous()
+
+    def _transition_means(self, past, ctrl, who: str):
+        """``(f(X, u) (n, N, M, d) float32 contiguous, scale_tril)`` of ``n N`` particle sets ``past (n, N, M, d)`` under the
+        controls ``ctrl (n, N, ...)``, noise-free, in one call of the dynamics: K2 (``propagate_encoded``) for the built-in
+        models, ``dyn(...)`` on the ``n N M`` rows for a user model, whose state-dependent noise is the ``ValueError`` of
+        ``who``."""
+        n, N, M, d = past.shape
+        dyn = self.dynamics_model
+        if hasattr(dyn, "propagate_encoded"):
+            ctx = dyn.encode_controls(tree_map(ctrl, lambda c: c.reshape((n * N,) + tuple(c.shape[2:]))))
+            pred = dyn.propagate_encoded(past.reshape(n * N, M, d), ctx, None).reshape(n, N, M, d)
+            tril = dyn.scale_tril()
+        else:
+            R = n * N * M
+            rows = tree_map(ctrl, lambda c: c[:, :, None].expand((n, N, M) + tuple(c.shape[2:])).reshape(
+                (R,) + tuple(c.shape[2:])))
+            pred, trils = dyn(initial_states=past.reshape(R, d), controls=rows)
+            if not bool((trils == trils[:1]).all()):
+                raise ValueError(f"{who} needs one process-noise scale_tril for all particles and "
+                                 "steps; this dynamics model returns state-dependent noise")
+            pred, tril = pred.reshape(n, N, M, d), trils[0]
+        return pred.to(torch.float32).contiguous(), tril
 
     def _smooth_simulation(self, h, num_draws: int) -> torch.Tensor:
         """Backward-simulation smoothing (forward filtering, backward simulation; ``mmf_pf_smooth_simulate``,
@@ -915,6 +927,62 @@ class ParticleFilter(base.Filter):
             _abi.pf_scores(states, log_a, log_b, y, crps, energy, spread, sc)
         self.last_scores = base.belief_record(crps=crps, energy=energy, spread=spread, of=of, scale=sc)
         return crps
+
+    def belief_forecast(self, horizon: int, truth: Optional[torch.Tensor] = None, *, crps: bool = True) -> torch.Tensor:
+        """k-step-ahead forecasts from every recorded step, scored in closed form (``mmf_pf_predictive``, ``include/mmf.h``):
+        where will the state be in ``h`` steps, and how sure is the filter?  With ``T`` recorded steps, origin ``t`` and lead
+        ``h`` in ``1 .. horizon``, the target is step ``t + h <= T - 1``.  The roll-out starts from the filtered sets --
+        ``last_history.states[t]`` under ``log_weights_in[t] + log_likelihoods[t]``, what ``of="filtered"`` means elsewhere --
+        and for ``k = 1 .. h`` propagates them noise-free under the recorded controls, ``F(k) = f(X(k-1), u_{t+k})``, one call
+        of the dynamics for all ``(T - k) N`` sets (K2 for the built-in models; a user model goes through ``dyn(...)`` as in the
+        smoothers, state-dependent noise refused), then adds the process noise, ``X(k) = F(k) + eps(k) L^T``, for the leads
+        that follow.  The weights never change.  The forecast at lead ``h`` is the mixture ``sum_i W_i N(x; F(h)_i, L L^T)``:
+        the noise of the last step is not drawn but integrated, so lead 1 draws nothing.
+        Returns ``mean (H, T, N, d)``: the forecast of ``x_{t+h}`` made at ``t`` sits at ``[h - 1, t]``, NaN where ``t + h >
+        T - 1`` (``horizon >= T`` is allowed: the leads beyond the data are NaN).  Leaves ``last_forecast``: ``mean``,
+        ``covariance (H, T, N, d, d)`` (the process noise of the last step included), ``horizon`` and, with ``crps`` (the
+        ``O(M^2)`` pair pass), ``spread (H, T, N, d)``; with ``truth (T, N, d)`` also ``error`` = ``mean - truth[t + h]``,
+        ``log_score (H, T, N)``, ``pit (H, T, N, d)`` and, with ``crps``, ``crps (H, T, N, d)`` -- strictly proper scores with
+        no bandwidth, where ``belief_density`` needs a kernel density estimate.
+        Noise: ``eps(k)`` is ONE ``self.noise.gaussian(((T - k) N, M, d))`` draw per ``k``, in the order ``k = 1 .. H - 1``
+        and only while a later lead has a target (``k < min(H, T - 1)``): ``horizon = 1`` leaves the noise stream where it
+        was, a ``ReplayNoise`` holding the blocks reproduces the forecasts, and ``CounterNoise`` serves.  Memory: two sets of
+        ``(T, N, M, d)`` at a time.  Evaluation mode only; ``last_history``, ``last_smoothed`` and the other records are left
+        as they are.  The Kalman filters have a ``belief_forecast`` of their own; the unscented and fused filters and the LSTM
+        baselines keep no history and are not reached."""
+        who = "belief_forecast"
+        if isinstance(horizon, bool) or not isinstance(horizon, numbers.Integral) or horizon < 1:
+            raise ValueError(f"{who}: horizon must be an int >= 1, got {horizon!r}")
+        if self.training:
+            raise RuntimeError(f"{who}: the training (autograd) paths keep no history; call .eval() first")
+        states, log_a, log_b, y = self._summary_inputs(who, "filtered", truth, "mmf_pf_predictive serves at most {}", "None or a")
+        T, N, M, d = states.shape
+        H, dev, controls = int(horizon), states.device, self.last_history.controls
+        blank = lambda *tail: torch.full((H, T, N) + tail, math.nan, dtype=torch.float32, device=dev)
+        with torch.no_grad():
+            out = {"mean": blank(d), "covariance": blank(d, d)}
+            if crps:
+                out["spread"] = blank(d)
+            if y is not None:
+                out.update(log_score=blank(), pit=blank(d))
+                if crps:
+                    out["crps"] = blank(d)
+            X = states
+            for k in range(1, min(H, T - 1) + 1):
+                n = T - k
+                F, tril = self._transition_means(X[:n], tree_map(controls, lambda c: c[k:T]), who)
+                tril = tril.detach().to(device=dev, dtype=torch.float32).contiguous()
+                _abi.pf_predictive(F, None if log_a is None else log_a[:n], None if log_b is None else log_b[:n], tril,
+                                   None if y is None else y[k:], **{name: buf[k - 1, :n] for name, buf in out.items()})
+                if k < min(H, T - 1):
+                    eps = self.noise.gaussian((n * N, M, d), like=F)
+                    X = F + (eps @ tril.t()).reshape(n, N, M, d)
+            if y is not None:
+                out["error"] = blank(d)
+                for k in range(1, min(H, T - 1) + 1):
+                    out["error"][k - 1, :T - k] = out["mean"][k - 1, :T - k] - y[k:]
+        self.last_forecast = base.belief_record(horizon=H, **out)
+        return out["mean"]
 
     def belief_density(self, truth: Optional[torch.Tensor] = None, *, of: str = "filtered", bandwidth="silverman",
                        min_bandwidth=1e-6) -> torch.Tensor:
@@ -1288,6 +1356,7 @@ class VirtualSensorExtendedKalmanFilter(base.Filter, InnovationSwitches):
         self.record_transition_moments = False  # smooth() also leaves the two-slice residual moments
         self.last_history = None
         self.last_smoothed = None
+        self.last_forecast = None               # belief_forecast(): the k-step-ahead Gaussian forecasts of the recorded beliefs
         self._init_innovation_switches()
 
     def _record_step_belief(self):
@@ -1504,35 +1573,83 @@ class VirtualSensorExtendedKalmanFilter(base.Filter, InnovationSwitches):
         the ``(T - 1) N`` rows (chunks of ``engine.JACOBIAN_MAX_ROWS`` where the Jacobian entry limits its rows) -- K5
         (``predict_with_jacobian``) for the built-in models, ``dyn(...)`` and ``dyn.jacobian(...)`` for a user model.
         A process noise that differs over the batch is refused."""
-        T, N, d = h.means.shape
-        dev = h.means.device
+        T = h.means.shape[0]
+        return self._transition_jacobians(h.means[:max(T - 1, 0)], tree_map(h.controls, lambda c: c[1:T]), "smooth(method='rts')")
+
+    def _transition_jacobians(self, means, ctrl, who: str):
+        """``(f(m, u) (n, N, d), A (n, N, d, d), L (d, d))`` at the ``n N`` points ``means (n, N, d)`` under the controls ``ctrl
+        (n, N, ...)``, float32 on the means' device; a noise that differs over the batch is the ``ValueError`` of ``who``."""
+        n, N, d = means.shape
+        dev = means.device
         dyn = self.dynamics_model
-        R = max(T - 1, 0) * N
+        R = n * N
         if R == 0:  # (no transition: the noise is never read)
             tril = dyn.scale_tril() if hasattr(dyn, "scale_tril") else torch.eye(d)
-            return (torch.empty((max(T - 1, 0), N, d), dtype=torch.float32, device=dev),
-                    torch.empty((max(T - 1, 0), N, d, d), dtype=torch.float32, device=dev),
+            return (torch.empty((n, N, d), dtype=torch.float32, device=dev),
+                    torch.empty((n, N, d, d), dtype=torch.float32, device=dev),
                     tril.detach().to(device=dev, dtype=torch.float32).contiguous())
-        past = h.means[:T - 1].reshape(R, d).to(torch.float32).contiguous()
-        rows = tree_map(h.controls, lambda c: c[1:T].reshape((R,) + tuple(c.shape[2:])))
+        past = means.reshape(R, d).to(torch.float32).contiguous()
+        rows = tree_map(ctrl, lambda c: c.reshape((R,) + tuple(c.shape[2:])))
         preds, jacs, tril = [], [], None
         for r0 in range(0, R, engine.JACOBIAN_MAX_ROWS):
             sl = slice(r0, min(r0 + engine.JACOBIAN_MAX_ROWS, R))
-            ctrl = tree_map(rows, lambda c: c[sl])
+            ctrl_rows = tree_map(rows, lambda c: c[sl])
             if hasattr(dyn, "predict_with_jacobian"):
-                x, J, tril = dyn.predict_with_jacobian(past[sl], dyn.encode_controls(ctrl))
+                x, J, tril = dyn.predict_with_jacobian(past[sl], dyn.encode_controls(ctrl_rows))
             else:
-                x, trils = dyn(initial_states=past[sl], controls=ctrl)
-                J = dyn.jacobian(initial_states=past[sl], controls=ctrl)
+                x, trils = dyn(initial_states=past[sl], controls=ctrl_rows)
+                J = dyn.jacobian(initial_states=past[sl], controls=ctrl_rows)
                 if (tril is not None and not bool((trils == tril).all())) or not bool((trils == trils[:1]).all()):
-                    raise ValueError("smooth(method='rts') needs one process-noise scale_tril for all trajectories and steps; "
+                    raise ValueError(f"{who} needs one process-noise scale_tril for all trajectories and steps; "
                                      "this dynamics model returns noise that differs over the batch")
                 tril = trils[0]
             preds.append(x.detach())
             jacs.append(J.detach())
         x, J = (preds[0], jacs[0]) if len(preds) == 1 else (torch.cat(preds), torch.cat(jacs))
-        return (x.to(torch.float32).reshape(T - 1, N, d).contiguous(), J.to(torch.float32).reshape(T - 1, N, d, d).contiguous(),
+        return (x.to(torch.float32).reshape(n, N, d).contiguous(), J.to(torch.float32).reshape(n, N, d, d).contiguous(),
                 tril.detach().to(device=dev, dtype=torch.float32).contiguous())
+
+    def belief_forecast(self, horizon: int, truth: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """k-step-ahead forecasts from every recorded step, the record of ``ParticleFilter.belief_forecast`` for a Gaussian
+        belief: with ``T`` recorded steps, origin ``t`` and lead ``h`` in ``1 .. horizon``, the filtered belief ``(means[t],
+        covariances[t])`` of ``last_history`` goes through the extended prediction ``h`` times under the recorded controls --
+        ``m <- f(m, u_{t+k})``, ``P <- A P A^T + L L^T`` with ``A`` the Jacobian at ``m`` -- one batched call of the dynamics per
+        ``k`` over the ``(T - k) N`` beliefs (``predict_with_jacobian`` in chunks of ``engine.JACOBIAN_MAX_ROWS``, or ``dyn()``
+        and ``dyn.jacobian()`` for a user model, as the smoother evaluates them), the covariances in torch ops.  Returns ``mean
+        (H, T, N, d)`` with the forecast of ``x_{t+h}`` made at ``t`` at ``[h - 1, t]`` and NaN where ``t + h > T - 1``; leaves
+        ``last_forecast``: ``mean``, ``covariance (H, T, N, d, d)``, ``horizon`` and, with ``truth (T, N, d)``, ``error`` =
+        ``mean - truth[t + h]`` (``evaluation.forecast_filter`` adds the Gaussian closed forms of the scores).  No noise is
+        drawn; evaluation mode only; ``last_history`` and ``last_smoothed`` are left as they are.  The unscented filter keeps
+        no history and answers so; the fused filters and the LSTM baselines have no such method."""
+        who = "belief_forecast"
+        if isinstance(horizon, bool) or not isinstance(horizon, numbers.Integral) or horizon < 1:
+            raise ValueError(f"{who}: horizon must be an int >= 1, got {horizon!r}")
+        if self.training:
+            raise RuntimeError(f"{who}: the training (autograd) paths keep no history; call .eval() first")
+        h = self.last_history
+        if h is None:
+            raise ValueError(f"{who} needs a history: set record_history and run forward_loop (evaluation mode) first")
+        T, N, d = h.means.shape
+        if truth is not None and (not isinstance(truth, torch.Tensor) or tuple(truth.shape) != (T, N, d)):
+            raise ValueError(f"{who}: truth must be None or a (T, N, d) = ({T}, {N}, {d}) tensor, got "
+                             f"{tuple(truth.shape) if isinstance(truth, torch.Tensor) else type(truth).__name__}")
+        H, dev = int(horizon), h.means.device
+        blank = lambda *tail: torch.full((H, T, N) + tail, math.nan, dtype=torch.float32, device=dev)
+        with torch.no_grad():
+            out = {"mean": blank(d), "covariance": blank(d, d)}
+            m, P = h.means.to(torch.float32), h.covariances.to(torch.float32)
+            for k in range(1, min(H, T - 1) + 1):
+                n = T - k
+                m, A, tril = self._transition_jacobians(m[:n], tree_map(h.controls, lambda c: c[k:T]), who)
+                P = A @ P[:n] @ A.transpose(-1, -2) + tril @ tril.t()
+                out["mean"][k - 1, :n], out["covariance"][k - 1, :n] = m, P
+            if truth is not None:
+                y = truth.detach().to(device=dev, dtype=torch.float32)
+                out["error"] = blank(d)
+                for k in range(1, min(H, T - 1) + 1):
+                    out["error"][k - 1, :T - k] = out["mean"][k - 1, :T - k] - y[k:]
+        self.last_forecast = base.belief_record(horizon=H, **out)
+        return out["mean"]
 
 
 # ------------------------------------------------------------------------------ unscented filter
