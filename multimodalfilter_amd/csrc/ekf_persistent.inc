@@ -80,7 +80,7 @@ __device__ __forceinline__ void jacobian_tile(const float* __restrict__ lds, con
   }
   Act<1> X, H;
   first_layer<1>(lds, b0, X, lane);
-  short2v amax = {0, 0};
+  half2v amax = {0, 0};
   if constexpr (F16) seed_nonfinite<1>(b0, amax);
   net_unpipelined<1, NRES, kJacobian, PREC>(lds, X, H, [&](Act<1>& acc) {
     join_init<1>(acc, 0, load_join_row(traj_bias_row, lane), primal);

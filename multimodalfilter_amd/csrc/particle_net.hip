@@ -138,7 +138,7 @@ __device__ __forceinline__ void act_tile(Act<CT>& a) {
 
 // rows of tile T -> k-steps 2T, 2T + 1 of the next layer's operand (split_act's arithmetic, one row tile)
 template <int CT, int T, bool SIGNED>
-__device__ __forceinline__ void split_tile(const Act<CT>& x, SplitAct<CT>& o, float neg_one, short2v& amax) {
+__device__ __forceinline__ void split_tile(const Act<CT>& x, SplitAct<CT>& o, float neg_one, half2v& amax) {
 #pragma unroll
   for (int u = 0; u < 2; ++u)
 #pragma unroll
@@ -152,15 +152,11 @@ __device__ __forceinline__ void split_tile(const Act<CT>& x, SplitAct<CT>& o, fl
         ll[p] = b;
       }
       constexpr unsigned kMask = SIGNED ? 0x7fff7fffu : 0xffffffffu;
-      const short2v m01 = __builtin_elementwise_max(__builtin_bit_cast(short2v, hh[0] & kMask), __builtin_bit_cast(short2v, hh[1] & kMask));
-      const short2v m23 = __builtin_elementwise_max(__builtin_bit_cast(short2v, hh[2] & kMask), __builtin_bit_cast(short2v, hh[3] & kMask));
-      amax = __builtin_elementwise_max(amax, __builtin_elementwise_max(m01, m23));
+      amax = range_fold(amax, hh[0] & kMask, hh[1] & kMask, hh[2] & kMask, hh[3] & kMask);
       o.hi[2 * T + u][c] = __builtin_bit_cast(half8, hh);
       o.lo[2 * T + u][c] = __builtin_bit_cast(half8, ll);
     }
-  unsigned pin = __builtin_bit_cast(unsigned, amax);  // see split_act
-  asm volatile("" : "+v"(pin));
-  amax = __builtin_bit_cast(short2v, pin);
+  range_pin(amax);
 }
 
 template <int CT, int G>
@@ -191,7 +187,7 @@ __device__ __forceinline__ void pin_small_region() {
 // activated (what the head reads).  `join_init(acc)`: writes the per-trajectory term of the join layer.
 template <int CT, int NRES, int KIND, class JoinInit>
 __device__ __forceinline__ void rowpipe_net_f16(const float* __restrict__ lds, Act<CT>& X, Act<CT>& H, SplitAct<CT>& SP,
-                                                JoinInit&& join_init, int lane, float neg_one, short2v& amax) {
+                                                JoinInit&& join_init, int lane, float neg_one, half2v& amax) {
   constexpr int NL = 3 + 2 * NRES;
   const int h = lane >> 5;
   const float* layers = lds + off_layers();
@@ -747,7 +743,7 @@ __global__ __launch_bounds__(WPS * 256, WPS) void particle_net_kernel(std::condi
       i_next = claim(i_next);
     }
     first_layer<CT>(lds, bcur, X, lane);
-    short2v amax = {0, 0};  // f16x3: largest hi halves handed to the MFMAs in this tile
+    half2v amax = {0, 0};  // f16x3: largest hi halves handed to the MFMAs in this tile
     if constexpr (F16) seed_nonfinite<CT>(bcur, amax);
     if constexpr (PIPE) {
       constexpr int NL = 3 + 2 * NRES;  // 64x64 layers: encoder block, join, NRES trunk blocks

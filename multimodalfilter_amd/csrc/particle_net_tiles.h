@@ -164,8 +164,10 @@ __device__ __forceinline__ float relu1(float v) {
 // that a NaN / inf input reaches the next operand split and raises the flag there (0x7C00 / 0x7E00 >= 0x7BFF),
 // and every later ReLU clamps whatever those produce.
 __device__ __forceinline__ float relu_sat(float v) { return __builtin_amdgcn_fmed3f(v, 0.f, kF16SplitMax); }
-// ReLU that keeps a NaN of EITHER sign (relu1 turns a negative NaN into 0): compare + select, used once per network
-__device__ __forceinline__ float relu_keepnan(float v) { return v <= 0.f ? 0.f : v; }
+// ReLU that keeps a NaN of EITHER sign (relu1 turns a negative NaN into 0), used once per network: IEEE-754 maximum
+// propagates a NaN operand and orders -0 below +0, so maximum(v, 0) is v <= 0 ? +0 : v for every number and a NaN for
+// every NaN -- ONE v_maximum3_f32 v, v, 0, 0 on gfx950, where the compare + select took two instructions
+__device__ __forceinline__ float relu_keepnan(float v) { return __builtin_elementwise_maximum(v, 0.f); }
 // signed operands (dynamics trunk entry, Jacobian tangents): saturate both ways; a NaN becomes -65504 (flagged)
 __device__ __forceinline__ float clamp_sat(float v) { return __builtin_amdgcn_fmed3f(v, -kF16SplitMax, kF16SplitMax); }
 
@@ -243,16 +245,36 @@ __device__ __forceinline__ void split_pair(float x0, float x1, float neg_one, un
 }
 
 // Range tracking on the packed hi halves: round-to-nearest maps every |x| >= 65504 to 0x7BFF or to
-// +inf (0x7C00), both >= the threshold below, and for non-negative halves the i16 order is the f16 order, so ONE
-// v_pk_max_i16 per pair keeps the running maximum (fmaxf on the fp32 values costs 3 ops per
-// pair once canonicalisation is counted).  Negative halves compare below zero and are ignored,
-// which is right after a ReLU; the one split that sees signed values (dynamics trunk entry, no
-// ReLU after the join layer) passes SIGNED and masks the sign bits first.
+// +inf (0x7C00), both >= the threshold below.  The running maximum is kept AS f16, with the IEEE-754 maximum of three
+// packed operands (v_pk_maximum3_f16): two instructions fold a fragment's four registers (eight halves) into it, half
+// of what one two-operand maximum per pair costs (fmaxf on the fp32 values costs 3 ops per pair once canonicalisation
+// is counted).  Negative halves and -0 lose against the running value, which starts at +0 -- right after a ReLU; the
+// one split that sees signed values (dynamics trunk entry, no ReLU after the join layer) passes SIGNED and masks the
+// sign bits first.  A NaN half of either sign propagates through every later link, so the test at the end of the tile
+// (range_saturated) looks at the magnitude bits: there the i16 order is the f16 order, with every NaN on top.
 using short2v = __attribute__((ext_vector_type(2))) short;
 constexpr short kF16Saturated = 0x7BFF;  // also below +inf (0x7C00) and every NaN pattern
 
+// one fragment's four hi registers folded into the running maximum: a three-way maximum beside the chain, one link on it
+__device__ __forceinline__ half2v range_fold(half2v amax, unsigned h0, unsigned h1, unsigned h2, unsigned h3) {
+  const half2v m = __builtin_elementwise_maximum(
+      __builtin_elementwise_maximum(__builtin_bit_cast(half2v, h0), __builtin_bit_cast(half2v, h1)), __builtin_bit_cast(half2v, h2));
+  return __builtin_elementwise_maximum(__builtin_elementwise_maximum(amax, m), __builtin_bit_cast(half2v, h3));
+}
+// Pin the running maximum (no instruction is emitted): left alone, the compiler sinks every v_pk_maximum3_f16 to the
+// flag test at the end of the tile and keeps the hi fragments of all seven layers alive for it -- in scratch.
+__device__ __forceinline__ void range_pin(half2v& amax) {
+  unsigned pin = __builtin_bit_cast(unsigned, amax);
+  asm volatile("" : "+v"(pin));
+  amax = __builtin_bit_cast(half2v, pin);
+}
+__device__ __forceinline__ bool range_saturated(half2v amax) {
+  const short2v m = __builtin_bit_cast(short2v, __builtin_bit_cast(unsigned, amax) & 0x7fff7fffu);  // a NaN of either sign counts
+  return m[0] >= kF16Saturated || m[1] >= kF16Saturated;
+}
+
 template <int CT, bool SIGNED = false>
-__device__ __forceinline__ void split_act(const Act<CT>& x, SplitAct<CT>& o, float neg_one, short2v& amax) {
+__device__ __forceinline__ void split_act(const Act<CT>& x, SplitAct<CT>& o, float neg_one, half2v& amax) {
 #pragma unroll
   for (int tp = 0; tp < 2; ++tp)
 #pragma unroll
@@ -267,22 +289,12 @@ __device__ __forceinline__ void split_act(const Act<CT>& x, SplitAct<CT>& o, flo
           h[p] = hh;
           l[p] = ll;
         }
-        // a short tree per fragment, then one link of the running chain
         constexpr unsigned kMask = SIGNED ? 0x7fff7fffu : 0xffffffffu;
-        const short2v m01 = __builtin_elementwise_max(__builtin_bit_cast(short2v, h[0] & kMask),
-                                                      __builtin_bit_cast(short2v, h[1] & kMask));
-        const short2v m23 = __builtin_elementwise_max(__builtin_bit_cast(short2v, h[2] & kMask),
-                                                      __builtin_bit_cast(short2v, h[3] & kMask));
-        amax = __builtin_elementwise_max(amax, __builtin_elementwise_max(m01, m23));
+        amax = range_fold(amax, h[0] & kMask, h[1] & kMask, h[2] & kMask, h[3] & kMask);
         o.hi[2 * tp + u][c] = __builtin_bit_cast(half8, h);
         o.lo[2 * tp + u][c] = __builtin_bit_cast(half8, l);
       }
-  // Pin the running maximum here (no instruction is emitted): left alone, the compiler sinks
-  // every v_pk_max_i16 to the flag test at the end of the tile and keeps the hi fragments of
-  // all seven layers alive for it -- in scratch.
-  unsigned pin = __builtin_bit_cast(unsigned, amax);
-  asm volatile("" : "+v"(pin));
-  amax = __builtin_bit_cast(short2v, pin);
+  range_pin(amax);
 }
 
 template <int CT>
@@ -310,7 +322,7 @@ __device__ __forceinline__ void mfma_layer_f16(const float* __restrict__ Wl, con
 template <int CT, bool SIGNED = false, bool JAC = false>
 __device__ __forceinline__ void res_block_f16(const float* __restrict__ lds, int n_res, int l1,
                                               Act<CT>& x, Act<CT>& hbuf, SplitAct<CT>& sp, int lane,
-                                              float neg_one, short2v& amax, bool primal = true) {
+                                              float neg_one, half2v& amax, bool primal = true) {
   const int h = lane >> 5;
   const float bs = (JAC && !primal) ? 0.f : 1.f;
   if constexpr (SIGNED) saturate<CT>(x);  // no ReLU in front of this split: saturate the signed values themselves
@@ -360,7 +372,7 @@ __device__ __forceinline__ void saturate_half(Act<2>& a) {
 }
 
 template <int C, bool SIGNED>
-__device__ __forceinline__ void split_half(const Act<2>& x, SplitAct<2>& o, float neg_one, short2v& amax) {
+__device__ __forceinline__ void split_half(const Act<2>& x, SplitAct<2>& o, float neg_one, half2v& amax) {
 #pragma unroll
   for (int tp = 0; tp < 2; ++tp)
 #pragma unroll
@@ -374,17 +386,11 @@ __device__ __forceinline__ void split_half(const Act<2>& x, SplitAct<2>& o, floa
         l[p] = ll;
       }
       constexpr unsigned kMask = SIGNED ? 0x7fff7fffu : 0xffffffffu;
-      const short2v m01 = __builtin_elementwise_max(__builtin_bit_cast(short2v, h[0] & kMask),
-                                                    __builtin_bit_cast(short2v, h[1] & kMask));
-      const short2v m23 = __builtin_elementwise_max(__builtin_bit_cast(short2v, h[2] & kMask),
-                                                    __builtin_bit_cast(short2v, h[3] & kMask));
-      amax = __builtin_elementwise_max(amax, __builtin_elementwise_max(m01, m23));
+      amax = range_fold(amax, h[0] & kMask, h[1] & kMask, h[2] & kMask, h[3] & kMask);
       o.hi[2 * tp + u][C] = __builtin_bit_cast(half8, h);
       o.lo[2 * tp + u][C] = __builtin_bit_cast(half8, l);
     }
-  unsigned pin = __builtin_bit_cast(unsigned, amax);  // see split_act
-  asm volatile("" : "+v"(pin));
-  amax = __builtin_bit_cast(short2v, pin);
+  range_pin(amax);
 }
 
 template <int C, bool ADD>
@@ -396,6 +402,9 @@ __device__ __forceinline__ void bias_half(const float* __restrict__ bl, Act<2>& 
       const f32x4 b = *reinterpret_cast<const f32x4*>(bl + 32 * t + 8 * g + 4 * h);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
+        // ADD, the skip + bias, stays one v_add_f32 per element here: in pairs (add_bias_packed's v_pk_add_f32) the
+        // compiler takes a third of them apart again under the MFMAs, the run-table kernels grow by four registers and
+        // the step measured no faster -- with the pairs slower than without (profiles/k2_vector/README.md)
         if (ADD) acc.v[t][C][4 * g + e] += b[e];
         else acc.v[t][C][4 * g + e] = b[e];
       }
@@ -477,13 +486,13 @@ __device__ __forceinline__ void first_layer(const float* __restrict__ lds, const
 // f16x3: a NaN / inf particle state.  The first layer's exact-f32 MFMAs turn it into NaNs of either sign, and a
 // negative NaN would pass the ReLU as 0 -- report the input itself (a handful of compares per tile).
 template <int CT, int KS0>
-__device__ __forceinline__ void seed_nonfinite(const float (&b)[KS0][CT], short2v& amax) {
+__device__ __forceinline__ void seed_nonfinite(const float (&b)[KS0][CT], half2v& amax) {
   bool bad = false;
 #pragma unroll
   for (int s = 0; s < KS0; ++s)
 #pragma unroll
     for (int c = 0; c < CT; ++c) bad |= !(fabsf(b[s][c]) <= 3.0e38f);
-  if (bad) amax = short2v{0x7fff, 0x7fff};
+  if (bad) amax = __builtin_bit_cast(half2v, 0x7fff7fffu);  // a NaN: every later link of the chain keeps it
 }
 
 // The join layer's accumulator starts from the hoisted per-trajectory term: the lane's 32 features of one (N, 64) row.
@@ -515,7 +524,7 @@ __device__ __forceinline__ void join_init(Act<CT>& acc, int c, const JoinRow& r,
 // Same contract as rowpipe_net_f16 (particle_net.hip), which computes the same bits on another schedule.
 template <int CT, int NRES, int KIND, int PREC, class Join>
 __device__ __forceinline__ void net_unpipelined(const float* __restrict__ lds, Act<CT>& X, Act<CT>& H, Join&& join, int lane,
-                                                float neg_one, short2v& amax, bool primal) {
+                                                float neg_one, half2v& amax, bool primal) {
   constexpr bool JAC = KIND == kJacobian, F16 = PREC == MMF_PREC_F16X3;
   SplitAct<F16 ? CT : 0> SP;
   relu<CT, JAC>(X, primal);
@@ -558,8 +567,8 @@ __device__ __forceinline__ void net_unpipelined(const float* __restrict__ lds, A
 // f16x3: an operand beyond the f16 range cannot be split exactly.  Inner activations saturate at 65504 (relu_sat,
 // hi = 0x7BFF), a non-finite state or per-trajectory term arrives as hi = inf / NaN (>= 0x7C00) and is clamped by the
 // next relu_sat -- either way the tile's outputs stay finite and the flag says they are invalid (engine.check_range).
-__device__ __forceinline__ void report_range(int* range_flag, short2v amax) {
-  if (range_flag != nullptr && (amax[0] >= kF16Saturated || amax[1] >= kF16Saturated)) atomicOr(range_flag, MMF_FLAG_RANGE);
+__device__ __forceinline__ void report_range(int* range_flag, half2v amax) {
+  if (range_flag != nullptr && range_saturated(amax)) atomicOr(range_flag, MMF_FLAG_RANGE);
 }
 
 // head (64 -> NOUT) on the VALU, bias not included: each lane holds 32 of the 64 features of its columns, the two lane

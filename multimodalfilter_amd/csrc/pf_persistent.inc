@@ -188,7 +188,7 @@ __device__ __forceinline__ bool small_tile(const float* __restrict__ lds, const 
   if (a.stamps && lane == 0) a.stamps[1] = persist_clock();
   Act<1> X, H;
   first_layer<1>(lds, b0, X, lane);
-  short2v amax = {0, 0};
+  half2v amax = {0, 0};
   if constexpr (F16) seed_nonfinite<1>(b0, amax);
   auto join = [&](Act<1>& acc) {
 #pragma unroll
