@@ -6,8 +6,8 @@
 //     keys    (order-preserving uint32 of the coordinate) << 32 | set bit | q, one uint64 per live particle of BOTH sets in
 //             LDS; a particle with q = 0 (its state row is not read) and every padding slot take the all-ones key; padded to
 //             P = 2^k >= max(Ma + Mb, 64)
-//     sort    the bitonic sort of pf_quantiles.hip, restated (that file keeps its device pieces to itself): a thread owns
-//             E = P / THREADS consecutive slots, the strides below E run in its registers, slot i lives at i + i / E
+//     sort    the bitonic sort of pf_sort.h (its plan, slots and register stages; the body's text is here) for Ma + Mb slots:
+//             a thread ends with its E = P / THREADS consecutive sorted slots in registers
 //     scans   two integer scans in sorted order, one per set, selected by the set bit
 //     gaps    one pass over the gaps between live neighbours: F_a - F_b from the two integer sums divided once in double,
 //             max for ks, the block_sum order of pf_summary.h for the two sums
@@ -20,16 +20,15 @@
 
 #include <cmath>
 
-#include "pf_summary.h"
+#include "pf_sort.h"
 
 namespace {
 
 namespace summary = mmf::summary;
-using u64 = unsigned long long;
+namespace sort = mmf::sort;
+using sort::u64;
 
 // ================================================================================================ the CDF kernel
-constexpr int kSortWaves = 4;
-constexpr u64 kPadKey = 0xFFFFFFFF00000000ull;
 constexpr unsigned kSetB = 0x80000000u;   // the set bit: below the key, above q <= 2^24
 constexpr unsigned kQMask = 0x01FFFFFFu;
 
@@ -40,78 +39,13 @@ struct CArgs {
   int Ma, Mb, d;
 };
 
-// threads and slots per thread of the workgroup that sorts M = Ma + Mb slots: pf_quantiles.hip's plan (one wave up to
-// P = 512, 256 threads beyond) and its padding slot after every run of E
-struct SortPlan {
-  int threads, E;
-};
-inline SortPlan sort_plan_of(int M) {
-  int P = MMF_WAVE;
-  while (P < M) P <<= 1;
-  const int threads = P <= 8 * MMF_WAVE ? MMF_WAVE : 256;
-  return {threads, P / threads};
-}
-inline size_t slots_of(const SortPlan& p) {
-  return static_cast<size_t>(p.threads) * p.E + (p.E > 1 ? p.threads : 0);
-}
-
-// a total order on the bit patterns that agrees with < on the numbers: negatives inverted, the others with the sign bit set
-__device__ __forceinline__ unsigned key_of(float x) {
-  const unsigned b = __float_as_uint(x);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float value_of(unsigned k) {
-  return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
-}
-
-template <int E>
-__device__ __forceinline__ int slot(int i) {
-  return E > 1 ? i + i / E : i;
-}
-
-// inclusive scan of per-thread values below 2^40 over the workgroup, and its total
-template <int THREADS>
-__device__ __forceinline__ u64 block_scan(u64 v, u64* scratch, int tid, u64& total) {
-  const int lane = tid & (MMF_WAVE - 1), wave = tid / MMF_WAVE;
-  u64 incl = mmf::wave_inclusive_scan(v, lane);
-  if (lane == MMF_WAVE - 1) scratch[wave] = incl;
-  __syncthreads();
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < THREADS / MMF_WAVE; ++w) {
-    const u64 t = scratch[w];
-    if (w < wave) incl += t;
-    total += t;
-  }
-  __syncthreads();
-  return incl;
-}
-
-// the stages of phase k whose stride is jmax, jmax / 2, .. 1, all below E: inside the E consecutive slots from `base`
-template <int E>
-__device__ __forceinline__ void local_stages(u64 (&v)[E], int base, int k, int jmax) {
-#pragma unroll
-  for (int j = E / 2; j >= 1; j >>= 1) {
-    if (j > jmax) continue;
-#pragma unroll
-    for (int l = 0; l < E; ++l) {
-      if (l & j) continue;
-      const bool up = ((base + l) & k) == 0;
-      const u64 lo = v[l], hi = v[l + j];
-      const bool swap = (lo > hi) == up;
-      v[l] = swap ? hi : lo;
-      v[l + j] = swap ? lo : hi;
-    }
-  }
-}
-
 template <int THREADS, int E>
 __global__ __launch_bounds__(THREADS) void pf_distance_cdf_kernel(CArgs a) {
   extern __shared__ u64 lds[];
-  __shared__ u64 wave_tot[kSortWaves];
-  __shared__ float wave_top[2][kSortWaves];
-  __shared__ double wave_sum[kSortWaves][2];
-  constexpr int P = THREADS * E, kWaves = THREADS / MMF_WAVE;
+  __shared__ u64 wave_tot[sort::kMaxWaves];
+  __shared__ float wave_top[2][sort::kMaxWaves];
+  __shared__ double wave_sum[sort::kMaxWaves][2];
+  constexpr int kWaves = THREADS / MMF_WAVE;
   const int tid = threadIdx.x, Ma = a.Ma, M = a.Ma + a.Mb, d = a.d;
   const int r = blockIdx.x / d, k = blockIdx.x - r * d;
   const size_t row_a = static_cast<size_t>(r) * Ma, row_b = static_cast<size_t>(r) * a.Mb;
@@ -140,32 +74,31 @@ __global__ __launch_bounds__(THREADS) void pf_distance_cdf_kernel(CArgs a) {
 #pragma unroll
   for (int u = 0; u < E; ++u) {
     const int m = tid + u * THREADS;
-    u64 packed = kPadKey;
+    u64 packed = sort::kPadKey;
     if (m < M) {
       const bool in_a = m < Ma;
-      const float t = av[u] - (in_a ? top_a : top_b);
-      const float e = expf(t);
-      const unsigned q = t <= 0.f ? static_cast<unsigned>(floorf(e * 16777216.0f)) : 0u;  // (the live-weight rule: a NaN t: 0)
+      const unsigned q = sort::fixed_weight(av[u] - (in_a ? top_a : top_b));
       if (q > 0u) {  // (a dead particle's state row is not read)
         const float xv = in_a ? xa[static_cast<size_t>(m) * d] : xb[static_cast<size_t>(m - Ma) * d];
-        packed = (static_cast<u64>(key_of(xv)) << 32) | (in_a ? 0u : kSetB) | q;
+        packed = (static_cast<u64>(sort::key_of(xv)) << 32) | (in_a ? 0u : kSetB) | q;
       }
     }
-    lds[slot<E>(m)] = packed;
+    lds[sort::slot<E>(m)] = packed;
   }
 
-  // ---- bitonic sort, ascending
+  // ---- bitonic sort, ascending (pf_sort.h: one textual copy here and in pf_quantiles.hip)
+  constexpr int P = THREADS * E;
   const int base = tid * E;
   u64 v[E];
   __syncthreads();
   if constexpr (E > 1) {
 #pragma unroll
-    for (int l = 0; l < E; ++l) v[l] = lds[slot<E>(base) + l];
+    for (int l = 0; l < E; ++l) v[l] = lds[sort::slot<E>(base) + l];
 #pragma unroll
-    for (int kk = 2; kk <= E; kk <<= 1) local_stages<E>(v, base, kk, kk / 2);
+    for (int kk = 2; kk <= E; kk <<= 1) sort::local_stages<E>(v, base, kk, kk / 2);
     for (int kk = 2 * E; kk <= P; kk <<= 1) {
 #pragma unroll
-      for (int l = 0; l < E; ++l) lds[slot<E>(base) + l] = v[l];
+      for (int l = 0; l < E; ++l) lds[sort::slot<E>(base) + l] = v[l];
       __syncthreads();
       for (int j = kk / 2; j >= E; j >>= 1) {
 #pragma unroll
@@ -173,17 +106,17 @@ __global__ __launch_bounds__(THREADS) void pf_distance_cdf_kernel(CArgs a) {
           const int p = tid + u * THREADS;
           const int i = 2 * p - (p & (j - 1));  // pair p of stride j: 2 j (p / j) + p % j
           const bool up = (i & kk) == 0;
-          const u64 lo = lds[slot<E>(i)], hi = lds[slot<E>(i + j)];
+          const u64 lo = lds[sort::slot<E>(i)], hi = lds[sort::slot<E>(i + j)];
           if ((lo > hi) == up) {
-            lds[slot<E>(i)] = hi;
-            lds[slot<E>(i + j)] = lo;
+            lds[sort::slot<E>(i)] = hi;
+            lds[sort::slot<E>(i + j)] = lo;
           }
         }
         __syncthreads();
       }
 #pragma unroll
-      for (int l = 0; l < E; ++l) v[l] = lds[slot<E>(base) + l];
-      local_stages<E>(v, base, kk, E / 2);
+      for (int l = 0; l < E; ++l) v[l] = lds[sort::slot<E>(base) + l];
+      sort::local_stages<E>(v, base, kk, E / 2);
     }
   } else {
     for (int kk = 2; kk <= P; kk <<= 1)
@@ -212,13 +145,13 @@ __global__ __launch_bounds__(THREADS) void pf_distance_cdf_kernel(CArgs a) {
     mine_b += (lo & kSetB) ? q : 0ull;
   }
   u64 Qa, Qb;
-  u64 ca = block_scan<THREADS>(mine_a, wave_tot, tid, Qa) - mine_a;
-  u64 cb = block_scan<THREADS>(mine_b, wave_tot, tid, Qb) - mine_b;  // (its closing barrier: every thread has its run)
+  u64 ca = sort::block_scan<THREADS>(mine_a, wave_tot, tid, Qa) - mine_a;
+  u64 cb = sort::block_scan<THREADS>(mine_b, wave_tot, tid, Qb) - mine_b;  // (its closing barrier: every thread has its run)
 
   // ---- the slot after this thread's run
   lds[tid] = v[0];
   __syncthreads();
-  const u64 after = tid + 1 < THREADS ? lds[tid + 1] : kPadKey;
+  const u64 after = tid + 1 < THREADS ? lds[tid + 1] : sort::kPadKey;
 
   const size_t out = static_cast<size_t>(r) * d + k;
   if (Qa == 0 || Qb == 0) {  // a set without a live particle
@@ -243,7 +176,7 @@ __global__ __launch_bounds__(THREADS) void pf_distance_cdf_kernel(CArgs a) {
     cb += (lo & kSetB) ? q : 0ull;
     const unsigned key = static_cast<unsigned>(cur >> 32), key_next = static_cast<unsigned>(nxt >> 32);
     if (key != 0xFFFFFFFFu && key_next != 0xFFFFFFFFu) {
-      const double gap = static_cast<double>(value_of(key_next)) - static_cast<double>(value_of(key));
+      const double gap = static_cast<double>(sort::value_of(key_next)) - static_cast<double>(sort::value_of(key));
       const double delta = static_cast<double>(ca) / qa - static_cast<double>(cb) / qb;
       const double ad = fabs(delta);
       s[0] += gap * ad;
@@ -261,30 +194,13 @@ __global__ __launch_bounds__(THREADS) void pf_distance_cdf_kernel(CArgs a) {
   }
 }
 
-template <int THREADS, int E>
-int run_cdf(const CArgs& k, unsigned grid, size_t lds_bytes, hipStream_t s) {
-  return mmf::launch(pf_distance_cdf_kernel<THREADS, E>, grid, THREADS, lds_bytes, s, k);
-}
-
 int launch_cdf(const CArgs& k, int R, hipStream_t s) {
   const unsigned grid = static_cast<unsigned>(R) * static_cast<unsigned>(k.d);
-  const SortPlan p = sort_plan_of(k.Ma + k.Mb);
-  const size_t lds_bytes = slots_of(p) * sizeof(u64);
-  if (p.threads == MMF_WAVE) {
-    switch (p.E) {
-      case 1: return run_cdf<MMF_WAVE, 1>(k, grid, lds_bytes, s);
-      case 2: return run_cdf<MMF_WAVE, 2>(k, grid, lds_bytes, s);
-      case 4: return run_cdf<MMF_WAVE, 4>(k, grid, lds_bytes, s);
-      default: return run_cdf<MMF_WAVE, 8>(k, grid, lds_bytes, s);
-    }
-  }
-  switch (p.E) {
-    case 4: return run_cdf<256, 4>(k, grid, lds_bytes, s);
-    case 8: return run_cdf<256, 8>(k, grid, lds_bytes, s);
-    case 16: return run_cdf<256, 16>(k, grid, lds_bytes, s);
-    case 32: return run_cdf<256, 32>(k, grid, lds_bytes, s);
-    default: return run_cdf<256, 64>(k, grid, lds_bytes, s);
-  }
+  const sort::Plan p = sort::plan_of(k.Ma + k.Mb);
+  return sort::with_plan(p, [&](auto T, auto E) {
+    constexpr int kT = decltype(T)::value, kE = decltype(E)::value;
+    return mmf::launch(pf_distance_cdf_kernel<kT, kE>, grid, kT, sort::slots_of(p) * sizeof(u64), s, k);
+  });
 }
 
 // ================================================================================================ the pair kernel
@@ -498,7 +414,7 @@ inline int clamp_m(int M) { return M < 1 ? 1 : M > summary::kMaxM ? summary::kMa
 extern "C" size_t mmf_pf_distance_lds_bytes(int Ma, int Mb) {
   if (Ma < 1 || Mb < 1) return 0;
   const long long M = static_cast<long long>(Ma) + Mb;
-  return slots_of(sort_plan_of(M > summary::kMaxM ? summary::kMaxM : static_cast<int>(M))) * sizeof(u64);
+  return sort::slots_of(sort::plan_of(M > summary::kMaxM ? summary::kMaxM : static_cast<int>(M))) * sizeof(u64);
 }
 
 extern "C" size_t mmf_pf_distance_workspace_bytes(int R, int Ma, int Mb, int d) {
@@ -511,8 +427,7 @@ extern "C" size_t mmf_pf_distance_workspace_bytes(int R, int Ma, int Mb, int d) 
 extern "C" int mmf_pf_distance(const MmfPfDistanceArgs* a, void* stream) {
   if (!a || summary::check_rows(a->states_a, a->R, a->Ma, a->d) || summary::check_rows(a->states_b, a->R, a->Mb, a->d))
     return MMF_EINVAL;
-  for (int k = 0; k < a->d; ++k)
-    if (!(a->scale[k] > 0.f && a->scale[k] < INFINITY)) return MMF_EINVAL;  // (a NaN fails)
+  if (summary::check_scale(a->scale, a->d)) return MMF_EINVAL;
   const bool want_cdf = a->wasserstein || a->cramer || a->ks, want_pairs = a->energy || a->terms;
   if (!want_cdf && !want_pairs) return MMF_EINVAL;
   if (static_cast<long long>(a->Ma) + a->Mb > summary::kMaxM) return MMF_ETOOLARGE;  // one limit: the union sort's
@@ -548,11 +463,7 @@ extern "C" int mmf_pf_distance(const MmfPfDistanceArgs* a, void* stream) {
   k.energy = a->energy; k.terms = a->terms;
   k.ws = ws_bytes > 0 ? static_cast<double*>(a->workspace) : nullptr;
   k.nb_a = pa.nb; k.chunk_a = pa.chunk; k.nb_b = pb.nb; k.chunk_b = pb.chunk;
-  bool scaled = false;
-  for (int i = 0; i < MMF_MAX_STATE_DIM; ++i) {
-    k.inv_scale[i] = i < a->d ? 1.0f / a->scale[i] : 1.0f;
-    scaled = scaled || k.inv_scale[i] != 1.0f;
-  }
+  const bool scaled = summary::inv_scale_of(a->scale, a->d, k.inv_scale);
   const unsigned R = static_cast<unsigned>(a->R);
   if (pa.nb == 1 && pb.nb == 1)  // one workgroup takes the row pair: the threads of the larger plan, one i-particle each
     return launch_pairs(k, a->d, scaled, kWholeRow, R, 1, pa.threads > pb.threads ? pa.threads : pb.threads, s);

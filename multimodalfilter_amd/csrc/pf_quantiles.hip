@@ -2,28 +2,25 @@
 // quantiles"): K1's integer fixed-point weights q_m = floor(exp(a_m - max a) 2^24), so that every sum is an integer sum and the
 // selection does not depend on the thread count, the scan order or the number of rows.  One kernel, one workgroup per
 // (row, dimension):
-//   weights    a = log_a + log_b held in registers, the row maximum, q_m under the live-weight rule (pf_summary.h)
+//   weights    a = log_a + log_b held in registers, the row maximum, q_m under the live-weight rule (sort::fixed_weight)
 //   cdf        the integer sum of q_m over x_m <= query, reduced before the sort; Q == 0 ends here
 //   keys       (order-preserving uint32 of x_m) << 32 | q_m, one uint64 per particle in LDS, padded to P = 2^k >= M with
 //              all-ones keys of weight 0
-//   sort       bitonic over the P uint64s: a thread owns E = P / THREADS consecutive slots; the stages whose stride is below E
-//              run in its registers, the others through LDS.  Slot i lives at i + i / E: the E-slot runs of neighbouring lanes
-//              start 8 (E + 1) bytes apart, an odd number of 8-byte bank pairs, so the run loads and stores are conflict-free
-//   scan       thread sums, the wave scan of K1 (mmf::wave_inclusive_scan), wave totals through LDS
+//   sort       the bitonic sort of pf_sort.h (its plan, slots and register stages; the body's text is here): a thread ends with
+//              its E = P / THREADS consecutive sorted slots in registers
+//   scan       the thread sums of the sorted runs (sort::block_scan)
 //   search     per p: thr = max(1, ceil(p Qtot)) in double; the one thread whose run crosses thr walks it and stores the value
 // The weights are recomputed by each of the d workgroups of a row (M reads, M exp beside a sort of P log^2 P compare-exchanges).
 
 #include <cmath>
 
-#include "pf_summary.h"
+#include "pf_sort.h"
 
 namespace {
 
 namespace summary = mmf::summary;
-using u64 = unsigned long long;
-
-constexpr int kMaxWaves = 4;
-constexpr u64 kPadKey = 0xFFFFFFFF00000000ull;
+namespace sort = mmf::sort;
+using sort::u64;
 
 struct QArgs {
   const float* states;  // (R, M, d)
@@ -36,78 +33,11 @@ struct QArgs {
   float probs[MMF_QUANTILES_MAX];
 };
 
-// threads and slots per thread of the workgroup that sorts M particles: one wave up to P = 512 (8 slots per lane), 256 threads
-// beyond.  Measured at P = 512 on the 32 x 300 x 100 history: 256 threads x 2 slots 0.083 ms, 128 x 4 0.076 ms, 64 x 8 0.067 ms;
-// at P = 4096: 256 x 16 0.162 ms, 128 x 32 0.214 ms, 64 x 64 0.314 ms (profiles/quantiles/README.md)
-struct Plan {
-  int threads, E;
-};
-inline Plan plan_of(int M) {
-  int P = MMF_WAVE;
-  while (P < M) P <<= 1;
-  const int threads = P <= 8 * MMF_WAVE ? MMF_WAVE : 256;
-  return {threads, P / threads};
-}
-inline size_t slots_of(const Plan& p) {
-  return static_cast<size_t>(p.threads) * p.E + (p.E > 1 ? p.threads : 0);  // the padding slot after every run of E
-}
-
-// a total order on the bit patterns that agrees with < on the numbers: negatives inverted, the others with the sign bit set
-__device__ __forceinline__ unsigned key_of(float x) {
-  const unsigned b = __float_as_uint(x);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float value_of(unsigned k) {
-  return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
-}
-
-template <int E>
-__device__ __forceinline__ int slot(int i) {
-  return E > 1 ? i + i / E : i;
-}
-
-// inclusive scan of per-thread values below 2^40 over the workgroup, and its total
-template <int THREADS>
-__device__ __forceinline__ u64 block_scan(u64 v, u64* scratch, int tid, u64& total) {
-  const int lane = tid & (MMF_WAVE - 1), wave = tid / MMF_WAVE;
-  u64 incl = mmf::wave_inclusive_scan(v, lane);
-  if (lane == MMF_WAVE - 1) scratch[wave] = incl;
-  __syncthreads();
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < THREADS / MMF_WAVE; ++w) {
-    const u64 t = scratch[w];
-    if (w < wave) incl += t;
-    total += t;
-  }
-  __syncthreads();
-  return incl;
-}
-
-// the stages of phase k whose stride is jmax, jmax / 2, .. 1, all below E: inside the E consecutive slots from `base`
-template <int E>
-__device__ __forceinline__ void local_stages(u64 (&v)[E], int base, int k, int jmax) {
-#pragma unroll
-  for (int j = E / 2; j >= 1; j >>= 1) {
-    if (j > jmax) continue;
-#pragma unroll
-    for (int l = 0; l < E; ++l) {
-      if (l & j) continue;
-      const bool up = ((base + l) & k) == 0;
-      const u64 lo = v[l], hi = v[l + j];
-      const bool swap = (lo > hi) == up;
-      v[l] = swap ? hi : lo;
-      v[l + j] = swap ? lo : hi;
-    }
-  }
-}
-
 template <int THREADS, int E>
 __global__ __launch_bounds__(THREADS) void pf_quantiles_kernel(QArgs a) {
   extern __shared__ u64 lds[];
-  __shared__ u64 wave_tot[kMaxWaves];
-  __shared__ float wave_top[kMaxWaves];
-  constexpr int P = THREADS * E;
+  __shared__ u64 wave_tot[sort::kMaxWaves];
+  __shared__ float wave_top[sort::kMaxWaves];
   const int tid = threadIdx.x, M = a.M, d = a.d;
   const int r = blockIdx.x / d, k = blockIdx.x - r * d;
   const size_t row = static_cast<size_t>(r) * M;
@@ -132,21 +62,19 @@ __global__ __launch_bounds__(THREADS) void pf_quantiles_kernel(QArgs a) {
 #pragma unroll
   for (int u = 0; u < E; ++u) {
     const int m = tid + u * THREADS;
-    u64 packed = kPadKey;
+    u64 packed = sort::kPadKey;
     if (m < M) {
-      const float t = av[u] - top;
-      const float e = expf(t);
-      const unsigned q = t <= 0.f ? static_cast<unsigned>(floorf(e * 16777216.0f)) : 0u;  // (the live-weight rule: a NaN t: 0)
+      const unsigned q = sort::fixed_weight(av[u] - top);
       const float xv = x[static_cast<size_t>(m) * d];
       qsum += q;
       if (xv <= query) below += q;
-      packed = (static_cast<u64>(key_of(xv)) << 32) | q;
+      packed = (static_cast<u64>(sort::key_of(xv)) << 32) | q;
     }
-    if (a.Q > 0) lds[slot<E>(m)] = packed;
+    if (a.Q > 0) lds[sort::slot<E>(m)] = packed;
   }
   u64 Qtot, below_tot = 0;
-  block_scan<THREADS>(qsum, wave_tot, tid, Qtot);
-  if (want_cdf) block_scan<THREADS>(below, wave_tot, tid, below_tot);
+  sort::block_scan<THREADS>(qsum, wave_tot, tid, Qtot);
+  if (want_cdf) sort::block_scan<THREADS>(below, wave_tot, tid, below_tot);
   const bool dead = !(top > -INFINITY) || !(top < INFINITY) || Qtot == 0;  // no live particle in the row
   if (want_cdf && tid == 0) {
     const float c = static_cast<float>(static_cast<double>(below_tot) / static_cast<double>(Qtot));
@@ -158,18 +86,19 @@ __global__ __launch_bounds__(THREADS) void pf_quantiles_kernel(QArgs a) {
     return;
   }
 
-  // ---- bitonic sort, ascending
+  // ---- bitonic sort, ascending (pf_sort.h: one textual copy here and in pf_distance.hip)
+  constexpr int P = THREADS * E;
   const int base = tid * E;
   u64 v[E];
   __syncthreads();
   if constexpr (E > 1) {
 #pragma unroll
-    for (int l = 0; l < E; ++l) v[l] = lds[slot<E>(base) + l];
+    for (int l = 0; l < E; ++l) v[l] = lds[sort::slot<E>(base) + l];
 #pragma unroll
-    for (int kk = 2; kk <= E; kk <<= 1) local_stages<E>(v, base, kk, kk / 2);
+    for (int kk = 2; kk <= E; kk <<= 1) sort::local_stages<E>(v, base, kk, kk / 2);
     for (int kk = 2 * E; kk <= P; kk <<= 1) {
 #pragma unroll
-      for (int l = 0; l < E; ++l) lds[slot<E>(base) + l] = v[l];
+      for (int l = 0; l < E; ++l) lds[sort::slot<E>(base) + l] = v[l];
       __syncthreads();
       for (int j = kk / 2; j >= E; j >>= 1) {
 #pragma unroll
@@ -177,17 +106,17 @@ __global__ __launch_bounds__(THREADS) void pf_quantiles_kernel(QArgs a) {
           const int p = tid + u * THREADS;
           const int i = 2 * p - (p & (j - 1));  // pair p of stride j: 2 j (p / j) + p % j
           const bool up = (i & kk) == 0;
-          const u64 lo = lds[slot<E>(i)], hi = lds[slot<E>(i + j)];
+          const u64 lo = lds[sort::slot<E>(i)], hi = lds[sort::slot<E>(i + j)];
           if ((lo > hi) == up) {
-            lds[slot<E>(i)] = hi;
-            lds[slot<E>(i + j)] = lo;
+            lds[sort::slot<E>(i)] = hi;
+            lds[sort::slot<E>(i + j)] = lo;
           }
         }
         __syncthreads();
       }
 #pragma unroll
-      for (int l = 0; l < E; ++l) v[l] = lds[slot<E>(base) + l];
-      local_stages<E>(v, base, kk, E / 2);
+      for (int l = 0; l < E; ++l) v[l] = lds[sort::slot<E>(base) + l];
+      sort::local_stages<E>(v, base, kk, E / 2);
     }
   } else {
     for (int kk = 2; kk <= P; kk <<= 1)
@@ -211,7 +140,7 @@ __global__ __launch_bounds__(THREADS) void pf_quantiles_kernel(QArgs a) {
 #pragma unroll
   for (int l = 0; l < E; ++l) mine += v[l] & 0xFFFFFFFFull;
   u64 total;
-  const u64 excl = block_scan<THREADS>(mine, wave_tot, tid, total) - mine;
+  const u64 excl = sort::block_scan<THREADS>(mine, wave_tot, tid, total) - mine;
 #pragma unroll 1
   for (int i = 0; i < a.Q; ++i) {
     const double want = ceil(static_cast<double>(a.probs[i]) * static_cast<double>(total));
@@ -227,14 +156,9 @@ __global__ __launch_bounds__(THREADS) void pf_quantiles_kernel(QArgs a) {
         key = hit ? static_cast<unsigned>(v[l] >> 32) : key;
         found = found || hit;
       }
-      a.quantiles[(static_cast<size_t>(r) * a.Q + i) * d + k] = value_of(key);
+      a.quantiles[(static_cast<size_t>(r) * a.Q + i) * d + k] = sort::value_of(key);
     }
   }
-}
-
-template <int THREADS, int E>
-int run(const QArgs& k, unsigned grid, size_t lds_bytes, hipStream_t s) {
-  return mmf::launch(pf_quantiles_kernel<THREADS, E>, grid, THREADS, lds_bytes, s, k);
 }
 
 }  // namespace
@@ -242,7 +166,7 @@ int run(const QArgs& k, unsigned grid, size_t lds_bytes, hipStream_t s) {
 extern "C" size_t mmf_pf_quantiles_lds_bytes(int M) {
   if (M < 1) return 0;
   if (M > summary::kMaxM) M = summary::kMaxM;
-  return slots_of(plan_of(M)) * sizeof(u64);
+  return sort::slots_of(sort::plan_of(M)) * sizeof(u64);
 }
 
 extern "C" int mmf_pf_quantiles(const MmfPfQuantilesArgs* a, void* stream) {
@@ -267,21 +191,9 @@ extern "C" int mmf_pf_quantiles(const MmfPfQuantilesArgs* a, void* stream) {
   for (int i = 0; i < a->Q; ++i) k.probs[i] = a->probs[i];
   hipStream_t s = static_cast<hipStream_t>(stream);
   const unsigned grid = static_cast<unsigned>(a->R) * static_cast<unsigned>(a->d);
-  const Plan p = plan_of(a->M);
-  const size_t lds_bytes = slots_of(p) * sizeof(u64);
-  if (p.threads == MMF_WAVE) {
-    switch (p.E) {
-      case 1: return run<MMF_WAVE, 1>(k, grid, lds_bytes, s);
-      case 2: return run<MMF_WAVE, 2>(k, grid, lds_bytes, s);
-      case 4: return run<MMF_WAVE, 4>(k, grid, lds_bytes, s);
-      default: return run<MMF_WAVE, 8>(k, grid, lds_bytes, s);
-    }
-  }
-  switch (p.E) {
-    case 4: return run<256, 4>(k, grid, lds_bytes, s);
-    case 8: return run<256, 8>(k, grid, lds_bytes, s);
-    case 16: return run<256, 16>(k, grid, lds_bytes, s);
-    case 32: return run<256, 32>(k, grid, lds_bytes, s);
-    default: return run<256, 64>(k, grid, lds_bytes, s);
-  }
+  const sort::Plan p = sort::plan_of(a->M);
+  return sort::with_plan(p, [&](auto T, auto E) {
+    constexpr int kT = decltype(T)::value, kE = decltype(E)::value;
+    return mmf::launch(pf_quantiles_kernel<kT, kE>, grid, kT, sort::slots_of(p) * sizeof(u64), s, k);
+  });
 }

@@ -200,9 +200,7 @@ extern "C" size_t mmf_pf_scores_workspace_bytes(int R, int M, int d) {
 }
 
 extern "C" int mmf_pf_scores(const MmfPfScoresArgs* a, void* stream) {
-  if (!a || check_rows(a->states, a->R, a->M, a->d)) return MMF_EINVAL;
-  for (int k = 0; k < a->d; ++k)
-    if (!(a->scale[k] > 0.f && a->scale[k] < INFINITY)) return MMF_EINVAL;  // (a NaN fails)
+  if (!a || check_rows(a->states, a->R, a->M, a->d) || check_scale(a->scale, a->d)) return MMF_EINVAL;
   if (!a->crps && !a->energy && !a->spread) return MMF_EINVAL;
   if ((a->crps || a->energy) && !a->truth) return MMF_EINVAL;
   const Plan p = plan_of(a->M <= kMaxM ? a->M : kMaxM);  // (a larger M: check_size refuses it)
@@ -221,11 +219,7 @@ extern "C" int mmf_pf_scores(const MmfPfScoresArgs* a, void* stream) {
   k.crps = a->crps; k.energy = a->energy; k.spread = a->spread;
   k.ws = ws_bytes > 0 ? static_cast<double*>(a->workspace) : nullptr;
   k.M = a->M; k.d = a->d; k.nb = p.nb; k.chunk = p.chunk;
-  bool scaled = false;
-  for (int i = 0; i < MMF_MAX_STATE_DIM; ++i) {
-    k.inv_scale[i] = i < a->d ? 1.0f / a->scale[i] : 1.0f;
-    scaled = scaled || k.inv_scale[i] != 1.0f;
-  }
+  const bool scaled = inv_scale_of(a->scale, a->d, k.inv_scale);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const unsigned grid = static_cast<unsigned>(a->R) * static_cast<unsigned>(p.nb);
   const int rc = mmf::with_state_dim(a->d, [&](auto D) {

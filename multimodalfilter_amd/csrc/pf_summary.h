@@ -6,8 +6,11 @@
 //   live weight    w_m = exp(a_m - max a) where a_m - max a <= 0, else 0: a NaN a_m and an empty row's -inf - -inf carry no weight
 //   dead particle  a particle with w_m = 0 is selected away, never multiplied by 0: its state row (NaN, by convention) is not read
 //                  into a sum, and the pair kernels stage it as zeros
-// Not shared, on purpose: the j-tile staging loops, the pair loops, the finish kernels and the quantile sort.  The staging loops
-// differ in what they store and in their padding; one body for them would branch on its caller.
+// The weighted-CDF sort of pf_quantiles.hip and pf_distance.hip (its plan, keys, fixed-point weight, scan and register stages)
+// is pf_sort.h, over this file.  Not shared, on purpose: the j-tile staging loops, the pair loops and the finish kernels.  The
+// staging loops of pf_density.hip and pf_modes.hip differ in what they store and in their padding; those of pf_scores.hip,
+// pf_predictive.hip and pf_distance.hip are alike, but one definition moved their register counts across occupancy steps
+// (profiles/summary_sort/README.md).
 #pragma once
 #include <cmath>
 
@@ -102,6 +105,22 @@ inline int check_rows(const void* states, int R, int M, int d) {
 // per_row: the workgroups of a row
 inline int check_size(int R, int M, int per_row) {
   return M > kMaxM || static_cast<long long>(R) * per_row > 0x7fffffffll ? MMF_ETOOLARGE : 0;
+}
+
+// the per-dimension scale of a Euclidean norm (scores, distance): every scale[k < d] positive and finite
+inline int check_scale(const float* scale, int d) {
+  for (int k = 0; k < d; ++k)
+    if (!(scale[k] > 0.f && scale[k] < INFINITY)) return MMF_EINVAL;  // (a NaN fails)
+  return 0;
+}
+// its reciprocals, 1 beyond d; does any of them scale at all?
+inline bool inv_scale_of(const float* scale, int d, float (&inv_scale)[MMF_MAX_STATE_DIM]) {
+  bool scaled = false;
+  for (int i = 0; i < MMF_MAX_STATE_DIM; ++i) {
+    inv_scale[i] = i < d ? 1.0f / scale[i] : 1.0f;
+    scaled = scaled || inv_scale[i] != 1.0f;
+  }
+  return scaled;
 }
 
 // `need` bytes of workspace (0: none is read) aligned to `align`

@@ -84,13 +84,7 @@ def scale64(case):
     return np.ones(d) if case["scale"] is None else np.asarray(case["scale"], np.float64)
 
 
-def fixed_point(side):
-    """K1's fixed-point weights of one set, formed in fp32 as the kernel forms them: ``(R, M)`` int64."""
-    t = sm.log_weight32(side)
-    with np.errstate(invalid="ignore", over="ignore"):
-        e = np.exp(t).astype(np.float32)
-        q = np.floor(e * np.float32(16777216.0))
-        return np.where(t <= 0, q, 0.0).astype(np.int64)  # (a NaN t: 0)
+fixed_point = sm.fixed_point_weights  # K1's fixed-point weights of one set: ``(R, M)`` int64
 
 
 def cdf_rows(Xa, qa, Xb, qb, dtype=np.float64):

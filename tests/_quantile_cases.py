@@ -130,10 +130,7 @@ def fixed_point(case):
     X, query = case["states"], case["query"]
     R, M, d = X.shape
     ps = probs32(case["probs"])
-    t = log_weight32(case)
-    with np.errstate(invalid="ignore"):
-        e = np.exp(t).astype(np.float32)
-        q = np.where(t <= 0, np.floor(e * np.float32(16777216.0)), 0).astype(np.int64)
+    q = sm.fixed_point_weights(case)
     quant = np.full((R, len(ps), d), np.nan, np.float32)
     cdf = np.full((R, d), np.nan, np.float32)
     for r in range(R):

@@ -1,6 +1,7 @@
-"""What the case modules of the three particle-posterior summaries share (``_quantile_cases``, ``_score_cases``,
-``_density_cases``): the sizes and sentinels of their tests, the generator of a weighted particle set, and the weights as the
-kernels form them (``csrc/pf_summary.h``) -- ``t = (log_a + log_b) - max`` in the kernels' own two fp32 operations, then fp64.
+"""What the case modules of the particle-posterior summaries share (``_quantile_cases``, ``_score_cases``, ``_density_cases``,
+``_mode_cases``, ``_distance_cases``, ``_forecast_cases``): the sizes and sentinels of their tests, the generator of a weighted
+particle set, and the weights as the kernels form them (``csrc/pf_summary.h``) -- ``t = (log_a + log_b) - max`` in the kernels'
+own two fp32 operations, then fp64, or K1's integer fixed point (``csrc/pf_sort.h``).
 
 The generator draws from the caller's ``rng``, and in one fixed order: each case module keeps its own seed formula and its own
 tail (queries, truths, scale, rule), so a case depends on nothing but its module's arguments."""
@@ -8,7 +9,7 @@ import math
 
 import numpy as np
 
-MAX_M = 16384       # particles per row that the three entry points serve (csrc/pf_summary.h: kMaxM)
+MAX_M = 16384       # particles per row that the entry points serve (csrc/pf_summary.h: kMaxM)
 SENTINEL = -77.25   # what a guard row and an output that was not asked for hold
 GUARD_ROWS = 2
 CHUNK = 256         # rows of a chunk of the fp64 pair references
@@ -65,6 +66,15 @@ def log_weight32(case):
         a = (la + lb).astype(np.float32)
         top = np.fmax.reduce(a, axis=1, initial=-np.inf).astype(np.float32)  # (fmax skips NaN)
         return (a - top[:, None]).astype(np.float32)
+
+
+def fixed_point_weights(case_or_side):
+    """K1's fixed-point weights ``q = floor(exp(t) 2^24)`` where ``t <= 0``, else 0 (a NaN ``t``: 0), formed with the kernels'
+    own fp32 operations (numpy's fp32 ``exp`` for ``expf``): ``(R, M)`` int64."""
+    t = log_weight32(case_or_side)
+    with np.errstate(invalid="ignore", over="ignore"):
+        e = np.exp(t).astype(np.float32)
+        return np.where(t <= 0, np.floor(e * np.float32(16777216.0)), 0.0).astype(np.int64)
 
 
 def weights64(case):

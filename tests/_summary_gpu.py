@@ -1,7 +1,9 @@
-"""What the GPU tests of the three particle-posterior summaries share (``test_gpu_quantiles.py``, ``test_gpu_scores.py``,
-``test_gpu_density.py``): guarded output buffers, the bit comparison, a small real filter with a history, and the records'
-tensors as a case of the case modules."""
+"""What the GPU tests of the particle-posterior summaries share (``test_gpu_quantiles.py``, ``_scores``, ``_density``,
+``_modes``, ``_modalities``, ``_distance``, ``_forecast``): guarded output buffers and the call between them, the bit
+comparison and its two loops (two calls and a row alone; every subset of the outputs), a small real filter with a history, and
+the records' tensors as a case of the case modules."""
 import functools
+import itertools
 
 import torch
 
@@ -32,6 +34,47 @@ N = lambda t: None if t is None else t.cpu().numpy()
 
 def _same_bits(a, b):
     return torch.equal(a.view(torch.int32), b.view(torch.int32))
+
+
+def guarded_call(call, R, tails, want, outputs, what, dtypes=None):
+    """``call(views)`` with every output of ``outputs`` between guard rows: ``views[k]`` is the ``(R,) + tails[k]`` view of
+    output ``k`` (float32, or ``dtypes[k]``) if ``k`` is in ``want`` and ``None`` otherwise.  The guard rows must come back
+    intact and the buffers not asked for untouched -> ``dict`` of device tensors (``None`` for those).  ``what``: the sizes,
+    for the messages."""
+    dev = sc.dev()
+    bufs = {k: _Guarded(R, tails[k], dev, (dtypes or {}).get(k, torch.float32)) for k in outputs}
+    call({k: (bufs[k].view if k in want else None) for k in outputs})
+    torch.cuda.synchronize()
+    for k, b in bufs.items():
+        assert b.guards_intact(), f"a guard row of {k} was written ({what})"
+        if k not in want:
+            assert b.untouched(), f"{k} was not asked for and was written ({what})"
+    return {k: (bufs[k].view.clone() if k in want else None) for k in outputs}
+
+
+def assert_repeatable(run, case, outputs, rows, what=()):
+    """Two calls of ``run(case)`` give the same bits, and so does each row of ``rows`` alone (``run(case, rows=slice)``)
+    -> the outputs of the first call."""
+    got, again = run(case), run(case)
+    for k in outputs:
+        assert _same_bits(got[k], again[k]), what + ("again", k)
+    for r in rows:
+        one = run(case, rows=slice(r, r + 1))
+        for k in outputs:
+            assert _same_bits(one[k], got[k][r:r + 1]), what + (r, k)
+    return got
+
+
+def assert_subsets_match_full(run, case, outputs, full=None, what=()):
+    """Every proper non-empty subset ``want`` of ``outputs`` writes, in ``run(case, want)``, the bits of the full call (the
+    untouched buffers are checked by ``guarded_call``) -> the full call's outputs."""
+    full = run(case) if full is None else full
+    for n in range(1, len(outputs)):
+        for want in itertools.combinations(outputs, n):
+            got = run(case, want)
+            for k in want:
+                assert _same_bits(got[k], full[k]), what + (want, k)
+    return full
 
 
 @functools.lru_cache(maxsize=None)

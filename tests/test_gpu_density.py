@@ -7,8 +7,6 @@ The bar of ``log_density``, ``log_score`` and ``entropy``: ``|got - fp64| <= REL
 with ``-inf`` and NaN exactly where the definition puts them; ``bandwidth``: ``rel_err_elementwise < REL_TOL``; the mode is the
 first maximum of the kernel's own ``log_density``, a bit copy of that particle, and within the bar of the reference's maximum
 (``_density_cases.check_mode``).  Every figure is printed before it is asserted."""
-import itertools
-
 import numpy as np
 import pytest
 import torch
@@ -18,7 +16,7 @@ import _quantile_cases as qc
 import _score_cases as sk
 import _smooth_cases as sc
 import _summary_gpu as sg
-from _summary_gpu import N, _filter_run, _Guarded, _same_bits
+from _summary_gpu import N, _filter_run, _same_bits
 from _tol import REL_TOL
 
 pytestmark = pytest.mark.gpu
@@ -32,24 +30,18 @@ def _run(case, want=OUTPUTS, rows=None):
     Without a truth ``log_score`` is never asked for."""
     from multimodalfilter_amd import _abi
 
-    dev = sc.dev()
     pick = (lambda x: x) if rows is None else (lambda x: None if x is None else x[rows])
     X, la, lb, y = (sc.to_device(pick(case[k])) for k in ("states", "log_a", "log_b", "truth"))
     if y is None:
         want = tuple(k for k in want if k != "log_score")
     R, M, d = X.shape
-    bufs = {"log_density": _Guarded(R, (M,), dev), "log_score": _Guarded(R, (), dev), "entropy": _Guarded(R, (), dev),
-            "mode": _Guarded(R, (d,), dev), "bandwidth": _Guarded(R, (d,), dev), "mode_index": _Guarded(R, (), dev, torch.int32)}
-    arg = lambda k: bufs[k].view if k in want else None
-    _abi.pf_density(X, la, lb, y, rule=case["rule"], bandwidth=case["bandwidth"], min_bandwidth=case["min_bandwidth"],
-                    log_density=arg("log_density"), log_score=arg("log_score"), entropy=arg("entropy"), mode=arg("mode"),
-                    mode_index=arg("mode_index"), bandwidth_out=arg("bandwidth"))
-    torch.cuda.synchronize()
-    for k, b in bufs.items():
-        assert b.guards_intact(), f"a guard row of {k} was written (M={M} d={d} R={R})"
-        if k not in want:
-            assert b.untouched(), f"{k} was not asked for and was written (M={M} d={d} R={R})"
-    return {k: (bufs[k].view.clone() if k in want else None) for k in OUTPUTS}
+
+    def call(out):
+        out["bandwidth_out"] = out.pop("bandwidth")
+        _abi.pf_density(X, la, lb, y, rule=case["rule"], bandwidth=case["bandwidth"], min_bandwidth=case["min_bandwidth"], **out)
+
+    tails = {"log_density": (M,), "log_score": (), "entropy": (), "mode": (d,), "bandwidth": (d,), "mode_index": ()}
+    return sg.guarded_call(call, R, tails, want, OUTPUTS, f"M={M} d={d} R={R}", {"mode_index": torch.int32})
 
 
 def _hold(case, ref, got, what):
@@ -133,14 +125,7 @@ PARTICLE_OUTPUTS = tuple(k for k in OUTPUTS if k != "log_score")
 def test_two_calls_a_row_alone_and_a_missing_truth_give_the_same_bits(M):
     for d, variant, rule in ((1, "plain", "silverman"), (3, "dead_row", "scott"), (4, "moderate", "fixed")):
         case = dc.make_case(M, d, 3, variant, rule)
-        got = _run(case)
-        again = _run(case)
-        for k in OUTPUTS:
-            assert _same_bits(got[k], again[k]), (M, d, variant, k)
-        for r in range(3):
-            one = _run(case, rows=slice(r, r + 1))
-            for k in OUTPUTS:
-                assert _same_bits(one[k], got[k][r:r + 1]), (M, d, variant, r, k)
+        got = sg.assert_repeatable(_run, case, OUTPUTS, range(3), (M, d, variant))
         blind = _run(dict(case, truth=None))
         assert blind["log_score"] is None
         for k in PARTICLE_OUTPUTS:
@@ -150,13 +135,7 @@ def test_two_calls_a_row_alone_and_a_missing_truth_give_the_same_bits(M):
 @pytest.mark.parametrize("M", BIT_MS)
 def test_every_subset_of_the_outputs_writes_the_bits_of_the_full_call_and_nothing_else(M):
     """All 63 non-empty subsets (the untouched buffers are checked inside ``_run``)."""
-    case = dc.make_case(M, 3, 3, "plain", "silverman")
-    full = _run(case)
-    for n in range(1, len(OUTPUTS)):
-        for want in itertools.combinations(OUTPUTS, n):
-            got = _run(case, want)
-            for k in want:
-                assert _same_bits(got[k], full[k]), (M, want, k)
+    sg.assert_subsets_match_full(_run, dc.make_case(M, 3, 3, "plain", "silverman"), OUTPUTS, what=(M,))
 
 
 # ------------------------------------------------------------------------------------------ 4. consistency

@@ -5,15 +5,13 @@ alone, any subset of the outputs, a set against itself, a permutation), its symm
 
 The bar: ``_tol.rel_err(got, fp64) < max(REL_TOL, 3 x the fp32 yardstick's own error)`` on every output, with NaN exactly
 where the definition puts it.  Every figure is printed before it is asserted."""
-import itertools
-
 import numpy as np
 import pytest
 import torch
 
 import _distance_cases as dc
 import _smooth_cases as sc
-from _summary_gpu import N, _filter_run, _Guarded, _same_bits
+from _summary_gpu import N, _filter_run, _same_bits, assert_repeatable, assert_subsets_match_full, guarded_call
 from _tol import REL_TOL
 
 pytestmark = pytest.mark.gpu
@@ -27,20 +25,13 @@ def _run(case, want=OUTPUTS, rows=None):
     are handed over as null and their buffers must come back untouched -> ``dict`` of device tensors (``None`` for those)."""
     from multimodalfilter_amd import _abi
 
-    dev = sc.dev()
     pick = (lambda x: x) if rows is None else (lambda x: None if x is None else x[rows])
     a, b = ([sc.to_device(pick(side[k])) for k in ("states", "log_a", "log_b")] for side in (case["a"], case["b"]))
     R, Ma, d = a[0].shape
     Mb = b[0].shape[1]
-    bufs = {"wasserstein": _Guarded(R, (d,), dev), "cramer": _Guarded(R, (d,), dev), "ks": _Guarded(R, (d,), dev),
-            "energy": _Guarded(R, (), dev), "terms": _Guarded(R, (3,), dev)}
-    _abi.pf_distance(*a, *b, scale=case["scale"], **{k: bufs[k].view for k in want})
-    torch.cuda.synchronize()
-    for k, buf in bufs.items():
-        assert buf.guards_intact(), f"a guard row of {k} was written (Ma={Ma} Mb={Mb} d={d} R={R})"
-        if k not in want:
-            assert buf.untouched(), f"{k} was not asked for and was written (Ma={Ma} Mb={Mb} d={d} R={R})"
-    return {k: (bufs[k].view.clone() if k in want else None) for k in OUTPUTS}
+    tails = {"wasserstein": (d,), "cramer": (d,), "ks": (d,), "energy": (), "terms": (3,)}
+    return guarded_call(lambda out: _abi.pf_distance(*a, *b, scale=case["scale"], **out), R, tails, want, OUTPUTS,
+                        f"Ma={Ma} Mb={Mb} d={d} R={R}")
 
 
 def _hold(ref, yard, got, what, outputs=OUTPUTS):
@@ -81,31 +72,34 @@ def test_cdf_kernel_at_the_particle_limit():
     _hold(ref, yard, got, f"Ma={Ma} Mb={Mb} d={d}", CDF)
 
 
+PLAN_PAIRS = ((100, 100), (2000, 49), (4000, 97))  # unions of 200, 2049 and 4097 slots
+
+
+@pytest.mark.parametrize("Ma,Mb", PLAN_PAIRS)
+def test_cdf_kernel_on_the_plans_between_the_family_and_the_limit(Ma, Mb):
+    """The smallest unions that the sort plan gives ``<64, 4>`` (129 .. 256 slots), ``<256, 16>`` (2049 .. 4096) and
+    ``<256, 32>`` (4097 .. 8192), which no pair of the family reaches.  Only the CDF outputs are asked for, as at the limit."""
+    d = 3
+    case = dc.make_case(Ma, Mb, d, 1)
+    ref, yard = _with_yardstick(case, CDF)
+    got = _run(case, CDF)
+    assert got["energy"] is None and got["terms"] is None
+    _hold(ref, yard, got, f"Ma={Ma} Mb={Mb} d={d}", CDF)
+
+
 # ------------------------------------------------------------------------------------------ 2. bit-for-bit identities
-@pytest.mark.parametrize("Ma,Mb", [(1, 37), (64, 64), (255, 257), (257, 256), (513, 600), (300, 1025)])
+# (the last three: the smallest unions of the CDF kernel's <64, 4>, <256, 16> and <256, 32>)
+@pytest.mark.parametrize("Ma,Mb", [(1, 37), (64, 64), (255, 257), (257, 256), (513, 600), (300, 1025)] + list(PLAN_PAIRS))
 def test_two_calls_and_a_row_pair_alone_give_the_same_bits(Ma, Mb):
     for d, v in ((1, 0), (3, 6), (4, 8)):
-        case = dc.make_case(Ma, Mb, d, 5, v)
-        got, again = _run(case), _run(case)
-        for k in OUTPUTS:
-            assert _same_bits(got[k], again[k]), (Ma, Mb, d, v, k)
-        for r in (0, 2, 4):
-            one = _run(case, rows=slice(r, r + 1))
-            for k in OUTPUTS:
-                assert _same_bits(one[k], got[k][r:r + 1]), (Ma, Mb, d, v, r, k)
+        assert_repeatable(_run, dc.make_case(Ma, Mb, d, 5, v), OUTPUTS, (0, 2, 4), (Ma, Mb, d, v))
 
 
 @pytest.mark.parametrize("Ma,Mb", [(37, 300), (513, 600)])
 def test_every_subset_of_the_outputs_writes_only_what_was_asked_for(Ma, Mb):
     """All 30 proper non-empty subsets: what is written has the bits of the full call (the untouched buffers are checked
     inside ``_run``), whichever of the two kernels the subset leaves out."""
-    case = dc.make_case(Ma, Mb, 3, 3, 0)
-    full = _run(case)
-    for n in range(1, len(OUTPUTS)):
-        for want in itertools.combinations(OUTPUTS, n):
-            got = _run(case, want)
-            for k in want:
-                assert _same_bits(got[k], full[k]), (Ma, Mb, want, k)
+    assert_subsets_match_full(_run, dc.make_case(Ma, Mb, 3, 3, 0), OUTPUTS, what=(Ma, Mb))
 
 
 @pytest.mark.parametrize("M", [37, 600])

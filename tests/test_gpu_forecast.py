@@ -15,7 +15,7 @@ import torch
 import _forecast_cases as fk
 import _rts_cases as rc
 import _smooth_cases as sc
-from _summary_gpu import N, _Guarded, _same_bits
+from _summary_gpu import N, _same_bits, assert_repeatable, assert_subsets_match_full, guarded_call
 from _tol import REL_TOL, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -30,7 +30,6 @@ def _run(case, want=None, rows=None):
     those)."""
     from multimodalfilter_amd import _abi
 
-    dev = sc.dev()
     pick = (lambda x: x) if rows is None else (lambda x: None if x is None else x[rows])
     X, la, lb, y = (sc.to_device(pick(case[k])) for k in ("states", "log_a", "log_b", "truth"))
     L = sc.to_device(case["scale_tril"])
@@ -38,14 +37,7 @@ def _run(case, want=None, rows=None):
         want = OUTPUTS if y is not None else NO_TRUTH
     R, M, d = X.shape
     tails = {"mean": (d,), "covariance": (d, d), "log_score": (), "pit": (d,), "spread": (d,), "crps": (d,)}
-    bufs = {k: _Guarded(R, tails[k], dev) for k in OUTPUTS}
-    _abi.pf_predictive(X, la, lb, L, y, **{k: bufs[k].view for k in want})
-    torch.cuda.synchronize()
-    for k, b in bufs.items():
-        assert b.guards_intact(), f"a guard row of {k} was written (M={M} d={d} R={R})"
-        if k not in want:
-            assert b.untouched(), f"{k} was not asked for and was written (M={M} d={d} R={R})"
-    return {k: (bufs[k].view.clone() if k in want else None) for k in OUTPUTS}
+    return guarded_call(lambda out: _abi.pf_predictive(X, la, lb, L, y, **out), R, tails, want, OUTPUTS, f"M={M} d={d} R={R}")
 
 
 def _hold(ref, got, what, worst=None):
@@ -113,14 +105,7 @@ def test_equal_centres_give_the_single_gaussian():
 def test_two_calls_a_row_alone_and_no_truth_give_the_same_bits(M):
     for d, variant, scale in ((1, "plain", 0.3), (3, "dead_row", 0.02), (4, "dead_particles", 3.0)):
         case = fk.make_case(M, d, 3, variant, scale)
-        got = _run(case)
-        again = _run(case)
-        for k in OUTPUTS:
-            assert _same_bits(got[k], again[k]), (M, d, variant, k)
-        for r in range(3):
-            one = _run(case, rows=slice(r, r + 1))
-            for k in OUTPUTS:
-                assert _same_bits(one[k], got[k][r:r + 1]), (M, d, variant, r, k)
+        got = assert_repeatable(_run, case, OUTPUTS, range(3), (M, d, variant))
         blind = _run(dict(case, truth=None))
         for k in NO_TRUTH:
             assert _same_bits(blind[k], got[k]), (M, d, variant, k)
@@ -131,12 +116,7 @@ def test_every_subset_of_outputs_writes_only_what_was_asked_for_with_the_same_bi
     """All 63 non-empty subsets with a truth, the 7 of ``mean``, ``covariance`` and ``spread`` without one (the untouched
     buffers are checked inside ``_run``)."""
     case = fk.make_case(M, 3, 3, "plain", 0.3)
-    full = _run(case)
-    for n in range(1, len(OUTPUTS)):
-        for want in itertools.combinations(OUTPUTS, n):
-            got = _run(case, want)
-            for k in want:
-                assert _same_bits(got[k], full[k]), (M, want, k)
+    full = assert_subsets_match_full(_run, case, OUTPUTS, what=(M,))
     blind = dict(case, truth=None)
     for n in range(1, len(NO_TRUTH) + 1):
         for want in itertools.combinations(NO_TRUTH, n):

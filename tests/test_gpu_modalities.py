@@ -4,8 +4,6 @@ alone, every subset of the outputs), the exact cases, and ``ParticleFilter.belie
 ``evaluation.run_filter(return_modalities=)`` end to end on small real filters.
 
 The bars are those of ``_modality_cases.compare``, every one ``< REL_TOL``; every figure is printed before it is asserted."""
-import itertools
-
 import numpy as np
 import pytest
 import torch
@@ -14,7 +12,7 @@ import _modality_cases as mc
 import _smooth_cases as sc
 from _density_cases import log_err
 from _score_cases import compare as rel_compare
-from _summary_gpu import N, _filter_run, _Guarded, _same_bits
+from _summary_gpu import N, _filter_run, assert_repeatable, assert_subsets_match_full, guarded_call
 from _tol import REL_TOL
 
 pytestmark = pytest.mark.gpu
@@ -28,20 +26,13 @@ def _run(case, want=OUTPUTS, rows=None):
     those)."""
     from multimodalfilter_amd import _abi
 
-    dev = sc.dev()
     pick = (lambda x: x) if rows is None else (lambda x: None if x is None else x[rows])
     X, lw, beta = (sc.to_device(pick(case[k])) for k in ("states", "log_w", "beta"))
     l = sc.to_device(case["loglik"] if rows is None else case["loglik"][:, rows])
     R, M, d = X.shape
     K = l.shape[0]
-    bufs = {k: _Guarded(R, tail, dev) for k, tail in mc.shapes(R, K, d).items()}
-    _abi.pf_modalities(X, lw, [l[k] for k in range(K)], beta, **{k: (bufs[k].view if k in want else None) for k in OUTPUTS})
-    torch.cuda.synchronize()
-    for k, b in bufs.items():
-        assert b.guards_intact(), f"a guard row of {k} was written (M={M} d={d} R={R} K={K})"
-        if k not in want:
-            assert b.untouched(), f"{k} was not asked for and was written (M={M} d={d} R={R} K={K})"
-    return {k: (bufs[k].view.clone() if k in want else None) for k in OUTPUTS}
+    return guarded_call(lambda out: _abi.pf_modalities(X, lw, [l[k] for k in range(K)], beta, **out), R, mc.shapes(R, K, d),
+                        want, OUTPUTS, f"M={M} d={d} R={R} K={K}")
 
 
 def _hold(case, ref, got, what):
@@ -78,27 +69,13 @@ def test_kernel_at_the_particle_limit():
 @pytest.mark.parametrize("M", [1, 65, 257, 513, mc.THREADS * mc.RUN_PT, mc.THREADS * mc.RUN_PT + 1, 2 * mc.THREADS * mc.RUN_PT + 1])
 def test_two_calls_and_a_row_alone_give_the_same_bits(M):
     for d, K, variant in ((1, 1, "plain"), (3, 2, "dead_row"), (4, 4, "blackout"), (2, 3, "nan_loglik")):
-        case = mc.make_case(M, d, 3, K, variant)
-        got = _run(case)
-        again = _run(case)
-        for k in OUTPUTS:
-            assert _same_bits(got[k], again[k]), (M, d, K, variant, k)
-        for r in range(3):
-            one = _run(case, rows=slice(r, r + 1))
-            for k in OUTPUTS:
-                assert _same_bits(one[k], got[k][r:r + 1]), (M, d, K, variant, r, k)
+        assert_repeatable(_run, mc.make_case(M, d, 3, K, variant), OUTPUTS, range(3), (M, d, K, variant))
 
 
 @pytest.mark.parametrize("M", [65, 257, mc.THREADS * mc.RUN_PT + 1])
 def test_every_subset_of_the_outputs_writes_the_bits_of_the_full_call_and_nothing_else(M):
     """(the untouched buffers and the guard rows are checked inside ``_run``)"""
-    case = mc.make_case(M, 3, 3, 3, "blackout")
-    full = _run(case)
-    for n in range(1, len(OUTPUTS)):
-        for want in itertools.combinations(OUTPUTS, n):
-            got = _run(case, want)
-            for k in want:
-                assert _same_bits(got[k], full[k]), (M, want, k)
+    assert_subsets_match_full(_run, mc.make_case(M, 3, 3, 3, "blackout"), OUTPUTS, what=(M,))
 
 
 # ------------------------------------------------------------------------------------------ 3. the exact cases

@@ -11,7 +11,7 @@ import _mode_cases as mc
 import _score_cases as sk
 import _smooth_cases as sc
 import _summary_gpu as sg
-from _summary_gpu import N, _filter_run, _Guarded, _same_bits
+from _summary_gpu import N, _filter_run, _same_bits
 from _tol import REL_TOL
 
 pytestmark = pytest.mark.gpu
@@ -24,23 +24,13 @@ def _run(case, want=OUTPUTS, rows=None):
     handed over as null and their buffers must come back untouched -> ``dict`` of device tensors (``None`` for those)."""
     from multimodalfilter_amd import _abi
 
-    dev = sc.dev()
     pick = (lambda x: x) if rows is None else (lambda x: None if x is None else x[rows])
     X, la, lb, ld, h = (sc.to_device(pick(case[k])) for k in ("states", "log_a", "log_b", "log_density", "bandwidth"))
     R, M, d = X.shape
     K = case["max_modes"]
-    i32 = torch.int32
-    bufs = {"parent": _Guarded(R, (M,), dev, i32), "labels": _Guarded(R, (M,), dev, i32), "count": _Guarded(R, (), dev, i32),
-            "index": _Guarded(R, (K,), dev, i32), "modes": _Guarded(R, (K, d), dev), "mass": _Guarded(R, (K,), dev),
-            "mean": _Guarded(R, (K, d), dev)}
-    _abi.pf_modes(X, la, lb, ld, h, link_radius=case["link_radius"], max_modes=K,
-                  **{k: (bufs[k].view if k in want else None) for k in OUTPUTS})
-    torch.cuda.synchronize()
-    for k, b in bufs.items():
-        assert b.guards_intact(), f"a guard row of {k} was written (M={M} d={d} R={R})"
-        if k not in want:
-            assert b.untouched(), f"{k} was not asked for and was written (M={M} d={d} R={R})"
-    return {k: (bufs[k].view.clone() if k in want else None) for k in OUTPUTS}
+    tails = {"parent": (M,), "labels": (M,), "count": (), "index": (K,), "modes": (K, d), "mass": (K,), "mean": (K, d)}
+    return sg.guarded_call(lambda out: _abi.pf_modes(X, la, lb, ld, h, link_radius=case["link_radius"], max_modes=K, **out), R,
+                           tails, want, OUTPUTS, f"M={M} d={d} R={R}", dict.fromkeys(mc.INT_OUTPUTS, torch.int32))
 
 
 def _hold(case, ref_parent, got, what, exact_index=False):
@@ -126,12 +116,7 @@ BIT_MS = [1, 65, 257, 512, 513, 1025, mc.LDS_MASS_M + 1]
 @pytest.mark.parametrize("M", BIT_MS)
 def test_two_calls_and_a_row_alone_give_the_same_bits(M):
     for case, name in _bit_cases(M):
-        got = _run(case)
-        _same(got, _run(case), (M, name, "again"))
-        R = len(case["states"])
-        for r in range(R):
-            one = _run(case, rows=slice(r, r + 1))
-            _same(one, {k: v[r:r + 1] for k, v in got.items()}, (M, name, r))
+        sg.assert_repeatable(_run, case, OUTPUTS, range(len(case["states"])), (M, name))
 
 
 @pytest.mark.parametrize("M", BIT_MS)

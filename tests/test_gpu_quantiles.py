@@ -78,7 +78,7 @@ def test_kernel_at_the_particle_limit():
 
 
 # ------------------------------------------------------------------------------------------ 2. bit-for-bit identities
-@pytest.mark.parametrize("M", [1, 65, 257, 512, 513, 1000, 4096])  # (512 | 513: one wave | 256 threads)
+@pytest.mark.parametrize("M", [1, 65, 257, 512, 513, 1000, 4096, 4097])  # (512 | 513: one wave | 256 threads; 4097: 32 slots)
 def test_two_calls_and_a_row_alone_give_the_same_bits(M):
     for d, variant in ((1, "plain"), (3, "dead_row"), (4, "plain")):
         case = qc.make_case(M, d, 5, variant)
@@ -90,7 +90,7 @@ def test_two_calls_and_a_row_alone_give_the_same_bits(M):
             assert _same_bits(q1, quant[r:r + 1]) and _same_bits(c1, cdf[r:r + 1]), (M, d, variant, r)
 
 
-@pytest.mark.parametrize("M,dead", qc.EXACT + ((512, True), (513, True), (4096, False), (4096, True)))
+@pytest.mark.parametrize("M,dead", qc.EXACT + ((512, True), (513, True), (4096, False), (4096, True), (4097, True)))
 def test_equal_weights_are_a_rank_of_np_sort(M, dead):
     for d, R in ((1, 1), (3, 5), (4, 2)):
         case = qc.exact_case(M, d, R, dead)

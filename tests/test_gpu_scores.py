@@ -5,8 +5,6 @@ to end on small real filters.
 
 The bar: ``rel_err_elementwise(got, fp64, floor=1e-3) < REL_TOL`` for ``crps``, ``energy`` and ``spread``, with NaN exactly
 where the definition puts it.  Every figure is printed before it is asserted."""
-import itertools
-
 import numpy as np
 import pytest
 import torch
@@ -14,7 +12,7 @@ import torch
 import _score_cases as sk
 import _smooth_cases as sc
 import _summary_gpu as sg
-from _summary_gpu import N, _filter_run, _Guarded, _same_bits
+from _summary_gpu import N, _filter_run, _same_bits
 from _tol import REL_TOL
 
 pytestmark = pytest.mark.gpu
@@ -27,20 +25,13 @@ def _run(case, want=OUTPUTS, rows=None, states=None):
     are handed over as null and their buffers must come back untouched -> ``dict`` of device tensors (``None`` for those)."""
     from multimodalfilter_amd import _abi
 
-    dev = sc.dev()
     pick = (lambda x: x) if rows is None else (lambda x: None if x is None else x[rows])
     X, la, lb, y = (sc.to_device(pick(case[k])) for k in ("states", "log_a", "log_b", "truth"))
     if states is not None:
         X = states
     R, M, d = X.shape
-    bufs = {"crps": _Guarded(R, (d,), dev), "energy": _Guarded(R, (), dev), "spread": _Guarded(R, (d + 1,), dev)}
-    _abi.pf_scores(X, la, lb, y, *(bufs[k].view if k in want else None for k in OUTPUTS), scale=case["scale"])
-    torch.cuda.synchronize()
-    for k, b in bufs.items():
-        assert b.guards_intact(), f"a guard row of {k} was written (M={M} d={d} R={R})"
-        if k not in want:
-            assert b.untouched(), f"{k} was not asked for and was written (M={M} d={d} R={R})"
-    return {k: (bufs[k].view.clone() if k in want else None) for k in OUTPUTS}
+    return sg.guarded_call(lambda out: _abi.pf_scores(X, la, lb, y, **out, scale=case["scale"]), R,
+                           {"crps": (d,), "energy": (), "spread": (d + 1,)}, want, OUTPUTS, f"M={M} d={d} R={R}")
 
 
 def _hold(case, ref, got, what):
@@ -73,12 +64,7 @@ def test_every_allowed_combination_of_null_outputs_writes_only_what_was_asked_fo
     """With a truth every non-empty subset of the three outputs, without one the spread alone; what is written has the
     bits of the full call (the untouched buffers are checked inside ``_run``)."""
     case, _ = sk.family_case(M, 3, 3, "plain") if M <= sk.SMALL else (sk.make_case(M, 3, 3, "plain"), None)
-    full = _run(case)
-    for n in (1, 2):
-        for want in itertools.combinations(OUTPUTS, n):
-            got = _run(case, want)
-            for k in want:
-                assert _same_bits(got[k], full[k]), (M, want, k)
+    full = sg.assert_subsets_match_full(_run, case, OUTPUTS, what=(M,))
     alone = _run(dict(case, truth=None), ("spread",))
     assert _same_bits(alone["spread"], full["spread"])
 
@@ -93,15 +79,7 @@ def test_kernel_at_the_particle_limit():
 @pytest.mark.parametrize("M", [1, 65, 257, sk.I_BLOCK, sk.I_BLOCK + 1, sk.J_TILE + 1, 4096])
 def test_two_calls_and_a_row_alone_give_the_same_bits(M):
     for d, variant in ((1, "plain"), (3, "dead_row"), (4, "scaled")):
-        case = sk.make_case(M, d, 3, variant)
-        got = _run(case)
-        again = _run(case)
-        for k in OUTPUTS:
-            assert _same_bits(got[k], again[k]), (M, d, variant, k)
-        for r in range(3):
-            one = _run(case, rows=slice(r, r + 1))
-            for k in OUTPUTS:
-                assert _same_bits(one[k], got[k][r:r + 1]), (M, d, variant, r, k)
+        sg.assert_repeatable(_run, sk.make_case(M, d, 3, variant), OUTPUTS, range(3), (M, d, variant))
 
 
 def test_a_point_mass_has_no_spread_exactly():
