@@ -1348,6 +1348,53 @@ typedef struct MmfPfPredictiveArgs {
 int mmf_pf_predictive(const MmfPfPredictiveArgs* args /* host */, void* stream);
 size_t mmf_pf_predictive_workspace_bytes(int R, int M, int d);
 
+/* ---------------------------------------------------------------- Particle-posterior belief maps: the density rasterised on a grid
+ * The one analysis tool of the reference beside the RMSE tables of crossmodal/eval_helpers.py:148-160 is
+ * scripts/door_task/vis_pf_likelihoods.ipynb: a grid over two state dimensions around the true state, one map per modality.
+ * Every summary above reduces a particle set to numbers; this one is the picture of a multimodal belief: the 2-D marginal
+ * of the product-kernel density of "Particle-posterior density" on Gx x Gy cells.  In torch ops two (R, M, G) factor
+ * tensors and a bmm.  Purely additive to ABI 42: a struct and one symbol of their own, no workspace.
+ * Per row r (R rows, e.g. T * N, of M particles x_m = states[r, m, :]) with the host values (dx, dy) = dims, (Gx, Gy) = cells,
+ * (step_x, step_y) = step and the device values (c_x, c_y) = center[r, :], (h_x, h_y) = bandwidth[r, :]:
+ *   a_m, w_m = expf(a_m - max a), W_m = w_m / sum w      exactly as in "Particle-posterior scores"
+ *   u_i = fmaf(float(i) - 0.5f (Gx - 1), step_x, c_x)    the cell centres, in fp32; v_j likewise.  With an odd cell count the
+ *                                                        middle cell is the centre, bit for bit
+ *   density[r, j, i] = (2 pi h_x h_y)^-1 sum_{m live} W_m exp(-1/2 ((u_i - x_m,dx) / h_x)^2) exp(-1/2 ((v_j - x_m,dy) / h_y)^2)
+ * (R, Gy, Gx), x fastest.  The other d - 2 dimensions are not read: the map is the marginal of the density mmf_pf_density
+ * evaluates when bandwidth holds the two entries of its bandwidth_out.  The kernel forms an offset relative to the centre
+ * before anything is scaled -- (float(i) - 0.5f (Gx - 1)) step_x - (x_m,dx - c_x), then times the fp32 reciprocal of h_x -- so a
+ * set far from the origin maps like the same set at the origin; it accumulates the unnormalised w_m and scales a cell once,
+ * by float(1 / (2 pi h_x h_y sum w)).
+ *   - a particle with w_m = 0 is selected away, never multiplied away: its state row (NaN, by convention) is not read and
+ *     reaches no operand;
+ *   - a row without a live particle, a NaN in the row's centre, a bandwidth of the row that is not positive and finite:
+ *     that row's map is NaN, and only that row's.
+ * Determinism: every sum is taken in a fixed order and there are no floating-point atomics -- two calls give the same bits,
+ * and a row's bits depend on neither R nor the other rows (the plan is a function of (M, Gx, Gy) alone).
+ * Kernel plan: a workgroup of four waves per row and 64 x 64 block of cells (a 128-cell axis is two blocks), each wave
+ * holding the block as 2 x 2 accumulator tiles of the exact-fp32 MFMA v_mfma_f32_32x32x2_f32, the tile's columns along x.  Every
+ * workgroup forms max a and sum w (in double) over the whole row itself.  The waves take four contiguous chunks of
+ * ceil(M / 4) particles, staged 64 at a time through LDS as (x - c_x, y - c_y, w), dead particles as zeros; per MFMA of two
+ * particles a lane forms A = w exp(..v..) and B = exp(..u..) with one v_exp_f32 each: 128 M exponentials and 4096 M
+ * multiply-adds per full block.  The waves meet once at the end through LDS and are added in wave order.
+ * Limits, all decided on the host before any HIP call: null args / states / center / bandwidth / density, d outside 2 .. 4,
+ * a dims[k] outside 0 .. d - 1 or dims[0] == dims[1], a cells[k] outside 2 .. 128, a step[k] that is not positive and finite,
+ * M < 1, R < 0, the output overlapping an input -> MMF_EINVAL; M > 16384 or R times the blocks of a map beyond a 32-bit grid
+ * -> MMF_ETOOLARGE; R == 0 is a successful no-op. */
+typedef struct MmfPfRasterArgs {
+  int32_t R, M, d;                  /* R rows (e.g. T*N) of M particles */
+  int32_t dims[2];                  /* host values: the state dimensions along x and y, distinct, in 0 .. d - 1 */
+  int32_t cells[2];                 /* host values: (Gx, Gy), each in 2 .. 128 */
+  float step[2];                    /* host values: the cells' widths along x and y, positive and finite */
+  const float* states;              /* (R, M, d) */
+  const float* log_a;               /* (R, M) or null = 0 */
+  const float* log_b;               /* (R, M) or null = 0 (history: log_weights_in + log_likelihoods) */
+  const float* center;              /* (R, 2): where the row's window sits, along dims[0] and dims[1] */
+  const float* bandwidth;           /* (R, 2): the kernel's bandwidths along dims[0] and dims[1] */
+  float* density;                   /* (R, Gy, Gx) */
+} MmfPfRasterArgs;                  /* host struct holding device pointers */
+int mmf_pf_raster(const MmfPfRasterArgs* args /* host */, void* stream);
+
 /* ---------------------------------------------------------------- K6, fused: one network call of the training backward
  * Recompute (the forward pass's f16x3 arithmetic), backward data path and weight / bias gradients of ONE per-particle
  * network over N * M rows in one kernel (the dynamics network: three launches -- encoder forward, trunk, encoder

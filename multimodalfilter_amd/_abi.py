@@ -195,6 +195,24 @@ class MmfPfPredictiveArgs(Structure):
                 ("workspace", _FP), ("workspace_bytes", c_size_t)]
 
 
+RASTER_MAX_M = SUMMARY_MAX_M  # particles per row that mmf_pf_raster serves
+RASTER_MAX_CELLS = 128        # cells of a map along each axis at most (at least 2)
+RASTER_WAVES = 4              # the waves of mmf_pf_raster's workgroup: each takes a contiguous chunk of ceil(M / 4) particles
+RASTER_STAGE = 64             # the particles one of them stages at a time
+MEASURE_MAX_PARTICLES = 0x7FFFFFFF // 8  # particles (N * M) of one K2 launch: beyond it mmf_pf_measure* answer MMF_ETOOLARGE
+
+
+def as_float32(x: float) -> float:
+    """``x`` rounded to float32, as a host float of an argument struct is."""
+    return c_float(x).value
+
+
+class MmfPfRasterArgs(Structure):
+    _fields_ = [("R", c_int32), ("M", c_int32), ("d", c_int32), ("dims", c_int32 * 2), ("cells", c_int32 * 2),
+                ("step", ctypes.c_float * 2),
+                ("states", _FP), ("log_a", _FP), ("log_b", _FP), ("center", _FP), ("bandwidth", _FP), ("density", _FP)]
+
+
 class MmfTrainNet(Structure):
     _fields_ = [("packed", _FP), ("packed_f32", _FP), ("packed_t", _FP), ("head_w", _FP), ("pw", _FP), ("pb", _FP),
                 ("p_first", _FP), ("p_head", _FP), ("p_dout", _FP), ("p_traj", _FP), ("packed_dual", _FP)]
@@ -305,6 +323,7 @@ SIGNATURES = {
     "mmf_pf_distance_lds_bytes": (c_size_t, [c_int, c_int]),
     "mmf_pf_predictive": (c_int, [POINTER(MmfPfPredictiveArgs), c_void_p]),
     "mmf_pf_predictive_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "mmf_pf_raster": (c_int, [POINTER(MmfPfRasterArgs), c_void_p]),
     "mmf_pf_density": (c_int, [POINTER(MmfPfDensityArgs), c_void_p]),
     "mmf_pf_density_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "mmf_pf_modes": (c_int, [POINTER(MmfPfModesArgs), c_void_p]),
@@ -1302,6 +1321,29 @@ def pf_density(states, log_a, log_b, truth, *, rule="silverman", bandwidth=None,
     with _on(states):
         work = _summary_workspace(a, pf_density_workspace_bytes(R, M, d), states)
         _check(load().mmf_pf_density(ctypes.byref(a), stream_of(states)), "mmf_pf_density")
+
+
+def pf_raster(states, log_a, log_b, center, bandwidth, density, *, dims, step):
+    """Belief maps, the 2-D marginal of the product-kernel density of weighted particle sets on a grid (``mmf_pf_raster``,
+    include/mmf.h): ``states (..., M, d)`` -- ``R`` rows, the product of the leading sizes -- with log-weights ``log_a +
+    log_b``, each ``(..., M)`` or ``None`` (0; both ``None``: uniform), ``center (..., 2)`` and ``bandwidth (..., 2)`` along
+    ``dims = (dx, dy)``, two distinct state dimensions, and ``step``, two positive finite host floats -> ``density (..., Gy,
+    Gx)``, whose shape gives the cells (2 .. 128 each).  Written in place, so a contiguous slice of a larger tensor serves."""
+    lead, R, M, d = _summary_rows(states, log_a, log_b)
+    dims, step = [int(k) for k in dims], [float(s) for s in step]
+    if len(dims) != 2 or len(step) != 2:
+        raise MmfError(f"mmf_pf_raster takes two state dimensions and two steps, got dims = {dims!r}, step = {step!r}")
+    assert tuple(center.shape) == lead + (2,) and tuple(bandwidth.shape) == lead + (2,)
+    assert density.dim() == len(lead) + 2 and tuple(density.shape[:-2]) == lead
+    a = MmfPfRasterArgs()
+    a.R, a.M, a.d = R, M, d
+    for k in range(2):
+        a.dims[k], a.step[k] = dims[k], step[k]
+    a.cells[0], a.cells[1] = int(density.shape[-1]), int(density.shape[-2])
+    a.states, a.log_a, a.log_b = vp(states), vp(log_a), vp(log_b)
+    a.center, a.bandwidth, a.density = vp(center), vp(bandwidth), vp(density)
+    with _on(states):
+        _check(load().mmf_pf_raster(ctypes.byref(a), stream_of(states)), "mmf_pf_raster")
 
 
 def pf_modes_workspace_bytes(R: int, M: int, d: int) -> int:

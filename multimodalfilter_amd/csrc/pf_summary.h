@@ -1,5 +1,5 @@
 // What the summaries of a weighted particle set share (pf_quantiles.hip, pf_scores.hip, pf_density.hip, pf_modes.hip,
-// pf_distance.hip, pf_predictive.hip): the log-weight
+// pf_distance.hip, pf_predictive.hip, pf_raster.hip): the log-weight
 // a_m = log_a[m] + log_b[m] (a null pointer: 0) and the row maximum, the live-weight rule, the dealing of the O(M^2) pair
 // kernels, the sum of doubles over a workgroup in its fixed order, and the host's argument, aliasing and workspace checks.
 // Two rules keep a dead particle out of every sum, and they live here and nowhere else:

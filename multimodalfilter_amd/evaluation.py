@@ -731,6 +731,53 @@ def density_summary(record, start: int = START_TRUNCATION) -> Dict[str, float]:
     return out
 
 
+def map_axes(record):
+    """The cell centres of a maps record (``ParticleFilter.last_maps``): ``(x (T, N, Gx), y (T, N, Gy))`` float32 along
+    ``record.dims[0]`` and ``record.dims[1]``, by the rasteriser's own formula (``include/mmf.h``, ``mmf_pf_raster``):
+    ``density[t, n, j, i]`` sits at ``(x[t, n, i], y[t, n, j])``."""
+    if getattr(record, "density", None) is None or getattr(record, "center", None) is None or getattr(record, "step", None) is None:
+        raise ValueError("map_axes: the record has no density, center and step; take it from belief_maps")
+    return filters.map_cell_centres(record.center, record.step, record.cells)
+
+
+def map_summary(record, true=None, start: int = START_TRUNCATION) -> Dict[str, object]:
+    """Means of a maps record (``ParticleFilter.last_maps``) over the finite entries of the steps after the burn-in, over time
+    and trajectories: ``mass``, the share of the belief inside the window (a float); with ``true (T, N, d)`` also
+    ``peak_error``, the distance in the two map dimensions between the centre of the highest-density cell (the first among
+    equals) and the truth; with likelihood maps also ``agreement (K + 1,)``, the Bhattacharyya coefficient between the
+    normalised density map and each normalised ``exp(l - max l)`` map, the fused one last: does what sensor ``k`` says lie
+    where the belief is?  Steps with a NaN map are left out, like ``score_summary`` leaves them."""
+    density = getattr(record, "density", None)
+    if density is None or density.dim() != 4 or getattr(record, "mass", None) is None:
+        raise ValueError("map_summary: the record has no density (T, N, Gy, Gx) and mass; take it from belief_maps")
+    T, N, Gy, Gx = density.shape
+    out = {"mass": float(_finite_mean(record.mass, start))}
+    with torch.no_grad():
+        flat = density.reshape(T, N, Gy * Gx).to(torch.float64)
+        blank = ~torch.isfinite(flat).all(dim=-1)
+        nan = torch.full((T, N), math.nan, dtype=torch.float64, device=density.device)
+        if true is not None:
+            if not isinstance(true, torch.Tensor) or true.dim() != 3 or tuple(true.shape[:2]) != (T, N) or true.shape[2] <= max(record.dims):
+                raise ValueError(f"map_summary: true must be a (T, N, d) = ({T}, {N}, d) tensor with d > {max(record.dims)}, got "
+                                 f"{tuple(true.shape) if isinstance(true, torch.Tensor) else type(true).__name__}")
+            x, y = map_axes(record)
+            peak = torch.argmax(torch.where(blank[..., None], torch.zeros_like(flat), flat), dim=-1)  # (the first maximum)
+            at = torch.stack([torch.gather(x, 2, (peak % Gx)[..., None])[..., 0],
+                              torch.gather(y, 2, (peak // Gx)[..., None])[..., 0]], dim=-1).to(torch.float64)
+            y2 = true.to(device=density.device, dtype=torch.float64)[..., list(record.dims)]
+            out["peak_error"] = float(_finite_mean(torch.where(blank, nan, torch.linalg.vector_norm(at - y2, dim=-1)), start))
+        ll = getattr(record, "log_likelihood", None)
+        if ll is not None:
+            K1 = ll.shape[2]
+            p = flat / flat.sum(dim=-1, keepdim=True)
+            l = ll.reshape(T, N, K1, Gy * Gx).to(torch.float64)
+            q = torch.exp(l - l.max(dim=-1, keepdim=True).values)
+            q = q / q.sum(dim=-1, keepdim=True)
+            bc = torch.sqrt(p[:, :, None, :] * q).sum(dim=-1)                                     # (T, N, K + 1)
+            out["agreement"] = _finite_mean(torch.where(blank[..., None], nan[..., None], bc), start, tail=1).to(torch.float32)
+    return out
+
+
 def mode_errors(record, true: torch.Tensor, scale=None) -> Dict[str, torch.Tensor]:
     """Errors of a modes record (``ParticleFilter.last_modes``; ``run_filter(return_modes=K)``) against the true states
     ``(T, N, d)``: ``top (T, N)``, the Euclidean error of the heaviest mode; ``best (T, N)``, the least error over the

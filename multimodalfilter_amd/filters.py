@@ -46,6 +46,20 @@ class _DefaultDraws(int):
 
 _DEFAULT_DRAWS = _DefaultDraws(64)
 
+_MAP_CHUNK_STATES = 1 << 22  # grid states of one measurement launch of belief_maps(likelihoods=True): 64 MiB of them at d = 4
+
+
+def map_cell_centres(center: torch.Tensor, step, cells):
+    """The cell centres of belief maps (``include/mmf.h``, ``mmf_pf_raster``): ``center (..., 2)``, ``step`` and ``cells =
+    (Gx, Gy)`` -> ``(u (..., Gx), v (..., Gy))`` float32, ``u_i = fmaf(float(i) - 0.5f (Gx - 1), step_x, c_x)``.  The product
+    is exact in float64 and the sum is rounded once more on the way to float32: the middle cell of an odd count is the centre
+    bit for bit."""
+    axes = []
+    for k, (s, g) in enumerate(zip(step, cells)):
+        i = torch.arange(g, dtype=torch.float64, device=center.device) - 0.5 * (g - 1)
+        axes.append((i * float(s) + center[..., k, None].to(torch.float64)).to(torch.float32))
+    return axes[0], axes[1]
+
 
 class ParticleFilter(base.Filter):
     """Bootstrap particle filter (T1).
@@ -103,6 +117,10 @@ class ParticleFilter(base.Filter):
     ``belief_forecast(horizon, truth=, crps=)``: k-step-ahead forecasts from every recorded step -- the sets rolled out through
     the dynamics, the predictive Gaussian mixture of each lead with its mean (returned), covariance, log score, PIT and CRPS in
     closed form -> ``last_forecast`` (``mmf_pf_predictive``).
+    ``belief_maps(center, span, dims=, cells=, of=, bandwidth=, min_bandwidth=, likelihoods=, observations=)``: the recorded
+    beliefs as pictures -- the 2-D marginal of that density on a grid around ``center`` (returned: ``density (T, N, Gy, Gx)``)
+    for the predicted, filtered or smoothed sets and, with ``likelihoods``, every sensor's and the fused log-likelihood on the
+    same grid -> ``last_maps`` (``mmf_pf_raster``).
     Randomness comes from ``self.noise`` (``utils.NoiseSource``), never from global RNG state.
     """
 
@@ -147,6 +165,7 @@ class ParticleFilter(base.Filter):
         self.last_modalities = None   # belief_modalities(): each modality's share, evidence and own posterior on the recorded sets
         self.last_distance = None     # belief_distance(): two-sample distances between the recorded sets of two posteriors
         self.last_forecast = None     # belief_forecast(): the k-step-ahead predictive mixtures of the recorded sets, scored
+        self.last_maps = None         # belief_maps(): the recorded beliefs (and the likelihoods) rasterised on a grid
         self.record_transition_moments = False  # smooth(method="marginal") adds the two-slice residual moments to last_smoothed
         self._step_history = None
         self.use_native_loop = True   # False: forward_loop keeps the step-by-step Python loop
@@ -1057,6 +1076,139 @@ class ParticleFilter(base.Filter):
         self.last_modes = base.belief_record(modes=modes, index=index, mass=mass, mean=mean, count=count, labels=labels,
                                              parent=parent, bandwidth=h, of=of, rule=rule, link_radius=tau, max_modes=K)
         return modes
+
+    @engine.checked_loop
+    def belief_maps(self, center: torch.Tensor, span, *, dims=(0, 1), cells=64, of: str = "filtered", bandwidth="silverman",
+                    min_bandwidth=1e-6, likelihoods: bool = False, observations=None) -> torch.Tensor:
+        """The recorded beliefs as pictures (``mmf_pf_raster``, ``include/mmf.h``): per step a grid of ``cells`` over the two
+        state dimensions ``dims`` around ``center``, holding the 2-D marginal of the kernel density of ``belief_density`` --
+        what shows a multimodal belief as two hills where every other summary gives numbers.  Returns ``density (T, N, Gy,
+        Gx)``, x fastest, rasterised in HIP with the exact-fp32 MFMA; no ``(M, G)`` factor array is formed.
+        ``center (T, N, d)``: where each step's window sits -- the truth, or the estimates ``forward_loop`` returned.
+        ``span``: two positive finite floats, the window's widths along ``dims[0]`` and ``dims[1]`` in the state's units; a
+        cell is ``span / cells`` wide.  ``cells``: an int or ``(Gx, Gy)``, each in 2 .. 128; with an odd count the middle
+        cell's centre is ``center`` bit for bit (``evaluation.map_axes`` gives every cell's).
+        ``of``: ``"filtered"`` and ``"smoothed"`` mean what they mean for ``belief_density``; ``"predicted"`` is the history's
+        ``states`` under ``log_weights_in`` alone, the belief before the step's measurement -- so three calls give prior,
+        likelihood and posterior on one grid.  ``bandwidth`` and ``min_bandwidth`` are ``belief_density``'s, and so are the
+        bandwidths (``mmf_pf_density`` asked for nothing else: it stops after the moments): the map is the marginal of the
+        density ``belief_density`` reports.
+        ``likelihoods=True`` adds ``log_likelihood (T, N, K + 1, Gy, Gx)``: the measurement networks evaluated on the grid
+        -- ``dims`` at the cell centres, every other dimension at ``center``'s value --, unnormalised log-likelihoods and no
+        densities.  Under a ``CrossmodalParticleFilterMeasurementModel`` the ``K`` enabled unimodal maps
+        (``modality_log_likelihoods``, every network in one launch) and, last, the fused ``logsumexp_k(beta_k + l_k)``, from
+        the observations and ``enabled_models`` the run left in the history, as ``belief_modalities`` reads them; under any
+        other measurement model one map of ``measurement_model(states=grid, observations=observations)``, ``observations (T,
+        N, ...)`` then being required (given, they are read under a crossmodal model too).  Rows go in chunks within K2's
+        limits, and the status word is cleared on entry and checked on the way out: a grid state that leaves the f16x3 range
+        raises here.
+        Leaves ``last_maps``: ``density``, ``mass (T, N)`` -- ``sum density step_x step_y``, the share of the belief inside
+        the window --, ``center (T, N, 2)``, ``step``, ``dims``, ``cells``, ``span`` (tuples), ``bandwidth (T, N, 2)``, ``of``,
+        ``rule`` and, with ``likelihoods``, ``log_likelihood``, ``modalities`` (the enabled models' indices; ``(0,)`` without
+        a fusion) and ``log_weights (T, N, K)`` (``beta``, or ``None``).  Draws no noise and leaves every other ``last_*``
+        record as it is.  Evaluation mode only.  A step without a live particle or with a NaN in ``center[..., dims]``
+        gives a NaN map."""
+        from .base_models import CrossmodalParticleFilterMeasurementModel  # (base_models imports this module)
+
+        who = "belief_maps"
+        if self.training:
+            raise RuntimeError(f"{who}: the training (autograd) paths keep no history; call .eval() first")
+        if of not in ("predicted", "filtered", "smoothed"):
+            raise ValueError(f"{who}: of must be 'predicted', 'filtered' or 'smoothed', got {of!r}")
+        states, log_a, log_b, _ = self._summary_inputs(who, "filtered" if of == "predicted" else of, None,
+                                                       "mmf_pf_raster serves at most {}")
+        if of == "predicted":
+            log_b = None  # (the belief before the step's measurement)
+        T, N, M, d = states.shape
+        whole = lambda v: not isinstance(v, bool) and isinstance(v, numbers.Integral)
+        real = lambda v: not isinstance(v, bool) and isinstance(v, numbers.Real) and 0.0 < float(v) < math.inf
+        pair = lambda v: list(v) if isinstance(v, (tuple, list)) else []
+        if d < 2:
+            raise ValueError(f"{who}: a map needs two state dimensions, the state has {d}")
+        if len(pair(dims)) != 2 or not all(whole(k) and 0 <= k < d for k in dims) or dims[0] == dims[1]:
+            raise ValueError(f"{who}: dims must be two distinct state dimensions in 0 .. {d - 1}, got {dims!r}")
+        grid = (cells, cells) if whole(cells) else tuple(pair(cells))
+        if len(grid) != 2 or not all(whole(g) and 2 <= g <= _abi.RASTER_MAX_CELLS for g in grid):
+            raise ValueError(f"{who}: cells must be an int or (Gx, Gy), each in 2 .. {_abi.RASTER_MAX_CELLS}, got {cells!r}")
+        dims, (Gx, Gy) = (int(dims[0]), int(dims[1])), (int(grid[0]), int(grid[1]))
+        step = ()
+        if len(pair(span)) == 2 and all(real(s) for s in span):
+            step = tuple(_abi.as_float32(float(s) / g) for s, g in zip(span, (Gx, Gy)))  # (the kernel's host floats)
+        if len(step) != 2 or not all(real(s) for s in step):
+            raise ValueError(f"{who}: span must be two positive finite floats (with span / cells positive and finite in "
+                             f"float32), got {span!r}")
+        if not isinstance(center, torch.Tensor) or tuple(center.shape) != (T, N, d):
+            raise ValueError(f"{who}: center must be a (T, N, d) = ({T}, {N}, {d}) tensor, got "
+                             f"{tuple(center.shape) if isinstance(center, torch.Tensor) else type(center).__name__}")
+        rule, fixed, floor = self._density_bandwidths(who, bandwidth, min_bandwidth, d)
+        meas, obs = self.measurement_model, None
+        if likelihoods:
+            crossmodal = isinstance(meas, CrossmodalParticleFilterMeasurementModel)
+            h = self.last_history
+            obs = observations
+            if crossmodal:
+                recorded = getattr(h, "enabled_models", None)
+                if obs is None:
+                    obs = getattr(h, "observations", None)
+                if recorded is not None and tuple(meas.enabled_models) != tuple(recorded):
+                    raise ValueError(f"{who}: enabled_models = {list(meas.enabled_models)} now, {list(recorded)} when the history "
+                                     "was recorded: the maps would be another fusion's; run forward_loop again")
+            if obs is None:
+                raise ValueError(f"{who}(likelihoods=True): no observations to evaluate the measurement model on: "
+                                 + ("the history holds none; " if crossmodal else f"{type(meas).__name__} leaves none in the history; ")
+                                 + "pass observations=, the (T, N, ...) observations of the run")
+            leaves = list(obs.values()) if isinstance(obs, dict) else [obs]
+            if not all(isinstance(x, torch.Tensor) and tuple(x.shape[:2]) == (T, N) for x in leaves):
+                raise ValueError(f"{who}: every tensor of observations must lead with (T, N) = ({T}, {N})")
+        dev = states.device
+        with torch.no_grad():
+            c = center.detach().to(device=dev, dtype=torch.float32).contiguous()
+            c2 = c[..., list(dims)].contiguous()
+            h_all = torch.empty((T, N, d), dtype=torch.float32, device=dev)
+            _abi.pf_density(states, log_a, log_b, None, rule=rule, bandwidth=fixed, min_bandwidth=floor, bandwidth_out=h_all)
+            h2 = h_all[..., list(dims)].contiguous()
+            density = torch.empty((T, N, Gy, Gx), dtype=torch.float32, device=dev)
+            _abi.pf_raster(states, log_a, log_b, c2, h2, density, dims=dims, step=step)
+            mass = (density.to(torch.float64).sum(dim=(-1, -2)) * (step[0] * step[1])).to(torch.float32)
+            extra = self._likelihood_maps(c, dims, step, (Gx, Gy), obs) if likelihoods else {}
+        self.last_maps = base.belief_record(density=density, mass=mass, center=c2.view(T, N, 2), step=step, dims=dims,
+                                            cells=(Gx, Gy), span=(float(span[0]), float(span[1])), bandwidth=h2.view(T, N, 2),
+                                            of=of, rule=rule, **extra)
+        return density
+
+    def _likelihood_maps(self, center, dims, step, cells, observations):
+        """The likelihood part of ``belief_maps``: ``center (T, N, d)`` float32 on the device and ``observations (T, N, ...)``
+        -> the ``log_likelihood (T, N, K + 1, Gy, Gx)``, ``modalities`` and ``log_weights`` of the record.  The grid states
+        hold ``dims`` at the cell centres and every other dimension at ``center``'s value; the rows go in chunks of at most
+        ``_MAP_CHUNK_STATES`` grid states, within what a K2 launch takes."""
+        from .base_models import CrossmodalParticleFilterMeasurementModel  # (base_models imports this module)
+
+        meas = self.measurement_model
+        crossmodal = isinstance(meas, CrossmodalParticleFilterMeasurementModel)
+        T, N, d = center.shape
+        (Gx, Gy), R = cells, T * N
+        u, v = map_cell_centres(center[..., list(dims)], step, cells)
+        flat = tree_map(observations, lambda x: x.reshape((R,) + tuple(x.shape[2:])))
+        rows = max(1, min(_abi.MEASURE_MAX_PARTICLES, _MAP_CHUNK_STATES) // (Gx * Gy))
+        maps, betas, enabled = [], [], (0,)
+        for r0 in range(0, R, rows):
+            r1 = min(R, r0 + rows)
+            g = center.reshape(R, d)[r0:r1, None, None, :].repeat(1, Gy, Gx, 1)
+            g[..., dims[0]] = u.view(R, Gx)[r0:r1, None, :]
+            g[..., dims[1]] = v.view(R, Gy)[r0:r1, :, None]
+            g = g.view(r1 - r0, Gy * Gx, d)
+            o = tree_map(flat, lambda x: x[r0:r1])
+            if crossmodal:
+                logliks, beta, enabled = meas.modality_log_likelihoods(g, meas.encode_observations(o))
+                ll = torch.stack(logliks, dim=1)                          # (rows, K, Gy Gx)
+                fused = torch.logsumexp(ll if beta is None else ll + beta[:, :, None], dim=1, keepdim=True)
+                maps.append(torch.cat([ll, fused], dim=1))
+                betas.append(beta)
+            else:
+                maps.append(meas(states=g, observations=o).to(torch.float32).reshape(r1 - r0, 1, Gy * Gx))
+        K1 = maps[0].shape[1]
+        return dict(log_likelihood=torch.cat(maps).view(T, N, K1, Gy, Gx), modalities=tuple(enabled),
+                    log_weights=torch.cat(betas).view(T, N, K1 - 1) if betas and betas[0] is not None else None)
 
     @engine.checked_loop
     def belief_modalities(self) -> torch.Tensor:
