@@ -1558,6 +1558,62 @@ typedef struct MmfPfTrainFinalizeArgs {
 } MmfPfTrainFinalizeArgs;
 int mmf_pf_train_finalize(const MmfPfTrainFinalizeArgs* args /* host */, void* stream);
 
+/* ---------------------------------------------------------------- Training on the particle set: the mixture log score and its gradients
+ * /root/reference/crossmodal/train_helpers.py:124-162 (torchfilter.train.train_filter) trains a filter on the mean-squared
+ * error of its estimates and nothing else; the differentiable-filter literature (Jonschkowski et al. 2018, Kloss et al. 2021)
+ * trains particle filters on the negative log-likelihood of the true state under a Gaussian mixture placed on the particles,
+ * which sees spread and multimodality where the mean's MSE is blind.  Two additions, purely additive to ABI 42 (a struct and two
+ * symbols of their own; MmfPfTrainArgs keeps its size):
+ *
+ * (1) mmf_pf_train_backward_sets: mmf_pf_train_backward with the direct loss gradients of every step's weighted set.
+ *   g_states_steps[t] (N, M, d) and g_logw_steps[t] (N, M) are dL/d states[t+1] and dL/d logw[t+1] of MmfPfTrainArgs -- the set
+ *   after step t, the one est_t is taken from, with normalised log-weights.  In the t = T-1 .. 0 loop the log-weight gradient
+ *   handed to mmf_pf_reweight_backward is (the later step's) + g_logw_steps[t] -- at the last step g_logw_steps[t] alone --
+ *   and the state gradient is (through est_t) + (the later step's) + g_states_steps[t], in that order.  Either pointer may be
+ *   null; both null is mmf_pf_train_backward: the same launches, the same bits (one body serves both symbols).
+ *
+ * (2) mmf_pf_set_nll: the loss itself.  Per row r (R rows, e.g. T * N: one step of one trajectory) of M particles
+ *   x_m = states[r, m, :] with log-weights a_m = logw[r, m] (not necessarily normalised), the true state y = truth[r, :] and the
+ *   component scales sigma_j = scale[j] > 0 (device memory, not checked), the mixture sum_m p_m N(y; x_m, diag sigma^2):
+ *     z_mj = (y_j - x_mj) / sigma_j              e_m = a_m - 1/2 sum_j z_mj^2
+ *     nll  = logsumexp_m a_m - logsumexp_m e_m + sum_j log sigma_j + (d / 2) log 2 pi
+ *     r = softmax(e)      p = softmax(a)
+ *     g_states[r, m, j]  = g -r_m z_mj / sigma_j           d nll / d x_mj
+ *     g_logw[r, m]       = g (p_m - r_m)                   d nll / d a_m
+ *     g_log_scale[r, j]  = g (1 - sum_m r_m z_mj^2)        d nll / d log sigma_j, PER ROW: the caller sums the rows (and divides
+ *                                                          by sigma_j for d / d sigma_j)
+ *   with g = g_nll[r] (null: 1), multiplied last: a power of two scales every gradient exactly.  nll is what
+ *   -mmf_pf_density's log_score reports with bandwidth = sigma fixed, so a filter is trained on what it is evaluated with.
+ *   Both log-sum-exps are true ones, each about its own maximum: a truth 50 sigma from every particle, or sigma = 1e-3 with the
+ *   truth 1.0 away, gives a finite nll and finite gradients.  The exponents and the sums are fp32, the last combination double.
+ *   - a_m = -inf (or NaN) is a dead particle: it contributes exactly nothing, its state row (NaN, by convention) is not read,
+ *     and its gradients are written as 0;
+ *   - a row without a live particle, with a NaN in y, or whose every e_m is -inf: nll = NaN and all gradients of the row are 0.
+ *   A forward call asks for nll alone; a backward call asks for gradients and recomputes (4 (d + 1) bytes read per particle,
+ *   as many written).  Determinism: fixed summation order, no floating-point atomics -- two calls give the same bits, and row
+ *   r's bits depend on neither R, nor its place in the batch, nor on which outputs are asked for.
+ *   Kernel plan: up to M = 256 a wave owns a row (four rows to a workgroup of 256 threads: the reference trains on hundreds of
+ *   rows of 30 particles), beyond that a workgroup of 512 threads does; three passes over the row (the maxima, the sums, the
+ *   per-particle gradients), which re-read it through the caches -- nothing is staged per particle in LDS, so M is bounded only
+ *   by int32.  Wave sums are the DPP butterfly, the waves are added in ascending order.
+ *   Limits, decided on the host before any HIP call: null args / states / logw / truth / scale, all four outputs null, d outside
+ *   1 .. 4, M < 1, R < 0, an output overlapping an input or another output -> MMF_EINVAL; R == 0 is a successful no-op. */
+typedef struct MmfPfSetNllArgs {
+  int32_t R, M, d;                  /* R rows (e.g. T*N) of M particles */
+  const float* states;              /* (R, M, d) */
+  const float* logw;                /* (R, M) */
+  const float* truth;               /* (R, d) */
+  const float* scale;               /* (d), device: the component scales sigma */
+  const float* g_nll;               /* (R) or null = 1 */
+  float* nll;                       /* (R) or null */
+  float* g_states;                  /* (R, M, d) or null */
+  float* g_logw;                    /* (R, M) or null */
+  float* g_log_scale;               /* (R, d) or null */
+} MmfPfSetNllArgs;                  /* host struct holding device pointers */
+int mmf_pf_set_nll(const MmfPfSetNllArgs* args /* host */, void* stream);
+int mmf_pf_train_backward_sets(const MmfPfTrainArgs* args /* host */, const float* g_states_steps /* (T, N, M, d) or null */,
+                               const float* g_logw_steps /* (T, N, M) or null */, void* stream);
+
 /* ---------------------------------------------------------------- K7: per-trajectory MLP programs
  * The N-row networks around the filters (vector encoders layers.py:11-40,66-95; PF weight
  * model crossmodal_pf.py:74-106; virtual sensor kf.py:81-126; EKF weight model

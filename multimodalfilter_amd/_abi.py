@@ -232,6 +232,15 @@ class MmfPfTrainArgs(Structure):
                 ("fused", c_int32), ("fused_act", _FP), ("fused_g_act", _FP), ("fused_sets", c_int32)]
 
 
+SET_NLL_WAVE_M = 256  # mmf_pf_set_nll: a wave owns a row up to here, a workgroup beyond (csrc/pf_set_loss.hip: kWaveM)
+
+
+class MmfPfSetNllArgs(Structure):
+    _fields_ = [("R", c_int32), ("M", c_int32), ("d", c_int32),
+                ("states", _FP), ("logw", _FP), ("truth", _FP), ("scale", _FP), ("g_nll", _FP),
+                ("nll", _FP), ("g_states", _FP), ("g_logw", _FP), ("g_log_scale", _FP)]
+
+
 class MmfTrainFusedArgs(Structure):
     _fields_ = [("packed_dual", _FP), ("n_res", c_int32), ("kind", c_int32), ("d", c_int32), ("N", c_int32), ("M", c_int32),
                 ("n_slots", c_int32), ("states", _FP), ("traj_bias", _FP), ("d_out", _FP), ("g_next", _FP), ("d_raw", _FP),
@@ -371,6 +380,8 @@ SIGNATURES = {
     "mmf_particle_net_weight_grads_acc": (c_int, [_FP, _FP, _FP, _FP, c_int, c_int, c_int, c_int, c_void_p]),
     "mmf_pf_train_forward": (c_int, [POINTER(MmfPfTrainArgs), c_void_p]),
     "mmf_pf_train_backward": (c_int, [POINTER(MmfPfTrainArgs), c_void_p]),
+    "mmf_pf_train_backward_sets": (c_int, [POINTER(MmfPfTrainArgs), c_void_p, c_void_p, c_void_p]),
+    "mmf_pf_set_nll": (c_int, [POINTER(MmfPfSetNllArgs), c_void_p]),
     "mmf_particle_net_train_fused": (c_int, [POINTER(MmfTrainFusedArgs), c_void_p]),
     "mmf_particle_net_train_fused_multi": (c_int, [POINTER(MmfTrainFusedArgs), c_int, c_void_p]),
     "mmf_particle_net_train_backward": (c_int, [_FP, _FP, c_int, c_int, _FP, _FP, _FP, _FP, c_int, c_int, c_void_p]),
@@ -747,6 +758,39 @@ def pf_train_forward(args: MmfPfTrainArgs, like: torch.Tensor):
 def pf_train_backward(args: MmfPfTrainArgs, like: torch.Tensor):
     with _on(like):
         _check(load().mmf_pf_train_backward(ctypes.byref(args), stream_of(like)), "mmf_pf_train_backward")
+
+
+def pf_train_backward_sets(args: MmfPfTrainArgs, g_states_steps, g_logw_steps, like: torch.Tensor):
+    """``mmf_pf_train_backward`` with the direct loss gradients of every step's weighted set: ``g_states_steps (T, N, M, d)``
+    and ``g_logw_steps (T, N, M)``, either ``None`` (both ``None``: ``mmf_pf_train_backward``, launch for launch)."""
+    T, N, M, d = args.T, args.N, args.M, args.d
+    assert g_states_steps is None or tuple(g_states_steps.shape) == (T, N, M, d)
+    assert g_logw_steps is None or tuple(g_logw_steps.shape) == (T, N, M)
+    with _on(like):
+        _check(load().mmf_pf_train_backward_sets(ctypes.byref(args), ptr(g_states_steps), ptr(g_logw_steps), stream_of(like)),
+               "mmf_pf_train_backward_sets")
+
+
+def pf_set_nll(states, logw, truth, scale, g_nll=None, *, nll=None, g_states=None, g_logw=None, g_log_scale=None):
+    """The mixture log score of weighted particle sets against true states and its closed-form gradients (``mmf_pf_set_nll``,
+    include/mmf.h): ``states (..., M, d)`` -- ``R`` rows, the product of the leading sizes --, ``logw (..., M)``, ``truth (...,
+    d)``, the component scales ``scale (d)`` on the device and ``g_nll (...)`` or ``None`` (1) -> ``nll (...)``, ``g_states``,
+    ``g_logw`` like their inputs and ``g_log_scale (..., d)`` per row, each of which may be ``None`` (not all four).  The
+    outputs are written in place."""
+    lead, (M, d) = tuple(states.shape[:-2]), states.shape[-2:]
+    R = 1
+    for n in lead:
+        R *= n
+    assert tuple(logw.shape) == lead + (M,) and tuple(truth.shape) == lead + (d,) and tuple(scale.shape) == (d,)
+    assert g_nll is None or tuple(g_nll.shape) == lead
+    for out, shape in ((nll, lead), (g_states, lead + (M, d)), (g_logw, lead + (M,)), (g_log_scale, lead + (d,))):
+        assert out is None or tuple(out.shape) == shape
+    a = MmfPfSetNllArgs()
+    a.R, a.M, a.d = R, M, d
+    a.states, a.logw, a.truth, a.scale, a.g_nll = vp(states), vp(logw), vp(truth), vp(scale), vp(g_nll)
+    a.nll, a.g_states, a.g_logw, a.g_log_scale = vp(nll), vp(g_states), vp(g_logw), vp(g_log_scale)
+    with _on(states):
+        _check(load().mmf_pf_set_nll(ctypes.byref(a), stream_of(states)), "mmf_pf_set_nll")
 
 
 def particle_net_train_fused(args: MmfTrainFusedArgs, like: torch.Tensor):

@@ -16,6 +16,10 @@
 // 256 MiB Infinity Cache were measured and LOSE (32,768 rows: 65.7 ms per step, 262,144 rows: 45.0): each
 // small launch re-stages 150 KB of weights per workgroup and half-fills the chip.  The caller sizes chunks
 // for memory (engine.TRAIN_CHUNK_ROWS).
+//
+// Losses on the particle sets themselves (include/mmf.h, "Training on the particle set"): the kept sets are handed out as
+// differentiable outputs, and mmf_pf_train_backward_sets takes their direct gradients back -- one add into the log-weight
+// gradient before a step's K1 backward, one into the state gradient after it.  Without them it is mmf_pf_train_backward.
 #include "mmf_common.h"
 
 namespace {
@@ -137,7 +141,11 @@ extern "C" int mmf_pf_train_forward(const MmfPfTrainArgs* a, void* stream) {
   return 0;
 }
 
-extern "C" int mmf_pf_train_backward(const MmfPfTrainArgs* a, void* stream) {
+namespace {
+
+// the backward recursion; gs_steps (T, N, M, d) / gl_steps (T, N, M) or null: the direct loss gradients of every step's set
+// (mmf_pf_train_backward_sets).  Both null: mmf_pf_train_backward, launch for launch
+int train_backward(const MmfPfTrainArgs* a, const float* gs_steps, const float* gl_steps, void* stream) {
   int rc = check(a);
   if (rc) return rc;
   if (!a->g_estimates || !a->stash || (!a->fused && (!a->mask || !a->raw)) || !a->dz || !a->d_raw || !a->g_states_a || !a->g_states_b || !a->g_logw_a ||
@@ -229,11 +237,25 @@ extern "C" int mmf_pf_train_backward(const MmfPfTrainArgs* a, void* stream) {
     const float* x = a->states + t * R * d;          // input of step t's dynamics
     const float* xn = a->states + (t + 1) * R * d;   // its output: what was measured and averaged
     // K1 (mode 0) backward: d_a = dL/d(logw[t] + loglik), g_tot = dL/d states[t+1] through the estimate
-    rc = mmf_pf_reweight_backward(a->logw + (t + 1) * R, xn, a->g_estimates + t * row * d, last ? nullptr : g_lw, d_a, g_tot,
+    // the set's own log-weight gradient joins the later step's (whose buffer is free to take it: it is overwritten next)
+    const float* g_lw_in = last ? nullptr : g_lw;
+    if (gl_steps) {
+      if (last) {
+        g_lw_in = gl_steps + t * R;
+      } else {
+        add_kernel<<<blocks(R), kThreads, 0, hs>>>(g_lw, gl_steps + t * R, R);
+        MMF_CHECK_LAUNCH();
+      }
+    }
+    rc = mmf_pf_reweight_backward(a->logw + (t + 1) * R, xn, a->g_estimates + t * row * d, g_lw_in, d_a, g_tot,
                                   N, M, d, stream);
     if (rc) return rc;
     if (!last) {
       add_kernel<<<blocks(R * d), kThreads, 0, hs>>>(g_tot, g_next, R * d);
+      MMF_CHECK_LAUNCH();
+    }
+    if (gs_steps) {  // after the estimate path and the later step's: the order is fixed
+      add_kernel<<<blocks(R * d), kThreads, 0, hs>>>(g_tot, gs_steps + t * R * d, R * d);
       MMF_CHECK_LAUNCH();
     }
     const float* ll = a->ll_steps + static_cast<size_t>(t) * K * R;
@@ -333,6 +355,15 @@ extern "C" int mmf_pf_train_backward(const MmfPfTrainArgs* a, void* stream) {
     if (e != hipSuccess) return static_cast<int>(e);
   }
   return 0;
+}
+
+}  // namespace
+
+extern "C" int mmf_pf_train_backward(const MmfPfTrainArgs* a, void* stream) { return train_backward(a, nullptr, nullptr, stream); }
+
+extern "C" int mmf_pf_train_backward_sets(const MmfPfTrainArgs* a, const float* g_states_steps, const float* g_logw_steps,
+                                          void* stream) {
+  return train_backward(a, g_states_steps, g_logw_steps, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

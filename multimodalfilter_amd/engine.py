@@ -4,6 +4,7 @@ the per-particle networks, and the launches of K2 / K5 (``csrc/particle_net.hip`
 import contextlib
 import ctypes
 import functools
+import math
 import os
 import threading
 import warnings
@@ -693,11 +694,18 @@ class PfTrainLoopFunction(torch.autograd.Function):
     ``apply(nets, T, N, M, states0 (N, M, d), logw0 (N, M), eps (T, N, M, d), tril (d, d), dyn_bias (T*N, 64),
     beta (T*N, K_all) | empty, *meas_biases (T*N, 64), *params)`` -> ``(estimates (T, N, d), states_T, logw_T)``
     with ``nets = (dyn_net, [(meas_net, beta column | None)], K_all)`` and ``params`` the concatenated
-    ``_sources()`` of the dynamics network and of every measurement network."""
+    ``_sources()`` of the dynamics network and of every measurement network.
+
+    ``nets = (dyn_net, [...], K_all, True)`` (``ParticleFilter.keep_training_sets``): two more outputs, ``states (T, N, M, d)``
+    and ``log_weights (T, N, M)`` -- every step's weighted set, the one its estimate is taken from, as differentiable views of
+    the buffers the recursion keeps anyway -- whose gradients the backward hands to ``mmf_pf_train_backward_sets``; an output
+    the loss does not use arrives as ``None``, not as a block of zeros.  Without the fourth entry: today's three outputs and
+    ``mmf_pf_train_backward``."""
 
     @staticmethod
     def forward(ctx, nets, T, N, M, states0, logw0, eps, tril, dyn_bias, beta, *rest):
-        dyn_net, meas, K_all = nets
+        dyn_net, meas, K_all = nets[:3]
+        ctx.keep_sets = len(nets) > 3 and bool(nets[3])
         K = len(meas)
         meas_biases, params = rest[:K], rest[K:]
         dev = states0.device
@@ -740,11 +748,14 @@ class PfTrainLoopFunction(torch.autograd.Function):
         ctx.save_for_backward(*[p.detach() for p in params])
         sT, lT = states[T], logw[T]
         ctx.mark_non_differentiable(sT, lT)
+        if ctx.keep_sets:
+            ctx.set_materialize_grads(False)
+            return est, sT, lT, states[1:], logw[1:]
         return est, sT, lT
 
     @staticmethod
-    def backward(ctx, g_est, _g_states, _g_logw):
-        dyn_net, meas, K_all = ctx.nets
+    def backward(ctx, g_est, _g_states, _g_logw, g_set_states=None, g_set_logw=None):
+        dyn_net, meas, K_all = ctx.nets[:3]
         T, N, M, d = ctx.shape
         keep = ctx.keep
         params = ctx.saved_tensors
@@ -797,6 +808,8 @@ class PfTrainLoopFunction(torch.autograd.Function):
             col = meas[k][1]
             if keep["beta"] is not None and col is not None:
                 a.meas_logw[k] = ctypes.c_void_p(keep["beta"].data_ptr() + 4 * col)
+        if g_est is None:  # (keep_sets: a loss on the sets alone)
+            g_est = torch.zeros((T, N, d), dtype=torch.float32, device=dev)
         g_est = g_est.to(torch.float32).contiguous()
         A = lambda *shape: torch.empty(shape, dtype=torch.float16, device=dev)   # the recompute buffers are f16 (ABI 39)
         if fused:  # only the three (C, 64) row slots of the narrow reductions + the dynamics' encoder hand-offs
@@ -816,7 +829,11 @@ class PfTrainLoopFunction(torch.autograd.Function):
         a.dz_scale = P(scratch["dz_scale"])
         a.g_states_a, a.g_states_b, a.g_logw_a, a.g_logw_b = P(scratch["ga"]), P(scratch["gb"]), P(scratch["la"]), P(scratch["lb"])
         a.d_states0, a.d_logw0 = P(scratch["d_states0"]), P(scratch["d_logw0"])
-        _abi.pf_train_backward(a, g_est)
+        if ctx.keep_sets:
+            g_sets = [None if g is None else g.to(torch.float32).contiguous() for g in (g_set_states, g_set_logw)]
+            _abi.pf_train_backward_sets(a, g_sets[0], g_sets[1], g_est)
+        else:
+            _abi.pf_train_backward(a, g_est)
         # the partial sums -> parameter gradients in _sources() order, d hoisted terms, d modality log-weights: two launches
         # per network (mmf_pf_train_finalize)
         param_grads, bias_grads, d_beta = [], [], None
@@ -876,6 +893,60 @@ def dynamics_with_jacobian_autograd(net: PackedParticleNet, x: torch.Tensor, tra
     A = torch.eye(d, dtype=x.dtype, device=x.device) + sg[:, :, None] * J_dir \
         + (dirp * sg * (1.0 - sg))[:, :, None] * J_gate[:, None, :]
     return x_next, A
+
+
+def particle_set_nll_torch(states: torch.Tensor, log_weights: torch.Tensor, truth: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """``ParticleSetNllFunction``'s definition (include/mmf.h, "Training on the particle set") in torch ops, on any device: a
+    dead particle (log-weight ``-inf`` or NaN) is masked out of both log-sum-exps BEFORE its state row is touched, so its
+    gradients are 0 where plain autograd gives NaN; a row without a live particle, or with a NaN in the truth, is NaN with
+    zero gradients."""
+    d = states.shape[-1]
+    live = log_weights > -math.inf
+    ok = live.any(-1) & ~torch.isnan(truth).any(-1)
+    keep = live & ok[..., None]
+    x = torch.where(keep[..., None], states, torch.zeros_like(states))
+    a = torch.where(keep, log_weights, torch.zeros_like(log_weights))
+    y = torch.where(ok[..., None], truth, torch.zeros_like(truth))
+    z = (y[..., None, :] - x) / scale[..., None, :]   # (scale (d), or one row of scales per set (..., d))
+    neg = torch.full_like(a, -math.inf)
+    e = torch.where(keep, a - 0.5 * (z * z).sum(-1), neg)
+    a = torch.where(keep, a, neg)
+    # a row that is not ok keeps one finite entry in each log-sum-exp, so that nothing NaN enters the graph
+    first = torch.zeros_like(keep)
+    first[..., 0] = True
+    pad = first & ~ok[..., None]
+    a, e = torch.where(pad, torch.zeros_like(a), a), torch.where(pad, torch.zeros_like(e), e)
+    nll = torch.logsumexp(a, dim=-1) - torch.logsumexp(e, dim=-1) + torch.log(scale).sum(-1) + 0.5 * d * math.log(2.0 * math.pi)
+    return torch.where(ok, nll, torch.full_like(nll, math.nan))
+
+
+class ParticleSetNllFunction(torch.autograd.Function):
+    """The mixture log score of weighted particle sets against true states (``mmf_pf_set_nll``): ``(states (..., M, d),
+    log_weights (..., M), truth (..., d), scale (d)) -> nll (...)``.  The backward is the same kernel asked for its closed-form
+    gradients (it recomputes the row); ``scale`` gets its gradient (the per-row ``d / d log sigma`` summed over the rows and
+    divided by ``sigma``), the truth gets none."""
+
+    @staticmethod
+    def forward(ctx, states, log_weights, truth, scale):
+        require_device(states, "ParticleSetNllFunction")
+        f32 = lambda t: t.detach().to(torch.float32).contiguous()
+        st, lw, y, sc = f32(states), f32(log_weights), f32(truth), f32(scale)
+        nll = torch.empty(st.shape[:-2], dtype=torch.float32, device=st.device)
+        _abi.pf_set_nll(st, lw, y, sc, nll=nll)
+        ctx.save_for_backward(st, lw, y, sc)
+        return nll
+
+    @staticmethod
+    def backward(ctx, g_nll):
+        st, lw, y, sc = ctx.saved_tensors
+        need_x, need_a, _, need_s = ctx.needs_input_grad
+        g_states = torch.empty_like(st) if need_x else None
+        g_logw = torch.empty_like(lw) if need_a else None
+        g_ls = torch.empty(st.shape[:-2] + (st.shape[-1],), dtype=torch.float32, device=st.device) if need_s else None
+        if need_x or need_a or need_s:
+            _abi.pf_set_nll(st, lw, y, sc, g_nll.to(torch.float32).contiguous(), g_states=g_states, g_logw=g_logw, g_log_scale=g_ls)
+        g_scale = None if g_ls is None else g_ls.reshape(-1, st.shape[-1]).sum(0) / sc
+        return g_states, g_logw, None, g_scale
 
 
 class ReweightEstimateFunction(torch.autograd.Function):

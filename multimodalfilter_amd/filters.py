@@ -121,6 +121,12 @@ class ParticleFilter(base.Filter):
     beliefs as pictures -- the 2-D marginal of that density on a grid around ``center`` (returned: ``density (T, N, Gy, Gx)``)
     for the predicted, filtered or smoothed sets and, with ``likelihoods``, every sensor's and the fused log-likelihood on the
     same grid -> ``last_maps`` (``mmf_pf_raster``).
+    ``keep_training_sets = True`` (training mode only; evaluation ignores it, ``record_history`` is its record there): a
+    ``forward_loop`` leaves ``last_training_sets = {"states" (T, N, M, d), "log_weights" (T, N, M)}``, every step's weighted set
+    -- the one its estimate is taken from, before any resampling -- as differentiable tensors, so that a loss can be put on the
+    belief as a distribution (``train.particle_set_nll``, ``train.filter_loss(loss="nll")``).  From the native recursion they
+    are views of the buffers it keeps anyway and their gradients return through ``mmf_pf_train_backward_sets``; the
+    step-by-step paths stack them.  Off (the default): every launch and every bit as before.
     Randomness comes from ``self.noise`` (``utils.NoiseSource``), never from global RNG state.
     """
 
@@ -167,6 +173,9 @@ class ParticleFilter(base.Filter):
         self.last_forecast = None     # belief_forecast(): the k-step-ahead predictive mixtures of the recorded sets, scored
         self.last_maps = None         # belief_maps(): the recorded beliefs (and the likelihoods) rasterised on a grid
         self.record_transition_moments = False  # smooth(method="marginal") adds the two-slice residual moments to last_smoothed
+        self.keep_training_sets = False   # a train-mode forward_loop leaves every step's weighted set, differentiable -> last_training_sets
+        self.last_training_sets = None
+        self._step_training_set = None
         self._step_history = None
         self.use_native_loop = True   # False: forward_loop keeps the step-by-step Python loop
         self.particle_states: torch.Tensor = None
@@ -430,6 +439,7 @@ class ParticleFilter(base.Filter):
             else:
                 estimate = states[torch.arange(N, device=states.device), torch.argmax(logw, dim=1)]
         self.particle_states, self.particle_log_weights = states, logw
+        self._step_training_set = (states, logw) if self.keep_training_sets else None  # (before any resampling)
         thr = self.resample_ess_threshold
         self.last_resampled = None if thr is None else torch.full((N,), bool(do_resample), dtype=torch.bool, device=states.device)
         if do_resample:
@@ -637,9 +647,15 @@ class ParticleFilter(base.Filter):
         for net, _col in nets:
             params += net._sources()
         empty = torch.empty(0, dtype=torch.float32, device=self.particle_states.device)
-        est, states, logw = engine.PfTrainLoopFunction.apply(
-            (dyn._net, nets, K_all), T, N, M, self.particle_states, self.particle_log_weights, eps,
-            dyn.scale_tril(), dyn_all, beta if beta is not None else empty, *biases, *params)
+        if self.keep_training_sets:  # the recursion's own buffers as two more (differentiable) outputs
+            est, states, logw, set_states, set_logw = engine.PfTrainLoopFunction.apply(
+                (dyn._net, nets, K_all, True), T, N, M, self.particle_states, self.particle_log_weights, eps,
+                dyn.scale_tril(), dyn_all, beta if beta is not None else empty, *biases, *params)
+            self.last_training_sets = {"states": set_states, "log_weights": set_logw}
+        else:
+            est, states, logw = engine.PfTrainLoopFunction.apply(
+                (dyn._net, nets, K_all), T, N, M, self.particle_states, self.particle_log_weights, eps,
+                dyn.scale_tril(), dyn_all, beta if beta is not None else empty, *biases, *params)
         self.particle_states, self.particle_log_weights = states, logw
         self._spare_states = None
         return est
@@ -647,12 +663,17 @@ class ParticleFilter(base.Filter):
     def _loop_of_steps(self, T, step, N):
         """``forward_loop`` step by step: ``step(t, rows of step t in the T*N flattened arrays)``; the per-step records
         (``last_belief``, ``last_resampled``) are stacked along a leading ``T`` axis."""
-        out, beliefs, took, hist = [], [], [], []
+        out, beliefs, took, hist, sets = [], [], [], [], []
+        self._step_training_set = None
         for t in range(T):
             out.append(step(t, slice(t * N, (t + 1) * N)))
             beliefs.append(self.last_belief)
             took.append(self.last_resampled)
             hist.append(self._step_history)
+            sets.append(self._step_training_set)
+        if sets and sets[0] is not None:  # (training steps with keep_training_sets: the sets before any resampling)
+            self.last_training_sets = {"states": torch.stack([s for s, _ in sets]), "log_weights": torch.stack([w for _, w in sets])}
+        self._step_training_set = None
         if self.record_belief:
             self.last_belief = base.stack_belief_records(beliefs)
         if took and took[0] is not None:
@@ -1372,6 +1393,7 @@ class ParticleFilter(base.Filter):
         if use_autograd(self):
             if self.record_history:
                 raise RuntimeError("record_history: the training (autograd) paths keep no history; call .eval() first")
+            self.last_training_sets = None
             if not engine.use_hip_backward():
                 return self._loop_of_steps(T, lambda t, sl: self(
                     observations=tree_index(observations, t), controls=tree_index(controls, t)), N)

@@ -41,13 +41,48 @@ def default_noise(filter_model) -> NoiseSource:
     return own if type(own) is NoiseSource else _DEFAULT_NOISE  # replayed / stacked blocks are the steps' own
 
 
+def particle_set_nll(states: torch.Tensor, log_weights: torch.Tensor, truth: torch.Tensor, scale) -> torch.Tensor:
+    """Negative log-likelihood of ``truth (..., d)`` under the Gaussian mixture ``sum_m softmax(log_weights)_m N(.; states_m,
+    diag scale^2)`` placed on the weighted sets ``states (..., M, d)``, ``log_weights (..., M)`` -> ``nll (...)`` -- the loss
+    the differentiable-filter literature trains particle filters on (Jonschkowski et al. 2018, Kloss et al. 2021), and the
+    negated ``log_score`` of ``belief_density(truth, bandwidth=scale)`` (``include/mmf.h``, "Training on the particle set").
+    ``log_weights`` need not be normalised; ``-inf`` is a dead particle, whose state row may hold NaN and whose gradients are
+    0; a row without a live particle or with a NaN in the truth is NaN with zero gradients.  ``scale``: ``d`` positive floats or
+    a tensor -- one that requires grad gets its gradient (parametrise ``sigma = exp(theta)`` yourself).  With the ``"hip"``
+    training backend and device tensors one HIP kernel forward and one backward (``engine.ParticleSetNllFunction``);
+    otherwise the same definition in torch ops (``engine.particle_set_nll_torch``), CPU tensors included."""
+    d = states.shape[-1]
+    if not isinstance(scale, torch.Tensor):
+        scale = torch.tensor([float(s) for s in scale], dtype=torch.float32).to(states.device)
+    assert tuple(scale.shape) == (d,), f"scale: one component scale per state dimension ({d}), got {tuple(scale.shape)}"
+    if engine.use_hip_backward() and states.is_cuda:
+        return engine.ParticleSetNllFunction.apply(states, log_weights, truth, scale)
+    return engine.particle_set_nll_torch(states, log_weights, truth, scale.to(states.dtype))
+
+
 def filter_loss(filter_model, batch: Dict[str, torch.Tensor], *, initial_covariance: torch.Tensor,
                 noise: Optional[NoiseSource] = None, measurement_initialize: bool = False,
-                initial_scale_tril: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """MSE of ``forward_loop`` on ``batch`` = ``{"states" (L, N, d), "controls" (L, N, 7), "image",
-    "gripper_pos", "gripper_sensors" (L, N, ...)}`` (time-major)."""
+                initial_scale_tril: Optional[torch.Tensor] = None, loss="mse", nll_scale=None) -> torch.Tensor:
+    """Loss of ``forward_loop`` on ``batch`` = ``{"states" (L, N, d), "controls" (L, N, 7), "image",
+    "gripper_pos", "gripper_sensors" (L, N, ...)}`` (time-major).  ``loss``: ``"mse"`` (the default, the reference's: the
+    estimates against ``states[1:]``); ``"nll"`` (particle filters): the mean over steps and trajectories of
+    ``particle_set_nll`` of every step's weighted set against ``states[1:]`` with the component scales ``nll_scale`` (required:
+    there is no hidden default); or a callable ``(estimates, sets, batch) -> scalar`` with ``sets`` the filter's
+    ``last_training_sets`` (``None`` for a filter that is not a particle filter), e.g. ``mse + lambda nll``.  ``"nll"`` and a
+    callable set ``keep_training_sets`` for the call and put it back."""
     assert filter_model.training, "call filter_model.train() first"
     assert engine.TRAINING_BACKEND is not None, "select engine.set_training_backend('hip' | 'autograd')"
+    from .filters import ParticleFilter  # (filters imports nothing from here; kept local like base_models' in filters)
+
+    is_pf = isinstance(filter_model, ParticleFilter)
+    if loss == "nll":
+        if not is_pf:
+            raise ValueError('loss="nll" is the mixture log score of a particle set: it needs a particle filter (the Kalman '
+                             "filters' Gaussian NLL on their belief covariance is a separate change)")
+        if nll_scale is None:
+            raise ValueError('loss="nll" needs nll_scale, the component scales of the mixture: there is no default')
+    elif loss != "mse" and not callable(loss):
+        raise ValueError(f'loss must be "mse", "nll" or a callable (estimates, sets, batch) -> scalar, got {loss!r}')
     states = batch["states"]
     L, N, d = states.shape
     obs = {k: batch[k] for k in ("image", "gripper_pos", "gripper_sensors")}
@@ -58,17 +93,30 @@ def filter_loss(filter_model, batch: Dict[str, torch.Tensor], *, initial_covaria
         tril = initial_scale_tril if initial_scale_tril is not None else torch.linalg.cholesky(initial_covariance.to(torch.float32))
         mean = states[0] + noise.gaussian((N, d), like=states) @ tril.t()
         filter_model.initialize_beliefs(mean=mean, covariance=initial_covariance[None].expand(N, d, d))
-    pred = filter_model.forward_loop(observations={k: v[1:] for k, v in obs.items()}, controls=batch["controls"][1:])
-    return torch.mean((pred - states[1:]) ** 2)
+    if loss == "mse":
+        pred = filter_model.forward_loop(observations={k: v[1:] for k, v in obs.items()}, controls=batch["controls"][1:])
+        return torch.mean((pred - states[1:]) ** 2)
+    was = filter_model.keep_training_sets if is_pf else None
+    if is_pf:
+        filter_model.keep_training_sets = True
+    try:
+        pred = filter_model.forward_loop(observations={k: v[1:] for k, v in obs.items()}, controls=batch["controls"][1:])
+        sets = filter_model.last_training_sets if is_pf else None
+    finally:
+        if is_pf:
+            filter_model.keep_training_sets = was
+    if callable(loss):
+        return loss(pred, sets, batch)
+    return torch.mean(particle_set_nll(sets["states"], sets["log_weights"], states[1:], nll_scale))
 
 
 def train_filter_step(filter_model, batch, optimizer: torch.optim.Optimizer, *, initial_covariance: torch.Tensor,
                       noise: Optional[NoiseSource] = None, measurement_initialize: bool = False,
-                      all_reduce: bool = False) -> float:
-    """One optimisation step on one batch of subsequences; returns the loss."""
+                      all_reduce: bool = False, loss="mse", nll_scale=None) -> float:
+    """One optimisation step on one batch of subsequences; returns the loss (``loss``, ``nll_scale``: ``filter_loss``)."""
     optimizer.zero_grad(set_to_none=True)
     loss = filter_loss(filter_model, batch, initial_covariance=initial_covariance, noise=noise,
-                       measurement_initialize=measurement_initialize)
+                       measurement_initialize=measurement_initialize, loss=loss, nll_scale=nll_scale)
     loss.backward()
     if all_reduce:
         distributed.all_reduce_gradients(filter_model)
@@ -96,16 +144,18 @@ class GraphedFilterStep:
     captured even when the blobs are fresh, or when a fused optimiser, which never moves it, ran the eager steps) and after
     every replay (the next eager or eval forward re-packs the weights the replay wrote).  Requirements: a capturable
     optimiser (``torch.optim.SGD``, or Adam with ``capturable=True``), no host-dependent control flow in user models,
-    batches of one shape (a new shape raises)."""
+    batches of one shape (a new shape raises).  ``loss``, ``nll_scale``: ``filter_loss``'s (a callable loss is captured too:
+    it must neither read the host nor allocate outside torch's allocator)."""
 
     def __init__(self, filter_model, optimizer: torch.optim.Optimizer, *, initial_covariance: torch.Tensor,
                  noise: Optional[NoiseSource] = None, measurement_initialize: bool = False, all_reduce: bool = False,
-                 eager_steps: int = 2):
+                 eager_steps: int = 2, loss="mse", nll_scale=None):
         assert not all_reduce, "the gradient all-reduce is not captured: use train_filter_step for data-parallel training"
         self.model, self.optimizer, self.cov = filter_model, optimizer, initial_covariance
         self.noise = noise if noise is not None else default_noise(filter_model)
         self.measurement_initialize, self.eager_left = measurement_initialize, int(eager_steps)
         self.graph, self.static, self.loss, self.tril = None, None, None, None
+        self.loss_kind, self.nll_scale = loss, nll_scale   # (filter_loss's; the scales go to the device once, before any capture)
         self.stream = None   # eager steps and the capture share ONE side stream: autograd remembers the stream a parameter's
                              # gradient accumulator was created on, and a capture must not reach back to the default stream
 
@@ -125,7 +175,8 @@ class GraphedFilterStep:
         engine.clear_range(dev)
         with engine.capturing(), torch.cuda.graph(self.graph, stream=self.stream):
             loss = filter_loss(self.model, self.static, initial_covariance=self.cov, noise=self.noise,
-                               measurement_initialize=self.measurement_initialize, initial_scale_tril=self.tril)
+                               measurement_initialize=self.measurement_initialize, initial_scale_tril=self.tril,
+                               loss=self.loss_kind, nll_scale=self.nll_scale)
             loss.backward()
             self.optimizer.step()
             self.loss = loss.detach()
@@ -133,12 +184,15 @@ class GraphedFilterStep:
     def __call__(self, batch: Dict[str, torch.Tensor]) -> float:
         if self.stream is None:
             self.stream = torch.cuda.Stream(device=batch["states"].device)
+            if self.nll_scale is not None and not isinstance(self.nll_scale, torch.Tensor):  # a capture must not copy from the host
+                self.nll_scale = torch.tensor([float(s) for s in self.nll_scale], dtype=torch.float32).to(batch["states"].device)
         if self.eager_left > 0:
             self.eager_left -= 1
             self.stream.wait_stream(torch.cuda.current_stream(batch["states"].device))
             with torch.cuda.stream(self.stream):
                 loss = train_filter_step(self.model, batch, self.optimizer, initial_covariance=self.cov, noise=self.noise,
-                                         measurement_initialize=self.measurement_initialize)   # (reads the loss: synchronises)
+                                         measurement_initialize=self.measurement_initialize, loss=self.loss_kind,
+                                         nll_scale=self.nll_scale)   # (reads the loss: synchronises)
             return loss
         if self.graph is None:
             self._capture(batch)
