@@ -7,6 +7,8 @@ fused-sensor matrix never above 5e-3 (the fp32 reference itself is capped at 1.7
 buffer carries ``GUARD_ROWS`` sentinel rows past its end, which must come back bit-unchanged.  Each figure is printed before it
 is asserted (``pytest -s`` shows them; ``profiles/kalman_kernels/README.md`` holds those of one MI355X run)."""
 
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -14,67 +16,14 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import _kalman_cases as kc
-import _tol
-
-
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a real MI355X (run with -m gpu on the GPU box)")
-    return torch.device("cuda:0")
-
-
-def _abi():
-    from multimodalfilter_amd import _abi
-
-    _abi.load()
-    return _abi
+from _guarded_gpu import Out as _Out, abi as _abi, bits as _bits, dev as _dev, hold, raw as _raw
 
 
 def _d(a):
     return torch.from_numpy(np.array(a)).to(_dev())
 
 
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-class _Out:
-    """An output buffer of ``lead`` rows of shape ``tail`` followed by ``GUARD_ROWS`` guard rows, all filled with the
-    sentinel (``init``: the in/out operand's input)."""
-
-    def __init__(self, lead, tail, init=None):
-        self.rows = int(np.prod(lead))
-        self.full = torch.full((self.rows + kc.GUARD_ROWS,) + tuple(tail), kc.SENTINEL, device=_dev())
-        self.t = self.full[:self.rows].view(tuple(lead) + tuple(tail))
-        if init is not None:
-            self.t.copy_(init)
-
-    def guard_intact(self):
-        g = self.full[self.rows:]
-        return torch.equal(_bits(g), _bits(torch.full_like(g, kc.SENTINEL)))
-
-    def untouched(self):
-        return torch.equal(_bits(self.full), _bits(torch.full_like(self.full, kc.SENTINEL)))
-
-
-def _raw(name, *args):
-    """The C entry point itself (tensors -> device pointers, None -> null, current stream appended): for the calls the typed
-    wrappers cannot express (N = 0, a null gate on the gated entry)."""
-    abi = _abi()
-    conv = [abi.ptr(a, dtype=a.dtype) if isinstance(a, torch.Tensor) else a for a in args]
-    with torch.cuda.device(_dev()):
-        return getattr(abi.load(), name)(*conv, torch.cuda.current_stream().cuda_stream)
-
-
-def _hold(group, tag, name, got, truth, yardstick, ceiling=None):
-    """Print, then assert, ``rel_err(got, fp64) < max(1e-4, 3 rel_err(yardstick, fp64))`` (at most ``ceiling``)."""
-    assert bool(torch.isfinite(got).all()), (group, tag, name, "not finite")
-    err, ref = _tol.rel_err(got, truth), _tol.rel_err(yardstick, truth)
-    bar = max(_tol.REL_TOL, 3.0 * ref)
-    if ceiling is not None:
-        bar = min(bar, ceiling)
-    print(f"KALMAN group={group} {tag} what={name} kernel={err:.3e} fp32={ref:.3e} bar={bar:.3e}")
-    assert err < bar, (group, tag, name, err, ref)
+_hold = functools.partial(hold, "KALMAN")
 
 
 # ------------------------------------------------------------------------------ A: mmf_ekf_step

@@ -9,6 +9,7 @@ pytestmark = pytest.mark.gpu
 from oracle import models as om
 from oracle.tf.base import ReplayNoise
 
+import _jacobian_cases as jc
 from _conv_cases import image_convs_against_fp64 as _image_convs_against_fp64
 from _tol import rel_err, scalar_rel
 
@@ -691,12 +692,14 @@ def test_k6_image_convs_function_matches_fp64_autograd(N, precision):
 
 
 @pytest.mark.parametrize("tname", ["door", "push"])
-@pytest.mark.parametrize("N", [3, 50])
+@pytest.mark.parametrize("N", jc.K6_NS)
 def test_k6_dynamics_with_jacobian_matches_fp64_autograd(tname, N):
     """K6 for K5: ``predict_with_jacobian_autograd`` (primal + tangent rows through the K6 kernels in
     groups of four, tangents following the primal's ReLU masks) against the oracle's dynamics model in
     fp64 with its autograd Jacobian (``create_graph``): ``x'``, ``A`` and the gradients of a random
-    linear functional of both with respect to every weight, ``x`` and the controls, 1e-4 relative."""
+    linear functional of both with respect to every weight, ``x`` and the controls, 1e-4 relative.
+    The rows are ``_jacobian_cases.case``'s (no ReLU mask within rounding of zero: the second derivative
+    passes through the same masks), N up to one group past a tile (9) and past a workgroup pass (65)."""
     import multimodalfilter_amd as mmf
     from multimodalfilter_amd import engine
 
@@ -704,11 +707,9 @@ def test_k6_dynamics_with_jacobian_matches_fp64_autograd(tname, N):
     task = om.TASKS[tname]
     d = task.state_dim
     g = torch.Generator().manual_seed(80 + N)
-    x, u = torch.randn((N, d), generator=g), torch.randn((N, 7), generator=g)
+    x, u = jc.case(tname, jc.MAIN_SEED, N)
     gm, gA = torch.randn((N, d), generator=g), torch.randn((N, d, d), generator=g)
-    o = om.DynamicsModel(task)
-    o.load_state_dict(om.seeded_state_dict(o, seed=15, gain=1.0))
-    o = o.double()
+    o = jc.oracle_model(tname, jc.MAIN_SEED, torch.float64)
     x6, u6 = x.double().requires_grad_(True), u.double().requires_grad_(True)
     mu6, _ = o(initial_states=x6, controls=u6)
     A6 = o.jacobian(initial_states=x6, controls=u6)
