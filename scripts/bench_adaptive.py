@@ -6,14 +6,14 @@ launches), on measurement heads calibrated so that the weights do degenerate (``
 
 One JSON document.  ``--unset-only`` touches nothing this feature added, so the same file runs on the parent commit.
 """
-import argparse
-import json
 import os
 import statistics
 import sys
 import time
 
 import torch
+
+import _bench_common as bc
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -27,22 +27,12 @@ def _timed(fn):
 
 
 def pf_case(N, M, T, reps, unset_only, dev):
-    import bench
     import multimodalfilter_amd as mmf
-    from multimodalfilter_amd import _abi, engine, synthetic
+    from multimodalfilter_amd import _abi, engine
 
-    d = 3
-    torch.manual_seed(0)
-    f = mmf.door_models.DoorCrossmodalParticleFilter().to(dev).eval()
-    synthetic.stabilise_dynamics(f)
-    traj = bench.to_device(synthetic.make_trajectories(state_dim=d, T=T + 1, N=N, seed=5), dev)
-    obs = {k: traj[k][1:] for k in ("image", "gripper_pos", "gripper_sensors")}
-    ctrl = traj["controls"][1:]
-    cal = traj["states"][0][:, None, :] + 0.3 * torch.randn((N, 256, d), device=dev)
-    synthetic.calibrate_measurement_heads(f, {k: v[0] for k, v in obs.items()}, cal)
-    f.num_particles = M
+    door = bc.recorded_door_run(N, M, T + 1, dev, run=False)
+    f, traj, obs, ctrl, cov0 = door.f, door.traj, door.obs, door.ctrl, door.cov0
     f.reserve(steps=T, batch=N, particles=M)
-    cov0 = (torch.eye(d, device=dev) * 0.1)[None].expand(N, d, d)
     settings = [None] if unset_only else [None, 0.5]
     shares = {}
 
@@ -72,19 +62,14 @@ def pf_case(N, M, T, reps, unset_only, dev):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=5)
+    ap = bc.arg_parser(__doc__)
+    ap.set_defaults(reps=5)
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--unset-only", action="store_true")
-    ap.add_argument("--out", default=None)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     doc = {"pf": [pf_case(N, M, args.steps, args.reps, args.unset_only, dev) for N, M in ((32, 300), (256, 4096))]}
-    text = json.dumps(doc, indent=1)
-    print(text)
-    if args.out:
-        with open(args.out, "w") as fh:
-            fh.write(text + "\n")
+    bc.write_document(doc, args.out)
 
 
 if __name__ == "__main__":

@@ -7,14 +7,14 @@ particle set.
 
 One JSON document.  ``--off-only`` touches nothing this feature added, so the same file runs on the parent commit.
 """
-import argparse
-import json
 import os
 import statistics
 import sys
 import time
 
 import torch
+
+import _bench_common as bc
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -137,20 +137,15 @@ def ekf_case(N, T, reps, off_only, dev):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=3)
+    ap = bc.arg_parser(__doc__)
+    ap.set_defaults(reps=3)
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--off-only", action="store_true")
-    ap.add_argument("--out", default=None)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     doc = {"pf": [pf_case(N, M, args.steps, args.reps, args.off_only, dev) for N, M in ((32, 300), (32, 4096), (256, 4096))],
            "ekf": [ekf_case(N, args.steps, args.reps, args.off_only, dev) for N in (32, 256)]}
-    text = json.dumps(doc, indent=1)
-    print(text)
-    if args.out:
-        with open(args.out, "w") as fh:
-            fh.write(text + "\n")
+    bc.write_document(doc, args.out)
 
 
 if __name__ == "__main__":

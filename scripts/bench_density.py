@@ -11,8 +11,6 @@ alternating.
 One JSON document.  ``pairs``: ``R M^2`` per call, what both formulations visit (the ``R M`` pairs of the truth beside them).
 ``max_log_difference``: the largest ``|kernel - torch| / max(1, |torch|)`` per log-valued output; ``mode_agreement``: the share
 of the rows whose ``mode_index`` is the same."""
-import argparse
-import json
 import math
 import os
 import statistics
@@ -20,23 +18,12 @@ import sys
 
 import torch
 
+import _bench_common as bc
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 CHUNK_BYTES = 256 << 20
 QUERIES = 256
-
-
-def _event_ms(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    out = fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b), out
-
-
-def _stats(v):
-    return {"median": statistics.median(v), "min": min(v), "max": max(v)}
 
 
 def torch_density(states, log_a, log_b, truth, min_bandwidth=1e-6):
@@ -77,27 +64,10 @@ def _log_difference(got, want):
 
 
 def case(N, M, T, reps, dev):
-    import bench
-    import multimodalfilter_amd as mmf
-    from multimodalfilter_amd import _abi, synthetic
+    from multimodalfilter_amd import _abi
 
-    d = 3
-    torch.manual_seed(0)
-    f = mmf.door_models.DoorCrossmodalParticleFilter().to(dev).eval()
-    synthetic.stabilise_dynamics(f)
-    traj = bench.to_device(synthetic.make_trajectories(state_dim=d, T=T, N=N, seed=5), dev)
-    obs = {k: traj[k][1:] for k in ("image", "gripper_pos", "gripper_sensors")}
-    ctrl = traj["controls"][1:]
-    cal = traj["states"][0][:, None, :] + 0.3 * torch.randn((N, 256, d), device=dev)
-    synthetic.calibrate_measurement_heads(f, {k: v[0] for k, v in obs.items()}, cal)
-    f.num_particles = M
-    f.record_history = True
-    f.noise = mmf.CounterNoise(7)
-    f.initialize_beliefs(mean=traj["states"][0], covariance=(torch.eye(d, device=dev) * 0.1)[None].expand(N, d, d))
-    f.forward_loop(observations=obs, controls=ctrl)
-    h = f.last_history
-    assert h.states.shape == (T, N, M, d)
-    truth = traj["states"][1:].contiguous()
+    door = bc.recorded_door_run(N, M, T, dev)
+    f, h, truth, d = door.f, door.f.last_history, door.truth, door.dims[3]
     out = dict(log_density=torch.empty((T, N, M), dtype=torch.float32, device=dev),
                log_score=torch.empty((T, N), dtype=torch.float32, device=dev),
                entropy=torch.empty((T, N), dtype=torch.float32, device=dev),
@@ -118,13 +88,7 @@ def case(N, M, T, reps, dev):
             "hip_log_score_only": hip_log_score_only,                      # the truth alone: R M pairs
             "torch_ops": lambda: torch_density(h.states, h.log_weights_in, h.log_likelihoods, truth)}
     with torch.no_grad():
-        for fn in runs.values():  # warm-up: code objects, allocator
-            fn()
-        torch.cuda.synchronize()
-        times = {k: [] for k in runs}
-        for _ in range(reps):
-            for k, fn in runs.items():  # alternating
-                times[k].append(_event_ms(fn)[0])
+        times = bc.time_alternating(runs, reps)
         hip_density()
         t_ld, t_score, t_entropy, t_index, t_h = torch_density(h.states, h.log_weights_in, h.log_likelihoods, truth)
         torch.cuda.synchronize()
@@ -134,7 +98,7 @@ def case(N, M, T, reps, dev):
             "rows": T * N, "pairs": pairs, "workgroups": T * N * ((M + 511) // 512),
             "workspace_bytes": _abi.pf_density_workspace_bytes(T * N, M, d),
             "torch_rows_per_chunk": max(1, CHUNK_BYTES // (4 * QUERIES * M * d)), "torch_queries_per_chunk": QUERIES,
-            "ms_per_call": {k: _stats(x) for k, x in times.items()},
+            "ms_per_call": {k: bc.stats(x) for k, x in times.items()},
             "torch_over_hip": med["torch_ops"] / med["hip_density"],
             "hip_pairs_per_second": pairs / (1e-3 * med["hip_density"]),
             "torch_pairs_per_second": pairs / (1e-3 * med["torch_ops"]),
@@ -149,19 +113,11 @@ def case(N, M, T, reps, dev):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = bc.arg_parser(__doc__).parse_args()
     dev = torch.device("cuda:0")
     doc = {"device": torch.cuda.get_device_name(0),
            "cases": [case(N, M, T, args.reps, dev) for N, M, T in ((32, 300, 100), (32, 4096, 20))]}
-    text = json.dumps(doc, indent=1)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write(text + "\n")
+    bc.write_document(doc, args.out)
 
 
 if __name__ == "__main__":

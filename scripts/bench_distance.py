@@ -15,30 +15,17 @@ formulation per output (relative: against ``max(|value|, 1e-3 x the output's lar
 ``torch_ops_against_fp64``: the same figures of either against the torch formulation in fp64 on ``fp64_row_pairs`` evenly
 spaced row pairs, which says which of the two is off where they differ (the fp64 formulation keeps plain weights, so on the
 CDF outputs it is the ``2^-24`` truncation of the kernel's fixed-point weights away from the kernel's definition)."""
-import argparse
-import json
 import os
 import statistics
 import sys
 
 import torch
 
+import _bench_common as bc
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 CHUNK_BYTES = 256 << 20
-
-
-def _event_ms(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    out = fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b), out
-
-
-def _stats(v):
-    return {"median": statistics.median(v), "min": min(v), "max": max(v)}
 
 
 def _flat(sets):
@@ -85,48 +72,17 @@ def torch_energy(Wa, Xa, Wb, Xb):
     return torch.sqrt((2 * terms[:, 0] - terms[:, 1] - terms[:, 2]).clamp_min(0)), terms
 
 
-def _difference(got, want):
-    ok = torch.isfinite(got) & torch.isfinite(want)
-    diff = torch.where(ok, (got - want).abs(), torch.zeros_like(got)).double()
-    top = float(torch.where(ok, want.abs(), torch.zeros_like(want)).max())
-    rel = diff / want.abs().double().clamp_min(1e-3 * top) if top > 0 else diff
-    return {"max_abs_difference": float(diff.max()), "max_rel_difference": float(torch.where(ok, rel, torch.zeros_like(rel)).max()),
-            "nan_placement_equal": bool(torch.equal(torch.isnan(got), torch.isnan(want)))}
-
-
-def _filter_with_history(N, M, T, dev):
-    import bench
-    import multimodalfilter_amd as mmf
-    from multimodalfilter_amd import synthetic
-
-    d = 3
-    torch.manual_seed(0)
-    f = mmf.door_models.DoorCrossmodalParticleFilter().to(dev).eval()
-    synthetic.stabilise_dynamics(f)
-    traj = bench.to_device(synthetic.make_trajectories(state_dim=d, T=T, N=N, seed=5), dev)
-    obs = {k: traj[k][1:] for k in ("image", "gripper_pos", "gripper_sensors")}
-    cal = traj["states"][0][:, None, :] + 0.3 * torch.randn((N, 256, d), device=dev)
-    synthetic.calibrate_measurement_heads(f, {k: v[0] for k, v in obs.items()}, cal)
-    f.num_particles = M
-    f.record_history = True
-    f.noise = mmf.CounterNoise(7)
-    f.initialize_beliefs(mean=traj["states"][0], covariance=(torch.eye(d, device=dev) * 0.1)[None].expand(N, d, d))
-    f.forward_loop(observations=obs, controls=traj["controls"][1:])
-    assert f.last_history.states.shape == (T, N, M, d)
-    return f
-
-
 def case(what, N, Ma, Mb, T, reps, dev):
     from multimodalfilter_amd import _abi
 
     d = 3
-    fa = _filter_with_history(N, Ma, T, dev)
+    fa = bc.recorded_door_run(N, Ma, T, dev).f
     if what == "filtered_vs_marginal_smoothed":
         assert Ma == Mb
         fb, kw = fa, dict(of="filtered", other_of="smoothed")
         fa.smooth(method="marginal")
     else:
-        fb, kw = _filter_with_history(N, Mb, T, dev), dict(of="filtered", other_of="filtered")
+        fb, kw = bc.recorded_door_run(N, Mb, T, dev).f, dict(of="filtered", other_of="filtered")
     a, b = fa._recorded_sets(kw["of"], "bench"), fb._recorded_sets(kw["other_of"], "bench")
     fa_, fb_ = _flat(a), _flat(b)
     new = lambda *tail: torch.empty((T, N) + tail, dtype=torch.float32, device=dev)
@@ -155,13 +111,7 @@ def case(what, N, Ma, Mb, T, reps, dev):
             "hip_pairs_only": lambda: _abi.pf_distance(*a, *b, **pairs_out),         # the pair kernel(s)
             "torch_ops": torch_all, "torch_cdf_only": torch_cdf_only, "torch_energy_only": torch_energy_only}
     with torch.no_grad():
-        for fn in runs.values():  # warm-up: code objects, allocator
-            fn()
-        torch.cuda.synchronize()
-        times = {k: [] for k in runs}
-        for _ in range(reps):
-            for k, fn in runs.items():  # alternating
-                times[k].append(_event_ms(fn)[0])
+        times = bc.time_alternating(runs, reps)
         runs["hip_distance"]()
         t_w, t_c, t_ks, t_energy, t_terms = torch_all()
         # which of the two is off where they differ: both against the same torch ops in fp64, on every STRIDE-th row pair
@@ -180,18 +130,18 @@ def case(what, N, Ma, Mb, T, reps, dev):
             "row_pairs": R, "pairs": pairs, "cdf_workgroups": R * d, "lds_bytes_per_cdf_workgroup": _abi.pf_distance_lds_bytes(Ma, Mb),
             "workspace_bytes": _abi.pf_distance_workspace_bytes(R, Ma, Mb, d),
             "torch_rows_per_chunk": max(1, CHUNK_BYTES // (4 * max(Ma, Mb) ** 2)),
-            "ms_per_call": {k: _stats(x) for k, x in times.items()},
+            "ms_per_call": {k: bc.stats(x) for k, x in times.items()},
             "torch_over_hip": med["torch_ops"] / med["hip_distance"],
             "torch_over_hip_cdf": med["torch_cdf_only"] / med["hip_cdf_only"],
             "torch_over_hip_pairs": med["torch_energy_only"] / med["hip_pairs_only"],
             "hip_pairs_per_second": pairs / (1e-3 * med["hip_pairs_only"]),
             "torch_pairs_per_second": pairs / (1e-3 * med["torch_energy_only"]),
-            "difference": {"wasserstein": _difference(flat(out["wasserstein"]), t_w), "cramer": _difference(flat(out["cramer"]), t_c),
-                           "ks": _difference(flat(out["ks"]), t_ks), "energy": _difference(flat(out["energy"]), t_energy),
-                           "terms": _difference(flat(out["terms"]), t_terms)},
+            "difference": {"wasserstein": bc.max_difference(flat(out["wasserstein"]), t_w), "cramer": bc.max_difference(flat(out["cramer"]), t_c),
+                           "ks": bc.max_difference(flat(out["ks"]), t_ks), "energy": bc.max_difference(flat(out["energy"]), t_energy),
+                           "terms": bc.max_difference(flat(out["terms"]), t_terms)},
             "fp64_row_pairs": int(sub.numel()),
-            "hip_against_fp64": {k: _difference(flat(out[k])[sub].double(), want[k]) for k in want},
-            "torch_ops_against_fp64": {k: _difference(torch32[k][sub].double(), want[k]) for k in want},
+            "hip_against_fp64": {k: bc.max_difference(flat(out[k])[sub].double(), want[k]) for k in want},
+            "torch_ops_against_fp64": {k: bc.max_difference(torch32[k][sub].double(), want[k]) for k in want},
             "row_pairs_without_a_live_particle": int(torch.isnan(out["energy"]).sum()),
             "mean_wasserstein": [float(v) for v in out["wasserstein"].nan_to_num(0.0).mean((0, 1))],
             "mean_cramer": [float(v) for v in out["cramer"].nan_to_num(0.0).mean((0, 1))],
@@ -200,20 +150,12 @@ def case(what, N, Ma, Mb, T, reps, dev):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = bc.arg_parser(__doc__).parse_args()
     dev = torch.device("cuda:0")
     cases = (("filtered_vs_marginal_smoothed", 32, 300, 300, 100), ("filtered_vs_marginal_smoothed", 32, 4096, 4096, 20),
              ("300_vs_4096_particles", 32, 300, 4096, 20))
     doc = {"device": torch.cuda.get_device_name(0), "cases": [case(*c, args.reps, dev) for c in cases]}
-    text = json.dumps(doc, indent=1)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write(text + "\n")
+    bc.write_document(doc, args.out)
 
 
 if __name__ == "__main__":

@@ -9,7 +9,6 @@ from ``rocprofv3 --kernel-trace --stats`` on a child process that only smooths (
 
 One JSON document.
 """
-import argparse
 import csv
 import glob
 import json
@@ -22,22 +21,11 @@ import tempfile
 
 import torch
 
+import _bench_common as bc
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 SIZES = ((32, 100), (2048, 100))
-
-
-def _event_ms(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    out = fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b), out
-
-
-def _stats(v):
-    return {"median": statistics.median(v), "min": min(v), "max": max(v)}
 
 
 def _setup(N, T, dev):
@@ -90,17 +78,11 @@ def case(N, T, reps, dev):
             "mmf_ekf_smooth_with_moments": lambda: _abi.ekf_smooth(h.means, h.covariances, A, pred, L, None, mean, cov, gain, Pp, e, m2),
             "mmf_ekf_smooth_lag_5": lambda: _abi.ekf_smooth(h.means, h.covariances, A, pred, L, 5, mean, cov, gain, Pp)}
     with torch.no_grad():
-        for fn in runs.values():  # warm-up: code objects, allocator
-            fn()
-        torch.cuda.synchronize()
-        times = {k: [] for k in runs}
-        for _ in range(reps):
-            for k, fn in runs.items():  # alternating
-                times[k].append(_event_ms(fn)[0])
+        times = bc.time_alternating(runs, reps)
     med = {k: statistics.median(v) for k, v in times.items()}
     return {"filter": "DoorKalmanFilter", "batch": N, "steps": T, "state_dim": d,
             "history_bytes": 4 * (d * d + d) * T * N, "workspace_bytes": 2 * 4 * d * d * (T - 1) * N,
-            "ms_per_call": {k: _stats(v) for k, v in times.items()},
+            "ms_per_call": {k: bc.stats(v) for k, v in times.items()},
             "smooth_over_forward_loop": med["smooth"] / med["forward_loop"],
             "recording_over_plain_forward_loop": med["forward_loop_recording"] / med["forward_loop"]}
 
@@ -145,9 +127,7 @@ def kernel_split(N, T, reps):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--out", default=None)
+    ap = bc.arg_parser(__doc__)
     ap.add_argument("--leg", action="store_true")
     ap.add_argument("--N", type=int, default=32)
     ap.add_argument("--T", type=int, default=100)
@@ -160,12 +140,7 @@ def main():
     doc = {"device": torch.cuda.get_device_name(0), "cases": [case(N, T, args.reps, dev) for N, T in SIZES]}
     if not args.no_profile:
         doc["kernel_split"] = [kernel_split(N, T, args.reps) for N, T in SIZES]
-    text = json.dumps(doc, indent=1)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write(text + "\n")
+    bc.write_document(doc, args.out)
 
 
 if __name__ == "__main__":

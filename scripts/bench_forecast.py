@@ -11,8 +11,6 @@ HIP events around each call, after a warm-up call of each, median / min / max of
 One JSON document.  ``pairs``: ``sum_h (T - h) N M^2`` per call, what both formulations visit.  ``difference``: the largest
 element-wise difference between the kernel and the torch formulation per output over all leads (relative: against
 ``max(|value|, 1e-3 x the output's largest)``)."""
-import argparse
-import json
 import math
 import os
 import statistics
@@ -20,23 +18,12 @@ import sys
 
 import torch
 
+import _bench_common as bc
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 CHUNK_BYTES = 256 << 20
 OUTPUTS = ("mean", "covariance", "log_score", "pit", "spread", "crps")
-
-
-def _event_ms(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    out = fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b), out
-
-
-def _stats(v):
-    return {"median": statistics.median(v), "min": min(v), "max": max(v)}
 
 
 def _expected_abs(m, s):
@@ -74,38 +61,13 @@ def torch_predictive(centres, log_a, log_b, tril, truth):
             "pit": pit.view(n, N, d), "spread": spread.view(n, N, d), "crps": crps.view(n, N, d)}
 
 
-def _difference(got, want):
-    ok = torch.isfinite(got) & torch.isfinite(want)
-    diff = torch.where(ok, (got - want).abs(), torch.zeros_like(got)).double()
-    top = float(torch.where(ok, want.abs(), torch.zeros_like(want)).max())
-    rel = diff / want.abs().double().clamp_min(1e-3 * top) if top > 0 else diff
-    return {"max_abs_difference": float(diff.max()), "max_rel_difference": float(torch.where(ok, rel, torch.zeros_like(rel)).max()),
-            "nan_placement_equal": bool(torch.equal(torch.isnan(got), torch.isnan(want)))}
-
-
 def case(N, M, T, H, reps, dev):
-    import bench
     import multimodalfilter_amd as mmf
-    from multimodalfilter_amd import _abi, evaluation, synthetic
+    from multimodalfilter_amd import _abi, evaluation
     from multimodalfilter_amd.utils import tree_map
 
-    d = 3
-    torch.manual_seed(0)
-    f = mmf.door_models.DoorCrossmodalParticleFilter().to(dev).eval()
-    synthetic.stabilise_dynamics(f)
-    traj = bench.to_device(synthetic.make_trajectories(state_dim=d, T=T, N=N, seed=5), dev)
-    obs = {k: traj[k][1:] for k in ("image", "gripper_pos", "gripper_sensors")}
-    ctrl = traj["controls"][1:]
-    cal = traj["states"][0][:, None, :] + 0.3 * torch.randn((N, 256, d), device=dev)
-    synthetic.calibrate_measurement_heads(f, {k: v[0] for k, v in obs.items()}, cal)
-    f.num_particles = M
-    f.record_history = True
-    f.noise = mmf.CounterNoise(7)
-    f.initialize_beliefs(mean=traj["states"][0], covariance=(torch.eye(d, device=dev) * 0.1)[None].expand(N, d, d))
-    f.forward_loop(observations=obs, controls=ctrl)
-    h = f.last_history
-    assert h.states.shape == (T, N, M, d)
-    truth = traj["states"][1:].contiguous()
+    door = bc.recorded_door_run(N, M, T, dev)
+    f, h, truth, d = door.f, door.f.last_history, door.truth, door.dims[3]
     la, lb = h.log_weights_in, h.log_likelihoods
 
     def forecast():
@@ -148,19 +110,13 @@ def case(N, M, T, H, reps, dev):
                 "hip_rows_only": lambda: hip(("mean", "covariance", "log_score", "pit")),  # the O(M) outputs
                 "k2_calls": k2_calls,                                            # the H noise-free dynamics calls
                 "torch_ops": torch_ops}
-        for fn in runs.values():  # warm-up: code objects, allocator
-            fn()
-        torch.cuda.synchronize()
-        times = {k: [] for k in runs}
-        for _ in range(reps):
-            for k, fn in runs.items():  # alternating
-                times[k].append(_event_ms(fn)[0])
+        times = bc.time_alternating(runs, reps)
         hip(OUTPUTS)
         want = torch_ops()
         torch.cuda.synchronize()
         difference = {}
         for name in OUTPUTS:
-            per_lead = [_difference(out[name][k - 1, :T - k], want[k - 1][name]) for k in range(1, H + 1)]
+            per_lead = [bc.max_difference(out[name][k - 1, :T - k], want[k - 1][name]) for k in range(1, H + 1)]
             difference[name] = {"max_abs_difference": max(p["max_abs_difference"] for p in per_lead),
                                 "max_rel_difference": max(p["max_rel_difference"] for p in per_lead),
                                 "nan_placement_equal": all(p["nan_placement_equal"] for p in per_lead)}
@@ -174,7 +130,7 @@ def case(N, M, T, H, reps, dev):
             "rows": rows, "pairs": pairs, "pair_workgroups": rows * ((M + 511) // 512),
             "workspace_bytes_lead_1": _abi.pf_predictive_workspace_bytes((T - 1) * N, M, d),
             "torch_rows_per_chunk": max(1, CHUNK_BYTES // (4 * M * M)),
-            "ms_per_call": {k: _stats(x) for k, x in times.items()},
+            "ms_per_call": {k: bc.stats(x) for k, x in times.items()},
             "torch_over_hip": med["torch_ops"] / med["hip_predictive"],
             "hip_pairs_per_second": pairs / (1e-3 * med["hip_pairs_only"]),
             "torch_pairs_per_second": pairs / (1e-3 * med["torch_ops"]),
@@ -186,19 +142,13 @@ def case(N, M, T, H, reps, dev):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--out", default=None)
+    ap = bc.arg_parser(__doc__)
+    ap.set_defaults(reps=5)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     doc = {"device": torch.cuda.get_device_name(0),
            "cases": [case(N, M, T, H, args.reps, dev) for N, M, T, H in ((32, 4096, 20, 5), (32, 300, 100, 10))]}
-    text = json.dumps(doc, indent=1)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write(text + "\n")
+    bc.write_document(doc, args.out)
 
 
 if __name__ == "__main__":

@@ -16,8 +16,6 @@ own run-to-run spread; ``recording_over_persistent`` is what a user who sets the
 
 One JSON document.  Needs the GPU: there is no CPU path to time.
 """
-import argparse
-import json
 import os
 import statistics
 import sys
@@ -25,20 +23,17 @@ import time
 
 import torch
 
+import _bench_common as bc
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 N, T, D = 32, 100, 3
 
 
-def _stats(v):
-    return {"median": statistics.median(v), "min": min(v), "max": max(v)}
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=15)
+    ap = bc.arg_parser(__doc__)
+    ap.set_defaults(reps=15)
     ap.add_argument("--calls", type=int, default=20)
-    ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_innovations: no GPU; a time is measured on the device or not at all")
@@ -87,18 +82,13 @@ def main():
            "sub_filters": 2, "state_dim": D, "calls_per_sample": args.calls, "samples": args.reps,
            "estimates_equal_to_loop_of_launches": same,
            "record_bytes": 3 * 4 * T * 2 * N,
-           "ms_per_forward_loop": {k: _stats(v) for k, v in times.items()},
+           "ms_per_forward_loop": {k: bc.stats(v) for k, v in times.items()},
            "loop_of_launches_spread_ms": spread,
            "recording_cost_ms": cost,
            "recording_cost_exceeds_spread": bool(cost > spread),
            "recording_over_loop_of_launches": med["loop_recording"] / med["loop_of_launches"],
            "recording_over_persistent": med["loop_recording"] / med["persistent"]}
-    text = json.dumps(doc, indent=1)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write(text + "\n")
+    bc.write_document(doc, args.out)
 
 
 if __name__ == "__main__":

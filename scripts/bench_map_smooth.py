@@ -9,28 +9,15 @@ from one profiled call (kernel durations by name).
 
 One JSON document.  ``pairs`` counts the transition densities the recursion evaluates, ``(T - 1) N M^2``.
 """
-import argparse
-import json
 import os
 import statistics
 import sys
 
 import torch
 
+import _bench_common as bc
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
-
-def _event_ms(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    out = fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b), out
-
-
-def _stats(v):
-    return {"median": statistics.median(v), "min": min(v), "max": max(v)}
 
 
 def _kernel_split(fn):
@@ -54,26 +41,10 @@ def _kernel_split(fn):
 
 
 def case(N, M, T, reps, dev):
-    import bench
-    import multimodalfilter_amd as mmf
-    from multimodalfilter_amd import _abi, evaluation, synthetic
+    from multimodalfilter_amd import _abi, evaluation
 
-    d = 3
-    torch.manual_seed(0)
-    f = mmf.door_models.DoorCrossmodalParticleFilter().to(dev).eval()
-    synthetic.stabilise_dynamics(f)
-    traj = bench.to_device(synthetic.make_trajectories(state_dim=d, T=T, N=N, seed=5), dev)
-    obs = {k: traj[k][1:] for k in ("image", "gripper_pos", "gripper_sensors")}
-    ctrl = traj["controls"][1:]
-    cal = traj["states"][0][:, None, :] + 0.3 * torch.randn((N, 256, d), device=dev)
-    synthetic.calibrate_measurement_heads(f, {k: v[0] for k, v in obs.items()}, cal)
-    f.num_particles = M
-    f.record_history = True
-    f.noise = mmf.CounterNoise(7)
-    f.initialize_beliefs(mean=traj["states"][0], covariance=(torch.eye(d, device=dev) * 0.1)[None].expand(N, d, d))
-    f.forward_loop(observations=obs, controls=ctrl)
-    h = f.last_history
-    assert h.states.shape == (T, N, M, d)
+    door = bc.recorded_door_run(N, M, T, dev)
+    f, h, d = door.f, door.f.last_history, door.dims[3]
     with torch.no_grad():
         F, L = f._smoothing_transition(h, "map")
     new = lambda *shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=dev)
@@ -92,13 +63,7 @@ def case(N, M, T, reps, dev):
             "hip_map": hip_map,                                      # mmf_pf_smooth_map alone, F given
             "hip_marginal": hip_marginal}                            # mmf_pf_smooth_marginal alone, F given
     with torch.no_grad():
-        for fn in runs.values():  # warm-up: code objects, allocator
-            fn()
-        torch.cuda.synchronize()
-        times = {k: [] for k in runs}
-        for _ in range(reps):
-            for k, fn in runs.items():  # alternating
-                times[k].append(_event_ms(fn)[0])
+        times = bc.time_alternating(runs, reps)
         split = _kernel_split(hip_map)
         map_path = f.smooth(method="map")
         rec = f.last_smoothed
@@ -108,7 +73,7 @@ def case(N, M, T, reps, dev):
     med = {k: statistics.median(x) for k, x in times.items()}
     err = ((rec.log_posterior.double() - own).abs() / own.abs().clamp_min(1.0)).max()
     return {"filter": "DoorCrossmodalParticleFilter", "batch": N, "particles": M, "steps": T, "state_dim": d, "pairs": pairs,
-            "workspace_bytes": 4 * (2 * T * N * M + T * N), "ms_per_call": {k: _stats(x) for k, x in times.items()},
+            "workspace_bytes": 4 * (2 * T * N * M + T * N), "ms_per_call": {k: bc.stats(x) for k, x in times.items()},
             "pairs_per_second": {"hip_map": pairs / (1e-3 * med["hip_map"]), "hip_marginal": 2.0 * pairs / (1e-3 * med["hip_marginal"])},
             "map_over_marginal": {"hip": med["hip_map"] / med["hip_marginal"], "smooth": med["smooth_map"] / med["smooth_marginal"]},
             "map_kernels": split,
@@ -118,19 +83,11 @@ def case(N, M, T, reps, dev):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = bc.arg_parser(__doc__).parse_args()
     dev = torch.device("cuda:0")
     doc = {"device": torch.cuda.get_device_name(0),
            "cases": [case(N, M, T, args.reps, dev) for N, M, T in ((32, 300, 100), (32, 4096, 20))]}
-    text = json.dumps(doc, indent=1)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write(text + "\n")
+    bc.write_document(doc, args.out)
 
 
 if __name__ == "__main__":

@@ -12,8 +12,6 @@ One JSON document.  ``multiply_adds``: ``R M Gx Gy`` per call, what both formula
 that over the median device time of ``hip_raster`` (a call's time, not a kernel's share of peak).  ``difference``: the kernel and
 the fp32 torch formulation against the same torch ops in fp64, the largest ``|got - fp64| / max(|fp64|, 1e-3 of the row's
 largest cell)`` over the rows whose largest cell is at least 1e-30."""
-import argparse
-import json
 import math
 import os
 import statistics
@@ -21,25 +19,13 @@ import sys
 
 import torch
 
+import _bench_common as bc
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 CHUNK_BYTES = 256 << 20
 CELLS = 64
 DIMS = (0, 1)
-
-
-def _event_ms(fn, inner):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(inner):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / inner
-
-
-def _stats(v):
-    return {"median": statistics.median(v), "min": min(v), "max": max(v)}
 
 
 def torch_maps(states, log_a, log_b, center2, h2, step, cells, dims, dtype=torch.float32):
@@ -82,27 +68,10 @@ def _difference(got, want):
 
 
 def case(N, M, T, reps, dev):
-    import bench
-    import multimodalfilter_amd as mmf
-    from multimodalfilter_amd import _abi, synthetic
+    from multimodalfilter_amd import _abi
 
-    d = 3
-    torch.manual_seed(0)
-    f = mmf.door_models.DoorCrossmodalParticleFilter().to(dev).eval()
-    synthetic.stabilise_dynamics(f)
-    traj = bench.to_device(synthetic.make_trajectories(state_dim=d, T=T, N=N, seed=5), dev)
-    obs = {k: traj[k][1:] for k in ("image", "gripper_pos", "gripper_sensors")}
-    ctrl = traj["controls"][1:]
-    cal = traj["states"][0][:, None, :] + 0.3 * torch.randn((N, 256, d), device=dev)
-    synthetic.calibrate_measurement_heads(f, {k: v[0] for k, v in obs.items()}, cal)
-    f.num_particles = M
-    f.record_history = True
-    f.noise = mmf.CounterNoise(7)
-    f.initialize_beliefs(mean=traj["states"][0], covariance=(torch.eye(d, device=dev) * 0.1)[None].expand(N, d, d))
-    f.forward_loop(observations=obs, controls=ctrl)
-    h = f.last_history
-    assert h.states.shape == (T, N, M, d)
-    truth = traj["states"][1:].contiguous()
+    door = bc.recorded_door_run(N, M, T, dev)
+    f, h, truth, d = door.f, door.f.last_history, door.truth, door.dims[3]
     f.belief_maps(truth, (1.0, 1.0), dims=DIMS, cells=CELLS)                       # (for the bandwidths: the window is 32 of them)
     span = tuple(float(32.0 * f.last_maps.bandwidth[..., k].nan_to_num(0.0).median()) for k in range(2))
     f.belief_maps(truth, span, dims=DIMS, cells=CELLS)
@@ -126,13 +95,7 @@ def case(N, M, T, reps, dev):
             "torch_ops": (lambda: torch_maps(*sets, c2, h2, step, cells, DIMS), 2),
             "hip_density": (lambda: _abi.pf_density(*sets, None, rule="silverman", min_bandwidth=floor, **dens_out), 2)}
     with torch.no_grad():
-        for fn, _ in runs.values():  # warm-up: code objects, allocator
-            fn()
-        torch.cuda.synchronize()
-        times = {k: [] for k in runs}
-        for _ in range(reps):
-            for k, (fn, inner) in runs.items():  # alternating
-                times[k].append(_event_ms(fn, inner))
+        times = bc.time_alternating(runs, reps)
         _abi.pf_raster(*sets, c2, h2, density, dims=DIMS, step=step)
         torch32 = torch_maps(*sets, c2, h2, step, cells, DIMS).double()
         want = torch_maps(*sets, c2, h2, step, cells, DIMS, dtype=torch.float64)
@@ -148,7 +111,7 @@ def case(N, M, T, reps, dev):
             "torch_rows_per_chunk": max(1, CHUNK_BYTES // (4 * M * (cells[0] + cells[1]))),
             "torch_factor_bytes": 4.0 * T * N * M * (cells[0] + cells[1]),
             "inner_calls_per_window": {k: inner for k, (_, inner) in runs.items()},
-            "ms_per_call": {k: _stats(x) for k, x in times.items()},
+            "ms_per_call": {k: bc.stats(x) for k, x in times.items()},
             "torch_over_hip": med["torch_ops"] / med["hip_raster"],
             "raster_tflops": 2.0 * macs / (1e-3 * med["hip_raster"]) / 1e12,
             "difference": difference,
@@ -158,19 +121,11 @@ def case(N, M, T, reps, dev):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = bc.arg_parser(__doc__).parse_args()
     dev = torch.device("cuda:0")
     doc = {"device": torch.cuda.get_device_name(0),
            "cases": [case(N, M, T, args.reps, dev) for N, M, T in ((32, 4096, 20), (32, 300, 100))]}
-    text = json.dumps(doc, indent=1)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write(text + "\n")
+    bc.write_document(doc, args.out)
 
 
 if __name__ == "__main__":

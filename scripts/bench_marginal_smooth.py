@@ -8,30 +8,17 @@ the two implementations alternating.
 
 One JSON document.  ``pairs`` counts the transition densities the recursion evaluates, ``2 (T - 1) N M^2``.
 """
-import argparse
-import json
 import os
 import statistics
 import sys
 
 import torch
 
+import _bench_common as bc
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 CHUNK_BYTES = 1 << 30  # most a torch-ops temporary of (N, rows, M, d) may take
-
-
-def _event_ms(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    out = fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b), out
-
-
-def _stats(v):
-    return {"median": statistics.median(v), "min": min(v), "max": max(v)}
 
 
 def torch_marginal(X, F, ll, lw, L):
@@ -60,26 +47,10 @@ def torch_marginal(X, F, ll, lw, L):
 
 
 def case(N, M, T, reps, dev):
-    import bench
-    import multimodalfilter_amd as mmf
-    from multimodalfilter_amd import _abi, synthetic
+    from multimodalfilter_amd import _abi
 
-    d = 3
-    torch.manual_seed(0)
-    f = mmf.door_models.DoorCrossmodalParticleFilter().to(dev).eval()
-    synthetic.stabilise_dynamics(f)
-    traj = bench.to_device(synthetic.make_trajectories(state_dim=d, T=T, N=N, seed=5), dev)
-    obs = {k: traj[k][1:] for k in ("image", "gripper_pos", "gripper_sensors")}
-    ctrl = traj["controls"][1:]
-    cal = traj["states"][0][:, None, :] + 0.3 * torch.randn((N, 256, d), device=dev)
-    synthetic.calibrate_measurement_heads(f, {k: v[0] for k, v in obs.items()}, cal)
-    f.num_particles = M
-    f.record_history = True
-    f.noise = mmf.CounterNoise(7)
-    f.initialize_beliefs(mean=traj["states"][0], covariance=(torch.eye(d, device=dev) * 0.1)[None].expand(N, d, d))
-    f.forward_loop(observations=obs, controls=ctrl)
-    h = f.last_history
-    assert h.states.shape == (T, N, M, d)
+    door = bc.recorded_door_run(N, M, T, dev)
+    f, h, ctrl, d = door.f, door.f.last_history, door.ctrl, door.dims[3]
     dyn = f.dynamics_model
     L = dyn.scale_tril().detach().float().contiguous()
     with torch.no_grad():
@@ -97,12 +68,8 @@ def case(N, M, T, reps, dev):
             "hip_recursion": hip_recursion,                              # mmf_pf_smooth_marginal alone, F given
             "torch_recursion": lambda: torch_marginal(h.states, F, h.log_likelihoods, h.log_weights_in, L)}
     with torch.no_grad():
-        out = {k: fn() for k, fn in runs.items()}  # warm-up: code objects, allocator
-        torch.cuda.synchronize()
-        times = {k: [] for k in runs}
-        for _ in range(reps):
-            for k, fn in runs.items():  # alternating
-                times[k].append(_event_ms(fn)[0])
+        times = bc.time_alternating(runs, reps)
+        out = {k: fn() for k, fn in runs.items()}
 
     def rel(a, b):  # worst row against its own norm (floored at 1e-3 of the largest: a collapsed step has no spread to speak of)
         den = b.double().flatten(2).norm(dim=-1)
@@ -113,7 +80,7 @@ def case(N, M, T, reps, dev):
     med = {k: statistics.median(v) for k, v in times.items()}
     return {"filter": "DoorCrossmodalParticleFilter", "batch": N, "particles": M, "steps": T, "state_dim": d,
             "pairs": pairs, "workspace_bytes": 4 * (T - 1) * N * M, "prediction_bytes": 4 * d * (T - 1) * N * M,
-            "ms_per_call": {k: _stats(v) for k, v in times.items()},
+            "ms_per_call": {k: bc.stats(v) for k, v in times.items()},
             "pairs_per_second": {k: pairs / (1e-3 * med[k]) for k in ("hip_recursion", "torch_recursion")},
             "torch_over_hip": med["torch_recursion"] / med["hip_recursion"],
             "hip_against_torch": {"weights": rel(hip[0], ref[0]), "mean": rel(hip[1], ref[1]), "cov": rel(hip[2].flatten(2), ref[2].flatten(2))},
@@ -122,19 +89,11 @@ def case(N, M, T, reps, dev):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = bc.arg_parser(__doc__).parse_args()
     dev = torch.device("cuda:0")
     doc = {"device": torch.cuda.get_device_name(0),
            "cases": [case(N, M, T, args.reps, dev) for N, M, T in ((32, 300, 100), (32, 4096, 20))]}
-    text = json.dumps(doc, indent=1)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write(text + "\n")
+    bc.write_document(doc, args.out)
     slower = [c for c in doc["cases"] if c["torch_over_hip"] <= 1.0]
     if slower:
         sys.exit("the HIP recursion is not faster than the torch one at " + ", ".join(f"{c['batch']} x {c['particles']}" for c in slower))

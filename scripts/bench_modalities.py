@@ -14,13 +14,13 @@ the kernel's median time, ``share_of_hbm`` that over the 6.3e12 B/s a streaming 
 sizes the inputs fit the 256 MiB Infinity Cache, so repeated calls measure the chip's caches, not HBM.  ``agreement``: the
 largest difference between the two formulations' outputs (``log_evidence`` and ``divergence`` absolute, the others relative
 to the largest entry)."""
-import argparse
-import json
 import os
 import statistics
 import sys
 
 import torch
+
+import _bench_common as bc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -31,41 +31,12 @@ HBM_PEAK = 8.0e12
 BACK_TO_BACK = 16   # launches of the kernel between one pair of events: its time without the gap around a single launch
 
 
-def _event_ms(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    out = fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b), out
-
-
-def _stats(v):
-    return {"median": statistics.median(v), "min": min(v), "max": max(v)}
-
-
 def case(N, M, T, reps, dev):
     import _modality_cases as mc
-    import bench
-    import multimodalfilter_amd as mmf
-    from multimodalfilter_amd import _abi, engine, evaluation, synthetic
+    from multimodalfilter_amd import _abi, engine, evaluation
 
-    d = 3
-    torch.manual_seed(0)
-    f = mmf.door_models.DoorCrossmodalParticleFilter().to(dev).eval()
-    synthetic.stabilise_dynamics(f)
-    traj = bench.to_device(synthetic.make_trajectories(state_dim=d, T=T, N=N, seed=5), dev)
-    obs = {k: traj[k][1:] for k in ("image", "gripper_pos", "gripper_sensors")}
-    ctrl = traj["controls"][1:]
-    cal = traj["states"][0][:, None, :] + 0.3 * torch.randn((N, 256, d), device=dev)
-    synthetic.calibrate_measurement_heads(f, {k: v[0] for k, v in obs.items()}, cal)
-    f.num_particles = M
-    f.record_history = True
-    f.noise = mmf.CounterNoise(7)
-    f.initialize_beliefs(mean=traj["states"][0], covariance=(torch.eye(d, device=dev) * 0.1)[None].expand(N, d, d))
-    f.forward_loop(observations=obs, controls=ctrl)
-    h = f.last_history
-    assert h.states.shape == (T, N, M, d)
+    door = bc.recorded_door_run(N, M, T, dev)
+    f, h, obs, d = door.f, door.f.last_history, door.obs, door.dims[3]
     R = T * N
     meas = f.measurement_model
     flat_obs = {k: v.reshape((R,) + tuple(v.shape[2:])) for k, v in obs.items()}
@@ -92,13 +63,7 @@ def case(N, M, T, reps, dev):
             "hip_modalities_x16": lambda: [_abi.pf_modalities(h.states, h.log_weights_in, cols, beta_v, **out) for _ in range(BACK_TO_BACK)],
             "torch_ops": lambda: mc.torch_rows(states, h.log_weights_in.view(R, M), stacked, beta)}
     with torch.no_grad():
-        for fn in runs.values():  # warm-up: code objects, allocator
-            fn()
-        torch.cuda.synchronize()
-        times = {k: [] for k in runs}
-        for _ in range(reps):
-            for k, fn in runs.items():  # alternating
-                times[k].append(_event_ms(fn)[0])
+        times = bc.time_alternating(runs, reps)
         runs["hip_modalities"]()
         ref = runs["torch_ops"]()
         torch.cuda.synchronize()
@@ -118,7 +83,7 @@ def case(N, M, T, reps, dev):
     summary = evaluation.modality_summary(f.last_modalities, start=0)
     return {"filter": "DoorCrossmodalParticleFilter", "batch": N, "particles": M, "steps": T, "state_dim": d, "modalities": K,
             "rows": R, "workgroups": R, "threads": min(512, ((M + 3) // 4 + 63) // 64 * 64), "bytes": byts,
-            "ms_per_call": {k: _stats(x) for k, x in times.items()},
+            "ms_per_call": {k: bc.stats(x) for k, x in times.items()},
             "torch_over_hip": med["torch_ops"] / med["hip_modalities"],
             "hip_bytes_per_second": rate, "share_of_hbm": rate / HBM_ACHIEVABLE, "share_of_hbm_peak": rate / HBM_PEAK,
             "hip_bytes_per_second_back_to_back": rate_b2b, "share_of_hbm_back_to_back": rate_b2b / HBM_ACHIEVABLE,
@@ -129,19 +94,11 @@ def case(N, M, T, reps, dev):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = bc.arg_parser(__doc__).parse_args()
     dev = torch.device("cuda:0")
     doc = {"device": torch.cuda.get_device_name(0),
            "cases": [case(N, M, T, args.reps, dev) for N, M, T in ((32, 300, 100), (32, 4096, 20))]}
-    text = json.dumps(doc, indent=1)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write(text + "\n")
+    bc.write_document(doc, args.out)
 
 
 if __name__ == "__main__":

@@ -10,30 +10,17 @@ One JSON document.  ``kernel_bytes_per_particle``: what the one launch moves thr
 in (the row's log-weights are read by each of the ``d`` workgroups of a row; the repeats hit L2) -- its outputs are ``4 d (Q
 + 1)`` bytes per ROW.  ``agreement`` compares the torch formulation's picks with the kernel's (they differ where the fp32
 cumulative sum crosses elsewhere than the integer CDF)."""
-import argparse
-import json
 import os
 import statistics
 import sys
 
 import torch
 
+import _bench_common as bc
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 PROBS = (0.025, 0.5, 0.975)
-
-
-def _event_ms(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    out = fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b), out
-
-
-def _stats(v):
-    return {"median": statistics.median(v), "min": min(v), "max": max(v)}
 
 
 def torch_quantiles(states, log_a, log_b, probs, truth):
@@ -52,27 +39,10 @@ def torch_quantiles(states, log_a, log_b, probs, truth):
 
 
 def case(N, M, T, reps, dev):
-    import bench
-    import multimodalfilter_amd as mmf
-    from multimodalfilter_amd import _abi, synthetic
+    from multimodalfilter_amd import _abi
 
-    d = 3
-    torch.manual_seed(0)
-    f = mmf.door_models.DoorCrossmodalParticleFilter().to(dev).eval()
-    synthetic.stabilise_dynamics(f)
-    traj = bench.to_device(synthetic.make_trajectories(state_dim=d, T=T, N=N, seed=5), dev)
-    obs = {k: traj[k][1:] for k in ("image", "gripper_pos", "gripper_sensors")}
-    ctrl = traj["controls"][1:]
-    cal = traj["states"][0][:, None, :] + 0.3 * torch.randn((N, 256, d), device=dev)
-    synthetic.calibrate_measurement_heads(f, {k: v[0] for k, v in obs.items()}, cal)
-    f.num_particles = M
-    f.record_history = True
-    f.noise = mmf.CounterNoise(7)
-    f.initialize_beliefs(mean=traj["states"][0], covariance=(torch.eye(d, device=dev) * 0.1)[None].expand(N, d, d))
-    f.forward_loop(observations=obs, controls=ctrl)
-    h = f.last_history
-    assert h.states.shape == (T, N, M, d)
-    truth = traj["states"][1:].contiguous()
+    door = bc.recorded_door_run(N, M, T, dev)
+    f, h, truth, d = door.f, door.f.last_history, door.truth, door.dims[3]
     quant = torch.empty((T, N, len(PROBS), d), dtype=torch.float32, device=dev)
     pit = torch.empty((T, N, d), dtype=torch.float32, device=dev)
 
@@ -91,13 +61,7 @@ def case(N, M, T, reps, dev):
             "hip_pit_only": hip_pit_only,                                  # Q == 0: no sort
             "torch_ops": lambda: torch_quantiles(h.states, h.log_weights_in, h.log_likelihoods, PROBS, truth)}
     with torch.no_grad():
-        for fn in runs.values():  # warm-up: code objects, allocator
-            fn()
-        torch.cuda.synchronize()
-        times = {k: [] for k in runs}
-        for _ in range(reps):
-            for k, fn in runs.items():  # alternating
-                times[k].append(_event_ms(fn)[0])
+        times = bc.time_alternating(runs, reps)
         hip_quantiles()
         tq, tp = torch_quantiles(h.states, h.log_weights_in, h.log_likelihoods, PROBS, truth)
         torch.cuda.synchronize()
@@ -107,7 +71,7 @@ def case(N, M, T, reps, dev):
     return {"filter": "DoorCrossmodalParticleFilter", "batch": N, "particles": M, "steps": T, "state_dim": d, "probs": list(PROBS),
             "rows": T * N, "workgroups": T * N * d, "lds_bytes_per_workgroup": _abi.pf_quantiles_lds_bytes(M),
             "kernel_bytes_per_particle": 4 * (d + 2), "kernel_output_bytes_per_row": 4 * d * (len(PROBS) + 1),
-            "ms_per_call": {k: _stats(x) for k, x in times.items()},
+            "ms_per_call": {k: bc.stats(x) for k, x in times.items()},
             "torch_over_hip": med["torch_ops"] / med["hip_quantiles"],
             "particles_per_second": particles / (1e-3 * med["hip_quantiles"]),
             "input_gb_per_second": particles * 4 * (d + 2) / (1e-3 * med["hip_quantiles"]) / 1e9,
@@ -118,19 +82,11 @@ def case(N, M, T, reps, dev):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = bc.arg_parser(__doc__).parse_args()
     dev = torch.device("cuda:0")
     doc = {"device": torch.cuda.get_device_name(0),
            "cases": [case(N, M, T, args.reps, dev) for N, M, T in ((32, 300, 100), (32, 4096, 20))]}
-    text = json.dumps(doc, indent=1)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write(text + "\n")
+    bc.write_document(doc, args.out)
 
 
 if __name__ == "__main__":

@@ -10,30 +10,17 @@ a warm-up call of each, median / min / max of ``--reps`` calls, the three altern
 One JSON document.  ``pairs``: ``R M^2`` per call, what both formulations visit.  ``max_abs_difference`` /
 ``max_rel_difference``: the largest element-wise difference between the kernel and the torch formulation per output
 (relative: against ``max(|value|, 1e-3 x the output's largest)``)."""
-import argparse
-import json
 import os
 import statistics
 import sys
 
 import torch
 
+import _bench_common as bc
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 CHUNK_BYTES = 256 << 20
-
-
-def _event_ms(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    out = fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b), out
-
-
-def _stats(v):
-    return {"median": statistics.median(v), "min": min(v), "max": max(v)}
 
 
 def torch_scores(states, log_a, log_b, truth):
@@ -58,37 +45,11 @@ def torch_scores(states, log_a, log_b, truth):
     return crps.view(T, N, d), energy.view(T, N), spread.view(T, N, d + 1)
 
 
-def _difference(got, want):
-    ok = torch.isfinite(got) & torch.isfinite(want)
-    diff = torch.where(ok, (got - want).abs(), torch.zeros_like(got)).double()
-    top = float(torch.where(ok, want.abs(), torch.zeros_like(want)).max())
-    rel = diff / want.abs().double().clamp_min(1e-3 * top) if top > 0 else diff
-    return {"max_abs_difference": float(diff.max()), "max_rel_difference": float(torch.where(ok, rel, torch.zeros_like(rel)).max()),
-            "nan_placement_equal": bool(torch.equal(torch.isnan(got), torch.isnan(want)))}
-
-
 def case(N, M, T, reps, dev):
-    import bench
-    import multimodalfilter_amd as mmf
-    from multimodalfilter_amd import _abi, synthetic
+    from multimodalfilter_amd import _abi
 
-    d = 3
-    torch.manual_seed(0)
-    f = mmf.door_models.DoorCrossmodalParticleFilter().to(dev).eval()
-    synthetic.stabilise_dynamics(f)
-    traj = bench.to_device(synthetic.make_trajectories(state_dim=d, T=T, N=N, seed=5), dev)
-    obs = {k: traj[k][1:] for k in ("image", "gripper_pos", "gripper_sensors")}
-    ctrl = traj["controls"][1:]
-    cal = traj["states"][0][:, None, :] + 0.3 * torch.randn((N, 256, d), device=dev)
-    synthetic.calibrate_measurement_heads(f, {k: v[0] for k, v in obs.items()}, cal)
-    f.num_particles = M
-    f.record_history = True
-    f.noise = mmf.CounterNoise(7)
-    f.initialize_beliefs(mean=traj["states"][0], covariance=(torch.eye(d, device=dev) * 0.1)[None].expand(N, d, d))
-    f.forward_loop(observations=obs, controls=ctrl)
-    h = f.last_history
-    assert h.states.shape == (T, N, M, d)
-    truth = traj["states"][1:].contiguous()
+    door = bc.recorded_door_run(N, M, T, dev)
+    f, h, truth, d = door.f, door.f.last_history, door.truth, door.dims[3]
     crps = torch.empty((T, N, d), dtype=torch.float32, device=dev)
     energy = torch.empty((T, N), dtype=torch.float32, device=dev)
     spread = torch.empty((T, N, d + 1), dtype=torch.float32, device=dev)
@@ -104,13 +65,7 @@ def case(N, M, T, reps, dev):
             "hip_spread_only": hip_spread_only,                            # no truth
             "torch_ops": lambda: torch_scores(h.states, h.log_weights_in, h.log_likelihoods, truth)}
     with torch.no_grad():
-        for fn in runs.values():  # warm-up: code objects, allocator
-            fn()
-        torch.cuda.synchronize()
-        times = {k: [] for k in runs}
-        for _ in range(reps):
-            for k, fn in runs.items():  # alternating
-                times[k].append(_event_ms(fn)[0])
+        times = bc.time_alternating(runs, reps)
         hip_scores()
         t_crps, t_energy, t_spread = torch_scores(h.states, h.log_weights_in, h.log_likelihoods, truth)
         torch.cuda.synchronize()
@@ -120,30 +75,22 @@ def case(N, M, T, reps, dev):
             "rows": T * N, "pairs": pairs, "workgroups": T * N * ((M + 511) // 512),
             "workspace_bytes": _abi.pf_scores_workspace_bytes(T * N, M, d),
             "torch_rows_per_chunk": max(1, CHUNK_BYTES // (4 * M * M)),
-            "ms_per_call": {k: _stats(x) for k, x in times.items()},
+            "ms_per_call": {k: bc.stats(x) for k, x in times.items()},
             "torch_over_hip": med["torch_ops"] / med["hip_scores"],
             "hip_pairs_per_second": pairs / (1e-3 * med["hip_scores"]),
             "torch_pairs_per_second": pairs / (1e-3 * med["torch_ops"]),
-            "difference": {"crps": _difference(crps, t_crps), "energy": _difference(energy, t_energy),
-                           "spread": _difference(spread, t_spread)},
+            "difference": {"crps": bc.max_difference(crps, t_crps), "energy": bc.max_difference(energy, t_energy),
+                           "spread": bc.max_difference(spread, t_spread)},
             "rows_without_a_live_particle": int(torch.isnan(energy).sum()),
             "mean_crps": [float(v) for v in crps.nan_to_num(0.0).mean((0, 1))], "mean_energy": float(energy.nan_to_num(0.0).mean())}
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = bc.arg_parser(__doc__).parse_args()
     dev = torch.device("cuda:0")
     doc = {"device": torch.cuda.get_device_name(0),
            "cases": [case(N, M, T, args.reps, dev) for N, M, T in ((32, 300, 100), (32, 4096, 20))]}
-    text = json.dumps(doc, indent=1)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write(text + "\n")
+    bc.write_document(doc, args.out)
 
 
 if __name__ == "__main__":

@@ -8,14 +8,14 @@ One JSON document.  ``--mse-only`` touches nothing this feature added (no kernel
 runs on the parent commit.  ``--trace mse|nll``: five eager steps of the reference-sized problem and nothing else -- the
 program of a kernel-trace run, whose kernel names and counts are what the ``mse`` step of two commits is compared by.
 """
-import argparse
-import json
 import os
 import statistics
 import sys
 import time
 
 import torch
+
+import _bench_common as bc
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -134,12 +134,11 @@ def trace(loss, dev):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=5)
+    ap = bc.arg_parser(__doc__)
+    ap.set_defaults(reps=5)
     ap.add_argument("--mse-only", action="store_true")
     ap.add_argument("--skip-kernel", action="store_true")
     ap.add_argument("--trace", default=None, choices=("mse", "nll"))
-    ap.add_argument("--out", default=None)
     args = ap.parse_args()
     from multimodalfilter_amd import engine
 
@@ -153,11 +152,7 @@ def main():
     if not (args.mse_only or args.skip_kernel):
         doc["kernel"] = [kernel_case(R, M, args.reps, dev) for R, M in KERNEL_SHAPES]
     doc["step"] = [step_case(*shape, args.reps, losses, dev) for shape in STEP_SHAPES]
-    text = json.dumps(doc, indent=1)
-    print(text)
-    if args.out:
-        with open(args.out, "w") as fh:
-            fh.write(text + "\n")
+    bc.write_document(doc, args.out)
 
 
 if __name__ == "__main__":

@@ -8,30 +8,17 @@ torch-ops statement of the same recursion on the same history, predictions and u
 
 One JSON document.  ``densities`` counts the transition densities the recursion evaluates, ``(T - 1) N S M``.
 """
-import argparse
-import json
 import os
 import statistics
 import sys
 
 import torch
 
+import _bench_common as bc
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 DRAWS = 64
-
-
-def _event_ms(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    out = fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b), out
-
-
-def _stats(v):
-    return {"median": statistics.median(v), "min": min(v), "max": max(v)}
 
 
 def torch_simulate(X, F, ll, lw, L, u):
@@ -61,26 +48,12 @@ def torch_simulate(X, F, ll, lw, L, u):
 
 
 def case(N, M, T, reps, dev):
-    import bench
     import multimodalfilter_amd as mmf
-    from multimodalfilter_amd import _abi, synthetic
+    from multimodalfilter_amd import _abi
 
-    d, S = 3, DRAWS
-    torch.manual_seed(0)
-    f = mmf.door_models.DoorCrossmodalParticleFilter().to(dev).eval()
-    synthetic.stabilise_dynamics(f)
-    traj = bench.to_device(synthetic.make_trajectories(state_dim=d, T=T, N=N, seed=5), dev)
-    obs = {k: traj[k][1:] for k in ("image", "gripper_pos", "gripper_sensors")}
-    ctrl = traj["controls"][1:]
-    cal = traj["states"][0][:, None, :] + 0.3 * torch.randn((N, 256, d), device=dev)
-    synthetic.calibrate_measurement_heads(f, {k: v[0] for k, v in obs.items()}, cal)
-    f.num_particles = M
-    f.record_history = True
-    f.noise = mmf.CounterNoise(7)
-    f.initialize_beliefs(mean=traj["states"][0], covariance=(torch.eye(d, device=dev) * 0.1)[None].expand(N, d, d))
-    f.forward_loop(observations=obs, controls=ctrl)
-    h = f.last_history
-    assert h.states.shape == (T, N, M, d)
+    door = bc.recorded_door_run(N, M, T, dev)
+    f, h, ctrl, d = door.f, door.f.last_history, door.ctrl, door.dims[3]
+    S = DRAWS
     dyn = f.dynamics_model
     L = dyn.scale_tril().detach().float().contiguous()
     with torch.no_grad():
@@ -107,14 +80,10 @@ def case(N, M, T, reps, dev):
             "torch_recursion": lambda: torch_simulate(h.states, F, h.log_likelihoods, h.log_weights_in, L, u),
             "smooth_marginal": lambda: f.smooth(method="marginal")}
     with torch.no_grad():
-        out = {k: fn() for k, fn in runs.items()}  # warm-up: code objects, allocator
-        torch.cuda.synchronize()
-        marginal_mean, marginal_cov = out["smooth_marginal"].clone(), f.last_smoothed.covariance.clone()
-        hip = [x.clone() for x in out["hip_recursion"]]
-        times = {k: [] for k in runs}
-        for _ in range(reps):
-            for k, fn in runs.items():  # alternating
-                times[k].append(_event_ms(fn)[0])
+        times = bc.time_alternating(runs, reps)
+        out = {k: fn() for k, fn in runs.items()}  # (smooth_marginal last: last_smoothed is its record)
+        marginal_mean, marginal_cov = out["smooth_marginal"], f.last_smoothed.covariance
+        hip = out["hip_recursion"]
 
     ref = out["torch_recursion"]
     densities = float(T - 1) * N * S * M
@@ -125,7 +94,7 @@ def case(N, M, T, reps, dev):
     stderr = (torch.diagonal(marginal_cov, dim1=-2, dim2=-1) / S).sqrt() + 1e-4 / 5
     return {"filter": "DoorCrossmodalParticleFilter", "batch": N, "particles": M, "steps": T, "state_dim": d, "draws": S,
             "densities": densities, "marginal_pairs": 2.0 * (T - 1) * N * M * M, "prediction_bytes": 4 * d * (T - 1) * N * M,
-            "ms_per_call": {k: _stats(v) for k, v in times.items()},
+            "ms_per_call": {k: bc.stats(v) for k, v in times.items()},
             "densities_per_second": {k: densities / (1e-3 * med[k]) for k in ("hip_recursion", "torch_recursion")},
             "torch_over_hip": med["torch_recursion"] / med["hip_recursion"],
             "marginal_over_simulation": med["smooth_marginal"] / med["smooth_simulation"],
@@ -138,19 +107,11 @@ def case(N, M, T, reps, dev):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = bc.arg_parser(__doc__).parse_args()
     dev = torch.device("cuda:0")
     doc = {"device": torch.cuda.get_device_name(0),
            "cases": [case(N, M, T, args.reps, dev) for N, M, T in ((32, 300, 100), (32, 4096, 20))]}
-    text = json.dumps(doc, indent=1)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write(text + "\n")
+    bc.write_document(doc, args.out)
 
 
 if __name__ == "__main__":

@@ -7,14 +7,14 @@ at 32 x 300 and 256 x 4096, on measurement heads calibrated so that the weights 
 One JSON document.  ``--off-only`` touches nothing this feature added, so the same file runs on the parent commit; with
 ``record_history`` off the loop is the parent's (the persistent launch at 32 x 300), with it on it is the loop of launches.
 """
-import argparse
-import json
 import os
 import statistics
 import sys
 import time
 
 import torch
+
+import _bench_common as bc
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -27,29 +27,15 @@ def _timed(fn):
     return time.perf_counter() - t0
 
 
-def _stats(v):
-    return {"median": statistics.median(v), "min": min(v), "max": max(v)}
-
-
 def pf_case(N, M, T, reps, off_only, dev):
-    import bench
     import multimodalfilter_amd as mmf
-    from multimodalfilter_amd import _abi, engine, synthetic
+    from multimodalfilter_amd import _abi, engine
 
-    d = 3
-    torch.manual_seed(0)
-    f = mmf.door_models.DoorCrossmodalParticleFilter().to(dev).eval()
-    synthetic.stabilise_dynamics(f)
-    traj = bench.to_device(synthetic.make_trajectories(state_dim=d, T=T + 1, N=N, seed=5), dev)
-    obs = {k: traj[k][1:] for k in ("image", "gripper_pos", "gripper_sensors")}
-    ctrl = traj["controls"][1:]
-    cal = traj["states"][0][:, None, :] + 0.3 * torch.randn((N, 256, d), device=dev)
-    synthetic.calibrate_measurement_heads(f, {k: v[0] for k, v in obs.items()}, cal)
-    f.num_particles = M
+    door = bc.recorded_door_run(N, M, T + 1, dev, run=False)
+    f, traj, obs, ctrl, cov0, d = door.f, door.traj, door.obs, door.ctrl, door.cov0, door.dims[3]
     if not off_only:
         f.record_history = True  # reserve() accounts for the history arrays
     f.reserve(steps=T, batch=N, particles=M)
-    cov0 = (torch.eye(d, device=dev) * 0.1)[None].expand(N, d, d)
     settings = [False] if off_only else [False, True]
 
     def run(history):
@@ -66,7 +52,7 @@ def pf_case(N, M, T, reps, off_only, dev):
             times[h].append(1e6 * _timed(lambda: run(h)) / T)
     doc = {"filter": "DoorCrossmodalParticleFilter", "batch": N, "particles": M, "steps": T,
            "persistent_eligible": bool(engine.PF_PERSISTENT and _abi.pf_persistent_plan(N, M, 2) > 0),
-           "forward_loop_us_per_step": {("record_history" if h else "off"): _stats(v) for h, v in times.items()}}
+           "forward_loop_us_per_step": {("record_history" if h else "off"): bc.stats(v) for h, v in times.items()}}
     if off_only:
         return doc
     doc["estimates_identical_bits"] = bool(torch.equal(est[False], est[True]))
@@ -76,27 +62,21 @@ def pf_case(N, M, T, reps, off_only, dev):
         f.smooth(lag)  # warm-up
         v = [1e3 * _timed(lambda: f.smooth(lag)) for _ in range(reps)]
         uniq = f.last_smoothed.unique.float()
-        smooth[name] = {"ms_per_call": _stats(v), "us_per_step": statistics.median(v) * 1e3 / T,
+        smooth[name] = {"ms_per_call": bc.stats(v), "us_per_step": statistics.median(v) * 1e3 / T,
                         "mean_unique_first_step": float(uniq[0].mean()), "mean_unique_last_step": float(uniq[-1].mean())}
     doc["smooth"] = smooth
     return doc
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=5)
+    ap = bc.arg_parser(__doc__)
+    ap.set_defaults(reps=5)
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--off-only", action="store_true")
-    ap.add_argument("--out", default=None)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     doc = {"pf": [pf_case(N, M, args.steps, args.reps, args.off_only, dev) for N, M in ((32, 300), (256, 4096))]}
-    text = json.dumps(doc, indent=1)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write(text + "\n")
+    bc.write_document(doc, args.out)
 
 
 if __name__ == "__main__":

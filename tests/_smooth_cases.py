@@ -249,6 +249,29 @@ def linear_gaussian_models(d, q, r, dev, state_dependent=False):
     return RandomWalk(), GaussianLik()
 
 
+def cpu_filter_with_history(T=4, N=2, M=6, d=3, seed=77, state_dependent=False):
+    """A random-walk filter on the CPU (``F_t = X_t``, ``L = 0.05 I``) holding a hand-made history, for the API tests that
+    need no device: a record of the filter ``f``, ``dims = (T, N, M, d)``, the numpy arrays ``X``, ``ll``, ``lw`` the history
+    was made from and the noise factor ``L``."""
+    from types import SimpleNamespace
+
+    import torch
+
+    import multimodalfilter_amd as mmf
+    from multimodalfilter_amd import base
+
+    q = 0.05
+    L = (q * np.eye(d)).astype(np.float32)
+    X, _, ll, lw = make_case(T, N, M, d, (1e-2, 0.3), 0.5, L, seed=seed)
+    dyn, meas = linear_gaussian_models(d, q, 0.3, torch.device("cpu"), state_dependent=state_dependent)
+    f = mmf.filters.ParticleFilter(dynamics_model=dyn, measurement_model=meas, num_particles=M)
+    f.eval()
+    f.last_history = base.history_record(states=torch.from_numpy(X), log_likelihoods=torch.from_numpy(ll),
+                                         log_weights_in=torch.from_numpy(lw), ancestors=None, resampled=None,
+                                         controls=torch.zeros((T, N, 7)))
+    return SimpleNamespace(f=f, dims=(T, N, M, d), X=X, ll=ll, lw=lw, L=L)
+
+
 # ------------------------------------------------------------------------------------------ on the device
 def dev():
     import torch

@@ -263,23 +263,6 @@ def test_the_binding_refuses_cpu_tensors():
 
 
 # ------------------------------------------------------------------------------------------ 4. the Python refusals
-def _cpu_filter_with_history(T=4, N=2, M=6, d=3):
-    """A random-walk filter on the CPU holding a hand-made history."""
-    import multimodalfilter_amd as mmf
-    from multimodalfilter_amd import base
-
-    q = 0.05
-    L = (q * np.eye(d)).astype(np.float32)
-    X, _, ll, lw = sc.make_case(T, N, M, d, (1e-2, 0.3), 0.5, L, seed=77)
-    dyn, meas = sc.linear_gaussian_models(d, q, 0.3, torch.device("cpu"))
-    f = mmf.filters.ParticleFilter(dynamics_model=dyn, measurement_model=meas, num_particles=M)
-    f.eval()
-    f.last_history = base.history_record(states=torch.from_numpy(X), log_likelihoods=torch.from_numpy(ll),
-                                         log_weights_in=torch.from_numpy(lw), ancestors=None, resampled=None,
-                                         controls=torch.zeros((T, N, 7)))
-    return f, (T, N, M, d)
-
-
 class _CountingNoise:
     """Counts the draws a filter asks for; serves none."""
 
@@ -309,7 +292,8 @@ def test_belief_forecast_refusals_come_before_any_device_work():
     assert list(sig) == ["horizon", "truth", "crps"] and sig["truth"].default is None
     assert sig["crps"].kind is inspect.Parameter.KEYWORD_ONLY and sig["crps"].default is True
 
-    f, (T, N, M, d) = _cpu_filter_with_history()
+    made = sc.cpu_filter_with_history()
+    f, (T, N, M, d) = made.f, made.dims
     f.noise = _CountingNoise()
     truth = torch.zeros((T, N, d))
     before = (f.last_history, f.last_smoothed, f.last_scores)
@@ -342,7 +326,7 @@ def test_belief_forecast_refusals_come_before_any_device_work():
     with pytest.raises(ValueError, match="^belief_forecast needs one process-noise scale_tril"):
         g.belief_forecast(2)
     # one recorded step: every lead is beyond the data, nothing is launched and nothing is drawn
-    one, _ = _cpu_filter_with_history(T=1)
+    one = sc.cpu_filter_with_history(T=1).f
     one.noise = _CountingNoise()
     mean = one.belief_forecast(3, torch.zeros((1, N, d)))
     rec = one.last_forecast

@@ -171,27 +171,8 @@ def test_smooth_map_refusals_on_a_cpu_filter():
         evaluation.path_log_density(pf, np.zeros((2, 2), dtype=np.int64))
 
 
-def _cpu_filter_with_history(state_dependent=False):
-    """A random-walk filter on the CPU (``F_t = X_t``, ``L = 0.05 I``) holding a hand-made history of T = 4, N = 2, M = 6."""
-    import torch
-
-    import multimodalfilter_amd as mmf
-    from multimodalfilter_amd import base
-
-    T, N, M, d, q = 4, 2, 6, 3, 0.05
-    L = (q * np.eye(d)).astype(np.float32)
-    X, _, ll, lw = sc.make_case(T, N, M, d, (1e-2, 0.3), 0.5, L, seed=77)
-    dyn, meas = sc.linear_gaussian_models(d, q, 0.3, torch.device("cpu"), state_dependent=state_dependent)
-    f = mmf.filters.ParticleFilter(dynamics_model=dyn, measurement_model=meas, num_particles=M)
-    f.eval()
-    f.last_history = base.history_record(states=torch.from_numpy(X), log_likelihoods=torch.from_numpy(ll),
-                                         log_weights_in=torch.from_numpy(lw), ancestors=None, resampled=None,
-                                         controls=torch.zeros((T, N, 7)))
-    return f, X, X[:-1].copy(), ll, lw, L
-
-
 def test_state_dependent_noise_is_refused():
-    f = _cpu_filter_with_history(state_dependent=True)[0]
+    f = sc.cpu_filter_with_history(state_dependent=True).f
     with pytest.raises(ValueError, match="state-dependent"):
         f.smooth(method="map")
     assert f.last_smoothed is None
@@ -202,7 +183,8 @@ def test_path_log_density_is_the_definition():
 
     from multimodalfilter_amd import evaluation
 
-    f, X, F, ll, lw, L = _cpu_filter_with_history()
+    made = sc.cpu_filter_with_history()
+    f, X, F, ll, lw, L = made.f, made.X, made.X[:-1].copy(), made.ll, made.lw, made.L
     T, N, M, _ = X.shape
     ref = mc.viterbi_reference(X, F, ll, lw[0], L)
     got = evaluation.path_log_density(f, ref["indices"])

@@ -271,7 +271,6 @@ def test_belief_modes_refusals_come_before_any_device_work():
 
     import multimodalfilter_amd as mmf
     from multimodalfilter_amd import _abi, base
-    from test_density_cases_cpu import _cpu_filter_with_history
 
     sig = inspect.signature(mmf.filters.ParticleFilter.belief_modes).parameters
     assert list(sig) == ["self", "of", "max_modes", "link_radius", "bandwidth", "min_bandwidth"] and sig["of"].default == "filtered"
@@ -287,7 +286,8 @@ def test_belief_modes_refusals_come_before_any_device_work():
     with pytest.raises(ValueError, match="of must be"):
         pf.belief_modes(of="predicted")
 
-    f, (T, N, M, d) = _cpu_filter_with_history()
+    made = sc.cpu_filter_with_history()
+    f, (T, N, M, d) = made.f, made.dims
     before = (f.last_history, f.last_smoothed, f.last_quantiles, f.last_scores, f.last_density)
     f.last_smoothed = base.belief_record(covariance=torch.zeros((T, N, d, d)), unique=torch.zeros((T, N), dtype=torch.int32), lag=None)
     with pytest.raises(ValueError, match=r"belief_modes\(of='smoothed'\).*no per-step weights"):

@@ -201,25 +201,6 @@ def test_the_raster_struct_matches_the_header_as_gcc_lays_it_out(tmp_path):
 
 
 # ------------------------------------------------------------------------------------------ 4. the Python refusals
-def _cpu_filter_with_history():
-    """A random-walk filter on the CPU holding a hand-made history of T = 4, N = 2, M = 6."""
-    import torch
-
-    import multimodalfilter_amd as mmf
-    from multimodalfilter_amd import base
-
-    T, N, M, d, q = 4, 2, 6, 3, 0.05
-    L = (q * np.eye(d)).astype(np.float32)
-    X, _, ll, lw = sc.make_case(T, N, M, d, (1e-2, 0.3), 0.5, L, seed=77)
-    dyn, meas = sc.linear_gaussian_models(d, q, 0.3, torch.device("cpu"))
-    f = mmf.filters.ParticleFilter(dynamics_model=dyn, measurement_model=meas, num_particles=M)
-    f.eval()
-    f.last_history = base.history_record(states=torch.from_numpy(X), log_likelihoods=torch.from_numpy(ll),
-                                         log_weights_in=torch.from_numpy(lw), ancestors=None, resampled=None,
-                                         controls=torch.zeros((T, N, 7)))
-    return f, (T, N, M, d)
-
-
 def test_belief_maps_refusals_come_before_any_device_work():
     import torch
 
@@ -242,7 +223,8 @@ def test_belief_maps_refusals_come_before_any_device_work():
         with pytest.raises(ValueError, match="of must be 'predicted', 'filtered' or 'smoothed'"):
             pf.belief_maps(torch.zeros((4, 2, 3)), (1.0, 1.0), of=bad)
 
-    f, (T, N, M, d) = _cpu_filter_with_history()
+    made = sc.cpu_filter_with_history()
+    f, (T, N, M, d) = made.f, made.dims
     c = torch.zeros((T, N, d))
     before = {k: v for k, v in vars(f).items() if k.startswith("last_")}
     f.last_smoothed = base.belief_record(indices=torch.zeros((T, N), dtype=torch.int32), log_posterior=torch.zeros(N), lag=None,
