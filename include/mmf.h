@@ -615,6 +615,87 @@ int mmf_pf_forward_loop_history(const MmfPfLoopArgs* args /* host */, const MmfP
                                 float ess_threshold, int32_t* resampled_steps,
                                 const MmfPfDedupWorkspace* ws /* host or null */, void* stream);
 
+/* REGULARISED (post-resampling) particle filter (Musso, Oudjane & Le Gland 2001): after a step resampled, every survivor is
+ * drawn from the kernel density of the weighted set instead of being copied, x <- x[a] + h C^{1/2} eps, so that the copies of
+ * an ancestor separate before the process noise does it.  Upstream torchfilter copies the survivors verbatim.  Purely additive
+ * to ABI 42: new symbols and structs of their own.  The ONE definition every path follows (fp32, per trajectory n):
+ *   inputs    mu (d), C (d, d), ess: what mmf_pf_reweight_resample_belief writes for the pre-resampling weighted set
+ *             (estimate, cov, ess -- same bits); x (M, d): the set K1 gathered; scale > 0, floor (d floats >= 0), shrink 0 / 1
+ *   bandwidth h = scale * powf(4 / ((d + 2) ess), 1 / (d + 4)): mmf_pf_density's Silverman factor on the ESS (not on M: after
+ *             a step that spent its weight on few particles the kernel must be wide)
+ *   factor    L = clamped Cholesky factor of C + diag(floor^2), column by column:
+ *               s_j = C_jj + floor_j^2 - sum_{k<j} L_jk^2,           L_jj = s_j > 0 ? sqrt(s_j) : 0
+ *               L_ij = L_jj > 0 ? (C_ij - sum_{k<j} L_ik L_jk) / L_jj : 0      (i > j)
+ *             a collapsed direction gets no jitter unless floor gives it one; H = h L (each entry one rounded product)
+ *   step      shrink == 0: x'_i = x_i + sum_{k<=i} H_ik eps_k          (the set's covariance becomes about (1 + h^2) C)
+ *             shrink != 0: x'_i = mu_i + a (x_i - mu_i) + sum_{k<=i} H_ik eps_k, a = sqrt(max(1 - h^2, 0))  (Liu & West: mean
+ *             and covariance are preserved).  Evaluated as an fma chain in ascending k, starting from x_i (or from
+ *             fma(a, x_i - mu_i, mu_i)): no other rounding, so the noise source does not change the bits
+ *   unchanged a trajectory whose ess is not finite or < 1, or whose C has a non-finite entry, is not written at all (NaN rows
+ *             stay NaN); neither is one with resampled[n] == 0 (an ESS-triggered step kept it: it has no copies to separate)
+ *   noise     eps standard normal: noise_mode 0, a tensor (N, M, d); noise_mode 2, generated in the kernel from
+ *             (noise_seed, noise_step, noise_traj0 + n, m) on the Philox stream MMF_PHILOX_STREAM_JITTER (include/mmf_philox.h),
+ *             the first d of the particle's four normals -- what mmf_philox_normals_stream materialises
+ * Ancestors, log-weights, the estimate and the belief record of the step are K1's: this call touches the gathered set only.
+ *   bandwidth (N) or null      h; NaN where ess is not finite or < 1; 0 where resampled[n] == 0
+ *   factor    (N, d, d) or null  H, the factor that was applied (upper triangle 0); all 0 where the row was left unchanged
+ * A streaming kernel (8 d bytes per particle with counter noise, 12 d with a tensor): a wave takes 256 consecutive particles
+ * of one trajectory, four per lane as d 16-byte vectors (the last M mod 4 particles of a row element by element), computes
+ * h and H once in uniform registers, and the grid is sized by the bytes (at most 8192 one-wave workgroups, grid-stride), not by
+ * the trajectories.  No atomics: every output particle is written by one lane, so two calls and any batch give the same bits.
+ * MMF_EINVAL: null args / states / cov / ess, null noise with noise_mode 0, shrink without mean, d outside 1..4, M < 1, N < 0,
+ * scale not finite or <= 0, a negative or NaN floor, noise_mode other than 0 / 2; N == 0 is a successful no-op. */
+typedef struct MmfPfRegulariseArgs {
+  int32_t N, M, d;
+  int32_t shrink;            /* != 0: Liu & West shrinkage towards `mean`                                          */
+  float* states;             /* (N, M, d) in place                                                                 */
+  const float* cov;          /* (N, d, d)                                                                          */
+  const float* ess;          /* (N)                                                                                */
+  const float* mean;         /* (N, d): required with shrink, otherwise unused (may be null)                       */
+  const int32_t* resampled;  /* (N) 1 / 0, or null: every trajectory resampled                                     */
+  const float* noise;        /* noise_mode 0: (N, M, d) standard normal                                            */
+  uint64_t noise_seed;       /* noise_mode 2                                                                       */
+  uint32_t noise_step;
+  uint32_t noise_traj0;      /* global index of this shard's first trajectory                                      */
+  int32_t noise_mode;        /* 0: `noise` tensor; 2: generated in the kernel                                      */
+  float scale;
+  float floor[MMF_MAX_STATE_DIM];
+  float* bandwidth;          /* (N) out or null                                                                    */
+  float* factor;             /* (N, d, d) out or null                                                              */
+} MmfPfRegulariseArgs;       /* host struct holding device pointers                                                */
+int mmf_pf_regularise(const MmfPfRegulariseArgs* args /* host */, void* stream);
+
+/* The step loop with regularised resampling: after the K1 launch of every step (plain, soft or ESS-triggered resampling) one
+ * mmf_pf_regularise launch on the buffer K1 gathered into, with K1's weighted mean (estimate_scratch under estimate_argmax),
+ * covariance and ESS -- K1 is called in its recording form, so the size limits of a recording call apply -- and, with a
+ * threshold, its decisions.  Always the loop of launches: the persistent form (args->persistent is ignored) and the run-table
+ * path are not eligible -- jittered particles have no runs.  Everything the loop wrote before -- estimates, records,
+ * ancestors, log-weights, the history -- is what the same loop writes from the jittered belief; the history holds the
+ * propagated sets and K1's ancestors as ever.
+ *   history          as mmf_pf_forward_loop_history (and what it refuses), or null
+ *   ess_threshold    0: off; otherwise as mmf_pf_forward_loop_adaptive, with resampled_steps (T, N) or null
+ *   reg              scale / floor / shrink as above; noise (T, N, M, d), or noise_mode 2 with step t drawing counter step
+ *                    noise_step0 + t; cov (N, d, d) / ess (N) / resampled (N) scratch for what args (cov_steps, ess_steps)
+ *                    and resampled_steps do not record (each required only then); bandwidth_steps (T, N) or null
+ * MMF_EINVAL: null args / reg, args->resample_mode == 0, a missing scratch, and whatever the loop and mmf_pf_regularise refuse. */
+typedef struct MmfPfLoopRegularise {
+  float scale;
+  float floor[MMF_MAX_STATE_DIM];
+  int32_t shrink;
+  const float* noise;        /* (T, N, M, d) or null with noise_mode 2                                             */
+  uint64_t noise_seed;
+  uint32_t noise_step0;
+  uint32_t noise_traj0;
+  int32_t noise_mode;
+  float* cov;                /* (N, d, d) scratch, or null where args->cov_steps is given                          */
+  float* ess;                /* (N) scratch, or null where args->ess_steps is given                                */
+  int32_t* resampled;        /* (N) scratch, or null without a threshold or where resampled_steps is given         */
+  float* bandwidth_steps;    /* (T, N) out or null                                                                 */
+} MmfPfLoopRegularise;       /* host struct holding device pointers                                                */
+int mmf_pf_forward_loop_regularised(const MmfPfLoopArgs* args /* host */, const MmfPfHistory* history /* host or null */,
+                                    float ess_threshold, int32_t* resampled_steps,
+                                    const MmfPfLoopRegularise* reg /* host */, void* stream);
+
 /* The persistent form of the step loop (MmfPfLoopArgs.persistent): at the sizes the reference itself runs (32
  * trajectories x 300 particles: door_models/pf.py:24-27, eval_helpers.py:125-142) a step is bound by the fixed cost
  * of its four launches; one launch whose workgroups keep ONE network's weights in LDS for all T steps and hand
@@ -644,6 +725,10 @@ int mmf_pf_dynamics_philox(const float* packed, int n_res, int precision, const 
                            void* stream);
 int mmf_philox_normals(unsigned long long seed, unsigned step, unsigned traj0, float* out, int N, int M, int d,
                        void* stream);
+/* the same block on another stream of the generator (MMF_PHILOX_STREAM_*; stream 0 IS mmf_philox_normals): what
+ * mmf_pf_regularise draws in noise_mode 2 is stream MMF_PHILOX_STREAM_JITTER */
+int mmf_philox_normals_stream(unsigned long long seed, unsigned philox_stream, unsigned step, unsigned traj0, float* out,
+                              int N, int M, int d, void* stream);
 int mmf_philox_uniforms(unsigned long long seed, unsigned step0, unsigned traj0, float* out, int T, int N,
                         void* stream);
 

@@ -22,6 +22,7 @@
 
 #define MMF_PHILOX_STREAM_NOISE 0u     /* per-particle process noise            */
 #define MMF_PHILOX_STREAM_UNIFORM 1u   /* per-trajectory resampling uniforms    */
+#define MMF_PHILOX_STREAM_JITTER 2u    /* per-particle jitter of regularised resampling (mmf_pf_regularise) */
 
 #if defined(__HIPCC__)
 #define MMF_PHILOX_MULHI(a, b) __umulhi((a), (b))
@@ -74,12 +75,12 @@ MMF_DET_FN void mmf_det_sincos2pi(uint32_t j, float* c, float* s) {
 }
 
 /* 4 standard normals of (seed, stream | t, n, m): key = seed, counter = (m, n, t, stream) */
-MMF_DET_FN void mmf_philox_normal4(uint64_t seed, uint32_t t, uint32_t n, uint32_t m, float z[4]) {
+MMF_DET_FN void mmf_philox_normal4_stream(uint64_t seed, uint32_t stream, uint32_t t, uint32_t n, uint32_t m, float z[4]) {
 #if defined(__HIPCC__)
 #pragma clang fp contract(off)
 #endif
   uint32_t x[4];
-  mmf_philox4x32_10((uint32_t)seed, (uint32_t)(seed >> 32), m, n, t, MMF_PHILOX_STREAM_NOISE, x);
+  mmf_philox4x32_10((uint32_t)seed, (uint32_t)(seed >> 32), m, n, t, stream, x);
   for (int p = 0; p < 2; ++p) {
     const float u1 = ((float)(x[2 * p] >> 9) + 0.5f) * 1.1920929e-07f;   /* (k + 1/2) 2^-23 in (0, 1): exact in fp32 */
     const float r = MMF_PHILOX_SQRT(-2.0f * mmf_det_log(u1));
@@ -88,6 +89,11 @@ MMF_DET_FN void mmf_philox_normal4(uint64_t seed, uint32_t t, uint32_t n, uint32
     z[2 * p] = r * c;
     z[2 * p + 1] = r * s;
   }
+}
+
+/* the process noise: stream 0 of the above, the bits it always had */
+MMF_DET_FN void mmf_philox_normal4(uint64_t seed, uint32_t t, uint32_t n, uint32_t m, float z[4]) {
+  mmf_philox_normal4_stream(seed, MMF_PHILOX_STREAM_NOISE, t, n, m, z);
 }
 
 /* uniform in [0, 1) with 24 bits for trajectory n at step t (systematic resampling) */

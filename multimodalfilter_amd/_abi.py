@@ -103,6 +103,25 @@ class MmfPfHistory(Structure):
     _fields_ = [("states_steps", _FP), ("logw_in_steps", _FP), ("logw_in0", _FP)]
 
 
+PHILOX_STREAM_NOISE, PHILOX_STREAM_UNIFORM, PHILOX_STREAM_JITTER = 0, 1, 2  # include/mmf_philox.h: MMF_PHILOX_STREAM_*
+
+
+class MmfPfRegulariseArgs(Structure):
+    """``mmf_pf_regularise`` (include/mmf.h): the kernel jitter of a resampled set."""
+    _fields_ = [("N", c_int32), ("M", c_int32), ("d", c_int32), ("shrink", c_int32),
+                ("states", _FP), ("cov", _FP), ("ess", _FP), ("mean", _FP), ("resampled", _FP), ("noise", _FP),
+                ("noise_seed", ctypes.c_uint64), ("noise_step", ctypes.c_uint32), ("noise_traj0", ctypes.c_uint32),
+                ("noise_mode", c_int32), ("scale", c_float), ("floor", c_float * MMF_MAX_STATE_DIM),
+                ("bandwidth", _FP), ("factor", _FP)]
+
+
+class MmfPfLoopRegularise(Structure):
+    """What ``mmf_pf_forward_loop_regularised`` adds to ``MmfPfLoopArgs`` (include/mmf.h)."""
+    _fields_ = [("scale", c_float), ("floor", c_float * MMF_MAX_STATE_DIM), ("shrink", c_int32), ("noise", _FP),
+                ("noise_seed", ctypes.c_uint64), ("noise_step0", ctypes.c_uint32), ("noise_traj0", ctypes.c_uint32),
+                ("noise_mode", c_int32), ("cov", _FP), ("ess", _FP), ("resampled", _FP), ("bandwidth_steps", _FP)]
+
+
 class MmfPfSmoothArgs(Structure):
     _fields_ = [("T", c_int32), ("N", c_int32), ("M", c_int32), ("d", c_int32), ("lag", c_int32),
                 ("states_steps", _FP), ("loglik_steps", _FP), ("logw_in_steps", _FP), ("logw_in0", _FP),
@@ -316,6 +335,9 @@ SIGNATURES = {
     "mmf_pf_forward_loop_dedup": (c_int, [POINTER(MmfPfLoopArgs), POINTER(MmfPfDedupWorkspace), c_void_p]),
     "mmf_pf_forward_loop_history": (c_int, [POINTER(MmfPfLoopArgs), POINTER(MmfPfHistory), ctypes.c_float, _FP,
                                             POINTER(MmfPfDedupWorkspace), c_void_p]),
+    "mmf_pf_regularise": (c_int, [POINTER(MmfPfRegulariseArgs), c_void_p]),
+    "mmf_pf_forward_loop_regularised": (c_int, [POINTER(MmfPfLoopArgs), POINTER(MmfPfHistory), ctypes.c_float, _FP,
+                                                POINTER(MmfPfLoopRegularise), c_void_p]),
     "mmf_pf_smooth": (c_int, [POINTER(MmfPfSmoothArgs), c_void_p]),
     "mmf_pf_smooth_lds_bytes": (c_size_t, [c_int]),
     "mmf_pf_smooth_marginal": (c_int, [POINTER(MmfPfSmoothMarginalArgs), c_void_p]),
@@ -352,6 +374,8 @@ SIGNATURES = {
     "mmf_pf_dynamics_philox": (c_int, [_FP, c_int, c_int, _FP, _FP, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
                                        _FP, _FP, _FP, c_int, c_int, c_int, c_void_p]),
     "mmf_philox_normals": (c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _FP, c_int, c_int, c_int, c_void_p]),
+    "mmf_philox_normals_stream": (c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _FP, c_int, c_int,
+                                          c_int, c_void_p]),
     "mmf_philox_uniforms": (c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _FP, c_int, c_int, c_void_p]),
     "mmf_dynamics_forward_loop": (c_int, [_FP, c_int, c_int, _FP, _FP, _FP, _FP, c_int, c_int, c_int, c_void_p]),
     "mmf_traj_program": (c_int, [_FP, c_int, _FP, POINTER(c_void_p), c_int, c_int, c_int, c_void_p]),
@@ -564,6 +588,57 @@ def philox_normals(seed: int, step: int, traj0: int, out: torch.Tensor):
     N, M, d = out.shape
     with _on(out):
         _check(load().mmf_philox_normals(seed, step, traj0, ptr(out), N, M, d, stream_of(out)), "mmf_philox_normals")
+
+
+def philox_normals_stream(seed: int, stream: int, step: int, traj0: int, out: torch.Tensor):
+    """The ``(N, M, d)`` block of counter step ``step`` on Philox stream ``stream`` (``PHILOX_STREAM_*``; 0 is ``philox_normals``)."""
+    N, M, d = out.shape
+    with _on(out):
+        _check(load().mmf_philox_normals_stream(seed, stream, step, traj0, ptr(out), N, M, d, stream_of(out)),
+               "mmf_philox_normals_stream")
+
+
+def regularise_floor(floor, d: int):
+    """``floor`` of regularised resampling as ``d`` floats: one float for every dimension or ``d`` of them, each finite and
+    ``>= 0``; anything else is a ``ValueError``."""
+    import numbers
+
+    vals = [floor] * d if isinstance(floor, numbers.Real) and not isinstance(floor, bool) else list(floor)
+    if len(vals) != d:
+        raise ValueError(f"regularisation floor must be a float or d = {d} floats, got {len(vals)}")
+    vals = [float(v) for v in vals]
+    if not all(v >= 0.0 and v != float("inf") for v in vals):
+        raise ValueError(f"regularisation floor must be finite and >= 0, got {vals!r}")
+    return vals
+
+
+def pf_regularise(states, cov, ess, *, scale: float, floor=0.0, shrink: bool = False, mean=None, resampled=None, noise=None,
+                  counter=None, bandwidth=None, factor=None):
+    """``mmf_pf_regularise`` (include/mmf.h): jitter the resampled set ``states (N, M, d)`` in place with ``h L eps`` -- ``h``
+    Silverman's factor on ``ess (N)`` times ``scale``, ``L`` the clamped Cholesky factor of ``cov (N, d, d) + diag(floor^2)``;
+    ``shrink`` shrinks towards ``mean (N, d)`` first (Liu & West).  ``noise (N, M, d)`` standard normal, or ``counter = (seed,
+    step, traj0)``: generated in the kernel on the jitter stream.  ``resampled (N)`` int32: rows with 0 are left as they are.
+    Optional outputs ``bandwidth (N)`` and ``factor (N, d, d)`` (``h L``)."""
+    N, M, d = states.shape
+    assert cov.shape == (N, d, d) and ess.shape == (N,)
+    assert (noise is None) != (counter is None), "either a noise tensor or a counter triple"
+    assert noise is None or noise.shape == (N, M, d)
+    assert mean is None or mean.shape == (N, d)
+    assert resampled is None or resampled.shape == (N,)
+    assert (bandwidth is None or bandwidth.shape == (N,)) and (factor is None or factor.shape == (N, d, d))
+    a = MmfPfRegulariseArgs()
+    a.N, a.M, a.d, a.shrink = N, M, d, int(bool(shrink))
+    a.states, a.cov, a.ess, a.mean = vp(states), vp(cov), vp(ess), vp(mean)
+    a.resampled, a.noise = vp(resampled, torch.int32), vp(noise)
+    if counter is not None:
+        a.noise_mode = 2
+        a.noise_seed, a.noise_step, a.noise_traj0 = (int(v) for v in counter)
+    a.scale = float(scale)
+    for i, v in enumerate(regularise_floor(floor, d)):
+        a.floor[i] = v
+    a.bandwidth, a.factor = vp(bandwidth), vp(factor)
+    with _on(states):
+        _check(load().mmf_pf_regularise(ctypes.byref(a), stream_of(states)), "mmf_pf_regularise")
 
 
 def philox_uniforms(seed: int, step0: int, traj0: int, out: torch.Tensor):
@@ -1051,14 +1126,16 @@ def pf_dynamics_runs_philox(packed, n_res, precision, states_prev, traj_bias, se
 
 def pf_forward_loop(args: MmfPfLoopArgs, like: torch.Tensor, events=None, event_stride: int = 1, *,
                     ess_threshold: float = None, resampled_steps=None, dedup: MmfPfDedupWorkspace = None,
-                    history: MmfPfHistory = None) -> int:
+                    history: MmfPfHistory = None, regularise: MmfPfLoopRegularise = None) -> int:
     """Enqueue T filter steps; returns the final-location bits (see include/mmf.h).
     ``events``: optional flat list of created ``torch.cuda.Event`` (timing) recorded in C
     around the launches of every ``event_stride``-th step.
     ``ess_threshold``: ESS-triggered resampling (``mmf_pf_forward_loop_adaptive``), ``resampled_steps`` its ``(T, N)`` int32
     decisions or ``None``.  ``dedup``: the run-table workspace (``mmf_pf_forward_loop_dedup``: the dynamics network once per
     distinct resampled ancestor; plain resampling only) or ``None``.  ``history``: the arrays a smoother needs
-    (``mmf_pf_forward_loop_history``: the loop of launches with the same threshold / workspace) or ``None``."""
+    (``mmf_pf_forward_loop_history``: the loop of launches with the same threshold / workspace) or ``None``.
+    ``regularise``: regularised resampling (``mmf_pf_forward_loop_regularised``: the loop of launches with one jitter launch
+    after every K1, the threshold and the history as given, no run table) or ``None``."""
     loc = c_int32(0)
     args.final_location = ctypes.pointer(loc)
     if events is not None:
@@ -1066,7 +1143,12 @@ def pf_forward_loop(args: MmfPfLoopArgs, like: torch.Tensor, events=None, event_
         args.events = arr
         args.event_stride = event_stride
     with _on(like):
-        if history is not None:
+        if regularise is not None:
+            _check(load().mmf_pf_forward_loop_regularised(
+                ctypes.byref(args), None if history is None else ctypes.byref(history),
+                0.0 if ess_threshold is None else float(ess_threshold), ptr(resampled_steps, dtype=torch.int32),
+                ctypes.byref(regularise), stream_of(like)), "mmf_pf_forward_loop_regularised")
+        elif history is not None:
             _check(load().mmf_pf_forward_loop_history(
                 ctypes.byref(args), ctypes.byref(history), 0.0 if ess_threshold is None else float(ess_threshold),
                 ptr(resampled_steps, dtype=torch.int32), None if dedup is None else ctypes.byref(dedup), stream_of(like)),

@@ -1187,13 +1187,13 @@ extern "C" int mmf_pf_dedup_deal(const int32_t* n_runs, int N, int M, int tile, 
 }
 
 namespace {
-__global__ void philox_normals_kernel(unsigned long long seed, unsigned step, unsigned traj0, int M, int d, size_t R,
-                                      float* __restrict__ out) {
+__global__ void philox_normals_kernel(unsigned long long seed, unsigned philox_stream, unsigned step, unsigned traj0, int M,
+                                      int d, size_t R, float* __restrict__ out) {
   const size_t r = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (r >= R) return;
   float z[4];
   const unsigned traj = static_cast<unsigned>(r / M);
-  mmf_philox_normal4(seed, step, traj0 + traj, static_cast<unsigned>(r - static_cast<size_t>(traj) * M), z);
+  mmf_philox_normal4_stream(seed, philox_stream, step, traj0 + traj, static_cast<unsigned>(r - static_cast<size_t>(traj) * M), z);
   for (int i = 0; i < d; ++i) out[r * d + i] = z[i];
 }
 __global__ void philox_uniforms_kernel(unsigned long long seed, unsigned step0, unsigned traj0, int T, int N,
@@ -1204,15 +1204,20 @@ __global__ void philox_uniforms_kernel(unsigned long long seed, unsigned step0, 
 }
 }  // namespace
 
-extern "C" int mmf_philox_normals(unsigned long long seed, unsigned step, unsigned traj0, float* out, int N, int M,
-                                  int d, void* stream) {
+extern "C" int mmf_philox_normals_stream(unsigned long long seed, unsigned philox_stream, unsigned step, unsigned traj0,
+                                         float* out, int N, int M, int d, void* stream) {
   if (!out || N < 0 || M < 1 || d < 1 || d > 4) return MMF_EINVAL;
   const size_t R = static_cast<size_t>(N) * M;
   if (R == 0) return 0;
   philox_normals_kernel<<<static_cast<unsigned>((R + 255) / 256), 256, 0, static_cast<hipStream_t>(stream)>>>(
-      seed, step, traj0, M, d, R, out);
+      seed, philox_stream, step, traj0, M, d, R, out);
   MMF_CHECK_LAUNCH();
   return 0;
+}
+
+extern "C" int mmf_philox_normals(unsigned long long seed, unsigned step, unsigned traj0, float* out, int N, int M,
+                                  int d, void* stream) {
+  return mmf_philox_normals_stream(seed, MMF_PHILOX_STREAM_NOISE, step, traj0, out, N, M, d, stream);
 }
 
 extern "C" int mmf_philox_uniforms(unsigned long long seed, unsigned step0, unsigned traj0, float* out, int T, int N,

@@ -18,11 +18,22 @@
 // h->states_steps (`prop`) instead of `other`, K1 still gathers into `cur` -- a scratch buffer, never a history slice --, and
 // where a step reads what the previous one PROPAGATED (no resampling, the run table) it reads slice t - 1 (`rd`).  `cur` /
 // `other` / `lw_cur` / `lw_other` keep swapping as names, so final_location is what it is without a history.  Same bits.
+// reg (mmf_pf_forward_loop_regularised): after the K1 launch of every resampling branch one mmf_pf_regularise launch on the
+// buffer K1 gathered into (`cur`), with K1's weighted mean, covariance and ESS -- K1 in its recording form, into the step's
+// slices of the records or into reg's scratch -- and, with a threshold, its decisions.  No run table: jittered particles
+// have no runs.  The launch sits inside K1's pair of timing events.
 static int pf_enqueue_steps(const MmfPfLoopArgs* a, void* stream, bool with_events, float ess_threshold = 0.f,
                             int32_t* resampled_steps = nullptr, const MmfPfDedupWorkspace* ws = nullptr,
-                            const MmfPfHistory* h = nullptr) {
+                            const MmfPfHistory* h = nullptr, const MmfPfLoopRegularise* reg = nullptr) {
   if (!a) return MMF_EINVAL;
   const bool adaptive = ess_threshold > 0.f;
+  if (reg) {
+    if (a->resample_mode == 0 || ws) return MMF_EINVAL;
+    if ((!a->cov_steps && !reg->cov) || (!a->ess_steps && !reg->ess)) return MMF_EINVAL;
+    if (adaptive && !resampled_steps && !reg->resampled) return MMF_EINVAL;
+    if (reg->noise_mode != 0 && reg->noise_mode != 2) return MMF_EINVAL;
+    if (reg->noise_mode == 0 && !reg->noise) return MMF_EINVAL;
+  }
   if (a->T < 0 || a->N < 1 || a->M < 1 || a->n_meas < 1 || a->n_meas > MMF_LOOP_MAX_MEAS) return MMF_EINVAL;
   if (a->resample_mode < 0 || a->resample_mode > 2) return MMF_EINVAL;
   if (!a->dyn_packed || !a->dyn_bias || (!a->noise && a->noise_mode != 2) || !a->scale_tril || !a->states_a || !a->states_b ||
@@ -109,6 +120,12 @@ static int pf_enqueue_steps(const MmfPfLoopArgs* a, void* stream, bool with_even
     float* cov = a->cov_steps ? a->cov_steps + t * row * a->d * a->d : nullptr;
     float* ess = a->ess_steps ? a->ess_steps + t * row : nullptr;
     float* lev = a->log_evidence_steps ? a->log_evidence_steps + t * row : nullptr;
+    int32_t* took = resampled_steps ? resampled_steps + t * row : nullptr;
+    if (reg) {  // the jitter reads K1's covariance, ESS and decisions: scratch where the caller records none
+      if (!cov) cov = reg->cov;
+      if (!ess) ess = reg->ess;
+      if (adaptive && !took) took = reg->resampled;
+    }
     if (a->estimate_argmax) {
       // the particle with the largest pre-resampling weight; K1's weighted mean goes to the scratch.  In the plain
       // resampling loop the incoming weights are uniform from the second step on (see below)
@@ -122,8 +139,7 @@ static int pf_enqueue_steps(const MmfPfLoopArgs* a, void* stream, bool with_even
       // a kept trajectory carries its weights forward, so the log-weights travel every step (as with soft resampling)
       const float* u = a->uniforms + t * (a->resample_mode == 1 ? row : nm);
       rc = mmf_pf_reweight_resample_adaptive(ll, lw_in, prop, u, est, cur, lw_out, anc, a->N, a->M, a->d, a->resample_mode,
-                                             soft ? a->soft_alpha : 1.0f, ess_threshold,
-                                             resampled_steps ? resampled_steps + t * row : nullptr, cov, ess, lev, stream);
+                                             soft ? a->soft_alpha : 1.0f, ess_threshold, took, cov, ess, lev, stream);
       if (rc) return rc;
     } else if (soft) {
       // torchfilter's soft resampling: survivors carry importance weights, so the log-weights travel every step
@@ -154,6 +170,18 @@ static int pf_enqueue_steps(const MmfPfLoopArgs* a, void* stream, bool with_even
                                            t == a->T - 1 || (h && h->logw_in_steps) ? lw_out : nullptr, anc, a->N, a->M, a->M, a->d,
                                            a->resample_mode, 1.0f, cov, ess, lev, stream);
       if (rc) return rc;  // resampled particles land back in `cur`
+    }
+    if (reg) {  // every branch that gets here with reg gathered into `cur` (resample_mode != 0, no run table)
+      MmfPfRegulariseArgs r{};
+      r.N = a->N; r.M = a->M; r.d = a->d; r.shrink = reg->shrink;
+      r.states = cur; r.cov = cov; r.ess = ess; r.mean = est; r.resampled = adaptive ? took : nullptr;
+      r.noise = reg->noise_mode == 0 ? reg->noise + t * nm * a->d : nullptr;
+      r.noise_seed = reg->noise_seed; r.noise_step = reg->noise_step0 + static_cast<unsigned>(t);
+      r.noise_traj0 = reg->noise_traj0; r.noise_mode = reg->noise_mode;
+      r.scale = reg->scale;
+      for (int i = 0; i < MMF_MAX_STATE_DIM; ++i) r.floor[i] = reg->floor[i];
+      r.bandwidth = reg->bandwidth_steps ? reg->bandwidth_steps + t * row : nullptr;
+      if ((rc = mmf_pf_regularise(&r, stream))) return rc;
     }
     if ((rc = mark())) return rc;
     float* l = lw_cur; lw_cur = lw_other; lw_other = l;
@@ -224,6 +252,24 @@ extern "C" int mmf_pf_forward_loop_history(const MmfPfLoopArgs* a, const MmfPfHi
   MmfPfLoopArgs launches = *a;
   launches.persistent = 0;
   return pf_enqueue_steps(&launches, stream, true, adaptive ? ess_threshold : 0.f, adaptive ? resampled_steps : nullptr, ws, h);
+}
+
+// The loop with regularised resampling (include/mmf.h): always the loop of launches, no run table; with a history the
+// checks of mmf_pf_forward_loop_history, with a threshold those of mmf_pf_forward_loop_adaptive.
+extern "C" int mmf_pf_forward_loop_regularised(const MmfPfLoopArgs* a, const MmfPfHistory* h, float ess_threshold,
+                                               int32_t* resampled_steps, const MmfPfLoopRegularise* reg, void* stream) {
+  if (!a || !reg || a->resample_mode == 0) return MMF_EINVAL;
+  const bool adaptive = ess_threshold != 0.f;
+  if (adaptive && !(ess_threshold > 0.f && ess_threshold <= 1.f)) return MMF_EINVAL;
+  if (h) {
+    if (!h->states_steps || !h->logw_in0 || !a->loglik_steps || !a->indices_steps) return MMF_EINVAL;
+    const bool soft = a->soft_alpha > 0.f && a->soft_alpha < 1.f;
+    if ((soft || adaptive) && !h->logw_in_steps) return MMF_EINVAL;  // the weights travel
+  }
+  MmfPfLoopArgs launches = *a;
+  launches.persistent = 0;
+  return pf_enqueue_steps(&launches, stream, true, adaptive ? ess_threshold : 0.f, adaptive ? resampled_steps : nullptr, nullptr,
+                          h, reg);
 }
 
 // Open-loop rollout x_t = f(x_{t-1}, u_t): replaces torchfilter's DynamicsModel.forward_loop (call

@@ -161,6 +161,9 @@ PF_PERSISTENT = os.environ.get("MMF_PF_PERSISTENT", "1") not in ("", "0")
 # resampled ancestor (mmf_pf_forward_loop_dedup, include/mmf.h: K1 writes a run table instead of gathering, the next dynamics
 # launch expands every run into its slots with the slots' own noise); bit-identical to mmf_pf_forward_loop.  "0": A/B, off.
 PF_DEDUP = os.environ.get("MMF_PF_DEDUP", "1") not in ("", "0")
+# Regularised resampling (ParticleFilter.regularisation; mmf_pf_regularise, include/mmf.h) is a per-filter switch, None by
+# default.  A float > 0 here is the scale a newly built ParticleFilter starts with: an A/B of whole scripts, evaluation only.
+PF_REGULARISATION = float(os.environ["MMF_PF_REGULARISATION"]) if os.environ.get("MMF_PF_REGULARISATION", "") not in ("", "0") else None
 # The EKF step loop likewise (mmf_ekf_persistent_plan > 0; csrc/ekf_persistent.inc): a wave owns 8 trajectories of one
 # sub-filter for all T steps, K > 1 sub-filters meet once per step through L2; bit-identical to the 2 T launches.
 EKF_PERSISTENT = os.environ.get("MMF_EKF_PERSISTENT", "1") not in ("", "0")

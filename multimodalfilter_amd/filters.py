@@ -127,6 +127,27 @@ class ParticleFilter(base.Filter):
     belief as a distribution (``train.particle_set_nll``, ``train.filter_loss(loss="nll")``).  From the native recursion they
     are views of the buffers it keeps anyway and their gradients return through ``mmf_pf_train_backward_sets``; the
     step-by-step paths stack them.  Off (the default): every launch and every bit as before.
+    ``regularisation`` (``None``: off, the default -- every launch and every bit as before; evaluation only, a training-mode
+    step with it set raises): the REGULARISED (post-resampling) particle filter of Musso, Oudjane & Le Gland.  A float ``> 0``
+    is the ``scale`` of the bandwidth, ``1.0`` the rule of thumb: on every step that resamples, each survivor of a
+    trajectory that resampled is drawn from the kernel density of the pre-resampling weighted set instead of being copied,
+    ``x <- x[a] + h L eps`` with ``h = scale (4 / ((d + 2) ess))^(1 / (d + 4))`` (Silverman's factor on the ESS) and ``L`` the
+    Cholesky factor of K1's weighted covariance plus ``diag(regularisation_floor^2)`` (``mmf_pf_regularise``,
+    ``include/mmf.h``); ``regularisation_floor`` (``0.0``; a float or ``d`` floats) gives a collapsed direction a jitter of
+    its own; ``regularisation_shrink = True`` shrinks the survivors towards the weighted mean first (Liu & West), which
+    leaves mean and covariance of the set unchanged.  The jitter's normals come from ``regularisation_noise``
+    (``NoiseSource(1)``: a stream of its own, so ``self.noise`` does not move with the switch; a ``CounterNoise`` on stream
+    ``CounterNoise.JITTER`` is generated inside the kernel by the native loop; one with the ``(seed, stream)`` of
+    ``self.noise`` is a ``ValueError`` -- it would correlate the jitter with the process noise).  ``last_regularisation``:
+    ``bandwidth (N,)`` after ``forward`` / ``(T, N)`` after ``forward_loop`` (0 where a trajectory kept its set, NaN where its
+    ESS was not finite), ``scale``, ``floor``, ``shrink``.  Ancestors, log-weights, estimates and belief records of a step are
+    K1's, unchanged; the native loop takes its loop of launches (the persistent form and the run table are not eligible:
+    jittered particles have no runs).  It composes with ``record_history`` / ``record_belief`` / ``resample_ess_threshold``
+    (a kept trajectory is left bit for bit) / ``soft_resample_alpha`` / ``estimation_method="argmax"`` / both resampling
+    modes / a changing particle count.  The history is what it was -- the propagated sets and K1's ancestors -- and all four
+    smoothers remain valid on it: the ancestry trace follows the ancestors, which still name the particle a survivor
+    descends from, and the pair-based ones (marginal, simulation, MAP) judge the model's transition density between the
+    recorded sets, not how a set was produced.
     Randomness comes from ``self.noise`` (``utils.NoiseSource``), never from global RNG state.
     """
 
@@ -182,6 +203,15 @@ class ParticleFilter(base.Filter):
         self.particle_log_weights: torch.Tensor = None
         self._spare_states = None
         self._dedup_words = None      # int32 run-table workspace of the native loop (engine.PF_DEDUP)
+        self._regularisation = None   # scale of regularised resampling (None: off) -> last_regularisation
+        if engine.PF_REGULARISATION is not None:  # env MMF_PF_REGULARISATION: the scale a new filter starts with (evaluation only)
+            if not 0.0 < engine.PF_REGULARISATION < math.inf:
+                raise ValueError(f"MMF_PF_REGULARISATION must be a finite float > 0, got {engine.PF_REGULARISATION!r}")
+            self._regularisation = engine.PF_REGULARISATION
+        self._regularisation_floor = 0.0
+        self.regularisation_shrink = False
+        self._regularisation_noise = NoiseSource(1)
+        self.last_regularisation = None
         self._initialized = False
 
     @property
@@ -192,6 +222,56 @@ class ParticleFilter(base.Filter):
     def resample_ess_threshold(self, value: Optional[float]) -> None:
         assert value is None or 0.0 < float(value) <= 1.0, "resample_ess_threshold must lie in (0, 1]"  # (a NaN fails too)
         self._resample_ess_threshold = None if value is None else float(value)
+
+    @property
+    def regularisation(self) -> Optional[float]:
+        return self._regularisation
+
+    @regularisation.setter
+    def regularisation(self, value: Optional[float]) -> None:
+        if value is not None:
+            if isinstance(value, bool) or not isinstance(value, numbers.Real) or not (0.0 < float(value) < math.inf):
+                raise ValueError(f"regularisation must be None or a finite float > 0 (the bandwidth's scale), got {value!r}")
+            if self.training:
+                raise RuntimeError("regularisation: the training (autograd) paths do not jitter; call .eval() first")
+        self._regularisation = None if value is None else float(value)
+
+    @property
+    def regularisation_floor(self):
+        return self._regularisation_floor
+
+    @regularisation_floor.setter
+    def regularisation_floor(self, value) -> None:
+        _abi.regularise_floor(value, self.state_dim)  # a float or d floats, finite and >= 0; otherwise a ValueError
+        self._regularisation_floor = float(value) if isinstance(value, numbers.Real) else tuple(float(v) for v in value)
+
+    @property
+    def regularisation_noise(self) -> NoiseSource:
+        return self._regularisation_noise
+
+    @regularisation_noise.setter
+    def regularisation_noise(self, value: NoiseSource) -> None:
+        self._check_regularisation_noise(value)
+        self._regularisation_noise = value
+
+    def _check_regularisation_noise(self, source=None) -> None:
+        """A counter source of the jitter must not be the process noise's: the same ``(seed, stream)`` draws the same normals
+        for particle ``m`` of step ``t`` twice."""
+        source = self._regularisation_noise if source is None else source
+        main = getattr(self, "noise", None)
+        if (isinstance(source, CounterNoise) and isinstance(main, CounterNoise)
+                and (source.seed, source.stream) == (main.seed, main.stream)):
+            raise ValueError(f"regularisation_noise shares (seed, stream) = ({source.seed}, {source.stream}) with the filter's "
+                             "noise: the jitter would repeat the process noise (use stream=CounterNoise.JITTER or another seed)")
+
+    def _regularisation_args(self):
+        """``None`` while the switch is off; otherwise ``(scale, floor as d floats, shrink)``, checked."""
+        if self._regularisation is None:
+            return None
+        if self.training:
+            raise RuntimeError("regularisation: the training (autograd) paths do not jitter; call .eval() first")
+        self._check_regularisation_noise()
+        return self._regularisation, _abi.regularise_floor(self._regularisation_floor, self.state_dim), bool(self.regularisation_shrink)
 
     @property
     def record_history(self) -> bool:
@@ -250,6 +330,8 @@ class ParticleFilter(base.Filter):
         nbytes = steps * batch * per_row + 8 * per_step + (64 << 20)
         if self.record_history:  # states, log-likelihoods, incoming log-weights, ancestors of every step
             nbytes += steps * batch * M * 4 * (d + 3)
+        if self._regularisation is not None:  # the jitter's (T, N, M, d) normals (a counter source on the jitter stream has none)
+            nbytes += steps * batch * M * 4 * d
         reserve_memory(dev, nbytes)
         return nbytes
 
@@ -304,6 +386,7 @@ class ParticleFilter(base.Filter):
 
     def _step(self, observations, controls, obs_ctx=None, ctrl_ctx=None) -> torch.Tensor:
         assert self._initialized, "Particle filter not initialized!"
+        reg = self._regularisation_args()  # (raises on a training-mode filter, before anything is drawn or launched)
         N, M, d = self.particle_states.shape
         do_resample = (not self.training) if self.resample is None else bool(self.resample)
         if not do_resample and self.num_particles != M:
@@ -312,6 +395,7 @@ class ParticleFilter(base.Filter):
             self._adapt_particle_count()
             N, M, d = self.particle_states.shape
 
+        self.last_regularisation = None
         with torch.no_grad():
             states = self._propagate(controls, ctrl_ctx, N, M, d)
             loglik = self._measure(states, observations, obs_ctx)
@@ -339,22 +423,35 @@ class ParticleFilter(base.Filter):
                 idx = (torch.empty((N, Mo), dtype=torch.int32, device=states.device)
                        if self.record_indices or keep_history else None)
                 lw_in = self.particle_log_weights
+                if reg is not None and rec is None:  # the jitter reads K1's covariance and ESS: the recording form, into scratch
+                    rk = dict(cov=torch.empty((N, d, d), dtype=torch.float32, device=states.device),
+                              ess=torch.empty((N,), dtype=torch.float32, device=states.device))
+                elif rec is not None:
+                    rk = dict(cov=rec.covariance, ess=rec.ess, log_evidence=rec.log_evidence)
+                else:
+                    rk = {}
                 if thr is not None and Mo == M:
                     took = torch.empty((N,), dtype=torch.int32, device=states.device)
-                    rk = {} if rec is None else dict(cov=rec.covariance, ess=rec.ess, log_evidence=rec.log_evidence)
                     k1 = lambda: _abi.pf_reweight_resample_adaptive(loglik, lw_in, states, u, estimate, out, logw_out, idx, mode,
                                                                     self.soft_resample_alpha, ess_threshold=thr,
                                                                     resampled=took, **rk)
-                elif rec is None:
+                elif not rk:
                     k1 = lambda: _abi.pf_reweight_resample(loglik, lw_in, states, u, estimate,
                                                            out, logw_out, idx, mode, self.soft_resample_alpha)
                 else:
                     k1 = lambda: _abi.pf_reweight_resample_belief(loglik, lw_in, states, u, estimate, out, logw_out, idx, mode,
-                                                                  self.soft_resample_alpha, cov=rec.covariance, ess=rec.ess,
-                                                                  log_evidence=rec.log_evidence)
+                                                                  self.soft_resample_alpha, **rk)
                 _timed("pf_reweight_resample", 0.0, N * M * 4.0 * (2 + d) + N * Mo * 4.0 * d, k1)
                 if thr is not None and Mo == M:
                     self.last_resampled = took.ne(0)
+                if reg is not None:  # `estimate` is still K1's weighted mean here (argmax replaces it below)
+                    scale, floor, shrink = reg
+                    h = torch.empty((N,), dtype=torch.float32, device=states.device)
+                    eps_j = self._regularisation_noise.gaussian((N, Mo, d), like=states)
+                    _timed("pf_regularise", 0.0, N * Mo * 4.0 * 3 * d, lambda: _abi.pf_regularise(
+                        out, rk["cov"], rk["ess"], scale=scale, floor=floor, shrink=shrink, mean=estimate,
+                        resampled=took if thr is not None and Mo == M else None, noise=eps_j, bandwidth=h))
+                    self.last_regularisation = base.belief_record(bandwidth=h, scale=scale, floor=tuple(floor), shrink=shrink)
                 # (the history keeps `states`: it must not come back as the next step's output buffer)
                 self._spare_states = None if keep_history else states
                 self.last_resample_indices = idx if self.record_indices else None
@@ -405,6 +502,8 @@ class ParticleFilter(base.Filter):
         flow through the reparameterised noise and the log-weights; resampling, when requested,
         runs through K1 on detached tensors (it stops gradients upstream as well)."""
         assert self._initialized, "Particle filter not initialized!"
+        if self._regularisation is not None:
+            raise RuntimeError("regularisation: the training (autograd) paths do not jitter; call .eval() first")
         N, M, d = self.particle_states.shape
         do_resample = (not self.training) if self.resample is None else bool(self.resample)
         if not do_resample and self.num_particles != M:
@@ -502,7 +601,11 @@ class ParticleFilter(base.Filter):
         mode = _MODES[self.resample_mode] if do_resample else 0
         like = self.particle_states
         u_shape = None if mode == 0 else ((N,) if mode == 1 else (N, M))
+        reg = self._regularisation_args()
+        self.last_regularisation = None
         eps, u = self.noise.draw_steps(T, (N, M, d), u_shape, like=like)
+        if isinstance(eps, CounterBlock) and eps.stream != 0:  # the dynamics kernel generates stream 0 only
+            eps = eps.tensor(like=like)
         dev = like.device
         states_a = like.contiguous()
         states_b = self._spare_states if (self._spare_states is not None and self._spare_states.shape == states_a.shape
@@ -563,9 +666,32 @@ class ParticleFilter(base.Filter):
             a.estimate_argmax, a.estimate_scratch = 1, P(est_scratch)
         # plain systematic resampling: the dynamics network once per distinct resampled ancestor (mmf_pf_forward_loop_dedup);
         # the C side takes the same decision from the same arguments and otherwise IS mmf_pf_forward_loop
+        # regularised resampling: one jitter launch after every K1 (mmf_pf_forward_loop_regularised), the loop of launches
+        regularise = None
+        if reg is not None and mode != 0:
+            scale, floor, shrink = reg
+            regularise = _abi.MmfPfLoopRegularise()
+            regularise.scale, regularise.shrink = scale, int(shrink)
+            for i, v in enumerate(floor):
+                regularise.floor[i] = v
+            eps_j, _ = self._regularisation_noise.draw_steps(T, (N, M, d), None, like=like)  # the steps' draws, in their order
+            if isinstance(eps_j, CounterBlock) and eps_j.stream != CounterNoise.JITTER:  # the kernel generates the jitter stream
+                eps_j = eps_j.tensor(like=like)
+            if isinstance(eps_j, CounterBlock):
+                regularise.noise_mode = 2
+                regularise.noise_seed, regularise.noise_step0, regularise.noise_traj0 = eps_j.seed, eps_j.step0, eps_j.traj0
+            else:
+                regularise.noise = P(eps_j)
+            h_steps = torch.empty((T, N), dtype=torch.float32, device=dev)
+            scratch = [None if self.record_belief else torch.empty((N, d, d), dtype=torch.float32, device=dev),
+                       None if self.record_belief else torch.empty((N,), dtype=torch.float32, device=dev)]
+            regularise.cov, regularise.ess = P(scratch[0]), P(scratch[1])
+            regularise.bandwidth_steps = P(h_steps)
+            keep += [eps_j, scratch]
+            self.last_regularisation = base.belief_record(bandwidth=h_steps, scale=scale, floor=tuple(floor), shrink=shrink)
         dedup = None
-        if dedup_eligible(T=T, M=M, d=d, mode=mode, soft_alpha=float(a.soft_alpha), adaptive=thr is not None,
-                          recording=self.record_belief):
+        if regularise is None and dedup_eligible(T=T, M=M, d=d, mode=mode, soft_alpha=float(a.soft_alpha), adaptive=thr is not None,
+                                                 recording=self.record_belief):
             words = dedup_workspace_words(N, M)
             if self._dedup_words is None or self._dedup_words.numel() != words or self._dedup_words.device != dev:
                 self._dedup_words = torch.empty(words, dtype=torch.int32, device=dev)
@@ -574,7 +700,7 @@ class ParticleFilter(base.Filter):
         # small problem: ONE launch for all T steps (csrc/pf_persistent.inc); same bits as the loop of launches
         # (ESS-triggered resampling does not change eligibility: the K1 role takes the adaptive branch)
         go = (engine.PF_PERSISTENT and mode == 1 and timer is None and not self.record_indices and history is None
-              and a.soft_alpha == 0.0 and not a.estimate_argmax and d in (2, 3)
+              and regularise is None and a.soft_alpha == 0.0 and not a.estimate_argmax and d in (2, 3)
               and dyn._net.n_res == 3 and all(net.n_res == 2 for net, _b, _l in nets)
               and _abi.pf_persistent_plan(N, M, len(nets)) > 0)
         events = None
@@ -586,7 +712,8 @@ class ParticleFilter(base.Filter):
         # the persistent launch needs ALL its workgroups resident; if it gives up (another process on this GPU) the belief
         # is restored and the loop re-run as launches, for this call and for the rest of the process (engine.run_persistent)
         loc = engine.run_persistent(a, lambda: _abi.pf_forward_loop(a, like, events, stride, ess_threshold=thr,
-                                                                    resampled_steps=took, dedup=dedup, history=history),
+                                                                    resampled_steps=took, dedup=dedup, history=history,
+                                                                    regularise=regularise),
                                     device=dev,
                                     n_sync_words=_abi.pf_persistent_sync_words(N, M, d, len(nets)) if go else 0,
                                     restore=(states_a, logw_a))
@@ -663,12 +790,14 @@ class ParticleFilter(base.Filter):
     def _loop_of_steps(self, T, step, N):
         """``forward_loop`` step by step: ``step(t, rows of step t in the T*N flattened arrays)``; the per-step records
         (``last_belief``, ``last_resampled``) are stacked along a leading ``T`` axis."""
-        out, beliefs, took, hist, sets = [], [], [], [], []
+        out, beliefs, took, hist, sets, jitter = [], [], [], [], [], []
         self._step_training_set = None
+        self.last_regularisation = None
         for t in range(T):
             out.append(step(t, slice(t * N, (t + 1) * N)))
             beliefs.append(self.last_belief)
             took.append(self.last_resampled)
+            jitter.append(self.last_regularisation)
             hist.append(self._step_history)
             sets.append(self._step_training_set)
         if sets and sets[0] is not None:  # (training steps with keep_training_sets: the sets before any resampling)
@@ -678,6 +807,11 @@ class ParticleFilter(base.Filter):
             self.last_belief = base.stack_belief_records(beliefs)
         if took and took[0] is not None:
             self.last_resampled = torch.stack(took, dim=0)
+        if jitter and all(j is not None for j in jitter):  # (every step of a loop resamples, or none does)
+            self.last_regularisation = base.belief_record(bandwidth=torch.stack([j.bandwidth for j in jitter]), scale=jitter[0].scale,
+                                                          floor=jitter[0].floor, shrink=jitter[0].shrink)
+        else:
+            self.last_regularisation = None
         self.last_history = None
         if self.record_history and T > 0:
             st, ll, lw, anc = zip(*hist)
@@ -1393,6 +1527,8 @@ class ParticleFilter(base.Filter):
         if use_autograd(self):
             if self.record_history:
                 raise RuntimeError("record_history: the training (autograd) paths keep no history; call .eval() first")
+            if self._regularisation is not None:
+                raise RuntimeError("regularisation: the training (autograd) paths do not jitter; call .eval() first")
             self.last_training_sets = None
             if not engine.use_hip_backward():
                 return self._loop_of_steps(T, lambda t, sl: self(

@@ -153,10 +153,20 @@ class StackedNoise(NoiseSource):
 class CounterBlock:
     """Marker returned by ``CounterNoise.draw_steps`` in place of a ``(T, N, M, d)`` tensor: the ``T``
     per-step noise blocks are counter steps ``step0 .. step0 + T - 1`` of ``seed`` -- generated inside the
-    dynamics kernel, never materialised."""
+    dynamics kernel, never materialised.  ``stream``: the Philox stream of the source (``CounterNoise.stream``); a kernel
+    generates the stream it is written for and every other block is materialised (``tensor``)."""
 
-    def __init__(self, seed: int, step0: int, traj0: int, T: int, shape):
-        self.seed, self.step0, self.traj0, self.T, self.shape = seed, step0, traj0, T, tuple(shape)
+    def __init__(self, seed: int, step0: int, traj0: int, T: int, shape, stream: int = 0):
+        self.seed, self.step0, self.traj0, self.T, self.shape, self.stream = seed, step0, traj0, T, tuple(shape), int(stream)
+
+    def tensor(self, *, like: torch.Tensor) -> torch.Tensor:
+        """The ``(T, *shape)`` block as a tensor (``mmf_philox_normals_stream``, one launch per step)."""
+        from . import _abi
+
+        out = torch.empty((self.T,) + self.shape, dtype=torch.float32, device=like.device)
+        for t in range(self.T):
+            _abi.philox_normals_stream(self.seed, self.stream, self.step0 + t, self.traj0, out[t])
+        return out
 
 
 class CounterNoise(NoiseSource):
@@ -166,11 +176,17 @@ class CounterNoise(NoiseSource):
     generates the Gaussians inside the dynamics kernel (no ``(T, N, M, d)`` tensor exists); step-by-step
     use materialises one block per call with ``mmf_philox_normals``; ``oracle.strict.philox_normals``
     reproduces every draw bit for bit on the CPU.  ``traj_offset``: index of this shard's first
-    trajectory, so a sharded run draws what the unsharded one would."""
+    trajectory, so a sharded run draws what the unsharded one would.  ``stream``: the Philox stream of the Gaussians -- 0,
+    the process noise the dynamics kernel generates, or ``CounterNoise.JITTER``, the stream of regularised resampling
+    (``ParticleFilter.regularisation_noise``), which ``mmf_pf_regularise`` generates; the uniforms have a stream of their own."""
 
-    def __init__(self, seed: int = 0, traj_offset: int = 0):
+    JITTER = 2  # MMF_PHILOX_STREAM_JITTER
+
+    def __init__(self, seed: int = 0, traj_offset: int = 0, stream: int = 0):
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.traj_offset = int(traj_offset)
+        self.stream = int(stream)
+        assert self.stream in (0, self.JITTER), "stream 0 (process noise) or CounterNoise.JITTER; 1 is the resampling uniforms'"
         self.step_gaussian = 0
         self.step_uniform = 0
 
@@ -179,7 +195,7 @@ class CounterNoise(NoiseSource):
 
         assert len(shape) == 3 and shape[2] <= 4, "counter noise draws (N, M, d <= 4) blocks"
         out = torch.empty(tuple(shape), dtype=torch.float32, device=like.device)
-        _abi.philox_normals(self.seed, self.step_gaussian, self.traj_offset, out)
+        _abi.philox_normals_stream(self.seed, self.stream, self.step_gaussian, self.traj_offset, out)
         self.step_gaussian += 1
         return out
 
@@ -195,7 +211,7 @@ class CounterNoise(NoiseSource):
     def draw_steps(self, T: int, gauss_shape, unif_shape, *, like: torch.Tensor):
         from . import _abi
 
-        block = CounterBlock(self.seed, self.step_gaussian, self.traj_offset, T, gauss_shape)
+        block = CounterBlock(self.seed, self.step_gaussian, self.traj_offset, T, gauss_shape, self.stream)
         self.step_gaussian += T
         u = None
         if unif_shape is not None:
