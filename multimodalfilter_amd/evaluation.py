@@ -10,9 +10,9 @@ from typing import Dict
 import numpy as np
 import torch
 
-from . import base, base_models, filters
+from . import base, base_models, filters, pf_summaries
 from .base_models import CrossmodalParticleFilterMeasurementModel
-from .filters import _DEFAULT_DRAWS
+from .pf_smoothing import _DEFAULT_DRAWS
 from .task_models import DOOR, PUSH
 
 START_TRUNCATION = 30
@@ -737,7 +737,7 @@ def map_axes(record):
     ``density[t, n, j, i]`` sits at ``(x[t, n, i], y[t, n, j])``."""
     if getattr(record, "density", None) is None or getattr(record, "center", None) is None or getattr(record, "step", None) is None:
         raise ValueError("map_axes: the record has no density, center and step; take it from belief_maps")
-    return filters.map_cell_centres(record.center, record.step, record.cells)
+    return pf_summaries.map_cell_centres(record.center, record.step, record.cells)
 
 
 def map_summary(record, true=None, start: int = START_TRUNCATION) -> Dict[str, object]:

@@ -14,12 +14,14 @@ Step order follows upstream torchfilter.
 """
 import math
 import numbers
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
 from . import _abi, base, engine
 from .engine import _timed, check_range, require_device, reserve_memory, use_autograd
+from .pf_smoothing import ParticleSmoothing
+from .pf_summaries import ParticleSummaries
 from .utils import CounterBlock, CounterNoise, NoiseSource, tree_index, tree_leading_shape, tree_map
 
 _MODES = {"none": 0, "systematic": 1, "multinomial": 2}
@@ -39,30 +41,22 @@ def dedup_eligible(*, T: int, M: int, d: int, mode: int, soft_alpha: float, adap
     return _abi.pf_dedup_plan(M, d, mode, soft_alpha, recording)
 
 
-class _DefaultDraws(int):
-    """The default of ``ParticleFilter.smooth(num_draws=)``: 64, told apart by identity from a 64 the caller passed, since
-    ``num_draws`` with a method that draws no paths is an error."""
+class _StepPolicy(NamedTuple):
+    """What one step does with a belief of ``M`` particles (``ParticleFilter._step_policy``)."""
+    resample: bool
+    mode: int                   # 1 systematic / 2 multinomial; 0 on a step that does not resample
+    M_out: int                  # the particle count the step leaves
+    soft: bool                  # soft_resample_alpha < 1 on a step that resamples
+    threshold: Optional[float]  # resample_ess_threshold on a resampling step that keeps the count, else None
 
 
-_DEFAULT_DRAWS = _DefaultDraws(64)
-
-_MAP_CHUNK_STATES = 1 << 22  # grid states of one measurement launch of belief_maps(likelihoods=True): 64 MiB of them at d = 4
-
-
-def map_cell_centres(center: torch.Tensor, step, cells):
-    """The cell centres of belief maps (``include/mmf.h``, ``mmf_pf_raster``): ``center (..., 2)``, ``step`` and ``cells =
-    (Gx, Gy)`` -> ``(u (..., Gx), v (..., Gy))`` float32, ``u_i = fmaf(float(i) - 0.5f (Gx - 1), step_x, c_x)``.  The product
-    is exact in float64 and the sum is rounded once more on the way to float32: the middle cell of an odd count is the centre
-    bit for bit."""
-    axes = []
-    for k, (s, g) in enumerate(zip(step, cells)):
-        i = torch.arange(g, dtype=torch.float64, device=center.device) - 0.5 * (g - 1)
-        axes.append((i * float(s) + center[..., k, None].to(torch.float64)).to(torch.float32))
-    return axes[0], axes[1]
+# the optional parts of one native loop (``ParticleFilter._loop_form``)
+_LoopForm = NamedTuple("_LoopForm", [(part, bool) for part in ("regularise", "dedup", "history", "per_step", "persistent")])
 
 
-class ParticleFilter(base.Filter):
-    """Bootstrap particle filter (T1).
+class ParticleFilter(base.Filter, ParticleSmoothing, ParticleSummaries):
+    """Bootstrap particle filter (T1).  The recursion and its switches are here; ``smooth()`` is
+    ``pf_smoothing.ParticleSmoothing``, the ``belief_*`` summaries of a recorded run are ``pf_summaries.ParticleSummaries``.
 
     ``resample=None`` resamples iff ``not self.training`` (upstream behaviour).
     ``soft_resample_alpha < 1`` (upstream option): ancestors are drawn from the
@@ -90,37 +84,10 @@ class ParticleFilter(base.Filter):
     smoother needs in ``last_history`` (``base.history_record``: the propagated sets, log-likelihoods, incoming log-weights
     and ancestors of every step, ``4 (d + 3)`` bytes per particle-step) -- the native loop writes it in place
     (``mmf_pf_forward_loop_history``: the loop of launches; the persistent launch is skipped, as with ``record_indices``),
-    the step-by-step loop stacks the same tensors.  ``smooth(lag)`` then returns the ancestry-smoothed means
-    ``E[x_t | y_1..min(t + lag, T)]`` (``mmf_pf_smooth``).  Every other output of the loop has the same bits either way.
-    ``record_transition_moments = True``: ``smooth(method="marginal")`` also leaves the two-slice moments of the transition
-    residual in ``last_smoothed`` (``residual_mean``, ``residual_second_moment``; ``mmf_pf_smooth_pair_moments``), what
-    ``evaluation.process_noise_m_step`` refits the process noise from.  A switch like the other ``record_*`` ones and not
-    an argument of ``smooth``, whose parameter list stays ``(lag, *, method, num_draws)``; another method with it set raises.
-    ``belief_quantiles(probs, of=, truth=)``: per-dimension weighted quantiles of the recorded sets (and the PIT of a true
-    state) -> ``last_quantiles``; the non-parametric counterpart of the covariance (``mmf_pf_quantiles``).
-    ``belief_scores(truth, of=, scale=)``: CRPS per dimension and the energy score of the recorded sets against the true
-    states -> ``last_scores``; strictly proper, so calibration and sharpness in one number (``mmf_pf_scores``).
-    ``belief_density(truth=, of=, bandwidth=, min_bandwidth=)``: the kernel density of the recorded sets -- the mode per step
-    (returned), the log density at every particle, the entropy and, with a truth, the logarithmic score -> ``last_density``
-    (``mmf_pf_density``).
-    ``belief_modes(of=, max_modes=, link_radius=, bandwidth=, min_bandwidth=)``: the modes of the recorded sets by quick shift
-    on that density -- how many, where, and the mass of each (returned: ``modes (T, N, K, d)``) -> ``last_modes``
-    (``mmf_pf_modes``).
-    ``belief_modalities()``: with a crossmodal measurement model, which sensor decided each step -- every enabled modality's
-    evidence-weighted share of the fused posterior (returned: ``responsibility (T, N, K)``), its own evidence, effective
-    sample size, mean, divergence from the fused posterior and overlap with the others -> ``last_modalities``
-    (``mmf_pf_modalities``); ``forward_loop`` keeps a reference to the observations and the ``enabled_models`` of the run
-    in the history for it.
-    ``belief_distance(other=, of=, other_of=, scale=)``: two-sample distances between the recorded sets of two filters, or of
-    one filter's filtered and smoothed sets -- 1-Wasserstein per dimension (returned), Cramer, Kolmogorov-Smirnov and the
-    energy distance -> ``last_distance`` (``mmf_pf_distance``).
-    ``belief_forecast(horizon, truth=, crps=)``: k-step-ahead forecasts from every recorded step -- the sets rolled out through
-    the dynamics, the predictive Gaussian mixture of each lead with its mean (returned), covariance, log score, PIT and CRPS in
-    closed form -> ``last_forecast`` (``mmf_pf_predictive``).
-    ``belief_maps(center, span, dims=, cells=, of=, bandwidth=, min_bandwidth=, likelihoods=, observations=)``: the recorded
-    beliefs as pictures -- the 2-D marginal of that density on a grid around ``center`` (returned: ``density (T, N, Gy, Gx)``)
-    for the predicted, filtered or smoothed sets and, with ``likelihoods``, every sensor's and the fused log-likelihood on the
-    same grid -> ``last_maps`` (``mmf_pf_raster``).
+    the step-by-step loop stacks the same tensors.  Every other output of the loop has the same bits either way.
+    ``smooth(lag, method=, num_draws=)`` and ``record_transition_moments``: ``pf_smoothing.ParticleSmoothing``.
+    ``belief_quantiles`` / ``_scores`` / ``_density`` / ``_modes`` / ``_modalities`` / ``_distance`` / ``_forecast`` / ``_maps``:
+    ``pf_summaries.ParticleSummaries``.
     ``keep_training_sets = True`` (training mode only; evaluation ignores it, ``record_history`` is its record there): a
     ``forward_loop`` leaves ``last_training_sets = {"states" (T, N, M, d), "log_weights" (T, N, M)}``, every step's weighted set
     -- the one its estimate is taken from, before any resampling -- as differentiable tensors, so that a loss can be put on the
@@ -184,16 +151,8 @@ class ParticleFilter(base.Filter):
         self.last_belief = None
         self.record_history = False   # forward_loop keeps the per-step sets / weights / ancestors -> last_history, smooth()
         self.last_history = None
-        self.last_smoothed = None
-        self.last_quantiles = None    # belief_quantiles(): per-dimension weighted quantiles (and the PIT) of the recorded sets
-        self.last_scores = None       # belief_scores(): CRPS, energy score and sharpness of the recorded sets against the truth
-        self.last_density = None      # belief_density(): mode, log density, entropy and log score of the recorded sets
-        self.last_modes = None        # belief_modes(): the modes of the recorded sets, their masses, means and members
-        self.last_modalities = None   # belief_modalities(): each modality's share, evidence and own posterior on the recorded sets
-        self.last_distance = None     # belief_distance(): two-sample distances between the recorded sets of two posteriors
-        self.last_forecast = None     # belief_forecast(): the k-step-ahead predictive mixtures of the recorded sets, scored
-        self.last_maps = None         # belief_maps(): the recorded beliefs (and the likelihoods) rasterised on a grid
-        self.record_transition_moments = False  # smooth(method="marginal") adds the two-slice residual moments to last_smoothed
+        self._init_smoothing()
+        self._init_summaries()
         self.keep_training_sets = False   # a train-mode forward_loop leaves every step's weighted set, differentiable -> last_training_sets
         self.last_training_sets = None
         self._step_training_set = None
@@ -360,6 +319,33 @@ class ParticleFilter(base.Filter):
         self._spare_states = None
 
     # ------------------------------------------------------------------ one step
+    def _step_policy(self, M: int) -> _StepPolicy:
+        """What a step does with a belief of ``M`` particles; the one place the switches are read for it.  A step that
+        changes the particle count resamples everybody: the threshold is dropped."""
+        resample = (not self.training) if self.resample is None else bool(self.resample)
+        M_out, thr = int(self.num_particles), self.resample_ess_threshold
+        return _StepPolicy(resample=resample, mode=_MODES[self.resample_mode] if resample else 0, M_out=M_out,
+                           soft=resample and self.soft_resample_alpha < 1.0,
+                           threshold=thr if resample and M_out == M else None)
+
+    def _adapt_unless_resampling(self, policy: _StepPolicy, M: int):
+        """A step that does not resample takes the belief to ``num_particles`` first -> the belief's ``(N, M, d)`` after that."""
+        if not policy.resample and policy.M_out != M:
+            self._adapt_particle_count()
+        return self.particle_states.shape
+
+    def _k1(self, *tensors_and_mode, threshold=None, resampled=None, **record):
+        """K1 (``loglik, logw_in, states, u, estimate, out, logw_out, idx, mode``) through the wrapper, and so the C symbol, of
+        this combination: a ``threshold`` (``_StepPolicy.threshold``) -> ``mmf_pf_reweight_resample_adaptive``; a ``record``
+        (``cov=``, ``ess=``, ``log_evidence=``: the belief record or the jitter's scratch) -> ``_belief``; neither -> the plain one."""
+        alpha = self.soft_resample_alpha if tensors_and_mode[-1] != 0 else 1.0
+        if threshold is not None:
+            _abi.pf_reweight_resample_adaptive(*tensors_and_mode, alpha, ess_threshold=threshold, resampled=resampled, **record)
+        elif record:
+            _abi.pf_reweight_resample_belief(*tensors_and_mode, alpha, **record)
+        else:
+            _abi.pf_reweight_resample(*tensors_and_mode, alpha)
+
     def _propagate(self, controls, ctrl_ctx, N, M, d):
         eps = self.noise.gaussian((N, M, d), like=self.particle_states)
         dyn = self.dynamics_model
@@ -387,13 +373,12 @@ class ParticleFilter(base.Filter):
     def _step(self, observations, controls, obs_ctx=None, ctrl_ctx=None) -> torch.Tensor:
         assert self._initialized, "Particle filter not initialized!"
         reg = self._regularisation_args()  # (raises on a training-mode filter, before anything is drawn or launched)
-        N, M, d = self.particle_states.shape
-        do_resample = (not self.training) if self.resample is None else bool(self.resample)
-        if not do_resample and self.num_particles != M:
-            if self.record_history:  # (the adapted set is a re-indexing of the belief that no ancestor array records)
-                raise RuntimeError("record_history: a step that adapts the particle count without resampling keeps no ancestry")
-            self._adapt_particle_count()
-            N, M, d = self.particle_states.shape
+        M = self.particle_states.shape[1]
+        policy = self._step_policy(M)
+        if self.record_history and not policy.resample and policy.M_out != M:
+            # (the adapted set is a re-indexing of the belief that no ancestor array records)
+            raise RuntimeError("record_history: a step that adapts the particle count without resampling keeps no ancestry")
+        N, M, d = self._adapt_unless_resampling(policy, M)
 
         self.last_regularisation = None
         with torch.no_grad():
@@ -407,13 +392,12 @@ class ParticleFilter(base.Filter):
 
             estimate = torch.empty((N, d), dtype=torch.float32, device=states.device)
             rec = self._new_belief_record((N,), d, states.device) if self.record_belief else None
-            thr = self.resample_ess_threshold
+            rk = {} if rec is None else dict(cov=rec.covariance, ess=rec.ess, log_evidence=rec.log_evidence)
             # the decisions of this step: nobody on a step that does not resample, everybody where the particle count changes
-            self.last_resampled = None if thr is None else torch.full(
-                (N,), bool(do_resample), dtype=torch.bool, device=states.device)
-            if do_resample:
-                Mo = self.num_particles
-                mode = _MODES[self.resample_mode]
+            self.last_resampled = None if self.resample_ess_threshold is None else torch.full(
+                (N,), policy.resample, dtype=torch.bool, device=states.device)
+            if policy.resample:
+                Mo, mode, thr = policy.M_out, policy.mode, policy.threshold
                 u = self.noise.uniform((N,) if mode == 1 else (N, Mo), like=states)
                 # two buffers ping-pong: dynamics wrote `states`; the old belief is free again
                 out = self.particle_states
@@ -426,23 +410,10 @@ class ParticleFilter(base.Filter):
                 if reg is not None and rec is None:  # the jitter reads K1's covariance and ESS: the recording form, into scratch
                     rk = dict(cov=torch.empty((N, d, d), dtype=torch.float32, device=states.device),
                               ess=torch.empty((N,), dtype=torch.float32, device=states.device))
-                elif rec is not None:
-                    rk = dict(cov=rec.covariance, ess=rec.ess, log_evidence=rec.log_evidence)
-                else:
-                    rk = {}
-                if thr is not None and Mo == M:
-                    took = torch.empty((N,), dtype=torch.int32, device=states.device)
-                    k1 = lambda: _abi.pf_reweight_resample_adaptive(loglik, lw_in, states, u, estimate, out, logw_out, idx, mode,
-                                                                    self.soft_resample_alpha, ess_threshold=thr,
-                                                                    resampled=took, **rk)
-                elif not rk:
-                    k1 = lambda: _abi.pf_reweight_resample(loglik, lw_in, states, u, estimate,
-                                                           out, logw_out, idx, mode, self.soft_resample_alpha)
-                else:
-                    k1 = lambda: _abi.pf_reweight_resample_belief(loglik, lw_in, states, u, estimate, out, logw_out, idx, mode,
-                                                                  self.soft_resample_alpha, **rk)
-                _timed("pf_reweight_resample", 0.0, N * M * 4.0 * (2 + d) + N * Mo * 4.0 * d, k1)
-                if thr is not None and Mo == M:
+                took = torch.empty((N,), dtype=torch.int32, device=states.device) if thr is not None else None
+                _timed("pf_reweight_resample", 0.0, N * M * 4.0 * (2 + d) + N * Mo * 4.0 * d, lambda: self._k1(
+                    loglik, lw_in, states, u, estimate, out, logw_out, idx, mode, threshold=thr, resampled=took, **rk))
+                if took is not None:
                     self.last_resampled = took.ne(0)
                 if reg is not None:  # `estimate` is still K1's weighted mean here (argmax replaces it below)
                     scale, floor, shrink = reg
@@ -450,7 +421,7 @@ class ParticleFilter(base.Filter):
                     eps_j = self._regularisation_noise.gaussian((N, Mo, d), like=states)
                     _timed("pf_regularise", 0.0, N * Mo * 4.0 * 3 * d, lambda: _abi.pf_regularise(
                         out, rk["cov"], rk["ess"], scale=scale, floor=floor, shrink=shrink, mean=estimate,
-                        resampled=took if thr is not None and Mo == M else None, noise=eps_j, bandwidth=h))
+                        resampled=took, noise=eps_j, bandwidth=h))
                     self.last_regularisation = base.belief_record(bandwidth=h, scale=scale, floor=tuple(floor), shrink=shrink)
                 # (the history keeps `states`: it must not come back as the next step's output buffer)
                 self._spare_states = None if keep_history else states
@@ -463,12 +434,7 @@ class ParticleFilter(base.Filter):
                     self._spare_states = None  # the old belief is a slice of the history: the next step gets a new buffer
                 elif states.data_ptr() != self.particle_states.data_ptr():
                     self._spare_states = self.particle_states  # the old belief is the next scratch
-                if rec is None:
-                    _abi.pf_reweight_resample(loglik, self.particle_log_weights, states, None, estimate,
-                                              None, logw_out, None, 0)
-                else:
-                    _abi.pf_reweight_resample_belief(loglik, self.particle_log_weights, states, None, estimate, None, logw_out,
-                                                     None, 0, cov=rec.covariance, ess=rec.ess, log_evidence=rec.log_evidence)
+                self._k1(loglik, self.particle_log_weights, states, None, estimate, None, logw_out, None, 0, **rk)
             self.last_belief = rec
             if self.estimation_method == "argmax":
                 # arg-max of the *pre-resampling* normalised weights
@@ -504,11 +470,9 @@ class ParticleFilter(base.Filter):
         assert self._initialized, "Particle filter not initialized!"
         if self._regularisation is not None:
             raise RuntimeError("regularisation: the training (autograd) paths do not jitter; call .eval() first")
-        N, M, d = self.particle_states.shape
-        do_resample = (not self.training) if self.resample is None else bool(self.resample)
-        if not do_resample and self.num_particles != M:
-            self._adapt_particle_count()
-            N, M, d = self.particle_states.shape
+        M = self.particle_states.shape[1]
+        policy = self._step_policy(M)
+        N, M, d = self._adapt_unless_resampling(policy, M)
         if engine.use_hip_backward() and hasattr(self.dynamics_model, "forward_particles"):
             # K6: the N*M-row network evaluates and differentiates in HIP
             pred = self.dynamics_model.forward_particles(states=self.particle_states, controls=controls,
@@ -539,29 +503,23 @@ class ParticleFilter(base.Filter):
                 estimate = states[torch.arange(N, device=states.device), torch.argmax(logw, dim=1)]
         self.particle_states, self.particle_log_weights = states, logw
         self._step_training_set = (states, logw) if self.keep_training_sets else None  # (before any resampling)
-        thr = self.resample_ess_threshold
-        self.last_resampled = None if thr is None else torch.full((N,), bool(do_resample), dtype=torch.bool, device=states.device)
-        if do_resample:
-            Mo = self.num_particles
-            mode = _MODES[self.resample_mode]
+        self.last_resampled = (None if self.resample_ess_threshold is None else
+                               torch.full((N,), policy.resample, dtype=torch.bool, device=states.device))
+        if policy.resample:
+            Mo, mode, soft, thr = policy.M_out, policy.mode, policy.soft, policy.threshold
             u = self.noise.uniform((N,) if mode == 1 else (N, Mo), like=states)
             out = torch.empty((N, Mo, d), dtype=torch.float32, device=states.device)
             logw_out = torch.empty((N, Mo), dtype=torch.float32, device=states.device)
             scratch = torch.empty((N, d), dtype=torch.float32, device=states.device)
-            soft = self.soft_resample_alpha < 1.0
             idx = torch.empty((N, Mo), dtype=torch.int32, device=states.device) if soft else None
-            adaptive = thr is not None and Mo == M
+            adaptive = thr is not None
             with torch.no_grad():
-                if adaptive:  # K1 supplies the ancestors and the decisions (the ESS of the normalised weights)
-                    took = torch.empty((N,), dtype=torch.int32, device=states.device)
-                    _abi.pf_reweight_resample_adaptive(torch.zeros_like(logw), logw.detach().contiguous(),
-                                                       states.detach().contiguous(), u, scratch, out, logw_out, idx, mode,
-                                                       self.soft_resample_alpha, ess_threshold=thr, resampled=took)
+                # (with a threshold K1 supplies the ancestors and the decisions: the ESS of the normalised weights)
+                took = torch.empty((N,), dtype=torch.int32, device=states.device) if adaptive else None
+                self._k1(torch.zeros_like(logw), logw.detach().contiguous(), states.detach().contiguous(), u, scratch, out,
+                         logw_out, idx, mode, threshold=thr, resampled=took)
+                if adaptive:
                     self.last_resampled = took.ne(0)
-                else:
-                    _abi.pf_reweight_resample(torch.zeros_like(logw), logw.detach().contiguous(),
-                                              states.detach().contiguous(), u, scratch, out, logw_out, idx, mode,
-                                              self.soft_resample_alpha)
             if soft:
                 # upstream's soft resampling is differentiable: the ancestors come from K1, the
                 # survivors' states and importance weights are re-derived with torch ops so that
@@ -581,28 +539,33 @@ class ParticleFilter(base.Filter):
             self.particle_states, self.particle_log_weights = out, logw_out
         return estimate
 
-    def _native_loop(self, obs_all, ctrl_all, T, N):
-        """All ``T`` steps through ``mmf_pf_forward_loop`` (one C call, no per-step Python) when
-        both models are fused networks; ``None`` -> the caller runs the step-by-step loop."""
-        dyn, meas = self.dynamics_model, self.measurement_model
-        if obs_all is None or ctrl_all is None or not hasattr(dyn, "_net") or not hasattr(meas, "fused_measurements"):
-            return None
-        if not self.use_native_loop:
-            return None
-        plan = meas.fused_measurements(obs_all)
-        if plan is None or T == 0:
-            return None
-        nets, stride = plan
-        Nb, M, d = self.particle_states.shape
-        do_resample = (not self.training) if self.resample is None else bool(self.resample)
-        if Nb != N or self.num_particles != M or len(nets) > _abi.LOOP_MAX_MEAS:
-            return None
-        assert self._initialized, "Particle filter not initialized!"
-        mode = _MODES[self.resample_mode] if do_resample else 0
-        like = self.particle_states
+    # ------------------------------------------------------------------ the native loop
+    def _loop_form(self, policy: _StepPolicy, reg, timer, T, N, M, d, nets) -> _LoopForm:
+        """Which optional parts this run has: what ``pf_enqueue_steps`` and the five ``mmf_pf_forward_loop*`` entries
+        (``csrc/pf_loop.hip``) decide from the same arguments.  ``regularise``: one jitter launch after every K1 of a loop
+        that resamples, and no run table (jittered particles have no runs).  ``dedup``: the run-table workspace, the dynamics
+        network once per distinct resampled ancestor (``dedup_eligible``).  ``history`` / ``per_step``: the per-step arrays of
+        ``record_history`` / ``record_indices``, which only the loop of launches writes.  ``persistent``: a small problem as
+        ONE launch for all T steps (``csrc/pf_persistent.inc``), same bits; a threshold or ``record_belief`` does not bar it."""
+        dyn = self.dynamics_model
+        history = bool(self.record_history)
+        regularise = reg is not None and policy.resample
+        alpha = _abi.as_float32(self.soft_resample_alpha) if policy.soft else 0.0  # (MmfPfLoopArgs.soft_alpha)
+        dedup = not regularise and dedup_eligible(T=T, M=M, d=d, mode=policy.mode, soft_alpha=alpha,
+                                                  adaptive=policy.threshold is not None, recording=self.record_belief)
+        persistent = bool(engine.PF_PERSISTENT and policy.mode == 1 and timer is None and not self.record_indices
+                          and not history and not regularise and alpha == 0.0 and self.estimation_method != "argmax"
+                          and d in (2, 3) and dyn._net.n_res == 3 and all(net.n_res == 2 for net, _b, _l in nets)
+                          and _abi.pf_persistent_plan(N, M, len(nets)) > 0)
+        return _LoopForm(regularise=regularise, dedup=dedup, history=history, per_step=bool(self.record_indices) or history,
+                         persistent=persistent)
+
+    def _loop_args(self, policy: _StepPolicy, T, N, nets, logw_stride, ctrl_all):
+        """The always-present fields of ``MmfPfLoopArgs``, the steps' noise (drawn here) among them -> ``(a, est, (states_a,
+        states_b, logw_a, logw_b), keep)``; ``keep`` holds what only the struct points to until the launches are enqueued."""
+        dyn, like, mode = self.dynamics_model, self.particle_states, policy.mode
+        _, M, d = like.shape
         u_shape = None if mode == 0 else ((N,) if mode == 1 else (N, M))
-        reg = self._regularisation_args()
-        self.last_regularisation = None
         eps, u = self.noise.draw_steps(T, (N, M, d), u_shape, like=like)
         if isinstance(eps, CounterBlock) and eps.stream != 0:  # the dynamics kernel generates stream 0 only
             eps = eps.tensor(like=like)
@@ -615,12 +578,12 @@ class ParticleFilter(base.Filter):
         loglik = torch.empty_like(logw_a)
         est = torch.empty((T, N, d), dtype=torch.float32, device=dev)
         tril = dyn.scale_tril().contiguous()
-        keep = [nets, eps, u, tril]  # keep every operand alive until the launches are enqueued
+        keep = [nets, eps, u, tril, loglik]
         P = _abi.vp
         a = _abi.MmfPfLoopArgs()
         a.T, a.N, a.M, a.d, a.n_meas, a.resample_mode = T, N, M, d, len(nets), mode
         a.precision = dyn._net.precision_code()
-        a.n_res_dyn, a.n_res_meas, a.logw_stride = dyn._net.n_res, nets[0][0].n_res, stride
+        a.n_res_dyn, a.n_res_meas, a.logw_stride = dyn._net.n_res, nets[0][0].n_res, logw_stride
         a.dyn_packed, a.dyn_bias = P(dyn._net.blob()), P(ctrl_all["bias"])
         for k, (net, bias, lw) in enumerate(nets):
             a.meas_packed[k], a.meas_bias[k], a.meas_logw[k] = P(net.blob()), P(bias), P(lw)
@@ -632,17 +595,31 @@ class ParticleFilter(base.Filter):
         a.scale_tril, a.uniforms = P(tril), P(u)
         a.states_a, a.states_b, a.logw_a, a.logw_b = P(states_a), P(states_b), P(logw_a), P(logw_b)
         a.loglik, a.estimates = P(loglik), P(est)
+        a.range_flag = P(engine.range_flag(dev), torch.int32)
+        if policy.soft:
+            a.soft_alpha = float(self.soft_resample_alpha)  # survivors carry importance weights (mmf_pf_reweight_resample_soft)
+        if self.estimation_method == "argmax":
+            est_scratch = torch.empty((N, d), dtype=torch.float32, device=dev)
+            keep.append(est_scratch)
+            a.estimate_argmax, a.estimate_scratch = 1, P(est_scratch)
+        return a, est, (states_a, states_b, logw_a, logw_b), keep
+
+    def _loop_records(self, a, keep, form: _LoopForm, policy: _StepPolicy, T, states_a, logw_a):
+        """The optional records, allocated and attached to ``a``: per-step log-likelihoods and ancestors, the history, the
+        belief records, the decisions of ESS-triggered resampling -> ``(hist, history, took)``, ``None`` where there is none."""
+        N, M, d = states_a.shape
+        dev, P = states_a.device, _abi.vp
         history = hist = None
-        if self.record_indices or self.record_history:
+        if form.per_step:
             ll_steps = torch.empty((T, N, M), dtype=torch.float32, device=dev)
-            idx_steps = torch.empty((T, N, M), dtype=torch.int32, device=dev) if mode != 0 else None
+            idx_steps = torch.empty((T, N, M), dtype=torch.int32, device=dev) if policy.mode != 0 else None
             a.loglik_steps, a.indices_steps = P(ll_steps), P(idx_steps, torch.int32)
             if self.record_indices:
                 self.last_log_weights_in = logw_a.clone()
                 self.last_log_likelihoods = ll_steps
-                if mode != 0:
+                if policy.mode != 0:
                     self.last_resample_indices = idx_steps
-            if self.record_history:  # the loop writes the propagated sets and the incoming log-weights in place
+            if form.history:  # the loop writes the propagated sets and the incoming log-weights in place
                 hist = base.history_record(states=torch.empty((T, N, M, d), dtype=torch.float32, device=dev),
                                            log_likelihoods=ll_steps,
                                            log_weights_in=torch.empty((T, N, M), dtype=torch.float32, device=dev),
@@ -655,84 +632,103 @@ class ParticleFilter(base.Filter):
         if self.record_belief:  # written by K1 in every form of the loop; does not change which form runs
             self.last_belief = rec = self._new_belief_record((T, N), d, dev)
             a.cov_steps, a.ess_steps, a.log_evidence_steps = P(rec.covariance), P(rec.ess), P(rec.log_evidence)
-        thr = self.resample_ess_threshold if mode != 0 else None  # (only steps that resample have a decision to take)
-        took = torch.empty((T, N), dtype=torch.int32, device=dev) if thr is not None else None
-        a.range_flag = P(engine.range_flag(dev), torch.int32)
-        if do_resample and self.soft_resample_alpha < 1.0:
-            a.soft_alpha = float(self.soft_resample_alpha)  # survivors carry importance weights (mmf_pf_reweight_resample_soft)
-        if self.estimation_method == "argmax":
-            est_scratch = torch.empty((N, d), dtype=torch.float32, device=dev)
-            keep.append(est_scratch)
-            a.estimate_argmax, a.estimate_scratch = 1, P(est_scratch)
-        # plain systematic resampling: the dynamics network once per distinct resampled ancestor (mmf_pf_forward_loop_dedup);
-        # the C side takes the same decision from the same arguments and otherwise IS mmf_pf_forward_loop
-        # regularised resampling: one jitter launch after every K1 (mmf_pf_forward_loop_regularised), the loop of launches
-        regularise = None
-        if reg is not None and mode != 0:
-            scale, floor, shrink = reg
-            regularise = _abi.MmfPfLoopRegularise()
-            regularise.scale, regularise.shrink = scale, int(shrink)
-            for i, v in enumerate(floor):
-                regularise.floor[i] = v
-            eps_j, _ = self._regularisation_noise.draw_steps(T, (N, M, d), None, like=like)  # the steps' draws, in their order
-            if isinstance(eps_j, CounterBlock) and eps_j.stream != CounterNoise.JITTER:  # the kernel generates the jitter stream
-                eps_j = eps_j.tensor(like=like)
-            if isinstance(eps_j, CounterBlock):
-                regularise.noise_mode = 2
-                regularise.noise_seed, regularise.noise_step0, regularise.noise_traj0 = eps_j.seed, eps_j.step0, eps_j.traj0
-            else:
-                regularise.noise = P(eps_j)
-            h_steps = torch.empty((T, N), dtype=torch.float32, device=dev)
-            scratch = [None if self.record_belief else torch.empty((N, d, d), dtype=torch.float32, device=dev),
-                       None if self.record_belief else torch.empty((N,), dtype=torch.float32, device=dev)]
-            regularise.cov, regularise.ess = P(scratch[0]), P(scratch[1])
-            regularise.bandwidth_steps = P(h_steps)
-            keep += [eps_j, scratch]
-            self.last_regularisation = base.belief_record(bandwidth=h_steps, scale=scale, floor=tuple(floor), shrink=shrink)
-        dedup = None
-        if regularise is None and dedup_eligible(T=T, M=M, d=d, mode=mode, soft_alpha=float(a.soft_alpha), adaptive=thr is not None,
-                                                 recording=self.record_belief):
-            words = dedup_workspace_words(N, M)
-            if self._dedup_words is None or self._dedup_words.numel() != words or self._dedup_words.device != dev:
-                self._dedup_words = torch.empty(words, dtype=torch.int32, device=dev)
-            dedup = _abi.pf_dedup_workspace(self._dedup_words, N, M)
-        timer = engine.kernel_timer()
-        # small problem: ONE launch for all T steps (csrc/pf_persistent.inc); same bits as the loop of launches
-        # (ESS-triggered resampling does not change eligibility: the K1 role takes the adaptive branch)
-        go = (engine.PF_PERSISTENT and mode == 1 and timer is None and not self.record_indices and history is None
-              and regularise is None and a.soft_alpha == 0.0 and not a.estimate_argmax and d in (2, 3)
-              and dyn._net.n_res == 3 and all(net.n_res == 2 for net, _b, _l in nets)
-              and _abi.pf_persistent_plan(N, M, len(nets)) > 0)
-        events = None
+        # (only steps that resample have a decision to take)
+        took = torch.empty((T, N), dtype=torch.int32, device=dev) if policy.threshold is not None else None
+        return hist, history, took
+
+    def _loop_regularise(self, reg, T, like, keep):
+        """``MmfPfLoopRegularise`` from ``reg`` (``_regularisation_args``): the jitter normals (drawn here, after the process
+        noise), K1's scratch where no belief record takes its covariance and ESS, the bandwidths -> ``last_regularisation``."""
+        scale, floor, shrink = reg
+        N, M, d = like.shape
+        dev, P = like.device, _abi.vp
+        regularise = _abi.MmfPfLoopRegularise()
+        regularise.scale, regularise.shrink = scale, int(shrink)
+        for i, v in enumerate(floor):
+            regularise.floor[i] = v
+        eps_j, _ = self._regularisation_noise.draw_steps(T, (N, M, d), None, like=like)  # the steps' draws, in their order
+        if isinstance(eps_j, CounterBlock) and eps_j.stream != CounterNoise.JITTER:  # the kernel generates the jitter stream
+            eps_j = eps_j.tensor(like=like)
+        if isinstance(eps_j, CounterBlock):
+            regularise.noise_mode = 2
+            regularise.noise_seed, regularise.noise_step0, regularise.noise_traj0 = eps_j.seed, eps_j.step0, eps_j.traj0
+        else:
+            regularise.noise = P(eps_j)
+        h_steps = torch.empty((T, N), dtype=torch.float32, device=dev)
+        scratch = [None if self.record_belief else torch.empty((N, d, d), dtype=torch.float32, device=dev),
+                   None if self.record_belief else torch.empty((N,), dtype=torch.float32, device=dev)]
+        regularise.cov, regularise.ess = P(scratch[0]), P(scratch[1])
+        regularise.bandwidth_steps = P(h_steps)
+        keep += [eps_j, scratch]
+        self.last_regularisation = base.belief_record(bandwidth=h_steps, scale=scale, floor=tuple(floor), shrink=shrink)
+        return regularise
+
+    def _loop_dedup(self, N, M, dev):
+        """The run-table workspace of the native loop (``engine.PF_DEDUP``), kept on the filter from one loop to the next."""
+        words = dedup_workspace_words(N, M)
+        if self._dedup_words is None or self._dedup_words.numel() != words or self._dedup_words.device != dev:
+            self._dedup_words = torch.empty(words, dtype=torch.int32, device=dev)
+        return _abi.pf_dedup_workspace(self._dedup_words, N, M)
+
+    def _loop_timing(self, timer, T, N, M, d, nets):
+        """The kernel timer's side: ``(events, stride, file)``, the events ``pf_loop.hip`` records around the launches of
+        every ``stride``-th step and ``file()``, which hands them to the timer with the kernels' names and work afterwards."""
+        if timer is None:
+            return None, 1, lambda: None
+        dyn = self.dynamics_model
         names = ["particle_net_dynamics"] + ["particle_net_measure"] * len(nets) + ["pf_reweight_resample"]
-        stride = 1
-        if timer is not None:
-            stride = max(1, int(timer.loop_stride))
-            events = timer.loop_events(2 * len(names) * len(range(stride // 2, T, stride)))  # pf_loop.hip samples t % stride == stride // 2
+        stride = max(1, int(timer.loop_stride))
+        events = timer.loop_events(2 * len(names) * len(range(stride // 2, T, stride)))  # pf_loop.hip samples t % stride == stride // 2
+        R = N * M
+        work = [(2.0 * R * engine.particle_net_macs(d, dyn._net.n_res, dyn._net.n_out), R * 4.0 * 3 * d)]
+        work += [(2.0 * R * engine.particle_net_macs(d, net.n_res, net.n_out), R * 4.0 * (d + 1 + (k > 0)))
+                 for k, (net, _, _) in enumerate(nets)]
+        work.append((0.0, R * 4.0 * (2 + 2 * d)))
+        return events, stride, lambda: timer.add_loop_records(names, work, events)
+
+    def _native_loop(self, obs_all, ctrl_all, T, N):
+        """All ``T`` steps through ``mmf_pf_forward_loop`` (one C call, no per-step Python) when
+        both models are fused networks; ``None`` -> the caller runs the step-by-step loop."""
+        dyn, meas = self.dynamics_model, self.measurement_model
+        if obs_all is None or ctrl_all is None or not hasattr(dyn, "_net") or not hasattr(meas, "fused_measurements"):
+            return None
+        if not self.use_native_loop:
+            return None
+        plan = meas.fused_measurements(obs_all)
+        if plan is None or T == 0:
+            return None
+        nets, logw_stride = plan
+        Nb, M, d = self.particle_states.shape
+        policy = self._step_policy(M)
+        if Nb != N or policy.M_out != M or len(nets) > _abi.LOOP_MAX_MEAS:
+            return None
+        assert self._initialized, "Particle filter not initialized!"
+        like = self.particle_states
+        reg = self._regularisation_args()  # (raises before anything is drawn or launched)
+        self.last_regularisation = None
+        timer = engine.kernel_timer()
+        form = self._loop_form(policy, reg, timer, T, N, M, d, nets)
+        a, est, (states_a, states_b, logw_a, logw_b), keep = self._loop_args(policy, T, N, nets, logw_stride, ctrl_all)
+        hist, history, took = self._loop_records(a, keep, form, policy, T, states_a, logw_a)
+        regularise = self._loop_regularise(reg, T, like, keep) if form.regularise else None
+        dedup = self._loop_dedup(N, M, like.device) if form.dedup else None
+        events, stride, file_timer_records = self._loop_timing(timer, T, N, M, d, nets)
         # the persistent launch needs ALL its workgroups resident; if it gives up (another process on this GPU) the belief
         # is restored and the loop re-run as launches, for this call and for the rest of the process (engine.run_persistent)
-        loc = engine.run_persistent(a, lambda: _abi.pf_forward_loop(a, like, events, stride, ess_threshold=thr,
+        loc = engine.run_persistent(a, lambda: _abi.pf_forward_loop(a, like, events, stride, ess_threshold=policy.threshold,
                                                                     resampled_steps=took, dedup=dedup, history=history,
                                                                     regularise=regularise),
-                                    device=dev,
-                                    n_sync_words=_abi.pf_persistent_sync_words(N, M, d, len(nets)) if go else 0,
+                                    device=like.device,
+                                    n_sync_words=_abi.pf_persistent_sync_words(N, M, d, len(nets)) if form.persistent else 0,
                                     restore=(states_a, logw_a))
-        if timer is not None:
-            R = N * M
-            dflops = 2.0 * R * engine.particle_net_macs(d, dyn._net.n_res, dyn._net.n_out)
-            work = [(dflops, R * 4.0 * 3 * d)]
-            mwork = [(2.0 * R * engine.particle_net_macs(d, net.n_res, net.n_out), R * 4.0 * (d + 1 + (k > 0)))
-                     for k, (net, _, _) in enumerate(nets)]
-            work += mwork
-            work.append((0.0, R * 4.0 * (2 + 2 * d)))
-            timer.add_loop_records(names, work, events)
+        file_timer_records()
         self.particle_states = states_b if loc & 1 else states_a
         self._spare_states = states_a if loc & 1 else states_b
         self.particle_log_weights = logw_b if loc & 2 else logw_a
         if self.resample_ess_threshold is None:
             self.last_resampled = None
         else:
-            self.last_resampled = took.ne(0) if took is not None else torch.zeros((T, N), dtype=torch.bool, device=dev)
+            self.last_resampled = took.ne(0) if took is not None else torch.zeros((T, N), dtype=torch.bool, device=like.device)
         if hist is not None:
             hist.resampled = self.last_resampled
         self.last_history = hist
@@ -744,14 +740,14 @@ class ParticleFilter(base.Filter):
         call, backward in one; ``None`` -> the caller's step-by-step autograd loop (user models, resampling
         while training, ``argmax`` estimates, a belief of another particle count)."""
         dyn, meas = self.dynamics_model, self.measurement_model
-        do_resample = (not self.training) if self.resample is None else bool(self.resample)
+        policy = self._step_policy(int(self.num_particles))  # (a belief of another count is turned away below)
         if (dyn_all is None or meas_all is None or not hasattr(dyn, "_net") or not hasattr(meas, "train_plan")
-                or do_resample or self.estimation_method != "weighted_average" or T == 0 or not self.use_native_loop
+                or policy.resample or self.estimation_method != "weighted_average" or T == 0 or not self.use_native_loop
                 or self.record_belief):  # (the training recursion keeps no per-step record: the step loop computes it)
             return None
         assert self._initialized, "Particle filter not initialized!"
         Nb, M, d = self.particle_states.shape
-        if Nb != N or self.num_particles != M:
+        if Nb != N or policy.M_out != M:
             return None
         plan = meas.train_plan(meas_all)
         if plan is None:
@@ -827,687 +823,6 @@ class ParticleFilter(base.Filter):
                 ancestors=None if anc[0] is None else torch.stack([pad(x, 0) for x in anc]), resampled=self.last_resampled)
         self._step_history = None
         return torch.stack(out, dim=0)
-
-    def smooth(self, lag: Optional[int] = None, *, method: str = "ancestry", num_draws: int = _DEFAULT_DRAWS) -> torch.Tensor:
-        """Ancestry (genealogy) smoothing of the last ``forward_loop`` run with ``record_history`` set: ``(T, N, d)`` means
-        of ``E[x_t | y_1..s(t)]``, ``s(t) = min(t + lag, T - 1)`` -- every particle of the endpoint ``s`` is traced back
-        through the ancestors to the particle of step ``t`` it descends from, and the moments of those are taken under the
-        endpoint's weights (``mmf_pf_smooth``, ``include/mmf.h``).  ``lag = None`` (or ``>= T - 1``): the full smoother;
-        ``lag = 0``: the filter's own weighted set.  Leaves ``last_smoothed``: ``covariance (T, N, d, d)``, ``unique (T, N)``
-        int32 -- the distinct particles of step ``t`` still alive on the endpoint's paths; where it drops to a handful the
-        genealogy has collapsed and a shorter lag trades bias for variance -- and ``lag``.  The smoothed estimate is the
-        weighted MEAN also where ``estimation_method == "argmax"`` makes the filter report another point.
-        ``method = "marginal"``: the forward-filter backward-smoothing recursion instead (``_smooth_marginal``); ``lag`` must
-        be ``None`` there.
-        ``method = "simulation"``: ``num_draws`` (default 64) whole trajectories drawn from the joint smoothing distribution
-        by backward simulation (``_smooth_simulation``); returns their mean, ``lag`` must be ``None``.  It draws
-        ``(T, N, num_draws)`` uniforms from ``self.noise`` and so ADVANCES the filter's noise stream.  ``num_draws`` belongs
-        to this method alone.
-        ``method = "map"``: the single most probable index path through the particle history instead (``_smooth_map``): a
-        ``(T, N, d)`` PATH of particles, not a mean; ``lag`` must be ``None``.  Its record has no ``covariance`` -- a path is
-        not a distribution, so ``evaluation.gaussian_nll`` / ``nees`` / ``coverage`` do not apply to it.
-        With ``self.record_transition_moments`` set (``method = "marginal"`` alone; any other method is a ``ValueError``):
-        also the two-slice moments of the transition residual ``X_{t+1} - f(X_t, u_{t+1})`` -- ``last_smoothed`` gains
-        ``residual_mean (T - 1, N, d)`` and ``residual_second_moment (T - 1, N, d, d)``, what
-        ``evaluation.process_noise_m_step`` refits the process noise from."""
-        if method not in ("ancestry", "marginal", "simulation", "map"):
-            raise ValueError(f"smooth: method must be 'ancestry', 'marginal', 'simulation' or 'map', got {method!r}")
-        if method != "ancestry" and lag is not None:
-            raise ValueError(f"smooth(method={method!r}) is the full smoother: a fixed-lag {method} smoother is not implemented")
-        if method != "simulation" and num_draws is not _DEFAULT_DRAWS:
-            raise ValueError(f"smooth: num_draws is the number of paths method='simulation' draws; method={method!r} takes none")
-        if isinstance(num_draws, bool) or not isinstance(num_draws, int) or num_draws < 1:
-            raise ValueError(f"smooth(method='simulation'): num_draws must be an int >= 1, got {num_draws!r}")
-        transition_moments = bool(getattr(self, "record_transition_moments", False))
-        if transition_moments and method != "marginal":
-            raise ValueError(f"smooth: record_transition_moments is set, and the two-slice moments are method='marginal''s; "
-                             f"method={method!r} has none (unset the switch, or smooth with method='marginal')")
-        h = self.last_history
-        assert h is not None, "smooth() needs a history: set record_history and run forward_loop (evaluation mode) first"
-        if method == "marginal":
-            return self._smooth_marginal(h, transition_moments)
-        if method == "simulation":
-            return self._smooth_simulation(h, num_draws)
-        if method == "map":
-            return self._smooth_map(h)
-        assert lag is None or int(lag) >= 0, "lag must be >= 0 (None: the full smoother)"
-        T, N, M, d = h.states.shape
-        dev = h.states.device
-        mean = torch.empty((T, N, d), dtype=torch.float32, device=dev)
-        cov = torch.empty((T, N, d, d), dtype=torch.float32, device=dev)
-        unique = torch.empty((T, N), dtype=torch.int32, device=dev)
-        _abi.pf_smooth(h.states, h.log_likelihoods, h.log_weights_in, None, h.ancestors,
-                       max(T - 1, 0) if lag is None else min(int(lag), max(T - 1, 0)), mean, cov, unique)
-        self.last_smoothed = base.belief_record(covariance=cov, unique=unique, lag=lag)
-        return mean
-
-    def _smooth_marginal(self, h, transition_moments: bool = False) -> torch.Tensor:
-        """Marginal smoothing (forward filter, backward smoother; ``mmf_pf_smooth_marginal``, ``include/mmf.h``): every
-        particle of step ``t`` is kept and re-weighted through the transition density ``N(X_{t+1}[j]; f(X_t[i], u_{t+1}),
-        L L^T)``, so no ancestors are read and every resampling mode is covered; ``O(M^2)`` pairs per trajectory and step.
-        The dynamics means of all ``(T - 1) N`` trajectories are evaluated in one go with the controls the history kept.
-        Leaves ``last_smoothed``: ``covariance (T, N, d, d)``, ``ess (T, N)`` = ``1 / sum W^2`` of the smoothed weights,
-        ``weights (T, N, M)``, ``lag = None``, ``method = "marginal"``.
-        ``transition_moments``: the same predictions, noise factor and ``logD`` go on to ``mmf_pf_smooth_pair_moments`` -- one
-        more pass over the pairs, all steps in one launch -- and the record gains ``residual_mean (T - 1, N, d)`` and
-        ``residual_second_moment (T - 1, N, d, d)``: mean and RAW second moment of ``X_{t+1}[j] - F_t[i]`` under the
-        two-slice smoothing distribution over the particle pairs ``(i, j)`` (leading size 0 for ``T == 1``)."""
-        T, N, M, d = h.states.shape
-        dev = h.states.device
-        extra = {}
-        with torch.no_grad():
-            pred, tril = self._smoothing_transition(h, "marginal")
-            weights = torch.empty((T, N, M), dtype=torch.float32, device=dev)
-            mean = torch.empty((T, N, d), dtype=torch.float32, device=dev)
-            cov = torch.empty((T, N, d, d), dtype=torch.float32, device=dev)
-            ess = torch.empty((T, N), dtype=torch.float32, device=dev)
-            logd = torch.empty((T - 1, N, M), dtype=torch.float32, device=dev) if transition_moments and T > 1 else None
-            _abi.pf_smooth_marginal(h.states, pred, h.log_likelihoods, h.log_weights_in, tril, weights, mean, cov, ess, logd)
-            if transition_moments:
-                extra["residual_mean"] = torch.empty((max(T - 1, 0), N, d), dtype=torch.float32, device=dev)
-                extra["residual_second_moment"] = torch.empty((max(T - 1, 0), N, d, d), dtype=torch.float32, device=dev)
-                _abi.pf_smooth_pair_moments(h.states, pred, h.log_likelihoods, h.log_weights_in, tril, weights, logd,
-                                            extra["residual_mean"], extra["residual_second_moment"])
-        self.last_smoothed = base.belief_record(covariance=cov, ess=ess, weights=weights, lag=None, method="marginal", **extra)
-        return mean
-
-    def _smoothing_transition(self, h, method: str):
-        """What the smoothers that evaluate the transition density read beside the history: the dynamics means
-        ``F_t = f(X_t, u_{t+1})`` of all ``(T - 1) N`` trajectories, evaluated in one go with the controls the history kept
-        (``(T - 1, N, M, d)`` float32, ``None`` for ``T < 2``), and the one process-noise ``scale_tril (d, d)`` on the
-        history's device.  State-dependent noise is refused."""
-        T, N, M, d = h.states.shape
-        dev = h.states.device
-        dyn = self.dynamics_model
-        pred = None
-        if T > 1:
-            ctrl = tree_map(h.controls, lambda c: c[1:])
-            pred, tril = self._transition_means(h.states[:-1], ctrl, f"smooth(method={method!r})")
-        elif hasattr(dyn, "scale_tril"):
-            tril = dyn.scale_tril()
-        else:  # (one step: the transition density is never evaluated)
-            tril = torch.eye(d, dtype=torch.float32, device=dev)
-        return pred, tril.detach().to(device=dev, dtype=torch.float32).contiguous()
-
-    def _transition_means(self, past, ctrl, who: str):
-        """``(f(X, u) (n, N, M, d) float32 contiguous, scale_tril)`` of ``n N`` particle sets ``past (n, N, M, d)`` under the
-        controls ``ctrl (n, N, ...)``, noise-free, in one call of the dynamics: K2 (``propagate_encoded``) for the built-in
-        models, ``dyn(...)`` on the ``n N M`` rows for a user model, whose state-dependent noise is the ``ValueError`` of
-        ``who``."""
-        n, N, M, d = past.shape
-        dyn = self.dynamics_model
-        if hasattr(dyn, "propagate_encoded"):
-            ctx = dyn.encode_controls(tree_map(ctrl, lambda c: c.reshape((n * N,) + tuple(c.shape[2:]))))
-            pred = dyn.propagate_encoded(past.reshape(n * N, M, d), ctx, None).reshape(n, N, M, d)
-            tril = dyn.scale_tril()
-        else:
-            R = n * N * M
-            rows = tree_map(ctrl, lambda c: c[:, :, None].expand((n, N, M) + tuple(c.shape[2:])).reshape(
-                (R,) + tuple(c.shape[2:])))
-            pred, trils = dyn(initial_states=past.reshape(R, d), controls=rows)
-            if not bool((trils == trils[:1]).all()):
-                raise ValueError(f"{who} needs one process-noise scale_tril for all particles and "
-                                 "steps; this dynamics model returns state-dependent noise")
-            pred, tril = pred.reshape(n, N, M, d), trils[0]
-        return pred.to(torch.float32).contiguous(), tril
-
-    def _smooth_simulation(self, h, num_draws: int) -> torch.Tensor:
-        """Backward-simulation smoothing (forward filtering, backward simulation; ``mmf_pf_smooth_simulate``,
-        ``include/mmf.h``): ``num_draws`` whole trajectories per filter trajectory from the joint smoothing distribution --
-        the last particle from the filter's weights, then backwards every particle of step ``t`` re-weighted by the
-        transition density into the particle the path chose at ``t + 1``.  ``(T - 1) N S M`` densities.  The ``(T, N, S)``
-        uniforms are ONE ``self.noise.uniform`` draw (a ``ReplayNoise`` can supply them); the filter's noise stream advances.
-        Returns the ``(T, N, d)`` mean of the draws and leaves ``last_smoothed``: ``covariance (T, N, d, d)`` of the draws,
-        ``trajectories (T, N, S, d)``, ``indices (T, N, S)`` int32 (``-1`` / NaN where a draw is dead), ``num_draws``,
-        ``lag = None``, ``method = "simulation"``."""
-        T, N, M, d = h.states.shape
-        dev = h.states.device
-        S = int(num_draws)
-        if isinstance(self.noise, CounterNoise):
-            raise ValueError("smooth(method='simulation') draws (T, N, num_draws) uniforms from the filter's noise source; "
-                             "CounterNoise draws one uniform per trajectory only: set filter.noise to a NoiseSource (or a "
-                             "ReplayNoise holding the uniforms) before smoothing")
-        with torch.no_grad():
-            pred, tril = self._smoothing_transition(h, "simulation")
-            u = self.noise.uniform((T, N, S), like=h.states)
-            indices = torch.empty((T, N, S), dtype=torch.int32, device=dev)
-            trajectories = torch.empty((T, N, S, d), dtype=torch.float32, device=dev)
-            mean = torch.empty((T, N, d), dtype=torch.float32, device=dev)
-            cov = torch.empty((T, N, d, d), dtype=torch.float32, device=dev)
-            _abi.pf_smooth_simulate(h.states, pred, h.log_likelihoods, h.log_weights_in, tril, u, indices, trajectories, mean, cov)
-        self.last_smoothed = base.belief_record(covariance=cov, trajectories=trajectories, indices=indices, num_draws=S,
-                                                lag=None, method="simulation")
-        return mean
-
-    def _smooth_map(self, h) -> torch.Tensor:
-        """MAP path smoothing (``mmf_pf_smooth_map``, ``include/mmf.h``; Godsill, Doucet & West 2001): the most probable
-        sequence of particles ``X_0[i_0], .., X_{T-1}[i_{T-1}]`` under ``p(x_0) prod_t p(y_t | x_t) N(x_t; f(x_{t-1}, u_t),
-        L L^T)`` restricted to the particle grid, by a max-plus (Viterbi) recursion over the ``(T - 1) N M^2`` particle pairs;
-        the incoming log-weights of step 0 stand in for ``log p(x_0)``.  No ancestors are read, so every resampling mode is
-        covered, and no noise is drawn: the filter's noise stream does not move.  Returns the ``(T, N, d)`` path -- a state
-        the filter did hold at every step, where a smoothed mean may lie between two modes -- and leaves ``last_smoothed``:
-        ``indices (T, N)`` int32 (``-1``, with a NaN path, where a step left no particle alive), ``log_posterior (N,)`` the
-        joint log-density of the path (``evaluation.path_log_density`` of ``indices``), ``lag = None``, ``method = "map"``.
-        There is NO ``covariance``: a path is not a distribution, and ``evaluation.gaussian_nll`` / ``nees`` / ``coverage``
-        do not apply."""
-        T, N, M, d = h.states.shape
-        dev = h.states.device
-        with torch.no_grad():
-            pred, tril = self._smoothing_transition(h, "map")
-            indices = torch.empty((T, N), dtype=torch.int32, device=dev)
-            path = torch.empty((T, N, d), dtype=torch.float32, device=dev)
-            log_posterior = torch.empty((N,), dtype=torch.float32, device=dev)
-            _abi.pf_smooth_map(h.states, pred, h.log_likelihoods, h.log_weights_in, tril, indices, path, log_posterior)
-        self.last_smoothed = base.belief_record(indices=indices, log_posterior=log_posterior, lag=None, method="map")
-        return path
-
-    def _recorded_sets(self, of: str, who: str):
-        """``(states (T, N, M, d), log_a, log_b)`` of the weighted particle sets that ``who`` (``belief_quantiles``,
-        ``belief_scores``, ``belief_density``) reads: ``of="filtered"`` the history's ``states`` under ``log_weights_in + log_likelihoods``;
-        ``of="smoothed"`` the history's states under ``log(weights)`` after the marginal smoother, the drawn ``trajectories``
-        with no weights after backward simulation.  Everything else is the ``ValueError`` of ``who``."""
-        h = self.last_history
-        if of == "filtered":
-            if h is None or getattr(h, "states", None) is None:
-                raise ValueError(f"{who} needs a history: set record_history and run forward_loop (evaluation mode) first")
-            return h.states, h.log_weights_in, h.log_likelihoods
-        s = self.last_smoothed
-        if s is None:
-            raise ValueError(f"{who}(of='smoothed') needs a smoothed record: call smooth(method='marginal') or "
-                             "smooth(method='simulation') first")
-        method = getattr(s, "method", "ancestry")
-        if method == "marginal":
-            if h is None or getattr(h, "states", None) is None or tuple(h.states.shape[:3]) != tuple(s.weights.shape):
-                raise ValueError(f"{who}(of='smoothed'): the marginal smoother's weights belong to a history that "
-                                 "is no longer there: run forward_loop with record_history and smooth again")
-            with torch.no_grad():
-                return h.states, torch.log(s.weights), None
-        if method == "simulation":
-            return s.trajectories, None, None
-        if method == "map":
-            raise ValueError(f"{who}(of='smoothed'): smooth(method='map') leaves one path, and a path is not a "
-                             "distribution: smooth with method='marginal' or 'simulation'")
-        raise ValueError(f"{who}(of='smoothed'): smooth(method={method!r}) keeps no per-step weights over the "
-                         "recorded sets: smooth with method='marginal' or 'simulation'")
-
-    def _summary_inputs(self, who: str, of: str, truth, serves: str, truth_is: str = "a", required: bool = False):
-        """What ``who`` (``belief_quantiles``, ``belief_scores``, ``belief_density``) opens with, in this order: the ``of``
-        check, the recorded sets, the particle cap (``serves``: how the error words it) and the shape of ``truth (T, N, d)``,
-        which may be ``None`` unless ``required``.  Returns ``(states, log_a, log_b, y)``, ``y`` the truth as a contiguous
-        float32 tensor on the sets' device, or ``None``."""
-        if of not in ("filtered", "smoothed"):
-            raise ValueError(f"{who}: of must be 'filtered' or 'smoothed', got {of!r}")
-        states, log_a, log_b = self._recorded_sets(of, who)
-        T, N, M, d = states.shape
-        if M > _abi.SUMMARY_MAX_M:
-            raise ValueError(f"{who}: {M} particles per set; {serves.format(_abi.SUMMARY_MAX_M)}")
-        if (required or truth is not None) and (not isinstance(truth, torch.Tensor) or tuple(truth.shape) != (T, N, d)):
-            raise ValueError(f"{who}: truth must be {truth_is} (T, N, d) = ({T}, {N}, {d}) tensor, got "
-                             f"{tuple(truth.shape) if isinstance(truth, torch.Tensor) else type(truth).__name__}")
-        with torch.no_grad():
-            y = None if truth is None else truth.detach().to(device=states.device, dtype=torch.float32).contiguous()
-        return states, log_a, log_b, y
-
-    @staticmethod
-    def _positive_floats(who: str, value, name: str, or_what: str, d: int):
-        """``value`` as a tuple of ``d`` positive finite floats, or the ``ValueError`` of ``who``: ``name`` must be
-        ``or_what`` or ``d`` positive finite floats."""
-        real = lambda v: not isinstance(v, bool) and isinstance(v, numbers.Real) and 0.0 < float(v) < math.inf
-        try:
-            vs = [] if isinstance(value, (str, bytes)) else [v for v in value]
-        except TypeError:
-            vs = []
-        if len(vs) != d or not all(real(v) for v in vs):
-            raise ValueError(f"{who}: {name} must be {or_what} or {d} positive finite floats, got {value!r}")
-        return tuple(float(v) for v in vs)
-
-    @classmethod
-    def _density_bandwidths(cls, who: str, bandwidth, min_bandwidth, d: int):
-        """``(rule, fixed, floor)`` of the ``bandwidth`` / ``min_bandwidth`` arguments of ``who`` (``belief_density``,
-        ``belief_modes``): ``"silverman"`` or ``"scott"`` with the floor (a float or ``d`` floats), or ``d`` positive finite
-        floats used as they are (``rule == "fixed"``); everything else is the ``ValueError`` of ``who``."""
-        floats = lambda value, name, or_what: cls._positive_floats(who, value, name, or_what, d)
-        if isinstance(bandwidth, str) and bandwidth in ("silverman", "scott"):
-            rule, fixed = str(bandwidth), None
-        else:
-            rule, fixed = "fixed", floats(bandwidth, "bandwidth", "'silverman', 'scott'")
-        if not isinstance(min_bandwidth, bool) and isinstance(min_bandwidth, numbers.Real):
-            min_bandwidth = (min_bandwidth,) * d
-        return rule, fixed, floats(min_bandwidth, "min_bandwidth", "a positive finite float")
-
-    def belief_scores(self, truth: torch.Tensor, *, of: str = "filtered", scale=None) -> torch.Tensor:
-        """Strictly proper scores of the recorded particle sets against the true states (``mmf_pf_scores``,
-        ``include/mmf.h``): the continuous ranked probability score per state dimension, ``crps (T, N, d)`` -- returned --
-        and its multivariate form, the energy score ``energy (T, N)``, both ``E|X - y| - 1/2 E|X - X'|`` over the weighted
-        set, the second expectation over all ``M^2`` pairs of a set in HIP.  They reward calibration and sharpness
-        together, are in the state's own units and reduce to the absolute / Euclidean error for a point mass
-        (``evaluation.gaussian_crps`` is the closed form of a Gaussian belief).  ``spread (T, N, d + 1)`` is the sharpness
-        term ``E|X - X'|`` alone, per dimension and, last, in the Euclidean norm.
-        ``truth (T, N, d)`` is required.  ``of`` means what it means for ``belief_quantiles``: ``"filtered"`` reads
-        ``last_history``, ``"smoothed"`` reads ``last_smoothed`` after ``smooth(method="marginal")`` or ``"simulation"``;
-        ``"ancestry"`` and ``"map"`` records are refused.  ``scale``: ``None`` or ``d`` positive finite floats dividing the
-        coordinates inside the Euclidean norm (``energy`` and ``spread[..., d]`` only), for states whose dimensions have
-        different units.  Leaves ``last_scores``: ``crps``, ``energy``, ``spread``, ``of``, ``scale`` (a tuple).  Draws no
-        noise and leaves ``last_history`` / ``last_smoothed`` / ``last_quantiles`` as they are.  A step without a live
-        particle gives NaN; a NaN component of the truth gives NaN in its ``crps`` and in ``energy``."""
-        states, log_a, log_b, y = self._summary_inputs("belief_scores", of, truth, "mmf_pf_scores serves at most {}", required=True)
-        T, N, M, d = states.shape
-        sc = (1.0,) * d if scale is None else self._positive_floats("belief_scores", scale, "scale", "None", d)
-        dev = states.device
-        with torch.no_grad():
-            crps = torch.empty((T, N, d), dtype=torch.float32, device=dev)
-            energy = torch.empty((T, N), dtype=torch.float32, device=dev)
-            spread = torch.empty((T, N, d + 1), dtype=torch.float32, device=dev)
-            _abi.pf_scores(states, log_a, log_b, y, crps, energy, spread, sc)
-        self.last_scores = base.belief_record(crps=crps, energy=energy, spread=spread, of=of, scale=sc)
-        return crps
-
-    def belief_forecast(self, horizon: int, truth: Optional[torch.Tensor] = None, *, crps: bool = True) -> torch.Tensor:
-        """k-step-ahead forecasts from every recorded step, scored in closed form (``mmf_pf_predictive``, ``include/mmf.h``):
-        where will the state be in ``h`` steps, and how sure is the filter?  With ``T`` recorded steps, origin ``t`` and lead
-        ``h`` in ``1 .. horizon``, the target is step ``t + h <= T - 1``.  The roll-out starts from the filtered sets --
-        ``last_history.states[t]`` under ``log_weights_in[t] + log_likelihoods[t]``, what ``of="filtered"`` means elsewhere --
-        and for ``k = 1 .. h`` propagates them noise-free under the recorded controls, ``F(k) = f(X(k-1), u_{t+k})``, one call
-        of the dynamics for all ``(T - k) N`` sets (K2 for the built-in models; a user model goes through ``dyn(...)`` as in the
-        smoothers, state-dependent noise refused), then adds the process noise, ``X(k) = F(k) + eps(k) L^T``, for the leads
-        that follow.  The weights never change.  The forecast at lead ``h`` is the mixture ``sum_i W_i N(x; F(h)_i, L L^T)``:
-        the noise of the last step is not drawn but integrated, so lead 1 draws nothing.
-        Returns ``mean (H, T, N, d)``: the forecast of ``x_{t+h}`` made at ``t`` sits at ``[h - 1, t]``, NaN where ``t + h >
-        T - 1`` (``horizon >= T`` is allowed: the leads beyond the data are NaN).  Leaves ``last_forecast``: ``mean``,
-        ``covariance (H, T, N, d, d)`` (the process noise of the last step included), ``horizon`` and, with ``crps`` (the
-        ``O(M^2)`` pair pass), ``spread (H, T, N, d)``; with ``truth (T, N, d)`` also ``error`` = ``mean - truth[t + h]``,
-        ``log_score (H, T, N)``, ``pit (H, T, N, d)`` and, with ``crps``, ``crps (H, T, N, d)`` -- strictly proper scores with
-        no bandwidth, where ``belief_density`` needs a kernel density estimate.
-        Noise: ``eps(k)`` is ONE ``self.noise.gaussian(((T - k) N, M, d))`` draw per ``k``, in the order ``k = 1 .. H - 1``
-        and only while a later lead has a target (``k < min(H, T - 1)``): ``horizon = 1`` leaves the noise stream where it
-        was, a ``ReplayNoise`` holding the blocks reproduces the forecasts, and ``CounterNoise`` serves.  Memory: two sets of
-        ``(T, N, M, d)`` at a time.  Evaluation mode only; ``last_history``, ``last_smoothed`` and the other records are left
-        as they are.  The Kalman filters have a ``belief_forecast`` of their own; the unscented and fused filters and the LSTM
-        baselines keep no history and are not reached."""
-        who = "belief_forecast"
-        if isinstance(horizon, bool) or not isinstance(horizon, numbers.Integral) or horizon < 1:
-            raise ValueError(f"{who}: horizon must be an int >= 1, got {horizon!r}")
-        if self.training:
-            raise RuntimeError(f"{who}: the training (autograd) paths keep no history; call .eval() first")
-        states, log_a, log_b, y = self._summary_inputs(who, "filtered", truth, "mmf_pf_predictive serves at most {}", "None or a")
-        T, N, M, d = states.shape
-        H, dev, controls = int(horizon), states.device, self.last_history.controls
-        blank = lambda *tail: torch.full((H, T, N) + tail, math.nan, dtype=torch.float32, device=dev)
-        with torch.no_grad():
-            out = {"mean": blank(d), "covariance": blank(d, d)}
-            if crps:
-                out["spread"] = blank(d)
-            if y is not None:
-                out.update(log_score=blank(), pit=blank(d))
-                if crps:
-                    out["crps"] = blank(d)
-            X = states
-            for k in range(1, min(H, T - 1) + 1):
-                n = T - k
-                F, tril = self._transition_means(X[:n], tree_map(controls, lambda c: c[k:T]), who)
-                tril = tril.detach().to(device=dev, dtype=torch.float32).contiguous()
-                _abi.pf_predictive(F, None if log_a is None else log_a[:n], None if log_b is None else log_b[:n], tril,
-                                   None if y is None else y[k:], **{name: buf[k - 1, :n] for name, buf in out.items()})
-                if k < min(H, T - 1):
-                    eps = self.noise.gaussian((n * N, M, d), like=F)
-                    X = F + (eps @ tril.t()).reshape(n, N, M, d)
-            if y is not None:
-                out["error"] = blank(d)
-                for k in range(1, min(H, T - 1) + 1):
-                    out["error"][k - 1, :T - k] = out["mean"][k - 1, :T - k] - y[k:]
-        self.last_forecast = base.belief_record(horizon=H, **out)
-        return out["mean"]
-
-    def belief_density(self, truth: Optional[torch.Tensor] = None, *, of: str = "filtered", bandwidth="silverman",
-                       min_bandwidth=1e-6) -> torch.Tensor:
-        """The kernel density estimate of the recorded particle sets (``mmf_pf_density``, ``include/mmf.h``): a Gaussian
-        product kernel on the weighted set, one bandwidth per state dimension, all ``M^2`` pairs of a set in HIP.  Returns
-        ``mode (T, N, d)``: per step the particle where the density is highest -- the point estimate of a multimodal belief,
-        a state the filter holds, where the mean lies between the modes.  Leaves ``last_density``: ``mode``, ``mode_index
-        (T, N)`` int32, ``log_density (T, N, M)`` (``-inf`` at a dead particle), ``entropy (T, N)`` -- the resubstitution
-        estimate ``-sum W log p(x)``, a sharpness figure that assumes no Gaussian --, ``bandwidth (T, N, d)``, ``of``,
-        ``rule`` and, with ``truth (T, N, d)``, ``log_score (T, N)``: the log density at the true state, the logarithmic
-        score (its negated mean is the NLL that ``evaluation.gaussian_nll`` is for a Gaussian belief).
-        ``bandwidth``: ``"silverman"`` or ``"scott"`` -- the rule of thumb per step on the weighted standard deviation of
-        each dimension and the effective sample size, not below ``min_bandwidth`` (a float or ``d`` floats) -- or ``d``
-        positive finite floats used as they are (``rule == "fixed"``).  ``of`` means what it means for ``belief_scores``.
-        Draws no noise and leaves ``last_history`` / ``last_smoothed`` / ``last_quantiles`` / ``last_scores`` as they are.  A
-        step without a live particle gives NaN and ``mode_index = -1``; a NaN component of the truth gives NaN in its
-        ``log_score`` only."""
-        states, log_a, log_b, y = self._summary_inputs("belief_density", of, truth, "mmf_pf_density serves at most {}", "None or a")
-        T, N, M, d = states.shape
-        rule, fixed, floor = self._density_bandwidths("belief_density", bandwidth, min_bandwidth, d)
-        dev = states.device
-        with torch.no_grad():
-            log_density = torch.empty((T, N, M), dtype=torch.float32, device=dev)
-            log_score = None if y is None else torch.empty((T, N), dtype=torch.float32, device=dev)
-            entropy = torch.empty((T, N), dtype=torch.float32, device=dev)
-            mode = torch.empty((T, N, d), dtype=torch.float32, device=dev)
-            mode_index = torch.empty((T, N), dtype=torch.int32, device=dev)
-            h = torch.empty((T, N, d), dtype=torch.float32, device=dev)
-            _abi.pf_density(states, log_a, log_b, y, rule=rule, bandwidth=fixed, min_bandwidth=floor, log_density=log_density,
-                            log_score=log_score, entropy=entropy, mode=mode, mode_index=mode_index, bandwidth_out=h)
-        extra = {} if log_score is None else {"log_score": log_score}
-        self.last_density = base.belief_record(mode=mode, mode_index=mode_index, log_density=log_density, entropy=entropy,
-                                               bandwidth=h, of=of, rule=rule, **extra)
-        return mode
-
-    def belief_modes(self, of: str = "filtered", *, max_modes: int = 4, link_radius: float = 3.0, bandwidth="silverman",
-                     min_bandwidth=1e-6) -> torch.Tensor:
-        """The modes of the recorded particle sets (``mmf_pf_modes``, ``include/mmf.h``): how many hypotheses the belief
-        holds per step, where each one is and how much probability it carries -- "the door is open with probability 0.7".
-        Quick shift on the kernel density of ``belief_density``: every particle links to its nearest neighbour of higher
-        density within ``link_radius`` bandwidths, the roots of that forest are the modes and a tree's weight is the mode's
-        mass; all ``M^2`` pairs of a set in HIP, deterministic, nothing iterated.  Returns ``modes (T, N, K, d)``, ``K =
-        max_modes`` (1 .. 8): per step the ``min(count, K)`` heaviest modes, heaviest first, each a particle of the set; ranks
-        beyond ``count`` are NaN.  Leaves ``last_modes``: ``modes``, ``index (T, N, K)`` int32 (``-1`` beyond ``count``),
-        ``mass (T, N, K)`` (0 beyond), ``mean (T, N, K, d)`` -- the weighted mean of each mode's members --, ``count (T, N)``
-        int32, ``labels`` and ``parent (T, N, M)`` int32 (every particle's mode and link, ``-1`` at a dead particle),
-        ``bandwidth (T, N, d)``, ``of``, ``rule``, ``link_radius``, ``max_modes``.
-        ``of``, ``bandwidth`` and ``min_bandwidth`` mean what they mean for ``belief_density``, whose log density and
-        bandwidths are computed here (``mmf_pf_density``) without touching ``last_density``.  Draws no noise and leaves every
-        other ``last_*`` record as it is.  A step without a live particle has ``count = 0``."""
-        states, log_a, log_b, _ = self._summary_inputs("belief_modes", of, None, "mmf_pf_modes serves at most {}")
-        T, N, M, d = states.shape
-        if isinstance(max_modes, bool) or not isinstance(max_modes, numbers.Integral) or not 1 <= max_modes <= _abi.MODES_MAX:
-            raise ValueError(f"belief_modes: max_modes must be an integer in 1 .. {_abi.MODES_MAX}, got {max_modes!r}")
-        if isinstance(link_radius, bool) or not isinstance(link_radius, numbers.Real) or not 0.0 < float(link_radius) < math.inf:
-            raise ValueError(f"belief_modes: link_radius must be a positive finite float (in bandwidths), got {link_radius!r}")
-        rule, fixed, floor = self._density_bandwidths("belief_modes", bandwidth, min_bandwidth, d)
-        K, tau = int(max_modes), float(link_radius)
-        dev = states.device
-        with torch.no_grad():
-            log_density = torch.empty((T, N, M), dtype=torch.float32, device=dev)
-            h = torch.empty((T, N, d), dtype=torch.float32, device=dev)
-            _abi.pf_density(states, log_a, log_b, None, rule=rule, bandwidth=fixed, min_bandwidth=floor, log_density=log_density,
-                            bandwidth_out=h)
-            ints = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
-            parent, labels, count, index = ints(T, N, M), ints(T, N, M), ints(T, N), ints(T, N, K)
-            modes = torch.empty((T, N, K, d), dtype=torch.float32, device=dev)
-            mass = torch.empty((T, N, K), dtype=torch.float32, device=dev)
-            mean = torch.empty((T, N, K, d), dtype=torch.float32, device=dev)
-            _abi.pf_modes(states, log_a, log_b, log_density, h, link_radius=tau, max_modes=K, parent=parent, labels=labels,
-                          count=count, index=index, modes=modes, mass=mass, mean=mean)
-        self.last_modes = base.belief_record(modes=modes, index=index, mass=mass, mean=mean, count=count, labels=labels,
-                                             parent=parent, bandwidth=h, of=of, rule=rule, link_radius=tau, max_modes=K)
-        return modes
-
-    @engine.checked_loop
-    def belief_maps(self, center: torch.Tensor, span, *, dims=(0, 1), cells=64, of: str = "filtered", bandwidth="silverman",
-                    min_bandwidth=1e-6, likelihoods: bool = False, observations=None) -> torch.Tensor:
-        """The recorded beliefs as pictures (``mmf_pf_raster``, ``include/mmf.h``): per step a grid of ``cells`` over the two
-        state dimensions ``dims`` around ``center``, holding the 2-D marginal of the kernel density of ``belief_density`` --
-        what shows a multimodal belief as two hills where every other summary gives numbers.  Returns ``density (T, N, Gy,
-        Gx)``, x fastest, rasterised in HIP with the exact-fp32 MFMA; no ``(M, G)`` factor array is formed.
-        ``center (T, N, d)``: where each step's window sits -- the truth, or the estimates ``forward_loop`` returned.
-        ``span``: two positive finite floats, the window's widths along ``dims[0]`` and ``dims[1]`` in the state's units; a
-        cell is ``span / cells`` wide.  ``cells``: an int or ``(Gx, Gy)``, each in 2 .. 128; with an odd count the middle
-        cell's centre is ``center`` bit for bit (``evaluation.map_axes`` gives every cell's).
-        ``of``: ``"filtered"`` and ``"smoothed"`` mean what they mean for ``belief_density``; ``"predicted"`` is the history's
-        ``states`` under ``log_weights_in`` alone, the belief before the step's measurement -- so three calls give prior,
-        likelihood and posterior on one grid.  ``bandwidth`` and ``min_bandwidth`` are ``belief_density``'s, and so are the
-        bandwidths (``mmf_pf_density`` asked for nothing else: it stops after the moments): the map is the marginal of the
-        density ``belief_density`` reports.
-        ``likelihoods=True`` adds ``log_likelihood (T, N, K + 1, Gy, Gx)``: the measurement networks evaluated on the grid
-        -- ``dims`` at the cell centres, every other dimension at ``center``'s value --, unnormalised log-likelihoods and no
-        densities.  Under a ``CrossmodalParticleFilterMeasurementModel`` the ``K`` enabled unimodal maps
-        (``modality_log_likelihoods``, every network in one launch) and, last, the fused ``logsumexp_k(beta_k + l_k)``, from
-        the observations and ``enabled_models`` the run left in the history, as ``belief_modalities`` reads them; under any
-        other measurement model one map of ``measurement_model(states=grid, observations=observations)``, ``observations (T,
-        N, ...)`` then being required (given, they are read under a crossmodal model too).  Rows go in chunks within K2's
-        limits, and the status word is cleared on entry and checked on the way out: a grid state that leaves the f16x3 range
-        raises here.
-        Leaves ``last_maps``: ``density``, ``mass (T, N)`` -- ``sum density step_x step_y``, the share of the belief inside
-        the window --, ``center (T, N, 2)``, ``step``, ``dims``, ``cells``, ``span`` (tuples), ``bandwidth (T, N, 2)``, ``of``,
-        ``rule`` and, with ``likelihoods``, ``log_likelihood``, ``modalities`` (the enabled models' indices; ``(0,)`` without
-        a fusion) and ``log_weights (T, N, K)`` (``beta``, or ``None``).  Draws no noise and leaves every other ``last_*``
-        record as it is.  Evaluation mode only.  A step without a live particle or with a NaN in ``center[..., dims]``
-        gives a NaN map."""
-        from .base_models import CrossmodalParticleFilterMeasurementModel  # (base_models imports this module)
-
-        who = "belief_maps"
-        if self.training:
-            raise RuntimeError(f"{who}: the training (autograd) paths keep no history; call .eval() first")
-        if of not in ("predicted", "filtered", "smoothed"):
-            raise ValueError(f"{who}: of must be 'predicted', 'filtered' or 'smoothed', got {of!r}")
-        states, log_a, log_b, _ = self._summary_inputs(who, "filtered" if of == "predicted" else of, None,
-                                                       "mmf_pf_raster serves at most {}")
-        if of == "predicted":
-            log_b = None  # (the belief before the step's measurement)
-        T, N, M, d = states.shape
-        whole = lambda v: not isinstance(v, bool) and isinstance(v, numbers.Integral)
-        real = lambda v: not isinstance(v, bool) and isinstance(v, numbers.Real) and 0.0 < float(v) < math.inf
-        pair = lambda v: list(v) if isinstance(v, (tuple, list)) else []
-        if d < 2:
-            raise ValueError(f"{who}: a map needs two state dimensions, the state has {d}")
-        if len(pair(dims)) != 2 or not all(whole(k) and 0 <= k < d for k in dims) or dims[0] == dims[1]:
-            raise ValueError(f"{who}: dims must be two distinct state dimensions in 0 .. {d - 1}, got {dims!r}")
-        grid = (cells, cells) if whole(cells) else tuple(pair(cells))
-        if len(grid) != 2 or not all(whole(g) and 2 <= g <= _abi.RASTER_MAX_CELLS for g in grid):
-            raise ValueError(f"{who}: cells must be an int or (Gx, Gy), each in 2 .. {_abi.RASTER_MAX_CELLS}, got {cells!r}")
-        dims, (Gx, Gy) = (int(dims[0]), int(dims[1])), (int(grid[0]), int(grid[1]))
-        step = ()
-        if len(pair(span)) == 2 and all(real(s) for s in span):
-            step = tuple(_abi.as_float32(float(s) / g) for s, g in zip(span, (Gx, Gy)))  # (the kernel's host floats)
-        if len(step) != 2 or not all(real(s) for s in step):
-            raise ValueError(f"{who}: span must be two positive finite floats (with span / cells positive and finite in "
-                             f"float32), got {span!r}")
-        if not isinstance(center, torch.Tensor) or tuple(center.shape) != (T, N, d):
-            raise ValueError(f"{who}: center must be a (T, N, d) = ({T}, {N}, {d}) tensor, got "
-                             f"{tuple(center.shape) if isinstance(center, torch.Tensor) else type(center).__name__}")
-        rule, fixed, floor = self._density_bandwidths(who, bandwidth, min_bandwidth, d)
-        meas, obs = self.measurement_model, None
-        if likelihoods:
-            crossmodal = isinstance(meas, CrossmodalParticleFilterMeasurementModel)
-            h = self.last_history
-            obs = observations
-            if crossmodal:
-                recorded = getattr(h, "enabled_models", None)
-                if obs is None:
-                    obs = getattr(h, "observations", None)
-                if recorded is not None and tuple(meas.enabled_models) != tuple(recorded):
-                    raise ValueError(f"{who}: enabled_models = {list(meas.enabled_models)} now, {list(recorded)} when the history "
-                                     "was recorded: the maps would be another fusion's; run forward_loop again")
-            if obs is None:
-                raise ValueError(f"{who}(likelihoods=True): no observations to evaluate the measurement model on: "
-                                 + ("the history holds none; " if crossmodal else f"{type(meas).__name__} leaves none in the history; ")
-                                 + "pass observations=, the (T, N, ...) observations of the run")
-            leaves = list(obs.values()) if isinstance(obs, dict) else [obs]
-            if not all(isinstance(x, torch.Tensor) and tuple(x.shape[:2]) == (T, N) for x in leaves):
-                raise ValueError(f"{who}: every tensor of observations must lead with (T, N) = ({T}, {N})")
-        dev = states.device
-        with torch.no_grad():
-            c = center.detach().to(device=dev, dtype=torch.float32).contiguous()
-            c2 = c[..., list(dims)].contiguous()
-            h_all = torch.empty((T, N, d), dtype=torch.float32, device=dev)
-            _abi.pf_density(states, log_a, log_b, None, rule=rule, bandwidth=fixed, min_bandwidth=floor, bandwidth_out=h_all)
-            h2 = h_all[..., list(dims)].contiguous()
-            density = torch.empty((T, N, Gy, Gx), dtype=torch.float32, device=dev)
-            _abi.pf_raster(states, log_a, log_b, c2, h2, density, dims=dims, step=step)
-            mass = (density.to(torch.float64).sum(dim=(-1, -2)) * (step[0] * step[1])).to(torch.float32)
-            extra = self._likelihood_maps(c, dims, step, (Gx, Gy), obs) if likelihoods else {}
-        self.last_maps = base.belief_record(density=density, mass=mass, center=c2.view(T, N, 2), step=step, dims=dims,
-                                            cells=(Gx, Gy), span=(float(span[0]), float(span[1])), bandwidth=h2.view(T, N, 2),
-                                            of=of, rule=rule, **extra)
-        return density
-
-    def _likelihood_maps(self, center, dims, step, cells, observations):
-        """The likelihood part of ``belief_maps``: ``center (T, N, d)`` float32 on the device and ``observations (T, N, ...)``
-        -> the ``log_likelihood (T, N, K + 1, Gy, Gx)``, ``modalities`` and ``log_weights`` of the record.  The grid states
-        hold ``dims`` at the cell centres and every other dimension at ``center``'s value; the rows go in chunks of at most
-        ``_MAP_CHUNK_STATES`` grid states, within what a K2 launch takes."""
-        from .base_models import CrossmodalParticleFilterMeasurementModel  # (base_models imports this module)
-
-        meas = self.measurement_model
-        crossmodal = isinstance(meas, CrossmodalParticleFilterMeasurementModel)
-        T, N, d = center.shape
-        (Gx, Gy), R = cells, T * N
-        u, v = map_cell_centres(center[..., list(dims)], step, cells)
-        flat = tree_map(observations, lambda x: x.reshape((R,) + tuple(x.shape[2:])))
-        rows = max(1, min(_abi.MEASURE_MAX_PARTICLES, _MAP_CHUNK_STATES) // (Gx * Gy))
-        maps, betas, enabled = [], [], (0,)
-        for r0 in range(0, R, rows):
-            r1 = min(R, r0 + rows)
-            g = center.reshape(R, d)[r0:r1, None, None, :].repeat(1, Gy, Gx, 1)
-            g[..., dims[0]] = u.view(R, Gx)[r0:r1, None, :]
-            g[..., dims[1]] = v.view(R, Gy)[r0:r1, :, None]
-            g = g.view(r1 - r0, Gy * Gx, d)
-            o = tree_map(flat, lambda x: x[r0:r1])
-            if crossmodal:
-                logliks, beta, enabled = meas.modality_log_likelihoods(g, meas.encode_observations(o))
-                ll = torch.stack(logliks, dim=1)                          # (rows, K, Gy Gx)
-                fused = torch.logsumexp(ll if beta is None else ll + beta[:, :, None], dim=1, keepdim=True)
-                maps.append(torch.cat([ll, fused], dim=1))
-                betas.append(beta)
-            else:
-                maps.append(meas(states=g, observations=o).to(torch.float32).reshape(r1 - r0, 1, Gy * Gx))
-        K1 = maps[0].shape[1]
-        return dict(log_likelihood=torch.cat(maps).view(T, N, K1, Gy, Gx), modalities=tuple(enabled),
-                    log_weights=torch.cat(betas).view(T, N, K1 - 1) if betas and betas[0] is not None else None)
-
-    @engine.checked_loop
-    def belief_modalities(self) -> torch.Tensor:
-        """Which sensor decided each step of the recorded run (``mmf_pf_modalities``, ``include/mmf.h``): the crossmodal
-        fusion ``logsumexp_k(beta_k + l_k)`` taken apart again.  Returns ``responsibility (T, N, K)``, ``K`` the enabled
-        modalities: the evidence-weighted share ``rho_k`` of modality ``k`` in the fused posterior, ``W = sum_k rho_k W^k``
-        with ``W^k`` the posterior that modality alone would have left on the same particles -- not ``beta``, which a
-        modality with likelihoods of larger scale overrules.  Leaves ``last_modalities``: ``responsibility``,
-        ``log_evidence (T, N, K + 1)`` -- how well each sensor alone explained the observation, the fused figure last --,
-        ``ess (T, N, K + 1)``, ``mean (T, N, K + 1, d)`` -- what each sensor alone would have estimated --, ``divergence
-        (T, N, K)``, ``KL(W^k || W)``, ``overlap (T, N, K, K)``, the Bhattacharyya coefficient between two sensors'
-        posteriors (do they agree?), ``log_likelihoods (K, T, N, M)``, the unimodal ``l_k`` themselves (likelihood maps),
-        ``log_weights (T, N, K)``, ``beta`` as the weight model gave it (``None`` without one), and ``modalities``, the
-        enabled models' indices.
-        Reads the filtered sets of ``last_history`` (``states`` under ``log_weights_in``; ``record_history`` and
-        ``forward_loop`` first) and the observations and ``enabled_models`` that run left there: the observations are encoded
-        again over the ``T N`` rows and every unimodal network is evaluated on the recorded particles in one launch
-        (``CrossmodalParticleFilterMeasurementModel.modality_log_likelihoods``).  There is no ``of=``: a smoothed weight is
-        not a prior times a likelihood.  Needs a crossmodal measurement model with the ``enabled_models`` of the run.  The
-        status word is cleared on entry and checked on the way out, as ``forward_loop`` does it, so an activation of the
-        encoders or of the networks that left the f16x3 range raises here (the weights may have changed since the run).  Draws no
-        noise and leaves every other ``last_*`` record as it is.  A modality without weight on any live particle has
-        responsibility 0 and NaN figures; a step without a live particle gives NaN."""
-        from .base_models import CrossmodalParticleFilterMeasurementModel  # (base_models imports this module)
-
-        who = "belief_modalities"
-        h = self.last_history
-        if h is None or getattr(h, "states", None) is None:
-            raise ValueError(f"{who} needs a history: set record_history and run forward_loop (evaluation mode) first")
-        meas = self.measurement_model
-        if not isinstance(meas, CrossmodalParticleFilterMeasurementModel):
-            raise ValueError(f"{who} attributes the fusion of a CrossmodalParticleFilterMeasurementModel; "
-                             f"{type(meas).__name__} fuses nothing")
-        recorded = getattr(h, "enabled_models", None)
-        if getattr(h, "observations", None) is None or recorded is None:
-            raise ValueError(f"{who}: the history holds no observations: it was not left by this filter's forward_loop")
-        if tuple(meas.enabled_models) != tuple(recorded):
-            raise ValueError(f"{who}: enabled_models = {list(meas.enabled_models)} now, {list(recorded)} when the history was "
-                             "recorded: the recorded log-likelihoods are another fusion's; run forward_loop again")
-        T, N, M, d = h.states.shape
-        if M > _abi.SUMMARY_MAX_M:
-            raise ValueError(f"{who}: {M} particles per set; mmf_pf_modalities serves at most {_abi.SUMMARY_MAX_M}")
-        R = T * N
-        dev = h.states.device
-        with torch.no_grad():
-            ctx = meas.encode_observations(tree_map(h.observations, lambda x: x.reshape((R,) + tuple(x.shape[2:]))))
-            logliks, beta, enabled = meas.modality_log_likelihoods(h.states.view(R, M, d), ctx)
-            K = len(logliks)
-            new = lambda *tail: torch.empty((T, N) + tail, dtype=torch.float32, device=dev)
-            out = dict(responsibility=new(K), log_evidence=new(K + 1), ess=new(K + 1), mean=new(K + 1, d), divergence=new(K),
-                       overlap=new(K, K))
-            _abi.pf_modalities(h.states, h.log_weights_in, [l.view(T, N, M) for l in logliks],
-                               None if beta is None else beta.view(T, N, K), **out)
-            log_likelihoods = torch.stack(logliks).view(K, T, N, M)
-        self.last_modalities = base.belief_record(log_likelihoods=log_likelihoods, log_weights=None if beta is None else beta.view(T, N, K),
-                                                  modalities=enabled, **out)
-        return out["responsibility"]
-
-    def belief_distance(self, other: Optional["ParticleFilter"] = None, *, of: str = "filtered", other_of: str = "filtered",
-                        scale=None) -> torch.Tensor:
-        """Two-sample distances between the recorded particle sets of this filter (set A, read with ``of``) and of ``other``
-        (set B, read with ``other_of``; ``None``: this filter), step by step (``mmf_pf_distance``, ``include/mmf.h``): how far
-        two posteriors are apart as distributions, where the means can only be subtracted.  ``f.belief_distance(of="filtered",
-        other_of="smoothed")`` after ``smooth(method="marginal")`` is how far the future moved the belief; two filters run on
-        the same data with 300 and 4096 particles, two arithmetic modes or two modality masks are compared the same way.
-        Returns ``wasserstein (T, N, d)``, the 1-Wasserstein (earth mover's) distance per state dimension in the state's own
-        units.  Leaves ``last_distance``: ``wasserstein``, ``cramer (T, N, d)`` -- the integral of the squared CDF difference,
-        which has no cancellation and resolves two posteriors that are almost the same --, ``ks (T, N, d)`` -- the
-        Kolmogorov-Smirnov statistic in [0, 1] --, all three on K1's integer fixed-point weights (identical sets give exactly
-        0, a step's bits do not depend on the batch); ``energy (T, N)``, the multivariate energy distance, and ``terms
-        (T, N, 3)``, ``E|X - Y|, E|X - X'|, E|Y - Y'|`` in the Euclidean norm, ``energy = sqrt(max(2 terms[0] - terms[1] -
-        terms[2], 0))`` -- a cancelling difference: below about 1e-3 of the sets' own spread read ``cramer``; ``of``,
-        ``other_of``, ``scale`` (a tuple) and ``particles = (M_a, M_b)``.
-        ``of`` and ``other_of`` mean what ``of`` means for ``belief_quantiles``.  The two sides must agree in ``(T, N, d)``;
-        their particle counts need not, and together may not exceed 16384.  ``scale``: as in ``belief_scores``, for the
-        norm of ``energy`` and ``terms`` only.  Draws no noise and leaves every other record of both filters as it is.  A
-        step at which either side has no live particle gives NaN."""
-        who = "belief_distance"
-        if other is None:
-            other = self
-        if not isinstance(other, ParticleFilter):
-            raise ValueError(f"{who}: other must be a ParticleFilter or None, got {type(other).__name__} (a Gaussian or a "
-                             "point estimate has no particle set)")
-        for name, value in (("of", of), ("other_of", other_of)):
-            if value not in ("filtered", "smoothed"):
-                raise ValueError(f"{who}: {name} must be 'filtered' or 'smoothed', got {value!r}")
-        xa, la_a, lb_a = self._recorded_sets(of, who)
-        xb, la_b, lb_b = other._recorded_sets(other_of, who)
-        T, N, Ma, d = xa.shape
-        Mb = xb.shape[2]
-        if (xb.shape[0], xb.shape[1], xb.shape[3]) != (T, N, d):
-            raise ValueError(f"{who}: the two sides must agree in (T, N, d): this filter's {of} sets have (T, N, d) = "
-                             f"({T}, {N}, {d}), the other's {other_of} sets ({xb.shape[0]}, {xb.shape[1]}, {xb.shape[3]})")
-        if xb.device != xa.device:
-            raise ValueError(f"{who}: the two sides are on different devices ({xa.device}, {xb.device})")
-        if Ma + Mb > _abi.DISTANCE_MAX_M:
-            raise ValueError(f"{who}: {Ma} + {Mb} particles per pair of sets; mmf_pf_distance sorts at most "
-                             f"{_abi.DISTANCE_MAX_M} of both sets together in LDS")
-        sc = (1.0,) * d if scale is None else self._positive_floats(who, scale, "scale", "None", d)
-        dev = xa.device
-        with torch.no_grad():
-            new = lambda *tail: torch.empty((T, N) + tail, dtype=torch.float32, device=dev)
-            out = dict(wasserstein=new(d), cramer=new(d), ks=new(d), energy=new(), terms=new(3))
-            _abi.pf_distance(xa, la_a, lb_a, xb, la_b, lb_b, scale=sc, **out)
-        self.last_distance = base.belief_record(of=of, other_of=other_of, scale=sc, particles=(Ma, Mb), **out)
-        return out["wasserstein"]
-
-    def belief_quantiles(self, probs, *, of: str = "filtered", truth: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Per-dimension weighted quantiles of the recorded particle sets (``mmf_pf_quantiles``, ``include/mmf.h``): the
-        non-parametric counterpart of ``record_belief``'s covariance -- median, credible intervals -- for a belief that need
-        not be Gaussian.  ``probs``: 1 .. 16 floats in ``[0, 1]``.  Returns ``(T, N, Q, d)``; every value is a particle's own
-        coordinate (the inverted weighted CDF on K1's integer fixed-point weights: the same bits whatever the batch).
-        ``of = "filtered"``: the pre-resampling weighted set of every step of ``last_history`` (``record_history`` and
-        ``forward_loop`` first) -- ``states`` under ``log_weights_in + log_likelihoods``, the set the estimate is taken from.
-        ``of = "smoothed"``: the sets of ``last_smoothed`` -- after ``smooth(method="marginal")`` the history's states under
-        the smoothed ``weights``; after ``smooth(method="simulation")`` the ``num_draws`` drawn ``trajectories``, equally
-        weighted.  ``"ancestry"`` keeps no per-step weights and ``"map"`` is a path, not a distribution: both are refused.
-        ``truth (T, N, d)``: also the probability integral transform of the true state, ``pit (T, N, d)`` -- the weighted share
-        of the particles at or below it, per dimension; under a calibrated filter it is uniform on ``[0, 1]``
-        (``evaluation.pit_histogram``).  Leaves ``last_quantiles``: ``probs`` (a tuple), ``quantiles``, ``of`` and, with a
-        truth, ``pit``.  Draws no noise and leaves ``last_history`` / ``last_smoothed`` as they are.  A step without a live
-        particle gives NaN."""
-        if of not in ("filtered", "smoothed"):  # (here as well as in _summary_inputs: it goes before the probs)
-            raise ValueError(f"belief_quantiles: of must be 'filtered' or 'smoothed', got {of!r}")
-        try:
-            ps = [p for p in probs]
-        except TypeError:
-            raise ValueError(f"belief_quantiles: probs must be a sequence of floats in [0, 1], got {probs!r}") from None
-        if not 1 <= len(ps) <= _abi.QUANTILES_MAX:
-            raise ValueError(f"belief_quantiles: probs must hold 1 .. {_abi.QUANTILES_MAX} probabilities, got {len(ps)}")
-        for p in ps:
-            if isinstance(p, bool) or not isinstance(p, numbers.Real) or not 0.0 <= float(p) <= 1.0:  # (a NaN fails the range)
-                raise ValueError(f"belief_quantiles: probs must be floats in [0, 1], got {p!r}")
-        ps = tuple(float(p) for p in ps)
-        states, log_a, log_b, query = self._summary_inputs("belief_quantiles", of, truth, "mmf_pf_quantiles sorts at most {} in LDS")
-        T, N, M, d = states.shape
-        dev = states.device
-        with torch.no_grad():
-            quantiles = torch.empty((T, N, len(ps), d), dtype=torch.float32, device=dev)
-            pit = None if query is None else torch.empty((T, N, d), dtype=torch.float32, device=dev)
-            _abi.pf_quantiles(states, log_a, log_b, ps, quantiles, query, pit)
-        extra = {} if pit is None else {"pit": pit}
-        self.last_quantiles = base.belief_record(probs=ps, quantiles=quantiles, of=of, **extra)
-        return quantiles
 
     @engine.checked_step
     def forward(self, *, observations, controls) -> torch.Tensor:

@@ -31,7 +31,7 @@ DIMS = (0, 1)
 def torch_maps(states, log_a, log_b, center2, h2, step, cells, dims, dtype=torch.float32):
     """The definition of ``include/mmf.h`` in torch ops, fp32 unless told otherwise: ``density (T, N, Gy, Gx)``.  Dead
     particles (weight 0, NaN rows) are zeroed before any difference is taken."""
-    from multimodalfilter_amd.filters import map_cell_centres
+    from multimodalfilter_amd.pf_summaries import map_cell_centres
 
     T, N, M, d = states.shape
     R = T * N

@@ -212,3 +212,56 @@ def test_capturing_is_seen_by_the_capturing_thread_only():
         assert done.wait(10)
     t.join()
     assert seen == {"own": True, "other": False} and not engine.is_capturing()
+
+
+# What a ParticleFilter step does, as ``_step``, ``_step_autograd``, ``_native_loop`` and ``_native_train_loop`` each spelled it
+# before ``_step_policy`` was the one place: (training, ``resample`` switch) -> does the step resample
+_STEP_RESAMPLES = {(False, None): True, (True, None): False,   # None: resample iff not training
+                   (False, True): True, (True, True): True, (False, False): False, (True, False): False}
+
+
+@pytest.mark.parametrize("training,switch", list(_STEP_RESAMPLES))
+def test_step_policy_is_what_the_four_step_paths_decided(training, switch):
+    """``ParticleFilter._step_policy(M)`` over ``training`` x ``resample`` x both modes x ``num_particles`` equal to and
+    different from the belief's ``M`` x threshold set / unset x alpha 1 / 0.5, against the record written out by hand."""
+    import itertools
+
+    import _smooth_cases as sc
+
+    dyn, meas = sc.linear_gaussian_models(3, 0.05, 0.3, torch.device("cpu"))
+    M = 6
+    resamples = _STEP_RESAMPLES[(training, switch)]
+    for (name, code), count, thr, alpha in itertools.product((("systematic", 1), ("multinomial", 2)), (6, 9), (None, 0.5),
+                                                             (1.0, 0.5)):
+        f = mmf.filters.ParticleFilter(dynamics_model=dyn, measurement_model=meas, num_particles=count, resample=switch,
+                                       resample_mode=name, soft_resample_alpha=alpha, resample_ess_threshold=thr)
+        f.train(training)
+        got = f._step_policy(M)
+        case = (training, switch, name, count, thr, alpha)
+        assert isinstance(got, tuple) and got._fields == ("resample", "mode", "M_out", "soft", "threshold"), case
+        assert got.resample is resamples, case
+        assert got.M_out == count, case
+        if not resamples:  # a step that does not resample: mode 0 whatever resample_mode says, nothing soft, no threshold
+            assert (got.mode, got.soft, got.threshold) == (0, False, None), case
+            continue
+        assert got.mode == code, case
+        assert got.soft is (alpha == 0.5), case
+        # a step that changes the particle count resamples everybody: the threshold is dropped
+        assert got.threshold == (0.5 if thr is not None and count == M else None), case
+    with pytest.raises(AttributeError):  # the record is immutable
+        got.mode = 3
+
+
+def test_step_policy_drops_the_threshold_with_the_count_and_the_mode_without_resampling():
+    """The two facts the code after the policy depends on, one example each."""
+    import _smooth_cases as sc
+
+    dyn, meas = sc.linear_gaussian_models(3, 0.05, 0.3, torch.device("cpu"))
+    f = mmf.filters.ParticleFilter(dynamics_model=dyn, measurement_model=meas, num_particles=9, resample_mode="multinomial",
+                                   resample_ess_threshold=0.5).eval()
+    assert f._step_policy(9) == (True, 2, 9, False, 0.5)
+    assert f._step_policy(6) == (True, 2, 9, False, None)      # 6 -> 9 particles: K1 resamples every trajectory
+    f.train()
+    assert f._step_policy(9) == (False, 0, 9, False, None)     # no resampling: mode 0, and no decision to take
+    f.resample = True
+    assert f._step_policy(9) == (True, 2, 9, False, 0.5)
