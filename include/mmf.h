@@ -1699,6 +1699,66 @@ int mmf_pf_set_nll(const MmfPfSetNllArgs* args /* host */, void* stream);
 int mmf_pf_train_backward_sets(const MmfPfTrainArgs* args /* host */, const float* g_states_steps /* (T, N, M, d) or null */,
                                const float* g_logw_steps /* (T, N, M) or null */, void* stream);
 
+/* ---------------------------------------------------------------- Training on the particle set's scores: the gradients of CRPS and the energy score
+ * The training loss of crossmodal/train_helpers.py:124-162 (torchfilter.train.train_filter) is the mean-squared error of the
+ * estimates; the section above adds the mixture log score, which needs a kernel bandwidth that changes what is optimised and
+ * whose gradient saturates for a truth several sigma from every particle.  CRPS and the energy score ("Particle-posterior
+ * scores" above; Gneiting & Raftery 2007) are strictly proper with no bandwidth at all, in the state's own units, and their
+ * gradient is bounded (|d / d x_m| <= W_m); they are the second loss on the weighted sets that mmf_pf_train_backward_sets
+ * carries into the native recursion.  Purely additive to ABI 42: a struct and two symbols of their own.
+ * The forward pass is NOT new: it is mmf_pf_scores as it stands, so a filter is trained on the bits it is evaluated with.
+ * mmf_pf_scores_backward is its reverse.  Per row r of M particles x_m = states[r, m, :] with the truth y = truth[r, :],
+ * the forward's own weights (a_m = log_a + log_b, w_m = live weight of a_m - max a, W = w / sum w) and s = scale, for the
+ * loss L = sum_k g_k crps[k] + g_E energy with g_k = g_crps[r, k], g_E = g_energy[r]:
+ *   t_mk = |x_mk - y_k|          s_mk = sum_l W_l |x_mk - x_lk|
+ *   t_mE = |(x_m - y) / s|_2     s_mE = sum_l W_l |(x_m - x_l) / s|_2
+ *   c_m  = sum_k g_k (t_mk - s_mk) + g_E (t_mE - s_mE)
+ *   g_logw[r, m]      = W_m (c_m - sum_l W_l c_l)                              dL / da_m (the same for log_a and log_b)
+ *   g_states[r, m, k] = W_m [ g_k (sgn(x_mk - y_k) - sum_l W_l sgn(x_mk - x_lk))
+ *                           + g_E (u_k(x_m - y) - sum_l W_l u_k(x_m - x_l)) ]
+ *   u_k(e) = e_k / (s_k^2 |e / s|_2), and 0 where e = 0;   sgn(0) = 0
+ * (the 1/2 of the definition and the symmetry of the pair sum cancel; coinciding particles contribute 0).
+ *   - a particle with w_m = 0 is dead: its state row is not read into any sum and both its gradients are WRITTEN as +0;
+ *   - a row without a live particle has all gradients 0;
+ *   - a term whose forward value is NaN -- crps[k] where y_k is NaN, energy where any y_k is NaN -- contributes nothing,
+ *     whatever its upstream gradient holds (NaN included); the row's other terms contribute as defined;
+ *   - the truth gets no gradient, and neither does the scale: it is a choice of units, not a parameter;
+ *   - a null g_crps or g_energy leaves that score's terms out; the upstream gradients multiply inside c_m and the bracket,
+ *     so scaling all of a row's upstream gradients by one power of two scales its outputs exactly.
+ * Determinism: every sum is taken in a fixed order and there are no floating-point atomics -- two calls give the same bits,
+ * and a row's bits depend on neither R, nor its place in the batch, nor which of the two outputs is asked for.
+ * Kernel plan: the pair plan of mmf_pf_scores, no (M, M) array anywhere.  nb = ceil(M / 512) workgroups to a row, one or two
+ * i-particles of a thread in registers, j-tiles of 1024 particles through LDS as structure-of-arrays, four j per broadcast
+ * 16-byte read.  Every workgroup takes the row maximum and sum w over the whole row itself, in one fixed order.  Per
+ * i-particle up to 3 d + 1 pair sums with w unnormalised (d absolute, d sign, one norm, d norm-gradient; one reciprocal
+ * square root per pair, a pair at distance 0 selected away), fp32 over runs of 64 pairs and flushed to double; the division
+ * by sum w is taken once, in double.  The kernel is compiled per null upstream gradient: a CRPS-only loss forms no norm, an
+ * energy-only loss no sign sums.  g_states is written by the pair kernel; with nb == 1 so is g_logw, otherwise c_m, W_m and
+ * the workgroups' partial sums of W c go to the workspace and a finishing kernel, a thread per particle, adds a row's nb
+ * partial sums in order.  mmf_pf_scores_backward_workspace_bytes(R, M, d): 8 R (nb + 2 M) bytes for M > 512, 0 up to 512
+ * (and for R, M or d below 1); it is needed for M > 512 whichever output is asked for.
+ * Limits, all decided on the host before any HIP call: null args / states / truth, both upstream gradients null, both
+ * outputs null, d outside 1 .. 4, M < 1, R < 0, a scale[k < d] that is not positive and finite, a workspace that is needed
+ * and null, smaller than the query's answer or not 8-byte aligned, an output (or the workspace) overlapping an input or
+ * another output -> MMF_EINVAL; M > 16384 or a grid beyond 32 bits -> MMF_ETOOLARGE; R == 0 is a successful no-op.
+ * Two states closer than 1e-19 in every scaled coordinate count as coinciding in the energy terms. */
+typedef struct MmfPfScoresBackwardArgs {
+  int32_t R, M, d;                  /* R rows (e.g. T*N) of M particles */
+  float scale[MMF_MAX_STATE_DIM];   /* host values, as in MmfPfScoresArgs */
+  const float* states;              /* (R, M, d) */
+  const float* log_a;               /* (R, M) or null = 0 */
+  const float* log_b;               /* (R, M) or null = 0 */
+  const float* truth;               /* (R, d) */
+  const float* g_crps;              /* (R, d) or null: no CRPS terms */
+  const float* g_energy;            /* (R) or null: no energy terms */
+  float* g_states;                  /* (R, M, d) or null */
+  float* g_logw;                    /* (R, M) or null */
+  void* workspace;                  /* device, 8-byte aligned, mmf_pf_scores_backward_workspace_bytes(R, M, d) bytes; unused when that is 0 */
+  size_t workspace_bytes;
+} MmfPfScoresBackwardArgs;          /* host struct holding device pointers */
+int mmf_pf_scores_backward(const MmfPfScoresBackwardArgs* args /* host */, void* stream);
+size_t mmf_pf_scores_backward_workspace_bytes(int R, int M, int d);
+
 /* ---------------------------------------------------------------- K7: per-trajectory MLP programs
  * The N-row networks around the filters (vector encoders layers.py:11-40,66-95; PF weight
  * model crossmodal_pf.py:74-106; virtual sensor kf.py:81-126; EKF weight model

@@ -172,6 +172,12 @@ class MmfPfScoresArgs(Structure):
                 ("workspace", _FP), ("workspace_bytes", c_size_t)]
 
 
+class MmfPfScoresBackwardArgs(Structure):
+    _fields_ = [("R", c_int32), ("M", c_int32), ("d", c_int32), ("scale", ctypes.c_float * MMF_MAX_STATE_DIM),
+                ("states", _FP), ("log_a", _FP), ("log_b", _FP), ("truth", _FP), ("g_crps", _FP), ("g_energy", _FP),
+                ("g_states", _FP), ("g_logw", _FP), ("workspace", _FP), ("workspace_bytes", c_size_t)]
+
+
 DENSITY_RULES = {"fixed": 0, "silverman": 1, "scott": 2}  # MmfPfDensityArgs.rule
 
 
@@ -349,6 +355,8 @@ SIGNATURES = {
     "mmf_pf_quantiles_lds_bytes": (c_size_t, [c_int]),
     "mmf_pf_scores": (c_int, [POINTER(MmfPfScoresArgs), c_void_p]),
     "mmf_pf_scores_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "mmf_pf_scores_backward": (c_int, [POINTER(MmfPfScoresBackwardArgs), c_void_p]),
+    "mmf_pf_scores_backward_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "mmf_pf_distance": (c_int, [POINTER(MmfPfDistanceArgs), c_void_p]),
     "mmf_pf_distance_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "mmf_pf_distance_lds_bytes": (c_size_t, [c_int, c_int]),
@@ -1378,6 +1386,37 @@ def pf_scores(states, log_a, log_b, truth, crps, energy, spread, scale=None):
     with _on(states):
         work = _summary_workspace(a, pf_scores_workspace_bytes(R, M, d), states)
         _check(load().mmf_pf_scores(ctypes.byref(a), stream_of(states)), "mmf_pf_scores")
+
+
+def pf_scores_backward_workspace_bytes(R: int, M: int, d: int) -> int:
+    return int(load().mmf_pf_scores_backward_workspace_bytes(int(R), int(M), int(d)))
+
+
+def pf_scores_backward(states, log_a, log_b, truth, g_crps, g_energy, *, g_states=None, g_logw=None, scale=None):
+    """The gradients of ``pf_scores``' CRPS and energy score (``mmf_pf_scores_backward``, include/mmf.h): ``states (..., M,
+    d)``, log-weights ``log_a + log_b``, each ``(..., M)`` or ``None`` (0), ``truth (..., d)`` and the upstream gradients
+    ``g_crps (..., d)`` and ``g_energy (...)``, either of which may be ``None`` (that score's terms are left out; not both) ->
+    ``g_states`` like ``states`` and ``g_logw (..., M)``, the gradient with respect to ``log_a`` and to ``log_b`` alike,
+    either of which may be ``None`` (not both); written in place.  ``scale``: ``pf_scores``'.  The workspace is allocated
+    here, on the tensors' device."""
+    lead, R, M, d = _summary_rows(states, log_a, log_b)
+    scale = [1.0] * d if scale is None else [float(s) for s in scale]
+    if len(scale) != d or d > MMF_MAX_STATE_DIM:
+        raise MmfError(f"mmf_pf_scores_backward takes one scale per state dimension (d = {d} <= {MMF_MAX_STATE_DIM}), got {len(scale)}")
+    assert truth is not None and tuple(truth.shape) == lead + (d,)
+    assert g_crps is None or tuple(g_crps.shape) == lead + (d,)
+    assert g_energy is None or tuple(g_energy.shape) == lead
+    assert g_states is None or tuple(g_states.shape) == lead + (M, d)
+    assert g_logw is None or tuple(g_logw.shape) == lead + (M,)
+    a = MmfPfScoresBackwardArgs()
+    a.R, a.M, a.d = R, M, d
+    for i, s in enumerate(scale):
+        a.scale[i] = s
+    a.states, a.log_a, a.log_b, a.truth = vp(states), vp(log_a), vp(log_b), vp(truth)
+    a.g_crps, a.g_energy, a.g_states, a.g_logw = vp(g_crps), vp(g_energy), vp(g_states), vp(g_logw)
+    with _on(states):
+        work = _summary_workspace(a, pf_scores_backward_workspace_bytes(R, M, d), states)
+        _check(load().mmf_pf_scores_backward(ctypes.byref(a), stream_of(states)), "mmf_pf_scores_backward")
 
 
 def pf_predictive_workspace_bytes(R: int, M: int, d: int) -> int:

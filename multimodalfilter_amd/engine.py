@@ -952,6 +952,91 @@ class ParticleSetNllFunction(torch.autograd.Function):
         return g_states, g_logw, None, g_scale
 
 
+SET_SCORES_TORCH_BLOCK = 1 << 22  # pairs (rows x i x j) of one chunk of particle_set_scores_torch
+
+
+def particle_set_scores_torch(states: torch.Tensor, log_weights: torch.Tensor, truth: torch.Tensor, scale=None, chunk: int = None):
+    """``ParticleSetScoresFunction``'s definition (include/mmf.h, "Particle-posterior scores" and "Training on the particle
+    set's scores") in torch ops, on any device: ``-> (crps (..., d), energy (...))``.  The weights are the kernels' --
+    ``w = exp(a - max a)``, kept unnormalised in every sum and divided by ``sum w`` and ``(sum w)^2`` once, at the end -- and a
+    dead particle (``w = 0``: log-weight ``-inf`` or NaN) is masked out BEFORE its state row is touched, so its gradients are 0
+    where plain autograd gives NaN; the norm's gradient at distance 0 is 0.  A row without a live particle is NaN with zero
+    gradients, as are ``crps[k]`` where ``truth[k]`` is NaN and ``energy`` where any is.  The ``M^2`` pairs are taken in chunks
+    of ``chunk`` i-particles (default: ``SET_SCORES_TORCH_BLOCK`` pairs of all rows at a time), which autograd keeps for the
+    backward: usable at a few thousand particles of a few rows, not at training sizes -- that is what the kernels are for."""
+    M, d = states.shape[-2:]
+    s = torch.ones(d, dtype=states.dtype, device=states.device) if scale is None else \
+        torch.tensor([float(v) for v in scale], dtype=states.dtype, device=states.device)
+    a = log_weights.detach()
+    top = torch.where(torch.isnan(a), torch.full_like(a, -math.inf), a).amax(-1, keepdim=True)
+    t = log_weights - top
+    live = (t <= 0) & (t > -math.inf)                      # (a NaN t -- an empty row's -inf - -inf -- is not live)
+    w = torch.where(live, torch.exp(torch.where(live, t, torch.zeros_like(t))), torch.zeros_like(t))
+    live = w > 0
+    x = torch.where(live[..., None], states, torch.zeros_like(states))
+    S = w.sum(-1)
+    row_ok = S > 0
+    S = torch.where(row_ok, S, torch.ones_like(S))
+    y_ok = ~torch.isnan(truth)
+    y = torch.where(y_ok, truth, torch.zeros_like(truth))
+
+    def norm(z):                                            # |z|_2 with gradient 0 at z = 0
+        n2 = (z * z).sum(-1)
+        pos = n2 > 0
+        return torch.where(pos, torch.sqrt(torch.where(pos, n2, torch.ones_like(n2))), torch.zeros_like(n2))
+
+    e = x - y[..., None, :]
+    t_abs = (w[..., None] * e.abs()).sum(-2)
+    t_norm = (w * norm(e / s)).sum(-1)
+    rows = max(1, states.numel() // (M * d))
+    if chunk is None:
+        chunk = max(1, min(M, SET_SCORES_TORCH_BLOCK // (rows * M)))
+    p_abs, p_norm = torch.zeros_like(t_abs), torch.zeros_like(t_norm)
+    for i0 in range(0, M, chunk):
+        e = x[..., i0:i0 + chunk, None, :] - x[..., None, :, :]          # (..., c, M, d)
+        ww = w[..., i0:i0 + chunk, None] * w[..., None, :]
+        p_abs = p_abs + (ww[..., None] * e.abs()).sum((-3, -2))
+        p_norm = p_norm + (ww * norm(e / s)).sum((-2, -1))
+    crps = t_abs / S[..., None] - 0.5 * p_abs / (S * S)[..., None]
+    energy = t_norm / S - 0.5 * p_norm / (S * S)
+    nan = math.nan
+    return (torch.where(row_ok[..., None] & y_ok, crps, torch.full_like(crps, nan)),
+            torch.where(row_ok & y_ok.all(-1), energy, torch.full_like(energy, nan)))
+
+
+class ParticleSetScoresFunction(torch.autograd.Function):
+    """CRPS per state dimension and the energy score of weighted particle sets against true states: ``(states (..., M, d),
+    log_weights (..., M), truth (..., d), scale) -> (crps (..., d), energy (...))`` with ``scale`` ``None`` or a tuple of
+    ``d`` host floats.  The forward is ``mmf_pf_scores`` as evaluation calls it (``log_a = log_weights``, no ``log_b``), the
+    backward one ``mmf_pf_scores_backward``; an output that the loss does not use arrives there as a null pointer, and its
+    terms are not computed.  The truth and the scale get no gradient."""
+
+    @staticmethod
+    def forward(ctx, states, log_weights, truth, scale):
+        require_device(states, "ParticleSetScoresFunction")
+        f32 = lambda t: t.detach().to(torch.float32).contiguous()
+        st, lw, y = f32(states), f32(log_weights), f32(truth)
+        crps = torch.empty(st.shape[:-2] + (st.shape[-1],), dtype=torch.float32, device=st.device)
+        energy = torch.empty(st.shape[:-2], dtype=torch.float32, device=st.device)
+        _abi.pf_scores(st, lw, None, y, crps, energy, None, scale)
+        ctx.save_for_backward(st, lw, y)
+        ctx.scale = scale
+        ctx.set_materialize_grads(False)
+        return crps, energy
+
+    @staticmethod
+    def backward(ctx, g_crps, g_energy):
+        st, lw, y = ctx.saved_tensors
+        need_x, need_a = ctx.needs_input_grad[:2]
+        if (g_crps is None and g_energy is None) or not (need_x or need_a):
+            return None, None, None, None
+        c = lambda g: None if g is None else g.to(torch.float32).contiguous()
+        g_states = torch.empty_like(st) if need_x else None
+        g_logw = torch.empty_like(lw) if need_a else None
+        _abi.pf_scores_backward(st, lw, None, y, c(g_crps), c(g_energy), g_states=g_states, g_logw=g_logw, scale=ctx.scale)
+        return g_states, g_logw, None, None
+
+
 class ReweightEstimateFunction(torch.autograd.Function):
     """K6 (K1, no-resample path): ``(loglik, logw_in, states) -> (estimate, logw_out)`` with
     ``logw_out = logw_in + loglik - logsumexp`` and ``estimate = sum_m exp(logw_out) x_m``;

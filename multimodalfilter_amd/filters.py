@@ -91,7 +91,8 @@ class ParticleFilter(base.Filter, ParticleSmoothing, ParticleSummaries):
     ``keep_training_sets = True`` (training mode only; evaluation ignores it, ``record_history`` is its record there): a
     ``forward_loop`` leaves ``last_training_sets = {"states" (T, N, M, d), "log_weights" (T, N, M)}``, every step's weighted set
     -- the one its estimate is taken from, before any resampling -- as differentiable tensors, so that a loss can be put on the
-    belief as a distribution (``train.particle_set_nll``, ``train.filter_loss(loss="nll")``).  From the native recursion they
+    belief as a distribution (``train.particle_set_nll``, ``train.particle_set_scores``, ``train.filter_loss(loss="nll" |
+    "energy" | train.crps_loss())``).  From the native recursion they
     are views of the buffers it keeps anyway and their gradients return through ``mmf_pf_train_backward_sets``; the
     step-by-step paths stack them.  Off (the default): every launch and every bit as before.
     ``regularisation`` (``None``: off, the default -- every launch and every bit as before; evaluation only, a training-mode

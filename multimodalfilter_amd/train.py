@@ -60,15 +60,83 @@ def particle_set_nll(states: torch.Tensor, log_weights: torch.Tensor, truth: tor
     return engine.particle_set_nll_torch(states, log_weights, truth, scale.to(states.dtype))
 
 
+def _host_scale(scale, d):
+    """``scale`` of the scores as the argument structs take it: ``None`` (ones) or a tuple of ``d`` positive finite host floats."""
+    if scale is None:
+        return None
+    scale = tuple(float(s) for s in scale)
+    if len(scale) != d or not all(0.0 < s < float("inf") for s in scale):
+        raise ValueError(f"scale: {d} positive finite floats, one per state dimension, got {scale!r}")
+    return scale
+
+
+def particle_set_scores(states: torch.Tensor, log_weights: torch.Tensor, truth: torch.Tensor, scale=None):
+    """CRPS per state dimension and the energy score of ``truth (..., d)`` under the weighted sets ``states (..., M, d)``,
+    ``log_weights (..., M)`` -> ``(crps (..., d), energy (...))``: ``E|X - y| - 1/2 E|X - X'|``, per coordinate and in the
+    Euclidean norm of the coordinates divided by ``scale`` -- the strictly proper scores ``belief_scores`` reports in
+    evaluation (``include/mmf.h``, "Particle-posterior scores"), as a training loss: no bandwidth, the state's own units, a
+    gradient bounded by each particle's weight.  ``log_weights`` need not be normalised; a particle without weight is dead,
+    its state row may hold NaN and its gradients are 0; a row without a live particle is NaN with zero gradients, as are
+    ``crps[k]`` where ``truth[k]`` is NaN and ``energy`` where any is.  ``scale``: ``None`` (ones) or ``d`` positive host
+    floats, ``belief_scores``' own keyword; it is a choice of units and gets no gradient, nor does the truth.  With the
+    ``"hip"`` training backend and device tensors the forward is ``mmf_pf_scores``, the kernel of evaluation, and the backward
+    one ``mmf_pf_scores_backward`` over all ``M^2`` pairs (``engine.ParticleSetScoresFunction``); otherwise the same
+    definition in torch ops (``engine.particle_set_scores_torch``), CPU tensors included."""
+    scale = _host_scale(scale, states.shape[-1])
+    if engine.use_hip_backward() and states.is_cuda:
+        return engine.ParticleSetScoresFunction.apply(states, log_weights, truth, scale)
+    return engine.particle_set_scores_torch(states, log_weights, truth, scale)
+
+
+def particle_set_crps(states: torch.Tensor, log_weights: torch.Tensor, truth: torch.Tensor) -> torch.Tensor:
+    """``particle_set_scores``' CRPS per state dimension ``(..., d)`` alone: the backward forms no norm."""
+    return particle_set_scores(states, log_weights, truth)[0]
+
+
+def particle_set_energy(states: torch.Tensor, log_weights: torch.Tensor, truth: torch.Tensor, scale=None) -> torch.Tensor:
+    """``particle_set_scores``' energy score ``(...)`` alone: the backward forms no per-coordinate sums."""
+    return particle_set_scores(states, log_weights, truth, scale)[1]
+
+
+def crps_loss(score_scale=None):
+    """The CRPS of the particle sets as a callable ``loss=`` of ``filter_loss`` / ``train_filter_step`` / ``GraphedFilterStep``:
+    ``(estimates, sets, batch) -> `` the mean over steps and trajectories of ``sum_k crps_k / score_scale_k`` of every step's
+    weighted set against ``batch["states"][1:]`` (``score_scale``: ``None``, ones, or ``d`` positive host floats -- the units
+    that make a sum over state dimensions meaningful, not a bandwidth; host floats, so a graph capture copies nothing).  The
+    string ``"crps"`` is not a keyword of ``filter_loss``: it names no loss there, as it never did.  On a filter that is not a
+    particle filter (``sets`` is ``None``) the callable raises a ``ValueError``."""
+    if score_scale is not None:
+        score_scale = _host_scale(score_scale, len(tuple(score_scale)))
+
+    def loss(estimates, sets, batch):
+        if sets is None:
+            raise ValueError("crps_loss is a score of a particle set: it needs a particle filter (a CRPS loss for the Kalman "
+                             "filters, evaluation.gaussian_crps in closed form, is a separate change)")
+        truth = batch["states"][1:]
+        scale = _host_scale(score_scale, truth.shape[-1])
+        crps = particle_set_crps(sets["states"], sets["log_weights"], truth)
+        if scale is None:
+            return torch.mean(crps.sum(-1))
+        return torch.mean(sum(crps[..., k] * (1.0 / v) for k, v in enumerate(scale)))
+
+    return loss
+
+
+SET_LOSSES = ("nll", "energy")   # filter_loss's keywords that are taken on the particle sets
+
+
 def filter_loss(filter_model, batch: Dict[str, torch.Tensor], *, initial_covariance: torch.Tensor,
                 noise: Optional[NoiseSource] = None, measurement_initialize: bool = False,
-                initial_scale_tril: Optional[torch.Tensor] = None, loss="mse", nll_scale=None) -> torch.Tensor:
+                initial_scale_tril: Optional[torch.Tensor] = None, loss="mse", nll_scale=None, score_scale=None) -> torch.Tensor:
     """Loss of ``forward_loop`` on ``batch`` = ``{"states" (L, N, d), "controls" (L, N, 7), "image",
     "gripper_pos", "gripper_sensors" (L, N, ...)}`` (time-major).  ``loss``: ``"mse"`` (the default, the reference's: the
     estimates against ``states[1:]``); ``"nll"`` (particle filters): the mean over steps and trajectories of
     ``particle_set_nll`` of every step's weighted set against ``states[1:]`` with the component scales ``nll_scale`` (required:
-    there is no hidden default); or a callable ``(estimates, sets, batch) -> scalar`` with ``sets`` the filter's
-    ``last_training_sets`` (``None`` for a filter that is not a particle filter), e.g. ``mse + lambda nll``.  ``"nll"`` and a
+    there is no hidden default); ``"energy"`` (particle filters): the mean over steps and trajectories of the energy score
+    under ``score_scale`` (``particle_set_energy``; ``score_scale``: ``None``, ones, or ``d`` positive host floats -- units, not
+    a bandwidth); or a callable ``(estimates, sets, batch) -> scalar`` with ``sets`` the filter's ``last_training_sets``
+    (``None`` for a filter that is not a particle filter), e.g. ``mse + lambda nll`` or ``crps_loss(score_scale)``, the CRPS of
+    the sets.  The set losses and a
     callable set ``keep_training_sets`` for the call and put it back."""
     assert filter_model.training, "call filter_model.train() first"
     assert engine.TRAINING_BACKEND is not None, "select engine.set_training_backend('hip' | 'autograd')"
@@ -81,8 +149,13 @@ def filter_loss(filter_model, batch: Dict[str, torch.Tensor], *, initial_covaria
                              "filters' Gaussian NLL on their belief covariance is a separate change)")
         if nll_scale is None:
             raise ValueError('loss="nll" needs nll_scale, the component scales of the mixture: there is no default')
+    elif isinstance(loss, str) and loss in SET_LOSSES:
+        if not is_pf:
+            raise ValueError(f'loss="{loss}" is a score of a particle set: it needs a particle filter (a CRPS loss for the Kalman '
+                             "filters, evaluation.gaussian_crps in closed form, is a separate change)")
+        score_scale = _host_scale(score_scale, batch["states"].shape[-1])
     elif loss != "mse" and not callable(loss):
-        raise ValueError(f'loss must be "mse", "nll" or a callable (estimates, sets, batch) -> scalar, got {loss!r}')
+        raise ValueError(f'loss must be "mse", "nll", "energy" or a callable (estimates, sets, batch) -> scalar, got {loss!r}')
     states = batch["states"]
     L, N, d = states.shape
     obs = {k: batch[k] for k in ("image", "gripper_pos", "gripper_sensors")}
@@ -107,16 +180,19 @@ def filter_loss(filter_model, batch: Dict[str, torch.Tensor], *, initial_covaria
             filter_model.keep_training_sets = was
     if callable(loss):
         return loss(pred, sets, batch)
-    return torch.mean(particle_set_nll(sets["states"], sets["log_weights"], states[1:], nll_scale))
+    if loss == "nll":
+        return torch.mean(particle_set_nll(sets["states"], sets["log_weights"], states[1:], nll_scale))
+    return torch.mean(particle_set_energy(sets["states"], sets["log_weights"], states[1:], score_scale))
 
 
 def train_filter_step(filter_model, batch, optimizer: torch.optim.Optimizer, *, initial_covariance: torch.Tensor,
                       noise: Optional[NoiseSource] = None, measurement_initialize: bool = False,
-                      all_reduce: bool = False, loss="mse", nll_scale=None) -> float:
-    """One optimisation step on one batch of subsequences; returns the loss (``loss``, ``nll_scale``: ``filter_loss``)."""
+                      all_reduce: bool = False, loss="mse", nll_scale=None, score_scale=None) -> float:
+    """One optimisation step on one batch of subsequences; returns the loss (``loss``, ``nll_scale``, ``score_scale``:
+    ``filter_loss``)."""
     optimizer.zero_grad(set_to_none=True)
     loss = filter_loss(filter_model, batch, initial_covariance=initial_covariance, noise=noise,
-                       measurement_initialize=measurement_initialize, loss=loss, nll_scale=nll_scale)
+                       measurement_initialize=measurement_initialize, loss=loss, nll_scale=nll_scale, score_scale=score_scale)
     loss.backward()
     if all_reduce:
         distributed.all_reduce_gradients(filter_model)
@@ -144,18 +220,19 @@ class GraphedFilterStep:
     captured even when the blobs are fresh, or when a fused optimiser, which never moves it, ran the eager steps) and after
     every replay (the next eager or eval forward re-packs the weights the replay wrote).  Requirements: a capturable
     optimiser (``torch.optim.SGD``, or Adam with ``capturable=True``), no host-dependent control flow in user models,
-    batches of one shape (a new shape raises).  ``loss``, ``nll_scale``: ``filter_loss``'s (a callable loss is captured too:
+    batches of one shape (a new shape raises).  ``loss``, ``nll_scale``, ``score_scale``: ``filter_loss``'s (a callable loss is captured too:
     it must neither read the host nor allocate outside torch's allocator)."""
 
     def __init__(self, filter_model, optimizer: torch.optim.Optimizer, *, initial_covariance: torch.Tensor,
                  noise: Optional[NoiseSource] = None, measurement_initialize: bool = False, all_reduce: bool = False,
-                 eager_steps: int = 2, loss="mse", nll_scale=None):
+                 eager_steps: int = 2, loss="mse", nll_scale=None, score_scale=None):
         assert not all_reduce, "the gradient all-reduce is not captured: use train_filter_step for data-parallel training"
         self.model, self.optimizer, self.cov = filter_model, optimizer, initial_covariance
         self.noise = noise if noise is not None else default_noise(filter_model)
         self.measurement_initialize, self.eager_left = measurement_initialize, int(eager_steps)
         self.graph, self.static, self.loss, self.tril = None, None, None, None
         self.loss_kind, self.nll_scale = loss, nll_scale   # (filter_loss's; the scales go to the device once, before any capture)
+        self.score_scale = score_scale                     # (host floats of the argument structs: nothing to copy)
         self.stream = None   # eager steps and the capture share ONE side stream: autograd remembers the stream a parameter's
                              # gradient accumulator was created on, and a capture must not reach back to the default stream
 
@@ -176,7 +253,7 @@ class GraphedFilterStep:
         with engine.capturing(), torch.cuda.graph(self.graph, stream=self.stream):
             loss = filter_loss(self.model, self.static, initial_covariance=self.cov, noise=self.noise,
                                measurement_initialize=self.measurement_initialize, initial_scale_tril=self.tril,
-                               loss=self.loss_kind, nll_scale=self.nll_scale)
+                               loss=self.loss_kind, nll_scale=self.nll_scale, score_scale=self.score_scale)
             loss.backward()
             self.optimizer.step()
             self.loss = loss.detach()
@@ -192,7 +269,7 @@ class GraphedFilterStep:
             with torch.cuda.stream(self.stream):
                 loss = train_filter_step(self.model, batch, self.optimizer, initial_covariance=self.cov, noise=self.noise,
                                          measurement_initialize=self.measurement_initialize, loss=self.loss_kind,
-                                         nll_scale=self.nll_scale)   # (reads the loss: synchronises)
+                                         nll_scale=self.nll_scale, score_scale=self.score_scale)   # (reads the loss: synchronises)
             return loss
         if self.graph is None:
             self._capture(batch)
