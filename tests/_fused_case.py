@@ -8,6 +8,43 @@ import torch
 import multimodalfilter_amd as mmf
 from multimodalfilter_amd import _abi, engine
 
+U = 64
+ROW_OUTPUTS = {"d_states": ("d", torch.float32), "dzf": (U, torch.float16), "scf": (None, torch.float32),
+               "dzj": (U, torch.float16), "scj": (None, torch.float32), "hl": (U, torch.float16),
+               "d_raw": ("d+1", torch.float32), "act": (U, torch.float32), "g_act": (U, torch.float32)}
+FIELDS = {"d_states": "d_states", "dzf": "dz_first_h", "scf": "sc_first", "dzj": "dz_join_h", "scj": "sc_join", "hl": "h_last_h"}
+
+
+def output_buffers(R, d, NL, S, dev, rows=None):
+    """The output buffers of one fused call by the short names used here: the row-indexed ones (``ROW_OUTPUTS``) from
+    ``rows(name, shape, dtype)`` (default: ``torch.empty``), the partials ``pw (NL, S, 64, 64)`` / ``pb (NL, S, 64)``
+    uninitialised."""
+    rows = rows or (lambda name, shape, dtype: torch.empty(shape, dtype=dtype, device=dev))
+    width = {"d": d, "d+1": d + 1, U: U}
+    bufs = {n: rows(n, (R,) if w is None else (R, width[w]), t) for n, (w, t) in ROW_OUTPUTS.items()}
+    bufs["pw"] = torch.empty((NL, S, U, U), dtype=torch.float32, device=dev)
+    bufs["pb"] = torch.empty((NL, S, U), dtype=torch.float32, device=dev)
+    return bufs
+
+
+def marshal(blob, n_res, k, d, N, M, S, st, tb, bufs, d_out=None, g_next=None, d_states_base=None):
+    """``MmfTrainFusedArgs`` of one call on the tensors given (which the caller keeps alive): ``k`` 0 = dynamics (``g_next``
+    and the ``d_raw`` / ``act`` / ``g_act`` buffers), 1 = measurement (``d_out (R,)``)."""
+    a = _abi.MmfTrainFusedArgs()
+    Pp = lambda t: ctypes.c_void_p(t.data_ptr())
+    a.packed_dual, a.n_res, a.kind, a.d, a.N, a.M, a.n_slots = Pp(blob), n_res, k, d, N, M, S
+    a.states, a.traj_bias = Pp(st), Pp(tb)
+    if k == 0:
+        a.g_next, a.d_raw, a.act, a.g_act = Pp(g_next), Pp(bufs["d_raw"]), Pp(bufs["act"]), Pp(bufs["g_act"])
+    else:
+        a.d_out = Pp(d_out)
+    for n, f in FIELDS.items():
+        setattr(a, f, Pp(bufs[n]))
+    if d_states_base is not None:
+        a.d_states_base = Pp(d_states_base)
+    a.pw, a.pb = Pp(bufs["pw"]), Pp(bufs["pb"])
+    return a
+
 
 def run_case(task, kind, N, M, seed=0, verbose=True, timing=False, return_rows=False):
     dev = torch.device("cuda:0")
@@ -20,7 +57,7 @@ def run_case(task, kind, N, M, seed=0, verbose=True, timing=False, return_rows=F
         model = getattr(ns, P + "MeasurementModel")(modalities={"pos", "sensors"})
     model.to(dev)
     net = model._net
-    d, R, U = net.d_in, N * M, 64
+    d, R = net.d_in, N * M
     NL = 3 + 2 * net.n_res
     g = torch.Generator().manual_seed(5 + seed)
     states = (0.7 * torch.randn((R, d), generator=g)).to(dev).requires_grad_(True)
@@ -41,25 +78,13 @@ def run_case(task, kind, N, M, seed=0, verbose=True, timing=False, return_rows=F
         want = torch.autograd.grad(out, [states, tbias] + params, d_out_ref)
 
     S = min(256, max(1, -(-R // 128)))
-    E = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
-    H = lambda *s: torch.empty(s, dtype=torch.float16, device=dev)
-    bufs = dict(d_states=E(R, d), dzf=H(R, U), scf=E(R), dzj=H(R, U), scj=E(R), hl=H(R, U),
-                pw=torch.zeros((NL, S, U, U), device=dev), pb=torch.zeros((NL, S, U), device=dev),
-                d_raw=E(R, d + 1), act=E(R, U), g_act=E(R, U))
-    a = _abi.MmfTrainFusedArgs()
-    Pp = lambda t: ctypes.c_void_p(t.data_ptr())
-    blob = net.blob(_abi.PREC_F16X3_DUAL)
-    a.packed_dual, a.n_res, a.kind, a.d, a.N, a.M, a.n_slots = Pp(blob), net.n_res, k, d, N, M, S
+    bufs = output_buffers(R, d, NL, S, dev)
+    bufs["pw"].zero_(); bufs["pb"].zero_()
     st = states.detach().contiguous()
     tb = tbias.detach().contiguous()
-    a.states, a.traj_bias = Pp(st), Pp(tb)
-    if kind == "dynamics":
-        a.g_next, a.d_raw, a.act, a.g_act = Pp(g_next), Pp(bufs["d_raw"]), Pp(bufs["act"]), Pp(bufs["g_act"])
-    else:
-        d_out = d_out_ref.reshape(R).contiguous()
-        a.d_out = Pp(d_out)
-    a.d_states, a.dz_first_h, a.sc_first, a.dz_join_h, a.sc_join, a.h_last_h = (Pp(bufs[n]) for n in ("d_states", "dzf", "scf", "dzj", "scj", "hl"))
-    a.pw, a.pb = Pp(bufs["pw"]), Pp(bufs["pb"])
+    d_out = None if kind == "dynamics" else d_out_ref.reshape(R).contiguous()
+    a = marshal(net.blob(_abi.PREC_F16X3_DUAL), net.n_res, k, d, N, M, S, st, tb, bufs, d_out=d_out,
+                g_next=g_next if kind == "dynamics" else None)
     _abi.particle_net_train_fused(a, st)
     torch.cuda.synchronize()
     if timing:

@@ -144,15 +144,24 @@ def forward_mode(sd, x, u, dtype, mask_ge=False):
     return Ref(x_next, J.transpose(1, 2).contiguous(), torch.stack(pres, dim=1))
 
 
-def margin(pre, skip_first=0):
-    """``min |pre| / max |pre of that layer in that row|`` over the ``N_SITES`` sites, per row; ``skip_first``: that many
+def margin(pre, skip_first=0, n_sites=N_SITES):
+    """``min |pre| / max |pre of that layer in that row|`` over the ``n_sites`` sites, per row; ``skip_first``: that many
     leading units of the first site are left out (the tie case's exact zeros)."""
-    assert pre.shape[1] == N_SITES
+    assert pre.shape[1] == n_sites
     rel = pre.abs() / pre.abs().amax(dim=2, keepdim=True)
     if skip_first:
         rel = rel.clone()
         rel[:, 0, :skip_first] = 1.0
     return rel.flatten(1).amin(dim=1)
+
+
+def kept_rows(pre, rows, n_sites=N_SITES):
+    """The pool rule, also of ``_fused_cases.py``: the indices of the first ``rows`` candidates, in the order drawn, whose
+    fp64 ``margin`` is at least ``MARGIN``, and the share of ALL the candidates that keep it."""
+    keep = margin(pre, n_sites=n_sites) >= MARGIN
+    idx = torch.nonzero(keep)[:rows, 0]
+    assert idx.numel() == rows, (rows, int(keep.sum()))
+    return idx, float(keep.double().mean())
 
 
 def _frozen(t):
@@ -179,10 +188,7 @@ def pool(task, seed):
     scale = torch.tensor(SCALES)[torch.arange(CANDIDATES) % len(SCALES)]
     x = torch.randn((CANDIDATES, d), generator=g) * scale[:, None]
     u = torch.randn((CANDIDATES, 7), generator=g)
-    keep = margin(forward_mode(state_dict(task, seed), x, u, torch.float64).pre) >= MARGIN
-    share = float(keep.double().mean())
-    idx = torch.nonzero(keep)[:POOL_ROWS, 0]
-    assert idx.numel() == POOL_ROWS, (task, seed, share)
+    idx, share = kept_rows(forward_mode(state_dict(task, seed), x, u, torch.float64).pre, POOL_ROWS)
     return Pool(_frozen(x[idx]), _frozen(u[idx]), share)
 
 
